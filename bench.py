@@ -2,6 +2,7 @@
 """Headline benchmark of the quasi-MCP solver path: Mreads/s selected at target coverage M=100.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg2] [--mode per-gpu|sharded]
+                  [--dump-outputs DIR]
 
 A step is one pass of the hot path (device-resident reads -> device keep bitmask, plus the
 RCCL gather of the masks when N > 1) over one batch of libs/reads-gen-style synthetic reads.
@@ -47,6 +48,34 @@ WORKLOADS = {
 def algorithmic_bytes(n_reads, total_len, n_contigs):
     """8 B/read in, 1 bit/read out, 8 B per base of coverage array"""
     return 8.0 * n_reads + n_reads / 8.0 + 8.0 * (total_len + n_contigs)
+
+
+def dump_outputs(out_dir, masks, n_reads):
+    """--dump-outputs: the keep bitmask(s) the timed path's caller received from its last step, as .npy files two
+    builds can be compared by, file for file (float32 / float64, well under 64 MB at any supported size):
+      keep_sample.npy        float32, 1.0 where the read is kept, for a fixed seeded sample of at most 2^21 reads
+                             (every read when there are fewer) -- one read drawn from each of 2^21 equal runs of indices
+      keep_sample_index.npy  float64, the (ascending) read indices of that sample
+      kept_per_block.npy     float32, kept reads in each run of 256 consecutive read indices, over the whole mask
+                             (runs twice as long, and again, while the array would pass 16 MB: past 10^9 reads)
+    masks: uint64 bitmasks, one per rank whose mask rank 0 holds, concatenated in rank order; n_reads: the reads each
+    of them covers."""
+    keep = np.concatenate([np.unpackbits(m.view(np.uint8), bitorder="little")[:n] for m, n in zip(masks, n_reads)])
+    n, n_sample = keep.size, 1 << 21
+    if n <= n_sample:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        edges = np.arange(n_sample + 1, dtype=np.int64) * n // n_sample
+        draw = np.random.default_rng(20240229).random(n_sample)
+        idx = edges[:-1] + (draw * (edges[1:] - edges[:-1])).astype(np.int64)
+    block = 256
+    while (n + block - 1) // block * 4 > 16e6:
+        block *= 2
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "keep_sample.npy"), keep[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "keep_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "kept_per_block.npy"),
+            np.add.reduceat(keep, np.arange(0, n, block), dtype=np.float32) if n else np.zeros(0, np.float32))
 
 
 def cfg5_share(pkg, torch, dev, solver, stream):
@@ -383,6 +412,8 @@ def main():
                          "separate them from the exchange in a scaling run)")
     ap.add_argument("--in-flight", type=int, default=2, choices=[1, 2, 3, 4],
                     help="solves kept in flight per GPU (one solver context each; 1 = one at a time)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the keep mask(s) the last timed step produced to DIR/*.npy (see dump_outputs)")
     # rehearsal knobs (not used by the driver): run several ranks on ONE GPU over gloo to
     # exercise the N > 1 plumbing on a single-GPU box
     ap.add_argument("--dist-backend", default="nccl", help=argparse.SUPPRESS)
@@ -391,6 +422,8 @@ def main():
     # a one-rank RCCL communicator -- the only way a one-GPU box can execute the RCCL calls of the N > 1 path
     ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: start the N ranks ourselves, as a CHILD process and before torch or
@@ -536,6 +569,16 @@ def main():
     elapsed = time.perf_counter() - t0
     ktimes_live = all_kernel_times()
     st_live = solvers[(step_no[0] - 1) % depth].last_stats  # of the last timed solve
+    if args.dump_outputs and rank == 0:
+        # the last timed step's mask buffer, before the steps below write every buffer again; with an exchange, rank 0
+        # holds every rank's mask (each padded to `words`)
+        b = (step_no[0] - 1) % n_buf
+        if use_dist and args.exchange != "none":
+            masks = d_alls[b].cpu().numpy().view(np.uint64).reshape(world, words)
+            sizes = [len(o) * 2 * pairs for o in owned] if sharded else [n_reads] * world
+        else:
+            masks, sizes = [d_masks[b].cpu().numpy().view(np.uint64)], [n_reads]
+        dump_outputs(args.dump_outputs, masks, sizes)
     # Per-kernel breakdown: the same step a few more times, untimed, with every kernel bracketed.
     breakdown_steps = min(args.steps, 5)
     for sv in solvers:

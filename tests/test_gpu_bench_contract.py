@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -44,12 +45,28 @@ def test_single_gpu_line_carries_what_the_driver_reads():
     assert abs(b["value_single_solve"] - 1.0 / b["single_solve_ms"] * 1e3) / b["value_single_solve"] < 0.02
 
 
-def test_two_ranks_over_gloo_on_one_gpu():
+def test_dump_outputs_is_the_timed_mask(tmp_path, pkg, oracle):
+    """--dump-outputs writes the keep mask of the last timed step: cfg2's million reads fit the sample whole, so every
+    read's flag is there, and it is the oracle's mask of the same seeded reads"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--steps", "3", "--warmup", "1",
+                          "--no-extras", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert _one_json_line(out.stdout)["steps"] == 3
+    s, e = pkg.reads_gen(pkg.KIND_UNIFORM, 500_000, 30_000, 150, seed=12345)
+    want = np.unpackbits(oracle.solve(s, e, 30_000, 100).view(np.uint8), bitorder="little")[:s.size]
+    keep, idx, per_block = (np.load(tmp_path / f) for f in ("keep_sample.npy", "keep_sample_index.npy", "kept_per_block.npy"))
+    assert keep.dtype == np.float32 and idx.dtype == np.float64 and per_block.dtype == np.float32
+    assert np.array_equal(idx, np.arange(s.size)) and np.array_equal(keep, want)
+    assert np.array_equal(per_block, np.add.reduceat(want.astype(np.int64), np.arange(0, s.size, 256)))
+
+
+def test_two_ranks_over_gloo_on_one_gpu(tmp_path, pkg, oracle):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(ROOT, "bench.py"),
                           "--gpus", "2", "--steps", "4", "--warmup", "2", "--workload", "cfg2", "--dist-backend", "gloo",
-                          "--single-device"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--single-device", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     b = _one_json_line(out.stdout)
     assert b["n_gpus"] == 2 and b["scaling"] == "weak" and "gather of the keep masks at rank 0" in b["config"]["workload"]
@@ -58,6 +75,12 @@ def test_two_ranks_over_gloo_on_one_gpu():
     rr = b["config"]["rccl_ranks"]
     assert rr["backend"] == "gloo" and rr["world_size"] == 2 and sorted(r["rank"] for r in rr["ranks"]) == [0, 1]
     assert b["config"]["exchange"] == "gather"
+    # --dump-outputs at rank 0: the gathered masks, rank 0's reads (seed 12345) then rank 1's (seed 12346)
+    want = []
+    for seed in (12345, 12346):
+        s, e = pkg.reads_gen(pkg.KIND_UNIFORM, 500_000, 30_000, 150, seed=seed)
+        want.append(np.unpackbits(oracle.solve(s, e, 30_000, 100).view(np.uint8), bitorder="little")[:s.size])
+    assert np.array_equal(np.load(tmp_path / "keep_sample.npy"), np.concatenate(want))
 
 
 def test_two_ranks_without_the_exchange():

@@ -7,12 +7,12 @@ another register).  Prints every offending instruction; exit code 1 if any.
 usage: tools/isa_hazards.py [-k] <kernel name substring> [...]"""
 import os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = "/tmp/isa/kernels.s"
+OUT = os.path.join(R, "build", "isa", "kernels.s")   # this checkout's own (shared with tools/isa_stats.py -k)
 
 
 def assembly(keep=False):
     if not (keep and os.path.exists(OUT)):
-        os.makedirs("/tmp/isa", exist_ok=True)
+        os.makedirs(os.path.dirname(OUT), exist_ok=True)
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{R}/include",
                         f"-I{R}/genome-downsampler_amd/csrc", "--cuda-device-only", "-S",
                         f"{R}/genome-downsampler_amd/csrc/qmcp_kernels.hip", "-o", OUT], check=True, stderr=subprocess.DEVNULL)

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Per-kernel instruction count / registers / scratch from the device assembly of qmcp_kernels.hip.
-usage: tools/isa_stats.py [name substring ...]   (writes /tmp/isa/kernels.s; -k keeps an existing one)"""
+usage: tools/isa_stats.py [name substring ...]   (writes build/isa/kernels.s; -k keeps an existing one)"""
 import os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = "/tmp/isa/kernels.s"
+out = os.path.join(R, "build", "isa", "kernels.s")
 args = [a for a in sys.argv[1:] if a != "-k"]
 if "-k" not in sys.argv or not os.path.exists(out):
-    os.makedirs("/tmp/isa", exist_ok=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{R}/include",
                     f"-I{R}/genome-downsampler_amd/csrc", "--cuda-device-only", "-S",
                     f"{R}/genome-downsampler_amd/csrc/qmcp_kernels.hip", "-o", out], check=True, stderr=subprocess.DEVNULL)
