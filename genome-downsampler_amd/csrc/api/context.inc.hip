@@ -312,15 +312,9 @@ int scan_counts(qmcp_hip_ctx* c, DevBuf& counts, DevBuf& out, uint32_t ltot) {
 // a range's ranking is one wave's serial walk (~0.65 ns per read) against ~0.03 ns per read for
 // the radix sort it replaces
 constexpr uint64_t kRankBalance = 24;
-// mean coverage / M below which the sweep runs every block in the general form (lab/sweep_lab.hip)
-constexpr double kGenDepth = 11.0;  // lab, cycles per block fast / general: 674 / 542 at 9 x M, 595 / 545 at 10.5, 500 / 543 at 12
 // ... and when the call is large enough for a per-range workgroup to have work (QMCP_HIP_RANK_MIN
 // overrides, for experiments)
 static uint32_t rank_min_reads(const qmcp_hip_ctx* c) { return c->opt.rank_min_reads ? c->opt.rank_min_reads : (1u << 17); }
-
-// shortest span the event-driven sweep is used for: its scratch is 256 bytes per block, i.e. grows as
-// the span shrinks; at 32 positions it is 8 bytes per position, what the bucket offsets themselves take
-static uint32_t ev_min_span() { return 32u; }
 
 float elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;

@@ -4,8 +4,9 @@
 // mixed-span route (nothing has touched the mask).  The head's producer may already have filtered on c->nu_ell
 // (run.nu_filter); otherwise the reads are counted first and, if the longest span is the dominant one, the head's
 // stages are queued again with the filter on.
+// (stretches two run-ins long instead of the one-span route's four: the route sweeps several times, and a sweep is
+//  as long as its longest stretch -- two 10^7-position contigs at 1.5 x M: 0.43 -> 0.24 ms a sweep; one run-in long: 0.37)
 constexpr uint32_t kNuRunInsApart = 2;
-constexpr double kNuStretchDepth = 3.1;
 int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uint32_t max_load, uint32_t* d_iters, bool& done) {
     done = false;
     SolveRun& run = c->run;
@@ -15,47 +16,15 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     local.near_uniform_giveup = QMCP_NU_GIVEUP_NOT_TRIED;
     if (c->opt.near_uniform < 0) return QMCP_OK;
     const uint32_t ell = max_span;
-    const double depth = (double)n * (double)ell / ((double)ltot * (double)(M ? M : 1));
-    const bool dbg = c->opt.near_uniform_debug == 1;
-    if (dbg) fprintf(stderr, "[near] pm %d may_rank %d ell %u ev %d depth %.2f min_span %u filter %u\n", (int)run.pm,
-                     (int)run.may_rank, ell, (int)qmcp::sweep_uniform_ev_supported(ell, M), depth, min_span, run.nu_filter);
-    double min_depth = kNuMinDepth;
-    if (c->opt.near_uniform_min_depth > 0.f) min_depth = c->opt.near_uniform_min_depth;  // (lab)
-    // (the sigma depth where it is larger: M = 400 at 1.2 x M has as few cut points as M = 50 at 1.67 x M -- and the mixed-span
-    //  walk it was left to took 233 ms for 11.9 M reads on 3.7 M positions, 200 x the one-length solve: lab/cliff_hunt.py)
-    if (!run.may_rank || spec_sigma_depth(depth, M) < min_depth || min_span == 0) return QMCP_OK;
-    // Which sweep the rounds run.  Deeper than 11 x M: one chain per contig in the event-driven form -- what the one-span
-    // route runs there too -- restarted from its checkpoints.  Shallower (round 4): the block-scan pipeline in STRETCHES,
-    // as the one-span route does -- real cut points (coverage of ALL reads <= M: every read over them is kept in every
-    // round, whatever has been selected) and speculative boundaries checked on the device (uniform_sweep.inc.hip) -- with
-    // the need moved by nadj; every round sweeps everything (hundreds of short chains side by side: a whole chain per
-    // contig was 7 ms a sweep for cfg4's 10^6 positions at 1.5 x M, and long shallow contigs did not take the route).
-    // Between 3.1 and 11 x M contigs of up to 2 M positions keep the chain: the speculative run-ins there are 1 536 - 2 304
-    // blocks, as long as such a contig, and the chain changes fewer blocks the deeper the data (lab/near_uniform_depths.py,
-    // cfg4's reads with 1 % clipped, chain / stretches ms: 6.3 x M 6.0 / 13.1; 4.7 x M 5.5 / 13.2; 3.75 x M 6.4 / 11.5;
-    // with 40 % of the reads: 5 x M 12.4 / 15.3; 3 x M 15.7 / 11.2; 2.1 x M gives up / 14.2; 1.5 x M 41.9 / 8.6).
     uint32_t longest = 0;
     for (uint32_t k = 0; k < n_contigs; ++k) longest = run.lengths[k] > longest ? run.lengths[k] : longest;
-    // (the event-driven form's own limits: scratch for short spans, M in a packed field)
-    const bool ev_ok = ell >= ev_min_span() && qmcp::sweep_uniform_ev_supported(ell, M);
-    // (many times M and yet sparse -- a small M: more than half of the blocks hold a position without a read, the chain
-    //  would run its general step on nearly every block -- is shallow in standard deviations: stretches, as in
-    //  launch_uniform_sweep.  66 M reads on one contig of 82.6 M positions at 12 x M with M = 10, 1 % clipped: 3.2 s in chains.)
-    const bool sparse = (double)n / (double)ltot < std::log((double)ell / 0.693);
-    const double depth_gate = (depth >= kGenDepth && sparse && spec_sigma_depth(depth, M) < kGenDepth) ? spec_sigma_depth(depth, M) : depth;
-    // (sparse data -- more than half of the blocks hold a position without a read -- makes the chain run its general step on
-    //  nearly every block: 551 k reads on 1 M positions at 4 x M with M = 20, 1 % clipped: 36.7 ms in chains, lab/cliff_hunt.py)
-    bool stretches = depth_gate < kGenDepth && qmcp::sweep_uniform_mw_supported(ell) && (depth_gate < kNuStretchDepth || longest > 2000000u || !ev_ok || sparse);
-    // (deep data whose M does not fit a packed field of the event-driven form -- M = 200 at reads of 250 --: the block-scan
-    //  pipeline, one chain per contig, every round a whole sweep; contigs of up to 2 M positions -- 99.7 M reads on 24
-    //  contigs at 12 x M were 112 ms on the mixed-span walk against 2.7 with one length, lab/cliff_hunt.py)
-    if (depth_gate >= kGenDepth && !ev_ok && qmcp::sweep_uniform_mw_supported(ell) && longest <= 2000000u) stretches = true;
-    if (c->opt.sweep == QMCP_SWEEP_EVENTS) stretches = false;
-    if (c->opt.sweep == QMCP_SWEEP_GENERAL) stretches = qmcp::sweep_uniform_mw_supported(ell);
-    if (!stretches) {
-        if (!ev_ok) return QMCP_OK;
-        if (depth_gate < kGenDepth && longest > 2000000u) return QMCP_OK;  // (spans the pipeline does not take: a whole chain per round)
-    }
+    // which sweep the rounds run, and whether the route is tried at all (sweep_plan.h)
+    const qmcp::NearUniformPlan plan = qmcp::plan_near_uniform(c->opt, n, ell, min_span, ltot, n_contigs, longest, M, run.may_rank);
+    const bool stretches = plan.stretches, speculate = plan.speculate;
+    const bool dbg = c->opt.near_uniform_debug == 1;
+    if (dbg) fprintf(stderr, "[near] pm %d may_rank %d ell %u ev %d depth %.2f min_span %u filter %u\n", (int)run.pm,
+                     (int)run.may_rank, ell, (int)qmcp::sweep_uniform_ev_supported(ell, M), plan.depth, min_span, run.nu_filter);
+    if (!plan.tried) return QMCP_OK;
     if (c->nu_failed_n == run.n64 && c->nu_failed_ltot == pr.ltot && c->nu_failed_ell == ell && c->nu_failed_M == M) {
         local.near_uniform_giveup = QMCP_NU_GIVEUP_REMEMBERED;
         c->nu_ell = 0;
@@ -124,23 +93,15 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         qmcp::launch_nu_setup(st, exc, cap, n_exc, d_stats + 6, boff, ltot, ell, M, (uint32_t*)c->nu_ce.p, (uint32_t*)c->spine.p,
                               nadj, state);
     }
-    // stretches: the exact table once (the cut points do not move between rounds), the speculative ones per sweep
     const uint32_t* seg = nullptr;
-    uint32_t n_seg_max = 0, windows = 0;
-    bool speculate = false;
-    const uint32_t burn_blocks = spec_first_run_in(c, spec_depth_in_sigma(depth, M)) * ((depth_gate != depth && !c->opt.speculation_run_in) ? 3u : 1u);  // (launch_uniform_sweep)
-    if (stretches) {
-        windows = sweep_cut_windows(c, ltot, ell, n_contigs, true);
-        if (windows != 0) {
-            KernelSpan sp(c, "k_find_cuts", st);
-            seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, ell, M, windows, (uint32_t*)c->segs.p,
-                                              (const uint32_t*)c->nu_ce.p);
-            n_seg_max = n_contigs + windows;
-        }
-        const double sig = spec_depth_in_sigma(depth, M);
-        speculate = spec_wanted(c, depth_gate != depth ? depth_gate : (sig > depth ? sig * (kSpecDepth / 9.0) : depth), spec_depth_in_sigma(depth_gate, M)) && windows != 0 && burn_blocks >= 2 && (uint64_t)ltot >= 8ull * burn_blocks * ell;
-        // (stretches two run-ins long instead of the one-span route's four: the route sweeps several times, and a sweep is
-        //  as long as its longest stretch -- two 10^7-position contigs at 1.5 x M: 0.43 -> 0.24 ms a sweep; one run-in long: 0.37)
+    uint32_t n_seg_max = 0;
+    const uint32_t windows = plan.windows, burn_blocks = plan.burn_blocks;
+    // stretches: the exact table once (the cut points do not move between rounds), the speculative ones per sweep
+    if (windows != 0) {
+        KernelSpan sp(c, "k_find_cuts", st);
+        seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, ell, M, windows, (uint32_t*)c->segs.p,
+                                          (const uint32_t*)c->nu_ce.p);
+        n_seg_max = n_contigs + windows;
     }
     // later rounds sweep only the exact stretches a selection of the round before touched (k_nu_select_apply marks them)
     uint32_t* marks[2] = {(uint32_t*)((char*)c->nu_sus.p + qmcp::nu_suspect_bytes(nu_suspects_for(n))), nullptr};

@@ -220,18 +220,15 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     } else {
         uint32_t ring = 64;
         while (ring <= max_span) ring <<= 1;
-        // shallow or gapped data: stretches between cut points, one wave each (depth judged with the
-        // longest span: an upper bound)
         const uint32_t* seg = nullptr;
         uint32_t n_seg_max = 0;
-        const double depth = (double)n * (double)max_span / ((double)ltot * (double)(M ? M : 1));
-        // (a mixed-span walk is one light workgroup per stretch and slow per position: five times the windows
-        //  the one-span sweeps get, whose seven-wave workgroups fill the chip at three per compute unit)
-        // (many times M and yet sparse -- a small M -- is shallow in standard deviations: launch_uniform_sweep)
-        const bool sparse_deep = depth >= kGenDepth && (double)n / (double)ltot < std::log((double)max_span / 0.693) &&
-                                 spec_sigma_depth(depth, M) < kGenDepth;
-        const double depth_gate = sparse_deep ? spec_sigma_depth(depth, M) : depth;
-        const uint32_t windows = sweep_cut_windows(c, ltot, max_span, n_contigs, depth_gate < kGenDepth, qmcp::kMaxSweepWindows);
+        // spans up to 448: the window of live buckets fits the wave's registers (8 per lane)
+        const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
+        // cut points and speculative boundaries (sweep_plan.h); a solve of this shape that speculated in vain is remembered
+        qmcp::MixedSweepPlan plan = qmcp::plan_mixed_sweep(
+            c->opt, n, max_span, ltot, n_contigs, M, in_regs,
+            c->spec_hopeless_n == n64 && c->spec_hopeless_ltot == pr.ltot && c->spec_hopeless_M == M);
+        const uint32_t windows = plan.windows;
         if (windows != 0) {
             KernelSpan sp(c, "k_find_cuts");
             seg = qmcp::launch_sweep_segments(c->stream, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
@@ -257,65 +254,23 @@ int enqueue_tail(qmcp_hip_ctx* c) {
                 qmcp::launch_reverse_min_scan(c->stream, (uint32_t*)c->next_head.p, n + 1,
                                               (uint32_t*)c->spine.p);
             }
-            // spans up to 448: the window of live buckets fits the wave's registers (8 per lane)
-            const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
-            // speculative stretch boundaries, as for one span (launch_uniform_sweep): the state is the
-            // selected reads still alive, i.e. the kept counts of the last max_span start positions, which
-            // k_spec_verify compares (selend = bucket start + kept count); the run-in is counted in
-            // windows of max_span positions
-            // (the first tier starts lower than for one span: a walk is slow per position, so short stretches
-            //  matter more, and the second tier is there)
-            uint32_t burn_blocks = c->opt.speculation_run_in ? spec_first_run_in(c, depth) : spec_first_run_in(c, depth) * 3u / 5u;
-            bool hopeless = c->spec_hopeless_n == n64 && c->spec_hopeless_ltot == pr.ltot && c->spec_hopeless_M == M;
-            if (!hopeless && spec_wanted(c, depth_gate, spec_depth_in_sigma(depth_gate, M)) && in_regs && seg != nullptr && n >= (1u << 20)) {
-                // One dominant read length (what is left for this route once the shorter reads have their own: a few
-                // LONGER ones) forgets its state as slowly as one-length data, and the walk's boundaries then disagree
-                // nearly everywhere (lab/mixed_spec_check.py: 430 against 185 ms at 7.5 x M); a broad mix of lengths
-                // forgets fast and gains (lab/mixed_spec_broad.py: 117 against 271 ms at 5 x M).  A sample of the spans
-                // tells the two apart before anything is queued.
+            if (plan.sample_span_mode) {
                 uint32_t* d_share = (uint32_t*)c->stats.p + 6;
                 qmcp::launch_span_mode_share(c->stream, d_starts, d_ends, n, d_share);
                 uint32_t share[3] = {0, 0, 0};
                 HIP_TRY(hipMemcpyAsync(share, d_share, sizeof(share), hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(hipStreamSynchronize(c->stream));
-                if (share[0] != 0 && (uint64_t)share[1] * 10u >= (uint64_t)share[0] * 9u) {
-                    // Second half of round 4: that finding was about how DEEP the data is in standard deviations, not about
-                    // the one length.  The run-in table (spec_burn_blocks) was measured at M = 50; what makes a sweep forget
-                    // is how often the coverage comes near M, i.e. z = (mean coverage - M) / sqrt(mean coverage) =
-                    // sqrt(M) (d - 1) / sqrt(d) for Poisson starts -- the lab's reads at 2.1 x M with M = 350 are as deep as
-                    // M = 50 at 6 x M, and their boundaries disagreed at the run-in of 2.1 x M.  So: the depth at which
-                    // M = 50 has the same z; below 3.1 of it the walk speculates with that depth's whole run-in (not three
-                    // fifths: a boundary that disagrees costs its exact stretch again, and on such data exact stretches are
-                    // long), deeper it does not.  One GPU's real share of configs[4] (117.7 M positions in its longest
-                    // contig, 2 x M, M = 50) with 1 % clipped reads, this route: 14.5 s as one chain per contig, 52 ms in
-                    // 1 925 stretches, no boundary disagreeing (lab/cfg5_share_mixed_spec.py) -- which is what a whole-genome
-                    // BAM with reads LONGER than the dominant length (deletions) gets, since those leave the near-uniform route.
-                    // (the call's depth is counted with the LONGEST span; nine tenths of the reads have this one)
-                    const double depth_mode = share[2] >= 1 && share[2] < 511 && share[2] < max_span
-                                                  ? depth * (double)share[2] / (double)max_span : depth;
-                    const double depth_eff = sparse_deep ? spec_sigma_depth(depth_mode, M)     // (a small M: shallower than its depth)
-                                                         : spec_depth_in_sigma(depth_mode, M);  // (uniform_sweep.inc.hip; >= its argument)
-                    const double d_run = depth_eff;
-                    hopeless = !(depth_eff < 3.1);
-                    if (hopeless && depth_eff < kSpecDepth) {
-                        // deeper than that (run-ins of 1 536 blocks and more) only where the longest contig holds a dozen
-                        // run-ins: a 10^6-position contig would become two stretches, a chromosome becomes hundreds
-                        uint32_t longest = 0;
-                        for (uint32_t k = 0; k < n_contigs; ++k) longest = lengths[k] > longest ? lengths[k] : longest;
-                        hopeless = (uint64_t)longest < 12ull * spec_first_run_in(c, d_run) * max_span;
-                    }
-                    if (!hopeless) burn_blocks = spec_first_run_in(c, sparse_deep ? depth : d_run) * ((sparse_deep && !c->opt.speculation_run_in) ? 3u : 1u);  // (launch_uniform_sweep)
-                }
+                uint32_t longest = 0;
+                for (uint32_t k = 0; k < n_contigs; ++k) longest = lengths[k] > longest ? lengths[k] : longest;
+                plan = qmcp::refine_mixed_with_span_sample(c->opt, plan, share, longest);
             }
-            if (c->opt.speculation != 0 || c->opt.speculation_run_in != 0) hopeless = false;
-            const bool speculate = !hopeless && spec_wanted(c, depth_gate, spec_depth_in_sigma(depth_gate, M)) && in_regs && seg != nullptr && burn_blocks >= 2 &&
-                                   (uint64_t)ltot >= 4ull * burn_blocks * max_span;
+            const bool speculate = plan.speculate;
             if (speculate) {
                 TRY(ensure(c, c->specsnap, qmcp::spec_snap_bytes(n_seg_max)));
                 const void* sorted = c->keys[kin].p;
-                // (a walk is one light workgroup: many short stretches beat few long ones -- two run-ins apart)
                 TRY(speculative_sweep(
-                    c, c->stream, n_contigs, ltot, windows, max_span, 64, burn_blocks, 2, seg, "k_sweep_general_reg",
+                    c, c->stream, n_contigs, ltot, windows, max_span, plan.round_to, plan.burn_blocks, plan.run_ins_apart, seg,
+                    "k_sweep_general_reg",
                     [&](const uint32_t* table, uint32_t* out_odd, const uint32_t* redo_in) {
                         return qmcp::launch_sweep_general_reg(c->stream, wide, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
                                                               sorted, (const uint32_t*)c->next_head.p, (const uint64_t*)c->poff.p,

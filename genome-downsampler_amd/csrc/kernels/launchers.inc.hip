@@ -103,15 +103,6 @@ void launch_radix_scatter(hipStream_t st, bool wide, const void* keys_in, const 
                            (uint32_t*)keys_out, vals_out);
 }
 
-// Cut-point segmentation: window count for a genome of ltot positions (0: not worth it).  Windows
-// hold at least 64 blocks, so a stretch is long enough to amortise a pipeline start.
-uint32_t sweep_segment_windows(uint32_t ltot, uint32_t ell, uint32_t n_contigs, uint32_t max_windows) {
-    if (n_contigs >= 256 || ell == 0) return 0;
-    const uint64_t w = (uint64_t)ltot / (64ull * ell);
-    const uint32_t most = (uint32_t)kSegMaxCandidates - 256;
-    const uint32_t cap = max_windows < most ? max_windows : most;
-    return (uint32_t)(w < 2 ? 0 : (w > cap ? cap : w));
-}
 size_t sweep_segment_words(uint32_t n_contigs, uint32_t n_windows) {
     // the windows' cuts, then three tables (the exact one, and two with speculative boundaries): count,
     // {start, end, contig end}, the owned-from position and the exact table's stretch per stretch
@@ -160,8 +151,6 @@ void launch_spec_verify(hipStream_t st, const uint32_t* seg, uint32_t n_cand, ui
     hipLaunchKernelGGL(k_spec_verify, dim3(n_cand), dim3(256), 0, st, seg, n_cand, ell, owned, run_in, mismatches,
                        redo_in, redo_out, own_marks);
 }
-
-bool sweep_uniform_mw_supported(uint32_t ell) { return ell >= 1 && (ell + 63) / 64 <= 4; }
 
 bool launch_sweep_uniform_mw(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
                              uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
@@ -218,13 +207,6 @@ bool launch_sweep_uniform_gen(hipStream_t st, const uint32_t* boff, const uint64
     return true;
 }
 
-// event-driven form (deep data): field widths per E in EvPack; M must leave room in a field (see the kernel)
-bool sweep_uniform_ev_supported(uint32_t ell, uint32_t M) {
-    if (!sweep_uniform_mw_supported(ell)) return false;
-    const uint32_t e = (ell + 63) / 64;
-    const uint64_t sat = (1ull << (30 / e - 1)) - 1;  // EvPack<E>::kSat
-    return (uint64_t)M + 1 <= sat;  // no kept count can reach a saturated field's value
-}
 uint32_t sweep_ev_pieces(uint32_t ltot, uint32_t ell, uint32_t n_wg) { return ltot / (4u * ell) + n_wg + 1; }
 size_t sweep_ev_pack_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) { return (size_t)sweep_ev_pieces(ltot, ell, n_wg) * 1024; }
 size_t sweep_ev_ckpt_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) {  // the chain's state at every 64th block

@@ -48,6 +48,10 @@ template <int E> struct EvPack {
     static constexpr uint32_t kPlain = 0x80000000u;         // deep block inside the contig (not the first)
     static constexpr uint32_t kAll = kGuard | kPlain;
 };
+// the host's copy of the field maximum decides which calls take this form (sweep_plan.h: sweep_uniform_ev_supported)
+static_assert(EvPack<1>::kSat == ev_pack_sat(1) && EvPack<2>::kSat == ev_pack_sat(2) && EvPack<3>::kSat == ev_pack_sat(3) &&
+                  EvPack<4>::kSat == ev_pack_sat(4),
+              "sweep_plan.h: ev_pack_sat must be EvPack<E>::kSat");
 static constexpr uint32_t kEvSlots = 64;    // LDS ring: 64 pieces of 1 KiB
 static constexpr int32_t kEvNeg = -(1 << 30);
 

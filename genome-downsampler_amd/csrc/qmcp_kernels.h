@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sweep_plan.h"  // the shape predicates and window counts the host decides with
+
 namespace qmcp {
 
 static constexpr uint32_t kMaxLdsRingSpan = 16383;   // two LDS rings of 16384 u32 = 128 KiB
@@ -37,7 +39,7 @@ void launch_radix_hist(hipStream_t st, bool wide, const void* keys_in, uint32_t 
 void launch_radix_scatter(hipStream_t st, bool wide, const void* keys_in, const uint32_t* vals_in,
                           uint32_t n, uint32_t shift, const uint32_t* offs, void* keys_out,
                           uint32_t* vals_out);
-// Cut points (coverage <= M) split a contig's sweep exactly.  sweep_segment_windows: how many
+// Cut points (coverage <= M) split a contig's sweep exactly.  sweep_segment_windows (sweep_plan.h): how many
 // windows to look for cuts in (0: not worth it); launch_sweep_segments fills `seg_words`
 // (sweep_segment_words() uint32) and returns the stretch table the sweep launchers take as `seg`
 // together with n_seg_max = n_contigs + n_windows workgroups (null: one workgroup per contig).
@@ -45,9 +47,6 @@ void launch_radix_scatter(hipStream_t st, bool wide, const void* keys_in, const 
 // table (k_prepare writes it, one plain scan over 256 * pitch entries turns it into offsets, the
 // partition reads it)
 uint32_t part_pass_pitch(uint32_t n);
-// (at most max_windows of them; the table kernels take up to 3840: kMaxSweepWindows)
-constexpr uint32_t kSweepWindowsOneSpan = 768, kMaxSweepWindows = 3840;
-uint32_t sweep_segment_windows(uint32_t ltot, uint32_t ell, uint32_t n_contigs, uint32_t max_windows = kSweepWindowsOneSpan);
 size_t sweep_segment_words(uint32_t n_contigs, uint32_t n_windows);
 // eoff: prefix counts of read ends for mixed spans (coverage = starts - ends); null for one span ell
 const uint32_t* launch_sweep_segments(hipStream_t st, const uint32_t* boff, const uint32_t* eoff,
@@ -55,8 +54,6 @@ const uint32_t* launch_sweep_segments(hipStream_t st, const uint32_t* boff, cons
                                       uint32_t M, uint32_t n_windows, uint32_t* seg_words,
                                       const uint32_t* other_cov = nullptr /* reads outside boff covering position q - 1:
                                           other_cov[q] (the near-uniform route's exceptions) */);
-// seven-wave pipelined forms (spans <= 256); false if the span needs the single-wave kernel
-bool sweep_uniform_mw_supported(uint32_t ell);
 // the same pipeline with every block in the general form (sparse data: the fast form rarely holds)
 // selend_run_in (or null): speculative tables -- a stretch's run-in is stored there, what it owns in selend;
 // redo_in (or null): a later tier -- only stretches whose exact stretch is marked there do anything
@@ -87,7 +84,6 @@ bool launch_sweep_uniform_mw(hipStream_t st, const uint32_t* boff, const uint64_
                              uint32_t n_seg_max);
 // event-driven form for deep data (kernels/sweep_uniform_events.inc.hip): pack, chain, expand.
 // pk / lastns are scratch of sweep_ev_pack_bytes / sweep_ev_last_bytes; sev has ltot + 8 words.
-bool sweep_uniform_ev_supported(uint32_t ell, uint32_t M);
 size_t sweep_ev_pack_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg);
 size_t sweep_ev_last_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg);
 bool launch_sweep_ev_pack(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,

@@ -12,9 +12,9 @@ import numpy as np
 # cost time per READ and add up over a rank's contigs; the selection sweep is one serial chain per
 # contig, all of a rank's chains side by side, so it costs the LONGEST contig's length -- unless the share's
 # sweep is cut into stretches (cut points, speculative boundaries): then it is throughput too, per position.
-# Whether it is cut is decided exactly as the solver decides it (csrc/qmcp_api.hip: launch_uniform_sweep,
-# spec_wanted, spec_burn_blocks), from the AGGREGATE depth of everything the rank owns -- not contig by
-# contig: a rank that mixes one deep contig with shallow ones sweeps whole contigs, and is priced so.
+# Whether it is cut is decided as the solver's cost model decides it (csrc/sweep_plan.h: share_sweeps_as_stretches,
+# after plan_uniform_sweep, spec_wanted, spec_burn_blocks), from the AGGREGATE depth of everything the rank owns --
+# not contig by contig: a rank that mixes one deep contig with shallow ones sweeps whole contigs, and is priced so.
 NS_PER_READ = 0.008        # prepare + partition + offsets + ranking: ~0.8 ms per 1e8 reads
 NS_PER_POSITION = 1.5      # block-scan sweep on shallow data; deep data (event sweep) is ~0.5
 NS_PER_POSITION_STRETCHES = 0.012   # the same sweep cut into stretches (2.0 ms per 187.5 M positions)
@@ -24,13 +24,13 @@ MAX_SPLIT_CONTIGS = 256    # the stretch tables take calls of fewer contigs than
 
 
 def spec_burn_blocks(depth):
-    """run-in of a speculative boundary, in blocks (csrc/qmcp_api.hip: spec_burn_blocks)"""
+    """run-in of a speculative boundary, in blocks (csrc/sweep_plan.h: spec_burn_blocks)"""
     return 320 if depth < 2.1 else 640 if depth < 2.6 else 1152 if depth < 3.1 else 2304 if depth < 4.1 else 1536
 
 
 def spec_depth_in_sigma(depth, max_coverage):
     """the depth at which M = 50 -- where the run-in table was measured -- sits as many standard deviations above M as
-    this depth does at max_coverage; never below the depth itself (csrc/api/uniform_sweep.inc.hip: spec_depth_in_sigma)"""
+    this depth does at max_coverage; never below the depth itself (csrc/sweep_plan.h: spec_depth_in_sigma)"""
     if not depth > 1.0:
         return depth
     y = (max_coverage / 50.0) ** 0.5 * (depth - 1.0) / depth ** 0.5
@@ -39,7 +39,8 @@ def spec_depth_in_sigma(depth, max_coverage):
 
 
 def share_sweeps_as_stretches(reads, positions, n_contigs, read_length, max_coverage):
-    """the solver's own predicate on a whole share (a list of contigs solved in one call)"""
+    """the solver's own predicate on a whole share (a list of contigs solved in one call; csrc/sweep_plan.h:
+    share_sweeps_as_stretches)"""
     if not read_length or not max_coverage or positions <= 0 or n_contigs >= MAX_SPLIT_CONTIGS:
         return False
     depth = float(reads) * float(read_length) / (float(positions) * float(max_coverage))
