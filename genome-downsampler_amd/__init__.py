@@ -30,11 +30,13 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_end", "qmcp_hip_demand_host", "qmcp_hip_solve_host64", "qmcp_hip_multi_create",
     "qmcp_hip_multi_destroy", "qmcp_hip_multi_solve_host", "qmcp_hip_kept_indices_host",
     "qmcp_hip_default_options", "qmcp_hip_set_options", "qmcp_hip_get_options",
+    "qmcp_hip_solve_by_contig_host", "qmcp_hip_solve_by_contig_device",
 )
 
 QMCP_OK = 0
 PATH_UNIFORM, PATH_GENERAL, PATH_NEAR_UNIFORM = 1, 2, 3
 KIND_UNIFORM, KIND_LOW_BOTH_SIDES, KIND_HOLE, KIND_ZERO_BOTH_SIDES = 0, 1, 2, 3
+NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never kept)
 
 
 # status codes of include/qmcp_hip.h
@@ -136,6 +138,10 @@ _hip.qmcp_hip_amplicon_filter_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, 
 _hip.qmcp_hip_filter_solve_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p,
                                             _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.c_int, _u64p, _u64p, C.POINTER(Stats)]
+_hip.qmcp_hip_solve_by_contig_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32,
+                                                C.c_uint32, _u64p, C.POINTER(Stats)]
+_hip.qmcp_hip_solve_by_contig_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -159,6 +165,14 @@ if _host is not None:
     _host.qmcp_host_downsample_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
                                                C.c_uint32, C.c_uint32]
     _host.qmcp_host_downsample_bam.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_per_reference.argtypes = _host.qmcp_host_downsample_bam.argtypes
+    _host.qmcp_host_downsample_bam_per_reference.restype = C.c_int64
+    _host.qmcp_host_read_bam_per_reference.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32,
+                                                       C.c_uint64, _u64p, _u32p, _u32p, _u32p, _u32p,
+                                                       C.POINTER(C.c_uint8), _u32p, C.c_uint64, _u64p,
+                                                       C.POINTER(C.c_uint64), C.c_uint64, _u32p,
+                                                       C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_read_bam_per_reference.restype = C.c_int64
     _host.qmcp_host_check_bam.argtypes = [C.c_char_p, _u64p, C.c_char_p, C.c_size_t]
     _host.qmcp_host_bamapi_probe.argtypes = [_u32p, _u32p, C.c_uint64, C.c_uint32, C.c_int, _u64p,
                                              C.c_uint64, _u32p, _u32p, _u64p]
@@ -277,6 +291,32 @@ class Solver:
                                         C.byref(st)))
         self.last_stats = st
         return mask[:mask_words(n)]
+
+    def solve_by_contig(self, starts, ends, contig_ids, contig_lengths, max_coverage):
+        """reads of several contigs in any order, one contig id each (NO_CONTIG: unplaced, never kept) -- grouped on
+        the device, solved per contig in batches within one call's limits; host keep bitmask in INPUT order out"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st = Stats()
+        _check(_hip.qmcp_hip_solve_by_contig_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                  lengths.size, int(max_coverage), _p64(mask), C.byref(st)))
+        self.last_stats = st
+        return mask[:mask_words(n)]
+
+    def solve_by_contig_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_mask,
+                               stream=0):
+        """the same on device pointers (ints); the input-order mask is written to d_mask"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        st = Stats()
+        _check(_hip.qmcp_hip_solve_by_contig_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                    C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths),
+                                                    lengths.size, int(max_coverage), C.c_void_p(d_mask),
+                                                    C.c_void_p(stream), C.byref(st)))
+        self.last_stats = st
+        return st
 
     def solve64(self, start_inds, end_inds, contig_lengths, max_coverage, contig_read_offsets=None):
         """the reference's own size_t columns in (qmcp_hip_solve_host64: narrowed inside the library),
@@ -567,9 +607,14 @@ def write_synthetic_bam(path, ref_length, names, flags, pos, mapq, clip_front, m
         raise OSError(f"cannot write {path}")
 
 
-def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0, capacity=1 << 24):
-    """BamApi(path, config).get_paired_reads_soa() of the host mirror: dict of columns + filtered-out ids"""
+def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0, capacity=1 << 24,
+             per_reference=False):
+    """BamApi(path, config).get_paired_reads_soa() of the host mirror: dict of columns + filtered-out ids.
+    per_reference=True (BamApiConfig::per_reference): also "contig_ids" (each read's refID, NO_CONTIG if unmapped) and
+    "contig_lengths" (every reference's length, header order); amplicons are refused there (ValueError)"""
     _need_host()
+    if per_reference:
+        return _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity)
     ids = np.empty(capacity, np.uint64)
     cols = {k: np.empty(capacity, np.uint32) for k in ("starts", "ends", "qualities", "seq_lengths")}
     first = np.empty(capacity, np.uint8)
@@ -586,6 +631,32 @@ def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0
     out = {k: v[:n].copy() for k, v in cols.items()}
     out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
                ref_genome_length=int(ref.value))
+    return out
+
+
+def _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity, ref_capacity=1 << 24):
+    ids = np.empty(capacity, np.uint64)
+    cols = {k: np.empty(capacity, np.uint32) for k in ("starts", "ends", "qualities", "seq_lengths", "contig_ids")}
+    first = np.empty(capacity, np.uint8)
+    filt = np.empty(capacity, np.uint64)
+    refs = np.empty(ref_capacity, np.uint32)
+    nf, nr = C.c_uint64(0), C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    n = _host.qmcp_host_read_bam_per_reference(str(path).encode(), str(bed).encode() if bed else None,
+                                               str(tsv).encode() if tsv else None, int(min_length), int(min_mapq),
+                                               capacity, _p64(ids), _p32(cols["starts"]), _p32(cols["ends"]),
+                                               _p32(cols["qualities"]), _p32(cols["seq_lengths"]),
+                                               first.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(cols["contig_ids"]),
+                                               capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
+                                               C.byref(nr), err, 512)
+    if n == -4:
+        raise ValueError(err.value.decode())
+    if n < 0:
+        raise OSError(f"read_bam({path}, per_reference=True) failed ({n})")
+    out = {k: v[:n].copy() for k, v in cols.items()}
+    lengths = refs[:nr.value].copy()
+    out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
+               ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths)
     return out
 
 
@@ -612,12 +683,14 @@ def copy_records(in_path, out_path, ids):
     return int(n)
 
 
-def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0):
-    """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow"""
+def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
+                   per_reference=False):
+    """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
+    per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference)"""
     _need_host()
-    n = _host.qmcp_host_downsample_bam(solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-                                       str(filtered_path).encode() if filtered_path else None,
-                                       int(max_coverage), int(min_length), int(min_mapq))
+    entry = _host.qmcp_host_downsample_bam_per_reference if per_reference else _host.qmcp_host_downsample_bam
+    n = entry(solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+              str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq))
     if n < 0:
         raise KeyError(solver_name)
     return int(n)

@@ -1,0 +1,208 @@
+// by_contig.inc.hip -- part of qmcp_api.hip (one translation unit).
+// qmcp_hip_solve_by_contig_host / _device: reads of several contigs in any order, one contig id per read.
+//   1. k_bc_keys checks every read against its contig and writes the sort keys (contig id; n_contigs for unplaced reads)
+//   2. the stable LSD record radix of the sort-based route groups {key, read index} by key, one pass per 8 bits of
+//      n_contigs, into the context's own record buffers (the solves below never touch them)
+//   3. k_bc_bounds turns the sorted keys into each contig's run; the bounds and the validation word come back to the host
+//   4. by_contig_plan.h packs the contigs into batches within one call's limits; per batch, its columns are gathered in
+//      grouped order, solved by the ordinary multi-contig solve, and its mask ORed back into input order
+// Grouping happens once; a batch only gathers its own reads.
+namespace {
+
+// the batches' stats as one: counts and times summed, the route of the batch with the most reads
+void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, bool largest) {
+    s.n_reads += b.n_reads;
+    s.n_kept += b.n_kept;
+    s.min_span = first ? b.min_span : std::min(s.min_span, b.min_span);
+    s.max_span = first ? b.max_span : std::max(s.max_span, b.max_span);
+    s.sweep_stretches += b.sweep_stretches;
+    s.ms_total += b.ms_total;
+    s.ms_prepare += b.ms_prepare;
+    s.ms_scan += b.ms_scan;
+    s.ms_sort += b.ms_sort;
+    s.ms_sweep += b.ms_sweep;
+    s.ms_mark += b.ms_mark;
+    s.spec_boundaries += b.spec_boundaries;
+    s.spec_mismatches += b.spec_mismatches;
+    s.spec_retry_mismatches += b.spec_retry_mismatches;
+    s.sweep_blocks_changed += b.sweep_blocks_changed;
+    s.sweep_blocks += b.sweep_blocks;
+    s.arena_grown_mid_solve += b.arena_grown_mid_solve;
+    s.near_uniform_exceptions += b.near_uniform_exceptions;
+    s.near_uniform_selected += b.near_uniform_selected;
+    if (largest) {
+        s.path = b.path;
+        s.sort_passes = b.sort_passes;
+        s.near_uniform_rounds = b.near_uniform_rounds;
+        s.near_uniform_giveup = b.near_uniform_giveup;
+    }
+}
+
+int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                              uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, uint32_t M, uint64_t* d_mask,
+                              qmcp_hip_stats* stats) {
+    if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
+    if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
+    if (n64 > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n64);
+    const uint32_t n = (uint32_t)n64;
+    const size_t words = (size_t)((n64 + 63) / 64);
+    const uint32_t n_groups = n_contigs + 1;  // the contigs, then the unplaced reads
+    const uint32_t n_tiles = qmcp::sort_tiles(n);
+    hipStream_t st = c->stream;
+    TRY(ensure(c, c->bc_len, (size_t)n_contigs * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_offs, ((size_t)n_groups + 1) * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_err, 16));
+    TRY(ensure(c, c->bc_key, (size_t)n * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_rec[0], (size_t)n * 2 * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_rec[1], (size_t)n * 2 * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_hist, (size_t)256 * n_tiles * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_spine, (size_t)qmcp::scan_spine_entries(256u * n_tiles) * sizeof(uint32_t) + 16));
+    if (words) HIP_TRY(hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(c->bc_err.p, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemcpyAsync(c->bc_len.p, lengths, (size_t)n_contigs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+
+    // 1-3: keys, grouping, bounds
+    {
+        KernelSpan sp(c, "k_bc_keys");
+        qmcp::launch_bc_keys(st, d_starts, d_ends, d_ids, n, (const uint32_t*)c->bc_len.p, n_contigs,
+                             (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
+    }
+    const uint32_t passes = std::max(1u, (bit_width(n_contigs) + 7) / 8);  // keys go up to n_contigs
+    const void* sorted = c->bc_rec[0].p;
+    if (n) {
+        const void* recs_in = nullptr;
+        int kin = 0;
+        for (uint32_t p = 0; p < passes; ++p) {
+            const bool first = p == 0;
+            const int kout = first ? 0 : (kin ^ 1);
+            {
+                KernelSpan sp(c, "k_radix_hist_rec(by contig)");
+                qmcp::launch_radix_hist_rec(st, first, (const uint32_t*)c->bc_key.p, recs_in, n, 8 * p,
+                                            (uint32_t*)c->bc_hist.p);
+            }
+            {
+                KernelSpan sp(c, "scan_radix_hist(by contig, 3 kernels)");
+                qmcp::launch_exclusive_scan(st, (const uint32_t*)c->bc_hist.p, 256u * n_tiles, (uint32_t*)c->bc_hist.p,
+                                            (uint32_t*)c->bc_spine.p, false);
+            }
+            {
+                KernelSpan sp(c, "k_radix_scatter_rec(by contig)");
+                qmcp::launch_radix_scatter_rec(st, first, (const uint32_t*)c->bc_key.p, recs_in, n, 8 * p,
+                                               (const uint32_t*)c->bc_hist.p, c->bc_rec[kout].p);
+            }
+            kin = kout;
+            recs_in = c->bc_rec[kin].p;
+        }
+        sorted = c->bc_rec[kin].p;
+    }
+    {
+        KernelSpan sp(c, "k_bc_bounds");
+        qmcp::launch_bc_bounds(st, sorted, n, n_groups, (uint32_t*)c->bc_offs.p);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> offs((size_t)n_groups + 1);
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(offs.data(), c->bc_offs.p, offs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, c->bc_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
+    if (err & 2u) return fail(QMCP_EREAD, "a read has start > end or end >= its contig's length");
+
+    // 4: batches
+    std::vector<uint64_t> counts(n_contigs);
+    for (uint32_t k = 0; k < n_contigs; ++k) counts[k] = offs[k + 1] - offs[k];
+    std::vector<qmcp::ContigBatch> batches;
+    uint32_t bad = 0;
+    if (qmcp::plan_contig_batches(counts.data(), lengths, n_contigs, batches, &bad) != QMCP_OK)
+        return fail(QMCP_ERANGE,
+                    "contig %u alone exceeds one call's limits: %llu reads (at most 2^30), %u positions (at most 2^31 - 2)",
+                    bad, (unsigned long long)counts[bad], lengths[bad]);
+    size_t largest = 0;
+    for (size_t b = 1; b < batches.size(); ++b)
+        if (batches[b].n_reads > batches[largest].n_reads) largest = b;
+    const uint64_t most = batches[largest].n_reads;
+    TRY(ensure(c, c->bc_starts, (size_t)most * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_ends, (size_t)most * sizeof(uint32_t)));
+    TRY(ensure(c, c->bc_mask, (size_t)((most + 63) / 64) * sizeof(uint64_t)));
+    qmcp_hip_stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    bool first = true;
+    std::vector<uint64_t> roff;
+    for (size_t b = 0; b < batches.size(); ++b) {
+        const qmcp::ContigBatch& bt = batches[b];
+        sum.n_contigs += bt.n_contigs;
+        sum.total_length += bt.positions;
+        if (bt.n_reads == 0) continue;  // (nothing to solve: empty contigs keep nothing)
+        const uint32_t nb = (uint32_t)bt.n_reads;
+        const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
+        {
+            KernelSpan sp(c, "k_bc_gather");
+            qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
+        }
+        HIP_TRY(hipGetLastError());
+        roff.assign((size_t)bt.n_contigs + 1, 0);
+        for (uint32_t k = 0; k <= bt.n_contigs; ++k) roff[k] = offs[bt.first_contig + k] - offs[bt.first_contig];
+        qmcp_hip_stats bs;
+        std::memset(&bs, 0, sizeof(bs));
+        TRY(solve_on_device(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, roff.data(),
+                            lengths + bt.first_contig, bt.n_contigs, nb, M, (uint64_t*)c->bc_mask.p, &bs));
+        {
+            KernelSpan sp(c, "k_bc_scatter_mask");
+            qmcp::launch_bc_scatter_mask(st, (const uint64_t*)c->bc_mask.p, bsorted, nb, d_mask);
+        }
+        HIP_TRY(hipGetLastError());
+        add_batch_stats(sum, bs, first, b == largest);
+        first = false;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    collect_spans(c);
+    if (stats) *stats = sum;
+    return QMCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmcp_hip_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* ends,
+                                  const uint32_t* contig_ids, uint64_t n_reads, const uint32_t* contig_lengths,
+                                  uint32_t n_contigs, uint32_t max_coverage, uint64_t* keep_mask_out,
+                                  qmcp_hip_stats* stats) {
+    TRY(use_device(c));
+    if (n_reads && (!starts || !ends || !contig_ids || !keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    if (n_reads > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n_reads);
+    const size_t nb = (size_t)n_reads * sizeof(uint32_t);
+    const size_t words = (size_t)((n_reads + 63) / 64);
+    TRY(ensure(c, c->in_starts, nb));
+    TRY(ensure(c, c->in_ends, nb));
+    TRY(ensure(c, c->in_aux0, nb));
+    TRY(ensure(c, c->mask, words * sizeof(uint64_t)));
+    c->mask_reads = 0;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(c->in_starts.p, starts, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(solve_by_contig_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
+                                  (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, max_coverage,
+                                  (uint64_t*)c->mask.p, stats));
+    if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mask_reads = n_reads;
+    return QMCP_OK;
+}
+
+int qmcp_hip_solve_by_contig_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends,
+                                    const uint32_t* d_contig_ids, uint64_t n_reads, const uint32_t* contig_lengths,
+                                    uint32_t n_contigs, uint32_t max_coverage, uint64_t* d_keep_mask_out,
+                                    void* hip_stream, qmcp_hip_stats* stats) {
+    TRY(use_device(c));
+    if (n_reads && (!d_starts || !d_ends || !d_contig_ids || !d_keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    TRY(order_after(c, hip_stream));
+    return solve_by_contig_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, max_coverage,
+                                     d_keep_mask_out, stats);
+}
+
+}  // extern "C"

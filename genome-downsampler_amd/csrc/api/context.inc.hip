@@ -116,6 +116,9 @@ struct qmcp_hip_ctx {
     DevBuf segs;     // cut-point windows and the sweep's stretch table
     DevBuf rings;    // mixed spans beyond 16 383: the plain event sweep's rings, in global memory
     DevBuf kidx;          // qmcp_hip_kept_indices_host: the expanded index list
+    // by-contig solves (api/by_contig.inc.hip): sort keys, the two record buffers of the grouping, its histogram and scan
+    // spine, the contigs' bounds, the validation word, the contig lengths, a batch's gathered columns and its mask
+    DevBuf bc_key, bc_rec[2], bc_hist, bc_spine, bc_offs, bc_err, bc_len, bc_starts, bc_ends, bc_mask;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

@@ -25,6 +25,7 @@
 
 #include "qmcp_hip.h"
 #include "qmcp_kernels.h"
+#include "by_contig_plan.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
@@ -37,6 +38,7 @@
 //   solve_tail          a solve's tail, collection, context creation, enqueue / complete
 //   host_entries        probes, column upload, the extern "C" entry points
 //   multi_device        several devices behind one call
+//   by_contig           reads in any order with a contig id each: grouped on the device, solved in batches, mask scattered back
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -45,3 +47,4 @@
 #include "api/solve_tail.inc.hip"
 #include "api/host_entries.inc.hip"
 #include "api/multi_device.inc.hip"
+#include "api/by_contig.inc.hip"

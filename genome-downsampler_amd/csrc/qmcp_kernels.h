@@ -250,5 +250,16 @@ size_t nu_suspect_bytes(uint32_t suspects_cap);  // `suspects`: the list and, be
 void launch_nu_mark_selected(hipStream_t st, uint32_t* exc, uint32_t cap, uint32_t n_exc, const uint32_t* n_over,
                              unsigned long long* mask, unsigned long long* kept_total);
 
+// reads in any order with a contig id each (kernels/by_contig.inc.hip; api/by_contig.inc.hip drives them): sort keys
+// (contig id, n_contigs for QMCP_NO_CONTIG) and the validation flags (err: bit 0 bad id, bit 1 bad read), the contigs'
+// bounds in grouped order from the sorted Rec{key, index} array (offs: n_groups + 1 words), a batch's columns gathered
+// in grouped order, and a batch's grouped keep mask ORed into the input-order mask
+void launch_bc_keys(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids, uint32_t n,
+                    const uint32_t* lengths, uint32_t n_contigs, uint32_t* keys, uint32_t* err);
+void launch_bc_bounds(hipStream_t st, const void* sorted, uint32_t n, uint32_t n_groups, uint32_t* offs);
+void launch_bc_gather(hipStream_t st, const void* sorted, uint32_t n, const uint32_t* starts, const uint32_t* ends,
+                      uint32_t* starts_out, uint32_t* ends_out);
+void launch_bc_scatter_mask(hipStream_t st, const uint64_t* batch_mask, const void* sorted, uint32_t n, uint64_t* mask);
+
 }  // namespace qmcp
 #endif

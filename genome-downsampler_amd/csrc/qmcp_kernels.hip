@@ -29,7 +29,8 @@
 //                            pair compaction / completion
 //   launchers                host-side launch wrappers declared in qmcp_kernels.h
 //   near_uniform             one dominant span + a few shorter reads: the one-span sweep over the regular reads, the
-//                            exceptions verified against it and selected one event at a time (included last)
+//                            exceptions verified against it and selected one event at a time
+//   by_contig                reads in any order with a contig id each: sort keys, contig bounds, gather, mask scatter-back
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -59,5 +60,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/launchers.inc.hip"
 #include "kernels/pass_major.inc.hip"
 #include "kernels/near_uniform.inc.hip"
+#include "kernels/by_contig.inc.hip"
 
 }  // namespace qmcp

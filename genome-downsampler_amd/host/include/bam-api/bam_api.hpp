@@ -27,6 +27,10 @@ struct BamApiConfig {
     std::uint32_t min_seq_length = 0;
     std::uint32_t min_mapq = 0;
     AmpliconBehaviour amplicon_behaviour = AmpliconBehaviour::IGNORE;
+    // Keep every read's reference (PairedReads::contig_ids / contig_lengths) instead of placing all reads on the first
+    // one; the solver then solves one coverage problem per reference.  Not combinable with amplicons (BED / TSV) yet:
+    // the constructor throws std::invalid_argument.
+    bool per_reference = false;
 };
 
 class BamApi {
@@ -62,6 +66,7 @@ class BamApi {
     std::vector<BAMReadId> filtered_out_reads_;
     std::filesystem::path input_filepath_;
     std::uint32_t min_seq_length_ = 0, min_mapq_ = 0;
+    bool per_reference_ = false;
     void read_bam_into(PairedReads& reads);
 };
 

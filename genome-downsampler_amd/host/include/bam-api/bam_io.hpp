@@ -25,6 +25,7 @@ struct BamFilters {
     std::uint32_t min_mapq = 0;        // on MAPQ of both mates    (bam_api.cpp:325-327)
     AmpliconBehaviour amplicon_behaviour = AmpliconBehaviour::IGNORE;
     const AmpliconSet* amplicons = nullptr;
+    bool per_reference = false;        // fill out.contig_ids / contig_lengths (BamApiConfig::per_reference)
 };
 
 struct BamIngestStats {
@@ -34,7 +35,9 @@ struct BamIngestStats {
 };
 
 // Appends accepted pairs to `out` (mate with FREAD1 first), sets out.ref_genome_length to the first
-// reference's length, lists every record id that was not imported in `filtered_out` (ascending).
+// reference's length, lists every record id that was not imported in `filtered_out` (ascending).  With
+// filters.per_reference also every reference's length (out.contig_lengths) and each appended read's refID
+// (out.contig_ids; QMCP_NO_CONTIG for refID == -1) -- pairing and filters are the same either way.
 // false + *err on a malformed or unreadable file (the reference exits the process there).
 bool read_bam(const std::filesystem::path& path, const BamFilters& filters, PairedReads& out,
               std::vector<BAMReadId>& filtered_out, BamIngestStats* stats, std::string* err);

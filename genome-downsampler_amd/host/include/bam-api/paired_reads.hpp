@@ -6,6 +6,7 @@
 #ifndef QMCP_AMD_BAM_API_PAIRED_READS_HPP
 #define QMCP_AMD_BAM_API_PAIRED_READS_HPP
 
+#include <cstdint>
 #include <vector>
 
 #include "bam-api/read.hpp"
@@ -14,6 +15,12 @@ namespace bam_api {
 
 struct PairedReads {
     Index ref_genome_length = 0;
+    // Per-reference ingest only (BamApiConfig::per_reference): every reference's length, in header order, and one
+    // contig id per read -- the record's refID, or QMCP_NO_CONTIG (0xFFFFFFFF) for an unmapped one (refID == -1).
+    // Both stay empty otherwise: the reads then lie on the first reference, as in the reference (bam_api.cpp:422).
+    std::vector<std::uint32_t> contig_lengths;
+    std::vector<std::uint32_t> contig_ids;
+    bool has_contig_ids() const { return !contig_lengths.empty(); }
 
     virtual ~PairedReads() = default;
     virtual void push_back(const Read& read) = 0;
@@ -75,6 +82,8 @@ struct SOAPairedReads : PairedReads {
 
 inline AOSPairedReads& AOSPairedReads::from(const SOAPairedReads& soa) {
     ref_genome_length = soa.ref_genome_length;
+    contig_lengths = soa.contig_lengths;
+    contig_ids = soa.contig_ids;
     reads.clear();
     reads.reserve(soa.get_reads_count());
     for (ReadIndex i = 0; i < soa.get_reads_count(); ++i) reads.push_back(soa.get_read_by_index(i));
@@ -83,6 +92,8 @@ inline AOSPairedReads& AOSPairedReads::from(const SOAPairedReads& soa) {
 inline SOAPairedReads& SOAPairedReads::from(const AOSPairedReads& aos) {
     ref_genome_length = aos.ref_genome_length;
     clear();
+    contig_lengths = aos.contig_lengths;
+    contig_ids = aos.contig_ids;
     reserve(aos.reads.size());
     for (const Read& r : aos.reads) push_back(r);
     return *this;

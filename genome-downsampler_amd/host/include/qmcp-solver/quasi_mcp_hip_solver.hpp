@@ -7,6 +7,7 @@
 #ifndef QMCP_AMD_QUASI_MCP_HIP_SOLVER_HPP
 #define QMCP_AMD_QUASI_MCP_HIP_SOLVER_HPP
 
+#include <chrono>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -43,6 +44,9 @@ class QuasiMcpHipSolver : public Solver {
     float last_solve_call_ms() const { return ms_solve_call_; }
 
    private:
+    std::unique_ptr<Solution> solve_by_contig(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
+                                              std::chrono::steady_clock::time_point t0);
+    std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves
     int device_ = 0;
     std::vector<int> devices_{0};

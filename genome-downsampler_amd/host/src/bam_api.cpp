@@ -3,6 +3,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 
 #include "bam-api/bam_io.hpp"
 
@@ -10,7 +11,11 @@ namespace bam_api {
 
 // bam_api.cpp:32-43: filters from the config; amplicons only when a BED file is given
 BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& config)
-    : input_filepath_(input_filepath), min_seq_length_(config.min_seq_length), min_mapq_(config.min_mapq) {
+    : input_filepath_(input_filepath), min_seq_length_(config.min_seq_length), min_mapq_(config.min_mapq),
+      per_reference_(config.per_reference) {
+    if (per_reference_ && (!config.bed_filepath.empty() || !config.tsv_filepath.empty()))
+        throw std::invalid_argument("per-reference downsampling does not take amplicons (BED / TSV) yet: amplicons "
+                                    "are not matched to references by name");
     if (!config.bed_filepath.empty()) {
         if (!amplicon_set_from_files(config.bed_filepath, config.tsv_filepath, amplicon_set_)) {
             std::fprintf(stderr, "[ERROR] could not open %s\n", config.bed_filepath.c_str());
@@ -26,6 +31,7 @@ void BamApi::read_bam_into(PairedReads& reads) {
     f.min_mapq = min_mapq_;
     f.amplicon_behaviour = amplicon_behaviour_;
     f.amplicons = &amplicon_set_;
+    f.per_reference = per_reference_;
     std::string err;
     if (!read_bam(input_filepath_, f, reads, filtered_out_reads_, nullptr, &err)) {
         std::fprintf(stderr, "[ERROR] %s\n", err.c_str());

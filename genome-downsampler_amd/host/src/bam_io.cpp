@@ -438,6 +438,13 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
     if (!read_header(in, h, err)) return false;
     if (h.n_ref == 0) return set_err(err, "BAM without a reference sequence");
     out.ref_genome_length = h.first_ref_length;  // bam_api.cpp:422: single contig, target_len[0]
+    const bool per_reference = filters.per_reference;
+    std::vector<std::uint32_t> ref_of_record;  // per_reference: each record's contig id, by BAMReadId
+    if (per_reference) {
+        out.contig_lengths.clear();
+        out.contig_ids.clear();
+        for (const auto& r : h.references) out.contig_lengths.push_back(r.second);
+    }
 
     BamIngestStats st;
     std::vector<bool> is_accepted, in_single_amplicon;
@@ -450,6 +457,12 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
     while (read_record(in, rec, &rec_err)) {
         Read current(id, 0, 0, 0, 0, false);
         if (!record_to_read(rec, id, current, qname)) return set_err(err, "BAM record with fields past its end");
+        if (per_reference) {
+            const std::int32_t ref_id = (std::int32_t)le32(rec.data() + 4);
+            if (ref_id < -1 || ref_id >= (std::int64_t)h.references.size())
+                return set_err(err, "BAM record with a refID outside the header's references");
+            ref_of_record.push_back(ref_id < 0 ? 0xFFFFFFFFu : (std::uint32_t)ref_id);   // QMCP_NO_CONTIG
+        }
         is_accepted.push_back(false);
         auto it = read_map.find(qname);
         if (it != read_map.end()) {
@@ -472,6 +485,10 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
             if (r2.is_first_read) std::swap(r1, r2);   // (swaps the map entry too, as the reference does)
             out.push_back(r1);
             out.push_back(r2);
+            if (per_reference) {
+                out.contig_ids.push_back(ref_of_record[r1.bam_id]);
+                out.contig_ids.push_back(ref_of_record[r2.bam_id]);
+            }
             is_accepted[r1.bam_id] = true;
             is_accepted[r2.bam_id] = true;
         } else {

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <functional>
 #include <random>
+#include <stdexcept>
 #include <string>
 
 #include "bam-api/amplicon_set.hpp"
@@ -217,6 +218,49 @@ std::int64_t qmcp_host_read_bam(const char* path, const char* bed, const char* t
     }
 }
 
+// qmcp_host_read_bam with BamApiConfig::per_reference: the same columns, plus each read's contig id (contig_ids, cap
+// entries; QMCP_NO_CONTIG for an unmapped read) and every reference's length (ref_lengths, ref_cap entries; *n_refs
+// receives the count).  -2 when a capacity is too small, -3 out of memory, -4 with amplicon files (message in err).
+std::int64_t qmcp_host_read_bam_per_reference(const char* path, const char* bed, const char* tsv,
+                                              std::uint32_t min_len, std::uint32_t min_mapq, std::uint64_t cap,
+                                              std::uint64_t* bam_ids, std::uint32_t* starts, std::uint32_t* ends,
+                                              std::uint32_t* qualities, std::uint32_t* seq_lengths,
+                                              std::uint8_t* is_first, std::uint32_t* contig_ids, std::uint64_t cap_f,
+                                              std::uint64_t* filtered_out, std::uint64_t* n_filtered_out,
+                                              std::uint64_t ref_cap, std::uint32_t* ref_lengths, std::uint64_t* n_refs,
+                                              char* err, std::size_t err_cap) {
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.per_reference = true;
+    try {
+        bam_api::BamApi api(path, cfg);
+        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
+        const std::uint64_t n = r.ids.size();
+        if (n > cap || api.get_filtered_out_reads().size() > cap_f || r.contig_lengths.size() > ref_cap) return -2;
+        for (std::uint64_t i = 0; i < n; ++i) {
+            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
+            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
+            contig_ids[i] = r.contig_ids[i];
+        }
+        *n_filtered_out = api.get_filtered_out_reads().size();
+        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
+        *n_refs = r.contig_lengths.size();
+        for (std::size_t k = 0; k < r.contig_lengths.size(); ++k) ref_lengths[k] = r.contig_lengths[k];
+        return (std::int64_t)n;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        if (err && err_cap) {
+            std::strncpy(err, e.what(), err_cap - 1);
+            err[err_cap - 1] = 0;
+        }
+        return -4;
+    }
+}
+
 // read_bam's own verdict on a file, without BamApi's exit-on-error (the reference exits the process on an
 // unreadable input; a caller that wants to look first -- and the tests of corrupt files -- use this): 0 and the
 // number of imported reads in *n_reads, or -1 and the reader's message in err (capacity cap).  Allocation
@@ -275,6 +319,29 @@ std::int64_t qmcp_host_downsample_bam(const char* solver_name, const char* in_pa
     bam_api::BamApiConfig cfg;
     cfg.min_seq_length = min_len;
     cfg.min_mapq = min_mapq;
+    try {
+        bam_api::BamApi api(in_path, cfg);
+        auto solution = manager().get(solver_name).solve(max_coverage, api);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    }
+}
+
+// qmcp_host_downsample_bam with BamApiConfig::per_reference: every reference of the file is its own coverage problem
+// (the solver takes qmcp_hip_solve_by_contig_host), pairing and writing as before -- a kept read still brings its mate,
+// on whichever reference that lies.  Returns the number of records written, -1 on an unknown solver.
+std::int64_t qmcp_host_downsample_bam_per_reference(const char* solver_name, const char* in_path, const char* out_path,
+                                                    const char* filtered_path, std::uint32_t max_coverage,
+                                                    std::uint32_t min_len, std::uint32_t min_mapq) {
+    if (!manager().contains(solver_name)) return -1;
+    bam_api::BamApiConfig cfg;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.per_reference = true;
     try {
         bam_api::BamApi api(in_path, cfg);
         auto solution = manager().get(solver_name).solve(max_coverage, api);

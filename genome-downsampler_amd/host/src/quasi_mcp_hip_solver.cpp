@@ -36,13 +36,15 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
     constexpr std::size_t kMax = std::numeric_limits<std::uint32_t>::max();
-    if (reads.ref_genome_length > kMax) die("narrowing ref_genome_length", QMCP_ERANGE);
+    if (reads.ref_genome_length > kMax && !reads.has_contig_ids()) die("narrowing ref_genome_length", QMCP_ERANGE);
     static_assert(sizeof(bam_api::Index) == sizeof(std::uint64_t), "Index is size_t on an LP64 host (read.hpp:11)");
 
     if (ctx_ == nullptr) {
         const int rc = qmcp_hip_create(device_, &ctx_);
         if (rc != QMCP_OK) die("qmcp_hip_create", rc);
     }
+
+    if (reads.has_contig_ids()) return solve_by_contig(required_cover, reads, t0);
 
     // the 64-bit columns go to the library as they are: it narrows them chunk by chunk on several
     // threads straight into pinned staging, each chunk's copy to the device issued as it is ready
@@ -61,6 +63,40 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
         rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
         if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
     }
+    return expand_kept(n, t0);
+}
+
+// Reads of several references (BamApiConfig::per_reference): one coverage problem per reference, through
+// qmcp_hip_solve_by_contig_host -- the reads stay in pairing order, the library groups them by contig on the device.
+// Unplaced reads (QMCP_NO_CONTIG) are never kept; their coordinates do not matter and go over as 0.
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_by_contig(std::uint32_t required_cover,
+                                                             const bam_api::SOAPairedReads& reads,
+                                                             std::chrono::steady_clock::time_point t0) {
+    const std::size_t n = reads.start_inds.size();
+    if (reads.contig_ids.size() != n) die("per-reference reads without one contig id each", QMCP_EINVAL);
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    int rc = qmcp_hip_solve_by_contig_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                           reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                           required_cover, mask.data(), &stats_);
+    if (rc != QMCP_OK) die("qmcp_hip_solve_by_contig_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) {
+        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
+        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
+    }
+    return expand_kept(n, t0);
+}
+
+// the context's keep mask as the ascending Solution
+std::unique_ptr<Solution> QuasiMcpHipSolver::expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0) {
+    int rc = QMCP_OK;
     const auto t1 = std::chrono::steady_clock::now();
 
     // ascending ReadIndex, as obtain_sequence produces (quasi_mcp_cpu_max_flow_solver.cpp:93-97): expanded from

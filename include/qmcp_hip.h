@@ -21,7 +21,8 @@
  *     (end_ind is inclusive in the reference: libs/bam-api/src/read.cpp:13)
  *   - reads are grouped by contig: contig c owns reads
  *     [contig_read_offsets[c], contig_read_offsets[c+1]); n_contigs == 1 reproduces the
- *     reference exactly (it is single-contig: libs/bam-api/src/bam_api.cpp:422)
+ *     reference exactly (it is single-contig: libs/bam-api/src/bam_api.cpp:422).  Reads in any
+ *     order with a contig id each take qmcp_hip_solve_by_contig_host / _device (at the end)
  *   - the result is a keep bitmask: bit (i & 63) of word (i >> 6) is set iff read i is kept;
  *     expanding it in ascending order gives the reference's `Solution` vector
  *     (quasi_mcp_cpu_max_flow_solver.cpp:89-100)
@@ -351,6 +352,34 @@ int qmcp_hip_filter_solve_host(qmcp_hip_ctx* ctx,
                                uint32_t ref_genome_length, uint32_t max_coverage, int complete_pairs,
                                uint64_t* keep_mask_out, uint64_t* pairs_filtered_out,
                                qmcp_hip_stats* stats);
+
+/* Reads of SEVERAL references in any order -- a multi-reference BAM in file (or pairing) order -- with one contig id per
+ * read: contig_ids[i] < n_contigs names read i's contig (contig c has contig_lengths[c] positions), QMCP_NO_CONTIG marks
+ * an unplaced read, which is left out of every problem and never kept.  Every other convention is the one above: read i
+ * is [starts[i], ends[i]] on its contig, and keep_mask_out (ceil(n_reads / 64) words, fully overwritten) is in INPUT order.
+ * The mask equals solving each contig, on its own reads in input order, as one call of qmcp_hip_solve_host.
+ * How: the ids are checked and the reads grouped by contig on the device once (a stable LSD radix sort of the ids, one
+ * pass per 8 bits of n_contigs); the contigs are packed, in id order, into batches within the per-call limits above
+ * (2^30 reads, 2^31 - 2 positions), which run back to back on this context; each batch's mask is scattered back to
+ * input order.  So a whole genome (GRCh38: 3.1 Gbp) is one call.  Limits: 2^31 reads, 2^24 contigs; one contig over a
+ * per-call limit fails with QMCP_ERANGE and a message naming it.  An id that is neither < n_contigs nor QMCP_NO_CONTIG
+ * fails with QMCP_EINVAL, a placed read with start > end or end >= its contig's length with QMCP_EREAD.
+ * stats (may be NULL) are summed over the batches: n_reads counts the placed reads, n_contigs and total_length every
+ * contig, the times every batch; path, min_span / max_span and the route fields are those of the batch with the most
+ * reads (min / max over all batches for the spans).  The host entry leaves the input-order mask in the context, for
+ * qmcp_hip_kept_indices_host and qmcp_hip_complete_pairs_host. */
+#define QMCP_NO_CONTIG 0xFFFFFFFFu
+int qmcp_hip_solve_by_contig_host(qmcp_hip_ctx* ctx,
+                                  const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                  uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                  uint32_t max_coverage, uint64_t* keep_mask_out, qmcp_hip_stats* stats);
+/* The same with the three columns and the mask in device memory (contig_lengths stays on the host); ordered after
+ * `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the solve has completed on the device. */
+int qmcp_hip_solve_by_contig_device(qmcp_hip_ctx* ctx,
+                                    const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                    uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                    uint32_t max_coverage, uint64_t* d_keep_mask_out, void* hip_stream,
+                                    qmcp_hip_stats* stats);
 
 #ifdef __cplusplus
 }
