@@ -30,7 +30,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_end", "qmcp_hip_demand_host", "qmcp_hip_solve_host64", "qmcp_hip_multi_create",
     "qmcp_hip_multi_destroy", "qmcp_hip_multi_solve_host", "qmcp_hip_kept_indices_host",
     "qmcp_hip_default_options", "qmcp_hip_set_options", "qmcp_hip_get_options",
-    "qmcp_hip_solve_by_contig_host", "qmcp_hip_solve_by_contig_device",
+    "qmcp_hip_solve_by_contig_host", "qmcp_hip_solve_by_contig_device", "qmcp_hip_filter_solve_by_contig_host",
 )
 
 QMCP_OK = 0
@@ -142,6 +142,9 @@ _hip.qmcp_hip_solve_by_contig_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, 
                                                 C.c_uint32, _u64p, C.POINTER(Stats)]
 _hip.qmcp_hip_solve_by_contig_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+_hip.qmcp_hip_filter_solve_by_contig_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p,
+                                                       C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.c_int, _u64p, _u64p, C.POINTER(Stats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -173,6 +176,21 @@ if _host is not None:
                                                        C.POINTER(C.c_uint64), C.c_uint64, _u32p,
                                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     _host.qmcp_host_read_bam_per_reference.restype = C.c_int64
+    _host.qmcp_host_read_bam_by_reference.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int,
+                                                      C.c_uint32, C.c_uint32, C.c_uint64, _u64p, _u32p, _u32p, _u32p,
+                                                      _u32p, C.POINTER(C.c_uint8), _u32p, C.c_uint64, _u64p,
+                                                      C.POINTER(C.c_uint64), C.c_uint64, _u32p, C.POINTER(C.c_uint64),
+                                                      C.c_char_p, C.c_size_t]
+    _host.qmcp_host_read_bam_by_reference.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_by_reference.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                            C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int,
+                                                            C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_by_reference.restype = C.c_int64
+    _host.qmcp_host_amplicons_by_reference.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint64,
+                                                       _u32p, _u32p, _u32p, C.c_uint64, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_amplicons_by_reference.restype = C.c_int64
+    _host.qmcp_host_reference_names.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, _u32p, C.c_uint64]
+    _host.qmcp_host_reference_names.restype = C.c_int64
     _host.qmcp_host_check_bam.argtypes = [C.c_char_p, _u64p, C.c_char_p, C.c_size_t]
     _host.qmcp_host_bamapi_probe.argtypes = [_u32p, _u32p, C.c_uint64, C.c_uint32, C.c_int, _u64p,
                                              C.c_uint64, _u32p, _u32p, _u64p]
@@ -448,6 +466,35 @@ class Solver:
         self.last_stats = st
         return mask[:mask_words(n)], int(dropped.value)
 
+    def filter_solve_by_contig(self, starts, ends, contig_ids, contig_lengths, max_coverage, amp_offsets=None,
+                               amp_starts=None, amp_ends=None, seq_lengths=None, qualities=None, min_length=0,
+                               min_mapq=0, complete_pairs=False):
+        """filter_solve for pairs on several contigs (qmcp_hip_filter_solve_by_contig_host): the amplicons of contig c
+        are [amp_offsets[c], amp_offsets[c + 1]) of amp_starts / amp_ends (amp_offsets None: IGNORE, only the length /
+        MAPQ filters act); a pair survives iff both mates lie on one contig, inside one of its amplicons.  Returns
+        (keep mask over the ORIGINAL read indices, number of pairs the FILTER dropped)"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs = _u32(amp_offsets) if amp_offsets is not None else None
+        if offs is not None:
+            assert offs.size == lengths.size + 1, "amp_offsets needs n_contigs + 1 entries"
+        a0 = _u32(amp_starts) if amp_starts is not None else None
+        a1 = _u32(amp_ends) if amp_ends is not None else None
+        sl = _u32(seq_lengths) if seq_lengths is not None else None
+        q = _u32(qualities) if qualities is not None else None
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        dropped = C.c_uint64(0)
+        st = Stats()
+        _check(_hip.qmcp_hip_filter_solve_by_contig_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(sl),
+                                                         _p32(q), n, _p32(lengths), lengths.size, _p32(offs),
+                                                         _p32(a0), _p32(a1), int(min_length), int(min_mapq),
+                                                         int(max_coverage), int(bool(complete_pairs)), _p64(mask),
+                                                         C.byref(dropped), C.byref(st)))
+        self.last_stats = st
+        return mask[:mask_words(n)], int(dropped.value)
+
     def amplicon_filter(self, starts, ends, amp_starts, amp_ends, seq_lengths=None, qualities=None,
                         min_length=0, min_mapq=0):
         starts, ends = _u32(starts), _u32(ends)
@@ -535,6 +582,38 @@ def amplicons_from_files(bed_path, tsv_path=None):
     return a0[:n].copy(), a1[:n].copy()
 
 
+def amplicons_by_reference(bed_path, tsv_path, reference_names):
+    """BED (+ optional TSV) matched to references by name (BamApiConfig::amplicons_by_reference) -> (offsets, starts,
+    ends): reference c owns amplicons [offsets[c], offsets[c + 1]).  ValueError naming an unknown chrom or a TSV pair
+    across references"""
+    _need_host()
+    names = [str(n) for n in reference_names]
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    cap = 1 << 20
+    offs = np.zeros(len(names) + 1, dtype=np.uint32)
+    a0 = np.empty(cap, dtype=np.uint32)
+    a1 = np.empty(cap, dtype=np.uint32)
+    err = C.create_string_buffer(1024)
+    n = _host.qmcp_host_amplicons_by_reference(str(bed_path).encode(), str(tsv_path).encode() if tsv_path else None,
+                                               arr, len(names), _p32(offs), _p32(a0), _p32(a1), cap, err, 1024)
+    if n == -4:
+        raise ValueError(err.value.decode())
+    if n < 0:
+        raise OSError(f"cannot build amplicons by reference from {bed_path} / {tsv_path} ({n})")
+    return offs, a0[:n].copy(), a1[:n].copy()
+
+
+def reference_names(path):
+    """the BAM header's reference names, in header order"""
+    _need_host()
+    buf = C.create_string_buffer(1 << 24)
+    lengths = np.empty(1 << 24, dtype=np.uint32)
+    n = _host.qmcp_host_reference_names(str(path).encode(), buf, len(buf), _p32(lengths), lengths.size)
+    if n < 0:
+        raise OSError(f"reference_names({path}) failed ({n}): {buf.value.decode(errors='replace') if n == -1 else ''}")
+    return [x for x in buf.value.decode().split("\n") if x][:n]
+
+
 def bamapi_probe(starts, ends, ref_genome_length, ids, layout=0):
     """in-memory BamApi of the host mirror: (find_input_cover, find_filtered_cover(ids), find_pairs(ids))"""
     _need_host()
@@ -608,11 +687,15 @@ def write_synthetic_bam(path, ref_length, names, flags, pos, mapq, clip_front, m
 
 
 def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0, capacity=1 << 24,
-             per_reference=False):
+             per_reference=False, amplicons_by_reference=False):
     """BamApi(path, config).get_paired_reads_soa() of the host mirror: dict of columns + filtered-out ids.
     per_reference=True (BamApiConfig::per_reference): also "contig_ids" (each read's refID, NO_CONTIG if unmapped) and
-    "contig_lengths" (every reference's length, header order); amplicons are refused there (ValueError)"""
+    "contig_lengths" (every reference's length, header order); amplicons are refused there (ValueError) unless
+    amplicons_by_reference=True (BamApiConfig::amplicons_by_reference: BED chroms matched to the references by name;
+    only with per_reference, ValueError otherwise)"""
     _need_host()
+    if amplicons_by_reference:
+        return _read_bam_by_reference(path, bed, tsv, amplicon_mode, per_reference, min_length, min_mapq, capacity)
     if per_reference:
         return _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity)
     ids = np.empty(capacity, np.uint64)
@@ -660,6 +743,34 @@ def _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity, ref_
     return out
 
 
+def _read_bam_by_reference(path, bed, tsv, amplicon_mode, per_reference, min_length, min_mapq, capacity,
+                           ref_capacity=1 << 24):
+    ids = np.empty(capacity, np.uint64)
+    cols = {k: np.empty(capacity, np.uint32) for k in ("starts", "ends", "qualities", "seq_lengths", "contig_ids")}
+    first = np.empty(capacity, np.uint8)
+    filt = np.empty(capacity, np.uint64)
+    refs = np.empty(ref_capacity, np.uint32)
+    nf, nr = C.c_uint64(0), C.c_uint64(0)
+    err = C.create_string_buffer(1024)
+    n = _host.qmcp_host_read_bam_by_reference(str(path).encode(), str(bed).encode() if bed else None,
+                                              str(tsv).encode() if tsv else None, int(amplicon_mode),
+                                              int(bool(per_reference)), 1, int(min_length), int(min_mapq), capacity,
+                                              _p64(ids), _p32(cols["starts"]), _p32(cols["ends"]),
+                                              _p32(cols["qualities"]), _p32(cols["seq_lengths"]),
+                                              first.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(cols["contig_ids"]),
+                                              capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
+                                              C.byref(nr), err, 1024)
+    if n == -4:
+        raise ValueError(err.value.decode())
+    if n < 0:
+        raise OSError(f"read_bam({path}, amplicons_by_reference=True) failed ({n})")
+    out = {k: v[:n].copy() for k, v in cols.items()}
+    lengths = refs[:nr.value].copy()
+    out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
+               ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths)
+    return out
+
+
 def check_bam(path):
     """read_bam's own verdict on a file (no exit-on-error as in BamApi): (True, reads imported, "") or
     (False, 0, the reader's message)"""
@@ -684,10 +795,28 @@ def copy_records(in_path, out_path, ids):
 
 
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
-                   per_reference=False):
+                   per_reference=False, bed=None, tsv=None, amplicon_mode=1, amplicons_by_reference=False):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
-    per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference)"""
+    per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
+    bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE) need per_reference=True and amplicons_by_reference=True:
+    the BED's chroms are matched to the file's references by name (ValueError otherwise)"""
     _need_host()
+    if (bed or tsv) and not (per_reference and amplicons_by_reference):
+        raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
+    if amplicons_by_reference:
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_by_reference(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None, int(amplicon_mode),
+            int(bool(per_reference)), 1, err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
     entry = _host.qmcp_host_downsample_bam_per_reference if per_reference else _host.qmcp_host_downsample_bam
     n = entry(solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
               str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq))

@@ -119,6 +119,9 @@ struct qmcp_hip_ctx {
     // by-contig solves (api/by_contig.inc.hip): sort keys, the two record buffers of the grouping, its histogram and scan
     // spine, the contigs' bounds, the validation word, the contig lengths, a batch's gathered columns and its mask
     DevBuf bc_key, bc_rec[2], bc_hist, bc_spine, bc_offs, bc_err, bc_len, bc_starts, bc_ends, bc_mask;
+    // FILTER -> by-contig solve (api/amplicon_by_contig.inc.hip): the input ids, the compacted ids, the contig lengths,
+    // the amplicon table (offsets, sorted starts, running maxima of the ends) and the validation word
+    DevBuf af_ids, af_ids_c, af_len, af_tab, af_err;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

@@ -26,6 +26,7 @@
 #include "qmcp_hip.h"
 #include "qmcp_kernels.h"
 #include "by_contig_plan.h"
+#include "amplicon_table.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
@@ -39,6 +40,7 @@
 //   host_entries        probes, column upload, the extern "C" entry points
 //   multi_device        several devices behind one call
 //   by_contig           reads in any order with a contig id each: grouped on the device, solved in batches, mask scattered back
+//   amplicon_by_contig  pairs of several contigs: FILTER against each contig's amplicons, compaction, the by-contig solve
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -48,3 +50,4 @@
 #include "api/host_entries.inc.hip"
 #include "api/multi_device.inc.hip"
 #include "api/by_contig.inc.hip"
+#include "api/amplicon_by_contig.inc.hip"

@@ -261,5 +261,18 @@ void launch_bc_gather(hipStream_t st, const void* sorted, uint32_t n, const uint
                       uint32_t* starts_out, uint32_t* ends_out);
 void launch_bc_scatter_mask(hipStream_t st, const uint64_t* batch_mask, const void* sorted, uint32_t n, uint64_t* mask);
 
+// pairs of several contigs against the amplicons of their own contig (kernels/amplicon_by_contig.inc.hip; api/
+// amplicon_by_contig.inc.hip drives them): the FILTER (amp_offs == NULL: no amplicon predicate; the table of
+// amplicon_table.h otherwise, n_amp entries; err as launch_bc_keys) into one bit per pair, and the compaction of the
+// surviving pairs with their contig ids.  Every column holds whole pairs and is 8-byte aligned.
+void launch_amplicon_filter_by_contig(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                                      const uint32_t* seq_lengths, const uint32_t* qualities, uint64_t n_pairs,
+                                      const uint32_t* lengths, uint32_t n_contigs, const uint32_t* amp_offs,
+                                      const uint32_t* amp_starts, const uint32_t* amp_pmax, uint32_t n_amp,
+                                      uint32_t min_length, uint32_t min_mapq, uint64_t* pair_keep, uint32_t* err);
+void launch_compact_pairs_ids(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                              const uint64_t* pair_keep, const uint32_t* word_base, uint64_t n_pairs, uint32_t* starts_c,
+                              uint32_t* ends_c, uint32_t* ids_c, uint32_t* orig_pair);
+
 }  // namespace qmcp
 #endif

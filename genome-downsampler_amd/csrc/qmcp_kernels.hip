@@ -31,6 +31,7 @@
 //   near_uniform             one dominant span + a few shorter reads: the one-span sweep over the regular reads, the
 //                            exceptions verified against it and selected one event at a time
 //   by_contig                reads in any order with a contig id each: sort keys, contig bounds, gather, mask scatter-back
+//   amplicon_by_contig       the FILTER of pairs against the amplicons of their own contig, compaction with the ids
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -61,5 +62,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/pass_major.inc.hip"
 #include "kernels/near_uniform.inc.hip"
 #include "kernels/by_contig.inc.hip"
+#include "kernels/amplicon_by_contig.inc.hip"
 
 }  // namespace qmcp

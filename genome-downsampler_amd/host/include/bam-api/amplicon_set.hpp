@@ -8,6 +8,7 @@
 #ifndef QMCP_AMD_BAM_API_AMPLICON_SET_HPP
 #define QMCP_AMD_BAM_API_AMPLICON_SET_HPP
 
+#include <cstdint>
 #include <filesystem>
 #include <map>
 #include <string>
@@ -54,6 +55,52 @@ AmpliconSet build_amplicon_set(PrimerMap primers,
                                const std::vector<std::pair<std::string, std::string>>* pairs);
 bool amplicon_set_from_files(const std::filesystem::path& bed, const std::filesystem::path& tsv,
                              AmpliconSet& out);
+
+// ---- amplicons matched to references by name (BamApiConfig::amplicons_by_reference)
+// A primer with the reference it lies on: the BED's chrom column, which read_primer_bed drops.
+struct ChromPrimer {
+    std::string chrom;
+    Index start = 0, end = 0;
+};
+using ChromPrimerMap = std::map<std::string, ChromPrimer>;
+
+// read_primer_bed keeping the chrom (the same parsing: the first line carrying a name wins, lines whose coordinates do
+// not parse or with an empty field are skipped).  chroms receives every chrom the accepted lines name, in order of
+// first appearance (later lines of a name included).  false if the file cannot be opened.
+bool read_primer_bed_by_chrom(const std::filesystem::path& path, ChromPrimerMap& out, std::vector<std::string>& chroms);
+
+// The amplicons of every reference in CSR form: reference c owns [offsets[c], offsets[c + 1]) of starts / ends
+// (inclusive bounds; the layout qmcp_hip_filter_solve_by_contig_host takes).  QMCP_NO_CONTIG (0xFFFFFFFF) is no
+// reference: an unplaced read lies in no amplicon.
+struct ReferenceAmpliconSet {
+    std::vector<std::uint32_t> offsets{0};
+    std::vector<Index> starts, ends;
+    std::size_t n_references() const { return offsets.size() - 1; }
+    // r1 on reference c1, r2 on c2: both on one reference, inside one of its amplicons
+    bool member_includes_both(std::uint32_t c1, const Read& r1, std::uint32_t c2, const Read& r2) const {
+        if (c1 != c2 || c1 >= n_references()) return false;
+        for (std::uint32_t k = offsets[c1]; k < offsets[c1 + 1]; ++k) {
+            const Amplicon a(starts[k], ends[k]);
+            if (a.includes(r1) && a.includes(r2)) return true;
+        }
+        return false;
+    }
+};
+
+// build_amplicon_set per reference.  Every chrom must be one of ref_names, exactly (no aliases).  With a TSV every pair
+// gives [left.start, right.end] after ordering the two primers by start (the reorder written back to the map, as in
+// build_amplicon_set), on the reference both primers lie on; a name missing from the BED is a (0, 0) primer on the
+// reference of the other one.  Without a TSV consecutive primers in name order WITHIN each chrom are paired (an odd
+// trailing primer of a chrom has no partner).  false + *err naming the culprit for an unknown chrom, a TSV pair across
+// two chroms, or a TSV pair neither of whose names is in the BED.
+bool build_reference_amplicon_set(ChromPrimerMap primers, const std::vector<std::string>& chroms,
+                                  const std::vector<std::pair<std::string, std::string>>* pairs,
+                                  const std::vector<std::string>& ref_names, ReferenceAmpliconSet& out,
+                                  std::string* err);
+// the files (tsv may be empty) -> the set; false + *err (also when a file cannot be opened)
+bool reference_amplicon_set_from_files(const std::filesystem::path& bed, const std::filesystem::path& tsv,
+                                       const std::vector<std::string>& ref_names, ReferenceAmpliconSet& out,
+                                       std::string* err);
 
 }  // namespace bam_api
 #endif

@@ -28,9 +28,14 @@ struct BamApiConfig {
     std::uint32_t min_mapq = 0;
     AmpliconBehaviour amplicon_behaviour = AmpliconBehaviour::IGNORE;
     // Keep every read's reference (PairedReads::contig_ids / contig_lengths) instead of placing all reads on the first
-    // one; the solver then solves one coverage problem per reference.  Not combinable with amplicons (BED / TSV) yet:
-    // the constructor throws std::invalid_argument.
+    // one; the solver then solves one coverage problem per reference.  Amplicons (BED / TSV) only with
+    // amplicons_by_reference below; without it the constructor throws std::invalid_argument.
     bool per_reference = false;
+    // Match every BED line's chrom to a reference of the BAM header by name (exactly) and build the amplicons per
+    // reference (build_reference_amplicon_set): FILTER keeps a pair only if both mates lie on one reference, inside
+    // one of its amplicons; GRADE grades by the same predicate.  Needs per_reference (std::invalid_argument
+    // otherwise); an unknown chrom or a TSV pair across references is a std::invalid_argument naming it.
+    bool amplicons_by_reference = false;
 };
 
 class BamApi {
@@ -62,11 +67,12 @@ class BamApi {
     AOSPairedReads aos_paired_reads_;
     bool is_aos_loaded_ = false;
     AmpliconSet amplicon_set_;
+    ReferenceAmpliconSet reference_amplicon_set_;
     AmpliconBehaviour amplicon_behaviour_ = AmpliconBehaviour::IGNORE;
     std::vector<BAMReadId> filtered_out_reads_;
     std::filesystem::path input_filepath_;
     std::uint32_t min_seq_length_ = 0, min_mapq_ = 0;
-    bool per_reference_ = false;
+    bool per_reference_ = false, amplicons_by_reference_ = false;
     void read_bam_into(PairedReads& reads);
 };
 

@@ -26,6 +26,9 @@ struct BamFilters {
     AmpliconBehaviour amplicon_behaviour = AmpliconBehaviour::IGNORE;
     const AmpliconSet* amplicons = nullptr;
     bool per_reference = false;        // fill out.contig_ids / contig_lengths (BamApiConfig::per_reference)
+    // BamApiConfig::amplicons_by_reference (needs per_reference): FILTER and GRADE ask this set, with each mate's
+    // reference, instead of `amplicons`
+    const ReferenceAmpliconSet* reference_amplicons = nullptr;
 };
 
 struct BamIngestStats {
@@ -41,6 +44,10 @@ struct BamIngestStats {
 // false + *err on a malformed or unreadable file (the reference exits the process there).
 bool read_bam(const std::filesystem::path& path, const BamFilters& filters, PairedReads& out,
               std::vector<BAMReadId>& filtered_out, BamIngestStats* stats, std::string* err);
+
+// The header's references alone: names and lengths in header order.  false + *err on a malformed or unreadable file.
+bool read_bam_references(const std::filesystem::path& path, std::vector<std::string>& names,
+                         std::vector<std::uint32_t>& lengths, std::string* err);
 
 // Copies the header and the records whose running id is in `bam_ids` (sorted in place, as the reference does)
 // to a new file: BAM if the output's extension is ".bam", SAM text otherwise (bam_api.cpp:564).  BGZF blocks are

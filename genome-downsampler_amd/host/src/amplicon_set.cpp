@@ -1,6 +1,8 @@
 #include "bam-api/amplicon_set.hpp"
 
+#include <algorithm>
 #include <fstream>
+#include <map>
 #include <sstream>
 #include <stdexcept>
 
@@ -80,6 +82,107 @@ bool amplicon_set_from_files(const std::filesystem::path& bed, const std::filesy
     if (!read_primer_pairs_tsv(tsv, pairs)) return false;
     out = build_amplicon_set(std::move(primers), &pairs);
     return true;
+}
+
+bool read_primer_bed_by_chrom(const std::filesystem::path& path, ChromPrimerMap& out, std::vector<std::string>& chroms) {
+    std::ifstream file(path);
+    if (!file.is_open()) return false;
+    std::string line;
+    while (std::getline(file, line)) {
+        std::istringstream fields(line);
+        std::string chrom, start, end, name;
+        std::getline(fields, chrom, '\t');
+        std::getline(fields, start, '\t');
+        std::getline(fields, end, '\t');
+        std::getline(fields, name, '\t');
+        Index s = 0, e = 0;
+        try {
+            s = std::stoull(start);
+            e = std::stoull(end);
+        } catch (const std::invalid_argument&) {
+            continue;
+        } catch (const std::out_of_range&) {
+            continue;
+        }
+        if (chrom.empty() || start.empty() || end.empty() || name.empty()) continue;
+        if (std::find(chroms.begin(), chroms.end(), chrom) == chroms.end()) chroms.push_back(chrom);
+        out.emplace(name, ChromPrimer{chrom, s, e});  // emplace: an existing name is kept
+    }
+    return true;
+}
+
+bool build_reference_amplicon_set(ChromPrimerMap primers, const std::vector<std::string>& chroms,
+                                  const std::vector<std::pair<std::string, std::string>>* pairs,
+                                  const std::vector<std::string>& ref_names, ReferenceAmpliconSet& out,
+                                  std::string* err) {
+    auto fail = [err](const std::string& msg) {
+        if (err) *err = msg;
+        return false;
+    };
+    std::map<std::string, std::uint32_t> ref_of;
+    for (std::size_t r = 0; r < ref_names.size(); ++r) ref_of.emplace(ref_names[r], (std::uint32_t)r);
+    for (const std::string& chrom : chroms)
+        if (ref_of.find(chrom) == ref_of.end())
+            return fail("BED chrom \"" + chrom + "\" names no reference of the BAM file (names must match exactly)");
+    std::vector<std::vector<Amplicon>> per(ref_names.size());
+    if (pairs != nullptr) {
+        for (const auto& names : *pairs) {
+            const auto il = primers.find(names.first), ir = primers.find(names.second);
+            if (il == primers.end() && ir == primers.end())
+                return fail("TSV pair " + names.first + " / " + names.second + " names no primer of the BED");
+            const std::string chrom = il != primers.end() ? il->second.chrom : ir->second.chrom;
+            ChromPrimer& left = primers[names.first];  // (a missing name: a (0, 0) primer on the other's chrom)
+            if (left.chrom.empty()) left.chrom = chrom;
+            ChromPrimer& right = primers[names.second];
+            if (right.chrom.empty()) right.chrom = chrom;
+            if (left.chrom != right.chrom)
+                return fail("TSV pair " + names.first + " / " + names.second + " crosses references: " + names.first +
+                            " on " + left.chrom + ", " + names.second + " on " + right.chrom);
+            if (left.start > right.start) std::swap(left, right);
+            per[ref_of[left.chrom]].emplace_back(left.start, right.end);
+        }
+    } else {
+        // name order within each chrom: the primers map is in name order already
+        std::map<std::string, std::vector<const ChromPrimer*>> by_chrom;
+        for (const auto& kv : primers) by_chrom[kv.second.chrom].push_back(&kv.second);
+        for (const auto& kv : by_chrom) {
+            const std::vector<const ChromPrimer*>& v = kv.second;
+            std::vector<Amplicon>& dst = per[ref_of[kv.first]];
+            for (std::size_t i = 0; i + 1 < v.size(); i += 2) {
+                const ChromPrimer* left = v[i];
+                const ChromPrimer* right = v[i + 1];
+                if (left->start > right->start) std::swap(left, right);
+                dst.emplace_back(left->start, right->end);
+            }
+        }
+    }
+    out = ReferenceAmpliconSet();
+    for (const auto& v : per) {
+        for (const Amplicon& a : v) {
+            out.starts.push_back(a.start);
+            out.ends.push_back(a.end);
+        }
+        out.offsets.push_back((std::uint32_t)out.starts.size());
+    }
+    return true;
+}
+
+bool reference_amplicon_set_from_files(const std::filesystem::path& bed, const std::filesystem::path& tsv,
+                                       const std::vector<std::string>& ref_names, ReferenceAmpliconSet& out,
+                                       std::string* err) {
+    ChromPrimerMap primers;
+    std::vector<std::string> chroms;
+    if (!read_primer_bed_by_chrom(bed, primers, chroms)) {
+        if (err) *err = "could not open " + bed.string();
+        return false;
+    }
+    if (tsv.empty()) return build_reference_amplicon_set(std::move(primers), chroms, nullptr, ref_names, out, err);
+    std::vector<std::pair<std::string, std::string>> pairs;
+    if (!read_primer_pairs_tsv(tsv, pairs)) {
+        if (err) *err = "could not open " + tsv.string();
+        return false;
+    }
+    return build_reference_amplicon_set(std::move(primers), chroms, &pairs, ref_names, out, err);
 }
 
 }  // namespace bam_api

@@ -12,10 +12,30 @@ namespace bam_api {
 // bam_api.cpp:32-43: filters from the config; amplicons only when a BED file is given
 BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& config)
     : input_filepath_(input_filepath), min_seq_length_(config.min_seq_length), min_mapq_(config.min_mapq),
-      per_reference_(config.per_reference) {
-    if (per_reference_ && (!config.bed_filepath.empty() || !config.tsv_filepath.empty()))
+      per_reference_(config.per_reference), amplicons_by_reference_(config.amplicons_by_reference) {
+    if (amplicons_by_reference_ && !per_reference_)
+        throw std::invalid_argument("amplicons_by_reference needs per_reference: amplicons are matched to the "
+                                    "references a per-reference ingest keeps");
+    if (per_reference_ && !amplicons_by_reference_ && (!config.bed_filepath.empty() || !config.tsv_filepath.empty()))
         throw std::invalid_argument("per-reference downsampling does not take amplicons (BED / TSV) yet: amplicons "
                                     "are not matched to references by name");
+    if (amplicons_by_reference_) {
+        if (!config.bed_filepath.empty()) {
+            // the BED's chroms are matched to the header's reference names, so the header is read first
+            std::vector<std::string> names;
+            std::vector<std::uint32_t> lengths;
+            std::string err;
+            if (!read_bam_references(input_filepath_, names, lengths, &err)) {
+                std::fprintf(stderr, "[ERROR] %s\n", err.c_str());
+                std::exit(EXIT_FAILURE);  // (as read_bam_into on an unreadable input)
+            }
+            if (!reference_amplicon_set_from_files(config.bed_filepath, config.tsv_filepath, names,
+                                                   reference_amplicon_set_, &err))
+                throw std::invalid_argument(err);
+            amplicon_behaviour_ = config.amplicon_behaviour;
+        }
+        return;
+    }
     if (!config.bed_filepath.empty()) {
         if (!amplicon_set_from_files(config.bed_filepath, config.tsv_filepath, amplicon_set_)) {
             std::fprintf(stderr, "[ERROR] could not open %s\n", config.bed_filepath.c_str());
@@ -32,6 +52,7 @@ void BamApi::read_bam_into(PairedReads& reads) {
     f.amplicon_behaviour = amplicon_behaviour_;
     f.amplicons = &amplicon_set_;
     f.per_reference = per_reference_;
+    if (amplicons_by_reference_) f.reference_amplicons = &reference_amplicon_set_;
     std::string err;
     if (!read_bam(input_filepath_, f, reads, filtered_out_reads_, nullptr, &err)) {
         std::fprintf(stderr, "[ERROR] %s\n", err.c_str());

@@ -452,8 +452,15 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
     std::vector<unsigned char> rec;
     std::string qname, rec_err;
     BAMReadId id = 0;
-    const bool filter_amplicons = filters.amplicon_behaviour == AmpliconBehaviour::FILTER && filters.amplicons != nullptr;
-    const bool grade = filters.amplicon_behaviour == AmpliconBehaviour::GRADE && filters.amplicons != nullptr;
+    const ReferenceAmpliconSet* by_ref = per_reference ? filters.reference_amplicons : nullptr;
+    const bool have_amplicons = filters.amplicons != nullptr || by_ref != nullptr;
+    const bool filter_amplicons = filters.amplicon_behaviour == AmpliconBehaviour::FILTER && have_amplicons;
+    const bool grade = filters.amplicon_behaviour == AmpliconBehaviour::GRADE && have_amplicons;
+    // the amplicon predicate of a pair: per reference (each mate's refID) or on the one set as always
+    auto includes_both = [&](const Read& r1, const Read& r2) {
+        if (by_ref) return by_ref->member_includes_both(ref_of_record[r1.bam_id], r1, ref_of_record[r2.bam_id], r2);
+        return filters.amplicons->member_includes_both(r1, r2);
+    };
     while (read_record(in, rec, &rec_err)) {
         Read current(id, 0, 0, 0, 0, false);
         if (!record_to_read(rec, id, current, qname)) return set_err(err, "BAM record with fields past its end");
@@ -471,14 +478,14 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
             Read& r2 = current;
             bool drop = !(r1.quality >= filters.min_mapq && r2.quality >= filters.min_mapq) ||
                         !(r1.seq_length >= filters.min_seq_length && r2.seq_length >= filters.min_seq_length);
-            if (filter_amplicons) drop = drop || !filters.amplicons->member_includes_both(r1, r2);
+            if (filter_amplicons) drop = drop || !includes_both(r1, r2);
             if (drop) { ++id; continue; }
             if (grade) {
                 for (const Read* r : {&r1, &r2}) {
                     st.min_imported_mapq = std::min(st.min_imported_mapq, (std::uint32_t)r->quality);
                     st.max_imported_mapq = std::max(st.max_imported_mapq, (std::uint32_t)r->quality);
                 }
-                const bool single = filters.amplicons->member_includes_both(r1, r2);
+                const bool single = includes_both(r1, r2);
                 in_single_amplicon.push_back(single);
                 in_single_amplicon.push_back(single);
             }
@@ -512,6 +519,21 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
     st.records = id;
     st.imported = out.get_reads_count();
     if (stats) *stats = st;
+    return true;
+}
+
+bool read_bam_references(const std::filesystem::path& path, std::vector<std::string>& names,
+                         std::vector<std::uint32_t>& lengths, std::string* err) {
+    BgzfReader in;
+    if (!in.open(path)) return set_err(err, "could not open " + path.string());
+    BamHeader h;
+    if (!read_header(in, h, err)) return false;
+    names.clear();
+    lengths.clear();
+    for (const auto& r : h.references) {
+        names.push_back(r.first);
+        lengths.push_back(r.second);
+    }
     return true;
 }
 

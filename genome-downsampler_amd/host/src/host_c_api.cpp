@@ -261,6 +261,107 @@ std::int64_t qmcp_host_read_bam_per_reference(const char* path, const char* bed,
     }
 }
 
+// ---- amplicons matched to references by name (BamApiConfig::amplicons_by_reference)
+namespace {
+void copy_err(const std::string& msg, char* err, std::size_t cap) {
+    if (err && cap) {
+        std::strncpy(err, msg.c_str(), cap - 1);
+        err[cap - 1] = 0;
+    }
+}
+}  // namespace
+
+// BED (+ optional TSV, may be NULL or "") against the references ref_names[0..n_refs) -> the amplicons of every
+// reference in CSR form (build_reference_amplicon_set): offsets_out (n_refs + 1 entries), starts_out / ends_out (cap
+// entries).  Returns the number of amplicons, -2 if cap is too small, -4 with the message in err (a file that cannot
+// be opened, an unknown chrom, a TSV pair across references).
+std::int64_t qmcp_host_amplicons_by_reference(const char* bed_path, const char* tsv_path, const char* const* ref_names,
+                                              std::uint64_t n_refs, std::uint32_t* offsets_out, std::uint32_t* starts_out,
+                                              std::uint32_t* ends_out, std::uint64_t cap, char* err, std::size_t err_cap) {
+    try {
+        std::vector<std::string> names;
+        for (std::uint64_t r = 0; r < n_refs; ++r) names.emplace_back(ref_names[r]);
+        bam_api::ReferenceAmpliconSet set;
+        std::string msg;
+        if (!bam_api::reference_amplicon_set_from_files(bed_path, tsv_path ? tsv_path : "", names, set, &msg)) {
+            copy_err(msg, err, err_cap);
+            return -4;
+        }
+        if (set.starts.size() > cap) return -2;
+        for (std::size_t k = 0; k < set.offsets.size(); ++k) offsets_out[k] = set.offsets[k];
+        for (std::size_t i = 0; i < set.starts.size(); ++i) {
+            starts_out[i] = static_cast<std::uint32_t>(set.starts[i]);
+            ends_out[i] = static_cast<std::uint32_t>(set.ends[i]);
+        }
+        return static_cast<std::int64_t>(set.starts.size());
+    } catch (const std::bad_alloc&) {
+        return -3;
+    }
+}
+
+// The header's reference names, '\n'-separated, into buf (capacity cap) and their lengths (lengths_cap entries).
+// Returns the number of references, -2 if a capacity is too small, -1 with the reader's message in buf.
+std::int64_t qmcp_host_reference_names(const char* path, char* buf, std::size_t cap, std::uint32_t* lengths,
+                                       std::uint64_t lengths_cap) {
+    std::vector<std::string> names;
+    std::vector<std::uint32_t> lens;
+    std::string msg;
+    if (!bam_api::read_bam_references(path, names, lens, &msg)) {
+        copy_err(msg, buf, cap);
+        return -1;
+    }
+    std::string all;
+    for (const std::string& n : names) { all += n; all += '\n'; }
+    if (all.size() + 1 > cap || lens.size() > lengths_cap) return -2;
+    std::memcpy(buf, all.c_str(), all.size() + 1);
+    for (std::size_t k = 0; k < lens.size(); ++k) lengths[k] = lens[k];
+    return static_cast<std::int64_t>(names.size());
+}
+
+// qmcp_host_read_bam_per_reference with amplicon_mode (0 IGNORE, 1 FILTER, 2 GRADE) and the two flags of BamApiConfig
+// (per_reference, amplicons_by_reference).  contig_ids is filled only with per_reference.  -2 when a capacity is too
+// small, -3 out of memory, -4 when BamApi refuses the configuration or the amplicon files (message in err).
+std::int64_t qmcp_host_read_bam_by_reference(const char* path, const char* bed, const char* tsv, int amplicon_mode,
+                                             int per_reference, int amplicons_by_reference, std::uint32_t min_len,
+                                             std::uint32_t min_mapq, std::uint64_t cap, std::uint64_t* bam_ids,
+                                             std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* qualities,
+                                             std::uint32_t* seq_lengths, std::uint8_t* is_first,
+                                             std::uint32_t* contig_ids, std::uint64_t cap_f,
+                                             std::uint64_t* filtered_out, std::uint64_t* n_filtered_out,
+                                             std::uint64_t ref_cap, std::uint32_t* ref_lengths, std::uint64_t* n_refs,
+                                             char* err, std::size_t err_cap) {
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.amplicon_behaviour = amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
+                           : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
+    cfg.per_reference = per_reference != 0;
+    cfg.amplicons_by_reference = amplicons_by_reference != 0;
+    try {
+        bam_api::BamApi api(path, cfg);
+        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
+        const std::uint64_t n = r.ids.size();
+        if (n > cap || api.get_filtered_out_reads().size() > cap_f || r.contig_lengths.size() > ref_cap) return -2;
+        for (std::uint64_t i = 0; i < n; ++i) {
+            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
+            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
+            contig_ids[i] = r.contig_ids.size() == n ? r.contig_ids[i] : 0u;
+        }
+        *n_filtered_out = api.get_filtered_out_reads().size();
+        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
+        *n_refs = r.contig_lengths.size();
+        for (std::size_t k = 0; k < r.contig_lengths.size(); ++k) ref_lengths[k] = r.contig_lengths[k];
+        return (std::int64_t)n;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // read_bam's own verdict on a file, without BamApi's exit-on-error (the reference exits the process on an
 // unreadable input; a caller that wants to look first -- and the tests of corrupt files -- use this): 0 and the
 // number of imported reads in *n_reads, or -1 and the reader's message in err (capacity cap).  Allocation
@@ -351,6 +452,40 @@ std::int64_t qmcp_host_downsample_bam_per_reference(const char* solver_name, con
         return written;
     } catch (const std::bad_alloc&) {
         return -3;
+    }
+}
+
+// qmcp_host_downsample_bam_per_reference with amplicons: BamApiConfig {bed, tsv, amplicon_mode (0 IGNORE, 1 FILTER,
+// 2 GRADE), per_reference, amplicons_by_reference}.  FILTER acts during ingest, as in the single-reference flow; the
+// survivors are solved one reference at a time and paired as before.  Returns the number of records written, -1 on an
+// unknown solver, -3 out of memory, -4 when BamApi refuses the configuration or the amplicon files (message in err).
+std::int64_t qmcp_host_downsample_bam_by_reference(const char* solver_name, const char* in_path, const char* out_path,
+                                                   const char* filtered_path, std::uint32_t max_coverage,
+                                                   std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
+                                                   const char* tsv, int amplicon_mode, int per_reference,
+                                                   int amplicons_by_reference, char* err, std::size_t err_cap) {
+    if (!manager().contains(solver_name)) return -1;
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.amplicon_behaviour = amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
+                           : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
+    cfg.per_reference = per_reference != 0;
+    cfg.amplicons_by_reference = amplicons_by_reference != 0;
+    try {
+        bam_api::BamApi api(in_path, cfg);
+        auto solution = manager().get(solver_name).solve(max_coverage, api);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
     }
 }
 

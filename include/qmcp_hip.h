@@ -381,6 +381,33 @@ int qmcp_hip_solve_by_contig_device(qmcp_hip_ctx* ctx,
                                     uint32_t max_coverage, uint64_t* d_keep_mask_out, void* hip_stream,
                                     qmcp_hip_stats* stats);
 
+/* qmcp_hip_filter_solve_host for pairs on SEVERAL references, amplicons matched to each read's own reference: the
+ * FILTER, a stable compaction of the surviving pairs, qmcp_hip_solve_by_contig_host on them, optional mate completion,
+ * and the keep mask in INPUT order (keep_mask_out: ceil(n_reads / 64) words, fully overwritten).  n_reads must be even:
+ * pair q is reads 2q, 2q + 1.  contig_ids / contig_lengths / n_contigs as in qmcp_hip_solve_by_contig_host.
+ * Amplicons: amp_offsets (n_contigs + 1 entries, starting at 0, never decreasing) gives contig c the amplicons
+ * [amp_offsets[c], amp_offsets[c + 1]) of amp_starts / amp_ends, inclusive bounds, in any order (duplicates and nested
+ * amplicons allowed).  A pair survives iff both mates are placed on the same contig c, one amplicon of c contains both
+ * mates (Amplicon::includes), and both pass min_length on seq_lengths and min_mapq on qualities (either may be NULL:
+ * that filter is off).  So pairs with mates on different contigs, with an unplaced mate, or on a contig without
+ * amplicons are dropped.  amp_offsets == NULL is AmpliconBehaviour::IGNORE: only the length / MAPQ filters act, and a
+ * pair with an unplaced or a cross-contig mate survives; an unplaced read is never selected itself, but with
+ * complete_pairs it comes back as the mate of a kept read -- as in the per-reference file flow.
+ * The result equals qmcp_hip_filter_solve_host run on each contig's surviving same-contig pairs in input order.
+ * Every read is validated, those of dropped pairs included: an id that is neither < n_contigs nor QMCP_NO_CONTIG fails
+ * with QMCP_EINVAL, a placed read with start > end or end >= its contig's length with QMCP_EREAD; bad amp_offsets and an
+ * odd n_reads with QMCP_EINVAL.  Limits: 2^31 reads, 2^24 contigs.  pairs_filtered_out (may be NULL) receives the
+ * number of dropped pairs; stats follow qmcp_hip_solve_by_contig_host (summed over its batches, n_reads = the placed
+ * surviving reads).  The final mask stays in the context for qmcp_hip_kept_indices_host. */
+int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* ctx,
+                                         const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                         const uint32_t* seq_lengths, const uint32_t* qualities, uint64_t n_reads,
+                                         const uint32_t* contig_lengths, uint32_t n_contigs,
+                                         const uint32_t* amp_offsets, const uint32_t* amp_starts,
+                                         const uint32_t* amp_ends, uint32_t min_length, uint32_t min_mapq,
+                                         uint32_t max_coverage, int complete_pairs, uint64_t* keep_mask_out,
+                                         uint64_t* pairs_filtered_out, qmcp_hip_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
