@@ -32,7 +32,7 @@ $(LIBDIR)/qmcp_api.o: $(CSRC)/qmcp_api.hip $(wildcard $(CSRC)/api/*.inc.hip) $(C
 $(LIBDIR)/libqmcp_hip.so: $(LIBDIR)/qmcp_kernels.o $(LIBDIR)/qmcp_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
 
-HOST_SRCS := $(HOST)/src/bam_api.cpp $(HOST)/src/reads_gen.cpp $(HOST)/src/quasi_mcp_hip_solver.cpp \
+HOST_SRCS := $(HOST)/src/bam_api.cpp $(HOST)/src/reads_gen.cpp $(HOST)/src/quasi_mcp_hip_solver.cpp $(HOST)/src/quasi_mcp_hip_quality_solver.cpp \
              $(HOST)/src/amplicon_set.cpp $(HOST)/src/bam_io.cpp \
              $(HOST)/src/host_c_api.cpp
 $(LIBDIR)/libqmcp_host.so: $(HOST_SRCS) $(wildcard $(HOST)/include/*.hpp $(HOST)/include/*/*.hpp) \

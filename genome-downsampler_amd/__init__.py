@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_multi_destroy", "qmcp_hip_multi_solve_host", "qmcp_hip_kept_indices_host",
     "qmcp_hip_default_options", "qmcp_hip_set_options", "qmcp_hip_get_options",
     "qmcp_hip_solve_by_contig_host", "qmcp_hip_solve_by_contig_device", "qmcp_hip_filter_solve_by_contig_host",
+    "qmcp_hip_solve_quality_host", "qmcp_hip_solve_quality_device", "qmcp_hip_solve_quality_by_contig_host",
 )
 
 QMCP_OK = 0
@@ -70,6 +71,16 @@ class Stats(C.Structure):
         ("near_uniform_selected", C.c_uint32), ("near_uniform_rounds", C.c_uint32),
         ("near_uniform_giveup", C.c_uint32),
     ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class QualityStats(C.Structure):
+    """qmcp_hip_quality_stats: what the quality pass after the plain solve did"""
+    _fields_ = [("quality_min", C.c_uint32), ("quality_max", C.c_uint32), ("key_bits", C.c_uint32),
+                ("sort_passes", C.c_uint32), ("cells_contested", C.c_uint64), ("reads_swapped", C.c_uint64),
+                ("ms_quality", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -145,6 +156,14 @@ _hip.qmcp_hip_solve_by_contig_device.argtypes = [C.c_void_p, C.c_void_p, C.c_voi
 _hip.qmcp_hip_filter_solve_by_contig_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p,
                                                        C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
                                                        C.c_uint32, C.c_int, _u64p, _u64p, C.POINTER(Stats)]
+_hip.qmcp_hip_solve_quality_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u64p, _u32p, C.c_uint32,
+                                             C.c_uint32, _u64p, C.POINTER(Stats), C.POINTER(QualityStats)]
+_hip.qmcp_hip_solve_quality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, _u32p,
+                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                               C.POINTER(QualityStats)]
+_hip.qmcp_hip_solve_quality_by_contig_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p,
+                                                       C.c_uint32, C.c_uint32, _u64p, C.POINTER(Stats),
+                                                       C.POINTER(QualityStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -155,6 +174,10 @@ if _host is not None:
     _host.qmcp_host_solve.argtypes = [C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_int, _u64p]
     _host.qmcp_host_solve.restype = C.c_int64
+    _host.qmcp_host_solve_with_qualities.argtypes = [C.c_char_p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32,
+                                                     C.c_uint32, C.c_int, C.c_int, _u64p]
+    _host.qmcp_host_solve_with_qualities.restype = C.c_int64
+    _host.qmcp_host_solver_uses_quality.argtypes = [C.c_char_p]
     _host.qmcp_host_plugin_solve_timed.argtypes = [C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint32,
                                                    C.c_uint32, _u64p, C.POINTER(C.c_float)]
     _host.qmcp_host_plugin_solve_timed.restype = C.c_int64
@@ -262,6 +285,7 @@ class Solver:
         _check(_hip.qmcp_hip_create(int(device), C.byref(self._ctx)))
         self.device = device
         self.last_stats = None
+        self.last_quality_stats = None
 
     def close(self):
         if self._ctx:
@@ -308,6 +332,50 @@ class Solver:
                                         _p32(lengths), lengths.size, int(max_coverage), _p64(mask),
                                         C.byref(st)))
         self.last_stats = st
+        return mask[:mask_words(n)]
+
+    def solve_quality(self, starts, ends, qualities, contig_lengths, max_coverage, contig_read_offsets=None):
+        """solve()'s coverage and number of reads, with the best reads: in every (contig, start, end) cell the plain
+        solve's count of reads, taken by quality descending, then read index; host keep bitmask out.  The plain solve's
+        stats go to last_stats, the quality pass's to last_quality_stats"""
+        starts, ends = _u32(starts), _u32(ends)
+        q = None if qualities is None else _u32(qualities)
+        n = starts.size
+        assert q is None or q.size == n, "one quality per read"
+        offs, lengths = _contig_tables(n, contig_read_offsets, contig_lengths)
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, qs = Stats(), QualityStats()
+        _check(_hip.qmcp_hip_solve_quality_host(self._ctx, _p32(starts), _p32(ends), _p32(q), n, _p64(offs),
+                                                _p32(lengths), lengths.size, int(max_coverage), _p64(mask),
+                                                C.byref(st), C.byref(qs)))
+        self.last_stats, self.last_quality_stats = st, qs
+        return mask[:mask_words(n)]
+
+    def solve_quality_device(self, d_starts, d_ends, d_qualities, n_reads, contig_lengths, max_coverage, d_mask,
+                             contig_read_offsets=None, stream=0):
+        """solve_quality on device pointers (ints); the mask is written to d_mask.  Returns the quality stats"""
+        offs, lengths = _contig_tables(n_reads, contig_read_offsets, contig_lengths)
+        st, qs = Stats(), QualityStats()
+        _check(_hip.qmcp_hip_solve_quality_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                  C.c_void_p(d_qualities), int(n_reads), _p64(offs), _p32(lengths),
+                                                  lengths.size, int(max_coverage), C.c_void_p(d_mask),
+                                                  C.c_void_p(stream), C.byref(st), C.byref(qs)))
+        self.last_stats, self.last_quality_stats = st, qs
+        return qs
+
+    def solve_quality_by_contig(self, starts, ends, contig_ids, qualities, contig_lengths, max_coverage):
+        """solve_by_contig, then the quality pass on its input-order mask (the contig is part of every cell)"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        q = None if qualities is None else _u32(qualities)
+        n = starts.size
+        assert ends.size == n and ids.size == n and (q is None or q.size == n), "one entry per read in every column"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, qs = Stats(), QualityStats()
+        _check(_hip.qmcp_hip_solve_quality_by_contig_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(q), n,
+                                                          _p32(lengths), lengths.size, int(max_coverage), _p64(mask),
+                                                          C.byref(st), C.byref(qs)))
+        self.last_stats, self.last_quality_stats = st, qs
         return mask[:mask_words(n)]
 
     def solve_by_contig(self, starts, ends, contig_ids, contig_lengths, max_coverage):
@@ -639,14 +707,33 @@ def solver_names():
     return [x for x in buf.value.decode().split("\n") if x]
 
 
-def host_solve(solver_name, starts, ends, ref_genome_length, max_coverage, with_pairs=False):
-    """SolverManager::get(name).solve(M, BamApi) through the C++ adapter; ascending ReadIndex"""
+def solver_uses_quality(solver_name):
+    """Solver::uses_quality_of_reads() of the default manager's solvers and of "quasi-mcp-hip-quality" (True / False),
+    None for an unknown name; builds nothing on the device"""
+    _need_host()
+    rc = _host.qmcp_host_solver_uses_quality(solver_name.encode())
+    return None if rc < 0 else bool(rc)
+
+
+def host_solve(solver_name, starts, ends, ref_genome_length, max_coverage, with_pairs=False, qualities=None,
+               adapter_pairs=False):
+    """SolverManager::get(name).solve(M, BamApi) through the C++ adapter; ascending ReadIndex.  qualities (one per read)
+    go into the reads' quality field (otherwise 0); "quasi-mcp-hip-quality" is resolved beside the default manager.
+    adapter_pairs=True (with qualities only): the adapter completes mate pairs on the device (set_complete_pairs)"""
     _need_host()
     starts, ends = _u32(starts), _u32(ends)
     kept = np.empty(max(starts.size, 1), dtype=np.uint64)
-    n = _host.qmcp_host_solve(solver_name.encode(), _p32(starts), _p32(ends), starts.size,
-                              int(ref_genome_length), int(max_coverage), int(bool(with_pairs)),
-                              _p64(kept))
+    assert qualities is not None or not adapter_pairs, "adapter_pairs goes through the entry with qualities"
+    if qualities is None:
+        n = _host.qmcp_host_solve(solver_name.encode(), _p32(starts), _p32(ends), starts.size,
+                                  int(ref_genome_length), int(max_coverage), int(bool(with_pairs)),
+                                  _p64(kept))
+    else:
+        q = _u32(qualities)
+        assert q.size == starts.size, "one quality per read"
+        n = _host.qmcp_host_solve_with_qualities(solver_name.encode(), _p32(starts), _p32(ends), _p32(q), starts.size,
+                                                 int(ref_genome_length), int(max_coverage), int(bool(with_pairs)),
+                                                 int(bool(adapter_pairs)), _p64(kept))
     if n < 0:
         raise KeyError(solver_name)
     return kept[:n].copy()
@@ -795,10 +882,11 @@ def copy_records(in_path, out_path, ids):
 
 
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
-                   per_reference=False, bed=None, tsv=None, amplicon_mode=1, amplicons_by_reference=False):
+                   per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
-    bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE) need per_reference=True and amplicons_by_reference=True:
+    bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
+    "quasi-mcp-hip-quality", FILTER for "quasi-mcp-hip") need per_reference=True and amplicons_by_reference=True:
     the BED's chroms are matched to the file's references by name (ValueError otherwise)"""
     _need_host()
     if (bed or tsv) and not (per_reference and amplicons_by_reference):
@@ -808,7 +896,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         n = _host.qmcp_host_downsample_bam_by_reference(
             solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
             str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None, int(amplicon_mode),
+            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
+            -1 if amplicon_mode is None else int(amplicon_mode),
             int(bool(per_reference)), 1, err, 1024)
         if n == -4:
             raise ValueError(err.value.decode())

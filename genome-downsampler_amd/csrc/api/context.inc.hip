@@ -122,6 +122,10 @@ struct qmcp_hip_ctx {
     // FILTER -> by-contig solve (api/amplicon_by_contig.inc.hip): the input ids, the compacted ids, the contig lengths,
     // the amplicon table (offsets, sorted starts, running maxima of the ends) and the validation word
     DevBuf af_ids, af_ids_c, af_len, af_tab, af_err;
+    // quality pass (api/quality.inc.hip): the quality range and counters, the contig tables, bare keys, the sort's two
+    // key buffers (records, or u64 keys) and two index buffers (u64 keys only), its histogram and spine, the scanned K
+    // bits and the segment bounds
+    DevBuf qc_words, qc_tab, qc_bare, qc_keys[2], qc_vals[2], qc_hist, qc_spine, qc_kb, qc_end, qc_head;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

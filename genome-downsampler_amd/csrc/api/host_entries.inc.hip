@@ -161,7 +161,8 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->cov, &c->amp, &c->scalars, &c->next_head, &c->ranges, &c->rankamb, &c->pm_desc, &c->pm_work, &c->segs, &c->specsnap, &c->specflags, &c->rings, &c->evpk, &c->evlast, &c->kidx, &c->f_starts, &c->f_ends, &c->f_map, &c->f_words, &c->f_mask, &c->nu_exc, &c->nu_nadj, &c->nu_ce, &c->nu_state, &c->nu_sus, &c->nu_ckpt, &c->nu_prev,
                       &c->bc_key, &c->bc_rec[0], &c->bc_rec[1], &c->bc_hist, &c->bc_spine, &c->bc_offs, &c->bc_err, &c->bc_len,
                       &c->bc_starts, &c->bc_ends, &c->bc_mask, &c->af_ids, &c->af_ids_c, &c->af_len, &c->af_tab,
-                      &c->af_err};
+                      &c->af_err, &c->qc_words, &c->qc_tab, &c->qc_bare, &c->qc_keys[0], &c->qc_keys[1],
+                      &c->qc_vals[0], &c->qc_vals[1], &c->qc_hist, &c->qc_spine, &c->qc_kb, &c->qc_end, &c->qc_head};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

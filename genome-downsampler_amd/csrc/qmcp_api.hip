@@ -41,6 +41,7 @@
 //   multi_device        several devices behind one call
 //   by_contig           reads in any order with a contig id each: grouped on the device, solved in batches, mask scattered back
 //   amplicon_by_contig  pairs of several contigs: FILTER against each contig's amplicons, compaction, the by-contig solve
+//   quality             the plain or by-contig solve, then the quality pass on its mask (same count per cell, best reads)
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -51,3 +52,4 @@
 #include "api/multi_device.inc.hip"
 #include "api/by_contig.inc.hip"
 #include "api/amplicon_by_contig.inc.hip"
+#include "api/quality.inc.hip"

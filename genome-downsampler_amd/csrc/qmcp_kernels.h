@@ -274,5 +274,20 @@ void launch_compact_pairs_ids(hipStream_t st, const uint32_t* starts, const uint
                               const uint64_t* pair_keep, const uint32_t* word_base, uint64_t n_pairs, uint32_t* starts_c,
                               uint32_t* ends_c, uint32_t* ids_c, uint32_t* orig_pair);
 
+// the quality pass of qmcp_hip_solve_quality_* (kernels/quality_cells.inc.hip; api/quality.inc.hip drives it): the
+// quality range of the placed reads (range: {min, max}, preset to {~0u, 0}), composite keys gstart | span - min_span |
+// q_max - q (u64 when `wide`, u32 otherwise; ids == NULL: contigs by roff, else by id with QMCP_NO_CONTIG reads in a cell
+// of their own), the segment marks and choice over the sorted {key, index} order (records, or split keys + svals when
+// `wide`), which flips the bits of the keep mask that change
+void launch_qc_range(hipStream_t st, const uint32_t* q, const uint32_t* ids, uint32_t n, uint32_t* range);
+void launch_qc_keys(hipStream_t st, bool wide, const uint32_t* starts, const uint32_t* ends, const uint32_t* q,
+                    const uint32_t* ids, const uint64_t* roff, const uint64_t* poff, uint32_t n_contigs, uint64_t ltot,
+                    uint32_t n, uint32_t min_span, uint32_t span_bits, uint32_t q_max, uint32_t q_bits, void* keys);
+void launch_qc_marks(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals, uint32_t n, uint32_t q_bits,
+                     const uint64_t* mask, uint32_t* kb, uint32_t* seg_end, uint32_t* seg_head_rev);
+void launch_qc_choose(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals, uint32_t n,
+                      const uint32_t* P, const uint32_t* seg_end, const uint32_t* seg_head_rev, uint64_t* mask,
+                      unsigned long long* counters);
+
 }  // namespace qmcp
 #endif

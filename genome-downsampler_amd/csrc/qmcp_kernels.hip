@@ -32,6 +32,8 @@
 //                            exceptions verified against it and selected one event at a time
 //   by_contig                reads in any order with a contig id each: sort keys, contig bounds, gather, mask scatter-back
 //   amplicon_by_contig       the FILTER of pairs against the amplicons of their own contig, compaction with the ids
+//   quality_cells            the quality pass: within every (contig, start, end) cell, the plain solve's count of reads
+//                            chosen by quality descending, then read index (composite keys, LSD radix, segmented choice)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -63,5 +65,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/near_uniform.inc.hip"
 #include "kernels/by_contig.inc.hip"
 #include "kernels/amplicon_by_contig.inc.hip"
+#include "kernels/quality_cells.inc.hip"
 
 }  // namespace qmcp

@@ -43,7 +43,7 @@ class QuasiMcpHipSolver : public Solver {
     float last_expand_ms() const { return ms_expand_; }
     float last_solve_call_ms() const { return ms_solve_call_; }
 
-   private:
+   protected:  // (QuasiMcpHipQualitySolver shares the context and the expansion)
     std::unique_ptr<Solution> solve_by_contig(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
                                               std::chrono::steady_clock::time_point t0);
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);

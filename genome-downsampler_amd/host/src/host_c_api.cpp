@@ -13,6 +13,7 @@
 #include "bam-api/amplicon_set.hpp"
 #include "bam-api/bam_api.hpp"
 #include "bam-api/bam_io.hpp"
+#include "qmcp-solver/quasi_mcp_hip_quality_solver.hpp"
 #include "reads_gen.hpp"
 #include "solver_manager.hpp"
 
@@ -29,6 +30,26 @@ double zero_both_sides(double x) { return -10.0 * (x - 0.5) * (x - 0.5) + 1.0; }
 SolverManager& manager() {
     static SolverManager m;
     return m;
+}
+
+// The default manager's solvers, and "quasi-mcp-hip-quality" beside them: an opt-in solver (an embedding application
+// registers it with SolverManager::add), so qmcp_host_solver_names keeps listing the default manager only.
+constexpr const char* kQualitySolverName = "quasi-mcp-hip-quality";
+qmcp::Solver* resolve(const char* name) {
+    if (manager().contains(name)) return &manager().get(name);
+    if (std::strcmp(name, kQualitySolverName) == 0) {
+        static qmcp::QuasiMcpHipQualitySolver quality;
+        return &quality;
+    }
+    return nullptr;
+}
+
+// amplicon_mode -1: the solver decides, as App::execute does (src/app.cpp:120-128) -- GRADE for a solver that uses the
+// reads' qualities, FILTER for every other
+bam_api::AmpliconBehaviour amplicon_behaviour(int amplicon_mode, qmcp::Solver& solver) {
+    if (amplicon_mode < 0) amplicon_mode = solver.uses_quality_of_reads() ? 2 : 1;
+    return amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
+         : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
 }
 
 }  // namespace
@@ -137,6 +158,41 @@ int qmcp_host_solver_names(char* buf, std::size_t cap) {
     return static_cast<int>(manager().get_names().size());
 }
 
+// 1 if the solver of that name (the default manager's, or "quasi-mcp-hip-quality") uses the reads' qualities -- the
+// app then grades amplicon pairs instead of filtering them --, 0 if not, -1 for an unknown name.  Builds nothing on the
+// device: solvers touch it on their first solve only.
+int qmcp_host_solver_uses_quality(const char* solver_name) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    return found->uses_quality_of_reads() ? 1 : 0;
+}
+
+// qmcp_host_solve with each read's quality (qmcp_host_solve builds reads of quality 0): kept_out (capacity n) gets the
+// ascending ReadIndex, with_pairs != 0 applies BamApi::find_pairs.  adapter_pairs != 0: the solver itself completes
+// pairs on the device for this call (QuasiMcpHipSolver::set_complete_pairs; -2 for a solver without that setter).
+// Negative on an unknown solver.
+std::int64_t qmcp_host_solve_with_qualities(const char* solver_name, const std::uint32_t* starts,
+                                            const std::uint32_t* ends, const std::uint32_t* qualities, std::uint64_t n,
+                                            std::uint32_t ref_genome_length, std::uint32_t max_coverage,
+                                            int with_pairs, int adapter_pairs, std::uint64_t* kept_out) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    bam_api::AOSPairedReads aos;
+    aos.ref_genome_length = ref_genome_length;
+    aos.reserve(n);
+    for (std::uint64_t i = 0; i < n; ++i)
+        aos.push_back(bam_api::Read(i, starts[i], ends[i], qualities[i], ends[i] - starts[i] + 1, i % 2 == 0));
+    bam_api::BamApi api(aos);
+    auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+    if (adapter_pairs && hip == nullptr) return -2;
+    if (adapter_pairs) hip->set_complete_pairs(true);
+    auto solution = found->solve(max_coverage, api);
+    if (adapter_pairs) hip->set_complete_pairs(false);
+    std::vector<bam_api::ReadIndex> ids = with_pairs ? api.find_pairs(*solution) : *solution;
+    for (std::size_t i = 0; i < ids.size(); ++i) kept_out[i] = ids[i];
+    return static_cast<std::int64_t>(ids.size());
+}
+
 // Runs SolverManager::get(name).solve(M, BamApi(aos)) the way src/app.cpp:134-135 and
 // src/tests/coverage_tester.cpp:109-118 do; returns the number of kept reads, fills
 // kept_out (capacity n) with ascending ReadIndex; with_pairs != 0 additionally applies
@@ -145,14 +201,15 @@ std::int64_t qmcp_host_solve(const char* solver_name, const std::uint32_t* start
                              const std::uint32_t* ends, std::uint64_t n,
                              std::uint32_t ref_genome_length, std::uint32_t max_coverage,
                              int with_pairs, std::uint64_t* kept_out) {
-    if (!manager().contains(solver_name)) return -1;
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
     bam_api::AOSPairedReads aos;
     aos.ref_genome_length = ref_genome_length;
     aos.reserve(n);
     for (std::uint64_t i = 0; i < n; ++i)
         aos.push_back(bam_api::Read(i, starts[i], ends[i], 0, ends[i] - starts[i] + 1, i % 2 == 0));
     bam_api::BamApi api(aos);
-    qmcp::Solver& solver = manager().get(solver_name);
+    qmcp::Solver& solver = *found;
     auto solution = solver.solve(max_coverage, api);
     std::vector<bam_api::ReadIndex> ids = with_pairs ? api.find_pairs(*solution) : *solution;
     for (std::size_t i = 0; i < ids.size(); ++i) kept_out[i] = ids[i];
@@ -416,13 +473,14 @@ std::int64_t qmcp_host_copy_records(const char* in_path, const char* out_path, c
 std::int64_t qmcp_host_downsample_bam(const char* solver_name, const char* in_path, const char* out_path,
                                       const char* filtered_path, std::uint32_t max_coverage,
                                       std::uint32_t min_len, std::uint32_t min_mapq) {
-    if (!manager().contains(solver_name)) return -1;
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
     bam_api::BamApiConfig cfg;
     cfg.min_seq_length = min_len;
     cfg.min_mapq = min_mapq;
     try {
         bam_api::BamApi api(in_path, cfg);
-        auto solution = manager().get(solver_name).solve(max_coverage, api);
+        auto solution = found->solve(max_coverage, api);
         std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
         const std::uint32_t written = api.write_paired_reads(out_path, paired);
         if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
@@ -438,14 +496,15 @@ std::int64_t qmcp_host_downsample_bam(const char* solver_name, const char* in_pa
 std::int64_t qmcp_host_downsample_bam_per_reference(const char* solver_name, const char* in_path, const char* out_path,
                                                     const char* filtered_path, std::uint32_t max_coverage,
                                                     std::uint32_t min_len, std::uint32_t min_mapq) {
-    if (!manager().contains(solver_name)) return -1;
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
     bam_api::BamApiConfig cfg;
     cfg.min_seq_length = min_len;
     cfg.min_mapq = min_mapq;
     cfg.per_reference = true;
     try {
         bam_api::BamApi api(in_path, cfg);
-        auto solution = manager().get(solver_name).solve(max_coverage, api);
+        auto solution = found->solve(max_coverage, api);
         std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
         const std::uint32_t written = api.write_paired_reads(out_path, paired);
         if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
@@ -464,19 +523,19 @@ std::int64_t qmcp_host_downsample_bam_by_reference(const char* solver_name, cons
                                                    std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
                                                    const char* tsv, int amplicon_mode, int per_reference,
                                                    int amplicons_by_reference, char* err, std::size_t err_cap) {
-    if (!manager().contains(solver_name)) return -1;
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
     bam_api::BamApiConfig cfg;
     if (bed && bed[0]) cfg.bed_filepath = bed;
     if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
     cfg.min_seq_length = min_len;
     cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
-                           : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
+    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
     cfg.per_reference = per_reference != 0;
     cfg.amplicons_by_reference = amplicons_by_reference != 0;
     try {
         bam_api::BamApi api(in_path, cfg);
-        auto solution = manager().get(solver_name).solve(max_coverage, api);
+        auto solution = found->solve(max_coverage, api);
         std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
         const std::uint32_t written = api.write_paired_reads(out_path, paired);
         if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
@@ -499,14 +558,15 @@ std::int64_t qmcp_host_plugin_solve_timed(const char* solver_name, const std::ui
                                           const std::uint32_t* ends, std::uint64_t n,
                                           std::uint32_t ref_genome_length, std::uint32_t max_coverage,
                                           std::uint64_t* kept_out, float* times) {
-    if (!manager().contains(solver_name)) return -1;
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
     bam_api::SOAPairedReads soa;
     soa.ref_genome_length = ref_genome_length;
     soa.reserve(n);
     for (std::uint64_t i = 0; i < n; ++i)
         soa.push_back(bam_api::Read(i, starts[i], ends[i], 0, ends[i] - starts[i] + 1, i % 2 == 0));
     bam_api::BamApi api(soa);
-    qmcp::Solver& solver = manager().get(solver_name);
+    qmcp::Solver& solver = *found;
     const auto t0 = std::chrono::steady_clock::now();
     auto solution = solver.solve(max_coverage, api);
     const float wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();

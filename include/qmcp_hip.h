@@ -408,6 +408,54 @@ int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* ctx,
                                          uint32_t max_coverage, int complete_pairs, uint64_t* keep_mask_out,
                                          uint64_t* pairs_filtered_out, qmcp_hip_stats* stats);
 
+/* Quality-aware selection: the solver the reference would register with uses_quality_of_reads() == true (its qmcp-cpu
+ * weighs reads by quality; src/app.cpp:120-128 then grades amplicon pairs instead of filtering them).  A CELL is the
+ * set of placed reads of one call that share (contig, start, end): reads of a cell are interchangeable for coverage.
+ * Let K be the mask qmcp_hip_solve_host (resp. qmcp_hip_solve_by_contig_host) returns for the same call and
+ * c = |K n C| for every cell C.  These entries return the mask Q that keeps, in every cell, the c reads that come first
+ * in the order (quality descending, read index ascending), and nothing else -- the canonical selection with its last
+ * key "smallest index" replaced by "highest quality, then smallest index".  So Q has the same per-position coverage and
+ * the same number of reads as K (a valid, minimum-cardinality maximum-flow support, like K), a cell whose reads share
+ * one quality is unchanged (all qualities equal: Q == K bit for bit), and every cell's kept quality is the largest
+ * possible.  Not claimed: the optimum of the reference's min-cost objective (qmcp-cpu), which may trade reads for
+ * other intervals or for more reads.
+ * qualities: one uint32 per read (MAPQ, or the graded quality of AmpliconBehaviour::GRADE), NULL fails with
+ * QMCP_EINVAL before anything else; a range (max - min over the placed reads) above 65535 fails with QMCP_ERANGE, found
+ * before the solve runs: the output mask is then not written.  Every other argument,
+ * limit and error is that of the plain entry; stats (may be NULL) are the plain solve's, qstats (may be NULL) the pass's.
+ * The pass runs after the solve on the same stream and before anything else; it is blocking (no _begin / _end form).
+ * The host entries leave the final mask in the context, for qmcp_hip_kept_indices_host and
+ * qmcp_hip_complete_pairs_host.  For the by-contig entry the cell includes the contig and QMCP_NO_CONTIG reads are
+ * never kept. */
+typedef struct qmcp_hip_quality_stats {
+    uint32_t quality_min, quality_max; /* over the placed reads                                                   */
+    uint32_t key_bits, sort_passes;    /* 0 passes: all qualities equal (or no read kept, or every read kept): the
+                                          mask is the plain one                                                   */
+    uint64_t cells_contested;          /* cells with 0 < c < size                                                 */
+    uint64_t reads_swapped;            /* reads that left the kept set (as many joined it)                         */
+    float ms_quality;                  /* device time of the pass                                                 */
+} qmcp_hip_quality_stats;
+int qmcp_hip_solve_quality_host(qmcp_hip_ctx* ctx,
+                                const uint32_t* starts, const uint32_t* ends, const uint32_t* qualities,
+                                uint64_t n_reads, const uint64_t* contig_read_offsets,
+                                const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                uint64_t* keep_mask_out, qmcp_hip_stats* stats, qmcp_hip_quality_stats* qstats);
+/* The same with the columns and the mask in device memory (contig tables stay on the host); ordered after `hip_stream`
+ * (or NULL) as qmcp_hip_solve_device is, and returns after the pass has completed on the device. */
+int qmcp_hip_solve_quality_device(qmcp_hip_ctx* ctx,
+                                  const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_qualities,
+                                  uint64_t n_reads, const uint64_t* contig_read_offsets,
+                                  const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                  uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                  qmcp_hip_quality_stats* qstats);
+/* qmcp_hip_solve_by_contig_host, then the pass on its input-order mask with the contig in the cell. */
+int qmcp_hip_solve_quality_by_contig_host(qmcp_hip_ctx* ctx,
+                                          const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                          const uint32_t* qualities, uint64_t n_reads,
+                                          const uint32_t* contig_lengths, uint32_t n_contigs,
+                                          uint32_t max_coverage, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                                          qmcp_hip_quality_stats* qstats);
+
 #ifdef __cplusplus
 }
 #endif

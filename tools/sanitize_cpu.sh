@@ -10,14 +10,14 @@ OUT=/tmp/qmcp_asan; mkdir -p $OUT
 PKG=genome-downsampler_amd
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g"
 g++ $SAN -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -I$PKG/host/include -DHIP_ENABLED -shared \
-    $PKG/host/src/bam_api.cpp $PKG/host/src/reads_gen.cpp $PKG/host/src/quasi_mcp_hip_solver.cpp $PKG/host/src/amplicon_set.cpp \
+    $PKG/host/src/bam_api.cpp $PKG/host/src/reads_gen.cpp $PKG/host/src/quasi_mcp_hip_solver.cpp $PKG/host/src/quasi_mcp_hip_quality_solver.cpp $PKG/host/src/amplicon_set.cpp \
     $PKG/host/src/bam_io.cpp $PKG/host/src/host_c_api.cpp -L$PKG/lib -lqmcp_hip -lz -lpthread -Wl,-rpath,$ROOT/$PKG/lib -o $OUT/libqmcp_host.so
 gcc $SAN -std=c11 -fPIC -Wall -shared oracle/qmcp_oracle.c -o $OUT/libqmcp_oracle.so
 export LD_PRELOAD="$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so)"
 export ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1
 export QMCP_HOST_LIB=$OUT/libqmcp_host.so QMCP_ORACLE_LIB=$OUT/libqmcp_oracle.so
 python -m pytest tests/test_bam_io.py tests/test_abi_and_host.py tests/test_oracle_golden.py tests/test_oracle_selection.py \
-    tests/test_oracle_forgetting.py tests/test_near_uniform_model.py -q -s -m "not gpu" > $OUT/run.log 2>&1 || { tail -30 $OUT/run.log; exit 1; }
+    tests/test_oracle_forgetting.py tests/test_near_uniform_model.py tests/test_quality_cpu.py -q -s -m "not gpu" > $OUT/run.log 2>&1 || { tail -30 $OUT/run.log; exit 1; }
 n=$(grep -c "runtime error\|AddressSanitizer" $OUT/run.log || true)
 tail -1 $OUT/run.log
 echo "sanitizer reports: $n"
