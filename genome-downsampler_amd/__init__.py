@@ -32,12 +32,14 @@ ABI_SYMBOLS = (
     "qmcp_hip_default_options", "qmcp_hip_set_options", "qmcp_hip_get_options",
     "qmcp_hip_solve_by_contig_host", "qmcp_hip_solve_by_contig_device", "qmcp_hip_filter_solve_by_contig_host",
     "qmcp_hip_solve_quality_host", "qmcp_hip_solve_quality_device", "qmcp_hip_solve_quality_by_contig_host",
+    "qmcp_hip_solve_targets_host", "qmcp_hip_solve_targets_device",
 )
 
 QMCP_OK = 0
 PATH_UNIFORM, PATH_GENERAL, PATH_NEAR_UNIFORM = 1, 2, 3
 KIND_UNIFORM, KIND_LOW_BOTH_SIDES, KIND_HOLE, KIND_ZERO_BOTH_SIDES = 0, 1, 2, 3
 NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never kept)
+TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
 
 
 # status codes of include/qmcp_hip.h
@@ -81,6 +83,15 @@ class QualityStats(C.Structure):
     _fields_ = [("quality_min", C.c_uint32), ("quality_max", C.c_uint32), ("key_bits", C.c_uint32),
                 ("sort_passes", C.c_uint32), ("cells_contested", C.c_uint64), ("reads_swapped", C.c_uint64),
                 ("ms_quality", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TargetStats(C.Structure):
+    """qmcp_hip_target_stats: what the projection, compaction and expansion around a target solve did"""
+    _fields_ = [("reads_on_target", C.c_uint64), ("reads_off_target", C.c_uint64), ("target_positions", C.c_uint64),
+                ("regions_in", C.c_uint32), ("regions_merged", C.c_uint32), ("ms_targets", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -164,6 +175,13 @@ _hip.qmcp_hip_solve_quality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_
 _hip.qmcp_hip_solve_quality_by_contig_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p,
                                                        C.c_uint32, C.c_uint32, _u64p, C.POINTER(Stats),
                                                        C.POINTER(QualityStats)]
+_hip.qmcp_hip_solve_targets_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32,
+                                             _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u64p,
+                                             C.POINTER(Stats), C.POINTER(TargetStats)]
+_hip.qmcp_hip_solve_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               _u32p, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                               C.POINTER(TargetStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -209,6 +227,13 @@ if _host is not None:
                                                             C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int,
                                                             C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_by_reference.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_targets.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                       C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                       C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_targets.restype = C.c_int64
+    _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
+                                                     C.c_size_t]
+    _host.qmcp_host_check_targets_config.restype = C.c_int64
     _host.qmcp_host_amplicons_by_reference.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint64,
                                                        _u32p, _u32p, _u32p, C.c_uint64, C.c_char_p, C.c_size_t]
     _host.qmcp_host_amplicons_by_reference.restype = C.c_int64
@@ -286,6 +311,7 @@ class Solver:
         self.device = device
         self.last_stats = None
         self.last_quality_stats = None
+        self.last_target_stats = None
 
     def close(self):
         if self._ctx:
@@ -403,6 +429,57 @@ class Solver:
                                                     C.c_void_p(stream), C.byref(st)))
         self.last_stats = st
         return st
+
+    @staticmethod
+    def _target_tables(n_contigs, target_offsets, target_starts, target_ends):
+        offs = None if target_offsets is None else _u32(target_offsets)
+        t0 = None if target_starts is None else _u32(target_starts)
+        t1 = None if target_ends is None else _u32(target_ends)
+        if offs is not None:
+            assert offs.size == n_contigs + 1, "target_offsets needs n_contigs + 1 entries"
+            n_reg = int(offs[-1])
+            assert (t0 is None or t0.size >= n_reg) and (t1 is None or t1.size >= n_reg), \
+                "target_starts / target_ends are shorter than target_offsets says"
+        return offs, t0, t1
+
+    def solve_targets(self, starts, ends, contig_ids, contig_lengths, max_coverage, target_offsets, target_starts,
+                      target_ends, padding=0, qualities=None, keep_off_target=False):
+        """on-target downsampling (qmcp_hip_solve_targets_host): coverage capped at max_coverage inside the target
+        regions only -- contig c owns regions [target_offsets[c], target_offsets[c + 1]) of target_starts / target_ends
+        (inclusive, any order, overlaps allowed), each widened by `padding`.  Reads that touch no target are dropped, or
+        all kept with keep_off_target=True.  qualities: the quality pass on the projected problem.  Host keep bitmask in
+        INPUT order out; the projected solve's stats go to last_stats, the pass around it to last_target_stats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        q = None if qualities is None else _u32(qualities)
+        n = starts.size
+        assert ends.size == n and ids.size == n and (q is None or q.size == n), "one entry per read in every column"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, t0, t1 = self._target_tables(lengths.size, target_offsets, target_starts, target_ends)
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ts = Stats(), TargetStats()
+        _check(_hip.qmcp_hip_solve_targets_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(q), n, _p32(lengths),
+                                                lengths.size, _p32(offs), _p32(t0), _p32(t1), int(padding),
+                                                int(max_coverage), TARGETS_KEEP_OFF_TARGET if keep_off_target else 0,
+                                                _p64(mask), C.byref(st), C.byref(ts)))
+        self.last_stats, self.last_target_stats = st, ts
+        return mask[:mask_words(n)]
+
+    def solve_targets_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, target_offsets,
+                             target_starts, target_ends, d_mask, padding=0, d_qualities=0, keep_off_target=False,
+                             stream=0):
+        """solve_targets on device pointers (ints; d_qualities 0: none); the input-order mask is written to d_mask.
+        Returns the target stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, t0, t1 = self._target_tables(lengths.size, target_offsets, target_starts, target_ends)
+        st, ts = Stats(), TargetStats()
+        _check(_hip.qmcp_hip_solve_targets_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                  C.c_void_p(d_contig_ids), C.c_void_p(d_qualities or None), int(n_reads),
+                                                  _p32(lengths), lengths.size, _p32(offs), _p32(t0), _p32(t1),
+                                                  int(padding), int(max_coverage),
+                                                  TARGETS_KEEP_OFF_TARGET if keep_off_target else 0, C.c_void_p(d_mask),
+                                                  C.c_void_p(stream), C.byref(st), C.byref(ts)))
+        self.last_stats, self.last_target_stats = st, ts
+        return ts
 
     def solve64(self, start_inds, end_inds, contig_lengths, max_coverage, contig_read_offsets=None):
         """the reference's own size_t columns in (qmcp_hip_solve_host64: narrowed inside the library),
@@ -671,6 +748,42 @@ def amplicons_by_reference(bed_path, tsv_path, reference_names):
     return offs, a0[:n].copy(), a1[:n].copy()
 
 
+def targets_from_bed(bed_path, reference_names):
+    """target regions from a BED file (BED3+, further columns ignored) matched to references by name -> (offsets, starts,
+    ends) as Solver.solve_targets takes them: reference c owns regions [offsets[c], offsets[c + 1]), in file order.  BED
+    is 0-based half-open, so a line "chrom s e" is the inclusive region [s, e - 1]; `track`, `browser` and `#` lines and
+    blank lines are skipped.  ValueError naming a chrom that matches no reference exactly, or a malformed line"""
+    names = [str(n) for n in reference_names]
+    index = {}
+    for k, name in enumerate(names):
+        index.setdefault(name, k)
+    per_ref = [[] for _ in names]
+    with open(bed_path) as bed:
+        for lineno, line in enumerate(bed, 1):
+            text = line.strip()
+            if not text or text.startswith("#") or text.split()[0] in ("track", "browser"):
+                continue
+            fields = text.split("\t") if "\t" in text else text.split()
+            if len(fields) < 3:
+                raise ValueError(f"{bed_path}:{lineno}: a BED line needs chrom, start and end")
+            chrom = fields[0]
+            try:
+                start, end = int(fields[1]), int(fields[2])
+            except ValueError:
+                raise ValueError(f"{bed_path}:{lineno}: start and end must be integers") from None
+            if start < 0 or end <= start or end > 0xFFFFFFFF:
+                raise ValueError(f"{bed_path}:{lineno}: region [{start}, {end}) is empty or out of range")
+            if chrom not in index:
+                raise ValueError(f"{bed_path}:{lineno}: chrom {chrom!r} matches no reference of the file")
+            per_ref[index[chrom]].append((start, end - 1))
+    offsets = np.zeros(len(names) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(r) for r in per_ref])
+    flat = [reg for r in per_ref for reg in r]
+    t0 = np.array([a for a, _ in flat], dtype=np.uint32)
+    t1 = np.array([b for _, b in flat], dtype=np.uint32)
+    return offsets, t0, t1
+
+
 def reference_names(path):
     """the BAM header's reference names, in header order"""
     _need_host()
@@ -881,16 +994,55 @@ def copy_records(in_path, out_path, ids):
     return int(n)
 
 
+def check_targets_config(in_path, targets, per_reference=True, target_padding=0):
+    """BamApi(in_path, BamApiConfig{targets_filepath, target_padding, per_reference}) without a solve: the number of
+    regions it parsed.  ValueError with BamApi's message when it refuses (targets without per_reference, a chrom that
+    names no reference, a malformed line)"""
+    _need_host()
+    err = C.create_string_buffer(1024)
+    n_regions = C.c_uint64(0)
+    rc = _host.qmcp_host_check_targets_config(str(in_path).encode(), str(targets).encode() if targets else None,
+                                              int(bool(per_reference)), int(target_padding), C.byref(n_regions), err,
+                                              1024)
+    if rc == -4:
+        raise ValueError(err.value.decode())
+    if rc < 0:
+        raise OSError(f"check_targets_config({in_path}) failed ({rc})")
+    return int(n_regions.value)
+
+
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
-                   per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False):
+                   per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
+                   targets=None, target_padding=0, keep_off_target=False):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
     "quasi-mcp-hip-quality", FILTER for "quasi-mcp-hip") need per_reference=True and amplicons_by_reference=True:
-    the BED's chroms are matched to the file's references by name (ValueError otherwise)"""
+    the BED's chroms are matched to the file's references by name (ValueError otherwise).
+    targets (a BED3+ file; BamApiConfig::targets_filepath, with target_padding and keep_off_target): coverage is capped
+    inside the target regions only, reads that touch none are dropped (or all kept with keep_off_target=True); needs
+    per_reference=True (ValueError otherwise), chroms matched to the references by name.  Amplicon files may be given as
+    well: FILTER / GRADE act at ingest, the targets in the solve"""
     _need_host()
     if (bed or tsv) and not (per_reference and amplicons_by_reference):
         raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
+    if targets:
+        if not per_reference:
+            raise ValueError("targets need per_reference=True")
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_targets(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
+            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)),
+            str(targets).encode(), int(target_padding), int(bool(keep_off_target)), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
     if amplicons_by_reference:
         err = C.create_string_buffer(1024)
         n = _host.qmcp_host_downsample_bam_by_reference(

@@ -126,6 +126,10 @@ struct qmcp_hip_ctx {
     // key buffers (records, or u64 keys) and two index buffers (u64 keys only), its histogram and spine, the scanned K
     // bits and the segment bounds
     DevBuf qc_words, qc_tab, qc_bare, qc_keys[2], qc_vals[2], qc_hist, qc_spine, qc_kb, qc_end, qc_head;
+    // target solves (api/targets.inc.hip): every read's projection, the mask of the placed off-target reads and the scan
+    // of its popcounts, the compacted qualities, and the table (lengths, region offsets, remap, bounds, cum); the
+    // compaction itself lives in the FILTER pipeline's buffers (f_*, af_ids_c, af_err, cov)
+    DevBuf tg_ps, tg_pe, tg_off, tg_offw, tg_q, tg_tab;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

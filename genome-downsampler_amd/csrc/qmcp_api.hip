@@ -27,6 +27,7 @@
 #include "qmcp_kernels.h"
 #include "by_contig_plan.h"
 #include "amplicon_table.h"
+#include "target_table.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
@@ -42,6 +43,8 @@
 //   by_contig           reads in any order with a contig id each: grouped on the device, solved in batches, mask scattered back
 //   amplicon_by_contig  pairs of several contigs: FILTER against each contig's amplicons, compaction, the by-contig solve
 //   quality             the plain or by-contig solve, then the quality pass on its mask (same count per cell, best reads)
+//   targets             coverage capped inside target regions only: reads projected onto each contig's target positions,
+//                       the by-contig solve (and quality pass) of the projected on-target reads, the mask expanded back
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -53,3 +56,4 @@
 #include "api/by_contig.inc.hip"
 #include "api/amplicon_by_contig.inc.hip"
 #include "api/quality.inc.hip"
+#include "api/targets.inc.hip"

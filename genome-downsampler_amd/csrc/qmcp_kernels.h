@@ -289,5 +289,20 @@ void launch_qc_choose(hipStream_t st, bool wide, const void* sorted, const uint3
                       const uint32_t* P, const uint32_t* seg_end, const uint32_t* seg_head_rev, uint64_t* mask,
                       unsigned long long* counters);
 
+// on-target downsampling (kernels/targets.inc.hip; api/targets.inc.hip drives them): every read validated (err as
+// launch_bc_keys) and projected onto its contig's target axis by target_table.h's project_read -- offs (n_contigs + 1),
+// rs / re / cum (n_regions) are the device copy of a TargetTable; on / off get one bit per read (on target; placed and off
+// target), ps / pe the projection --, the stable compaction of the on-target reads (ids through remap, q may be NULL),
+// the compact mask ORed into the zeroed input-order mask through orig, and mask |= other
+void launch_target_project(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids, uint32_t n,
+                           const uint32_t* lengths, uint32_t n_contigs, const uint32_t* offs, const uint32_t* rs,
+                           const uint32_t* re, const uint32_t* cum, uint32_t n_regions, uint32_t* ps, uint32_t* pe,
+                           uint64_t* on, uint64_t* off, uint32_t* err);
+void launch_compact_reads(hipStream_t st, const uint32_t* ps, const uint32_t* pe, const uint32_t* ids, const uint32_t* q,
+                          const uint32_t* remap, const uint64_t* on, const uint32_t* word_base, uint32_t n,
+                          uint32_t* starts_c, uint32_t* ends_c, uint32_t* ids_c, uint32_t* q_c, uint32_t* orig);
+void launch_expand_mask_reads(hipStream_t st, const uint64_t* mask_c, const uint32_t* orig, uint32_t n_c, uint64_t* mask);
+void launch_or_words(hipStream_t st, uint64_t* mask, const uint64_t* other, uint32_t n_words);
+
 }  // namespace qmcp
 #endif

@@ -34,10 +34,13 @@
 //   amplicon_by_contig       the FILTER of pairs against the amplicons of their own contig, compaction with the ids
 //   quality_cells            the quality pass: within every (contig, start, end) cell, the plain solve's count of reads
 //                            chosen by quality descending, then read index (composite keys, LSD radix, segmented choice)
+//   targets                  on-target downsampling: reads projected onto their contig's target positions, compaction
+//                            of the on-target reads, the compact mask expanded back to input order
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "qmcp_kernels.h"
+#include "target_table.h"  // project_read: shared with the host
 
 namespace qmcp {
 
@@ -66,5 +69,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/by_contig.inc.hip"
 #include "kernels/amplicon_by_contig.inc.hip"
 #include "kernels/quality_cells.inc.hip"
+#include "kernels/targets.inc.hip"
 
 }  // namespace qmcp

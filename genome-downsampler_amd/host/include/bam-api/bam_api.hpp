@@ -12,6 +12,7 @@
 
 #include <cstdint>
 #include <filesystem>
+#include <string>
 #include <vector>
 
 #include "bam-api/amplicon_set.hpp"
@@ -36,7 +37,28 @@ struct BamApiConfig {
     // one of its amplicons; GRADE grades by the same predicate.  Needs per_reference (std::invalid_argument
     // otherwise); an unknown chrom or a TSV pair across references is a std::invalid_argument naming it.
     bool amplicons_by_reference = false;
+    // On-target downsampling: a BED3+ file of target regions (0-based half-open; `track`, `browser` and `#` lines
+    // skipped), every chrom matched exactly to a reference of the BAM header.  Coverage is capped inside the regions
+    // (each widened by target_padding) only; reads that touch no region are dropped, or all kept with keep_off_target.
+    // Needs per_reference (std::invalid_argument otherwise); an unknown chrom or a malformed line is a
+    // std::invalid_argument naming it.  Independent of the amplicon files: FILTER / GRADE act at ingest, the targets in
+    // the solve (the hip solvers call qmcp_hip_solve_targets_host when the BamApi holds targets).
+    std::filesystem::path targets_filepath;
+    std::uint32_t target_padding = 0;
+    bool keep_off_target = false;
 };
+
+// the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
+// starts / ends (inclusive bounds, file order), as qmcp_hip_solve_targets_host takes them
+struct TargetRegions {
+    std::vector<std::uint32_t> offsets, starts, ends;
+    std::uint32_t padding = 0;
+    bool keep_off_target = false;
+};
+
+// false + *err: the file cannot be opened, a line is malformed, or a chrom names no reference
+bool target_regions_from_bed(const std::filesystem::path& bed, const std::vector<std::string>& ref_names,
+                             TargetRegions& out, std::string* err);
 
 class BamApi {
    public:
@@ -50,6 +72,9 @@ class BamApi {
     const PairedReads& get_paired_reads() const;
     void set_amplicon_behaviour(AmpliconBehaviour b) { amplicon_behaviour_ = b; }
     const std::vector<BAMReadId>& get_filtered_out_reads() const { return filtered_out_reads_; }
+    // BamApiConfig::targets_filepath was given: the solve is capped inside these regions only
+    bool has_targets() const { return has_targets_; }
+    const TargetRegions& get_targets() const { return targets_; }
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -73,6 +98,8 @@ class BamApi {
     std::filesystem::path input_filepath_;
     std::uint32_t min_seq_length_ = 0, min_mapq_ = 0;
     bool per_reference_ = false, amplicons_by_reference_ = false;
+    TargetRegions targets_;
+    bool has_targets_ = false;
     void read_bam_into(PairedReads& reads);
 };
 

@@ -38,6 +38,7 @@ class QuasiMcpHipSolver : public Solver {
     // host with BamApi::find_pairs); off by default, like the reference solvers
     void set_complete_pairs(bool on) { complete_pairs_ = on; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
+    const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
     const qmcp_hip_host_breakdown& last_breakdown() const { return breakdown_; }
     float last_expand_ms() const { return ms_expand_; }
@@ -46,6 +47,12 @@ class QuasiMcpHipSolver : public Solver {
    protected:  // (QuasiMcpHipQualitySolver shares the context and the expansion)
     std::unique_ptr<Solution> solve_by_contig(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
                                               std::chrono::steady_clock::time_point t0);
+    // the BamApi holds target regions (BamApiConfig::targets_filepath): qmcp_hip_solve_targets_host, with the reads'
+    // qualities when `with_qualities`
+    std::unique_ptr<Solution> solve_targets(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
+                                            const bam_api::TargetRegions& targets, bool with_qualities,
+                                            std::chrono::steady_clock::time_point t0);
+    qmcp_hip_target_stats tstats_{};
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves
     int device_ = 0;

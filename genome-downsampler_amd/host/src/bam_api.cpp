@@ -3,11 +3,63 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
+#include <map>
+#include <sstream>
 #include <stdexcept>
 
 #include "bam-api/bam_io.hpp"
 
 namespace bam_api {
+
+bool target_regions_from_bed(const std::filesystem::path& bed, const std::vector<std::string>& ref_names,
+                             TargetRegions& out, std::string* err) {
+    auto fail = [err](const std::string& msg) {
+        if (err) *err = msg;
+        return false;
+    };
+    std::ifstream file(bed);
+    if (!file.is_open()) return fail("could not open " + bed.string());
+    std::map<std::string, std::uint32_t> ref_of;
+    for (std::size_t r = 0; r < ref_names.size(); ++r) ref_of.emplace(ref_names[r], (std::uint32_t)r);
+    std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> per(ref_names.size());
+    std::string line;
+    std::size_t lineno = 0;
+    while (std::getline(file, line)) {
+        ++lineno;
+        const std::string where = bed.string() + ":" + std::to_string(lineno);
+        std::istringstream fields(line);
+        std::string chrom, start, end;
+        if (!(fields >> chrom) || chrom[0] == '#' || chrom == "track" || chrom == "browser") continue;
+        if (!(fields >> start >> end)) return fail(where + ": a BED line needs chrom, start and end");
+        unsigned long long s = 0, e = 0;
+        try {
+            std::size_t used_s = 0, used_e = 0;
+            s = std::stoull(start, &used_s);
+            e = std::stoull(end, &used_e);
+            if (used_s != start.size() || used_e != end.size() || start[0] == '-' || end[0] == '-')
+                throw std::invalid_argument("");
+        } catch (const std::exception&) {
+            return fail(where + ": start and end must be integers");
+        }
+        if (e <= s || e > 0xFFFFFFFFull) return fail(where + ": region is empty or out of range");
+        const auto ref = ref_of.find(chrom);
+        if (ref == ref_of.end())
+            return fail(where + ": BED chrom \"" + chrom + "\" names no reference of the BAM file (names must match exactly)");
+        per[ref->second].emplace_back((std::uint32_t)s, (std::uint32_t)(e - 1));  // half-open -> inclusive
+    }
+    out.offsets.assign(1, 0);
+    out.starts.clear();
+    out.ends.clear();
+    for (const auto& v : per) {
+        for (const auto& r : v) {
+            out.starts.push_back(r.first);
+            out.ends.push_back(r.second);
+        }
+        out.offsets.push_back((std::uint32_t)out.starts.size());
+    }
+    return true;
+}
 
 // bam_api.cpp:32-43: filters from the config; amplicons only when a BED file is given
 BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& config)
@@ -16,6 +68,22 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     if (amplicons_by_reference_ && !per_reference_)
         throw std::invalid_argument("amplicons_by_reference needs per_reference: amplicons are matched to the "
                                     "references a per-reference ingest keeps");
+    if (!config.targets_filepath.empty()) {
+        if (!per_reference_)
+            throw std::invalid_argument("targets need per_reference: target regions are matched to the references a "
+                                        "per-reference ingest keeps");
+        std::vector<std::string> names;
+        std::vector<std::uint32_t> lengths;
+        std::string err;
+        if (!read_bam_references(input_filepath_, names, lengths, &err)) {
+            std::fprintf(stderr, "[ERROR] %s\n", err.c_str());
+            std::exit(EXIT_FAILURE);  // (as read_bam_into on an unreadable input)
+        }
+        if (!target_regions_from_bed(config.targets_filepath, names, targets_, &err)) throw std::invalid_argument(err);
+        targets_.padding = config.target_padding;
+        targets_.keep_off_target = config.keep_off_target;
+        has_targets_ = true;
+    }
     if (per_reference_ && !amplicons_by_reference_ && (!config.bed_filepath.empty() || !config.tsv_filepath.empty()))
         throw std::invalid_argument("per-reference downsampling does not take amplicons (BED / TSV) yet: amplicons "
                                     "are not matched to references by name");

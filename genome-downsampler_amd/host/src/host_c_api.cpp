@@ -548,6 +548,66 @@ std::int64_t qmcp_host_downsample_bam_by_reference(const char* solver_name, cons
     }
 }
 
+// qmcp_host_downsample_bam_by_reference with target regions: BamApiConfig {targets_filepath, target_padding,
+// keep_off_target} on top of the amplicon fields (bed / tsv may be NULL).  FILTER / GRADE act at ingest as before; the
+// targets act in the solve (qmcp_hip_solve_targets_host).  Returns as qmcp_host_downsample_bam_by_reference; -4 also
+// when the target BED is refused (targets without per_reference, an unknown chrom, a malformed line).
+std::int64_t qmcp_host_downsample_bam_targets(const char* solver_name, const char* in_path, const char* out_path,
+                                              const char* filtered_path, std::uint32_t max_coverage,
+                                              std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
+                                              const char* tsv, int amplicon_mode, int per_reference,
+                                              int amplicons_by_reference, const char* targets,
+                                              std::uint32_t target_padding, int keep_off_target, char* err,
+                                              std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
+    cfg.per_reference = per_reference != 0;
+    cfg.amplicons_by_reference = amplicons_by_reference != 0;
+    if (targets && targets[0]) cfg.targets_filepath = targets;
+    cfg.target_padding = target_padding;
+    cfg.keep_off_target = keep_off_target != 0;
+    try {
+        bam_api::BamApi api(in_path, cfg);
+        auto solution = found->solve(max_coverage, api);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
+// BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
+// message otherwise (targets without per_reference, an unknown chrom, a malformed line)
+std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,
+                                            std::uint32_t target_padding, std::uint64_t* n_regions, char* err,
+                                            std::size_t err_cap) {
+    bam_api::BamApiConfig cfg;
+    cfg.per_reference = per_reference != 0;
+    if (targets && targets[0]) cfg.targets_filepath = targets;
+    cfg.target_padding = target_padding;
+    try {
+        bam_api::BamApi api(in_path, cfg);
+        if (n_regions) *n_regions = api.has_targets() ? api.get_targets().starts.size() : 0;
+        return 0;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // The span the reference times as "solve took" (src/app.cpp:132-139) at the plugin boundary: a BamApi
 // that already holds the reads as SOAPairedReads (size_t columns) -> solver.solve(M, api) -> Solution.
 // Building the BamApi is outside the span, as parsing the BAM is in the reference.  `times` receives

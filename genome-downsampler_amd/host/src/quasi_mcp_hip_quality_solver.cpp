@@ -31,6 +31,7 @@ std::unique_ptr<Solution> QuasiMcpHipQualitySolver::solve(std::uint32_t required
         const int rc = qmcp_hip_create(device_, &ctx_);
         if (rc != QMCP_OK) die("qmcp_hip_create", rc);
     }
+    if (bam_api.has_targets()) return solve_targets(required_cover, reads, bam_api.get_targets(), true, t0);
     std::vector<std::uint32_t> starts(n), ends(n);
     for (std::size_t i = 0; i < n; ++i) {
         if (by_contig && reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)

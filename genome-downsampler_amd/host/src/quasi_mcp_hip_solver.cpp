@@ -44,6 +44,7 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
         if (rc != QMCP_OK) die("qmcp_hip_create", rc);
     }
 
+    if (bam_api.has_targets()) return solve_targets(required_cover, reads, bam_api.get_targets(), false, t0);
     if (reads.has_contig_ids()) return solve_by_contig(required_cover, reads, t0);
 
     // the 64-bit columns go to the library as they are: it narrows them chunk by chunk on several
@@ -86,6 +87,42 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_by_contig(std::uint32_t requi
                                            reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
                                            required_cover, mask.data(), &stats_);
     if (rc != QMCP_OK) die("qmcp_hip_solve_by_contig_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) {
+        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
+        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
+    }
+    return expand_kept(n, t0);
+}
+
+// Per-reference reads with target regions (BamApiConfig::targets_filepath): coverage capped inside the regions only,
+// through qmcp_hip_solve_targets_host; otherwise as solve_by_contig.
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_targets(std::uint32_t required_cover,
+                                                           const bam_api::SOAPairedReads& reads,
+                                                           const bam_api::TargetRegions& targets, bool with_qualities,
+                                                           std::chrono::steady_clock::time_point t0) {
+    const std::size_t n = reads.start_inds.size();
+    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("target regions without one contig id per read", QMCP_EINVAL);
+    if (with_qualities && reads.qualities.size() != n) die("reads without one quality each", QMCP_EINVAL);
+    if (targets.offsets.size() != reads.contig_lengths.size() + 1) die("target regions of other references", QMCP_EINVAL);
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    int rc = qmcp_hip_solve_targets_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(),
+                                         with_qualities ? reads.qualities.data() : nullptr, n,
+                                         reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                         targets.offsets.data(), targets.starts.data(), targets.ends.data(),
+                                         targets.padding, required_cover,
+                                         targets.keep_off_target ? QMCP_TARGETS_KEEP_OFF_TARGET : 0u, mask.data(),
+                                         &stats_, &tstats_);
+    if (rc != QMCP_OK) die("qmcp_hip_solve_targets_host", rc);
+    if (targets.keep_off_target) stats_.n_kept += tstats_.reads_off_target;  // (expand_kept sizes the Solution by it)
     breakdown_ = qmcp_hip_host_breakdown{};
     if (complete_pairs_) {
         rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)

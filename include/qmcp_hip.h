@@ -456,6 +456,59 @@ int qmcp_hip_solve_quality_by_contig_host(qmcp_hip_ctx* ctx,
                                           uint32_t max_coverage, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
                                           qmcp_hip_quality_stats* qstats);
 
+/* On-target downsampling (exomes, hybrid-capture and amplicon panels): coverage is capped at max_coverage INSIDE target
+ * regions only, and reads that touch no target are out of the way.  Reads, contig ids, contig_lengths / n_contigs, limits
+ * and errors are those of qmcp_hip_solve_by_contig_host; qualities (one uint32 per read) may be NULL.
+ * Targets: target_offsets (n_contigs + 1 entries, starting at 0, never decreasing) gives contig c the regions
+ * [target_offsets[c], target_offsets[c + 1]) of target_starts / target_ends, inclusive bounds, in any order, overlapping
+ * and nested regions allowed.  Every region is widened by `padding` positions on both sides and clipped to its contig
+ * (a region that then begins at or beyond the contig's length is dropped); T_c is the union of contig c's regions.
+ * A placed read is ON TARGET iff it covers a position of its contig's T_c, OFF TARGET otherwise (every placed read of a
+ * contig without regions is).  The kept set F satisfies cov_F(p) >= min(cov(p), max_coverage) at every target position
+ * p with the fewest reads possible, and is defined exactly: with rank_c(p) = |{t in T_c : t < p}|, an on-target read
+ * [s, e] becomes [rank_c(s), rank_c(e + 1) - 1] on an axis of |T_c| positions, and the mask is what
+ * qmcp_hip_solve_by_contig_host returns for these projected reads (input order kept, contig lengths |T_c|), expressed
+ * over the input indices.  With qualities it is what qmcp_hip_solve_quality_by_contig_host returns for them: a cell is
+ * the set of reads of one contig with the same PROJECTED interval (a quality range of the on-target reads above 65535
+ * fails with QMCP_ERANGE).
+ * Off-target reads are never kept, unless flags has QMCP_TARGETS_KEEP_OFF_TARGET: then every placed off-target read is
+ * kept ("cap the targets, drop nothing else").  Unplaced reads are never kept.  No region at all is a valid call: it
+ * keeps nothing, or with the flag every placed read.
+ * Errors: target_offsets == NULL, offsets that do not start at 0 or that decrease, a region with start > end, null region
+ * arrays with a non-zero count and unknown flag bits fail with QMCP_EINVAL on the host, before anything is copied or
+ * launched: the output mask is not written.  A bad contig id (QMCP_EINVAL) or a bad read (QMCP_EREAD) is found on the
+ * device among ALL reads, off-target ones included, before anything is compacted; by then the device mask
+ * (d_keep_mask_out, or the context's own for the host entry) has been cleared, as qmcp_hip_solve_by_contig_* clears it
+ * before it validates -- it stays all zero, and the host entry does not write keep_mask_out.  The same holds for the
+ * quality range error.
+ * keep_mask_out: ceil(n_reads / 64) words in INPUT order, fully overwritten; the host entry leaves it in the context for
+ * qmcp_hip_kept_indices_host and qmcp_hip_complete_pairs_host.  stats (may be NULL) are those of the by-contig solve of
+ * the projected reads (all zero when no read is on target); tstats (may be NULL) describe the pre- and post-pass.
+ * The device entry takes the columns and the mask in device memory (the contig and target tables stay on the host), is
+ * ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the work has completed. */
+typedef struct qmcp_hip_target_stats {
+    uint64_t reads_on_target, reads_off_target;  /* placed reads                     */
+    uint64_t target_positions;                   /* sum of |T_c|                      */
+    uint32_t regions_in, regions_merged;
+    float ms_targets;                            /* project + compaction + expansion  */
+} qmcp_hip_target_stats;
+#define QMCP_TARGETS_KEEP_OFF_TARGET 1u
+int qmcp_hip_solve_targets_host(qmcp_hip_ctx* ctx,
+                                const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                const uint32_t* qualities /* may be NULL */, uint64_t n_reads,
+                                const uint32_t* contig_lengths, uint32_t n_contigs,
+                                const uint32_t* target_offsets, const uint32_t* target_starts,
+                                const uint32_t* target_ends, uint32_t padding, uint32_t max_coverage, uint32_t flags,
+                                uint64_t* keep_mask_out, qmcp_hip_stats* stats, qmcp_hip_target_stats* tstats);
+int qmcp_hip_solve_targets_device(qmcp_hip_ctx* ctx,
+                                  const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                  const uint32_t* d_qualities /* may be NULL */, uint64_t n_reads,
+                                  const uint32_t* contig_lengths, uint32_t n_contigs,
+                                  const uint32_t* target_offsets, const uint32_t* target_starts,
+                                  const uint32_t* target_ends, uint32_t padding, uint32_t max_coverage, uint32_t flags,
+                                  uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                  qmcp_hip_target_stats* tstats);
+
 #ifdef __cplusplus
 }
 #endif
