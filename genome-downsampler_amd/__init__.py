@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_by_contig_host", "qmcp_hip_solve_by_contig_device", "qmcp_hip_filter_solve_by_contig_host",
     "qmcp_hip_solve_quality_host", "qmcp_hip_solve_quality_device", "qmcp_hip_solve_quality_by_contig_host",
     "qmcp_hip_solve_targets_host", "qmcp_hip_solve_targets_device",
+    "qmcp_hip_depth_report_host", "qmcp_hip_depth_report_device",
 )
 
 QMCP_OK = 0
@@ -95,6 +96,42 @@ class TargetStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class DepthRow(C.Structure):
+    """qmcp_hip_depth_row: depth before (in) and after (kept) over the inclusive interval [start, end] of one contig"""
+    _fields_ = [("contig", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("min_in", C.c_uint32),
+                ("max_in", C.c_uint32), ("min_kept", C.c_uint32), ("max_kept", C.c_uint32), ("reserved", C.c_uint32),
+                ("positions", C.c_uint64), ("sum_in", C.c_uint64), ("sum_kept", C.c_uint64),
+                ("capped_positions", C.c_uint64), ("deficit_positions", C.c_uint64), ("deficit_sum", C.c_uint64)]
+
+
+DEPTH_ROW_DTYPE = np.dtype([(name, np.uint32 if t is C.c_uint32 else np.uint64) for name, t in DepthRow._fields_])
+assert DEPTH_ROW_DTYPE.itemsize == C.sizeof(DepthRow) == 80
+
+
+class DepthStats(C.Structure):
+    """qmcp_hip_depth_stats"""
+    _fields_ = [("reads_placed", C.c_uint64), ("reads_kept", C.c_uint64), ("scope_positions", C.c_uint64),
+                ("deficit_positions", C.c_uint64), ("regions_in", C.c_uint32), ("regions_merged", C.c_uint32),
+                ("position_batches", C.c_uint32), ("ms_report", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class DepthReport:
+    """what Solver.depth_report returns: contig_rows / region_rows (numpy structured arrays of DEPTH_ROW_DTYPE),
+    hist_in / hist_kept (uint64, n_bins entries), stats (DepthStats); valid: no position in scope is short of
+    min(coverage, max_coverage)"""
+
+    def __init__(self, contig_rows, region_rows, hist_in, hist_kept, stats):
+        self.contig_rows, self.region_rows = contig_rows, region_rows
+        self.hist_in, self.hist_kept, self.stats = hist_in, hist_kept, stats
+
+    @property
+    def valid(self):
+        return self.stats.deficit_positions == 0
 
 
 class Options(C.Structure):
@@ -182,6 +219,13 @@ _hip.qmcp_hip_solve_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_
                                                _u32p, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
                                                C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
                                                C.POINTER(TargetStats)]
+_depth_out = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, _u64p, _u64p, _u64p]
+_hip.qmcp_hip_depth_report_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u64p,
+                                            C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32] + _depth_out + \
+                                           [C.POINTER(DepthStats)]
+_hip.qmcp_hip_depth_report_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                              C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32] + \
+                                             _depth_out + [C.c_void_p, C.POINTER(DepthStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -231,6 +275,9 @@ if _host is not None:
                                                        C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                                        C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_targets.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_report.argtypes = _host.qmcp_host_downsample_bam_targets.argtypes[:-2] + \
+        [C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_report.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -480,6 +527,49 @@ class Solver:
                                                   C.c_void_p(stream), C.byref(st), C.byref(ts)))
         self.last_stats, self.last_target_stats = st, ts
         return ts
+
+    def _depth_call(self, entry, head, n, lengths, mask_arg, max_coverage, target_offsets, target_starts, target_ends,
+                    padding, n_bins, tail):
+        offs, t0, t1 = self._target_tables(lengths.size, target_offsets, target_starts, target_ends)
+        n_bins = int(n_bins)
+        cap = 0 if offs is None else int(offs[-1])
+        contig_rows = np.zeros(lengths.size, DEPTH_ROW_DTYPE)
+        region_rows = np.zeros(cap, DEPTH_ROW_DTYPE)
+        hist_in, hist_kept = np.zeros(max(n_bins, 1), np.uint64), np.zeros(max(n_bins, 1), np.uint64)
+        n_rows, st = C.c_uint64(0), DepthStats()
+        _check(entry(self._ctx, *head, n, _p32(lengths), lengths.size, mask_arg, int(max_coverage), _p32(offs), _p32(t0),
+                     _p32(t1), int(padding), n_bins, contig_rows.ctypes.data, region_rows.ctypes.data, cap,
+                     C.byref(n_rows), _p64(hist_in), _p64(hist_kept), *tail, C.byref(st)))
+        self.last_depth_stats = st
+        return DepthReport(contig_rows, region_rows[:n_rows.value].copy(), hist_in[:n_bins], hist_kept[:n_bins], st)
+
+    def depth_report(self, starts, ends, contig_ids, contig_lengths, max_coverage, keep_mask=None, target_offsets=None,
+                     target_starts=None, target_ends=None, padding=0, n_bins=0):
+        """depth before and after (qmcp_hip_depth_report_host): the reads of solve_by_contig, a keep mask in input order
+        (None: every placed read is kept) and optional regions in solve_targets' CSR form -> a DepthReport with one row
+        per contig, one per MERGED region, histograms of both depths over the positions in scope (the regions when given,
+        everything otherwise; depth d counts in bin min(d, n_bins - 1)) and the positions short of
+        min(coverage, max_coverage).  Computed on the device; nothing per position comes back"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = None
+        if keep_mask is not None:
+            mask = np.ascontiguousarray(keep_mask, dtype=np.uint64)
+            assert mask.size >= mask_words(n), "keep_mask needs ceil(n_reads / 64) words"
+        return self._depth_call(_hip.qmcp_hip_depth_report_host, (_p32(starts), _p32(ends), _p32(ids)), n, lengths,
+                                _p64(mask), max_coverage, target_offsets, target_starts, target_ends, padding, n_bins, ())
+
+    def depth_report_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_keep_mask=0,
+                            target_offsets=None, target_starts=None, target_ends=None, padding=0, n_bins=0, stream=0):
+        """depth_report on device pointers (ints; d_keep_mask 0: every placed read is kept); the tables and the report
+        itself are host memory"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        head = (C.c_void_p(d_starts), C.c_void_p(d_ends), C.c_void_p(d_contig_ids))
+        return self._depth_call(_hip.qmcp_hip_depth_report_device, head, int(n_reads), lengths,
+                                C.c_void_p(d_keep_mask or None), max_coverage, target_offsets, target_starts, target_ends,
+                                padding, n_bins, (C.c_void_p(stream),))
 
     def solve64(self, start_inds, end_inds, contig_lengths, max_coverage, contig_read_offsets=None):
         """the reference's own size_t columns in (qmcp_hip_solve_host64: narrowed inside the library),
@@ -784,6 +874,51 @@ def targets_from_bed(bed_path, reference_names):
     return offsets, t0, t1
 
 
+def window_regions(contig_lengths, size):
+    """fixed windows of `size` positions over every contig (the last window of a contig is shorter), in the CSR form
+    depth_report and solve_targets take: (offsets, starts, ends), inclusive bounds -- the regions of a mosdepth-style "--by size" report.  The report merges adjacent regions like
+    overlapping ones (target_table.h's rule), so windows passed as they are come back as one row per contig; shorten
+    each by one position (ends - 1 where ends > starts) to keep one row per window"""
+    size = int(size)
+    if size < 1:
+        raise ValueError("window size must be at least 1")
+    lengths = np.atleast_1d(np.asarray(contig_lengths, dtype=np.int64))
+    counts = (lengths + size - 1) // size
+    offsets = np.zeros(lengths.size + 1, np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    if offsets[-1] >= 1 << 32:
+        raise ValueError("more than 2^32 - 1 windows")
+    within = np.arange(offsets[-1], dtype=np.int64) - np.repeat(offsets[:-1], counts)
+    starts = within * size
+    ends = np.minimum(starts + size, np.repeat(lengths, counts)) - 1
+    return offsets.astype(np.uint32), starts.astype(np.uint32), ends.astype(np.uint32)
+
+
+DEPTH_REPORT_COLUMNS = ("kind", "reference", "start", "end", "positions", "mean_in", "mean_kept", "min_in", "max_in",
+                        "min_kept", "max_kept", "capped_positions", "deficit_positions", "deficit_sum")
+
+
+def write_depth_report(path, report, reference_names):
+    """a DepthReport as TSV: a '#'-prefixed header line (DEPTH_REPORT_COLUMNS), then one line per contig row and one per
+    region row -- start 0-based, end exclusive (BED style), the means with six decimals.  Histograms, when the report
+    has any, follow as '#hist' comment lines (bin, positions before, positions after)"""
+    names = list(reference_names)
+    with open(path, "w") as f:
+        f.write("#" + "\t".join(DEPTH_REPORT_COLUMNS) + "\n")
+        for kind, rows in (("contig", report.contig_rows), ("region", report.region_rows)):
+            for r in rows:
+                pos = int(r["positions"])
+                end = int(r["end"]) + 1 if pos else int(r["start"])
+                mean_in = int(r["sum_in"]) / pos if pos else 0.0
+                mean_kept = int(r["sum_kept"]) / pos if pos else 0.0
+                f.write("\t".join([kind, names[int(r["contig"])], str(int(r["start"])), str(end), str(pos),
+                                   f"{mean_in:.6f}", f"{mean_kept:.6f}", str(int(r["min_in"])), str(int(r["max_in"])),
+                                   str(int(r["min_kept"])), str(int(r["max_kept"])), str(int(r["capped_positions"])),
+                                   str(int(r["deficit_positions"])), str(int(r["deficit_sum"]))]) + "\n")
+        for b in range(len(report.hist_in)):
+            f.write(f"#hist\t{b}\t{int(report.hist_in[b])}\t{int(report.hist_kept[b])}\n")
+
+
 def reference_names(path):
     """the BAM header's reference names, in header order"""
     _need_host()
@@ -1013,7 +1148,7 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
 
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
-                   targets=None, target_padding=0, keep_off_target=False):
+                   targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1022,10 +1157,34 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     targets (a BED3+ file; BamApiConfig::targets_filepath, with target_padding and keep_off_target): coverage is capped
     inside the target regions only, reads that touch none are dropped (or all kept with keep_off_target=True); needs
     per_reference=True (ValueError otherwise), chroms matched to the references by name.  Amplicon files may be given as
-    well: FILTER / GRADE act at ingest, the targets in the solve"""
+    well: FILTER / GRADE act at ingest, the targets in the solve.
+    report (a path; BamApiConfig::depth_report_filepath, with report_bins histogram bins): after the output has been
+    written, the depth report (write_depth_report's TSV) of the reads the solve saw -- those that passed the ingest
+    filters -- against the FINAL kept set (after mate completion), with max_coverage and, if given, the targets and
+    their padding as regions; needs per_reference=True (ValueError otherwise).  None: nothing changes"""
     _need_host()
     if (bed or tsv) and not (per_reference and amplicons_by_reference):
         raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
+    if report:
+        if not per_reference:
+            raise ValueError("a depth report needs per_reference=True")
+        if targets and not per_reference:
+            raise ValueError("targets need per_reference=True")
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_report(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
+            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)),
+            str(targets).encode() if targets else None, int(target_padding), int(bool(keep_off_target)),
+            str(report).encode(), int(report_bins), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n}): {err.value.decode()}")
+        return int(n)
     if targets:
         if not per_reference:
             raise ValueError("targets need per_reference=True")

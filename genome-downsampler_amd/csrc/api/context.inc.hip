@@ -130,6 +130,9 @@ struct qmcp_hip_ctx {
     // of its popcounts, the compacted qualities, and the table (lengths, region offsets, remap, bounds, cum); the
     // compaction itself lives in the FILTER pipeline's buffers (f_*, af_ids_c, af_err, cov)
     DevBuf tg_ps, tg_pe, tg_off, tg_offw, tg_q, tg_tab;
+    // depth report (api/depth_report.inc.hip): a batch's event words, its tables (lengths, offsets, the two interval
+    // tables), the rows' accumulators, the histograms, the chunk sums, and the read counts + validation word
+    DevBuf dr_ev, dr_tab, dr_acc, dr_hist, dr_sums, dr_cnt;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

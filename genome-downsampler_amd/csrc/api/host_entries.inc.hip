@@ -163,7 +163,8 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->bc_starts, &c->bc_ends, &c->bc_mask, &c->af_ids, &c->af_ids_c, &c->af_len, &c->af_tab,
                       &c->af_err, &c->qc_words, &c->qc_tab, &c->qc_bare, &c->qc_keys[0], &c->qc_keys[1],
                       &c->qc_vals[0], &c->qc_vals[1], &c->qc_hist, &c->qc_spine, &c->qc_kb, &c->qc_end, &c->qc_head,
-                      &c->tg_ps, &c->tg_pe, &c->tg_off, &c->tg_offw, &c->tg_q, &c->tg_tab};
+                      &c->tg_ps, &c->tg_pe, &c->tg_off, &c->tg_offw, &c->tg_q, &c->tg_tab,
+                      &c->dr_ev, &c->dr_tab, &c->dr_acc, &c->dr_hist, &c->dr_sums, &c->dr_cnt};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

@@ -45,6 +45,8 @@
 //   quality             the plain or by-contig solve, then the quality pass on its mask (same count per cell, best reads)
 //   targets             coverage capped inside target regions only: reads projected onto each contig's target positions,
 //                       the by-contig solve (and quality pass) of the projected on-target reads, the mask expanded back
+//   depth_report        depth before and after a keep mask, per contig and per region, with histograms: position batches,
+//                       the reads' events, the positions pass, rows and statistics assembled on the host
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -57,3 +59,4 @@
 #include "api/amplicon_by_contig.inc.hip"
 #include "api/quality.inc.hip"
 #include "api/targets.inc.hip"
+#include "api/depth_report.inc.hip"

@@ -304,5 +304,23 @@ void launch_compact_reads(hipStream_t st, const uint32_t* ps, const uint32_t* pe
 void launch_expand_mask_reads(hipStream_t st, const uint64_t* mask_c, const uint32_t* orig, uint32_t n_c, uint64_t* mask);
 void launch_or_words(hipStream_t st, uint64_t* mask, const uint64_t* other, uint32_t n_words);
 
+// the depth report of qmcp_hip_depth_report_* (kernels/depth_report.inc.hip; api/depth_report.inc.hip drives it), one
+// position batch = the contigs [c0, c1) on an axis of `positions` positions: the reads' events (ev: positions + 1 zeroed
+// 64-bit words; lengths: every contig's; boff: the batch-local offsets of [c0, c1); mask may be NULL; counts: placed and
+// kept reads; err as launch_bc_keys), the chunk sums and their scan (sums: depth_chunks(positions) words), and the pass
+// that turns the events into rows (two tables of sorted disjoint intervals lo / hi with the accumulator row of each;
+// acc64: 5 x n_rows, acc32: 4 x n_rows with the minima preset to ~0u) and histograms (hist: 2 x n_bins 64-bit words)
+void launch_depth_events(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids, uint32_t n,
+                         const uint64_t* mask, const uint32_t* lengths, const uint32_t* boff, uint32_t n_contigs,
+                         uint32_t c0, uint32_t c1, uint64_t* ev, uint64_t* counts, uint32_t* err);
+uint32_t depth_lds_contigs();  // contig tables up to this many contigs are staged in LDS
+uint32_t depth_chunks(uint32_t positions);
+void launch_depth_sums(hipStream_t st, const uint64_t* ev, uint32_t positions, uint64_t* sums);
+void launch_depth_consume(hipStream_t st, const uint64_t* ev, uint32_t positions, const uint64_t* sums, uint32_t M,
+                          const uint32_t* c_lo, const uint32_t* c_hi, const uint32_t* c_row, uint32_t n_c,
+                          const uint32_t* r_lo, const uint32_t* r_hi, const uint32_t* r_row, uint32_t n_r,
+                          bool scope_regions, uint32_t n_rows, uint64_t* acc64, uint32_t* acc32, uint32_t n_bins,
+                          uint64_t* hist);
+
 }  // namespace qmcp
 #endif

@@ -36,6 +36,8 @@
 //                            chosen by quality descending, then read index (composite keys, LSD radix, segmented choice)
 //   targets                  on-target downsampling: reads projected onto their contig's target positions, compaction
 //                            of the on-target reads, the compact mask expanded back to input order
+//   depth_report             depth before and after a keep mask per contig and region: the reads' events (two 64-bit
+//                            atomics per read), chunk sums, spine, and the pass that turns them into rows and histograms
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -70,5 +72,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/amplicon_by_contig.inc.hip"
 #include "kernels/quality_cells.inc.hip"
 #include "kernels/targets.inc.hip"
+#include "kernels/depth_report.inc.hip"
 
 }  // namespace qmcp

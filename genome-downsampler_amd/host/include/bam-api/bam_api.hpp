@@ -46,6 +46,12 @@ struct BamApiConfig {
     std::filesystem::path targets_filepath;
     std::uint32_t target_padding = 0;
     bool keep_off_target = false;
+    // Depth report: after the output has been written, the caller (App::execute's place) asks the hip solver for the
+    // depth of the reads the solve saw against the final kept set, per reference and per target region, and writes it
+    // here as TSV (QuasiMcpHipSolver::depth_report / write_depth_report_tsv); depth_report_bins > 0 adds histograms.
+    // Needs per_reference (std::invalid_argument otherwise).  Empty: no report, nothing changes.
+    std::filesystem::path depth_report_filepath;
+    std::uint32_t depth_report_bins = 0;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -75,6 +81,9 @@ class BamApi {
     // BamApiConfig::targets_filepath was given: the solve is capped inside these regions only
     bool has_targets() const { return has_targets_; }
     const TargetRegions& get_targets() const { return targets_; }
+    // BamApiConfig::depth_report_filepath (empty: none) and depth_report_bins
+    const std::filesystem::path& depth_report_filepath() const { return depth_report_filepath_; }
+    std::uint32_t depth_report_bins() const { return depth_report_bins_; }
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -100,6 +109,8 @@ class BamApi {
     bool per_reference_ = false, amplicons_by_reference_ = false;
     TargetRegions targets_;
     bool has_targets_ = false;
+    std::filesystem::path depth_report_filepath_;
+    std::uint32_t depth_report_bins_ = 0;
     void read_bam_into(PairedReads& reads);
 };
 

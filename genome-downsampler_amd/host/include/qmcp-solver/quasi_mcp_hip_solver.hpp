@@ -9,13 +9,27 @@
 
 #include <chrono>
 #include <cstdint>
+#include <filesystem>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "qmcp-solver/solver.hpp"
 #include "qmcp_hip.h"
 
 namespace qmcp {
+
+// qmcp_hip_depth_report_host's outputs
+struct DepthReport {
+    std::vector<qmcp_hip_depth_row> contig_rows, region_rows;
+    std::vector<std::uint64_t> hist_in, hist_kept;
+    qmcp_hip_depth_stats stats{};
+};
+
+// the report as TSV: a '#'-prefixed header line, one line per contig row and per region row (start 0-based, end
+// exclusive, means with six decimals), then '#hist' lines when there are histograms.  false: the file cannot be written
+bool write_depth_report_tsv(const std::filesystem::path& path, const DepthReport& report,
+                            const std::vector<std::string>& reference_names);
 
 class QuasiMcpHipSolver : public Solver {
    public:
@@ -37,6 +51,12 @@ class QuasiMcpHipSolver : public Solver {
     // complete mate pairs on the device before returning (what src/app.cpp:141 does on the
     // host with BamApi::find_pairs); off by default, like the reference solvers
     void set_complete_pairs(bool on) { complete_pairs_ = on; }
+    // Depth before and after, for the reads of a per-reference BamApi against the kept set `kept` (ascending or not;
+    // App::execute would pass find_pairs' result after write_paired_reads): qmcp_hip_depth_report_host with
+    // M = required_cover, the BamApi's target regions and padding when it holds any, n_bins histogram bins.
+    // std::terminate on a device failure, like solve()
+    void depth_report(std::uint32_t required_cover, bam_api::BamApi& bam_api, const std::vector<bam_api::ReadIndex>& kept,
+                      std::uint32_t n_bins, DepthReport& out);
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call

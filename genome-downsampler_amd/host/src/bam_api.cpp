@@ -68,6 +68,13 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     if (amplicons_by_reference_ && !per_reference_)
         throw std::invalid_argument("amplicons_by_reference needs per_reference: amplicons are matched to the "
                                     "references a per-reference ingest keeps");
+    if (!config.depth_report_filepath.empty()) {
+        if (!per_reference_)
+            throw std::invalid_argument("a depth report needs per_reference: its rows are the references a per-reference "
+                                        "ingest keeps");
+        depth_report_filepath_ = config.depth_report_filepath;
+        depth_report_bins_ = config.depth_report_bins;
+    }
     if (!config.targets_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("targets need per_reference: target regions are matched to the references a "

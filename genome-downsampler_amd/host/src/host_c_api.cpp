@@ -587,6 +587,66 @@ std::int64_t qmcp_host_downsample_bam_targets(const char* solver_name, const cha
     }
 }
 
+// qmcp_host_downsample_bam_targets with a depth report: BamApiConfig {depth_report_filepath, depth_report_bins} on top
+// (targets may be NULL: the report is then per reference only).  After the output has been written, the hip solver
+// reports the reads the solve saw against the final kept set (after find_pairs) with M = max_coverage and the call's
+// targets and padding, and the TSV goes to report_path.  Returns as qmcp_host_downsample_bam_targets; -4 also for a
+// report without per_reference or with a solver that has none, -5 when the report cannot be written.
+std::int64_t qmcp_host_downsample_bam_report(const char* solver_name, const char* in_path, const char* out_path,
+                                             const char* filtered_path, std::uint32_t max_coverage,
+                                             std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
+                                             const char* tsv, int amplicon_mode, int per_reference,
+                                             int amplicons_by_reference, const char* targets,
+                                             std::uint32_t target_padding, int keep_off_target, const char* report_path,
+                                             std::uint32_t report_bins, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
+    cfg.per_reference = per_reference != 0;
+    cfg.amplicons_by_reference = amplicons_by_reference != 0;
+    if (targets && targets[0]) cfg.targets_filepath = targets;
+    cfg.target_padding = target_padding;
+    cfg.keep_off_target = keep_off_target != 0;
+    if (report_path && report_path[0]) cfg.depth_report_filepath = report_path;
+    cfg.depth_report_bins = report_bins;
+    try {
+        bam_api::BamApi api(in_path, cfg);
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr && !api.depth_report_filepath().empty())
+            throw std::invalid_argument("this solver has no depth report");
+        auto solution = found->solve(max_coverage, api);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        if (!api.depth_report_filepath().empty()) {
+            std::vector<std::string> names;
+            std::vector<std::uint32_t> lengths;
+            std::string msg;
+            if (!bam_api::read_bam_references(in_path, names, lengths, &msg)) {
+                copy_err(msg, err, err_cap);
+                return -5;
+            }
+            qmcp::DepthReport report;
+            hip->depth_report(max_coverage, api, paired, api.depth_report_bins(), report);
+            if (!qmcp::write_depth_report_tsv(api.depth_report_filepath(), report, names)) {
+                copy_err("could not write " + api.depth_report_filepath().string(), err, err_cap);
+                return -5;
+            }
+        }
+        return written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

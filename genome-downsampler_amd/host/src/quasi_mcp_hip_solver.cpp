@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <exception>
 #include <algorithm>
+#include <fstream>
 #include <limits>
 #include <vector>
 
@@ -129,6 +130,71 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_targets(std::uint32_t require
         if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
     }
     return expand_kept(n, t0);
+}
+
+void QuasiMcpHipSolver::depth_report(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                     const std::vector<bam_api::ReadIndex>& kept, std::uint32_t n_bins, DepthReport& out) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const std::size_t n = reads.start_inds.size();
+    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("a depth report without one contig id per read", QMCP_EINVAL);
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    for (const bam_api::ReadIndex i : kept)
+        if (i < n) mask[i >> 6] |= 1ull << (i & 63);
+    const std::uint32_t n_contigs = (std::uint32_t)reads.contig_lengths.size();
+    const bool regions = bam_api.has_targets();
+    const bam_api::TargetRegions& t = bam_api.get_targets();
+    out = DepthReport();
+    out.contig_rows.resize(n_contigs);
+    out.region_rows.resize(regions ? t.starts.size() : 0);
+    out.hist_in.assign(n_bins, 0);
+    out.hist_kept.assign(n_bins, 0);
+    std::uint64_t n_rows = 0;
+    const int rc = qmcp_hip_depth_report_host(
+        ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(), n_contigs, mask.data(),
+        required_cover, regions ? t.offsets.data() : nullptr, regions ? t.starts.data() : nullptr,
+        regions ? t.ends.data() : nullptr, regions ? t.padding : 0u, n_bins, out.contig_rows.data(), out.region_rows.data(),
+        out.region_rows.size(), &n_rows, n_bins ? out.hist_in.data() : nullptr, n_bins ? out.hist_kept.data() : nullptr,
+        &out.stats);
+    if (rc != QMCP_OK) die("qmcp_hip_depth_report_host", rc);
+    out.region_rows.resize(n_rows);
+}
+
+bool write_depth_report_tsv(const std::filesystem::path& path, const DepthReport& report,
+                            const std::vector<std::string>& reference_names) {
+    std::FILE* f = std::fopen(path.c_str(), "w");
+    if (f == nullptr) return false;
+    std::fputs("#kind\treference\tstart\tend\tpositions\tmean_in\tmean_kept\tmin_in\tmax_in\tmin_kept\tmax_kept\t"
+               "capped_positions\tdeficit_positions\tdeficit_sum\n", f);
+    auto rows = [&](const char* kind, const std::vector<qmcp_hip_depth_row>& v) {
+        for (const qmcp_hip_depth_row& r : v) {
+            const unsigned long long pos = r.positions;
+            const unsigned long long end = pos ? (unsigned long long)r.end + 1 : r.start;
+            const double mean_in = pos ? (double)r.sum_in / (double)pos : 0.0;
+            const double mean_kept = pos ? (double)r.sum_kept / (double)pos : 0.0;
+            const char* name = r.contig < reference_names.size() ? reference_names[r.contig].c_str() : "*";
+            std::fprintf(f, "%s\t%s\t%u\t%llu\t%llu\t%.6f\t%.6f\t%u\t%u\t%u\t%u\t%llu\t%llu\t%llu\n", kind, name, r.start,
+                         end, pos, mean_in, mean_kept, r.min_in, r.max_in, r.min_kept, r.max_kept,
+                         (unsigned long long)r.capped_positions, (unsigned long long)r.deficit_positions,
+                         (unsigned long long)r.deficit_sum);
+        }
+    };
+    rows("contig", report.contig_rows);
+    rows("region", report.region_rows);
+    for (std::size_t b = 0; b < report.hist_in.size(); ++b)
+        std::fprintf(f, "#hist\t%zu\t%llu\t%llu\n", b, (unsigned long long)report.hist_in[b],
+                     (unsigned long long)report.hist_kept[b]);
+    return std::fclose(f) == 0;
 }
 
 // the context's keep mask as the ascending Solution

@@ -509,6 +509,72 @@ int qmcp_hip_solve_targets_device(qmcp_hip_ctx* ctx,
                                   uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                   qmcp_hip_target_stats* tstats);
 
+/* Depth report: what `samtools depth` / mosdepth on the input and on the output would tell, computed on the device from
+ * the read columns and a keep mask and summarised per contig and per region -- nothing of the size of the genome crosses
+ * the link.  Reads, contig_ids (QMCP_NO_CONTIG = unplaced), contig_lengths / n_contigs as in qmcp_hip_solve_by_contig_host,
+ * in any order (nothing is grouped or sorted); at most 2^31 - 1 reads.  keep_mask: ceil(n_reads / 64) words in input order,
+ * NULL = every placed read is kept; bits of unplaced reads and bits beyond n_reads are ignored.  Regions (optional:
+ * target_offsets == NULL means none) in the CSR form of qmcp_hip_solve_targets_host, padded, clipped, sorted and merged in
+ * the same way, so overlapping rows are fine.
+ * With cov(p) the number of placed reads covering position p of a contig and kept(p) the number of those whose mask bit
+ * is set, a ROW over the inclusive interval [start, end] of one contig holds the sums, the extrema, and
+ *   capped_positions   positions with cov(p) > max_coverage (where downsampling had anything to remove)
+ *   deficit_positions  positions with kept(p) < min(cov(p), max_coverage) -- 0 for every valid answer
+ *   deficit_sum        the sum of max(0, min(cov(p), max_coverage) - kept(p))
+ * Outputs, all in host memory in both entries, each may be NULL:
+ *   contig_rows[n_contigs]  one row per contig, the whole contig; a contig of length 0 has positions == 0 and every other
+ *                           field but `contig` 0
+ *   region_rows[region_capacity], *n_region_rows_out   one row per MERGED region, contigs in id order, regions in position
+ *                           order; a capacity below the merged count (which never exceeds the number of regions passed
+ *                           in) fails with QMCP_EINVAL and a message naming the count needed
+ *   hist_in[n_bins], hist_kept[n_bins]   the number of positions in scope with depth d, counted in bin
+ *                           min(d, n_bins - 1); scope = the target positions when regions are given, every position of
+ *                           every contig otherwise; n_bins in 0 .. 4096, 0 = no histograms
+ *   stats                   reads_placed, reads_kept (placed and kept), scope_positions, deficit_positions (in scope),
+ *                           regions_in / regions_merged, position_batches, ms_report (device time)
+ * A call of more than 2^31 - 2 positions is cut at contig borders into position batches, each one pass over the reads
+ * (GRCh38: two); one contig above that fails with QMCP_ERANGE.
+ * Errors: null columns, a bad table, n_bins > 4096 and a capacity that is too small fail on the host before the context
+ * is looked at and before anything is copied or launched; a bad contig id (QMCP_EINVAL) or a bad placed read
+ * (QMCP_EREAD) is found on the device among ALL reads, and then no output buffer has been written.  A context with a
+ * pending qmcp_hip_solve_device_begin is refused.  Every number is an integer sum, minimum, maximum or count: the result
+ * is deterministic.  The context's own keep mask is left as it is. */
+typedef struct qmcp_hip_depth_row {
+    uint32_t contig, start, end;                  /* the interval, inclusive                               */
+    uint32_t min_in, max_in, min_kept, max_kept;  /* over the interval                                     */
+    uint32_t reserved;                            /* 0                                                     */
+    uint64_t positions;                           /* end - start + 1                                       */
+    uint64_t sum_in, sum_kept;                    /* sums of cov(p) and kept(p)                            */
+    uint64_t capped_positions, deficit_positions, deficit_sum;
+} qmcp_hip_depth_row;
+typedef struct qmcp_hip_depth_stats {
+    uint64_t reads_placed, reads_kept;
+    uint64_t scope_positions, deficit_positions;
+    uint32_t regions_in, regions_merged, position_batches;
+    float ms_report;                              /* HIP events on the context's stream                    */
+} qmcp_hip_depth_stats;
+int qmcp_hip_depth_report_host(qmcp_hip_ctx* ctx,
+                               const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                               uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                               const uint64_t* keep_mask /* may be NULL */, uint32_t max_coverage,
+                               const uint32_t* target_offsets /* may be NULL */, const uint32_t* target_starts,
+                               const uint32_t* target_ends, uint32_t padding, uint32_t n_bins,
+                               qmcp_hip_depth_row* contig_rows, qmcp_hip_depth_row* region_rows,
+                               uint64_t region_capacity, uint64_t* n_region_rows_out, uint64_t* hist_in,
+                               uint64_t* hist_kept, qmcp_hip_depth_stats* stats);
+/* The same with the three columns and the mask in device memory (the tables stay on the host, the outputs go to host
+ * memory); ordered after `hip_stream` (or NULL) as qmcp_hip_solve_by_contig_device is, and returns when the outputs are in
+ * host memory. */
+int qmcp_hip_depth_report_device(qmcp_hip_ctx* ctx,
+                                 const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                 uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                 const uint64_t* d_keep_mask /* may be NULL */, uint32_t max_coverage,
+                                 const uint32_t* target_offsets /* may be NULL */, const uint32_t* target_starts,
+                                 const uint32_t* target_ends, uint32_t padding, uint32_t n_bins,
+                                 qmcp_hip_depth_row* contig_rows, qmcp_hip_depth_row* region_rows,
+                                 uint64_t region_capacity, uint64_t* n_region_rows_out, uint64_t* hist_in,
+                                 uint64_t* hist_kept, void* hip_stream, qmcp_hip_depth_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
