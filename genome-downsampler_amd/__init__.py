@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_quality_host", "qmcp_hip_solve_quality_device", "qmcp_hip_solve_quality_by_contig_host",
     "qmcp_hip_solve_targets_host", "qmcp_hip_solve_targets_device",
     "qmcp_hip_depth_report_host", "qmcp_hip_depth_report_device",
+    "qmcp_hip_solve_ladder_host", "qmcp_hip_solve_ladder_device",
 )
 
 QMCP_OK = 0
@@ -41,6 +42,7 @@ PATH_UNIFORM, PATH_GENERAL, PATH_NEAR_UNIFORM = 1, 2, 3
 KIND_UNIFORM, KIND_LOW_BOTH_SIDES, KIND_HOLE, KIND_ZERO_BOTH_SIDES = 0, 1, 2, 3
 NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never kept)
 TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
+LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
 
 
 # status codes of include/qmcp_hip.h
@@ -118,6 +120,17 @@ class DepthStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LadderStats(C.Structure):
+    """qmcp_hip_ladder_stats: the levels of a coverage ladder (n_kept / ms_level: the first n_levels entries count)"""
+    _fields_ = [("n_levels", C.c_uint32), ("reserved", C.c_uint32), ("n_kept", C.c_uint64 * LADDER_MAX_LEVELS),
+                ("ms_level", C.c_float * LADDER_MAX_LEVELS), ("ms_ladder", C.c_float)]
+
+    def as_dict(self):
+        k = self.n_levels
+        return {"n_levels": k, "n_kept": list(self.n_kept[:k]), "ms_level": list(self.ms_level[:k]),
+                "ms_ladder": self.ms_ladder}
 
 
 class DepthReport:
@@ -226,6 +239,11 @@ _hip.qmcp_hip_depth_report_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c
 _hip.qmcp_hip_depth_report_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32] + \
                                              _depth_out + [C.c_void_p, C.POINTER(DepthStats)]
+_hip.qmcp_hip_solve_ladder_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p,
+                                            C.c_uint32, C.c_void_p, C.POINTER(Stats), C.POINTER(LadderStats)]
+_hip.qmcp_hip_solve_ladder_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                              C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                              C.POINTER(LadderStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -278,6 +296,11 @@ if _host is not None:
     _host.qmcp_host_downsample_bam_report.argtypes = _host.qmcp_host_downsample_bam_targets.argtypes[:-2] + \
         [C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_report.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_ladder.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                      C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                      C.c_int, _u32p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int64),
+                                                      C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_ladder.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -338,6 +361,14 @@ def indices_to_mask(indices, n_reads):
     return np.packbits(bits, bitorder="little").view(np.uint64).copy()
 
 
+def ladder_mask(levels, j):
+    """the packed keep mask (np.uint64 words, input order) of level j of a coverage ladder: K_j = {i : levels[i] > j}"""
+    levels = np.ascontiguousarray(levels, dtype=np.uint8)
+    bits = np.zeros(mask_words(levels.size) * 64, dtype=np.uint8)
+    bits[:levels.size] = levels > int(j)
+    return np.packbits(bits, bitorder="little").view(np.uint64).copy()
+
+
 def _contig_tables(n_reads, contig_read_offsets, contig_lengths):
     if contig_read_offsets is None:
         lengths = np.atleast_1d(np.asarray(contig_lengths, dtype=np.uint32))
@@ -359,6 +390,7 @@ class Solver:
         self.last_stats = None
         self.last_quality_stats = None
         self.last_target_stats = None
+        self.last_ladder_stats = None
 
     def close(self):
         if self._ctx:
@@ -476,6 +508,38 @@ class Solver:
                                                     C.c_void_p(stream), C.byref(st)))
         self.last_stats = st
         return st
+
+    def solve_ladder(self, starts, ends, contig_ids, contig_lengths, coverages):
+        """solve_by_contig at several falling coverages in one call (qmcp_hip_solve_ladder_host): level 0 is
+        solve_by_contig at coverages[0], every further level is solved on the reads the level above kept, so the levels
+        are nested.  -> one uint8 per read in INPUT order, the number of levels that keep it (ladder_mask(levels, j) is
+        level j's mask).  Level 0's stats go to last_stats, the levels' to last_ladder_stats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        cov = np.atleast_1d(np.ascontiguousarray(coverages, dtype=np.uint32))
+        levels = np.zeros(max(n, 1), dtype=np.uint8)
+        st, ls = Stats(), LadderStats()
+        _check(_hip.qmcp_hip_solve_ladder_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                               lengths.size, _p32(cov), cov.size, C.c_void_p(levels.ctypes.data),
+                                               C.byref(st), C.byref(ls)))
+        self.last_stats, self.last_ladder_stats = st, ls
+        return levels[:n]
+
+    def solve_ladder_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, coverages, d_levels,
+                            stream=0):
+        """the same on device pointers (ints); the level bytes (n_reads of them, input order) are written to d_levels.
+        Returns the ladder stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        cov = np.atleast_1d(np.ascontiguousarray(coverages, dtype=np.uint32))
+        st, ls = Stats(), LadderStats()
+        _check(_hip.qmcp_hip_solve_ladder_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                 C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                 _p32(cov), cov.size, C.c_void_p(d_levels), C.c_void_p(stream),
+                                                 C.byref(st), C.byref(ls)))
+        self.last_stats, self.last_ladder_stats = st, ls
+        return ls
 
     @staticmethod
     def _target_tables(n_contigs, target_offsets, target_starts, target_ends):
@@ -1148,7 +1212,8 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
 
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
-                   targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0):
+                   targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
+                   ladder_out=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1161,8 +1226,46 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     report (a path; BamApiConfig::depth_report_filepath, with report_bins histogram bins): after the output has been
     written, the depth report (write_depth_report's TSV) of the reads the solve saw -- those that passed the ingest
     filters -- against the FINAL kept set (after mate completion), with max_coverage and, if given, the targets and
-    their padding as regions; needs per_reference=True (ValueError otherwise).  None: nothing changes"""
+    their padding as regions; needs per_reference=True (ValueError otherwise).  None: nothing changes.
+    ladder (a list of coverages strictly below max_coverage and strictly decreasing; BamApiConfig::coverage_ladder) with
+    ladder_out (a path template holding "{M}"): a titration in one call.  The level at max_coverage goes to out_path as
+    always; every further level is solved on the reads the level above kept, completed by find_pairs (monotone, so the
+    files stay nested) and written to ladder_out with {M} replaced by its coverage.  Returns the list of written
+    counts, out_path's first.  Needs per_reference=True; not together with targets, report or
+    "quasi-mcp-hip-quality" (ValueError).  Amplicon FILTER at ingest works as before.  None: nothing changes"""
     _need_host()
+    if ladder is not None:
+        levels = [int(m) for m in ladder]
+        if not per_reference:
+            raise ValueError("a coverage ladder needs per_reference=True")
+        if ladder_out is None or "{M}" not in str(ladder_out):
+            raise ValueError("ladder_out must be a path template holding {M}")
+        if targets or report:
+            raise ValueError("a coverage ladder does not go together with targets or a depth report")
+        if solver_uses_quality(solver_name):
+            raise ValueError("a coverage ladder does not take a solver that grades by quality")
+        if not levels or levels[0] >= int(max_coverage):
+            raise ValueError("the levels of a coverage ladder must be strictly below max_coverage")
+        if any(b >= a for a, b in zip(levels, levels[1:])) or levels[-1] < 1:
+            raise ValueError("the levels of a coverage ladder must be strictly decreasing and >= 1")
+        if (bed or tsv) and not amplicons_by_reference:
+            raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
+        lv = np.array(levels, dtype=np.uint32)
+        counts = (C.c_int64 * (len(levels) + 1))()
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_ladder(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
+            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)), _p32(lv), lv.size,
+            str(ladder_out).encode(), counts, err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return [int(c) for c in counts[:n]]
     if (bed or tsv) and not (per_reference and amplicons_by_reference):
         raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
     if report:

@@ -7,7 +7,12 @@
 //   4. by_contig_plan.h packs the contigs into batches within one call's limits; per batch, its columns are gathered in
 //      grouped order, solved by the ordinary multi-contig solve, and its mask ORed back into input order
 // Grouping happens once; a batch only gathers its own reads.
+// A coverage ladder (api/ladder.inc.hip) is this call with further levels run inside each batch, on its gathered columns.
 namespace {
+
+struct LadderRun;
+int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, uint32_t nb, const uint64_t* roff,
+                           const uint32_t* lengths, uint32_t n_contigs);
 
 // the batches' stats as one: counts and times summed, the route of the batch with the most reads
 void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, bool largest) {
@@ -40,7 +45,7 @@ void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, boo
 
 int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                               uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, uint32_t M, uint64_t* d_mask,
-                              qmcp_hip_stats* stats) {
+                              qmcp_hip_stats* stats, LadderRun* ladder = nullptr) {
     if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
     if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
     if (n64 > (1ull << 31))
@@ -152,6 +157,7 @@ int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
             qmcp::launch_bc_scatter_mask(st, (const uint64_t*)c->bc_mask.p, bsorted, nb, d_mask);
         }
         HIP_TRY(hipGetLastError());
+        if (ladder) TRY(ladder_levels_of_batch(c, *ladder, bsorted, nb, roff.data(), lengths + bt.first_contig, bt.n_contigs));
         add_batch_stats(sum, bs, first, b == largest);
         first = false;
     }

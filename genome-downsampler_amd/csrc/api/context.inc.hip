@@ -133,6 +133,10 @@ struct qmcp_hip_ctx {
     // depth report (api/depth_report.inc.hip): a batch's event words, its tables (lengths, offsets, the two interval
     // tables), the rows' accumulators, the histograms, the chunk sums, and the read counts + validation word
     DevBuf dr_ev, dr_tab, dr_acc, dr_hist, dr_sums, dr_cnt;
+    // coverage ladder (api/ladder.inc.hip): the two sets of compacted columns (starts, ends, input indices) that
+    // ping-pong between levels, the scanned word popcounts of a level's mask and their spine, the two offset tables, the
+    // host entry's level bytes and the device entry's first-level mask
+    DevBuf ld_starts[2], ld_ends[2], ld_orig[2], ld_words, ld_spine, ld_offs[2], ld_levels, ld_mask0;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

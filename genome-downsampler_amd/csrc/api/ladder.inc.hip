@@ -1,0 +1,194 @@
+// ladder.inc.hip -- part of qmcp_api.hip (one translation unit).
+// qmcp_hip_solve_ladder_host / _device: the by-contig solve at coverages[0], then level j + 1 solved on the reads level j
+// kept, down the list; one byte per read says how many levels keep it.  The grouping of solve_by_contig_on_device runs
+// once per call; the further levels run inside each batch (ladder_levels_of_batch), on its gathered columns:
+//   1. k_ladder_levels writes levels[origin] = j + 1 for the reads level j kept (the byte array was zeroed first)
+//   2. k_word_popcounts -> exclusive scan of the level's mask; k_ladder_offsets evaluates the kept rank at each contig's
+//      offset: the next level's contig_read_offsets, n_contigs + 1 values, read back once per level
+//   3. k_ladder_compact writes the kept reads' starts, ends and origins (input indices) into the other set of buffers
+//   4. solve_on_device on the compacted columns at the next coverage; its mask goes to bc_mask again
+// Buffers, all the ladder's own: two sets of compacted columns (ld_starts / ld_ends / ld_orig) that ping-pong from
+// level to level, the scanned popcounts (ld_words) and their spine (ld_spine), two offset tables (ld_offs), the host
+// entry's level bytes (ld_levels) and the device entry's first-level mask (ld_mask0).  Nothing solve_on_device owns is
+// touched: a solve sizes and frees its arena as it likes.  bc_mask is the by-contig solve's and holds a batch's mask from
+// one solve to the next; every use of it here is queued on the stream between the two.
+namespace {
+
+struct LadderRun {
+    const uint32_t* coverages = nullptr;
+    uint32_t n_levels = 0;
+    uint8_t* d_levels = nullptr;
+    qmcp_hip_ladder_stats ls;
+};
+
+int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, uint32_t nb, const uint64_t* roff,
+                           const uint32_t* lengths, uint32_t n_contigs) {
+    hipStream_t st = c->stream;
+    EventPair ev_a(c), ev_b(c);
+    if (!ev_a.a || !ev_a.b || !ev_b.a || !ev_b.b) return fail(QMCP_EHIP, "event creation failed");
+    const size_t tab = (size_t)n_contigs + 1;
+    std::vector<uint32_t> offs32(tab), ranks(tab);
+    std::vector<uint64_t> cur(roff, roff + tab), next;
+    if (ld.n_levels > 1) {
+        TRY(ensure(c, c->ld_offs[0], tab * sizeof(uint32_t)));
+        TRY(ensure(c, c->ld_offs[1], tab * sizeof(uint32_t)));
+        const size_t words0 = ((size_t)nb + 63) / 64;
+        TRY(ensure(c, c->ld_words, (words0 + 2) * sizeof(uint32_t)));
+        TRY(ensure(c, c->ld_spine, (size_t)(qmcp::scan_spine_entries((uint32_t)words0 + 1) + 1) * sizeof(uint32_t) + 16));
+        for (size_t k = 0; k < tab; ++k) offs32[k] = (uint32_t)roff[k];  // (a batch holds at most 2^30 reads)
+        HIP_TRY(hipMemcpyAsync(c->ld_offs[0].p, offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    // the level whose mask is in bc_mask: its reads, their columns and their origins
+    uint32_t n = nb;
+    const uint32_t* d_s = (const uint32_t*)c->bc_starts.p;
+    const uint32_t* d_e = (const uint32_t*)c->bc_ends.p;
+    const void* d_o = bsorted;
+    const uint64_t* d_m = (const uint64_t*)c->bc_mask.p;
+    bool compact_timed = false;
+    for (uint32_t j = 0; j < ld.n_levels; ++j) {
+        const bool first = j == 0;
+        const bool last = j + 1 == ld.n_levels;
+        HIP_TRY(hipEventRecord(ev_a.a, st));
+        {
+            KernelSpan sp(c, "k_ladder_levels");
+            qmcp::launch_ladder_levels(st, first, d_m, d_o, n, j + 1, ld.d_levels);
+        }
+        if (!last) {
+            const uint32_t words = (n + 63u) / 64u;
+            KernelSpan sp(c, "ladder offsets(popcounts, scan, k_ladder_offsets)");
+            qmcp::launch_word_popcounts(st, d_m, words, (uint32_t*)c->ld_words.p);
+            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->ld_words.p, words, (uint32_t*)c->ld_words.p,
+                                        (uint32_t*)c->ld_spine.p, true);
+            qmcp::launch_ladder_offsets(st, (const uint32_t*)c->ld_offs[j & 1u].p, n_contigs, d_m,
+                                        (const uint32_t*)c->ld_words.p, (uint32_t*)c->ld_offs[(j & 1u) ^ 1u].p);
+        }
+        HIP_TRY(hipEventRecord(ev_a.b, st));
+        HIP_TRY(hipGetLastError());
+        if (!last)
+            HIP_TRY(hipMemcpyAsync(ranks.data(), c->ld_offs[(j & 1u) ^ 1u].p, tab * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                   st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ld.ls.ms_ladder += elapsed(ev_a.a, ev_a.b);
+        if (compact_timed) ld.ls.ms_ladder += elapsed(ev_b.a, ev_b.b);
+        compact_timed = false;
+        if (last) break;
+        if (qmcp::ladder_next_offsets(cur.data(), ranks.data(), n_contigs, next) != QMCP_OK)
+            return fail(QMCP_EHIP, "ladder level %u: the kept ranks do not fit the contig offsets", j);
+        const uint32_t n_next = ranks[n_contigs];
+        if (n_next == 0) break;  // (n == 0 only: a level at >= 1 keeps a read of every contig that has one)
+        const uint32_t set = j & 1u;
+        const size_t cb = (size_t)n_next * sizeof(uint32_t);
+        TRY(ensure(c, c->ld_starts[set], cb));
+        TRY(ensure(c, c->ld_ends[set], cb));
+        TRY(ensure(c, c->ld_orig[set], cb));
+        HIP_TRY(hipEventRecord(ev_b.a, st));
+        {
+            KernelSpan sp(c, "k_ladder_compact");
+            qmcp::launch_ladder_compact(st, first, d_s, d_e, d_o, d_m, (const uint32_t*)c->ld_words.p, n,
+                                        (uint32_t*)c->ld_starts[set].p, (uint32_t*)c->ld_ends[set].p,
+                                        (uint32_t*)c->ld_orig[set].p);
+        }
+        HIP_TRY(hipEventRecord(ev_b.b, st));
+        HIP_TRY(hipGetLastError());
+        compact_timed = true;
+        n = n_next;
+        d_s = (const uint32_t*)c->ld_starts[set].p;
+        d_e = (const uint32_t*)c->ld_ends[set].p;
+        d_o = c->ld_orig[set].p;
+        cur.swap(next);
+        qmcp_hip_stats bs;
+        std::memset(&bs, 0, sizeof(bs));
+        TRY(solve_on_device(c, d_s, d_e, cur.data(), lengths, n_contigs, n, ld.coverages[j + 1], (uint64_t*)c->bc_mask.p,
+                            &bs));
+        ld.ls.n_kept[j + 1] += bs.n_kept;
+        ld.ls.ms_level[j + 1] += bs.ms_total;
+    }
+    return QMCP_OK;
+}
+
+// what both entries check before anything is copied or launched
+int check_ladder_call(const uint32_t* coverages, uint32_t n_levels) {
+    uint32_t bad = 0;
+    if (qmcp::check_ladder_coverages(coverages, n_levels, &bad) == QMCP_OK) return QMCP_OK;
+    if (!coverages) return fail(QMCP_EINVAL, "coverages missing");
+    if (n_levels == 0 || n_levels > QMCP_LADDER_MAX_LEVELS)
+        return fail(QMCP_EINVAL, "n_levels %u is not in 1 .. %u", n_levels, (unsigned)QMCP_LADDER_MAX_LEVELS);
+    if (coverages[bad] == 0) return fail(QMCP_EINVAL, "coverages[%u] is 0: every level needs a coverage >= 1", bad);
+    return fail(QMCP_EINVAL, "coverages must fall strictly: coverages[%u] = %u is not below coverages[%u] = %u", bad,
+                coverages[bad], bad - 1, coverages[bad - 1]);
+}
+
+int solve_ladder_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                           uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const uint32_t* coverages,
+                           uint32_t n_levels, uint64_t* d_mask0, uint8_t* d_levels, qmcp_hip_stats* stats,
+                           qmcp_hip_ladder_stats* lstats) {
+    LadderRun ld;
+    ld.coverages = coverages;
+    ld.n_levels = n_levels;
+    ld.d_levels = d_levels;
+    std::memset(&ld.ls, 0, sizeof(ld.ls));
+    ld.ls.n_levels = n_levels;
+    if (lstats) *lstats = ld.ls;
+    // (the bytes are cleared before the reads are validated, as solve_by_contig_on_device clears its mask)
+    if (n64 && n64 <= (1ull << 31)) HIP_TRY(hipMemsetAsync(d_levels, 0, (size_t)n64, c->stream));
+    qmcp_hip_stats plain;
+    std::memset(&plain, 0, sizeof(plain));
+    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, coverages[0], d_mask0, &plain, &ld));
+    ld.ls.n_kept[0] = plain.n_kept;
+    ld.ls.ms_level[0] = plain.ms_total;
+    if (stats) *stats = plain;
+    if (lstats) *lstats = ld.ls;
+    return QMCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmcp_hip_solve_ladder_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                               uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                               const uint32_t* coverages, uint32_t n_levels, uint8_t* levels_out, qmcp_hip_stats* stats,
+                               qmcp_hip_ladder_stats* lstats) {
+    TRY(check_ladder_call(coverages, n_levels));
+    TRY(use_device(c));
+    if (n_reads && (!starts || !ends || !contig_ids || !levels_out)) return fail(QMCP_EINVAL, "null buffer");
+    if (n_reads > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n_reads);
+    const size_t nb = (size_t)n_reads * sizeof(uint32_t);
+    const size_t words = (size_t)((n_reads + 63) / 64);
+    TRY(ensure(c, c->in_starts, nb));
+    TRY(ensure(c, c->in_ends, nb));
+    TRY(ensure(c, c->in_aux0, nb));
+    TRY(ensure(c, c->mask, words * sizeof(uint64_t)));
+    TRY(ensure(c, c->ld_levels, (size_t)n_reads));
+    c->mask_reads = 0;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(c->in_starts.p, starts, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(solve_ladder_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
+                               (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, coverages, n_levels,
+                               (uint64_t*)c->mask.p, (uint8_t*)c->ld_levels.p, stats, lstats));
+    if (n_reads) HIP_TRY(hipMemcpyAsync(levels_out, c->ld_levels.p, (size_t)n_reads, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mask_reads = n_reads;
+    return QMCP_OK;
+}
+
+int qmcp_hip_solve_ladder_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends,
+                                 const uint32_t* d_contig_ids, uint64_t n_reads, const uint32_t* contig_lengths,
+                                 uint32_t n_contigs, const uint32_t* coverages, uint32_t n_levels, uint8_t* d_levels_out,
+                                 void* hip_stream, qmcp_hip_stats* stats, qmcp_hip_ladder_stats* lstats) {
+    TRY(check_ladder_call(coverages, n_levels));
+    TRY(use_device(c));
+    if (n_reads && (!d_starts || !d_ends || !d_contig_ids || !d_levels_out)) return fail(QMCP_EINVAL, "null buffer");
+    if (n_reads > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n_reads);
+    TRY(ensure(c, c->ld_mask0, (size_t)((n_reads + 63) / 64) * sizeof(uint64_t)));
+    TRY(order_after(c, hip_stream));
+    return solve_ladder_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, coverages,
+                                  n_levels, (uint64_t*)c->ld_mask0.p, d_levels_out, stats, lstats);
+}
+
+}  // extern "C"

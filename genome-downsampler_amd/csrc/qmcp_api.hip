@@ -26,6 +26,7 @@
 #include "qmcp_hip.h"
 #include "qmcp_kernels.h"
 #include "by_contig_plan.h"
+#include "ladder_plan.h"
 #include "amplicon_table.h"
 #include "target_table.h"
 
@@ -47,6 +48,8 @@
 //                       the by-contig solve (and quality pass) of the projected on-target reads, the mask expanded back
 //   depth_report        depth before and after a keep mask, per contig and per region, with histograms: position batches,
 //                       the reads' events, the positions pass, rows and statistics assembled on the host
+//   ladder              several falling coverages in one by-contig call: every further level solved on the reads the level
+//                       above kept, inside each batch; one byte per read counts the levels that keep it
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -60,3 +63,4 @@
 #include "api/quality.inc.hip"
 #include "api/targets.inc.hip"
 #include "api/depth_report.inc.hip"
+#include "api/ladder.inc.hip"

@@ -261,6 +261,19 @@ void launch_bc_gather(hipStream_t st, const void* sorted, uint32_t n, const uint
                       uint32_t* starts_out, uint32_t* ends_out);
 void launch_bc_scatter_mask(hipStream_t st, const uint64_t* batch_mask, const void* sorted, uint32_t n, uint64_t* mask);
 
+// the coverage ladder between two levels of a batch (kernels/ladder.inc.hip; api/ladder.inc.hip drives them): the stable
+// compaction of the reads `mask` keeps (word_base: its scanned word popcounts, the total behind the last word) with an
+// origin column -- origin_in is the grouping's Rec{key, index} array when `first`, the previous origin column otherwise
+// --, the kept rank at each of the n_contigs + 1 contig offsets (the next level's offsets), and levels[origin] = level
+// for the kept reads of a level
+void launch_ladder_compact(hipStream_t st, bool first, const uint32_t* starts, const uint32_t* ends,
+                           const void* origin_in, const uint64_t* mask, const uint32_t* word_base, uint32_t n,
+                           uint32_t* starts_c, uint32_t* ends_c, uint32_t* origin_c);
+void launch_ladder_offsets(hipStream_t st, const uint32_t* offs, uint32_t n_contigs, const uint64_t* mask,
+                           const uint32_t* word_base, uint32_t* next);
+void launch_ladder_levels(hipStream_t st, bool first, const uint64_t* mask, const void* origin_in, uint32_t n,
+                          uint32_t level, uint8_t* levels);
+
 // pairs of several contigs against the amplicons of their own contig (kernels/amplicon_by_contig.inc.hip; api/
 // amplicon_by_contig.inc.hip drives them): the FILTER (amp_offs == NULL: no amplicon predicate; the table of
 // amplicon_table.h otherwise, n_amp entries; err as launch_bc_keys) into one bit per pair, and the compaction of the

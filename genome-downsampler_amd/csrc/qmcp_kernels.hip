@@ -31,6 +31,8 @@
 //   near_uniform             one dominant span + a few shorter reads: the one-span sweep over the regular reads, the
 //                            exceptions verified against it and selected one event at a time
 //   by_contig                reads in any order with a contig id each: sort keys, contig bounds, gather, mask scatter-back
+//   ladder                   the coverage ladder between two levels: compaction of the kept reads with their input index,
+//                            the next level's contig offsets, the level bytes
 //   amplicon_by_contig       the FILTER of pairs against the amplicons of their own contig, compaction with the ids
 //   quality_cells            the quality pass: within every (contig, start, end) cell, the plain solve's count of reads
 //                            chosen by quality descending, then read index (composite keys, LSD radix, segmented choice)
@@ -69,6 +71,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/pass_major.inc.hip"
 #include "kernels/near_uniform.inc.hip"
 #include "kernels/by_contig.inc.hip"
+#include "kernels/ladder.inc.hip"
 #include "kernels/amplicon_by_contig.inc.hip"
 #include "kernels/quality_cells.inc.hip"
 #include "kernels/targets.inc.hip"

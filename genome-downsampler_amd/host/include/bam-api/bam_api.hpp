@@ -52,6 +52,11 @@ struct BamApiConfig {
     // Needs per_reference (std::invalid_argument otherwise).  Empty: no report, nothing changes.
     std::filesystem::path depth_report_filepath;
     std::uint32_t depth_report_bins = 0;
+    // Coverage ladder: further coverages below the solve's max_coverage, strictly decreasing, each solved on the reads
+    // the level above kept (QuasiMcpHipSolver::solve_ladder / qmcp_hip_solve_ladder_host), so the outputs are nested.
+    // Needs per_reference; not together with targets or a depth report (std::invalid_argument otherwise).  Empty: no
+    // ladder, nothing changes.
+    std::vector<std::uint32_t> coverage_ladder;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -84,6 +89,8 @@ class BamApi {
     // BamApiConfig::depth_report_filepath (empty: none) and depth_report_bins
     const std::filesystem::path& depth_report_filepath() const { return depth_report_filepath_; }
     std::uint32_t depth_report_bins() const { return depth_report_bins_; }
+    // BamApiConfig::coverage_ladder (empty: none)
+    const std::vector<std::uint32_t>& coverage_ladder() const { return coverage_ladder_; }
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -111,6 +118,7 @@ class BamApi {
     bool has_targets_ = false;
     std::filesystem::path depth_report_filepath_;
     std::uint32_t depth_report_bins_ = 0;
+    std::vector<std::uint32_t> coverage_ladder_;
     void read_bam_into(PairedReads& reads);
 };
 

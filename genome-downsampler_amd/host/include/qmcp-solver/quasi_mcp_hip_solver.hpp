@@ -57,6 +57,14 @@ class QuasiMcpHipSolver : public Solver {
     // std::terminate on a device failure, like solve()
     void depth_report(std::uint32_t required_cover, bam_api::BamApi& bam_api, const std::vector<bam_api::ReadIndex>& kept,
                       std::uint32_t n_bins, DepthReport& out);
+    // Coverage ladder for the reads of a per-reference BamApi: the solve at required_cover, then at each of `levels`
+    // (strictly below required_cover, strictly decreasing, >= 1; std::invalid_argument otherwise) on the reads the
+    // level above kept, in one qmcp_hip_solve_ladder_host call.  One ascending Solution per level, required_cover's
+    // first; each is a subset of the one before.  Mate completion is left to the caller (BamApi::find_pairs is
+    // monotone, so completed levels stay nested).  std::terminate on a device failure, like solve()
+    std::vector<std::unique_ptr<Solution>> solve_ladder(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                                        const std::vector<std::uint32_t>& levels);
+    const qmcp_hip_ladder_stats& last_ladder_stats() const { return lstats_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -73,6 +81,7 @@ class QuasiMcpHipSolver : public Solver {
                                             const bam_api::TargetRegions& targets, bool with_qualities,
                                             std::chrono::steady_clock::time_point t0);
     qmcp_hip_target_stats tstats_{};
+    qmcp_hip_ladder_stats lstats_{};
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves
     int device_ = 0;

@@ -68,6 +68,20 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     if (amplicons_by_reference_ && !per_reference_)
         throw std::invalid_argument("amplicons_by_reference needs per_reference: amplicons are matched to the "
                                     "references a per-reference ingest keeps");
+    if (!config.coverage_ladder.empty()) {
+        if (!per_reference_)
+            throw std::invalid_argument("a coverage ladder needs per_reference: its levels are solved one reference at "
+                                        "a time");
+        if (!config.targets_filepath.empty())
+            throw std::invalid_argument("a coverage ladder does not take targets");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("a coverage ladder does not take a depth report");
+        for (std::size_t j = 1; j < config.coverage_ladder.size(); ++j)
+            if (config.coverage_ladder[j] >= config.coverage_ladder[j - 1])
+                throw std::invalid_argument("the levels of a coverage ladder must be strictly decreasing");
+        if (config.coverage_ladder.back() == 0) throw std::invalid_argument("a coverage ladder ends at a coverage >= 1");
+        coverage_ladder_ = config.coverage_ladder;
+    }
     if (!config.depth_report_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a depth report needs per_reference: its rows are the references a per-reference "

@@ -647,6 +647,62 @@ std::int64_t qmcp_host_downsample_bam_report(const char* solver_name, const char
     }
 }
 
+// qmcp_host_downsample_bam_by_reference with a coverage ladder: BamApiConfig {coverage_ladder} on top of the amplicon
+// fields (bed / tsv may be NULL; FILTER acts at ingest as before).  One ingest and one qmcp_hip_solve_ladder_host call;
+// the level at max_coverage goes to out_path, level `levels[j]` through find_pairs to out_template with its "{M}"
+// replaced by the coverage.  written_out (1 + n_levels entries) receives each file's record count, out_path's first.
+// Returns the number of files written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the
+// configuration is refused: no per_reference, a template without "{M}", levels not strictly below max_coverage and
+// strictly decreasing, a solver that grades by quality or has no ladder.
+std::int64_t qmcp_host_downsample_bam_ladder(const char* solver_name, const char* in_path, const char* out_path,
+                                             const char* filtered_path, std::uint32_t max_coverage,
+                                             std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
+                                             const char* tsv, int amplicon_mode, int per_reference,
+                                             int amplicons_by_reference, const std::uint32_t* levels,
+                                             std::uint32_t n_levels, const char* out_template,
+                                             std::int64_t* written_out, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
+    cfg.per_reference = per_reference != 0;
+    cfg.amplicons_by_reference = amplicons_by_reference != 0;
+    if (levels != nullptr) cfg.coverage_ladder.assign(levels, levels + n_levels);
+    try {
+        const std::string tmpl = out_template ? out_template : "";
+        const std::size_t at = tmpl.find("{M}");
+        if (cfg.coverage_ladder.empty()) throw std::invalid_argument("a coverage ladder needs at least one level");
+        if (at == std::string::npos) throw std::invalid_argument("the ladder's output template has no {M}");
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("a coverage ladder does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no coverage ladder");
+        bam_api::BamApi api(in_path, cfg);
+        auto solutions = hip->solve_ladder(max_coverage, api, api.coverage_ladder());
+        for (std::size_t j = 0; j < solutions.size(); ++j) {
+            std::string path = out_path;
+            if (j > 0) {
+                path = tmpl;
+                path.replace(at, 3, std::to_string(api.coverage_ladder()[j - 1]));
+            }
+            std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solutions[j]);
+            const std::uint32_t written = api.write_paired_reads(path, paired);
+            if (written_out) written_out[j] = written;
+        }
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return (std::int64_t)solutions.size();
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

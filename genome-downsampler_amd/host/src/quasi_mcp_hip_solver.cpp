@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <fstream>
 #include <limits>
+#include <stdexcept>
 #include <vector>
 
 namespace qmcp {
@@ -130,6 +131,52 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_targets(std::uint32_t require
         if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
     }
     return expand_kept(n, t0);
+}
+
+std::vector<std::unique_ptr<Solution>> QuasiMcpHipSolver::solve_ladder(std::uint32_t required_cover,
+                                                                       bam_api::BamApi& bam_api,
+                                                                       const std::vector<std::uint32_t>& levels) {
+    std::vector<std::uint32_t> coverages{required_cover};
+    coverages.insert(coverages.end(), levels.begin(), levels.end());
+    if (coverages.size() > QMCP_LADDER_MAX_LEVELS)
+        throw std::invalid_argument("a coverage ladder has at most " + std::to_string(QMCP_LADDER_MAX_LEVELS - 1) +
+                                    " levels below max_coverage");
+    for (std::size_t j = 1; j < coverages.size(); ++j)
+        if (coverages[j] >= coverages[j - 1])
+            throw std::invalid_argument(j == 1 ? "the levels of a coverage ladder must be strictly below max_coverage"
+                                               : "the levels of a coverage ladder must be strictly decreasing");
+    if (coverages.back() == 0) throw std::invalid_argument("a coverage ladder ends at a coverage >= 1");
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const std::size_t n = reads.start_inds.size();
+    if (!reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("a coverage ladder needs per_reference reads (one contig id each)");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint8_t> bytes(n, 0);
+    const int rc = qmcp_hip_solve_ladder_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                              reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                              coverages.data(), (std::uint32_t)coverages.size(), bytes.data(), &stats_,
+                                              &lstats_);
+    if (rc != QMCP_OK) die("qmcp_hip_solve_ladder_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    std::vector<std::unique_ptr<Solution>> out;
+    for (std::size_t j = 0; j < coverages.size(); ++j) {
+        auto kept = std::make_unique<Solution>();
+        kept->reserve(lstats_.n_kept[j]);
+        for (std::size_t i = 0; i < n; ++i)
+            if (bytes[i] > j) kept->push_back(i);
+        out.push_back(std::move(kept));
+    }
+    return out;
 }
 
 void QuasiMcpHipSolver::depth_report(std::uint32_t required_cover, bam_api::BamApi& bam_api,

@@ -575,6 +575,45 @@ int qmcp_hip_depth_report_device(qmcp_hip_ctx* ctx,
                                  uint64_t region_capacity, uint64_t* n_region_rows_out, uint64_t* hist_in,
                                  uint64_t* hist_kept, void* hip_stream, qmcp_hip_depth_stats* stats);
 
+/* Coverage ladder: the same reads at several falling coverages in one call -- a titration (100x, 50x, 30x, 10x of one
+ * sample).  Reads, contig_ids, contig_lengths / n_contigs and limits are those of qmcp_hip_solve_by_contig_host.
+ * coverages[0] > coverages[1] > ... > coverages[n_levels - 1] >= 1, 1 <= n_levels <= QMCP_LADDER_MAX_LEVELS.
+ * Definition: K_0 is the mask qmcp_hip_solve_by_contig_host returns for the call at coverages[0]; K_j is the mask it
+ * returns at coverages[j] for the reads of K_(j-1) ALONE, in input order with their contig ids, expressed over the input
+ * indices.  So K_0 >= K_1 >= ... (the levels are nested), and every K_j is valid for the ORIGINAL reads:
+ * cov_Kj(p) >= min(cov_K(j-1)(p), coverages[j]) >= min(cov(p), coverages[j]) because coverages[j] < coverages[j - 1].
+ * Output: one byte per read, levels[i] = the number of levels that keep read i (0 .. n_levels), K_j = {i : levels[i] > j};
+ * unplaced reads get 0.  levels_out: n_reads bytes in INPUT order, fully overwritten.
+ * How: the reads are grouped by contig once; inside each batch the first level is the plain solve, and every further
+ * level is a stable compaction of the kept reads (with their input indices) and a solve of the compacted columns.
+ * Errors: n_levels == 0 or > QMCP_LADDER_MAX_LEVELS, coverages == NULL, a coverage of 0 and a list that does not fall
+ * strictly fail with QMCP_EINVAL on the host, before the context is looked at and before anything is copied or launched:
+ * levels_out is not written.  A bad contig id (QMCP_EINVAL) or a bad read (QMCP_EREAD) is found on the device as in
+ * qmcp_hip_solve_by_contig_host; by then the device bytes (d_levels_out, or the context's own for the host entry) have
+ * been cleared -- they stay all zero, and the host entry does not write levels_out.
+ * stats (may be NULL) are those of level 0: they equal the plain by-contig call at coverages[0].  lstats (may be NULL):
+ * the levels.  The host entry leaves K_0 in the context, for qmcp_hip_kept_indices_host and qmcp_hip_complete_pairs_host.
+ * The device entry takes the three columns and the bytes in device memory (contig_lengths and coverages stay on the
+ * host), is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the work has completed. */
+#define QMCP_LADDER_MAX_LEVELS 16
+typedef struct qmcp_hip_ladder_stats {
+    uint32_t n_levels, reserved;
+    uint64_t n_kept[QMCP_LADDER_MAX_LEVELS];   /* |K_j|                                                               */
+    float ms_level[QMCP_LADDER_MAX_LEVELS];    /* device time per level, level 0 = the plain solve                    */
+    float ms_ladder;                           /* everything the ladder adds around the solves: level bytes, popcounts,
+                                                  scans, offsets, compactions                                         */
+} qmcp_hip_ladder_stats;
+int qmcp_hip_solve_ladder_host(qmcp_hip_ctx* ctx,
+                               const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                               uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                               const uint32_t* coverages, uint32_t n_levels, uint8_t* levels_out,
+                               qmcp_hip_stats* stats, qmcp_hip_ladder_stats* lstats);
+int qmcp_hip_solve_ladder_device(qmcp_hip_ctx* ctx,
+                                 const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                 uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                 const uint32_t* coverages, uint32_t n_levels, uint8_t* d_levels_out,
+                                 void* hip_stream, qmcp_hip_stats* stats, qmcp_hip_ladder_stats* lstats);
+
 #ifdef __cplusplus
 }
 #endif
