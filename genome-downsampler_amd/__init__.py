@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_targets_host", "qmcp_hip_solve_targets_device",
     "qmcp_hip_depth_report_host", "qmcp_hip_depth_report_device",
     "qmcp_hip_solve_ladder_host", "qmcp_hip_solve_ladder_device",
+    "qmcp_hip_solve_stratified_host", "qmcp_hip_solve_stratified_device",
 )
 
 QMCP_OK = 0
@@ -43,6 +44,8 @@ KIND_UNIFORM, KIND_LOW_BOTH_SIDES, KIND_HOLE, KIND_ZERO_BOTH_SIDES = 0, 1, 2, 3
 NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never kept)
 TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
 LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
+NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
+STRATUM_TALLY_TILE = 1024  # qmcp::kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces
 
 
 # status codes of include/qmcp_hip.h
@@ -131,6 +134,14 @@ class LadderStats(C.Structure):
         k = self.n_levels
         return {"n_levels": k, "n_kept": list(self.n_kept[:k]), "ms_level": list(self.ms_level[:k]),
                 "ms_ladder": self.ms_ladder}
+
+
+class StratumRow(C.Structure):
+    """qmcp_hip_stratum_row: a stratum's placed reads, how many of them are kept, and the bases of both"""
+    _fields_ = [("n_reads", C.c_uint64), ("n_kept", C.c_uint64), ("bases_in", C.c_uint64), ("bases_kept", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class DepthReport:
@@ -244,6 +255,11 @@ _hip.qmcp_hip_solve_ladder_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c
 _hip.qmcp_hip_solve_ladder_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
                                               C.POINTER(LadderStats)]
+_hip.qmcp_hip_solve_stratified_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32,
+                                                _u32p, C.c_uint32, _u64p, C.POINTER(StratumRow), C.POINTER(Stats)]
+_hip.qmcp_hip_solve_stratified_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                  _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
+                                                  C.POINTER(StratumRow), C.c_void_p, C.POINTER(Stats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -301,6 +317,17 @@ if _host is not None:
                                                       C.c_int, _u32p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int64),
                                                       C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_ladder.restype = C.c_int64
+    _host.qmcp_host_read_bam_stratified.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, _u64p,
+                                                    _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_uint8), _u32p, _u32p,
+                                                    C.c_uint64, _u64p, C.POINTER(C.c_uint64), C.c_uint64, _u32p,
+                                                    C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t,
+                                                    C.POINTER(C.c_uint64), C.c_int, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_read_bam_stratified.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_stratified.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                          C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_char_p,
+                                                          C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_char_p,
+                                                          C.c_size_t]
+    _host.qmcp_host_downsample_bam_stratified.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -391,6 +418,7 @@ class Solver:
         self.last_quality_stats = None
         self.last_target_stats = None
         self.last_ladder_stats = None
+        self.last_stratum_rows = None
 
     def close(self):
         if self._ctx:
@@ -540,6 +568,43 @@ class Solver:
                                                  C.byref(st), C.byref(ls)))
         self.last_stats, self.last_ladder_stats = st, ls
         return ls
+
+    def solve_stratified(self, starts, ends, contig_ids, strata, contig_lengths, max_coverages):
+        """one coverage cap per stratum (qmcp_hip_solve_stratified_host): strata[i] < len(max_coverages) names read i's
+        stratum (strand, read group, sample, ...), NO_STRATUM a read that belongs to none (never kept).  The mask is the
+        OR over the strata of solve_by_contig on that stratum's reads alone at max_coverages[s]; a cap of 0 keeps
+        nothing.  Every stratum keeps its own floor min(its coverage, its cap); a stratum with little data is NOT topped
+        up from another.  -> host keep bitmask in INPUT order; last_stats, and last_stratum_rows (a list of StratumRow,
+        one per stratum)"""
+        starts, ends, ids, strata = _u32(starts), _u32(ends), _u32(contig_ids), _u32(strata)
+        n = starts.size
+        assert ends.size == n and ids.size == n and strata.size == n, \
+            "starts, ends, contig_ids and strata must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        caps = np.atleast_1d(np.ascontiguousarray(max_coverages, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        rows = (StratumRow * max(caps.size, 1))()
+        st = Stats()
+        _check(_hip.qmcp_hip_solve_stratified_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(strata), n,
+                                                   _p32(lengths), lengths.size, _p32(caps), caps.size, _p64(mask), rows,
+                                                   C.byref(st)))
+        self.last_stats, self.last_stratum_rows = st, list(rows)[:caps.size]
+        return mask[:mask_words(n)]
+
+    def solve_stratified_device(self, d_starts, d_ends, d_contig_ids, d_strata, n_reads, contig_lengths, max_coverages,
+                                d_mask, stream=0):
+        """the same on device pointers (ints); the input-order mask is written to d_mask, the rows come back to the host
+        (last_stratum_rows).  Returns the stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        caps = np.atleast_1d(np.ascontiguousarray(max_coverages, dtype=np.uint32))
+        rows = (StratumRow * max(caps.size, 1))()
+        st = Stats()
+        _check(_hip.qmcp_hip_solve_stratified_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                     C.c_void_p(d_contig_ids), C.c_void_p(d_strata), int(n_reads),
+                                                     _p32(lengths), lengths.size, _p32(caps), caps.size,
+                                                     C.c_void_p(d_mask), rows, C.c_void_p(stream), C.byref(st)))
+        self.last_stats, self.last_stratum_rows = st, list(rows)[:caps.size]
+        return st
 
     @staticmethod
     def _target_tables(n_contigs, target_offsets, target_starts, target_ends):
@@ -1086,13 +1151,24 @@ def write_synthetic_bam(path, ref_length, names, flags, pos, mapq, clip_front, m
 
 
 def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0, capacity=1 << 24,
-             per_reference=False, amplicons_by_reference=False):
+             per_reference=False, amplicons_by_reference=False, stratify=None):
     """BamApi(path, config).get_paired_reads_soa() of the host mirror: dict of columns + filtered-out ids.
+    stratify ("strand" | "read_group"; BamApiConfig::stratify_by, needs per_reference=True and no amplicon files,
+    ValueError otherwise): also "strata" (one stratum id per read) and "stratum_names" -- ["+", "-"] (flag 0x10), or the
+    header's @RG IDs in header order followed by "*" for records without an RG:Z field the header lists.
     per_reference=True (BamApiConfig::per_reference): also "contig_ids" (each read's refID, NO_CONTIG if unmapped) and
     "contig_lengths" (every reference's length, header order); amplicons are refused there (ValueError) unless
     amplicons_by_reference=True (BamApiConfig::amplicons_by_reference: BED chroms matched to the references by name;
     only with per_reference, ValueError otherwise)"""
     _need_host()
+    if stratify is not None:
+        if stratify not in ("strand", "read_group"):
+            raise ValueError(f'stratify must be "strand" or "read_group", not {stratify!r}')
+        if not per_reference:
+            raise ValueError("stratified downsampling needs per_reference=True")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("read_bam(stratify=...) does not take amplicon files")
+        return _read_bam_stratified(path, stratify, min_length, min_mapq, capacity)
     if amplicons_by_reference:
         return _read_bam_by_reference(path, bed, tsv, amplicon_mode, per_reference, min_length, min_mapq, capacity)
     if per_reference:
@@ -1139,6 +1215,34 @@ def _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity, ref_
     lengths = refs[:nr.value].copy()
     out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
                ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths)
+    return out
+
+
+def _read_bam_stratified(path, stratify, min_length, min_mapq, capacity, ref_capacity=1 << 24, names_capacity=1 << 22):
+    ids = np.empty(capacity, np.uint64)
+    cols = {k: np.empty(capacity, np.uint32)
+            for k in ("starts", "ends", "qualities", "seq_lengths", "contig_ids", "strata")}
+    first = np.empty(capacity, np.uint8)
+    filt = np.empty(capacity, np.uint64)
+    refs = np.empty(ref_capacity, np.uint32)
+    nf, nr, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    names = C.create_string_buffer(names_capacity)
+    err = C.create_string_buffer(1024)
+    n = _host.qmcp_host_read_bam_stratified(str(path).encode(), stratify.encode(), int(min_length), int(min_mapq),
+                                            capacity, _p64(ids), _p32(cols["starts"]), _p32(cols["ends"]),
+                                            _p32(cols["qualities"]), _p32(cols["seq_lengths"]),
+                                            first.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(cols["contig_ids"]),
+                                            _p32(cols["strata"]), capacity, _p64(filt), C.byref(nf), ref_capacity,
+                                            _p32(refs), C.byref(nr), names, names_capacity, C.byref(ns), 1, err, 1024)
+    if n == -4:
+        raise ValueError(err.value.decode())
+    if n < 0:
+        raise OSError(f"read_bam({path}, stratify={stratify!r}) failed ({n})")
+    out = {k: v[:n].copy() for k, v in cols.items()}
+    lengths = refs[:nr.value].copy()
+    out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
+               ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths,
+               stratum_names=names.value.decode().split("\n")[:ns.value])
     return out
 
 
@@ -1213,7 +1317,7 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
                    targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
-                   ladder_out=None):
+                   ladder_out=None, stratify=None, strata_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1232,8 +1336,44 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     always; every further level is solved on the reads the level above kept, completed by find_pairs (monotone, so the
     files stay nested) and written to ladder_out with {M} replaced by its coverage.  Returns the list of written
     counts, out_path's first.  Needs per_reference=True; not together with targets, report or
-    "quasi-mcp-hip-quality" (ValueError).  Amplicon FILTER at ingest works as before.  None: nothing changes"""
+    "quasi-mcp-hip-quality" (ValueError).  Amplicon FILTER at ingest works as before.  None: nothing changes.
+    stratify ("strand" | "read_group"; BamApiConfig::stratify_by): one coverage cap per stratum in one
+    qmcp_hip_solve_stratified_host call.  "read_group": every @RG of the header (and "*", the records without a listed
+    RG) is brought to max_coverage on its own -- every sample to M x.  "strand": the forward reads are capped at
+    ceil(max_coverage / 2), the reverse reads at floor(max_coverage / 2).  Every stratum keeps its own floor
+    min(its coverage, its cap); a stratum with little data is not topped up from another.  find_pairs then completes
+    mates as always -- it only adds reads, so every floor still holds; with "strand" the mates of a proper pair lie on
+    the OTHER strand, so the per-strand totals of the written file exceed the caps.  strata_report (a path): after the
+    output, a TSV with one line per stratum -- name, cap, reads, kept, mean depth before and after -- of the solve's
+    kept set.  Needs per_reference=True; not together with targets, report, ladder, amplicon files or
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
+    if stratify is not None:
+        if stratify not in ("strand", "read_group"):
+            raise ValueError(f'stratify must be "strand" or "read_group", not {stratify!r}')
+        if not per_reference:
+            raise ValueError("stratified downsampling needs per_reference=True")
+        if targets or report or ladder is not None:
+            raise ValueError("stratified downsampling does not go together with targets, a depth report or a coverage "
+                             "ladder")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("stratified downsampling does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("stratified downsampling does not take a solver that grades by quality")
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_stratified(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            1, stratify.encode(), None, None, None, 0, str(strata_report).encode() if strata_report else None, err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
+    if strata_report is not None:
+        raise ValueError("strata_report needs stratify")
     if ladder is not None:
         levels = [int(m) for m in ladder]
         if not per_reference:

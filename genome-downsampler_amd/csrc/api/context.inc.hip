@@ -137,6 +137,9 @@ struct qmcp_hip_ctx {
     // ping-pong between levels, the scanned word popcounts of a level's mask and their spine, the two offset tables, the
     // host entry's level bytes and the device entry's first-level mask
     DevBuf ld_starts[2], ld_ends[2], ld_orig[2], ld_words, ld_spine, ld_offs[2], ld_levels, ld_mask0;
+    // stratified solves (api/stratified.inc.hip): the host entry's strata column and the per-stratum rows (the grouping
+    // and the batches use the by-contig buffers)
+    DevBuf st_strata, st_rows;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

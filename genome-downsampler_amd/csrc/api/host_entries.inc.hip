@@ -166,7 +166,8 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->tg_ps, &c->tg_pe, &c->tg_off, &c->tg_offw, &c->tg_q, &c->tg_tab,
                       &c->dr_ev, &c->dr_tab, &c->dr_acc, &c->dr_hist, &c->dr_sums, &c->dr_cnt,
                       &c->ld_starts[0], &c->ld_starts[1], &c->ld_ends[0], &c->ld_ends[1], &c->ld_orig[0], &c->ld_orig[1],
-                      &c->ld_words, &c->ld_spine, &c->ld_offs[0], &c->ld_offs[1], &c->ld_levels, &c->ld_mask0};
+                      &c->ld_words, &c->ld_spine, &c->ld_offs[0], &c->ld_offs[1], &c->ld_levels, &c->ld_mask0,
+                      &c->st_strata, &c->st_rows};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

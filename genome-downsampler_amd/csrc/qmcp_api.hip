@@ -27,6 +27,7 @@
 #include "qmcp_kernels.h"
 #include "by_contig_plan.h"
 #include "ladder_plan.h"
+#include "stratified_plan.h"
 #include "amplicon_table.h"
 #include "target_table.h"
 
@@ -50,6 +51,8 @@
 //                       the reads' events, the positions pass, rows and statistics assembled on the host
 //   ladder              several falling coverages in one by-contig call: every further level solved on the reads the level
 //                       above kept, inside each batch; one byte per read counts the levels that keep it
+//   stratified          one coverage cap per stratum (strand, read group, sample): reads grouped once by (stratum, contig),
+//                       every stratum solved in batches of its own at its cap, one row of counts per stratum
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -64,3 +67,4 @@
 #include "api/targets.inc.hip"
 #include "api/depth_report.inc.hip"
 #include "api/ladder.inc.hip"
+#include "api/stratified.inc.hip"

@@ -274,6 +274,18 @@ void launch_ladder_offsets(hipStream_t st, const uint32_t* offs, uint32_t n_cont
 void launch_ladder_levels(hipStream_t st, bool first, const uint64_t* mask, const void* origin_in, uint32_t n,
                           uint32_t level, uint8_t* levels);
 
+// stratified downsampling (kernels/stratified.inc.hip; api/stratified.inc.hip drives them): validation (err: bits 0 and 1
+// as launch_bc_keys, bit 2 a bad stratum id) and the stratum-major sort keys stratum * n_contigs + contig (n_strata *
+// n_contigs for a read without contig or stratum), and the per-stratum rows -- rows[4 * s ..] = {reads, kept reads, bases,
+// kept bases}, zeroed by the caller -- from the n_placed grouped Rec{key, index} records and the input-order keep mask.
+// kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces.
+static constexpr uint32_t kStratumTallyTile = 1024;
+void launch_st_keys(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                    const uint32_t* strata, uint32_t n, const uint32_t* lengths, uint32_t n_contigs, uint32_t n_strata,
+                    uint32_t* keys, uint32_t* err);
+void launch_st_tally(hipStream_t st, const void* sorted, uint32_t n_placed, uint32_t n_contigs, const uint32_t* starts,
+                     const uint32_t* ends, const uint64_t* mask, uint64_t* rows);
+
 // pairs of several contigs against the amplicons of their own contig (kernels/amplicon_by_contig.inc.hip; api/
 // amplicon_by_contig.inc.hip drives them): the FILTER (amp_offs == NULL: no amplicon predicate; the table of
 // amplicon_table.h otherwise, n_amp entries; err as launch_bc_keys) into one bit per pair, and the compaction of the

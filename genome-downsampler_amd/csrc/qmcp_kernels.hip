@@ -40,6 +40,8 @@
 //                            of the on-target reads, the compact mask expanded back to input order
 //   depth_report             depth before and after a keep mask per contig and region: the reads' events (two 64-bit
 //                            atomics per read), chunk sums, spine, and the pass that turns them into rows and histograms
+//   stratified               one coverage cap per stratum (strand, read group, sample): validation and stratum-major sort
+//                            keys, and the per-stratum rows as a segmented reduction over the grouped records
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -76,5 +78,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/quality_cells.inc.hip"
 #include "kernels/targets.inc.hip"
 #include "kernels/depth_report.inc.hip"
+#include "kernels/stratified.inc.hip"
 
 }  // namespace qmcp

@@ -57,6 +57,12 @@ struct BamApiConfig {
     // Needs per_reference; not together with targets or a depth report (std::invalid_argument otherwise).  Empty: no
     // ladder, nothing changes.
     std::vector<std::uint32_t> coverage_ladder;
+    // Stratified downsampling: every read gets a stratum at ingest (bam_io.hpp's Stratify: by strand, or by the read
+    // group of its RG:Z field) and QuasiMcpHipSolver::solve caps every stratum on its own
+    // (qmcp_hip_solve_stratified_host): STRAND at ceil(M / 2) forward and floor(M / 2) reverse, READ_GROUP at M for
+    // every read group.  Needs per_reference; not together with targets, a coverage ladder or a depth report
+    // (std::invalid_argument otherwise).  NONE: nothing changes.
+    Stratify stratify_by = Stratify::NONE;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -91,6 +97,8 @@ class BamApi {
     std::uint32_t depth_report_bins() const { return depth_report_bins_; }
     // BamApiConfig::coverage_ladder (empty: none)
     const std::vector<std::uint32_t>& coverage_ladder() const { return coverage_ladder_; }
+    // BamApiConfig::stratify_by (NONE: the reads carry no strata)
+    Stratify stratify_by() const { return stratify_by_; }
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -119,6 +127,7 @@ class BamApi {
     std::filesystem::path depth_report_filepath_;
     std::uint32_t depth_report_bins_ = 0;
     std::vector<std::uint32_t> coverage_ladder_;
+    Stratify stratify_by_ = Stratify::NONE;
     void read_bam_into(PairedReads& reads);
 };
 

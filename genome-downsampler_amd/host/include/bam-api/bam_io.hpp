@@ -29,6 +29,8 @@ struct BamFilters {
     // BamApiConfig::amplicons_by_reference (needs per_reference): FILTER and GRADE ask this set, with each mate's
     // reference, instead of `amplicons`
     const ReferenceAmpliconSet* reference_amplicons = nullptr;
+    // other than NONE (needs per_reference): fill out.strata / stratum_names
+    Stratify stratify = Stratify::NONE;
 };
 
 struct BamIngestStats {
@@ -41,6 +43,8 @@ struct BamIngestStats {
 // reference's length, lists every record id that was not imported in `filtered_out` (ascending).  With
 // filters.per_reference also every reference's length (out.contig_lengths) and each appended read's refID
 // (out.contig_ids; QMCP_NO_CONTIG for refID == -1) -- pairing and filters are the same either way.
+// With filters.stratify also each appended read's stratum (out.strata) and the strata's names (out.stratum_names); no
+// record is dropped for its stratum.
 // false + *err on a malformed or unreadable file (the reference exits the process there).
 bool read_bam(const std::filesystem::path& path, const BamFilters& filters, PairedReads& out,
               std::vector<BAMReadId>& filtered_out, BamIngestStats* stats, std::string* err);

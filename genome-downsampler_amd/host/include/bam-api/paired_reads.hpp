@@ -7,11 +7,20 @@
 #define QMCP_AMD_BAM_API_PAIRED_READS_HPP
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "bam-api/read.hpp"
 
 namespace bam_api {
+
+// what a stratified ingest turns into a read's stratum (BamApiConfig::stratify_by)
+enum class Stratify {
+    NONE,
+    STRAND,      // stratum 0 "+": forward, stratum 1 "-": reverse (flag 0x10)
+    READ_GROUP,  // the ID of every @RG line of the header text, in header order, then "*": a record without an RG:Z
+                 // field, or with one the header does not list
+};
 
 struct PairedReads {
     Index ref_genome_length = 0;
@@ -21,6 +30,12 @@ struct PairedReads {
     std::vector<std::uint32_t> contig_lengths;
     std::vector<std::uint32_t> contig_ids;
     bool has_contig_ids() const { return !contig_lengths.empty(); }
+    // Stratified ingest only (BamApiConfig::stratify_by, which needs per_reference): one stratum id per read, an index
+    // into stratum_names -- "+" and "-" by strand, or the header's @RG IDs in header order followed by "*" for the
+    // records that carry no RG the header lists.  Both stay empty otherwise.
+    std::vector<std::uint32_t> strata;
+    std::vector<std::string> stratum_names;
+    bool has_strata() const { return !stratum_names.empty(); }
 
     virtual ~PairedReads() = default;
     virtual void push_back(const Read& read) = 0;
@@ -84,6 +99,8 @@ inline AOSPairedReads& AOSPairedReads::from(const SOAPairedReads& soa) {
     ref_genome_length = soa.ref_genome_length;
     contig_lengths = soa.contig_lengths;
     contig_ids = soa.contig_ids;
+    strata = soa.strata;
+    stratum_names = soa.stratum_names;
     reads.clear();
     reads.reserve(soa.get_reads_count());
     for (ReadIndex i = 0; i < soa.get_reads_count(); ++i) reads.push_back(soa.get_read_by_index(i));
@@ -94,6 +111,8 @@ inline SOAPairedReads& SOAPairedReads::from(const AOSPairedReads& aos) {
     clear();
     contig_lengths = aos.contig_lengths;
     contig_ids = aos.contig_ids;
+    strata = aos.strata;
+    stratum_names = aos.stratum_names;
     reserve(aos.reads.size());
     for (const Read& r : aos.reads) push_back(r);
     return *this;

@@ -65,6 +65,12 @@ class QuasiMcpHipSolver : public Solver {
     std::vector<std::unique_ptr<Solution>> solve_ladder(std::uint32_t required_cover, bam_api::BamApi& bam_api,
                                                         const std::vector<std::uint32_t>& levels);
     const qmcp_hip_ladder_stats& last_ladder_stats() const { return lstats_; }
+    // Stratified reads (BamApiConfig::stratify_by): solve() caps every stratum on its own through
+    // qmcp_hip_solve_stratified_host -- STRAND at ceil(M / 2) and floor(M / 2), READ_GROUP at M for every stratum.
+    // The caps and the rows of the last such solve, one per stratum of the reads' stratum_names
+    static std::vector<std::uint32_t> stratum_caps(std::uint32_t required_cover, bam_api::Stratify by, std::size_t n_strata);
+    const std::vector<std::uint32_t>& last_stratum_caps() const { return stratum_caps_; }
+    const std::vector<qmcp_hip_stratum_row>& last_stratum_rows() const { return stratum_rows_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -82,6 +88,10 @@ class QuasiMcpHipSolver : public Solver {
                                             std::chrono::steady_clock::time_point t0);
     qmcp_hip_target_stats tstats_{};
     qmcp_hip_ladder_stats lstats_{};
+    std::unique_ptr<Solution> solve_stratified(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
+                                               bam_api::Stratify by, std::chrono::steady_clock::time_point t0);
+    std::vector<std::uint32_t> stratum_caps_;
+    std::vector<qmcp_hip_stratum_row> stratum_rows_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves
     int device_ = 0;

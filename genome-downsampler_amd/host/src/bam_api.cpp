@@ -82,6 +82,18 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
         if (config.coverage_ladder.back() == 0) throw std::invalid_argument("a coverage ladder ends at a coverage >= 1");
         coverage_ladder_ = config.coverage_ladder;
     }
+    if (config.stratify_by != Stratify::NONE) {
+        if (!per_reference_)
+            throw std::invalid_argument("stratified downsampling needs per_reference: every stratum is solved one "
+                                        "reference at a time");
+        if (!config.targets_filepath.empty())
+            throw std::invalid_argument("stratified downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("stratified downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("stratified downsampling does not take a depth report");
+        stratify_by_ = config.stratify_by;
+    }
     if (!config.depth_report_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a depth report needs per_reference: its rows are the references a per-reference "
@@ -141,6 +153,7 @@ void BamApi::read_bam_into(PairedReads& reads) {
     f.amplicon_behaviour = amplicon_behaviour_;
     f.amplicons = &amplicon_set_;
     f.per_reference = per_reference_;
+    f.stratify = stratify_by_;
     if (amplicons_by_reference_) f.reference_amplicons = &reference_amplicon_set_;
     std::string err;
     if (!read_bam(input_filepath_, f, reads, filtered_out_reads_, nullptr, &err)) {

@@ -428,6 +428,76 @@ bool record_to_read(const std::vector<unsigned char>& rec, BAMReadId id, Read& o
     return true;
 }
 
+// the ID: values of the header text's @RG lines, in header order
+std::vector<std::string> read_group_ids(const std::string& text) {
+    std::vector<std::string> ids;
+    std::size_t at = 0;
+    while (at < text.size()) {
+        std::size_t eol = text.find('\n', at);
+        if (eol == std::string::npos) eol = text.size();
+        if (text.compare(at, 4, "@RG\t") == 0) {
+            std::size_t f = at + 4;
+            while (f < eol) {
+                std::size_t tab = text.find('\t', f);
+                if (tab == std::string::npos || tab > eol) tab = eol;
+                if (text.compare(f, 3, "ID:") == 0) {
+                    ids.emplace_back(text, f + 3, tab - f - 3);
+                    break;
+                }
+                f = tab + 1;
+            }
+        }
+        at = eol + 1;
+    }
+    return ids;
+}
+
+// Walks a record's optional fields up to the first RG:Z and copies its value.  Every type has a fixed size except Z and
+// H (NUL-terminated) and B (a subtype and a count).  false without RG, and for fields that run past the record's end
+// or have an unknown type (*malformed is set then).
+bool record_read_group(const std::vector<unsigned char>& rec, std::string& value, bool* malformed) {
+    const unsigned char* p = rec.data() + 4;
+    const std::size_t size = rec.size() - 4;
+    const std::size_t l_read_name = p[8], n_cigar = le16(p + 12), l_seq = le32(p + 16);
+    const std::size_t fixed_end = 32u + l_read_name + 4u * n_cigar + (l_seq + 1) / 2 + l_seq;
+    *malformed = true;
+    if (fixed_end > size) return false;
+    auto width = [](char t) -> std::size_t {
+        return t == 'A' || t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : t == 'i' || t == 'I' || t == 'f' ? 4 : 0;
+    };
+    const unsigned char* a = p + fixed_end;
+    const unsigned char* const end = p + size;
+    while (a + 3 <= end) {
+        const bool is_rg = a[0] == 'R' && a[1] == 'G';
+        const char type = (char)a[2];
+        a += 3;
+        if (type == 'Z' || type == 'H') {
+            const unsigned char* v = a;
+            while (a < end && *a != 0) ++a;
+            if (a >= end) return false;
+            if (is_rg && type == 'Z') {
+                value.assign(reinterpret_cast<const char*>(v), (std::size_t)(a - v));
+                *malformed = false;
+                return true;
+            }
+            ++a;
+        } else if (type == 'B') {
+            if (a + 5 > end) return false;
+            const std::size_t w = width((char)a[0]), count = le32(a + 1);
+            a += 5;
+            if (w == 0 || (char)a[-5] == 'A' || count > (std::size_t)(end - a) / w) return false;
+            a += count * w;
+        } else {
+            const std::size_t w = width(type);
+            if (w == 0 || a + w > end) return false;
+            a += w;
+        }
+    }
+    if (a != end) return false;
+    *malformed = false;
+    return false;
+}
+
 }  // namespace
 
 bool read_bam(const std::filesystem::path& path, const BamFilters& filters, PairedReads& out,
@@ -445,6 +515,22 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
         out.contig_ids.clear();
         for (const auto& r : h.references) out.contig_lengths.push_back(r.second);
     }
+
+    const Stratify stratify = filters.stratify;
+    if (stratify != Stratify::NONE && !per_reference) return set_err(err, "a stratified ingest needs per_reference");
+    std::vector<std::uint32_t> stratum_of_record;  // stratified: each record's stratum, by BAMReadId
+    std::map<std::string, std::uint32_t> stratum_of_group;
+    out.strata.clear();
+    out.stratum_names.clear();
+    if (stratify == Stratify::STRAND) out.stratum_names = {"+", "-"};
+    if (stratify == Stratify::READ_GROUP) {
+        out.stratum_names = read_group_ids(h.text);
+        for (std::size_t k = 0; k < out.stratum_names.size(); ++k)
+            stratum_of_group.insert({out.stratum_names[k], (std::uint32_t)k});  // (a repeated ID keeps its first line)
+        out.stratum_names.push_back("*");
+    }
+    const std::uint32_t other_stratum = out.stratum_names.empty() ? 0u : (std::uint32_t)out.stratum_names.size() - 1;
+    std::string group;
 
     BamIngestStats st;
     std::vector<bool> is_accepted, in_single_amplicon;
@@ -469,6 +555,19 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
             if (ref_id < -1 || ref_id >= (std::int64_t)h.references.size())
                 return set_err(err, "BAM record with a refID outside the header's references");
             ref_of_record.push_back(ref_id < 0 ? 0xFFFFFFFFu : (std::uint32_t)ref_id);   // QMCP_NO_CONTIG
+        }
+        if (stratify == Stratify::STRAND) {
+            stratum_of_record.push_back((le16(rec.data() + 4 + 14) & 0x10) ? 1u : 0u);
+        } else if (stratify == Stratify::READ_GROUP) {
+            bool malformed = false;
+            std::uint32_t s = other_stratum;
+            if (record_read_group(rec, group, &malformed)) {
+                auto g = stratum_of_group.find(group);
+                if (g != stratum_of_group.end()) s = g->second;
+            } else if (malformed) {
+                return set_err(err, "BAM record with optional fields past its end");
+            }
+            stratum_of_record.push_back(s);
         }
         is_accepted.push_back(false);
         auto it = read_map.find(qname);
@@ -495,6 +594,10 @@ bool read_bam(const std::filesystem::path& path, const BamFilters& filters, Pair
             if (per_reference) {
                 out.contig_ids.push_back(ref_of_record[r1.bam_id]);
                 out.contig_ids.push_back(ref_of_record[r2.bam_id]);
+            }
+            if (stratify != Stratify::NONE) {
+                out.strata.push_back(stratum_of_record[r1.bam_id]);
+                out.strata.push_back(stratum_of_record[r2.bam_id]);
             }
             is_accepted[r1.bam_id] = true;
             is_accepted[r2.bam_id] = true;

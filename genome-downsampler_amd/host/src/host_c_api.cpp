@@ -703,6 +703,121 @@ std::int64_t qmcp_host_downsample_bam_ladder(const char* solver_name, const char
     }
 }
 
+namespace {
+// "strand" / "read_group" -> BamApiConfig::stratify_by; anything else is refused
+bam_api::Stratify stratify_from_name(const char* name) {
+    const std::string s = name ? name : "";
+    if (s == "strand") return bam_api::Stratify::STRAND;
+    if (s == "read_group") return bam_api::Stratify::READ_GROUP;
+    throw std::invalid_argument("stratify must be \"strand\" or \"read_group\", not \"" + s + "\"");
+}
+}  // namespace
+
+// qmcp_host_read_bam_per_reference with BamApiConfig::stratify_by ("strand" / "read_group"): the same columns, plus each
+// read's stratum (strata, cap entries) and the strata's names, one per line, in names_out (names_cap bytes; *n_strata
+// receives the count).  -2 when a capacity is too small, -3 out of memory, -4 with the message in err.
+std::int64_t qmcp_host_read_bam_stratified(const char* path, const char* stratify, std::uint32_t min_len,
+                                           std::uint32_t min_mapq, std::uint64_t cap, std::uint64_t* bam_ids,
+                                           std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* qualities,
+                                           std::uint32_t* seq_lengths, std::uint8_t* is_first, std::uint32_t* contig_ids,
+                                           std::uint32_t* strata, std::uint64_t cap_f, std::uint64_t* filtered_out,
+                                           std::uint64_t* n_filtered_out, std::uint64_t ref_cap,
+                                           std::uint32_t* ref_lengths, std::uint64_t* n_refs, char* names_out,
+                                           std::size_t names_cap, std::uint64_t* n_strata, int per_reference, char* err,
+                                           std::size_t err_cap) {
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.stratify_by = stratify_from_name(stratify);
+        bam_api::BamApi api(path, cfg);
+        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
+        const std::uint64_t n = r.ids.size();
+        std::string names;
+        for (const std::string& s : r.stratum_names) names += s + "\n";
+        if (n > cap || api.get_filtered_out_reads().size() > cap_f || r.contig_lengths.size() > ref_cap ||
+            names.size() + 1 > names_cap)
+            return -2;
+        for (std::uint64_t i = 0; i < n; ++i) {
+            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
+            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
+            contig_ids[i] = r.contig_ids[i];
+            strata[i] = r.strata[i];
+        }
+        *n_filtered_out = api.get_filtered_out_reads().size();
+        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
+        *n_refs = r.contig_lengths.size();
+        for (std::size_t k = 0; k < r.contig_lengths.size(); ++k) ref_lengths[k] = r.contig_lengths[k];
+        std::memcpy(names_out, names.c_str(), names.size() + 1);
+        *n_strata = r.stratum_names.size();
+        return (std::int64_t)n;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
+// The file-to-file flow with BamApiConfig::stratify_by ("strand" / "read_group"): one ingest, one
+// qmcp_hip_solve_stratified_host call (QuasiMcpHipSolver::solve picks it when the reads carry strata), find_pairs,
+// write_paired_reads.  targets / report / ladder_levels are handed to BamApiConfig as given so that it refuses the
+// combinations it refuses.  strata_report (may be NULL): a TSV written after the output, one line per stratum -- name,
+// cap, reads, kept, mean depth before and after (bases / the sum of the reference lengths) -- of the solve's own kept
+// set (before mate completion).  Returns the number of records written; -1 on an unknown solver, -3 out of memory, -4
+// with a message in err when the configuration is refused, -5 when the report cannot be written.
+std::int64_t qmcp_host_downsample_bam_stratified(const char* solver_name, const char* in_path, const char* out_path,
+                                                 const char* filtered_path, std::uint32_t max_coverage,
+                                                 std::uint32_t min_len, std::uint32_t min_mapq, int per_reference,
+                                                 const char* stratify, const char* targets, const char* report,
+                                                 const std::uint32_t* ladder_levels, std::uint32_t n_ladder_levels,
+                                                 const char* strata_report, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.stratify_by = stratify_from_name(stratify);
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        bam_api::BamApi api(in_path, cfg);
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("stratified downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no stratified downsampling");
+        std::unique_ptr<qmcp::Solution> solution = hip->solve(max_coverage, api);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        if (strata_report && strata_report[0]) {
+            const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
+            double positions = 0;
+            for (std::uint32_t l : r.contig_lengths) positions += l;
+            std::FILE* f = std::fopen(strata_report, "w");
+            if (f == nullptr) return -5;
+            std::fprintf(f, "#stratum\tcap\treads\tkept\tmean_depth_in\tmean_depth_kept\n");
+            for (std::size_t s = 0; s < r.stratum_names.size(); ++s) {
+                const qmcp_hip_stratum_row& row = hip->last_stratum_rows()[s];
+                std::fprintf(f, "%s\t%u\t%llu\t%llu\t%.6f\t%.6f\n", r.stratum_names[s].c_str(),
+                             hip->last_stratum_caps()[s], (unsigned long long)row.n_reads, (unsigned long long)row.n_kept,
+                             positions > 0 ? (double)row.bases_in / positions : 0.0,
+                             positions > 0 ? (double)row.bases_kept / positions : 0.0);
+            }
+            if (std::fclose(f) != 0) return -5;
+        }
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

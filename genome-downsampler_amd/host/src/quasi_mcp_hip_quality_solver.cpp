@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <exception>
+#include <stdexcept>
 #include <vector>
 
 namespace qmcp {
@@ -23,6 +24,8 @@ std::unique_ptr<Solution> QuasiMcpHipQualitySolver::solve(std::uint32_t required
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
+    if (reads.has_strata())
+        throw std::invalid_argument("stratified downsampling does not take a solver that grades by quality");
     const bool by_contig = reads.has_contig_ids();
     if (by_contig && reads.contig_ids.size() != n) die("per-reference reads without one contig id each", QMCP_EINVAL);
     if (reads.qualities.size() != n) die("reads without one quality each", QMCP_EINVAL);

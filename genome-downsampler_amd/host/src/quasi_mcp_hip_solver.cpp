@@ -46,6 +46,7 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
         if (rc != QMCP_OK) die("qmcp_hip_create", rc);
     }
 
+    if (reads.has_strata()) return solve_stratified(required_cover, reads, bam_api.stratify_by(), t0);
     if (bam_api.has_targets()) return solve_targets(required_cover, reads, bam_api.get_targets(), false, t0);
     if (reads.has_contig_ids()) return solve_by_contig(required_cover, reads, t0);
 
@@ -89,6 +90,49 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_by_contig(std::uint32_t requi
                                            reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
                                            required_cover, mask.data(), &stats_);
     if (rc != QMCP_OK) die("qmcp_hip_solve_by_contig_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) {
+        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
+        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
+    }
+    return expand_kept(n, t0);
+}
+
+// STRAND: the two strands share M, the forward strand taking the odd one; every other stratification brings every
+// stratum to M ("every sample to M x")
+std::vector<std::uint32_t> QuasiMcpHipSolver::stratum_caps(std::uint32_t required_cover, bam_api::Stratify by,
+                                                           std::size_t n_strata) {
+    std::vector<std::uint32_t> caps(n_strata, required_cover);
+    if (by == bam_api::Stratify::STRAND && n_strata == 2) {
+        caps[0] = required_cover - required_cover / 2;
+        caps[1] = required_cover / 2;
+    }
+    return caps;
+}
+
+// Per-reference reads with a stratum each (BamApiConfig::stratify_by): one cap per stratum, through
+// qmcp_hip_solve_stratified_host; otherwise as solve_by_contig.
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_stratified(std::uint32_t required_cover,
+                                                              const bam_api::SOAPairedReads& reads, bam_api::Stratify by,
+                                                              std::chrono::steady_clock::time_point t0) {
+    const std::size_t n = reads.start_inds.size();
+    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("strata without one contig id per read", QMCP_EINVAL);
+    if (reads.strata.size() != n) die("stratified reads without one stratum each", QMCP_EINVAL);
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    stratum_caps_ = stratum_caps(required_cover, by, reads.stratum_names.size());
+    stratum_rows_.assign(stratum_caps_.size(), qmcp_hip_stratum_row{});
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    int rc = qmcp_hip_solve_stratified_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), reads.strata.data(),
+                                            n, reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                            stratum_caps_.data(), (std::uint32_t)stratum_caps_.size(), mask.data(),
+                                            stratum_rows_.data(), &stats_);
+    if (rc != QMCP_OK) die("qmcp_hip_solve_stratified_host", rc);
     breakdown_ = qmcp_hip_host_breakdown{};
     if (complete_pairs_) {
         rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)

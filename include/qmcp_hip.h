@@ -614,6 +614,57 @@ int qmcp_hip_solve_ladder_device(qmcp_hip_ctx* ctx,
                                  const uint32_t* coverages, uint32_t n_levels, uint8_t* d_levels_out,
                                  void* hip_stream, qmcp_hip_stats* stats, qmcp_hip_ladder_stats* lstats);
 
+/* Stratified downsampling: one coverage cap per stratum -- strand, read group, sample, lane, haplotype, anything the
+ * caller can turn into a small integer per read ("bring every sample of a pooled file to 30x"; "half of the coverage
+ * from each strand").  Reads, contig_ids, contig_lengths / n_contigs and the per-read rules are those of
+ * qmcp_hip_solve_by_contig_host.  strata[i] < n_strata names read i's stratum, QMCP_NO_STRATUM marks a read that belongs
+ * to none: it is never kept, exactly like a QMCP_NO_CONTIG read, and is still validated against its contig.
+ * max_coverages[s] is stratum s's cap, 1 <= n_strata <= 65536, n_strata * n_contigs <= 2^24.
+ * Definition: the mask is the OR over the strata s of the mask qmcp_hip_solve_by_contig_host returns, at
+ * M = max_coverages[s], for the placed reads with strata[i] == s ALONE, in input order, expressed over the input indices.
+ * A stratum whose cap is 0 keeps nothing (no solve is run for it).  With n_strata == 1 and every placed read in stratum 0
+ * the mask and stats.n_kept are bit-identical to qmcp_hip_solve_by_contig_host at that M.
+ * Guarantee: for every stratum s, contig c and position p, the kept reads OF STRATUM s cover p at least
+ * min(coverage of p by stratum s, max_coverages[s]) times.  Nothing is promised about the total over the strata: a
+ * stratum with little data is NOT topped up from another, and the total at p may be anything between the largest
+ * floor and the sum of the caps.
+ * How: the reads are grouped once, on the device, by the key stratum * n_contigs + contig; every stratum with a cap and
+ * reads is cut into solver calls of its own (never across a stratum boundary), each gathered, solved at the stratum's cap
+ * and scattered back; a last pass over the grouped records fills the rows.  One (stratum, contig) must fit one solver
+ * call (2^30 reads, 2^31 - 2 positions): QMCP_ERANGE with a message naming the pair otherwise.
+ * rows_out (host memory in both entries, n_strata rows, may be NULL): per stratum its placed reads, how many of them are
+ * kept, and the bases (end - start + 1) of both; mean depth = bases / sum of the contig lengths.  Written on success only.
+ * stats (may be NULL) follow the by-contig convention: the solver calls summed, the route of the largest; n_reads is the
+ * number of placed reads = the sum of the rows' n_reads, n_kept the sum of the rows' n_kept.
+ * Errors: NULL buffers, max_coverages == NULL and n_strata == 0 fail with QMCP_EINVAL, n_strata > 65536 and
+ * n_strata * n_contigs > 2^24 with QMCP_ERANGE, all on the host before anything is copied or launched.  A stratum id that
+ * is neither < n_strata nor QMCP_NO_STRATUM (QMCP_EINVAL), a bad contig id (QMCP_EINVAL) and a bad read (QMCP_EREAD) are
+ * found on the device; by then the device mask (d_keep_mask_out, or the context's own for the host entry) has been
+ * cleared -- ceil(n_reads / 64) words and nothing beyond them -- and the host entry does not write keep_mask_out.
+ * The device entry takes the four columns and the mask in device memory (contig_lengths, max_coverages and rows_out stay
+ * on the host), is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the work has
+ * completed.  The host entry leaves the mask in the context, for qmcp_hip_kept_indices_host. */
+#define QMCP_NO_STRATUM 0xFFFFFFFFu
+typedef struct qmcp_hip_stratum_row {   /* 32 bytes */
+    uint64_t n_reads;     /* placed reads of the stratum                                                               */
+    uint64_t n_kept;      /* ... of which the mask keeps                                                               */
+    uint64_t bases_in;    /* sum of (end - start + 1) over n_reads                                                     */
+    uint64_t bases_kept;  /* ... over the kept ones                                                                    */
+} qmcp_hip_stratum_row;
+int qmcp_hip_solve_stratified_host(qmcp_hip_ctx* ctx,
+                                   const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                   const uint32_t* strata, uint64_t n_reads,
+                                   const uint32_t* contig_lengths, uint32_t n_contigs,
+                                   const uint32_t* max_coverages, uint32_t n_strata,
+                                   uint64_t* keep_mask_out, qmcp_hip_stratum_row* rows_out, qmcp_hip_stats* stats);
+int qmcp_hip_solve_stratified_device(qmcp_hip_ctx* ctx,
+                                     const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                     const uint32_t* d_strata, uint64_t n_reads,
+                                     const uint32_t* contig_lengths, uint32_t n_contigs,
+                                     const uint32_t* max_coverages, uint32_t n_strata,
+                                     uint64_t* d_keep_mask_out, qmcp_hip_stratum_row* rows_out, void* hip_stream,
+                                     qmcp_hip_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
