@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_depth_report_host", "qmcp_hip_depth_report_device",
     "qmcp_hip_solve_ladder_host", "qmcp_hip_solve_ladder_device",
     "qmcp_hip_solve_stratified_host", "qmcp_hip_solve_stratified_device",
+    "qmcp_hip_solve_dedup_host", "qmcp_hip_solve_dedup_device",
 )
 
 QMCP_OK = 0
@@ -45,6 +46,8 @@ NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never ke
 TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
 LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
+DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
+DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
 STRATUM_TALLY_TILE = 1024  # qmcp::kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces
 
 
@@ -139,6 +142,17 @@ class LadderStats(C.Structure):
 class StratumRow(C.Structure):
     """qmcp_hip_stratum_row: a stratum's placed reads, how many of them are kept, and the bases of both"""
     _fields_ = [("n_reads", C.c_uint64), ("n_kept", C.c_uint64), ("bases_in", C.c_uint64), ("bases_kept", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class DedupStats(C.Structure):
+    """qmcp_hip_dedup_stats: what the duplicate pass before the solve found (units: placed reads, or pairs with a placed
+    mate; families: distinct cells / signatures; reads_survived: reads handed to the inner solve)"""
+    _fields_ = [("units", C.c_uint64), ("families", C.c_uint64), ("duplicate_units", C.c_uint64),
+                ("largest_family", C.c_uint64), ("reads_survived", C.c_uint64), ("key_bits", C.c_uint32),
+                ("sort_passes", C.c_uint32), ("ms_dedup", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -260,6 +274,13 @@ _hip.qmcp_hip_solve_stratified_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p,
 _hip.qmcp_hip_solve_stratified_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                   _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
                                                   C.POINTER(StratumRow), C.c_void_p, C.POINTER(Stats)]
+_hip.qmcp_hip_solve_dedup_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, _u64p, _u64p, _u64p, C.c_uint32, C.POINTER(Stats),
+                                           C.POINTER(DedupStats)]
+_hip.qmcp_hip_solve_dedup_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_uint64, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, _u64p, C.c_uint32, C.c_void_p, C.POINTER(Stats),
+                                             C.POINTER(DedupStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -328,6 +349,11 @@ if _host is not None:
                                                           C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_char_p,
                                                           C.c_size_t]
     _host.qmcp_host_downsample_bam_stratified.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_dedup.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                     C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_char_p, _u32p,
+                                                     C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
+                                                     C.c_char_p, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_dedup.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -419,6 +445,7 @@ class Solver:
         self.last_target_stats = None
         self.last_ladder_stats = None
         self.last_stratum_rows = None
+        self.last_dedup_stats = None
 
     def close(self):
         if self._ctx:
@@ -605,6 +632,54 @@ class Solver:
                                                      C.c_void_p(d_mask), rows, C.c_void_p(stream), C.byref(st)))
         self.last_stats, self.last_stratum_rows = st, list(rows)[:caps.size]
         return st
+
+    def solve_dedup(self, starts, ends, contig_ids, contig_lengths, max_coverage, tags=None, qualities=None, pairs=False,
+                    complete_pairs=False, hist_bins=0):
+        """duplicate families collapsed to their representative before solve_by_contig (qmcp_hip_solve_dedup_host).
+        A cell is (contig, start, end, tag).  Read mode: a family is the placed reads of one cell, its representative the
+        read of highest quality, then lowest index.  pairs=True: unit q is the reads (2q, 2q + 1), a family the units
+        with equal unordered pair of cells, the representative the unit of highest summed quality of its placed mates,
+        then lowest q.  The mask is solve_by_contig's on the representatives' reads, in INPUT order; complete_pairs ORs
+        inside each aligned bit pair afterwards.  tags / qualities: one uint32 per read or None (all 0).
+        -> (mask, dup_mask, stats_dict, hist): dup_mask marks the reads of non-representative units, hist[k - 1] counts
+        the families of size k (the last of the hist_bins bins: sizes >= hist_bins).  last_stats is the inner solve's,
+        last_dedup_stats the DedupStats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        t = None if tags is None else _u32(tags)
+        q = None if qualities is None else _u32(qualities)
+        n = starts.size
+        assert ends.size == n and ids.size == n and (t is None or t.size == n) and (q is None or q.size == n), \
+            "one entry per read in every column"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        flags = (DEDUP_PAIRS if pairs else 0) | (DEDUP_COMPLETE_PAIRS if complete_pairs else 0)
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        dup = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        hist = np.zeros(max(int(hist_bins), 1), dtype=np.uint64)
+        st, ds = Stats(), DedupStats()
+        _check(_hip.qmcp_hip_solve_dedup_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(t), _p32(q), n,
+                                              _p32(lengths), lengths.size, int(max_coverage), flags, _p64(mask),
+                                              _p64(dup), _p64(hist) if hist_bins else None, int(hist_bins),
+                                              C.byref(st), C.byref(ds)))
+        self.last_stats, self.last_dedup_stats = st, ds
+        return mask[:mask_words(n)], dup[:mask_words(n)], ds.as_dict(), hist[:int(hist_bins)]
+
+    def solve_dedup_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_mask,
+                           d_tags=0, d_qualities=0, pairs=False, complete_pairs=False, d_dup_mask=0, hist_bins=0,
+                           stream=0):
+        """the same on device pointers (ints; 0: no tags / no qualities / no duplicate mask), columns at any 4-byte
+        alignment; the masks are written to d_mask / d_dup_mask.  -> (stats_dict, hist)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        flags = (DEDUP_PAIRS if pairs else 0) | (DEDUP_COMPLETE_PAIRS if complete_pairs else 0)
+        hist = np.zeros(max(int(hist_bins), 1), dtype=np.uint64)
+        st, ds = Stats(), DedupStats()
+        _check(_hip.qmcp_hip_solve_dedup_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                C.c_void_p(d_contig_ids), C.c_void_p(d_tags or None),
+                                                C.c_void_p(d_qualities or None), int(n_reads), _p32(lengths),
+                                                lengths.size, int(max_coverage), flags, C.c_void_p(d_mask),
+                                                C.c_void_p(d_dup_mask or None), _p64(hist) if hist_bins else None,
+                                                int(hist_bins), C.c_void_p(stream), C.byref(st), C.byref(ds)))
+        self.last_stats, self.last_dedup_stats = st, ds
+        return ds.as_dict(), hist[:int(hist_bins)]
 
     @staticmethod
     def _target_tables(n_contigs, target_offsets, target_starts, target_ends):
@@ -1317,7 +1392,7 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
                    targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
-                   ladder_out=None, stratify=None, strata_report=None):
+                   ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1346,8 +1421,39 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     the OTHER strand, so the per-strand totals of the written file exceed the caps.  strata_report (a path): after the
     output, a TSV with one line per stratum -- name, cap, reads, kept, mean depth before and after -- of the solve's
     kept set.  Needs per_reference=True; not together with targets, report, ladder, amplicon files or
-    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes.
+    dedup=True (BamApiConfig::dedup): duplicate pairs -- equal unordered pair of (reference, start, end, strand) cells
+    -- are collapsed to the pair of highest summed MAPQ (then the first in the file's pairing order) before the solve:
+    one qmcp_hip_solve_dedup_host call in pair mode with mate completion.  Duplicates are simply not written;
+    filtered_path keeps its meaning of ingest filters only.  dedup_report (a path): a TSV with the statistics, then one
+    size<TAB>families line per family-size bin (DEDUP_REPORT_BINS bins, the last holding the larger sizes).  Needs
+    per_reference=True; not together with targets, report, ladder, stratify, amplicon files or
+    "quasi-mcp-hip-quality" (ValueError).  False: nothing changes"""
     _need_host()
+    if dedup:
+        if not per_reference:
+            raise ValueError("duplicate-aware downsampling needs per_reference=True")
+        if targets or report or ladder is not None or stratify is not None:
+            raise ValueError("duplicate-aware downsampling does not go together with targets, a depth report, a "
+                             "coverage ladder or stratify")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("duplicate-aware downsampling does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("duplicate-aware downsampling does not take a solver that grades by quality")
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_dedup(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            1, None, None, None, 0, None, None, None, 0, str(dedup_report).encode() if dedup_report else None, err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
+    if dedup_report is not None:
+        raise ValueError("dedup_report needs dedup")
     if stratify is not None:
         if stratify not in ("strand", "read_group"):
             raise ValueError(f'stratify must be "strand" or "read_group", not {stratify!r}')

@@ -140,6 +140,13 @@ struct qmcp_hip_ctx {
     // stratified solves (api/stratified.inc.hip): the host entry's strata column and the per-stratum rows (the grouping
     // and the batches use the by-contig buffers)
     DevBuf st_strata, st_rows;
+    // duplicate-aware solves (api/dedup.inc.hip), all its own: the position offsets and contig lengths, the range words
+    // and counters, bare keys, the sorts' two key buffers (records, or u64 keys) and two index columns, their histogram
+    // and spine, the scanned head flags, the families' first positions, the reads' cell ids (pair mode), the survivor
+    // mask and its scanned word popcounts, the size histogram, the survivors' columns, input indices and keep mask, and
+    // the host entry's tag column and duplicate mask
+    DevBuf dd_tab, dd_stat, dd_bare, dd_keys[2], dd_vals[2], dd_hist, dd_spine, dd_flag, dd_head, dd_cid, dd_surv, dd_words,
+        dd_histo, dd_cs, dd_ce, dd_ci, dd_map, dd_maskc, dd_tags, dd_dupm;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

@@ -167,7 +167,10 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->dr_ev, &c->dr_tab, &c->dr_acc, &c->dr_hist, &c->dr_sums, &c->dr_cnt,
                       &c->ld_starts[0], &c->ld_starts[1], &c->ld_ends[0], &c->ld_ends[1], &c->ld_orig[0], &c->ld_orig[1],
                       &c->ld_words, &c->ld_spine, &c->ld_offs[0], &c->ld_offs[1], &c->ld_levels, &c->ld_mask0,
-                      &c->st_strata, &c->st_rows};
+                      &c->st_strata, &c->st_rows,
+                      &c->dd_tab, &c->dd_stat, &c->dd_bare, &c->dd_keys[0], &c->dd_keys[1], &c->dd_vals[0], &c->dd_vals[1],
+                      &c->dd_hist, &c->dd_spine, &c->dd_flag, &c->dd_head, &c->dd_cid, &c->dd_surv, &c->dd_words,
+                      &c->dd_histo, &c->dd_cs, &c->dd_ce, &c->dd_ci, &c->dd_map, &c->dd_maskc, &c->dd_tags, &c->dd_dupm};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

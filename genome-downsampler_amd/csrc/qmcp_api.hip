@@ -28,6 +28,7 @@
 #include "by_contig_plan.h"
 #include "ladder_plan.h"
 #include "stratified_plan.h"
+#include "dedup_plan.h"
 #include "amplicon_table.h"
 #include "target_table.h"
 
@@ -53,6 +54,8 @@
 //                       above kept, inside each batch; one byte per read counts the levels that keep it
 //   stratified          one coverage cap per stratum (strand, read group, sample): reads grouped once by (stratum, contig),
 //                       every stratum solved in batches of its own at its cap, one row of counts per stratum
+//   dedup               duplicate families (reads or pairs with equal cells) collapsed to their best unit before the
+//                       by-contig solve; duplicate mask, family-size histogram and statistics from the device
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -68,3 +71,4 @@
 #include "api/depth_report.inc.hip"
 #include "api/ladder.inc.hip"
 #include "api/stratified.inc.hip"
+#include "api/dedup.inc.hip"

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "sweep_plan.h"  // the shape predicates and window counts the host decides with
+#include "dedup_plan.h"  // DedupPack, DedupSortForm: how a round's key is packed, which form the sort takes
 
 namespace qmcp {
 
@@ -346,6 +347,38 @@ void launch_depth_consume(hipStream_t st, const uint64_t* ev, uint32_t positions
                           const uint32_t* r_lo, const uint32_t* r_hi, const uint32_t* r_row, uint32_t n_r,
                           bool scope_regions, uint32_t n_rows, uint64_t* acc64, uint32_t* acc32, uint32_t n_bins,
                           uint64_t* hist);
+
+// duplicate-aware downsampling (kernels/dedup.inc.hip; api/dedup.inc.hip drives them; keys and forms: dedup_plan.h): the
+// ranges and validation of a call (out: 9 words preset to {~0u, 0, ~0u, 0, ~0u, 0, 0, 0, 0} -- tag, quality and span min /
+// max over the placed reads, err as launch_bc_keys, placed reads, pairs without a placed mate), a round's keys of the reads
+// (key_bytes 4 or 8; idx == NULL: record j is read j) and of the units (cid: dense cell ids, idu for an unplaced mate),
+// head flags over the n_act active records of a sorted order (form: DedupSortForm; compared on the keys above low_bits, or
+// on the columns / cell ids after a sort field by field), the cell ids scattered to input order, survivor and duplicate
+// bits + every family's first position from the scanned flags E, the family statistics (counters: families, duplicate
+// units, largest; hist_bins <= dedup_hist_max()), and the stable compaction of the survivors
+uint32_t dedup_hist_max();
+void launch_dd_range(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                     const uint32_t* tags, const uint32_t* q, uint32_t n, const uint32_t* lengths, uint32_t n_contigs,
+                     bool pairs, uint32_t* out);
+void launch_dd_read_keys(hipStream_t st, uint32_t key_bytes, const uint32_t* starts, const uint32_t* ends,
+                         const uint32_t* ids, const uint32_t* tags, const uint32_t* q, const uint32_t* idx,
+                         const uint64_t* poff, uint64_t ltot, uint32_t n, uint32_t min_span, uint32_t tag_min,
+                         uint32_t q_max, const DedupPack& pack, void* keys);
+void launch_dd_pair_keys(hipStream_t st, uint32_t key_bytes, const uint32_t* cid, const uint32_t* q, const uint32_t* idx,
+                         uint32_t n_units, uint32_t idu, uint32_t q_min, uint32_t score_max, const DedupPack& pack,
+                         void* keys);
+void launch_dd_heads(hipStream_t st, uint32_t form, const void* sorted, const uint32_t* svals, uint32_t low_bits,
+                     uint32_t n_act, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                     const uint32_t* tags, const uint32_t* cid, uint32_t* flag);
+void launch_dd_cell_ids(hipStream_t st, const uint32_t* vals, uint32_t stride, const uint32_t* E, uint32_t n_placed,
+                        uint32_t n, uint32_t idu, uint32_t* cid);
+void launch_dd_segments(hipStream_t st, bool pairs, const uint32_t* vals, uint32_t stride, const uint32_t* E,
+                        uint32_t n_act, uint64_t* surv, uint64_t* dup, uint32_t* headpos);
+void launch_dd_family_stats(hipStream_t st, const uint32_t* headpos, const uint32_t* n_fam, uint32_t n_act,
+                            uint32_t hist_bins, uint64_t* hist, uint64_t* counters);
+void launch_dd_compact(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                       const uint64_t* surv, const uint32_t* word_base, uint32_t n, uint32_t* starts_c, uint32_t* ends_c,
+                       uint32_t* ids_c, uint32_t* orig);
 
 }  // namespace qmcp
 #endif

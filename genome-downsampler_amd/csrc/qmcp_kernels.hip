@@ -42,6 +42,8 @@
 //                            atomics per read), chunk sums, spine, and the pass that turns them into rows and histograms
 //   stratified               one coverage cap per stratum (strand, read group, sample): validation and stratum-major sort
 //                            keys, and the per-stratum rows as a segmented reduction over the grouped records
+//   dedup                    duplicate families collapsed before the solve: ranges and validation, composite keys, head
+//                            flags, cell ids, survivor / duplicate bits, family statistics, compaction of the survivors
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -79,5 +81,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/targets.inc.hip"
 #include "kernels/depth_report.inc.hip"
 #include "kernels/stratified.inc.hip"
+#include "kernels/dedup.inc.hip"
 
 }  // namespace qmcp

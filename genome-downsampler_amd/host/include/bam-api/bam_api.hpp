@@ -63,6 +63,12 @@ struct BamApiConfig {
     // every read group.  Needs per_reference; not together with targets, a coverage ladder or a depth report
     // (std::invalid_argument otherwise).  NONE: nothing changes.
     Stratify stratify_by = Stratify::NONE;
+    // Duplicate-aware downsampling: duplicate pairs -- equal unordered pair of (reference, start, end, strand) cells --
+    // are collapsed to the pair of highest summed MAPQ before the solve (QuasiMcpHipSolver::solve_dedup /
+    // qmcp_hip_solve_dedup_host in pair mode with mate completion); the ingest keeps every record's reverse-strand bit as
+    // the reads' strata column for it.  Needs per_reference; not together with targets, a depth report, a coverage
+    // ladder, stratify_by or amplicon files (std::invalid_argument otherwise).  false: nothing changes.
+    bool dedup = false;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -99,6 +105,8 @@ class BamApi {
     const std::vector<std::uint32_t>& coverage_ladder() const { return coverage_ladder_; }
     // BamApiConfig::stratify_by (NONE: the reads carry no strata)
     Stratify stratify_by() const { return stratify_by_; }
+    // BamApiConfig::dedup (the reads' strata column then holds the reverse-strand bit)
+    bool dedup() const { return dedup_; }
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -128,6 +136,7 @@ class BamApi {
     std::uint32_t depth_report_bins_ = 0;
     std::vector<std::uint32_t> coverage_ladder_;
     Stratify stratify_by_ = Stratify::NONE;
+    bool dedup_ = false;
     void read_bam_into(PairedReads& reads);
 };
 

@@ -71,6 +71,13 @@ class QuasiMcpHipSolver : public Solver {
     static std::vector<std::uint32_t> stratum_caps(std::uint32_t required_cover, bam_api::Stratify by, std::size_t n_strata);
     const std::vector<std::uint32_t>& last_stratum_caps() const { return stratum_caps_; }
     const std::vector<qmcp_hip_stratum_row>& last_stratum_rows() const { return stratum_rows_; }
+    // Duplicate-aware downsampling for the reads of a BamApi built with BamApiConfig::dedup: qmcp_hip_solve_dedup_host
+    // in pair mode with mate completion, tag = the reads' strand bit, quality = MAPQ; hist_bins bins of family sizes.
+    // Duplicate pairs are not in the Solution.  std::invalid_argument for reads without contig ids or strand column;
+    // std::terminate on a device failure, like solve()
+    std::unique_ptr<Solution> solve_dedup(std::uint32_t required_cover, bam_api::BamApi& bam_api, std::uint32_t hist_bins);
+    const qmcp_hip_dedup_stats& last_dedup_stats() const { return dstats_; }
+    const std::vector<std::uint64_t>& last_dedup_hist() const { return dedup_hist_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -92,6 +99,8 @@ class QuasiMcpHipSolver : public Solver {
                                                bam_api::Stratify by, std::chrono::steady_clock::time_point t0);
     std::vector<std::uint32_t> stratum_caps_;
     std::vector<qmcp_hip_stratum_row> stratum_rows_;
+    qmcp_hip_dedup_stats dstats_{};
+    std::vector<std::uint64_t> dedup_hist_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves
     int device_ = 0;

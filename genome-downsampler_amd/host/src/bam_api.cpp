@@ -94,6 +94,22 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
             throw std::invalid_argument("stratified downsampling does not take a depth report");
         stratify_by_ = config.stratify_by;
     }
+    if (config.dedup) {
+        if (!per_reference_)
+            throw std::invalid_argument("duplicate-aware downsampling needs per_reference: a duplicate's cell includes "
+                                        "its reference");
+        if (!config.targets_filepath.empty())
+            throw std::invalid_argument("duplicate-aware downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("duplicate-aware downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("duplicate-aware downsampling does not take a depth report");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("duplicate-aware downsampling does not take stratify_by");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("duplicate-aware downsampling does not take amplicon files");
+        dedup_ = true;
+    }
     if (!config.depth_report_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a depth report needs per_reference: its rows are the references a per-reference "
@@ -153,7 +169,7 @@ void BamApi::read_bam_into(PairedReads& reads) {
     f.amplicon_behaviour = amplicon_behaviour_;
     f.amplicons = &amplicon_set_;
     f.per_reference = per_reference_;
-    f.stratify = stratify_by_;
+    f.stratify = dedup_ ? Stratify::STRAND : stratify_by_;  // (dedup: the strand bit is the duplicate cell's tag)
     if (amplicons_by_reference_) f.reference_amplicons = &reference_amplicon_set_;
     std::string err;
     if (!read_bam(input_filepath_, f, reads, filtered_out_reads_, nullptr, &err)) {

@@ -818,6 +818,71 @@ std::int64_t qmcp_host_downsample_bam_stratified(const char* solver_name, const 
     }
 }
 
+// The file-to-file flow with BamApiConfig::dedup: one ingest (strand bit and MAPQ per read), one
+// qmcp_hip_solve_dedup_host call in pair mode with mate completion (QuasiMcpHipSolver::solve_dedup), find_pairs,
+// write_paired_reads -- duplicate pairs are simply not written; filtered_path keeps its meaning of ingest filters only.
+// targets / report / ladder_levels / stratify / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given so
+// that it refuses the combinations it refuses.  dedup_report (may be NULL): a TSV written after the output -- the
+// statistics, then one size<TAB>families line per bin of the family-size histogram at 64 bins.  Returns the number of
+// records written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the configuration is
+// refused, -5 when the report cannot be written.
+std::int64_t qmcp_host_downsample_bam_dedup(const char* solver_name, const char* in_path, const char* out_path,
+                                            const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                            std::uint32_t min_mapq, int per_reference, const char* targets,
+                                            const char* report, const std::uint32_t* ladder_levels,
+                                            std::uint32_t n_ladder_levels, const char* stratify, const char* bed,
+                                            const char* tsv, int amplicons_by_reference, const char* dedup_report,
+                                            char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.dedup = true;
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
+        if (bed && bed[0]) cfg.bed_filepath = bed;
+        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        if (cfg.dedup && cfg.per_reference && cfg.amplicons_by_reference)
+            throw std::invalid_argument("duplicate-aware downsampling does not take amplicon files");
+        bam_api::BamApi api(in_path, cfg);
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("duplicate-aware downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no duplicate-aware downsampling");
+        constexpr std::uint32_t kBins = 64;
+        std::unique_ptr<qmcp::Solution> solution = hip->solve_dedup(max_coverage, api, kBins);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        if (dedup_report && dedup_report[0]) {
+            const qmcp_hip_dedup_stats& ds = hip->last_dedup_stats();
+            std::FILE* f = std::fopen(dedup_report, "w");
+            if (f == nullptr) return -5;
+            std::fprintf(f, "#stat\tvalue\n");
+            std::fprintf(f, "units\t%llu\nfamilies\t%llu\nduplicate_units\t%llu\nlargest_family\t%llu\nreads_survived\t%llu\n",
+                         (unsigned long long)ds.units, (unsigned long long)ds.families,
+                         (unsigned long long)ds.duplicate_units, (unsigned long long)ds.largest_family,
+                         (unsigned long long)ds.reads_survived);
+            std::fprintf(f, "#size\tfamilies\n");
+            for (std::uint32_t b = 0; b < kBins; ++b)
+                std::fprintf(f, "%u\t%llu\n", b + 1, (unsigned long long)hip->last_dedup_hist()[b]);
+            if (std::fclose(f) != 0) return -5;
+        }
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

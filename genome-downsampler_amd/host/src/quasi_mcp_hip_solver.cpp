@@ -177,6 +177,47 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_targets(std::uint32_t require
     return expand_kept(n, t0);
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_dedup(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                                         std::uint32_t hist_bins) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.dedup() || !reads.has_contig_ids() || reads.contig_ids.size() != n || reads.strata.size() != n)
+        throw std::invalid_argument("duplicate-aware downsampling needs a BamApi built with BamApiConfig::dedup");
+    if (reads.qualities.size() != n) throw std::invalid_argument("reads without one quality each");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
+    dedup_hist_.assign(hist_bins, 0);
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    const int rc = qmcp_hip_solve_dedup_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), reads.strata.data(),
+                                             reads.qualities.data(), n, reads.contig_lengths.data(),
+                                             (std::uint32_t)reads.contig_lengths.size(), required_cover,
+                                             QMCP_DEDUP_PAIRS | QMCP_DEDUP_COMPLETE_PAIRS, mask.data(), nullptr,
+                                             hist_bins ? dedup_hist_.data() : nullptr, hist_bins, &stats_, &dstats_);
+    if (rc != QMCP_OK) die("qmcp_hip_solve_dedup_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    // the context holds the completed mask: at most two reads per read the solve kept
+    auto kept = std::make_unique<Solution>();
+    const std::uint64_t upper = std::min<std::uint64_t>(n, 2 * stats_.n_kept);
+    kept->resize(upper);
+    std::uint64_t n_out = 0;
+    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
+    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
+    kept->resize(n_out);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return kept;
+}
+
 std::vector<std::unique_ptr<Solution>> QuasiMcpHipSolver::solve_ladder(std::uint32_t required_cover,
                                                                        bam_api::BamApi& bam_api,
                                                                        const std::vector<std::uint32_t>& levels) {

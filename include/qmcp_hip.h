@@ -665,6 +665,72 @@ int qmcp_hip_solve_stratified_device(qmcp_hip_ctx* ctx,
                                      uint64_t* d_keep_mask_out, qmcp_hip_stratum_row* rows_out, void* hip_stream,
                                      qmcp_hip_stats* stats);
 
+/* Duplicate-aware downsampling: duplicate families are collapsed to one representative each BEFORE the solve, so that a
+ * PCR or optical duplicate does not count towards min(coverage, M) like an independent read.  starts, ends, contig_ids,
+ * n_reads, contig_lengths / n_contigs, max_coverage, keep_mask_out, stats, limits and errors are those of
+ * qmcp_hip_solve_by_contig_host / _device.  In addition:
+ *   tags        one uint32 per read, any value (strand, a library id, a UMI hash); NULL: every tag is 0.
+ *   qualities   one uint32 per read; NULL: every quality is 0.  A range (max - min over the placed reads) above 65535
+ *               fails with QMCP_ERANGE before anything is written, as in the quality entries.
+ *   flags       QMCP_DEDUP_PAIRS selects pair mode, QMCP_DEDUP_COMPLETE_PAIRS asks for mate completion.  Either with an
+ *               odd n_reads, COMPLETE_PAIRS without PAIRS, and unknown bits fail with QMCP_EINVAL.
+ *   dup_mask_out  may be NULL; ceil(n_reads / 64) words, fully overwritten.
+ *   hist_out, hist_bins  may be NULL / 0; hist_bins uint64 words in host memory (both entries), at most 4096 bins
+ *               (QMCP_ERANGE beyond).
+ *   dstats      may be NULL.
+ * CELL: the cell of a placed read is (contig, start, end, tag).  All QMCP_NO_CONTIG reads share one extra cell U.
+ * READ MODE (default): the unit is a placed read and a family is a cell.  A unit's score is its quality; the
+ * representative of a family is the unit of highest score, then of lowest index.  Unplaced reads are in no family.
+ * PAIR MODE: unit q is the reads (2q, 2q + 1), eligible iff at least one mate is placed.  Its signature is the UNORDERED
+ * pair {cell(2q), cell(2q + 1)} (mates on different contigs are fine), a family is the set of eligible units with equal
+ * signature, a unit's score is the sum of the qualities of its placed mates, the representative is the unit of highest
+ * score, then of lowest q.  A pair with both mates unplaced is in no family.
+ * RESULT: the survivors are the reads of all representatives (in pair mode an unplaced mate of a representative
+ * included).  keep_mask_out is the mask qmcp_hip_solve_by_contig_host returns for the survivors in input order, mapped
+ * back to input positions; every other bit is clear.  With COMPLETE_PAIRS the OR inside each aligned bit pair is applied
+ * afterwards: it can only add the mate of a kept survivor, a survivor itself.  Bit i of dup_mask_out is set iff read i
+ * belongs to a unit that is in a family and is not its representative (in pair mode both mates get the bit, an unplaced
+ * one too), so keep & dup == 0 always.  hist_out[k - 1] is the number of families of size k for k < hist_bins, the last
+ * bin holds the sizes >= hist_bins.  When no two units share a cell / signature, the mask is that of
+ * qmcp_hip_solve_by_contig_host bit for bit.
+ * VALIDATION: every read is validated as the by-contig entries do -- the reads of duplicates too -- before anything is
+ * written: a bad contig id gives QMCP_EINVAL, a bad read QMCP_EREAD, and no output buffer has been touched.
+ * HOW: one pass validates and takes the ranges of tag, quality and span; the widths of the key gstart | span - min_span |
+ * tag - tag_min | q_max - q come from those ranges (tags == NULL and one span cost nothing); the stable LSD radix sorts
+ * {key, index} as 32-bit records, as split 64-bit keys, or -- beyond 64 bits -- field by field, least significant first.
+ * A family then is a run of the sorted order with its representative first.  Pair mode sorts the reads by cell first
+ * (dense cell ids), then the units by min id | max id | score_max - score.  Survivor and duplicate bits, the histogram
+ * and the counters are made on the device; the survivors are compacted in input order, solved, and the mask expanded.
+ * stats (may be NULL) are the inner solve's: n_reads counts the placed survivors.
+ * The pass is blocking (no _begin / _end form).  The device entry takes the columns and both masks in device memory
+ * (contig_lengths, hist_out and the stats stay on the host), columns at any 4-byte alignment, and is ordered after
+ * `hip_stream` (or NULL) as qmcp_hip_solve_device is.  The host entry leaves the keep mask in the context. */
+#define QMCP_DEDUP_PAIRS 1u
+#define QMCP_DEDUP_COMPLETE_PAIRS 2u
+typedef struct qmcp_hip_dedup_stats {
+    uint64_t units;            /* placed reads (read mode), pairs with a placed mate (pair mode)                      */
+    uint64_t families;         /* distinct cells / signatures among the units                                         */
+    uint64_t duplicate_units;  /* units - families                                                                    */
+    uint64_t largest_family;   /* units of the largest family                                                         */
+    uint64_t reads_survived;   /* reads handed to the inner solve                                                     */
+    uint32_t key_bits;         /* width of the key the units were sorted by                                           */
+    uint32_t sort_passes;      /* 8-bit LSD passes, both sorts of pair mode together                                  */
+    float ms_dedup;            /* device time of everything except the inner solve                                    */
+} qmcp_hip_dedup_stats;
+int qmcp_hip_solve_dedup_host(qmcp_hip_ctx* ctx,
+                              const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                              const uint32_t* tags, const uint32_t* qualities, uint64_t n_reads,
+                              const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage, uint32_t flags,
+                              uint64_t* keep_mask_out, uint64_t* dup_mask_out, uint64_t* hist_out, uint32_t hist_bins,
+                              qmcp_hip_stats* stats, qmcp_hip_dedup_stats* dstats);
+int qmcp_hip_solve_dedup_device(qmcp_hip_ctx* ctx,
+                                const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                const uint32_t* d_tags, const uint32_t* d_qualities, uint64_t n_reads,
+                                const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                uint32_t flags, uint64_t* d_keep_mask_out, uint64_t* d_dup_mask_out, uint64_t* hist_out,
+                                uint32_t hist_bins, void* hip_stream, qmcp_hip_stats* stats,
+                                qmcp_hip_dedup_stats* dstats);
+
 #ifdef __cplusplus
 }
 #endif
