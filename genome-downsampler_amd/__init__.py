@@ -9,6 +9,7 @@ import, and without a GPU every solver call raises :class:`QmcpError`.
 """
 import contextlib
 import ctypes as C
+import heapq
 import os
 
 import numpy as np
@@ -37,6 +38,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_ladder_host", "qmcp_hip_solve_ladder_device",
     "qmcp_hip_solve_stratified_host", "qmcp_hip_solve_stratified_device",
     "qmcp_hip_solve_dedup_host", "qmcp_hip_solve_dedup_device",
+    "qmcp_hip_solve_profile_host", "qmcp_hip_solve_profile_device",
 )
 
 QMCP_OK = 0
@@ -101,6 +103,15 @@ class TargetStats(C.Structure):
     """qmcp_hip_target_stats: what the projection, compaction and expansion around a target solve did"""
     _fields_ = [("reads_on_target", C.c_uint64), ("reads_off_target", C.c_uint64), ("target_positions", C.c_uint64),
                 ("regions_in", C.c_uint32), ("regions_merged", C.c_uint32), ("ms_targets", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class ProfileStats(C.Structure):
+    """qmcp_hip_profile_stats: the cap table of a profile solve and what the kernel that builds need(p) counted"""
+    _fields_ = [("positions_in_regions", C.c_uint64), ("capped_positions", C.c_uint64), ("demand", C.c_uint64),
+                ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_profile", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -281,6 +292,12 @@ _hip.qmcp_hip_solve_dedup_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_uint64, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                              C.c_void_p, _u64p, C.c_uint32, C.c_void_p, C.POINTER(Stats),
                                              C.POINTER(DedupStats)]
+_hip.qmcp_hip_solve_profile_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p, _u32p,
+                                             _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p, C.POINTER(Stats),
+                                             C.POINTER(ProfileStats)]
+_hip.qmcp_hip_solve_profile_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                               C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(ProfileStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -354,6 +371,11 @@ if _host is not None:
                                                      C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
                                                      C.c_char_p, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_dedup.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                       C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p, _u32p,
+                                                       C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p,
+                                                       C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_profile.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -732,6 +754,51 @@ class Solver:
         self.last_stats, self.last_target_stats = st, ts
         return ts
 
+    @staticmethod
+    def _region_tables(n_contigs, region_offsets, region_starts, region_ends, region_caps):
+        if region_offsets is None:
+            return None, None, None, None
+        offs = _u32(region_offsets)
+        assert offs.size == n_contigs + 1, "region_offsets needs n_contigs + 1 entries"
+        cols = [None if a is None else _u32(a) for a in (region_starts, region_ends, region_caps)]
+        assert all(a is None or a.size >= int(offs[-1]) for a in cols), \
+            "region_starts / region_ends / region_caps are shorter than region_offsets says"
+        return (offs, *cols)
+
+    def solve_profile(self, starts, ends, contig_ids, contig_lengths, default_cap, region_offsets=None, region_starts=None,
+                      region_ends=None, region_caps=None, flags=0):
+        """a cap that varies along the genome (qmcp_hip_solve_profile_host): contig c owns regions
+        [region_offsets[c], region_offsets[c + 1]) of region_starts / region_ends (inclusive, any order, disjoint per
+        contig after clipping) with region_caps; default_cap everywhere else.  The kept set covers every position p
+        min(cov(p), cap(p)) times with the fewest reads (the canonical rule).  No regions: solve_by_contig at default_cap.
+        Host keep bitmask in INPUT order out; last_stats, last_profile_stats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ps = Stats(), ProfileStats()
+        _check(_hip.qmcp_hip_solve_profile_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                lengths.size, _p32(offs), _p32(r0), _p32(r1), _p32(caps), int(default_cap),
+                                                int(flags), _p64(mask), C.byref(st), C.byref(ps)))
+        self.last_stats, self.last_profile_stats = st, ps
+        return mask[:mask_words(n)]
+
+    def solve_profile_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, default_cap, d_mask,
+                             region_offsets=None, region_starts=None, region_ends=None, region_caps=None, flags=0,
+                             stream=0):
+        """solve_profile on device pointers (ints); the input-order mask is written to d_mask.  Returns the profile stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
+        st, ps = Stats(), ProfileStats()
+        _check(_hip.qmcp_hip_solve_profile_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                  C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                  _p32(offs), _p32(r0), _p32(r1), _p32(caps), int(default_cap), int(flags),
+                                                  C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(ps)))
+        self.last_stats, self.last_profile_stats = st, ps
+        return ps
+
     def _depth_call(self, entry, head, n, lengths, mask_arg, max_coverage, target_offsets, target_starts, target_ends,
                     padding, n_bins, tail):
         offs, t0, t1 = self._target_tables(lengths.size, target_offsets, target_starts, target_ends)
@@ -1078,6 +1145,71 @@ def targets_from_bed(bed_path, reference_names):
     return offsets, t0, t1
 
 
+def profile_from_bedgraph(path, reference_names):
+    """a coverage profile from a bedGraph file (four columns: chrom start end cap) matched to references by name ->
+    (offsets, starts, ends, caps) as Solver.solve_profile takes them: reference c owns regions
+    [offsets[c], offsets[c + 1]), ascending and disjoint.  bedGraph is 0-based half-open, so a line "chrom s e cap" is
+    the inclusive region [s, e - 1]; `track`, `browser` and `#` lines and blank lines are skipped.  Overlapping lines are
+    flattened here with the LATER line winning (the C ABI takes disjoint regions only); neighbouring pieces with one
+    cap are joined.  ValueError naming a chrom that matches no reference exactly, a cap that is no integer in
+    [0, 2^31), or a malformed line"""
+    names = [str(n) for n in reference_names]
+    index = {}
+    for k, name in enumerate(names):
+        index.setdefault(name, k)
+    per_ref = [[] for _ in names]
+    with open(path) as src:
+        for lineno, line in enumerate(src, 1):
+            text = line.strip()
+            if not text or text.startswith("#") or text.split()[0] in ("track", "browser"):
+                continue
+            fields = text.split("\t") if "\t" in text else text.split()
+            if len(fields) < 4:
+                raise ValueError(f"{path}:{lineno}: a bedGraph line needs chrom, start, end and cap")
+            chrom = fields[0]
+            try:
+                start, end = int(fields[1]), int(fields[2])
+            except ValueError:
+                raise ValueError(f"{path}:{lineno}: start and end must be integers") from None
+            try:
+                cap = int(fields[3])
+            except ValueError:
+                raise ValueError(f"{path}:{lineno}: the cap {fields[3]!r} is not an integer") from None
+            if start < 0 or end <= start or end > 0xFFFFFFFF:
+                raise ValueError(f"{path}:{lineno}: region [{start}, {end}) is empty or out of range")
+            if cap < 0 or cap >= 1 << 31:
+                raise ValueError(f"{path}:{lineno}: the cap {cap} is not in [0, 2^31)")
+            if chrom not in index:
+                raise ValueError(f"{path}:{lineno}: chrom {chrom!r} matches no reference of the file")
+            per_ref[index[chrom]].append((start, end - 1, cap))
+    flat_refs = []
+    for lines in per_ref:
+        # elementary intervals between the lines' bounds; each takes the cap of the last line that covers it (a sweep
+        # with a heap of the covering lines, latest on top, ended lines dropped lazily)
+        cuts = sorted({a for a, _, _ in lines} | {b + 1 for _, b, _ in lines})
+        order = sorted(range(len(lines)), key=lambda i: lines[i][0])
+        live, nxt, pieces = [], 0, []
+        for lo, hi in zip(cuts, cuts[1:]):
+            while nxt < len(order) and lines[order[nxt]][0] <= lo:
+                heapq.heappush(live, -order[nxt])
+                nxt += 1
+            while live and lines[-live[0]][1] < lo:
+                heapq.heappop(live)
+            if not live:
+                continue
+            cap = lines[-live[0]][2]
+            if pieces and pieces[-1][1] + 1 == lo and pieces[-1][2] == cap:
+                pieces[-1][1] = hi - 1
+            else:
+                pieces.append([lo, hi - 1, cap])
+        flat_refs.append(pieces)
+    offsets = np.zeros(len(names) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(r) for r in flat_refs])
+    flat = [reg for r in flat_refs for reg in r]
+    return (offsets, np.array([a for a, _, _ in flat], dtype=np.uint32), np.array([b for _, b, _ in flat], dtype=np.uint32),
+            np.array([c for _, _, c in flat], dtype=np.uint32))
+
+
 def window_regions(contig_lengths, size):
     """fixed windows of `size` positions over every contig (the last window of a contig is shorter), in the CSR form
     depth_report and solve_targets take: (offsets, starts, ends), inclusive bounds -- the regions of a mosdepth-style "--by size" report.  The report merges adjacent regions like
@@ -1392,7 +1524,7 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
                    targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
-                   ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None):
+                   ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1428,8 +1560,37 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     filtered_path keeps its meaning of ingest filters only.  dedup_report (a path): a TSV with the statistics, then one
     size<TAB>families line per family-size bin (DEDUP_REPORT_BINS bins, the last holding the larger sizes).  Needs
     per_reference=True; not together with targets, report, ladder, stratify, amplicon files or
-    "quasi-mcp-hip-quality" (ValueError).  False: nothing changes"""
+    "quasi-mcp-hip-quality" (ValueError).  False: nothing changes.
+    profile (a bedGraph file: chrom start end cap; profile_from_bedgraph): a cap that varies along the genome, with
+    max_coverage as the cap outside the file's regions -- one qmcp_hip_solve_profile_host call.  Chroms are matched to
+    the file's references by name, overlapping lines are flattened with the later line winning.  Needs
+    per_reference=True; not together with targets, report, ladder, stratify, dedup, amplicon files or
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
+    if profile is not None:
+        if not per_reference:
+            raise ValueError("a coverage profile needs per_reference=True")
+        if targets or report or ladder is not None or stratify is not None or dedup:
+            raise ValueError("a coverage profile does not go together with targets, a depth report, a coverage ladder, "
+                             "stratify or dedup")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("a coverage profile does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("a coverage profile does not take a solver that grades by quality")
+        names = reference_names(in_path)
+        offs, r0, r1, caps = profile_from_bedgraph(profile, names)
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_profile(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            1, _p32(offs), _p32(r0), _p32(r1), _p32(caps), len(names), None, None, 0, None, 0, None, None, 0, err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
     if dedup:
         if not per_reference:
             raise ValueError("duplicate-aware downsampling needs per_reference=True")

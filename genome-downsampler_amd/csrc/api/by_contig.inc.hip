@@ -8,11 +8,16 @@
 //      grouped order, solved by the ordinary multi-contig solve, and its mask ORed back into input order
 // Grouping happens once; a batch only gathers its own reads.
 // A coverage ladder (api/ladder.inc.hip) is this call with further levels run inside each batch, on its gathered columns.
+// A coverage profile (api/profile.inc.hip) is this call with every batch solved under its own regions' caps.
 namespace {
 
 struct LadderRun;
 int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, uint32_t nb, const uint64_t* roff,
                            const uint32_t* lengths, uint32_t n_contigs);
+struct ProfileRun;
+int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
+                        const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
+                        qmcp_hip_stats* st);
 
 // the batches' stats as one: counts and times summed, the route of the batch with the most reads
 void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, bool largest) {
@@ -45,7 +50,8 @@ void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, boo
 
 int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                               uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, uint32_t M, uint64_t* d_mask,
-                              qmcp_hip_stats* stats, LadderRun* ladder = nullptr) {
+                              qmcp_hip_stats* stats, LadderRun* ladder = nullptr,
+                              ProfileRun* profile = nullptr /* then M is the default cap */) {
     if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
     if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
     if (n64 > (1ull << 31))
@@ -150,8 +156,12 @@ int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
         for (uint32_t k = 0; k <= bt.n_contigs; ++k) roff[k] = offs[bt.first_contig + k] - offs[bt.first_contig];
         qmcp_hip_stats bs;
         std::memset(&bs, 0, sizeof(bs));
-        TRY(solve_on_device(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, roff.data(),
-                            lengths + bt.first_contig, bt.n_contigs, nb, M, (uint64_t*)c->bc_mask.p, &bs));
+        if (profile)
+            TRY(profile_solve_batch(c, *profile, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, roff.data(),
+                                    lengths, bt.first_contig, bt.n_contigs, nb, (uint64_t*)c->bc_mask.p, &bs));
+        else
+            TRY(solve_on_device(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, roff.data(),
+                                lengths + bt.first_contig, bt.n_contigs, nb, M, (uint64_t*)c->bc_mask.p, &bs));
         {
             KernelSpan sp(c, "k_bc_scatter_mask");
             qmcp::launch_bc_scatter_mask(st, (const uint64_t*)c->bc_mask.p, bsorted, nb, d_mask);

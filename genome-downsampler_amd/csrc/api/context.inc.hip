@@ -147,6 +147,9 @@ struct qmcp_hip_ctx {
     // the host entry's tag column and duplicate mask
     DevBuf dd_tab, dd_stat, dd_bare, dd_keys[2], dd_vals[2], dd_hist, dd_spine, dd_flag, dd_head, dd_cid, dd_surv, dd_words,
         dd_histo, dd_cs, dd_ce, dd_ci, dd_map, dd_maskc, dd_tags, dd_dupm;
+    // coverage profile (api/profile.inc.hip): a batch's need[] (min(cov, cap) per position, top bit = cut position), its
+    // regions in global positions (starts | ends | caps), and the call's two counters (capped positions, demand)
+    DevBuf pf_need, pf_tab, pf_stat;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

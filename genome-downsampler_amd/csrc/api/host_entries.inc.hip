@@ -170,7 +170,8 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->st_strata, &c->st_rows,
                       &c->dd_tab, &c->dd_stat, &c->dd_bare, &c->dd_keys[0], &c->dd_keys[1], &c->dd_vals[0], &c->dd_vals[1],
                       &c->dd_hist, &c->dd_spine, &c->dd_flag, &c->dd_head, &c->dd_cid, &c->dd_surv, &c->dd_words,
-                      &c->dd_histo, &c->dd_cs, &c->dd_ce, &c->dd_ci, &c->dd_map, &c->dd_maskc, &c->dd_tags, &c->dd_dupm};
+                      &c->dd_histo, &c->dd_cs, &c->dd_ce, &c->dd_ci, &c->dd_map, &c->dd_maskc, &c->dd_tags, &c->dd_dupm,
+                      &c->pf_need, &c->pf_tab, &c->pf_stat};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

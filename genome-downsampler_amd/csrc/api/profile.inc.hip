@@ -1,0 +1,337 @@
+// profile.inc.hip -- part of qmcp_api.hip (one translation unit).
+// qmcp_hip_solve_profile_host / _device: a cap per region, need(p) = min(cov(p), cap(p)).  The call is the by-contig solve
+// (api/by_contig.inc.hip: validation, grouping, batches, gather, mask scatter) with every batch solved under its own
+// regions:
+//   1. cap_table.h builds the table on the host (a bad table fails here, before anything is copied or launched)
+//   2. a batch without a region is the unchanged solve at default_cap (a call without regions is therefore exactly
+//      qmcp_hip_solve_by_contig_* at default_cap); a batch whose largest cap is 0 keeps nothing
+//   3. any other batch takes the sort-based mixed-span route whatever its spans (span_bits == 0 is legal):
+//      k_prepare -> k_general_keys + ecnt scan -> radix -> bucket heads -> k_profile_need -> [k_profile_cuts +
+//      k_build_segments] -> capped sweep -> k_mark.  Windows as plan_mixed_sweep chooses them for M = the batch's largest
+//      cap, exact cuts only.  One blocking round trip after k_prepare (span statistics, validation) and one at the end
+//      (kept count, stretches), as the mixed route of the plain solve has.
+// Buffers: the solve's own arena for everything the plain mixed route uses; need[] in pf_need, the batch's regions in
+// pf_tab, the two counters in pf_stat.
+namespace {
+
+struct ProfileRun {
+    const qmcp::CapTable* tab = nullptr;
+    uint32_t default_cap = 0;
+    float ms_profile = 0.f;
+    std::vector<uint32_t> gs, ge, gcap;  // the batch's regions in its global positions
+};
+
+int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
+                        const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
+                        qmcp_hip_stats* st_out) {
+    const qmcp::CapTable& tab = *pf.tab;
+    const uint32_t* lengths = lengths_all + first_contig;
+    const uint32_t r0 = tab.offs[first_contig], r1 = tab.offs[first_contig + n_contigs];
+    uint32_t max_cap = pf.default_cap;
+    for (uint32_t k = r0; k < r1; ++k) max_cap = std::max(max_cap, tab.cap[k]);
+    if (r0 == r1 && max_cap != 0)
+        return solve_on_device(c, d_starts, d_ends, roff, lengths, n_contigs, n64, pf.default_cap, d_mask, st_out);
+    if (c->pending) return fail(QMCP_EINVAL, "a solve is already pending on this context (call qmcp_hip_solve_end)");
+    Problem pr;
+    TRY(check_problem(roff, lengths, n_contigs, n64, pr));
+    const uint32_t n = (uint32_t)pr.n, ltot = (uint32_t)pr.ltot;
+    const size_t mask_words = (size_t)((n64 + 63) / 64);
+    hipStream_t st = c->stream;
+    qmcp_hip_stats local;
+    std::memset(&local, 0, sizeof(local));
+    local.n_reads = n64;
+    local.n_contigs = n_contigs;
+    local.total_length = pr.ltot;
+    local.path = QMCP_PATH_GENERAL;
+    if (mask_words) HIP_TRY(hipMemsetAsync(d_mask, 0, mask_words * sizeof(uint64_t), st));
+    if (n == 0 || ltot == 0 || max_cap == 0) {  // (reads on zero-length contigs were refused by k_bc_keys)
+        if (st_out) *st_out = local;
+        return QMCP_OK;
+    }
+    if (!c->h_scalars) HIP_TRY(hipHostMalloc((void**)&c->h_scalars, 16 * sizeof(unsigned long long), hipHostMallocDefault));
+    // the arena, sized before anything is queued
+    const uint32_t n_tiles = qmcp::sort_tiles(n);
+    const uint32_t n_reg = r1 - r0;
+    c->sized = false;
+    {
+        const uint32_t spine_a = qmcp::scan_spine_entries(256u * n_tiles);
+        const uint32_t spine_b = std::max(qmcp::scan_spine_entries(ltot + 1), qmcp::scan_spine_entries(n + 1)) + 1;
+        TRY(ensure(c, c->spine, (size_t)std::max(spine_a, spine_b) * sizeof(uint32_t) + 16));
+        TRY(ensure(c, c->hist, (size_t)256 * std::max(qmcp::seg_tile_bound(n), n_tiles) * sizeof(uint32_t)));
+        TRY(ensure(c, c->keys[0], (size_t)n * sizeof(uint64_t)));
+        TRY(ensure(c, c->keys[1], (size_t)n * sizeof(uint64_t)));
+        TRY(ensure(c, c->vals[0], (size_t)n * sizeof(uint32_t)));
+        TRY(ensure(c, c->vals[1], (size_t)n * sizeof(uint32_t)));
+        TRY(ensure(c, c->boff, ((size_t)ltot + 1) * sizeof(uint32_t)));
+        TRY(ensure(c, c->ecnt, ((size_t)ltot + 1) * sizeof(uint32_t)));
+        TRY(ensure(c, c->eoff, ((size_t)ltot + 1) * sizeof(uint32_t)));
+        TRY(ensure(c, c->selend, ((size_t)ltot + 8) * sizeof(uint32_t)));
+        TRY(ensure(c, c->next_head, ((size_t)n + 2) * sizeof(uint32_t)));
+        TRY(ensure(c, c->scalars, 64));
+        TRY(ensure(c, c->stats, 12 * sizeof(uint32_t)));
+        TRY(ensure(c, c->segs, qmcp::sweep_segment_words(n_contigs < 256 ? n_contigs : 0, qmcp::kMaxSweepWindows) * sizeof(uint32_t)));
+        TRY(ensure(c, c->pf_need, ((size_t)ltot + 8) * sizeof(uint32_t)));
+        TRY(ensure(c, c->pf_tab, 3 * (size_t)n_reg * sizeof(uint32_t) + 16));
+    }
+    c->grew_mid_solve = 0;
+    c->mixed_seen = true;
+    HIP_TRY(hipEventRecord(c->ev[EV_BEGIN], st));
+    TRY(upload_tables(c, roff, pr));
+    c->sized = true;
+    qmcp::batch_cap_table(tab, lengths_all, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
+    uint32_t* d_rs = (uint32_t*)c->pf_tab.p;
+    uint32_t* d_re = d_rs + n_reg;
+    uint32_t* d_cap = d_re + n_reg;
+    if (n_reg) {
+        HIP_TRY(hipMemcpyAsync(d_rs, pf.gs.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_re, pf.ge.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_cap, pf.gcap.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
+    }
+    // span statistics, validation, global start positions (vals[1]): the one read-back that shapes the keys
+    uint32_t hs[3];
+    TRY(run_prepare(c, d_starts, d_ends, pr, nullptr, true, false, false, 0, nullptr, hs));
+    HIP_TRY(hipEventRecord(c->ev[EV_PREP], st));
+    const uint32_t min_span = hs[0], max_span = hs[1];
+    local.min_span = min_span;
+    local.max_span = max_span;
+    if (max_span > qmcp::kMaxGeneralSpan)
+        return fail(QMCP_ERANGE, "reads with span %u > %u are not supported by this build", max_span, qmcp::kMaxGeneralSpan);
+    const uint32_t pos_bits = bit_width(ltot - 1) == 0 ? 1u : bit_width(ltot - 1);
+    const uint32_t span_bits = bit_width(max_span - min_span);
+    const bool wide = pos_bits + span_bits > 32;
+    const uint32_t* d_gstart = (const uint32_t*)c->vals[1].p;
+    HIP_TRY(hipMemsetAsync(c->ecnt.p, 0, ((size_t)ltot + 1) * sizeof(uint32_t), st));
+    {
+        KernelSpan sp(c, "k_general_keys");
+        qmcp::launch_general_keys(st, wide, d_gstart, d_starts, d_ends, n, span_bits, max_span, nullptr,
+                                  wide ? c->keys[0].p : c->vals[0].p, (uint32_t*)c->ecnt.p, ltot + 1);
+    }
+    HIP_TRY(hipGetLastError());
+    TRY(scan_counts(c, c->ecnt, c->eoff, ltot));
+    HIP_TRY(hipEventRecord(c->ev[EV_SCAN], st));
+    HIP_TRY(hipMemsetAsync(c->scalars.p, 0, 64, st));
+    // radix bucketing: stable LSD, 8-bit digits (as the plain solve's sort-based routes)
+    const uint32_t passes = (pos_bits + span_bits + 7) / 8;
+    local.sort_passes = passes;
+    int kin = 0, vin = 0;
+    if (!wide) {
+        const uint32_t* d_key32 = (const uint32_t*)c->vals[0].p;
+        const void* recs_in = nullptr;
+        for (uint32_t p = 0; p < passes; ++p) {
+            const bool first = p == 0;
+            const int kout = first ? 0 : (kin ^ 1);
+            KernelSpan sp(c, "radix pass (hist, scan, scatter)");
+            qmcp::launch_radix_hist_rec(st, first, d_key32, recs_in, n, 8 * p, (uint32_t*)c->hist.p);
+            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->hist.p, 256u * n_tiles, (uint32_t*)c->hist.p,
+                                        (uint32_t*)c->spine.p, false);
+            qmcp::launch_radix_scatter_rec(st, first, d_key32, recs_in, n, 8 * p, (const uint32_t*)c->hist.p, c->keys[kout].p);
+            kin = kout;
+            recs_in = c->keys[kin].p;
+        }
+    } else {
+        const uint32_t* vals_in = nullptr;
+        for (uint32_t p = 0; p < passes; ++p) {
+            const int kout = kin ^ 1, vout = (vals_in == nullptr) ? 0 : (vin ^ 1);
+            KernelSpan sp(c, "radix pass (hist, scan, scatter)");
+            qmcp::launch_radix_hist(st, true, c->keys[kin].p, n, 8 * p, (uint32_t*)c->hist.p);
+            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->hist.p, 256u * n_tiles, (uint32_t*)c->hist.p,
+                                        (uint32_t*)c->spine.p, false);
+            qmcp::launch_radix_scatter(st, true, c->keys[kin].p, vals_in, n, 8 * p, (const uint32_t*)c->hist.p, c->keys[kout].p,
+                                       (uint32_t*)c->vals[vout].p);
+            kin = kout;
+            vin = vout;
+            vals_in = (const uint32_t*)c->vals[vin].p;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(c->boff.p, 0xFF, ((size_t)ltot + 1) * sizeof(uint32_t), st));
+    {
+        KernelSpan sp(c, "k_bucket_heads");
+        qmcp::launch_bucket_heads(st, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, n, span_bits, ltot,
+                                  (uint32_t*)c->boff.p);
+    }
+    {
+        KernelSpan sp(c, "reverse_min_scan(3 kernels)");
+        qmcp::launch_reverse_min_scan(st, (uint32_t*)c->boff.p, ltot + 1, (uint32_t*)c->spine.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
+    // need[], cut points
+    const uint32_t* d_need = (const uint32_t*)c->pf_need.p;
+    const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
+    const uint32_t windows = qmcp::plan_mixed_sweep(c->opt, n, max_span, ltot, n_contigs, max_cap, in_regs, false).windows;
+    const uint32_t* seg = nullptr;
+    uint32_t n_seg_max = 0;
+    uint32_t* d_iters = (uint32_t*)((char*)c->scalars.p + 16);
+    EventPair ev_pf(c);
+    if (!ev_pf.a || !ev_pf.b) return fail(QMCP_EHIP, "event creation failed");
+    HIP_TRY(hipEventRecord(ev_pf.a, st));
+    {
+        KernelSpan sp(c, "k_profile_need");
+        qmcp::launch_profile_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, d_rs, d_re, d_cap, n_reg,
+                                  pf.default_cap, (uint32_t*)c->pf_need.p, (unsigned long long*)c->pf_stat.p);
+    }
+    if (windows != 0) {
+        KernelSpan sp(c, "k_profile_cuts");
+        seg = qmcp::launch_profile_segments(st, d_need, (const uint64_t*)c->poff.p, n_contigs, ltot, windows, (uint32_t*)c->segs.p);
+        n_seg_max = n_contigs + windows;
+        HIP_TRY(hipMemcpyAsync(d_iters + 2, seg, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipEventRecord(ev_pf.b, st));
+    HIP_TRY(hipGetLastError());
+    // the capped sweep
+    bool swept = false;
+    if (in_regs) {
+        {
+            KernelSpan sp(c, "k_group_heads");
+            qmcp::launch_group_heads(st, wide, c->keys[kin].p, n, (uint32_t*)c->next_head.p);
+        }
+        {
+            KernelSpan sp(c, "reverse_min_scan(3 kernels)");
+            qmcp::launch_reverse_min_scan(st, (uint32_t*)c->next_head.p, n + 1, (uint32_t*)c->spine.p);
+        }
+        KernelSpan sp(c, "k_sweep_general_reg(capped)");
+        swept = qmcp::launch_sweep_general_reg_capped(st, wide, (const uint32_t*)c->boff.p, d_need, c->keys[kin].p,
+                                                      (const uint32_t*)c->next_head.p, (const uint64_t*)c->poff.p, n_contigs,
+                                                      span_bits, max_span, (uint32_t*)c->selend.p, seg, n_seg_max);
+    }
+    if (!swept) {
+        uint32_t ring = 64;
+        while (ring <= max_span) ring <<= 1;
+        uint32_t* g_rings = nullptr;
+        if (max_span > qmcp::kMaxLdsRingSpan) {  // long reads: the two rings of a workgroup no longer fit LDS
+            const size_t n_wg = seg ? n_seg_max : n_contigs;
+            TRY(ensure(c, c->rings, n_wg * 2 * (size_t)ring * sizeof(uint32_t)));
+            g_rings = (uint32_t*)c->rings.p;
+        }
+        KernelSpan sp(c, "k_sweep_general(capped)");
+        qmcp::launch_sweep_general_capped(st, wide, (const uint32_t*)c->boff.p, d_need, c->keys[kin].p,
+                                          (const uint64_t*)c->poff.p, n_contigs, span_bits, max_span, (uint32_t*)c->selend.p,
+                                          ring, seg, n_seg_max, g_rings);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], st));
+    {
+        KernelSpan sp(c, "k_mark");
+        qmcp::launch_mark(st, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, ltot, (const uint32_t*)c->boff.p,
+                          (const uint32_t*)c->selend.p, d_mask, (unsigned long long*)c->scalars.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[EV_MARK], st));
+    HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars.p, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    collect_spans(c);
+    local.n_kept = c->h_scalars[0];
+    local.sweep_stretches = (uint32_t)(c->h_scalars[3] & 0xFFFFFFFFu);
+    if (seg == nullptr)  // one wave per non-empty contig
+        for (uint32_t k = 0; k < n_contigs; ++k) local.sweep_stretches += lengths[k] != 0 ? 1u : 0u;
+    local.ms_prepare = elapsed(c->ev[EV_BEGIN], c->ev[EV_PREP]);
+    local.ms_scan = elapsed(c->ev[EV_PREP], c->ev[EV_SCAN]);
+    local.ms_sort = elapsed(c->ev[EV_SCAN], c->ev[EV_SORT]);
+    local.ms_sweep = elapsed(c->ev[EV_SORT], c->ev[EV_SWEEP]);
+    local.ms_mark = elapsed(c->ev[EV_SWEEP], c->ev[EV_MARK]);
+    local.ms_total = elapsed(c->ev[EV_BEGIN], c->ev[EV_MARK]);
+    local.arena_grown_mid_solve = c->grew_mid_solve;
+    pf.ms_profile += elapsed(ev_pf.a, ev_pf.b);
+    if (st_out) *st_out = local;
+    return QMCP_OK;
+}
+
+// the checks both entries make before anything is copied or launched, and the table
+int check_profile_call(uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs, const uint32_t* region_offsets,
+                       const uint32_t* region_starts, const uint32_t* region_ends, const uint32_t* region_caps,
+                       uint32_t default_cap, uint32_t flags, qmcp::CapTable& tab) {
+    if (n_reads > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n_reads);
+    if (!contig_lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
+    if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
+    if (flags != 0) return fail(QMCP_EINVAL, "unknown flag bits 0x%x", flags);
+    const int rc = qmcp::build_cap_table(region_offsets, region_starts, region_ends, region_caps, contig_lengths, n_contigs, tab);
+    if (rc == QMCP_ERANGE) return fail(QMCP_ERANGE, "a region's cap is 2^31 or more");
+    if (rc != QMCP_OK)
+        return fail(QMCP_EINVAL, "region table: offsets must start at 0 and never decrease, arrays must not be null, every "
+                                 "region needs start <= end, and the regions of one contig must be disjoint after clipping");
+    if (default_cap >= qmcp::kCapLimit) return fail(QMCP_ERANGE, "default_cap %u is 2^31 or more", default_cap);
+    return QMCP_OK;
+}
+
+int solve_profile_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                            uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const qmcp::CapTable& tab,
+                            uint32_t default_cap, uint64_t* d_mask, qmcp_hip_stats* stats, qmcp_hip_profile_stats* pstats) {
+    qmcp_hip_profile_stats ps;
+    std::memset(&ps, 0, sizeof(ps));
+    ps.regions_in = tab.regions_in;
+    ps.regions_used = tab.regions_used;
+    ps.positions_in_regions = tab.positions;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (pstats) *pstats = ps;
+    if (tab.regions_used == 0 && default_cap != 0)  // the fast path: the plain by-contig call
+        return solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, default_cap, d_mask, stats);
+    TRY(ensure(c, c->pf_stat, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->pf_stat.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    ProfileRun pf;
+    pf.tab = &tab;
+    pf.default_cap = default_cap;
+    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, default_cap, d_mask, stats, nullptr, &pf));
+    unsigned long long counters[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counters, c->pf_stat.p, sizeof(counters), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ps.capped_positions = counters[0];
+    ps.demand = counters[1];
+    ps.ms_profile = pf.ms_profile;
+    if (pstats) *pstats = ps;
+    return QMCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmcp_hip_solve_profile_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                const uint32_t* region_offsets, const uint32_t* region_starts, const uint32_t* region_ends,
+                                const uint32_t* region_caps, uint32_t default_cap, uint32_t flags, uint64_t* keep_mask_out,
+                                qmcp_hip_stats* stats, qmcp_hip_profile_stats* pstats) {
+    TRY(use_device(c));
+    if (n_reads && (!starts || !ends || !contig_ids || !keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    qmcp::CapTable tab;
+    TRY(check_profile_call(n_reads, contig_lengths, n_contigs, region_offsets, region_starts, region_ends, region_caps,
+                           default_cap, flags, tab));
+    const size_t nb = (size_t)n_reads * sizeof(uint32_t);
+    const size_t words = (size_t)((n_reads + 63) / 64);
+    TRY(ensure(c, c->in_starts, nb));
+    TRY(ensure(c, c->in_ends, nb));
+    TRY(ensure(c, c->in_aux0, nb));
+    TRY(ensure(c, c->mask, words * sizeof(uint64_t)));
+    c->mask_reads = 0;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(c->in_starts.p, starts, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(solve_profile_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
+                                (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, tab, default_cap,
+                                (uint64_t*)c->mask.p, stats, pstats));
+    if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mask_reads = n_reads;
+    return QMCP_OK;
+}
+
+int qmcp_hip_solve_profile_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends,
+                                  const uint32_t* d_contig_ids, uint64_t n_reads, const uint32_t* contig_lengths,
+                                  uint32_t n_contigs, const uint32_t* region_offsets, const uint32_t* region_starts,
+                                  const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                  uint32_t flags, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                  qmcp_hip_profile_stats* pstats) {
+    TRY(use_device(c));
+    if (n_reads && (!d_starts || !d_ends || !d_contig_ids || !d_keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    qmcp::CapTable tab;
+    TRY(check_profile_call(n_reads, contig_lengths, n_contigs, region_offsets, region_starts, region_ends, region_caps,
+                           default_cap, flags, tab));
+    TRY(order_after(c, hip_stream));
+    return solve_profile_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, tab, default_cap,
+                                   d_keep_mask_out, stats, pstats);
+}
+
+}  // extern "C"

@@ -38,7 +38,10 @@ __device__ __forceinline__ uint32_t seed_stretch_expiry(Sorted skeys, const uint
 // GRING: the two rings live in global memory (`g_rings`, 2 * ring_size words per workgroup) instead
 // of LDS -- spans beyond 16 383 (long reads); every ring access is then a write-through / L1-bypassing
 // access, ordered by the wave's program order and the workgroup barriers as the LDS ones are.
-template <typename Sorted, bool GRING>
+// kCapped (a coverage profile, kernels/profile.inc.hip): need(p) is read from k_profile_need's array, which comes in
+// the place of `eoff` (its top bit, the cut flag, masked off); M is not looked at.  Everything else is the same walk.
+static constexpr uint32_t kNeedValueMask = 0x7FFFFFFFu;
+template <typename Sorted, bool GRING, bool kCapped = false>
 __global__ __launch_bounds__(64) void k_sweep_general(const uint32_t* __restrict__ boff,
                                                       const uint32_t* __restrict__ eoff,
                                                       Sorted skeys,
@@ -83,8 +86,13 @@ __global__ __launch_bounds__(64) void k_sweep_general(const uint32_t* __restrict
             wr(s_ptr, p & rmask, 0u);
         }
         __syncthreads();
-        const uint32_t cov = boff[gp + 1] - eoff[gp];
-        const uint32_t need = min(cov, M);
+        uint32_t need;
+        if constexpr (kCapped) {
+            need = eoff[gp] & kNeedValueMask;
+        } else {
+            const uint32_t cov = boff[gp + 1] - eoff[gp];
+            need = min(cov, M);
+        }
         uint32_t k = need > cur ? need - cur : 0u;
         while (k > 0) {
             // best head among buckets q in (p - max_span, p]
@@ -347,7 +355,8 @@ __device__ __forceinline__ uint32_t reg_sweep_key(uint32_t gx, uint32_t gy, uint
 
 static constexpr uint32_t kSpecSnapWords = 512;  // >= the register sweep's window of live buckets
 
-template <typename Sorted, int B, int kRegLoaders>
+// kCapped: as in k_sweep_general -- `eoff` is the profile's need[] array, read by the loader waves.
+template <typename Sorted, int B, int kRegLoaders, bool kCapped = false>
 __global__ __launch_bounds__(64 * (1 + kRegLoaders)) void k_sweep_general_reg(
     const uint32_t* __restrict__ boff, const uint32_t* __restrict__ eoff, Sorted skeys,
     const uint32_t* __restrict__ next_head, const uint64_t* __restrict__ contig_pos_off,
@@ -429,7 +438,8 @@ __global__ __launch_bounds__(64 * (1 + kRegLoaders)) void k_sweep_general_reg(
             if (q < L) {
                 b0 = cb[q];
                 b1 = cb[q + 1];
-                need = min(b1 - ce[q], M);  // cov(q) = boff[q + 1] - eoff[q]
+                if constexpr (kCapped) need = ce[q] & kNeedValueMask;
+                else need = min(b1 - ce[q], M);  // cov(q) = boff[q + 1] - eoff[q]
                 load_group(b0, b1, q, x0, y0);
                 load_group(b0 + y0, b1, q, x1, y1);
                 nj = b0 + y0 + y1;

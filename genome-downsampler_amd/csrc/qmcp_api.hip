@@ -31,6 +31,7 @@
 #include "dedup_plan.h"
 #include "amplicon_table.h"
 #include "target_table.h"
+#include "cap_table.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
@@ -56,6 +57,8 @@
 //                       every stratum solved in batches of its own at its cap, one row of counts per stratum
 //   dedup               duplicate families (reads or pairs with equal cells) collapsed to their best unit before the
 //                       by-contig solve; duplicate mask, family-size histogram and statistics from the device
+//   profile             one cap per region (a piecewise-constant cap along every contig): the cap table, and a batch's
+//                       solve on the sort-based mixed route with need(p) = min(cov(p), cap(p)) built on the device
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -72,3 +75,4 @@
 #include "api/ladder.inc.hip"
 #include "api/stratified.inc.hip"
 #include "api/dedup.inc.hip"
+#include "api/profile.inc.hip"

@@ -129,6 +129,23 @@ void launch_spec_verify_merge_mixed(hipStream_t st, const uint32_t* seg, uint32_
 void launch_mark(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals, uint32_t ltot,
                  const uint32_t* boff, const uint32_t* selend, uint64_t* mask,
                  unsigned long long* n_kept);
+// Coverage profile (kernels/profile.inc.hip): need[p] = min(cov(p), cap(p)) with the top bit set where cov(p) <= cap(p),
+// from a batch's sorted, disjoint regions in global positions (rs / re / cap, n_regions of them; default_cap elsewhere);
+// pstat[0] += positions with cov > cap, pstat[1] += the sum of need.  launch_profile_segments is launch_sweep_segments
+// reading that bit; the two capped sweeps take need[] where the scalar ones take eoff and M.
+void launch_profile_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, uint32_t ltot, const uint32_t* rs,
+                         const uint32_t* re, const uint32_t* cap, uint32_t n_regions, uint32_t default_cap, uint32_t* need,
+                         unsigned long long* pstat);
+const uint32_t* launch_profile_segments(hipStream_t st, const uint32_t* need, const uint64_t* d_poff, uint32_t n_contigs,
+                                        uint32_t ltot, uint32_t n_windows, uint32_t* seg_words);
+bool launch_sweep_general_reg_capped(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* need,
+                                     const void* sorted, const uint32_t* next_head, const uint64_t* d_poff,
+                                     uint32_t n_contigs, uint32_t span_bits, uint32_t max_span, uint32_t* selend,
+                                     const uint32_t* seg, uint32_t n_seg_max);
+void launch_sweep_general_capped(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* need, const void* sorted,
+                                 const uint64_t* d_poff, uint32_t n_contigs, uint32_t span_bits, uint32_t max_span,
+                                 uint32_t* selend, uint32_t ring_size, const uint32_t* seg, uint32_t n_seg_max,
+                                 uint32_t* g_rings);
 void launch_bucket_heads(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals,
                          uint32_t n, uint32_t span_bits, uint32_t ltot, uint32_t* boff);
 void launch_reverse_min_scan(hipStream_t st, uint32_t* data, uint32_t n, uint32_t* spine);

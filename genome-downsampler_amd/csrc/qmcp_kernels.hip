@@ -44,6 +44,8 @@
 //                            keys, and the per-stratum rows as a segmented reduction over the grouped records
 //   dedup                    duplicate families collapsed before the solve: ranges and validation, composite keys, head
 //                            flags, cell ids, survivor / duplicate bits, family statistics, compaction of the survivors
+//   profile                  a cap that varies along the genome: need(p) = min(cov(p), cap(p)) per position with its cut
+//                            flag, the cut-point scan over it, and the launchers of the capped mixed-span sweeps
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -82,5 +84,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/depth_report.inc.hip"
 #include "kernels/stratified.inc.hip"
 #include "kernels/dedup.inc.hip"
+#include "kernels/profile.inc.hip"
 
 }  // namespace qmcp

@@ -78,6 +78,15 @@ class QuasiMcpHipSolver : public Solver {
     std::unique_ptr<Solution> solve_dedup(std::uint32_t required_cover, bam_api::BamApi& bam_api, std::uint32_t hist_bins);
     const qmcp_hip_dedup_stats& last_dedup_stats() const { return dstats_; }
     const std::vector<std::uint64_t>& last_dedup_hist() const { return dedup_hist_; }
+    // Coverage profile for the reads of a per-reference BamApi: qmcp_hip_solve_profile_host with the regions in CSR form
+    // per reference (offsets: one more entry than the file has references; inclusive bounds, disjoint per reference)
+    // and required_cover as the default cap.  std::invalid_argument for reads without contig ids or a table of other
+    // references, and for what the library refuses in the table (overlap, start > end, a cap of 2^31 or more);
+    // std::terminate on a device failure, like solve()
+    std::unique_ptr<Solution> solve_profile(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                            const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
+                                            const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps);
+    const qmcp_hip_profile_stats& last_profile_stats() const { return pstats_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -100,6 +109,7 @@ class QuasiMcpHipSolver : public Solver {
     std::vector<std::uint32_t> stratum_caps_;
     std::vector<qmcp_hip_stratum_row> stratum_rows_;
     qmcp_hip_dedup_stats dstats_{};
+    qmcp_hip_profile_stats pstats_{};
     std::vector<std::uint64_t> dedup_hist_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves

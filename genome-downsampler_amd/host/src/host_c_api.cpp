@@ -883,6 +883,60 @@ std::int64_t qmcp_host_downsample_bam_dedup(const char* solver_name, const char*
     }
 }
 
+// The file-to-file flow with a coverage profile: one per-reference ingest, one qmcp_hip_solve_profile_host call
+// (QuasiMcpHipSolver::solve_profile) with the regions in CSR form per reference of the file (n_refs + 1 offsets; the
+// caller has matched chroms to references and flattened overlaps) and max_coverage as the default cap, find_pairs,
+// write_paired_reads.  Refused, each with its own message (-4): no per_reference, targets, a depth report, a ladder,
+// stratify, dedup, amplicon files, a solver that grades by quality, offsets for another number of references.  Returns
+// the number of records written; -1 on an unknown solver, -3 out of memory.
+std::int64_t qmcp_host_downsample_bam_profile(const char* solver_name, const char* in_path, const char* out_path,
+                                              const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                              std::uint32_t min_mapq, int per_reference, const std::uint32_t* region_offsets,
+                                              const std::uint32_t* region_starts, const std::uint32_t* region_ends,
+                                              const std::uint32_t* region_caps, std::uint64_t n_refs, const char* targets,
+                                              const char* report, std::uint32_t n_ladder_levels, const char* stratify,
+                                              int dedup, const char* bed, const char* tsv, int amplicons_by_reference,
+                                              char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        if (!per_reference) throw std::invalid_argument("a coverage profile needs per_reference");
+        if (targets && targets[0]) throw std::invalid_argument("a coverage profile does not go together with targets");
+        if (report && report[0]) throw std::invalid_argument("a coverage profile does not go together with a depth report");
+        if (n_ladder_levels) throw std::invalid_argument("a coverage profile does not go together with a coverage ladder");
+        if (stratify && stratify[0]) throw std::invalid_argument("a coverage profile does not go together with stratify_by");
+        if (dedup) throw std::invalid_argument("a coverage profile does not go together with dedup");
+        if ((bed && bed[0]) || (tsv && tsv[0]) || amplicons_by_reference)
+            throw std::invalid_argument("a coverage profile does not take amplicon files");
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("a coverage profile does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no coverage profile");
+        if (region_offsets == nullptr) throw std::invalid_argument("a coverage profile needs its region offsets");
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = true;
+        bam_api::BamApi api(in_path, cfg);
+        const std::uint32_t n_reg = region_offsets[n_refs];
+        if (n_reg && (!region_starts || !region_ends || !region_caps))
+            throw std::invalid_argument("a coverage profile with regions needs their starts, ends and caps");
+        const std::vector<std::uint32_t> offs(region_offsets, region_offsets + n_refs + 1);
+        const std::vector<std::uint32_t> rs(region_starts, region_starts + n_reg), re(region_ends, region_ends + n_reg),
+            caps(region_caps, region_caps + n_reg);
+        std::unique_ptr<qmcp::Solution> solution = hip->solve_profile(max_coverage, api, offs, rs, re, caps);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

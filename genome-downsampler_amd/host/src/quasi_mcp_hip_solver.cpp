@@ -218,6 +218,45 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_dedup(std::uint32_t required_
     return kept;
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                                           const std::vector<std::uint32_t>& offsets,
+                                                           const std::vector<std::uint32_t>& region_starts,
+                                                           const std::vector<std::uint32_t>& region_ends,
+                                                           const std::vector<std::uint32_t>& caps) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("a coverage profile needs per_reference reads (one contig id per read)");
+    if (offsets.size() != reads.contig_lengths.size() + 1) throw std::invalid_argument("cap regions of other references");
+    if (region_starts.size() < offsets.back() || region_ends.size() < offsets.back() || caps.size() < offsets.back())
+        throw std::invalid_argument("cap region arrays are shorter than their offsets say");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    int rc = qmcp_hip_solve_profile_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                         reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                         offsets.data(), region_starts.data(), region_ends.data(), caps.data(),
+                                         required_cover, 0u, mask.data(), &stats_, &pstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_profile_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) {
+        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
+        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
+    }
+    return expand_kept(n, t0);
+}
+
 std::vector<std::unique_ptr<Solution>> QuasiMcpHipSolver::solve_ladder(std::uint32_t required_cover,
                                                                        bam_api::BamApi& bam_api,
                                                                        const std::vector<std::uint32_t>& levels) {

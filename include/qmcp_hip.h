@@ -509,6 +509,60 @@ int qmcp_hip_solve_targets_device(qmcp_hip_ctx* ctx,
                                   uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                   qmcp_hip_target_stats* tstats);
 
+/* Coverage profile: a cap that varies along the genome -- 1 000 x on a hotspot panel inside a 100 x exome, 0 on decoy
+ * stretches, another sample's own depth profile, "what forced reads leave uncovered".  Reads, contig ids (QMCP_NO_CONTIG
+ * is never kept), contig_lengths / n_contigs, limits, read validation and "the mask is cleared before the reads are
+ * validated" as in qmcp_hip_solve_by_contig_host.
+ * Regions: region_offsets (n_contigs + 1 entries, starting at 0, never decreasing; NULL = no region at all) gives contig
+ * c the regions [region_offsets[c], region_offsets[c + 1]) of region_starts / region_ends / region_caps, inclusive bounds,
+ * in any order.  A region is clipped to its contig; one that begins at or beyond the contig's length is dropped.  After
+ * clipping the regions of one contig must be disjoint (adjacent is fine).
+ * Cap: cap_c(p) is the cap of the region of contig c that holds p, default_cap elsewhere.  A cap of 0 is legal: nothing is
+ * required there, and a read that lies wholly in such positions is never kept.
+ * Answer: the kept set F satisfies cov_F(p) >= min(cov(p), cap_c(p)) at every position with the fewest reads possible,
+ * and is defined exactly: per contig, on its reads in input order, the canonical selection rule (DESIGN.md sections 2
+ * and 4.2: at the leftmost position with a deficit take the unselected covering reads with the furthest end, then the
+ * furthest start, then the lowest index) with need(p) = min(cov(p), cap_c(p)).  With every cap equal to M the mask is
+ * bit-identical to qmcp_hip_solve_by_contig_host at M.  A call without regions -- and every batch of contigs (the
+ * by-contig solve's batches) that holds no region -- IS that call at default_cap, through the unchanged solve; batches
+ * with regions take the sort-based mixed-span route whatever their spans, with need built on the device
+ * (k_profile_need), exact cut points only (options.cut_points is honoured, nothing is speculated) and the capped forms
+ * of the register-resident walk (spans up to 448; options.mixed_sweep_in_lds = 1 and longer spans: the plain walk).
+ * flags: none defined, must be 0.
+ * Errors: overlapping regions (after clipping), a region with start > end, offsets that do not start at 0 or that
+ * decrease, null region arrays with a non-zero count and unknown flag bits fail with QMCP_EINVAL; a cap or default_cap of
+ * 2^31 or more with QMCP_ERANGE -- all on the host, before anything is copied or launched: the output mask is not
+ * written.  A bad contig id (QMCP_EINVAL) or a bad read (QMCP_EREAD) is found on the device; by then the device mask has
+ * been cleared (the host entry's keep_mask_out is not written).
+ * stats (may be NULL): the batch-summed qmcp_hip_stats as in the by-contig solve; path == QMCP_PATH_GENERAL for batches
+ * on the capped route.  pstats (may be NULL): regions_in as given, regions_used after dropping, positions_in_regions
+ * after clipping; capped_positions (cov > cap) and demand (the sum of need) are reduced on the device by the kernel that
+ * builds need, so they count the positions of the batches that hold a region (0 for a call without regions);
+ * ms_profile is the device time of that kernel and the cut-point scan.
+ * The device entry takes the columns and the mask in device memory (the contig and region tables stay on the host) and is
+ * ordered after hip_stream; both entries block until the mask is complete (no _begin / _end form). */
+typedef struct qmcp_hip_profile_stats {
+    uint64_t positions_in_regions;
+    uint64_t capped_positions;
+    uint64_t demand;
+    uint32_t regions_in, regions_used;
+    float ms_profile;
+} qmcp_hip_profile_stats;
+int qmcp_hip_solve_profile_host(qmcp_hip_ctx* ctx,
+                                const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids, uint64_t n_reads,
+                                const uint32_t* contig_lengths, uint32_t n_contigs,
+                                const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                uint32_t flags, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                                qmcp_hip_profile_stats* pstats);
+int qmcp_hip_solve_profile_device(qmcp_hip_ctx* ctx,
+                                  const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                  uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                  const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                  const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                  uint32_t flags, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                  qmcp_hip_profile_stats* pstats);
+
 /* Depth report: what `samtools depth` / mosdepth on the input and on the output would tell, computed on the device from
  * the read columns and a keep mask and summarised per contig and per region -- nothing of the size of the genome crosses
  * the link.  Reads, contig_ids (QMCP_NO_CONTIG = unplaced), contig_lengths / n_contigs as in qmcp_hip_solve_by_contig_host,
