@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_quality_host", "qmcp_hip_solve_quality_device", "qmcp_hip_solve_quality_by_contig_host",
     "qmcp_hip_solve_targets_host", "qmcp_hip_solve_targets_device",
     "qmcp_hip_depth_report_host", "qmcp_hip_depth_report_device",
+    "qmcp_hip_depth_track_host", "qmcp_hip_depth_track_device",
     "qmcp_hip_solve_ladder_host", "qmcp_hip_solve_ladder_device",
     "qmcp_hip_solve_stratified_host", "qmcp_hip_solve_stratified_device",
     "qmcp_hip_solve_dedup_host", "qmcp_hip_solve_dedup_device",
@@ -50,6 +51,8 @@ LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
 DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
+TRACK_IN, TRACK_KEPT, TRACK_SHORT_ONLY, TRACK_SKIP_ZERO = 1, 2, 4, 8  # QMCP_TRACK_*
+TRACK_FIRST_CAPACITY = 1 << 22  # records Solver.depth_track offers first (96 MiB); beyond it, one more call at the exact count
 STRATUM_TALLY_TILE = 1024  # qmcp::kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces
 
 
@@ -137,6 +140,30 @@ class DepthStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TrackRun(C.Structure):
+    """qmcp_hip_track_run: a maximal run [start, end] (inclusive) of one contig with one (depth_in, depth_kept, short)"""
+    _fields_ = [("contig", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("depth_in", C.c_uint32),
+                ("depth_kept", C.c_uint32), ("flags", C.c_uint32)]
+
+
+TRACK_RUN_DTYPE = np.dtype([(name, np.uint32) for name, _ in TrackRun._fields_])
+assert TRACK_RUN_DTYPE.itemsize == C.sizeof(TrackRun) == 24
+
+
+class TrackStats(C.Structure):
+    """qmcp_hip_track_stats"""
+    _fields_ = [("n_runs", C.c_uint64), ("positions_in_runs", C.c_uint64), ("scope_positions", C.c_uint64),
+                ("short_positions", C.c_uint64), ("reads_placed", C.c_uint64), ("reads_kept", C.c_uint64),
+                ("regions_in", C.c_uint32), ("regions_merged", C.c_uint32), ("position_batches", C.c_uint32),
+                ("ms_track", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+assert C.sizeof(TrackStats) == 64
 
 
 class LadderStats(C.Structure):
@@ -275,6 +302,13 @@ _hip.qmcp_hip_depth_report_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c
 _hip.qmcp_hip_depth_report_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32] + \
                                              _depth_out + [C.c_void_p, C.POINTER(DepthStats)]
+_track_out = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]
+_hip.qmcp_hip_depth_track_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u64p,
+                                           C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32] + _track_out + \
+                                          [C.POINTER(TrackStats)]
+_hip.qmcp_hip_depth_track_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                             C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32] + \
+                                            _track_out + [C.c_void_p, C.POINTER(TrackStats)]
 _hip.qmcp_hip_solve_ladder_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p,
                                             C.c_uint32, C.c_void_p, C.POINTER(Stats), C.POINTER(LadderStats)]
 _hip.qmcp_hip_solve_ladder_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
@@ -350,6 +384,9 @@ if _host is not None:
     _host.qmcp_host_downsample_bam_report.argtypes = _host.qmcp_host_downsample_bam_targets.argtypes[:-2] + \
         [C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_report.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_track.argtypes = _host.qmcp_host_downsample_bam_report.argtypes[:-2] + \
+        [C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_track.restype = C.c_int64
     _host.qmcp_host_downsample_bam_ladder.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
                                                       C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                                       C.c_int, _u32p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int64),
@@ -842,6 +879,61 @@ class Solver:
                                 C.c_void_p(d_keep_mask or None), max_coverage, target_offsets, target_starts, target_ends,
                                 padding, n_bins, (C.c_void_p(stream),))
 
+    def _track_call(self, entry, head, n, lengths, mask_arg, max_coverage, target_offsets, target_starts, target_ends,
+                    padding, channels, short_only, skip_zero, depth_cap, tail):
+        offs, t0, t1 = self._target_tables(lengths.size, target_offsets, target_starts, target_ends)
+        flags = track_flags(channels, short_only, skip_zero)
+        # the header's bound on the runs: 2 x reads + contigs + regions (the merged regions are no more than those given)
+        bound = 2 * int(n) + int(lengths.size) + (0 if offs is None else int(offs[-1]))
+        capacity = min(bound, TRACK_FIRST_CAPACITY)
+        for attempt in range(2):
+            runs = np.zeros(capacity, TRACK_RUN_DTYPE)
+            n_runs, st = C.c_uint64(0), TrackStats()
+            rc = entry(self._ctx, *head, n, _p32(lengths), lengths.size, mask_arg, int(max_coverage), _p32(offs), _p32(t0),
+                       _p32(t1), int(padding), flags, int(depth_cap), runs.ctypes.data, capacity, C.byref(n_runs), *tail,
+                       C.byref(st))
+            if rc == QMCP_ERANGE and attempt == 0 and n_runs.value > capacity:
+                capacity = int(n_runs.value)          # the exact count, once
+                continue
+            _check(rc)
+            break
+        self.last_track_stats = st
+        return runs[:n_runs.value].copy(), st
+
+    def depth_track(self, starts, ends, contig_ids, contig_lengths, max_coverage, keep_mask=None, target_offsets=None,
+                    target_starts=None, target_ends=None, padding=0, channels=("in", "kept"), short_only=False,
+                    skip_zero=False, depth_cap=0):
+        """per-base depth before and after as runs (qmcp_hip_depth_track_host): depth_report's inputs -> (runs, stats),
+        runs a numpy structured array of TRACK_RUN_DTYPE in ascending (contig, start) order -- one record per maximal
+        interval [start, end] of one contig (and one merged region, when regions are given) on which depth_in =
+        min(cov, depth_cap), depth_kept = min(kept, depth_cap) and short = [kept < min(cov, max_coverage)] are constant.
+        channels: which of "in" and "kept" are compared and reported (the other is 0); short_only: only short positions;
+        skip_zero: no positions whose selected channels are all 0 (genomecov -bg); depth_cap 0: no clamp.
+        stats (TrackStats, also last_track_stats): short_positions counts every short position in scope whatever the
+        flags.  write_bedgraph turns the runs into a file"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = None
+        if keep_mask is not None:
+            mask = np.ascontiguousarray(keep_mask, dtype=np.uint64)
+            assert mask.size >= mask_words(n), "keep_mask needs ceil(n_reads / 64) words"
+        return self._track_call(_hip.qmcp_hip_depth_track_host, (_p32(starts), _p32(ends), _p32(ids)), n, lengths,
+                                _p64(mask), max_coverage, target_offsets, target_starts, target_ends, padding, channels,
+                                short_only, skip_zero, depth_cap, ())
+
+    def depth_track_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_keep_mask=0,
+                           target_offsets=None, target_starts=None, target_ends=None, padding=0, channels=("in", "kept"),
+                           short_only=False, skip_zero=False, depth_cap=0, stream=0):
+        """depth_track on device pointers (ints; d_keep_mask 0: every placed read is kept); the tables, the runs and
+        the stats are host memory"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        head = (C.c_void_p(d_starts), C.c_void_p(d_ends), C.c_void_p(d_contig_ids))
+        return self._track_call(_hip.qmcp_hip_depth_track_device, head, int(n_reads), lengths,
+                                C.c_void_p(d_keep_mask or None), max_coverage, target_offsets, target_starts, target_ends,
+                                padding, channels, short_only, skip_zero, depth_cap, (C.c_void_p(stream),))
+
     def solve64(self, start_inds, end_inds, contig_lengths, max_coverage, contig_read_offsets=None):
         """the reference's own size_t columns in (qmcp_hip_solve_host64: narrowed inside the library),
         host keep bitmask out; self.last_breakdown tells how (threads, chunks, columns sent)"""
@@ -1255,6 +1347,49 @@ def write_depth_report(path, report, reference_names):
             f.write(f"#hist\t{b}\t{int(report.hist_in[b])}\t{int(report.hist_kept[b])}\n")
 
 
+def track_flags(channels=("in", "kept"), short_only=False, skip_zero=False):
+    """the QMCP_TRACK_* word of Solver.depth_track's keywords; channels: "in", "kept", "both" or a collection of the
+    first two"""
+    if isinstance(channels, str):
+        channels = ("in", "kept") if channels == "both" else (channels,)
+    channels = tuple(channels)
+    if not channels or any(ch not in ("in", "kept") for ch in channels):
+        raise ValueError(f'channels must name "in", "kept" or both, not {channels!r}')
+    return (TRACK_IN if "in" in channels else 0) | (TRACK_KEPT if "kept" in channels else 0) | \
+        (TRACK_SHORT_ONLY if short_only else 0) | (TRACK_SKIP_ZERO if skip_zero else 0)
+
+
+def write_bedgraph(path, runs, reference_names, channel="kept"):
+    """the runs of Solver.depth_track as bedGraph: chrom<TAB>start<TAB>end + 1<TAB>value, 0-based half-open, in the runs'
+    order; channel "kept" or "in" writes that depth, "both" writes depth_in and depth_kept as two value columns under a
+    '#chrom start end depth_in depth_kept' header line.  Neighbouring runs of one contig that touch and have the same
+    written value(s) are joined, so the file does not depend on the channels the call compared.  profile_from_bedgraph
+    reads a one-channel file back.  Returns the number of lines written (without the header)"""
+    if channel not in ("kept", "in", "both"):
+        raise ValueError(f'channel must be "kept", "in" or "both", not {channel!r}')
+    names = [str(x) for x in reference_names]
+    runs = np.asarray(runs)
+    contig = runs["contig"].astype(np.int64)
+    start, end = runs["start"].astype(np.int64), runs["end"].astype(np.int64)
+    values = [runs["depth_in"]] if channel == "in" else [runs["depth_kept"]] if channel == "kept" else \
+        [runs["depth_in"], runs["depth_kept"]]
+    if runs.size:
+        joined = (contig[1:] == contig[:-1]) & (start[1:] == end[:-1] + 1)
+        for v in values:
+            joined &= v[1:] == v[:-1]
+        first = np.flatnonzero(np.concatenate([[True], ~joined]))
+        last = np.concatenate([first[1:] - 1, [runs.size - 1]])
+    else:
+        first = last = np.zeros(0, np.int64)
+    with open(path, "w") as f:
+        if channel == "both":
+            f.write("#chrom\tstart\tend\tdepth_in\tdepth_kept\n")
+        cols = [[names[c] for c in contig[first].tolist()], start[first].tolist(), (end[last] + 1).tolist()] + \
+            [v[first].tolist() for v in values]
+        f.writelines("\t".join(map(str, line)) + "\n" for line in zip(*cols))
+    return int(first.size)
+
+
 def reference_names(path):
     """the BAM header's reference names, in header order"""
     _need_host()
@@ -1524,7 +1659,8 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
                    targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
-                   ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None):
+                   ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None,
+                   track=None, track_channel="kept", track_cap=0):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1565,8 +1701,40 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     max_coverage as the cap outside the file's regions -- one qmcp_hip_solve_profile_host call.  Chroms are matched to
     the file's references by name, overlapping lines are flattened with the later line winning.  Needs
     per_reference=True; not together with targets, report, ladder, stratify, dedup, amplicon files or
-    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes.
+    track (a path; BamApiConfig::depth_track_filepath, with track_channel "kept" | "in" | "both" and track_cap, a clamp
+    on the written depths, 0: none): after the output has been written, the per-base depth (write_bedgraph's bedGraph;
+    Solver.depth_track with both channels) of the reads the solve saw against the FINAL kept set (after mate
+    completion), inside the targets with their padding when given.  Needs per_reference=True; goes together with
+    targets, report and amplicon files as report does; not together with ladder, stratify, dedup or profile
+    (ValueError).  None: nothing changes"""
     _need_host()
+    if track is not None:
+        if not per_reference:
+            raise ValueError("a depth track needs per_reference=True")
+        if track_channel not in ("kept", "in", "both"):
+            raise ValueError(f'track_channel must be "kept", "in" or "both", not {track_channel!r}')
+        if ladder is not None or stratify is not None or dedup or profile is not None:
+            raise ValueError("a depth track does not go together with a coverage ladder, stratify, dedup or a coverage "
+                             "profile")
+        if (bed or tsv) and not amplicons_by_reference:
+            raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_track(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
+            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)),
+            str(targets).encode() if targets else None, int(target_padding), int(bool(keep_off_target)),
+            str(report).encode() if report else None, int(report_bins), str(track).encode(), track_channel.encode(),
+            int(track_cap), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n}): {err.value.decode()}")
+        return int(n)
     if profile is not None:
         if not per_reference:
             raise ValueError("a coverage profile needs per_reference=True")

@@ -133,6 +133,9 @@ struct qmcp_hip_ctx {
     // depth report (api/depth_report.inc.hip): a batch's event words, its tables (lengths, offsets, the two interval
     // tables), the rows' accumulators, the histograms, the chunk sums, and the read counts + validation word
     DevBuf dr_ev, dr_tab, dr_acc, dr_hist, dr_sums, dr_cnt;
+    // depth track (api/depth_track.inc.hip; the events, tables, chunk sums and counters are the report's): the chunks'
+    // counts with the batch's three totals behind them, and a batch's records
+    DevBuf dt_cnt, dt_runs;
     // coverage ladder (api/ladder.inc.hip): the two sets of compacted columns (starts, ends, input indices) that
     // ping-pong between levels, the scanned word popcounts of a level's mask and their spine, the two offset tables, the
     // host entry's level bytes and the device entry's first-level mask

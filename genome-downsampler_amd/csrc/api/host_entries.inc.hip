@@ -164,7 +164,7 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->af_err, &c->qc_words, &c->qc_tab, &c->qc_bare, &c->qc_keys[0], &c->qc_keys[1],
                       &c->qc_vals[0], &c->qc_vals[1], &c->qc_hist, &c->qc_spine, &c->qc_kb, &c->qc_end, &c->qc_head,
                       &c->tg_ps, &c->tg_pe, &c->tg_off, &c->tg_offw, &c->tg_q, &c->tg_tab,
-                      &c->dr_ev, &c->dr_tab, &c->dr_acc, &c->dr_hist, &c->dr_sums, &c->dr_cnt,
+                      &c->dr_ev, &c->dr_tab, &c->dr_acc, &c->dr_hist, &c->dr_sums, &c->dr_cnt, &c->dt_cnt, &c->dt_runs,
                       &c->ld_starts[0], &c->ld_starts[1], &c->ld_ends[0], &c->ld_ends[1], &c->ld_orig[0], &c->ld_orig[1],
                       &c->ld_words, &c->ld_spine, &c->ld_offs[0], &c->ld_offs[1], &c->ld_levels, &c->ld_mask0,
                       &c->st_strata, &c->st_rows,

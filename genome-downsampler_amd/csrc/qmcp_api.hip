@@ -51,6 +51,8 @@
 //                       the by-contig solve (and quality pass) of the projected on-target reads, the mask expanded back
 //   depth_report        depth before and after a keep mask, per contig and per region, with histograms: position batches,
 //                       the reads' events, the positions pass, rows and statistics assembled on the host
+//   depth_track         the same pipeline ending in a run-length compaction: per-base depth before and after as records
+//                       (contig, start, end, depth_in, depth_kept, short), counted first, then written and copied out
 //   ladder              several falling coverages in one by-contig call: every further level solved on the reads the level
 //                       above kept, inside each batch; one byte per read counts the levels that keep it
 //   stratified          one coverage cap per stratum (strand, read group, sample): reads grouped once by (stratum, contig),
@@ -72,6 +74,7 @@
 #include "api/quality.inc.hip"
 #include "api/targets.inc.hip"
 #include "api/depth_report.inc.hip"
+#include "api/depth_track.inc.hip"
 #include "api/ladder.inc.hip"
 #include "api/stratified.inc.hip"
 #include "api/dedup.inc.hip"

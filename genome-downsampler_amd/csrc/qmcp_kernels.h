@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qmcp_hip.h"    // qmcp_hip_track_run
 #include "sweep_plan.h"  // the shape predicates and window counts the host decides with
 #include "dedup_plan.h"  // DedupPack, DedupSortForm: how a round's key is packed, which form the sort takes
 
@@ -364,6 +365,19 @@ void launch_depth_consume(hipStream_t st, const uint64_t* ev, uint32_t positions
                           const uint32_t* r_lo, const uint32_t* r_hi, const uint32_t* r_row, uint32_t n_r,
                           bool scope_regions, uint32_t n_rows, uint64_t* acc64, uint32_t* acc32, uint32_t n_bins,
                           uint64_t* hist);
+
+// the depth track of qmcp_hip_depth_track_* (kernels/depth_track.inc.hip; api/depth_track.inc.hip drives it) over the event
+// words, chunk sums and chunks of the depth report: a batch's runs of equal (depth_in, depth_kept, short) inside the scope
+// intervals s_lo / s_hi (sorted, disjoint: the merged regions, or the contigs), counted and then written.  cnt: 3 x
+// depth_chunks(positions) words, totals: 3 words (runs, emitted positions, short positions in scope); launch_track_emit
+// takes cnt as launch_track_count left it, with the same M, flags and depth_cap, and writes totals[0] records
+void launch_track_count(hipStream_t st, const uint64_t* ev, uint32_t positions, const uint64_t* sums, uint32_t M,
+                        uint32_t flags, uint32_t depth_cap, const uint32_t* s_lo, const uint32_t* s_hi, uint32_t n_s,
+                        uint32_t* cnt, uint64_t* totals);
+void launch_track_emit(hipStream_t st, const uint64_t* ev, uint32_t positions, const uint64_t* sums, uint32_t M,
+                       uint32_t flags, uint32_t depth_cap, const uint32_t* s_lo, const uint32_t* s_hi, uint32_t n_s,
+                       const uint32_t* c_lo, const uint32_t* c_hi, const uint32_t* c_row, uint32_t n_c,
+                       const uint32_t* cnt, qmcp_hip_track_run* runs);
 
 // duplicate-aware downsampling (kernels/dedup.inc.hip; api/dedup.inc.hip drives them; keys and forms: dedup_plan.h): the
 // ranges and validation of a call (out: 9 words preset to {~0u, 0, ~0u, 0, ~0u, 0, 0, 0, 0} -- tag, quality and span min /

@@ -40,6 +40,8 @@
 //                            of the on-target reads, the compact mask expanded back to input order
 //   depth_report             depth before and after a keep mask per contig and region: the reads' events (two 64-bit
 //                            atomics per read), chunk sums, spine, and the pass that turns them into rows and histograms
+//   depth_track              the report's events and spine again, run-length compacted: runs of equal depth counted per
+//                            chunk, the counts scanned, and the records written at their ranks (no atomics)
 //   stratified               one coverage cap per stratum (strand, read group, sample): validation and stratum-major sort
 //                            keys, and the per-stratum rows as a segmented reduction over the grouped records
 //   dedup                    duplicate families collapsed before the solve: ranges and validation, composite keys, head
@@ -82,6 +84,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/quality_cells.inc.hip"
 #include "kernels/targets.inc.hip"
 #include "kernels/depth_report.inc.hip"
+#include "kernels/depth_track.inc.hip"
 #include "kernels/stratified.inc.hip"
 #include "kernels/dedup.inc.hip"
 #include "kernels/profile.inc.hip"

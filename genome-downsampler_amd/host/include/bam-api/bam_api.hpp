@@ -52,6 +52,14 @@ struct BamApiConfig {
     // Needs per_reference (std::invalid_argument otherwise).  Empty: no report, nothing changes.
     std::filesystem::path depth_report_filepath;
     std::uint32_t depth_report_bins = 0;
+    // Depth track: after the output has been written, the per-base depth of the reads the solve saw against the final
+    // kept set goes here as bedGraph (QuasiMcpHipSolver::depth_track / write_depth_track_bedgraph): the channel "kept",
+    // "in" or "both", depths clamped to depth_track_cap (0: no clamp), inside the targets with their padding when the
+    // BamApi holds any.  Needs per_reference; not together with a coverage ladder, stratify_by or dedup
+    // (std::invalid_argument otherwise, also for another channel).  Empty: no track, nothing changes.
+    std::filesystem::path depth_track_filepath;
+    std::string depth_track_channel = "kept";
+    std::uint32_t depth_track_cap = 0;
     // Coverage ladder: further coverages below the solve's max_coverage, strictly decreasing, each solved on the reads
     // the level above kept (QuasiMcpHipSolver::solve_ladder / qmcp_hip_solve_ladder_host), so the outputs are nested.
     // Needs per_reference; not together with targets or a depth report (std::invalid_argument otherwise).  Empty: no
@@ -101,6 +109,10 @@ class BamApi {
     // BamApiConfig::depth_report_filepath (empty: none) and depth_report_bins
     const std::filesystem::path& depth_report_filepath() const { return depth_report_filepath_; }
     std::uint32_t depth_report_bins() const { return depth_report_bins_; }
+    // BamApiConfig::depth_track_filepath (empty: none), depth_track_channel and depth_track_cap
+    const std::filesystem::path& depth_track_filepath() const { return depth_track_filepath_; }
+    const std::string& depth_track_channel() const { return depth_track_channel_; }
+    std::uint32_t depth_track_cap() const { return depth_track_cap_; }
     // BamApiConfig::coverage_ladder (empty: none)
     const std::vector<std::uint32_t>& coverage_ladder() const { return coverage_ladder_; }
     // BamApiConfig::stratify_by (NONE: the reads carry no strata)
@@ -134,6 +146,9 @@ class BamApi {
     bool has_targets_ = false;
     std::filesystem::path depth_report_filepath_;
     std::uint32_t depth_report_bins_ = 0;
+    std::filesystem::path depth_track_filepath_;
+    std::string depth_track_channel_ = "kept";
+    std::uint32_t depth_track_cap_ = 0;
     std::vector<std::uint32_t> coverage_ladder_;
     Stratify stratify_by_ = Stratify::NONE;
     bool dedup_ = false;

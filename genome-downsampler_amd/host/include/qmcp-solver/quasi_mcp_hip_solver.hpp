@@ -31,6 +31,18 @@ struct DepthReport {
 bool write_depth_report_tsv(const std::filesystem::path& path, const DepthReport& report,
                             const std::vector<std::string>& reference_names);
 
+// qmcp_hip_depth_track_host's outputs
+struct DepthTrack {
+    std::vector<qmcp_hip_track_run> runs;
+    qmcp_hip_track_stats stats{};
+};
+
+// the runs as bedGraph (chrom, start, end + 1, value; 0-based half-open): channel "kept" or "in" writes that depth, "both"
+// writes depth_in and depth_kept under a '#' header line.  Neighbouring runs of one contig that touch and have the same
+// written value(s) are joined.  false: another channel, or the file cannot be written
+bool write_depth_track_bedgraph(const std::filesystem::path& path, const DepthTrack& track,
+                                const std::vector<std::string>& reference_names, const std::string& channel);
+
 class QuasiMcpHipSolver : public Solver {
    public:
     QuasiMcpHipSolver() = default;  // trivial: solvers are built eagerly (src/app.hpp:35)
@@ -57,6 +69,11 @@ class QuasiMcpHipSolver : public Solver {
     // std::terminate on a device failure, like solve()
     void depth_report(std::uint32_t required_cover, bam_api::BamApi& bam_api, const std::vector<bam_api::ReadIndex>& kept,
                       std::uint32_t n_bins, DepthReport& out);
+    // The per-base form of depth_report, for the same reads and kept set: qmcp_hip_depth_track_host with
+    // M = required_cover, the BamApi's target regions and padding when it holds any, `flags` (QMCP_TRACK_*) and
+    // depth_cap; counted first, then fetched at the exact size.  std::terminate on a device failure, like solve()
+    void depth_track(std::uint32_t required_cover, bam_api::BamApi& bam_api, const std::vector<bam_api::ReadIndex>& kept,
+                     std::uint32_t flags, std::uint32_t depth_cap, DepthTrack& out);
     // Coverage ladder for the reads of a per-reference BamApi: the solve at required_cover, then at each of `levels`
     // (strictly below required_cover, strictly decreasing, >= 1; std::invalid_argument otherwise) on the reads the
     // level above kept, in one qmcp_hip_solve_ladder_host call.  One ascending Solution per level, required_cover's

@@ -117,6 +117,21 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
         depth_report_filepath_ = config.depth_report_filepath;
         depth_report_bins_ = config.depth_report_bins;
     }
+    if (!config.depth_track_filepath.empty()) {
+        if (!per_reference_)
+            throw std::invalid_argument("a depth track needs per_reference: its runs lie on the references a "
+                                        "per-reference ingest keeps");
+        if (!config.coverage_ladder.empty()) throw std::invalid_argument("a coverage ladder does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("stratified downsampling does not take a depth track");
+        if (config.dedup) throw std::invalid_argument("duplicate-aware downsampling does not take a depth track");
+        if (config.depth_track_channel != "kept" && config.depth_track_channel != "in" &&
+            config.depth_track_channel != "both")
+            throw std::invalid_argument("the channel of a depth track is \"kept\", \"in\" or \"both\"");
+        depth_track_filepath_ = config.depth_track_filepath;
+        depth_track_channel_ = config.depth_track_channel;
+        depth_track_cap_ = config.depth_track_cap;
+    }
     if (!config.targets_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("targets need per_reference: target regions are matched to the references a "

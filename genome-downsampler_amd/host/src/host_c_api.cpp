@@ -647,6 +647,82 @@ std::int64_t qmcp_host_downsample_bam_report(const char* solver_name, const char
     }
 }
 
+// qmcp_host_downsample_bam_report with a depth track: BamApiConfig {depth_track_filepath, depth_track_channel,
+// depth_track_cap} on top (report_path may be NULL: no report).  After the output -- and the report -- has been written,
+// the hip solver's depth track of the reads the solve saw against the final kept set (after find_pairs), inside the
+// call's targets and padding when given, goes to track_path as bedGraph: channel "kept", "in" or "both", both depths
+// compared, zero positions kept.  Returns as qmcp_host_downsample_bam_report; -4 also for a track without per_reference,
+// another channel, or a solver that has none, -5 when the track cannot be written.
+std::int64_t qmcp_host_downsample_bam_track(const char* solver_name, const char* in_path, const char* out_path,
+                                            const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                            std::uint32_t min_mapq, const char* bed, const char* tsv, int amplicon_mode,
+                                            int per_reference, int amplicons_by_reference, const char* targets,
+                                            std::uint32_t target_padding, int keep_off_target, const char* report_path,
+                                            std::uint32_t report_bins, const char* track_path, const char* track_channel,
+                                            std::uint32_t track_cap, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    bam_api::BamApiConfig cfg;
+    if (bed && bed[0]) cfg.bed_filepath = bed;
+    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
+    cfg.per_reference = per_reference != 0;
+    cfg.amplicons_by_reference = amplicons_by_reference != 0;
+    if (targets && targets[0]) cfg.targets_filepath = targets;
+    cfg.target_padding = target_padding;
+    cfg.keep_off_target = keep_off_target != 0;
+    if (report_path && report_path[0]) cfg.depth_report_filepath = report_path;
+    cfg.depth_report_bins = report_bins;
+    if (track_path && track_path[0]) cfg.depth_track_filepath = track_path;
+    if (track_channel && track_channel[0]) cfg.depth_track_channel = track_channel;
+    cfg.depth_track_cap = track_cap;
+    try {
+        bam_api::BamApi api(in_path, cfg);
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr && !api.depth_report_filepath().empty())
+            throw std::invalid_argument("this solver has no depth report");
+        if (hip == nullptr && !api.depth_track_filepath().empty())
+            throw std::invalid_argument("this solver has no depth track");
+        auto solution = found->solve(max_coverage, api);
+        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
+        const std::uint32_t written = api.write_paired_reads(out_path, paired);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        if (!api.depth_report_filepath().empty() || !api.depth_track_filepath().empty()) {
+            std::vector<std::string> names;
+            std::vector<std::uint32_t> lengths;
+            std::string msg;
+            if (!bam_api::read_bam_references(in_path, names, lengths, &msg)) {
+                copy_err(msg, err, err_cap);
+                return -5;
+            }
+            if (!api.depth_report_filepath().empty()) {
+                qmcp::DepthReport report;
+                hip->depth_report(max_coverage, api, paired, api.depth_report_bins(), report);
+                if (!qmcp::write_depth_report_tsv(api.depth_report_filepath(), report, names)) {
+                    copy_err("could not write " + api.depth_report_filepath().string(), err, err_cap);
+                    return -5;
+                }
+            }
+            if (!api.depth_track_filepath().empty()) {
+                qmcp::DepthTrack track;
+                hip->depth_track(max_coverage, api, paired, QMCP_TRACK_IN | QMCP_TRACK_KEPT, api.depth_track_cap(), track);
+                if (!qmcp::write_depth_track_bedgraph(api.depth_track_filepath(), track, names, api.depth_track_channel())) {
+                    copy_err("could not write " + api.depth_track_filepath().string(), err, err_cap);
+                    return -5;
+                }
+            }
+        }
+        return written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // qmcp_host_downsample_bam_by_reference with a coverage ladder: BamApiConfig {coverage_ladder} on top of the amplicon
 // fields (bed / tsv may be NULL; FILTER acts at ingest as before).  One ingest and one qmcp_hip_solve_ladder_host call;
 // the level at max_coverage goes to out_path, level `levels[j]` through find_pairs to out_template with its "{M}"

@@ -341,6 +341,67 @@ void QuasiMcpHipSolver::depth_report(std::uint32_t required_cover, bam_api::BamA
     out.region_rows.resize(n_rows);
 }
 
+void QuasiMcpHipSolver::depth_track(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                    const std::vector<bam_api::ReadIndex>& kept, std::uint32_t flags,
+                                    std::uint32_t depth_cap, DepthTrack& out) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const std::size_t n = reads.start_inds.size();
+    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("a depth track without one contig id per read", QMCP_EINVAL);
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    for (const bam_api::ReadIndex i : kept)
+        if (i < n) mask[i >> 6] |= 1ull << (i & 63);
+    const std::uint32_t n_contigs = (std::uint32_t)reads.contig_lengths.size();
+    const bool regions = bam_api.has_targets();
+    const bam_api::TargetRegions& t = bam_api.get_targets();
+    out = DepthTrack();
+    std::uint64_t n_runs = 0;
+    for (int pass = 0; pass < 2; ++pass) {  // the count, then the records at that size
+        const int rc = qmcp_hip_depth_track_host(
+            ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(), n_contigs,
+            mask.data(), required_cover, regions ? t.offsets.data() : nullptr, regions ? t.starts.data() : nullptr,
+            regions ? t.ends.data() : nullptr, regions ? t.padding : 0u, flags, depth_cap,
+            pass ? out.runs.data() : nullptr, out.runs.size(), &n_runs, &out.stats);
+        if (rc != QMCP_OK) die("qmcp_hip_depth_track_host", rc);
+        if (pass == 0) {
+            if (n_runs == 0) break;
+            out.runs.resize(n_runs);
+        }
+    }
+}
+
+bool write_depth_track_bedgraph(const std::filesystem::path& path, const DepthTrack& track,
+                                const std::vector<std::string>& reference_names, const std::string& channel) {
+    const bool both = channel == "both", in = channel == "in";
+    if (!both && !in && channel != "kept") return false;
+    std::FILE* f = std::fopen(path.c_str(), "w");
+    if (f == nullptr) return false;
+    if (both) std::fputs("#chrom\tstart\tend\tdepth_in\tdepth_kept\n", f);
+    const std::vector<qmcp_hip_track_run>& v = track.runs;
+    for (std::size_t i = 0; i < v.size();) {
+        std::size_t k = i + 1;  // the runs joined to run i
+        while (k < v.size() && v[k].contig == v[i].contig && v[k].start == v[k - 1].end + 1 &&
+               (in || v[k].depth_kept == v[i].depth_kept) && (!in && !both ? true : v[k].depth_in == v[i].depth_in))
+            ++k;
+        const char* name = v[i].contig < reference_names.size() ? reference_names[v[i].contig].c_str() : "*";
+        const unsigned long long end = (unsigned long long)v[k - 1].end + 1;
+        if (both) std::fprintf(f, "%s\t%u\t%llu\t%u\t%u\n", name, v[i].start, end, v[i].depth_in, v[i].depth_kept);
+        else std::fprintf(f, "%s\t%u\t%llu\t%u\n", name, v[i].start, end, in ? v[i].depth_in : v[i].depth_kept);
+        i = k;
+    }
+    return std::fclose(f) == 0;
+}
+
 bool write_depth_report_tsv(const std::filesystem::path& path, const DepthReport& report,
                             const std::vector<std::string>& reference_names) {
     std::FILE* f = std::fopen(path.c_str(), "w");

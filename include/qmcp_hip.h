@@ -629,6 +629,65 @@ int qmcp_hip_depth_report_device(qmcp_hip_ctx* ctx,
                                  uint64_t region_capacity, uint64_t* n_region_rows_out, uint64_t* hist_in,
                                  uint64_t* hist_kept, void* hip_stream, qmcp_hip_depth_stats* stats);
 
+/* Depth track: the per-base form of the depth report -- what `bedtools genomecov -bg` / mosdepth's per-base file on the
+ * input and on the output would hold, as runs of equal depth.  Reads, contig_ids, contig_lengths / n_contigs, keep_mask,
+ * max_coverage, the optional regions with `padding`, the limits and the position batches are those of
+ * qmcp_hip_depth_report_host, and cov(p) / kept(p) are defined there.  The SCOPE is every position of every contig or,
+ * when regions are given, every position inside a merged region.  `flags` chooses what a run is:
+ *   QMCP_TRACK_IN          depth_in = min(cov, depth_cap) takes part in the run tuple (depth_cap == 0: no clamp)
+ *   QMCP_TRACK_KEPT        depth_kept = min(kept, depth_cap) takes part
+ *   QMCP_TRACK_SHORT_ONLY  only positions with kept < min(cov, max_coverage) are emitted (on the unclamped values)
+ *   QMCP_TRACK_SKIP_ZERO   positions whose selected channels are all 0 are not emitted (genomecov -bg's behaviour)
+ * At least one of IN and KEPT must be set; anything else, or an unknown bit, is QMCP_EINVAL before the context is looked
+ * at.  A channel that is not selected is reported as 0 and is not compared.  The tuple of a position is (depth_in,
+ * depth_kept, short) with short = [kept < min(cov, max_coverage)].  A RUN is a maximal interval [start, end] of
+ * consecutive emitted positions with one tuple; it lies in one contig and, with regions, in one merged region.  Runs come
+ * back in ascending (contig, start) order: the result is unique and deterministic.
+ * Outputs, all in host memory in both entries:
+ *   runs[run_capacity], *n_runs_out   the records; runs == NULL counts only.  When runs is given and the total exceeds
+ *                           run_capacity the call returns QMCP_ERANGE with *n_runs_out set to the total, and runs and
+ *                           stats untouched
+ *   stats                   n_runs, positions_in_runs (emitted positions), scope_positions, short_positions (ALL short
+ *                           positions in scope, whatever the flags say: the report's deficit_positions), reads_placed,
+ *                           reads_kept, regions_in / regions_merged, position_batches, ms_track (device time)
+ * Invariant: n_runs <= min(positions_in_runs, 2 * reads_placed + n_contigs + regions_merged) -- every change of any
+ * channel sits at some read's start or end + 1, every other run begins at the start of a contig or merged region.
+ * Errors: the report's, in its order -- null columns, a bad table and a contig above one position batch on the host
+ * before the context is looked at; a bad contig id (QMCP_EINVAL) or a bad placed read (QMCP_EREAD) found on the device
+ * among ALL reads; the capacity last.  The caller's buffers are written only after all of them. */
+#define QMCP_TRACK_IN 1u
+#define QMCP_TRACK_KEPT 2u
+#define QMCP_TRACK_SHORT_ONLY 4u
+#define QMCP_TRACK_SKIP_ZERO 8u
+typedef struct qmcp_hip_track_run {
+    uint32_t contig, start, end;                  /* the run, inclusive, in the contig's coordinates       */
+    uint32_t depth_in, depth_kept;                /* clamped; 0 for a channel that is not selected         */
+    uint32_t flags;                               /* bit 0: short                                          */
+} qmcp_hip_track_run;
+typedef struct qmcp_hip_track_stats {
+    uint64_t n_runs, positions_in_runs, scope_positions, short_positions, reads_placed, reads_kept;
+    uint32_t regions_in, regions_merged, position_batches;
+    float ms_track;                               /* HIP events on the context's stream                    */
+} qmcp_hip_track_stats;
+int qmcp_hip_depth_track_host(qmcp_hip_ctx* ctx,
+                              const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                              uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                              const uint64_t* keep_mask /* may be NULL */, uint32_t max_coverage,
+                              const uint32_t* target_offsets /* may be NULL */, const uint32_t* target_starts,
+                              const uint32_t* target_ends, uint32_t padding, uint32_t flags, uint32_t depth_cap,
+                              qmcp_hip_track_run* runs /* may be NULL */, uint64_t run_capacity,
+                              uint64_t* n_runs_out, qmcp_hip_track_stats* stats);
+/* The same with the three columns and the mask in device memory, ordered after `hip_stream` as
+ * qmcp_hip_depth_report_device is; returns when the outputs are in host memory. */
+int qmcp_hip_depth_track_device(qmcp_hip_ctx* ctx,
+                                const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                const uint64_t* d_keep_mask /* may be NULL */, uint32_t max_coverage,
+                                const uint32_t* target_offsets /* may be NULL */, const uint32_t* target_starts,
+                                const uint32_t* target_ends, uint32_t padding, uint32_t flags, uint32_t depth_cap,
+                                qmcp_hip_track_run* runs /* may be NULL */, uint64_t run_capacity,
+                                uint64_t* n_runs_out, void* hip_stream, qmcp_hip_track_stats* stats);
+
 /* Coverage ladder: the same reads at several falling coverages in one call -- a titration (100x, 50x, 30x, 10x of one
  * sample).  Reads, contig_ids, contig_lengths / n_contigs and limits are those of qmcp_hip_solve_by_contig_host.
  * coverages[0] > coverages[1] > ... > coverages[n_levels - 1] >= 1, 1 <= n_levels <= QMCP_LADDER_MAX_LEVELS.
