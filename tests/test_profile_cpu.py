@@ -1,9 +1,11 @@
 """The coverage profile without a device: the model of tests/profile_model.py tied to the oracle, to brute force and to
-the target model; the host cap table (genome-downsampler_amd/csrc/cap_table.h through tests/cpp/cap_table_driver.cpp);
+the target model; its second restatement from sorted events (fast_select) and the translation helper tied to the first;
+the host cap table (genome-downsampler_amd/csrc/cap_table.h through tests/cpp/cap_table_driver.cpp);
 the bedGraph parser; the C ABI (header, exports, struct layout, version)."""
 import ctypes as C
 import os
 import subprocess
+import types
 
 import numpy as np
 import pytest
@@ -78,6 +80,102 @@ def test_model_count_equals_target_model(oracle):
         want, _ = tm.expected_mask(oracle, s, e, ids, lengths, offs, r0, r1, M)
         count = lambda m: int(pm.unpack(m, n).sum())
         assert count(mask) == count(want)
+
+
+
+# ---------------------------------------------------------------------------------------------- the model from sorted events
+def test_fast_model_equals_the_model_bit_for_bit():
+    """2 000 instances drawn as test_gpu_profile.random_instance draws them (1..4 contigs on <= 700 positions, <= 400
+    reads of spans up to 3 | 40 | 130 | 500, 5 % unplaced, regions at multiples of 64 and +-1 with caps 0..12, some
+    clipped).  What the draw has to contain is counted: cap-0 runs longer than the longest read, caps far above the
+    coverage, and reads that tie in end and start (decided by the index)"""
+    from test_gpu_profile import random_instance
+    rng = np.random.default_rng(20265)
+    zero_runs = high_caps = ties = kept_some = 0
+    for _ in range(2000):
+        s, e, ids, lengths, default, offs, r0, r1, caps = inst = random_instance(rng)
+        want = pm.expected_mask(*inst)
+        assert np.array_equal(pm.fast_expected_mask(*inst), want), (lengths.tolist(), s.size)
+        placed = ids != pm.NO_CONTIG
+        span_max = int((e.astype(np.int64) - s + 1).max())
+        zero_runs += bool(np.any((caps == 0) & (r1.astype(np.int64) - r0 + 1 > span_max)))
+        high_caps += bool(np.any(caps == 100_000))
+        cells = (ids[placed].astype(np.int64) << 40) | (s[placed].astype(np.int64) << 20) | e[placed]
+        ties += np.unique(cells).size < cells.size
+        kept_some += bool(want.any())
+    assert zero_runs > 600 and high_caps > 400 and ties > 1000 and kept_some > 1500, (zero_runs, high_caps, ties, kept_some)
+
+
+def test_fast_model_is_minimum_under_random_caps():
+    rng = np.random.default_rng(20262)                       # the instances of test_model_is_valid_and_minimum_under_random_caps
+    for _ in range(1200):
+        s, e, L = tiny_instance(rng)
+        cap = run_caps(rng, L, 5)
+        offs, r0, r1, caps = pm.regions_of(cap)
+        kept = pm.fast_select(s, e, L, 77, pm.clipped_regions(L, r0, r1, caps))   # (the regions tile the contig)
+        assert pm.is_valid(s, e, cap, kept)
+        assert int(kept.sum()) == pm.brute_minimum(s, e, cap)
+
+
+def test_translation_helper_changes_nothing():
+    """random instances, and instances whose reads sit in a few islands of long contigs (still short enough for the
+    model with an array per position): the mask, demand and capped positions of the compact instance are the original's,
+    under both models; the compact contigs are no longer than the reads' islands and the gaps between them"""
+    from test_gpu_profile import random_instance
+    rng = np.random.default_rng(20266)
+    shrunk = 0
+    for k in range(400):
+        if k % 2:
+            s, e, ids, lengths, default, offs, r0, r1, caps = random_instance(rng)
+        else:
+            n_contigs = int(rng.integers(1, 4))
+            lengths = rng.integers(5_000, 30_000, size=n_contigs).astype(np.uint32)
+            n = int(rng.integers(1, 200))
+            ids = rng.integers(0, n_contigs, size=n).astype(np.uint32)
+            Ls = lengths[ids].astype(np.int64)
+            anchors = rng.integers(0, 30_000, size=(n_contigs, 3))                # three islands per contig, the
+            anchors[:, 0], anchors[:, 2] = 0, 30_000                              # first and last at the contig's ends
+            span = rng.integers(1, 120, size=n)
+            s = np.clip(anchors[ids, rng.integers(0, 3, size=n)] + rng.integers(-100, 100, size=n), 0, Ls - span)
+            e = s + span - 1
+            ids[rng.random(n) < 0.05] = pm.NO_CONTIG
+            offs, r0, r1, caps = pm.random_regions(rng, lengths, 6, max_regions=20)
+            default = int(rng.integers(0, 7))
+            s, e = s.astype(np.uint32), e.astype(np.uint32)
+        c = pm.compact(s, e, ids, lengths, offs, r0, r1, caps)
+        cs, ce, cids, clen = c[:4]
+        assert np.array_equal(cids, ids) and np.all(clen <= np.maximum(lengths, 1))
+        assert np.array_equal(ce.astype(np.int64) - cs, e.astype(np.int64) - s)
+        shrunk += int(clen.sum()) * 4 < int(lengths.sum())
+        want = pm.expected_mask(s, e, ids, lengths, default, offs, r0, r1, caps)
+        assert np.array_equal(pm.expected_mask(cs, ce, cids, clen, default, *c[4:]), want), k
+        assert np.array_equal(pm.fast_expected_mask(cs, ce, cids, clen, default, *c[4:]), want), k
+        assert np.array_equal(pm.fast_expected_mask(s, e, ids, lengths, default, offs, r0, r1, caps), want), k
+        assert pm.demand_and_capped(cs, ce, cids, clen, default, *c[4:]) == \
+            pm.demand_and_capped(s, e, ids, lengths, default, offs, r0, r1, caps), k
+    assert shrunk > 100
+
+
+def test_form_of_at_every_threshold():
+    """the forms as kernels/profile.inc.hip's launchers and api/profile.inc.hip choose them: B from (max_span + 127) / 64
+    (5 takes the form of 6, 7 that of 8, beyond 8 the plain walk), K = 4 up to 64 workgroups, rings in global memory
+    beyond spans of 16 383, 64-bit keys from 5 sort passes, windows of at least 64 longest spans and none from 256 contigs"""
+    st = lambda span, passes=4, ltot=1000: types.SimpleNamespace(max_span=span, sort_passes=passes, total_length=ltot)
+    want = {1: 2, 64: 2, 65: 3, 128: 3, 129: 4, 192: 4, 193: 6, 320: 6, 321: 8, 448: 8}
+    for span, b in want.items():
+        assert pm.form_of(st(span), 3, -1) == ("rec", "reg", b, 4)
+        assert pm.form_of(st(span, 5), 65, -1) == ("k64", "reg", b, 1)
+    assert pm.form_of(st(449), 3, -1) == ("rec", "plain", "lds")
+    assert pm.form_of(st(16383, 6), 3, 1) == ("k64", "plain", "lds")
+    assert pm.form_of(st(16384), 3, 1) == ("rec", "plain", "global")
+    assert pm.form_of(st(100), 64, -1)[3] == 4 and pm.form_of(st(100), 65, -1)[3] == 1
+    assert pm.stretch_windows(2 * 6400 - 1, 100, 3) == 0 and pm.stretch_windows(2 * 6400, 100, 3) == 2
+    assert pm.stretch_windows(1 << 30, 100, 255) == 3840 and pm.stretch_windows(1 << 30, 100, 256) == 0
+    assert pm.form_of(st(100, 4, 61 * 6400), 3, 1)[3] == 4 and pm.form_of(st(100, 4, 62 * 6400), 3, 1)[3] == 1
+    assert pm.form_of(st(100, 4, 62 * 6400), 3, -1)[3] == 4
+    assert (pm.need_form(4096), pm.need_form(4097)) == ("need_lds", "need_global")
+    with pytest.raises(ValueError):
+        pm.form_of(st(100), 3, 0)
 
 
 # ---------------------------------------------------------------------------------------------- the host table
