@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_stratified_host", "qmcp_hip_solve_stratified_device",
     "qmcp_hip_solve_dedup_host", "qmcp_hip_solve_dedup_device",
     "qmcp_hip_solve_profile_host", "qmcp_hip_solve_profile_device",
+    "qmcp_hip_solve_pairs_host", "qmcp_hip_solve_pairs_device",
 )
 
 QMCP_OK = 0
@@ -48,6 +49,7 @@ KIND_UNIFORM, KIND_LOW_BOTH_SIDES, KIND_HOLE, KIND_ZERO_BOTH_SIDES = 0, 1, 2, 3
 NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never kept)
 TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
 LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
+PAIR_MAX_STAGES = 16  # QMCP_PAIR_MAX_STAGES
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
 DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
@@ -118,6 +120,22 @@ class ProfileStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PairStats(C.Structure):
+    """qmcp_hip_pair_stats: the stages of a pair-aware solve (the first n_stages entries of every array count)"""
+    _fields_ = [("n_stages", C.c_uint32), ("reserved", C.c_uint32), ("n_selected", C.c_uint64 * PAIR_MAX_STAGES),
+                ("n_kept", C.c_uint64 * PAIR_MAX_STAGES), ("capped_positions", C.c_uint64 * PAIR_MAX_STAGES),
+                ("demand", C.c_uint64 * PAIR_MAX_STAGES), ("target", C.c_uint32 * PAIR_MAX_STAGES),
+                ("sweeps", C.c_uint32 * PAIR_MAX_STAGES), ("ms_stage", C.c_float * PAIR_MAX_STAGES),
+                ("ms_pairs", C.c_float), ("reserved2", C.c_uint32)]
+
+    def as_dict(self):
+        k = self.n_stages
+        out = {name: list(getattr(self, name))[:k]
+               for name in ("target", "n_selected", "n_kept", "capped_positions", "demand", "sweeps", "ms_stage")}
+        out.update(n_stages=k, ms_pairs=self.ms_pairs)
+        return out
 
 
 class DepthRow(C.Structure):
@@ -332,6 +350,11 @@ _hip.qmcp_hip_solve_profile_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.
 _hip.qmcp_hip_solve_profile_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                                C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
                                                C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(ProfileStats)]
+_hip.qmcp_hip_solve_pairs_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
+                                           _u32p, C.c_uint32, _u64p, C.POINTER(Stats), C.POINTER(PairStats)]
+_hip.qmcp_hip_solve_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p, C.c_uint32,
+                                             C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                             C.POINTER(PairStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -413,6 +436,11 @@ if _host is not None:
                                                        C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p,
                                                        C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_profile.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_pairs.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                     C.c_uint32, C.c_uint32, C.c_int, _u32p, C.c_uint32, C.c_char_p,
+                                                     C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_int,
+                                                     C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_pairs.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -505,6 +533,7 @@ class Solver:
         self.last_ladder_stats = None
         self.last_stratum_rows = None
         self.last_dedup_stats = None
+        self.last_pair_stats = None
 
     def close(self):
         if self._ctx:
@@ -835,6 +864,38 @@ class Solver:
                                                   C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(ps)))
         self.last_stats, self.last_profile_stats = st, ps
         return ps
+
+    def solve_pairs(self, starts, ends, contig_ids, contig_lengths, max_coverage, stages=None):
+        """pair-aware downsampling (qmcp_hip_solve_pairs_host): reads (2q, 2q + 1) are pair q, stages the rising targets
+        T_1 < ... < T_k = max_coverage (None: ceil(M / 2), then M).  Stage 1 is solve_by_contig at T_1 with the pairs
+        completed; every further stage credits the depth of the reads already kept and tops up to its target among the
+        others, then completes the pairs again.  -> (mask, stats, pair_stats): the host keep bitmask in INPUT order (whole
+        pairs), stage 1's Stats, the PairStats.  Also left in last_stats / last_pair_stats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ps = Stats(), PairStats()
+        _check(_hip.qmcp_hip_solve_pairs_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                              lengths.size, int(max_coverage), _p32(tg), 0 if tg is None else tg.size,
+                                              _p64(mask), C.byref(st), C.byref(ps)))
+        self.last_stats, self.last_pair_stats = st, ps
+        return mask[:mask_words(n)], st, ps
+
+    def solve_pairs_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_mask, stages=None,
+                           stream=0):
+        """solve_pairs on device pointers (ints); the input-order mask is written to d_mask.  -> (stats, pair_stats)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        st, ps = Stats(), PairStats()
+        _check(_hip.qmcp_hip_solve_pairs_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                int(max_coverage), _p32(tg), 0 if tg is None else tg.size,
+                                                C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(ps)))
+        self.last_stats, self.last_pair_stats = st, ps
+        return st, ps
 
     def _depth_call(self, entry, head, n, lengths, mask_arg, max_coverage, target_offsets, target_starts, target_ends,
                     padding, n_bins, tail):
@@ -1660,7 +1721,7 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
                    targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
                    ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None,
-                   track=None, track_channel="kept", track_cap=0):
+                   track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1707,8 +1768,43 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     Solver.depth_track with both channels) of the reads the solve saw against the FINAL kept set (after mate
     completion), inside the targets with their padding when given.  Needs per_reference=True; goes together with
     targets, report and amplicon files as report does; not together with ladder, stratify, dedup or profile
-    (ValueError).  None: nothing changes"""
+    (ValueError).  None: nothing changes.
+    pair_aware=True (BamApiConfig::pair_aware, with pair_stages: rising targets that end at max_coverage; None:
+    ceil(max_coverage / 2), then max_coverage): one qmcp_hip_solve_pairs_host call -- the solve runs in stages that
+    credit the coverage of the mates already kept, so the output stays near max_coverage instead of near twice that.
+    The output is written from the final mask, which holds whole pairs: no find_pairs follows.  Needs
+    per_reference=True; not together with targets, report, track, ladder, stratify, dedup, profile, amplicon files or
+    "quasi-mcp-hip-quality" (ValueError).  False: nothing changes"""
     _need_host()
+    if pair_aware:
+        if not per_reference:
+            raise ValueError("pair-aware downsampling needs per_reference=True")
+        for given, what in ((targets, "targets"), (report, "a depth report"), (track is not None, "a depth track"),
+                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
+                            (dedup, "dedup"), (profile is not None, "a coverage profile")):
+            if given:
+                raise ValueError(f"pair-aware downsampling does not go together with {what}")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("pair-aware downsampling does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("pair-aware downsampling does not take a solver that grades by quality")
+        tg = None if pair_stages is None else np.array([int(t) for t in pair_stages], dtype=np.uint32)
+        if tg is not None and tg.size == 0:
+            raise ValueError("pair_stages must hold at least one target (or be None for the default schedule)")
+        err = C.create_string_buffer(1024)
+        n = _host.qmcp_host_downsample_bam_pairs(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            1, _p32(tg), 0 if tg is None else tg.size, None, None, None, None, 0, None, 0, 0, None, None, 0, err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
+    if pair_stages is not None:
+        raise ValueError("pair_stages need pair_aware=True")
     if track is not None:
         if not per_reference:
             raise ValueError("a depth track needs per_reference=True")

@@ -9,6 +9,8 @@
 // Grouping happens once; a batch only gathers its own reads.
 // A coverage ladder (api/ladder.inc.hip) is this call with further levels run inside each batch, on its gathered columns.
 // A coverage profile (api/profile.inc.hip) is this call with every batch solved under its own regions' caps.
+// A pair-aware solve (api/pairs.inc.hip) is this call at its first target, with the further stages run over all batches
+// once the last batch's mask is in place.
 namespace {
 
 struct LadderRun;
@@ -18,6 +20,10 @@ struct ProfileRun;
 int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
                         const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
                         qmcp_hip_stats* st);
+struct PairRun;
+int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
+                      const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
+                      const uint32_t* lengths, uint64_t n64, uint64_t* d_mask, const qmcp_hip_stats& first);
 
 // the batches' stats as one: counts and times summed, the route of the batch with the most reads
 void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, bool largest) {
@@ -51,7 +57,8 @@ void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, boo
 int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                               uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, uint32_t M, uint64_t* d_mask,
                               qmcp_hip_stats* stats, LadderRun* ladder = nullptr,
-                              ProfileRun* profile = nullptr /* then M is the default cap */) {
+                              ProfileRun* profile = nullptr /* then M is the default cap */,
+                              PairRun* pairs = nullptr /* then M is the first stage's target */) {
     if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
     if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
     if (n64 > (1ull << 31))
@@ -171,6 +178,7 @@ int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
         add_batch_stats(sum, bs, first, b == largest);
         first = false;
     }
+    if (pairs) TRY(pair_later_stages(c, *pairs, sorted, offs, batches, d_starts, d_ends, lengths, n64, d_mask, sum));
     HIP_TRY(hipStreamSynchronize(st));
     collect_spans(c);
     if (stats) *stats = sum;

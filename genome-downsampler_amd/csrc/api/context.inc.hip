@@ -153,6 +153,12 @@ struct qmcp_hip_ctx {
     // coverage profile (api/profile.inc.hip): a batch's need[] (min(cov, cap) per position, top bit = cut position), its
     // regions in global positions (starts | ends | caps), and the call's two counters (capped positions, demand)
     DevBuf pf_need, pf_tab, pf_stat;
+    // pair-aware solves (api/pairs.inc.hip), all its own: the kept set's bits in a batch's grouped order and their
+    // complement (the candidates), the complement's scanned word popcounts and their spine, the batch's read offsets and
+    // the candidates' ranks at them, its position offsets, the credit events and their scan with its spine, the
+    // candidates' columns, input indices and keep mask, need[], and the counters (capped positions, demand, |S|)
+    DevBuf pr_in, pr_rest, pr_words, pr_spine, pr_offs[2], pr_poff, pr_credit, pr_cspine, pr_starts, pr_ends, pr_orig,
+        pr_mask, pr_need, pr_stat;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

@@ -171,7 +171,10 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->dd_tab, &c->dd_stat, &c->dd_bare, &c->dd_keys[0], &c->dd_keys[1], &c->dd_vals[0], &c->dd_vals[1],
                       &c->dd_hist, &c->dd_spine, &c->dd_flag, &c->dd_head, &c->dd_cid, &c->dd_surv, &c->dd_words,
                       &c->dd_histo, &c->dd_cs, &c->dd_ce, &c->dd_ci, &c->dd_map, &c->dd_maskc, &c->dd_tags, &c->dd_dupm,
-                      &c->pf_need, &c->pf_tab, &c->pf_stat};
+                      &c->pf_need, &c->pf_tab, &c->pf_stat,
+                      &c->pr_in, &c->pr_rest, &c->pr_words, &c->pr_spine, &c->pr_offs[0], &c->pr_offs[1], &c->pr_poff,
+                      &c->pr_credit, &c->pr_cspine, &c->pr_starts, &c->pr_ends, &c->pr_orig, &c->pr_mask, &c->pr_need,
+                      &c->pr_stat};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

@@ -1,0 +1,295 @@
+// pairs.inc.hip -- part of qmcp_api.hip (one translation unit).
+// qmcp_hip_solve_pairs_host / _device: a staged solve that credits the mates' coverage.  Reads (2q, 2q + 1) are pair q;
+// targets T_1 < ... < T_k = M.  Stage 1 is the by-contig solve at T_1 (solve_by_contig_on_device, every fast route) and
+// the pair OR over its input-order mask S.  Stage j > 1 runs over ALL batches of the same grouping before the next stage
+// begins -- a mate may lie in another batch, so S must be whole first -- and per batch:
+//   1. k_bc_gather (the batch's columns again) and k_pair_gather_mask: S in grouped order, and its complement, the
+//      stage's candidates
+//   2. k_word_popcounts -> exclusive scan of the complement; k_ladder_offsets: the candidates' contig offsets, read back
+//      once; k_ladder_compact: their starts, ends and input indices
+//   3. k_pair_credit_events on a zeroed axis, scanned in place: credit[p], the depth of the batch's reads in S
+//   4. capped_solve_batch (api/profile.inc.hip) on the candidates with k_pair_need building need[p] = min(cov_rest(p),
+//      max(0, T_j - credit[p])); its counters come back before the sweep is queued, and a batch that asks for nothing
+//      queues none
+//   5. k_expand_mask_reads ORs the kept candidates into S
+// and after the last batch k_complete_pairs over S and its popcount.  A batch without candidates stops after step 2.
+// Buffers: all the feature's own (pr_*), apart from the by-contig call's gathered columns (bc_starts / bc_ends), which
+// are refilled per batch; nothing a solve owns is held across a solve.
+namespace {
+
+struct PairRun {
+    std::vector<uint32_t> targets;
+    qmcp_hip_pair_stats ps;
+};
+
+// need[] of a stage after the first: the credit of the reads already kept, through k_pair_need
+struct PairNeed : CappedNeed {
+    uint32_t target;
+    unsigned long long counters[2] = {0, 0};  // capped positions, demand: this batch's
+    explicit PairNeed(uint32_t t) : target(t) {}
+    const char* name() const override { return "k_pair_need"; }
+    DevBuf& need_buf(qmcp_hip_ctx* c) override { return c->pr_need; }
+    int reserve(qmcp_hip_ctx*) override { return QMCP_OK; }
+    int upload(qmcp_hip_ctx* c, hipStream_t st) override {
+        HIP_TRY(hipMemsetAsync(c->pr_stat.p, 0, 2 * sizeof(unsigned long long), st));
+        return QMCP_OK;
+    }
+    void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
+        qmcp::launch_pair_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
+                               (const uint32_t*)c->pr_credit.p + qmcp::pair_credit_pad(), ltot, target, need,
+                               (unsigned long long*)c->pr_stat.p);
+    }
+    int no_demand(qmcp_hip_ctx* c, hipStream_t st, bool* none) override {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(counters, c->pr_stat.p, sizeof(counters), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *none = counters[1] == 0;
+        return QMCP_OK;
+    }
+};
+
+// queues S |= mates and |S| -> pr_stat[2]
+int pair_complete_and_count(qmcp_hip_ctx* c, uint64_t* d_mask, uint64_t n64) {
+    hipStream_t st = c->stream;
+    const uint32_t words = (uint32_t)((n64 + 63) / 64);
+    unsigned long long* d_count = (unsigned long long*)c->pr_stat.p + 2;
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+    if (words) {
+        KernelSpan sp(c, "k_complete_pairs(pairs) + k_pair_count_bits");
+        qmcp::launch_complete_pairs(st, d_mask, words, n64);
+        qmcp::launch_pair_count_bits(st, d_mask, words, d_count);
+    }
+    HIP_TRY(hipGetLastError());
+    return QMCP_OK;
+}
+
+int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
+                      const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
+                      const uint32_t* lengths, uint64_t n64, uint64_t* d_mask, const qmcp_hip_stats& first) {
+    hipStream_t st = c->stream;
+    qmcp_hip_pair_stats& ps = pr.ps;
+    const uint32_t pad = qmcp::pair_credit_pad();
+    EventPair ev_a(c), ev_b(c);
+    if (!ev_a.a || !ev_a.b || !ev_b.a || !ev_b.b) return fail(QMCP_EHIP, "event creation failed");
+    TRY(ensure(c, c->pr_stat, 4 * sizeof(unsigned long long)));
+    unsigned long long count = 0;
+    const unsigned long long* d_count = (const unsigned long long*)c->pr_stat.p + 2;
+    ps.n_selected[0] = first.n_kept;
+    ps.ms_stage[0] = first.ms_total;
+    // ev_a brackets what is queued between two host waits; `open` says its first event has been recorded
+    bool open = false;
+    auto begin = [&]() -> int {
+        if (!open) HIP_TRY(hipEventRecord(ev_a.a, st));
+        open = true;
+        return QMCP_OK;
+    };
+    auto wait = [&]() -> int {  // close the bracket, wait, add its time
+        HIP_TRY(hipEventRecord(ev_a.b, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ps.ms_pairs += elapsed(ev_a.a, ev_a.b);
+        open = false;
+        return QMCP_OK;
+    };
+    TRY(begin());
+    TRY(pair_complete_and_count(c, d_mask, n64));
+    HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
+    TRY(wait());
+    ps.n_kept[0] = count;
+
+    std::vector<uint32_t> offs32, poff32, ranks;
+    std::vector<uint64_t> roff, cand_roff;
+    for (uint32_t j = 1; j < (uint32_t)pr.targets.size(); ++j) {
+        const uint32_t target = pr.targets[j];
+        for (size_t b = 0; b < batches.size(); ++b) {
+            const qmcp::ContigBatch& bt = batches[b];
+            if (bt.n_reads == 0) continue;
+            const uint32_t nb = (uint32_t)bt.n_reads;
+            const uint32_t ltot = (uint32_t)bt.positions;
+            const uint32_t words = (nb + 63u) / 64u;
+            const size_t tab = (size_t)bt.n_contigs + 1;
+            const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
+            roff.assign(tab, 0);
+            offs32.assign(tab, 0);
+            poff32.assign(tab, 0);
+            ranks.assign(tab, 0);
+            for (uint32_t k = 0; k <= bt.n_contigs; ++k) {
+                roff[k] = offs[bt.first_contig + k] - offs[bt.first_contig];
+                offs32[k] = (uint32_t)roff[k];  // (a batch holds at most 2^30 reads)
+                if (k) poff32[k] = poff32[k - 1] + lengths[bt.first_contig + k - 1];  // (and at most 2^31 - 2 positions)
+            }
+            TRY(ensure(c, c->pr_in, (size_t)words * sizeof(uint64_t)));
+            TRY(ensure(c, c->pr_rest, (size_t)words * sizeof(uint64_t)));
+            TRY(ensure(c, c->pr_words, ((size_t)words + 2) * sizeof(uint32_t)));
+            TRY(ensure(c, c->pr_spine, (size_t)(qmcp::scan_spine_entries(words + 1) + 1) * sizeof(uint32_t) + 16));
+            TRY(ensure(c, c->pr_offs[0], tab * sizeof(uint32_t)));
+            TRY(ensure(c, c->pr_offs[1], tab * sizeof(uint32_t)));
+            TRY(ensure(c, c->pr_poff, tab * sizeof(uint32_t)));
+            TRY(ensure(c, c->pr_credit, ((size_t)ltot + pad + 4) * sizeof(uint32_t)));
+            TRY(ensure(c, c->pr_cspine, (size_t)(qmcp::scan_spine_entries(ltot + pad) + 1) * sizeof(uint32_t) + 16));
+            // 1 - 3: S and the candidates in grouped order, the candidates' offsets, the credit of S
+            TRY(begin());
+            HIP_TRY(hipMemcpyAsync(c->pr_offs[0].p, offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c->pr_poff.p, poff32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(c->pr_credit.p, 0, ((size_t)ltot + pad) * sizeof(uint32_t), st));
+            {
+                KernelSpan sp(c, "k_bc_gather");
+                qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
+            }
+            {
+                KernelSpan sp(c, "k_pair_gather_mask");
+                qmcp::launch_pair_gather_mask(st, bsorted, nb, d_mask, (uint64_t*)c->pr_in.p, (uint64_t*)c->pr_rest.p);
+            }
+            {
+                KernelSpan sp(c, "pair candidates(popcounts, scan, k_ladder_offsets)");
+                qmcp::launch_word_popcounts(st, (const uint64_t*)c->pr_rest.p, words, (uint32_t*)c->pr_words.p);
+                qmcp::launch_exclusive_scan(st, (const uint32_t*)c->pr_words.p, words, (uint32_t*)c->pr_words.p,
+                                            (uint32_t*)c->pr_spine.p, true);
+                qmcp::launch_ladder_offsets(st, (const uint32_t*)c->pr_offs[0].p, bt.n_contigs, (const uint64_t*)c->pr_rest.p,
+                                            (const uint32_t*)c->pr_words.p, (uint32_t*)c->pr_offs[1].p);
+            }
+            {
+                KernelSpan sp(c, "k_pair_credit_events + scan");
+                qmcp::launch_pair_credit_events(st, bsorted, nb, (const uint64_t*)c->pr_in.p, (const uint32_t*)c->bc_starts.p,
+                                                (const uint32_t*)c->bc_ends.p, (const uint32_t*)c->pr_poff.p, bt.first_contig,
+                                                (uint32_t*)c->pr_credit.p);
+                qmcp::launch_exclusive_scan(st, (const uint32_t*)c->pr_credit.p, ltot + pad, (uint32_t*)c->pr_credit.p,
+                                            (uint32_t*)c->pr_cspine.p, false);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(ranks.data(), c->pr_offs[1].p, tab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            TRY(wait());
+            if (qmcp::pair_candidate_offsets(roff.data(), ranks.data(), bt.n_contigs, cand_roff) != QMCP_OK)
+                return fail(QMCP_EHIP, "pair stage %u: the candidates' ranks do not fit the contig offsets", j);
+            const uint32_t n_c = ranks[bt.n_contigs];
+            if (n_c == 0) continue;  // every read of the batch is kept already
+            const size_t cb = (size_t)n_c * sizeof(uint32_t);
+            TRY(ensure(c, c->pr_starts, cb));
+            TRY(ensure(c, c->pr_ends, cb));
+            TRY(ensure(c, c->pr_orig, cb));
+            TRY(ensure(c, c->pr_mask, (size_t)((n_c + 63u) / 64u) * sizeof(uint64_t)));
+            HIP_TRY(hipEventRecord(ev_b.a, st));
+            {
+                KernelSpan sp(c, "k_ladder_compact(pairs)");
+                qmcp::launch_ladder_compact(st, true, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, bsorted,
+                                            (const uint64_t*)c->pr_rest.p, (const uint32_t*)c->pr_words.p, nb,
+                                            (uint32_t*)c->pr_starts.p, (uint32_t*)c->pr_ends.p, (uint32_t*)c->pr_orig.p);
+            }
+            HIP_TRY(hipEventRecord(ev_b.b, st));
+            HIP_TRY(hipGetLastError());
+            // 4: the capped route on the candidates
+            PairNeed nd(target);
+            qmcp_hip_stats bs;
+            std::memset(&bs, 0, sizeof(bs));
+            bool swept = false;
+            TRY(capped_solve_batch(c, nd, target, (const uint32_t*)c->pr_starts.p, (const uint32_t*)c->pr_ends.p,
+                                   cand_roff.data(), lengths + bt.first_contig, bt.n_contigs, n_c, (uint64_t*)c->pr_mask.p, &bs,
+                                   &swept));
+            ps.ms_pairs += elapsed(ev_b.a, ev_b.b) + nd.ms;
+            ps.n_selected[j] += bs.n_kept;
+            ps.ms_stage[j] += bs.ms_total;
+            ps.sweeps[j] += swept ? 1u : 0u;
+            ps.capped_positions[j] += nd.counters[0];
+            ps.demand[j] += nd.counters[1];
+            // 5: the kept candidates join S (the bracket stays open into the next batch, or the stage's end)
+            if (bs.n_kept) {
+                TRY(begin());
+                KernelSpan sp(c, "k_expand_mask_reads(pairs)");
+                qmcp::launch_expand_mask_reads(st, (const uint64_t*)c->pr_mask.p, (const uint32_t*)c->pr_orig.p, n_c, d_mask);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        TRY(begin());
+        TRY(pair_complete_and_count(c, d_mask, n64));
+        HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
+        TRY(wait());
+        ps.n_kept[j] = count;
+    }
+    return QMCP_OK;
+}
+
+// what both entries check before anything is copied or launched, and the schedule
+int check_pairs_call(uint64_t n_reads, const uint32_t* stages, uint32_t n_stages, uint32_t M, std::vector<uint32_t>& targets) {
+    if (n_reads & 1ull)
+        return fail(QMCP_EINVAL, "n_reads %llu is odd: reads (2q, 2q + 1) are pair q", (unsigned long long)n_reads);
+    uint32_t bad = 0;
+    const int rc = qmcp::pair_schedule(stages, n_stages, M, targets, &bad);
+    if (rc == QMCP_OK) return QMCP_OK;
+    if (M >= qmcp::kPairTargetLimit) return fail(QMCP_ERANGE, "max_coverage %u is 2^31 or more", M);
+    if (rc == QMCP_ERANGE) return fail(QMCP_ERANGE, "stages[%u] = %u is 2^31 or more", bad, stages[bad]);
+    if (M == 0) return fail(QMCP_EINVAL, "max_coverage is 0: a staged solve needs a target >= 1");
+    if (n_stages == 0 || n_stages > QMCP_PAIR_MAX_STAGES)
+        return fail(QMCP_EINVAL, "n_stages %u is not in 1 .. %u", n_stages, (unsigned)QMCP_PAIR_MAX_STAGES);
+    if (stages[bad] == 0) return fail(QMCP_EINVAL, "stages[%u] is 0: every stage needs a target >= 1", bad);
+    if (bad > 0 && stages[bad] <= stages[bad - 1])
+        return fail(QMCP_EINVAL, "stages must rise strictly: stages[%u] = %u is not above stages[%u] = %u", bad, stages[bad],
+                    bad - 1, stages[bad - 1]);
+    return fail(QMCP_EINVAL, "the last stage must be max_coverage: stages[%u] = %u, max_coverage = %u", bad, stages[bad], M);
+}
+
+int solve_pairs_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                          uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const std::vector<uint32_t>& targets,
+                          uint64_t* d_mask, qmcp_hip_stats* stats, qmcp_hip_pair_stats* pstats) {
+    PairRun pr;
+    pr.targets = targets;
+    std::memset(&pr.ps, 0, sizeof(pr.ps));
+    pr.ps.n_stages = (uint32_t)targets.size();
+    for (size_t j = 0; j < targets.size(); ++j) pr.ps.target[j] = targets[j];
+    if (pstats) *pstats = pr.ps;
+    qmcp_hip_stats plain;
+    std::memset(&plain, 0, sizeof(plain));
+    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, targets[0], d_mask, &plain, nullptr,
+                                  nullptr, &pr));
+    if (stats) *stats = plain;
+    if (pstats) *pstats = pr.ps;
+    return QMCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmcp_hip_solve_pairs_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                              uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                              const uint32_t* stages, uint32_t n_stages, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                              qmcp_hip_pair_stats* pstats) {
+    std::vector<uint32_t> targets;
+    TRY(check_pairs_call(n_reads, stages, n_stages, max_coverage, targets));
+    TRY(use_device(c));
+    if (n_reads && (!starts || !ends || !contig_ids || !keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    if (n_reads > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n_reads);
+    const size_t nb = (size_t)n_reads * sizeof(uint32_t);
+    const size_t words = (size_t)((n_reads + 63) / 64);
+    TRY(ensure(c, c->in_starts, nb));
+    TRY(ensure(c, c->in_ends, nb));
+    TRY(ensure(c, c->in_aux0, nb));
+    TRY(ensure(c, c->mask, words * sizeof(uint64_t)));
+    c->mask_reads = 0;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(c->in_starts.p, starts, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(solve_pairs_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, (const uint32_t*)c->in_aux0.p,
+                              n_reads, contig_lengths, n_contigs, targets, (uint64_t*)c->mask.p, stats, pstats));
+    if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mask_reads = n_reads;
+    return QMCP_OK;
+}
+
+int qmcp_hip_solve_pairs_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends,
+                                const uint32_t* d_contig_ids, uint64_t n_reads, const uint32_t* contig_lengths,
+                                uint32_t n_contigs, uint32_t max_coverage, const uint32_t* stages, uint32_t n_stages,
+                                uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                qmcp_hip_pair_stats* pstats) {
+    std::vector<uint32_t> targets;
+    TRY(check_pairs_call(n_reads, stages, n_stages, max_coverage, targets));
+    TRY(use_device(c));
+    if (n_reads && (!d_starts || !d_ends || !d_contig_ids || !d_keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    TRY(order_after(c, hip_stream));
+    return solve_pairs_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, targets,
+                                 d_keep_mask_out, stats, pstats);
+}
+
+}  // extern "C"

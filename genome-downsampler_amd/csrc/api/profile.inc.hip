@@ -12,6 +12,8 @@
 //      (kept count, stretches), as the mixed route of the plain solve has.
 // Buffers: the solve's own arena for everything the plain mixed route uses; need[] in pf_need, the batch's regions in
 // pf_tab, the two counters in pf_stat.
+// Step 3 is capped_solve_batch, which takes what builds need[] as a CappedNeed: the region table here (ProfileNeed), the
+// credit of the reads already kept in api/pairs.inc.hip.
 namespace {
 
 struct ProfileRun {
@@ -21,16 +23,29 @@ struct ProfileRun {
     std::vector<uint32_t> gs, ge, gcap;  // the batch's regions in its global positions
 };
 
-int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
-                        const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
-                        qmcp_hip_stats* st_out) {
-    const qmcp::CapTable& tab = *pf.tab;
-    const uint32_t* lengths = lengths_all + first_contig;
-    const uint32_t r0 = tab.offs[first_contig], r1 = tab.offs[first_contig + n_contigs];
-    uint32_t max_cap = pf.default_cap;
-    for (uint32_t k = r0; k < r1; ++k) max_cap = std::max(max_cap, tab.cap[k]);
-    if (r0 == r1 && max_cap != 0)
-        return solve_on_device(c, d_starts, d_ends, roff, lengths, n_contigs, n64, pf.default_cap, d_mask, st_out);
+// What builds need[] for capped_solve_batch: a profile's regions here, the credit of the reads already kept in
+// api/pairs.inc.hip.  reserve runs inside the solve's arena block, upload behind the contig tables, launch once boff and
+// eoff exist; no_demand may look at what launch counted (a blocking read-back) and report that nothing is asked for.
+struct CappedNeed {
+    float ms = 0.f;  // device time of launch (+ the cut-point scan), summed over the batches
+    virtual ~CappedNeed() {}
+    virtual const char* name() const = 0;
+    virtual DevBuf& need_buf(qmcp_hip_ctx* c) = 0;
+    virtual int reserve(qmcp_hip_ctx* c) = 0;
+    virtual int upload(qmcp_hip_ctx* c, hipStream_t st) = 0;
+    virtual void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) = 0;
+    virtual int no_demand(qmcp_hip_ctx*, hipStream_t, bool* none) {
+        *none = false;
+        return QMCP_OK;
+    }
+};
+
+// One batch on the sort-based mixed-span route under need[] (steps 3 of the header above); max_cap > 0 is the largest
+// cap the batch can meet, which chooses the windows.  *swept (may be NULL): a sweep was queued.
+int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const uint32_t* d_starts, const uint32_t* d_ends,
+                       const uint64_t* roff, const uint32_t* lengths, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
+                       qmcp_hip_stats* st_out, bool* swept_out = nullptr) {
+    if (swept_out) *swept_out = false;
     if (c->pending) return fail(QMCP_EINVAL, "a solve is already pending on this context (call qmcp_hip_solve_end)");
     Problem pr;
     TRY(check_problem(roff, lengths, n_contigs, n64, pr));
@@ -51,7 +66,6 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     if (!c->h_scalars) HIP_TRY(hipHostMalloc((void**)&c->h_scalars, 16 * sizeof(unsigned long long), hipHostMallocDefault));
     // the arena, sized before anything is queued
     const uint32_t n_tiles = qmcp::sort_tiles(n);
-    const uint32_t n_reg = r1 - r0;
     c->sized = false;
     {
         const uint32_t spine_a = qmcp::scan_spine_entries(256u * n_tiles);
@@ -70,23 +84,15 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
         TRY(ensure(c, c->scalars, 64));
         TRY(ensure(c, c->stats, 12 * sizeof(uint32_t)));
         TRY(ensure(c, c->segs, qmcp::sweep_segment_words(n_contigs < 256 ? n_contigs : 0, qmcp::kMaxSweepWindows) * sizeof(uint32_t)));
-        TRY(ensure(c, c->pf_need, ((size_t)ltot + 8) * sizeof(uint32_t)));
-        TRY(ensure(c, c->pf_tab, 3 * (size_t)n_reg * sizeof(uint32_t) + 16));
+        TRY(ensure(c, nd.need_buf(c), ((size_t)ltot + 8) * sizeof(uint32_t)));
+        TRY(nd.reserve(c));
     }
     c->grew_mid_solve = 0;
     c->mixed_seen = true;
     HIP_TRY(hipEventRecord(c->ev[EV_BEGIN], st));
     TRY(upload_tables(c, roff, pr));
     c->sized = true;
-    qmcp::batch_cap_table(tab, lengths_all, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
-    uint32_t* d_rs = (uint32_t*)c->pf_tab.p;
-    uint32_t* d_re = d_rs + n_reg;
-    uint32_t* d_cap = d_re + n_reg;
-    if (n_reg) {
-        HIP_TRY(hipMemcpyAsync(d_rs, pf.gs.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_re, pf.ge.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_cap, pf.gcap.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
-    }
+    TRY(nd.upload(c, st));
     // span statistics, validation, global start positions (vals[1]): the one read-back that shapes the keys
     uint32_t hs[3];
     TRY(run_prepare(c, d_starts, d_ends, pr, nullptr, true, false, false, 0, nullptr, hs));
@@ -157,7 +163,7 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
     // need[], cut points
-    const uint32_t* d_need = (const uint32_t*)c->pf_need.p;
+    const uint32_t* d_need = (const uint32_t*)nd.need_buf(c).p;
     const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
     const uint32_t windows = qmcp::plan_mixed_sweep(c->opt, n, max_span, ltot, n_contigs, max_cap, in_regs, false).windows;
     const uint32_t* seg = nullptr;
@@ -167,11 +173,12 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     if (!ev_pf.a || !ev_pf.b) return fail(QMCP_EHIP, "event creation failed");
     HIP_TRY(hipEventRecord(ev_pf.a, st));
     {
-        KernelSpan sp(c, "k_profile_need");
-        qmcp::launch_profile_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, d_rs, d_re, d_cap, n_reg,
-                                  pf.default_cap, (uint32_t*)c->pf_need.p, (unsigned long long*)c->pf_stat.p);
+        KernelSpan sp(c, nd.name());
+        nd.launch(c, st, ltot, (uint32_t*)nd.need_buf(c).p);
     }
-    if (windows != 0) {
+    bool idle = false;  // nothing is asked for anywhere: no sweep, the zeroed mask stands
+    TRY(nd.no_demand(c, st, &idle));
+    if (windows != 0 && !idle) {
         KernelSpan sp(c, "k_profile_cuts");
         seg = qmcp::launch_profile_segments(st, d_need, (const uint64_t*)c->poff.p, n_contigs, ltot, windows, (uint32_t*)c->segs.p);
         n_seg_max = n_contigs + windows;
@@ -180,8 +187,8 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     HIP_TRY(hipEventRecord(ev_pf.b, st));
     HIP_TRY(hipGetLastError());
     // the capped sweep
-    bool swept = false;
-    if (in_regs) {
+    bool swept = idle;
+    if (in_regs && !idle) {
         {
             KernelSpan sp(c, "k_group_heads");
             qmcp::launch_group_heads(st, wide, c->keys[kin].p, n, (uint32_t*)c->next_head.p);
@@ -211,7 +218,7 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], st));
-    {
+    if (!idle) {
         KernelSpan sp(c, "k_mark");
         qmcp::launch_mark(st, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, ltot, (const uint32_t*)c->boff.p,
                           (const uint32_t*)c->selend.p, d_mask, (unsigned long long*)c->scalars.p);
@@ -223,7 +230,7 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     collect_spans(c);
     local.n_kept = c->h_scalars[0];
     local.sweep_stretches = (uint32_t)(c->h_scalars[3] & 0xFFFFFFFFu);
-    if (seg == nullptr)  // one wave per non-empty contig
+    if (seg == nullptr && !idle)  // one wave per non-empty contig
         for (uint32_t k = 0; k < n_contigs; ++k) local.sweep_stretches += lengths[k] != 0 ? 1u : 0u;
     local.ms_prepare = elapsed(c->ev[EV_BEGIN], c->ev[EV_PREP]);
     local.ms_scan = elapsed(c->ev[EV_PREP], c->ev[EV_SCAN]);
@@ -232,8 +239,50 @@ int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_start
     local.ms_mark = elapsed(c->ev[EV_SWEEP], c->ev[EV_MARK]);
     local.ms_total = elapsed(c->ev[EV_BEGIN], c->ev[EV_MARK]);
     local.arena_grown_mid_solve = c->grew_mid_solve;
-    pf.ms_profile += elapsed(ev_pf.a, ev_pf.b);
+    nd.ms += elapsed(ev_pf.a, ev_pf.b);
+    if (swept_out) *swept_out = !idle;
     if (st_out) *st_out = local;
+    return QMCP_OK;
+}
+
+// a profile's need[]: the batch's regions (pf_tab: starts | ends | caps) through k_profile_need
+struct ProfileNeed : CappedNeed {
+    ProfileRun& pf;
+    uint32_t n_reg;
+    ProfileNeed(ProfileRun& run, uint32_t regions) : pf(run), n_reg(regions) {}
+    const char* name() const override { return "k_profile_need"; }
+    DevBuf& need_buf(qmcp_hip_ctx* c) override { return c->pf_need; }
+    int reserve(qmcp_hip_ctx* c) override { return ensure(c, c->pf_tab, 3 * (size_t)n_reg * sizeof(uint32_t) + 16); }
+    int upload(qmcp_hip_ctx* c, hipStream_t st) override {
+        uint32_t* d_rs = (uint32_t*)c->pf_tab.p;
+        if (n_reg) {
+            HIP_TRY(hipMemcpyAsync(d_rs, pf.gs.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_rs + n_reg, pf.ge.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_rs + 2 * (size_t)n_reg, pf.gcap.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
+        }
+        return QMCP_OK;
+    }
+    void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
+        const uint32_t* d_rs = (const uint32_t*)c->pf_tab.p;
+        qmcp::launch_profile_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, d_rs, d_rs + n_reg,
+                                  d_rs + 2 * (size_t)n_reg, n_reg, pf.default_cap, need, (unsigned long long*)c->pf_stat.p);
+    }
+};
+
+int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
+                        const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
+                        qmcp_hip_stats* st_out) {
+    const qmcp::CapTable& tab = *pf.tab;
+    const uint32_t* lengths = lengths_all + first_contig;
+    const uint32_t r0 = tab.offs[first_contig], r1 = tab.offs[first_contig + n_contigs];
+    uint32_t max_cap = pf.default_cap;
+    for (uint32_t k = r0; k < r1; ++k) max_cap = std::max(max_cap, tab.cap[k]);
+    if (r0 == r1 && max_cap != 0)
+        return solve_on_device(c, d_starts, d_ends, roff, lengths, n_contigs, n64, pf.default_cap, d_mask, st_out);
+    qmcp::batch_cap_table(tab, lengths_all, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
+    ProfileNeed nd(pf, r1 - r0);
+    TRY(capped_solve_batch(c, nd, max_cap, d_starts, d_ends, roff, lengths, n_contigs, n64, d_mask, st_out));
+    pf.ms_profile += nd.ms;
     return QMCP_OK;
 }
 

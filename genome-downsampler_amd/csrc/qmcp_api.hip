@@ -32,6 +32,7 @@
 #include "amplicon_table.h"
 #include "target_table.h"
 #include "cap_table.h"
+#include "pair_plan.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
@@ -61,6 +62,8 @@
 //                       by-contig solve; duplicate mask, family-size histogram and statistics from the device
 //   profile             one cap per region (a piecewise-constant cap along every contig): the cap table, and a batch's
 //                       solve on the sort-based mixed route with need(p) = min(cov(p), cap(p)) built on the device
+//   pairs               pair-aware downsampling: the by-contig solve at a first target, then stages over all batches that
+//                       credit the depth of the pairs already kept and top up among the other reads on the capped route
 #include "api/context.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
@@ -79,3 +82,4 @@
 #include "api/stratified.inc.hip"
 #include "api/dedup.inc.hip"
 #include "api/profile.inc.hip"
+#include "api/pairs.inc.hip"

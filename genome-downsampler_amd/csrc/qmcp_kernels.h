@@ -411,5 +411,22 @@ void launch_dd_compact(hipStream_t st, const uint32_t* starts, const uint32_t* e
                        const uint64_t* surv, const uint32_t* word_base, uint32_t n, uint32_t* starts_c, uint32_t* ends_c,
                        uint32_t* ids_c, uint32_t* orig);
 
+// pair-aware downsampling (kernels/pairs.inc.hip; api/pairs.inc.hip drives them), one batch of the by-contig grouping and
+// one stage after the first: the input-order mask of the kept set S as bits in the batch's grouped order (in_bits) and
+// its complement inside the batch (rest_bits: the stage's candidates), ceil(n / 64) words each; the events of the batch's
+// reads in S on its concatenated axis (ev: pair_credit_pad() + positions + 1 zeroed words; starts / ends: the batch's
+// gathered columns; pos_off: the batch-local position offset of each of its contigs) -- launch_exclusive_scan over the
+// whole buffer, in place, leaves credit[p] at ev[pair_credit_pad() + p]; need[p] = min(cov_rest(p), max(0, target -
+// credit[p])) with launch_profile_need's cut bit and counters; and *count += the set bits of a mask
+uint32_t pair_credit_pad();
+void launch_pair_gather_mask(hipStream_t st, const void* sorted, uint32_t n, const uint64_t* mask, uint64_t* in_bits,
+                             uint64_t* rest_bits);
+void launch_pair_credit_events(hipStream_t st, const void* sorted, uint32_t n, const uint64_t* in_bits,
+                               const uint32_t* starts, const uint32_t* ends, const uint32_t* pos_off, uint32_t first_contig,
+                               uint32_t* ev);
+void launch_pair_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, const uint32_t* credit, uint32_t ltot,
+                      uint32_t target, uint32_t* need, unsigned long long* pstat);
+void launch_pair_count_bits(hipStream_t st, const uint64_t* mask, uint32_t n_words, unsigned long long* count);
+
 }  // namespace qmcp
 #endif

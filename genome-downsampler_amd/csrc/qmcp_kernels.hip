@@ -48,6 +48,8 @@
 //                            flags, cell ids, survivor / duplicate bits, family statistics, compaction of the survivors
 //   profile                  a cap that varies along the genome: need(p) = min(cov(p), cap(p)) per position with its cut
 //                            flag, the cut-point scan over it, and the launchers of the capped mixed-span sweeps
+//   pairs                    pair-aware downsampling: the kept set's bits in a batch's grouped order and their complement,
+//                            the kept reads' depth as scanned events, need(p) = min(cov_rest(p), T - credit(p))
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -88,5 +90,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/stratified.inc.hip"
 #include "kernels/dedup.inc.hip"
 #include "kernels/profile.inc.hip"
+#include "kernels/pairs.inc.hip"
 
 }  // namespace qmcp

@@ -77,6 +77,14 @@ struct BamApiConfig {
     // the reads' strata column for it.  Needs per_reference; not together with targets, a depth report, a coverage
     // ladder, stratify_by or amplicon files (std::invalid_argument otherwise).  false: nothing changes.
     bool dedup = false;
+    // Pair-aware downsampling: the solve runs in stages that credit the coverage of the mates already kept
+    // (QuasiMcpHipSolver::solve_pairs / qmcp_hip_solve_pairs_host), so the output -- whole pairs, written without a
+    // further find_pairs -- stays near max_coverage instead of near twice that.  pair_stages: the stages' rising targets,
+    // the last one max_coverage; empty: ceil(M / 2), then M.  Needs per_reference; not together with targets, a depth
+    // report or track, a coverage ladder, stratify_by, dedup or amplicon files (std::invalid_argument otherwise).
+    // false: nothing changes.
+    bool pair_aware = false;
+    std::vector<std::uint32_t> pair_stages;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -119,6 +127,9 @@ class BamApi {
     Stratify stratify_by() const { return stratify_by_; }
     // BamApiConfig::dedup (the reads' strata column then holds the reverse-strand bit)
     bool dedup() const { return dedup_; }
+    // BamApiConfig::pair_aware and pair_stages (empty: the default schedule)
+    bool pair_aware() const { return pair_aware_; }
+    const std::vector<std::uint32_t>& pair_stages() const { return pair_stages_; }
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -152,6 +163,8 @@ class BamApi {
     std::vector<std::uint32_t> coverage_ladder_;
     Stratify stratify_by_ = Stratify::NONE;
     bool dedup_ = false;
+    bool pair_aware_ = false;
+    std::vector<std::uint32_t> pair_stages_;
     void read_bam_into(PairedReads& reads);
 };
 

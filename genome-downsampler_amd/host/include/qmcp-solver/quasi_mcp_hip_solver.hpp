@@ -104,6 +104,12 @@ class QuasiMcpHipSolver : public Solver {
                                             const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
                                             const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps);
     const qmcp_hip_profile_stats& last_profile_stats() const { return pstats_; }
+    // Pair-aware downsampling for the reads of a BamApi built with BamApiConfig::pair_aware: qmcp_hip_solve_pairs_host
+    // under its pair_stages (empty: the default schedule).  The Solution holds whole pairs already -- the caller writes it
+    // without find_pairs.  std::invalid_argument for reads without contig ids, an odd number of reads and a refused
+    // stage list (the library's message)
+    std::unique_ptr<Solution> solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_pair_stats& last_pair_stats() const { return prstats_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -127,6 +133,7 @@ class QuasiMcpHipSolver : public Solver {
     std::vector<qmcp_hip_stratum_row> stratum_rows_;
     qmcp_hip_dedup_stats dstats_{};
     qmcp_hip_profile_stats pstats_{};
+    qmcp_hip_pair_stats prstats_{};
     std::vector<std::uint64_t> dedup_hist_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves

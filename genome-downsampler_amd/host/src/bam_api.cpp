@@ -110,6 +110,27 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
             throw std::invalid_argument("duplicate-aware downsampling does not take amplicon files");
         dedup_ = true;
     }
+    if (config.pair_aware) {
+        if (!per_reference_)
+            throw std::invalid_argument("pair-aware downsampling needs per_reference: its stages are solved one "
+                                        "reference at a time");
+        if (!config.targets_filepath.empty()) throw std::invalid_argument("pair-aware downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("pair-aware downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("pair-aware downsampling does not take a depth report");
+        if (!config.depth_track_filepath.empty())
+            throw std::invalid_argument("pair-aware downsampling does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("pair-aware downsampling does not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("pair-aware downsampling does not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("pair-aware downsampling does not take amplicon files");
+        pair_aware_ = true;
+        pair_stages_ = config.pair_stages;
+    } else if (!config.pair_stages.empty()) {
+        throw std::invalid_argument("pair_stages need pair_aware");
+    }
     if (!config.depth_report_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a depth report needs per_reference: its rows are the references a per-reference "

@@ -1013,6 +1013,57 @@ std::int64_t qmcp_host_downsample_bam_profile(const char* solver_name, const cha
     }
 }
 
+// The file-to-file flow with BamApiConfig::pair_aware: one per-reference ingest, one qmcp_hip_solve_pairs_host call
+// (QuasiMcpHipSolver::solve_pairs) under `stages` (NULL or n_stages == 0: the default schedule), write_paired_reads from
+// its mask -- whole pairs already, so NO find_pairs.  targets / report / track / ladder_levels / stratify / dedup / bed /
+// tsv / amplicons_by_reference are handed to BamApiConfig as given so that it refuses the combinations it refuses; a
+// coverage profile (profile != 0) and a solver that grades by quality are refused here.  Returns the number of records
+// written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the configuration is refused.
+std::int64_t qmcp_host_downsample_bam_pairs(const char* solver_name, const char* in_path, const char* out_path,
+                                            const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                            std::uint32_t min_mapq, int per_reference, const std::uint32_t* stages,
+                                            std::uint32_t n_stages, const char* targets, const char* report,
+                                            const char* track, const std::uint32_t* ladder_levels,
+                                            std::uint32_t n_ladder_levels, const char* stratify, int dedup, int profile,
+                                            const char* bed, const char* tsv, int amplicons_by_reference, char* err,
+                                            std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.pair_aware = true;
+        if (stages != nullptr && n_stages) cfg.pair_stages.assign(stages, stages + n_stages);
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (track && track[0]) cfg.depth_track_filepath = track;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
+        cfg.dedup = dedup != 0;
+        if (bed && bed[0]) cfg.bed_filepath = bed;
+        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        if (profile) throw std::invalid_argument("pair-aware downsampling does not go together with a coverage profile");
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("pair-aware downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no pair-aware downsampling");
+        bam_api::BamApi api(in_path, cfg);
+        std::unique_ptr<qmcp::Solution> solution = hip->solve_pairs(max_coverage, api);
+        std::vector<bam_api::ReadIndex> kept(solution->begin(), solution->end());
+        const std::uint32_t written = api.write_paired_reads(out_path, kept);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

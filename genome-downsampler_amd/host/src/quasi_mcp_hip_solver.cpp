@@ -257,6 +257,44 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t require
     return expand_kept(n, t0);
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.pair_aware() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("pair-aware downsampling needs a BamApi built with BamApiConfig::pair_aware");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    const std::vector<std::uint32_t>& stages = bam_api.pair_stages();
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    const int rc = qmcp_hip_solve_pairs_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                             reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                             required_cover, stages.empty() ? nullptr : stages.data(),
+                                             (std::uint32_t)stages.size(), mask.data(), &stats_, &prstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_pairs_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    // the context holds the last stage's completed mask
+    auto kept = std::make_unique<Solution>();
+    const std::uint64_t upper = prstats_.n_kept[prstats_.n_stages - 1];
+    kept->resize(upper);
+    std::uint64_t n_out = 0;
+    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
+    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
+    kept->resize(n_out);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return kept;
+}
+
 std::vector<std::unique_ptr<Solution>> QuasiMcpHipSolver::solve_ladder(std::uint32_t required_cover,
                                                                        bam_api::BamApi& bam_api,
                                                                        const std::vector<std::uint32_t>& levels) {

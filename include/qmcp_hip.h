@@ -844,6 +844,64 @@ int qmcp_hip_solve_dedup_device(qmcp_hip_ctx* ctx,
                                 uint32_t hist_bins, void* hip_stream, qmcp_hip_stats* stats,
                                 qmcp_hip_dedup_stats* dstats);
 
+/* Pair-aware downsampling: a staged solve that credits the mates' coverage.  Paired-end data solved read by read and
+ * then completed pair by pair keeps almost twice what was asked for: the solve returns a minimum set for min(cov, M) and
+ * never learns that a mate comes along with nearly every read it keeps.  Here the solve sees the mates: it solves for a
+ * part of the target, completes the pairs, and tops up only what is still missing.
+ * Input: reads, contig_ids (QMCP_NO_CONTIG = unplaced), contig_lengths / n_contigs and limits as in
+ * qmcp_hip_solve_by_contig_host, with n_reads even and pair q = reads (2q, 2q + 1).  stages: targets T_1 < T_2 < ... <
+ * T_k = max_coverage, 1 <= k <= QMCP_PAIR_MAX_STAGES, T_1 >= 1; stages == NULL (n_stages ignored) is the default
+ * {ceil(M / 2), M}, which is {1} for M = 1.
+ * Stages: S_0 is empty.  For stage j, credit_j(p) is the depth of the placed reads of S_(j-1) at p and cap_j(p) =
+ * max(0, T_j - credit_j(p)); K_j is the canonical selection of qmcp_hip_solve_profile_host -- per contig, leftmost deficit
+ * first, then furthest end, furthest start, lowest index -- taken over the placed reads NOT in S_(j-1), alone, in input
+ * order, with need(p) = min(cov_rest(p), cap_j(p)); S_j = complete_pairs(S_(j-1) | K_j).  The result is S_k, a keep mask
+ * in INPUT order that holds whole pairs.
+ * An unplaced read is never a candidate and gives no credit: it enters only as the mate of a kept read.  Mates on
+ * different contigs are fine.
+ * Why S_k is valid: with cov = credit + cov_rest, min(cov_rest, max(0, T - credit)) = max(0, min(cov, T) - credit)
+ * (check cov >= T and cov < T), so after stage j the depth of S_j is at least min(cov, T_j) everywhere; completion only
+ * adds reads; at j = k this is the plain solve's invariant at max_coverage.
+ * Stage 1 has no credit: it IS qmcp_hip_solve_by_contig_* at T_1, with every route that call takes, so k = 1 is bit for
+ * bit that call at max_coverage followed by qmcp_hip_complete_pairs_*.  Later stages take the capped mixed-span route of
+ * the coverage profile.
+ * Not claimed: that S_k is minimum among whole-pair solutions, or that more stages are always better.  The result is
+ * defined by the stages, as the ladder's is by its chain.
+ * Errors, all on the host before the context is looked at and before anything is copied or launched: an odd n_reads
+ * and a bad stage list (a count outside 1 .. QMCP_PAIR_MAX_STAGES, a target of 0, a list that does not rise strictly, a
+ * last target that is not max_coverage, max_coverage 0) fail with QMCP_EINVAL and a message naming the entry; a target
+ * or max_coverage of 2^31 or more with QMCP_ERANGE.  Bad ids and reads as in qmcp_hip_solve_by_contig_host.
+ * stats (may be NULL) are stage 1's; pstats (may be NULL): the stages.  The host entry leaves S_k in the context, for
+ * qmcp_hip_kept_indices_host.  The device entry takes the three columns and the mask in device memory (contig_lengths
+ * and stages stay on the host), is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after
+ * the work has completed. */
+#define QMCP_PAIR_MAX_STAGES 16
+typedef struct qmcp_hip_pair_stats {
+    uint32_t n_stages, reserved;
+    uint64_t n_selected[QMCP_PAIR_MAX_STAGES];        /* |K_j|                                                         */
+    uint64_t n_kept[QMCP_PAIR_MAX_STAGES];            /* |S_j|, after completion                                       */
+    uint64_t capped_positions[QMCP_PAIR_MAX_STAGES];  /* stages after the first: positions with cov_rest > cap_j ...   */
+    uint64_t demand[QMCP_PAIR_MAX_STAGES];            /* ... and the sum of need over the batches that had candidates  */
+    uint32_t target[QMCP_PAIR_MAX_STAGES];            /* T_j                                                           */
+    uint32_t sweeps[QMCP_PAIR_MAX_STAGES];            /* capped sweeps queued (one per batch that asked for a read;
+                                                         0 for stage 1, the plain solve)                               */
+    float ms_stage[QMCP_PAIR_MAX_STAGES];             /* device time of the stage's solves                             */
+    float ms_pairs;                                   /* everything the feature adds around the solves: mask gather,
+                                                         compaction, credit, need, mask expansion, completion, counts  */
+    uint32_t reserved2;
+} qmcp_hip_pair_stats;
+int qmcp_hip_solve_pairs_host(qmcp_hip_ctx* ctx,
+                              const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                              uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                              uint32_t max_coverage, const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                              uint64_t* keep_mask_out, qmcp_hip_stats* stats, qmcp_hip_pair_stats* pstats);
+int qmcp_hip_solve_pairs_device(qmcp_hip_ctx* ctx,
+                                const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                uint32_t max_coverage, const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                qmcp_hip_pair_stats* pstats);
+
 #ifdef __cplusplus
 }
 #endif
