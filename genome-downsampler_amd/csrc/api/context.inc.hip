@@ -203,7 +203,7 @@ struct KernelSpan {
     hipStream_t st;
     KernelSpan(qmcp_hip_ctx* ctx, const char* nm, hipStream_t stream = nullptr)
         : c(ctx), name(nm), st(stream ? stream : ctx->stream) {
-        if (!c->profiling) return;
+        if (!c->profiling || !nm) return;  // (no name: no span -- a helper whose caller brackets differently)
         if (c->profiling == 2 && std::strncmp(nm, "k_sweep", 7) != 0) return;
         a = pool_event(c);
         b = pool_event(c);

@@ -29,64 +29,31 @@ template <typename Build>
 int dedup_sort(qmcp_hip_ctx* c, uint32_t n, const qmcp::DedupSortPlan& plan, const char* what, Build build,
                DedupSorted& out) {
     hipStream_t st = c->stream;
-    const uint32_t n_tiles = qmcp::sort_tiles(n);
     uint32_t* hist = (uint32_t*)c->dd_hist.p;
     uint32_t* spine = (uint32_t*)c->dd_spine.p;
     out.form = plan.form;
     (void)what;
     if (plan.form == qmcp::DEDUP_SORT_REC32) {
         build(0u, 4u, (const uint32_t*)nullptr, c->dd_bare.p);
-        const void* recs_in = nullptr;
         int kin = 0;
-        for (uint32_t p = 0; p < plan.rounds[0].passes; ++p) {
-            const bool first = p == 0;
-            const int kout = first ? 0 : (kin ^ 1);
-            {
-                KernelSpan sp(c, "k_radix_hist_rec(dedup)");
-                qmcp::launch_radix_hist_rec(st, first, (const uint32_t*)c->dd_bare.p, recs_in, n, 8 * p, hist);
-            }
-            {
-                KernelSpan sp(c, "scan_radix_hist(dedup, 3 kernels)");
-                qmcp::launch_exclusive_scan(st, hist, 256u * n_tiles, hist, spine, false);
-            }
-            {
-                KernelSpan sp(c, "k_radix_scatter_rec(dedup)");
-                qmcp::launch_radix_scatter_rec(st, first, (const uint32_t*)c->dd_bare.p, recs_in, n, 8 * p, hist,
-                                               c->dd_keys[kout].p);
-            }
-            kin = kout;
-            recs_in = c->dd_keys[kin].p;
-        }
+        TRY(radix_sort_records(c, st, (const uint32_t*)c->dd_bare.p, n, plan.rounds[0].passes, hist, spine, c->dd_keys,
+                               {"k_radix_hist_rec(dedup)", "scan_radix_hist(dedup, 3 kernels)", "k_radix_scatter_rec(dedup)"},
+                               &kin));
         out.keys = c->dd_keys[kin].p;
         out.vals = (const uint32_t*)c->dd_keys[kin].p + 1;
         out.stride = 2;
         return QMCP_OK;
     }
-    int kin = 0;
-    bool have_vals = false;
+    // one u64 sort per round; a later round's keys are built in the order the rounds before it left (the value column)
+    WideBufs wb;
     for (uint32_t r = 0; r < plan.n_rounds; ++r) {
-        build(r, 8u, have_vals ? (const uint32_t*)c->dd_vals[kin].p : (const uint32_t*)nullptr, c->dd_keys[kin].p);
-        for (uint32_t p = 0; p < plan.rounds[r].passes; ++p) {
-            const int kout = kin ^ 1;
-            {
-                KernelSpan sp(c, "k_radix_hist(dedup, u64)");
-                qmcp::launch_radix_hist(st, true, c->dd_keys[kin].p, n, 8 * p, hist);
-            }
-            {
-                KernelSpan sp(c, "scan_radix_hist(dedup, 3 kernels)");
-                qmcp::launch_exclusive_scan(st, hist, 256u * n_tiles, hist, spine, false);
-            }
-            {
-                KernelSpan sp(c, "k_radix_scatter(dedup, u64)");
-                qmcp::launch_radix_scatter(st, true, c->dd_keys[kin].p, have_vals ? (const uint32_t*)c->dd_vals[kin].p : nullptr,
-                                           n, 8 * p, hist, c->dd_keys[kout].p, (uint32_t*)c->dd_vals[kout].p);
-            }
-            have_vals = true;
-            kin = kout;
-        }
+        build(r, 8u, wb.v < 0 ? (const uint32_t*)nullptr : (const uint32_t*)c->dd_vals[wb.v].p, c->dd_keys[wb.k].p);
+        TRY(radix_sort_wide(c, st, n, plan.rounds[r].passes, hist, spine, c->dd_keys, c->dd_vals,
+                            {"k_radix_hist(dedup, u64)", "scan_radix_hist(dedup, 3 kernels)", "k_radix_scatter(dedup, u64)"},
+                            &wb));
     }
-    out.keys = c->dd_keys[kin].p;
-    out.vals = (const uint32_t*)c->dd_vals[kin].p;
+    out.keys = c->dd_keys[wb.k].p;
+    out.vals = (const uint32_t*)c->dd_vals[wb.v].p;
     out.stride = 1;
     return QMCP_OK;
 }

@@ -108,12 +108,11 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             const uint32_t words = (nb + 63u) / 64u;
             const size_t tab = (size_t)bt.n_contigs + 1;
             const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
-            roff.assign(tab, 0);
+            batch_roff(offs.data() + bt.first_contig, bt.n_contigs, roff);
             offs32.assign(tab, 0);
             poff32.assign(tab, 0);
             ranks.assign(tab, 0);
             for (uint32_t k = 0; k <= bt.n_contigs; ++k) {
-                roff[k] = offs[bt.first_contig + k] - offs[bt.first_contig];
                 offs32[k] = (uint32_t)roff[k];  // (a batch holds at most 2^30 reads)
                 if (k) poff32[k] = poff32[k - 1] + lengths[bt.first_contig + k - 1];  // (and at most 2^31 - 2 positions)
             }

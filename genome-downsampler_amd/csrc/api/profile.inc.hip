@@ -120,36 +120,16 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     const uint32_t passes = (pos_bits + span_bits + 7) / 8;
     local.sort_passes = passes;
     int kin = 0, vin = 0;
+    const RadixNames radix_names = {"radix pass (hist, scan, scatter)"};
     if (!wide) {
-        const uint32_t* d_key32 = (const uint32_t*)c->vals[0].p;
-        const void* recs_in = nullptr;
-        for (uint32_t p = 0; p < passes; ++p) {
-            const bool first = p == 0;
-            const int kout = first ? 0 : (kin ^ 1);
-            KernelSpan sp(c, "radix pass (hist, scan, scatter)");
-            qmcp::launch_radix_hist_rec(st, first, d_key32, recs_in, n, 8 * p, (uint32_t*)c->hist.p);
-            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->hist.p, 256u * n_tiles, (uint32_t*)c->hist.p,
-                                        (uint32_t*)c->spine.p, false);
-            qmcp::launch_radix_scatter_rec(st, first, d_key32, recs_in, n, 8 * p, (const uint32_t*)c->hist.p, c->keys[kout].p);
-            kin = kout;
-            recs_in = c->keys[kin].p;
-        }
+        TRY(radix_sort_records(c, st, (const uint32_t*)c->vals[0].p, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p,
+                               c->keys, radix_names, &kin));
     } else {
-        const uint32_t* vals_in = nullptr;
-        for (uint32_t p = 0; p < passes; ++p) {
-            const int kout = kin ^ 1, vout = (vals_in == nullptr) ? 0 : (vin ^ 1);
-            KernelSpan sp(c, "radix pass (hist, scan, scatter)");
-            qmcp::launch_radix_hist(st, true, c->keys[kin].p, n, 8 * p, (uint32_t*)c->hist.p);
-            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->hist.p, 256u * n_tiles, (uint32_t*)c->hist.p,
-                                        (uint32_t*)c->spine.p, false);
-            qmcp::launch_radix_scatter(st, true, c->keys[kin].p, vals_in, n, 8 * p, (const uint32_t*)c->hist.p, c->keys[kout].p,
-                                       (uint32_t*)c->vals[vout].p);
-            kin = kout;
-            vin = vout;
-            vals_in = (const uint32_t*)c->vals[vin].p;
-        }
+        WideBufs wb;
+        TRY(radix_sort_wide(c, st, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, c->keys, c->vals, radix_names, &wb));
+        kin = wb.k;
+        vin = wb.v;
     }
-    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(c->boff.p, 0xFF, ((size_t)ltot + 1) * sizeof(uint32_t), st));
     {
         KernelSpan sp(c, "k_bucket_heads");

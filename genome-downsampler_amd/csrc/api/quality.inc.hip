@@ -125,56 +125,22 @@ int quality_pass(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         const void* sorted = nullptr;
         const uint32_t* svals = nullptr;
         if (!wide) {
-            const void* recs_in = nullptr;
             int kin = 0;
-            for (uint32_t p = 0; p < passes; ++p) {
-                const bool first = p == 0;
-                const int kout = first ? 0 : (kin ^ 1);
-                {
-                    KernelSpan sp(c, "k_radix_hist_rec(quality)");
-                    qmcp::launch_radix_hist_rec(st, first, (const uint32_t*)c->qc_bare.p, recs_in, n, 8 * p,
-                                                (uint32_t*)c->qc_hist.p);
-                }
-                {
-                    KernelSpan sp(c, "scan_radix_hist(quality, 3 kernels)");
-                    qmcp::launch_exclusive_scan(st, (const uint32_t*)c->qc_hist.p, 256u * n_tiles,
-                                                (uint32_t*)c->qc_hist.p, (uint32_t*)c->qc_spine.p, false);
-                }
-                {
-                    KernelSpan sp(c, "k_radix_scatter_rec(quality)");
-                    qmcp::launch_radix_scatter_rec(st, first, (const uint32_t*)c->qc_bare.p, recs_in, n, 8 * p,
-                                                   (const uint32_t*)c->qc_hist.p, c->qc_keys[kout].p);
-                }
-                kin = kout;
-                recs_in = c->qc_keys[kin].p;
-            }
+            TRY(radix_sort_records(c, st, (const uint32_t*)c->qc_bare.p, n, passes, (uint32_t*)c->qc_hist.p,
+                                   (uint32_t*)c->qc_spine.p, c->qc_keys,
+                                   {"k_radix_hist_rec(quality)", "scan_radix_hist(quality, 3 kernels)",
+                                    "k_radix_scatter_rec(quality)"},
+                                   &kin));
             sorted = c->qc_keys[kin].p;
         } else {
-            int kin = 0;
-            for (uint32_t p = 0; p < passes; ++p) {
-                const int kout = kin ^ 1;
-                {
-                    KernelSpan sp(c, "k_radix_hist(quality, u64)");
-                    qmcp::launch_radix_hist(st, true, c->qc_keys[kin].p, n, 8 * p, (uint32_t*)c->qc_hist.p);
-                }
-                {
-                    KernelSpan sp(c, "scan_radix_hist(quality, 3 kernels)");
-                    qmcp::launch_exclusive_scan(st, (const uint32_t*)c->qc_hist.p, 256u * n_tiles,
-                                                (uint32_t*)c->qc_hist.p, (uint32_t*)c->qc_spine.p, false);
-                }
-                {
-                    KernelSpan sp(c, "k_radix_scatter(quality, u64)");
-                    qmcp::launch_radix_scatter(st, true, c->qc_keys[kin].p,
-                                               p == 0 ? nullptr : (const uint32_t*)c->qc_vals[kin].p, n, 8 * p,
-                                               (const uint32_t*)c->qc_hist.p, c->qc_keys[kout].p,
-                                               (uint32_t*)c->qc_vals[kout].p);
-                }
-                kin = kout;
-            }
-            sorted = c->qc_keys[kin].p;
-            svals = (const uint32_t*)c->qc_vals[kin].p;
+            WideBufs wb;
+            TRY(radix_sort_wide(c, st, n, passes, (uint32_t*)c->qc_hist.p, (uint32_t*)c->qc_spine.p, c->qc_keys, c->qc_vals,
+                                {"k_radix_hist(quality, u64)", "scan_radix_hist(quality, 3 kernels)",
+                                 "k_radix_scatter(quality, u64)"},
+                                &wb));
+            sorted = c->qc_keys[wb.k].p;
+            svals = (const uint32_t*)c->qc_vals[wb.v].p;
         }
-        HIP_TRY(hipGetLastError());
         // 4: segments and the choice
         uint32_t* kb = (uint32_t*)c->qc_kb.p;
         uint32_t* seg_end = (uint32_t*)c->qc_end.p;

@@ -140,61 +140,21 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     const uint32_t key_bits = pos_bits + span_bits;
     const uint32_t passes = (key_bits + 7) / 8;
     local.sort_passes = ranked ? 1u : passes;  // ranked path: one range partition, no sort
-    const uint32_t n_tiles = qmcp::sort_tiles(n);
     int kin = 0, vin = 0;  // buffers holding the sorted output at the end
     if (!ranked && uniform) need_gstart();  // the sort-based routes bucket the bare keys
     if (ranked) {
         // keep mask already written by k_rank_mark
     } else if (!wide) {
         // records {key, read index}: keys[0] <-> keys[1]; the first pass reads bare keys
-        const void* recs_in = nullptr;
-        for (uint32_t p = 0; p < passes; ++p) {
-            const bool first = p == 0;
-            const int kout = first ? 0 : (kin ^ 1);
-            {
-                KernelSpan sp(c, "k_radix_hist_rec");
-                qmcp::launch_radix_hist_rec(c->stream, first, d_key32, recs_in, n, 8 * p,
-                                            (uint32_t*)c->hist.p);
-            }
-            {
-                KernelSpan sp(c, "scan_radix_hist(3 kernels)");
-                qmcp::launch_exclusive_scan(c->stream, (const uint32_t*)c->hist.p, 256u * n_tiles,
-                                            (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, false);
-            }
-            {
-                KernelSpan sp(c, "k_radix_scatter_rec");
-                qmcp::launch_radix_scatter_rec(c->stream, first, d_key32, recs_in, n, 8 * p,
-                                               (const uint32_t*)c->hist.p, c->keys[kout].p);
-            }
-            HIP_TRY(hipGetLastError());
-            kin = kout;
-            recs_in = c->keys[kin].p;
-        }
+        TRY(radix_sort_records(c, c->stream, d_key32, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, c->keys,
+                               {"k_radix_hist_rec", "scan_radix_hist(3 kernels)", "k_radix_scatter_rec"}, &kin));
     } else {
         // 64-bit composite keys (huge genome x wide span range): split key / payload arrays
-        const uint32_t* vals_in = nullptr;
-        for (uint32_t p = 0; p < passes; ++p) {
-            const int kout = kin ^ 1, vout = (vals_in == nullptr) ? 0 : (vin ^ 1);
-            {
-                KernelSpan sp(c, "k_radix_hist");
-                qmcp::launch_radix_hist(c->stream, true, c->keys[kin].p, n, 8 * p, (uint32_t*)c->hist.p);
-            }
-            {
-                KernelSpan sp(c, "scan_radix_hist(3 kernels)");
-                qmcp::launch_exclusive_scan(c->stream, (const uint32_t*)c->hist.p, 256u * n_tiles,
-                                            (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, false);
-            }
-            {
-                KernelSpan sp(c, "k_radix_scatter");
-                qmcp::launch_radix_scatter(c->stream, true, c->keys[kin].p, vals_in, n, 8 * p,
-                                           (const uint32_t*)c->hist.p, c->keys[kout].p,
-                                           (uint32_t*)c->vals[vout].p);
-            }
-            HIP_TRY(hipGetLastError());
-            kin = kout;
-            vin = vout;
-            vals_in = (const uint32_t*)c->vals[vin].p;
-        }
+        WideBufs wb;
+        TRY(radix_sort_wide(c, c->stream, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, c->keys, c->vals,
+                            {"k_radix_hist", "scan_radix_hist(3 kernels)", "k_radix_scatter"}, &wb));
+        kin = wb.k;
+        vin = wb.v;
     }
     // bucket offsets straight from the sorted keys (no atomics)
     if (!sweep_done) {

@@ -2,13 +2,11 @@
 // qmcp_hip_solve_stratified_host / _device: reads of several contigs AND several strata (strand, read group, sample)
 // in any order, one coverage cap per stratum.  The mask is the OR over the strata of the by-contig solve of that
 // stratum's reads alone at its cap.
-//   1. k_st_keys checks every read against its contig, checks its stratum id, and writes the stratum-major sort key
-//      stratum * n_contigs + contig (n_strata * n_contigs for a read without contig or stratum)
-//   2. the stable LSD record radix groups {key, read index} by key, one pass per 8 bits of n_strata * n_contigs, into
-//      the by-contig record buffers; k_bc_bounds turns the grouped keys into each (stratum, contig)'s run
+//   1, 2. group_reads (api/by_contig.inc.hip) around k_st_keys, which checks every read against its contig, checks its
+//      stratum id, and writes the stratum-major sort key stratum * n_contigs + contig (n_strata * n_contigs for a read
+//      without contig or stratum): one radix pass per 8 bits of n_strata * n_contigs, each (stratum, contig)'s run
 //   3. stratified_plan.h cuts every stratum that has a cap and reads into batches (by_contig_plan.h's packing, one
-//      stratum at a time); per batch the by-contig gather, the ordinary solve at the stratum's cap, and the scatter of
-//      its mask into input order
+//      stratum at a time); per batch solve_gathered_batch at the stratum's cap
 //   4. k_st_tally reduces the grouped records against the final mask into one row per stratum; n_strata x 32 bytes
 //      come back
 // Buffers: the grouping and the batches live in the by-contig solve's buffers (bc_*), which nothing else uses while
@@ -35,68 +33,26 @@ int solve_stratified_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
                                const uint32_t* caps, uint32_t n_strata, uint64_t* d_mask, qmcp_hip_stratum_row* rows_out,
                                qmcp_hip_stats* stats) {
     const uint32_t n = (uint32_t)n64;
-    const size_t words = (size_t)((n64 + 63) / 64);
     const uint32_t n_pairs = n_strata * n_contigs;  // the (stratum, contig) groups, <= 2^24
     const uint32_t n_groups = n_pairs + 1;          // ... then the reads without contig or stratum
-    const uint32_t n_tiles = qmcp::sort_tiles(n);
     hipStream_t st = c->stream;
-    TRY(ensure(c, c->bc_len, (size_t)n_contigs * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_offs, ((size_t)n_groups + 1) * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_err, 16));
-    TRY(ensure(c, c->bc_key, (size_t)n * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_rec[0], (size_t)n * 2 * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_rec[1], (size_t)n * 2 * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_hist, (size_t)256 * n_tiles * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_spine, (size_t)qmcp::scan_spine_entries(256u * n_tiles) * sizeof(uint32_t) + 16));
     TRY(ensure(c, c->st_rows, (size_t)n_strata * sizeof(qmcp_hip_stratum_row)));
-    if (words) HIP_TRY(hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), st));
-    HIP_TRY(hipMemsetAsync(c->bc_err.p, 0, sizeof(uint32_t), st));
-    HIP_TRY(hipMemcpyAsync(c->bc_len.p, lengths, (size_t)n_contigs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
 
     // 1, 2: keys, grouping, bounds
-    {
-        KernelSpan sp(c, "k_st_keys");
-        qmcp::launch_st_keys(st, d_starts, d_ends, d_ids, d_strata, n, (const uint32_t*)c->bc_len.p, n_contigs, n_strata,
-                             (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
-    }
     const uint32_t passes = std::max(1u, (bit_width(n_pairs) + 7) / 8);  // keys go up to n_pairs
-    const void* sorted = c->bc_rec[0].p;
-    if (n) {
-        const void* recs_in = nullptr;
-        int kin = 0;
-        for (uint32_t p = 0; p < passes; ++p) {
-            const bool first = p == 0;
-            const int kout = first ? 0 : (kin ^ 1);
-            {
-                KernelSpan sp(c, "k_radix_hist_rec(stratified)");
-                qmcp::launch_radix_hist_rec(st, first, (const uint32_t*)c->bc_key.p, recs_in, n, 8 * p,
-                                            (uint32_t*)c->bc_hist.p);
-            }
-            {
-                KernelSpan sp(c, "scan_radix_hist(stratified, 3 kernels)");
-                qmcp::launch_exclusive_scan(st, (const uint32_t*)c->bc_hist.p, 256u * n_tiles, (uint32_t*)c->bc_hist.p,
-                                            (uint32_t*)c->bc_spine.p, false);
-            }
-            {
-                KernelSpan sp(c, "k_radix_scatter_rec(stratified)");
-                qmcp::launch_radix_scatter_rec(st, first, (const uint32_t*)c->bc_key.p, recs_in, n, 8 * p,
-                                               (const uint32_t*)c->bc_hist.p, c->bc_rec[kout].p);
-            }
-            kin = kout;
-            recs_in = c->bc_rec[kin].p;
-        }
-        sorted = c->bc_rec[kin].p;
-    }
-    {
-        KernelSpan sp(c, "k_bc_bounds(stratified)");
-        qmcp::launch_bc_bounds(st, sorted, n, n_groups, (uint32_t*)c->bc_offs.p);
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> offs((size_t)n_groups + 1);
+    std::vector<uint32_t> offs;
+    const void* sorted = nullptr;
     uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(offs.data(), c->bc_offs.p, offs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&err, c->bc_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(group_reads(
+        c, n64, lengths, n_contigs, n_groups, passes,
+        {{"k_radix_hist_rec(stratified)", "scan_radix_hist(stratified, 3 kernels)", "k_radix_scatter_rec(stratified)"},
+         "k_bc_bounds(stratified)"},
+        [&] {
+            KernelSpan sp(c, "k_st_keys");
+            qmcp::launch_st_keys(st, d_starts, d_ends, d_ids, d_strata, n, (const uint32_t*)c->bc_len.p, n_contigs, n_strata,
+                                 (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
+        },
+        d_mask, offs, &sorted, &err));
     if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
     if (err & 4u) return fail(QMCP_EINVAL, "a stratum id is neither < n_strata (%u) nor QMCP_NO_STRATUM", n_strata);
     if (err & 2u) return fail(QMCP_EREAD, "a read has start > end or end >= its contig's length");
@@ -115,15 +71,7 @@ int solve_stratified_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
                     bad_s, bad_c, (unsigned long long)counts[(size_t)bad_s * n_contigs + bad_c], lengths[bad_c]);
     if (prc != QMCP_OK) return fail(prc, "the stratified plan refused its tables");
     size_t largest = 0;
-    uint64_t most = 0;
-    for (size_t b = 0; b < batches.size(); ++b)
-        if (batches[b].n_reads > most) {
-            most = batches[b].n_reads;
-            largest = b;
-        }
-    TRY(ensure(c, c->bc_starts, (size_t)most * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_ends, (size_t)most * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_mask, (size_t)((most + 63) / 64) * sizeof(uint64_t)));
+    TRY(reserve_batch_buffers(c, batches, &largest));
     qmcp_hip_stats sum;
     std::memset(&sum, 0, sizeof(sum));
     bool first = true;
@@ -133,26 +81,10 @@ int solve_stratified_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
         sum.n_contigs += bt.n_contigs;
         sum.total_length += bt.positions;
         if (bt.n_reads == 0) continue;  // (contigs the stratum has no reads on keep nothing)
-        const uint32_t nb = (uint32_t)bt.n_reads;
         const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
-        {
-            KernelSpan sp(c, "k_bc_gather");
-            qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
-        }
-        HIP_TRY(hipGetLastError());
-        const uint32_t* goffs = offs.data() + (size_t)bt.stratum * n_contigs + bt.first_contig;
-        roff.assign((size_t)bt.n_contigs + 1, 0);
-        for (uint32_t k = 0; k <= bt.n_contigs; ++k) roff[k] = goffs[k] - goffs[0];
-        qmcp_hip_stats bs;
-        std::memset(&bs, 0, sizeof(bs));
-        TRY(solve_on_device(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, roff.data(),
-                            lengths + bt.first_contig, bt.n_contigs, nb, bt.M, (uint64_t*)c->bc_mask.p, &bs));
-        {
-            KernelSpan sp(c, "k_bc_scatter_mask");
-            qmcp::launch_bc_scatter_mask(st, (const uint64_t*)c->bc_mask.p, bsorted, nb, d_mask);
-        }
-        HIP_TRY(hipGetLastError());
-        add_batch_stats(sum, bs, first, b == largest);
+        TRY(solve_gathered_batch(c, bsorted, (uint32_t)bt.n_reads, d_starts, d_ends,
+                                 offs.data() + (size_t)bt.stratum * n_contigs + bt.first_contig, lengths, bt.first_contig,
+                                 bt.n_contigs, bt.M, nullptr, d_mask, roff, sum, first, b == largest));
         first = false;
     }
     sum.n_reads = n_placed;  // (strata without a cap are not solved, yet their reads are part of the call)

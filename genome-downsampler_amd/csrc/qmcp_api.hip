@@ -36,6 +36,7 @@
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
+//   radix_passes        the stable LSD radix sort's passes (records form, wide u64 form): the one loop every sorting entry queues
 //   uniform_sweep       which one-length sweep a call takes and its launches (pipelines, event-driven form, stretches,
 //                       speculative tiers)
 //   near_uniform_sizes  the near-uniform route's sizes, round budget and buffers
@@ -65,6 +66,7 @@
 //   pairs               pair-aware downsampling: the by-contig solve at a first target, then stages over all batches that
 //                       credit the depth of the pairs already kept and top up among the other reads on the capped route
 #include "api/context.inc.hip"
+#include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
 #include "api/solve_head.inc.hip"
