@@ -68,9 +68,8 @@ struct qmcp_hip_ctx {
     DevBuf in_starts, in_ends, in_aux0, in_aux1, mask, cov, amp, next_head;
     DevBuf f_starts, f_ends, f_map, f_words, f_mask;  // filter -> solve pipeline
     DevBuf ranges;     // range-ranked path: 257 range starts + heaviest load
-    DevBuf rankamb;    // range-ranked path: per-range lists of quota-crossing groups settled after the walk
-    // pass-major form (kernels/pass_major.inc.hip): one descriptor word per wave-slot; k_pm_descr's working words + the
-    // ranges' counts of quota-crossing groups
+    DevBuf rankamb;    // range-ranked path: per-range lists of quota-crossing groups, settled in the walk's tail
+    // pass-major form (kernels/pass_major.inc.hip): one descriptor word per wave-slot; the table stage's working words
     DevBuf pm_desc, pm_work;
     // near-uniform route (kernels/near_uniform.inc.hip): the dominant span of the last call that took it -- the next
     // call's head filters on it at once -- and the route's buffers
@@ -165,6 +164,7 @@ struct qmcp_hip_ctx {
     // the two halves of a solve's enqueue (enqueue_head / enqueue_tail) and what they share
     SolveRun run;
     uint32_t* h_head = nullptr;       // pinned landing zone of the read-back that picks the route (8 words)
+    uint32_t* h_stats_init = nullptr; // pinned, behind h_head: the statistics' initial values (8 words: ~0, then zeros)
     hipEvent_t ev_head = nullptr;     // the solve's head (prepare, partition, bucket offsets) has been queued up to here
     hipEvent_t ev_done = nullptr;     // everything of the solve has been queued up to here
     bool mixed_seen = false;          // a call took the mixed-span route: its arrays are sized up front from then on

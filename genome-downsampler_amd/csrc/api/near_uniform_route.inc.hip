@@ -55,7 +55,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         }
         // the head again, regular reads only (exceptions listed): producer, scan, range table, bucket offsets
         c->nu_ell = ell;
-        if (run.pm) TRY(queue_pm_head(c, st, ell));
+        if (run.pm) TRY(queue_pm_head(c, st, ell, true));
         else TRY(queue_rm_head(c, st, ell, true));
         uint32_t* d_max_load = (uint32_t*)c->ranges.p + 65540;
         HIP_TRY(hipMemcpyAsync(c->h_nu, d_max_load, sizeof(uint32_t), hipMemcpyDeviceToHost, st));

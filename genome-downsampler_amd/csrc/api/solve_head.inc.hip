@@ -1,7 +1,7 @@
 // solve_head.inc.hip -- part of qmcp_api.hip (one translation unit).
 // A solve's head: everything that depends only on the reads' start positions -- arena sizing, the producers of the range-ranked route (pass-major or range-major form), bucket offsets -- and the pass-major ranking.
 int queue_rm_head(qmcp_hip_ctx* c, hipStream_t s1, uint32_t filter, bool clear_mask);
-int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter);
+int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun);
 
 // The pass-major form of the range-ranked route (kernels/pass_major.inc.hip) pads every (range, pass) slice to whole
 // groups of 64 slots: it pays where slices are long -- a pass's 8 192 reads over the ranges its contig spans --, and
@@ -74,7 +74,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         if (may_pm) {
             const size_t groups = pm_bytes / (64 * sizeof(uint16_t));
             TRY(ensure(c, c->pm_desc, groups * sizeof(uint32_t)));
-            TRY(ensure(c, c->pm_work, 1024 * sizeof(uint32_t)));
+            TRY(ensure(c, c->pm_work, (size_t)qmcp::pm_work_words() * sizeof(uint32_t)));
         }
         TRY(ensure(c, c->vals[0], (size_t)n * sizeof(uint32_t)));
         TRY(ensure(c, c->vals[1], (size_t)n * sizeof(uint32_t)));
@@ -137,8 +137,8 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         // start positions on this route -- the partition rebuilds them from the starts.
         run.have_gstart = false;
         hipStream_t s1 = c->stream;
-        static const uint32_t init[8] = {0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        HIP_TRY(hipMemcpyAsync(c->stats.p, init, sizeof(init), hipMemcpyHostToDevice, s1));
+        // (one copy of eight words from pinned memory: span minimum, and zeros for everything the head counts)
+        HIP_TRY(hipMemcpyAsync(c->stats.p, c->h_stats_init, 8 * sizeof(uint32_t), hipMemcpyHostToDevice, s1));
         run.pm = !two_level && pm_route_ok(c, roff, pr, range_shift);
         run.nu_filter = c->nu_ell;
         hs[5] = hs[6] = 0;
@@ -147,7 +147,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
             // (4 B per read out, two [range][pass] tables); a scan of the padded count table gives the padded flat
             // coordinates, one more small kernel the wave-slot descriptors the per-range kernels follow.  No range-major
             // copy, no second read of the starts.
-            TRY(queue_pm_head(c, s1, run.nu_filter));
+            TRY(queue_pm_head(c, s1, run.nu_filter, false));
         } else {
             // the range-major form: k_prepare, scan, partition (one or two levels), bucket offsets
             TRY(queue_rm_head(c, s1, run.nu_filter, true));
@@ -242,35 +242,35 @@ int queue_rm_head(qmcp_hip_ctx* c, hipStream_t s1, uint32_t filter, bool clear_m
 }
 
 // The pass-major head's stages once more on `st` -- producer (regular reads: span == filter, or every read when
-// filter == 0), scan, range table, bucket offsets -- for a call whose head ran with the wrong idea of the spans.
-int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter) {
+// filter == 0), table stage, bucket offsets -- for a call whose head ran with the wrong idea of the spans.
+int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) {
     SolveRun& run = c->run;
     const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot, n_contigs = run.n_contigs;
     uint32_t* d_stats = (uint32_t*)c->stats.p;
-    static const uint32_t zeros[4] = {0u, 0u, 0u, 0u};
-    HIP_TRY(hipMemcpyAsync(d_stats + 3, zeros, sizeof(zeros), hipMemcpyHostToDevice, st));  // empty positions, exceptions, list flag, overflow entries
+    // (a re-run must not add to what the first run counted -- empty positions, exceptions, list flag, overflow entries;
+    //  the first run's words were cleared with the statistics' initial values)
+    if (rerun) HIP_TRY(hipMemcpyAsync(d_stats + 3, c->h_stats_init + 1, 4 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     uint32_t* d_range_start = (uint32_t*)c->ranges.p;
     uint32_t* d_max_load = d_range_start + 65540;
     {
         KernelSpan sp(c, "k_pm_prepare_sort", st);
         qmcp::launch_pm_prepare_sort(st, run.d_starts, run.d_ends, n, (const uint64_t*)c->roff.p, (const uint64_t*)c->poff.p,
                                      n_contigs, run.range_shift, ltot, (uint16_t*)c->keys[0].p, (uint16_t*)c->keys[1].p,
-                                     (uint32_t*)c->hist2.p, (uint32_t*)c->hist.p,
-                                     (uint32_t*)c->pm_work.p, d_stats, (unsigned long long*)run.d_mask, filter,
+                                     (uint32_t*)c->hist2.p, (uint32_t*)c->hist.p, d_stats, (unsigned long long*)run.d_mask, filter,
                                      filter ? (uint32_t*)c->nu_exc.p : nullptr, nu_cap_for(n),
                                      filter ? qmcp::nu_exc_counts((uint32_t*)c->nu_exc.p, nu_cap_for(n)) : nullptr);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_PREP], st));
     {
-        KernelSpan sp(c, "scan_radix_hist(3 kernels)", st);
-        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->hist2.p, 256u * qmcp::pm_pitch(n), (uint32_t*)c->hist2.p,
-                                    (uint32_t*)c->spine2.p, true);
+        KernelSpan sp(c, "k_pm_row_sums", st);
+        qmcp::launch_pm_row_sums(st, (const uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, (uint32_t*)c->pm_work.p);
     }
     {
-        KernelSpan sp(c, "k_pm_descr + k_pm_range_table", st);
-        qmcp::launch_pm_descr(st, (const uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, ltot, run.range_shift,
-                              (uint32_t*)c->pm_desc.p, (uint32_t*)c->pm_work.p, d_range_start, d_max_load);
+        KernelSpan sp(c, "k_pm_tables", st);
+        qmcp::launch_pm_tables(st, (uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, ltot, run.range_shift,
+                               (uint32_t*)c->pm_desc.p, (const uint32_t*)c->pm_work.p, d_range_start, d_max_load,
+                               rerun ? nullptr : (uint32_t*)c->scalars.p);  // (the result scalars, 64 bytes: cleared here for the one-span tail)
     }
     HIP_TRY(hipEventRecord(c->ev_fork, st));  // statistics and heaviest load are final here
     {
@@ -283,25 +283,15 @@ int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter) {
     return QMCP_OK;
 }
 
-// The ranking of the pass-major form on `st`: the ordered walk, then the settling of the quota-crossing groups it listed.
+// The ranking of the pass-major form on `st`: the ordered walk; the quota-crossing groups it lists are settled in its tail.
 void queue_pm_rank(qmcp_hip_ctx* c, hipStream_t st, const uint32_t* ev_sev, const uint32_t* ev_lastns, uint32_t ell) {
     SolveRun& run = c->run;
     const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot;
     const bool by_records = qmcp::rank_scratch_by_records(run.range_shift, ltot, n);
-    const uint16_t* keys16 = (const uint16_t*)c->keys[0].p;
-    const uint16_t* idx16 = (const uint16_t*)c->keys[1].p;
-    const uint32_t* desc = (const uint32_t*)c->pm_desc.p;
-    const uint32_t* Tp = (const uint32_t*)c->hist2.p;
-    const uint32_t* range_start = (const uint32_t*)c->ranges.p;
-    uint32_t* amb_count = (uint32_t*)c->pm_work.p + 512;
-    unsigned long long* kept_total = (unsigned long long*)c->scalars.p;
-    {
-        KernelSpan sp(c, "k_pm_walk", st);
-        qmcp::launch_pm_walk(st, keys16, idx16, desc, Tp, n, range_start, run.range_shift, ltot, (const uint32_t*)c->boff.p,
-                             (const uint32_t*)c->selend.p, (unsigned long long*)run.d_mask, kept_total, c->rankamb.p, by_records,
-                             amb_count, ev_sev, ev_lastns, (const uint64_t*)c->poff.p, run.n_contigs, ell);
-    }
-    KernelSpan sp(c, "k_pm_settle", st);
-    qmcp::launch_pm_settle(st, keys16, idx16, desc, Tp, n, range_start, run.range_shift, ltot, c->rankamb.p, by_records,
-                           amb_count, (unsigned long long*)run.d_mask, kept_total);
+    KernelSpan sp(c, "k_pm_walk", st);
+    qmcp::launch_pm_walk(st, (const uint16_t*)c->keys[0].p, (const uint16_t*)c->keys[1].p, (const uint32_t*)c->pm_desc.p,
+                         (const uint32_t*)c->hist2.p, n, (const uint32_t*)c->ranges.p, run.range_shift, ltot,
+                         (const uint32_t*)c->boff.p, (const uint32_t*)c->selend.p, (unsigned long long*)run.d_mask,
+                         (unsigned long long*)c->scalars.p, c->rankamb.p, by_records, ev_sev, ev_lastns,
+                         (const uint64_t*)c->poff.p, run.n_contigs, ell);
 }

@@ -68,7 +68,7 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     if (uniform && run.nu_filter != 0 && run.nu_filter != max_span) {
         // the head listed every read as an exception to the last call's span: its stages again, unfiltered
         c->nu_ell = 0;
-        if (run.pm) TRY(queue_pm_head(c, c->stream, 0));
+        if (run.pm) TRY(queue_pm_head(c, c->stream, 0, true));
         else TRY(queue_rm_head(c, c->stream, 0, true));
         HIP_TRY(hipMemcpyAsync(c->h_nu, (uint32_t*)c->ranges.p + 65540, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -109,7 +109,8 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     // one range holds too much (its ranking is one wave's serial walk), the keep mask comes from
     // the radix sort instead (the counts and the sweep done here stay valid).
     bool mixed_whole_contigs = false;
-    if (!near_done) HIP_TRY(hipMemsetAsync(c->scalars.p, 0, 64, c->stream));
+    // (one span after a pass-major head: k_pm_tables cleared the scalars on this stream, and nothing has touched them since)
+    if (!near_done && !(uniform && run.pm)) HIP_TRY(hipMemsetAsync(c->scalars.p, 0, 64, c->stream));
     if (uniform && may_rank) {
         hipStream_t s1 = c->stream;  // (partition and bucket offsets are already queued)
         HIP_TRY(hipGetLastError());
@@ -423,7 +424,12 @@ int create_ctx(int device, qmcp_hip_ctx** out_ctx) {
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_head, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_head, 8 * sizeof(uint32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_head, 16 * sizeof(uint32_t), hipHostMallocDefault);
+    if (e == hipSuccess) {
+        c->h_stats_init = c->h_head + 8;
+        c->h_stats_init[0] = 0xFFFFFFFFu;
+        for (int i = 1; i < 8; ++i) c->h_stats_init[i] = 0u;
+    }
     if (e != hipSuccess) {
         qmcp_hip_destroy(c);
         return fail(QMCP_EHIP, "context setup: %s", hipGetErrorString(e));

@@ -13,18 +13,20 @@
 //                       stride = 8192 + 64 n_ranges, the slices follow each other padded to whole groups of 64 slots.
 //                       Two tables laid out [range][pass]: the slice's record count rounded up to a multiple of 64, and
 //                       (first slot - P stride) / 64 | true count << 16.
-//   (scan)              exclusive scan over the padded count table: Tp[d][P] = the PADDED FLAT position of the slice --
+//   k_pm_row_sums,      exclusive scan over the padded count table in two launches (partial sums of the rows' parts, then
+//   k_pm_tables         every part scanned from a base it derives itself): Tp[d][P] = the PADDED FLAT position of the slice --
 //                       range d's records in read-index order are its slices in pass order, each padded to whole
 //                       groups, so a group of 64 padded flat positions (a WAVE-SLOT) lies in exactly one slice.
-//   k_pm_descr          one thread per table entry: one descriptor word per wave-slot -- pass << 15 | slot group inside the
-//                       pass << 6 | (records in the group - 1) --; the rows' true record counts (k_pm_range_table scans
-//                       them: the ranges' true flat starts -- the bucket offsets' bases -- and the heaviest load).
+//   k_pm_tables         the same launch, one thread per table entry: one descriptor word per wave-slot -- pass << 15 |
+//                       slot group inside the pass << 6 | (records in the group - 1) --; from the rows' true record counts
+//                       the ranges' true flat starts -- the bucket offsets' bases -- and the heaviest load.
 //   k_pm_offsets        per range: LDS histogram of its wave-slots' positions -> bucket offsets (k_range_offsets' job).
 //   k_pm_walk           per range: k_rank_mark's ordered walk, a chunk of sixteen wave-slots per step, each wave's
 //                       records found through ONE descriptor word (round 3 searched the table's row with a cursor in
 //                       LDS: 57 vector instructions per wave and chunk against the range-major walk's 21).  Kept
 //                       records' read indices collect in a ring in LDS, per wave, and are marked 64 at a time.
-//   k_pm_settle         the (chunk, position) groups whose quota ran out inside a chunk, one wave per group, chip-wide.
+//                       The (chunk, position) groups whose quota ran out inside a chunk are listed and settled in the
+//                       kernel's tail, one wave per group, by the workgroup that listed them.
 // A range's records in read-index order are its slices in pass order, so nothing about the selection changes: the
 // kept set is bit for bit the first form's.  One-level genomes only (<= 256 ranges); longer ones keep the two-level
 // partition, and so do calls whose slices would be short (narrow ranges: the padding would be most of a group).
@@ -46,7 +48,6 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
     uint32_t shift, uint32_t stride /* pm_stride_of(ranges of the genome) */,
     uint16_t* __restrict__ keys16, uint16_t* __restrict__ idx16,
     uint32_t* __restrict__ cnt_tab, uint32_t* __restrict__ lst_tab, uint32_t pitch /* multiple of 4 */,
-    uint32_t* __restrict__ work /* 260 words k_pm_descr adds into: cleared here */,
     uint32_t* __restrict__ stats, unsigned long long* __restrict__ zero_mask,
     // near-uniform route (kernels/near_uniform.inc.hip): reads whose span is not ell_reg are left out of the sorted
     // passes and listed instead -- {global start, global end, read index}, three arrays of exc_cap words.  Every wave
@@ -64,7 +65,6 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
     uint32_t* s_tabc = s_wave + 16;                     // [4][256] the workgroup's table entries
     uint32_t* s_tabl = s_tabc + kPmPassesPerWg * 256;   // [4][256]
     uint32_t* s_exc = s_tabl + kPmPassesPerWg * 256;    // [8][128][3] every wave's exceptions of the pass, until the pass is written out
-    if (blockIdx.x == 0 && threadIdx.x < 260) work[threadIdx.x] = 0;  // (k_pm_descr's row sums and ticket)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t mn = 0xFFFFFFFFu, mx = 0, bad = 0;
     auto contig_of = [&](uint32_t i) {
@@ -307,9 +307,10 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
     }
 }
 
-// k_pm_descr's working words (cleared by k_pm_prepare_sort): [0..255] the rows' true record counts
-static constexpr uint32_t kPmWorkWords = 260;
+// The table stage's working words: per (range, part of the row) the part's padded and true record counts -- written by
+// k_pm_row_sums with plain stores (every word every call: nothing to clear), read whole by every k_pm_tables workgroup.
 static constexpr uint32_t kPmDescrY = 8;  // workgroups per range
+static constexpr uint32_t kPmWorkWords = 256u * kPmDescrY * 2u;
 
 // A wave-slot's descriptor: pass << 15 | slot group inside the pass << 6 | (records - 1).  (2^17 passes: 2^30 reads; 512
 // slot groups: a pass holds at most 8192 / 64 + 256.)
@@ -325,66 +326,141 @@ __device__ __forceinline__ PmSlot pm_unpack(uint32_t dsc, bool has, uint32_t str
     return s;
 }
 
-// A thread per (range, pass) table entry: the slice's wave-slot descriptors; per range the true record count (one atomic
-// per workgroup; kPmDescrY workgroups a range).  (A first form had a workgroup per 256 entries, every one ending in an
-// atomic on one ticket word: 12 288 same-address atomics, 0.49 ms; one workgroup per range with a ticket: 0.044 ms, a
-// serial loop of dependent loads per thread.)
-__global__ __launch_bounds__(256) void k_pm_descr(const uint32_t* __restrict__ Tp, const uint32_t* __restrict__ lstw,
-                                                  uint32_t pitch, uint32_t n_groups /* total padded flat / 64 bound */,
-                                                  uint32_t* __restrict__ desc, uint32_t* __restrict__ work) {
-    __shared__ uint32_t s_red[4];
+// The table stage in two launches (the launches are the only synchronisation: no flags, no look-back).  A row of the
+// [range][pass] tables is cut into kPmDescrY parts; workgroup (d, y) owns part y of row d in both kernels.
+__device__ __forceinline__ void pm_row_part(uint32_t pitch, uint32_t& P_beg, uint32_t& P_end) {
+    const uint32_t per = (pitch + kPmDescrY - 1u) / kPmDescrY;
+    P_beg = min(pitch, blockIdx.y * per);
+    P_end = min(pitch, (blockIdx.y + 1u) * per);
+}
+
+// k_pm_row_sums: the part's padded record count (cnt_tab) and true record count (lst_tab >> 16) -> work[(d Y + y) 2 ..].
+__global__ __launch_bounds__(256) void k_pm_row_sums(const uint32_t* __restrict__ cnt_tab, const uint32_t* __restrict__ lstw,
+                                                     uint32_t pitch, uint32_t* __restrict__ work) {
+    __shared__ uint32_t s_red[2][4];
     const uint32_t d = blockIdx.x;
-    const uint32_t per = (pitch + gridDim.y - 1u) / gridDim.y;
-    const uint32_t P_end = min(pitch, (blockIdx.y + 1u) * per);
-    uint32_t mine = 0;
-    for (uint32_t P0 = blockIdx.y * per + threadIdx.x; P0 < P_end; P0 += 4u * 256u) {
-        uint32_t w[4], t[4];
+    uint32_t P_beg, P_end;
+    pm_row_part(pitch, P_beg, P_end);
+    uint32_t pad = 0, tru = 0;
+    for (uint32_t P0 = P_beg + threadIdx.x; P0 < P_end; P0 += 4u * 256u) {
+        uint32_t c[4], w[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t P = min(P0 + (uint32_t)u * 256u, P_end - 1u);  // clamped: every load is issued
+            c[u] = cnt_tab[(size_t)d * pitch + P];
             w[u] = lstw[(size_t)d * pitch + P];
-            t[u] = Tp[(size_t)d * pitch + P];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (P0 + (uint32_t)u * 256u < P_end) { pad += c[u]; tru += w[u] >> 16; }
+    }
+    pad = wave_sum_u32(pad);
+    tru = wave_sum_u32(tru);
+    if ((threadIdx.x & 63u) == 0u) { s_red[0][threadIdx.x >> 6] = pad; s_red[1][threadIdx.x >> 6] = tru; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t* const out = work + ((size_t)d * kPmDescrY + blockIdx.y) * 2u;
+        out[0] = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
+        out[1] = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
+    }
+}
+
+// k_pm_tables: everything else of the stage.  Every workgroup reads all 256 x Y partial pairs (16 KB; thread t takes row
+// t) and derives what it needs itself: the padded flat start of its part -- the rows before d, the parts before y --, and
+// workgroup (0, 0) the ranges' true flat starts (257 entries), the heaviest range's load and the scan's grand total (and
+// it clears the sixteen words of clear16: the stream orders that ahead of everything the solve's tail queues).  It
+// then scans its part of the padded count table IN PLACE (tab: cnt_tab in, Tp out -- absolute padded flat coordinates,
+// what an exclusive scan over the whole table gives; a thread overwrites only the entries it has read itself) and
+// writes the slices' wave-slot descriptors, a thread per (range, pass) table entry.  (First forms of the descriptor
+// kernel: a workgroup per 256 entries, every one ending in an atomic on one ticket word: 12 288 same-address atomics,
+// 0.49 ms; one workgroup per range walking its row serially: 0.044 ms.)
+__global__ __launch_bounds__(256) void k_pm_tables(uint32_t* tab, const uint32_t* __restrict__ lstw, uint32_t pitch,
+                                                   uint32_t n_groups /* total padded flat / 64 bound */,
+                                                   uint32_t* __restrict__ desc, const uint32_t* __restrict__ work,
+                                                   uint32_t* __restrict__ range_start, uint32_t* __restrict__ max_load,
+                                                   uint32_t* __restrict__ clear16 /* or null */) {
+    __shared__ uint32_t s_red[4], s_base, s_tile[2][4][4];
+    const uint32_t d = blockIdx.x, y = blockIdx.y, tid = threadIdx.x;
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
+    const bool first = d == 0u && y == 0u;  // (uniform)
+    uint32_t rp = 0, rt = 0, before = 0;  // row tid: padded total, true total, padded total of its parts before y
+    {
+        const uint4* const src = reinterpret_cast<const uint4*>(work + (size_t)tid * kPmDescrY * 2u);
+        uint4 q[kPmDescrY / 2u];
+#pragma unroll
+        for (uint32_t k = 0; k < kPmDescrY / 2u; ++k) q[k] = src[k];
+#pragma unroll
+        for (uint32_t k = 0; k < kPmDescrY / 2u; ++k) {
+            if (2u * k < y) before += q[k].x;
+            if (2u * k + 1u < y) before += q[k].z;
+            rp += q[k].x + q[k].z;
+            rt += q[k].y + q[k].w;
+        }
+    }
+    {
+        const uint32_t inc = wave_incl_scan_add(rp);
+        if (lane == 63u) s_red[wv] = inc;
+        __syncthreads();
+        uint32_t base = 0;
+        for (uint32_t x = 0; x < wv; ++x) base += s_red[x];
+        if (tid == d) s_base = base + inc - rp + before;
+        if (first && tid == 255u) tab[(size_t)256u * pitch] = base + inc;  // the scan's total
+        __syncthreads();
+    }
+    if (first) {  // the ranges' true flat starts and the heaviest range's load, from the rows' true counts
+        if (clear16 != nullptr && tid < 16u) clear16[tid] = 0u;  // (the solve's result scalars: saves the tail a memset launch)
+        const uint32_t inc = wave_incl_scan_add(rt);
+        const uint32_t mx = wave_max_u32(rt);
+        if (lane == 63u) s_red[wv] = inc;
+        __syncthreads();
+        uint32_t base = 0;
+        for (uint32_t x = 0; x < wv; ++x) base += s_red[x];
+        range_start[tid] = base + inc - rt;
+        if (tid == 255u) range_start[256] = base + inc;
+        __syncthreads();
+        if (lane == 0u) s_red[wv] = mx;
+        __syncthreads();
+        if (tid == 0) max_load[0] = max(max(s_red[0], s_red[1]), max(s_red[2], s_red[3]));
+    }
+    uint32_t P_beg, P_end;
+    pm_row_part(pitch, P_beg, P_end);
+    uint32_t carry = s_base;  // padded flat position of entry P0 of the round (uniform)
+    uint32_t round = 0;
+    for (uint32_t P0 = P_beg; P0 < P_end; P0 += 4u * 256u, round ^= 1u) {
+        uint32_t c[4], w[4], inc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t P = P0 + (uint32_t)u * 256u + tid;
+            const bool in = P < P_end;
+            const size_t at = (size_t)d * pitch + min(P, P_end - 1u);  // clamped: every load is issued
+            c[u] = tab[at];
+            w[u] = lstw[at];
+            if (!in) { c[u] = 0u; w[u] = 0u; }
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const uint32_t P = P0 + (uint32_t)u * 256u;
-            const uint32_t cnt = P < P_end ? w[u] >> 16 : 0u;
+            inc[u] = wave_incl_scan_add(c[u]);
+            if (lane == 63u) s_tile[round][u][wv] = inc[u];
+        }
+        __syncthreads();  // (one barrier a round: the next round writes the other half of s_tile)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            uint32_t base = carry;
+            for (uint32_t x = 0; x < wv; ++x) base += s_tile[round][u][x];
+            carry += s_tile[round][u][0] + s_tile[round][u][1] + s_tile[round][u][2] + s_tile[round][u][3];
+            const uint32_t P = P0 + (uint32_t)u * 256u + tid;
+            if (P >= P_end) continue;
+            const uint32_t t = base + inc[u] - c[u];
+            tab[(size_t)d * pitch + P] = t;
+            const uint32_t cnt = w[u] >> 16;
             if (cnt == 0u) continue;
-            mine += cnt;
-            const uint32_t g = t[u] >> 6;
+            const uint32_t g = t >> 6;
             const uint32_t n_ws = (cnt + 63u) >> 6;
             for (uint32_t j = 0; j < n_ws; ++j)
                 if (g + j < n_groups)  // (always: the bound is the buffer's size)
                     desc[g + j] = (P << 15) | (((w[u] & 0xFFFFu) + j) << 6) | (min(64u, cnt - 64u * j) - 1u);
         }
     }
-    const uint32_t sum = wave_sum_u32(mine);
-    if ((threadIdx.x & 63u) == 0u) s_red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t tot = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-        if (tot != 0u) atomicAdd(&work[d], tot);
-    }
-}
-
-// the ranges' true flat starts (257 entries) and the heaviest range's load, from the rows' true counts
-__global__ __launch_bounds__(256) void k_pm_range_table(const uint32_t* __restrict__ work, uint32_t* __restrict__ range_start,
-                                                        uint32_t* __restrict__ max_load) {
-    __shared__ uint32_t s_red[4];
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint32_t c = work[threadIdx.x];
-    const uint32_t inc = wave_incl_scan_add(c);
-    const uint32_t mx = wave_max_u32(c);
-    if (lane == 63u) s_red[wv] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (uint32_t x = 0; x < wv; ++x) base += s_red[x];
-    range_start[threadIdx.x] = base + inc - c;
-    if (threadIdx.x == 255u) range_start[256] = base + inc;
-    __syncthreads();
-    if (lane == 0u) s_red[wv] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) max_load[0] = max(max(s_red[0], s_red[1]), max(s_red[2], s_red[3]));
 }
 
 // k_range_offsets for the pass-major layout: the range's positions come as wave-slots, in any order.  A wave takes four
@@ -483,11 +559,68 @@ __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict_
 // ranking to read back (30 us and 100 MB a solve; here the ranking reads the sweep's own output).
 struct EvQuota { const uint32_t* sev; const uint32_t* lastns; const uint64_t* poff; uint32_t n_contigs, ell; };
 
+// Settling, in the walk's own tail: the listed (chunk, position) groups of the range.  The position's `skip` LAST records
+// of that chunk are the ones the quota did not reach, so a wave walks the chunk's sixteen wave-slots backwards, passes
+// over that many matches and keeps the rest.  The workgroup's sixteen waves deal the groups out (a few dozen per range
+// at cfg4: 20 000 in all), and a wave takes two at a time (all their loads asked for before either is looked at: a group
+// is four dependent trips to memory and little else).  -> records kept by this wave (uniform).  (This was a kernel of
+// its own, k_pm_settle -- a second launch that loaded Tp, the range's start and a per-range group count again.)
+__device__ __forceinline__ uint32_t pm_settle_groups(const uint16_t* __restrict__ keys16, const uint16_t* __restrict__ idx16,
+                                                     const uint32_t* __restrict__ desc, uint32_t g0, uint32_t n_ws,
+                                                     uint32_t stride, const uint2* amb, uint32_t namb, uint32_t w,
+                                                     uint32_t lane, unsigned long long* __restrict__ mask) {
+    const uint64_t gt_mask = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);  // lanes above this one
+    uint32_t kept = 0;
+    constexpr int kSteps = 16, kE = 2;
+    constexpr uint32_t stride_k = 16;  // waves of the workgroup
+    for (uint32_t k0 = w; k0 < namb; k0 += kE * stride_k) {
+        uint32_t key[kE][kSteps], dscv[kE] /* lane t < 16: the descriptor of the chunk's wave-slot t */, p[kE], skip[kE], c_of[kE];
+#pragma unroll
+        for (int x = 0; x < kE; ++x) {
+            const uint32_t k = k0 + (uint32_t)x * stride_k;
+            const uint2 ent = k < namb ? amb[k] : make_uint2(0u, 0u);
+            c_of[x] = ent.x >> 15;
+            p[x] = k < namb ? ent.x & 0x7FFFu : 0xFFFFFFFFu;  // (no 16-bit position equals it)
+            skip[x] = ent.y;  // matches still to be passed over, from the chunk's end
+            const uint32_t ws = 16u * c_of[x] + (lane & 15u);
+            dscv[x] = ws < n_ws ? desc[g0 + ws] : 0u;
+        }
+#pragma unroll
+        for (int x = 0; x < kE; ++x) {
+#pragma unroll
+            for (int t = 0; t < kSteps; ++t) {
+                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)dscv[x], t);
+                key[x][t] = keys16[pm_unpack<false>(dsc, 16u * c_of[x] + (uint32_t)t < n_ws, stride).slot0 + lane];
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < kE; ++x) {
+#pragma unroll
+            for (int t = kSteps - 1; t >= 0; --t) {
+                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)dscv[x], t);
+                const PmSlot at = pm_unpack<false>(dsc, 16u * c_of[x] + (uint32_t)t < n_ws, stride);
+                const bool member = lane < at.nv && key[x][t] == p[x];
+                const uint64_t m = __ballot(member);
+                if (m == 0) continue;
+                const uint32_t above = (uint32_t)__popcll(m & gt_mask);  // matches after this one in the step
+                if (member && above >= skip[x]) {
+                    const uint32_t v = at.pass * (uint32_t)kPmPass + idx16[at.slot0 + lane];
+                    atomicOr(&mask[v >> 6], 1ull << (v & 63u));
+                }
+                const uint32_t in_step = (uint32_t)__popcll(m);
+                kept += in_step > skip[x] ? in_step - skip[x] : 0u;
+                skip[x] = skip[x] > in_step ? skip[x] - in_step : 0u;
+            }
+        }
+    }
+    return kept;
+}
+
 // k_rank_mark's ordered walk for the pass-major layout: one workgroup (16 waves) per range, quota array q[p] = S(p) in
 // LDS, the range's wave-slots in order, sixteen (a CHUNK: one per wave) per step: `old = q[p]--`, barrier, `aft = q[p]`,
 // barrier; kept iff old > 0 -- except where the quota runs out inside the chunk (old > 0 but aft < 0: the draws of one
 // chunk come in no particular order): those groups are listed (chunk, position, -aft) by the record that drew
-// old == 1 and settled by k_pm_settle.  A wave's records are the 64 slots its descriptor names -- one word, asked for
+// old == 1 and settled after the last chunk by the same workgroup (pm_settle_groups).  A wave's records are the 64 slots its descriptor names -- one word, asked for
 // fifteen chunks ahead -- and their positions and read indices are asked for seven chunks ahead, issued and waited for by
 // hand.  Kept records: the wave collects their read indices in a ring of 128 words in LDS and marks them 64 at a time --
 // one atomic instruction every ~20 chunks instead of one per chunk: atomics and stores share the loads' counter, and a
@@ -501,7 +634,6 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
                                                   EvQuota evq,
                                                   unsigned long long* __restrict__ mask,
                                                   uint2* __restrict__ amb_lists, int lists_by_records,
-                                                  uint32_t* __restrict__ amb_count /* [256] */,
                                                   unsigned long long* __restrict__ kept_total) {
     extern __shared__ int32_t s_q[];  // [(1 << shift) + 1] quotas
     __shared__ uint32_t s_namb, s_kept;
@@ -513,7 +645,6 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint32_t lo_p = Tp[(size_t)range * pitch];
     const uint32_t hi_p = Tp[(size_t)(range + 1) * pitch];  // (range 255: the scan's total)
-    if (tid == 0) amb_count[range] = 0;
     if (lo_p >= hi_p) return;  // uniform: a range without reads needs no quotas either
     const uint32_t g0 = lo_p >> 6, n_ws = (hi_p - lo_p) >> 6;
     const uint32_t n_chunks = (n_ws + 15u) >> 4;
@@ -695,88 +826,14 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
         atomicOr(&mask[v >> 6], 1ull << (v & 63u));
     }
     kept = cur;
+    // The groups this workgroup listed, settled where they were produced: the barrier makes its amb[] stores (and
+    // s_namb) visible to its own waves -- workgroup scope is all that is needed, nobody else reads the list.  Plain C++
+    // from here on: the ring registers are dead.
+    __syncthreads();
+    kept += pm_settle_groups(keys16, idx16, desc, g0, n_ws, stride, amb, s_namb, w, lane, mask);
     if (lane == 0 && kept) atomicAdd(&s_kept, kept);
     __syncthreads();
-    if (tid == 0) {
-        amb_count[range] = s_namb;
-        if (s_kept) atomicAdd(kept_total, (unsigned long long)s_kept);
-    }
-}
-
-// The listed (chunk, position) groups of every range: the position's `skip` LAST records of that chunk are the ones the
-// quota did not reach, so a wave walks the chunk's sixteen wave-slots backwards, passes over that many matches and
-// keeps the rest.  grid (ranges, kPmSettleY), sixteen waves per
-// workgroup: a range's groups (a few dozen at cfg4: 20 000 in all) are dealt to 16 kPmSettleY waves, and a wave takes two
-// groups at a time (all their loads asked for before either is looked at: a group is four dependent trips to memory and
-// little else).  Few, large workgroups: every workgroup ends in one atomic on the kept count, and same-address atomics
-// queue up behind one another (a first form with 32 small workgroups per range: 5 000 of them, 0.07 ms for 0.006 of work).
-static constexpr uint32_t kPmSettleY = 2;
-static constexpr uint32_t kPmSettleWaves = 16;
-__global__ __launch_bounds__(1024) void k_pm_settle(const uint16_t* __restrict__ keys16, const uint16_t* __restrict__ idx16,
-                                                   const uint32_t* __restrict__ desc, const uint32_t* __restrict__ Tp,
-                                                   uint32_t pitch, const uint32_t* __restrict__ range_start, uint32_t shift,
-                                                   uint32_t stride, const uint2* __restrict__ amb_lists, int lists_by_records,
-                                                   const uint32_t* __restrict__ amb_count,
-                                                   unsigned long long* __restrict__ mask,
-                                                   unsigned long long* __restrict__ kept_total) {
-    __shared__ uint32_t s_kept;
-    const uint32_t range = blockIdx.x, width = 1u << shift;
-    const uint32_t namb = amb_count[range];
-    if (blockIdx.y * kPmSettleWaves >= namb) return;  // uniform
-    if (threadIdx.x == 0) s_kept = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t lo_p = Tp[(size_t)range * pitch], hi_p = Tp[(size_t)(range + 1) * pitch];
-    const uint32_t g0 = lo_p >> 6, n_ws = (hi_p - lo_p) >> 6;
-    const uint2* const amb = amb_lists + (lists_by_records ? (size_t)range_start[range] : (size_t)range * width);
-    const uint64_t gt_mask = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);  // lanes above this one
-    uint32_t kept = 0;
-    constexpr int kSteps = 16, kE = 2;
-    const uint32_t stride_k = kPmSettleWaves * gridDim.y;
-    for (uint32_t k0 = blockIdx.y * kPmSettleWaves + w; k0 < namb; k0 += kE * stride_k) {
-        uint32_t key[kE][kSteps], dscv[kE] /* lane t < 16: the descriptor of the chunk's wave-slot t */, p[kE], skip[kE], c_of[kE];
-#pragma unroll
-        for (int x = 0; x < kE; ++x) {
-            const uint32_t k = k0 + (uint32_t)x * stride_k;
-            const uint2 ent = k < namb ? amb[k] : make_uint2(0u, 0u);
-            c_of[x] = ent.x >> 15;
-            p[x] = k < namb ? ent.x & 0x7FFFu : 0xFFFFFFFFu;  // (no 16-bit position equals it)
-            skip[x] = ent.y;  // matches still to be passed over, from the chunk's end
-            const uint32_t ws = 16u * c_of[x] + (lane & 15u);
-            dscv[x] = ws < n_ws ? desc[g0 + ws] : 0u;
-        }
-#pragma unroll
-        for (int x = 0; x < kE; ++x) {
-#pragma unroll
-            for (int t = 0; t < kSteps; ++t) {
-                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)dscv[x], t);
-                key[x][t] = keys16[pm_unpack<false>(dsc, 16u * c_of[x] + (uint32_t)t < n_ws, stride).slot0 + lane];
-            }
-        }
-#pragma unroll
-        for (int x = 0; x < kE; ++x) {
-#pragma unroll
-            for (int t = kSteps - 1; t >= 0; --t) {
-                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)dscv[x], t);
-                const PmSlot at = pm_unpack<false>(dsc, 16u * c_of[x] + (uint32_t)t < n_ws, stride);
-                const bool member = lane < at.nv && key[x][t] == p[x];
-                const uint64_t m = __ballot(member);
-                if (m == 0) continue;
-                const uint32_t above = (uint32_t)__popcll(m & gt_mask);  // matches after this one in the step
-                if (member && above >= skip[x]) {
-                    const uint32_t v = at.pass * (uint32_t)kPmPass + idx16[at.slot0 + lane];
-                    atomicOr(&mask[v >> 6], 1ull << (v & 63u));
-                }
-                const uint32_t in_step = (uint32_t)__popcll(m);
-                kept += in_step > skip[x] ? in_step - skip[x] : 0u;
-                skip[x] = skip[x] > in_step ? skip[x] - in_step : 0u;
-            }
-        }
-    }
-    if (lane == 0 && kept) atomicAdd(&s_kept, kept);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_kept) atomicAdd(kept_total, (unsigned long long)s_kept);
+    if (tid == 0 && s_kept) atomicAdd(kept_total, (unsigned long long)s_kept);
 }
 
 // ---- launchers
@@ -789,23 +846,32 @@ uint32_t pm_exc_slots(uint32_t n) { return pm_pitch(n) * kPmWaves * kPmExcPerWav
 void launch_pm_prepare_sort(hipStream_t st, const uint32_t* starts, const uint32_t* ends, uint32_t n,
                             const uint64_t* d_roff, const uint64_t* d_poff, uint32_t n_contigs, uint32_t shift, uint32_t ltot,
                             uint16_t* keys16, uint16_t* idx16, uint32_t* cnt_tab, uint32_t* lst_tab,
-                            uint32_t* work, uint32_t* stats, unsigned long long* zero_mask, uint32_t ell_reg, uint32_t* exc,
+                            uint32_t* stats, unsigned long long* zero_mask, uint32_t ell_reg, uint32_t* exc,
                             uint32_t exc_cap, uint32_t* exc_cnt) {
     const uint32_t pitch = pm_pitch(n);
     if (pitch == 0) return;
     (void)hipFuncSetAttribute((const void*)k_pm_prepare_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPmSortLds);
     hipLaunchKernelGGL(k_pm_prepare_sort, dim3(pitch / kPmPassesPerWg), dim3(kPmThreads), kPmSortLds, st, starts, ends, n,
                        d_roff, d_poff, n_contigs, shift, pm_stride(ltot, shift), keys16, idx16, cnt_tab, lst_tab, pitch,
-                       work, stats, zero_mask, exc != nullptr ? ell_reg : 0u, exc, exc_cap, exc_cnt);
+                       stats, zero_mask, exc != nullptr ? ell_reg : 0u, exc, exc_cap, exc_cnt);
     if (exc != nullptr && ell_reg != 0u)
         hipLaunchKernelGGL(k_nu_count_groups, dim3(32), dim3(256), 0, st, exc_cnt, pitch * kPmWaves, stats);
 }
-void launch_pm_descr(hipStream_t st, const uint32_t* Tp, const uint32_t* lstw, uint32_t n, uint32_t ltot, uint32_t shift,
-                     uint32_t* desc, uint32_t* work, uint32_t* range_start, uint32_t* max_load) {
-    const uint32_t pitch = pm_pitch(n), n_ranges = (ltot >> shift) + 1u;
+// The table stage: the padded count table scanned in place (tab: counts in, Tp out, the total at tab[256 pitch]), the
+// wave-slot descriptors, the ranges' true flat starts and the heaviest load -- two launches.  All 256 rows, whatever the
+// genome's ranges: the rows beyond them hold zeros and scan to the total.
+void launch_pm_row_sums(hipStream_t st, const uint32_t* cnt_tab, const uint32_t* lstw, uint32_t n, uint32_t* work) {
+    const uint32_t pitch = pm_pitch(n);
+    if (pitch == 0) return;
+    hipLaunchKernelGGL(k_pm_row_sums, dim3(256, kPmDescrY), dim3(256), 0, st, cnt_tab, lstw, pitch, work);
+}
+void launch_pm_tables(hipStream_t st, uint32_t* tab, const uint32_t* lstw, uint32_t n, uint32_t ltot, uint32_t shift,
+                      uint32_t* desc, const uint32_t* work, uint32_t* range_start, uint32_t* max_load, uint32_t* clear16) {
+    const uint32_t pitch = pm_pitch(n);
+    if (pitch == 0) return;
     const uint32_t s64 = pm_stride(ltot, shift) / 64u;
-    hipLaunchKernelGGL(k_pm_descr, dim3(n_ranges, kPmDescrY), dim3(256), 0, st, Tp, lstw, pitch, pitch * s64, desc, work);
-    hipLaunchKernelGGL(k_pm_range_table, dim3(1), dim3(256), 0, st, work, range_start, max_load);
+    hipLaunchKernelGGL(k_pm_tables, dim3(256, kPmDescrY), dim3(256), 0, st, tab, lstw, pitch, pitch * s64, desc, work,
+                       range_start, max_load, clear16);
 }
 void launch_pm_offsets(hipStream_t st, const uint16_t* keys16, const uint32_t* desc, const uint32_t* Tp, uint32_t n,
                        const uint32_t* range_start, uint32_t shift, uint32_t ltot, uint32_t* boff, uint32_t* empty_positions) {
@@ -816,11 +882,11 @@ void launch_pm_offsets(hipStream_t st, const uint16_t* keys16, const uint32_t* d
     hipLaunchKernelGGL(k_pm_offsets, dim3(n_ranges), dim3(1024), lds, st, keys16, desc, Tp, pm_pitch(n), range_start, shift,
                        pm_stride(ltot, shift), ltot, boff, empty_positions);
 }
-// The ranking: walk, then the settling of the groups it listed -- two launches, in this order.
+// The ranking: the ordered walk, with the settling of the groups it listed in its tail -- one launch.
 void launch_pm_walk(hipStream_t st, const uint16_t* keys16, const uint16_t* idx16, const uint32_t* desc, const uint32_t* Tp,
                     uint32_t n, const uint32_t* range_start, uint32_t shift, uint32_t ltot, const uint32_t* boff,
                     const uint32_t* selend, unsigned long long* mask, unsigned long long* kept_total, void* scratch,
-                    bool scratch_by_records, uint32_t* amb_count, const uint32_t* ev_sev, const uint32_t* ev_lastns,
+                    bool scratch_by_records, const uint32_t* ev_sev, const uint32_t* ev_lastns,
                     const uint64_t* d_poff, uint32_t n_contigs, uint32_t ell) {
     const uint32_t n_ranges = (ltot >> shift) + 1;
     const EvQuota evq{ev_sev, ev_lastns, d_poff, n_contigs, ell};
@@ -828,14 +894,5 @@ void launch_pm_walk(hipStream_t st, const uint16_t* keys16, const uint16_t* idx1
     (void)hipFuncSetAttribute((const void*)k_pm_walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_pm_walk, dim3(n_ranges), dim3(1024), lds, st, keys16, idx16, desc, Tp, pm_pitch(n), range_start, shift,
                        pm_stride(ltot, shift), ltot, boff, selend, evq, mask, (uint2*)scratch, scratch_by_records ? 1 : 0,
-                       amb_count, kept_total);
-}
-void launch_pm_settle(hipStream_t st, const uint16_t* keys16, const uint16_t* idx16, const uint32_t* desc, const uint32_t* Tp,
-                      uint32_t n, const uint32_t* range_start, uint32_t shift, uint32_t ltot, const void* scratch,
-                      bool scratch_by_records, const uint32_t* amb_count, unsigned long long* mask,
-                      unsigned long long* kept_total) {
-    const uint32_t n_ranges = (ltot >> shift) + 1;
-    hipLaunchKernelGGL(k_pm_settle, dim3(n_ranges, kPmSettleY), dim3(64 * kPmSettleWaves), 0, st, keys16, idx16, desc, Tp, pm_pitch(n),
-                       range_start, shift, pm_stride(ltot, shift), (const uint2*)scratch, scratch_by_records ? 1 : 0, amb_count,
-                       mask, kept_total);
+                       kept_total);
 }
