@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_dedup_host", "qmcp_hip_solve_dedup_device",
     "qmcp_hip_solve_profile_host", "qmcp_hip_solve_profile_device",
     "qmcp_hip_solve_pairs_host", "qmcp_hip_solve_pairs_device",
+    "qmcp_hip_solve_templates_host", "qmcp_hip_solve_templates_device",
 )
 
 QMCP_OK = 0
@@ -135,6 +136,27 @@ class PairStats(C.Structure):
         out = {name: list(getattr(self, name))[:k]
                for name in ("target", "n_selected", "n_kept", "capped_positions", "demand", "sweeps", "ms_stage")}
         out.update(n_stages=k, ms_pairs=self.ms_pairs)
+        return out
+
+
+class TemplateStats(C.Structure):
+    """qmcp_hip_template_stats: the stages of a template-aware solve (the first n_stages entries of every per-stage array
+    count) and the templates: how many have a segment, how many are kept, the largest, the histogram of their sizes
+    (1 .. 7 segments, then 8 or more)"""
+    _fields_ = [("n_stages", C.c_uint32), ("reserved", C.c_uint32), ("n_selected", C.c_uint64 * PAIR_MAX_STAGES),
+                ("n_kept", C.c_uint64 * PAIR_MAX_STAGES), ("capped_positions", C.c_uint64 * PAIR_MAX_STAGES),
+                ("demand", C.c_uint64 * PAIR_MAX_STAGES), ("target", C.c_uint32 * PAIR_MAX_STAGES),
+                ("sweeps", C.c_uint32 * PAIR_MAX_STAGES), ("ms_stage", C.c_float * PAIR_MAX_STAGES),
+                ("ms_templates", C.c_float), ("max_template_size", C.c_uint32), ("n_templates_used", C.c_uint64),
+                ("n_templates_kept", C.c_uint64), ("size_hist", C.c_uint64 * 8)]
+
+    def as_dict(self):
+        k = self.n_stages
+        out = {name: list(getattr(self, name))[:k]
+               for name in ("target", "n_selected", "n_kept", "capped_positions", "demand", "sweeps", "ms_stage")}
+        out.update(n_stages=k, ms_templates=self.ms_templates, max_template_size=self.max_template_size,
+                   n_templates_used=self.n_templates_used, n_templates_kept=self.n_templates_kept,
+                   size_hist=list(self.size_hist))
         return out
 
 
@@ -355,6 +377,12 @@ _hip.qmcp_hip_solve_pairs_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_
 _hip.qmcp_hip_solve_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p, C.c_uint32,
                                              C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
                                              C.POINTER(PairStats)]
+_hip.qmcp_hip_solve_templates_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, _u32p,
+                                               C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p, C.POINTER(Stats),
+                                               C.POINTER(TemplateStats)]
+_hip.qmcp_hip_solve_templates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                 C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(Stats), C.POINTER(TemplateStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -441,6 +469,17 @@ if _host is not None:
                                                      C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_int,
                                                      C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_pairs.restype = C.c_int64
+    _host.qmcp_host_read_bam_templates.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _u32p,
+                                                   _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, C.c_uint64, _u64p,
+                                                   C.POINTER(C.c_uint64), C.c_uint64, _u32p, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_read_bam_templates.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_templates.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                         C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _u32p,
+                                                         C.c_uint32, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, _u32p,
+                                                         C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                         C.c_int, C.POINTER(TemplateStats), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_templates.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -534,6 +573,7 @@ class Solver:
         self.last_stratum_rows = None
         self.last_dedup_stats = None
         self.last_pair_stats = None
+        self.last_template_stats = None
 
     def close(self):
         if self._ctx:
@@ -896,6 +936,44 @@ class Solver:
                                                 C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(ps)))
         self.last_stats, self.last_pair_stats = st, ps
         return st, ps
+
+    def solve_templates(self, starts, ends, contig_ids, template_ids, n_templates, contig_lengths, max_coverage,
+                        stages=None):
+        """template-aware downsampling (qmcp_hip_solve_templates_host): every row is a segment, template_ids[i] <
+        n_templates names its template (a single-end read, a pair, the pieces of a split read, the aligned blocks of a
+        spliced read and its mate), stages as in solve_pairs.  The staged solve of solve_pairs with the completion by
+        template: a template is kept whole or not at all; depth is counted per segment.  -> (mask, stats,
+        template_stats): the host keep bitmask in INPUT order, stage 1's Stats, the TemplateStats.  Also left in
+        last_stats / last_template_stats"""
+        starts, ends, ids, tids = _u32(starts), _u32(ends), _u32(contig_ids), _u32(template_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n and tids.size == n, \
+            "starts, ends, contig_ids and template_ids must have one entry per segment"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ts = Stats(), TemplateStats()
+        _check(_hip.qmcp_hip_solve_templates_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(tids), n,
+                                                  int(n_templates), _p32(lengths), lengths.size, int(max_coverage),
+                                                  _p32(tg), 0 if tg is None else tg.size, _p64(mask), C.byref(st),
+                                                  C.byref(ts)))
+        self.last_stats, self.last_template_stats = st, ts
+        return mask[:mask_words(n)], st, ts
+
+    def solve_templates_device(self, d_starts, d_ends, d_contig_ids, d_template_ids, n_reads, n_templates, contig_lengths,
+                               max_coverage, d_mask, stages=None, stream=0):
+        """solve_templates on device pointers (ints); the input-order mask is written to d_mask.  -> (stats,
+        template_stats)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        st, ts = Stats(), TemplateStats()
+        _check(_hip.qmcp_hip_solve_templates_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                    C.c_void_p(d_contig_ids), C.c_void_p(d_template_ids), int(n_reads),
+                                                    int(n_templates), _p32(lengths), lengths.size, int(max_coverage),
+                                                    _p32(tg), 0 if tg is None else tg.size, C.c_void_p(d_mask),
+                                                    C.c_void_p(stream), C.byref(st), C.byref(ts)))
+        self.last_stats, self.last_template_stats = st, ts
+        return st, ts
 
     def _depth_call(self, entry, head, n, lengths, mask_arg, max_coverage, target_offsets, target_starts, target_ends,
                     padding, n_bins, tail):
@@ -1554,8 +1632,18 @@ def write_synthetic_bam(path, ref_length, names, flags, pos, mapq, clip_front, m
 
 
 def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0, capacity=1 << 24,
-             per_reference=False, amplicons_by_reference=False, stratify=None):
+             per_reference=False, amplicons_by_reference=False, stratify=None, templates=False, split_spliced=True,
+             include_secondary=False):
     """BamApi(path, config).get_paired_reads_soa() of the host mirror: dict of columns + filtered-out ids.
+    templates=True (BamApiConfig::template_aware; needs per_reference=True, takes no amplicon files and no stratify,
+    ValueError otherwise): one SEGMENT per aligned block of every record instead of paired reads -- a record is cut at
+    every N of its CIGAR (split_spliced=False: one segment per record), D stays inside its block, an unmapped record
+    (flag 0x4 or refID -1) is one NO_CONTIG segment, secondary records (0x100) are skipped and listed in filtered_out
+    unless include_secondary=True, supplementary records (0x800) are taken, and a CG:B,I field replaces the placeholder
+    CIGAR <l_seq>S<rlen>N.  A template is the accepted records of one QNAME; min_mapq / min_length drop a template when
+    any of its accepted mapped records fails.  Columns: starts, ends, contig_ids, template_ids (dense, in order of first
+    appearance), qualities, seq_lengths, segment_records (each segment's BAM record id), in file order, a record's
+    blocks left to right; plus n_templates, contig_lengths and filtered_out.
     stratify ("strand" | "read_group"; BamApiConfig::stratify_by, needs per_reference=True and no amplicon files,
     ValueError otherwise): also "strata" (one stratum id per read) and "stratum_names" -- ["+", "-"] (flag 0x10), or the
     header's @RG IDs in header order followed by "*" for records without an RG:Z field the header lists.
@@ -1564,6 +1652,16 @@ def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0
     amplicons_by_reference=True (BamApiConfig::amplicons_by_reference: BED chroms matched to the references by name;
     only with per_reference, ValueError otherwise)"""
     _need_host()
+    if templates:
+        if not per_reference:
+            raise ValueError("read_bam(templates=True) needs per_reference=True")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("read_bam(templates=True) does not take amplicon files")
+        if stratify is not None:
+            raise ValueError("read_bam(templates=True) does not take stratify")
+        return _read_bam_templates(path, min_length, min_mapq, split_spliced, include_secondary, capacity)
+    if not split_spliced or include_secondary:
+        raise ValueError("split_spliced and include_secondary need templates=True")
     if stratify is not None:
         if stratify not in ("strand", "read_group"):
             raise ValueError(f'stratify must be "strand" or "read_group", not {stratify!r}')
@@ -1618,6 +1716,26 @@ def _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity, ref_
     lengths = refs[:nr.value].copy()
     out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
                ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths)
+    return out
+
+
+def _read_bam_templates(path, min_length, min_mapq, split_spliced, include_secondary, capacity, ref_capacity=1 << 24):
+    names = ("starts", "ends", "contig_ids", "template_ids", "qualities", "seq_lengths")
+    cols = {k: np.empty(capacity, np.uint32) for k in names}
+    recs = np.empty(capacity, np.uint64)
+    filt = np.empty(capacity, np.uint64)
+    refs = np.empty(ref_capacity, np.uint32)
+    nf, nr, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    n = _host.qmcp_host_read_bam_templates(str(path).encode(), int(min_length), int(min_mapq), int(bool(split_spliced)),
+                                           int(bool(include_secondary)), capacity, *(_p32(cols[k]) for k in names),
+                                           _p64(recs), capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
+                                           C.byref(nr), C.byref(nt), err, 512)
+    if n < 0:
+        raise OSError(f"read_bam({path}, templates=True) failed ({n}): {err.value.decode(errors='replace')}")
+    out = {k: v[:n].copy() for k, v in cols.items()}
+    out.update(segment_records=recs[:n].copy(), filtered_out=filt[:nf.value].copy(), n_templates=int(nt.value),
+               contig_lengths=refs[:nr.value].copy())
     return out
 
 
@@ -1717,11 +1835,33 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
     return int(n_regions.value)
 
 
+def write_template_report(path, template_stats, records_written=None):
+    """downsample_bam(template_report=)'s TSV: the TemplateStats as stat<TAB>value lines (the per-stage arrays as
+    stage<j>_<name>), then one size<TAB>templates line per bin of the template-size histogram (1 .. 7, 8+)"""
+    ts = template_stats
+    k = ts.n_stages
+    with open(path, "w") as f:
+        f.write("#stat\tvalue\n")
+        if records_written is not None:
+            f.write(f"records_written\t{int(records_written)}\n")
+        f.write(f"templates_used\t{ts.n_templates_used}\ntemplates_kept\t{ts.n_templates_kept}\n")
+        f.write(f"segments_kept\t{ts.n_kept[k - 1] if k else 0}\nmax_template_size\t{ts.max_template_size}\n")
+        f.write(f"stages\t{k}\n")
+        for j in range(k):
+            for name in ("target", "n_selected", "n_kept", "capped_positions", "demand", "sweeps"):
+                f.write(f"stage{j + 1}_{name}\t{getattr(ts, name)[j]}\n")
+        f.write("#size\ttemplates\n")
+        for b, count in enumerate(ts.size_hist):
+            f.write(f"{b + 1 if b < 7 else '8+'}\t{count}\n")
+
+
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
                    per_reference=False, bed=None, tsv=None, amplicon_mode=None, amplicons_by_reference=False,
                    targets=None, target_padding=0, keep_off_target=False, report=None, report_bins=0, ladder=None,
                    ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None,
-                   track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None):
+                   track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None,
+                   template_aware=False, split_spliced=True, include_secondary=False, template_stages=None,
+                   template_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1774,8 +1914,48 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     credit the coverage of the mates already kept, so the output stays near max_coverage instead of near twice that.
     The output is written from the final mask, which holds whole pairs: no find_pairs follows.  Needs
     per_reference=True; not together with targets, report, track, ladder, stratify, dedup, profile, amplicon files or
-    "quasi-mcp-hip-quality" (ValueError).  False: nothing changes"""
+    "quasi-mcp-hip-quality" (ValueError).  False: nothing changes.
+    template_aware=True (BamApiConfig::template_aware, with split_spliced and include_secondary as in
+    read_bam(templates=True), and template_stages as pair_stages): one qmcp_hip_solve_templates_host call on the file's
+    segments -- single-end reads, pairs, split reads with their supplementary alignments and spliced reads are kept or
+    dropped as whole templates, and an intron gets no depth.  A record is written if and only if its template is kept;
+    no find_pairs follows.  template_report (a path): a TSV with the statistics, then one size<TAB>templates line per
+    bin of the template-size histogram (1 .. 7 and 8+).  Needs per_reference=True; not together with pair_aware or
+    anything pair_aware refuses (ValueError).  False: nothing changes"""
     _need_host()
+    if template_aware:
+        if not per_reference:
+            raise ValueError("template-aware downsampling needs per_reference=True")
+        for given, what in ((pair_aware, "pair_aware"), (targets, "targets"), (report, "a depth report"),
+                            (track is not None, "a depth track"), (ladder is not None, "a coverage ladder"),
+                            (stratify is not None, "stratify"), (dedup, "dedup"), (profile is not None, "a coverage profile")):
+            if given:
+                raise ValueError(f"template-aware downsampling does not go together with {what}")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("template-aware downsampling does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("template-aware downsampling does not take a solver that grades by quality")
+        tg = None if template_stages is None else np.array([int(t) for t in template_stages], dtype=np.uint32)
+        if tg is not None and tg.size == 0:
+            raise ValueError("template_stages must hold at least one target (or be None for the default schedule)")
+        err = C.create_string_buffer(1024)
+        ts = TemplateStats()
+        n = _host.qmcp_host_downsample_bam_templates(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            1, int(bool(split_spliced)), int(bool(include_secondary)), _p32(tg), 0 if tg is None else tg.size, 0, None,
+            None, None, None, 0, None, 0, 0, None, None, 0, C.byref(ts), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        if template_report is not None:
+            write_template_report(template_report, ts, int(n))
+        return int(n)
+    if template_stages is not None or template_report is not None or not split_spliced or include_secondary:
+        raise ValueError("template_stages, template_report, split_spliced and include_secondary need template_aware=True")
     if pair_aware:
         if not per_reference:
             raise ValueError("pair-aware downsampling needs per_reference=True")

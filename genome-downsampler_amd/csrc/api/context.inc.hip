@@ -158,6 +158,9 @@ struct qmcp_hip_ctx {
     // candidates' columns, input indices and keep mask, need[], and the counters (capped positions, demand, |S|)
     DevBuf pr_in, pr_rest, pr_words, pr_spine, pr_offs[2], pr_poff, pr_credit, pr_cspine, pr_starts, pr_ends, pr_orig,
         pr_mask, pr_need, pr_stat;
+    // template-aware solves (api/templates.inc.hip): the host entry's id column, the bitset of template ids a completion
+    // goes through, the segments per template, and the counters (size histogram, templates in use, largest, kept, error)
+    DevBuf tp_ids, tp_flags, tp_sizes, tp_stat;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

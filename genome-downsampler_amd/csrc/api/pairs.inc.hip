@@ -12,14 +12,23 @@
 //      max(0, T_j - credit[p])); its counters come back before the sweep is queued, and a batch that asks for nothing
 //      queues none
 //   5. k_expand_mask_reads ORs the kept candidates into S
-// and after the last batch k_complete_pairs over S and its popcount.  A batch without candidates stops after step 2.
+// and after the last batch the completion (a UnitCompletion: k_complete_pairs here) over S and its popcount.  A batch
+// without candidates stops after step 2.
 // Buffers: all the feature's own (pr_*), apart from the by-contig call's gathered columns (bc_starts / bc_ends), which
 // are refilled per batch; nothing a solve owns is held across a solve.
 namespace {
 
+// how a stage's kept set S is completed to whole units: queues S |= the rest of every unit S touches, and |S| ->
+// pr_stat[2].  The pairs entry ORs inside each aligned bit pair; api/templates.inc.hip goes through a bitset of ids.
+struct UnitCompletion {
+    virtual int complete_and_count(qmcp_hip_ctx* c, uint64_t* d_mask, uint64_t n64) = 0;
+    virtual ~UnitCompletion() = default;
+};
+
 struct PairRun {
     std::vector<uint32_t> targets;
     qmcp_hip_pair_stats ps;
+    UnitCompletion* completion = nullptr;  // set by the entry, for the length of its call
 };
 
 // need[] of a stage after the first: the credit of the reads already kept, through k_pair_need
@@ -63,6 +72,12 @@ int pair_complete_and_count(qmcp_hip_ctx* c, uint64_t* d_mask, uint64_t n64) {
     return QMCP_OK;
 }
 
+struct PairCompletion : UnitCompletion {
+    int complete_and_count(qmcp_hip_ctx* c, uint64_t* d_mask, uint64_t n64) override {
+        return pair_complete_and_count(c, d_mask, n64);
+    }
+};
+
 int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
                       const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
                       const uint32_t* lengths, uint64_t n64, uint64_t* d_mask, const qmcp_hip_stats& first) {
@@ -91,7 +106,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
         return QMCP_OK;
     };
     TRY(begin());
-    TRY(pair_complete_and_count(c, d_mask, n64));
+    TRY(pr.completion->complete_and_count(c, d_mask, n64));
     HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
     TRY(wait());
     ps.n_kept[0] = count;
@@ -198,7 +213,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             HIP_TRY(hipGetLastError());
         }
         TRY(begin());
-        TRY(pair_complete_and_count(c, d_mask, n64));
+        TRY(pr.completion->complete_and_count(c, d_mask, n64));
         HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
         TRY(wait());
         ps.n_kept[j] = count;
@@ -206,10 +221,8 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
     return QMCP_OK;
 }
 
-// what both entries check before anything is copied or launched, and the schedule
-int check_pairs_call(uint64_t n_reads, const uint32_t* stages, uint32_t n_stages, uint32_t M, std::vector<uint32_t>& targets) {
-    if (n_reads & 1ull)
-        return fail(QMCP_EINVAL, "n_reads %llu is odd: reads (2q, 2q + 1) are pair q", (unsigned long long)n_reads);
+// the stage list of a staged call (pairs, templates), checked before anything is copied or launched, and the schedule
+int check_stage_list(const uint32_t* stages, uint32_t n_stages, uint32_t M, std::vector<uint32_t>& targets) {
     uint32_t bad = 0;
     const int rc = qmcp::pair_schedule(stages, n_stages, M, targets, &bad);
     if (rc == QMCP_OK) return QMCP_OK;
@@ -225,10 +238,19 @@ int check_pairs_call(uint64_t n_reads, const uint32_t* stages, uint32_t n_stages
     return fail(QMCP_EINVAL, "the last stage must be max_coverage: stages[%u] = %u, max_coverage = %u", bad, stages[bad], M);
 }
 
+// what both pair entries check first
+int check_pairs_call(uint64_t n_reads, const uint32_t* stages, uint32_t n_stages, uint32_t M, std::vector<uint32_t>& targets) {
+    if (n_reads & 1ull)
+        return fail(QMCP_EINVAL, "n_reads %llu is odd: reads (2q, 2q + 1) are pair q", (unsigned long long)n_reads);
+    return check_stage_list(stages, n_stages, M, targets);
+}
+
 int solve_pairs_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                           uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const std::vector<uint32_t>& targets,
                           uint64_t* d_mask, qmcp_hip_stats* stats, qmcp_hip_pair_stats* pstats) {
     PairRun pr;
+    PairCompletion mates;
+    pr.completion = &mates;
     pr.targets = targets;
     std::memset(&pr.ps, 0, sizeof(pr.ps));
     pr.ps.n_stages = (uint32_t)targets.size();

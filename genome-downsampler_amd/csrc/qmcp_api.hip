@@ -65,6 +65,8 @@
 //                       solve on the sort-based mixed route with need(p) = min(cov(p), cap(p)) built on the device
 //   pairs               pair-aware downsampling: the by-contig solve at a first target, then stages over all batches that
 //                       credit the depth of the pairs already kept and top up among the other reads on the capped route
+//   templates           the pair-aware stages with the unit generalised: every segment that carries one template id
+//                       (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
@@ -85,3 +87,4 @@
 #include "api/dedup.inc.hip"
 #include "api/profile.inc.hip"
 #include "api/pairs.inc.hip"
+#include "api/templates.inc.hip"

@@ -426,5 +426,17 @@ void launch_pair_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff
                       uint32_t target, uint32_t* need, unsigned long long* pstat);
 void launch_pair_count_bits(hipStream_t st, const uint64_t* mask, uint32_t n_words, unsigned long long* count);
 
+// template-aware downsampling (kernels/templates.inc.hip; api/templates.inc.hip drives them): ids holds one template id
+// per segment, n <= 2^31.  Once per call: err |= 1 for an id >= n_templates, sizes[id] (n_templates zeroed words) counts
+// the segments, tstat (10 zeroed counters) takes the size histogram [0 .. 7], the templates in use [8] and the largest
+// size [9].  Per completion: flags (ceil(n_templates / 32) zeroed words) |= the ids of the segments set in mask; then
+// mask = the segments whose template is flagged, whole words stored, no bit at or beyond n, and *count += its set bits
+void launch_tpl_check_sizes(hipStream_t st, const uint32_t* ids, uint32_t n, uint32_t n_templates, uint32_t* err,
+                            uint32_t* sizes, unsigned long long* tstat);
+void launch_tpl_mark(hipStream_t st, const uint64_t* mask, const uint32_t* ids, uint32_t n, uint32_t n_templates,
+                     uint32_t* flags);
+void launch_tpl_spread(hipStream_t st, const uint32_t* ids, uint32_t n, uint32_t n_templates, const uint32_t* flags,
+                       uint64_t* mask, unsigned long long* count);
+
 }  // namespace qmcp
 #endif

@@ -50,6 +50,8 @@
 //                            flag, the cut-point scan over it, and the launchers of the capped mixed-span sweeps
 //   pairs                    pair-aware downsampling: the kept set's bits in a batch's grouped order and their complement,
 //                            the kept reads' depth as scanned events, need(p) = min(cov_rest(p), T - credit(p))
+//   templates                template-aware downsampling: id check and template sizes, and the completion of a kept set
+//                            through a bitset of template ids (mark, spread)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -91,5 +93,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/dedup.inc.hip"
 #include "kernels/profile.inc.hip"
 #include "kernels/pairs.inc.hip"
+#include "kernels/templates.inc.hip"
 
 }  // namespace qmcp

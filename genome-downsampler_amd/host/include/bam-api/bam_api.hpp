@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "bam-api/amplicon_set.hpp"
+#include "bam-api/bam_io.hpp"
 #include "bam-api/paired_reads.hpp"
 
 namespace bam_api {
@@ -85,6 +86,18 @@ struct BamApiConfig {
     // false: nothing changes.
     bool pair_aware = false;
     std::vector<std::uint32_t> pair_stages;
+    // Template-aware downsampling: the ingest is read_bam_templates (bam_io.hpp) -- one segment per aligned block of every
+    // record, a template = the accepted records of one QNAME -- and the solve QuasiMcpHipSolver::solve_templates /
+    // qmcp_hip_solve_templates_host: single-end reads, split reads with their supplementary alignments and spliced reads
+    // are kept or dropped as whole templates, and an intron gets no depth.  split_spliced: cut a record at every N of its
+    // CIGAR; include_secondary: take records with flag 0x100 instead of skipping them; template_stages: as pair_stages.
+    // A record is written when its template is kept; no find_pairs follows.  Needs per_reference; not together with
+    // pair_aware or anything pair_aware refuses (std::invalid_argument otherwise).  false: nothing changes, and the
+    // three other fields must be left at their defaults.
+    bool template_aware = false;
+    bool split_spliced = true;
+    bool include_secondary = false;
+    std::vector<std::uint32_t> template_stages;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -130,6 +143,13 @@ class BamApi {
     // BamApiConfig::pair_aware and pair_stages (empty: the default schedule)
     bool pair_aware() const { return pair_aware_; }
     const std::vector<std::uint32_t>& pair_stages() const { return pair_stages_; }
+    // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
+    // get_template_segments call, which also fills get_filtered_out_reads
+    bool template_aware() const { return template_aware_; }
+    const std::vector<std::uint32_t>& template_stages() const { return template_stages_; }
+    const TemplateSegments& get_template_segments();
+    // the records with these ids (sorted in place), copied from the input; number of records written
+    std::uint32_t write_records(const std::filesystem::path& output_filepath, std::vector<BAMReadId>& bam_ids) const;
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
@@ -165,6 +185,10 @@ class BamApi {
     bool dedup_ = false;
     bool pair_aware_ = false;
     std::vector<std::uint32_t> pair_stages_;
+    bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false;
+    std::vector<std::uint32_t> template_stages_;
+    TemplateSegments template_segments_;
+    bool are_segments_loaded_ = false;
     void read_bam_into(PairedReads& reads);
 };
 

@@ -49,6 +49,34 @@ struct BamIngestStats {
 bool read_bam(const std::filesystem::path& path, const BamFilters& filters, PairedReads& out,
               std::vector<BAMReadId>& filtered_out, BamIngestStats* stats, std::string* err);
 
+// Template-aware ingest (BamApiConfig::template_aware): every accepted record gives one segment per aligned block, and a
+// template is the set of accepted records that share a QNAME -- a single-end read, a pair, a split read with its
+// supplementary alignments, a spliced read and its mate.
+struct TemplateIngest {
+    std::uint32_t min_seq_length = 0;  // a template is dropped when any of its accepted MAPPED records has a shorter l_seq
+    std::uint32_t min_mapq = 0;        // ... or a lower MAPQ (the pair rule of read_bam, extended)
+    bool split_spliced = true;         // a record is cut at every N operation of its CIGAR; false: one segment per record
+    bool include_secondary = false;    // records with flag 0x100 are taken; false: skipped and listed in filtered_out
+};
+struct TemplateSegments {
+    // one entry per segment, in file order, a record's blocks left to right: the inclusive interval, the refID
+    // (QMCP_NO_CONTIG for an unmapped record: flag 0x4 or refID -1, one segment with start = end = 0), the template id,
+    // the record's MAPQ and l_seq, and the record's id (BAMReadId, the running number of the alignment in the file)
+    std::vector<std::uint32_t> starts, ends, contig_ids, template_ids, qualities, seq_lengths;
+    std::vector<BAMReadId> segment_records;
+    std::uint32_t n_templates = 0;     // ids are dense, in order of first appearance
+    std::vector<std::uint32_t> contig_lengths;
+    std::uint64_t records = 0;         // alignments in the file
+};
+// D stays inside its block (as rlen counts it in read_bam); a block is what lies between two N operations and consumes
+// reference.  A record whose in-place CIGAR is <l_seq>S<rlen>N and that carries a CG:B,I field takes its CIGAR from the
+// field (the long-CIGAR convention, SAM specification 4.2.2).  Every accepted record gives at least one segment: a mapped
+// record whose CIGAR consumes no reference gives [pos, pos].  Supplementary records (0x800) are taken.  filtered_out:
+// the records that are not in the segments (skipped secondaries, and the records of dropped templates), ascending.
+// false + *err on a malformed or unreadable file.
+bool read_bam_templates(const std::filesystem::path& path, const TemplateIngest& cfg, TemplateSegments& out,
+                        std::vector<BAMReadId>& filtered_out, std::string* err);
+
 // The header's references alone: names and lengths in header order.  false + *err on a malformed or unreadable file.
 bool read_bam_references(const std::filesystem::path& path, std::vector<std::string>& names,
                          std::vector<std::uint32_t>& lengths, std::string* err);

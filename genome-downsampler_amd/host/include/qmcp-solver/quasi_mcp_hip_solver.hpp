@@ -110,6 +110,12 @@ class QuasiMcpHipSolver : public Solver {
     // stage list (the library's message)
     std::unique_ptr<Solution> solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_pair_stats& last_pair_stats() const { return prstats_; }
+    // Template-aware downsampling for a BamApi built with BamApiConfig::template_aware: qmcp_hip_solve_templates_host on
+    // its segments under its template_stages (empty: the default schedule).  Returns the ids of the records whose
+    // template is kept (ascending) -- the caller writes them with BamApi::write_records, without find_pairs.
+    // std::invalid_argument for a BamApi without template_aware and a refused stage list (the library's message)
+    std::vector<bam_api::BAMReadId> solve_templates(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_template_stats& last_template_stats() const { return tpstats_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -134,6 +140,7 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_dedup_stats dstats_{};
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
+    qmcp_hip_template_stats tpstats_{};
     std::vector<std::uint64_t> dedup_hist_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves

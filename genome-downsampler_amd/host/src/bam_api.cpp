@@ -131,6 +131,31 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     } else if (!config.pair_stages.empty()) {
         throw std::invalid_argument("pair_stages need pair_aware");
     }
+    if (config.template_aware) {
+        if (!per_reference_)
+            throw std::invalid_argument("template-aware downsampling needs per_reference: its stages are solved one "
+                                        "reference at a time");
+        if (config.pair_aware) throw std::invalid_argument("template-aware downsampling does not take pair_aware");
+        if (!config.targets_filepath.empty())
+            throw std::invalid_argument("template-aware downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("template-aware downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("template-aware downsampling does not take a depth report");
+        if (!config.depth_track_filepath.empty())
+            throw std::invalid_argument("template-aware downsampling does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("template-aware downsampling does not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("template-aware downsampling does not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("template-aware downsampling does not take amplicon files");
+        template_aware_ = true;
+        split_spliced_ = config.split_spliced;
+        include_secondary_ = config.include_secondary;
+        template_stages_ = config.template_stages;
+    } else if (!config.template_stages.empty() || !config.split_spliced || config.include_secondary) {
+        throw std::invalid_argument("template_stages, split_spliced and include_secondary need template_aware");
+    }
     if (!config.depth_report_filepath.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a depth report needs per_reference: its rows are the references a per-reference "
@@ -212,6 +237,31 @@ void BamApi::read_bam_into(PairedReads& reads) {
         std::fprintf(stderr, "[ERROR] %s\n", err.c_str());
         std::exit(EXIT_FAILURE);
     }
+}
+
+const TemplateSegments& BamApi::get_template_segments() {
+    if (!are_segments_loaded_) {
+        if (!template_aware_) throw std::invalid_argument("segments need a BamApi built with BamApiConfig::template_aware");
+        TemplateIngest cfg;
+        cfg.min_seq_length = min_seq_length_;
+        cfg.min_mapq = min_mapq_;
+        cfg.split_spliced = split_spliced_;
+        cfg.include_secondary = include_secondary_;
+        std::string err;
+        if (!read_bam_templates(input_filepath_, cfg, template_segments_, filtered_out_reads_, &err)) {
+            std::fprintf(stderr, "[ERROR] %s\n", err.c_str());
+            std::exit(EXIT_FAILURE);
+        }
+        are_segments_loaded_ = true;
+    }
+    return template_segments_;
+}
+
+std::uint32_t BamApi::write_records(const std::filesystem::path& output_filepath, std::vector<BAMReadId>& bam_ids) const {
+    std::string err;
+    const std::uint32_t n = write_bam(input_filepath_, output_filepath, bam_ids, &err);
+    if (n == UINT32_MAX) { std::fprintf(stderr, "[ERROR] %s\n", err.c_str()); std::exit(EXIT_FAILURE); }
+    return n;
 }
 
 std::uint32_t BamApi::write_paired_reads(const std::filesystem::path& output_filepath,

@@ -498,7 +498,147 @@ bool record_read_group(const std::vector<unsigned char>& rec, std::string& value
     return false;
 }
 
+// The CIGAR a template-aware ingest reads: the record's own, or -- when that is <l_seq>S<rlen>N, the placeholder of the
+// long-CIGAR convention -- the values of its CG:B,I field.  The optional fields are walked as in record_read_group.
+// false for fields that run past the record's end or have an unknown type.
+bool record_cigar(const std::vector<unsigned char>& rec, std::vector<std::uint32_t>& cigar) {
+    const unsigned char* p = rec.data() + 4;
+    const std::size_t size = rec.size() - 4;
+    const std::size_t l_read_name = p[8], n_cigar = le16(p + 12), l_seq = le32(p + 16);
+    if (32u + l_read_name + 4u * n_cigar > size) return false;
+    const unsigned char* cg = p + 32 + l_read_name;
+    cigar.resize(n_cigar);
+    for (std::size_t k = 0; k < n_cigar; ++k) cigar[k] = le32(cg + 4 * k);
+    const bool placeholder = n_cigar == 2 && (cigar[0] & 0xF) == 4 && (cigar[0] >> 4) == l_seq && (cigar[1] & 0xF) == 3;
+    if (!placeholder) return true;
+    const std::size_t fixed_end = 32u + l_read_name + 4u * n_cigar + (l_seq + 1) / 2 + l_seq;
+    if (fixed_end > size) return false;
+    auto width = [](char t) -> std::size_t {
+        return t == 'A' || t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : t == 'i' || t == 'I' || t == 'f' ? 4 : 0;
+    };
+    const unsigned char* a = p + fixed_end;
+    const unsigned char* const end = p + size;
+    while (a + 3 <= end) {
+        const bool is_cg = a[0] == 'C' && a[1] == 'G';
+        const char type = (char)a[2];
+        a += 3;
+        if (type == 'Z' || type == 'H') {
+            while (a < end && *a != 0) ++a;
+            if (a >= end) return false;
+            ++a;
+        } else if (type == 'B') {
+            if (a + 5 > end) return false;
+            const char sub = (char)a[0];
+            const std::size_t w = width(sub), count = le32(a + 1);
+            a += 5;
+            if (w == 0 || sub == 'A' || count > (std::size_t)(end - a) / w) return false;
+            if (is_cg && sub == 'I' && count != 0) {
+                cigar.resize(count);
+                for (std::size_t k = 0; k < count; ++k) cigar[k] = le32(a + 4 * k);
+                return true;
+            }
+            a += count * w;
+        } else {
+            const std::size_t w = width(type);
+            if (w == 0 || a + w > end) return false;
+            a += w;
+        }
+    }
+    return a == end;  // (no CG field: the record's own CIGAR stands)
+}
+
 }  // namespace
+
+bool read_bam_templates(const std::filesystem::path& path, const TemplateIngest& cfg, TemplateSegments& out,
+                        std::vector<BAMReadId>& filtered_out, std::string* err) {
+    BgzfReader in;
+    if (!in.open(path)) return set_err(err, "could not open " + path.string());
+    BamHeader h;
+    if (!read_header(in, h, err)) return false;
+    if (h.n_ref == 0) return set_err(err, "BAM without a reference sequence");
+    out = TemplateSegments();
+    for (const auto& r : h.references) out.contig_lengths.push_back(r.second);
+    std::map<std::string, std::uint32_t> template_of;   // ids in order of first appearance, before any template is dropped
+    std::vector<bool> dropped;                           // by that id: a mapped record failed a filter
+    std::vector<bool> accepted;                          // by BAMReadId
+    std::vector<unsigned char> rec;
+    std::vector<std::uint32_t> cigar;
+    std::string qname, rec_err;
+    BAMReadId id = 0;
+    auto push = [&](std::uint64_t s, std::uint64_t e, std::uint32_t contig, std::uint32_t tpl, std::uint32_t q, std::uint32_t l) {
+        out.starts.push_back((std::uint32_t)s);
+        out.ends.push_back((std::uint32_t)e);
+        out.contig_ids.push_back(contig);
+        out.template_ids.push_back(tpl);
+        out.qualities.push_back(q);
+        out.seq_lengths.push_back(l);
+        out.segment_records.push_back(id);
+    };
+    for (; read_record(in, rec, &rec_err); ++id) {
+        const unsigned char* p = rec.data() + 4;
+        const std::int32_t ref_id = (std::int32_t)le32(p), pos = (std::int32_t)le32(p + 4);
+        const std::uint32_t l_read_name = p[8], mapq = p[9], flag = le16(p + 14), l_seq = le32(p + 16);
+        if (ref_id < -1 || ref_id >= (std::int64_t)h.references.size())
+            return set_err(err, "BAM record with a refID outside the header's references");
+        if (!record_cigar(rec, cigar)) return set_err(err, "BAM record with fields past its end");
+        accepted.push_back(false);
+        if ((flag & 0x100) && !cfg.include_secondary) continue;
+        accepted.back() = true;
+        qname.assign(reinterpret_cast<const char*>(p + 32), l_read_name ? l_read_name - 1 : 0);
+        const auto at = template_of.insert({qname, (std::uint32_t)template_of.size()});
+        const std::uint32_t tpl = at.first->second;
+        if (at.second) dropped.push_back(false);
+        if ((flag & 0x4) || ref_id < 0) {
+            push(0, 0, 0xFFFFFFFFu, tpl, mapq, l_seq);   // QMCP_NO_CONTIG
+            continue;
+        }
+        if (pos < 0) return set_err(err, "mapped BAM record with a negative position");
+        if (mapq < cfg.min_mapq || l_seq < cfg.min_seq_length) dropped[tpl] = true;
+        // the blocks: what lies between two N operations and consumes reference (M D = X)
+        std::uint64_t block_start = (std::uint64_t)pos, block_len = 0, rlen = 0;
+        std::size_t blocks = 0;
+        for (const std::uint32_t v : cigar) {
+            const std::uint32_t op = v & 0xF, len = v >> 4;
+            if (op == 0 || op == 2 || op == 7 || op == 8 || (op == 3 && !cfg.split_spliced)) {
+                block_len += len;
+            } else if (op == 3) {
+                if (block_len) { push(block_start, block_start + block_len - 1, (std::uint32_t)ref_id, tpl, mapq, l_seq); ++blocks; }
+                block_start += block_len + len;
+                block_len = 0;
+            }
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
+        }
+        if ((std::uint64_t)pos + rlen > 0xFFFFFFFFull) return set_err(err, "BAM record that ends beyond 2^32");
+        if (block_len) { push(block_start, block_start + block_len - 1, (std::uint32_t)ref_id, tpl, mapq, l_seq); ++blocks; }
+        if (blocks == 0) push((std::uint64_t)pos, (std::uint64_t)pos + (rlen ? rlen - 1 : 0), (std::uint32_t)ref_id, tpl, mapq, l_seq);
+    }
+    if (!rec_err.empty()) return set_err(err, rec_err);
+    out.records = id;
+    // dropped templates leave, the others are renumbered in their order of first appearance
+    std::vector<std::uint32_t> renumber(dropped.size(), 0xFFFFFFFFu);
+    std::uint32_t next = 0;
+    for (std::size_t t = 0; t < dropped.size(); ++t)
+        if (!dropped[t]) renumber[t] = next++;
+    out.n_templates = next;
+    std::size_t w = 0;
+    for (std::size_t i = 0; i < out.starts.size(); ++i) {
+        const std::uint32_t t = renumber[out.template_ids[i]];
+        if (t == 0xFFFFFFFFu) {
+            accepted[out.segment_records[i]] = false;
+            continue;
+        }
+        out.starts[w] = out.starts[i]; out.ends[w] = out.ends[i]; out.contig_ids[w] = out.contig_ids[i];
+        out.template_ids[w] = t; out.qualities[w] = out.qualities[i]; out.seq_lengths[w] = out.seq_lengths[i];
+        out.segment_records[w] = out.segment_records[i];
+        ++w;
+    }
+    for (auto* v : {&out.starts, &out.ends, &out.contig_ids, &out.template_ids, &out.qualities, &out.seq_lengths}) v->resize(w);
+    out.segment_records.resize(w);
+    filtered_out.clear();
+    for (BAMReadId b = 0; b < accepted.size(); ++b)
+        if (!accepted[b]) filtered_out.push_back(b);
+    return true;
+}
 
 bool read_bam(const std::filesystem::path& path, const BamFilters& filters, PairedReads& out,
               std::vector<BAMReadId>& filtered_out, BamIngestStats* stats, std::string* err) {

@@ -1064,6 +1064,105 @@ std::int64_t qmcp_host_downsample_bam_pairs(const char* solver_name, const char*
     }
 }
 
+// Template-aware ingest alone (BamApiConfig::template_aware; bam_api::read_bam_templates): the segments' columns (cap
+// entries each; segment_records: each segment's BAM record id), the skipped and dropped records (filtered_out, cap_f
+// entries), every reference's length and the number of templates.  Returns the number of segments; -2 when a capacity is
+// too small, -3 out of memory, -1 with the reader's message in err on a malformed or unreadable file.
+std::int64_t qmcp_host_read_bam_templates(const char* path, std::uint32_t min_len, std::uint32_t min_mapq,
+                                          int split_spliced, int include_secondary, std::uint64_t cap,
+                                          std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* contig_ids,
+                                          std::uint32_t* template_ids, std::uint32_t* qualities,
+                                          std::uint32_t* seq_lengths, std::uint64_t* segment_records, std::uint64_t cap_f,
+                                          std::uint64_t* filtered_out, std::uint64_t* n_filtered_out, std::uint64_t ref_cap,
+                                          std::uint32_t* ref_lengths, std::uint64_t* n_refs, std::uint64_t* n_templates,
+                                          char* err, std::size_t err_cap) {
+    try {
+        bam_api::TemplateIngest cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.split_spliced = split_spliced != 0;
+        cfg.include_secondary = include_secondary != 0;
+        bam_api::TemplateSegments seg;
+        std::vector<bam_api::BAMReadId> filtered;
+        std::string msg;
+        if (!bam_api::read_bam_templates(path, cfg, seg, filtered, &msg)) {
+            copy_err(msg, err, err_cap);
+            return -1;
+        }
+        const std::uint64_t n = seg.starts.size();
+        if (n > cap || filtered.size() > cap_f || seg.contig_lengths.size() > ref_cap) return -2;
+        for (std::uint64_t i = 0; i < n; ++i) {
+            starts[i] = seg.starts[i]; ends[i] = seg.ends[i]; contig_ids[i] = seg.contig_ids[i];
+            template_ids[i] = seg.template_ids[i]; qualities[i] = seg.qualities[i]; seq_lengths[i] = seg.seq_lengths[i];
+            segment_records[i] = seg.segment_records[i];
+        }
+        *n_filtered_out = filtered.size();
+        for (std::size_t i = 0; i < filtered.size(); ++i) filtered_out[i] = filtered[i];
+        *n_refs = seg.contig_lengths.size();
+        for (std::size_t k = 0; k < seg.contig_lengths.size(); ++k) ref_lengths[k] = seg.contig_lengths[k];
+        *n_templates = seg.n_templates;
+        return (std::int64_t)n;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    }
+}
+
+// The file-to-file flow with BamApiConfig::template_aware: one template-aware ingest, one qmcp_hip_solve_templates_host
+// call (QuasiMcpHipSolver::solve_templates) under `stages` (NULL or n_stages == 0: the default schedule), the records of
+// the kept templates written with BamApi::write_records -- NO find_pairs.  Everything pair_aware refuses, and pair_aware
+// itself, is handed to BamApiConfig as given so that it refuses it; a coverage profile and a solver that grades by
+// quality are refused here.  tstats (may be NULL) receives the call's qmcp_hip_template_stats.  Returns the number of
+// records written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the configuration is refused.
+std::int64_t qmcp_host_downsample_bam_templates(const char* solver_name, const char* in_path, const char* out_path,
+                                                const char* filtered_path, std::uint32_t max_coverage,
+                                                std::uint32_t min_len, std::uint32_t min_mapq, int per_reference,
+                                                int split_spliced, int include_secondary, const std::uint32_t* stages,
+                                                std::uint32_t n_stages, int pair_aware, const char* targets,
+                                                const char* report, const char* track,
+                                                const std::uint32_t* ladder_levels, std::uint32_t n_ladder_levels,
+                                                const char* stratify, int dedup, int profile, const char* bed,
+                                                const char* tsv, int amplicons_by_reference,
+                                                qmcp_hip_template_stats* tstats, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.template_aware = true;
+        cfg.split_spliced = split_spliced != 0;
+        cfg.include_secondary = include_secondary != 0;
+        if (stages != nullptr && n_stages) cfg.template_stages.assign(stages, stages + n_stages);
+        cfg.pair_aware = pair_aware != 0;
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (track && track[0]) cfg.depth_track_filepath = track;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
+        cfg.dedup = dedup != 0;
+        if (bed && bed[0]) cfg.bed_filepath = bed;
+        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        if (profile) throw std::invalid_argument("template-aware downsampling does not go together with a coverage profile");
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("template-aware downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no template-aware downsampling");
+        bam_api::BamApi api(in_path, cfg);
+        std::vector<bam_api::BAMReadId> kept = hip->solve_templates(max_coverage, api);
+        if (tstats) *tstats = hip->last_template_stats();
+        const std::uint32_t written = api.write_records(out_path, kept);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

@@ -902,6 +902,67 @@ int qmcp_hip_solve_pairs_device(qmcp_hip_ctx* ctx,
                                 uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                 qmcp_hip_pair_stats* pstats);
 
+/* Template-aware downsampling: the pair-aware staged solve with the unit of selection generalised from the reads
+ * (2q, 2q + 1) to every segment that carries one template id.  One entry then serves single-end reads (templates of one
+ * segment), pairs (two), long reads with supplementary alignments (every piece of a split read) and spliced reads (every
+ * aligned block of the read and of its mate, so that an intron gets no depth).
+ * Input: every row is a SEGMENT: one interval [start, end] on contig_id, or QMCP_NO_CONTIG; contig_lengths / n_contigs
+ * and limits as in qmcp_hip_solve_by_contig_host.  template_ids[i] < n_templates <= 2^32 - 1 names the segment's
+ * template.  The segments of a template may lie anywhere in the input and on any contigs, ids need not all be used, and
+ * n_reads (the number of segments) may be odd.  stages as in qmcp_hip_solve_pairs_host: T_1 < ... < T_k = max_coverage,
+ * k <= QMCP_PAIR_MAX_STAGES, NULL for {ceil(M / 2), M} ({1} for M = 1).
+ * Definition: that of qmcp_hip_solve_pairs_host word for word, with complete_pairs replaced by
+ *   complete_templates(S) = { i : some j in S has template_ids[j] == template_ids[i] }.
+ * Credit comes from placed segments only; an unplaced segment is never a candidate and enters only through its
+ * template.  Depth is counted per segment: two overlapping segments of one template count twice, as overlapping mates do
+ * in the pairs entry.  The result S_k is a keep mask in INPUT order that holds whole templates and whose depth is at
+ * least min(cov, max_coverage) everywhere.
+ * Identities: (1) template_ids[i] = i / 2 with n_reads even gives the mask and the per-stage statistics of
+ * qmcp_hip_solve_pairs_* for the same stages, bit for bit; (2) ids that are all distinct with the one stage
+ * {max_coverage} give the mask of qmcp_hip_solve_by_contig_* bit for bit; (3) one stage gives
+ * qmcp_hip_solve_by_contig_* at max_coverage followed by template completion.
+ * Not claimed: that S_k is minimum among whole-template solutions.
+ * Errors: the stage-list and max_coverage errors of qmcp_hip_solve_pairs_host, then template_ids == NULL or
+ * n_templates == 0 with n_reads > 0 (QMCP_EINVAL), all on the host before the context is looked at and before anything
+ * is copied.  An id >= n_templates is found on the device: QMCP_EINVAL with a message; the mask has been cleared by
+ * then, as in the by-contig entries, and the host entry does not write keep_mask_out.  Bad contig ids and bad reads as in
+ * qmcp_hip_solve_by_contig_host.
+ * stats (may be NULL) are stage 1's; tstats (may be NULL): the stages and the templates.  The completion goes through a
+ * bitset of n_templates bits and a count per template (n_templates / 8 + 4 * n_templates bytes of device memory).  The
+ * host entry leaves S_k in the context, for qmcp_hip_kept_indices_host.  The device entry takes the four columns and the
+ * mask in device memory, is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the work
+ * has completed. */
+typedef struct qmcp_hip_template_stats {
+    uint32_t n_stages, reserved;
+    uint64_t n_selected[QMCP_PAIR_MAX_STAGES];        /* |K_j|, segments                                               */
+    uint64_t n_kept[QMCP_PAIR_MAX_STAGES];            /* |S_j|, segments, after completion                             */
+    uint64_t capped_positions[QMCP_PAIR_MAX_STAGES];  /* as in qmcp_hip_pair_stats                                     */
+    uint64_t demand[QMCP_PAIR_MAX_STAGES];
+    uint32_t target[QMCP_PAIR_MAX_STAGES];            /* T_j                                                           */
+    uint32_t sweeps[QMCP_PAIR_MAX_STAGES];
+    float ms_stage[QMCP_PAIR_MAX_STAGES];             /* device time of the stage's solves                             */
+    float ms_templates;                               /* everything the feature adds around the solves: id check, sizes,
+                                                         mask gather, compaction, credit, need, expansion, completion  */
+    uint32_t max_template_size;                       /* segments of the largest template                              */
+    uint64_t n_templates_used;                        /* templates with at least one segment                           */
+    uint64_t n_templates_kept;                        /* templates in S_k                                              */
+    uint64_t size_hist[8];                            /* templates of 1 .. 7 segments, and of 8 or more, over the
+                                                         templates with at least one segment                           */
+} qmcp_hip_template_stats;
+int qmcp_hip_solve_templates_host(qmcp_hip_ctx* ctx,
+                                  const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                  const uint32_t* template_ids, uint64_t n_reads, uint32_t n_templates,
+                                  const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                  const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                  uint64_t* keep_mask_out, qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats);
+int qmcp_hip_solve_templates_device(qmcp_hip_ctx* ctx,
+                                    const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                    const uint32_t* d_template_ids, uint64_t n_reads, uint32_t n_templates,
+                                    const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                    const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                    uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                    qmcp_hip_template_stats* tstats);
+
 #ifdef __cplusplus
 }
 #endif
