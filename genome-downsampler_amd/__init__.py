@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_profile_host", "qmcp_hip_solve_profile_device",
     "qmcp_hip_solve_pairs_host", "qmcp_hip_solve_pairs_device",
     "qmcp_hip_solve_templates_host", "qmcp_hip_solve_templates_device",
+    "qmcp_hip_solve_templates_profile_host", "qmcp_hip_solve_templates_profile_device",
 )
 
 QMCP_OK = 0
@@ -158,6 +159,16 @@ class TemplateStats(C.Structure):
                    n_templates_used=self.n_templates_used, n_templates_kept=self.n_templates_kept,
                    size_hist=list(self.size_hist))
         return out
+
+
+class TemplateProfileStats(C.Structure):
+    """qmcp_hip_template_profile_stats: the cap table of a template-aware solve under caps, the placed segments that
+    cover a position with a positive cap, the templates that own one, and the device time of the need kernels"""
+    _fields_ = [("positions_in_regions", C.c_uint64), ("n_segments_on_cap", C.c_uint64), ("n_templates_on_cap", C.c_uint64),
+                ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_need", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
 class DepthRow(C.Structure):
@@ -383,6 +394,14 @@ _hip.qmcp_hip_solve_templates_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, 
 _hip.qmcp_hip_solve_templates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                  C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
                                                  C.c_void_p, C.POINTER(Stats), C.POINTER(TemplateStats)]
+_hip.qmcp_hip_solve_templates_profile_host.argtypes = [
+    C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _u32p,
+    C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p, C.POINTER(Stats), C.POINTER(TemplateStats),
+    C.POINTER(TemplateProfileStats)]
+_hip.qmcp_hip_solve_templates_profile_device.argtypes = [
+    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p,
+    _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+    C.POINTER(TemplateStats), C.POINTER(TemplateProfileStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -480,6 +499,11 @@ if _host is not None:
                                                          C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                                          C.c_int, C.POINTER(TemplateStats), C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_templates.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_templates_profile.argtypes = [
+        C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _u32p,
+        C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, C.POINTER(TemplateStats),
+        C.POINTER(TemplateProfileStats), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_templates_profile.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -574,6 +598,7 @@ class Solver:
         self.last_dedup_stats = None
         self.last_pair_stats = None
         self.last_template_stats = None
+        self.last_template_profile_stats = None
 
     def close(self):
         if self._ctx:
@@ -974,6 +999,50 @@ class Solver:
                                                     C.c_void_p(stream), C.byref(st), C.byref(ts)))
         self.last_stats, self.last_template_stats = st, ts
         return st, ts
+
+    def solve_templates_profile(self, starts, ends, contig_ids, template_ids, n_templates, contig_lengths, max_coverage,
+                                default_cap, region_offsets=None, region_starts=None, region_ends=None, region_caps=None,
+                                stages=None, flags=0):
+        """template-aware downsampling under a cap table (qmcp_hip_solve_templates_profile_host): solve_templates'
+        segments and template ids, solve_profile's regions and default_cap.  Stage j of the schedule T_1 < ... < T_k =
+        max_coverage (None: ceil(M / 2), then M) runs under ceil(cap(p) * T_j / M), credits the depth of the templates
+        already kept and completes the templates again.  -> (mask, stats, template_stats, template_profile_stats): the
+        host keep bitmask in INPUT order (whole templates that cover min(cov(p), cap(p)) everywhere), stage 1's Stats,
+        the TemplateStats, the TemplateProfileStats.  Also left in last_stats / last_template_stats /
+        last_template_profile_stats"""
+        starts, ends, ids, tids = _u32(starts), _u32(ends), _u32(contig_ids), _u32(template_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n and tids.size == n, \
+            "starts, ends, contig_ids and template_ids must have one entry per segment"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ts, qs = Stats(), TemplateStats(), TemplateProfileStats()
+        _check(_hip.qmcp_hip_solve_templates_profile_host(
+            self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(tids), n, int(n_templates), _p32(lengths), lengths.size,
+            _p32(offs), _p32(r0), _p32(r1), _p32(caps), int(default_cap), int(flags), int(max_coverage), _p32(tg),
+            0 if tg is None else tg.size, _p64(mask), C.byref(st), C.byref(ts), C.byref(qs)))
+        self.last_stats, self.last_template_stats, self.last_template_profile_stats = st, ts, qs
+        return mask[:mask_words(n)], st, ts, qs
+
+    def solve_templates_profile_device(self, d_starts, d_ends, d_contig_ids, d_template_ids, n_reads, n_templates,
+                                       contig_lengths, max_coverage, default_cap, d_mask, region_offsets=None,
+                                       region_starts=None, region_ends=None, region_caps=None, stages=None, flags=0,
+                                       stream=0):
+        """solve_templates_profile on device pointers (ints); the input-order mask is written to d_mask.  -> (stats,
+        template_stats, template_profile_stats)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        st, ts, qs = Stats(), TemplateStats(), TemplateProfileStats()
+        _check(_hip.qmcp_hip_solve_templates_profile_device(
+            self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends), C.c_void_p(d_contig_ids), C.c_void_p(d_template_ids),
+            int(n_reads), int(n_templates), _p32(lengths), lengths.size, _p32(offs), _p32(r0), _p32(r1), _p32(caps),
+            int(default_cap), int(flags), int(max_coverage), _p32(tg), 0 if tg is None else tg.size, C.c_void_p(d_mask),
+            C.c_void_p(stream), C.byref(st), C.byref(ts), C.byref(qs)))
+        self.last_stats, self.last_template_stats, self.last_template_profile_stats = st, ts, qs
+        return st, ts, qs
 
     def _depth_call(self, entry, head, n, lengths, mask_arg, max_coverage, target_offsets, target_starts, target_ends,
                     padding, n_bins, tail):
@@ -1376,6 +1445,42 @@ def targets_from_bed(bed_path, reference_names):
     return offsets, t0, t1
 
 
+def targets_as_regions(target_offsets, target_starts, target_ends, contig_lengths, padding, cap):
+    """target regions (as targets_from_bed gives them: CSR per contig, inclusive bounds, any order, overlapping and
+    nested allowed) as a cap table for Solver.solve_profile / solve_templates_profile -> (offsets, starts, ends, caps):
+    per contig, by the rule of qmcp_hip_solve_targets_*, every region padded to [start - padding, end + padding] (the
+    start saturating at 0), clipped to [0, length - 1] (dropped when it begins at or beyond the contig's length), sorted,
+    overlapping and adjacent regions merged; every merged region carries `cap`.  ValueError for offsets that do not fit
+    the contigs, a region with start > end, or a cap outside [0, 2^31)"""
+    lengths = np.atleast_1d(np.asarray(contig_lengths, dtype=np.int64))
+    offs = np.atleast_1d(np.asarray(target_offsets, dtype=np.int64))
+    t0 = np.atleast_1d(np.asarray(target_starts, dtype=np.int64))
+    t1 = np.atleast_1d(np.asarray(target_ends, dtype=np.int64))
+    padding, cap = int(padding), int(cap)
+    if offs.size != lengths.size + 1 or offs[0] != 0 or np.any(np.diff(offs) < 0) or offs[-1] > min(t0.size, t1.size):
+        raise ValueError("target_offsets needs one entry per contig plus one, starting at 0 and never decreasing")
+    if np.any(t0[:offs[-1]] > t1[:offs[-1]]):
+        raise ValueError("a target region has start > end")
+    if padding < 0 or cap < 0 or cap >= 1 << 31:
+        raise ValueError("padding must not be negative and the cap must lie in [0, 2^31)")
+    out_offs, out0, out1 = [0], [], []
+    for c, length in enumerate(lengths.tolist()):
+        a = np.maximum(t0[offs[c]:offs[c + 1]] - padding, 0)
+        b = np.minimum(t1[offs[c]:offs[c + 1]] + padding, length - 1)
+        inside = a < length
+        order = np.argsort(a[inside], kind="stable")
+        first = len(out0)
+        for lo, hi in zip(a[inside][order].tolist(), b[inside][order].tolist()):
+            if len(out0) > first and lo <= out1[-1] + 1:
+                out1[-1] = max(out1[-1], hi)
+            else:
+                out0.append(lo)
+                out1.append(hi)
+        out_offs.append(len(out0))
+    u = lambda x: np.asarray(x, dtype=np.uint32)
+    return u(out_offs), u(out0), u(out1), np.full(len(out0), cap, dtype=np.uint32)
+
+
 def profile_from_bedgraph(path, reference_names):
     """a coverage profile from a bedGraph file (four columns: chrom start end cap) matched to references by name ->
     (offsets, starts, ends, caps) as Solver.solve_profile takes them: reference c owns regions
@@ -1529,15 +1634,20 @@ def write_bedgraph(path, runs, reference_names, channel="kept"):
     return int(first.size)
 
 
-def reference_names(path):
-    """the BAM header's reference names, in header order"""
+def _reference_table(path):
+    """the BAM header's references, in header order -> (names, lengths)"""
     _need_host()
     buf = C.create_string_buffer(1 << 24)
     lengths = np.empty(1 << 24, dtype=np.uint32)
     n = _host.qmcp_host_reference_names(str(path).encode(), buf, len(buf), _p32(lengths), lengths.size)
     if n < 0:
         raise OSError(f"reference_names({path}) failed ({n}): {buf.value.decode(errors='replace') if n == -1 else ''}")
-    return [x for x in buf.value.decode().split("\n") if x][:n]
+    return [x for x in buf.value.decode().split("\n") if x][:n], lengths[:n].copy()
+
+
+def reference_names(path):
+    """the BAM header's reference names, in header order"""
+    return _reference_table(path)[0]
 
 
 def bamapi_probe(starts, ends, ref_genome_length, ids, layout=0):
@@ -1835,9 +1945,11 @@ def check_targets_config(in_path, targets, per_reference=True, target_padding=0)
     return int(n_regions.value)
 
 
-def write_template_report(path, template_stats, records_written=None):
+def write_template_report(path, template_stats, records_written=None, template_profile_stats=None):
     """downsample_bam(template_report=)'s TSV: the TemplateStats as stat<TAB>value lines (the per-stage arrays as
-    stage<j>_<name>), then one size<TAB>templates line per bin of the template-size histogram (1 .. 7, 8+)"""
+    stage<j>_<name>), then one size<TAB>templates line per bin of the template-size histogram (1 .. 7, 8+).  With the
+    TemplateProfileStats of a call under a cap table: segments_on_cap, templates_on_cap, regions_in, regions_used and
+    positions_in_regions as well"""
     ts = template_stats
     k = ts.n_stages
     with open(path, "w") as f:
@@ -1846,6 +1958,11 @@ def write_template_report(path, template_stats, records_written=None):
             f.write(f"records_written\t{int(records_written)}\n")
         f.write(f"templates_used\t{ts.n_templates_used}\ntemplates_kept\t{ts.n_templates_kept}\n")
         f.write(f"segments_kept\t{ts.n_kept[k - 1] if k else 0}\nmax_template_size\t{ts.max_template_size}\n")
+        if template_profile_stats is not None:
+            qs = template_profile_stats
+            f.write(f"segments_on_cap\t{qs.n_segments_on_cap}\ntemplates_on_cap\t{qs.n_templates_on_cap}\n")
+            f.write(f"regions_in\t{qs.regions_in}\nregions_used\t{qs.regions_used}\n")
+            f.write(f"positions_in_regions\t{qs.positions_in_regions}\n")
         f.write(f"stages\t{k}\n")
         for j in range(k):
             for name in ("target", "n_selected", "n_kept", "capped_positions", "demand", "sweeps"):
@@ -1861,7 +1978,7 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None,
                    track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None,
                    template_aware=False, split_spliced=True, include_secondary=False, template_stages=None,
-                   template_report=None):
+                   template_report=None, template_targets=None, template_target_padding=0, template_profile=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -1921,8 +2038,22 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     dropped as whole templates, and an intron gets no depth.  A record is written if and only if its template is kept;
     no find_pairs follows.  template_report (a path): a TSV with the statistics, then one size<TAB>templates line per
     bin of the template-size histogram (1 .. 7 and 8+).  Needs per_reference=True; not together with pair_aware or
-    anything pair_aware refuses (ValueError).  False: nothing changes"""
+    anything pair_aware refuses (ValueError).  False: nothing changes.
+    template_targets (a BED3+ file, with template_target_padding) or template_profile (a bedGraph file), with
+    template_aware=True and per_reference=True: whole templates under a cap per region -- one
+    qmcp_hip_solve_templates_profile_host call.  template_targets: the cap is max_coverage inside the targets (padded,
+    clipped and merged by targets_as_regions) and 0 outside, so reads off target come out only as part of a template that
+    is kept for its depth on target.  template_profile: the caps of profile_from_bedgraph, max_coverage elsewhere.
+    max_coverage is the scale of template_stages in both.  template_report then also lists segments_on_cap,
+    templates_on_cap, regions_in, regions_used and positions_in_regions.  Not both at once, and not with anything
+    template_aware refuses -- targets= and profile= included (ValueError).  None: nothing changes"""
     _need_host()
+    if (template_targets is not None or template_profile is not None) and not (template_aware and per_reference):
+        raise ValueError("template_targets and template_profile need template_aware=True and per_reference=True")
+    if template_targets is not None and template_profile is not None:
+        raise ValueError("template_targets and template_profile do not go together: give one table")
+    if template_target_padding and template_targets is None:
+        raise ValueError("template_target_padding needs template_targets")
     if template_aware:
         if not per_reference:
             raise ValueError("template-aware downsampling needs per_reference=True")
@@ -1939,12 +2070,31 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         if tg is not None and tg.size == 0:
             raise ValueError("template_stages must hold at least one target (or be None for the default schedule)")
         err = C.create_string_buffer(1024)
-        ts = TemplateStats()
-        n = _host.qmcp_host_downsample_bam_templates(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            1, int(bool(split_spliced)), int(bool(include_secondary)), _p32(tg), 0 if tg is None else tg.size, 0, None,
-            None, None, None, 0, None, 0, 0, None, None, 0, C.byref(ts), err, 1024)
+        ts, qs = TemplateStats(), None
+        if template_targets is not None or template_profile is not None:
+            if int(template_target_padding) < 0:
+                raise ValueError("template_target_padding must not be negative")
+            names, ref_lengths = _reference_table(in_path)
+            if template_targets is not None:
+                table = targets_as_regions(*targets_from_bed(template_targets, names), ref_lengths,
+                                           int(template_target_padding), int(max_coverage))
+                default_cap = 0
+            else:
+                table = profile_from_bedgraph(template_profile, names)
+                default_cap = int(max_coverage)
+            qs = TemplateProfileStats()
+            n = _host.qmcp_host_downsample_bam_templates_profile(
+                solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+                str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length),
+                int(min_mapq), 1, int(bool(split_spliced)), int(bool(include_secondary)), _p32(tg),
+                0 if tg is None else tg.size, _p32(table[0]), _p32(table[1]), _p32(table[2]), _p32(table[3]), len(names),
+                default_cap, C.byref(ts), C.byref(qs), err, 1024)
+        else:
+            n = _host.qmcp_host_downsample_bam_templates(
+                solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+                str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+                1, int(bool(split_spliced)), int(bool(include_secondary)), _p32(tg), 0 if tg is None else tg.size, 0, None,
+                None, None, None, 0, None, 0, 0, None, None, 0, C.byref(ts), err, 1024)
         if n == -4:
             raise ValueError(err.value.decode())
         if n == -1:
@@ -1952,7 +2102,7 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         if n < 0:
             raise OSError(f"downsample_bam({in_path}) failed ({n})")
         if template_report is not None:
-            write_template_report(template_report, ts, int(n))
+            write_template_report(template_report, ts, int(n), qs)
         return int(n)
     if template_stages is not None or template_report is not None or not split_spliced or include_secondary:
         raise ValueError("template_stages, template_report, split_spliced and include_secondary need template_aware=True")

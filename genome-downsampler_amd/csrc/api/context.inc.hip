@@ -161,6 +161,10 @@ struct qmcp_hip_ctx {
     // template-aware solves (api/templates.inc.hip): the host entry's id column, the bitset of template ids a completion
     // goes through, the segments per template, and the counters (size histogram, templates in use, largest, kept, error)
     DevBuf tp_ids, tp_flags, tp_sizes, tp_stat;
+    // template-aware solves under a cap table (api/templates_profile.inc.hip): a later stage's scaled regions of a batch
+    // (starts | ends | caps), the call's table for the on-cap pass (offsets | starts | ends | caps | positive positions
+    // before), the bitset of templates that touch a positive cap, and the two on-cap counters (segments, templates)
+    DevBuf tq_tab, tq_cap, tq_flags, tq_stat;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

@@ -9,8 +9,8 @@
 //      once; k_ladder_compact: their starts, ends and input indices
 //   3. k_pair_credit_events on a zeroed axis, scanned in place: credit[p], the depth of the batch's reads in S
 //   4. capped_solve_batch (api/profile.inc.hip) on the candidates with k_pair_need building need[p] = min(cov_rest(p),
-//      max(0, T_j - credit[p])); its counters come back before the sweep is queued, and a batch that asks for nothing
-//      queues none
+//      max(0, T_j - credit[p])) -- or whatever StageNeed the entry's StageNeeds hands out; its counters come back before
+//      the sweep is queued, and a batch that asks for nothing queues none
 //   5. k_expand_mask_reads ORs the kept candidates into S
 // and after the last batch the completion (a UnitCompletion: k_complete_pairs here) over S and its popcount.  A batch
 // without candidates stops after step 2.
@@ -25,34 +25,61 @@ struct UnitCompletion {
     virtual ~UnitCompletion() = default;
 };
 
-struct PairRun {
-    std::vector<uint32_t> targets;
-    qmcp_hip_pair_stats ps;
-    UnitCompletion* completion = nullptr;  // set by the entry, for the length of its call
-};
-
-// need[] of a stage after the first: the credit of the reads already kept, through k_pair_need
-struct PairNeed : CappedNeed {
-    uint32_t target;
+// need[] of a stage after the first: built over the candidates from the credit of the reads already kept; need[] lives
+// in pr_need, the two counters in pr_stat[0 .. 1]
+struct StageNeed : CappedNeed {
     unsigned long long counters[2] = {0, 0};  // capped positions, demand: this batch's
-    explicit PairNeed(uint32_t t) : target(t) {}
-    const char* name() const override { return "k_pair_need"; }
     DevBuf& need_buf(qmcp_hip_ctx* c) override { return c->pr_need; }
     int reserve(qmcp_hip_ctx*) override { return QMCP_OK; }
     int upload(qmcp_hip_ctx* c, hipStream_t st) override {
         HIP_TRY(hipMemsetAsync(c->pr_stat.p, 0, 2 * sizeof(unsigned long long), st));
         return QMCP_OK;
     }
-    void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
-        qmcp::launch_pair_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
-                               (const uint32_t*)c->pr_credit.p + qmcp::pair_credit_pad(), ltot, target, need,
-                               (unsigned long long*)c->pr_stat.p);
-    }
     int no_demand(qmcp_hip_ctx* c, hipStream_t st, bool* none) override {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(counters, c->pr_stat.p, sizeof(counters), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         *none = counters[1] == 0;
+        return QMCP_OK;
+    }
+};
+
+// one target everywhere, through k_pair_need
+struct PairNeed : StageNeed {
+    uint32_t target;
+    explicit PairNeed(uint32_t t) : target(t) {}
+    const char* name() const override { return "k_pair_need"; }
+    void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
+        qmcp::launch_pair_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
+                               (const uint32_t*)c->pr_credit.p + qmcp::pair_credit_pad(), ltot, target, need,
+                               (unsigned long long*)c->pr_stat.p);
+    }
+};
+
+// What gives stage j (>= 1) of a batch its StageNeed, and the largest cap that need can meet: it chooses the sweep's
+// windows, and a batch whose largest cap is 0 is skipped before its gather.  The pairs and templates entries ask for the
+// stage's target everywhere; api/templates_profile.inc.hip scales the batch's region table to the stage.
+struct StageNeeds {
+    virtual ~StageNeeds() = default;
+    // the returned object lives until the next call
+    virtual int make(qmcp_hip_ctx* c, uint32_t j, const qmcp::ContigBatch& bt, StageNeed** need, uint32_t* max_cap) = 0;
+};
+
+struct PairRun {
+    std::vector<uint32_t> targets;
+    qmcp_hip_pair_stats ps;
+    UnitCompletion* completion = nullptr;  // set by the entry, for the length of its call
+    StageNeeds* needs = nullptr;           // set by the entry, for the length of its call
+};
+
+struct TargetNeeds : StageNeeds {
+    const std::vector<uint32_t>& targets;
+    PairNeed nd{0};
+    explicit TargetNeeds(const std::vector<uint32_t>& t) : targets(t) {}
+    int make(qmcp_hip_ctx*, uint32_t j, const qmcp::ContigBatch&, StageNeed** need, uint32_t* max_cap) override {
+        nd = PairNeed(targets[j]);
+        *need = &nd;
+        *max_cap = targets[j];
         return QMCP_OK;
     }
 };
@@ -114,10 +141,13 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
     std::vector<uint32_t> offs32, poff32, ranks;
     std::vector<uint64_t> roff, cand_roff;
     for (uint32_t j = 1; j < (uint32_t)pr.targets.size(); ++j) {
-        const uint32_t target = pr.targets[j];
         for (size_t b = 0; b < batches.size(); ++b) {
             const qmcp::ContigBatch& bt = batches[b];
             if (bt.n_reads == 0) continue;
+            StageNeed* need = nullptr;
+            uint32_t max_cap = 0;
+            TRY(pr.needs->make(c, j, bt, &need, &max_cap));
+            if (max_cap == 0) continue;  // nothing can be asked for anywhere in this batch
             const uint32_t nb = (uint32_t)bt.n_reads;
             const uint32_t ltot = (uint32_t)bt.positions;
             const uint32_t words = (nb + 63u) / 64u;
@@ -191,11 +221,11 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             HIP_TRY(hipEventRecord(ev_b.b, st));
             HIP_TRY(hipGetLastError());
             // 4: the capped route on the candidates
-            PairNeed nd(target);
+            StageNeed& nd = *need;
             qmcp_hip_stats bs;
             std::memset(&bs, 0, sizeof(bs));
             bool swept = false;
-            TRY(capped_solve_batch(c, nd, target, (const uint32_t*)c->pr_starts.p, (const uint32_t*)c->pr_ends.p,
+            TRY(capped_solve_batch(c, nd, max_cap, (const uint32_t*)c->pr_starts.p, (const uint32_t*)c->pr_ends.p,
                                    cand_roff.data(), lengths + bt.first_contig, bt.n_contigs, n_c, (uint64_t*)c->pr_mask.p, &bs,
                                    &swept));
             ps.ms_pairs += elapsed(ev_b.a, ev_b.b) + nd.ms;
@@ -250,7 +280,9 @@ int solve_pairs_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
                           uint64_t* d_mask, qmcp_hip_stats* stats, qmcp_hip_pair_stats* pstats) {
     PairRun pr;
     PairCompletion mates;
+    TargetNeeds needs(targets);
     pr.completion = &mates;
+    pr.needs = &needs;
     pr.targets = targets;
     std::memset(&pr.ps, 0, sizeof(pr.ps));
     pr.ps.n_stages = (uint32_t)targets.size();

@@ -7,6 +7,8 @@
 //      completion step: the bitset cleared, k_tpl_mark (flags |= the ids of S), k_tpl_spread (S = the segments of flagged
 //      templates, and |S|)
 //   3. after the last stage the bitset still holds the kept templates: its popcount is n_templates_kept
+// api/templates_profile.inc.hip runs the same call under a cap per region: it hands in the StageNeeds of the later
+// stages and the ProfileRun of the first.
 // Buffers: the feature's own (tp_*) and the pair stages' (pr_*).
 namespace {
 
@@ -59,13 +61,16 @@ void copy_stage_stats(qmcp_hip_template_stats& ts, const qmcp_hip_pair_stats& ps
 int solve_templates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                               const uint32_t* d_tids, uint64_t n64, uint32_t n_templates, const uint32_t* lengths,
                               uint32_t n_contigs, const std::vector<uint32_t>& targets, uint64_t* d_mask,
-                              qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats) {
+                              qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats, StageNeeds* capped_needs = nullptr,
+                              ProfileRun* first_stage = nullptr /* then its default_cap is stage 1's plain cap */) {
     hipStream_t st = c->stream;
     qmcp_hip_template_stats ts;
     std::memset(&ts, 0, sizeof(ts));
     PairRun pr;
     TemplateCompletion whole(d_tids, n_templates);
+    TargetNeeds needs(targets);  // (a reference and one PairNeed: nothing to pay where capped_needs takes its place)
     pr.completion = &whole;
+    pr.needs = capped_needs ? capped_needs : &needs;
     pr.targets = targets;
     std::memset(&pr.ps, 0, sizeof(pr.ps));
     pr.ps.n_stages = (uint32_t)targets.size();
@@ -110,8 +115,11 @@ int solve_templates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
     // 2: the stages
     qmcp_hip_stats plain;
     std::memset(&plain, 0, sizeof(plain));
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, targets[0], d_mask, &plain, nullptr,
-                                  nullptr, &pr));
+    // with a ProfileRun the by-contig call reads this argument as the default cap outside the regions (as
+    // solve_profile_on_device passes it), and 0 is legal there: profile_solve_batch then keeps nothing outside regions
+    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs,
+                                  first_stage ? first_stage->default_cap : targets[0], d_mask, &plain, nullptr, first_stage,
+                                  &pr));
     copy_stage_stats(ts, pr.ps);
     ts.ms_templates += pr.ps.ms_pairs;
 

@@ -97,5 +97,28 @@ inline void batch_cap_table(const CapTable& t, const uint32_t* lengths, uint32_t
     }
 }
 
+// A staged solve under a cap table (api/templates_profile.inc.hip) runs stage T of a schedule that ends at M under
+// ceil(cap * T / M), in 64 bits: never above cap, cap itself at T == M, T where cap == M, and 0 only where cap is 0.
+inline uint32_t scale_cap(uint32_t cap, uint32_t T, uint32_t M) {
+    return (uint32_t)(((uint64_t)cap * T + M - 1) / M);
+}
+
+// before[k], per kept region: the positions below rs[k] of its contig whose cap is positive -- F(rs[k]) of the prefix
+// count F(x) = |{ p < x : cap(p) > 0 }| that k_tpl_on_cap evaluates at a segment's two ends.  Between two region borders
+// F is linear, so the values at the borders are all the kernel needs.  (A contig holds fewer than 2^31 positions.)
+inline void cap_positive_before(const CapTable& t, uint32_t default_cap, std::vector<uint32_t>& before) {
+    before.assign(t.rs.size(), 0);
+    const size_t n_contigs = t.offs.size() - 1;
+    for (size_t c = 0; c < n_contigs; ++c) {
+        uint32_t f = 0, x = 0;  // f = F(x)
+        for (uint32_t k = t.offs[c]; k < t.offs[c + 1]; ++k) {
+            if (default_cap != 0) f += t.rs[k] - x;
+            before[k] = f;
+            if (t.cap[k] != 0) f += t.re[k] - t.rs[k] + 1;
+            x = t.re[k] + 1;
+        }
+    }
+}
+
 }  // namespace qmcp
 #endif

@@ -22,16 +22,21 @@ __device__ __forceinline__ uint32_t profile_first_region(const uint32_t* re, uin
     return a;
 }
 
-// kLds: the table in LDS ([rs | re | cap], n_regions each), else read from global memory.
-// A thread takes four consecutive positions at a time (16-byte loads of boff and eoff, one 16-byte store of need; the
-// arrays are arena buffers, 256-byte aligned, and groups start at multiples of four); the last positions of the axis
-// go one by one.  pstat: [0] positions with cov > cap, [1] the sum of need -- one atomic each per workgroup.
-template <bool kLds>
-__global__ __launch_bounds__(256) void k_profile_need(const uint32_t* __restrict__ boff, const uint32_t* __restrict__ eoff,
-                                                      uint32_t ltot, const uint32_t* __restrict__ g_rs,
-                                                      const uint32_t* __restrict__ g_re, const uint32_t* __restrict__ g_cap,
-                                                      uint32_t n_regions, uint32_t default_cap, uint32_t* __restrict__ need,
-                                                      unsigned long long* __restrict__ pstat) {
+// The one pass behind k_profile_need and k_tpl_profile_need (kernels/templates_profile.inc.hip).
+// kLds: the table in LDS ([rs | re | cap], n_regions each), else read from global memory.  kCredit: the cap of a
+// position is what its region (or default_cap) leaves above credit[p] -- max(0, cap - credit[p]) -- and cov is the
+// candidates' coverage; without it credit is not read.
+// A thread takes four consecutive positions at a time (16-byte loads of boff, eoff and, with kCredit, credit, one 16-byte
+// store of need; the arrays are arena buffers, 256-byte aligned -- credit from its 16-byte aligned entry on -- and groups
+// start at multiples of four); the last positions of the axis go one by one.  pstat: [0] positions with cov > cap,
+// [1] the sum of need -- one atomic each per workgroup.
+template <bool kLds, bool kCredit>
+__device__ __forceinline__ void profile_need_pass(const uint32_t* __restrict__ boff, const uint32_t* __restrict__ eoff,
+                                                  const uint32_t* __restrict__ credit, uint32_t ltot,
+                                                  const uint32_t* __restrict__ g_rs, const uint32_t* __restrict__ g_re,
+                                                  const uint32_t* __restrict__ g_cap, uint32_t n_regions,
+                                                  uint32_t default_cap, uint32_t* __restrict__ need,
+                                                  unsigned long long* __restrict__ pstat) {
     extern __shared__ uint32_t s_cap_tab[];
     __shared__ unsigned long long s_acc[2];
     const uint32_t* rs = g_rs;
@@ -55,15 +60,23 @@ __global__ __launch_bounds__(256) void k_profile_need(const uint32_t* __restrict
     unsigned long long demand = 0;
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n_groups; g += stride) {
         const uint32_t p0 = 4u * g;
-        uint32_t cov[4];
+        uint32_t cov[4], cr[4] = {0u, 0u, 0u, 0u};
         const bool whole = p0 + 3u < ltot;  // (then boff[p0 + 4] exists: boff has ltot + 1 entries)
         if (whole) {
             const uint4 b = *(const uint4*)(boff + p0), e = *(const uint4*)(eoff + p0);
             const uint32_t b4 = boff[p0 + 4];
             cov[0] = b.y - e.x; cov[1] = b.z - e.y; cov[2] = b.w - e.z; cov[3] = b4 - e.w;  // cov(p) = boff[p + 1] - eoff[p]
+            if constexpr (kCredit) {
+                const uint4 c = *(const uint4*)(credit + p0);
+                cr[0] = c.x; cr[1] = c.y; cr[2] = c.z; cr[3] = c.w;
+            }
         } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) cov[r] = p0 + r < ltot ? boff[p0 + r + 1] - eoff[p0 + r] : 0u;
+            for (int r = 0; r < 4; ++r) {
+                const bool in = p0 + r < ltot;
+                cov[r] = in ? boff[p0 + r + 1] - eoff[p0 + r] : 0u;
+                if constexpr (kCredit) cr[r] = in ? credit[p0 + r] : 0u;
+            }
         }
         uint32_t k = profile_first_region(re, n_regions, p0);
         uint32_t out[4];
@@ -71,7 +84,8 @@ __global__ __launch_bounds__(256) void k_profile_need(const uint32_t* __restrict
         for (int r = 0; r < 4; ++r) {
             const uint32_t p = p0 + (uint32_t)r;
             while (k < n_regions && re[k] < p) ++k;
-            const uint32_t cap = (k < n_regions && rs[k] <= p) ? cp[k] : default_cap;
+            uint32_t cap = (k < n_regions && rs[k] <= p) ? cp[k] : default_cap;
+            if constexpr (kCredit) cap = cap > cr[r] ? cap - cr[r] : 0u;
             const uint32_t nd = min(cov[r], cap);
             out[r] = nd | (cov[r] <= cap ? kNeedCutBit : 0u);
             if (p < ltot) {
@@ -97,8 +111,17 @@ __global__ __launch_bounds__(256) void k_profile_need(const uint32_t* __restrict
     __syncthreads();
     if (threadIdx.x == 0 && (s_acc[0] | s_acc[1]) != 0) {
         if (s_acc[0]) atomicAdd(&pstat[0], s_acc[0]);
-        atomicAdd(&pstat[1], s_acc[1]);
+        if (!kCredit || s_acc[1]) atomicAdd(&pstat[1], s_acc[1]);
     }
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(256) void k_profile_need(const uint32_t* __restrict__ boff, const uint32_t* __restrict__ eoff,
+                                                      uint32_t ltot, const uint32_t* __restrict__ g_rs,
+                                                      const uint32_t* __restrict__ g_re, const uint32_t* __restrict__ g_cap,
+                                                      uint32_t n_regions, uint32_t default_cap, uint32_t* __restrict__ need,
+                                                      unsigned long long* __restrict__ pstat) {
+    profile_need_pass<kLds, false>(boff, eoff, nullptr, ltot, g_rs, g_re, g_cap, n_regions, default_cap, need, pstat);
 }
 
 // k_find_cuts with the profile's own rule: window w reports the first position q in it at which a stretch may start --

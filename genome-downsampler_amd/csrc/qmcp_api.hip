@@ -67,6 +67,8 @@
 //                       credit the depth of the pairs already kept and top up among the other reads on the capped route
 //   templates           the pair-aware stages with the unit generalised: every segment that carries one template id
 //                       (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
+//   templates_profile   the template stages under a cap per region: stage 1 is the profile's batches at the scaled
+//                       caps, later stages build need[] from the scaled region table and the credit
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
@@ -88,3 +90,4 @@
 #include "api/profile.inc.hip"
 #include "api/pairs.inc.hip"
 #include "api/templates.inc.hip"
+#include "api/templates_profile.inc.hip"

@@ -438,5 +438,21 @@ void launch_tpl_mark(hipStream_t st, const uint64_t* mask, const uint32_t* ids, 
 void launch_tpl_spread(hipStream_t st, const uint32_t* ids, uint32_t n, uint32_t n_templates, const uint32_t* flags,
                        uint64_t* mask, unsigned long long* count);
 
+// template-aware downsampling under a cap table (kernels/templates_profile.inc.hip; api/templates_profile.inc.hip drives
+// them).  launch_tpl_profile_need is launch_pair_need with the target replaced by a region table as launch_profile_need
+// takes it (the batch's regions in its global positions, ascending and disjoint, caps already scaled to the stage):
+// need[p] = min(cov_rest(p), max(0, cap(p) - credit[p])), the cut bit, the two counters.  launch_tpl_on_cap, once per
+// call over the segments in input order: roffs (n_contigs + 1) gives contig c the regions [roffs[c], roffs[c + 1]) of
+// rs / re / cap in contig positions, before[k] the positions below rs[k] of its contig whose cap is positive
+// (cap_table.h: cap_positive_before); a placed segment that covers a position with a positive cap sets its template's
+// bit in flags (ceil(n_templates / 32) zeroed words) and adds one to *count
+void launch_tpl_profile_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, const uint32_t* credit, uint32_t ltot,
+                             const uint32_t* rs, const uint32_t* re, const uint32_t* cap, uint32_t n_regions,
+                             uint32_t default_cap, uint32_t* need, unsigned long long* pstat);
+void launch_tpl_on_cap(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                       const uint32_t* tids, uint32_t n, uint32_t n_contigs, uint32_t n_templates, const uint32_t* roffs,
+                       const uint32_t* rs, const uint32_t* re, const uint32_t* cap, const uint32_t* before,
+                       bool default_positive, uint32_t* flags, unsigned long long* count);
+
 }  // namespace qmcp
 #endif

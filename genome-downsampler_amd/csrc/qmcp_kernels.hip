@@ -52,6 +52,8 @@
 //                            the kept reads' depth as scanned events, need(p) = min(cov_rest(p), T - credit(p))
 //   templates                template-aware downsampling: id check and template sizes, and the completion of a kept set
 //                            through a bitset of template ids (mark, spread)
+//   templates_profile        the template stages under a cap table: need(p) from the regions' scaled caps and the credit,
+//                            and the segments and templates that touch a positive cap
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -94,5 +96,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/profile.inc.hip"
 #include "kernels/pairs.inc.hip"
 #include "kernels/templates.inc.hip"
+#include "kernels/templates_profile.inc.hip"
 
 }  // namespace qmcp

@@ -116,6 +116,17 @@ class QuasiMcpHipSolver : public Solver {
     // std::invalid_argument for a BamApi without template_aware and a refused stage list (the library's message)
     std::vector<bam_api::BAMReadId> solve_templates(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_template_stats& last_template_stats() const { return tpstats_; }
+    // solve_templates under a cap per region: qmcp_hip_solve_templates_profile_host with the regions in CSR form per
+    // reference (as solve_profile takes them), default_cap outside them, and required_cover as the scale of the
+    // BamApi's template_stages.  Returns the ids of the records whose template is kept, as solve_templates does.
+    // std::invalid_argument in addition for a table of other references and for what the library refuses in the table
+    std::vector<bam_api::BAMReadId> solve_templates_profile(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                                            const std::vector<std::uint32_t>& offsets,
+                                                            const std::vector<std::uint32_t>& starts,
+                                                            const std::vector<std::uint32_t>& ends,
+                                                            const std::vector<std::uint32_t>& caps,
+                                                            std::uint32_t default_cap);
+    const qmcp_hip_template_profile_stats& last_template_profile_stats() const { return tqstats_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -141,6 +152,7 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_template_stats tpstats_{};
+    qmcp_hip_template_profile_stats tqstats_{};
     std::vector<std::uint64_t> dedup_hist_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves

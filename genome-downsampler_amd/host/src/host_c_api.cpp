@@ -1163,6 +1163,63 @@ std::int64_t qmcp_host_downsample_bam_templates(const char* solver_name, const c
     }
 }
 
+// The template-aware flow under a cap per region: one template-aware ingest, one qmcp_hip_solve_templates_profile_host
+// call (QuasiMcpHipSolver::solve_templates_profile) with the regions in CSR form per reference of the file (n_refs + 1
+// offsets, as qmcp_host_downsample_bam_profile takes them; the caller has matched chroms to references and made the
+// regions disjoint), default_cap outside them and max_coverage as the scale of `stages`; the records of the kept
+// templates written with BamApi::write_records -- NO find_pairs.  per_reference goes to BamApiConfig as given, so that it
+// refuses its absence; a solver that grades by quality and offsets for another number of references are refused here.
+// tstats / qstats (may be NULL) receive the call's statistics.  Returns the number of records written; -1 on an unknown
+// solver, -3 out of memory, -4 with a message in err when the configuration is refused.
+std::int64_t qmcp_host_downsample_bam_templates_profile(const char* solver_name, const char* in_path, const char* out_path,
+                                                        const char* filtered_path, std::uint32_t max_coverage,
+                                                        std::uint32_t min_len, std::uint32_t min_mapq, int per_reference,
+                                                        int split_spliced, int include_secondary,
+                                                        const std::uint32_t* stages, std::uint32_t n_stages,
+                                                        const std::uint32_t* region_offsets,
+                                                        const std::uint32_t* region_starts,
+                                                        const std::uint32_t* region_ends, const std::uint32_t* region_caps,
+                                                        std::uint64_t n_refs, std::uint32_t default_cap,
+                                                        qmcp_hip_template_stats* tstats,
+                                                        qmcp_hip_template_profile_stats* qstats, char* err,
+                                                        std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.template_aware = true;
+        cfg.split_spliced = split_spliced != 0;
+        cfg.include_secondary = include_secondary != 0;
+        if (stages != nullptr && n_stages) cfg.template_stages.assign(stages, stages + n_stages);
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("template-aware downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no template-aware downsampling");
+        if (region_offsets == nullptr) throw std::invalid_argument("a cap table needs its region offsets");
+        const std::uint32_t n_reg = region_offsets[n_refs];
+        if (n_reg && (!region_starts || !region_ends || !region_caps))
+            throw std::invalid_argument("a cap table with regions needs their starts, ends and caps");
+        bam_api::BamApi api(in_path, cfg);
+        const std::vector<std::uint32_t> offs(region_offsets, region_offsets + n_refs + 1);
+        const std::vector<std::uint32_t> rs(region_starts, region_starts + n_reg), re(region_ends, region_ends + n_reg),
+            caps(region_caps, region_caps + n_reg);
+        std::vector<bam_api::BAMReadId> kept = hip->solve_templates_profile(max_coverage, api, offs, rs, re, caps, default_cap);
+        if (tstats) *tstats = hip->last_template_stats();
+        if (qstats) *qstats = hip->last_template_profile_stats();
+        const std::uint32_t written = api.write_records(out_path, kept);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
 // message otherwise (targets without per_reference, an unknown chrom, a malformed line)
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,

@@ -295,6 +295,16 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_
     return kept;
 }
 
+// a record is written iff one of its segments is kept; its segments are consecutive, in file order
+static std::vector<bam_api::BAMReadId> records_of_kept_segments(const bam_api::TemplateSegments& seg,
+                                                                const std::vector<std::uint64_t>& mask) {
+    std::vector<bam_api::BAMReadId> records;
+    for (std::size_t i = 0; i < seg.starts.size(); ++i)
+        if (((mask[i >> 6] >> (i & 63)) & 1ull) && (records.empty() || records.back() != seg.segment_records[i]))
+            records.push_back(seg.segment_records[i]);
+    return records;
+}
+
 std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     if (!bam_api.template_aware())
         throw std::invalid_argument("template-aware downsampling needs a BamApi built with BamApiConfig::template_aware");
@@ -315,11 +325,41 @@ std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates(std::uint32_t
     if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
     if (rc != QMCP_OK) die("qmcp_hip_solve_templates_host", rc);
     breakdown_ = qmcp_hip_host_breakdown{};
-    // a record is written iff one of its segments is kept; its segments are consecutive, in file order
-    std::vector<bam_api::BAMReadId> records;
-    for (std::size_t i = 0; i < n; ++i)
-        if (((mask[i >> 6] >> (i & 63)) & 1ull) && (records.empty() || records.back() != seg.segment_records[i]))
-            records.push_back(seg.segment_records[i]);
+    std::vector<bam_api::BAMReadId> records = records_of_kept_segments(seg, mask);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return records;
+}
+
+std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates_profile(std::uint32_t required_cover,
+                                                                           bam_api::BamApi& bam_api,
+                                                                           const std::vector<std::uint32_t>& offsets,
+                                                                           const std::vector<std::uint32_t>& region_starts,
+                                                                           const std::vector<std::uint32_t>& region_ends,
+                                                                           const std::vector<std::uint32_t>& caps,
+                                                                           std::uint32_t default_cap) {
+    if (!bam_api.template_aware())
+        throw std::invalid_argument("template-aware downsampling needs a BamApi built with BamApiConfig::template_aware");
+    const bam_api::TemplateSegments& seg = bam_api.get_template_segments();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = seg.starts.size();
+    if (offsets.size() != seg.contig_lengths.size() + 1) throw std::invalid_argument("cap regions of other references");
+    if (region_starts.size() < offsets.back() || region_ends.size() < offsets.back() || caps.size() < offsets.back())
+        throw std::invalid_argument("cap region arrays are shorter than their offsets say");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    const std::vector<std::uint32_t>& stages = bam_api.template_stages();
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    const int rc = qmcp_hip_solve_templates_profile_host(
+        ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(), seg.template_ids.data(), n, seg.n_templates,
+        seg.contig_lengths.data(), (std::uint32_t)seg.contig_lengths.size(), offsets.data(), region_starts.data(),
+        region_ends.data(), caps.data(), default_cap, 0u, required_cover, stages.empty() ? nullptr : stages.data(),
+        (std::uint32_t)stages.size(), mask.data(), &stats_, &tpstats_, &tqstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_templates_profile_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    std::vector<bam_api::BAMReadId> records = records_of_kept_segments(seg, mask);
     ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return records;
 }

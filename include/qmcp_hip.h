@@ -963,6 +963,71 @@ int qmcp_hip_solve_templates_device(qmcp_hip_ctx* ctx,
                                     uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                     qmcp_hip_template_stats* tstats);
 
+/* Template-aware downsampling under a cap table: qmcp_hip_solve_templates_* with the region table of
+ * qmcp_hip_solve_profile_* in the place of the one max_coverage -- whole templates, capped by region (a paired exome
+ * under its targets, a split-read library under a hotspot profile).
+ * Input: the segments, template_ids / n_templates and contig table of qmcp_hip_solve_templates_host; region_offsets (may be
+ * NULL), region_starts / region_ends / region_caps, default_cap and flags of qmcp_hip_solve_profile_host (regions clipped,
+ * disjoint per contig after clipping; flags must be 0); max_coverage = M >= 1, the scale of the schedule, and stages /
+ * n_stages as in qmcp_hip_solve_templates_host: T_1 < ... < T_k = M, NULL for {ceil(M / 2), M}.  default_cap is independent
+ * of M and may be 0.
+ * Definition: cap(p) is the profile entry's.  The stage cap is c_j(p) = ceil(cap(p) * T_j / M), computed in 64 bits: it
+ * never decreases in j, c_k = cap, and where cap(p) = M it is T_j.  S_0 is empty.  Stage j: credit_j(p) is the depth of
+ * the placed segments of S_(j-1); K_j is the canonical selection of the profile entry over the placed segments not in
+ * S_(j-1), alone, in input order, with need(p) = min(cov_rest(p), max(0, c_j(p) - credit_j(p)));
+ * S_j = complete_templates(S_(j-1) | K_j).  The result is S_k: whole templates whose depth is at least
+ * min(cov(p), cap(p)) everywhere (min(cov_rest, max(0, c - credit)) = max(0, min(cov, c) - credit) holds position by
+ * position, so the depth of S_j is at least min(cov, c_j); completion only adds segments).  A segment that lies wholly on
+ * cap-0 positions is never selected and enters only through its template.
+ * Identities: (1) no region used and default_cap == M is qmcp_hip_solve_templates_*: the mask and every field of
+ * qmcp_hip_template_stats, bit for bit (the call IS that entry); (2) ids that are all distinct with the one stage {M}
+ * give the mask of qmcp_hip_solve_profile_* for the same table; (3) every cap equal to M, regions present, gives the mask
+ * of qmcp_hip_solve_templates_* (another route, the same canonical rule); (4) one stage gives qmcp_hip_solve_profile_*
+ * followed by template completion.
+ * Not claimed: that S_k is minimum among whole-template solutions; that more stages are better; overlap-corrected depth
+ * inside a template.
+ * Errors, all on the host before the context is looked at and before anything is copied or launched: those of
+ * qmcp_hip_solve_templates_host (stage list, max_coverage == 0 or >= 2^31, template_ids == NULL, n_templates == 0), then
+ * those of qmcp_hip_solve_profile_host (table shape QMCP_EINVAL, a cap or default_cap of 2^31 or more QMCP_ERANGE, unknown
+ * flag bits QMCP_EINVAL).  An id >= n_templates is found on the device as in qmcp_hip_solve_templates_host, with the mask
+ * cleared.
+ * stats / tstats (may be NULL) as in qmcp_hip_solve_templates_host, target[j] = T_j.  qstats (may be NULL): the table as
+ * in qmcp_hip_profile_stats; the placed segments that cover a position with cap(p) > 0 and the templates that own one;
+ * ms_need, the device time of the kernels that build need[] (and of the cut-point scans behind them).  After an error
+ * found on the device tstats holds the schedule without counts and qstats the table's counts without the on-cap counts.  Route: stage 1 is
+ * the profile entry's batches at c_1 (a batch without regions takes the plain solve at ceil(default_cap * T_1 / M), a
+ * batch whose largest c_1 is 0 keeps nothing); later stages are the templates entry's with need[] built by
+ * k_tpl_profile_need from the batch's scaled regions and the credit; a batch whose largest c_j is 0 is skipped.  No
+ * _begin / _end form. */
+typedef struct qmcp_hip_template_profile_stats {
+    uint64_t positions_in_regions;
+    uint64_t n_segments_on_cap;                       /* placed segments that cover a position with cap(p) > 0         */
+    uint64_t n_templates_on_cap;                      /* templates with at least one such segment                      */
+    uint32_t regions_in, regions_used;
+    float ms_need;
+    uint32_t reserved;
+} qmcp_hip_template_profile_stats;
+int qmcp_hip_solve_templates_profile_host(qmcp_hip_ctx* ctx,
+                                          const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                          const uint32_t* template_ids, uint64_t n_reads, uint32_t n_templates,
+                                          const uint32_t* contig_lengths, uint32_t n_contigs,
+                                          const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                          const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                          uint32_t flags, uint32_t max_coverage,
+                                          const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                          uint64_t* keep_mask_out, qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats,
+                                          qmcp_hip_template_profile_stats* qstats);
+int qmcp_hip_solve_templates_profile_device(qmcp_hip_ctx* ctx,
+                                            const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                            const uint32_t* d_template_ids, uint64_t n_reads, uint32_t n_templates,
+                                            const uint32_t* contig_lengths, uint32_t n_contigs,
+                                            const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                            const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                            uint32_t flags, uint32_t max_coverage,
+                                            const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                            uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                            qmcp_hip_template_stats* tstats, qmcp_hip_template_profile_stats* qstats);
+
 #ifdef __cplusplus
 }
 #endif
