@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_pairs_host", "qmcp_hip_solve_pairs_device",
     "qmcp_hip_solve_templates_host", "qmcp_hip_solve_templates_device",
     "qmcp_hip_solve_templates_profile_host", "qmcp_hip_solve_templates_profile_device",
+    "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
 )
 
 QMCP_OK = 0
@@ -52,6 +53,7 @@ NO_CONTIG = 0xFFFFFFFF  # QMCP_NO_CONTIG: an unplaced read's contig id (never ke
 TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
 LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
 PAIR_MAX_STAGES = 16  # QMCP_PAIR_MAX_STAGES
+CEILING_WHOLE_PAIRS = 1  # QMCP_CEILING_WHOLE_PAIRS
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
 DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
@@ -119,6 +121,18 @@ class ProfileStats(C.Structure):
     """qmcp_hip_profile_stats: the cap table of a profile solve and what the kernel that builds need(p) counted"""
     _fields_ = [("positions_in_regions", C.c_uint64), ("capped_positions", C.c_uint64), ("demand", C.c_uint64),
                 ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_profile", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class CeilingStats(C.Structure):
+    """qmcp_hip_ceiling_stats: what a ceiling solve dropped, where the data lies above its caps, and what the device-side
+    check of the kept depth found (short_*, excess_positions and max_kept_depth: before mates are dropped)"""
+    _fields_ = [("reads_placed", C.c_uint64), ("reads_dropped", C.c_uint64), ("mates_dropped", C.c_uint64),
+                ("over_positions", C.c_uint64), ("over_bases", C.c_uint64), ("short_positions", C.c_uint64),
+                ("short_bases", C.c_uint64), ("excess_positions", C.c_uint64), ("max_kept_depth", C.c_uint32),
+                ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_ceiling", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -402,6 +416,12 @@ _hip.qmcp_hip_solve_templates_profile_device.argtypes = [
     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p,
     _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
     C.POINTER(TemplateStats), C.POINTER(TemplateProfileStats)]
+_hip.qmcp_hip_solve_ceiling_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p, _u32p,
+                                             _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p, C.POINTER(Stats),
+                                             C.POINTER(CeilingStats)]
+_hip.qmcp_hip_solve_ceiling_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                               C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(CeilingStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -488,6 +508,12 @@ if _host is not None:
                                                      C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_int,
                                                      C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_pairs.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_ceiling.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                       C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p, _u32p,
+                                                       C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32,
+                                                       C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                       C.c_int, C.c_char_p, C.POINTER(CeilingStats), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_ceiling.restype = C.c_int64
     _host.qmcp_host_read_bam_templates.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _u32p,
                                                    _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, C.c_uint64, _u64p,
                                                    C.POINTER(C.c_uint64), C.c_uint64, _u32p, C.POINTER(C.c_uint64),
@@ -599,6 +625,7 @@ class Solver:
         self.last_pair_stats = None
         self.last_template_stats = None
         self.last_template_profile_stats = None
+        self.last_ceiling_stats = None
 
     def close(self):
         if self._ctx:
@@ -929,6 +956,40 @@ class Solver:
                                                   C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(ps)))
         self.last_stats, self.last_profile_stats = st, ps
         return ps
+
+    def solve_ceiling(self, starts, ends, contig_ids, contig_lengths, default_cap, region_offsets=None, region_starts=None,
+                      region_ends=None, region_caps=None, flags=0):
+        """ceiling downsampling (qmcp_hip_solve_ceiling_host): solve_profile's reads, regions and default_cap, but the
+        caps are CEILINGS -- the kept depth is at most cap(p) at every position and as many reads as possible are kept
+        (the dropped set is the canonical selection under max(0, cov - cap)).  The depth may fall below min(cov, cap):
+        last_ceiling_stats.short_positions / short_bases say where.  flags: CEILING_WHOLE_PAIRS also drops the mate
+        (reads 2q, 2q + 1) of every dropped read.  Host keep bitmask in INPUT order out; last_stats, last_ceiling_stats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, cs = Stats(), CeilingStats()
+        _check(_hip.qmcp_hip_solve_ceiling_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                lengths.size, _p32(offs), _p32(r0), _p32(r1), _p32(caps), int(default_cap),
+                                                int(flags), _p64(mask), C.byref(st), C.byref(cs)))
+        self.last_stats, self.last_ceiling_stats = st, cs
+        return mask[:mask_words(n)]
+
+    def solve_ceiling_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, default_cap, d_mask,
+                             region_offsets=None, region_starts=None, region_ends=None, region_caps=None, flags=0,
+                             stream=0):
+        """solve_ceiling on device pointers (ints); the input-order mask is written to d_mask.  Returns the ceiling stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
+        st, cs = Stats(), CeilingStats()
+        _check(_hip.qmcp_hip_solve_ceiling_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                  C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                  _p32(offs), _p32(r0), _p32(r1), _p32(caps), int(default_cap), int(flags),
+                                                  C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(cs)))
+        self.last_stats, self.last_ceiling_stats = st, cs
+        return cs
 
     def solve_pairs(self, starts, ends, contig_ids, contig_lengths, max_coverage, stages=None):
         """pair-aware downsampling (qmcp_hip_solve_pairs_host): reads (2q, 2q + 1) are pair q, stages the rising targets
@@ -1978,7 +2039,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    ladder_out=None, stratify=None, strata_report=None, dedup=False, dedup_report=None, profile=None,
                    track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None,
                    template_aware=False, split_spliced=True, include_secondary=False, template_stages=None,
-                   template_report=None, template_targets=None, template_target_padding=0, template_profile=None):
+                   template_report=None, template_targets=None, template_target_padding=0, template_profile=None,
+                   ceiling=False, ceiling_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2046,8 +2108,51 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     is kept for its depth on target.  template_profile: the caps of profile_from_bedgraph, max_coverage elsewhere.
     max_coverage is the scale of template_stages in both.  template_report then also lists segments_on_cap,
     templates_on_cap, regions_in, regions_used and positions_in_regions.  Not both at once, and not with anything
-    template_aware refuses -- targets= and profile= included (ValueError).  None: nothing changes"""
+    template_aware refuses -- targets= and profile= included (ValueError).  None: nothing changes.
+    ceiling=True (BamApiConfig::ceiling): max_coverage is a CEILING -- the written depth is at most max_coverage at every
+    position and as many reads as possible are kept -- one qmcp_hip_solve_ceiling_host call with CEILING_WHOLE_PAIRS on
+    the reads as the pair-aware flow pairs them.  With profile (a bedGraph file) the file's caps are ceilings and
+    max_coverage applies elsewhere.  The output is written from the final mask, which holds whole pairs: no find_pairs
+    follows (it would put depth back).  The depth may fall below min(coverage, cap) next to deeper positions;
+    ceiling_report (a path) gets a stat<TAB>value TSV with the CeilingStats (short_positions, short_bases, ...) and
+    records_written.  Needs per_reference=True; not together with targets, report, track, ladder, stratify, dedup,
+    pair_aware, template_aware, amplicon files or "quasi-mcp-hip-quality" (ValueError).  False: nothing changes"""
     _need_host()
+    if ceiling_report is not None and not ceiling:
+        raise ValueError("ceiling_report needs ceiling=True")
+    if ceiling:
+        if not per_reference:
+            raise ValueError("ceiling downsampling needs per_reference=True")
+        for given, what in ((pair_aware, "pair_aware"), (template_aware, "template_aware"), (targets, "targets"),
+                            (report, "a depth report"), (track is not None, "a depth track"),
+                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
+                            (dedup, "dedup")):
+            if given:
+                raise ValueError(f"ceiling downsampling does not go together with {what}")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("ceiling downsampling does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("ceiling downsampling does not take a solver that grades by quality")
+        offs = r0 = r1 = caps = None
+        n_refs = 0
+        if profile is not None:
+            names = reference_names(in_path)
+            offs, r0, r1, caps = profile_from_bedgraph(profile, names)
+            n_refs = len(names)
+        err = C.create_string_buffer(1024)
+        cs = CeilingStats()
+        n = _host.qmcp_host_downsample_bam_ceiling(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
+            1, _p32(offs), _p32(r0), _p32(r1), _p32(caps), n_refs, None, None, None, None, 0, None, 0, 0, 0, None, None, 0,
+            str(ceiling_report).encode() if ceiling_report else None, C.byref(cs), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
     if (template_targets is not None or template_profile is not None) and not (template_aware and per_reference):
         raise ValueError("template_targets and template_profile need template_aware=True and per_reference=True")
     if template_targets is not None and template_profile is not None:

@@ -8,7 +8,8 @@
 //      columns gathered in grouped order, solved by the ordinary multi-contig solve, its mask ORed back into input order
 // Grouping happens once; a batch only gathers its own reads.
 // A coverage ladder (api/ladder.inc.hip) is this call with further levels run inside each batch, on its gathered columns.
-// A coverage profile (api/profile.inc.hip) is this call with every batch solved under its own regions' caps.
+// A coverage profile (api/profile.inc.hip) is this call with every batch solved under its own regions' caps; a ceiling
+// solve (api/ceiling.inc.hip) is a profile whose batches select the DROPPED reads, complemented once the call is through.
 // A pair-aware solve (api/pairs.inc.hip) is this call at its first target, with the further stages run over all batches
 // once the last batch's mask is in place.
 namespace {
@@ -17,9 +18,9 @@ struct LadderRun;
 int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, uint32_t nb, const uint64_t* roff,
                            const uint32_t* lengths, uint32_t n_contigs);
 struct ProfileRun;
-int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
-                        const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
-                        qmcp_hip_stats* st);
+int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
+                        const uint64_t* roff, const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs,
+                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st);
 struct PairRun;
 int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
                       const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
@@ -144,7 +145,7 @@ int solve_gathered_batch(qmcp_hip_ctx* c, const void* bsorted, uint32_t nb, cons
     qmcp_hip_stats bs;
     std::memset(&bs, 0, sizeof(bs));
     if (profile)
-        TRY(profile_solve_batch(c, *profile, bs_starts, bs_ends, roff.data(), lengths, first_contig, n_contigs, nb,
+        TRY(profile_solve_batch(c, *profile, bsorted, bs_starts, bs_ends, roff.data(), lengths, first_contig, n_contigs, nb,
                                 (uint64_t*)c->bc_mask.p, &bs));
     else
         TRY(solve_on_device(c, bs_starts, bs_ends, roff.data(), lengths + first_contig, n_contigs, nb, M,

@@ -1,0 +1,205 @@
+// ceiling.inc.hip -- part of qmcp_api.hip (one translation unit).
+// qmcp_hip_solve_ceiling_host / _device: kept(p) <= cap(p) everywhere with the most reads kept.  kept <= cap is dropped >=
+// cov - cap, and keeping the most is dropping the fewest: the dropped set D is the canonical selection under need(p) =
+// max(0, cov(p) - cap(p)), and need <= cov, so the greedy never runs dry.  The call is the profile call (api/profile.inc.hip:
+// the by-contig grouping and batches, the cap table, capped_solve_batch) with
+//   1. per batch, k_ceiling_need as the CappedNeed: the dual need, its cut bit where need(p) == cov(p), and the largest
+//      need, which is what plans the sweep (CeilingNeed::plan_cap) -- a batch that is nowhere above its caps queues none
+//   2. per batch, once k_mark has written D in grouped order: k_pair_credit_events + scan give depth_D(p), k_ceiling_check
+//      holds cov - depth_D against the caps; the by-contig layer then ORs D into input order
+//   3. once, k_ceiling_finish over the input-order mask: keep = placed & ~D, mates joined to D first under
+//      QMCP_CEILING_WHOLE_PAIRS
+// Buffers: the profile's pf_need / pf_tab, and cl_* (a batch's position offsets, depth_D and its spine, the counters).
+namespace {
+
+struct CeilingRun {
+    float ms_check = 0.f;
+    std::vector<uint32_t> poff32;  // the batch's position offsets
+};
+
+// need[] of the dropped set: the batch's regions as ProfileNeed uploads them, through k_ceiling_need
+struct CeilingNeed : ProfileNeed {
+    unsigned long long largest = 0;  // this batch's largest need
+    CeilingNeed(ProfileRun& run, uint32_t regions) : ProfileNeed(run, regions) {}
+    const char* name() const override { return "k_ceiling_need"; }
+    int upload(qmcp_hip_ctx* c, hipStream_t st) override {
+        HIP_TRY(hipMemsetAsync((unsigned long long*)c->cl_stat.p + qmcp::kCeilMaxNeed, 0, sizeof(unsigned long long), st));
+        return ProfileNeed::upload(c, st);
+    }
+    void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
+        const uint32_t* d_rs = (const uint32_t*)c->pf_tab.p;
+        qmcp::launch_ceiling_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, d_rs, d_rs + n_reg,
+                                  d_rs + 2 * (size_t)n_reg, n_reg, pf.default_cap, need, (unsigned long long*)c->cl_stat.p);
+    }
+    int no_demand(qmcp_hip_ctx* c, hipStream_t st, bool* none) override {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&largest, (const unsigned long long*)c->cl_stat.p + qmcp::kCeilMaxNeed, sizeof(largest),
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *none = largest == 0;
+        return QMCP_OK;
+    }
+    // under a ceiling the demand is cov - cap, not the cap (a cap of 0 is the FULL demand)
+    uint32_t plan_cap(uint32_t) const override { return std::max((uint32_t)largest, 1u); }
+};
+
+int ceiling_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
+                        const uint64_t* roff, const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs,
+                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st_out) {
+    CeilingRun& cl = *pf.ceiling;
+    const qmcp::CapTable& tab = *pf.tab;
+    const uint32_t* lengths = lengths_all + first_contig;
+    hipStream_t st = c->stream;
+    qmcp::batch_cap_table(tab, lengths_all, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
+    CeilingNeed nd(pf, tab.offs[first_contig + n_contigs] - tab.offs[first_contig]);
+    bool swept = false;
+    // (max_cap only short-circuits at 0 here: the windows come from CeilingNeed::plan_cap)
+    TRY(capped_solve_batch(c, nd, 1u, d_starts, d_ends, roff, lengths, n_contigs, n64, d_mask, st_out, &swept));
+    pf.ms_profile += nd.ms;
+    cl.poff32.assign((size_t)n_contigs + 1, 0);
+    for (uint32_t k = 0; k < n_contigs; ++k) cl.poff32[k + 1] = cl.poff32[k] + lengths[k];  // (at most 2^31 - 2 positions)
+    const uint32_t ltot = cl.poff32[n_contigs], nb = (uint32_t)n64;
+    if (nb == 0 || ltot == 0) return QMCP_OK;
+    // the depth of D on the batch's axis, and the kept depth against the caps: boff, eoff and pf_tab are the solve's
+    const uint32_t pad = qmcp::pair_credit_pad();
+    TRY(ensure(c, c->cl_depth, ((size_t)ltot + pad + 4) * sizeof(uint32_t)));
+    TRY(ensure(c, c->cl_spine, (size_t)(qmcp::scan_spine_entries(ltot + pad) + 1) * sizeof(uint32_t) + 16));
+    TRY(ensure(c, c->cl_poff, ((size_t)n_contigs + 1) * sizeof(uint32_t)));
+    EventPair ev(c);
+    if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
+    HIP_TRY(hipEventRecord(ev.a, st));
+    HIP_TRY(hipMemsetAsync(c->cl_depth.p, 0, ((size_t)ltot + pad + 4) * sizeof(uint32_t), st));
+    if (swept) {  // (no sweep: D is empty, the zeroed depth stands)
+        HIP_TRY(hipMemcpyAsync(c->cl_poff.p, cl.poff32.data(), ((size_t)n_contigs + 1) * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, st));
+        KernelSpan sp(c, "k_pair_credit_events + scan(ceiling)");
+        qmcp::launch_pair_credit_events(st, bsorted, nb, d_mask, d_starts, d_ends, (const uint32_t*)c->cl_poff.p, first_contig,
+                                        (uint32_t*)c->cl_depth.p);
+        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->cl_depth.p, ltot + pad, (uint32_t*)c->cl_depth.p,
+                                    (uint32_t*)c->cl_spine.p, false);
+    }
+    {
+        KernelSpan sp(c, "k_ceiling_check");
+        const uint32_t* d_rs = (const uint32_t*)c->pf_tab.p;
+        qmcp::launch_ceiling_check(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
+                                   (const uint32_t*)c->cl_depth.p + pad, ltot, d_rs, d_rs + nd.n_reg,
+                                   d_rs + 2 * (size_t)nd.n_reg, nd.n_reg, pf.default_cap, (unsigned long long*)c->cl_stat.p);
+    }
+    HIP_TRY(hipEventRecord(ev.b, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // (the copy of poff32 is done, the time can be read)
+    cl.ms_check += elapsed(ev.a, ev.b);
+    return QMCP_OK;
+}
+
+// the checks both entries make before anything is copied or launched, and the table
+int check_ceiling_call(uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs, const uint32_t* region_offsets,
+                       const uint32_t* region_starts, const uint32_t* region_ends, const uint32_t* region_caps,
+                       uint32_t default_cap, uint32_t flags, qmcp::CapTable& tab) {
+    if (flags & ~QMCP_CEILING_WHOLE_PAIRS) return fail(QMCP_EINVAL, "unknown flag bits 0x%x", flags & ~QMCP_CEILING_WHOLE_PAIRS);
+    if ((flags & QMCP_CEILING_WHOLE_PAIRS) && (n_reads & 1ull))
+        return fail(QMCP_EINVAL, "n_reads %llu is odd: reads (2q, 2q + 1) are pair q", (unsigned long long)n_reads);
+    return check_profile_call(n_reads, contig_lengths, n_contigs, region_offsets, region_starts, region_ends, region_caps,
+                              default_cap, 0u, tab);
+}
+
+int solve_ceiling_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                            uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const qmcp::CapTable& tab,
+                            uint32_t default_cap, uint32_t flags, uint64_t* d_mask, qmcp_hip_stats* stats,
+                            qmcp_hip_ceiling_stats* cstats) {
+    qmcp_hip_ceiling_stats cs;
+    std::memset(&cs, 0, sizeof(cs));
+    cs.regions_in = tab.regions_in;
+    cs.regions_used = tab.regions_used;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (cstats) *cstats = cs;
+    hipStream_t st = c->stream;
+    TRY(ensure(c, c->cl_stat, qmcp::kCeilingStatWords * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->cl_stat.p, 0, qmcp::kCeilingStatWords * sizeof(unsigned long long), st));
+    ProfileRun pf;
+    CeilingRun cl;
+    pf.tab = &tab;
+    pf.default_cap = default_cap;
+    pf.ceiling = &cl;
+    // d_mask leaves this call holding D in input order
+    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, default_cap, d_mask, stats, nullptr, &pf));
+    EventPair ev(c);
+    if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
+    HIP_TRY(hipEventRecord(ev.a, st));
+    {
+        KernelSpan sp(c, "k_ceiling_finish");
+        qmcp::launch_ceiling_finish(st, d_ids, n64, (flags & QMCP_CEILING_WHOLE_PAIRS) != 0, d_mask,
+                                    (unsigned long long*)c->cl_stat.p);
+    }
+    HIP_TRY(hipEventRecord(ev.b, st));
+    HIP_TRY(hipGetLastError());
+    unsigned long long w[qmcp::kCeilingStatWords];
+    HIP_TRY(hipMemcpyAsync(w, c->cl_stat.p, sizeof(w), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    collect_spans(c);
+    cs.reads_placed = w[qmcp::kCeilPlaced];
+    cs.reads_dropped = w[qmcp::kCeilPlaced] - w[qmcp::kCeilKept];
+    cs.mates_dropped = w[qmcp::kCeilMatesDropped];
+    cs.over_positions = w[qmcp::kCeilOverPositions];
+    cs.over_bases = w[qmcp::kCeilOverBases];
+    cs.short_positions = w[qmcp::kCeilShortPositions];
+    cs.short_bases = w[qmcp::kCeilShortBases];
+    cs.excess_positions = w[qmcp::kCeilExcessPositions];
+    cs.max_kept_depth = (uint32_t)w[qmcp::kCeilMaxKept];
+    cs.ms_ceiling = pf.ms_profile + cl.ms_check + elapsed(ev.a, ev.b);
+    if (cstats) *cstats = cs;
+    return QMCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmcp_hip_solve_ceiling_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                const uint32_t* region_offsets, const uint32_t* region_starts, const uint32_t* region_ends,
+                                const uint32_t* region_caps, uint32_t default_cap, uint32_t flags, uint64_t* keep_mask_out,
+                                qmcp_hip_stats* stats, qmcp_hip_ceiling_stats* cstats) {
+    TRY(use_device(c));
+    if (n_reads && (!starts || !ends || !contig_ids || !keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    qmcp::CapTable tab;
+    TRY(check_ceiling_call(n_reads, contig_lengths, n_contigs, region_offsets, region_starts, region_ends, region_caps,
+                           default_cap, flags, tab));
+    const size_t nb = (size_t)n_reads * sizeof(uint32_t);
+    const size_t words = (size_t)((n_reads + 63) / 64);
+    TRY(ensure(c, c->in_starts, nb));
+    TRY(ensure(c, c->in_ends, nb));
+    TRY(ensure(c, c->in_aux0, nb));
+    TRY(ensure(c, c->mask, words * sizeof(uint64_t)));
+    c->mask_reads = 0;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(c->in_starts.p, starts, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(solve_ceiling_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
+                                (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, tab, default_cap, flags,
+                                (uint64_t*)c->mask.p, stats, cstats));
+    if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mask_reads = n_reads;
+    return QMCP_OK;
+}
+
+int qmcp_hip_solve_ceiling_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends,
+                                  const uint32_t* d_contig_ids, uint64_t n_reads, const uint32_t* contig_lengths,
+                                  uint32_t n_contigs, const uint32_t* region_offsets, const uint32_t* region_starts,
+                                  const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                  uint32_t flags, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                  qmcp_hip_ceiling_stats* cstats) {
+    TRY(use_device(c));
+    if (n_reads && (!d_starts || !d_ends || !d_contig_ids || !d_keep_mask_out)) return fail(QMCP_EINVAL, "null buffer");
+    qmcp::CapTable tab;
+    TRY(check_ceiling_call(n_reads, contig_lengths, n_contigs, region_offsets, region_starts, region_ends, region_caps,
+                           default_cap, flags, tab));
+    TRY(order_after(c, hip_stream));
+    return solve_ceiling_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, tab, default_cap,
+                                   flags, d_keep_mask_out, stats, cstats);
+}
+
+}  // extern "C"

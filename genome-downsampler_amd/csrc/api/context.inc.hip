@@ -165,6 +165,9 @@ struct qmcp_hip_ctx {
     // (starts | ends | caps), the call's table for the on-cap pass (offsets | starts | ends | caps | positive positions
     // before), the bitset of templates that touch a positive cap, and the two on-cap counters (segments, templates)
     DevBuf tq_tab, tq_cap, tq_flags, tq_stat;
+    // ceiling solves (api/ceiling.inc.hip; need[] and the batch's regions are the profile's pf_need / pf_tab): a batch's
+    // position offsets, the events of its dropped reads and their scan with its spine, and the call's counters
+    DevBuf cl_poff, cl_depth, cl_spine, cl_stat;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

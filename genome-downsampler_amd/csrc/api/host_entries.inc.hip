@@ -175,7 +175,8 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->pr_in, &c->pr_rest, &c->pr_words, &c->pr_spine, &c->pr_offs[0], &c->pr_offs[1], &c->pr_poff,
                       &c->pr_credit, &c->pr_cspine, &c->pr_starts, &c->pr_ends, &c->pr_orig, &c->pr_mask, &c->pr_need,
                       &c->pr_stat, &c->tp_ids, &c->tp_flags, &c->tp_sizes, &c->tp_stat,
-                      &c->tq_tab, &c->tq_cap, &c->tq_flags, &c->tq_stat};
+                      &c->tq_tab, &c->tq_cap, &c->tq_flags, &c->tq_stat,
+                      &c->cl_poff, &c->cl_depth, &c->cl_spine, &c->cl_stat};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

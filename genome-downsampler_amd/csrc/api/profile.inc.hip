@@ -13,15 +13,21 @@
 // Buffers: the solve's own arena for everything the plain mixed route uses; need[] in pf_need, the batch's regions in
 // pf_tab, the two counters in pf_stat.
 // Step 3 is capped_solve_batch, which takes what builds need[] as a CappedNeed: the region table here (ProfileNeed), the
-// credit of the reads already kept in api/pairs.inc.hip.
+// credit of the reads already kept in api/pairs.inc.hip, the dual need of a ceiling in api/ceiling.inc.hip (a ProfileRun
+// with a CeilingRun sends every batch there).
 namespace {
 
+struct CeilingRun;
 struct ProfileRun {
     const qmcp::CapTable* tab = nullptr;
     uint32_t default_cap = 0;
     float ms_profile = 0.f;
     std::vector<uint32_t> gs, ge, gcap;  // the batch's regions in its global positions
+    CeilingRun* ceiling = nullptr;       // the caps are ceilings: every batch goes to api/ceiling.inc.hip
 };
+int ceiling_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
+                        const uint64_t* roff, const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs,
+                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st_out);
 
 // What builds need[] for capped_solve_batch: a profile's regions here, the credit of the reads already kept in
 // api/pairs.inc.hip.  reserve runs inside the solve's arena block, upload behind the contig tables, launch once boff and
@@ -38,10 +44,14 @@ struct CappedNeed {
         *none = false;
         return QMCP_OK;
     }
+    // the cap that chooses the sweep's windows, asked for after no_demand: the caller's max_cap, unless the largest demand
+    // is only known once launch has counted it
+    virtual uint32_t plan_cap(uint32_t max_cap) const { return max_cap; }
 };
 
 // One batch on the sort-based mixed-span route under need[] (steps 3 of the header above); max_cap > 0 is the largest
-// cap the batch can meet, which chooses the windows.  *swept (may be NULL): a sweep was queued.
+// cap the batch can meet, which chooses the windows (through nd.plan_cap, once need[] is built).  *swept (may be NULL):
+// a sweep was queued.
 int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const uint32_t* d_starts, const uint32_t* d_ends,
                        const uint64_t* roff, const uint32_t* lengths, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
                        qmcp_hip_stats* st_out, bool* swept_out = nullptr) {
@@ -145,7 +155,6 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     // need[], cut points
     const uint32_t* d_need = (const uint32_t*)nd.need_buf(c).p;
     const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
-    const uint32_t windows = qmcp::plan_mixed_sweep(c->opt, n, max_span, ltot, n_contigs, max_cap, in_regs, false).windows;
     const uint32_t* seg = nullptr;
     uint32_t n_seg_max = 0;
     uint32_t* d_iters = (uint32_t*)((char*)c->scalars.p + 16);
@@ -158,6 +167,8 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     }
     bool idle = false;  // nothing is asked for anywhere: no sweep, the zeroed mask stands
     TRY(nd.no_demand(c, st, &idle));
+    const uint32_t windows =
+        qmcp::plan_mixed_sweep(c->opt, n, max_span, ltot, n_contigs, nd.plan_cap(max_cap), in_regs, false).windows;
     if (windows != 0 && !idle) {
         KernelSpan sp(c, "k_profile_cuts");
         seg = qmcp::launch_profile_segments(st, d_need, (const uint64_t*)c->poff.p, n_contigs, ltot, windows, (uint32_t*)c->segs.p);
@@ -249,9 +260,12 @@ struct ProfileNeed : CappedNeed {
     }
 };
 
-int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const uint32_t* d_starts, const uint32_t* d_ends, const uint64_t* roff,
-                        const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs, uint64_t n64, uint64_t* d_mask,
-                        qmcp_hip_stats* st_out) {
+int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
+                        const uint64_t* roff, const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs,
+                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st_out) {
+    if (pf.ceiling)
+        return ceiling_solve_batch(c, pf, bsorted, d_starts, d_ends, roff, lengths_all, first_contig, n_contigs, n64, d_mask,
+                                   st_out);
     const qmcp::CapTable& tab = *pf.tab;
     const uint32_t* lengths = lengths_all + first_contig;
     const uint32_t r0 = tab.offs[first_contig], r1 = tab.offs[first_contig + n_contigs];

@@ -69,6 +69,8 @@
 //                       (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
 //   templates_profile   the template stages under a cap per region: stage 1 is the profile's batches at the scaled
 //                       caps, later stages build need[] from the scaled region table and the credit
+//   ceiling             kept depth never above the cap, the most reads kept: the profile's batches with the dual need
+//                       max(0, cov(p) - cap(p)) selecting the DROPPED reads, a device-side check, and the complement
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
@@ -91,3 +93,4 @@
 #include "api/pairs.inc.hip"
 #include "api/templates.inc.hip"
 #include "api/templates_profile.inc.hip"
+#include "api/ceiling.inc.hip"

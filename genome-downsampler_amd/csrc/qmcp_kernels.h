@@ -454,5 +454,33 @@ void launch_tpl_on_cap(hipStream_t st, const uint32_t* starts, const uint32_t* e
                        const uint32_t* rs, const uint32_t* re, const uint32_t* cap, const uint32_t* before,
                        bool default_positive, uint32_t* flags, unsigned long long* count);
 
+// ceiling downsampling (kernels/ceiling.inc.hip; api/ceiling.inc.hip drives them).  The region table and boff / eoff as
+// launch_profile_need takes them.  launch_ceiling_need: need[p] = max(0, cov(p) - cap(p)), the cut bit where need(p) ==
+// cov(p) (cov == 0 or cap == 0).  launch_ceiling_check, once the batch's D is marked: depth[p] (16-byte aligned) is the
+// depth of D, kept(p) = cov(p) - depth[p] is held against cap(p) and min(cov(p), cap(p)).  launch_ceiling_finish, once per
+// call: mask (ceil(n_reads / 64) words, input order) holds D and leaves as placed & ~D, with whole_pairs after the mates
+// (2q, 2q + 1) of D's reads have joined D.  cst: kCeilingStatWords counters, zeroed by the caller.
+enum CeilingStat : uint32_t {
+    kCeilOverPositions = 0,  // positions with cov > cap
+    kCeilOverBases,          // the sum of need
+    kCeilMaxNeed,            // the largest need (cleared per batch: it plans the batch's sweep)
+    kCeilExcessPositions,    // positions with kept > cap
+    kCeilShortPositions,     // positions with kept < min(cov, cap)
+    kCeilShortBases,         // the sum of that shortfall
+    kCeilMaxKept,            // the largest kept depth
+    kCeilPlaced,             // placed reads
+    kCeilKept,               // placed reads outside D (and outside its mates, when they are joined)
+    kCeilMatesDropped,       // placed reads dropped only as mates
+    kCeilingStatWords = 12
+};
+void launch_ceiling_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, uint32_t ltot, const uint32_t* rs,
+                         const uint32_t* re, const uint32_t* cap, uint32_t n_regions, uint32_t default_cap, uint32_t* need,
+                         unsigned long long* cst);
+void launch_ceiling_check(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, const uint32_t* depth, uint32_t ltot,
+                          const uint32_t* rs, const uint32_t* re, const uint32_t* cap, uint32_t n_regions,
+                          uint32_t default_cap, unsigned long long* cst);
+void launch_ceiling_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, bool whole_pairs, uint64_t* mask,
+                           unsigned long long* cst);
+
 }  // namespace qmcp
 #endif

@@ -54,6 +54,8 @@
 //                            through a bitset of template ids (mark, spread)
 //   templates_profile        the template stages under a cap table: need(p) from the regions' scaled caps and the credit,
 //                            and the segments and templates that touch a positive cap
+//   ceiling                  ceiling downsampling: need(p) = max(0, cov(p) - cap(p)) for the dropped set, the check of the
+//                            kept depth against the caps, and the complement over the placed reads (mates joined first)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -97,5 +99,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/pairs.inc.hip"
 #include "kernels/templates.inc.hip"
 #include "kernels/templates_profile.inc.hip"
+#include "kernels/ceiling.inc.hip"
 
 }  // namespace qmcp

@@ -98,6 +98,13 @@ struct BamApiConfig {
     bool split_spliced = true;
     bool include_secondary = false;
     std::vector<std::uint32_t> template_stages;
+    // Ceiling downsampling: max_coverage (and the caps of a coverage profile) bound the written depth from ABOVE, and as
+    // many reads as possible are kept (QuasiMcpHipSolver::solve_ceiling / qmcp_hip_solve_ceiling_host with
+    // QMCP_CEILING_WHOLE_PAIRS).  The output -- whole pairs -- is written from the final mask WITHOUT find_pairs, which
+    // would put depth back.  The depth may fall below min(coverage, cap) next to deeper positions; the ceiling report
+    // counts where.  Needs per_reference; goes together with a coverage profile and with nothing else pair_aware refuses,
+    // and not with pair_aware or template_aware (std::invalid_argument otherwise).  false: nothing changes.
+    bool ceiling = false;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -143,6 +150,8 @@ class BamApi {
     // BamApiConfig::pair_aware and pair_stages (empty: the default schedule)
     bool pair_aware() const { return pair_aware_; }
     const std::vector<std::uint32_t>& pair_stages() const { return pair_stages_; }
+    // BamApiConfig::ceiling
+    bool ceiling() const { return ceiling_; }
     // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
     // get_template_segments call, which also fills get_filtered_out_reads
     bool template_aware() const { return template_aware_; }
@@ -184,6 +193,7 @@ class BamApi {
     Stratify stratify_by_ = Stratify::NONE;
     bool dedup_ = false;
     bool pair_aware_ = false;
+    bool ceiling_ = false;
     std::vector<std::uint32_t> pair_stages_;
     bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false;
     std::vector<std::uint32_t> template_stages_;

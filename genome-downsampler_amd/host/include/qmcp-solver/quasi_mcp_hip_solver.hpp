@@ -110,6 +110,14 @@ class QuasiMcpHipSolver : public Solver {
     // stage list (the library's message)
     std::unique_ptr<Solution> solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_pair_stats& last_pair_stats() const { return prstats_; }
+    // Ceiling downsampling for the reads of a BamApi built with BamApiConfig::ceiling: qmcp_hip_solve_ceiling_host with
+    // QMCP_CEILING_WHOLE_PAIRS, the regions as solve_profile takes them (all empty: none) and required_cover as the cap
+    // elsewhere.  The Solution holds whole pairs already -- the caller writes it without find_pairs.
+    // std::invalid_argument as solve_profile, and for an odd number of reads
+    std::unique_ptr<Solution> solve_ceiling(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                            const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
+                                            const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps);
+    const qmcp_hip_ceiling_stats& last_ceiling_stats() const { return clstats_; }
     // Template-aware downsampling for a BamApi built with BamApiConfig::template_aware: qmcp_hip_solve_templates_host on
     // its segments under its template_stages (empty: the default schedule).  Returns the ids of the records whose
     // template is kept (ascending) -- the caller writes them with BamApi::write_records, without find_pairs.
@@ -151,6 +159,7 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_dedup_stats dstats_{};
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
+    qmcp_hip_ceiling_stats clstats_{};
     qmcp_hip_template_stats tpstats_{};
     qmcp_hip_template_profile_stats tqstats_{};
     std::vector<std::uint64_t> dedup_hist_;

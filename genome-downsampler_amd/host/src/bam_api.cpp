@@ -131,6 +131,26 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     } else if (!config.pair_stages.empty()) {
         throw std::invalid_argument("pair_stages need pair_aware");
     }
+    if (config.ceiling) {
+        if (!per_reference_)
+            throw std::invalid_argument("ceiling downsampling needs per_reference: its ceilings are solved one reference "
+                                        "at a time");
+        if (config.pair_aware) throw std::invalid_argument("ceiling downsampling does not take pair_aware");
+        if (config.template_aware) throw std::invalid_argument("ceiling downsampling does not take template_aware");
+        if (!config.targets_filepath.empty()) throw std::invalid_argument("ceiling downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("ceiling downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("ceiling downsampling does not take a depth report");
+        if (!config.depth_track_filepath.empty())
+            throw std::invalid_argument("ceiling downsampling does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("ceiling downsampling does not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("ceiling downsampling does not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("ceiling downsampling does not take amplicon files");
+        ceiling_ = true;
+    }
     if (config.template_aware) {
         if (!per_reference_)
             throw std::invalid_argument("template-aware downsampling needs per_reference: its stages are solved one "

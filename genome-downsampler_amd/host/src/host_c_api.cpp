@@ -1064,6 +1064,91 @@ std::int64_t qmcp_host_downsample_bam_pairs(const char* solver_name, const char*
     }
 }
 
+// The file-to-file flow with BamApiConfig::ceiling: one per-reference ingest, one qmcp_hip_solve_ceiling_host call with
+// QMCP_CEILING_WHOLE_PAIRS (QuasiMcpHipSolver::solve_ceiling) -- max_coverage is the ceiling; with a coverage profile
+// (region_offsets != NULL: n_refs + 1 offsets, as qmcp_host_downsample_bam_profile takes them) the regions' caps are
+// ceilings and max_coverage applies elsewhere -- and write_paired_reads from its mask: whole pairs already, and NO
+// find_pairs, which would put depth back.  targets / report / track / ladder_levels / stratify / dedup / pair_aware /
+// template_aware / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given so that it refuses the
+// combinations it refuses; a solver that grades by quality is refused here.  ceiling_report (may be NULL): a TSV
+// stat<TAB>value with the qmcp_hip_ceiling_stats and the records written.  cstats (may be NULL) takes the stats.  Returns
+// the number of records written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the
+// configuration is refused, -5 when the report cannot be written.
+std::int64_t qmcp_host_downsample_bam_ceiling(const char* solver_name, const char* in_path, const char* out_path,
+                                              const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                              std::uint32_t min_mapq, int per_reference, const std::uint32_t* region_offsets,
+                                              const std::uint32_t* region_starts, const std::uint32_t* region_ends,
+                                              const std::uint32_t* region_caps, std::uint64_t n_refs, const char* targets,
+                                              const char* report, const char* track, const std::uint32_t* ladder_levels,
+                                              std::uint32_t n_ladder_levels, const char* stratify, int dedup, int pair_aware,
+                                              int template_aware, const char* bed, const char* tsv,
+                                              int amplicons_by_reference, const char* ceiling_report,
+                                              qmcp_hip_ceiling_stats* cstats, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.ceiling = true;
+        cfg.pair_aware = pair_aware != 0;
+        cfg.template_aware = template_aware != 0;
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (track && track[0]) cfg.depth_track_filepath = track;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
+        cfg.dedup = dedup != 0;
+        if (bed && bed[0]) cfg.bed_filepath = bed;
+        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("ceiling downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no ceiling downsampling");
+        bam_api::BamApi api(in_path, cfg);
+        std::vector<std::uint32_t> offs, rs, re, caps;
+        if (region_offsets != nullptr) {
+            const std::uint32_t n_reg = region_offsets[n_refs];
+            if (n_reg && (!region_starts || !region_ends || !region_caps))
+                throw std::invalid_argument("a coverage profile with regions needs their starts, ends and caps");
+            offs.assign(region_offsets, region_offsets + n_refs + 1);
+            if (n_reg) {
+                rs.assign(region_starts, region_starts + n_reg);
+                re.assign(region_ends, region_ends + n_reg);
+                caps.assign(region_caps, region_caps + n_reg);
+            }
+        }
+        std::unique_ptr<qmcp::Solution> solution = hip->solve_ceiling(max_coverage, api, offs, rs, re, caps);
+        std::vector<bam_api::ReadIndex> kept(solution->begin(), solution->end());
+        const std::uint32_t written = api.write_paired_reads(out_path, kept);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        const qmcp_hip_ceiling_stats& cs = hip->last_ceiling_stats();
+        if (cstats != nullptr) *cstats = cs;
+        if (ceiling_report && ceiling_report[0]) {
+            std::FILE* f = std::fopen(ceiling_report, "w");
+            if (f == nullptr) return -5;
+            std::fprintf(f, "#stat\tvalue\n");
+            std::fprintf(f, "reads_placed\t%llu\nreads_dropped\t%llu\nmates_dropped\t%llu\nover_positions\t%llu\n"
+                            "over_bases\t%llu\nshort_positions\t%llu\nshort_bases\t%llu\nexcess_positions\t%llu\n",
+                         (unsigned long long)cs.reads_placed, (unsigned long long)cs.reads_dropped,
+                         (unsigned long long)cs.mates_dropped, (unsigned long long)cs.over_positions,
+                         (unsigned long long)cs.over_bases, (unsigned long long)cs.short_positions,
+                         (unsigned long long)cs.short_bases, (unsigned long long)cs.excess_positions);
+            std::fprintf(f, "max_kept_depth\t%u\nregions_in\t%u\nregions_used\t%u\nrecords_written\t%u\n", cs.max_kept_depth,
+                         cs.regions_in, cs.regions_used, written);
+            if (std::fclose(f) != 0) return -5;
+        }
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // Template-aware ingest alone (BamApiConfig::template_aware; bam_api::read_bam_templates): the segments' columns (cap
 // entries each; segment_records: each segment's BAM record id), the skipped and dropped records (filtered_out, cap_f
 // entries), every reference's length and the number of templates.  Returns the number of segments; -2 when a capacity is

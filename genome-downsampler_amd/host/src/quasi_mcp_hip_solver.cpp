@@ -295,6 +295,54 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_
     return kept;
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_ceiling(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                                           const std::vector<std::uint32_t>& offsets,
+                                                           const std::vector<std::uint32_t>& region_starts,
+                                                           const std::vector<std::uint32_t>& region_ends,
+                                                           const std::vector<std::uint32_t>& caps) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.ceiling() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("ceiling downsampling needs a BamApi built with BamApiConfig::ceiling");
+    const bool with_regions = !offsets.empty();
+    if (with_regions) {
+        if (offsets.size() != reads.contig_lengths.size() + 1) throw std::invalid_argument("cap regions of other references");
+        if (region_starts.size() < offsets.back() || region_ends.size() < offsets.back() || caps.size() < offsets.back())
+            throw std::invalid_argument("cap region arrays are shorter than their offsets say");
+    }
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    const int rc = qmcp_hip_solve_ceiling_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                               reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                               with_regions ? offsets.data() : nullptr, region_starts.data(),
+                                               region_ends.data(), caps.data(), required_cover, QMCP_CEILING_WHOLE_PAIRS,
+                                               mask.data(), &stats_, &clstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_ceiling_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    // the context holds the final mask
+    auto kept = std::make_unique<Solution>();
+    const std::uint64_t upper = clstats_.reads_placed - clstats_.reads_dropped;
+    kept->resize(upper);
+    std::uint64_t n_out = 0;
+    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
+    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
+    kept->resize(n_out);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return kept;
+}
+
 // a record is written iff one of its segments is kept; its segments are consecutive, in file order
 static std::vector<bam_api::BAMReadId> records_of_kept_segments(const bam_api::TemplateSegments& seg,
                                                                 const std::vector<std::uint64_t>& mask) {

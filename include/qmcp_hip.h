@@ -1028,6 +1028,66 @@ int qmcp_hip_solve_templates_profile_device(qmcp_hip_ctx* ctx,
                                             uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                             qmcp_hip_template_stats* tstats, qmcp_hip_template_profile_stats* qstats);
 
+/* Ceiling downsampling: the kept depth never EXCEEDS the cap, and as many reads as possible are kept.  Every other entry
+ * of this header is a floor (kept depth >= min(cov, cap), fewest reads) and may overshoot the cap; this one is for a hard
+ * limit -- a pileup depth limit, a caller that degrades on a 100 000 x hotspot, a fixed memory budget per locus.
+ * Input: reads, contig_ids (QMCP_NO_CONTIG = unplaced), contig_lengths / n_contigs, the region table (region_offsets,
+ * may be NULL, region_starts / region_ends / region_caps), default_cap, limits and read validation exactly as in
+ * qmcp_hip_solve_profile_host; without regions cap(p) = default_cap everywhere.
+ * Answer: per contig, with cov the depth of its placed reads, D is the canonical selection (reads in input order; at the
+ * leftmost position with a deficit take the unselected covering reads with the furthest end, then the furthest start,
+ * then the lowest index: DESIGN.md sections 2 and 4.12) for need(p) = max(0, cov(p) - cap(p)).  D is the set of DROPPED
+ * reads: bit i of the mask is set if and only if read i is placed and not in D.  Unplaced reads are never kept.
+ * Guaranteed: kept(p) <= cap(p) at every position (kept <= cap is dropped >= cov - cap); |D| is minimum, so the kept set
+ * is a maximum-cardinality subset of the placed reads under the ceiling; the result is deterministic; a cap of 0 drops
+ * every read over that position; a contig that is nowhere above its cap keeps every placed read.
+ * NOT guaranteed: kept(p) >= min(cov(p), cap(p)).  A hard ceiling can force the depth below the cap next to a deeper
+ * position; short_positions / short_bases say where and by how much.  Inside a cell (reads of equal start and end) the
+ * lowest index is DROPPED first; a quality-aware choice of which read to drop is not part of this entry.
+ * flags: QMCP_CEILING_WHOLE_PAIRS -- reads (2q, 2q + 1) are pair q (n_reads must be even: QMCP_EINVAL otherwise); after the
+ * solve a read is also dropped when its mate is in D (the mates' bits are ORed inside D before the complement), so the
+ * mask holds whole pairs among the placed reads.  This only lowers depth: the ceiling still holds, but the maximum size
+ * is no longer claimed.  An unplaced mate stays unkept whatever happens to its partner.
+ * Route: the by-contig solve's grouping and batches; every batch with reads takes the sort-based mixed-span route of the
+ * profile entries with need built by k_ceiling_need.  Its cut bit marks need(p) == cov(p) (cov == 0 or cap == 0), the
+ * only positions behind which a stretch may start: where cov > cap over long runs a contig is one serial chain
+ * (limits).  options.cut_points is honoured, nothing is speculated.  A batch that is nowhere above its
+ * caps queues no sweep.  k_ceiling_check then holds the kept depth of every batch against the caps on the device.
+ * Errors: as qmcp_hip_solve_profile_host -- a bad table, null arrays, unknown flag bits and an odd n_reads under
+ * QMCP_CEILING_WHOLE_PAIRS are QMCP_EINVAL, a cap or default_cap of 2^31 or more is QMCP_ERANGE, all on the host before
+ * anything is copied or launched (the output mask is not written); a bad contig id or read is found on the device.
+ * stats (may be NULL): the batch-summed qmcp_hip_stats of the solves that select D (n_kept there counts D).
+ * cstats (may be NULL): see the struct; short_*, excess_positions and max_kept_depth describe the solve's own mask,
+ * before mates are dropped.  The device entry is ordered after hip_stream; both entries block (no _begin / _end form). */
+#define QMCP_CEILING_WHOLE_PAIRS 1u
+typedef struct qmcp_hip_ceiling_stats {
+    uint64_t reads_placed;       /* placed reads                                                                      */
+    uint64_t reads_dropped;      /* placed reads not kept, mates included                                             */
+    uint64_t mates_dropped;      /* of those, the reads dropped only as mates (QMCP_CEILING_WHOLE_PAIRS)              */
+    uint64_t over_positions;     /* positions with cov > cap                                                          */
+    uint64_t over_bases;         /* the sum of cov - cap there                                                        */
+    uint64_t short_positions;    /* positions with kept < min(cov, cap)                                               */
+    uint64_t short_bases;        /* the sum of that shortfall                                                         */
+    uint64_t excess_positions;   /* positions with kept > cap: 0 by contract, counted on the device all the same      */
+    uint32_t max_kept_depth;     /* the largest kept depth                                                            */
+    uint32_t regions_in, regions_used;  /* as in qmcp_hip_profile_stats                                               */
+    float ms_ceiling;            /* device time of k_ceiling_need (+ cut-point scan), k_ceiling_check, k_ceiling_finish */
+} qmcp_hip_ceiling_stats;
+int qmcp_hip_solve_ceiling_host(qmcp_hip_ctx* ctx,
+                                const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids, uint64_t n_reads,
+                                const uint32_t* contig_lengths, uint32_t n_contigs,
+                                const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                uint32_t flags, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                                qmcp_hip_ceiling_stats* cstats);
+int qmcp_hip_solve_ceiling_device(qmcp_hip_ctx* ctx,
+                                  const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                  uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                  const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                  const uint32_t* region_ends, const uint32_t* region_caps, uint32_t default_cap,
+                                  uint32_t flags, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                  qmcp_hip_ceiling_stats* cstats);
+
 #ifdef __cplusplus
 }
 #endif
