@@ -10,6 +10,7 @@ import, and without a GPU every solver call raises :class:`QmcpError`.
 import contextlib
 import ctypes as C
 import heapq
+import math
 import os
 
 import numpy as np
@@ -44,6 +45,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_templates_host", "qmcp_hip_solve_templates_device",
     "qmcp_hip_solve_templates_profile_host", "qmcp_hip_solve_templates_profile_device",
     "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
+    "qmcp_hip_solve_budget_host", "qmcp_hip_solve_budget_device",
 )
 
 QMCP_OK = 0
@@ -54,6 +56,8 @@ TARGETS_KEEP_OFF_TARGET = 1  # QMCP_TARGETS_KEEP_OFF_TARGET
 LADDER_MAX_LEVELS = 16  # QMCP_LADDER_MAX_LEVELS
 PAIR_MAX_STAGES = 16  # QMCP_PAIR_MAX_STAGES
 CEILING_WHOLE_PAIRS = 1  # QMCP_CEILING_WHOLE_PAIRS
+BUDGET_WHOLE_PAIRS = 1  # QMCP_BUDGET_WHOLE_PAIRS
+BUDGET_CURVE_MAX = 8191  # QMCP_BUDGET_CURVE_MAX: the last coverage the curve of a budget solve reaches
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
 DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
@@ -133,6 +137,19 @@ class CeilingStats(C.Structure):
                 ("over_positions", C.c_uint64), ("over_bases", C.c_uint64), ("short_positions", C.c_uint64),
                 ("short_bases", C.c_uint64), ("excess_positions", C.c_uint64), ("max_kept_depth", C.c_uint32),
                 ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_ceiling", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class BudgetStats(C.Structure):
+    """qmcp_hip_budget_stats: the coverage a budget solve ended on (coverage = M*), what it keeps there (n_kept) and
+    what one coverage more would keep (kept_above where a probe measured it, else the lower bound bound_above that
+    ruled it out), the data's depth (reads_placed, total_bases, max_depth, top) and the search's cost"""
+    _fields_ = [("budget", C.c_uint64), ("reads_placed", C.c_uint64), ("n_kept", C.c_uint64), ("kept_above", C.c_uint64),
+                ("bound_above", C.c_uint64), ("total_bases", C.c_uint64), ("coverage", C.c_uint32),
+                ("max_depth", C.c_uint32), ("top", C.c_uint32), ("probes", C.c_uint32), ("curve_entries", C.c_uint32),
+                ("saturated", C.c_uint32), ("ms_budget", C.c_float), ("ms_solves", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -422,6 +439,12 @@ _hip.qmcp_hip_solve_ceiling_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.
 _hip.qmcp_hip_solve_ceiling_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                                C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32,
                                                C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(CeilingStats)]
+_hip.qmcp_hip_solve_budget_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
+                                            C.c_uint64, C.c_uint32, _u64p, C.c_uint32, _u64p, C.POINTER(Stats),
+                                            C.POINTER(BudgetStats)]
+_hip.qmcp_hip_solve_budget_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                              C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(BudgetStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -514,6 +537,12 @@ if _host is not None:
                                                        C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                                        C.c_int, C.c_char_p, C.POINTER(CeilingStats), C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_ceiling.restype = C.c_int64
+    _host.qmcp_host_downsample_bam_budget.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                      C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_double,
+                                                      C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int,
+                                                      C.c_char_p, C.POINTER(BudgetStats), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_budget.restype = C.c_int64
     _host.qmcp_host_read_bam_templates.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _u32p,
                                                    _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, C.c_uint64, _u64p,
                                                    C.POINTER(C.c_uint64), C.c_uint64, _u32p, C.POINTER(C.c_uint64),
@@ -626,6 +655,7 @@ class Solver:
         self.last_template_stats = None
         self.last_template_profile_stats = None
         self.last_ceiling_stats = None
+        self.last_budget_stats = None
 
     def close(self):
         if self._ctx:
@@ -990,6 +1020,62 @@ class Solver:
                                                   C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(cs)))
         self.last_stats, self.last_ceiling_stats = st, cs
         return cs
+
+    @staticmethod
+    def _budget_of(budget_reads, fraction, placed):
+        """the read budget of a budget solve: budget_reads, or floor(fraction * placed reads)"""
+        if (budget_reads is None) == (fraction is None):
+            raise ValueError("a budget solve takes exactly one of budget_reads and fraction")
+        if budget_reads is not None:
+            if int(budget_reads) < 0 or int(budget_reads) >= 1 << 64:
+                raise ValueError("budget_reads must fit an unsigned 64-bit count")
+            return int(budget_reads)
+        if not 0.0 <= float(fraction) <= 1.0:
+            raise ValueError("fraction must lie in 0 .. 1")
+        if placed is None:
+            raise ValueError("fraction needs the number of placed reads (placed_reads=)")
+        return int(math.floor(float(fraction) * int(placed)))
+
+    def solve_budget(self, starts, ends, contig_ids, contig_lengths, max_coverage, budget_reads=None, fraction=None,
+                     flags=0, curve=False):
+        """budget downsampling (qmcp_hip_solve_budget_host): solve_by_contig's reads, and the DEEPEST coverage M* in
+        0 .. min(max_coverage, largest depth) whose solve keeps at most budget_reads reads -- or fraction (0 .. 1) of the
+        placed reads, floor(fraction * placed), counted from contig_ids here.  flags: BUDGET_WHOLE_PAIRS counts and
+        returns whole pairs (reads 2q, 2q + 1) among the placed reads.  -> (mask, M*, BudgetStats), the mask being
+        solve_by_contig's at M* bit for bit (all zero for M* == 0); curve=True appends the curve S(M) = sum of
+        min(cov, M), M = 0 .. min(top, BUDGET_CURVE_MAX), as a uint64 array.  last_stats: the solve at M*"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        budget = self._budget_of(budget_reads, fraction, int(np.count_nonzero(ids != NO_CONTIG)))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        cap = BUDGET_CURVE_MAX + 1 if curve else 0
+        table = np.zeros(cap, dtype=np.uint64) if curve else None
+        st, bs = Stats(), BudgetStats()
+        _check(_hip.qmcp_hip_solve_budget_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                               lengths.size, int(max_coverage), budget, int(flags), _p64(table), cap,
+                                               _p64(mask), C.byref(st), C.byref(bs)))
+        self.last_stats, self.last_budget_stats = st, bs
+        out = (mask[:mask_words(n)], int(bs.coverage), bs)
+        return out + (table[:bs.curve_entries],) if curve else out
+
+    def solve_budget_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_mask,
+                            budget_reads=None, fraction=None, placed_reads=None, flags=0, curve=False, stream=0):
+        """solve_budget on device pointers (ints); the input-order mask is written to d_mask.  fraction needs
+        placed_reads, the number of ids that are not NO_CONTIG.  -> (M*, BudgetStats), with curve=True also the curve"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        budget = self._budget_of(budget_reads, fraction, placed_reads)
+        cap = BUDGET_CURVE_MAX + 1 if curve else 0
+        table = np.zeros(cap, dtype=np.uint64) if curve else None
+        st, bs = Stats(), BudgetStats()
+        _check(_hip.qmcp_hip_solve_budget_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                 C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                 int(max_coverage), budget, int(flags), _p64(table), cap,
+                                                 C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(bs)))
+        self.last_stats, self.last_budget_stats = st, bs
+        out = (int(bs.coverage), bs)
+        return out + (table[:bs.curve_entries],) if curve else out
 
     def solve_pairs(self, starts, ends, contig_ids, contig_lengths, max_coverage, stages=None):
         """pair-aware downsampling (qmcp_hip_solve_pairs_host): reads (2q, 2q + 1) are pair q, stages the rising targets
@@ -2040,7 +2126,7 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None,
                    template_aware=False, split_spliced=True, include_secondary=False, template_stages=None,
                    template_report=None, template_targets=None, template_target_padding=0, template_profile=None,
-                   ceiling=False, ceiling_report=None):
+                   ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2116,8 +2202,53 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     follows (it would put depth back).  The depth may fall below min(coverage, cap) next to deeper positions;
     ceiling_report (a path) gets a stat<TAB>value TSV with the CeilingStats (short_positions, short_bases, ...) and
     records_written.  Needs per_reference=True; not together with targets, report, track, ladder, stratify, dedup,
-    pair_aware, template_aware, amplicon files or "quasi-mcp-hip-quality" (ValueError).  False: nothing changes"""
+    pair_aware, template_aware, amplicon files or "quasi-mcp-hip-quality" (ValueError).  False: nothing changes.
+    budget_reads=N or budget_fraction=f (BamApiConfig::budget_reads / budget_fraction): the deepest downsample that
+    writes at most N records -- or at most floor(f * placed reads), f in 0 .. 1, the placed reads being those that
+    passed the ingest filters.  max_coverage is the upper end of the search; one qmcp_hip_solve_budget_host call with
+    BUDGET_WHOLE_PAIRS on the reads as the ceiling and pair-aware flows pair them finds the largest coverage whose solve,
+    completed to whole pairs, fits.  The output is written from the final mask and no find_pairs follows (it would add
+    reads): records written <= budget.  budget_report (a path) gets a stat<TAB>value TSV with the BudgetStats and
+    records_written, then one M<TAB>bases line per entry of the curve S(M).  Needs per_reference=True; exactly one of
+    the two budgets; not together with targets, report, track, ladder, stratify, dedup, profile, pair_aware,
+    template_aware, ceiling, amplicon files or "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
+    if budget_report is not None and (budget_reads is None) == (budget_fraction is None):
+        raise ValueError("budget_report needs exactly one of budget_reads and budget_fraction")
+    if budget_reads is not None or budget_fraction is not None:
+        if budget_reads is not None and budget_fraction is not None:
+            raise ValueError("budget downsampling takes budget_reads or budget_fraction, not both")
+        if budget_reads is not None and not 0 <= int(budget_reads) < 1 << 64:
+            raise ValueError("budget_reads must fit an unsigned 64-bit count")
+        if budget_fraction is not None and not 0.0 <= float(budget_fraction) <= 1.0:
+            raise ValueError("budget_fraction must lie in 0 .. 1")
+        if not per_reference:
+            raise ValueError("budget downsampling needs per_reference=True")
+        for given, what in ((ceiling, "ceiling"), (pair_aware, "pair_aware"), (template_aware, "template_aware"),
+                            (targets, "targets"), (report, "a depth report"), (track is not None, "a depth track"),
+                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
+                            (dedup, "dedup"), (profile is not None, "a coverage profile")):
+            if given:
+                raise ValueError(f"budget downsampling does not go together with {what}")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("budget downsampling does not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("budget downsampling does not take a solver that grades by quality")
+        err = C.create_string_buffer(1024)
+        bs = BudgetStats()
+        n = _host.qmcp_host_downsample_bam_budget(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq), 1,
+            int(budget_reads is not None), int(budget_reads or 0),
+            float(budget_fraction) if budget_fraction is not None else -1.0, None, None, None, None, 0, None, 0, 0, 0, 0,
+            None, None, 0, str(budget_report).encode() if budget_report else None, C.byref(bs), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return int(n)
     if ceiling_report is not None and not ceiling:
         raise ValueError("ceiling_report needs ceiling=True")
     if ceiling:

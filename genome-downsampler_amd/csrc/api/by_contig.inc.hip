@@ -12,6 +12,8 @@
 // solve (api/ceiling.inc.hip) is a profile whose batches select the DROPPED reads, complemented once the call is through.
 // A pair-aware solve (api/pairs.inc.hip) is this call at its first target, with the further stages run over all batches
 // once the last batch's mask is in place.
+// A budget solve (api/budget.inc.hip) is this call's grouping and batches under a search of its own: several whole solves,
+// each over every batch, at the coverages budget_plan.h picks.
 namespace {
 
 struct LadderRun;
@@ -129,14 +131,15 @@ void batch_roff(const uint32_t* goffs, uint32_t n_contigs, std::vector<uint64_t>
 // One batch of grouped reads (nb > 0 records at bsorted; contigs first_contig .. + n_contigs, offsets from goffs): its
 // columns gathered in grouped order, solved by the ordinary multi-contig solve at M (under `profile`'s caps when given),
 // its mask ORed back into input order, its stats added to `sum`.  roff is left holding the batch's read offsets.
+// gather == false: bc_starts / bc_ends hold this batch's columns already (a budget call of one batch, between its probes).
 int solve_gathered_batch(qmcp_hip_ctx* c, const void* bsorted, uint32_t nb, const uint32_t* d_starts, const uint32_t* d_ends,
                          const uint32_t* goffs, const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs, uint32_t M,
                          ProfileRun* profile, uint64_t* d_mask, std::vector<uint64_t>& roff, qmcp_hip_stats& sum, bool first,
-                         bool largest) {
+                         bool largest, bool gather = true) {
     hipStream_t st = c->stream;
     const uint32_t* bs_starts = (const uint32_t*)c->bc_starts.p;
     const uint32_t* bs_ends = (const uint32_t*)c->bc_ends.p;
-    {
+    if (gather) {
         KernelSpan sp(c, "k_bc_gather");
         qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
     }

@@ -176,7 +176,7 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->pr_credit, &c->pr_cspine, &c->pr_starts, &c->pr_ends, &c->pr_orig, &c->pr_mask, &c->pr_need,
                       &c->pr_stat, &c->tp_ids, &c->tp_flags, &c->tp_sizes, &c->tp_stat,
                       &c->tq_tab, &c->tq_cap, &c->tq_flags, &c->tq_stat,
-                      &c->cl_poff, &c->cl_depth, &c->cl_spine, &c->cl_stat};
+                      &c->cl_poff, &c->cl_depth, &c->cl_spine, &c->cl_stat, &c->bg_acc, &c->bg_mask};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

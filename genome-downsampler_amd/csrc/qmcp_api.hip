@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -27,6 +28,7 @@
 #include "qmcp_kernels.h"
 #include "by_contig_plan.h"
 #include "ladder_plan.h"
+#include "budget_plan.h"
 #include "stratified_plan.h"
 #include "dedup_plan.h"
 #include "amplicon_table.h"
@@ -71,6 +73,8 @@
 //                       caps, later stages build need[] from the scaled region table and the credit
 //   ceiling             kept depth never above the cap, the most reads kept: the profile's batches with the dual need
 //                       max(0, cov(p) - cap(p)) selecting the DROPPED reads, a device-side check, and the complement
+//   budget              the deepest coverage whose by-contig solve fits a number of reads: one grouping, the curve
+//                       S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
@@ -94,3 +98,4 @@
 #include "api/templates.inc.hip"
 #include "api/templates_profile.inc.hip"
 #include "api/ceiling.inc.hip"
+#include "api/budget.inc.hip"

@@ -482,5 +482,23 @@ void launch_ceiling_check(hipStream_t st, const uint32_t* boff, const uint32_t* 
 void launch_ceiling_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, bool whole_pairs, uint64_t* mask,
                            unsigned long long* cst);
 
+// budget downsampling (kernels/budget.inc.hip; api/budget.inc.hip drives them).  launch_budget_tally: cov[0 .. ltot) is a
+// batch's per-position depth; hist (H bins, H <= kBudgetBinsMax) takes min(cov, H - 1), acc the largest depth and the sum of
+// the depths -- both live across the batches of a call, zeroed by the caller.  launch_budget_curve, once: curve[M] =
+// sum over positions of min(cov, M), M = 0 .. H - 1.  launch_budget_finish, per probe under QMCP_BUDGET_WHOLE_PAIRS: mask
+// (ceil(n_reads / 64) words, input order, n_reads even) leaves with the mates (2q, 2q + 1) joined among the placed reads,
+// its popcount added to acc[kBudgetKept].
+static constexpr uint32_t kBudgetBinsMax = QMCP_BUDGET_CURVE_MAX + 1u;  // 32 KiB of LDS per workgroup
+enum BudgetWord : uint32_t {
+    kBudgetMaxDepth = 0,  // the largest depth
+    kBudgetTotalBases,    // the sum of the depths
+    kBudgetKept,          // a probe's reads after pair completion (cleared per probe)
+    kBudgetWords = 4
+};
+void launch_budget_tally(hipStream_t st, const uint32_t* cov, uint32_t ltot, uint32_t H, unsigned long long* acc,
+                         unsigned long long* hist);
+void launch_budget_curve(hipStream_t st, const unsigned long long* hist, uint32_t H, unsigned long long* curve);
+void launch_budget_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, uint64_t* mask, unsigned long long* acc);
+
 }  // namespace qmcp
 #endif

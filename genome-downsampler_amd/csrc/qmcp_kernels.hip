@@ -56,6 +56,8 @@
 //                            and the segments and templates that touch a positive cap
 //   ceiling                  ceiling downsampling: need(p) = max(0, cov(p) - cap(p)) for the dropped set, the check of the
 //                            kept depth against the caps, and the complement over the placed reads (mates joined first)
+//   budget                   budget downsampling: the depth histogram of a call, the curve S(M) = sum of min(cov, M) from
+//                            it, and a probe's pair completion with its popcount
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -100,5 +102,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/templates.inc.hip"
 #include "kernels/templates_profile.inc.hip"
 #include "kernels/ceiling.inc.hip"
+#include "kernels/budget.inc.hip"
 
 }  // namespace qmcp

@@ -12,6 +12,7 @@
 
 #include <cstdint>
 #include <filesystem>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -105,6 +106,14 @@ struct BamApiConfig {
     // counts where.  Needs per_reference; goes together with a coverage profile and with nothing else pair_aware refuses,
     // and not with pair_aware or template_aware (std::invalid_argument otherwise).  false: nothing changes.
     bool ceiling = false;
+    // Budget downsampling: the deepest coverage in 0 .. min(max_coverage, largest depth) whose solve, completed to whole
+    // pairs, writes at most budget_reads records -- or at most floor(budget_fraction * placed reads), the placed reads
+    // being those that passed the ingest filters (QuasiMcpHipSolver::solve_budget / qmcp_hip_solve_budget_host with
+    // QMCP_BUDGET_WHOLE_PAIRS).  The output is written from the final mask WITHOUT find_pairs, which would add reads.
+    // Exactly one of the two; budget_fraction in 0 .. 1.  Needs per_reference and goes together with nothing that
+    // ceiling refuses, nor with ceiling or a coverage profile (std::invalid_argument otherwise).  Neither: nothing changes.
+    std::optional<std::uint64_t> budget_reads;
+    std::optional<double> budget_fraction;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -152,6 +161,9 @@ class BamApi {
     const std::vector<std::uint32_t>& pair_stages() const { return pair_stages_; }
     // BamApiConfig::ceiling
     bool ceiling() const { return ceiling_; }
+    // BamApiConfig::budget_reads / budget_fraction: whether one is set, and the budget for a number of placed reads
+    bool budget() const { return budget_reads_.has_value() || budget_fraction_.has_value(); }
+    std::uint64_t budget_for(std::uint64_t placed_reads) const;
     // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
     // get_template_segments call, which also fills get_filtered_out_reads
     bool template_aware() const { return template_aware_; }
@@ -194,6 +206,8 @@ class BamApi {
     bool dedup_ = false;
     bool pair_aware_ = false;
     bool ceiling_ = false;
+    std::optional<std::uint64_t> budget_reads_;
+    std::optional<double> budget_fraction_;
     std::vector<std::uint32_t> pair_stages_;
     bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false;
     std::vector<std::uint32_t> template_stages_;

@@ -118,6 +118,14 @@ class QuasiMcpHipSolver : public Solver {
                                             const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
                                             const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps);
     const qmcp_hip_ceiling_stats& last_ceiling_stats() const { return clstats_; }
+    // Budget downsampling for the reads of a BamApi built with BamApiConfig::budget_reads or budget_fraction: one
+    // qmcp_hip_solve_budget_host call with QMCP_BUDGET_WHOLE_PAIRS, required_cover as the upper end of the search and
+    // BamApi::budget_for(placed reads) as the budget.  The Solution holds whole pairs already -- the caller writes it
+    // without find_pairs.  std::invalid_argument for a BamApi without a budget and for what the library refuses
+    std::unique_ptr<Solution> solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_budget_stats& last_budget_stats() const { return bgstats_; }
+    // S(M) = the bases any answer at coverage M must hold, M = 0 .. last_budget_stats().curve_entries - 1
+    const std::vector<std::uint64_t>& last_budget_curve() const { return budget_curve_; }
     // Template-aware downsampling for a BamApi built with BamApiConfig::template_aware: qmcp_hip_solve_templates_host on
     // its segments under its template_stages (empty: the default schedule).  Returns the ids of the records whose
     // template is kept (ascending) -- the caller writes them with BamApi::write_records, without find_pairs.
@@ -160,6 +168,8 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_ceiling_stats clstats_{};
+    qmcp_hip_budget_stats bgstats_{};
+    std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_template_stats tpstats_{};
     qmcp_hip_template_profile_stats tqstats_{};
     std::vector<std::uint64_t> dedup_hist_;

@@ -1,6 +1,8 @@
 // In-memory BamApi (see include/bam-api/bam_api.hpp for the reference lines mirrored).
 #include "bam-api/bam_api.hpp"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -150,6 +152,32 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
         if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
             throw std::invalid_argument("ceiling downsampling does not take amplicon files");
         ceiling_ = true;
+    }
+    if (config.budget_reads.has_value() || config.budget_fraction.has_value()) {
+        if (config.budget_reads.has_value() && config.budget_fraction.has_value())
+            throw std::invalid_argument("budget downsampling takes budget_reads or budget_fraction, not both");
+        if (config.budget_fraction.has_value() && !(*config.budget_fraction >= 0.0 && *config.budget_fraction <= 1.0))
+            throw std::invalid_argument("budget_fraction must lie in 0 .. 1");
+        if (!per_reference_)
+            throw std::invalid_argument("budget downsampling needs per_reference: its probes are solved one reference at "
+                                        "a time");
+        if (config.ceiling) throw std::invalid_argument("budget downsampling does not take ceiling");
+        if (config.pair_aware) throw std::invalid_argument("budget downsampling does not take pair_aware");
+        if (config.template_aware) throw std::invalid_argument("budget downsampling does not take template_aware");
+        if (!config.targets_filepath.empty()) throw std::invalid_argument("budget downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("budget downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("budget downsampling does not take a depth report");
+        if (!config.depth_track_filepath.empty())
+            throw std::invalid_argument("budget downsampling does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("budget downsampling does not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("budget downsampling does not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("budget downsampling does not take amplicon files");
+        budget_reads_ = config.budget_reads;
+        budget_fraction_ = config.budget_fraction;
     }
     if (config.template_aware) {
         if (!per_reference_)
@@ -367,6 +395,13 @@ std::vector<std::uint32_t> BamApi::find_filtered_cover(const std::vector<ReadInd
         for (Index p = r.start_ind; p <= r.end_ind; ++p) ++cover[p];
     }
     return cover;
+}
+
+std::uint64_t BamApi::budget_for(std::uint64_t placed_reads) const {
+    if (budget_reads_.has_value()) return *budget_reads_;
+    if (!budget_fraction_.has_value()) throw std::invalid_argument("this BamApi was built without a budget");
+    const double want = std::floor(*budget_fraction_ * static_cast<double>(placed_reads));
+    return std::min(static_cast<std::uint64_t>(want), placed_reads);
 }
 
 }  // namespace bam_api

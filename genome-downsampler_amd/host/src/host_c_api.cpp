@@ -1149,6 +1149,88 @@ std::int64_t qmcp_host_downsample_bam_ceiling(const char* solver_name, const cha
     }
 }
 
+// The file-to-file flow with BamApiConfig::budget_reads / budget_fraction: one per-reference ingest, one
+// qmcp_hip_solve_budget_host call with QMCP_BUDGET_WHOLE_PAIRS (QuasiMcpHipSolver::solve_budget) -- max_coverage is the
+// upper end of the search -- and write_paired_reads from its mask: whole pairs already, and NO find_pairs, which would
+// add reads, so the records written stay within the budget.  has_budget_reads != 0: budget_reads counts; budget_fraction
+// >= 0: the fraction of the placed reads that passed the ingest filters; both or neither are handed on for BamApiConfig
+// and this function to refuse.  targets / report / track / ladder_levels / stratify / dedup / pair_aware / template_aware /
+// ceiling / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given so that it refuses the combinations it
+// refuses; a solver that grades by quality is refused here.  budget_report (may be NULL): a TSV stat<TAB>value with the
+// qmcp_hip_budget_stats and the records written, then one M<TAB>bases line per entry of the curve.  bstats (may be NULL)
+// takes the stats.  Returns the number of records written; -1 on an unknown solver, -3 out of memory, -4 with a message
+// in err when the configuration is refused, -5 when the report cannot be written.
+std::int64_t qmcp_host_downsample_bam_budget(const char* solver_name, const char* in_path, const char* out_path,
+                                             const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                             std::uint32_t min_mapq, int per_reference, int has_budget_reads,
+                                             std::uint64_t budget_reads, double budget_fraction, const char* targets,
+                                             const char* report, const char* track, const std::uint32_t* ladder_levels,
+                                             std::uint32_t n_ladder_levels, const char* stratify, int dedup, int pair_aware,
+                                             int template_aware, int ceiling, const char* bed, const char* tsv,
+                                             int amplicons_by_reference, const char* budget_report,
+                                             qmcp_hip_budget_stats* bstats, char* err, std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        if (has_budget_reads != 0) cfg.budget_reads = budget_reads;
+        if (budget_fraction >= 0.0 || budget_fraction != budget_fraction) cfg.budget_fraction = budget_fraction;
+        if (!cfg.budget_reads.has_value() && !cfg.budget_fraction.has_value())
+            throw std::invalid_argument("budget downsampling needs budget_reads or budget_fraction");
+        cfg.ceiling = ceiling != 0;
+        cfg.pair_aware = pair_aware != 0;
+        cfg.template_aware = template_aware != 0;
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (track && track[0]) cfg.depth_track_filepath = track;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
+        cfg.dedup = dedup != 0;
+        if (bed && bed[0]) cfg.bed_filepath = bed;
+        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("budget downsampling does not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no budget downsampling");
+        bam_api::BamApi api(in_path, cfg);
+        std::unique_ptr<qmcp::Solution> solution = hip->solve_budget(max_coverage, api);
+        std::vector<bam_api::ReadIndex> kept(solution->begin(), solution->end());
+        const std::uint32_t written = api.write_paired_reads(out_path, kept);
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        const qmcp_hip_budget_stats& bs = hip->last_budget_stats();
+        if (bstats != nullptr) *bstats = bs;
+        if (budget_report && budget_report[0]) {
+            std::FILE* f = std::fopen(budget_report, "w");
+            if (f == nullptr) return -5;
+            std::fprintf(f, "#stat\tvalue\n");
+            std::fprintf(f, "budget\t%llu\nreads_placed\t%llu\nn_kept\t%llu\nkept_above\t%llu\nbound_above\t%llu\n"
+                            "total_bases\t%llu\n",
+                         (unsigned long long)bs.budget, (unsigned long long)bs.reads_placed, (unsigned long long)bs.n_kept,
+                         (unsigned long long)bs.kept_above, (unsigned long long)bs.bound_above,
+                         (unsigned long long)bs.total_bases);
+            std::fprintf(f, "coverage\t%u\nmax_depth\t%u\ntop\t%u\nprobes\t%u\ncurve_entries\t%u\nsaturated\t%u\n"
+                            "ms_budget\t%.6g\nms_solves\t%.6g\nrecords_written\t%u\n",
+                         bs.coverage, bs.max_depth, bs.top, bs.probes, bs.curve_entries, bs.saturated, (double)bs.ms_budget,
+                         (double)bs.ms_solves, written);
+            std::fprintf(f, "#M\tbases\n");
+            const std::vector<std::uint64_t>& curve = hip->last_budget_curve();
+            for (std::size_t m = 0; m < curve.size(); ++m)
+                std::fprintf(f, "%zu\t%llu\n", m, (unsigned long long)curve[m]);
+            if (std::fclose(f) != 0) return -5;
+        }
+        return (std::int64_t)written;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // Template-aware ingest alone (BamApiConfig::template_aware; bam_api::read_bam_templates): the segments' columns (cap
 // entries each; segment_records: each segment's BAM record id), the skipped and dropped records (filtered_out, cap_f
 // entries), every reference's length and the number of templates.  Returns the number of segments; -2 when a capacity is

@@ -343,6 +343,48 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_ceiling(std::uint32_t require
     return kept;
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.budget() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("budget downsampling needs a BamApi built with BamApiConfig::budget_reads or "
+                                    "budget_fraction");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    std::uint64_t placed = 0;
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+        ++placed;
+    }
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    budget_curve_.assign(QMCP_BUDGET_CURVE_MAX + 1u, 0);
+    const int rc = qmcp_hip_solve_budget_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                              reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                              required_cover, bam_api.budget_for(placed), QMCP_BUDGET_WHOLE_PAIRS,
+                                              budget_curve_.data(), (std::uint32_t)budget_curve_.size(), mask.data(),
+                                              &stats_, &bgstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_budget_host", rc);
+    budget_curve_.resize(bgstats_.curve_entries);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    // the context holds the final mask
+    auto kept = std::make_unique<Solution>();
+    kept->resize(bgstats_.n_kept);
+    std::uint64_t n_out = 0;
+    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), bgstats_.n_kept, &n_out);
+    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
+    kept->resize(n_out);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return kept;
+}
+
 // a record is written iff one of its segments is kept; its segments are consecutive, in file order
 static std::vector<bam_api::BAMReadId> records_of_kept_segments(const bam_api::TemplateSegments& seg,
                                                                 const std::vector<std::uint64_t>& mask) {

@@ -1088,6 +1088,66 @@ int qmcp_hip_solve_ceiling_device(qmcp_hip_ctx* ctx,
                                   uint32_t flags, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                   qmcp_hip_ceiling_stats* cstats);
 
+/* Budget downsampling: the deepest coverage whose by-contig solve fits a number of reads.  Every other entry takes a
+ * coverage and returns however many reads that costs; this one takes the reads a caller can afford (what samtools view -s,
+ * Picard DownsampleSam and seqtk sample ask for) and searches the coverage on the device: one grouping, one pass over the
+ * depth, a few whole solves.
+ * Input: reads in any order, contig_ids (QMCP_NO_CONTIG = unplaced), contig_lengths / n_contigs, limits and read
+ * validation exactly as in qmcp_hip_solve_by_contig_host; max_coverage (1 .. 2^31 - 1) is the upper end of the search.
+ * Definitions: count(M), M >= 1, is the popcount of the mask qmcp_hip_solve_by_contig_host returns at M; under
+ * QMCP_BUDGET_WHOLE_PAIRS after completion -- reads (2q, 2q + 1) are pair q (n_reads must be even), a placed read is
+ * also kept when its placed mate is, an unplaced mate is never kept.  count(0) = 0.  top = min(max_coverage, largest depth
+ * of the placed reads).
+ * Answer: a coverage M* in 0 .. top (bstats->coverage) with
+ *   (1) count(M*) <= budget_reads, and
+ *   (2) M* == top or count(M* + 1) > budget_reads,
+ * and in keep_mask_out exactly that solve's mask (after completion under the flag), bit for bit; M* == 0 is the all-zero
+ * mask.  The result is deterministic.
+ * Without the flag count is monotone -- the canonical selection has minimum cardinality among the covers of
+ * need_M = min(cov, M), and need_M <= need_(M + 1) makes every cover for M + 1 a cover for M -- so M* is
+ * the one largest feasible coverage.  WITH the flag monotonicity has been observed and is NOT proven: only (1) and (2) are
+ * promised.  budget_reads >= the placed reads gives M* == top, and where top is the largest depth (max_coverage at least
+ * that) every placed read is kept: saturated = 1.
+ * curve_out (may be NULL, then curve_capacity must be 0): curve_out[M] = S(M) = the sum over all positions of
+ * min(cov(p), M) for M = 0 .. min(top, QMCP_BUDGET_CURVE_MAX, curve_capacity - 1): the bases any valid answer at M must
+ * hold -- read it to pick a budget.  A HOST array in both entries; bstats->curve_entries says how many were written.
+ * Errors: null arrays, unknown flag bits, an odd n_reads under QMCP_BUDGET_WHOLE_PAIRS, max_coverage == 0 or a
+ * curve_capacity without curve_out are QMCP_EINVAL, max_coverage >= 2^31 is QMCP_ERANGE, all on the host before anything
+ * is copied or launched; a bad contig id or read is found on the device with the codes of the by-contig entry.  The
+ * output mask is written by a successful call only.
+ * stats (may be NULL): the batch-summed qmcp_hip_stats of the probe at M* (zeros for M* == 0).  bstats (may be NULL): see
+ * the struct.  The device entry is ordered after hip_stream; both entries block (no _begin / _end form). */
+#define QMCP_BUDGET_WHOLE_PAIRS 1u
+#define QMCP_BUDGET_CURVE_MAX 8191u
+typedef struct qmcp_hip_budget_stats {
+    uint64_t budget;         /* the budget given                                                                      */
+    uint64_t reads_placed;   /* placed reads                                                                          */
+    uint64_t n_kept;         /* count(M*)                                                                             */
+    uint64_t kept_above;     /* count(M* + 1) when a probe measured it, else 0                                        */
+    uint64_t bound_above;    /* else the lower bound of count(M* + 1) that ruled M* + 1 out; 0 when M* == top         */
+    uint64_t total_bases;    /* the sum of the depth over all positions                                               */
+    uint32_t coverage;       /* M*                                                                                    */
+    uint32_t max_depth;      /* the largest depth of the placed reads                                                 */
+    uint32_t top;            /* min(max_coverage, max_depth)                                                          */
+    uint32_t probes;         /* whole solves run                                                                      */
+    uint32_t curve_entries;  /* entries written to curve_out                                                          */
+    uint32_t saturated;      /* 1 when every placed read is kept                                                      */
+    float ms_budget;         /* device time of k_budget_tally, k_budget_curve and k_budget_finish                     */
+    float ms_solves;         /* device time of the probes' solves                                                     */
+} qmcp_hip_budget_stats;
+int qmcp_hip_solve_budget_host(qmcp_hip_ctx* ctx,
+                               const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids, uint64_t n_reads,
+                               const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                               uint64_t budget_reads, uint32_t flags, uint64_t* curve_out /* may be NULL */,
+                               uint32_t curve_capacity, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                               qmcp_hip_budget_stats* bstats);
+int qmcp_hip_solve_budget_device(qmcp_hip_ctx* ctx,
+                                 const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                 uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                 uint64_t budget_reads, uint32_t flags, uint64_t* curve_out /* host; may be NULL */,
+                                 uint32_t curve_capacity, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                 qmcp_hip_budget_stats* bstats);
+
 #ifdef __cplusplus
 }
 #endif
