@@ -95,7 +95,7 @@ class Stats(C.Structure):
         ("spec_retry_mismatches", C.c_uint32), ("sweep_blocks_changed", C.c_uint32), ("sweep_blocks", C.c_uint32),
         ("arena_grown_mid_solve", C.c_uint32), ("near_uniform_exceptions", C.c_uint32),
         ("near_uniform_selected", C.c_uint32), ("near_uniform_rounds", C.c_uint32),
-        ("near_uniform_giveup", C.c_uint32),
+        ("near_uniform_giveup", C.c_uint32), ("pm_grid", C.c_int32), ("pm_heaviest_wave_slots", C.c_uint32),
     ]
 
     def as_dict(self):
@@ -300,7 +300,7 @@ class Options(C.Structure):
         ("near_uniform_rounds", C.c_uint32), ("near_uniform_min_depth", C.c_float), ("near_uniform_debug", C.c_int32),
         ("force_sort_route", C.c_int32), ("keep_expand", C.c_int32), ("mixed_sweep_in_lds", C.c_int32),
         ("rank_min_reads", C.c_uint32), ("host_threads", C.c_uint32), ("copy_streams", C.c_uint32),
-        ("host_both_columns", C.c_int32),
+        ("host_both_columns", C.c_int32), ("pm_grid", C.c_int32),
     ]
 
 

@@ -49,6 +49,8 @@ struct SolveRun {
     bool ranked_counted = false, wait_empty = false;
     bool pm = false;                    // range-ranked route in its pass-major form (kernels/pass_major.inc.hip)
     uint32_t range_shift = 0;
+    uint32_t pm_ranges = 0;             // ... the ranges of the grid it cuts (pm_grid_plan.h), and whether that is the aligned one
+    bool pm_aligned = false;
     uint32_t nu_filter = 0;             // near-uniform route: the span the head's producer treated as regular (0: every read)
 };
 
@@ -71,6 +73,12 @@ struct qmcp_hip_ctx {
     DevBuf rankamb;    // range-ranked path: per-range lists of quota-crossing groups, settled in the walk's tail
     // pass-major form (kernels/pass_major.inc.hip): one descriptor word per wave-slot; the table stage's working words
     DevBuf pm_desc, pm_work;
+    // ... and the grid's tables (pm_grid_plan.h): on the device, in pinned staging, and as last uploaded
+    DevBuf pm_grid;
+    uint32_t* h_pm_grid = nullptr;
+    size_t h_pm_grid_cap = 0;
+    std::vector<uint32_t> pm_grid_sent;
+    void* pm_grid_dev = nullptr;
     // near-uniform route (kernels/near_uniform.inc.hip): the dominant span of the last call that took it -- the next
     // call's head filters on it at once -- and the route's buffers
     uint32_t nu_ell = 0;
@@ -316,6 +324,24 @@ int upload_tables(qmcp_hip_ctx* c, const uint64_t* roff, const Problem& pr) {
     c->tables_dev_poff = c->poff.p;
     HIP_TRY(hipMemcpyAsync(c->roff.p, c->h_tables, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->poff.p, c->h_tables + count, bytes, hipMemcpyHostToDevice, c->stream));
+    return QMCP_OK;
+}
+
+// The pass-major grid's tables, with the contig tables: one small copy, skipped while the grid stays what it was.
+int upload_pm_grid(qmcp_hip_ctx* c, const qmcp::PmGridPlan& grid) {
+    const size_t words = grid.words.size(), bytes = words * sizeof(uint32_t);
+    TRY(ensure(c, c->pm_grid, bytes));
+    if (c->h_pm_grid_cap < words) {
+        if (c->h_pm_grid) HIP_TRY(hipHostFree(c->h_pm_grid));
+        c->h_pm_grid = nullptr;
+        HIP_TRY(hipHostMalloc((void**)&c->h_pm_grid, bytes, hipHostMallocDefault));
+        c->h_pm_grid_cap = words;
+    }
+    if (c->pm_grid_dev == c->pm_grid.p && c->pm_grid_sent == grid.words) return QMCP_OK;
+    std::memcpy(c->h_pm_grid, grid.words.data(), bytes);
+    c->pm_grid_sent = grid.words;
+    c->pm_grid_dev = c->pm_grid.p;
+    HIP_TRY(hipMemcpyAsync(c->pm_grid.p, c->h_pm_grid, bytes, hipMemcpyHostToDevice, c->stream));
     return QMCP_OK;
 }
 

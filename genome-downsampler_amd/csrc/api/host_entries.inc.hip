@@ -158,7 +158,7 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
     DevBuf* bufs[] = {&c->roff, &c->poff, &c->stats, &c->cstart, &c->boff, &c->ecnt, &c->eoff,
                       &c->selend, &c->spine, &c->hist, &c->spine2, &c->hist2, &c->keys[0], &c->keys[1], &c->vals[0],
                       &c->vals[1], &c->in_starts, &c->in_ends, &c->in_aux0, &c->in_aux1, &c->mask,
-                      &c->cov, &c->amp, &c->scalars, &c->next_head, &c->ranges, &c->rankamb, &c->pm_desc, &c->pm_work, &c->segs, &c->specsnap, &c->specflags, &c->rings, &c->evpk, &c->evlast, &c->kidx, &c->f_starts, &c->f_ends, &c->f_map, &c->f_words, &c->f_mask, &c->nu_exc, &c->nu_nadj, &c->nu_ce, &c->nu_state, &c->nu_sus, &c->nu_ckpt, &c->nu_prev,
+                      &c->cov, &c->amp, &c->scalars, &c->next_head, &c->ranges, &c->rankamb, &c->pm_desc, &c->pm_work, &c->pm_grid, &c->segs, &c->specsnap, &c->specflags, &c->rings, &c->evpk, &c->evlast, &c->kidx, &c->f_starts, &c->f_ends, &c->f_map, &c->f_words, &c->f_mask, &c->nu_exc, &c->nu_nadj, &c->nu_ce, &c->nu_state, &c->nu_sus, &c->nu_ckpt, &c->nu_prev,
                       &c->bc_key, &c->bc_rec[0], &c->bc_rec[1], &c->bc_hist, &c->bc_spine, &c->bc_offs, &c->bc_err, &c->bc_len,
                       &c->bc_starts, &c->bc_ends, &c->bc_mask, &c->af_ids, &c->af_ids_c, &c->af_len, &c->af_tab,
                       &c->af_err, &c->qc_words, &c->qc_tab, &c->qc_bare, &c->qc_keys[0], &c->qc_keys[1],
@@ -185,6 +185,7 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
     for (auto& sp : c->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_tables) (void)hipHostFree(c->h_tables);
+    if (c->h_pm_grid) (void)hipHostFree(c->h_pm_grid);
     if (c->h_scalars) (void)hipHostFree(c->h_scalars);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_mask) (void)hipHostFree(c->h_mask);

@@ -6,18 +6,20 @@ int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun);
 // The pass-major form of the range-ranked route (kernels/pass_major.inc.hip) pads every (range, pass) slice to whole
 // groups of 64 slots: it pays where slices are long -- a pass's 8 192 reads over the ranges its contig spans --, and
 // where they would be short (narrow ranges: small genomes) the padding is most of a group and the range-major form is
-// kept.  Hard limits: one partition level, slots addressable with 32-bit byte offsets.
-bool pm_route_ok(const qmcp_hip_ctx* c, const uint64_t* roff, const Problem& pr, uint32_t shift) {
+// kept.  Hard limits: one partition level, slots addressable with 32-bit byte offsets.  Ranges and slices are those of
+// the grid the call would take (pm_grid_plan.h).
+bool pm_route_ok(const qmcp_hip_ctx* c, const uint64_t* roff, const Problem& pr, uint32_t shift, const qmcp::PmGridPlan& grid) {
     if (c->opt.pass_major < 0) return false;  // (A/B: the range-major form)
-    const uint32_t n = (uint32_t)pr.n, ltot = (uint32_t)pr.ltot;
-    if ((uint64_t)qmcp::pm_slots(n, ltot, shift) >= (1ull << 31)) return false;
+    const uint32_t n = (uint32_t)pr.n;
+    if ((uint64_t)qmcp::pm_slots(n, grid.n_ranges) >= (1ull << 31)) return false;
     if (c->opt.pass_major > 0) return true;   // (tests: the form on small inputs)
     // expected wave-slots against the records' own 1 / 64: a contig's pass deals its reads to the ranges the contig spans
     double slots = 0.0;
     for (uint32_t k = 0; k < pr.n_contigs; ++k) {
         const uint64_t reads = roff[k + 1] - roff[k];
         if (reads == 0 || pr.poff[k + 1] == pr.poff[k]) continue;
-        const double ranges = (double)(((pr.poff[k + 1] - 1) >> shift) - (pr.poff[k] >> shift) + 1);
+        const double ranges = grid.aligned ? (double)((pr.poff[k + 1] - pr.poff[k] + ((1ull << shift) - 1)) >> shift)
+                                           : (double)(((pr.poff[k + 1] - 1) >> shift) - (pr.poff[k] >> shift) + 1);
         const double passes = (double)reads / (double)qmcp::pm_pass() < 1.0 ? 1.0 : (double)reads / (double)qmcp::pm_pass();
         const double slice = (double)reads / (passes * ranges);
         slots += passes * ranges * std::ceil(slice / 64.0);
@@ -59,6 +61,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     // size the whole arena before anything is enqueued (growing a buffer frees it, and
     // hipFree would stall on the work in flight)
     c->sized = false;
+    qmcp::PmGridPlan grid;
     {
         const uint32_t tiles_seg = qmcp::seg_tile_bound(n);  // second partition level: tiles aligned to super-ranges
         const uint32_t spine_a = qmcp::scan_spine_entries(256u * tiles_seg);
@@ -66,9 +69,14 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         TRY(ensure(c, c->spine, (size_t)(spine_a > spine_b ? spine_a : spine_b) * sizeof(uint32_t) + 16));
         TRY(ensure(c, c->hist, (size_t)256 * tiles_seg * sizeof(uint32_t)));
         // (the pass-major form's two 16-bit record streams live in keys[0] and keys[1]: padded slices, ~6 B per read)
-        const bool may_pm = n >= rank_min_reads(c) && qmcp::range_path_supported(ltot) && !qmcp::range_path_two_level(ltot) &&
-                            pm_route_ok(c, roff, pr, qmcp::range_shift_for(ltot));
-        const size_t pm_bytes = may_pm ? qmcp::pm_slots(n, ltot, qmcp::range_shift_for(ltot)) * sizeof(uint16_t) : 0;
+        // (which grid the form cuts its ranges on is decided here, before anything is queued: every size below follows it)
+        const bool one_level = n >= rank_min_reads(c) && qmcp::range_path_supported(ltot) && !qmcp::range_path_two_level(ltot);
+        if (one_level) grid = qmcp::pm_grid_plan(roff, pr.poff.data(), n_contigs, qmcp::range_shift_for(ltot), qmcp::pm_pass(), c->opt.pm_grid);
+        const bool may_pm = one_level && pm_route_ok(c, roff, pr, qmcp::range_shift_for(ltot), grid);
+        run.pm = may_pm;
+        run.pm_ranges = grid.n_ranges;
+        run.pm_aligned = grid.aligned != 0;
+        const size_t pm_bytes = may_pm ? qmcp::pm_slots(n, grid.n_ranges) * sizeof(uint16_t) : 0;
         TRY(ensure(c, c->keys[0], std::max((size_t)n * sizeof(uint64_t), pm_bytes)));
         TRY(ensure(c, c->keys[1], std::max((size_t)n * sizeof(uint64_t), pm_bytes)));
         if (may_pm) {
@@ -89,7 +97,8 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         TRY(ensure(c, c->specsnap, qmcp::spec_snap_bytes(4096)));            // ... and the mixed-span walk's states at boundaries
         TRY(ensure(c, c->ranges, (65537 + 7 + 771 + 5) * sizeof(uint32_t)));  // range starts, heaviest load, level-2 tables
         if (n >= rank_min_reads(c) && qmcp::range_path_supported(ltot))
-            TRY(ensure(c, c->rankamb, qmcp::rank_scratch_bytes(qmcp::range_shift_for(ltot), ltot, n)));
+            TRY(ensure(c, c->rankamb, std::max(qmcp::rank_scratch_bytes(qmcp::range_shift_for(ltot), ltot, n),
+                                               may_pm ? qmcp::pm_rank_scratch_bytes(qmcp::range_shift_for(ltot), grid.n_ranges, n) : (size_t)0)));
         TRY(ensure(c, c->stats, 12 * sizeof(uint32_t)));  // (words 6..8: the mixed-span route's sample of the spans)
         // (the near-uniform route's buffers: a context that has met mixed spans may look at the route on any call)
         if (c->nu_ell != 0 || c->mixed_seen) TRY(ensure_near_uniform(c, n, ltot, n_contigs));
@@ -106,6 +115,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     c->grew_mid_solve = 0;
     HIP_TRY(hipEventRecord(c->ev[EV_BEGIN], c->stream));
     TRY(upload_tables(c, roff, pr));
+    if (run.pm) TRY(upload_pm_grid(c, grid));
     c->sized = true;
 
     uint32_t* const hs = c->h_head;  // pinned: [0..2] span min / max / error flag, [3] heaviest range, [4] empty positions
@@ -118,7 +128,6 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     uint32_t* d_max_load = d_range_start + 65540;
     uint32_t* d_seg_tables = d_range_start + 65544;  // super_start, tile_base, pass_base (257 each)
     run.two_level = qmcp::range_path_two_level(ltot);
-    const bool two_level = run.two_level;
     hs[3] = 0;
     hs[4] = 0xFFFFFFFFu;  // unknown unless the range-ranked route counted them
     run.have_gstart = true;
@@ -139,7 +148,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         hipStream_t s1 = c->stream;
         // (one copy of eight words from pinned memory: span minimum, and zeros for everything the head counts)
         HIP_TRY(hipMemcpyAsync(c->stats.p, c->h_stats_init, 8 * sizeof(uint32_t), hipMemcpyHostToDevice, s1));
-        run.pm = !two_level && pm_route_ok(c, roff, pr, range_shift);
+        if (run.pm) local.pm_grid = run.pm_aligned ? 1 : -1;
         run.nu_filter = c->nu_ell;
         hs[5] = hs[6] = 0;
         if (run.pm) {
@@ -157,6 +166,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
         HIP_TRY(hipMemcpyAsync(hs, c->stats.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
         HIP_TRY(hipMemcpyAsync(hs + 3, d_max_load, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
+        if (run.pm) HIP_TRY(hipMemcpyAsync(hs + 7, d_max_load + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));  // (the heaviest range's wave-slots: stats only)
         if (run.nu_filter) HIP_TRY(hipMemcpyAsync(hs + 5, (uint32_t*)c->stats.p + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
         // How spiky the starts are only decides WHICH exact sweep kernel runs, so the count of the previous
         // call of this shape is good enough (and saves waiting for k_range_offsets); a first call waits.
@@ -246,6 +256,7 @@ int queue_rm_head(qmcp_hip_ctx* c, hipStream_t s1, uint32_t filter, bool clear_m
 int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) {
     SolveRun& run = c->run;
     const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot, n_contigs = run.n_contigs;
+    const uint32_t* d_grid = (const uint32_t*)c->pm_grid.p;
     uint32_t* d_stats = (uint32_t*)c->stats.p;
     // (a re-run must not add to what the first run counted -- empty positions, exceptions, list flag, overflow entries;
     //  the first run's words were cleared with the statistics' initial values)
@@ -255,7 +266,7 @@ int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) 
     {
         KernelSpan sp(c, "k_pm_prepare_sort", st);
         qmcp::launch_pm_prepare_sort(st, run.d_starts, run.d_ends, n, (const uint64_t*)c->roff.p, (const uint64_t*)c->poff.p,
-                                     n_contigs, run.range_shift, ltot, (uint16_t*)c->keys[0].p, (uint16_t*)c->keys[1].p,
+                                     n_contigs, run.range_shift, run.pm_ranges, d_grid, (uint16_t*)c->keys[0].p, (uint16_t*)c->keys[1].p,
                                      (uint32_t*)c->hist2.p, (uint32_t*)c->hist.p, d_stats, (unsigned long long*)run.d_mask, filter,
                                      filter ? (uint32_t*)c->nu_exc.p : nullptr, nu_cap_for(n),
                                      filter ? qmcp::nu_exc_counts((uint32_t*)c->nu_exc.p, nu_cap_for(n)) : nullptr);
@@ -268,7 +279,7 @@ int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) 
     }
     {
         KernelSpan sp(c, "k_pm_tables", st);
-        qmcp::launch_pm_tables(st, (uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, ltot, run.range_shift,
+        qmcp::launch_pm_tables(st, (uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, run.pm_ranges,
                                (uint32_t*)c->pm_desc.p, (const uint32_t*)c->pm_work.p, d_range_start, d_max_load,
                                rerun ? nullptr : (uint32_t*)c->scalars.p);  // (the result scalars, 64 bytes: cleared here for the one-span tail)
     }
@@ -276,7 +287,7 @@ int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) 
     {
         KernelSpan sp(c, "k_pm_offsets", st);
         qmcp::launch_pm_offsets(st, (const uint16_t*)c->keys[0].p, (const uint32_t*)c->pm_desc.p, (const uint32_t*)c->hist2.p, n,
-                                d_range_start, run.range_shift, ltot, (uint32_t*)c->boff.p, d_stats + 3);
+                                d_range_start, run.range_shift, run.pm_ranges, d_grid, ltot, (uint32_t*)c->boff.p, d_stats + 3);
     }
     HIP_TRY(hipGetLastError());
     run.nu_filter = filter;
@@ -286,12 +297,12 @@ int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) 
 // The ranking of the pass-major form on `st`: the ordered walk; the quota-crossing groups it lists are settled in its tail.
 void queue_pm_rank(qmcp_hip_ctx* c, hipStream_t st, const uint32_t* ev_sev, const uint32_t* ev_lastns, uint32_t ell) {
     SolveRun& run = c->run;
-    const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot;
-    const bool by_records = qmcp::rank_scratch_by_records(run.range_shift, ltot, n);
+    const uint32_t n = (uint32_t)run.pr.n;
+    const bool by_records = qmcp::pm_rank_scratch_by_records(run.range_shift, run.pm_ranges, n);
     KernelSpan sp(c, "k_pm_walk", st);
     qmcp::launch_pm_walk(st, (const uint16_t*)c->keys[0].p, (const uint16_t*)c->keys[1].p, (const uint32_t*)c->pm_desc.p,
-                         (const uint32_t*)c->hist2.p, n, (const uint32_t*)c->ranges.p, run.range_shift, ltot,
-                         (const uint32_t*)c->boff.p, (const uint32_t*)c->selend.p, (unsigned long long*)run.d_mask,
+                         (const uint32_t*)c->hist2.p, n, (const uint32_t*)c->ranges.p, run.range_shift, run.pm_ranges,
+                         (const uint32_t*)c->pm_grid.p, (const uint32_t*)c->boff.p, (const uint32_t*)c->selend.p, (unsigned long long*)run.d_mask,
                          (unsigned long long*)c->scalars.p, c->rankamb.p, by_records, ev_sev, ev_lastns,
                          (const uint64_t*)c->poff.p, run.n_contigs, ell);
 }

@@ -33,6 +33,7 @@ int enqueue_tail(qmcp_hip_ctx* c) {
         }
     }
     const uint32_t max_load = hs[3];
+    if (run.pm) local.pm_heaviest_wave_slots = hs[7];
     const uint32_t empty_positions = hs[4];            // (the last solve of this shape's, or this one's: set by the head)
     const uint32_t min_span = hs[0], max_span = hs[1];
     local.min_span = min_span;
@@ -396,6 +397,7 @@ void options_from_env(qmcp_hip_options& o) {
     o.host_threads = num("QMCP_HIP_HOST_THREADS");
     o.copy_streams = num("QMCP_HIP_COPY_STREAMS");
     o.host_both_columns = flag("QMCP_HIP_HOST_BOTH_COLUMNS");
+    if (const char* e = std::getenv("QMCP_HIP_PM_GRID")) o.pm_grid = e[0] == '-' ? -1 : e[0] == '1' || e[0] == '+' ? 1 : 0;
 }
 
 int create_ctx(int device, qmcp_hip_ctx** out_ctx) {

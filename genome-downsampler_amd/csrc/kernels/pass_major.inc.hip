@@ -20,15 +20,28 @@
 //   k_pm_tables         the same launch, one thread per table entry: one descriptor word per wave-slot -- pass << 15 |
 //                       slot group inside the pass << 6 | (records in the group - 1) --; from the rows' true record counts
 //                       the ranges' true flat starts -- the bucket offsets' bases -- and the heaviest load.
-//   k_pm_offsets        per range: LDS histogram of its wave-slots' positions -> bucket offsets (k_range_offsets' job).
+//   k_pm_offsets        per range: LDS histogram of its wave-slots' positions -> bucket offsets (k_range_offsets' job);
+//                       eight position requests a wave in flight, the next round's descriptors asked for behind them.
 //   k_pm_walk           per range: k_rank_mark's ordered walk, a chunk of sixteen wave-slots per step, each wave's
 //                       records found through ONE descriptor word (round 3 searched the table's row with a cursor in
 //                       LDS: 57 vector instructions per wave and chunk against the range-major walk's 21).  Kept
 //                       records' read indices collect in a ring in LDS, per wave, and are marked 64 at a time.
 //                       The (chunk, position) groups whose quota ran out inside a chunk are listed and settled in the
 //                       kernel's tail, one wave per group, by the workgroup that listed them.
+// THE RANGE GRID (pm_grid_plan.h; the host decides before anything is queued).  A range is 2^shift positions of an axis
+// the starts are laid on.  On the genome's global axis every contig border falls inside a range, and a range that
+// straddles one gets two slices per pass pair, each padded to whole groups of 64: the same records in more wave-slots.
+// k_pm_offsets and k_pm_walk run one workgroup per range, a single wave of workgroups on the chip, so they take as long
+// as their heaviest range: at cfg4 (8 contigs of 10^6, 245 ranges of 32 768) the seven straddling ranges, 8 506
+// wave-slots against a median near 7 300.  The ALIGNED grid lays contig c at (rbase[c] << shift), rbase[c] = the ranges
+// of the contigs before it: no range straddles a border -- 248 ranges, the heaviest 7 322 wave-slots (-14 %), k_pm_walk
+// 0.275 -> 0.250 ms.  It is taken where its ranges still fit the 256 digits and the heaviest range's expected wave-slots
+// come out strictly lighter (options.pm_grid forces either).  To the kernels both grids are the same tables: the
+// producer adds vbase[c] in place of the contig's global offset; the per-range kernels take the real position of key 0
+// (pos0), the positions that exist (live) and the range's contig from the table.  boff[ltot], the grand total, is no
+// range's position and is written apart.
 // A range's records in read-index order are its slices in pass order, so nothing about the selection changes: the
-// kept set is bit for bit the first form's.  One-level genomes only (<= 256 ranges); longer ones keep the two-level
+// kept set is bit for bit the first form's, under either grid.  One-level genomes only (<= 256 ranges); longer ones keep the two-level
 // partition, and so do calls whose slices would be short (narrow ranges: the padding would be most of a group).
 static constexpr int kPmPass = 8192;             // reads per pass
 // slots between the beginnings of two passes: the pass's records and up to 63 slots of padding per range
@@ -45,7 +58,8 @@ static constexpr uint32_t kPmExcPerWave = 128;  // list slots per wave and pass:
 __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_sort(
     const uint32_t* __restrict__ starts, const uint32_t* __restrict__ ends, uint32_t n,
     const uint64_t* __restrict__ contig_read_off, const uint64_t* __restrict__ contig_pos_off, uint32_t n_contigs,
-    uint32_t shift, uint32_t stride /* pm_stride_of(ranges of the genome) */,
+    const uint32_t* __restrict__ vbase /* [n_contigs + 1] where a contig begins on the grid's axis (pm_grid_plan.h) */,
+    uint32_t shift, uint32_t stride /* pm_stride_of(ranges of the grid) */,
     uint16_t* __restrict__ keys16, uint16_t* __restrict__ idx16,
     uint32_t* __restrict__ cnt_tab, uint32_t* __restrict__ lst_tab, uint32_t pitch /* multiple of 4 */,
     uint32_t* __restrict__ stats, unsigned long long* __restrict__ zero_mask,
@@ -101,9 +115,11 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         const uint32_t c_last = n_contigs > 1 ? contig_of(base + count - 1) : 0u;
         uint32_t match_bits;
         {
-            // the pass's digits lie in the range its contigs span (k_range_partition, MODE 1)
-            const uint32_t d_lo = ((uint32_t)contig_pos_off[c_first] >> shift) & 255u;
-            const uint32_t d_hi = ((uint32_t)contig_pos_off[c_last + 1] >> shift) & 255u;
+            // the pass's digits lie in the ranges its contigs span on the grid's axis: from the first contig's first
+            // position to the last one's last
+            const uint32_t len_last = (uint32_t)(contig_pos_off[c_last + 1] - contig_pos_off[c_last]);
+            const uint32_t d_lo = (vbase[c_first] >> shift) & 255u;
+            const uint32_t d_hi = ((vbase[c_last] + (len_last ? len_last - 1u : 0u)) >> shift) & 255u;
             match_bits = d_hi >= d_lo ? 32u - (uint32_t)__builtin_clz((d_hi - d_lo) | 1u) : 8u;
             if (d_hi == d_lo) match_bits = 0;
         }
@@ -128,11 +144,12 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
                 filled += (uint32_t)__popcll(m);
             }
         };
-        // validate, span range, global start (a start beyond its contig -- the call fails -- is taken as the
-        // contig's last position, so that its digit lies inside the pass's digit interval)
+        // validate, span range, start on the grid's axis (a start beyond its contig -- the call fails -- is taken as
+        // the contig's last position, so that its digit lies inside the pass's digit interval)
         if (c_first == c_last) {
             const uint32_t p0 = (uint32_t)contig_pos_off[c_first];
             const uint32_t len = (uint32_t)contig_pos_off[c_first + 1] - p0;
+            const uint32_t v0 = vbase[c_first];
             const uint32_t last = len ? len - 1u : 0u;
 #pragma unroll
             for (int k = 0; k < kSortItems; ++k) {
@@ -146,15 +163,15 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
                     mx = max(mx, span);
                     isx = span != ell_reg;
                 }
-                rec[k].key = p0 + min(s, last);
-                if (ell_reg != 0u) put_aside(k, isx, rec[k].key, p0 + min(e, last), i);
+                rec[k].key = v0 + min(s, last);
+                if (ell_reg != 0u) put_aside(k, isx, p0 + min(s, last), p0 + min(e, last), i);  // (the list holds global positions)
             }
         } else {
 #pragma unroll
             for (int k = 0; k < kSortItems; ++k) {
                 const uint32_t i = wbase + k * 64 + lane;
                 bool isx = false;
-                uint32_t ge = 0;
+                uint32_t gs = 0, ge = 0;
                 if (i < n) {
                     const uint32_t cc = contig_of(i);
                     const uint32_t p0 = (uint32_t)contig_pos_off[cc];
@@ -164,11 +181,12 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
                     const uint32_t span = e - s + 1;
                     mn = min(mn, span);
                     mx = max(mx, span);
-                    rec[k].key = p0 + min(s, len ? len - 1u : 0u);
+                    rec[k].key = vbase[cc] + min(s, len ? len - 1u : 0u);
                     isx = span != ell_reg;
+                    gs = p0 + min(s, len ? len - 1u : 0u);
                     ge = p0 + min(e, len ? len - 1u : 0u);
                 }
-                if (ell_reg != 0u) put_aside(k, isx, rec[k].key, ge, i);
+                if (ell_reg != 0u) put_aside(k, isx, gs, ge, i);
             }
         }
         __syncthreads();  // (counters cleared)
@@ -377,9 +395,10 @@ __global__ __launch_bounds__(256) void k_pm_row_sums(const uint32_t* __restrict_
 __global__ __launch_bounds__(256) void k_pm_tables(uint32_t* tab, const uint32_t* __restrict__ lstw, uint32_t pitch,
                                                    uint32_t n_groups /* total padded flat / 64 bound */,
                                                    uint32_t* __restrict__ desc, const uint32_t* __restrict__ work,
-                                                   uint32_t* __restrict__ range_start, uint32_t* __restrict__ max_load,
+                                                   uint32_t* __restrict__ range_start,
+                                                   uint32_t* __restrict__ max_load /* [0] records, [1] wave-slots of the heaviest range */,
                                                    uint32_t* __restrict__ clear16 /* or null */) {
-    __shared__ uint32_t s_red[4], s_base, s_tile[2][4][4];
+    __shared__ uint32_t s_red[4], s_red2[4], s_base, s_tile[2][4][4];
     const uint32_t d = blockIdx.x, y = blockIdx.y, tid = threadIdx.x;
     const uint32_t lane = tid & 63u, wv = tid >> 6;
     const bool first = d == 0u && y == 0u;  // (uniform)
@@ -410,7 +429,7 @@ __global__ __launch_bounds__(256) void k_pm_tables(uint32_t* tab, const uint32_t
     if (first) {  // the ranges' true flat starts and the heaviest range's load, from the rows' true counts
         if (clear16 != nullptr && tid < 16u) clear16[tid] = 0u;  // (the solve's result scalars: saves the tail a memset launch)
         const uint32_t inc = wave_incl_scan_add(rt);
-        const uint32_t mx = wave_max_u32(rt);
+        const uint32_t mx = wave_max_u32(rt), mxp = wave_max_u32(rp);
         if (lane == 63u) s_red[wv] = inc;
         __syncthreads();
         uint32_t base = 0;
@@ -418,9 +437,12 @@ __global__ __launch_bounds__(256) void k_pm_tables(uint32_t* tab, const uint32_t
         range_start[tid] = base + inc - rt;
         if (tid == 255u) range_start[256] = base + inc;
         __syncthreads();
-        if (lane == 0u) s_red[wv] = mx;
+        if (lane == 0u) { s_red[wv] = mx; s_red2[wv] = mxp; }
         __syncthreads();
-        if (tid == 0) max_load[0] = max(max(s_red[0], s_red[1]), max(s_red[2], s_red[3]));
+        if (tid == 0) {
+            max_load[0] = max(max(s_red[0], s_red[1]), max(s_red[2], s_red[3]));
+            max_load[1] = max(max(s_red2[0], s_red2[1]), max(s_red2[2], s_red2[3])) >> 6;  // (a row's padded total is its wave-slots x 64)
+        }
     }
     uint32_t P_beg, P_end;
     pm_row_part(pitch, P_beg, P_end);
@@ -463,18 +485,34 @@ __global__ __launch_bounds__(256) void k_pm_tables(uint32_t* tab, const uint32_t
     }
 }
 
+// The grid's per-range tables (pm_grid_plan.h), one buffer: where key 0 of range r lies in the genome, how many of the
+// range's positions exist, and the range's contig (kPmNoContig where the range straddles a border).
+__device__ __forceinline__ uint32_t pm_grid_pos0(const uint32_t* __restrict__ grid, uint32_t r) { return grid[r]; }
+__device__ __forceinline__ uint32_t pm_grid_live(const uint32_t* __restrict__ grid, uint32_t r) { return grid[kPmGridRows + r]; }
+__device__ __forceinline__ uint32_t pm_grid_contig(const uint32_t* __restrict__ grid, uint32_t r) { return grid[2u * kPmGridRows + r]; }
+
+#ifndef QMCP_PM_OFFSETS_U
+#define QMCP_PM_OFFSETS_U 8  // position requests a wave keeps in flight
+#endif
 // k_range_offsets for the pass-major layout: the range's positions come as wave-slots, in any order.  A wave takes four
 // wave-slots at a time -- sixteen lanes each, four records (8 bytes) per lane: one 512-byte request -- and keeps kU
-// such requests in flight.
+// such requests in flight.  The descriptors of a round are asked for one round ahead, a word per quarter-wave in one
+// vector load, right behind the round's position requests: by the time the positions have been counted they are there.
+// (They were sixteen scalar loads by uniform index, each in another line of an array the previous kernel has just
+// written, waited for before the first position could be asked for: two dependent trips to memory per round, four
+// requests in flight.  cfg4, one solve alone, aligned grid: 0.086 -> 0.078 ms; the grid itself: 0.092 -> 0.086.)
+// One workgroup per range of the grid (gridDim.x); the last one also writes the grand total, boff[ltot].
 __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict__ keys16, const uint32_t* __restrict__ desc,
                                                      const uint32_t* __restrict__ Tp, uint32_t pitch,
                                                      const uint32_t* __restrict__ range_start /* true flat starts */,
+                                                     const uint32_t* __restrict__ grid,
                                                      uint32_t shift, uint32_t stride, uint32_t ltot, uint32_t* __restrict__ boff,
                                                      uint32_t* __restrict__ empty_positions) {
     extern __shared__ uint32_t s_cnt32[];  // [(1 << shift) padded] counters
 #define PADDED(i) ((i) + ((i) >> 5))
     __shared__ uint32_t s_wsum[16], s_esum[16];
-    const uint32_t range = blockIdx.x, width = 1u << shift, pos0 = range << shift;
+    const uint32_t range = blockIdx.x, width = 1u << shift;
+    const uint32_t pos0 = pm_grid_pos0(grid, range), live = pm_grid_live(grid, range);
     const uint32_t lo_p = Tp[(size_t)range * pitch], hi_p = Tp[(size_t)(range + 1) * pitch];
     const uint32_t g0 = lo_p >> 6, n_ws = (hi_p - lo_p) >> 6;
     const uint32_t lo = range_start[range];
@@ -483,30 +521,25 @@ __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict_
     const uint32_t lane = threadIdx.x & 63u, nw = blockDim.x >> 6;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t sub = lane >> 4, l16 = lane & 15u;
-    constexpr int kU = 4;
+    constexpr int kU = QMCP_PM_OFFSETS_U;
     const uint32_t n_quads = (n_ws + 3u) >> 2;
+    // the lane's wave-slots of the kU quads from q0 on: their descriptors (beyond the range's last: that one's, never used)
+    uint32_t dsc[kU];
+    auto ask_descriptors = [&](uint32_t q0) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) dsc[u] = desc[g0 + min(4u * (q0 + (uint32_t)u * nw) + sub, n_ws - 1u)];
+    };
+    if (n_ws != 0u) ask_descriptors(w);
     for (uint32_t q0 = w; q0 < n_quads; q0 += kU * nw) {
         uint2 v[kU];
         uint32_t nv[kU];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            const uint32_t q = q0 + (uint32_t)u * nw;
-            // the lane's wave-slot of the quad: its descriptor (four scalar words, the lane's one picked out)
-            uint32_t dsc = 0;
-            bool has = false;
-            if (q < n_quads) {  // uniform
-                const uint32_t ws = 4u * q;
-                const uint32_t d0 = desc[g0 + ws];
-                const uint32_t d1 = ws + 1 < n_ws ? desc[g0 + ws + 1] : 0u;
-                const uint32_t d2 = ws + 2 < n_ws ? desc[g0 + ws + 2] : 0u;
-                const uint32_t d3 = ws + 3 < n_ws ? desc[g0 + ws + 3] : 0u;
-                dsc = sub == 0 ? d0 : sub == 1 ? d1 : sub == 2 ? d2 : d3;
-                has = ws + sub < n_ws;
-            }
-            const PmSlot at = pm_unpack<true>(dsc, has, stride);
+            const PmSlot at = pm_unpack<true>(dsc[u], 4u * (q0 + (uint32_t)u * nw) + sub < n_ws, stride);
             nv[u] = at.nv;
             v[u] = *reinterpret_cast<const uint2*>(keys16 + at.slot0 + 4u * l16);   // (inside the slice's padded group: always readable)
         }
+        if (q0 + kU * nw < n_quads) ask_descriptors(q0 + kU * nw);  // (uniform) the next round's, behind this round's positions
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const uint32_t e = 4u * l16;
@@ -525,7 +558,7 @@ __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict_
         for (uint32_t qq = 0; qq < per; ++qq) {
             const uint32_t cq = s_cnt32[PADDED(firstp + qq)];
             sum += cq;
-            empties += (cq == 0 && pos0 + firstp + qq < ltot) ? 1u : 0u;
+            empties += (cq == 0 && firstp + qq < live) ? 1u : 0u;
         }
     const uint32_t inc = wave_incl_scan_add(sum);
     const uint32_t wv = threadIdx.x >> 6;
@@ -549,8 +582,9 @@ __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict_
             run += cq;
         }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < width; i += blockDim.x)
-        if (pos0 + i <= ltot) boff[pos0 + i] = s_cnt32[PADDED(i)];
+    for (uint32_t i = threadIdx.x; i < live; i += blockDim.x) boff[pos0 + i] = s_cnt32[PADDED(i)];
+    // (the grand total: the ranges of the grid end where the genome does, so no range has a position ltot of its own)
+    if (range == gridDim.x - 1u && threadIdx.x == 0) boff[ltot] = range_start[kPmGridRows];
 #undef PADDED
 }
 
@@ -629,7 +663,8 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
                                                   const uint32_t* __restrict__ desc,
                                                   const uint32_t* __restrict__ Tp, uint32_t pitch,
                                                   const uint32_t* __restrict__ range_start /* true flat starts */,
-                                                  uint32_t shift, uint32_t stride, uint32_t ltot,
+                                                  const uint32_t* __restrict__ grid,
+                                                  uint32_t shift, uint32_t stride,
                                                   const uint32_t* __restrict__ boff, const uint32_t* __restrict__ selend,
                                                   EvQuota evq,
                                                   unsigned long long* __restrict__ mask,
@@ -638,8 +673,8 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     extern __shared__ int32_t s_q[];  // [(1 << shift) + 1] quotas
     __shared__ uint32_t s_namb, s_kept;
     __shared__ uint32_t s_ring[16][128];  // per wave: kept records' read indices on their way to the mask
-    const uint32_t range = blockIdx.x, width = 1u << shift, pos0 = range << shift;
-    const uint32_t live = pos0 < ltot ? min(width, ltot - pos0) : 0u;
+    const uint32_t range = blockIdx.x, width = 1u << shift;
+    const uint32_t pos0 = pm_grid_pos0(grid, range), live = pm_grid_live(grid, range);
     const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
     const uint32_t lane = tid & 63u;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -651,13 +686,17 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     const uint32_t lo_true = range_start[range];
     uint2* const amb = amb_lists + (lists_by_records ? (size_t)lo_true : (size_t)range * width);
     if (evq.sev != nullptr) {
-        // straight from the event-driven sweep's output (two dependent loads per position, eight positions in flight)
+        // straight from the event-driven sweep's output (two dependent loads per position, eight positions in flight).
+        // On the aligned grid the range lies in one contig; a range of the global grid that straddles a border looks
+        // every position's contig up.
+        const uint32_t c_range = pm_grid_contig(grid, range);  // (uniform)
         for (uint32_t i0 = tid; i0 < live; i0 += 8 * nthreads) {
             uint32_t src[8], back[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const uint32_t p = pos0 + min(i0 + u * nthreads, live - 1);  // clamped: every load is issued
-                uint32_t c_lo = 0, c_hi = evq.n_contigs;  // last contig with poff[c] <= p
+                uint32_t c_lo = c_range, c_hi = c_range + 1u;
+                if (c_range == kPmNoContig) { c_lo = 0; c_hi = evq.n_contigs; }  // last contig with poff[c] <= p
                 while (c_hi - c_lo > 1) {
                     const uint32_t mid = (c_lo + c_hi) >> 1;
                     if ((uint32_t)evq.poff[mid] <= p) c_lo = mid; else c_hi = mid;
@@ -839,12 +878,19 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
 // ---- launchers
 uint32_t pm_pitch(uint32_t n) { return part_pass_pitch(n); }  // passes of the call, rounded up to a multiple of 4
 uint32_t pm_pass() { return (uint32_t)kPmPass; }
-uint32_t pm_stride(uint32_t ltot, uint32_t shift) { return pm_stride_of((ltot >> shift) + 1u); }
-size_t pm_slots(uint32_t n, uint32_t ltot, uint32_t shift) { return (size_t)pm_pitch(n) * pm_stride(ltot, shift); }  // slots of keys16 / idx16
+uint32_t pm_stride(uint32_t n_ranges) { return pm_stride_of(n_ranges); }
+size_t pm_slots(uint32_t n, uint32_t n_ranges) { return (size_t)pm_pitch(n) * pm_stride(n_ranges); }  // slots of keys16 / idx16
 uint32_t pm_work_words() { return kPmWorkWords; }
 uint32_t pm_exc_slots(uint32_t n) { return pm_pitch(n) * kPmWaves * kPmExcPerWave + kNuOverflow; }  // the exception list's slots: 128 per wave and pass, and the overflow region
+// the walk's lists of quota-crossing groups: a slot per position of every range of the grid, or per read
+bool pm_rank_scratch_by_records(uint32_t shift, uint32_t n_ranges, uint32_t n) { return (size_t)n < ((size_t)n_ranges << shift); }
+size_t pm_rank_scratch_bytes(uint32_t shift, uint32_t n_ranges, uint32_t n) {
+    const size_t by_pos = (size_t)n_ranges << shift;
+    return (by_pos < (size_t)n ? by_pos : (size_t)n) * sizeof(uint2) + 64;
+}
 void launch_pm_prepare_sort(hipStream_t st, const uint32_t* starts, const uint32_t* ends, uint32_t n,
-                            const uint64_t* d_roff, const uint64_t* d_poff, uint32_t n_contigs, uint32_t shift, uint32_t ltot,
+                            const uint64_t* d_roff, const uint64_t* d_poff, uint32_t n_contigs, uint32_t shift,
+                            uint32_t n_ranges, const uint32_t* d_grid,
                             uint16_t* keys16, uint16_t* idx16, uint32_t* cnt_tab, uint32_t* lst_tab,
                             uint32_t* stats, unsigned long long* zero_mask, uint32_t ell_reg, uint32_t* exc,
                             uint32_t exc_cap, uint32_t* exc_cnt) {
@@ -852,47 +898,46 @@ void launch_pm_prepare_sort(hipStream_t st, const uint32_t* starts, const uint32
     if (pitch == 0) return;
     (void)hipFuncSetAttribute((const void*)k_pm_prepare_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPmSortLds);
     hipLaunchKernelGGL(k_pm_prepare_sort, dim3(pitch / kPmPassesPerWg), dim3(kPmThreads), kPmSortLds, st, starts, ends, n,
-                       d_roff, d_poff, n_contigs, shift, pm_stride(ltot, shift), keys16, idx16, cnt_tab, lst_tab, pitch,
-                       stats, zero_mask, exc != nullptr ? ell_reg : 0u, exc, exc_cap, exc_cnt);
+                       d_roff, d_poff, n_contigs, d_grid + 3u * kPmGridRows, shift, pm_stride(n_ranges), keys16, idx16,
+                       cnt_tab, lst_tab, pitch, stats, zero_mask, exc != nullptr ? ell_reg : 0u, exc, exc_cap, exc_cnt);
     if (exc != nullptr && ell_reg != 0u)
         hipLaunchKernelGGL(k_nu_count_groups, dim3(32), dim3(256), 0, st, exc_cnt, pitch * kPmWaves, stats);
 }
 // The table stage: the padded count table scanned in place (tab: counts in, Tp out, the total at tab[256 pitch]), the
-// wave-slot descriptors, the ranges' true flat starts and the heaviest load -- two launches.  All 256 rows, whatever the
-// genome's ranges: the rows beyond them hold zeros and scan to the total.
+// wave-slot descriptors, the ranges' true flat starts and the heaviest load (records, and wave-slots) -- two launches.
+// All 256 rows, whatever the grid's ranges: the rows beyond them hold zeros and scan to the total.
 void launch_pm_row_sums(hipStream_t st, const uint32_t* cnt_tab, const uint32_t* lstw, uint32_t n, uint32_t* work) {
     const uint32_t pitch = pm_pitch(n);
     if (pitch == 0) return;
     hipLaunchKernelGGL(k_pm_row_sums, dim3(256, kPmDescrY), dim3(256), 0, st, cnt_tab, lstw, pitch, work);
 }
-void launch_pm_tables(hipStream_t st, uint32_t* tab, const uint32_t* lstw, uint32_t n, uint32_t ltot, uint32_t shift,
+void launch_pm_tables(hipStream_t st, uint32_t* tab, const uint32_t* lstw, uint32_t n, uint32_t n_ranges,
                       uint32_t* desc, const uint32_t* work, uint32_t* range_start, uint32_t* max_load, uint32_t* clear16) {
     const uint32_t pitch = pm_pitch(n);
     if (pitch == 0) return;
-    const uint32_t s64 = pm_stride(ltot, shift) / 64u;
+    const uint32_t s64 = pm_stride(n_ranges) / 64u;
     hipLaunchKernelGGL(k_pm_tables, dim3(256, kPmDescrY), dim3(256), 0, st, tab, lstw, pitch, pitch * s64, desc, work,
                        range_start, max_load, clear16);
 }
 void launch_pm_offsets(hipStream_t st, const uint16_t* keys16, const uint32_t* desc, const uint32_t* Tp, uint32_t n,
-                       const uint32_t* range_start, uint32_t shift, uint32_t ltot, uint32_t* boff, uint32_t* empty_positions) {
-    const uint32_t n_ranges = (ltot >> shift) + 1;  // covers positions 0..ltot
+                       const uint32_t* range_start, uint32_t shift, uint32_t n_ranges, const uint32_t* d_grid, uint32_t ltot,
+                       uint32_t* boff, uint32_t* empty_positions) {
     const size_t width = (size_t)1 << shift;
     const size_t lds = (width + width / 32 + 1) * sizeof(uint32_t);
     (void)hipFuncSetAttribute((const void*)k_pm_offsets, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_pm_offsets, dim3(n_ranges), dim3(1024), lds, st, keys16, desc, Tp, pm_pitch(n), range_start, shift,
-                       pm_stride(ltot, shift), ltot, boff, empty_positions);
+    hipLaunchKernelGGL(k_pm_offsets, dim3(n_ranges), dim3(1024), lds, st, keys16, desc, Tp, pm_pitch(n), range_start, d_grid,
+                       shift, pm_stride(n_ranges), ltot, boff, empty_positions);
 }
 // The ranking: the ordered walk, with the settling of the groups it listed in its tail -- one launch.
 void launch_pm_walk(hipStream_t st, const uint16_t* keys16, const uint16_t* idx16, const uint32_t* desc, const uint32_t* Tp,
-                    uint32_t n, const uint32_t* range_start, uint32_t shift, uint32_t ltot, const uint32_t* boff,
-                    const uint32_t* selend, unsigned long long* mask, unsigned long long* kept_total, void* scratch,
+                    uint32_t n, const uint32_t* range_start, uint32_t shift, uint32_t n_ranges, const uint32_t* d_grid,
+                    const uint32_t* boff, const uint32_t* selend, unsigned long long* mask, unsigned long long* kept_total, void* scratch,
                     bool scratch_by_records, const uint32_t* ev_sev, const uint32_t* ev_lastns,
                     const uint64_t* d_poff, uint32_t n_contigs, uint32_t ell) {
-    const uint32_t n_ranges = (ltot >> shift) + 1;
     const EvQuota evq{ev_sev, ev_lastns, d_poff, n_contigs, ell};
     const size_t lds = (((size_t)1 << shift) + 1) * sizeof(uint32_t);
     (void)hipFuncSetAttribute((const void*)k_pm_walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_pm_walk, dim3(n_ranges), dim3(1024), lds, st, keys16, idx16, desc, Tp, pm_pitch(n), range_start, shift,
-                       pm_stride(ltot, shift), ltot, boff, selend, evq, mask, (uint2*)scratch, scratch_by_records ? 1 : 0,
+    hipLaunchKernelGGL(k_pm_walk, dim3(n_ranges), dim3(1024), lds, st, keys16, idx16, desc, Tp, pm_pitch(n), range_start, d_grid, shift,
+                       pm_stride(n_ranges), boff, selend, evq, mask, (uint2*)scratch, scratch_by_records ? 1 : 0,
                        kept_total);
 }

@@ -8,6 +8,7 @@
 #include "qmcp_hip.h"    // qmcp_hip_track_run
 #include "sweep_plan.h"  // the shape predicates and window counts the host decides with
 #include "dedup_plan.h"  // DedupPack, DedupSortForm: how a round's key is packed, which form the sort takes
+#include "pm_grid_plan.h"  // PmGridPlan: where the pass-major form cuts its ranges, and the tables that say so
 
 namespace qmcp {
 
@@ -207,28 +208,33 @@ void launch_rank_mark(hipStream_t st, const uint16_t* keys16, const uint32_t* id
 // range-ranked route, pass-major layout (kernels/pass_major.inc.hip): one-level genomes
 uint32_t pm_pitch(uint32_t n);     // row pitch of the [range][pass] tables
 uint32_t pm_pass();                // reads per pass
-uint32_t pm_stride(uint32_t ltot, uint32_t shift);              // slots between the beginnings of two passes
-size_t pm_slots(uint32_t n, uint32_t ltot, uint32_t shift);     // slots of the two 16-bit record streams
+// (n_ranges, d_grid: the grid pm_grid_plan.h cut -- its range count and its tables on the device, pos0 | live | contig |
+//  vbase in one buffer)
+uint32_t pm_stride(uint32_t n_ranges);                          // slots between the beginnings of two passes
+size_t pm_slots(uint32_t n, uint32_t n_ranges);                 // slots of the two 16-bit record streams
+size_t pm_rank_scratch_bytes(uint32_t shift, uint32_t n_ranges, uint32_t n);  // the walk's list slots: per position of the grid or per read
+bool pm_rank_scratch_by_records(uint32_t shift, uint32_t n_ranges, uint32_t n);
 uint32_t pm_work_words();          // words of the table stage's working buffer (k_pm_row_sums -> k_pm_tables)
 void launch_pm_prepare_sort(hipStream_t st, const uint32_t* starts, const uint32_t* ends, uint32_t n,
-                            const uint64_t* d_roff, const uint64_t* d_poff, uint32_t n_contigs, uint32_t shift, uint32_t ltot,
-                            uint16_t* keys16, uint16_t* idx16, uint32_t* cnt_tab, uint32_t* lst_tab,
+                            const uint64_t* d_roff, const uint64_t* d_poff, uint32_t n_contigs, uint32_t shift,
+                            uint32_t n_ranges, const uint32_t* d_grid, uint16_t* keys16, uint16_t* idx16, uint32_t* cnt_tab, uint32_t* lst_tab,
                             uint32_t* stats, unsigned long long* zero_mask, uint32_t ell_reg = 0, uint32_t* exc = nullptr,
                             uint32_t exc_cap = 0, uint32_t* exc_cnt = nullptr);
 uint32_t pm_exc_slots(uint32_t n);  // slots of the near-uniform route's exception list (groups of 64, one per wave and pass)
 // the table stage, two launches in this order on one stream: the parts' sums of the two tables (work: pm_work_words());
 // then the padded count table scanned in place (tab: counts in, padded flat positions out, the total at
-// tab[256 pitch]), wave-slot descriptors (pm_slots / 64 words), the ranges' true flat starts (257 words), heaviest
-// load.  clear16: sixteen words the second launch also sets to zero (or null)
+// tab[256 pitch]), wave-slot descriptors (pm_slots / 64 words), the ranges' true flat starts (257 words), the heaviest
+// range's records and wave-slots (max_load: two words).  clear16: sixteen words the second launch also sets to zero (or null)
 void launch_pm_row_sums(hipStream_t st, const uint32_t* cnt_tab, const uint32_t* lstw, uint32_t n, uint32_t* work);
-void launch_pm_tables(hipStream_t st, uint32_t* tab, const uint32_t* lstw, uint32_t n, uint32_t ltot, uint32_t shift,
+void launch_pm_tables(hipStream_t st, uint32_t* tab, const uint32_t* lstw, uint32_t n, uint32_t n_ranges,
                       uint32_t* desc, const uint32_t* work, uint32_t* range_start, uint32_t* max_load, uint32_t* clear16);
 void launch_pm_offsets(hipStream_t st, const uint16_t* keys16, const uint32_t* desc, const uint32_t* Tp, uint32_t n,
-                       const uint32_t* range_start, uint32_t shift, uint32_t ltot, uint32_t* boff, uint32_t* empty_positions);
+                       const uint32_t* range_start, uint32_t shift, uint32_t n_ranges, const uint32_t* d_grid, uint32_t ltot,
+                       uint32_t* boff, uint32_t* empty_positions);
 // the ranking: ordered walk (kept reads marked 64 at a time); the quota-crossing groups it lists are settled in its tail
 void launch_pm_walk(hipStream_t st, const uint16_t* keys16, const uint16_t* idx16, const uint32_t* desc, const uint32_t* Tp,
-                    uint32_t n, const uint32_t* range_start, uint32_t shift, uint32_t ltot, const uint32_t* boff,
-                    const uint32_t* selend, unsigned long long* mask, unsigned long long* kept_total, void* scratch,
+                    uint32_t n, const uint32_t* range_start, uint32_t shift, uint32_t n_ranges, const uint32_t* d_grid,
+                    const uint32_t* boff, const uint32_t* selend, unsigned long long* mask, unsigned long long* kept_total, void* scratch,
                     bool scratch_by_records,
                     // quotas straight from the event-driven sweep's output (whole contigs, no stretch table), instead
                     // of selend[] - boff[]: the changed blocks' kept counts, the last changed block per block

@@ -112,6 +112,10 @@ typedef struct qmcp_hip_stats {
     uint32_t near_uniform_selected;   /* ... of those, kept                                              */
     uint32_t near_uniform_rounds;     /* ... sweeps it took (1 = no exception was wanted by the sweep)   */
     uint32_t near_uniform_giveup;     /* 0, or why the route handed the call to the mixed-span one: QMCP_NU_GIVEUP_* */
+    int32_t pm_grid;                  /* pass-major form of the range-ranked route: the grid its ranges were cut on, -1 the
+                                 global axis, +1 aligned to the contigs' starts; 0: the form did not run             */
+    uint32_t pm_heaviest_wave_slots;  /* ... and the wave-slots (groups of 64 padded record slots) of its heaviest range:
+                                 what the per-range kernels' slowest workgroup walks                                */
 } qmcp_hip_stats;
 
 /* qmcp_hip_stats.near_uniform_giveup */
@@ -165,6 +169,9 @@ typedef struct qmcp_hip_options {
     uint32_t host_threads;        /* host entries: threads that narrow / check the columns (QMCP_HIP_HOST_THREADS; 8)     */
     uint32_t copy_streams;        /* host entries: copy streams (QMCP_HIP_COPY_STREAMS)                                   */
     int32_t host_both_columns;    /* 1: host entries always send starts AND ends (QMCP_HIP_HOST_BOTH_COLUMNS)             */
+    int32_t pm_grid;              /* pass-major form: where its ranges are cut -- -1 on the global axis, +1 at the contigs'
+                                     starts wherever that still fits 256 ranges; 0: there, if the heaviest range comes out
+                                     lighter (QMCP_HIP_PM_GRID=-1|1)                                                       */
 } qmcp_hip_options;
 enum { QMCP_SWEEP_AUTO = 0, QMCP_SWEEP_FAST = 1, QMCP_SWEEP_GENERAL = 2, QMCP_SWEEP_EVENTS = 3 };
 void qmcp_hip_default_options(qmcp_hip_options* out);            /* all zero but struct_size                          */
