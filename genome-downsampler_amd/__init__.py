@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_templates_profile_host", "qmcp_hip_solve_templates_profile_device",
     "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
     "qmcp_hip_solve_budget_host", "qmcp_hip_solve_budget_device",
+    "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
 )
 
 QMCP_OK = 0
@@ -58,6 +59,8 @@ PAIR_MAX_STAGES = 16  # QMCP_PAIR_MAX_STAGES
 CEILING_WHOLE_PAIRS = 1  # QMCP_CEILING_WHOLE_PAIRS
 BUDGET_WHOLE_PAIRS = 1  # QMCP_BUDGET_WHOLE_PAIRS
 BUDGET_CURVE_MAX = 8191  # QMCP_BUDGET_CURVE_MAX: the last coverage the curve of a budget solve reaches
+REPLICATES_MAX = 16  # QMCP_REPLICATES_MAX
+REPLICATES_WHOLE_PAIRS, REPLICATES_SHORTFALL = 1, 2  # QMCP_REPLICATES_*
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
 DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
@@ -259,6 +262,25 @@ class LadderStats(C.Structure):
                 "ms_ladder": self.ms_ladder}
 
 
+class ReplicatesStats(C.Structure):
+    """qmcp_hip_replicates_stats: the replicates of a split (the arrays' first n_replicates entries count)"""
+    _fields_ = [("n_replicates", C.c_uint32), ("flags", C.c_uint32), ("n_full", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_offered", C.c_uint64 * REPLICATES_MAX), ("n_kept", C.c_uint64 * REPLICATES_MAX),
+                ("n_mates", C.c_uint64 * REPLICATES_MAX), ("short_positions", C.c_uint64 * REPLICATES_MAX),
+                ("short_bases", C.c_uint64 * REPLICATES_MAX), ("ms_replicate", C.c_float * REPLICATES_MAX),
+                ("ms_split", C.c_float), ("reserved1", C.c_float)]
+
+    def as_dict(self):
+        k = self.n_replicates
+        out = {"n_replicates": k, "flags": self.flags, "n_full": self.n_full, "ms_split": self.ms_split}
+        for name in ("n_offered", "n_kept", "n_mates", "short_positions", "short_bases", "ms_replicate"):
+            out[name] = list(getattr(self, name)[:k])
+        return out
+
+
+assert C.sizeof(ReplicatesStats) == 16 + 5 * 8 * REPLICATES_MAX + 4 * REPLICATES_MAX + 8
+
+
 class StratumRow(C.Structure):
     """qmcp_hip_stratum_row: a stratum's placed reads, how many of them are kept, and the bases of both"""
     _fields_ = [("n_reads", C.c_uint64), ("n_kept", C.c_uint64), ("bases_in", C.c_uint64), ("bases_kept", C.c_uint64)]
@@ -393,6 +415,12 @@ _hip.qmcp_hip_depth_track_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                             _track_out + [C.c_void_p, C.POINTER(TrackStats)]
 _hip.qmcp_hip_solve_ladder_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p,
                                             C.c_uint32, C.c_void_p, C.POINTER(Stats), C.POINTER(LadderStats)]
+_hip.qmcp_hip_solve_replicates_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p,
+                                                C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats), C.POINTER(Stats),
+                                                C.POINTER(ReplicatesStats)]
+_hip.qmcp_hip_solve_replicates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                                  C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(Stats), C.POINTER(Stats), C.POINTER(ReplicatesStats)]
 _hip.qmcp_hip_solve_ladder_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
                                               C.POINTER(LadderStats)]
@@ -537,6 +565,16 @@ if _host is not None:
                                                        C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                                        C.c_int, C.c_char_p, C.POINTER(CeilingStats), C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam_ceiling.restype = C.c_int64
+    # (solver, in, out, filtered, M, min_len, min_mapq, per_reference, further, n_further, out_template, targets, report,
+    #  track, ladder_levels, n_ladder_levels, stratify, dedup, pair_aware, template_aware, ceiling, bed, tsv,
+    #  amplicons_by_reference, replicates_report, written_out, rstats, err, err_cap)
+    _host.qmcp_host_downsample_bam_replicates.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                          C.c_uint32, C.c_uint32, C.c_int, _u32p, C.c_uint32, C.c_char_p,
+                                                          C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32,
+                                                          C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
+                                                          C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int64),
+                                                          C.POINTER(ReplicatesStats), C.c_char_p, C.c_size_t]
+    _host.qmcp_host_downsample_bam_replicates.restype = C.c_int64
     _host.qmcp_host_downsample_bam_budget.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
                                                       C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_double,
                                                       C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p,
@@ -627,6 +665,15 @@ def ladder_mask(levels, j):
     return np.packbits(bits, bitorder="little").view(np.uint64).copy()
 
 
+def replicate_mask(labels, r):
+    """the packed mask (np.uint64 words, input order) of replicate r (1-based) of a replicate split: R_r = {i : labels[i]
+    == r}"""
+    labels = np.ascontiguousarray(labels, dtype=np.uint8)
+    bits = np.zeros(mask_words(labels.size) * 64, dtype=np.uint8)
+    bits[:labels.size] = labels == int(r)
+    return np.packbits(bits, bitorder="little").view(np.uint64).copy()
+
+
 def _contig_tables(n_reads, contig_read_offsets, contig_lengths):
     if contig_read_offsets is None:
         lengths = np.atleast_1d(np.asarray(contig_lengths, dtype=np.uint32))
@@ -656,6 +703,8 @@ class Solver:
         self.last_template_profile_stats = None
         self.last_ceiling_stats = None
         self.last_budget_stats = None
+        self.last_replicates_stats = None
+        self.last_replicate_solve_stats = None
 
     def close(self):
         if self._ctx:
@@ -805,6 +854,45 @@ class Solver:
                                                  C.byref(st), C.byref(ls)))
         self.last_stats, self.last_ladder_stats = st, ls
         return ls
+
+    def solve_replicates(self, starts, ends, contig_ids, contig_lengths, coverages, flags=0):
+        """one read set split into disjoint downsamples in one call (qmcp_hip_solve_replicates_host): replicate 1 is
+        solve_by_contig at coverages[0], replicate r + 1 is solve_by_contig at coverages[r] of the placed reads that no
+        earlier replicate took.  flags: REPLICATES_WHOLE_PAIRS (reads (2q, 2q + 1) move together),
+        REPLICATES_SHORTFALL (per replicate, how far it stays below min(cov, coverage)).  -> one uint8 per read in INPUT
+        order, the replicate that holds it (1-based; 0: none; replicate_mask(labels, r) is replicate r's mask).
+        Replicate 1's solve stats go to last_stats, the replicates' to last_replicates_stats, and the batch-summed
+        stats of each replicate's solves to last_replicate_solve_stats (a list)"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        cov = np.atleast_1d(np.ascontiguousarray(coverages, dtype=np.uint32))
+        labels = np.zeros(max(n, 1), dtype=np.uint8)
+        st, rs = Stats(), ReplicatesStats()
+        reps = (Stats * max(cov.size, 1))()
+        _check(_hip.qmcp_hip_solve_replicates_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                   lengths.size, _p32(cov), cov.size, int(flags),
+                                                   C.c_void_p(labels.ctypes.data), C.byref(st), reps, C.byref(rs)))
+        self.last_stats, self.last_replicates_stats = st, rs
+        self.last_replicate_solve_stats = list(reps)[:cov.size]
+        return labels[:n]
+
+    def solve_replicates_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, coverages, d_labels,
+                                flags=0, stream=0):
+        """the same on device pointers (ints); the label bytes (n_reads of them, input order) are written to d_labels.
+        Returns the replicates' stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        cov = np.atleast_1d(np.ascontiguousarray(coverages, dtype=np.uint32))
+        st, rs = Stats(), ReplicatesStats()
+        reps = (Stats * max(cov.size, 1))()
+        _check(_hip.qmcp_hip_solve_replicates_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                     C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                     _p32(cov), cov.size, int(flags), C.c_void_p(d_labels),
+                                                     C.c_void_p(stream), C.byref(st), reps, C.byref(rs)))
+        self.last_stats, self.last_replicates_stats = st, rs
+        self.last_replicate_solve_stats = list(reps)[:cov.size]
+        return rs
 
     def solve_stratified(self, starts, ends, contig_ids, strata, contig_lengths, max_coverages):
         """one coverage cap per stratum (qmcp_hip_solve_stratified_host): strata[i] < len(max_coverages) names read i's
@@ -2126,7 +2214,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    track=None, track_channel="kept", track_cap=0, pair_aware=False, pair_stages=None,
                    template_aware=False, split_spliced=True, include_secondary=False, template_stages=None,
                    template_report=None, template_targets=None, template_target_padding=0, template_profile=None,
-                   ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None):
+                   ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None,
+                   replicates=None, replicates_out=None, replicates_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2211,8 +2300,64 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     reads): records written <= budget.  budget_report (a path) gets a stat<TAB>value TSV with the BudgetStats and
     records_written, then one M<TAB>bases line per entry of the curve S(M).  Needs per_reference=True; exactly one of
     the two budgets; not together with targets, report, track, ladder, stratify, dedup, profile, pair_aware,
-    template_aware, ceiling, amplicon files or "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
+    template_aware, ceiling, amplicon files or "quasi-mcp-hip-quality" (ValueError).  None: nothing changes.
+    replicates=K or [c_2, .., c_K] (BamApiConfig::replicates) with replicates_out (a path template holding "{R}"): the
+    file split into K disjoint downsamples in one qmcp_hip_solve_replicates_host call with REPLICATES_WHOLE_PAIRS |
+    REPLICATES_SHORTFALL on the reads as the ceiling and pair-aware flows pair them.  An int K: K replicates at
+    max_coverage; a list: replicate 1 at max_coverage, then the list's coverages.  Replicate 1 goes to out_path,
+    replicate R to replicates_out with {R} replaced.  Every file is written from its label and no find_pairs follows (it
+    would copy a record into two files): every input record is written at most once over all files.  Returns the list
+    of written counts.  replicates_report (a path) gets a TSV with one line per replicate -- coverage, offered, kept,
+    mates, short_positions, short_bases, records_written -- and an n_full line.  Replicates are disjoint, not
+    exchangeable: replicate 1 gets the first choices.  Needs per_reference=True; not together with targets, report,
+    track, ladder, stratify, dedup, profile, pair_aware, template_aware, ceiling, a budget, amplicon files or
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
+    if (replicates_out is not None or replicates_report is not None) and replicates is None:
+        raise ValueError("replicates_out and replicates_report need replicates")
+    if replicates is not None:
+        if isinstance(replicates, (int, np.integer)):
+            if not 1 <= int(replicates) <= REPLICATES_MAX:
+                raise ValueError(f"replicates must lie in 1 .. {REPLICATES_MAX}")
+            further = [int(max_coverage)] * (int(replicates) - 1)
+        else:
+            further = [int(c) for c in replicates]
+            if len(further) + 1 > REPLICATES_MAX:
+                raise ValueError(f"replicates: at most {REPLICATES_MAX} replicates in one call")
+        if any(not 1 <= c < 1 << 31 for c in further + [int(max_coverage)]):
+            raise ValueError("replicates: every coverage must lie in 1 .. 2^31 - 1")
+        if not per_reference:
+            raise ValueError("disjoint replicates need per_reference=True")
+        if further and (replicates_out is None or "{R}" not in str(replicates_out)):
+            raise ValueError("replicates_out must be a path template holding {R}")
+        for given, what in ((budget_reads is not None or budget_fraction is not None, "a budget"), (ceiling, "ceiling"),
+                            (pair_aware, "pair_aware"), (template_aware, "template_aware"), (targets, "targets"),
+                            (report, "a depth report"), (track is not None, "a depth track"),
+                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
+                            (dedup, "dedup"), (profile is not None, "a coverage profile")):
+            if given:
+                raise ValueError(f"disjoint replicates do not go together with {what}")
+        if bed or tsv or amplicons_by_reference:
+            raise ValueError("disjoint replicates do not take amplicon files")
+        if solver_uses_quality(solver_name):
+            raise ValueError("disjoint replicates do not take a solver that grades by quality")
+        err = C.create_string_buffer(1024)
+        rs = ReplicatesStats()
+        fur = np.array(further, dtype=np.uint32)
+        counts = (C.c_int64 * (len(further) + 1))()
+        n = _host.qmcp_host_downsample_bam_replicates(
+            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
+            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq), 1,
+            _p32(fur) if fur.size else None, fur.size, str(replicates_out).encode() if replicates_out else None,
+            None, None, None, None, 0, None, 0, 0, 0, 0, None, None, 0,
+            str(replicates_report).encode() if replicates_report else None, counts, C.byref(rs), err, 1024)
+        if n == -4:
+            raise ValueError(err.value.decode())
+        if n == -1:
+            raise KeyError(solver_name)
+        if n < 0:
+            raise OSError(f"downsample_bam({in_path}) failed ({n})")
+        return [int(c) for c in counts[:n]]
     if budget_report is not None and (budget_reads is None) == (budget_fraction is None):
         raise ValueError("budget_report needs exactly one of budget_reads and budget_fraction")
     if budget_reads is not None or budget_fraction is not None:

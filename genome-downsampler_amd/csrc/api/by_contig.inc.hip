@@ -12,6 +12,8 @@
 // solve (api/ceiling.inc.hip) is a profile whose batches select the DROPPED reads, complemented once the call is through.
 // A pair-aware solve (api/pairs.inc.hip) is this call at its first target, with the further stages run over all batches
 // once the last batch's mask is in place.
+// A replicate split (api/replicates.inc.hip) is this call at its first coverage, with the further replicates run over all
+// batches on the reads still free.
 // A budget solve (api/budget.inc.hip) is this call's grouping and batches under a search of its own: several whole solves,
 // each over every batch, at the coverages budget_plan.h picks.
 namespace {
@@ -27,6 +29,11 @@ struct PairRun;
 int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
                       const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
                       const uint32_t* lengths, uint64_t n64, uint64_t* d_mask, const qmcp_hip_stats& first);
+struct ReplicatesRun;
+int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, const std::vector<uint32_t>& offs,
+                     const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
+                     const uint32_t* d_ids, const uint32_t* lengths, uint32_t n_contigs_all, uint64_t n64, uint64_t* d_mask,
+                     const qmcp_hip_stats& first);
 
 // the batches' stats as one: counts and times summed, the route of the batch with the most reads
 void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, bool largest) {
@@ -166,7 +173,8 @@ int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
                               uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, uint32_t M, uint64_t* d_mask,
                               qmcp_hip_stats* stats, LadderRun* ladder = nullptr,
                               ProfileRun* profile = nullptr /* then M is the default cap */,
-                              PairRun* pairs = nullptr /* then M is the first stage's target */) {
+                              PairRun* pairs = nullptr /* then M is the first stage's target */,
+                              ReplicatesRun* replicates = nullptr /* then M is the first replicate's coverage */) {
     if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
     if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
     if (n64 > (1ull << 31))
@@ -221,6 +229,9 @@ int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
         first = false;
     }
     if (pairs) TRY(pair_later_stages(c, *pairs, sorted, offs, batches, d_starts, d_ends, lengths, n64, d_mask, sum));
+    if (replicates)
+        TRY(replicates_later(c, *replicates, sorted, offs, batches, d_starts, d_ends, d_ids, lengths, n_contigs, n64, d_mask,
+                             sum));
     HIP_TRY(hipStreamSynchronize(st));
     collect_spans(c);
     if (stats) *stats = sum;

@@ -179,6 +179,12 @@ struct qmcp_hip_ctx {
     // budget solves (api/budget.inc.hip), all its own: the accumulators, the curve and the depth histogram in one buffer
     // (BudgetWord words | curve | histogram), and the second input-order mask of the probes
     DevBuf bg_acc, bg_mask;
+    // disjoint replicates (api/replicates.inc.hip), all its own: the two sets of free reads' columns (starts, ends, input
+    // indices) that ping-pong between replicates, the scanned word popcounts of the taken candidates and their spine, the
+    // two offset tables, the candidates' taken bits, the input-order taken mask (whole pairs, several batches), the packed
+    // mask of one label, the mates' counters, the host entry's label bytes and the device entry's first mask
+    DevBuf rp_starts[2], rp_ends[2], rp_orig[2], rp_words, rp_spine, rp_offs[2], rp_kept, rp_taken, rp_lmask, rp_stat,
+        rp_labels, rp_mask0;
     uint64_t mask_reads = 0;  // reads the context's own mask buffer (c->mask) currently describes
     DevBuf evpk, evlast;  // event-driven uniform sweep: packed block words, last-changed-block index per block
     uint32_t last_iters = 0, last_blocks = 0;

@@ -176,7 +176,10 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
                       &c->pr_credit, &c->pr_cspine, &c->pr_starts, &c->pr_ends, &c->pr_orig, &c->pr_mask, &c->pr_need,
                       &c->pr_stat, &c->tp_ids, &c->tp_flags, &c->tp_sizes, &c->tp_stat,
                       &c->tq_tab, &c->tq_cap, &c->tq_flags, &c->tq_stat,
-                      &c->cl_poff, &c->cl_depth, &c->cl_spine, &c->cl_stat, &c->bg_acc, &c->bg_mask};
+                      &c->cl_poff, &c->cl_depth, &c->cl_spine, &c->cl_stat, &c->bg_acc, &c->bg_mask,
+                      &c->rp_starts[0], &c->rp_starts[1], &c->rp_ends[0], &c->rp_ends[1], &c->rp_orig[0], &c->rp_orig[1],
+                      &c->rp_words, &c->rp_spine, &c->rp_offs[0], &c->rp_offs[1], &c->rp_kept, &c->rp_taken, &c->rp_lmask,
+                      &c->rp_stat, &c->rp_labels, &c->rp_mask0};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < EV_COUNT; ++i)

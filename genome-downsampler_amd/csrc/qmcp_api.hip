@@ -35,6 +35,7 @@
 #include "target_table.h"
 #include "cap_table.h"
 #include "pair_plan.h"
+#include "replicates_plan.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
@@ -75,6 +76,8 @@
 //                       max(0, cov(p) - cap(p)) selecting the DROPPED reads, a device-side check, and the complement
 //   budget              the deepest coverage whose by-contig solve fits a number of reads: one grouping, the curve
 //                       S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
+//   replicates          one read set split into disjoint downsamples: the by-contig solve at the first coverage, every
+//                       further replicate solved on the reads still free, replicate-major over the one grouping's batches
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
@@ -99,3 +102,4 @@
 #include "api/templates_profile.inc.hip"
 #include "api/ceiling.inc.hip"
 #include "api/budget.inc.hip"
+#include "api/replicates.inc.hip"

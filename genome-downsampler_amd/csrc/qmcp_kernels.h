@@ -506,5 +506,32 @@ void launch_budget_tally(hipStream_t st, const uint32_t* cov, uint32_t ltot, uin
 void launch_budget_curve(hipStream_t st, const unsigned long long* hist, uint32_t H, unsigned long long* curve);
 void launch_budget_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, uint64_t* mask, unsigned long long* acc);
 
+// disjoint replicates (kernels/replicates.inc.hip; api/replicates.inc.hip drives them).  A replicate's candidates are n
+// reads in three columns with an origin column (origin_in: the grouping's Rec{key, index} array when `first`, a plain
+// column of input indices otherwise); `taken` has one bit per candidate (the solve's mask, or the input-order taken mask
+// gathered through the origin) and taken_base its scanned word popcounts with the total behind the last word.
+// launch_rep_split: the candidates that are NOT taken go, stably, to the other column set (16-byte aligned: the call's
+// own buffers); label != 0: labels[origin] = label for the taken ones.  kRepTileReads: the candidates one workgroup
+// takes at a time.  launch_rep_offsets: next[k] = offs[k] - (taken candidates before offs[k]) for k in [0, n_contigs].
+// launch_rep_mark: labels[origin] = label and the origin's bit in the input-order mask taken_in for the candidates a
+// solve kept; launch_rep_gather_taken: that mask's bits in candidate order; launch_rep_label_input: labels[i] = label
+// for the set bits of an input-order mask; launch_rep_complete_pairs: a placed read with label 0 whose mate (2q, 2q + 1)
+// carries `label` gets it too, with its bit in taken_in, *n_mates += the reads that joined; launch_rep_label_mask: the
+// packed mask of labels == label.
+static constexpr uint32_t kRepTileReads = 1024;
+void launch_rep_split(hipStream_t st, bool first, const uint32_t* starts, const uint32_t* ends, const void* origin_in,
+                      const uint64_t* taken, const uint32_t* taken_base, uint32_t n, uint32_t label, uint8_t* labels,
+                      uint32_t* starts_f, uint32_t* ends_f, uint32_t* origin_f);
+void launch_rep_offsets(hipStream_t st, const uint32_t* offs, uint32_t n_contigs, const uint64_t* taken,
+                        const uint32_t* taken_base, uint32_t* next);
+void launch_rep_mark(hipStream_t st, const uint64_t* kept, const uint32_t* origin, uint32_t n, uint32_t label,
+                     uint8_t* labels, uint64_t* taken_in);
+void launch_rep_gather_taken(hipStream_t st, bool first, const void* origin_in, uint32_t n, const uint64_t* taken_in,
+                             uint64_t* taken);
+void launch_rep_label_input(hipStream_t st, const uint64_t* mask, uint64_t n_reads, uint32_t label, uint8_t* labels);
+void launch_rep_complete_pairs(hipStream_t st, const uint32_t* ids, uint64_t n_reads, uint32_t label, uint8_t* labels,
+                               uint64_t* taken_in, unsigned long long* n_mates);
+void launch_rep_label_mask(hipStream_t st, const uint8_t* labels, uint64_t n_reads, uint32_t label, uint64_t* mask);
+
 }  // namespace qmcp
 #endif

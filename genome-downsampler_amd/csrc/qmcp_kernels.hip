@@ -58,6 +58,9 @@
 //                            kept depth against the caps, and the complement over the placed reads (mates joined first)
 //   budget                   budget downsampling: the depth histogram of a call, the curve S(M) = sum of min(cov, M) from
 //                            it, and a probe's pair completion with its popcount
+//   replicates               disjoint replicates: the dense split of a replicate's candidates into labels and the next
+//                            replicate's columns (LDS-staged), the next contig offsets, the taken mask and its gather,
+//                            the mates' completion, the packed mask of one label
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -103,5 +106,6 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/templates_profile.inc.hip"
 #include "kernels/ceiling.inc.hip"
 #include "kernels/budget.inc.hip"
+#include "kernels/replicates.inc.hip"
 
 }  // namespace qmcp

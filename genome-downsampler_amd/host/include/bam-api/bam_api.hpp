@@ -114,6 +114,14 @@ struct BamApiConfig {
     // ceiling refuses, nor with ceiling or a coverage profile (std::invalid_argument otherwise).  Neither: nothing changes.
     std::optional<std::uint64_t> budget_reads;
     std::optional<double> budget_fraction;
+    // Disjoint replicates: the coverages of replicates 2 .. K (an empty list: one replicate); replicate 1 is solved at
+    // the solve's max_coverage, replicate r + 1 on the reads the earlier ones left free
+    // (QuasiMcpHipSolver::solve_replicates / qmcp_hip_solve_replicates_host with QMCP_REPLICATES_WHOLE_PAIRS |
+    // QMCP_REPLICATES_SHORTFALL).  Every file is written from its label WITHOUT find_pairs, which would copy a record
+    // into two files.  Each coverage in 1 .. 2^31 - 1, at most QMCP_REPLICATES_MAX - 1 of them.  Needs per_reference and
+    // goes together with nothing that budget downsampling refuses, nor with a budget or a coverage profile
+    // (std::invalid_argument otherwise).  Not set: nothing changes.
+    std::optional<std::vector<std::uint32_t>> replicates;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -164,6 +172,8 @@ class BamApi {
     // BamApiConfig::budget_reads / budget_fraction: whether one is set, and the budget for a number of placed reads
     bool budget() const { return budget_reads_.has_value() || budget_fraction_.has_value(); }
     std::uint64_t budget_for(std::uint64_t placed_reads) const;
+    // BamApiConfig::replicates (not set: no replicate split)
+    const std::optional<std::vector<std::uint32_t>>& replicates() const { return replicates_; }
     // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
     // get_template_segments call, which also fills get_filtered_out_reads
     bool template_aware() const { return template_aware_; }
@@ -208,6 +218,7 @@ class BamApi {
     bool ceiling_ = false;
     std::optional<std::uint64_t> budget_reads_;
     std::optional<double> budget_fraction_;
+    std::optional<std::vector<std::uint32_t>> replicates_;
     std::vector<std::uint32_t> pair_stages_;
     bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false;
     std::vector<std::uint32_t> template_stages_;

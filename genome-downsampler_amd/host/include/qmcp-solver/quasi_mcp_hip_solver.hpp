@@ -124,6 +124,13 @@ class QuasiMcpHipSolver : public Solver {
     // without find_pairs.  std::invalid_argument for a BamApi without a budget and for what the library refuses
     std::unique_ptr<Solution> solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_budget_stats& last_budget_stats() const { return bgstats_; }
+    // Disjoint replicates for the reads of a BamApi built with BamApiConfig::replicates: one
+    // qmcp_hip_solve_replicates_host call with QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL at required_cover,
+    // then the BamApi's further coverages.  Returns one byte per read, the replicate that holds it (1-based, 0: none);
+    // a replicate holds whole pairs already -- the caller writes it without find_pairs.  std::invalid_argument for a
+    // BamApi without replicates and for what the library refuses
+    std::vector<std::uint8_t> solve_replicates(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_replicates_stats& last_replicates_stats() const { return rpstats_; }
     // S(M) = the bases any answer at coverage M must hold, M = 0 .. last_budget_stats().curve_entries - 1
     const std::vector<std::uint64_t>& last_budget_curve() const { return budget_curve_; }
     // Template-aware downsampling for a BamApi built with BamApiConfig::template_aware: qmcp_hip_solve_templates_host on
@@ -169,6 +176,7 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_ceiling_stats clstats_{};
     qmcp_hip_budget_stats bgstats_{};
+    qmcp_hip_replicates_stats rpstats_{};
     std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_template_stats tpstats_{};
     qmcp_hip_template_profile_stats tqstats_{};

@@ -179,6 +179,31 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
         budget_reads_ = config.budget_reads;
         budget_fraction_ = config.budget_fraction;
     }
+    if (config.replicates.has_value()) {
+        if (!per_reference_)
+            throw std::invalid_argument("disjoint replicates need per_reference: every replicate is solved one reference "
+                                        "at a time");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value())
+            throw std::invalid_argument("disjoint replicates do not take a budget");
+        if (config.ceiling) throw std::invalid_argument("disjoint replicates do not take ceiling");
+        if (config.pair_aware) throw std::invalid_argument("disjoint replicates do not take pair_aware");
+        if (config.template_aware) throw std::invalid_argument("disjoint replicates do not take template_aware");
+        if (!config.targets_filepath.empty()) throw std::invalid_argument("disjoint replicates do not take targets");
+        if (!config.coverage_ladder.empty()) throw std::invalid_argument("disjoint replicates do not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("disjoint replicates do not take a depth report");
+        if (!config.depth_track_filepath.empty()) throw std::invalid_argument("disjoint replicates do not take a depth track");
+        if (config.stratify_by != Stratify::NONE) throw std::invalid_argument("disjoint replicates do not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("disjoint replicates do not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("disjoint replicates do not take amplicon files");
+        if (config.replicates->size() > 15)
+            throw std::invalid_argument("disjoint replicates: at most 16 replicates in one call");
+        for (std::uint32_t cov : *config.replicates)
+            if (cov == 0 || cov >= (1u << 31))
+                throw std::invalid_argument("disjoint replicates: every coverage must lie in 1 .. 2^31 - 1");
+        replicates_ = config.replicates;
+    }
     if (config.template_aware) {
         if (!per_reference_)
             throw std::invalid_argument("template-aware downsampling needs per_reference: its stages are solved one "

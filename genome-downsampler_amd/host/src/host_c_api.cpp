@@ -1149,6 +1149,96 @@ std::int64_t qmcp_host_downsample_bam_ceiling(const char* solver_name, const cha
     }
 }
 
+// The file-to-file flow with BamApiConfig::replicates: one per-reference ingest, one qmcp_hip_solve_replicates_host call
+// with QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL (QuasiMcpHipSolver::solve_replicates) -- replicate 1 at
+// max_coverage, replicate r + 2 at further[r] -- and one write_paired_reads per replicate from its label: replicate 1 to
+// out_path, replicate R to out_template with its "{R}" replaced.  NO find_pairs: it would copy a record into two files,
+// so every input record is written at most once over all files.  targets / report / track / ladder_levels / stratify /
+// dedup / pair_aware / template_aware / ceiling / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given
+// so that it refuses the combinations it refuses; a solver that grades by quality is refused here.  written_out (1 +
+// n_further entries) receives each file's record count.  replicates_report (may be NULL): a TSV with one line per
+// replicate -- coverage, offered, kept, mates, short_positions, short_bases, records_written -- and an n_full line.
+// rstats (may be NULL) takes the stats.  Returns the number of files written; -1 on an unknown solver, -3 out of memory,
+// -4 with a message in err when the configuration is refused, -5 when the report cannot be written.
+std::int64_t qmcp_host_downsample_bam_replicates(const char* solver_name, const char* in_path, const char* out_path,
+                                                 const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
+                                                 std::uint32_t min_mapq, int per_reference, const std::uint32_t* further,
+                                                 std::uint32_t n_further, const char* out_template, const char* targets,
+                                                 const char* report, const char* track, const std::uint32_t* ladder_levels,
+                                                 std::uint32_t n_ladder_levels, const char* stratify, int dedup,
+                                                 int pair_aware, int template_aware, int ceiling, const char* bed,
+                                                 const char* tsv, int amplicons_by_reference, const char* replicates_report,
+                                                 std::int64_t* written_out, qmcp_hip_replicates_stats* rstats, char* err,
+                                                 std::size_t err_cap) {
+    qmcp::Solver* found = resolve(solver_name);
+    if (found == nullptr) return -1;
+    try {
+        bam_api::BamApiConfig cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.per_reference = per_reference != 0;
+        cfg.replicates = std::vector<std::uint32_t>();
+        if (further != nullptr) cfg.replicates->assign(further, further + n_further);
+        cfg.pair_aware = pair_aware != 0;
+        cfg.template_aware = template_aware != 0;
+        cfg.ceiling = ceiling != 0;
+        if (targets && targets[0]) cfg.targets_filepath = targets;
+        if (report && report[0]) cfg.depth_report_filepath = report;
+        if (track && track[0]) cfg.depth_track_filepath = track;
+        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
+        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
+        cfg.dedup = dedup != 0;
+        if (bed && bed[0]) cfg.bed_filepath = bed;
+        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        const std::string tmpl = out_template ? out_template : "";
+        const std::size_t at = tmpl.find("{R}");
+        if (!cfg.replicates->empty() && at == std::string::npos)
+            throw std::invalid_argument("the replicates' output template has no {R}");
+        if (found->uses_quality_of_reads())
+            throw std::invalid_argument("disjoint replicates do not take a solver that grades by quality");
+        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
+        if (hip == nullptr) throw std::invalid_argument("this solver has no disjoint replicates");
+        bam_api::BamApi api(in_path, cfg);
+        const std::vector<std::uint8_t> labels = hip->solve_replicates(max_coverage, api);
+        const std::size_t k = api.replicates()->size() + 1;
+        std::vector<std::uint32_t> written(k, 0);
+        for (std::size_t r = 1; r <= k; ++r) {
+            std::string path = out_path;
+            if (r > 1) {
+                path = tmpl;
+                path.replace(at, 3, std::to_string(r));
+            }
+            std::vector<bam_api::ReadIndex> kept;
+            for (std::size_t i = 0; i < labels.size(); ++i)
+                if (labels[i] == r) kept.push_back(i);
+            written[r - 1] = api.write_paired_reads(path, kept);
+            if (written_out) written_out[r - 1] = written[r - 1];
+        }
+        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
+        const qmcp_hip_replicates_stats& rs = hip->last_replicates_stats();
+        if (rstats != nullptr) *rstats = rs;
+        if (replicates_report && replicates_report[0]) {
+            std::FILE* f = std::fopen(replicates_report, "w");
+            if (f == nullptr) return -5;
+            std::fprintf(f, "#replicate\tcoverage\toffered\tkept\tmates\tshort_positions\tshort_bases\trecords_written\n");
+            for (std::size_t r = 0; r < k; ++r)
+                std::fprintf(f, "%zu\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%u\n", r + 1,
+                             r == 0 ? max_coverage : (*api.replicates())[r - 1], (unsigned long long)rs.n_offered[r],
+                             (unsigned long long)rs.n_kept[r], (unsigned long long)rs.n_mates[r],
+                             (unsigned long long)rs.short_positions[r], (unsigned long long)rs.short_bases[r], written[r]);
+            std::fprintf(f, "n_full\t%u\n", rs.n_full);
+            if (std::fclose(f) != 0) return -5;
+        }
+        return (std::int64_t)k;
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
 // The file-to-file flow with BamApiConfig::budget_reads / budget_fraction: one per-reference ingest, one
 // qmcp_hip_solve_budget_host call with QMCP_BUDGET_WHOLE_PAIRS (QuasiMcpHipSolver::solve_budget) -- max_coverage is the
 // upper end of the search -- and write_paired_reads from its mask: whole pairs already, and NO find_pairs, which would

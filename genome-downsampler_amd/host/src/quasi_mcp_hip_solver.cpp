@@ -295,6 +295,38 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_
     return kept;
 }
 
+std::vector<std::uint8_t> QuasiMcpHipSolver::solve_replicates(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.replicates().has_value() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("disjoint replicates need a BamApi built with BamApiConfig::replicates");
+    std::vector<std::uint32_t> coverages{required_cover};
+    coverages.insert(coverages.end(), bam_api.replicates()->begin(), bam_api.replicates()->end());
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    std::vector<std::uint8_t> labels(n, 0);
+    const int rc = qmcp_hip_solve_replicates_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                                  reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                                  coverages.data(), (std::uint32_t)coverages.size(),
+                                                  QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL, labels.data(),
+                                                  &stats_, nullptr, &rpstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_replicates_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return labels;
+}
+
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_ceiling(std::uint32_t required_cover, bam_api::BamApi& bam_api,
                                                            const std::vector<std::uint32_t>& offsets,
                                                            const std::vector<std::uint32_t>& region_starts,

@@ -734,6 +734,67 @@ int qmcp_hip_solve_ladder_device(qmcp_hip_ctx* ctx,
                                  const uint32_t* coverages, uint32_t n_levels, uint8_t* d_levels_out,
                                  void* hip_stream, qmcp_hip_stats* stats, qmcp_hip_ladder_stats* lstats);
 
+/* Disjoint replicates: one read set split into several INDEPENDENT downsamples in one call -- pseudo-replicates at 30x, a
+ * 30x "truth" subset beside a disjoint 10x "test" subset.  Reads, contig_ids, contig_lengths / n_contigs and limits are
+ * those of qmcp_hip_solve_by_contig_host.  coverages[0 .. n_replicates - 1], each in 1 .. 2^31 - 1, in any order, equal
+ * values allowed; 1 <= n_replicates <= QMCP_REPLICATES_MAX.
+ * Definition: R_1 is the mask qmcp_hip_solve_by_contig_host returns at coverages[0]; R_r (r > 1) is the mask it returns
+ * at coverages[r - 1] for the placed reads that lie in none of R_1 .. R_(r-1), ALONE, in input order with their contig
+ * ids, expressed over the input indices.  Output: one byte per read, labels[i] = r if i is in R_r, 0 otherwise (unplaced
+ * reads get 0); n_reads bytes in INPUT order, fully overwritten.
+ * The replicates are disjoint, R_r has minimum cardinality on the reads that were left when it was solved, and at every
+ * position cov_Rr(p) >= min(cov(p) - sum_{j<r} cov_Rj(p), coverages[r - 1]).  A replicate that finds no read left is
+ * empty, and so is every later one; that is no error.
+ * QMCP_REPLICATES_WHOLE_PAIRS: reads (2q, 2q + 1) are pair q (an odd n_reads is QMCP_EINVAL).  After replicate r's solve
+ * a placed read whose placed mate is in R_r joins R_r (it is still free: pairs move together; an unplaced mate never
+ * joins).  The coverage guarantee still holds -- a replicate only grows --, disjointness holds pair-wise, minimum
+ * cardinality is no longer claimed.
+ * QMCP_REPLICATES_SHORTFALL: per replicate, short_positions counts the positions where the replicate's depth (mates
+ * included) is below min(cov(p), coverages[r - 1]), cov the depth of ALL placed reads, short_bases sums the differences,
+ * and n_full is the number of leading replicates without a short position.  Computed on the device by the depth
+ * report's kernels over the packed mask of labels == r; without the flag the fields are 0.
+ * How: the reads are grouped by contig once per call; a call of one batch keeps the batch's gathered columns and
+ * compacts the reads that are still free from replicate to replicate between two sets of columns; a call of several
+ * batches walks replicate-major over them and gathers each batch's free reads from the grouping.
+ * Errors: NULL coverages, n_replicates outside 1 .. QMCP_REPLICATES_MAX, a coverage of 0, unknown flag bits and an odd
+ * n_reads under QMCP_REPLICATES_WHOLE_PAIRS are QMCP_EINVAL, a coverage of 2^31 or more is QMCP_ERANGE: on the host,
+ * before the context is looked at and before anything is copied or launched; labels_out is not written.  A bad contig
+ * id (QMCP_EINVAL) or a bad read (QMCP_EREAD) is found on the device as in qmcp_hip_solve_by_contig_host; by then the
+ * device bytes have been cleared -- they stay all zero, and the host entry does not write labels_out.
+ * stats (may be NULL) are replicate 1's solve: they equal the plain by-contig call at coverages[0].  rep_stats (may be
+ * NULL; n_replicates entries): the batch-summed stats of each replicate's solves.  rstats (may be NULL): the replicates.
+ * The host entry leaves R_1 in the context.  The device entry takes the three columns and the bytes in device memory,
+ * is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the work has completed. */
+#define QMCP_REPLICATES_MAX 16
+#define QMCP_REPLICATES_WHOLE_PAIRS 1u
+#define QMCP_REPLICATES_SHORTFALL 2u
+typedef struct qmcp_hip_replicates_stats {
+    uint32_t n_replicates, flags;
+    uint32_t n_full, reserved;                        /* leading replicates without a short position (SHORTFALL)     */
+    uint64_t n_offered[QMCP_REPLICATES_MAX];          /* reads left when the replicate began                         */
+    uint64_t n_kept[QMCP_REPLICATES_MAX];             /* |R_r|, mates included                                       */
+    uint64_t n_mates[QMCP_REPLICATES_MAX];            /* reads that joined only as mates (WHOLE_PAIRS)               */
+    uint64_t short_positions[QMCP_REPLICATES_MAX];    /* SHORTFALL                                                   */
+    uint64_t short_bases[QMCP_REPLICATES_MAX];        /* SHORTFALL                                                   */
+    float ms_replicate[QMCP_REPLICATES_MAX];          /* device time of the replicate's solves                       */
+    float ms_split;                                   /* everything the call adds around the solves                  */
+    float reserved1;
+} qmcp_hip_replicates_stats;
+int qmcp_hip_solve_replicates_host(qmcp_hip_ctx* ctx,
+                                   const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                   uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                   const uint32_t* coverages, uint32_t n_replicates, uint32_t flags,
+                                   uint8_t* labels_out, qmcp_hip_stats* stats,
+                                   qmcp_hip_stats* rep_stats /* n_replicates entries, or NULL */,
+                                   qmcp_hip_replicates_stats* rstats);
+int qmcp_hip_solve_replicates_device(qmcp_hip_ctx* ctx,
+                                     const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                     uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                     const uint32_t* coverages, uint32_t n_replicates, uint32_t flags,
+                                     uint8_t* d_labels_out, void* hip_stream, qmcp_hip_stats* stats,
+                                     qmcp_hip_stats* rep_stats /* n_replicates entries, or NULL */,
+                                     qmcp_hip_replicates_stats* rstats);
+
 /* Stratified downsampling: one coverage cap per stratum -- strand, read group, sample, lane, haplotype, anything the
  * caller can turn into a small integer per read ("bring every sample of a pooled file to 30x"; "half of the coverage
  * from each strand").  Reads, contig_ids, contig_lengths / n_contigs and the per-read rules are those of
