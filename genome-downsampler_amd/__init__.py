@@ -326,6 +326,29 @@ class Options(C.Structure):
     ]
 
 
+class DownsampleRequest(C.Structure):
+    """qmcp_host_downsample_request (genome-downsampler_amd/host/include/qmcp_host_request.h): what
+    qmcp_host_downsample_bam takes.  Build one with _downsample_request, which knows the fields whose "not given" is
+    not zero"""
+    _fields_ = (
+        [("struct_size", C.c_uint64)]
+        + [(name, C.c_char_p) for name in ("solver_name", "in_path", "out_path", "filtered_path", "bed", "tsv", "targets",
+                                           "report", "track", "track_channel")]
+        + [("ladder_levels", C.POINTER(C.c_uint32))]
+        + [(name, C.c_char_p) for name in ("ladder_template", "stratify", "strata_report", "dedup_report")]
+        + [(name, C.POINTER(C.c_uint32)) for name in ("region_offsets", "region_starts", "region_ends", "region_caps")]
+        + [("n_refs", C.c_uint64), ("pair_stages", C.POINTER(C.c_uint32)), ("template_stages", C.POINTER(C.c_uint32)),
+           ("ceiling_report", C.c_char_p), ("budget_report", C.c_char_p), ("budget_reads", C.c_uint64),
+           ("budget_fraction", C.c_double), ("replicates_further", C.POINTER(C.c_uint32)),
+           ("replicates_template", C.c_char_p), ("replicates_report", C.c_char_p)]
+        + [(name, C.c_uint32) for name in ("max_coverage", "min_len", "min_mapq", "target_padding", "report_bins",
+                                           "track_cap", "n_ladder_levels", "default_cap", "n_pair_stages",
+                                           "n_template_stages", "n_replicates_further")]
+        + [(name, C.c_int32) for name in ("amplicon_mode", "per_reference", "amplicons_by_reference", "keep_off_target",
+                                          "dedup", "has_regions", "pair_aware", "template_aware", "split_spliced",
+                                          "include_secondary", "ceiling", "has_budget_reads", "has_replicates")])
+
+
 SWEEP_AUTO, SWEEP_FAST, SWEEP_GENERAL, SWEEP_EVENTS = 0, 1, 2, 3
 _SWEEP_NAMES = {None: 0, "auto": 0, "fast": 1, "gen": 2, "general": 2, "ev": 3, "events": 3}
 
@@ -497,11 +520,11 @@ if _host is not None:
                                          C.c_uint64, _u64p, _u32p, _u32p, _u32p, _u32p, _u8p, C.c_uint64, _u64p,
                                          _u64p, _u32p]
     _host.qmcp_host_read_bam.restype = C.c_int64
-    _host.qmcp_host_downsample_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                               C.c_uint32, C.c_uint32]
+    _host.qmcp_host_downsample_bam.argtypes = [C.POINTER(DownsampleRequest), C.POINTER(C.c_int64), C.c_uint64,
+                                               C.POINTER(CeilingStats), C.POINTER(BudgetStats),
+                                               C.POINTER(ReplicatesStats), C.POINTER(TemplateStats),
+                                               C.POINTER(TemplateProfileStats), C.c_char_p, C.c_size_t]
     _host.qmcp_host_downsample_bam.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_per_reference.argtypes = _host.qmcp_host_downsample_bam.argtypes
-    _host.qmcp_host_downsample_bam_per_reference.restype = C.c_int64
     _host.qmcp_host_read_bam_per_reference.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32,
                                                        C.c_uint64, _u64p, _u32p, _u32p, _u32p, _u32p,
                                                        C.POINTER(C.c_uint8), _u32p, C.c_uint64, _u64p,
@@ -514,89 +537,17 @@ if _host is not None:
                                                       C.POINTER(C.c_uint64), C.c_uint64, _u32p, C.POINTER(C.c_uint64),
                                                       C.c_char_p, C.c_size_t]
     _host.qmcp_host_read_bam_by_reference.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_by_reference.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                            C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int,
-                                                            C.c_int, C.c_int, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_by_reference.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_targets.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                       C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
-                                                       C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_targets.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_report.argtypes = _host.qmcp_host_downsample_bam_targets.argtypes[:-2] + \
-        [C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_report.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_track.argtypes = _host.qmcp_host_downsample_bam_report.argtypes[:-2] + \
-        [C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_track.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_ladder.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                      C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
-                                                      C.c_int, _u32p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int64),
-                                                      C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_ladder.restype = C.c_int64
     _host.qmcp_host_read_bam_stratified.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, _u64p,
                                                     _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_uint8), _u32p, _u32p,
                                                     C.c_uint64, _u64p, C.POINTER(C.c_uint64), C.c_uint64, _u32p,
                                                     C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t,
                                                     C.POINTER(C.c_uint64), C.c_int, C.c_char_p, C.c_size_t]
     _host.qmcp_host_read_bam_stratified.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_stratified.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                          C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_char_p,
-                                                          C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_char_p,
-                                                          C.c_size_t]
-    _host.qmcp_host_downsample_bam_stratified.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_dedup.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                     C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_char_p, _u32p,
-                                                     C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
-                                                     C.c_char_p, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_dedup.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                       C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p, _u32p,
-                                                       C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p,
-                                                       C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_profile.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_pairs.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                     C.c_uint32, C.c_uint32, C.c_int, _u32p, C.c_uint32, C.c_char_p,
-                                                     C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p, C.c_int,
-                                                     C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_pairs.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_ceiling.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                       C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p, _u32p,
-                                                       C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32,
-                                                       C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                                       C.c_int, C.c_char_p, C.POINTER(CeilingStats), C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_ceiling.restype = C.c_int64
-    # (solver, in, out, filtered, M, min_len, min_mapq, per_reference, further, n_further, out_template, targets, report,
-    #  track, ladder_levels, n_ladder_levels, stratify, dedup, pair_aware, template_aware, ceiling, bed, tsv,
-    #  amplicons_by_reference, replicates_report, written_out, rstats, err, err_cap)
-    _host.qmcp_host_downsample_bam_replicates.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                          C.c_uint32, C.c_uint32, C.c_int, _u32p, C.c_uint32, C.c_char_p,
-                                                          C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32,
-                                                          C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
-                                                          C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int64),
-                                                          C.POINTER(ReplicatesStats), C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_replicates.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_budget.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                      C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_double,
-                                                      C.c_char_p, C.c_char_p, C.c_char_p, _u32p, C.c_uint32, C.c_char_p,
-                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int,
-                                                      C.c_char_p, C.POINTER(BudgetStats), C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_budget.restype = C.c_int64
     _host.qmcp_host_read_bam_templates.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _u32p,
                                                    _u32p, _u32p, _u32p, _u32p, _u32p, _u64p, C.c_uint64, _u64p,
                                                    C.POINTER(C.c_uint64), C.c_uint64, _u32p, C.POINTER(C.c_uint64),
                                                    C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     _host.qmcp_host_read_bam_templates.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_templates.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
-                                                         C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _u32p,
-                                                         C.c_uint32, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, _u32p,
-                                                         C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                                         C.c_int, C.POINTER(TemplateStats), C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_templates.restype = C.c_int64
-    _host.qmcp_host_downsample_bam_templates_profile.argtypes = [
-        C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _u32p,
-        C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, C.POINTER(TemplateStats),
-        C.POINTER(TemplateProfileStats), C.c_char_p, C.c_size_t]
-    _host.qmcp_host_downsample_bam_templates_profile.restype = C.c_int64
     _host.qmcp_host_check_targets_config.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, _u64p, C.c_char_p,
                                                      C.c_size_t]
     _host.qmcp_host_check_targets_config.restype = C.c_int64
@@ -2038,105 +1989,65 @@ def read_bam(path, bed=None, tsv=None, amplicon_mode=0, min_length=0, min_mapq=0
     return out
 
 
-def _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity, ref_capacity=1 << 24):
-    ids = np.empty(capacity, np.uint64)
-    cols = {k: np.empty(capacity, np.uint32) for k in ("starts", "ends", "qualities", "seq_lengths", "contig_ids")}
-    first = np.empty(capacity, np.uint8)
-    filt = np.empty(capacity, np.uint64)
-    refs = np.empty(ref_capacity, np.uint32)
-    nf, nr = C.c_uint64(0), C.c_uint64(0)
-    err = C.create_string_buffer(512)
-    n = _host.qmcp_host_read_bam_per_reference(str(path).encode(), str(bed).encode() if bed else None,
-                                               str(tsv).encode() if tsv else None, int(min_length), int(min_mapq),
-                                               capacity, _p64(ids), _p32(cols["starts"]), _p32(cols["ends"]),
-                                               _p32(cols["qualities"]), _p32(cols["seq_lengths"]),
-                                               first.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(cols["contig_ids"]),
-                                               capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
-                                               C.byref(nr), err, 512)
-    if n == -4:
-        raise ValueError(err.value.decode())
-    if n < 0:
-        raise OSError(f"read_bam({path}, per_reference=True) failed ({n})")
-    out = {k: v[:n].copy() for k, v in cols.items()}
-    lengths = refs[:nr.value].copy()
-    out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
-               ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths)
-    return out
+# the column arguments of the qmcp_host_read_bam_* entries that hand out paired reads, in their order
+_PAIRED_COLUMNS = (("bam_ids", np.uint64), ("starts", np.uint32), ("ends", np.uint32), ("qualities", np.uint32),
+                   ("seq_lengths", np.uint32), ("is_first", np.uint8), ("contig_ids", np.uint32))
 
 
-def _read_bam_templates(path, min_length, min_mapq, split_spliced, include_secondary, capacity, ref_capacity=1 << 24):
-    names = ("starts", "ends", "contig_ids", "template_ids", "qualities", "seq_lengths")
-    cols = {k: np.empty(capacity, np.uint32) for k in names}
-    recs = np.empty(capacity, np.uint64)
-    filt = np.empty(capacity, np.uint64)
-    refs = np.empty(ref_capacity, np.uint32)
-    nf, nr, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    err = C.create_string_buffer(512)
-    n = _host.qmcp_host_read_bam_templates(str(path).encode(), int(min_length), int(min_mapq), int(bool(split_spliced)),
-                                           int(bool(include_secondary)), capacity, *(_p32(cols[k]) for k in names),
-                                           _p64(recs), capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
-                                           C.byref(nr), C.byref(nt), err, 512)
-    if n < 0:
-        raise OSError(f"read_bam({path}, templates=True) failed ({n}): {err.value.decode(errors='replace')}")
-    out = {k: v[:n].copy() for k, v in cols.items()}
-    out.update(segment_records=recs[:n].copy(), filtered_out=filt[:nf.value].copy(), n_templates=int(nt.value),
-               contig_lengths=refs[:nr.value].copy())
-    return out
-
-
-def _read_bam_stratified(path, stratify, min_length, min_mapq, capacity, ref_capacity=1 << 24, names_capacity=1 << 22):
-    ids = np.empty(capacity, np.uint64)
-    cols = {k: np.empty(capacity, np.uint32)
-            for k in ("starts", "ends", "qualities", "seq_lengths", "contig_ids", "strata")}
-    first = np.empty(capacity, np.uint8)
-    filt = np.empty(capacity, np.uint64)
-    refs = np.empty(ref_capacity, np.uint32)
-    nf, nr, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    names = C.create_string_buffer(names_capacity)
-    err = C.create_string_buffer(1024)
-    n = _host.qmcp_host_read_bam_stratified(str(path).encode(), stratify.encode(), int(min_length), int(min_mapq),
-                                            capacity, _p64(ids), _p32(cols["starts"]), _p32(cols["ends"]),
-                                            _p32(cols["qualities"]), _p32(cols["seq_lengths"]),
-                                            first.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(cols["contig_ids"]),
-                                            _p32(cols["strata"]), capacity, _p64(filt), C.byref(nf), ref_capacity,
-                                            _p32(refs), C.byref(nr), names, names_capacity, C.byref(ns), 1, err, 1024)
-    if n == -4:
-        raise ValueError(err.value.decode())
-    if n < 0:
-        raise OSError(f"read_bam({path}, stratify={stratify!r}) failed ({n})")
-    out = {k: v[:n].copy() for k, v in cols.items()}
-    lengths = refs[:nr.value].copy()
-    out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
-               ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths,
-               stratum_names=names.value.decode().split("\n")[:ns.value])
-    return out
-
-
-def _read_bam_by_reference(path, bed, tsv, amplicon_mode, per_reference, min_length, min_mapq, capacity,
-                           ref_capacity=1 << 24):
-    ids = np.empty(capacity, np.uint64)
-    cols = {k: np.empty(capacity, np.uint32) for k in ("starts", "ends", "qualities", "seq_lengths", "contig_ids")}
-    first = np.empty(capacity, np.uint8)
-    filt = np.empty(capacity, np.uint64)
-    refs = np.empty(ref_capacity, np.uint32)
+def _read_bam_call(entry, path, head, capacity, columns, what, tail=(), ref_capacity=1 << 24):
+    """one qmcp_host_read_bam_* call on buffers of `capacity` entries: (path, *head, capacity, one buffer per (name,
+    dtype) of `columns`, the filtered-out ids, the reference lengths, *tail, the message) -> the columns cut to the
+    entry's count, with filtered_out and contig_lengths.  -4 raises ValueError with the entry's message, another
+    negative return OSError naming the call as read_bam(path<what>)"""
+    bufs = {name: np.empty(capacity, dtype) for name, dtype in columns}
+    filt, refs = np.empty(capacity, np.uint64), np.empty(ref_capacity, np.uint32)
     nf, nr = C.c_uint64(0), C.c_uint64(0)
     err = C.create_string_buffer(1024)
-    n = _host.qmcp_host_read_bam_by_reference(str(path).encode(), str(bed).encode() if bed else None,
-                                              str(tsv).encode() if tsv else None, int(amplicon_mode),
-                                              int(bool(per_reference)), 1, int(min_length), int(min_mapq), capacity,
-                                              _p64(ids), _p32(cols["starts"]), _p32(cols["ends"]),
-                                              _p32(cols["qualities"]), _p32(cols["seq_lengths"]),
-                                              first.ctypes.data_as(C.POINTER(C.c_uint8)), _p32(cols["contig_ids"]),
-                                              capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
-                                              C.byref(nr), err, 1024)
+    pointers = (b.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(b.dtype))) for b in bufs.values())
+    n = entry(str(path).encode(), *head, capacity, *pointers, capacity, _p64(filt), C.byref(nf), ref_capacity, _p32(refs),
+              C.byref(nr), *tail, err, 1024)
     if n == -4:
         raise ValueError(err.value.decode())
     if n < 0:
-        raise OSError(f"read_bam({path}, amplicons_by_reference=True) failed ({n})")
-    out = {k: v[:n].copy() for k, v in cols.items()}
-    lengths = refs[:nr.value].copy()
-    out.update(bam_ids=ids[:n].copy(), is_first=first[:n].astype(bool), filtered_out=filt[:nf.value].copy(),
-               ref_genome_length=int(lengths[0]) if lengths.size else 0, contig_lengths=lengths)
+        message = err.value.decode(errors="replace")
+        raise OSError(f"read_bam({path}{what}) failed ({n})" + (f": {message}" if message else ""))
+    out = {name: b[:n].copy() for name, b in bufs.items()}
+    out.update(filtered_out=filt[:nf.value].copy(), contig_lengths=refs[:nr.value].copy())
+    if "is_first" in out:
+        out.update(is_first=out["is_first"].astype(bool),
+                   ref_genome_length=int(out["contig_lengths"][0]) if out["contig_lengths"].size else 0)
+    return out
+
+
+def _read_bam_per_reference(path, bed, tsv, min_length, min_mapq, capacity):
+    head = (str(bed).encode() if bed else None, str(tsv).encode() if tsv else None, int(min_length), int(min_mapq))
+    return _read_bam_call(_host.qmcp_host_read_bam_per_reference, path, head, capacity, _PAIRED_COLUMNS,
+                          ", per_reference=True")
+
+
+def _read_bam_by_reference(path, bed, tsv, amplicon_mode, per_reference, min_length, min_mapq, capacity):
+    head = (str(bed).encode() if bed else None, str(tsv).encode() if tsv else None, int(amplicon_mode),
+            int(bool(per_reference)), 1, int(min_length), int(min_mapq))
+    return _read_bam_call(_host.qmcp_host_read_bam_by_reference, path, head, capacity, _PAIRED_COLUMNS,
+                          ", amplicons_by_reference=True")
+
+
+def _read_bam_stratified(path, stratify, min_length, min_mapq, capacity, names_capacity=1 << 22):
+    names, ns = C.create_string_buffer(names_capacity), C.c_uint64(0)
+    out = _read_bam_call(_host.qmcp_host_read_bam_stratified, path, (stratify.encode(), int(min_length), int(min_mapq)),
+                         capacity, _PAIRED_COLUMNS + (("strata", np.uint32),), f", stratify={stratify!r}",
+                         tail=(names, names_capacity, C.byref(ns), 1))
+    out["stratum_names"] = names.value.decode().split("\n")[:ns.value]
+    return out
+
+
+def _read_bam_templates(path, min_length, min_mapq, split_spliced, include_secondary, capacity):
+    columns = tuple((k, np.uint32) for k in ("starts", "ends", "contig_ids", "template_ids", "qualities", "seq_lengths"))
+    nt = C.c_uint64(0)
+    out = _read_bam_call(_host.qmcp_host_read_bam_templates, path,
+                         (int(min_length), int(min_mapq), int(bool(split_spliced)), int(bool(include_secondary))), capacity,
+                         columns + (("segment_records", np.uint64),), ", templates=True", tail=(C.byref(nt),))
+    out["n_templates"] = int(nt.value)
     return out
 
 
@@ -2205,6 +2116,64 @@ def write_template_report(path, template_stats, records_written=None, template_p
         f.write("#size\ttemplates\n")
         for b, count in enumerate(ts.size_hist):
             f.write(f"{b + 1 if b < 7 else '8+'}\t{count}\n")
+
+
+class _Mode:
+    """one mode of downsample_bam as its refusals name it: `name` ("disjoint replicates", plural), the options it does
+    not go together with in the order they are reported -- one_sentence: the older modes name them all in one sentence
+    --, and whether it takes amplicon files and a solver that grades by quality"""
+
+    def __init__(self, name, refuses, plural=False, one_sentence=False, amplicon_files=False, quality_solver=False):
+        self.name, self.refuses, self.plural, self.one_sentence = name, refuses, plural, one_sentence
+        self.amplicon_files, self.quality_solver = amplicon_files, quality_solver
+
+
+_REPLICATES = _Mode("disjoint replicates", ("a budget", "ceiling", "pair_aware", "template_aware", "targets", "a depth report",
+                                            "a depth track", "a coverage ladder", "stratify", "dedup", "a coverage profile"),
+                    plural=True)
+_BUDGET = _Mode("budget downsampling", ("ceiling", "pair_aware", "template_aware", "targets", "a depth report",
+                                        "a depth track", "a coverage ladder", "stratify", "dedup", "a coverage profile"))
+_CEILING = _Mode("ceiling downsampling", ("pair_aware", "template_aware", "targets", "a depth report", "a depth track",
+                                          "a coverage ladder", "stratify", "dedup"))
+_TEMPLATES = _Mode("template-aware downsampling", ("pair_aware", "targets", "a depth report", "a depth track",
+                                                   "a coverage ladder", "stratify", "dedup", "a coverage profile"))
+_PAIRS = _Mode("pair-aware downsampling", ("targets", "a depth report", "a depth track", "a coverage ladder", "stratify",
+                                           "dedup", "a coverage profile"))
+_TRACK = _Mode("a depth track", ("a coverage ladder", "stratify", "dedup", "a coverage profile"), one_sentence=True,
+               amplicon_files=True, quality_solver=True)
+_PROFILE = _Mode("a coverage profile", ("targets", "a depth report", "a coverage ladder", "stratify", "dedup"),
+                 one_sentence=True)
+_DEDUP = _Mode("duplicate-aware downsampling", ("targets", "a depth report", "a coverage ladder", "stratify"),
+               one_sentence=True)
+_STRATIFIED = _Mode("stratified downsampling", ("targets", "a depth report", "a coverage ladder"), one_sentence=True)
+_LADDER = _Mode("a coverage ladder", ("targets", "a depth report"), one_sentence=True, amplicon_files=True)
+
+_REGION_FIELDS = ("region_offsets", "region_starts", "region_ends", "region_caps")
+_COUNT_FIELDS = {"ladder_levels": "n_ladder_levels", "pair_stages": "n_pair_stages", "template_stages": "n_template_stages",
+                 "replicates_further": "n_replicates_further"}
+
+
+def _downsample_request(**fields):
+    """a DownsampleRequest from its fields by name (an unknown name is a KeyError): None is "not given"; a path or a
+    name is anything str() renders; an array is a sequence of uint32, its count field filled in with it.  The fields
+    whose "not given" is not zero start there: amplicon_mode -1, split_spliced 1, budget_fraction -1"""
+    types = dict(DownsampleRequest._fields_)
+    request = DownsampleRequest(struct_size=C.sizeof(DownsampleRequest), amplicon_mode=-1, split_spliced=1,
+                                budget_fraction=-1.0)
+    request.arrays = []  # (the request points into them)
+    for name, value in fields.items():
+        if value is None:
+            continue
+        if types[name] is C.c_char_p:
+            value = str(value).encode()
+        elif types[name] is _u32p:
+            array = np.ascontiguousarray(value, dtype=np.uint32)
+            request.arrays.append(array)
+            if name in _COUNT_FIELDS:
+                setattr(request, _COUNT_FIELDS[name], array.size)
+            value = _p32(array)
+        setattr(request, name, value)
+    return request
 
 
 def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=None, min_length=0, min_mapq=0,
@@ -2313,6 +2282,52 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     track, ladder, stratify, dedup, profile, pair_aware, template_aware, ceiling, a budget, amplicon files or
     "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
+    given = {"a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
+             "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
+             "a depth report": bool(report), "a depth track": track is not None, "a coverage ladder": ladder is not None,
+             "stratify": stratify is not None, "dedup": bool(dedup), "a coverage profile": profile is not None}
+    amplicon_files = bool(bed or tsv or amplicons_by_reference)
+
+    def need_per_reference(mode):
+        if not per_reference:
+            raise ValueError(f"{mode.name} {'need' if mode.plural else 'needs'} per_reference=True")
+
+    def refuse(mode):
+        does_not = f"{mode.name} {'do' if mode.plural else 'does'} not"
+        offences = [what for what in mode.refuses if given[what]]
+        if offences and mode.one_sentence:
+            raise ValueError(f"{does_not} go together with {', '.join(mode.refuses[:-1])} or {mode.refuses[-1]}")
+        if offences:
+            raise ValueError(f"{does_not} go together with {offences[0]}")
+        if amplicon_files and not mode.amplicon_files:
+            raise ValueError(f"{does_not} take amplicon files")
+        if not mode.quality_solver and solver_uses_quality(solver_name):
+            raise ValueError(f"{does_not} take a solver that grades by quality")
+
+    def stages_of(stages, name):
+        stages = None if stages is None else [int(t) for t in stages]
+        if stages is not None and not stages:
+            raise ValueError(f"{name} must hold at least one target (or be None for the default schedule)")
+        return stages
+
+    def solve_fields():
+        """what Solver::solve's own flow takes, with or without a depth track or a ladder: amplicons, targets, a report"""
+        if (bed or tsv) and not (per_reference and amplicons_by_reference):
+            raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
+        if report and not per_reference:
+            raise ValueError("a depth report needs per_reference=True")
+        if targets and not per_reference:
+            raise ValueError("targets need per_reference=True")
+        return dict(bed=bed or None, tsv=tsv or None, amplicon_mode=None if amplicon_mode is None else int(amplicon_mode),
+                    amplicons_by_reference=bool(amplicons_by_reference), targets=targets or None,
+                    target_padding=int(target_padding), keep_off_target=bool(keep_off_target), report=report or None,
+                    report_bins=int(report_bins))
+
+    # the request, by field name; what a mode does not name stays "not given"
+    fields = dict(solver_name=solver_name, in_path=in_path, out_path=out_path, filtered_path=filtered_path or None,
+                  max_coverage=int(max_coverage), min_len=int(min_length), min_mapq=int(min_mapq),
+                  per_reference=bool(per_reference))
+    n_files = None  # a ladder and replicates write several files and return a list
     if (replicates_out is not None or replicates_report is not None) and replicates is None:
         raise ValueError("replicates_out and replicates_report need replicates")
     if replicates is not None:
@@ -2326,132 +2341,47 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                 raise ValueError(f"replicates: at most {REPLICATES_MAX} replicates in one call")
         if any(not 1 <= c < 1 << 31 for c in further + [int(max_coverage)]):
             raise ValueError("replicates: every coverage must lie in 1 .. 2^31 - 1")
-        if not per_reference:
-            raise ValueError("disjoint replicates need per_reference=True")
+        need_per_reference(_REPLICATES)
         if further and (replicates_out is None or "{R}" not in str(replicates_out)):
             raise ValueError("replicates_out must be a path template holding {R}")
-        for given, what in ((budget_reads is not None or budget_fraction is not None, "a budget"), (ceiling, "ceiling"),
-                            (pair_aware, "pair_aware"), (template_aware, "template_aware"), (targets, "targets"),
-                            (report, "a depth report"), (track is not None, "a depth track"),
-                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
-                            (dedup, "dedup"), (profile is not None, "a coverage profile")):
-            if given:
-                raise ValueError(f"disjoint replicates do not go together with {what}")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("disjoint replicates do not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("disjoint replicates do not take a solver that grades by quality")
-        err = C.create_string_buffer(1024)
-        rs = ReplicatesStats()
-        fur = np.array(further, dtype=np.uint32)
-        counts = (C.c_int64 * (len(further) + 1))()
-        n = _host.qmcp_host_downsample_bam_replicates(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq), 1,
-            _p32(fur) if fur.size else None, fur.size, str(replicates_out).encode() if replicates_out else None,
-            None, None, None, None, 0, None, 0, 0, 0, 0, None, None, 0,
-            str(replicates_report).encode() if replicates_report else None, counts, C.byref(rs), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return [int(c) for c in counts[:n]]
-    if budget_report is not None and (budget_reads is None) == (budget_fraction is None):
+        refuse(_REPLICATES)
+        n_files = len(further) + 1
+        fields.update(has_replicates=1, replicates_further=further or None, replicates_template=replicates_out,
+                      replicates_report=replicates_report)
+    elif budget_report is not None and (budget_reads is None) == (budget_fraction is None):
         raise ValueError("budget_report needs exactly one of budget_reads and budget_fraction")
-    if budget_reads is not None or budget_fraction is not None:
+    elif given["a budget"]:
         if budget_reads is not None and budget_fraction is not None:
             raise ValueError("budget downsampling takes budget_reads or budget_fraction, not both")
         if budget_reads is not None and not 0 <= int(budget_reads) < 1 << 64:
             raise ValueError("budget_reads must fit an unsigned 64-bit count")
         if budget_fraction is not None and not 0.0 <= float(budget_fraction) <= 1.0:
             raise ValueError("budget_fraction must lie in 0 .. 1")
-        if not per_reference:
-            raise ValueError("budget downsampling needs per_reference=True")
-        for given, what in ((ceiling, "ceiling"), (pair_aware, "pair_aware"), (template_aware, "template_aware"),
-                            (targets, "targets"), (report, "a depth report"), (track is not None, "a depth track"),
-                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
-                            (dedup, "dedup"), (profile is not None, "a coverage profile")):
-            if given:
-                raise ValueError(f"budget downsampling does not go together with {what}")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("budget downsampling does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("budget downsampling does not take a solver that grades by quality")
-        err = C.create_string_buffer(1024)
-        bs = BudgetStats()
-        n = _host.qmcp_host_downsample_bam_budget(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq), 1,
-            int(budget_reads is not None), int(budget_reads or 0),
-            float(budget_fraction) if budget_fraction is not None else -1.0, None, None, None, None, 0, None, 0, 0, 0, 0,
-            None, None, 0, str(budget_report).encode() if budget_report else None, C.byref(bs), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if ceiling_report is not None and not ceiling:
+        need_per_reference(_BUDGET)
+        refuse(_BUDGET)
+        fields.update(has_budget_reads=budget_reads is not None, budget_reads=int(budget_reads or 0),
+                      budget_fraction=None if budget_fraction is None else float(budget_fraction),
+                      budget_report=budget_report)
+    elif ceiling_report is not None and not ceiling:
         raise ValueError("ceiling_report needs ceiling=True")
-    if ceiling:
-        if not per_reference:
-            raise ValueError("ceiling downsampling needs per_reference=True")
-        for given, what in ((pair_aware, "pair_aware"), (template_aware, "template_aware"), (targets, "targets"),
-                            (report, "a depth report"), (track is not None, "a depth track"),
-                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
-                            (dedup, "dedup")):
-            if given:
-                raise ValueError(f"ceiling downsampling does not go together with {what}")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("ceiling downsampling does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("ceiling downsampling does not take a solver that grades by quality")
-        offs = r0 = r1 = caps = None
-        n_refs = 0
+    elif ceiling:
+        need_per_reference(_CEILING)
+        refuse(_CEILING)
+        fields.update(ceiling=1, ceiling_report=ceiling_report)
         if profile is not None:
             names = reference_names(in_path)
-            offs, r0, r1, caps = profile_from_bedgraph(profile, names)
-            n_refs = len(names)
-        err = C.create_string_buffer(1024)
-        cs = CeilingStats()
-        n = _host.qmcp_host_downsample_bam_ceiling(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            1, _p32(offs), _p32(r0), _p32(r1), _p32(caps), n_refs, None, None, None, None, 0, None, 0, 0, 0, None, None, 0,
-            str(ceiling_report).encode() if ceiling_report else None, C.byref(cs), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if (template_targets is not None or template_profile is not None) and not (template_aware and per_reference):
+            fields.update(zip(_REGION_FIELDS, profile_from_bedgraph(profile, names)), has_regions=1, n_refs=len(names))
+    elif (template_targets is not None or template_profile is not None) and not (template_aware and per_reference):
         raise ValueError("template_targets and template_profile need template_aware=True and per_reference=True")
-    if template_targets is not None and template_profile is not None:
+    elif template_targets is not None and template_profile is not None:
         raise ValueError("template_targets and template_profile do not go together: give one table")
-    if template_target_padding and template_targets is None:
+    elif template_target_padding and template_targets is None:
         raise ValueError("template_target_padding needs template_targets")
-    if template_aware:
-        if not per_reference:
-            raise ValueError("template-aware downsampling needs per_reference=True")
-        for given, what in ((pair_aware, "pair_aware"), (targets, "targets"), (report, "a depth report"),
-                            (track is not None, "a depth track"), (ladder is not None, "a coverage ladder"),
-                            (stratify is not None, "stratify"), (dedup, "dedup"), (profile is not None, "a coverage profile")):
-            if given:
-                raise ValueError(f"template-aware downsampling does not go together with {what}")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("template-aware downsampling does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("template-aware downsampling does not take a solver that grades by quality")
-        tg = None if template_stages is None else np.array([int(t) for t in template_stages], dtype=np.uint32)
-        if tg is not None and tg.size == 0:
-            raise ValueError("template_stages must hold at least one target (or be None for the default schedule)")
-        err = C.create_string_buffer(1024)
-        ts, qs = TemplateStats(), None
+    elif template_aware:
+        need_per_reference(_TEMPLATES)
+        refuse(_TEMPLATES)
+        fields.update(template_aware=1, split_spliced=bool(split_spliced), include_secondary=bool(include_secondary),
+                      template_stages=stages_of(template_stages, "template_stages"))
         if template_targets is not None or template_profile is not None:
             if int(template_target_padding) < 0:
                 raise ValueError("template_target_padding must not be negative")
@@ -2459,252 +2389,70 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
             if template_targets is not None:
                 table = targets_as_regions(*targets_from_bed(template_targets, names), ref_lengths,
                                            int(template_target_padding), int(max_coverage))
-                default_cap = 0
             else:
                 table = profile_from_bedgraph(template_profile, names)
-                default_cap = int(max_coverage)
-            qs = TemplateProfileStats()
-            n = _host.qmcp_host_downsample_bam_templates_profile(
-                solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-                str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length),
-                int(min_mapq), 1, int(bool(split_spliced)), int(bool(include_secondary)), _p32(tg),
-                0 if tg is None else tg.size, _p32(table[0]), _p32(table[1]), _p32(table[2]), _p32(table[3]), len(names),
-                default_cap, C.byref(ts), C.byref(qs), err, 1024)
-        else:
-            n = _host.qmcp_host_downsample_bam_templates(
-                solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-                str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-                1, int(bool(split_spliced)), int(bool(include_secondary)), _p32(tg), 0 if tg is None else tg.size, 0, None,
-                None, None, None, 0, None, 0, 0, None, None, 0, C.byref(ts), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        if template_report is not None:
-            write_template_report(template_report, ts, int(n), qs)
-        return int(n)
-    if template_stages is not None or template_report is not None or not split_spliced or include_secondary:
+            fields.update(zip(_REGION_FIELDS, table), has_regions=1, n_refs=len(names),
+                          default_cap=0 if template_targets is not None else int(max_coverage))
+    elif template_stages is not None or template_report is not None or not split_spliced or include_secondary:
         raise ValueError("template_stages, template_report, split_spliced and include_secondary need template_aware=True")
-    if pair_aware:
-        if not per_reference:
-            raise ValueError("pair-aware downsampling needs per_reference=True")
-        for given, what in ((targets, "targets"), (report, "a depth report"), (track is not None, "a depth track"),
-                            (ladder is not None, "a coverage ladder"), (stratify is not None, "stratify"),
-                            (dedup, "dedup"), (profile is not None, "a coverage profile")):
-            if given:
-                raise ValueError(f"pair-aware downsampling does not go together with {what}")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("pair-aware downsampling does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("pair-aware downsampling does not take a solver that grades by quality")
-        tg = None if pair_stages is None else np.array([int(t) for t in pair_stages], dtype=np.uint32)
-        if tg is not None and tg.size == 0:
-            raise ValueError("pair_stages must hold at least one target (or be None for the default schedule)")
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_pairs(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            1, _p32(tg), 0 if tg is None else tg.size, None, None, None, None, 0, None, 0, 0, None, None, 0, err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if pair_stages is not None:
+    elif pair_aware:
+        need_per_reference(_PAIRS)
+        refuse(_PAIRS)
+        fields.update(pair_aware=1, pair_stages=stages_of(pair_stages, "pair_stages"))
+    elif pair_stages is not None:
         raise ValueError("pair_stages need pair_aware=True")
-    if track is not None:
-        if not per_reference:
-            raise ValueError("a depth track needs per_reference=True")
+    elif track is not None:
+        need_per_reference(_TRACK)
         if track_channel not in ("kept", "in", "both"):
             raise ValueError(f'track_channel must be "kept", "in" or "both", not {track_channel!r}')
-        if ladder is not None or stratify is not None or dedup or profile is not None:
-            raise ValueError("a depth track does not go together with a coverage ladder, stratify, dedup or a coverage "
-                             "profile")
-        if (bed or tsv) and not amplicons_by_reference:
-            raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_track(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
-            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)),
-            str(targets).encode() if targets else None, int(target_padding), int(bool(keep_off_target)),
-            str(report).encode() if report else None, int(report_bins), str(track).encode(), track_channel.encode(),
-            int(track_cap), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n}): {err.value.decode()}")
-        return int(n)
-    if profile is not None:
-        if not per_reference:
-            raise ValueError("a coverage profile needs per_reference=True")
-        if targets or report or ladder is not None or stratify is not None or dedup:
-            raise ValueError("a coverage profile does not go together with targets, a depth report, a coverage ladder, "
-                             "stratify or dedup")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("a coverage profile does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("a coverage profile does not take a solver that grades by quality")
+        refuse(_TRACK)
+        fields.update(solve_fields(), track=track, track_channel=track_channel, track_cap=int(track_cap))
+    elif profile is not None:
+        need_per_reference(_PROFILE)
+        refuse(_PROFILE)
         names = reference_names(in_path)
-        offs, r0, r1, caps = profile_from_bedgraph(profile, names)
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_profile(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            1, _p32(offs), _p32(r0), _p32(r1), _p32(caps), len(names), None, None, 0, None, 0, None, None, 0, err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if dedup:
-        if not per_reference:
-            raise ValueError("duplicate-aware downsampling needs per_reference=True")
-        if targets or report or ladder is not None or stratify is not None:
-            raise ValueError("duplicate-aware downsampling does not go together with targets, a depth report, a "
-                             "coverage ladder or stratify")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("duplicate-aware downsampling does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("duplicate-aware downsampling does not take a solver that grades by quality")
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_dedup(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            1, None, None, None, 0, None, None, None, 0, str(dedup_report).encode() if dedup_report else None, err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if dedup_report is not None:
+        fields.update(zip(_REGION_FIELDS, profile_from_bedgraph(profile, names)), has_regions=1, n_refs=len(names))
+    elif dedup:
+        need_per_reference(_DEDUP)
+        refuse(_DEDUP)
+        fields.update(dedup=1, dedup_report=dedup_report)
+    elif dedup_report is not None:
         raise ValueError("dedup_report needs dedup")
-    if stratify is not None:
+    elif stratify is not None:
         if stratify not in ("strand", "read_group"):
             raise ValueError(f'stratify must be "strand" or "read_group", not {stratify!r}')
-        if not per_reference:
-            raise ValueError("stratified downsampling needs per_reference=True")
-        if targets or report or ladder is not None:
-            raise ValueError("stratified downsampling does not go together with targets, a depth report or a coverage "
-                             "ladder")
-        if bed or tsv or amplicons_by_reference:
-            raise ValueError("stratified downsampling does not take amplicon files")
-        if solver_uses_quality(solver_name):
-            raise ValueError("stratified downsampling does not take a solver that grades by quality")
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_stratified(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            1, stratify.encode(), None, None, None, 0, str(strata_report).encode() if strata_report else None, err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if strata_report is not None:
+        need_per_reference(_STRATIFIED)
+        refuse(_STRATIFIED)
+        fields.update(stratify=stratify, strata_report=strata_report)
+    elif strata_report is not None:
         raise ValueError("strata_report needs stratify")
-    if ladder is not None:
+    elif ladder is not None:
         levels = [int(m) for m in ladder]
-        if not per_reference:
-            raise ValueError("a coverage ladder needs per_reference=True")
+        need_per_reference(_LADDER)
         if ladder_out is None or "{M}" not in str(ladder_out):
             raise ValueError("ladder_out must be a path template holding {M}")
-        if targets or report:
-            raise ValueError("a coverage ladder does not go together with targets or a depth report")
-        if solver_uses_quality(solver_name):
-            raise ValueError("a coverage ladder does not take a solver that grades by quality")
+        refuse(_LADDER)
         if not levels or levels[0] >= int(max_coverage):
             raise ValueError("the levels of a coverage ladder must be strictly below max_coverage")
         if any(b >= a for a, b in zip(levels, levels[1:])) or levels[-1] < 1:
             raise ValueError("the levels of a coverage ladder must be strictly decreasing and >= 1")
-        if (bed or tsv) and not amplicons_by_reference:
-            raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
-        lv = np.array(levels, dtype=np.uint32)
-        counts = (C.c_int64 * (len(levels) + 1))()
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_ladder(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
-            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)), _p32(lv), lv.size,
-            str(ladder_out).encode(), counts, err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return [int(c) for c in counts[:n]]
-    if (bed or tsv) and not (per_reference and amplicons_by_reference):
-        raise ValueError("amplicon files (bed / tsv) need per_reference=True and amplicons_by_reference=True")
-    if report:
-        if not per_reference:
-            raise ValueError("a depth report needs per_reference=True")
-        if targets and not per_reference:
-            raise ValueError("targets need per_reference=True")
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_report(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
-            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)),
-            str(targets).encode() if targets else None, int(target_padding), int(bool(keep_off_target)),
-            str(report).encode(), int(report_bins), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n}): {err.value.decode()}")
-        return int(n)
-    if targets:
-        if not per_reference:
-            raise ValueError("targets need per_reference=True")
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_targets(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
-            -1 if amplicon_mode is None else int(amplicon_mode), 1, int(bool(amplicons_by_reference)),
-            str(targets).encode(), int(target_padding), int(bool(keep_off_target)), err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    if amplicons_by_reference:
-        err = C.create_string_buffer(1024)
-        n = _host.qmcp_host_downsample_bam_by_reference(
-            solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-            str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq),
-            str(bed).encode() if bed else None, str(tsv).encode() if tsv else None,
-            -1 if amplicon_mode is None else int(amplicon_mode),
-            int(bool(per_reference)), 1, err, 1024)
-        if n == -4:
-            raise ValueError(err.value.decode())
-        if n == -1:
-            raise KeyError(solver_name)
-        if n < 0:
-            raise OSError(f"downsample_bam({in_path}) failed ({n})")
-        return int(n)
-    entry = _host.qmcp_host_downsample_bam_per_reference if per_reference else _host.qmcp_host_downsample_bam
-    n = entry(solver_name.encode(), str(in_path).encode(), str(out_path).encode(),
-              str(filtered_path).encode() if filtered_path else None, int(max_coverage), int(min_length), int(min_mapq))
-    if n < 0:
+        n_files = len(levels) + 1
+        fields.update(solve_fields(), ladder_levels=levels, ladder_template=ladder_out)
+    else:
+        fields.update(solve_fields())
+
+    counts = (C.c_int64 * (n_files or 1))()
+    ts, qs = TemplateStats(), TemplateProfileStats()  # (the other modes' stats are in their reports)
+    err = C.create_string_buffer(1024)
+    n = _host.qmcp_host_downsample_bam(C.byref(_downsample_request(**fields)), counts, len(counts), None, None, None,
+                                       C.byref(ts), C.byref(qs), err, 1024)
+    if n == -4:
+        raise ValueError(err.value.decode())
+    if n == -1:
         raise KeyError(solver_name)
-    return int(n)
+    if n < 0:
+        message = err.value.decode(errors="replace")
+        raise OSError(f"downsample_bam({in_path}) failed ({n})" + (f": {message}" if message else ""))
+    if template_aware and template_report is not None:
+        write_template_report(template_report, ts, int(n), qs if fields.get("has_regions") else None)
+    return int(n) if n_files is None else [int(c) for c in counts[:n]]

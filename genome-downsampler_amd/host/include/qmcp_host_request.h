@@ -1,0 +1,105 @@
+/* The file-to-file downsample request of libqmcp_host.so: one plain struct that names every BamApiConfig knob of the
+ * flow, and the one entry that takes it.  C99; the bridge is private to the package (the ctypes mirror is
+ * DownsampleRequest in genome-downsampler_amd/__init__.py) -- integrations use BamApiConfig and QuasiMcpHipSolver.
+ *
+ * A zeroed request with struct_size, solver_name, in_path, out_path and max_coverage set is the reference's plain flow,
+ * but for three fields whose "not given" is not zero: amplicon_mode (-1), split_spliced (1) and budget_fraction (< 0).
+ * Every pointer may be NULL; a path that is NULL or "" is not given; an array is a pointer and a count. */
+#ifndef QMCP_HOST_REQUEST_H
+#define QMCP_HOST_REQUEST_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "qmcp_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct qmcp_host_downsample_request {
+    uint64_t struct_size; /* sizeof(qmcp_host_downsample_request); a request of another size is refused */
+    const char* solver_name;
+    const char* in_path;
+    const char* out_path;
+    const char* filtered_path; /* the records the ingest filters dropped */
+    /* amplicons (BamApiConfig::bed_filepath, tsv_filepath, amplicon_behaviour, amplicons_by_reference) */
+    const char* bed;
+    const char* tsv;
+    /* on-target downsampling (targets_filepath, target_padding, keep_off_target) */
+    const char* targets;
+    /* depth report and depth track, written after the output (depth_report_*, depth_track_*) */
+    const char* report;
+    const char* track;
+    const char* track_channel; /* "kept" (also NULL), "in" or "both" */
+    /* coverage ladder (coverage_ladder): level j to ladder_template with its "{M}" replaced by the coverage */
+    const uint32_t* ladder_levels;
+    const char* ladder_template;
+    /* stratified downsampling (stratify_by): "strand" or "read_group" */
+    const char* stratify;
+    const char* strata_report;
+    const char* dedup_report;
+    /* a cap per region, CSR per reference of the file: n_refs + 1 offsets.  Alone it is a coverage profile with
+     * max_coverage elsewhere; with ceiling the caps are ceilings; with template_aware it is the cap table of whole
+     * templates, default_cap elsewhere.  has_regions says whether the table is given at all. */
+    const uint32_t* region_offsets;
+    const uint32_t* region_starts;
+    const uint32_t* region_ends;
+    const uint32_t* region_caps;
+    uint64_t n_refs;
+    /* the staged solves (pair_stages, template_stages); no stages: the default schedule */
+    const uint32_t* pair_stages;
+    const uint32_t* template_stages;
+    const char* ceiling_report;
+    /* budget downsampling (budget_reads, budget_fraction): has_budget_reads != 0 and / or budget_fraction >= 0 ask for
+     * it; budget_report alone is refused */
+    const char* budget_report;
+    uint64_t budget_reads;
+    double budget_fraction;
+    /* disjoint replicates (replicates): has_replicates != 0 asks for them, replicate r + 2 at replicates_further[r],
+     * written to replicates_template with its "{R}" replaced */
+    const uint32_t* replicates_further;
+    const char* replicates_template;
+    const char* replicates_report;
+
+    uint32_t max_coverage;
+    uint32_t min_len;
+    uint32_t min_mapq;
+    uint32_t target_padding;
+    uint32_t report_bins;
+    uint32_t track_cap;
+    uint32_t n_ladder_levels;
+    uint32_t default_cap;
+    uint32_t n_pair_stages;
+    uint32_t n_template_stages;
+    uint32_t n_replicates_further;
+    int32_t amplicon_mode; /* 0 IGNORE, 1 FILTER, 2 GRADE, -1: GRADE for a solver that grades by quality, else FILTER */
+    int32_t per_reference;
+    int32_t amplicons_by_reference;
+    int32_t keep_off_target;
+    int32_t dedup;
+    int32_t has_regions;
+    int32_t pair_aware;
+    int32_t template_aware;
+    int32_t split_spliced;
+    int32_t include_secondary;
+    int32_t ceiling;
+    int32_t has_budget_reads;
+    int32_t has_replicates;
+} qmcp_host_downsample_request;
+
+/* BamApi(in_path, the request's BamApiConfig) -> the solve the configuration selects -> the output file(s) -> the
+ * filtered-out file -> the stats -> the reports.  written_out (written_cap entries, may be NULL) receives each output
+ * file's record count, out_path's first; the stats pointers may be NULL and are written only by the mode they belong
+ * to.  Returns the records written -- for a ladder and for replicates the files written --, -1 for an unknown solver,
+ * -3 out of memory, -4 when the request is refused (message in err), -5 when a report or track cannot be written. */
+int64_t qmcp_host_downsample_bam(const qmcp_host_downsample_request* request, int64_t* written_out, uint64_t written_cap,
+                                 qmcp_hip_ceiling_stats* ceiling_stats, qmcp_hip_budget_stats* budget_stats,
+                                 qmcp_hip_replicates_stats* replicates_stats, qmcp_hip_template_stats* template_stats,
+                                 qmcp_hip_template_profile_stats* template_profile_stats, char* err, size_t err_cap);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -13,6 +13,7 @@
 #include "bam-api/amplicon_set.hpp"
 #include "bam-api/bam_api.hpp"
 #include "bam-api/bam_io.hpp"
+#include "qmcp_host_request.h"
 #include "qmcp-solver/quasi_mcp_hip_quality_solver.hpp"
 #include "reads_gen.hpp"
 #include "solver_manager.hpp"
@@ -44,12 +45,425 @@ qmcp::Solver* resolve(const char* name) {
     return nullptr;
 }
 
+// amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE
+bam_api::AmpliconBehaviour amplicon_behaviour(int amplicon_mode) {
+    return amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
+         : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
+}
 // amplicon_mode -1: the solver decides, as App::execute does (src/app.cpp:120-128) -- GRADE for a solver that uses the
 // reads' qualities, FILTER for every other
 bam_api::AmpliconBehaviour amplicon_behaviour(int amplicon_mode, qmcp::Solver& solver) {
-    if (amplicon_mode < 0) amplicon_mode = solver.uses_quality_of_reads() ? 2 : 1;
-    return amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
-         : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
+    return amplicon_behaviour(amplicon_mode >= 0 ? amplicon_mode : solver.uses_quality_of_reads() ? 2 : 1);
+}
+
+void copy_err(const std::string& msg, char* err, std::size_t cap) {
+    if (err && cap) {
+        std::strncpy(err, msg.c_str(), cap - 1);
+        err[cap - 1] = 0;
+    }
+}
+
+// Nothing is thrown through the C boundary: -3 out of memory, -4 with the message in err when BamApi or an entry refuses
+template <class Body>
+std::int64_t guarded(char* err, std::size_t err_cap, Body body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return -3;
+    } catch (const std::invalid_argument& e) {
+        copy_err(e.what(), err, err_cap);
+        return -4;
+    }
+}
+
+// "strand" / "read_group" -> BamApiConfig::stratify_by; anything else is refused
+bam_api::Stratify stratify_from_name(const char* name) {
+    const std::string s = name ? name : "";
+    if (s == "strand") return bam_api::Stratify::STRAND;
+    if (s == "read_group") return bam_api::Stratify::READ_GROUP;
+    throw std::invalid_argument("stratify must be \"strand\" or \"read_group\", not \"" + s + "\"");
+}
+
+// ---- what the qmcp_host_read_bam* entries take and hand out
+bool given(const char* s) { return s && s[0]; }
+
+bam_api::BamApiConfig ingest_config(const char* bed, const char* tsv, int amplicon_mode, std::uint32_t min_len,
+                                    std::uint32_t min_mapq) {
+    bam_api::BamApiConfig cfg;
+    if (given(bed)) cfg.bed_filepath = bed;
+    if (given(tsv)) cfg.tsv_filepath = tsv;
+    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode);
+    cfg.min_seq_length = min_len;
+    cfg.min_mapq = min_mapq;
+    return cfg;
+}
+
+// the ingest's by-products: the filtered-out ids (cap_f entries) and every reference's length (ref_cap entries;
+// ref_lengths NULL: not wanted).  false when a capacity is too small.
+struct IngestOut {
+    std::uint64_t cap_f;
+    std::uint64_t* filtered_out;
+    std::uint64_t* n_filtered_out;
+    std::uint64_t ref_cap;
+    std::uint32_t* ref_lengths;
+    std::uint64_t* n_refs;
+};
+bool copy_out_ingest(const std::vector<bam_api::BAMReadId>& filtered, const std::vector<std::uint32_t>& lengths,
+                     const IngestOut& o) {
+    if (filtered.size() > o.cap_f || (o.ref_lengths && lengths.size() > o.ref_cap)) return false;
+    *o.n_filtered_out = filtered.size();
+    for (std::size_t i = 0; i < filtered.size(); ++i) o.filtered_out[i] = filtered[i];
+    if (o.ref_lengths) {
+        *o.n_refs = lengths.size();
+        for (std::size_t k = 0; k < lengths.size(); ++k) o.ref_lengths[k] = lengths[k];
+    }
+    return true;
+}
+
+// the SoA columns of get_paired_reads_soa() (cap entries each; contig_ids / strata NULL: not wanted -- reads without
+// a contig column get contig 0) and the ingest's by-products.  Returns the number of reads, -2 when a capacity is too small.
+struct ReadsOut {
+    std::uint64_t cap;
+    std::uint64_t* bam_ids;
+    std::uint32_t *starts, *ends, *qualities, *seq_lengths;
+    std::uint8_t* is_first;
+    std::uint32_t *contig_ids, *strata;
+};
+std::int64_t copy_out_reads(bam_api::BamApi& api, const ReadsOut& c, const IngestOut& o) {
+    const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
+    const std::uint64_t n = r.ids.size();
+    if (n > c.cap || !copy_out_ingest(api.get_filtered_out_reads(), r.contig_lengths, o)) return -2;
+    for (std::uint64_t i = 0; i < n; ++i) {
+        c.bam_ids[i] = r.ids[i]; c.starts[i] = (std::uint32_t)r.start_inds[i]; c.ends[i] = (std::uint32_t)r.end_inds[i];
+        c.qualities[i] = r.qualities[i]; c.seq_lengths[i] = r.seq_lengths[i]; c.is_first[i] = r.is_first_reads[i] ? 1 : 0;
+        if (c.contig_ids) c.contig_ids[i] = r.contig_ids.size() == n ? r.contig_ids[i] : 0u;
+        if (c.strata) c.strata[i] = r.strata[i];
+    }
+    return (std::int64_t)n;
+}
+
+// ---- the file-to-file flow behind qmcp_host_downsample_bam
+
+// The request as a BamApiConfig, every knob handed on as given so that BamApiConfig refuses the combinations it
+// refuses.  The only place that knows the request's "not given": NULL or "" for a path, NULL for an array, a negative
+// budget_fraction (a NaN is handed on, to be refused).
+bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Solver& solver) {
+    bam_api::BamApiConfig cfg = ingest_config(q.bed, q.tsv, 0, q.min_len, q.min_mapq);
+    cfg.amplicon_behaviour = amplicon_behaviour(q.amplicon_mode, solver);
+    cfg.per_reference = q.per_reference != 0;
+    cfg.amplicons_by_reference = q.amplicons_by_reference != 0;
+    if (given(q.targets)) cfg.targets_filepath = q.targets;
+    cfg.target_padding = q.target_padding;
+    cfg.keep_off_target = q.keep_off_target != 0;
+    if (given(q.report)) cfg.depth_report_filepath = q.report;
+    cfg.depth_report_bins = q.report_bins;
+    if (given(q.track)) cfg.depth_track_filepath = q.track;
+    if (given(q.track_channel)) cfg.depth_track_channel = q.track_channel;
+    cfg.depth_track_cap = q.track_cap;
+    if (q.ladder_levels) cfg.coverage_ladder.assign(q.ladder_levels, q.ladder_levels + q.n_ladder_levels);
+    if (given(q.stratify)) cfg.stratify_by = stratify_from_name(q.stratify);
+    cfg.dedup = q.dedup != 0;
+    cfg.pair_aware = q.pair_aware != 0;
+    if (q.pair_stages) cfg.pair_stages.assign(q.pair_stages, q.pair_stages + q.n_pair_stages);
+    cfg.template_aware = q.template_aware != 0;
+    cfg.split_spliced = q.split_spliced != 0;
+    cfg.include_secondary = q.include_secondary != 0;
+    if (q.template_stages) cfg.template_stages.assign(q.template_stages, q.template_stages + q.n_template_stages);
+    cfg.ceiling = q.ceiling != 0;
+    if (q.has_budget_reads) cfg.budget_reads = q.budget_reads;
+    if (q.budget_fraction >= 0.0 || q.budget_fraction != q.budget_fraction) cfg.budget_fraction = q.budget_fraction;
+    if (q.has_replicates) {
+        cfg.replicates = std::vector<std::uint32_t>();
+        if (q.replicates_further) cfg.replicates->assign(q.replicates_further, q.replicates_further + q.n_replicates_further);
+    }
+    return cfg;
+}
+
+// Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
+// amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
+enum class Mode { REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (cfg.replicates) return Mode::REPLICATES;
+    if (cfg.budget_reads || cfg.budget_fraction || given(q.budget_report)) return Mode::BUDGET;
+    if (cfg.ceiling) return Mode::CEILING;
+    if (cfg.template_aware) return Mode::TEMPLATES;
+    if (cfg.pair_aware) return Mode::PAIRS;
+    if (q.has_regions) return Mode::PROFILE;
+    if (cfg.dedup) return Mode::DEDUP;
+    if (cfg.stratify_by != bam_api::Stratify::NONE) return Mode::STRATIFIED;
+    if (!cfg.coverage_ladder.empty() || given(q.ladder_template)) return Mode::LADDER;
+    return Mode::PLAIN;
+}
+
+// a mode's words in the refusals: "<refuses> take ..." / "<refuses> go together with ...", "this solver has no <noun>"
+struct ModeWords {
+    std::string refuses, noun;
+};
+ModeWords words_of(Mode mode) {
+    switch (mode) {
+        case Mode::REPLICATES: return {"disjoint replicates do not", "disjoint replicates"};
+        case Mode::BUDGET: return {"budget downsampling does not", "budget downsampling"};
+        case Mode::CEILING: return {"ceiling downsampling does not", "ceiling downsampling"};
+        case Mode::TEMPLATES: return {"template-aware downsampling does not", "template-aware downsampling"};
+        case Mode::PAIRS: return {"pair-aware downsampling does not", "pair-aware downsampling"};
+        case Mode::PROFILE: return {"a coverage profile does not", "coverage profile"};
+        case Mode::DEDUP: return {"duplicate-aware downsampling does not", "duplicate-aware downsampling"};
+        case Mode::STRATIFIED: return {"stratified downsampling does not", "stratified downsampling"};
+        case Mode::LADDER: return {"a coverage ladder does not", "coverage ladder"};
+        case Mode::PLAIN: break;
+    }
+    return {};
+}
+
+// What an entry refuses from the request alone, before the ingest (BamApiConfig's own rules follow in BamApi's
+// constructor).  hip: the solver as the hip solver, NULL for another.
+void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg, Mode mode,
+                          qmcp::Solver& solver, const qmcp::QuasiMcpHipSolver* hip, std::uint64_t written_cap) {
+    const auto refuse = [](const std::string& why) { throw std::invalid_argument(why); };
+    const ModeWords words = words_of(mode);
+    if (q.in_path == nullptr || q.out_path == nullptr) refuse("a request needs in_path and out_path");
+    const std::string ladder_template = q.ladder_template ? q.ladder_template : "";
+    const std::string replicates_template = q.replicates_template ? q.replicates_template : "";
+    if (mode == Mode::BUDGET && !cfg.budget_reads && !cfg.budget_fraction)
+        refuse("budget downsampling needs budget_reads or budget_fraction");
+    if (mode == Mode::LADDER && cfg.coverage_ladder.empty()) refuse("a coverage ladder needs at least one level");
+    if (mode == Mode::LADDER && ladder_template.find("{M}") == std::string::npos)
+        refuse("the ladder's output template has no {M}");
+    if (mode == Mode::REPLICATES && !cfg.replicates->empty() && replicates_template.find("{R}") == std::string::npos)
+        refuse("the replicates' output template has no {R}");
+    if (mode == Mode::PROFILE) {  // (BamApiConfig knows no coverage profile, so its rules stand here)
+        if (!cfg.per_reference) refuse("a coverage profile needs per_reference");
+        if (!cfg.targets_filepath.empty()) refuse("a coverage profile does not go together with targets");
+        if (!cfg.depth_report_filepath.empty()) refuse("a coverage profile does not go together with a depth report");
+        if (!cfg.coverage_ladder.empty()) refuse("a coverage profile does not go together with a coverage ladder");
+        if (cfg.stratify_by != bam_api::Stratify::NONE) refuse("a coverage profile does not go together with stratify_by");
+        if (cfg.dedup) refuse("a coverage profile does not go together with dedup");
+        if (!cfg.depth_track_filepath.empty()) refuse("a coverage profile does not go together with a depth track");
+        if (!cfg.bed_filepath.empty() || !cfg.tsv_filepath.empty() || cfg.amplicons_by_reference)
+            refuse("a coverage profile does not take amplicon files");
+    }
+    if (q.has_regions && (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES))
+        refuse(words.refuses + " go together with a coverage profile");
+    if (mode != Mode::PLAIN && solver.uses_quality_of_reads()) refuse(words.refuses + " take a solver that grades by quality");
+    if (mode != Mode::PLAIN && hip == nullptr) refuse("this solver has no " + words.noun);
+    if (hip == nullptr && !cfg.depth_report_filepath.empty()) refuse("this solver has no depth report");
+    if (hip == nullptr && !cfg.depth_track_filepath.empty()) refuse("this solver has no depth track");
+    if (q.has_regions) {
+        const std::string table = mode == Mode::TEMPLATES ? "a cap table" : "a coverage profile";
+        if (q.region_offsets == nullptr) refuse(table + " needs its region offsets");
+        if (q.region_offsets[q.n_refs] && (!q.region_starts || !q.region_ends || !q.region_caps))
+            refuse(table + " with regions needs their starts, ends and caps");
+    }
+    const std::size_t files = mode == Mode::LADDER       ? 1 + cfg.coverage_ladder.size()
+                              : mode == Mode::REPLICATES ? 1 + cfg.replicates->size() : 1;
+    if (files > 1 && written_cap < files) refuse("written_out is too short for this request's output files");
+}
+
+// ---- the reports, each written after the output; false when the file cannot be written
+// one line per stratum: name, cap, reads, kept, mean depth before and after (bases / the sum of the reference lengths)
+// of the solve's own kept set (before mate completion)
+bool write_strata_report(const char* path, const bam_api::SOAPairedReads& r, const qmcp::QuasiMcpHipSolver& hip) {
+    double positions = 0;
+    for (std::uint32_t l : r.contig_lengths) positions += l;
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stratum\tcap\treads\tkept\tmean_depth_in\tmean_depth_kept\n");
+    for (std::size_t s = 0; s < r.stratum_names.size(); ++s) {
+        const qmcp_hip_stratum_row& row = hip.last_stratum_rows()[s];
+        std::fprintf(f, "%s\t%u\t%llu\t%llu\t%.6f\t%.6f\n", r.stratum_names[s].c_str(), hip.last_stratum_caps()[s],
+                     (unsigned long long)row.n_reads, (unsigned long long)row.n_kept,
+                     positions > 0 ? (double)row.bases_in / positions : 0.0,
+                     positions > 0 ? (double)row.bases_kept / positions : 0.0);
+    }
+    return std::fclose(f) == 0;
+}
+
+// the statistics, then one size<TAB>families line per bin of the family-size histogram
+constexpr std::uint32_t kDedupBins = 64;
+bool write_dedup_report(const char* path, const qmcp::QuasiMcpHipSolver& hip) {
+    const qmcp_hip_dedup_stats& ds = hip.last_dedup_stats();
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "units\t%llu\nfamilies\t%llu\nduplicate_units\t%llu\nlargest_family\t%llu\nreads_survived\t%llu\n",
+                 (unsigned long long)ds.units, (unsigned long long)ds.families, (unsigned long long)ds.duplicate_units,
+                 (unsigned long long)ds.largest_family, (unsigned long long)ds.reads_survived);
+    std::fprintf(f, "#size\tfamilies\n");
+    for (std::uint32_t b = 0; b < kDedupBins; ++b)
+        std::fprintf(f, "%u\t%llu\n", b + 1, (unsigned long long)hip.last_dedup_hist()[b]);
+    return std::fclose(f) == 0;
+}
+
+// stat<TAB>value: the qmcp_hip_ceiling_stats and the records written
+bool write_ceiling_report(const char* path, const qmcp_hip_ceiling_stats& cs, std::int64_t written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "reads_placed\t%llu\nreads_dropped\t%llu\nmates_dropped\t%llu\nover_positions\t%llu\n"
+                    "over_bases\t%llu\nshort_positions\t%llu\nshort_bases\t%llu\nexcess_positions\t%llu\n",
+                 (unsigned long long)cs.reads_placed, (unsigned long long)cs.reads_dropped,
+                 (unsigned long long)cs.mates_dropped, (unsigned long long)cs.over_positions,
+                 (unsigned long long)cs.over_bases, (unsigned long long)cs.short_positions,
+                 (unsigned long long)cs.short_bases, (unsigned long long)cs.excess_positions);
+    std::fprintf(f, "max_kept_depth\t%u\nregions_in\t%u\nregions_used\t%u\nrecords_written\t%u\n", cs.max_kept_depth,
+                 cs.regions_in, cs.regions_used, (unsigned)written);
+    return std::fclose(f) == 0;
+}
+
+// stat<TAB>value: the qmcp_hip_budget_stats and the records written, then one M<TAB>bases line per entry of the curve
+bool write_budget_report(const char* path, const qmcp_hip_budget_stats& bs, const std::vector<std::uint64_t>& curve,
+                         std::int64_t written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "budget\t%llu\nreads_placed\t%llu\nn_kept\t%llu\nkept_above\t%llu\nbound_above\t%llu\n"
+                    "total_bases\t%llu\n",
+                 (unsigned long long)bs.budget, (unsigned long long)bs.reads_placed, (unsigned long long)bs.n_kept,
+                 (unsigned long long)bs.kept_above, (unsigned long long)bs.bound_above, (unsigned long long)bs.total_bases);
+    std::fprintf(f, "coverage\t%u\nmax_depth\t%u\ntop\t%u\nprobes\t%u\ncurve_entries\t%u\nsaturated\t%u\n"
+                    "ms_budget\t%.6g\nms_solves\t%.6g\nrecords_written\t%u\n",
+                 bs.coverage, bs.max_depth, bs.top, bs.probes, bs.curve_entries, bs.saturated, (double)bs.ms_budget,
+                 (double)bs.ms_solves, (unsigned)written);
+    std::fprintf(f, "#M\tbases\n");
+    for (std::size_t m = 0; m < curve.size(); ++m) std::fprintf(f, "%zu\t%llu\n", m, (unsigned long long)curve[m]);
+    return std::fclose(f) == 0;
+}
+
+// one line per replicate -- coverage, offered, kept, mates, short_positions, short_bases, records_written -- and n_full
+bool write_replicates_report(const char* path, const qmcp_hip_replicates_stats& rs, std::uint32_t max_coverage,
+                             const std::vector<std::uint32_t>& further, const std::vector<std::int64_t>& written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#replicate\tcoverage\toffered\tkept\tmates\tshort_positions\tshort_bases\trecords_written\n");
+    for (std::size_t r = 0; r < written.size(); ++r)
+        std::fprintf(f, "%zu\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%u\n", r + 1, r == 0 ? max_coverage : further[r - 1],
+                     (unsigned long long)rs.n_offered[r], (unsigned long long)rs.n_kept[r], (unsigned long long)rs.n_mates[r],
+                     (unsigned long long)rs.short_positions[r], (unsigned long long)rs.short_bases[r], (unsigned)written[r]);
+    std::fprintf(f, "n_full\t%u\n", rs.n_full);
+    return std::fclose(f) == 0;
+}
+
+// The depth report and the depth track of BamApiConfig: the reads the solve saw against the final kept set (after
+// find_pairs), with M = max_coverage and the call's targets and padding -- the report as TSV, the track as bedGraph with
+// both depths compared and zero positions kept.  false with the reason in *why.
+bool write_depth_report(qmcp::QuasiMcpHipSolver& hip, std::uint32_t max_coverage, bam_api::BamApi& api,
+                        const std::vector<bam_api::ReadIndex>& kept, const std::vector<std::string>& names, std::string* why) {
+    qmcp::DepthReport report;
+    hip.depth_report(max_coverage, api, kept, api.depth_report_bins(), report);
+    if (qmcp::write_depth_report_tsv(api.depth_report_filepath(), report, names)) return true;
+    *why = "could not write " + api.depth_report_filepath().string();
+    return false;
+}
+bool write_depth_track(qmcp::QuasiMcpHipSolver& hip, std::uint32_t max_coverage, bam_api::BamApi& api,
+                       const std::vector<bam_api::ReadIndex>& kept, const std::vector<std::string>& names, std::string* why) {
+    qmcp::DepthTrack track;
+    hip.depth_track(max_coverage, api, kept, QMCP_TRACK_IN | QMCP_TRACK_KEPT, api.depth_track_cap(), track);
+    if (qmcp::write_depth_track_bedgraph(api.depth_track_filepath(), track, names, api.depth_track_channel())) return true;
+    *why = "could not write " + api.depth_track_filepath().string();
+    return false;
+}
+
+// Everything qmcp_host_downsample_bam does (include/qmcp_host_request.h) but the exception mapping, in the order:
+// solver, configuration, refusals, ingest, solve, output file(s), filtered-out file, stats, reports.
+std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* written_out, std::uint64_t written_cap,
+                        qmcp_hip_ceiling_stats* ceiling_stats, qmcp_hip_budget_stats* budget_stats,
+                        qmcp_hip_replicates_stats* replicates_stats, qmcp_hip_template_stats* template_stats,
+                        qmcp_hip_template_profile_stats* template_profile_stats, char* err, std::size_t err_cap) {
+    if (q.struct_size != sizeof(q)) throw std::invalid_argument("the request has another struct_size than this library's");
+    qmcp::Solver* solver = q.solver_name ? resolve(q.solver_name) : nullptr;
+    if (solver == nullptr) return -1;
+    bam_api::BamApiConfig cfg = config_of(q, *solver);
+    const Mode mode = mode_of(q, cfg);
+    auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(solver);
+    refuse_before_ingest(q, cfg, mode, *solver, hip, written_out ? written_cap : UINT64_MAX);
+    const std::uint32_t M = q.max_coverage;
+    std::vector<std::uint32_t> offsets, starts, ends, caps;  // the region table; all empty: none
+    if (q.has_regions) {
+        const std::uint32_t n_regions = q.region_offsets[q.n_refs];
+        offsets.assign(q.region_offsets, q.region_offsets + q.n_refs + 1);
+        starts.assign(q.region_starts, q.region_starts + n_regions);
+        ends.assign(q.region_ends, q.region_ends + n_regions);
+        caps.assign(q.region_caps, q.region_caps + n_regions);
+    }
+
+    bam_api::BamApi api(q.in_path, cfg);
+
+    // solve, and write every kept set: `written` gets one record count per output file, out_path's first.  Pairs are
+    // completed by find_pairs where the solve does not leave whole pairs itself -- and never where that would put
+    // depth or reads back (ceiling, budget) or copy a record into two files (replicates).
+    std::vector<std::int64_t> written;
+    std::vector<bam_api::ReadIndex> kept;  // the last kept set as written (the depth report and track describe it)
+    const auto write_reads = [&](const qmcp::Solution& solution, bool complete_pairs, const std::string& path) {
+        kept = complete_pairs ? api.find_pairs(solution) : solution;
+        written.push_back(api.write_paired_reads(path, kept));
+    };
+    const auto path_from = [](const char* path_template, const char* token, std::uint64_t value) {
+        std::string path = path_template;
+        return path.replace(path.find(token), 3, std::to_string(value));
+    };
+    switch (mode) {
+        case Mode::PLAIN:
+        case Mode::STRATIFIED: write_reads(*solver->solve(M, api), true, q.out_path); break;
+        case Mode::DEDUP: write_reads(*hip->solve_dedup(M, api, kDedupBins), true, q.out_path); break;
+        case Mode::PROFILE: write_reads(*hip->solve_profile(M, api, offsets, starts, ends, caps), true, q.out_path); break;
+        case Mode::PAIRS: write_reads(*hip->solve_pairs(M, api), false, q.out_path); break;
+        case Mode::CEILING: write_reads(*hip->solve_ceiling(M, api, offsets, starts, ends, caps), false, q.out_path); break;
+        case Mode::BUDGET: write_reads(*hip->solve_budget(M, api), false, q.out_path); break;
+        case Mode::LADDER: {
+            const auto levels = hip->solve_ladder(M, api, api.coverage_ladder());
+            for (std::size_t j = 0; j < levels.size(); ++j)
+                write_reads(*levels[j], true, j == 0 ? q.out_path : path_from(q.ladder_template, "{M}", api.coverage_ladder()[j - 1]));
+            break;
+        }
+        case Mode::REPLICATES: {
+            const std::vector<std::uint8_t> labels = hip->solve_replicates(M, api);
+            for (std::size_t r = 1; r <= api.replicates()->size() + 1; ++r) {
+                qmcp::Solution labelled;
+                for (std::size_t i = 0; i < labels.size(); ++i)
+                    if (labels[i] == r) labelled.push_back(i);
+                write_reads(labelled, false, r == 1 ? q.out_path : path_from(q.replicates_template, "{R}", r));
+            }
+            break;
+        }
+        case Mode::TEMPLATES: {  // whole templates: the kept RECORDS, written as they are
+            std::vector<bam_api::BAMReadId> records = q.has_regions
+                ? hip->solve_templates_profile(M, api, offsets, starts, ends, caps, q.default_cap)
+                : hip->solve_templates(M, api);
+            written.push_back(api.write_records(q.out_path, records));
+            break;
+        }
+    }
+    if (given(q.filtered_path)) api.write_bam_api_filtered_out_reads(q.filtered_path);
+
+    for (std::size_t j = 0; written_out && j < written.size() && j < written_cap; ++j) written_out[j] = written[j];
+    if (mode == Mode::CEILING && ceiling_stats) *ceiling_stats = hip->last_ceiling_stats();
+    if (mode == Mode::BUDGET && budget_stats) *budget_stats = hip->last_budget_stats();
+    if (mode == Mode::REPLICATES && replicates_stats) *replicates_stats = hip->last_replicates_stats();
+    if (mode == Mode::TEMPLATES && template_stats) *template_stats = hip->last_template_stats();
+    if (mode == Mode::TEMPLATES && q.has_regions && template_profile_stats)
+        *template_profile_stats = hip->last_template_profile_stats();
+
+    bool reported = true;
+    if (mode == Mode::STRATIFIED && given(q.strata_report))
+        reported = write_strata_report(q.strata_report, api.get_paired_reads_soa(), *hip);
+    if (mode == Mode::DEDUP && given(q.dedup_report)) reported = write_dedup_report(q.dedup_report, *hip);
+    if (mode == Mode::CEILING && given(q.ceiling_report))
+        reported = write_ceiling_report(q.ceiling_report, hip->last_ceiling_stats(), written[0]);
+    if (mode == Mode::BUDGET && given(q.budget_report))
+        reported = write_budget_report(q.budget_report, hip->last_budget_stats(), hip->last_budget_curve(), written[0]);
+    if (mode == Mode::REPLICATES && given(q.replicates_report))
+        reported = write_replicates_report(q.replicates_report, hip->last_replicates_stats(), M, *api.replicates(), written);
+    if (!api.depth_report_filepath().empty() || !api.depth_track_filepath().empty()) {
+        std::vector<std::string> names;
+        std::vector<std::uint32_t> lengths;
+        std::string why;
+        reported = bam_api::read_bam_references(q.in_path, names, lengths, &why);
+        if (reported && !api.depth_report_filepath().empty()) reported = write_depth_report(*hip, M, api, kept, names, &why);
+        if (reported && !api.depth_track_filepath().empty()) reported = write_depth_track(*hip, M, api, kept, names, &why);
+        if (!reported) copy_err(why, err, err_cap);
+    }
+    if (!reported) return -5;
+    return mode == Mode::LADDER || mode == Mode::REPLICATES ? (std::int64_t)written.size() : written[0];
 }
 
 }  // namespace
@@ -243,41 +657,49 @@ int qmcp_host_write_synthetic_bam(const char* path, std::uint32_t ref_length, st
 
 // BamApi(path, config) -> get_paired_reads_soa(): columns out (capacity cap reads); returns the number of
 // imported reads, *n_filtered_out = size of get_filtered_out_reads() (ids into filtered_out, capacity cap_f),
-// *ref_len = ref_genome_length.  amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE (bed/tsv may be NULL or "").
+// *ref_len = ref_genome_length.  amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE (bed/tsv may be NULL or "").  -2 when a
+// capacity is too small, -3 out of memory, -4 when BamApi refuses the configuration.
 std::int64_t qmcp_host_read_bam(const char* path, const char* bed, const char* tsv, int amplicon_mode,
                                 std::uint32_t min_len, std::uint32_t min_mapq, std::uint64_t cap,
                                 std::uint64_t* bam_ids, std::uint32_t* starts, std::uint32_t* ends,
                                 std::uint32_t* qualities, std::uint32_t* seq_lengths, std::uint8_t* is_first,
                                 std::uint64_t cap_f, std::uint64_t* filtered_out, std::uint64_t* n_filtered_out,
                                 std::uint32_t* ref_len) {
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
-                           : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
-    try {
-        bam_api::BamApi api(path, cfg);
-        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
-        const std::uint64_t n = r.ids.size();
-        if (n > cap || api.get_filtered_out_reads().size() > cap_f) return -2;
-        for (std::uint64_t i = 0; i < n; ++i) {
-            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
-            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
-        }
-        *n_filtered_out = api.get_filtered_out_reads().size();
-        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
-        *ref_len = (std::uint32_t)r.ref_genome_length;
-        return (std::int64_t)n;
-    } catch (const std::bad_alloc&) {
-        return -3;  // (nothing is thrown through the C boundary)
-    }
+    return guarded(nullptr, 0, [&]() -> std::int64_t {
+        bam_api::BamApi api(path, ingest_config(bed, tsv, amplicon_mode, min_len, min_mapq));
+        const std::int64_t n = copy_out_reads(api, {cap, bam_ids, starts, ends, qualities, seq_lengths, is_first, nullptr, nullptr},
+                                              {cap_f, filtered_out, n_filtered_out, 0, nullptr, nullptr});
+        if (n >= 0) *ref_len = (std::uint32_t)api.get_paired_reads_soa().ref_genome_length;
+        return n;
+    });
 }
 
-// qmcp_host_read_bam with BamApiConfig::per_reference: the same columns, plus each read's contig id (contig_ids, cap
-// entries; QMCP_NO_CONTIG for an unmapped read) and every reference's length (ref_lengths, ref_cap entries; *n_refs
-// receives the count).  -2 when a capacity is too small, -3 out of memory, -4 with amplicon files (message in err).
+// qmcp_host_read_bam with amplicon_mode (0 IGNORE, 1 FILTER, 2 GRADE) and the two flags of BamApiConfig (per_reference,
+// amplicons_by_reference): the same columns, plus each read's contig id (contig_ids, cap entries; QMCP_NO_CONTIG for an
+// unmapped read, 0 without per_reference) and every reference's length (ref_lengths, ref_cap entries; *n_refs receives
+// the count).  -2 when a capacity is too small, -3 out of memory, -4 when BamApi refuses the configuration or the
+// amplicon files (message in err).
+std::int64_t qmcp_host_read_bam_by_reference(const char* path, const char* bed, const char* tsv, int amplicon_mode,
+                                             int per_reference, int amplicons_by_reference, std::uint32_t min_len,
+                                             std::uint32_t min_mapq, std::uint64_t cap, std::uint64_t* bam_ids,
+                                             std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* qualities,
+                                             std::uint32_t* seq_lengths, std::uint8_t* is_first,
+                                             std::uint32_t* contig_ids, std::uint64_t cap_f,
+                                             std::uint64_t* filtered_out, std::uint64_t* n_filtered_out,
+                                             std::uint64_t ref_cap, std::uint32_t* ref_lengths, std::uint64_t* n_refs,
+                                             char* err, std::size_t err_cap) {
+    return guarded(err, err_cap, [&]() -> std::int64_t {
+        bam_api::BamApiConfig cfg = ingest_config(bed, tsv, amplicon_mode, min_len, min_mapq);
+        cfg.per_reference = per_reference != 0;
+        cfg.amplicons_by_reference = amplicons_by_reference != 0;
+        bam_api::BamApi api(path, cfg);
+        return copy_out_reads(api, {cap, bam_ids, starts, ends, qualities, seq_lengths, is_first, contig_ids, nullptr},
+                              {cap_f, filtered_out, n_filtered_out, ref_cap, ref_lengths, n_refs});
+    });
+}
+
+// qmcp_host_read_bam_by_reference with its two flags fixed: per_reference on, amplicons_by_reference off (amplicon
+// files are then refused, -4), amplicons ignored
 std::int64_t qmcp_host_read_bam_per_reference(const char* path, const char* bed, const char* tsv,
                                               std::uint32_t min_len, std::uint32_t min_mapq, std::uint64_t cap,
                                               std::uint64_t* bam_ids, std::uint32_t* starts, std::uint32_t* ends,
@@ -286,47 +708,80 @@ std::int64_t qmcp_host_read_bam_per_reference(const char* path, const char* bed,
                                               std::uint64_t* filtered_out, std::uint64_t* n_filtered_out,
                                               std::uint64_t ref_cap, std::uint32_t* ref_lengths, std::uint64_t* n_refs,
                                               char* err, std::size_t err_cap) {
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.per_reference = true;
-    try {
-        bam_api::BamApi api(path, cfg);
-        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
-        const std::uint64_t n = r.ids.size();
-        if (n > cap || api.get_filtered_out_reads().size() > cap_f || r.contig_lengths.size() > ref_cap) return -2;
-        for (std::uint64_t i = 0; i < n; ++i) {
-            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
-            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
-            contig_ids[i] = r.contig_ids[i];
-        }
-        *n_filtered_out = api.get_filtered_out_reads().size();
-        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
-        *n_refs = r.contig_lengths.size();
-        for (std::size_t k = 0; k < r.contig_lengths.size(); ++k) ref_lengths[k] = r.contig_lengths[k];
-        return (std::int64_t)n;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        if (err && err_cap) {
-            std::strncpy(err, e.what(), err_cap - 1);
-            err[err_cap - 1] = 0;
-        }
-        return -4;
-    }
+    return qmcp_host_read_bam_by_reference(path, bed, tsv, /*amplicon_mode=*/0, /*per_reference=*/1,
+                                           /*amplicons_by_reference=*/0, min_len, min_mapq, cap, bam_ids, starts, ends,
+                                           qualities, seq_lengths, is_first, contig_ids, cap_f, filtered_out, n_filtered_out,
+                                           ref_cap, ref_lengths, n_refs, err, err_cap);
 }
 
-// ---- amplicons matched to references by name (BamApiConfig::amplicons_by_reference)
-namespace {
-void copy_err(const std::string& msg, char* err, std::size_t cap) {
-    if (err && cap) {
-        std::strncpy(err, msg.c_str(), cap - 1);
-        err[cap - 1] = 0;
-    }
+// qmcp_host_read_bam_by_reference with BamApiConfig::stratify_by ("strand" / "read_group") in place of amplicons: the
+// same columns, plus each read's stratum (strata, cap entries) and the strata's names, one per line, in names_out
+// (names_cap bytes; *n_strata receives the count).  -2 when a capacity is too small, -3 out of memory, -4 with the
+// message in err.
+std::int64_t qmcp_host_read_bam_stratified(const char* path, const char* stratify, std::uint32_t min_len,
+                                           std::uint32_t min_mapq, std::uint64_t cap, std::uint64_t* bam_ids,
+                                           std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* qualities,
+                                           std::uint32_t* seq_lengths, std::uint8_t* is_first, std::uint32_t* contig_ids,
+                                           std::uint32_t* strata, std::uint64_t cap_f, std::uint64_t* filtered_out,
+                                           std::uint64_t* n_filtered_out, std::uint64_t ref_cap,
+                                           std::uint32_t* ref_lengths, std::uint64_t* n_refs, char* names_out,
+                                           std::size_t names_cap, std::uint64_t* n_strata, int per_reference, char* err,
+                                           std::size_t err_cap) {
+    return guarded(err, err_cap, [&]() -> std::int64_t {
+        bam_api::BamApiConfig cfg = ingest_config(nullptr, nullptr, 0, min_len, min_mapq);
+        cfg.per_reference = per_reference != 0;
+        cfg.stratify_by = stratify_from_name(stratify);
+        bam_api::BamApi api(path, cfg);
+        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
+        std::string names;
+        for (const std::string& s : r.stratum_names) names += s + "\n";
+        if (names.size() + 1 > names_cap) return -2;
+        const std::int64_t n = copy_out_reads(api, {cap, bam_ids, starts, ends, qualities, seq_lengths, is_first, contig_ids, strata},
+                                              {cap_f, filtered_out, n_filtered_out, ref_cap, ref_lengths, n_refs});
+        if (n < 0) return n;
+        std::memcpy(names_out, names.c_str(), names.size() + 1);
+        *n_strata = r.stratum_names.size();
+        return n;
+    });
 }
-}  // namespace
+
+// Template-aware ingest alone (BamApiConfig::template_aware; bam_api::read_bam_templates): the segments' columns (cap
+// entries each; segment_records: each segment's BAM record id), the skipped and dropped records (filtered_out, cap_f
+// entries), every reference's length and the number of templates.  Returns the number of segments; -2 when a capacity is
+// too small, -3 out of memory, -1 with the reader's message in err on a malformed or unreadable file.
+std::int64_t qmcp_host_read_bam_templates(const char* path, std::uint32_t min_len, std::uint32_t min_mapq,
+                                          int split_spliced, int include_secondary, std::uint64_t cap,
+                                          std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* contig_ids,
+                                          std::uint32_t* template_ids, std::uint32_t* qualities,
+                                          std::uint32_t* seq_lengths, std::uint64_t* segment_records, std::uint64_t cap_f,
+                                          std::uint64_t* filtered_out, std::uint64_t* n_filtered_out, std::uint64_t ref_cap,
+                                          std::uint32_t* ref_lengths, std::uint64_t* n_refs, std::uint64_t* n_templates,
+                                          char* err, std::size_t err_cap) {
+    return guarded(err, err_cap, [&]() -> std::int64_t {
+        bam_api::TemplateIngest cfg;
+        cfg.min_seq_length = min_len;
+        cfg.min_mapq = min_mapq;
+        cfg.split_spliced = split_spliced != 0;
+        cfg.include_secondary = include_secondary != 0;
+        bam_api::TemplateSegments seg;
+        std::vector<bam_api::BAMReadId> filtered;
+        std::string msg;
+        if (!bam_api::read_bam_templates(path, cfg, seg, filtered, &msg)) {
+            copy_err(msg, err, err_cap);
+            return -1;
+        }
+        const std::uint64_t n = seg.starts.size();
+        if (n > cap || !copy_out_ingest(filtered, seg.contig_lengths, {cap_f, filtered_out, n_filtered_out, ref_cap, ref_lengths, n_refs}))
+            return -2;
+        for (std::uint64_t i = 0; i < n; ++i) {
+            starts[i] = seg.starts[i]; ends[i] = seg.ends[i]; contig_ids[i] = seg.contig_ids[i];
+            template_ids[i] = seg.template_ids[i]; qualities[i] = seg.qualities[i]; seq_lengths[i] = seg.seq_lengths[i];
+            segment_records[i] = seg.segment_records[i];
+        }
+        *n_templates = seg.n_templates;
+        return (std::int64_t)n;
+    });
+}
 
 // BED (+ optional TSV, may be NULL or "") against the references ref_names[0..n_refs) -> the amplicons of every
 // reference in CSR form (build_reference_amplicon_set): offsets_out (n_refs + 1 entries), starts_out / ends_out (cap
@@ -375,49 +830,6 @@ std::int64_t qmcp_host_reference_names(const char* path, char* buf, std::size_t 
     return static_cast<std::int64_t>(names.size());
 }
 
-// qmcp_host_read_bam_per_reference with amplicon_mode (0 IGNORE, 1 FILTER, 2 GRADE) and the two flags of BamApiConfig
-// (per_reference, amplicons_by_reference).  contig_ids is filled only with per_reference.  -2 when a capacity is too
-// small, -3 out of memory, -4 when BamApi refuses the configuration or the amplicon files (message in err).
-std::int64_t qmcp_host_read_bam_by_reference(const char* path, const char* bed, const char* tsv, int amplicon_mode,
-                                             int per_reference, int amplicons_by_reference, std::uint32_t min_len,
-                                             std::uint32_t min_mapq, std::uint64_t cap, std::uint64_t* bam_ids,
-                                             std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* qualities,
-                                             std::uint32_t* seq_lengths, std::uint8_t* is_first,
-                                             std::uint32_t* contig_ids, std::uint64_t cap_f,
-                                             std::uint64_t* filtered_out, std::uint64_t* n_filtered_out,
-                                             std::uint64_t ref_cap, std::uint32_t* ref_lengths, std::uint64_t* n_refs,
-                                             char* err, std::size_t err_cap) {
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_mode == 1 ? bam_api::AmpliconBehaviour::FILTER
-                           : amplicon_mode == 2 ? bam_api::AmpliconBehaviour::GRADE : bam_api::AmpliconBehaviour::IGNORE;
-    cfg.per_reference = per_reference != 0;
-    cfg.amplicons_by_reference = amplicons_by_reference != 0;
-    try {
-        bam_api::BamApi api(path, cfg);
-        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
-        const std::uint64_t n = r.ids.size();
-        if (n > cap || api.get_filtered_out_reads().size() > cap_f || r.contig_lengths.size() > ref_cap) return -2;
-        for (std::uint64_t i = 0; i < n; ++i) {
-            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
-            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
-            contig_ids[i] = r.contig_ids.size() == n ? r.contig_ids[i] : 0u;
-        }
-        *n_filtered_out = api.get_filtered_out_reads().size();
-        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
-        *n_refs = r.contig_lengths.size();
-        for (std::size_t k = 0; k < r.contig_lengths.size(); ++k) ref_lengths[k] = r.contig_lengths[k];
-        return (std::int64_t)n;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
 
 // read_bam's own verdict on a file, without BamApi's exit-on-error (the reference exits the process on an
 // unreadable input; a caller that wants to look first -- and the tests of corrupt files -- use this): 0 and the
@@ -467,1014 +879,18 @@ std::int64_t qmcp_host_copy_records(const char* in_path, const char* out_path, c
     return rc;
 }
 
-// The file-to-file flow of App::execute (src/app.cpp:113-151) for one solver: BamApi(path) -> solve ->
-// find_pairs -> write_paired_reads(out) (+ write_bam_api_filtered_out_reads(filtered) if given).
-// Returns the number of records written to `out_path`, negative on an unknown solver.
-std::int64_t qmcp_host_downsample_bam(const char* solver_name, const char* in_path, const char* out_path,
-                                      const char* filtered_path, std::uint32_t max_coverage,
-                                      std::uint32_t min_len, std::uint32_t min_mapq) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    try {
-        bam_api::BamApi api(in_path, cfg);
-        auto solution = found->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    }
-}
-
-// qmcp_host_downsample_bam with BamApiConfig::per_reference: every reference of the file is its own coverage problem
-// (the solver takes qmcp_hip_solve_by_contig_host), pairing and writing as before -- a kept read still brings its mate,
-// on whichever reference that lies.  Returns the number of records written, -1 on an unknown solver.
-std::int64_t qmcp_host_downsample_bam_per_reference(const char* solver_name, const char* in_path, const char* out_path,
-                                                    const char* filtered_path, std::uint32_t max_coverage,
-                                                    std::uint32_t min_len, std::uint32_t min_mapq) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.per_reference = true;
-    try {
-        bam_api::BamApi api(in_path, cfg);
-        auto solution = found->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    }
-}
-
-// qmcp_host_downsample_bam_per_reference with amplicons: BamApiConfig {bed, tsv, amplicon_mode (0 IGNORE, 1 FILTER,
-// 2 GRADE), per_reference, amplicons_by_reference}.  FILTER acts during ingest, as in the single-reference flow; the
-// survivors are solved one reference at a time and paired as before.  Returns the number of records written, -1 on an
-// unknown solver, -3 out of memory, -4 when BamApi refuses the configuration or the amplicon files (message in err).
-std::int64_t qmcp_host_downsample_bam_by_reference(const char* solver_name, const char* in_path, const char* out_path,
-                                                   const char* filtered_path, std::uint32_t max_coverage,
-                                                   std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
-                                                   const char* tsv, int amplicon_mode, int per_reference,
-                                                   int amplicons_by_reference, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
-    cfg.per_reference = per_reference != 0;
-    cfg.amplicons_by_reference = amplicons_by_reference != 0;
-    try {
-        bam_api::BamApi api(in_path, cfg);
-        auto solution = found->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// qmcp_host_downsample_bam_by_reference with target regions: BamApiConfig {targets_filepath, target_padding,
-// keep_off_target} on top of the amplicon fields (bed / tsv may be NULL).  FILTER / GRADE act at ingest as before; the
-// targets act in the solve (qmcp_hip_solve_targets_host).  Returns as qmcp_host_downsample_bam_by_reference; -4 also
-// when the target BED is refused (targets without per_reference, an unknown chrom, a malformed line).
-std::int64_t qmcp_host_downsample_bam_targets(const char* solver_name, const char* in_path, const char* out_path,
-                                              const char* filtered_path, std::uint32_t max_coverage,
-                                              std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
-                                              const char* tsv, int amplicon_mode, int per_reference,
-                                              int amplicons_by_reference, const char* targets,
-                                              std::uint32_t target_padding, int keep_off_target, char* err,
-                                              std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
-    cfg.per_reference = per_reference != 0;
-    cfg.amplicons_by_reference = amplicons_by_reference != 0;
-    if (targets && targets[0]) cfg.targets_filepath = targets;
-    cfg.target_padding = target_padding;
-    cfg.keep_off_target = keep_off_target != 0;
-    try {
-        bam_api::BamApi api(in_path, cfg);
-        auto solution = found->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// qmcp_host_downsample_bam_targets with a depth report: BamApiConfig {depth_report_filepath, depth_report_bins} on top
-// (targets may be NULL: the report is then per reference only).  After the output has been written, the hip solver
-// reports the reads the solve saw against the final kept set (after find_pairs) with M = max_coverage and the call's
-// targets and padding, and the TSV goes to report_path.  Returns as qmcp_host_downsample_bam_targets; -4 also for a
-// report without per_reference or with a solver that has none, -5 when the report cannot be written.
-std::int64_t qmcp_host_downsample_bam_report(const char* solver_name, const char* in_path, const char* out_path,
-                                             const char* filtered_path, std::uint32_t max_coverage,
-                                             std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
-                                             const char* tsv, int amplicon_mode, int per_reference,
-                                             int amplicons_by_reference, const char* targets,
-                                             std::uint32_t target_padding, int keep_off_target, const char* report_path,
-                                             std::uint32_t report_bins, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
-    cfg.per_reference = per_reference != 0;
-    cfg.amplicons_by_reference = amplicons_by_reference != 0;
-    if (targets && targets[0]) cfg.targets_filepath = targets;
-    cfg.target_padding = target_padding;
-    cfg.keep_off_target = keep_off_target != 0;
-    if (report_path && report_path[0]) cfg.depth_report_filepath = report_path;
-    cfg.depth_report_bins = report_bins;
-    try {
-        bam_api::BamApi api(in_path, cfg);
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr && !api.depth_report_filepath().empty())
-            throw std::invalid_argument("this solver has no depth report");
-        auto solution = found->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        if (!api.depth_report_filepath().empty()) {
-            std::vector<std::string> names;
-            std::vector<std::uint32_t> lengths;
-            std::string msg;
-            if (!bam_api::read_bam_references(in_path, names, lengths, &msg)) {
-                copy_err(msg, err, err_cap);
-                return -5;
-            }
-            qmcp::DepthReport report;
-            hip->depth_report(max_coverage, api, paired, api.depth_report_bins(), report);
-            if (!qmcp::write_depth_report_tsv(api.depth_report_filepath(), report, names)) {
-                copy_err("could not write " + api.depth_report_filepath().string(), err, err_cap);
-                return -5;
-            }
-        }
-        return written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// qmcp_host_downsample_bam_report with a depth track: BamApiConfig {depth_track_filepath, depth_track_channel,
-// depth_track_cap} on top (report_path may be NULL: no report).  After the output -- and the report -- has been written,
-// the hip solver's depth track of the reads the solve saw against the final kept set (after find_pairs), inside the
-// call's targets and padding when given, goes to track_path as bedGraph: channel "kept", "in" or "both", both depths
-// compared, zero positions kept.  Returns as qmcp_host_downsample_bam_report; -4 also for a track without per_reference,
-// another channel, or a solver that has none, -5 when the track cannot be written.
-std::int64_t qmcp_host_downsample_bam_track(const char* solver_name, const char* in_path, const char* out_path,
-                                            const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                            std::uint32_t min_mapq, const char* bed, const char* tsv, int amplicon_mode,
-                                            int per_reference, int amplicons_by_reference, const char* targets,
-                                            std::uint32_t target_padding, int keep_off_target, const char* report_path,
-                                            std::uint32_t report_bins, const char* track_path, const char* track_channel,
-                                            std::uint32_t track_cap, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
-    cfg.per_reference = per_reference != 0;
-    cfg.amplicons_by_reference = amplicons_by_reference != 0;
-    if (targets && targets[0]) cfg.targets_filepath = targets;
-    cfg.target_padding = target_padding;
-    cfg.keep_off_target = keep_off_target != 0;
-    if (report_path && report_path[0]) cfg.depth_report_filepath = report_path;
-    cfg.depth_report_bins = report_bins;
-    if (track_path && track_path[0]) cfg.depth_track_filepath = track_path;
-    if (track_channel && track_channel[0]) cfg.depth_track_channel = track_channel;
-    cfg.depth_track_cap = track_cap;
-    try {
-        bam_api::BamApi api(in_path, cfg);
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr && !api.depth_report_filepath().empty())
-            throw std::invalid_argument("this solver has no depth report");
-        if (hip == nullptr && !api.depth_track_filepath().empty())
-            throw std::invalid_argument("this solver has no depth track");
-        auto solution = found->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        if (!api.depth_report_filepath().empty() || !api.depth_track_filepath().empty()) {
-            std::vector<std::string> names;
-            std::vector<std::uint32_t> lengths;
-            std::string msg;
-            if (!bam_api::read_bam_references(in_path, names, lengths, &msg)) {
-                copy_err(msg, err, err_cap);
-                return -5;
-            }
-            if (!api.depth_report_filepath().empty()) {
-                qmcp::DepthReport report;
-                hip->depth_report(max_coverage, api, paired, api.depth_report_bins(), report);
-                if (!qmcp::write_depth_report_tsv(api.depth_report_filepath(), report, names)) {
-                    copy_err("could not write " + api.depth_report_filepath().string(), err, err_cap);
-                    return -5;
-                }
-            }
-            if (!api.depth_track_filepath().empty()) {
-                qmcp::DepthTrack track;
-                hip->depth_track(max_coverage, api, paired, QMCP_TRACK_IN | QMCP_TRACK_KEPT, api.depth_track_cap(), track);
-                if (!qmcp::write_depth_track_bedgraph(api.depth_track_filepath(), track, names, api.depth_track_channel())) {
-                    copy_err("could not write " + api.depth_track_filepath().string(), err, err_cap);
-                    return -5;
-                }
-            }
-        }
-        return written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// qmcp_host_downsample_bam_by_reference with a coverage ladder: BamApiConfig {coverage_ladder} on top of the amplicon
-// fields (bed / tsv may be NULL; FILTER acts at ingest as before).  One ingest and one qmcp_hip_solve_ladder_host call;
-// the level at max_coverage goes to out_path, level `levels[j]` through find_pairs to out_template with its "{M}"
-// replaced by the coverage.  written_out (1 + n_levels entries) receives each file's record count, out_path's first.
-// Returns the number of files written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the
-// configuration is refused: no per_reference, a template without "{M}", levels not strictly below max_coverage and
-// strictly decreasing, a solver that grades by quality or has no ladder.
-std::int64_t qmcp_host_downsample_bam_ladder(const char* solver_name, const char* in_path, const char* out_path,
-                                             const char* filtered_path, std::uint32_t max_coverage,
-                                             std::uint32_t min_len, std::uint32_t min_mapq, const char* bed,
-                                             const char* tsv, int amplicon_mode, int per_reference,
-                                             int amplicons_by_reference, const std::uint32_t* levels,
-                                             std::uint32_t n_levels, const char* out_template,
-                                             std::int64_t* written_out, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    bam_api::BamApiConfig cfg;
-    if (bed && bed[0]) cfg.bed_filepath = bed;
-    if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-    cfg.min_seq_length = min_len;
-    cfg.min_mapq = min_mapq;
-    cfg.amplicon_behaviour = amplicon_behaviour(amplicon_mode, *found);
-    cfg.per_reference = per_reference != 0;
-    cfg.amplicons_by_reference = amplicons_by_reference != 0;
-    if (levels != nullptr) cfg.coverage_ladder.assign(levels, levels + n_levels);
-    try {
-        const std::string tmpl = out_template ? out_template : "";
-        const std::size_t at = tmpl.find("{M}");
-        if (cfg.coverage_ladder.empty()) throw std::invalid_argument("a coverage ladder needs at least one level");
-        if (at == std::string::npos) throw std::invalid_argument("the ladder's output template has no {M}");
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("a coverage ladder does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no coverage ladder");
-        bam_api::BamApi api(in_path, cfg);
-        auto solutions = hip->solve_ladder(max_coverage, api, api.coverage_ladder());
-        for (std::size_t j = 0; j < solutions.size(); ++j) {
-            std::string path = out_path;
-            if (j > 0) {
-                path = tmpl;
-                path.replace(at, 3, std::to_string(api.coverage_ladder()[j - 1]));
-            }
-            std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solutions[j]);
-            const std::uint32_t written = api.write_paired_reads(path, paired);
-            if (written_out) written_out[j] = written;
-        }
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return (std::int64_t)solutions.size();
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-namespace {
-// "strand" / "read_group" -> BamApiConfig::stratify_by; anything else is refused
-bam_api::Stratify stratify_from_name(const char* name) {
-    const std::string s = name ? name : "";
-    if (s == "strand") return bam_api::Stratify::STRAND;
-    if (s == "read_group") return bam_api::Stratify::READ_GROUP;
-    throw std::invalid_argument("stratify must be \"strand\" or \"read_group\", not \"" + s + "\"");
-}
-}  // namespace
-
-// qmcp_host_read_bam_per_reference with BamApiConfig::stratify_by ("strand" / "read_group"): the same columns, plus each
-// read's stratum (strata, cap entries) and the strata's names, one per line, in names_out (names_cap bytes; *n_strata
-// receives the count).  -2 when a capacity is too small, -3 out of memory, -4 with the message in err.
-std::int64_t qmcp_host_read_bam_stratified(const char* path, const char* stratify, std::uint32_t min_len,
-                                           std::uint32_t min_mapq, std::uint64_t cap, std::uint64_t* bam_ids,
-                                           std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* qualities,
-                                           std::uint32_t* seq_lengths, std::uint8_t* is_first, std::uint32_t* contig_ids,
-                                           std::uint32_t* strata, std::uint64_t cap_f, std::uint64_t* filtered_out,
-                                           std::uint64_t* n_filtered_out, std::uint64_t ref_cap,
-                                           std::uint32_t* ref_lengths, std::uint64_t* n_refs, char* names_out,
-                                           std::size_t names_cap, std::uint64_t* n_strata, int per_reference, char* err,
-                                           std::size_t err_cap) {
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.stratify_by = stratify_from_name(stratify);
-        bam_api::BamApi api(path, cfg);
-        const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
-        const std::uint64_t n = r.ids.size();
-        std::string names;
-        for (const std::string& s : r.stratum_names) names += s + "\n";
-        if (n > cap || api.get_filtered_out_reads().size() > cap_f || r.contig_lengths.size() > ref_cap ||
-            names.size() + 1 > names_cap)
-            return -2;
-        for (std::uint64_t i = 0; i < n; ++i) {
-            bam_ids[i] = r.ids[i]; starts[i] = (std::uint32_t)r.start_inds[i]; ends[i] = (std::uint32_t)r.end_inds[i];
-            qualities[i] = r.qualities[i]; seq_lengths[i] = r.seq_lengths[i]; is_first[i] = r.is_first_reads[i] ? 1 : 0;
-            contig_ids[i] = r.contig_ids[i];
-            strata[i] = r.strata[i];
-        }
-        *n_filtered_out = api.get_filtered_out_reads().size();
-        for (std::size_t i = 0; i < api.get_filtered_out_reads().size(); ++i) filtered_out[i] = api.get_filtered_out_reads()[i];
-        *n_refs = r.contig_lengths.size();
-        for (std::size_t k = 0; k < r.contig_lengths.size(); ++k) ref_lengths[k] = r.contig_lengths[k];
-        std::memcpy(names_out, names.c_str(), names.size() + 1);
-        *n_strata = r.stratum_names.size();
-        return (std::int64_t)n;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::stratify_by ("strand" / "read_group"): one ingest, one
-// qmcp_hip_solve_stratified_host call (QuasiMcpHipSolver::solve picks it when the reads carry strata), find_pairs,
-// write_paired_reads.  targets / report / ladder_levels are handed to BamApiConfig as given so that it refuses the
-// combinations it refuses.  strata_report (may be NULL): a TSV written after the output, one line per stratum -- name,
-// cap, reads, kept, mean depth before and after (bases / the sum of the reference lengths) -- of the solve's own kept
-// set (before mate completion).  Returns the number of records written; -1 on an unknown solver, -3 out of memory, -4
-// with a message in err when the configuration is refused, -5 when the report cannot be written.
-std::int64_t qmcp_host_downsample_bam_stratified(const char* solver_name, const char* in_path, const char* out_path,
-                                                 const char* filtered_path, std::uint32_t max_coverage,
-                                                 std::uint32_t min_len, std::uint32_t min_mapq, int per_reference,
-                                                 const char* stratify, const char* targets, const char* report,
-                                                 const std::uint32_t* ladder_levels, std::uint32_t n_ladder_levels,
-                                                 const char* strata_report, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.stratify_by = stratify_from_name(stratify);
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        bam_api::BamApi api(in_path, cfg);
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("stratified downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no stratified downsampling");
-        std::unique_ptr<qmcp::Solution> solution = hip->solve(max_coverage, api);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        if (strata_report && strata_report[0]) {
-            const bam_api::SOAPairedReads& r = api.get_paired_reads_soa();
-            double positions = 0;
-            for (std::uint32_t l : r.contig_lengths) positions += l;
-            std::FILE* f = std::fopen(strata_report, "w");
-            if (f == nullptr) return -5;
-            std::fprintf(f, "#stratum\tcap\treads\tkept\tmean_depth_in\tmean_depth_kept\n");
-            for (std::size_t s = 0; s < r.stratum_names.size(); ++s) {
-                const qmcp_hip_stratum_row& row = hip->last_stratum_rows()[s];
-                std::fprintf(f, "%s\t%u\t%llu\t%llu\t%.6f\t%.6f\n", r.stratum_names[s].c_str(),
-                             hip->last_stratum_caps()[s], (unsigned long long)row.n_reads, (unsigned long long)row.n_kept,
-                             positions > 0 ? (double)row.bases_in / positions : 0.0,
-                             positions > 0 ? (double)row.bases_kept / positions : 0.0);
-            }
-            if (std::fclose(f) != 0) return -5;
-        }
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::dedup: one ingest (strand bit and MAPQ per read), one
-// qmcp_hip_solve_dedup_host call in pair mode with mate completion (QuasiMcpHipSolver::solve_dedup), find_pairs,
-// write_paired_reads -- duplicate pairs are simply not written; filtered_path keeps its meaning of ingest filters only.
-// targets / report / ladder_levels / stratify / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given so
-// that it refuses the combinations it refuses.  dedup_report (may be NULL): a TSV written after the output -- the
-// statistics, then one size<TAB>families line per bin of the family-size histogram at 64 bins.  Returns the number of
-// records written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the configuration is
-// refused, -5 when the report cannot be written.
-std::int64_t qmcp_host_downsample_bam_dedup(const char* solver_name, const char* in_path, const char* out_path,
-                                            const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                            std::uint32_t min_mapq, int per_reference, const char* targets,
-                                            const char* report, const std::uint32_t* ladder_levels,
-                                            std::uint32_t n_ladder_levels, const char* stratify, const char* bed,
-                                            const char* tsv, int amplicons_by_reference, const char* dedup_report,
-                                            char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.dedup = true;
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
-        if (bed && bed[0]) cfg.bed_filepath = bed;
-        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-        cfg.amplicons_by_reference = amplicons_by_reference != 0;
-        if (cfg.dedup && cfg.per_reference && cfg.amplicons_by_reference)
-            throw std::invalid_argument("duplicate-aware downsampling does not take amplicon files");
-        bam_api::BamApi api(in_path, cfg);
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("duplicate-aware downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no duplicate-aware downsampling");
-        constexpr std::uint32_t kBins = 64;
-        std::unique_ptr<qmcp::Solution> solution = hip->solve_dedup(max_coverage, api, kBins);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        if (dedup_report && dedup_report[0]) {
-            const qmcp_hip_dedup_stats& ds = hip->last_dedup_stats();
-            std::FILE* f = std::fopen(dedup_report, "w");
-            if (f == nullptr) return -5;
-            std::fprintf(f, "#stat\tvalue\n");
-            std::fprintf(f, "units\t%llu\nfamilies\t%llu\nduplicate_units\t%llu\nlargest_family\t%llu\nreads_survived\t%llu\n",
-                         (unsigned long long)ds.units, (unsigned long long)ds.families,
-                         (unsigned long long)ds.duplicate_units, (unsigned long long)ds.largest_family,
-                         (unsigned long long)ds.reads_survived);
-            std::fprintf(f, "#size\tfamilies\n");
-            for (std::uint32_t b = 0; b < kBins; ++b)
-                std::fprintf(f, "%u\t%llu\n", b + 1, (unsigned long long)hip->last_dedup_hist()[b]);
-            if (std::fclose(f) != 0) return -5;
-        }
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with a coverage profile: one per-reference ingest, one qmcp_hip_solve_profile_host call
-// (QuasiMcpHipSolver::solve_profile) with the regions in CSR form per reference of the file (n_refs + 1 offsets; the
-// caller has matched chroms to references and flattened overlaps) and max_coverage as the default cap, find_pairs,
-// write_paired_reads.  Refused, each with its own message (-4): no per_reference, targets, a depth report, a ladder,
-// stratify, dedup, amplicon files, a solver that grades by quality, offsets for another number of references.  Returns
-// the number of records written; -1 on an unknown solver, -3 out of memory.
-std::int64_t qmcp_host_downsample_bam_profile(const char* solver_name, const char* in_path, const char* out_path,
-                                              const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                              std::uint32_t min_mapq, int per_reference, const std::uint32_t* region_offsets,
-                                              const std::uint32_t* region_starts, const std::uint32_t* region_ends,
-                                              const std::uint32_t* region_caps, std::uint64_t n_refs, const char* targets,
-                                              const char* report, std::uint32_t n_ladder_levels, const char* stratify,
-                                              int dedup, const char* bed, const char* tsv, int amplicons_by_reference,
-                                              char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        if (!per_reference) throw std::invalid_argument("a coverage profile needs per_reference");
-        if (targets && targets[0]) throw std::invalid_argument("a coverage profile does not go together with targets");
-        if (report && report[0]) throw std::invalid_argument("a coverage profile does not go together with a depth report");
-        if (n_ladder_levels) throw std::invalid_argument("a coverage profile does not go together with a coverage ladder");
-        if (stratify && stratify[0]) throw std::invalid_argument("a coverage profile does not go together with stratify_by");
-        if (dedup) throw std::invalid_argument("a coverage profile does not go together with dedup");
-        if ((bed && bed[0]) || (tsv && tsv[0]) || amplicons_by_reference)
-            throw std::invalid_argument("a coverage profile does not take amplicon files");
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("a coverage profile does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no coverage profile");
-        if (region_offsets == nullptr) throw std::invalid_argument("a coverage profile needs its region offsets");
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = true;
-        bam_api::BamApi api(in_path, cfg);
-        const std::uint32_t n_reg = region_offsets[n_refs];
-        if (n_reg && (!region_starts || !region_ends || !region_caps))
-            throw std::invalid_argument("a coverage profile with regions needs their starts, ends and caps");
-        const std::vector<std::uint32_t> offs(region_offsets, region_offsets + n_refs + 1);
-        const std::vector<std::uint32_t> rs(region_starts, region_starts + n_reg), re(region_ends, region_ends + n_reg),
-            caps(region_caps, region_caps + n_reg);
-        std::unique_ptr<qmcp::Solution> solution = hip->solve_profile(max_coverage, api, offs, rs, re, caps);
-        std::vector<bam_api::ReadIndex> paired = api.find_pairs(*solution);
-        const std::uint32_t written = api.write_paired_reads(out_path, paired);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::pair_aware: one per-reference ingest, one qmcp_hip_solve_pairs_host call
-// (QuasiMcpHipSolver::solve_pairs) under `stages` (NULL or n_stages == 0: the default schedule), write_paired_reads from
-// its mask -- whole pairs already, so NO find_pairs.  targets / report / track / ladder_levels / stratify / dedup / bed /
-// tsv / amplicons_by_reference are handed to BamApiConfig as given so that it refuses the combinations it refuses; a
-// coverage profile (profile != 0) and a solver that grades by quality are refused here.  Returns the number of records
-// written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the configuration is refused.
-std::int64_t qmcp_host_downsample_bam_pairs(const char* solver_name, const char* in_path, const char* out_path,
-                                            const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                            std::uint32_t min_mapq, int per_reference, const std::uint32_t* stages,
-                                            std::uint32_t n_stages, const char* targets, const char* report,
-                                            const char* track, const std::uint32_t* ladder_levels,
-                                            std::uint32_t n_ladder_levels, const char* stratify, int dedup, int profile,
-                                            const char* bed, const char* tsv, int amplicons_by_reference, char* err,
-                                            std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.pair_aware = true;
-        if (stages != nullptr && n_stages) cfg.pair_stages.assign(stages, stages + n_stages);
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (track && track[0]) cfg.depth_track_filepath = track;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
-        cfg.dedup = dedup != 0;
-        if (bed && bed[0]) cfg.bed_filepath = bed;
-        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-        cfg.amplicons_by_reference = amplicons_by_reference != 0;
-        if (profile) throw std::invalid_argument("pair-aware downsampling does not go together with a coverage profile");
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("pair-aware downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no pair-aware downsampling");
-        bam_api::BamApi api(in_path, cfg);
-        std::unique_ptr<qmcp::Solution> solution = hip->solve_pairs(max_coverage, api);
-        std::vector<bam_api::ReadIndex> kept(solution->begin(), solution->end());
-        const std::uint32_t written = api.write_paired_reads(out_path, kept);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::ceiling: one per-reference ingest, one qmcp_hip_solve_ceiling_host call with
-// QMCP_CEILING_WHOLE_PAIRS (QuasiMcpHipSolver::solve_ceiling) -- max_coverage is the ceiling; with a coverage profile
-// (region_offsets != NULL: n_refs + 1 offsets, as qmcp_host_downsample_bam_profile takes them) the regions' caps are
-// ceilings and max_coverage applies elsewhere -- and write_paired_reads from its mask: whole pairs already, and NO
-// find_pairs, which would put depth back.  targets / report / track / ladder_levels / stratify / dedup / pair_aware /
-// template_aware / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given so that it refuses the
-// combinations it refuses; a solver that grades by quality is refused here.  ceiling_report (may be NULL): a TSV
-// stat<TAB>value with the qmcp_hip_ceiling_stats and the records written.  cstats (may be NULL) takes the stats.  Returns
-// the number of records written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the
-// configuration is refused, -5 when the report cannot be written.
-std::int64_t qmcp_host_downsample_bam_ceiling(const char* solver_name, const char* in_path, const char* out_path,
-                                              const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                              std::uint32_t min_mapq, int per_reference, const std::uint32_t* region_offsets,
-                                              const std::uint32_t* region_starts, const std::uint32_t* region_ends,
-                                              const std::uint32_t* region_caps, std::uint64_t n_refs, const char* targets,
-                                              const char* report, const char* track, const std::uint32_t* ladder_levels,
-                                              std::uint32_t n_ladder_levels, const char* stratify, int dedup, int pair_aware,
-                                              int template_aware, const char* bed, const char* tsv,
-                                              int amplicons_by_reference, const char* ceiling_report,
-                                              qmcp_hip_ceiling_stats* cstats, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.ceiling = true;
-        cfg.pair_aware = pair_aware != 0;
-        cfg.template_aware = template_aware != 0;
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (track && track[0]) cfg.depth_track_filepath = track;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
-        cfg.dedup = dedup != 0;
-        if (bed && bed[0]) cfg.bed_filepath = bed;
-        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-        cfg.amplicons_by_reference = amplicons_by_reference != 0;
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("ceiling downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no ceiling downsampling");
-        bam_api::BamApi api(in_path, cfg);
-        std::vector<std::uint32_t> offs, rs, re, caps;
-        if (region_offsets != nullptr) {
-            const std::uint32_t n_reg = region_offsets[n_refs];
-            if (n_reg && (!region_starts || !region_ends || !region_caps))
-                throw std::invalid_argument("a coverage profile with regions needs their starts, ends and caps");
-            offs.assign(region_offsets, region_offsets + n_refs + 1);
-            if (n_reg) {
-                rs.assign(region_starts, region_starts + n_reg);
-                re.assign(region_ends, region_ends + n_reg);
-                caps.assign(region_caps, region_caps + n_reg);
-            }
-        }
-        std::unique_ptr<qmcp::Solution> solution = hip->solve_ceiling(max_coverage, api, offs, rs, re, caps);
-        std::vector<bam_api::ReadIndex> kept(solution->begin(), solution->end());
-        const std::uint32_t written = api.write_paired_reads(out_path, kept);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        const qmcp_hip_ceiling_stats& cs = hip->last_ceiling_stats();
-        if (cstats != nullptr) *cstats = cs;
-        if (ceiling_report && ceiling_report[0]) {
-            std::FILE* f = std::fopen(ceiling_report, "w");
-            if (f == nullptr) return -5;
-            std::fprintf(f, "#stat\tvalue\n");
-            std::fprintf(f, "reads_placed\t%llu\nreads_dropped\t%llu\nmates_dropped\t%llu\nover_positions\t%llu\n"
-                            "over_bases\t%llu\nshort_positions\t%llu\nshort_bases\t%llu\nexcess_positions\t%llu\n",
-                         (unsigned long long)cs.reads_placed, (unsigned long long)cs.reads_dropped,
-                         (unsigned long long)cs.mates_dropped, (unsigned long long)cs.over_positions,
-                         (unsigned long long)cs.over_bases, (unsigned long long)cs.short_positions,
-                         (unsigned long long)cs.short_bases, (unsigned long long)cs.excess_positions);
-            std::fprintf(f, "max_kept_depth\t%u\nregions_in\t%u\nregions_used\t%u\nrecords_written\t%u\n", cs.max_kept_depth,
-                         cs.regions_in, cs.regions_used, written);
-            if (std::fclose(f) != 0) return -5;
-        }
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::replicates: one per-reference ingest, one qmcp_hip_solve_replicates_host call
-// with QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL (QuasiMcpHipSolver::solve_replicates) -- replicate 1 at
-// max_coverage, replicate r + 2 at further[r] -- and one write_paired_reads per replicate from its label: replicate 1 to
-// out_path, replicate R to out_template with its "{R}" replaced.  NO find_pairs: it would copy a record into two files,
-// so every input record is written at most once over all files.  targets / report / track / ladder_levels / stratify /
-// dedup / pair_aware / template_aware / ceiling / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given
-// so that it refuses the combinations it refuses; a solver that grades by quality is refused here.  written_out (1 +
-// n_further entries) receives each file's record count.  replicates_report (may be NULL): a TSV with one line per
-// replicate -- coverage, offered, kept, mates, short_positions, short_bases, records_written -- and an n_full line.
-// rstats (may be NULL) takes the stats.  Returns the number of files written; -1 on an unknown solver, -3 out of memory,
-// -4 with a message in err when the configuration is refused, -5 when the report cannot be written.
-std::int64_t qmcp_host_downsample_bam_replicates(const char* solver_name, const char* in_path, const char* out_path,
-                                                 const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                                 std::uint32_t min_mapq, int per_reference, const std::uint32_t* further,
-                                                 std::uint32_t n_further, const char* out_template, const char* targets,
-                                                 const char* report, const char* track, const std::uint32_t* ladder_levels,
-                                                 std::uint32_t n_ladder_levels, const char* stratify, int dedup,
-                                                 int pair_aware, int template_aware, int ceiling, const char* bed,
-                                                 const char* tsv, int amplicons_by_reference, const char* replicates_report,
-                                                 std::int64_t* written_out, qmcp_hip_replicates_stats* rstats, char* err,
-                                                 std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.replicates = std::vector<std::uint32_t>();
-        if (further != nullptr) cfg.replicates->assign(further, further + n_further);
-        cfg.pair_aware = pair_aware != 0;
-        cfg.template_aware = template_aware != 0;
-        cfg.ceiling = ceiling != 0;
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (track && track[0]) cfg.depth_track_filepath = track;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
-        cfg.dedup = dedup != 0;
-        if (bed && bed[0]) cfg.bed_filepath = bed;
-        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-        cfg.amplicons_by_reference = amplicons_by_reference != 0;
-        const std::string tmpl = out_template ? out_template : "";
-        const std::size_t at = tmpl.find("{R}");
-        if (!cfg.replicates->empty() && at == std::string::npos)
-            throw std::invalid_argument("the replicates' output template has no {R}");
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("disjoint replicates do not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no disjoint replicates");
-        bam_api::BamApi api(in_path, cfg);
-        const std::vector<std::uint8_t> labels = hip->solve_replicates(max_coverage, api);
-        const std::size_t k = api.replicates()->size() + 1;
-        std::vector<std::uint32_t> written(k, 0);
-        for (std::size_t r = 1; r <= k; ++r) {
-            std::string path = out_path;
-            if (r > 1) {
-                path = tmpl;
-                path.replace(at, 3, std::to_string(r));
-            }
-            std::vector<bam_api::ReadIndex> kept;
-            for (std::size_t i = 0; i < labels.size(); ++i)
-                if (labels[i] == r) kept.push_back(i);
-            written[r - 1] = api.write_paired_reads(path, kept);
-            if (written_out) written_out[r - 1] = written[r - 1];
-        }
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        const qmcp_hip_replicates_stats& rs = hip->last_replicates_stats();
-        if (rstats != nullptr) *rstats = rs;
-        if (replicates_report && replicates_report[0]) {
-            std::FILE* f = std::fopen(replicates_report, "w");
-            if (f == nullptr) return -5;
-            std::fprintf(f, "#replicate\tcoverage\toffered\tkept\tmates\tshort_positions\tshort_bases\trecords_written\n");
-            for (std::size_t r = 0; r < k; ++r)
-                std::fprintf(f, "%zu\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%u\n", r + 1,
-                             r == 0 ? max_coverage : (*api.replicates())[r - 1], (unsigned long long)rs.n_offered[r],
-                             (unsigned long long)rs.n_kept[r], (unsigned long long)rs.n_mates[r],
-                             (unsigned long long)rs.short_positions[r], (unsigned long long)rs.short_bases[r], written[r]);
-            std::fprintf(f, "n_full\t%u\n", rs.n_full);
-            if (std::fclose(f) != 0) return -5;
-        }
-        return (std::int64_t)k;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::budget_reads / budget_fraction: one per-reference ingest, one
-// qmcp_hip_solve_budget_host call with QMCP_BUDGET_WHOLE_PAIRS (QuasiMcpHipSolver::solve_budget) -- max_coverage is the
-// upper end of the search -- and write_paired_reads from its mask: whole pairs already, and NO find_pairs, which would
-// add reads, so the records written stay within the budget.  has_budget_reads != 0: budget_reads counts; budget_fraction
-// >= 0: the fraction of the placed reads that passed the ingest filters; both or neither are handed on for BamApiConfig
-// and this function to refuse.  targets / report / track / ladder_levels / stratify / dedup / pair_aware / template_aware /
-// ceiling / bed / tsv / amplicons_by_reference are handed to BamApiConfig as given so that it refuses the combinations it
-// refuses; a solver that grades by quality is refused here.  budget_report (may be NULL): a TSV stat<TAB>value with the
-// qmcp_hip_budget_stats and the records written, then one M<TAB>bases line per entry of the curve.  bstats (may be NULL)
-// takes the stats.  Returns the number of records written; -1 on an unknown solver, -3 out of memory, -4 with a message
-// in err when the configuration is refused, -5 when the report cannot be written.
-std::int64_t qmcp_host_downsample_bam_budget(const char* solver_name, const char* in_path, const char* out_path,
-                                             const char* filtered_path, std::uint32_t max_coverage, std::uint32_t min_len,
-                                             std::uint32_t min_mapq, int per_reference, int has_budget_reads,
-                                             std::uint64_t budget_reads, double budget_fraction, const char* targets,
-                                             const char* report, const char* track, const std::uint32_t* ladder_levels,
-                                             std::uint32_t n_ladder_levels, const char* stratify, int dedup, int pair_aware,
-                                             int template_aware, int ceiling, const char* bed, const char* tsv,
-                                             int amplicons_by_reference, const char* budget_report,
-                                             qmcp_hip_budget_stats* bstats, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        if (has_budget_reads != 0) cfg.budget_reads = budget_reads;
-        if (budget_fraction >= 0.0 || budget_fraction != budget_fraction) cfg.budget_fraction = budget_fraction;
-        if (!cfg.budget_reads.has_value() && !cfg.budget_fraction.has_value())
-            throw std::invalid_argument("budget downsampling needs budget_reads or budget_fraction");
-        cfg.ceiling = ceiling != 0;
-        cfg.pair_aware = pair_aware != 0;
-        cfg.template_aware = template_aware != 0;
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (track && track[0]) cfg.depth_track_filepath = track;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
-        cfg.dedup = dedup != 0;
-        if (bed && bed[0]) cfg.bed_filepath = bed;
-        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-        cfg.amplicons_by_reference = amplicons_by_reference != 0;
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("budget downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no budget downsampling");
-        bam_api::BamApi api(in_path, cfg);
-        std::unique_ptr<qmcp::Solution> solution = hip->solve_budget(max_coverage, api);
-        std::vector<bam_api::ReadIndex> kept(solution->begin(), solution->end());
-        const std::uint32_t written = api.write_paired_reads(out_path, kept);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        const qmcp_hip_budget_stats& bs = hip->last_budget_stats();
-        if (bstats != nullptr) *bstats = bs;
-        if (budget_report && budget_report[0]) {
-            std::FILE* f = std::fopen(budget_report, "w");
-            if (f == nullptr) return -5;
-            std::fprintf(f, "#stat\tvalue\n");
-            std::fprintf(f, "budget\t%llu\nreads_placed\t%llu\nn_kept\t%llu\nkept_above\t%llu\nbound_above\t%llu\n"
-                            "total_bases\t%llu\n",
-                         (unsigned long long)bs.budget, (unsigned long long)bs.reads_placed, (unsigned long long)bs.n_kept,
-                         (unsigned long long)bs.kept_above, (unsigned long long)bs.bound_above,
-                         (unsigned long long)bs.total_bases);
-            std::fprintf(f, "coverage\t%u\nmax_depth\t%u\ntop\t%u\nprobes\t%u\ncurve_entries\t%u\nsaturated\t%u\n"
-                            "ms_budget\t%.6g\nms_solves\t%.6g\nrecords_written\t%u\n",
-                         bs.coverage, bs.max_depth, bs.top, bs.probes, bs.curve_entries, bs.saturated, (double)bs.ms_budget,
-                         (double)bs.ms_solves, written);
-            std::fprintf(f, "#M\tbases\n");
-            const std::vector<std::uint64_t>& curve = hip->last_budget_curve();
-            for (std::size_t m = 0; m < curve.size(); ++m)
-                std::fprintf(f, "%zu\t%llu\n", m, (unsigned long long)curve[m]);
-            if (std::fclose(f) != 0) return -5;
-        }
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// Template-aware ingest alone (BamApiConfig::template_aware; bam_api::read_bam_templates): the segments' columns (cap
-// entries each; segment_records: each segment's BAM record id), the skipped and dropped records (filtered_out, cap_f
-// entries), every reference's length and the number of templates.  Returns the number of segments; -2 when a capacity is
-// too small, -3 out of memory, -1 with the reader's message in err on a malformed or unreadable file.
-std::int64_t qmcp_host_read_bam_templates(const char* path, std::uint32_t min_len, std::uint32_t min_mapq,
-                                          int split_spliced, int include_secondary, std::uint64_t cap,
-                                          std::uint32_t* starts, std::uint32_t* ends, std::uint32_t* contig_ids,
-                                          std::uint32_t* template_ids, std::uint32_t* qualities,
-                                          std::uint32_t* seq_lengths, std::uint64_t* segment_records, std::uint64_t cap_f,
-                                          std::uint64_t* filtered_out, std::uint64_t* n_filtered_out, std::uint64_t ref_cap,
-                                          std::uint32_t* ref_lengths, std::uint64_t* n_refs, std::uint64_t* n_templates,
-                                          char* err, std::size_t err_cap) {
-    try {
-        bam_api::TemplateIngest cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.split_spliced = split_spliced != 0;
-        cfg.include_secondary = include_secondary != 0;
-        bam_api::TemplateSegments seg;
-        std::vector<bam_api::BAMReadId> filtered;
-        std::string msg;
-        if (!bam_api::read_bam_templates(path, cfg, seg, filtered, &msg)) {
-            copy_err(msg, err, err_cap);
-            return -1;
-        }
-        const std::uint64_t n = seg.starts.size();
-        if (n > cap || filtered.size() > cap_f || seg.contig_lengths.size() > ref_cap) return -2;
-        for (std::uint64_t i = 0; i < n; ++i) {
-            starts[i] = seg.starts[i]; ends[i] = seg.ends[i]; contig_ids[i] = seg.contig_ids[i];
-            template_ids[i] = seg.template_ids[i]; qualities[i] = seg.qualities[i]; seq_lengths[i] = seg.seq_lengths[i];
-            segment_records[i] = seg.segment_records[i];
-        }
-        *n_filtered_out = filtered.size();
-        for (std::size_t i = 0; i < filtered.size(); ++i) filtered_out[i] = filtered[i];
-        *n_refs = seg.contig_lengths.size();
-        for (std::size_t k = 0; k < seg.contig_lengths.size(); ++k) ref_lengths[k] = seg.contig_lengths[k];
-        *n_templates = seg.n_templates;
-        return (std::int64_t)n;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    }
-}
-
-// The file-to-file flow with BamApiConfig::template_aware: one template-aware ingest, one qmcp_hip_solve_templates_host
-// call (QuasiMcpHipSolver::solve_templates) under `stages` (NULL or n_stages == 0: the default schedule), the records of
-// the kept templates written with BamApi::write_records -- NO find_pairs.  Everything pair_aware refuses, and pair_aware
-// itself, is handed to BamApiConfig as given so that it refuses it; a coverage profile and a solver that grades by
-// quality are refused here.  tstats (may be NULL) receives the call's qmcp_hip_template_stats.  Returns the number of
-// records written; -1 on an unknown solver, -3 out of memory, -4 with a message in err when the configuration is refused.
-std::int64_t qmcp_host_downsample_bam_templates(const char* solver_name, const char* in_path, const char* out_path,
-                                                const char* filtered_path, std::uint32_t max_coverage,
-                                                std::uint32_t min_len, std::uint32_t min_mapq, int per_reference,
-                                                int split_spliced, int include_secondary, const std::uint32_t* stages,
-                                                std::uint32_t n_stages, int pair_aware, const char* targets,
-                                                const char* report, const char* track,
-                                                const std::uint32_t* ladder_levels, std::uint32_t n_ladder_levels,
-                                                const char* stratify, int dedup, int profile, const char* bed,
-                                                const char* tsv, int amplicons_by_reference,
-                                                qmcp_hip_template_stats* tstats, char* err, std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.template_aware = true;
-        cfg.split_spliced = split_spliced != 0;
-        cfg.include_secondary = include_secondary != 0;
-        if (stages != nullptr && n_stages) cfg.template_stages.assign(stages, stages + n_stages);
-        cfg.pair_aware = pair_aware != 0;
-        if (targets && targets[0]) cfg.targets_filepath = targets;
-        if (report && report[0]) cfg.depth_report_filepath = report;
-        if (track && track[0]) cfg.depth_track_filepath = track;
-        if (ladder_levels != nullptr) cfg.coverage_ladder.assign(ladder_levels, ladder_levels + n_ladder_levels);
-        if (stratify && stratify[0]) cfg.stratify_by = stratify_from_name(stratify);
-        cfg.dedup = dedup != 0;
-        if (bed && bed[0]) cfg.bed_filepath = bed;
-        if (tsv && tsv[0]) cfg.tsv_filepath = tsv;
-        cfg.amplicons_by_reference = amplicons_by_reference != 0;
-        if (profile) throw std::invalid_argument("template-aware downsampling does not go together with a coverage profile");
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("template-aware downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no template-aware downsampling");
-        bam_api::BamApi api(in_path, cfg);
-        std::vector<bam_api::BAMReadId> kept = hip->solve_templates(max_coverage, api);
-        if (tstats) *tstats = hip->last_template_stats();
-        const std::uint32_t written = api.write_records(out_path, kept);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
-}
-
-// The template-aware flow under a cap per region: one template-aware ingest, one qmcp_hip_solve_templates_profile_host
-// call (QuasiMcpHipSolver::solve_templates_profile) with the regions in CSR form per reference of the file (n_refs + 1
-// offsets, as qmcp_host_downsample_bam_profile takes them; the caller has matched chroms to references and made the
-// regions disjoint), default_cap outside them and max_coverage as the scale of `stages`; the records of the kept
-// templates written with BamApi::write_records -- NO find_pairs.  per_reference goes to BamApiConfig as given, so that it
-// refuses its absence; a solver that grades by quality and offsets for another number of references are refused here.
-// tstats / qstats (may be NULL) receive the call's statistics.  Returns the number of records written; -1 on an unknown
-// solver, -3 out of memory, -4 with a message in err when the configuration is refused.
-std::int64_t qmcp_host_downsample_bam_templates_profile(const char* solver_name, const char* in_path, const char* out_path,
-                                                        const char* filtered_path, std::uint32_t max_coverage,
-                                                        std::uint32_t min_len, std::uint32_t min_mapq, int per_reference,
-                                                        int split_spliced, int include_secondary,
-                                                        const std::uint32_t* stages, std::uint32_t n_stages,
-                                                        const std::uint32_t* region_offsets,
-                                                        const std::uint32_t* region_starts,
-                                                        const std::uint32_t* region_ends, const std::uint32_t* region_caps,
-                                                        std::uint64_t n_refs, std::uint32_t default_cap,
-                                                        qmcp_hip_template_stats* tstats,
-                                                        qmcp_hip_template_profile_stats* qstats, char* err,
-                                                        std::size_t err_cap) {
-    qmcp::Solver* found = resolve(solver_name);
-    if (found == nullptr) return -1;
-    try {
-        bam_api::BamApiConfig cfg;
-        cfg.min_seq_length = min_len;
-        cfg.min_mapq = min_mapq;
-        cfg.per_reference = per_reference != 0;
-        cfg.template_aware = true;
-        cfg.split_spliced = split_spliced != 0;
-        cfg.include_secondary = include_secondary != 0;
-        if (stages != nullptr && n_stages) cfg.template_stages.assign(stages, stages + n_stages);
-        if (found->uses_quality_of_reads())
-            throw std::invalid_argument("template-aware downsampling does not take a solver that grades by quality");
-        auto* hip = dynamic_cast<qmcp::QuasiMcpHipSolver*>(found);
-        if (hip == nullptr) throw std::invalid_argument("this solver has no template-aware downsampling");
-        if (region_offsets == nullptr) throw std::invalid_argument("a cap table needs its region offsets");
-        const std::uint32_t n_reg = region_offsets[n_refs];
-        if (n_reg && (!region_starts || !region_ends || !region_caps))
-            throw std::invalid_argument("a cap table with regions needs their starts, ends and caps");
-        bam_api::BamApi api(in_path, cfg);
-        const std::vector<std::uint32_t> offs(region_offsets, region_offsets + n_refs + 1);
-        const std::vector<std::uint32_t> rs(region_starts, region_starts + n_reg), re(region_ends, region_ends + n_reg),
-            caps(region_caps, region_caps + n_reg);
-        std::vector<bam_api::BAMReadId> kept = hip->solve_templates_profile(max_coverage, api, offs, rs, re, caps, default_cap);
-        if (tstats) *tstats = hip->last_template_stats();
-        if (qstats) *qstats = hip->last_template_profile_stats();
-        const std::uint32_t written = api.write_records(out_path, kept);
-        if (filtered_path && filtered_path[0]) api.write_bam_api_filtered_out_reads(filtered_path);
-        return (std::int64_t)written;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
+// The file-to-file flow of App::execute (src/app.cpp:113-151), one entry for every mode: see
+// include/qmcp_host_request.h and downsample() above.
+std::int64_t qmcp_host_downsample_bam(const qmcp_host_downsample_request* request, std::int64_t* written_out,
+                                      std::uint64_t written_cap, qmcp_hip_ceiling_stats* ceiling_stats,
+                                      qmcp_hip_budget_stats* budget_stats, qmcp_hip_replicates_stats* replicates_stats,
+                                      qmcp_hip_template_stats* template_stats,
+                                      qmcp_hip_template_profile_stats* template_profile_stats, char* err, std::size_t err_cap) {
+    return guarded(err, err_cap, [&]() -> std::int64_t {
+        if (request == nullptr) throw std::invalid_argument("no request");
+        return downsample(*request, written_out, written_cap, ceiling_stats, budget_stats, replicates_stats, template_stats,
+                          template_profile_stats, err, err_cap);
+    });
 }
 
 // BamApiConfig's rule for targets, without a solve: 0 when BamApi accepts {per_reference, targets, padding}, -4 with its
@@ -1482,20 +898,15 @@ std::int64_t qmcp_host_downsample_bam_templates_profile(const char* solver_name,
 std::int64_t qmcp_host_check_targets_config(const char* in_path, const char* targets, int per_reference,
                                             std::uint32_t target_padding, std::uint64_t* n_regions, char* err,
                                             std::size_t err_cap) {
-    bam_api::BamApiConfig cfg;
-    cfg.per_reference = per_reference != 0;
-    if (targets && targets[0]) cfg.targets_filepath = targets;
-    cfg.target_padding = target_padding;
-    try {
+    return guarded(err, err_cap, [&]() -> std::int64_t {
+        bam_api::BamApiConfig cfg;
+        cfg.per_reference = per_reference != 0;
+        if (given(targets)) cfg.targets_filepath = targets;
+        cfg.target_padding = target_padding;
         bam_api::BamApi api(in_path, cfg);
         if (n_regions) *n_regions = api.has_targets() ? api.get_targets().starts.size() : 0;
         return 0;
-    } catch (const std::bad_alloc&) {
-        return -3;
-    } catch (const std::invalid_argument& e) {
-        copy_err(e.what(), err, err_cap);
-        return -4;
-    }
+    });
 }
 
 // The span the reference times as "solve took" (src/app.cpp:132-139) at the plugin boundary: a BamApi

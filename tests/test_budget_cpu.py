@@ -189,7 +189,7 @@ def test_entries_flag_and_stats_are_declared_listed_and_exported(pkg):
     assert declared == FIELDS == [name for name, _ in pkg.BudgetStats._fields_]
     assert "NOT proven" in text                     # the header says what is only observed under the flag
     host_nm = subprocess.run(["nm", "-D", "--defined-only", pkg.HOST_LIB_PATH], capture_output=True, text=True).stdout
-    assert re.search(r" T qmcp_host_downsample_bam_budget\b", host_nm)
+    assert re.search(r" T qmcp_host_downsample_bam\b", host_nm)
 
 
 def test_budget_stats_layout_matches_the_header_which_is_c99(pkg, tmp_path):
@@ -291,26 +291,29 @@ def test_downsample_bam_budget_refuses_what_it_does_not_go_together_with(pkg, tm
 
 
 def test_host_config_refuses_the_same_combinations(pkg, tmp_path):
-    """BamApiConfig's own refusals, reached through the C entry with everything handed on as given"""
+    """BamApiConfig's own refusals, reached through the C entry with everything handed on as given.  A request with
+    neither budget is no budget request at all, so that case names a budget report, which asks for the mode"""
     refs = [("chrA", 4000)]
     path = tmp_path / "in.bam"
     bam_py.write_bam(path, refs, tb.single_end_records(np.random.default_rng(2), refs, 50))
     bed = tmp_path / "t.bed"
     bed.write_text("chrA\t10\t500\n")
-    enc = lambda p: str(p).encode() if p is not None else None
 
-    def call(per_reference=1, has_reads=1, reads=20, fraction=-1.0, targets=None, report=None, track=None, ladder=None,
-             stratify=None, dedup=0, pair_aware=0, template_aware=0, ceiling=0, bed_=None, tsv=None, by_ref=0):
+    def call(solver=b"quasi-mcp-hip", per_reference=1, has_reads=1, reads=20, fraction=-1.0, targets=None, report=None,
+             track=None, ladder=None, stratify=None, dedup=0, pair_aware=0, template_aware=0, ceiling=0, bed_=None, tsv=None,
+             by_ref=0, budget_report=None):
         err = C.create_string_buffer(1024)
-        lv = np.asarray(ladder, np.uint32) if ladder is not None else None
-        n = pkg._host.qmcp_host_downsample_bam_budget(
-            b"quasi-mcp-hip", enc(path), enc(tmp_path / "no.bam"), None, 4, 0, 0, per_reference, has_reads, reads, fraction,
-            enc(targets), enc(report), enc(track), pkg._p32(lv), 0 if lv is None else lv.size, enc(stratify), dedup,
-            pair_aware, template_aware, ceiling, enc(bed_), enc(tsv), by_ref, None, None, err, 1024)
+        request = pkg._downsample_request(
+            solver_name=solver.decode(), in_path=path, out_path=tmp_path / "no.bam", max_coverage=4, min_len=0, min_mapq=0,
+            per_reference=per_reference, has_budget_reads=has_reads, budget_reads=reads, budget_fraction=fraction,
+            targets=targets, report=report, track=track, ladder_levels=ladder, stratify=stratify, dedup=dedup,
+            pair_aware=pair_aware, template_aware=template_aware, ceiling=ceiling, bed=bed_, tsv=tsv,
+            amplicons_by_reference=by_ref, budget_report=budget_report)
+        n = pkg._host.qmcp_host_downsample_bam(C.byref(request), None, 0, None, None, None, None, None, err, 1024)
         return n, err.value.decode()
 
     refused = [
-        (dict(per_reference=0), "per_reference"), (dict(has_reads=0), "needs budget_reads or budget_fraction"),
+        (dict(per_reference=0), "per_reference"), (dict(has_reads=0, budget_report=tmp_path / "b.tsv"), "needs budget_reads or budget_fraction"),
         (dict(fraction=0.5), "not both"), (dict(has_reads=0, fraction=1.5), "0 .. 1"),
         (dict(has_reads=0, fraction=float("nan")), "0 .. 1"),
         (dict(targets=bed), "targets"), (dict(report=tmp_path / "r.tsv"), "depth report"),
@@ -321,7 +324,5 @@ def test_host_config_refuses_the_same_combinations(pkg, tmp_path):
     for kw, word in refused:
         n, message = call(**kw)
         assert n == -4 and word in message, (kw, n, message)
-    assert pkg._host.qmcp_host_downsample_bam_budget(
-        b"no-such-solver", enc(path), enc(tmp_path / "no.bam"), None, 4, 0, 0, 1, 1, 20, -1.0, None, None, None, None, 0,
-        None, 0, 0, 0, 0, None, None, 0, None, None, None, 0) == -1
-    assert not (tmp_path / "no.bam").exists()
+    assert call(solver=b"no-such-solver")[0] == -1
+    assert not (tmp_path / "no.bam").exists() and not (tmp_path / "b.tsv").exists()

@@ -234,7 +234,8 @@ def test_a_report_of_the_file_flow_needs_per_reference(pkg, tmp_path):
     # the C++ mirror refuses the same configuration (BamApiConfig::depth_report_filepath without per_reference)
     import ctypes as C
     err = C.create_string_buffer(1024)
-    n = pkg._host.qmcp_host_downsample_bam_report(b"quasi-mcp-hip", str(path).encode(), str(tmp_path / "o.bam").encode(), None,
-                                                  10, 0, 0, None, None, -1, 0, 0, None, 0, 0,
-                                                  str(tmp_path / "d.tsv").encode(), 0, err, 1024)
+    request = pkg._downsample_request(solver_name="quasi-mcp-hip", in_path=path, out_path=tmp_path / "o.bam", max_coverage=10,
+                                      amplicon_mode=-1, per_reference=0, amplicons_by_reference=0, target_padding=0,
+                                      keep_off_target=0, report=tmp_path / "d.tsv", report_bins=0)
+    n = pkg._host.qmcp_host_downsample_bam(C.byref(request), None, 0, None, None, None, None, None, err, 1024)
     assert n == -4 and "per_reference" in err.value.decode()

@@ -279,10 +279,13 @@ def test_a_track_of_the_file_flow_is_refused_where_it_cannot_be_made(pkg, tmp_pa
     assert not out.exists() and not track.exists()
     # the C++ mirror refuses the same configurations (BamApiConfig::depth_track_filepath)
     err = C.create_string_buffer(1024)
-    entry = pkg._host.qmcp_host_downsample_bam_track
-    common = (b"quasi-mcp-hip", str(path).encode(), str(tmp_path / "o.bam").encode(), None, 10, 0, 0, None, None, -1)
-    n = entry(*common, 0, 0, None, 0, 0, None, 0, str(track).encode(), b"kept", 0, err, 1024)
-    assert n == -4 and "per_reference" in err.value.decode()
-    n = entry(*common, 1, 0, None, 0, 0, None, 0, str(track).encode(), b"short", 0, err, 1024)
-    assert n == -4 and "channel" in err.value.decode()
+    def entry(per_reference, channel):
+        request = pkg._downsample_request(solver_name="quasi-mcp-hip", in_path=path, out_path=tmp_path / "o.bam",
+                                          max_coverage=10, amplicon_mode=-1, per_reference=per_reference,
+                                          amplicons_by_reference=0, target_padding=0, keep_off_target=0, report_bins=0,
+                                          track=track, track_channel=channel, track_cap=0)
+        return pkg._host.qmcp_host_downsample_bam(C.byref(request), None, 0, None, None, None, None, None, err, 1024)
+
+    assert entry(0, "kept") == -4 and "per_reference" in err.value.decode()
+    assert entry(1, "short") == -4 and "channel" in err.value.decode()
     assert not (tmp_path / "o.bam").exists() and not track.exists()

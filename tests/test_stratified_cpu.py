@@ -199,16 +199,15 @@ def test_refused_combinations(pkg, bam, tmp_path):
     with pytest.raises(ValueError, match="stratify"):
         pkg.downsample_bam("quasi-mcp-hip", path, out, 20, per_reference=True, strata_report=tmp_path / "s.tsv")
     # BamApiConfig's own rules (std::invalid_argument, brought back as -4 and its message), without the Python checks
-    levels = np.array([5, 2], dtype=np.uint32)
-    p32 = levels.ctypes.data_as(C.POINTER(C.c_uint32))
     for per_ref, targets, report, ladder, word in [(0, None, None, None, "needs per_reference"),
-                                                   (1, b"t.bed", None, None, "does not take targets"),
-                                                   (1, None, b"r.tsv", None, "does not take a depth report"),
-                                                   (1, None, None, p32, "does not take a coverage ladder")]:
+                                                   (1, "t.bed", None, None, "does not take targets"),
+                                                   (1, None, "r.tsv", None, "does not take a depth report"),
+                                                   (1, None, None, [5, 2], "does not take a coverage ladder")]:
         err = C.create_string_buffer(1024)
-        rc = pkg._host.qmcp_host_downsample_bam_stratified(b"quasi-mcp-hip", str(path).encode(), str(out).encode(), None,
-                                                           20, 0, 0, per_ref, b"strand", targets, report, ladder,
-                                                           2 if ladder else 0, None, err, 1024)
+        request = pkg._downsample_request(solver_name="quasi-mcp-hip", in_path=path, out_path=out, max_coverage=20,
+                                          per_reference=per_ref, stratify="strand", targets=targets, report=report,
+                                          ladder_levels=ladder)
+        rc = pkg._host.qmcp_host_downsample_bam(C.byref(request), None, 0, None, None, None, None, None, err, 1024)
         assert rc == -4 and word in err.value.decode(), err.value
     assert not out.exists()
     assert pkg.solver_names() == ["quasi-mcp-hip"]      # the registry lists what it listed before

@@ -261,7 +261,7 @@ def test_entries_are_declared_listed_and_exported(pkg):
     for word in ("c_j(p) = ceil(cap(p) * T_j / M)", "Identities: (1)", "Not claimed"):
         assert word in text
     nm_host = subprocess.run(["nm", "-D", "--defined-only", pkg.HOST_LIB_PATH], capture_output=True, text=True).stdout
-    assert re.search(r" T qmcp_host_downsample_bam_templates_profile\b", nm_host)
+    assert re.search(r" T qmcp_host_downsample_bam\b", nm_host)
 
 
 def test_template_profile_stats_layout_matches_the_header(pkg, tmp_path):
