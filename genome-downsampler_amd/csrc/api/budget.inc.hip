@@ -1,14 +1,14 @@
 // budget.inc.hip -- part of qmcp_api.hip (one translation unit).
 // qmcp_hip_solve_budget_host / _device: the deepest coverage M* in 0 .. top whose by-contig solve keeps at most
 // budget_reads reads (after pair completion under QMCP_BUDGET_WHOLE_PAIRS), and that solve's mask.
-//   1. group_reads and plan_contig_batches as the by-contig call: once per call
+//   1. group_by_contig (api/by_contig.inc.hip): once per call
 //   2. per batch with reads, before the first probe: its columns gathered, its per-position depth built by the launches
 //      of coverage_common (k_prepare's start counts, the two scans, the end counts, k_coverage), k_budget_tally over it
 //   3. k_budget_curve; the curve, the largest depth and the sum of the depths come back in one copy
-//   4. budget_plan.h picks the probes; a probe is solve_gathered_batch at M over every batch into a cleared input-order
-//      mask, then k_budget_finish under the flag.  Two masks: the one a probe scatters into and the one of the best
+//   4. budget_plan.h picks the probes; a probe is run_batches with a PlainSolver at M into a cleared input-order mask,
+//      then k_budget_finish under the flag.  Two masks: the one a probe scatters into and the one of the best
 //      feasible probe; they swap roles when a probe is feasible, so nothing is solved twice
-// A call of one batch gathers its columns once, in step 2, for all probes.
+// A call of one batch with reads gathers its columns once, in step 2, for all probes: its probes are solve_scatter_batch.
 // Buffers: bg_acc (BudgetWord words | curve | histogram), bg_mask; step 2 passes through the solve's own arena (cstart,
 // boff, ecnt, eoff, cov) before the first solve and holds nothing of it afterwards.
 namespace {
@@ -64,8 +64,6 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     bs.budget = budget;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (bstats) *bstats = bs;
-    const uint32_t n = (uint32_t)n64;
-    const uint32_t n_groups = n_contigs + 1;  // the contigs, then the unplaced reads
     const size_t words = (size_t)((n64 + 63) / 64);
     const bool whole_pairs = (flags & QMCP_BUDGET_WHOLE_PAIRS) != 0;
     hipStream_t st = c->stream;
@@ -78,36 +76,10 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     unsigned long long* d_hist = d_curve + H;
     HIP_TRY(hipMemsetAsync(d_acc, 0, acc_words * sizeof(unsigned long long), st));
 
-    // 1: keys, grouping, bounds (the mask it clears is the budget's own: a refused call leaves d_mask alone)
-    const uint32_t passes = std::max(1u, (bit_width(n_contigs) + 7) / 8);
-    std::vector<uint32_t> offs;
-    const void* sorted = nullptr;
-    uint32_t err = 0;
-    TRY(group_reads(
-        c, n64, lengths, n_contigs, n_groups, passes,
-        {{"k_radix_hist_rec(by contig)", "scan_radix_hist(by contig, 3 kernels)", "k_radix_scatter_rec(by contig)"},
-         "k_bc_bounds"},
-        [&] {
-            KernelSpan sp(c, "k_bc_keys");
-            qmcp::launch_bc_keys(st, d_starts, d_ends, d_ids, n, (const uint32_t*)c->bc_len.p, n_contigs,
-                                 (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
-        },
-        (uint64_t*)c->bg_mask.p, offs, &sorted, &err));
-    if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
-    if (err & 2u) return fail(QMCP_EREAD, "a read has start > end or end >= its contig's length");
-    std::vector<uint64_t> counts(n_contigs);
-    for (uint32_t k = 0; k < n_contigs; ++k) counts[k] = offs[k + 1] - offs[k];
-    std::vector<qmcp::ContigBatch> batches;
-    uint32_t bad = 0;
-    if (qmcp::plan_contig_batches(counts.data(), lengths, n_contigs, batches, &bad) != QMCP_OK)
-        return fail(QMCP_ERANGE,
-                    "contig %u alone exceeds one call's limits: %llu reads (at most 2^30), %u positions (at most 2^31 - 2)",
-                    bad, (unsigned long long)counts[bad], lengths[bad]);
-    size_t largest = 0;
-    TRY(reserve_batch_buffers(c, batches, &largest));
-    const uint64_t placed = offs[n_contigs];
-    size_t solving = 0;  // batches with reads
-    for (const qmcp::ContigBatch& bt : batches) solving += bt.n_reads != 0;
+    // 1: the grouping (the mask it clears is the budget's own: a refused call leaves d_mask alone)
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, (uint64_t*)c->bg_mask.p, g));
+    const uint64_t placed = g.offs[n_contigs];
 
     // 2-3: the depth histogram over every batch, the curve
     std::vector<std::unique_ptr<EventPair>> evs;  // one per k_budget_tally, one for k_budget_curve
@@ -116,20 +88,13 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
         return evs.back()->a && evs.back()->b ? evs.back().get() : nullptr;
     };
     uint32_t span_max = 0;
-    std::vector<uint64_t> roff;
-    for (const qmcp::ContigBatch& bt : batches) {
-        if (bt.n_reads == 0) continue;  // (no read: no depth)
-        const uint32_t nb = (uint32_t)bt.n_reads;
-        const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;
-        {
-            KernelSpan sp(c, "k_bc_gather");
-            qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
-        }
-        HIP_TRY(hipGetLastError());
-        batch_roff(offs.data() + bt.first_contig, bt.n_contigs, roff);
+    BatchView v;
+    for (size_t b : g.live) {  // (no read: no depth)
+        g.view(b, v);
+        TRY(gather_batch(c, v, d_starts, d_ends));
         uint32_t ltot = 0;
-        TRY(budget_batch_depth(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, roff.data(),
-                               lengths + bt.first_contig, bt.n_contigs, nb, &ltot, &span_max));
+        TRY(budget_batch_depth(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.roff.data(), v.lengths,
+                               v.n_contigs, v.nb, &ltot, &span_max));
         EventPair* ev = bracket();
         if (!ev) return fail(QMCP_EHIP, "event creation failed");
         HIP_TRY(hipEventRecord(ev->a, st));
@@ -179,19 +144,13 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
         const uint32_t M = plan.next();
         uint64_t* pm = masks[scratch];
         if (words) HIP_TRY(hipMemsetAsync(pm, 0, words * sizeof(uint64_t), st));  // (k_bc_scatter_mask ORs)
+        PlainSolver plain(M);
         qmcp_hip_stats sum;
-        std::memset(&sum, 0, sizeof(sum));
-        bool first = true;
-        for (size_t b = 0; b < batches.size(); ++b) {
-            const qmcp::ContigBatch& bt = batches[b];
-            sum.n_contigs += bt.n_contigs;
-            sum.total_length += bt.positions;
-            if (bt.n_reads == 0) continue;
-            const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;
-            TRY(solve_gathered_batch(c, bsorted, (uint32_t)bt.n_reads, d_starts, d_ends, offs.data() + bt.first_contig, lengths,
-                                     bt.first_contig, bt.n_contigs, M, nullptr, pm, roff, sum, first, b == largest,
-                                     /*gather=*/solving > 1));
-            first = false;
+        if (g.live.size() > 1) {
+            TRY(run_batches(c, g, plain, pm, sum));
+        } else {  // v is the one batch with reads, if any, and bc_starts / bc_ends hold its columns since step 2
+            start_sum(g, sum);
+            if (!g.live.empty()) TRY(solve_scatter_batch(c, v, plain, pm, sum, true, true));
         }
         uint64_t count = sum.n_kept;
         if (whole_pairs) {

@@ -1,39 +1,20 @@
 // by_contig.inc.hip -- part of qmcp_api.hip (one translation unit).
-// qmcp_hip_solve_by_contig_host / _device: reads of several contigs in any order, one contig id per read.
-//   1-3. group_reads: k_bc_keys checks every read against its contig and writes the sort keys (contig id; n_contigs for
-//      unplaced reads); the stable record radix (api/radix_passes.inc.hip) groups {key, read index} by key, one pass per
-//      8 bits of n_contigs, into the context's own record buffers (the solves below never touch them); k_bc_bounds turns
-//      the sorted keys into each contig's run; the bounds and the validation word come back to the host
-//   4. by_contig_plan.h packs the contigs into batches within one call's limits; per batch solve_gathered_batch: its
-//      columns gathered in grouped order, solved by the ordinary multi-contig solve, its mask ORed back into input order
-// Grouping happens once; a batch only gathers its own reads.
-// A coverage ladder (api/ladder.inc.hip) is this call with further levels run inside each batch, on its gathered columns.
-// A coverage profile (api/profile.inc.hip) is this call with every batch solved under its own regions' caps; a ceiling
-// solve (api/ceiling.inc.hip) is a profile whose batches select the DROPPED reads, complemented once the call is through.
-// A pair-aware solve (api/pairs.inc.hip) is this call at its first target, with the further stages run over all batches
-// once the last batch's mask is in place.
-// A replicate split (api/replicates.inc.hip) is this call at its first coverage, with the further replicates run over all
-// batches on the reads still free.
-// A budget solve (api/budget.inc.hip) is this call's grouping and batches under a search of its own: several whole solves,
-// each over every batch, at the coverages budget_plan.h picks.
+// qmcp_hip_solve_by_contig_host / _device: reads of several contigs in any order, one contig id per read.  The pieces, which
+// every entry of the by-contig family (ladder, profile, ceiling, budget, pairs, templates, replicates; stratified with keys
+// and a plan of its own) puts together in a flow of its own:
+//   group_reads      a key kernel checks every read and writes its sort key; the stable record radix
+//                    (api/radix_passes.inc.hip) groups {key, read index} by key into the context's own record buffers (the
+//                    solves never touch them); k_bc_bounds turns the sorted keys into each group's run; the bounds and the
+//                    validation word come back to the host
+//   group_by_contig  the grouping as a value (GroupedReads), once per call: group_reads around k_bc_keys (key: the contig
+//                    id; n_contigs for unplaced reads), by_contig_plan.h's batches within one call's limits, the gathered
+//                    columns and the batch mask sized for the largest batch
+//   BatchView        one batch: its records, contigs' lengths and read offsets; on request the 32-bit offset tables
+//   run_batches      per batch with reads: gather_batch (its columns in grouped order), solve_scatter_batch (a BatchSolver
+//                    -- PlainSolver is the ordinary multi-contig solve at M -- fills the batch mask, which is ORed back
+//                    into input order; the batch's stats join the call's), then the solver's after_batch
+// The by-contig call itself is group_by_contig, run_batches with a PlainSolver, and the final wait.
 namespace {
-
-struct LadderRun;
-int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, uint32_t nb, const uint64_t* roff,
-                           const uint32_t* lengths, uint32_t n_contigs);
-struct ProfileRun;
-int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
-                        const uint64_t* roff, const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs,
-                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st);
-struct PairRun;
-int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
-                      const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
-                      const uint32_t* lengths, uint64_t n64, uint64_t* d_mask, const qmcp_hip_stats& first);
-struct ReplicatesRun;
-int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, const std::vector<uint32_t>& offs,
-                     const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
-                     const uint32_t* d_ids, const uint32_t* lengths, uint32_t n_contigs_all, uint64_t n64, uint64_t* d_mask,
-                     const qmcp_hip_stats& first);
 
 // the batches' stats as one: counts and times summed, the route of the batch with the most reads
 void add_batch_stats(qmcp_hip_stats& s, const qmcp_hip_stats& b, bool first, bool largest) {
@@ -129,110 +110,162 @@ int reserve_batch_buffers(qmcp_hip_ctx* c, const std::vector<Batch>& batches, si
     return QMCP_OK;
 }
 
-// a batch's contig_read_offsets from the grouping's offsets: goffs points at its first group, n_contigs + 1 are read
-void batch_roff(const uint32_t* goffs, uint32_t n_contigs, std::vector<uint64_t>& roff) {
-    roff.resize((size_t)n_contigs + 1);
-    for (uint32_t k = 0; k <= n_contigs; ++k) roff[k] = goffs[k] - goffs[0];
+// One batch of grouped reads as its consumers see it: nb > 0 records, contigs first_contig .. + n_contigs.
+struct BatchView {
+    const void* records = nullptr;  // the batch's {key, index} records
+    uint32_t nb = 0, first_contig = 0, n_contigs = 0;
+    uint64_t positions = 0;
+    const uint32_t* lengths = nullptr;     // of the batch's contigs
+    std::vector<uint64_t> roff;            // contig_read_offsets, n_contigs + 1
+    std::vector<uint32_t> offs32, poff32;  // after tables32(): roff and the contigs' position offsets in 32 bits
+    void tables32() {  // (a batch holds at most 2^30 reads and 2^31 - 2 positions)
+        offs32.assign(roff.begin(), roff.end());
+        poff32.assign(roff.size(), 0);
+        for (uint32_t k = 0; k < n_contigs; ++k) poff32[k + 1] = poff32[k] + lengths[k];
+    }
+};
+
+// goffs points at the offsets of the batch's first group in the grouping's table
+template <typename Batch>
+void batch_view(const void* sorted, const uint32_t* goffs, const uint32_t* lengths, const Batch& bt, BatchView& v) {
+    v.records = (const uint32_t*)sorted + 2 * bt.first_read;
+    v.nb = (uint32_t)bt.n_reads;
+    v.first_contig = bt.first_contig;
+    v.n_contigs = bt.n_contigs;
+    v.positions = bt.positions;
+    v.lengths = lengths + bt.first_contig;
+    v.roff.resize((size_t)bt.n_contigs + 1);
+    for (uint32_t k = 0; k <= bt.n_contigs; ++k) v.roff[k] = goffs[k] - goffs[0];
 }
 
-// One batch of grouped reads (nb > 0 records at bsorted; contigs first_contig .. + n_contigs, offsets from goffs): its
-// columns gathered in grouped order, solved by the ordinary multi-contig solve at M (under `profile`'s caps when given),
-// its mask ORed back into input order, its stats added to `sum`.  roff is left holding the batch's read offsets.
-// gather == false: bc_starts / bc_ends hold this batch's columns already (a budget call of one batch, between its probes).
-int solve_gathered_batch(qmcp_hip_ctx* c, const void* bsorted, uint32_t nb, const uint32_t* d_starts, const uint32_t* d_ends,
-                         const uint32_t* goffs, const uint32_t* lengths, uint32_t first_contig, uint32_t n_contigs, uint32_t M,
-                         ProfileRun* profile, uint64_t* d_mask, std::vector<uint64_t>& roff, qmcp_hip_stats& sum, bool first,
-                         bool largest, bool gather = true) {
-    hipStream_t st = c->stream;
-    const uint32_t* bs_starts = (const uint32_t*)c->bc_starts.p;
-    const uint32_t* bs_ends = (const uint32_t*)c->bc_ends.p;
-    if (gather) {
+// What one grouping by contig produced, and what every consumer of it needs.
+struct GroupedReads {
+    const uint32_t *d_starts = nullptr, *d_ends = nullptr, *d_ids = nullptr;  // the call's device columns, input order
+    const uint32_t* lengths = nullptr;                                        // host
+    uint32_t n_contigs = 0;
+    uint64_t n64 = 0, total_length = 0;
+    const void* sorted = nullptr;  // the grouped {key, index} records
+    std::vector<uint32_t> offs;    // each contig's run in them, then the unplaced reads'
+    std::vector<qmcp::ContigBatch> batches;
+    std::vector<size_t> live;  // the batches with reads
+    size_t largest = 0;        // the batch with the most reads: its route is the call's
+    void view(size_t b, BatchView& v) const {
+        batch_view(sorted, offs.data() + batches[b].first_contig, lengths, batches[b], v);
+    }
+};
+
+// Steps 1-4 of a by-contig call up to its first batch: the size checks, the grouping (mask_to_clear is cleared before the
+// reads are validated), the device-found refusals, the batches, the buffers of the largest one.
+int group_by_contig(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids, uint64_t n64,
+                    const uint32_t* lengths, uint32_t n_contigs, uint64_t* mask_to_clear, GroupedReads& g) {
+    if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
+    if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
+    if (n64 > (1ull << 31))
+        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n64);
+    g = GroupedReads{d_starts, d_ends, d_ids, lengths, n_contigs, n64};
+    const uint32_t passes = std::max(1u, (bit_width(n_contigs) + 7) / 8);  // keys go up to n_contigs
+    uint32_t err = 0;
+    TRY(group_reads(
+        c, n64, lengths, n_contigs, n_contigs + 1 /* the contigs, then the unplaced reads */, passes,
+        {{"k_radix_hist_rec(by contig)", "scan_radix_hist(by contig, 3 kernels)", "k_radix_scatter_rec(by contig)"},
+         "k_bc_bounds"},
+        [&] {
+            KernelSpan sp(c, "k_bc_keys");
+            qmcp::launch_bc_keys(c->stream, d_starts, d_ends, d_ids, (uint32_t)n64, (const uint32_t*)c->bc_len.p, n_contigs,
+                                 (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
+        },
+        mask_to_clear, g.offs, &g.sorted, &err));
+    if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
+    if (err & 2u) return fail(QMCP_EREAD, "a read has start > end or end >= its contig's length");
+    std::vector<uint64_t> counts(n_contigs);
+    for (uint32_t k = 0; k < n_contigs; ++k) counts[k] = g.offs[k + 1] - g.offs[k];
+    uint32_t bad = 0;
+    if (qmcp::plan_contig_batches(counts.data(), lengths, n_contigs, g.batches, &bad) != QMCP_OK)
+        return fail(QMCP_ERANGE,
+                    "contig %u alone exceeds one call's limits: %llu reads (at most 2^30), %u positions (at most 2^31 - 2)",
+                    bad, (unsigned long long)counts[bad], lengths[bad]);
+    TRY(reserve_batch_buffers(c, g.batches, &g.largest));
+    for (size_t b = 0; b < g.batches.size(); ++b) {
+        g.total_length += g.batches[b].positions;
+        if (g.batches[b].n_reads != 0) g.live.push_back(b);
+    }
+    return QMCP_OK;
+}
+
+// What solves one gathered batch: its columns are in bc_starts / bc_ends in grouped order, its mask goes to bc_mask.
+struct BatchSolver {
+    virtual ~BatchSolver() {}
+    virtual int solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* bs) = 0;
+    // once the batch's mask is in input order and its stats are added (the ladder's further levels)
+    virtual int after_batch(qmcp_hip_ctx*, BatchView&) { return QMCP_OK; }
+};
+
+// the ordinary multi-contig solve at M
+struct PlainSolver : BatchSolver {
+    uint32_t M;
+    explicit PlainSolver(uint32_t m) : M(m) {}
+    int solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* bs) override {
+        return solve_on_device(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.roff.data(), v.lengths,
+                               v.n_contigs, v.nb, M, (uint64_t*)c->bc_mask.p, bs);
+    }
+};
+
+// the batch's columns, in grouped order, into bc_starts / bc_ends
+int gather_batch(qmcp_hip_ctx* c, const BatchView& v, const uint32_t* d_starts, const uint32_t* d_ends) {
+    {
         KernelSpan sp(c, "k_bc_gather");
-        qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
+        qmcp::launch_bc_gather(c->stream, v.records, v.nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p,
+                               (uint32_t*)c->bc_ends.p);
     }
     HIP_TRY(hipGetLastError());
-    batch_roff(goffs, n_contigs, roff);
+    return QMCP_OK;
+}
+
+// a gathered batch solved, its mask ORed back into input order, its stats added to `sum`
+int solve_scatter_batch(qmcp_hip_ctx* c, BatchView& v, BatchSolver& solver, uint64_t* d_mask, qmcp_hip_stats& sum, bool first,
+                        bool largest) {
     qmcp_hip_stats bs;
     std::memset(&bs, 0, sizeof(bs));
-    if (profile)
-        TRY(profile_solve_batch(c, *profile, bsorted, bs_starts, bs_ends, roff.data(), lengths, first_contig, n_contigs, nb,
-                                (uint64_t*)c->bc_mask.p, &bs));
-    else
-        TRY(solve_on_device(c, bs_starts, bs_ends, roff.data(), lengths + first_contig, n_contigs, nb, M,
-                            (uint64_t*)c->bc_mask.p, &bs));
+    TRY(solver.solve(c, v, &bs));
     {
         KernelSpan sp(c, "k_bc_scatter_mask");
-        qmcp::launch_bc_scatter_mask(st, (const uint64_t*)c->bc_mask.p, bsorted, nb, d_mask);
+        qmcp::launch_bc_scatter_mask(c->stream, (const uint64_t*)c->bc_mask.p, v.records, v.nb, d_mask);
     }
     HIP_TRY(hipGetLastError());
     add_batch_stats(sum, bs, first, largest);
     return QMCP_OK;
 }
 
+// a call's stats before its first batch: every contig counts, those of batches without reads included
+void start_sum(const GroupedReads& g, qmcp_hip_stats& sum) {
+    std::memset(&sum, 0, sizeof(sum));
+    sum.n_contigs = g.n_contigs;
+    sum.total_length = g.total_length;
+}
+
+// The batch loop: every batch with reads gathered, solved by `solver`, scattered into d_mask (cleared by the grouping:
+// the scatter ORs); `sum` takes the call's stats.  (Batches without reads solve nothing: empty contigs keep nothing.)
+int run_batches(qmcp_hip_ctx* c, const GroupedReads& g, BatchSolver& solver, uint64_t* d_mask, qmcp_hip_stats& sum) {
+    start_sum(g, sum);
+    BatchView v;
+    for (size_t b : g.live) {
+        g.view(b, v);
+        TRY(gather_batch(c, v, g.d_starts, g.d_ends));
+        TRY(solve_scatter_batch(c, v, solver, d_mask, sum, b == g.live.front(), b == g.largest));
+        TRY(solver.after_batch(c, v));
+    }
+    return QMCP_OK;
+}
+
 int solve_by_contig_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                               uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, uint32_t M, uint64_t* d_mask,
-                              qmcp_hip_stats* stats, LadderRun* ladder = nullptr,
-                              ProfileRun* profile = nullptr /* then M is the default cap */,
-                              PairRun* pairs = nullptr /* then M is the first stage's target */,
-                              ReplicatesRun* replicates = nullptr /* then M is the first replicate's coverage */) {
-    if (!lengths || n_contigs == 0) return fail(QMCP_EINVAL, "contig_lengths missing or n_contigs == 0");
-    if (n_contigs > (1u << 24)) return fail(QMCP_ERANGE, "n_contigs %u exceeds 2^24 per by-contig call", n_contigs);
-    if (n64 > (1ull << 31))
-        return fail(QMCP_ERANGE, "n_reads %llu exceeds 2^31 per by-contig call", (unsigned long long)n64);
-    const uint32_t n = (uint32_t)n64;
-    const uint32_t n_groups = n_contigs + 1;  // the contigs, then the unplaced reads
-    hipStream_t st = c->stream;
-
-    // 1-3: keys, grouping, bounds
-    const uint32_t passes = std::max(1u, (bit_width(n_contigs) + 7) / 8);  // keys go up to n_contigs
-    std::vector<uint32_t> offs;
-    const void* sorted = nullptr;
-    uint32_t err = 0;
-    TRY(group_reads(
-        c, n64, lengths, n_contigs, n_groups, passes,
-        {{"k_radix_hist_rec(by contig)", "scan_radix_hist(by contig, 3 kernels)", "k_radix_scatter_rec(by contig)"},
-         "k_bc_bounds"},
-        [&] {
-            KernelSpan sp(c, "k_bc_keys");
-            qmcp::launch_bc_keys(st, d_starts, d_ends, d_ids, n, (const uint32_t*)c->bc_len.p, n_contigs,
-                                 (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
-        },
-        d_mask, offs, &sorted, &err));
-    if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
-    if (err & 2u) return fail(QMCP_EREAD, "a read has start > end or end >= its contig's length");
-
-    // 4: batches
-    std::vector<uint64_t> counts(n_contigs);
-    for (uint32_t k = 0; k < n_contigs; ++k) counts[k] = offs[k + 1] - offs[k];
-    std::vector<qmcp::ContigBatch> batches;
-    uint32_t bad = 0;
-    if (qmcp::plan_contig_batches(counts.data(), lengths, n_contigs, batches, &bad) != QMCP_OK)
-        return fail(QMCP_ERANGE,
-                    "contig %u alone exceeds one call's limits: %llu reads (at most 2^30), %u positions (at most 2^31 - 2)",
-                    bad, (unsigned long long)counts[bad], lengths[bad]);
-    size_t largest = 0;
-    TRY(reserve_batch_buffers(c, batches, &largest));
+                              qmcp_hip_stats* stats) {
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask, g));
+    PlainSolver plain(M);
     qmcp_hip_stats sum;
-    std::memset(&sum, 0, sizeof(sum));
-    bool first = true;
-    std::vector<uint64_t> roff;
-    for (size_t b = 0; b < batches.size(); ++b) {
-        const qmcp::ContigBatch& bt = batches[b];
-        sum.n_contigs += bt.n_contigs;
-        sum.total_length += bt.positions;
-        if (bt.n_reads == 0) continue;  // (nothing to solve: empty contigs keep nothing)
-        const uint32_t nb = (uint32_t)bt.n_reads;
-        const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
-        TRY(solve_gathered_batch(c, bsorted, nb, d_starts, d_ends, offs.data() + bt.first_contig, lengths, bt.first_contig,
-                                 bt.n_contigs, M, profile, d_mask, roff, sum, first, b == largest));
-        if (ladder) TRY(ladder_levels_of_batch(c, *ladder, bsorted, nb, roff.data(), lengths + bt.first_contig, bt.n_contigs));
-        first = false;
-    }
-    if (pairs) TRY(pair_later_stages(c, *pairs, sorted, offs, batches, d_starts, d_ends, lengths, n64, d_mask, sum));
-    if (replicates)
-        TRY(replicates_later(c, *replicates, sorted, offs, batches, d_starts, d_ends, d_ids, lengths, n_contigs, n64, d_mask,
-                             sum));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(run_batches(c, g, plain, d_mask, sum));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     collect_spans(c);
     if (stats) *stats = sum;
     return QMCP_OK;

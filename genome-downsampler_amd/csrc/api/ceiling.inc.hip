@@ -1,21 +1,16 @@
 // ceiling.inc.hip -- part of qmcp_api.hip (one translation unit).
 // qmcp_hip_solve_ceiling_host / _device: kept(p) <= cap(p) everywhere with the most reads kept.  kept <= cap is dropped >=
 // cov - cap, and keeping the most is dropping the fewest: the dropped set D is the canonical selection under need(p) =
-// max(0, cov(p) - cap(p)), and need <= cov, so the greedy never runs dry.  The call is the profile call (api/profile.inc.hip:
-// the by-contig grouping and batches, the cap table, capped_solve_batch) with
+// max(0, cov(p) - cap(p)), and need <= cov, so the greedy never runs dry.  The call is the profile's flow (group_by_contig,
+// run_batches, the cap table and capped_solve_batch of api/profile.inc.hip) with CeilingSolver as the batch solver:
 //   1. per batch, k_ceiling_need as the CappedNeed: the dual need, its cut bit where need(p) == cov(p), and the largest
 //      need, which is what plans the sweep (CeilingNeed::plan_cap) -- a batch that is nowhere above its caps queues none
 //   2. per batch, once k_mark has written D in grouped order: k_pair_credit_events + scan give depth_D(p), k_ceiling_check
-//      holds cov - depth_D against the caps; the by-contig layer then ORs D into input order
+//      holds cov - depth_D against the caps; the batch loop then ORs D into input order
 //   3. once, k_ceiling_finish over the input-order mask: keep = placed & ~D, mates joined to D first under
 //      QMCP_CEILING_WHOLE_PAIRS
 // Buffers: the profile's pf_need / pf_tab, and cl_* (a batch's position offsets, depth_D and its spine, the counters).
 namespace {
-
-struct CeilingRun {
-    float ms_check = 0.f;
-    std::vector<uint32_t> poff32;  // the batch's position offsets
-};
 
 // need[] of the dropped set: the batch's regions as ProfileNeed uploads them, through k_ceiling_need
 struct CeilingNeed : ProfileNeed {
@@ -43,22 +38,29 @@ struct CeilingNeed : ProfileNeed {
     uint32_t plan_cap(uint32_t) const override { return std::max((uint32_t)largest, 1u); }
 };
 
-int ceiling_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
-                        const uint64_t* roff, const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs,
-                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st_out) {
-    CeilingRun& cl = *pf.ceiling;
+// a batch's dropped set D into the batch mask, and the kept depth held against the caps
+struct CeilingSolver : BatchSolver {
+    ProfileRun& pf;
+    float ms_check = 0.f;
+    explicit CeilingSolver(ProfileRun& run) : pf(run) {}
+    int solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* bs) override;
+};
+
+int CeilingSolver::solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* st_out) {
     const qmcp::CapTable& tab = *pf.tab;
-    const uint32_t* lengths = lengths_all + first_contig;
+    const uint32_t first_contig = v.first_contig, n_contigs = v.n_contigs, nb = v.nb;
+    const uint32_t* d_starts = (const uint32_t*)c->bc_starts.p;
+    const uint32_t* d_ends = (const uint32_t*)c->bc_ends.p;
+    uint64_t* d_mask = (uint64_t*)c->bc_mask.p;
     hipStream_t st = c->stream;
-    qmcp::batch_cap_table(tab, lengths_all, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
+    qmcp::batch_cap_table(tab, v.lengths - first_contig, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
     CeilingNeed nd(pf, tab.offs[first_contig + n_contigs] - tab.offs[first_contig]);
     bool swept = false;
     // (max_cap only short-circuits at 0 here: the windows come from CeilingNeed::plan_cap)
-    TRY(capped_solve_batch(c, nd, 1u, d_starts, d_ends, roff, lengths, n_contigs, n64, d_mask, st_out, &swept));
+    TRY(capped_solve_batch(c, nd, 1u, d_starts, d_ends, v.roff.data(), v.lengths, n_contigs, nb, d_mask, st_out, &swept));
     pf.ms_profile += nd.ms;
-    cl.poff32.assign((size_t)n_contigs + 1, 0);
-    for (uint32_t k = 0; k < n_contigs; ++k) cl.poff32[k + 1] = cl.poff32[k] + lengths[k];  // (at most 2^31 - 2 positions)
-    const uint32_t ltot = cl.poff32[n_contigs], nb = (uint32_t)n64;
+    v.tables32();
+    const uint32_t ltot = v.poff32[n_contigs];
     if (nb == 0 || ltot == 0) return QMCP_OK;
     // the depth of D on the batch's axis, and the kept depth against the caps: boff, eoff and pf_tab are the solve's
     const uint32_t pad = qmcp::pair_credit_pad();
@@ -70,10 +72,10 @@ int ceiling_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, co
     HIP_TRY(hipEventRecord(ev.a, st));
     HIP_TRY(hipMemsetAsync(c->cl_depth.p, 0, ((size_t)ltot + pad + 4) * sizeof(uint32_t), st));
     if (swept) {  // (no sweep: D is empty, the zeroed depth stands)
-        HIP_TRY(hipMemcpyAsync(c->cl_poff.p, cl.poff32.data(), ((size_t)n_contigs + 1) * sizeof(uint32_t),
+        HIP_TRY(hipMemcpyAsync(c->cl_poff.p, v.poff32.data(), ((size_t)n_contigs + 1) * sizeof(uint32_t),
                                hipMemcpyHostToDevice, st));
         KernelSpan sp(c, "k_pair_credit_events + scan(ceiling)");
-        qmcp::launch_pair_credit_events(st, bsorted, nb, d_mask, d_starts, d_ends, (const uint32_t*)c->cl_poff.p, first_contig,
+        qmcp::launch_pair_credit_events(st, v.records, nb, d_mask, d_starts, d_ends, (const uint32_t*)c->cl_poff.p, first_contig,
                                         (uint32_t*)c->cl_depth.p);
         qmcp::launch_exclusive_scan(st, (const uint32_t*)c->cl_depth.p, ltot + pad, (uint32_t*)c->cl_depth.p,
                                     (uint32_t*)c->cl_spine.p, false);
@@ -88,7 +90,7 @@ int ceiling_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, co
     HIP_TRY(hipEventRecord(ev.b, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));  // (the copy of poff32 is done, the time can be read)
-    cl.ms_check += elapsed(ev.a, ev.b);
+    ms_check += elapsed(ev.a, ev.b);
     return QMCP_OK;
 }
 
@@ -117,12 +119,17 @@ int solve_ceiling_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     TRY(ensure(c, c->cl_stat, qmcp::kCeilingStatWords * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(c->cl_stat.p, 0, qmcp::kCeilingStatWords * sizeof(unsigned long long), st));
     ProfileRun pf;
-    CeilingRun cl;
     pf.tab = &tab;
     pf.default_cap = default_cap;
-    pf.ceiling = &cl;
-    // d_mask leaves this call holding D in input order
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, default_cap, d_mask, stats, nullptr, &pf));
+    // the batch loop leaves d_mask holding D in input order
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask, g));
+    CeilingSolver dropped(pf);
+    qmcp_hip_stats sum;
+    TRY(run_batches(c, g, dropped, d_mask, sum));
+    HIP_TRY(hipStreamSynchronize(st));
+    collect_spans(c);
+    if (stats) *stats = sum;
     EventPair ev(c);
     if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
     HIP_TRY(hipEventRecord(ev.a, st));
@@ -146,7 +153,7 @@ int solve_ceiling_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     cs.short_bases = w[qmcp::kCeilShortBases];
     cs.excess_positions = w[qmcp::kCeilExcessPositions];
     cs.max_kept_depth = (uint32_t)w[qmcp::kCeilMaxKept];
-    cs.ms_ceiling = pf.ms_profile + cl.ms_check + elapsed(ev.a, ev.b);
+    cs.ms_ceiling = pf.ms_profile + dropped.ms_check + elapsed(ev.a, ev.b);
     if (cstats) *cstats = cs;
     return QMCP_OK;
 }

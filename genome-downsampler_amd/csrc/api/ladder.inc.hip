@@ -1,7 +1,7 @@
 // ladder.inc.hip -- part of qmcp_api.hip (one translation unit).
 // qmcp_hip_solve_ladder_host / _device: the by-contig solve at coverages[0], then level j + 1 solved on the reads level j
-// kept, down the list; one byte per read says how many levels keep it.  The grouping of solve_by_contig_on_device runs
-// once per call; the further levels run inside each batch (ladder_levels_of_batch), on its gathered columns:
+// kept, down the list; one byte per read says how many levels keep it.  group_by_contig runs once per call; the batch loop
+// solves level 0, and the further levels run after each batch (LadderSolver::after_batch), on its gathered columns:
 //   1. k_ladder_levels writes levels[origin] = j + 1 for the reads level j kept (the byte array was zeroed first)
 //   2. k_word_popcounts -> exclusive scan of the level's mask; k_ladder_offsets evaluates the kept rank at each contig's
 //      offset: the next level's contig_read_offsets, n_contigs + 1 values, read back once per level
@@ -14,44 +14,48 @@
 // one solve to the next; every use of it here is queued on the stream between the two.
 namespace {
 
-struct LadderRun {
-    const uint32_t* coverages = nullptr;
-    uint32_t n_levels = 0;
-    uint8_t* d_levels = nullptr;
+// level 0 is the plain solve of the batch; the further levels follow once its mask is scattered
+struct LadderSolver : PlainSolver {
+    const uint32_t* coverages;
+    uint32_t n_levels;
+    uint8_t* d_levels;
     qmcp_hip_ladder_stats ls;
+    LadderSolver(const uint32_t* cov, uint32_t levels, uint8_t* bytes)
+        : PlainSolver(cov[0]), coverages(cov), n_levels(levels), d_levels(bytes) {}
+    int after_batch(qmcp_hip_ctx* c, BatchView& v) override;
 };
 
-int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, uint32_t nb, const uint64_t* roff,
-                           const uint32_t* lengths, uint32_t n_contigs) {
+int LadderSolver::after_batch(qmcp_hip_ctx* c, BatchView& v) {
     hipStream_t st = c->stream;
+    const uint32_t nb = v.nb, n_contigs = v.n_contigs;
     EventPair ev_a(c), ev_b(c);
     if (!ev_a.a || !ev_a.b || !ev_b.a || !ev_b.b) return fail(QMCP_EHIP, "event creation failed");
     const size_t tab = (size_t)n_contigs + 1;
-    std::vector<uint32_t> offs32(tab), ranks(tab);
-    std::vector<uint64_t> cur(roff, roff + tab), next;
-    if (ld.n_levels > 1) {
+    std::vector<uint32_t> ranks(tab);
+    std::vector<uint64_t> cur(v.roff), next;
+    if (n_levels > 1) {
         TRY(ensure(c, c->ld_offs[0], tab * sizeof(uint32_t)));
         TRY(ensure(c, c->ld_offs[1], tab * sizeof(uint32_t)));
         const size_t words0 = ((size_t)nb + 63) / 64;
         TRY(ensure(c, c->ld_words, (words0 + 2) * sizeof(uint32_t)));
         TRY(ensure(c, c->ld_spine, (size_t)(qmcp::scan_spine_entries((uint32_t)words0 + 1) + 1) * sizeof(uint32_t) + 16));
-        for (size_t k = 0; k < tab; ++k) offs32[k] = (uint32_t)roff[k];  // (a batch holds at most 2^30 reads)
-        HIP_TRY(hipMemcpyAsync(c->ld_offs[0].p, offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        v.tables32();
+        HIP_TRY(hipMemcpyAsync(c->ld_offs[0].p, v.offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
     // the level whose mask is in bc_mask: its reads, their columns and their origins
     uint32_t n = nb;
     const uint32_t* d_s = (const uint32_t*)c->bc_starts.p;
     const uint32_t* d_e = (const uint32_t*)c->bc_ends.p;
-    const void* d_o = bsorted;
+    const void* d_o = v.records;
     const uint64_t* d_m = (const uint64_t*)c->bc_mask.p;
     bool compact_timed = false;
-    for (uint32_t j = 0; j < ld.n_levels; ++j) {
+    for (uint32_t j = 0; j < n_levels; ++j) {
         const bool first = j == 0;
-        const bool last = j + 1 == ld.n_levels;
+        const bool last = j + 1 == n_levels;
         HIP_TRY(hipEventRecord(ev_a.a, st));
         {
             KernelSpan sp(c, "k_ladder_levels");
-            qmcp::launch_ladder_levels(st, first, d_m, d_o, n, j + 1, ld.d_levels);
+            qmcp::launch_ladder_levels(st, first, d_m, d_o, n, j + 1, d_levels);
         }
         if (!last) {
             const uint32_t words = (n + 63u) / 64u;
@@ -68,8 +72,8 @@ int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, 
             HIP_TRY(hipMemcpyAsync(ranks.data(), c->ld_offs[(j & 1u) ^ 1u].p, tab * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                    st));
         HIP_TRY(hipStreamSynchronize(st));
-        ld.ls.ms_ladder += elapsed(ev_a.a, ev_a.b);
-        if (compact_timed) ld.ls.ms_ladder += elapsed(ev_b.a, ev_b.b);
+        ls.ms_ladder += elapsed(ev_a.a, ev_a.b);
+        if (compact_timed) ls.ms_ladder += elapsed(ev_b.a, ev_b.b);
         compact_timed = false;
         if (last) break;
         if (qmcp::ladder_next_offsets(cur.data(), ranks.data(), n_contigs, next) != QMCP_OK)
@@ -98,10 +102,10 @@ int ladder_levels_of_batch(qmcp_hip_ctx* c, LadderRun& ld, const void* bsorted, 
         cur.swap(next);
         qmcp_hip_stats bs;
         std::memset(&bs, 0, sizeof(bs));
-        TRY(solve_on_device(c, d_s, d_e, cur.data(), lengths, n_contigs, n, ld.coverages[j + 1], (uint64_t*)c->bc_mask.p,
+        TRY(solve_on_device(c, d_s, d_e, cur.data(), v.lengths, n_contigs, n, coverages[j + 1], (uint64_t*)c->bc_mask.p,
                             &bs));
-        ld.ls.n_kept[j + 1] += bs.n_kept;
-        ld.ls.ms_level[j + 1] += bs.ms_total;
+        ls.n_kept[j + 1] += bs.n_kept;
+        ls.ms_level[j + 1] += bs.ms_total;
     }
     return QMCP_OK;
 }
@@ -122,18 +126,18 @@ int solve_ladder_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
                            uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const uint32_t* coverages,
                            uint32_t n_levels, uint64_t* d_mask0, uint8_t* d_levels, qmcp_hip_stats* stats,
                            qmcp_hip_ladder_stats* lstats) {
-    LadderRun ld;
-    ld.coverages = coverages;
-    ld.n_levels = n_levels;
-    ld.d_levels = d_levels;
+    LadderSolver ld(coverages, n_levels, d_levels);
     std::memset(&ld.ls, 0, sizeof(ld.ls));
     ld.ls.n_levels = n_levels;
     if (lstats) *lstats = ld.ls;
-    // (the bytes are cleared before the reads are validated, as solve_by_contig_on_device clears its mask)
+    // (the bytes are cleared before the reads are validated, as group_by_contig clears the mask)
     if (n64 && n64 <= (1ull << 31)) HIP_TRY(hipMemsetAsync(d_levels, 0, (size_t)n64, c->stream));
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask0, g));
     qmcp_hip_stats plain;
-    std::memset(&plain, 0, sizeof(plain));
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, coverages[0], d_mask0, &plain, &ld));
+    TRY(run_batches(c, g, ld, d_mask0, plain));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    collect_spans(c);
     ld.ls.n_kept[0] = plain.n_kept;
     ld.ls.ms_level[0] = plain.ms_total;
     if (stats) *stats = plain;

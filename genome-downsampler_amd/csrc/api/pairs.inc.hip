@@ -1,8 +1,8 @@
 // pairs.inc.hip -- part of qmcp_api.hip (one translation unit).
 // qmcp_hip_solve_pairs_host / _device: a staged solve that credits the mates' coverage.  Reads (2q, 2q + 1) are pair q;
-// targets T_1 < ... < T_k = M.  Stage 1 is the by-contig solve at T_1 (solve_by_contig_on_device, every fast route) and
-// the pair OR over its input-order mask S.  Stage j > 1 runs over ALL batches of the same grouping before the next stage
-// begins -- a mate may lie in another batch, so S must be whole first -- and per batch:
+// targets T_1 < ... < T_k = M.  Stage 1 is the by-contig flow at T_1 (group_by_contig, run_batches with a PlainSolver: every
+// fast route) and the pair OR over its input-order mask S.  Stage j > 1 runs over ALL batches of the same grouping before
+// the next stage begins -- a mate may lie in another batch, so S must be whole first -- and per batch:
 //   1. k_bc_gather (the batch's columns again) and k_pair_gather_mask: S in grouped order, and its complement, the
 //      stage's candidates
 //   2. k_word_popcounts -> exclusive scan of the complement; k_ladder_offsets: the candidates' contig offsets, read back
@@ -66,10 +66,16 @@ struct StageNeeds {
 };
 
 struct PairRun {
-    std::vector<uint32_t> targets;
+    const std::vector<uint32_t>& targets;
     qmcp_hip_pair_stats ps;
-    UnitCompletion* completion = nullptr;  // set by the entry, for the length of its call
-    StageNeeds* needs = nullptr;           // set by the entry, for the length of its call
+    UnitCompletion* completion;  // the entry's, for the length of its call
+    StageNeeds* needs;           // the entry's, for the length of its call
+    PairRun(const std::vector<uint32_t>& t, UnitCompletion& whole, StageNeeds& later)
+        : targets(t), completion(&whole), needs(&later) {
+        std::memset(&ps, 0, sizeof(ps));
+        ps.n_stages = (uint32_t)targets.size();
+        for (size_t j = 0; j < targets.size(); ++j) ps.target[j] = targets[j];
+    }
 };
 
 struct TargetNeeds : StageNeeds {
@@ -105,9 +111,8 @@ struct PairCompletion : UnitCompletion {
     }
 };
 
-int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const std::vector<uint32_t>& offs,
-                      const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
-                      const uint32_t* lengths, uint64_t n64, uint64_t* d_mask, const qmcp_hip_stats& first) {
+// the completion of stage 1's mask, and every later stage over all batches of the grouping
+int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint64_t* d_mask, const qmcp_hip_stats& first) {
     hipStream_t st = c->stream;
     qmcp_hip_pair_stats& ps = pr.ps;
     const uint32_t pad = qmcp::pair_credit_pad();
@@ -133,17 +138,17 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
         return QMCP_OK;
     };
     TRY(begin());
-    TRY(pr.completion->complete_and_count(c, d_mask, n64));
+    TRY(pr.completion->complete_and_count(c, d_mask, g.n64));
     HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
     TRY(wait());
     ps.n_kept[0] = count;
 
-    std::vector<uint32_t> offs32, poff32, ranks;
-    std::vector<uint64_t> roff, cand_roff;
+    std::vector<uint32_t> ranks;
+    std::vector<uint64_t> cand_roff;
+    BatchView v;
     for (uint32_t j = 1; j < (uint32_t)pr.targets.size(); ++j) {
-        for (size_t b = 0; b < batches.size(); ++b) {
-            const qmcp::ContigBatch& bt = batches[b];
-            if (bt.n_reads == 0) continue;
+        for (size_t b : g.live) {
+            const qmcp::ContigBatch& bt = g.batches[b];
             StageNeed* need = nullptr;
             uint32_t max_cap = 0;
             TRY(pr.needs->make(c, j, bt, &need, &max_cap));
@@ -152,15 +157,9 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             const uint32_t ltot = (uint32_t)bt.positions;
             const uint32_t words = (nb + 63u) / 64u;
             const size_t tab = (size_t)bt.n_contigs + 1;
-            const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
-            batch_roff(offs.data() + bt.first_contig, bt.n_contigs, roff);
-            offs32.assign(tab, 0);
-            poff32.assign(tab, 0);
+            g.view(b, v);
+            v.tables32();
             ranks.assign(tab, 0);
-            for (uint32_t k = 0; k <= bt.n_contigs; ++k) {
-                offs32[k] = (uint32_t)roff[k];  // (a batch holds at most 2^30 reads)
-                if (k) poff32[k] = poff32[k - 1] + lengths[bt.first_contig + k - 1];  // (and at most 2^31 - 2 positions)
-            }
             TRY(ensure(c, c->pr_in, (size_t)words * sizeof(uint64_t)));
             TRY(ensure(c, c->pr_rest, (size_t)words * sizeof(uint64_t)));
             TRY(ensure(c, c->pr_words, ((size_t)words + 2) * sizeof(uint32_t)));
@@ -172,16 +171,13 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             TRY(ensure(c, c->pr_cspine, (size_t)(qmcp::scan_spine_entries(ltot + pad) + 1) * sizeof(uint32_t) + 16));
             // 1 - 3: S and the candidates in grouped order, the candidates' offsets, the credit of S
             TRY(begin());
-            HIP_TRY(hipMemcpyAsync(c->pr_offs[0].p, offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(c->pr_poff.p, poff32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c->pr_offs[0].p, v.offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c->pr_poff.p, v.poff32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemsetAsync(c->pr_credit.p, 0, ((size_t)ltot + pad) * sizeof(uint32_t), st));
-            {
-                KernelSpan sp(c, "k_bc_gather");
-                qmcp::launch_bc_gather(st, bsorted, nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p, (uint32_t*)c->bc_ends.p);
-            }
+            TRY(gather_batch(c, v, g.d_starts, g.d_ends));
             {
                 KernelSpan sp(c, "k_pair_gather_mask");
-                qmcp::launch_pair_gather_mask(st, bsorted, nb, d_mask, (uint64_t*)c->pr_in.p, (uint64_t*)c->pr_rest.p);
+                qmcp::launch_pair_gather_mask(st, v.records, nb, d_mask, (uint64_t*)c->pr_in.p, (uint64_t*)c->pr_rest.p);
             }
             {
                 KernelSpan sp(c, "pair candidates(popcounts, scan, k_ladder_offsets)");
@@ -193,7 +189,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             }
             {
                 KernelSpan sp(c, "k_pair_credit_events + scan");
-                qmcp::launch_pair_credit_events(st, bsorted, nb, (const uint64_t*)c->pr_in.p, (const uint32_t*)c->bc_starts.p,
+                qmcp::launch_pair_credit_events(st, v.records, nb, (const uint64_t*)c->pr_in.p, (const uint32_t*)c->bc_starts.p,
                                                 (const uint32_t*)c->bc_ends.p, (const uint32_t*)c->pr_poff.p, bt.first_contig,
                                                 (uint32_t*)c->pr_credit.p);
                 qmcp::launch_exclusive_scan(st, (const uint32_t*)c->pr_credit.p, ltot + pad, (uint32_t*)c->pr_credit.p,
@@ -202,7 +198,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(ranks.data(), c->pr_offs[1].p, tab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             TRY(wait());
-            if (qmcp::pair_candidate_offsets(roff.data(), ranks.data(), bt.n_contigs, cand_roff) != QMCP_OK)
+            if (qmcp::pair_candidate_offsets(v.roff.data(), ranks.data(), bt.n_contigs, cand_roff) != QMCP_OK)
                 return fail(QMCP_EHIP, "pair stage %u: the candidates' ranks do not fit the contig offsets", j);
             const uint32_t n_c = ranks[bt.n_contigs];
             if (n_c == 0) continue;  // every read of the batch is kept already
@@ -214,7 +210,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             HIP_TRY(hipEventRecord(ev_b.a, st));
             {
                 KernelSpan sp(c, "k_ladder_compact(pairs)");
-                qmcp::launch_ladder_compact(st, true, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, bsorted,
+                qmcp::launch_ladder_compact(st, true, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.records,
                                             (const uint64_t*)c->pr_rest.p, (const uint32_t*)c->pr_words.p, nb,
                                             (uint32_t*)c->pr_starts.p, (uint32_t*)c->pr_ends.p, (uint32_t*)c->pr_orig.p);
             }
@@ -226,7 +222,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             std::memset(&bs, 0, sizeof(bs));
             bool swept = false;
             TRY(capped_solve_batch(c, nd, max_cap, (const uint32_t*)c->pr_starts.p, (const uint32_t*)c->pr_ends.p,
-                                   cand_roff.data(), lengths + bt.first_contig, bt.n_contigs, n_c, (uint64_t*)c->pr_mask.p, &bs,
+                                   cand_roff.data(), v.lengths, bt.n_contigs, n_c, (uint64_t*)c->pr_mask.p, &bs,
                                    &swept));
             ps.ms_pairs += elapsed(ev_b.a, ev_b.b) + nd.ms;
             ps.n_selected[j] += bs.n_kept;
@@ -243,7 +239,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const void* sorted, const st
             HIP_TRY(hipGetLastError());
         }
         TRY(begin());
-        TRY(pr.completion->complete_and_count(c, d_mask, n64));
+        TRY(pr.completion->complete_and_count(c, d_mask, g.n64));
         HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
         TRY(wait());
         ps.n_kept[j] = count;
@@ -278,20 +274,18 @@ int check_pairs_call(uint64_t n_reads, const uint32_t* stages, uint32_t n_stages
 int solve_pairs_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
                           uint64_t n64, const uint32_t* lengths, uint32_t n_contigs, const std::vector<uint32_t>& targets,
                           uint64_t* d_mask, qmcp_hip_stats* stats, qmcp_hip_pair_stats* pstats) {
-    PairRun pr;
     PairCompletion mates;
     TargetNeeds needs(targets);
-    pr.completion = &mates;
-    pr.needs = &needs;
-    pr.targets = targets;
-    std::memset(&pr.ps, 0, sizeof(pr.ps));
-    pr.ps.n_stages = (uint32_t)targets.size();
-    for (size_t j = 0; j < targets.size(); ++j) pr.ps.target[j] = targets[j];
+    PairRun pr(targets, mates, needs);
     if (pstats) *pstats = pr.ps;
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask, g));
+    PlainSolver first(targets[0]);
     qmcp_hip_stats plain;
-    std::memset(&plain, 0, sizeof(plain));
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, targets[0], d_mask, &plain, nullptr,
-                                  nullptr, &pr));
+    TRY(run_batches(c, g, first, d_mask, plain));
+    TRY(pair_later_stages(c, pr, g, d_mask, plain));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    collect_spans(c);
     if (stats) *stats = plain;
     if (pstats) *pstats = pr.ps;
     return QMCP_OK;

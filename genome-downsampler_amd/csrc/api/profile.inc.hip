@@ -1,7 +1,7 @@
 // profile.inc.hip -- part of qmcp_api.hip (one translation unit).
-// qmcp_hip_solve_profile_host / _device: a cap per region, need(p) = min(cov(p), cap(p)).  The call is the by-contig solve
-// (api/by_contig.inc.hip: validation, grouping, batches, gather, mask scatter) with every batch solved under its own
-// regions:
+// qmcp_hip_solve_profile_host / _device: a cap per region, need(p) = min(cov(p), cap(p)).  The call is the by-contig flow
+// (api/by_contig.inc.hip: group_by_contig, run_batches, the final wait) with ProfileSolver as the batch solver, which solves
+// every batch under its own regions:
 //   1. cap_table.h builds the table on the host (a bad table fails here, before anything is copied or launched)
 //   2. a batch without a region is the unchanged solve at default_cap (a call without regions is therefore exactly
 //      qmcp_hip_solve_by_contig_* at default_cap); a batch whose largest cap is 0 keeps nothing
@@ -13,21 +13,16 @@
 // Buffers: the solve's own arena for everything the plain mixed route uses; need[] in pf_need, the batch's regions in
 // pf_tab, the two counters in pf_stat.
 // Step 3 is capped_solve_batch, which takes what builds need[] as a CappedNeed: the region table here (ProfileNeed), the
-// credit of the reads already kept in api/pairs.inc.hip, the dual need of a ceiling in api/ceiling.inc.hip (a ProfileRun
-// with a CeilingRun sends every batch there).
+// credit of the reads already kept in api/pairs.inc.hip, the dual need of a ceiling in api/ceiling.inc.hip (a batch solver
+// of its own over the same ProfileRun).
 namespace {
 
-struct CeilingRun;
 struct ProfileRun {
     const qmcp::CapTable* tab = nullptr;
     uint32_t default_cap = 0;
     float ms_profile = 0.f;
     std::vector<uint32_t> gs, ge, gcap;  // the batch's regions in its global positions
-    CeilingRun* ceiling = nullptr;       // the caps are ceilings: every batch goes to api/ceiling.inc.hip
 };
-int ceiling_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
-                        const uint64_t* roff, const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs,
-                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st_out);
 
 // What builds need[] for capped_solve_batch: a profile's regions here, the credit of the reads already kept in
 // api/pairs.inc.hip.  reserve runs inside the solve's arena block, upload behind the contig tables, launch once boff and
@@ -260,25 +255,24 @@ struct ProfileNeed : CappedNeed {
     }
 };
 
-int profile_solve_batch(qmcp_hip_ctx* c, ProfileRun& pf, const void* bsorted, const uint32_t* d_starts, const uint32_t* d_ends,
-                        const uint64_t* roff, const uint32_t* lengths_all, uint32_t first_contig, uint32_t n_contigs,
-                        uint64_t n64, uint64_t* d_mask, qmcp_hip_stats* st_out) {
-    if (pf.ceiling)
-        return ceiling_solve_batch(c, pf, bsorted, d_starts, d_ends, roff, lengths_all, first_contig, n_contigs, n64, d_mask,
-                                   st_out);
-    const qmcp::CapTable& tab = *pf.tab;
-    const uint32_t* lengths = lengths_all + first_contig;
-    const uint32_t r0 = tab.offs[first_contig], r1 = tab.offs[first_contig + n_contigs];
-    uint32_t max_cap = pf.default_cap;
-    for (uint32_t k = r0; k < r1; ++k) max_cap = std::max(max_cap, tab.cap[k]);
-    if (r0 == r1 && max_cap != 0)
-        return solve_on_device(c, d_starts, d_ends, roff, lengths, n_contigs, n64, pf.default_cap, d_mask, st_out);
-    qmcp::batch_cap_table(tab, lengths_all, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
-    ProfileNeed nd(pf, r1 - r0);
-    TRY(capped_solve_batch(c, nd, max_cap, d_starts, d_ends, roff, lengths, n_contigs, n64, d_mask, st_out));
-    pf.ms_profile += nd.ms;
-    return QMCP_OK;
-}
+// a batch under its own regions' caps: the plain solve at default_cap where it has none, else the capped route
+struct ProfileSolver : BatchSolver {
+    ProfileRun& pf;
+    explicit ProfileSolver(ProfileRun& run) : pf(run) {}
+    int solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* bs) override {
+        const qmcp::CapTable& tab = *pf.tab;
+        const uint32_t r0 = tab.offs[v.first_contig], r1 = tab.offs[v.first_contig + v.n_contigs];
+        uint32_t max_cap = pf.default_cap;
+        for (uint32_t k = r0; k < r1; ++k) max_cap = std::max(max_cap, tab.cap[k]);
+        if (r0 == r1 && max_cap != 0) return PlainSolver(pf.default_cap).solve(c, v, bs);
+        qmcp::batch_cap_table(tab, v.lengths - v.first_contig, v.first_contig, v.n_contigs, pf.gs, pf.ge, pf.gcap);
+        ProfileNeed nd(pf, r1 - r0);
+        TRY(capped_solve_batch(c, nd, max_cap, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.roff.data(),
+                               v.lengths, v.n_contigs, v.nb, (uint64_t*)c->bc_mask.p, bs));
+        pf.ms_profile += nd.ms;
+        return QMCP_OK;
+    }
+};
 
 // the checks both entries make before anything is copied or launched, and the table
 int check_profile_call(uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs, const uint32_t* region_offsets,
@@ -315,7 +309,14 @@ int solve_profile_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     ProfileRun pf;
     pf.tab = &tab;
     pf.default_cap = default_cap;
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, default_cap, d_mask, stats, nullptr, &pf));
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask, g));
+    ProfileSolver capped(pf);
+    qmcp_hip_stats sum;
+    TRY(run_batches(c, g, capped, d_mask, sum));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    collect_spans(c);
+    if (stats) *stats = sum;
     unsigned long long counters[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(counters, c->pf_stat.p, sizeof(counters), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

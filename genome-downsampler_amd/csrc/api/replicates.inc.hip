@@ -1,7 +1,7 @@
 // replicates.inc.hip -- part of qmcp_api.hip (one translation unit).
 // qmcp_hip_solve_replicates_host / _device: one read set split into disjoint downsamples.  Replicate 1 is the by-contig
-// solve at coverages[0] (solve_by_contig_on_device, every fast route); replicate r + 1 is the ordinary multi-contig solve
-// of the reads replicates 1 .. r left free.  The grouping of solve_by_contig_on_device runs once per call; what follows
+// flow at coverages[0] (group_by_contig, run_batches with a PlainSolver: every fast route); replicate r + 1 is the ordinary
+// multi-contig solve of the reads replicates 1 .. r left free.  The grouping runs once per call; what follows
 // (replicates_later) walks replicate-major over its batches -- a mate may lie in another batch -- and per batch:
 //   1. the candidates' taken bits: the last solve's mask (one batch, no pairs flag), or the input-order taken mask
 //      gathered through the candidates' origins (k_rep_gather_taken)
@@ -38,11 +38,12 @@ struct RepCands {
     std::vector<uint64_t> offs;  // contig_read_offsets of the candidates
 };
 
-int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, const std::vector<uint32_t>& offs,
-                     const std::vector<qmcp::ContigBatch>& batches, const uint32_t* d_starts, const uint32_t* d_ends,
-                     const uint32_t* d_ids, const uint32_t* lengths, uint32_t n_contigs_all, uint64_t n64, uint64_t* d_mask,
-                     const qmcp_hip_stats& first) {
+// every replicate after the first, over all batches of the grouping; d_mask holds replicate 1
+int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, uint64_t* d_mask, const qmcp_hip_stats& first) {
     hipStream_t st = c->stream;
+    const std::vector<qmcp::ContigBatch>& batches = g.batches;
+    const std::vector<size_t>& live = g.live;
+    const uint64_t n64 = g.n64;
     qmcp_hip_replicates_stats& rs = rp.rs;
     const uint32_t K = rp.n_replicates;
     const bool pairs = (rp.flags & QMCP_REPLICATES_WHOLE_PAIRS) != 0;
@@ -52,19 +53,9 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
     rs.n_kept[0] = first.n_kept;
     rs.ms_replicate[0] = first.ms_total;
     rp.rep[0] = first;
-    std::vector<size_t> live;
-    size_t largest = 0;
-    uint64_t most = 0;
+    const uint64_t most = live.empty() ? 0 : batches[g.largest].n_reads;
     uint32_t tab_max = 1;
-    for (size_t b = 0; b < batches.size(); ++b) {
-        if (batches[b].n_reads == 0) continue;
-        live.push_back(b);
-        tab_max = std::max(tab_max, batches[b].n_contigs + 1);
-        if (batches[b].n_reads > most) {
-            most = batches[b].n_reads;
-            largest = b;
-        }
-    }
+    for (size_t b : live) tab_max = std::max(tab_max, batches[b].n_contigs + 1);
     const bool single = live.size() == 1;
     const bool by_mask = single && !pairs;  // the candidates' taken bits are the last solve's mask
     const size_t words_in = (size_t)((n64 + 63) / 64);
@@ -107,14 +98,15 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
         }
         if (pairs) {
             KernelSpan sp(c, "k_rep_complete_pairs");
-            qmcp::launch_rep_complete_pairs(st, d_ids, n64, 1, rp.d_labels, d_taken, d_mates);
+            qmcp::launch_rep_complete_pairs(st, g.d_ids, n64, 1, rp.d_labels, d_taken, d_mates);
             HIP_TRY(hipMemcpyAsync(d_mask, d_taken, words_in * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
         }
         HIP_TRY(hipGetLastError());
     }
 
-    std::vector<uint32_t> offs32, ranks;
+    std::vector<uint32_t> ranks;
     std::vector<uint64_t> next;
+    BatchView v;
     uint32_t cur = 0;  // which of rp_offs holds the candidates' offsets
     uint32_t set = 0;  // which set of columns the next split fills
     // steps 2 and 3 for one batch: cd becomes the candidates `taken` leaves free
@@ -164,19 +156,19 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
         return QMCP_OK;
     };
     // a batch's candidates before any split: its gathered columns (in bc_starts / bc_ends) and the grouping's records
-    auto whole_batch = [&](const qmcp::ContigBatch& bt, RepCands& cd) -> int {
-        const size_t tab = (size_t)bt.n_contigs + 1;
+    auto whole_batch = [&](size_t b, RepCands& cd) -> int {
+        g.view(b, v);
+        v.tables32();
         cd.s = (const uint32_t*)c->bc_starts.p;
         cd.e = (const uint32_t*)c->bc_ends.p;
-        cd.o = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
+        cd.o = v.records;
         cd.first = true;
-        cd.n = (uint32_t)bt.n_reads;
-        batch_roff(offs.data() + bt.first_contig, bt.n_contigs, cd.offs);
-        offs32.assign(tab, 0);
-        for (size_t k = 0; k < tab; ++k) offs32[k] = (uint32_t)cd.offs[k];  // (a batch holds at most 2^30 reads)
+        cd.n = v.nb;
+        cd.offs = v.roff;
         TRY(begin());
-        // (offs32 stays untouched until the next wait: every use of it is followed by one)
-        HIP_TRY(hipMemcpyAsync(c->rp_offs[0].p, offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        // (v stays untouched until the next wait: every use of it is followed by one)
+        HIP_TRY(hipMemcpyAsync(c->rp_offs[0].p, v.offs32.data(), v.offs32.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               st));
         cur = 0;
         return QMCP_OK;
     };
@@ -184,7 +176,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
     auto solve = [&](const RepCands& cd, const qmcp::ContigBatch& bt, uint32_t j, bool first_of_j, bool is_largest) -> int {
         qmcp_hip_stats bs;
         std::memset(&bs, 0, sizeof(bs));
-        TRY(solve_on_device(c, cd.s, cd.e, cd.offs.data(), lengths + bt.first_contig, bt.n_contigs, cd.n, rp.coverages[j],
+        TRY(solve_on_device(c, cd.s, cd.e, cd.offs.data(), g.lengths + bt.first_contig, bt.n_contigs, cd.n, rp.coverages[j],
                             (uint64_t*)c->bc_mask.p, &bs));
         add_batch_stats(rp.rep[j], bs, first_of_j, is_largest);
         rp.rep[j].n_contigs += bt.n_contigs;
@@ -198,7 +190,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
     if (by_mask) {
         const qmcp::ContigBatch& bt = batches[live[0]];
         RepCands cd;
-        TRY(whole_batch(bt, cd));
+        TRY(whole_batch(live[0], cd));
         uint32_t unlabelled = 1;  // the replicate whose mask is in bc_mask and whose labels are not written yet
         for (uint32_t j = 1; j < K; ++j) {
             TRY(advance(cd, (const uint64_t*)c->bc_mask.p, bt.n_contigs, j));
@@ -215,16 +207,14 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
         HIP_TRY(hipGetLastError());
     } else if (!live.empty()) {
         RepCands cd;
-        if (single) TRY(whole_batch(batches[live[0]], cd));
+        if (single) TRY(whole_batch(live[0], cd));
         for (uint32_t j = 1; j < K; ++j) {
             bool first_of_j = true;
             for (size_t b : live) {
                 const qmcp::ContigBatch& bt = batches[b];
                 if (!single) {
-                    TRY(whole_batch(bt, cd));
-                    KernelSpan sp(c, "k_bc_gather");
-                    qmcp::launch_bc_gather(st, cd.o, cd.n, d_starts, d_ends, (uint32_t*)c->bc_starts.p,
-                                           (uint32_t*)c->bc_ends.p);
+                    TRY(whole_batch(b, cd));
+                    TRY(gather_batch(c, v, g.d_starts, g.d_ends));
                     set = 0;
                 }
                 if (cd.n == 0) continue;
@@ -234,7 +224,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
                 }
                 TRY(advance(cd, (const uint64_t*)c->rp_kept.p, bt.n_contigs, 0));
                 if (cd.n == 0) continue;
-                TRY(solve(cd, bt, j, first_of_j, b == largest));
+                TRY(solve(cd, bt, j, first_of_j, b == g.largest));
                 first_of_j = false;
                 TRY(begin());
                 KernelSpan sp(c, "k_rep_mark");
@@ -246,7 +236,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
             if (pairs) {
                 TRY(begin());
                 KernelSpan sp(c, "k_rep_complete_pairs");
-                qmcp::launch_rep_complete_pairs(st, d_ids, n64, j + 1, rp.d_labels, d_taken, d_mates + j);
+                qmcp::launch_rep_complete_pairs(st, g.d_ids, n64, j + 1, rp.d_labels, d_taken, d_mates + j);
             }
             HIP_TRY(hipGetLastError());
         }
@@ -261,9 +251,9 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
 
     if (rp.flags & QMCP_REPLICATES_SHORTFALL) {
         DepthCall dc;
-        TRY(check_depth_call(n64, false, lengths, n_contigs_all, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, dc));
+        TRY(check_depth_call(n64, false, g.lengths, g.n_contigs, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, dc));
         TRY(ensure(c, c->rp_lmask, words_in * sizeof(uint64_t)));
-        std::vector<qmcp_hip_depth_row> rows(n_contigs_all);
+        std::vector<qmcp_hip_depth_row> rows(g.n_contigs);
         for (uint32_t j = 0; j < K; ++j) {
             {
                 KernelSpan sp(c, "k_rep_label_mask");
@@ -271,7 +261,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const void* sorted, con
             }
             HIP_TRY(hipGetLastError());
             qmcp_hip_depth_stats ds;
-            TRY(depth_report_on_device(c, d_starts, d_ends, d_ids, (const uint64_t*)c->rp_lmask.p, n64, lengths, n_contigs_all,
+            TRY(depth_report_on_device(c, g.d_starts, g.d_ends, g.d_ids, (const uint64_t*)c->rp_lmask.p, n64, g.lengths, g.n_contigs,
                                        rp.coverages[j], dc, 0, rows.data(), nullptr, nullptr, nullptr, nullptr, &ds));
             for (const qmcp_hip_depth_row& row : rows) {
                 rs.short_positions[j] += row.deficit_positions;
@@ -314,12 +304,16 @@ int solve_replicates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     rp->rs.flags = flags;
     if (rstats) *rstats = rp->rs;
     if (rep_stats) std::memset(rep_stats, 0, (size_t)n_replicates * sizeof(qmcp_hip_stats));
-    // (the bytes are cleared before the reads are validated, as solve_by_contig_on_device clears its mask)
+    // (the bytes are cleared before the reads are validated, as group_by_contig clears the mask)
     if (n64 && n64 <= (1ull << 31)) HIP_TRY(hipMemsetAsync(d_labels, 0, (size_t)n64, c->stream));
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask0, g));
+    PlainSolver first(coverages[0]);
     qmcp_hip_stats plain;
-    std::memset(&plain, 0, sizeof(plain));
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, coverages[0], d_mask0, &plain, nullptr,
-                                  nullptr, nullptr, rp.get()));
+    TRY(run_batches(c, g, first, d_mask0, plain));
+    TRY(replicates_later(c, *rp, g, d_mask0, plain));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    collect_spans(c);
     if (stats) *stats = plain;
     if (rep_stats) std::memcpy(rep_stats, rp->rep, (size_t)n_replicates * sizeof(qmcp_hip_stats));
     if (rstats) *rstats = rp->rs;

@@ -6,7 +6,7 @@
 //      stratum id, and writes the stratum-major sort key stratum * n_contigs + contig (n_strata * n_contigs for a read
 //      without contig or stratum): one radix pass per 8 bits of n_strata * n_contigs, each (stratum, contig)'s run
 //   3. stratified_plan.h cuts every stratum that has a cap and reads into batches (by_contig_plan.h's packing, one
-//      stratum at a time); per batch solve_gathered_batch at the stratum's cap
+//      stratum at a time); per batch gather_batch and solve_scatter_batch with a PlainSolver at the stratum's cap
 //   4. k_st_tally reduces the grouped records against the final mask into one row per stratum; n_strata x 32 bytes
 //      come back
 // Buffers: the grouping and the batches live in the by-contig solve's buffers (bc_*), which nothing else uses while
@@ -75,16 +75,16 @@ int solve_stratified_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     qmcp_hip_stats sum;
     std::memset(&sum, 0, sizeof(sum));
     bool first = true;
-    std::vector<uint64_t> roff;
+    BatchView v;
     for (size_t b = 0; b < batches.size(); ++b) {
         const qmcp::StratumBatch& bt = batches[b];
         sum.n_contigs += bt.n_contigs;
         sum.total_length += bt.positions;
         if (bt.n_reads == 0) continue;  // (contigs the stratum has no reads on keep nothing)
-        const void* bsorted = (const uint32_t*)sorted + 2 * bt.first_read;  // {key, index} records
-        TRY(solve_gathered_batch(c, bsorted, (uint32_t)bt.n_reads, d_starts, d_ends,
-                                 offs.data() + (size_t)bt.stratum * n_contigs + bt.first_contig, lengths, bt.first_contig,
-                                 bt.n_contigs, bt.M, nullptr, d_mask, roff, sum, first, b == largest));
+        batch_view(sorted, offs.data() + (size_t)bt.stratum * n_contigs + bt.first_contig, lengths, bt, v);
+        PlainSolver plain(bt.M);
+        TRY(gather_batch(c, v, d_starts, d_ends));
+        TRY(solve_scatter_batch(c, v, plain, d_mask, sum, first, b == largest));
         first = false;
     }
     sum.n_reads = n_placed;  // (strata without a cap are not solved, yet their reads are part of the call)

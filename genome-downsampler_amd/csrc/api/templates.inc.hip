@@ -3,12 +3,12 @@
 // generalised from the reads (2q, 2q + 1) to every segment that carries one template id.
 //   1. once per call: the mask cleared, k_tpl_check (an id >= n_templates), k_tpl_sizes and k_tpl_size_hist (segments per
 //      template, their histogram, the templates in use, the largest); the error word and the counts come back
-//   2. solve_by_contig_on_device at the first target and pair_later_stages, as for pairs, with TemplateCompletion as the
-//      completion step: the bitset cleared, k_tpl_mark (flags |= the ids of S), k_tpl_spread (S = the segments of flagged
-//      templates, and |S|)
+//   2. group_by_contig, run_batches with the first stage's batch solver (a PlainSolver at the first target) and
+//      pair_later_stages, as for pairs, with TemplateCompletion as the completion step: the bitset cleared, k_tpl_mark
+//      (flags |= the ids of S), k_tpl_spread (S = the segments of flagged templates, and |S|)
 //   3. after the last stage the bitset still holds the kept templates: its popcount is n_templates_kept
-// api/templates_profile.inc.hip runs the same call under a cap per region: it hands in the StageNeeds of the later
-// stages and the ProfileRun of the first.
+// api/templates_profile.inc.hip runs the same call (solve_templates_staged) under a cap per region: it hands in the
+// StageNeeds of the later stages and the profile's batch solver for the first.
 // Buffers: the feature's own (tp_*) and the pair stages' (pr_*).
 namespace {
 
@@ -58,23 +58,16 @@ void copy_stage_stats(qmcp_hip_template_stats& ts, const qmcp_hip_pair_stats& ps
     }
 }
 
-int solve_templates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
-                              const uint32_t* d_tids, uint64_t n64, uint32_t n_templates, const uint32_t* lengths,
-                              uint32_t n_contigs, const std::vector<uint32_t>& targets, uint64_t* d_mask,
-                              qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats, StageNeeds* capped_needs = nullptr,
-                              ProfileRun* first_stage = nullptr /* then its default_cap is stage 1's plain cap */) {
+// the staged call: stage 1's batches go through first_stage, the later stages ask later_needs for their need[]
+int solve_templates_staged(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                           const uint32_t* d_tids, uint64_t n64, uint32_t n_templates, const uint32_t* lengths,
+                           uint32_t n_contigs, const std::vector<uint32_t>& targets, BatchSolver& first_stage,
+                           StageNeeds& later_needs, uint64_t* d_mask, qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats) {
     hipStream_t st = c->stream;
     qmcp_hip_template_stats ts;
     std::memset(&ts, 0, sizeof(ts));
-    PairRun pr;
     TemplateCompletion whole(d_tids, n_templates);
-    TargetNeeds needs(targets);  // (a reference and one PairNeed: nothing to pay where capped_needs takes its place)
-    pr.completion = &whole;
-    pr.needs = capped_needs ? capped_needs : &needs;
-    pr.targets = targets;
-    std::memset(&pr.ps, 0, sizeof(pr.ps));
-    pr.ps.n_stages = (uint32_t)targets.size();
-    for (size_t j = 0; j < targets.size(); ++j) pr.ps.target[j] = targets[j];
+    PairRun pr(targets, whole, later_needs);
     copy_stage_stats(ts, pr.ps);
     if (tstats) *tstats = ts;
     if (n64 > (1ull << 31))
@@ -113,13 +106,13 @@ int solve_templates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
     ts.max_template_size = (uint32_t)h_tstat[kTplLargest];
 
     // 2: the stages
+    GroupedReads g;
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, d_mask, g));
     qmcp_hip_stats plain;
-    std::memset(&plain, 0, sizeof(plain));
-    // with a ProfileRun the by-contig call reads this argument as the default cap outside the regions (as
-    // solve_profile_on_device passes it), and 0 is legal there: profile_solve_batch then keeps nothing outside regions
-    TRY(solve_by_contig_on_device(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs,
-                                  first_stage ? first_stage->default_cap : targets[0], d_mask, &plain, nullptr, first_stage,
-                                  &pr));
+    TRY(run_batches(c, g, first_stage, d_mask, plain));
+    TRY(pair_later_stages(c, pr, g, d_mask, plain));
+    HIP_TRY(hipStreamSynchronize(st));
+    collect_spans(c);
     copy_stage_stats(ts, pr.ps);
     ts.ms_templates += pr.ps.ms_pairs;
 
@@ -136,6 +129,17 @@ int solve_templates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const u
     if (stats) *stats = plain;
     if (tstats) *tstats = ts;
     return QMCP_OK;
+}
+
+// every stage at its target everywhere
+int solve_templates_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_ids,
+                              const uint32_t* d_tids, uint64_t n64, uint32_t n_templates, const uint32_t* lengths,
+                              uint32_t n_contigs, const std::vector<uint32_t>& targets, uint64_t* d_mask,
+                              qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats) {
+    PlainSolver first(targets[0]);
+    TargetNeeds needs(targets);
+    return solve_templates_staged(c, d_starts, d_ends, d_ids, d_tids, n64, n_templates, lengths, n_contigs, targets, first,
+                                  needs, d_mask, stats, tstats);
 }
 
 }  // namespace

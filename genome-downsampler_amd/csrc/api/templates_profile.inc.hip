@@ -4,9 +4,9 @@
 // c_j(p) = ceil(cap(p) * T_j / M); its need is min(cov_rest(p), max(0, c_j(p) - credit_j(p))).
 //   1. every argument checked on the host: the templates entry's, then the profile entry's; cap_table.h builds the table
 //   2. no region used and default_cap == M: solve_templates_on_device as it is (identity 1)
-//   3. otherwise solve_templates_on_device with
-//        stage 1   a ProfileRun over a copy of the table scaled to c_1: per batch the plain solve at the scaled default
-//                  cap (no region), nothing (largest cap 0), or the profile's capped route -- profile_solve_batch
+//   3. otherwise solve_templates_staged with
+//        stage 1   a ProfileSolver over a copy of the table scaled to c_1: per batch the plain solve at the scaled default
+//                  cap (no region), nothing (largest cap 0), or the profile's capped route
 //        later     TemplateProfileNeeds: per stage and batch batch_cap_table, the caps scaled to c_j and uploaded into
 //                  tq_tab, k_tpl_profile_need as the CappedNeed of capped_solve_batch; a batch whose largest c_j is 0 is
 //                  skipped before its gather
@@ -154,9 +154,10 @@ int solve_templates_profile_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts,
         pf.default_cap = qmcp::scale_cap(default_cap, targets[0], M);
         TRY(ensure(c, c->pf_stat, 2 * sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(c->pf_stat.p, 0, 2 * sizeof(unsigned long long), c->stream));
+        ProfileSolver first_stage(pf);
         TemplateProfileNeeds needs(tab, lengths, default_cap, M, targets);
-        TRY(solve_templates_on_device(c, d_starts, d_ends, d_ids, d_tids, n64, n_templates, lengths, n_contigs, targets, d_mask,
-                                      stats, tstats, &needs, &pf));
+        TRY(solve_templates_staged(c, d_starts, d_ends, d_ids, d_tids, n64, n_templates, lengths, n_contigs, targets,
+                                   first_stage, needs, d_mask, stats, tstats));
         qs.ms_need = pf.ms_profile + needs.ms_need();
     }
     if (tstats) ts = *tstats;

@@ -37,7 +37,8 @@
 #include "pair_plan.h"
 #include "replicates_plan.h"
 
-// One translation unit, kept in parts under api/ (included below, in dependency order):
+// One translation unit, kept in parts under api/ (included below, in dependency order: a part uses only parts above it,
+// those a by-contig feature builds on are named in brackets):
 //   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
 //   radix_passes        the stable LSD radix sort's passes (records form, wide u64 form): the one loop every sorting entry queues
 //   uniform_sweep       which one-length sweep a call takes and its launches (pipelines, event-driven form, stretches,
@@ -49,7 +50,8 @@
 //   solve_tail          a solve's tail, collection, context creation, enqueue / complete
 //   host_entries        probes, column upload, the extern "C" entry points
 //   multi_device        several devices behind one call
-//   by_contig           reads in any order with a contig id each: grouped on the device, solved in batches, mask scattered back
+//   by_contig           reads in any order with a contig id each: the grouping as a value, a batch's view, the batch loop
+//                       over a batch solver, the mask scattered back; the by-contig entries.  Knows no feature built on it
 //   amplicon_by_contig  pairs of several contigs: FILTER against each contig's amplicons, compaction, the by-contig solve
 //   quality             the plain or by-contig solve, then the quality pass on its mask (same count per cell, best reads)
 //   targets             coverage capped inside target regions only: reads projected onto each contig's target positions,
@@ -58,26 +60,29 @@
 //                       the reads' events, the positions pass, rows and statistics assembled on the host
 //   depth_track         the same pipeline ending in a run-length compaction: per-base depth before and after as records
 //                       (contig, start, end, depth_in, depth_kept, short), counted first, then written and copied out
-//   ladder              several falling coverages in one by-contig call: every further level solved on the reads the level
-//                       above kept, inside each batch; one byte per read counts the levels that keep it
-//   stratified          one coverage cap per stratum (strand, read group, sample): reads grouped once by (stratum, contig),
-//                       every stratum solved in batches of its own at its cap, one row of counts per stratum
+//   ladder              (by_contig) several falling coverages in one call: a batch solver whose further levels run after
+//                       each batch, on the reads the level above kept; one byte per read counts the levels that keep it
+//   stratified          (by_contig) one coverage cap per stratum (strand, read group, sample): reads grouped once by
+//                       (stratum, contig), every stratum solved in batches of its own at its cap, one row of counts each
 //   dedup               duplicate families (reads or pairs with equal cells) collapsed to their best unit before the
 //                       by-contig solve; duplicate mask, family-size histogram and statistics from the device
-//   profile             one cap per region (a piecewise-constant cap along every contig): the cap table, and a batch's
-//                       solve on the sort-based mixed route with need(p) = min(cov(p), cap(p)) built on the device
-//   pairs               pair-aware downsampling: the by-contig solve at a first target, then stages over all batches that
-//                       credit the depth of the pairs already kept and top up among the other reads on the capped route
-//   templates           the pair-aware stages with the unit generalised: every segment that carries one template id
-//                       (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
-//   templates_profile   the template stages under a cap per region: stage 1 is the profile's batches at the scaled
-//                       caps, later stages build need[] from the scaled region table and the credit
-//   ceiling             kept depth never above the cap, the most reads kept: the profile's batches with the dual need
+//   profile             (by_contig) one cap per region (a piecewise-constant cap along every contig): the cap table, the
+//                       capped route (the sort-based mixed route under a need[] built on the device) and the batch solver
+//                       with need(p) = min(cov(p), cap(p))
+//   pairs               (by_contig, profile) pair-aware downsampling: the batch loop at a first target, then stages over
+//                       all batches that credit the depth of the pairs already kept and top up among the other reads on
+//                       the capped route
+//   templates           (pairs) the pair-aware stages with the unit generalised: every segment that carries one template
+//                       id (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
+//   templates_profile   (templates, profile) the template stages under a cap per region: stage 1 is the profile's batch
+//                       solver at the scaled caps, later stages build need[] from the scaled region table and the credit
+//   ceiling             (profile) kept depth never above the cap, the most reads kept: a batch solver with the dual need
 //                       max(0, cov(p) - cap(p)) selecting the DROPPED reads, a device-side check, and the complement
-//   budget              the deepest coverage whose by-contig solve fits a number of reads: one grouping, the curve
-//                       S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
-//   replicates          one read set split into disjoint downsamples: the by-contig solve at the first coverage, every
-//                       further replicate solved on the reads still free, replicate-major over the one grouping's batches
+//   budget              (by_contig) the deepest coverage whose by-contig solve fits a number of reads: one grouping, the
+//                       curve S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
+//   replicates          (by_contig, depth_report) one read set split into disjoint downsamples: the batch loop at the
+//                       first coverage, every further replicate solved on the reads still free, replicate-major over the
+//                       one grouping's batches
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
