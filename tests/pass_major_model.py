@@ -25,6 +25,9 @@ import numpy as np
 
 PASS = 8192
 CHUNK_WS = 16          # wave-slots per chunk (one per wave of the walking workgroup)
+WAVE_READS = 1024      # reads of a pass one producer wave owns (eight waves a pass)
+EXC_PER_WAVE = 128     # exception-list slots per (pass, wave)
+MAX_RANGE_SHIFT = 15
 
 
 def pitch_for(n):
@@ -36,8 +39,10 @@ def stride_for(n_ranges):
     return PASS + 64 * n_ranges
 
 
-def producer(gstart, shift, n_ranges):
-    """-> keys16, idx16 (pitch * stride slots, 0xFFFF where nothing was written), cntp, lstw ([256][pitch] uint32)"""
+def producer(gstart, shift, n_ranges, regular=None):
+    """-> keys16, idx16 (pitch * stride slots, 0xFFFF where nothing was written), cntp, lstw ([256][pitch] uint32).
+    regular (bool per read, or None: every read): the reads that enter the slices -- the near-uniform route's filter
+    leaves the others out; idx16 stays the read's index inside its pass"""
     n = gstart.size
     pitch = pitch_for(n)
     stride = stride_for(n_ranges)
@@ -47,8 +52,9 @@ def producer(gstart, shift, n_ranges):
     lstw = np.zeros((256, pitch), np.uint32)
     for P in range((n + PASS - 1) // PASS):
         lo, hi = P * PASS, min(n, (P + 1) * PASS)
-        d = (gstart[lo:hi] >> shift).astype(np.int64)
-        assert d.max() < n_ranges <= 256
+        sel = np.arange(hi - lo) if regular is None else np.nonzero(regular[lo:hi])[0]
+        d = (gstart[lo:hi][sel] >> shift).astype(np.int64)
+        assert d.size == 0 or d.max() < n_ranges <= 256
         order = np.argsort(d, kind="stable")
         c = np.bincount(d, minlength=256).astype(np.int64)
         pad = (c + 63) // 64 * 64
@@ -56,7 +62,7 @@ def producer(gstart, shift, n_ranges):
         assert first[-1] + pad[-1] <= stride
         compact = np.concatenate([[0], np.cumsum(c)[:-1]])
         for dd in np.nonzero(c)[0]:
-            src = order[compact[dd]:compact[dd] + c[dd]]
+            src = sel[order[compact[dd]:compact[dd] + c[dd]]]
             at = P * stride + first[dd]
             keys16[at:at + c[dd]] = (gstart[lo:hi][src] & ((1 << shift) - 1)).astype(np.uint16)
             idx16[at:at + c[dd]] = src.astype(np.uint16)
@@ -181,3 +187,95 @@ def settle(amb, keys16, idx16, desc, Tp, pitch, d, n, stride, mask):
             mask[i] = True
             kept += 1
     return kept
+
+
+# ---- what the kernels write besides the layout (tests/pm_stage_compare.py holds the device's buffers against these)
+def range_shift_for(ltot):
+    """the smallest shift whose ranges of positions 0..ltot fit one partition level (one-level genomes only)"""
+    shift = 0
+    while shift < MAX_RANGE_SHIFT and (ltot >> shift) >= 256:
+        shift += 1
+    assert (ltot >> shift) < 256, "two partition levels: not the pass-major form"
+    return shift
+
+
+def contig_of_reads(roff):
+    roff = np.asarray(roff, np.int64)
+    return np.repeat(np.arange(roff.size - 1), np.diff(roff))
+
+
+def clamped(local, contig, lengths):
+    """k_pm_prepare_sort: a coordinate beyond its contig -- the call fails -- is taken as the contig's last position
+    (min(s, len - 1); position 0 of a contig without positions)"""
+    last = np.maximum(np.asarray(lengths, np.int64) - 1, 0)
+    return np.minimum(np.asarray(local, np.int64), last[contig])
+
+
+def statistics(starts, ends, contig, lengths):
+    """stats[0..2]: minimum and maximum span over all reads (e - s + 1 in 32-bit arithmetic, as the kernel has it) and
+    the bad flag (start > end, or end at or beyond the contig's length)"""
+    s, e = np.asarray(starts, np.int64), np.asarray(ends, np.int64)
+    span = (e - s + 1) & 0xFFFFFFFF
+    bad = (s > e) | (e >= np.asarray(lengths, np.int64)[contig])
+    return int(span.min()), int(span.max()), int(bad.any())
+
+
+def regular_reads(starts, ends, ell_reg):
+    """the reads that enter the slices: all of them, or with a filter those of span ell_reg"""
+    s, e = np.asarray(starts, np.int64), np.asarray(ends, np.int64)
+    if ell_reg == 0:
+        return np.ones(s.size, bool)
+    return ((e - s + 1) & 0xFFFFFFFF) == ell_reg
+
+
+def exception_lists(gs, ge, regular):
+    """the filtered producer's lists.  gs / ge: clamped global starts and ends of every read.  Each (pass, wave of 1 024
+    reads) lists its first 128 exceptions in read-index order at slots (8 P + w) 128 ...; the rest go to the overflow
+    region in any order.  -> cnt [pitch * 8], groups {group: int64 [k][3] = (start, end, index)}, overflow int64 [m][3]
+    (in read-index order here)"""
+    n = gs.size
+    cnt = np.zeros(pitch_for(n) * (PASS // WAVE_READS), np.int64)
+    groups, over = {}, []
+    exc = np.nonzero(~regular)[0]
+    grp = exc // WAVE_READS     # = 8 P + w: passes are eight waves
+    for g in np.unique(grp):
+        idx = exc[grp == g]
+        ent = np.stack([gs[idx], ge[idx], idx], axis=1).astype(np.int64)
+        cnt[g] = min(idx.size, EXC_PER_WAVE)
+        groups[int(g)] = ent[:EXC_PER_WAVE]
+        over.append(ent[EXC_PER_WAVE:])
+    overflow = np.concatenate(over) if over else np.zeros((0, 3), np.int64)
+    return cnt, groups, overflow
+
+
+def loads(cntp, lstw):
+    """max_load[0], [1]: the heaviest range's records (largest true row sum) and wave-slots (largest padded row sum / 64)"""
+    return int((lstw >> 16).astype(np.int64).sum(axis=1).max()), int(cntp.astype(np.int64).sum(axis=1).max()) // 64
+
+
+def bucket_offsets(gs_regular, ltot):
+    """boff[p], p = 0 .. ltot: the regular reads that start below p (plain reference, not through the layout)"""
+    return np.searchsorted(np.sort(np.asarray(gs_regular, np.int64)), np.arange(ltot + 1), side="left").astype(np.uint32)
+
+
+def empty_positions(gs_regular, ltot):
+    """stats[3]: positions of [0, ltot) at which no regular read starts"""
+    return int(ltot - np.unique(np.asarray(gs_regular, np.int64)).size)
+
+
+def expected_mask(gs, quota, regular=None):
+    """the quota[p] lowest read indices of every global start p (plain reference, not through the layout); quota: an
+    array per global position, or a callable.  Only the regular reads take part."""
+    n = gs.size
+    quota_of = quota if callable(quota) else (lambda p: quota[p])
+    reads = np.arange(n) if regular is None else np.nonzero(regular)[0]
+    mask = np.zeros(n, bool)
+    if reads.size == 0:
+        return mask
+    order = reads[np.argsort(gs[reads], kind="stable")]
+    sorted_g = gs[order]
+    starts = np.concatenate([[0], np.nonzero(np.diff(sorted_g.astype(np.int64)))[0] + 1, [order.size]])
+    for a, b in zip(starts[:-1], starts[1:]):
+        k = min(int(quota_of(int(sorted_g[a]))), b - a)
+        mask[order[a:a + k]] = True
+    return mask

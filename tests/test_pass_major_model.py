@@ -36,17 +36,7 @@ CASES = [
 ]
 
 
-def _expected_mask(gs, quota_of):
-    """the quota_of(p) lowest read indices of every global start p"""
-    n = gs.size
-    order = np.argsort(gs, kind="stable")
-    mask = np.zeros(n, bool)
-    sorted_g = gs[order]
-    starts = np.concatenate([[0], np.nonzero(np.diff(sorted_g))[0] + 1, [n]])
-    for a, b in zip(starts[:-1], starts[1:]):
-        k = min(int(quota_of(int(sorted_g[a]))), b - a)
-        mask[order[a:a + k]] = True
-    return mask
+_expected_mask = pm.expected_mask     # (shared with the stage tests: tests/pm_stage_compare.py)
 
 
 @pytest.mark.parametrize("lengths,counts,shift", CASES)
@@ -128,3 +118,109 @@ def test_skewed_passes_with_long_and_empty_slices():
     for d, amb in ambs.items():
         pm.settle(amb, keys16, idx16, desc, Tp, pitch, d, n, stride, mask)
     assert np.array_equal(mask, _expected_mask(gs, lambda p: quota[p]))
+
+
+# ---- what the kernels write besides the layout: the model's functions against brute-force loops
+def _ragged_reads(rng, ell):
+    lengths = np.array([3_000, 0, 700, 9_000], np.int64)
+    counts = np.array([2 * 8192 + 300, 0, 1_500, 8192 - 11], np.int64)
+    contig = np.repeat(np.arange(4), counts)
+    starts = np.concatenate([rng.integers(0, max(int(L) - ell, 1), size=int(k)) for L, k in zip(lengths, counts)])
+    return lengths, counts, contig, starts, starts + ell - 1
+
+
+def test_exception_lists_against_a_loop():
+    """every (pass, wave of 1 024 reads) lists its first 128 exceptions in read-index order; the rest overflow"""
+    rng = np.random.default_rng(11)
+    ell = 50
+    lengths, counts, contig, starts, ends = _ragged_reads(rng, ell)
+    n = starts.size
+    ends = ends.copy()
+    clipped = rng.random(n) < 0.03
+    clipped[5_000:5_700] = True                      # a run: waves 4 and 5 overflow their slots
+    ends[clipped] -= rng.integers(1, 20, size=int(clipped.sum()))
+    starts[17] = 4_000_000_000                       # an invalid read is an exception like any other, clamped
+    ends[17] = 4_000_000_020
+    ends[18] = lengths[0] + 5
+    poff = np.concatenate([[0], np.cumsum(lengths)])
+    gs = poff[contig] + pm.clamped(starts, contig, lengths)
+    ge = poff[contig] + pm.clamped(ends, contig, lengths)
+    regular = pm.regular_reads(starts, ends, ell)
+    cnt, groups, overflow = pm.exception_lists(gs, ge, regular)
+    want_cnt = [0] * (pm.pitch_for(n) * 8)
+    want_groups, want_over = {}, []
+    for i in range(n):
+        span = (int(ends[i]) - int(starts[i]) + 1) % (1 << 32)
+        assert bool(regular[i]) == (span == ell)
+        if span == ell:
+            continue
+        last = max(int(lengths[contig[i]]) - 1, 0)
+        ent = (int(poff[contig[i]]) + min(int(starts[i]), last), int(poff[contig[i]]) + min(int(ends[i]), last), i)
+        g = 8 * (i // pm.PASS) + (i % pm.PASS) // 1024
+        if want_cnt[g] < 128:
+            want_groups.setdefault(g, []).append(ent)
+            want_cnt[g] += 1
+        else:
+            want_over.append(ent)
+    assert not regular[17] and not regular[18] and len(want_over) > 0 and max(want_cnt) == 128
+    assert cnt.tolist() == want_cnt and sorted(groups) == sorted(want_groups)
+    for g, ent in want_groups.items():
+        assert groups[g].tolist() == [list(e) for e in ent]
+    assert sorted(map(tuple, overflow.tolist())) == sorted(want_over)
+    # the filtered producer: only the regular reads enter the slices, under their index inside the pass
+    keys16, idx16, cntp, lstw = pm.producer(gs.astype(np.uint32), 6, (int(poff[-1]) >> 6) + 1, regular)
+    assert int((lstw >> 16).sum()) == int(regular.sum())
+    stride = pm.stride_for((int(poff[-1]) >> 6) + 1)
+    seen = []
+    for d, P in zip(*np.nonzero(lstw >> 16)):
+        at = int(P) * stride + int(lstw[d, P] & 0xFFFF) * 64
+        seen.append(int(P) * pm.PASS + idx16[at:at + int(lstw[d, P] >> 16)].astype(np.int64))
+    assert np.array_equal(np.sort(np.concatenate(seen)), np.nonzero(regular)[0])
+
+
+def test_statistics_and_plain_references_against_loops():
+    rng = np.random.default_rng(12)
+    lengths, counts, contig, starts, ends = _ragged_reads(rng, 30)
+    n = starts.size
+    for variant in range(4):
+        s, e = starts.copy(), ends.copy()
+        if variant == 1:
+            s[n - 3], e[n - 3] = 4_000_000_000, 4_000_000_029      # a start beyond its contig
+        elif variant == 2:
+            s[9_000], e[9_000] = e[9_000], s[9_000]                  # start > end: the span wraps, as in the kernel
+        elif variant == 3:
+            e[40] = lengths[contig[40]]                              # an end at the contig's length
+            s[40] = e[40] - 29
+        mn, mx, bad = 1 << 32, 0, 0
+        for i in range(n):
+            span = (int(e[i]) - int(s[i]) + 1) % (1 << 32)
+            mn, mx = min(mn, span), max(mx, span)
+            bad |= int(s[i] > e[i] or e[i] >= lengths[contig[i]])
+        assert pm.statistics(s, e, contig, lengths) == (mn, mx, bad) and bad == (variant != 0)
+        assert np.array_equal(pm.clamped(s, contig, lengths),
+                              [min(int(v), max(int(lengths[c]) - 1, 0)) for v, c in zip(s, contig)])
+    # bucket offsets, empty positions, loads
+    poff = np.concatenate([[0], np.cumsum(lengths)])
+    ltot = int(poff[-1])
+    gs = (poff[contig] + starts).astype(np.int64)
+    count = [0] * ltot
+    for v in gs:
+        count[int(v)] += 1
+    boff = [0]
+    for p in range(ltot):
+        boff.append(boff[-1] + count[p])
+    assert pm.bucket_offsets(gs, ltot).tolist() == boff
+    assert pm.empty_positions(gs, ltot) == sum(1 for c in count if c == 0)
+    n_ranges = (ltot >> 6) + 1
+    _, _, cntp, lstw = pm.producer(gs.astype(np.uint32), 6, n_ranges)
+    rows_true = [0] * 256
+    rows_slots = [0] * 256
+    for P in range((n + pm.PASS - 1) // pm.PASS):
+        per = [0] * 256
+        for v in gs[P * pm.PASS:(P + 1) * pm.PASS]:
+            per[int(v) >> 6] += 1
+        for d in range(256):
+            rows_true[d] += per[d]
+            rows_slots[d] += (per[d] + 63) // 64
+    assert pm.loads(cntp, lstw) == (max(rows_true), max(rows_slots))
+    assert [pm.range_shift_for(v) for v in (1, 255, 256, 300, 14_336, 100_000, (1 << 21) - 5, (1 << 23) - 1)] == [0, 0, 1, 1, 6, 9, 13, 15]

@@ -16,16 +16,7 @@ def driver(tmp_path_factory):
     return gm.build_driver(tmp_path_factory.mktemp("pm_grid_plan"))
 
 
-def _expected_mask(gs, quota):
-    """the quota[p] lowest read indices of every global start p"""
-    n = gs.size
-    order = np.argsort(gs, kind="stable")
-    sorted_g = gs[order]
-    mask = np.zeros(n, bool)
-    starts = np.concatenate([[0], np.nonzero(np.diff(sorted_g))[0] + 1, [n]])
-    for a, b in zip(starts[:-1], starts[1:]):
-        mask[order[a:a + min(int(quota[int(sorted_g[a])]), b - a)]] = True
-    return mask
+_expected_mask = pm.expected_mask
 
 
 CASES = [
