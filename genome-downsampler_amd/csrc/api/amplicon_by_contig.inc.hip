@@ -59,7 +59,7 @@ int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts
     TRY(ensure(c, c->f_mask, pwords * 8 + 16));
     TRY(ensure(c, c->mask, words * 8));
     TRY(ensure(c, c->cov, words * 8 + 16));  // compact-index keep mask
-    TRY(ensure(c, c->spine, (size_t)(qmcp::scan_spine_entries((uint32_t)pwords + 1) + 1) * 4 + 16));
+    TRY(ensure(c, c->spine, scan_spine_bytes((uint32_t)pwords + 1, 1)));
     TRY(ensure(c, c->af_len, (size_t)n_contigs * 4));
     TRY(ensure(c, c->af_err, 16));
     TRY(ensure(c, c->af_tab, ((size_t)n_contigs + 1 + 2 * (size_t)n_amp) * 4));
@@ -74,18 +74,18 @@ int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts
     if (seq_lengths) {
         TRY(ensure(c, c->in_aux0, nb));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, seq_lengths, nb, hipMemcpyHostToDevice, st));
-        d_len = (const uint32_t*)c->in_aux0.p;
+        d_len = c->in_aux0.u32();
     }
     if (qualities) {
         TRY(ensure(c, c->in_aux1, nb));
         HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, st));
-        d_q = (const uint32_t*)c->in_aux1.p;
+        d_q = c->in_aux1.u32();
     }
     uint32_t* d_offs = nullptr;
     uint32_t* d_tab_s = nullptr;
     uint32_t* d_tab_p = nullptr;
     if (amp_offsets) {
-        d_offs = (uint32_t*)c->af_tab.p;
+        d_offs = c->af_tab.u32();
         d_tab_s = d_offs + n_contigs + 1;
         d_tab_p = d_tab_s + n_amp;
         HIP_TRY(hipMemcpyAsync(d_offs, amp_offsets, ((size_t)n_contigs + 1) * 4, hipMemcpyHostToDevice, st));
@@ -97,21 +97,18 @@ int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts
     // 1. FILTER + validation
     {
         KernelSpan sp(c, "k_amplicon_filter_by_contig");
-        qmcp::launch_amplicon_filter_by_contig(st, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                               (const uint32_t*)c->af_ids.p, d_len, d_q, n_pairs,
-                                               (const uint32_t*)c->af_len.p, n_contigs, d_offs, d_tab_s, d_tab_p, n_amp,
-                                               min_length, min_mapq, (uint64_t*)c->f_mask.p, (uint32_t*)c->af_err.p);
+        qmcp::launch_amplicon_filter_by_contig(st, c->in_starts.u32(), c->in_ends.u32(), c->af_ids.u32(), d_len, d_q,
+                                               n_pairs, c->af_len.u32(), n_contigs, d_offs, d_tab_s, d_tab_p, n_amp,
+                                               min_length, min_mapq, c->f_mask.u64(), c->af_err.u32());
     }
     // 2. compaction
     {
         KernelSpan sp(c, "compact survivors(popcounts, scan)");
-        qmcp::launch_word_popcounts(st, (const uint64_t*)c->f_mask.p, (uint32_t)pwords, (uint32_t*)c->f_words.p);
-        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->f_words.p, (uint32_t)pwords, (uint32_t*)c->f_words.p,
-                                    (uint32_t*)c->spine.p, true);
+        queue_mask_ranks(st, c->f_mask.u64(), (uint32_t)pwords, c->f_words, c->spine);
     }
     HIP_TRY(hipGetLastError());
     uint32_t err = 0, n_surv_pairs = 0;
-    HIP_TRY(hipMemcpyAsync(&n_surv_pairs, (uint32_t*)c->f_words.p + pwords, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_surv_pairs, c->f_words.u32() + pwords, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&err, c->af_err.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     collect_spans(c);
@@ -119,18 +116,16 @@ int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts
     if (err & 2u) return fail(QMCP_EREAD, "a read has start > end or end >= its contig's length");
     {
         KernelSpan sp(c, "k_compact_pairs_ids");
-        qmcp::launch_compact_pairs_ids(st, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                       (const uint32_t*)c->af_ids.p, (const uint64_t*)c->f_mask.p,
-                                       (const uint32_t*)c->f_words.p, n_pairs, (uint32_t*)c->f_starts.p,
-                                       (uint32_t*)c->f_ends.p, (uint32_t*)c->af_ids_c.p, (uint32_t*)c->f_map.p);
+        qmcp::launch_compact_pairs_ids(st, c->in_starts.u32(), c->in_ends.u32(), c->af_ids.u32(), c->f_mask.u64(),
+                                       c->f_words.u32(), n_pairs, c->f_starts.u32(), c->f_ends.u32(), c->af_ids_c.u32(),
+                                       c->f_map.u32());
     }
     HIP_TRY(hipGetLastError());
     // 3. the by-contig solve of the survivors, 4. mates, 5. back to the original indices
     const uint64_t n_c = 2ull * n_surv_pairs;
-    uint64_t* d_mask_c = (uint64_t*)c->cov.p;
-    TRY(solve_by_contig_on_device(c, (const uint32_t*)c->f_starts.p, (const uint32_t*)c->f_ends.p,
-                                  (const uint32_t*)c->af_ids_c.p, n_c, contig_lengths, n_contigs, max_coverage, d_mask_c,
-                                  stats));
+    uint64_t* d_mask_c = c->cov.u64();
+    TRY(solve_by_contig_on_device(c, c->f_starts.u32(), c->f_ends.u32(), c->af_ids_c.u32(), n_c, contig_lengths,
+        n_contigs, max_coverage, d_mask_c, stats));
     const uint32_t words_c = (uint32_t)((n_c + 63) / 64);
     if (complete_pairs && words_c) {
         KernelSpan sp(c, "k_complete_pairs");
@@ -140,7 +135,7 @@ int qmcp_hip_filter_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts
     HIP_TRY(hipMemsetAsync(c->mask.p, 0, words * 8, st));
     if (n_c) {
         KernelSpan sp(c, "k_expand_mask");
-        qmcp::launch_expand_mask(st, d_mask_c, (const uint32_t*)c->f_map.p, (uint32_t)n_c, (uint64_t*)c->mask.p);
+        qmcp::launch_expand_mask(st, d_mask_c, c->f_map.u32(), (uint32_t)n_c, c->mask.u64());
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * 8, hipMemcpyDeviceToHost, st));

@@ -29,12 +29,12 @@ int budget_batch_depth(qmcp_hip_ctx* c, const uint32_t* bs_starts, const uint32_
     TRY(scan_counts(c, c->cstart, c->boff, ltot));
     TRY(ensure(c, c->ecnt, ((size_t)ltot + 1) * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(c->ecnt.p, 0, ((size_t)ltot + 1) * sizeof(uint32_t), c->stream));
-    qmcp::launch_general_keys(c->stream, false, (const uint32_t*)c->vals[1].p, bs_starts, bs_ends, n, 0, hs[1], nullptr,
-                              nullptr, (uint32_t*)c->ecnt.p, ltot + 1);
+    qmcp::launch_general_keys(c->stream, false, c->vals[1].u32(), bs_starts, bs_ends, n, 0, hs[1], nullptr,
+                              nullptr, c->ecnt.u32(), ltot + 1);
     HIP_TRY(hipGetLastError());
     TRY(scan_counts(c, c->ecnt, c->eoff, ltot));
     TRY(ensure(c, c->cov, (size_t)ltot * sizeof(uint32_t)));
-    qmcp::launch_coverage(c->stream, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, (uint32_t*)c->cov.p);
+    qmcp::launch_coverage(c->stream, c->boff.u32(), c->eoff.u32(), ltot, c->cov.u32());
     HIP_TRY(hipGetLastError());
     return QMCP_OK;
 }
@@ -71,14 +71,14 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     const size_t acc_words = (size_t)qmcp::kBudgetWords + 2 * (size_t)H;
     TRY(ensure(c, c->bg_mask, words * sizeof(uint64_t)));
     TRY(ensure(c, c->bg_acc, acc_words * sizeof(unsigned long long)));
-    unsigned long long* d_acc = (unsigned long long*)c->bg_acc.p;
+    unsigned long long* d_acc = c->bg_acc.as<unsigned long long>();
     unsigned long long* d_curve = d_acc + qmcp::kBudgetWords;
     unsigned long long* d_hist = d_curve + H;
     HIP_TRY(hipMemsetAsync(d_acc, 0, acc_words * sizeof(unsigned long long), st));
 
     // 1: the grouping (the mask it clears is the budget's own: a refused call leaves d_mask alone)
     GroupedReads g;
-    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, (uint64_t*)c->bg_mask.p, g));
+    TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, c->bg_mask.u64(), g));
     const uint64_t placed = g.offs[n_contigs];
 
     // 2-3: the depth histogram over every batch, the curve
@@ -93,14 +93,14 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
         g.view(b, v);
         TRY(gather_batch(c, v, d_starts, d_ends));
         uint32_t ltot = 0;
-        TRY(budget_batch_depth(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.roff.data(), v.lengths,
+        TRY(budget_batch_depth(c, c->bc_starts.u32(), c->bc_ends.u32(), v.roff.data(), v.lengths,
                                v.n_contigs, v.nb, &ltot, &span_max));
         EventPair* ev = bracket();
         if (!ev) return fail(QMCP_EHIP, "event creation failed");
         HIP_TRY(hipEventRecord(ev->a, st));
         {
             KernelSpan sp(c, "k_budget_tally");
-            qmcp::launch_budget_tally(st, (const uint32_t*)c->cov.p, ltot, H, d_acc, d_hist);
+            qmcp::launch_budget_tally(st, c->cov.u32(), ltot, H, d_acc, d_hist);
         }
         HIP_TRY(hipEventRecord(ev->b, st));
         HIP_TRY(hipGetLastError());
@@ -134,7 +134,7 @@ int solve_budget_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     // 4: the probes
     qmcp::BudgetPlan plan;
     plan.start(curve, H, bs.top, span_max, bs.total_bases, placed, budget);
-    uint64_t* masks[2] = {d_mask, (uint64_t*)c->bg_mask.p};
+    uint64_t* masks[2] = {d_mask, c->bg_mask.u64()};
     int best = -1, scratch = 0;
     qmcp_hip_stats best_stats;
     std::memset(&best_stats, 0, sizeof(best_stats));
@@ -221,9 +221,8 @@ int qmcp_hip_solve_budget_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_budget_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                               (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, max_coverage, budget_reads,
-                               flags, curve_out, curve_capacity, (uint64_t*)c->mask.p, stats, bstats));
+    TRY(solve_budget_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), n_reads, contig_lengths,
+        n_contigs, max_coverage, budget_reads, flags, curve_out, curve_capacity, c->mask.u64(), stats, bstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

@@ -71,19 +71,19 @@ int group_reads(qmcp_hip_ctx* c, uint64_t n64, const uint32_t* lengths, uint32_t
     TRY(ensure(c, c->bc_rec[0], (size_t)n * 2 * sizeof(uint32_t)));
     TRY(ensure(c, c->bc_rec[1], (size_t)n * 2 * sizeof(uint32_t)));
     TRY(ensure(c, c->bc_hist, (size_t)256 * n_tiles * sizeof(uint32_t)));
-    TRY(ensure(c, c->bc_spine, (size_t)qmcp::scan_spine_entries(256u * n_tiles) * sizeof(uint32_t) + 16));
+    TRY(ensure(c, c->bc_spine, scan_spine_bytes(256u * n_tiles)));
     if (words) HIP_TRY(hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), st));
     HIP_TRY(hipMemsetAsync(c->bc_err.p, 0, sizeof(uint32_t), st));
     HIP_TRY(hipMemcpyAsync(c->bc_len.p, lengths, (size_t)n_contigs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     queue_keys();
     int k = 0;
     if (n)
-        TRY(radix_sort_records(c, st, (const uint32_t*)c->bc_key.p, n, passes, (uint32_t*)c->bc_hist.p,
-                               (uint32_t*)c->bc_spine.p, c->bc_rec, nm.radix, &k));
+        TRY(radix_sort_records(c, st, c->bc_key.u32(), n, passes, c->bc_hist.u32(),
+                               c->bc_spine.u32(), c->bc_rec, nm.radix, &k));
     *sorted = c->bc_rec[k].p;
     {
         KernelSpan sp(c, nm.bounds);
-        qmcp::launch_bc_bounds(st, *sorted, n, n_groups, (uint32_t*)c->bc_offs.p);
+        qmcp::launch_bc_bounds(st, *sorted, n, n_groups, c->bc_offs.u32());
     }
     HIP_TRY(hipGetLastError());
     offs.assign((size_t)n_groups + 1, 0);
@@ -171,8 +171,8 @@ int group_by_contig(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d
          "k_bc_bounds"},
         [&] {
             KernelSpan sp(c, "k_bc_keys");
-            qmcp::launch_bc_keys(c->stream, d_starts, d_ends, d_ids, (uint32_t)n64, (const uint32_t*)c->bc_len.p, n_contigs,
-                                 (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
+            qmcp::launch_bc_keys(c->stream, d_starts, d_ends, d_ids, (uint32_t)n64, c->bc_len.u32(), n_contigs,
+                                 c->bc_key.u32(), c->bc_err.u32());
         },
         mask_to_clear, g.offs, &g.sorted, &err));
     if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
@@ -205,8 +205,8 @@ struct PlainSolver : BatchSolver {
     uint32_t M;
     explicit PlainSolver(uint32_t m) : M(m) {}
     int solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* bs) override {
-        return solve_on_device(c, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.roff.data(), v.lengths,
-                               v.n_contigs, v.nb, M, (uint64_t*)c->bc_mask.p, bs);
+        return solve_on_device(c, c->bc_starts.u32(), c->bc_ends.u32(), v.roff.data(), v.lengths,
+                               v.n_contigs, v.nb, M, c->bc_mask.u64(), bs);
     }
 };
 
@@ -214,8 +214,7 @@ struct PlainSolver : BatchSolver {
 int gather_batch(qmcp_hip_ctx* c, const BatchView& v, const uint32_t* d_starts, const uint32_t* d_ends) {
     {
         KernelSpan sp(c, "k_bc_gather");
-        qmcp::launch_bc_gather(c->stream, v.records, v.nb, d_starts, d_ends, (uint32_t*)c->bc_starts.p,
-                               (uint32_t*)c->bc_ends.p);
+        qmcp::launch_bc_gather(c->stream, v.records, v.nb, d_starts, d_ends, c->bc_starts.u32(), c->bc_ends.u32());
     }
     HIP_TRY(hipGetLastError());
     return QMCP_OK;
@@ -229,7 +228,7 @@ int solve_scatter_batch(qmcp_hip_ctx* c, BatchView& v, BatchSolver& solver, uint
     TRY(solver.solve(c, v, &bs));
     {
         KernelSpan sp(c, "k_bc_scatter_mask");
-        qmcp::launch_bc_scatter_mask(c->stream, (const uint64_t*)c->bc_mask.p, v.records, v.nb, d_mask);
+        qmcp::launch_bc_scatter_mask(c->stream, c->bc_mask.u64(), v.records, v.nb, d_mask);
     }
     HIP_TRY(hipGetLastError());
     add_batch_stats(sum, bs, first, largest);
@@ -295,9 +294,8 @@ int qmcp_hip_solve_by_contig_host(qmcp_hip_ctx* c, const uint32_t* starts, const
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_by_contig_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                  (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, max_coverage,
-                                  (uint64_t*)c->mask.p, stats));
+    TRY(solve_by_contig_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), n_reads, contig_lengths,
+        n_contigs, max_coverage, c->mask.u64(), stats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

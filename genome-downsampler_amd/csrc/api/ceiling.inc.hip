@@ -18,17 +18,17 @@ struct CeilingNeed : ProfileNeed {
     CeilingNeed(ProfileRun& run, uint32_t regions) : ProfileNeed(run, regions) {}
     const char* name() const override { return "k_ceiling_need"; }
     int upload(qmcp_hip_ctx* c, hipStream_t st) override {
-        HIP_TRY(hipMemsetAsync((unsigned long long*)c->cl_stat.p + qmcp::kCeilMaxNeed, 0, sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(c->cl_stat.as<unsigned long long>() + qmcp::kCeilMaxNeed, 0, sizeof(unsigned long long), st));
         return ProfileNeed::upload(c, st);
     }
     void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
-        const uint32_t* d_rs = (const uint32_t*)c->pf_tab.p;
-        qmcp::launch_ceiling_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, d_rs, d_rs + n_reg,
-                                  d_rs + 2 * (size_t)n_reg, n_reg, pf.default_cap, need, (unsigned long long*)c->cl_stat.p);
+        const uint32_t* d_rs = c->pf_tab.u32();
+        qmcp::launch_ceiling_need(st, c->boff.u32(), c->eoff.u32(), ltot, d_rs, d_rs + n_reg,
+                                  d_rs + 2 * (size_t)n_reg, n_reg, pf.default_cap, need, c->cl_stat.as<unsigned long long>());
     }
     int no_demand(qmcp_hip_ctx* c, hipStream_t st, bool* none) override {
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&largest, (const unsigned long long*)c->cl_stat.p + qmcp::kCeilMaxNeed, sizeof(largest),
+        HIP_TRY(hipMemcpyAsync(&largest, c->cl_stat.as<unsigned long long>() + qmcp::kCeilMaxNeed, sizeof(largest),
                                hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         *none = largest == 0;
@@ -49,9 +49,9 @@ struct CeilingSolver : BatchSolver {
 int CeilingSolver::solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* st_out) {
     const qmcp::CapTable& tab = *pf.tab;
     const uint32_t first_contig = v.first_contig, n_contigs = v.n_contigs, nb = v.nb;
-    const uint32_t* d_starts = (const uint32_t*)c->bc_starts.p;
-    const uint32_t* d_ends = (const uint32_t*)c->bc_ends.p;
-    uint64_t* d_mask = (uint64_t*)c->bc_mask.p;
+    const uint32_t* d_starts = c->bc_starts.u32();
+    const uint32_t* d_ends = c->bc_ends.u32();
+    uint64_t* d_mask = c->bc_mask.u64();
     hipStream_t st = c->stream;
     qmcp::batch_cap_table(tab, v.lengths - first_contig, first_contig, n_contigs, pf.gs, pf.ge, pf.gcap);
     CeilingNeed nd(pf, tab.offs[first_contig + n_contigs] - tab.offs[first_contig]);
@@ -65,7 +65,7 @@ int CeilingSolver::solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* st_out) 
     // the depth of D on the batch's axis, and the kept depth against the caps: boff, eoff and pf_tab are the solve's
     const uint32_t pad = qmcp::pair_credit_pad();
     TRY(ensure(c, c->cl_depth, ((size_t)ltot + pad + 4) * sizeof(uint32_t)));
-    TRY(ensure(c, c->cl_spine, (size_t)(qmcp::scan_spine_entries(ltot + pad) + 1) * sizeof(uint32_t) + 16));
+    TRY(ensure(c, c->cl_spine, scan_spine_bytes(ltot + pad, 1)));
     TRY(ensure(c, c->cl_poff, ((size_t)n_contigs + 1) * sizeof(uint32_t)));
     EventPair ev(c);
     if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
@@ -75,17 +75,16 @@ int CeilingSolver::solve(qmcp_hip_ctx* c, BatchView& v, qmcp_hip_stats* st_out) 
         HIP_TRY(hipMemcpyAsync(c->cl_poff.p, v.poff32.data(), ((size_t)n_contigs + 1) * sizeof(uint32_t),
                                hipMemcpyHostToDevice, st));
         KernelSpan sp(c, "k_pair_credit_events + scan(ceiling)");
-        qmcp::launch_pair_credit_events(st, v.records, nb, d_mask, d_starts, d_ends, (const uint32_t*)c->cl_poff.p, first_contig,
-                                        (uint32_t*)c->cl_depth.p);
-        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->cl_depth.p, ltot + pad, (uint32_t*)c->cl_depth.p,
-                                    (uint32_t*)c->cl_spine.p, false);
+        qmcp::launch_pair_credit_events(st, v.records, nb, d_mask, d_starts, d_ends, c->cl_poff.u32(), first_contig,
+                                        c->cl_depth.u32());
+        qmcp::launch_exclusive_scan(st, c->cl_depth.u32(), ltot + pad, c->cl_depth.u32(), c->cl_spine.u32(), false);
     }
     {
         KernelSpan sp(c, "k_ceiling_check");
-        const uint32_t* d_rs = (const uint32_t*)c->pf_tab.p;
-        qmcp::launch_ceiling_check(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
-                                   (const uint32_t*)c->cl_depth.p + pad, ltot, d_rs, d_rs + nd.n_reg,
-                                   d_rs + 2 * (size_t)nd.n_reg, nd.n_reg, pf.default_cap, (unsigned long long*)c->cl_stat.p);
+        const uint32_t* d_rs = c->pf_tab.u32();
+        qmcp::launch_ceiling_check(st, c->boff.u32(), c->eoff.u32(),
+                                   c->cl_depth.u32() + pad, ltot, d_rs, d_rs + nd.n_reg,
+                                   d_rs + 2 * (size_t)nd.n_reg, nd.n_reg, pf.default_cap, c->cl_stat.as<unsigned long long>());
     }
     HIP_TRY(hipEventRecord(ev.b, st));
     HIP_TRY(hipGetLastError());
@@ -136,7 +135,7 @@ int solve_ceiling_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     {
         KernelSpan sp(c, "k_ceiling_finish");
         qmcp::launch_ceiling_finish(st, d_ids, n64, (flags & QMCP_CEILING_WHOLE_PAIRS) != 0, d_mask,
-                                    (unsigned long long*)c->cl_stat.p);
+                                    c->cl_stat.as<unsigned long long>());
     }
     HIP_TRY(hipEventRecord(ev.b, st));
     HIP_TRY(hipGetLastError());
@@ -184,9 +183,8 @@ int qmcp_hip_solve_ceiling_host(qmcp_hip_ctx* c, const uint32_t* starts, const u
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_ceiling_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, tab, default_cap, flags,
-                                (uint64_t*)c->mask.p, stats, cstats));
+    TRY(solve_ceiling_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), n_reads, contig_lengths,
+        n_contigs, tab, default_cap, flags, c->mask.u64(), stats, cstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

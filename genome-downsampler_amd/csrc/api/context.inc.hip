@@ -1,5 +1,6 @@
 // context.inc.hip -- part of qmcp_api.hip (one translation unit).
-// The solver context, its device arena, per-kernel timing spans, problem checks, contig tables, small stage helpers.
+// The solver context and the owning types of its device arena, pinned blocks, events and streams; per-kernel timing
+// spans, problem checks, contig tables, small stage helpers.
 namespace {
 
 thread_local char g_err[512] = "";
@@ -20,10 +21,50 @@ int fail(int code, const char* fmt, ...) {
                         #expr, hipGetErrorString(_e), __FILE__, __LINE__);                 \
     } while (0)
 
+// Ownership: every device buffer, pinned block, event and stream of a context is a member of one of the four types
+// below and frees itself when the context is deleted.  A feature declares its members in qmcp_hip_ctx and sizes them
+// with ensure / ensure_pinned; there is no list to add them to.
+
+// A device buffer of the arena.  Only ensure() allocates, grows or frees one; everything else reads p (an identity
+// check, a void* parameter) or takes a typed pointer.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    uint32_t* u32() const { return as<uint32_t>(); }
+    uint64_t* u64() const { return as<uint64_t>(); }
 };
+
+// A pinned host block (staging, landing zones); only ensure_pinned() allocates or grows one.
+template <class T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // bytes
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    operator T*() const { return p; }
+};
+
+// An event or a stream: move-only, destroyed with its owner.  Created in place (hipEventCreate(&e.h)).
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    explicit Handle(H raw) : h(raw) {}
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&&) = delete;
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+    H release() { H raw = h; h = nullptr; return raw; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 enum Ev { EV_BEGIN = 0, EV_PREP, EV_SCAN, EV_SORT, EV_SWEEP, EV_MARK, EV_COUNT };
 
@@ -59,11 +100,12 @@ struct SolveRun {
 struct qmcp_hip_ctx {
     int device = 0;
     qmcp_hip_options opt = {};      // which kernels and routes a solve takes where the data would decide (qmcp_hip_set_options)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[EV_COUNT] = {};
-    hipEvent_t ev_in = nullptr;
-    hipStream_t stream2 = nullptr;  // side stream: small read-backs beside the work queued on `stream`
-    hipEvent_t ev_fork = nullptr;   // main stream -> side stream: statistics and heaviest load are final
+    // (members are destroyed last to first: the main stream outlives everything queued on it)
+    Stream stream;
+    Event ev[EV_COUNT];
+    Event ev_in;
+    Stream stream2;  // side stream: small read-backs beside the work queued on `stream`
+    Event ev_fork;  // main stream -> side stream: statistics and heaviest load are final
     // arena (grow-only, reused across solves like a reference solver instance's members)
     DevBuf roff, poff, stats, cstart, boff, ecnt, eoff, selend, spine, hist, spine2, hist2, specsnap, specflags;
     DevBuf keys[2], vals[2];
@@ -75,8 +117,7 @@ struct qmcp_hip_ctx {
     DevBuf pm_desc, pm_work;
     // ... and the grid's tables (pm_grid_plan.h): on the device, in pinned staging, and as last uploaded
     DevBuf pm_grid;
-    uint32_t* h_pm_grid = nullptr;
-    size_t h_pm_grid_cap = 0;
+    PinnedBuf<uint32_t> h_pm_grid;
     std::vector<uint32_t> pm_grid_sent;
     void* pm_grid_dev = nullptr;
     // near-uniform route (kernels/near_uniform.inc.hip): the dominant span of the last call that took it -- the next
@@ -94,18 +135,15 @@ struct qmcp_hip_ctx {
     uint32_t nu_need_ell = 0, nu_need_M = 0, nu_need_rounds = 0;
     bool nu_deferred = false;       // the pending solve's rounds were queued unseen
     DevBuf nu_exc, nu_nadj, nu_ce, nu_state, nu_sus, nu_ckpt, nu_prev;
-    uint32_t* h_nu = nullptr;       // pinned landing zone of the route's state words (8)
-    uint64_t* h_tables = nullptr;  // pinned staging for the contig tables (2 x (n_contigs + 1))
-    size_t h_tables_cap = 0;
-    unsigned long long* h_scalars = nullptr;  // pinned landing zone of the solve's result scalars (4 words)
+    PinnedBuf<uint32_t> h_nu;  // pinned landing zone of the route's state words (8)
+    PinnedBuf<uint64_t> h_tables;  // pinned staging for the contig tables (2 x (n_contigs + 1))
+    PinnedBuf<unsigned long long> h_scalars;  // pinned landing zone of the solve's result scalars (4 words)
     // qmcp_hip_solve_host64: pinned staging, two slots per narrowing thread, and a pinned mask landing zone
-    uint32_t* h_stage = nullptr;
-    size_t h_stage_words = 0;
-    uint64_t* h_mask = nullptr;
-    size_t h_mask_words = 0;
-    std::vector<hipEvent_t> stage_ev;
-    std::vector<hipStream_t> stage_streams;  // copy streams: one DMA engine moves ~29 GB/s, PCIe twice that
-    std::vector<hipEvent_t> stage_done;
+    PinnedBuf<uint32_t> h_stage;
+    PinnedBuf<uint64_t> h_mask;
+    std::vector<Event> stage_ev;
+    std::vector<Stream> stage_streams;  // copy streams: one DMA engine moves ~29 GB/s, PCIe twice that
+    std::vector<Event> stage_done;
     // a solve that has been enqueued but not yet completed (qmcp_hip_solve_device_begin / _end)
     bool pending = false;
     qmcp_hip_stats pend_stats;
@@ -190,10 +228,10 @@ struct qmcp_hip_ctx {
     uint32_t last_iters = 0, last_blocks = 0;
     // the two halves of a solve's enqueue (enqueue_head / enqueue_tail) and what they share
     SolveRun run;
-    uint32_t* h_head = nullptr;       // pinned landing zone of the read-back that picks the route (8 words)
-    uint32_t* h_stats_init = nullptr; // pinned, behind h_head: the statistics' initial values (8 words: ~0, then zeros)
-    hipEvent_t ev_head = nullptr;     // the solve's head (prepare, partition, bucket offsets) has been queued up to here
-    hipEvent_t ev_done = nullptr;     // everything of the solve has been queued up to here
+    PinnedBuf<uint32_t> h_head;       // pinned landing zone of the read-back that picks the route (8 words)
+    uint32_t* h_stats_init = nullptr; // in h_head, behind its 8 words: the statistics' initial values (8 words: ~0, then zeros)
+    Event ev_head;                    // the solve's head (prepare, partition, bucket offsets) has been queued up to here
+    Event ev_done;                    // everything of the solve has been queued up to here
     bool mixed_seen = false;          // a call took the mixed-span route: its arrays are sized up front from then on
     bool sized = false;               // the arena block of the current solve is behind us (growth now is growth mid-solve)
     uint32_t grew_mid_solve = 0;      // buffers that had to grow after the solve's first launch (stats.arena_grown_mid_solve)
@@ -202,9 +240,9 @@ struct qmcp_hip_ctx {
     size_t tables_count = 0;          // contig tables currently on the device (upload_tables)
     void* tables_dev_roff = nullptr;
     void* tables_dev_poff = nullptr;
-    struct Span { const char* name; hipEvent_t a, b; };
+    struct Span { const char* name; Event a, b; };
     std::vector<Span> spans;          // spans of the solve in flight
-    std::vector<hipEvent_t> ev_pool;  // recycled events
+    std::vector<Event> ev_pool;       // recycled events
     struct Acc { std::string name; uint64_t launches; double ms; };
     std::vector<Acc> acc;             // accumulated since the last reset
 };
@@ -213,7 +251,7 @@ namespace {
 
 hipEvent_t pool_event(qmcp_hip_ctx* c) {
     if (!c->ev_pool.empty()) {
-        hipEvent_t e = c->ev_pool.back();
+        hipEvent_t e = c->ev_pool.back().release();
         c->ev_pool.pop_back();
         return e;
     }
@@ -221,6 +259,19 @@ hipEvent_t pool_event(qmcp_hip_ctx* c) {
     if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
+
+// two pooled events, returned to the pool when the scope ends
+struct EventPair {
+    qmcp_hip_ctx* c;
+    hipEvent_t a, b;
+    explicit EventPair(qmcp_hip_ctx* ctx) : c(ctx), a(pool_event(ctx)), b(pool_event(ctx)) {}
+    ~EventPair() {
+        if (a) c->ev_pool.emplace_back(a);
+        if (b) c->ev_pool.emplace_back(b);
+    }
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+};
 
 // RAII bracket around one kernel (or one kernel + its helper launches) when profiling is on
 struct KernelSpan {
@@ -239,7 +290,7 @@ struct KernelSpan {
     ~KernelSpan() {
         if (!c->profiling || !a || !b) return;
         (void)hipEventRecord(b, st);
-        c->spans.push_back({name, a, b});
+        c->spans.push_back({name, Event(a), Event(b)});
     }
 };
 
@@ -252,8 +303,8 @@ void collect_spans(qmcp_hip_ctx* c) {
                 if (a.name == sp.name) { a.launches++; a.ms += ms; found = true; break; }
             if (!found) c->acc.push_back({sp.name, 1, ms});
         }
-        c->ev_pool.push_back(sp.a);
-        c->ev_pool.push_back(sp.b);
+        c->ev_pool.push_back(std::move(sp.a));
+        c->ev_pool.push_back(std::move(sp.b));
     }
     c->spans.clear();
 }
@@ -273,6 +324,19 @@ int ensure(qmcp_hip_ctx* c, DevBuf& b, size_t bytes) {
         b.cap = 0;
     }
     HIP_TRY(hipMalloc(&b.p, bytes));
+    b.cap = bytes;
+    return QMCP_OK;
+}
+
+// The pinned counterpart: grow-only, no floor (a block nobody asked bytes for stays unallocated).  A regrown block
+// holds nothing of the old one: what was last sent is compared on the host side of upload_tables / upload_pm_grid.
+template <class T>
+int ensure_pinned(qmcp_hip_ctx*, PinnedBuf<T>& b, size_t bytes) {
+    if (b.cap >= bytes) return QMCP_OK;
+    if (b.p) HIP_TRY(hipHostFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&b.p, bytes, hipHostMallocDefault));
     b.cap = bytes;
     return QMCP_OK;
 }
@@ -311,12 +375,7 @@ int upload_tables(qmcp_hip_ctx* c, const uint64_t* roff, const Problem& pr) {
     TRY(ensure(c, c->poff, bytes));
     // staged through pinned memory owned by the context: the copies are truly asynchronous and
     // nothing has to wait for them on the host (the previous solve has fully completed)
-    if (c->h_tables_cap < 2 * count) {
-        if (c->h_tables) HIP_TRY(hipHostFree(c->h_tables));
-        c->h_tables = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&c->h_tables, 2 * bytes, hipHostMallocDefault));
-        c->h_tables_cap = 2 * count;
-    }
+    TRY(ensure_pinned(c, c->h_tables, 2 * bytes));
     // the device copies stay valid across solves: skip the upload when nothing changed (a caller
     // that solves the same genome repeatedly saves two small copies per call)
     if (c->tables_count == count && c->tables_dev_roff == c->roff.p && c->tables_dev_poff == c->poff.p &&
@@ -337,12 +396,7 @@ int upload_tables(qmcp_hip_ctx* c, const uint64_t* roff, const Problem& pr) {
 int upload_pm_grid(qmcp_hip_ctx* c, const qmcp::PmGridPlan& grid) {
     const size_t words = grid.words.size(), bytes = words * sizeof(uint32_t);
     TRY(ensure(c, c->pm_grid, bytes));
-    if (c->h_pm_grid_cap < words) {
-        if (c->h_pm_grid) HIP_TRY(hipHostFree(c->h_pm_grid));
-        c->h_pm_grid = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&c->h_pm_grid, bytes, hipHostMallocDefault));
-        c->h_pm_grid_cap = words;
-    }
+    TRY(ensure_pinned(c, c->h_pm_grid, bytes));
     if (c->pm_grid_dev == c->pm_grid.p && c->pm_grid_sent == grid.words) return QMCP_OK;
     std::memcpy(c->h_pm_grid, grid.words.data(), bytes);
     c->pm_grid_sent = grid.words;
@@ -368,11 +422,9 @@ int run_prepare(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_end
         HIP_TRY(hipMemsetAsync(c->cstart.p, 0, ((size_t)pr.ltot + 1) * sizeof(uint32_t), c->stream));
     {
         KernelSpan sp(c, "k_prepare");
-        qmcp::launch_prepare(c->stream, d_starts, d_ends, n, (const uint64_t*)c->roff.p,
-                             (const uint64_t*)c->poff.p, pr.n_contigs, d_keep_mask,
-                             want_keys ? (uint32_t*)c->vals[1].p : nullptr,
-                             want_counts ? (uint32_t*)c->cstart.p : nullptr, (uint32_t*)c->stats.p,
-                             part_shift, want_part_hist ? (uint32_t*)c->hist2.p : nullptr, nullptr,
+        qmcp::launch_prepare(c->stream, d_starts, d_ends, n, c->roff.u64(), c->poff.u64(), pr.n_contigs, d_keep_mask,
+                             want_keys ? c->vals[1].u32() : nullptr, want_counts ? c->cstart.u32() : nullptr,
+                             c->stats.u32(), part_shift, want_part_hist ? c->hist2.u32() : nullptr, nullptr,
                              d_global_digit_hist, nullptr);
     }
     HIP_TRY(hipGetLastError());
@@ -384,13 +436,33 @@ int run_prepare(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_end
     return QMCP_OK;
 }
 
+// The bytes of launch_exclusive_scan's spine over n entries; `more` further entries where a site has always asked for
+// them (most ask for one).
+size_t scan_spine_bytes(uint32_t n, uint32_t more = 0) {
+    return (size_t)(qmcp::scan_spine_entries(n) + more) * sizeof(uint32_t) + 16;
+}
+
+// The rank of every bit of a mask, one step: the words' popcounts, scanned in place (exclusive, the total behind the
+// last word).  queue_mask_ranks only queues the two launches, for buffers sized ahead of a loop or with the rest of a
+// call's arena; mask_ranks sizes `ranks` ((words + 2) words) and `spine` first.  Neither opens a span.
+void queue_mask_ranks(hipStream_t st, const uint64_t* mask, uint32_t words, const DevBuf& ranks, const DevBuf& spine) {
+    qmcp::launch_word_popcounts(st, mask, words, ranks.u32());
+    qmcp::launch_exclusive_scan(st, ranks.u32(), words, ranks.u32(), spine.u32(), true);
+}
+
+int mask_ranks(qmcp_hip_ctx* c, hipStream_t st, const uint64_t* mask, uint32_t words, DevBuf& ranks, DevBuf& spine) {
+    TRY(ensure(c, ranks, ((size_t)words + 2) * sizeof(uint32_t)));
+    TRY(ensure(c, spine, scan_spine_bytes(words + 1, 1)));
+    queue_mask_ranks(st, mask, words, ranks, spine);
+    return QMCP_OK;
+}
+
 int scan_counts(qmcp_hip_ctx* c, DevBuf& counts, DevBuf& out, uint32_t ltot) {
     TRY(ensure(c, out, ((size_t)ltot + 1) * sizeof(uint32_t)));
-    TRY(ensure(c, c->spine, (size_t)qmcp::scan_spine_entries(ltot) * sizeof(uint32_t) + 16));
+    TRY(ensure(c, c->spine, scan_spine_bytes(ltot)));
     {
         KernelSpan sp(c, "scan_positions(3 kernels)");
-        qmcp::launch_exclusive_scan(c->stream, (const uint32_t*)counts.p, ltot, (uint32_t*)out.p,
-                                    (uint32_t*)c->spine.p, true);
+        qmcp::launch_exclusive_scan(c->stream, counts.u32(), ltot, out.u32(), c->spine.u32(), true);
     }
     HIP_TRY(hipGetLastError());
     return QMCP_OK;

@@ -29,31 +29,31 @@ template <typename Build>
 int dedup_sort(qmcp_hip_ctx* c, uint32_t n, const qmcp::DedupSortPlan& plan, const char* what, Build build,
                DedupSorted& out) {
     hipStream_t st = c->stream;
-    uint32_t* hist = (uint32_t*)c->dd_hist.p;
-    uint32_t* spine = (uint32_t*)c->dd_spine.p;
+    uint32_t* hist = c->dd_hist.u32();
+    uint32_t* spine = c->dd_spine.u32();
     out.form = plan.form;
     (void)what;
     if (plan.form == qmcp::DEDUP_SORT_REC32) {
         build(0u, 4u, (const uint32_t*)nullptr, c->dd_bare.p);
         int kin = 0;
-        TRY(radix_sort_records(c, st, (const uint32_t*)c->dd_bare.p, n, plan.rounds[0].passes, hist, spine, c->dd_keys,
+        TRY(radix_sort_records(c, st, c->dd_bare.u32(), n, plan.rounds[0].passes, hist, spine, c->dd_keys,
                                {"k_radix_hist_rec(dedup)", "scan_radix_hist(dedup, 3 kernels)", "k_radix_scatter_rec(dedup)"},
                                &kin));
         out.keys = c->dd_keys[kin].p;
-        out.vals = (const uint32_t*)c->dd_keys[kin].p + 1;
+        out.vals = c->dd_keys[kin].u32() + 1;
         out.stride = 2;
         return QMCP_OK;
     }
     // one u64 sort per round; a later round's keys are built in the order the rounds before it left (the value column)
     WideBufs wb;
     for (uint32_t r = 0; r < plan.n_rounds; ++r) {
-        build(r, 8u, wb.v < 0 ? (const uint32_t*)nullptr : (const uint32_t*)c->dd_vals[wb.v].p, c->dd_keys[wb.k].p);
+        build(r, 8u, wb.v < 0 ? (const uint32_t*)nullptr : c->dd_vals[wb.v].u32(), c->dd_keys[wb.k].p);
         TRY(radix_sort_wide(c, st, n, plan.rounds[r].passes, hist, spine, c->dd_keys, c->dd_vals,
                             {"k_radix_hist(dedup, u64)", "scan_radix_hist(dedup, 3 kernels)", "k_radix_scatter(dedup, u64)"},
                             &wb));
     }
     out.keys = c->dd_keys[wb.k].p;
-    out.vals = (const uint32_t*)c->dd_vals[wb.v].p;
+    out.vals = c->dd_vals[wb.v].u32();
     out.stride = 1;
     return QMCP_OK;
 }
@@ -84,10 +84,10 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
     const uint64_t ltot = poff[n_contigs];
     TRY(ensure(c, c->dd_tab, tab * sizeof(uint64_t) + (size_t)n_contigs * sizeof(uint32_t)));
     TRY(ensure(c, c->dd_stat, 16 * sizeof(uint64_t)));
-    uint64_t* d_poff = (uint64_t*)c->dd_tab.p;
+    uint64_t* d_poff = c->dd_tab.u64();
     uint32_t* d_len = (uint32_t*)(d_poff + tab);
-    uint32_t* d_range = (uint32_t*)c->dd_stat.p;                 // 9 words (of 16)
-    uint64_t* d_counters = (uint64_t*)c->dd_stat.p + 8;          // families, duplicate units, largest family
+    uint32_t* d_range = c->dd_stat.u32();                 // 9 words (of 16)
+    uint64_t* d_counters = c->dd_stat.u64() + 8;          // families, duplicate units, largest family
     HIP_TRY(hipMemcpyAsync(d_poff, poff.data(), tab * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_len, lengths, (size_t)n_contigs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     uint32_t range[16] = {0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -123,18 +123,18 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
     TRY(ensure(c, c->dd_vals[1], (size_t)n * sizeof(uint32_t)));
     TRY(ensure(c, c->dd_hist, (size_t)256 * n_tiles * sizeof(uint32_t)));
     const uint32_t spine_n = std::max(std::max(256u * n_tiles, n + 1), (uint32_t)words + 1);
-    TRY(ensure(c, c->dd_spine, (size_t)(qmcp::scan_spine_entries(spine_n) + 1) * sizeof(uint32_t) + 16));
+    TRY(ensure(c, c->dd_spine, scan_spine_bytes(spine_n, 1)));
     TRY(ensure(c, c->dd_flag, ((size_t)n + 2) * sizeof(uint32_t)));
     TRY(ensure(c, c->dd_head, ((size_t)n + 2) * sizeof(uint32_t)));
     TRY(ensure(c, c->dd_surv, words * 8 + 16));
     TRY(ensure(c, c->dd_words, (words + 2) * sizeof(uint32_t)));
     TRY(ensure(c, c->dd_histo, (size_t)std::max(hist_bins, 1u) * sizeof(uint64_t)));
     if (pairs) TRY(ensure(c, c->dd_cid, ((size_t)n + 2) * sizeof(uint32_t)));
-    uint32_t* flag = (uint32_t*)c->dd_flag.p;
-    uint32_t* headpos = (uint32_t*)c->dd_head.p;
-    uint32_t* cid = pairs ? (uint32_t*)c->dd_cid.p : nullptr;
-    uint64_t* surv = (uint64_t*)c->dd_surv.p;
-    uint32_t* spine = (uint32_t*)c->dd_spine.p;
+    uint32_t* flag = c->dd_flag.u32();
+    uint32_t* headpos = c->dd_head.u32();
+    uint32_t* cid = pairs ? c->dd_cid.u32() : nullptr;
+    uint64_t* surv = c->dd_surv.u64();
+    uint32_t* spine = c->dd_spine.u32();
 
     HIP_TRY(hipEventRecord(ev_b.a, st));
     HIP_TRY(hipMemsetAsync(surv, 0, words * 8, st));
@@ -206,20 +206,18 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
     }
     {
         KernelSpan sp(c, "k_dd_family_stats");
-        qmcp::launch_dd_family_stats(st, headpos, flag + n_act, n_act, hist_bins, (uint64_t*)c->dd_histo.p, d_counters);
+        qmcp::launch_dd_family_stats(st, headpos, flag + n_act, n_act, hist_bins, c->dd_histo.u64(), d_counters);
     }
     // 4. the survivors' count
     {
         KernelSpan sp(c, "count survivors(popcounts, scan)");
-        qmcp::launch_word_popcounts(st, surv, (uint32_t)words, (uint32_t*)c->dd_words.p);
-        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->dd_words.p, (uint32_t)words, (uint32_t*)c->dd_words.p, spine,
-                                    true);
+        queue_mask_ranks(st, surv, (uint32_t)words, c->dd_words, c->dd_spine);
     }
     HIP_TRY(hipEventRecord(ev_b.b, st));
     HIP_TRY(hipGetLastError());
     uint32_t n_surv = 0;
     uint64_t counters[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(&n_surv, (uint32_t*)c->dd_words.p + words, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_surv, c->dd_words.u32() + words, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, st));
     if (hist_out && hist_bins)
         HIP_TRY(hipMemcpyAsync(hist_out, c->dd_histo.p, (size_t)hist_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -244,22 +242,20 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
         HIP_TRY(hipEventRecord(ev_c.a, st));
         {
             KernelSpan sp(c, "k_dd_compact");
-            qmcp::launch_dd_compact(st, d_starts, d_ends, d_ids, surv, (const uint32_t*)c->dd_words.p, n,
-                                    (uint32_t*)c->dd_cs.p, (uint32_t*)c->dd_ce.p, (uint32_t*)c->dd_ci.p,
-                                    (uint32_t*)c->dd_map.p);
+            qmcp::launch_dd_compact(st, d_starts, d_ends, d_ids, surv, c->dd_words.u32(), n, c->dd_cs.u32(),
+                                    c->dd_ce.u32(), c->dd_ci.u32(), c->dd_map.u32());
         }
         HIP_TRY(hipEventRecord(ev_c.b, st));
         HIP_TRY(hipGetLastError());
-        TRY(solve_by_contig_on_device(c, (const uint32_t*)c->dd_cs.p, (const uint32_t*)c->dd_ce.p,
-                                      (const uint32_t*)c->dd_ci.p, n_surv, lengths, n_contigs, M, (uint64_t*)c->dd_maskc.p,
-                                      &plain));
+        TRY(solve_by_contig_on_device(c, c->dd_cs.u32(), c->dd_ce.u32(), c->dd_ci.u32(), n_surv, lengths, n_contigs, M,
+            c->dd_maskc.u64(), &plain));
         ds.ms_dedup += elapsed(ev_c.a, ev_c.b);
     }
     HIP_TRY(hipEventRecord(ev_c.a, st));
     HIP_TRY(hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), st));
     if (n_surv) {
         KernelSpan sp(c, "k_expand_mask_reads(dedup)");
-        qmcp::launch_expand_mask_reads(st, (const uint64_t*)c->dd_maskc.p, (const uint32_t*)c->dd_map.p, n_surv, d_mask);
+        qmcp::launch_expand_mask_reads(st, c->dd_maskc.u64(), c->dd_map.u32(), n_surv, d_mask);
     }
     if ((flags & QMCP_DEDUP_COMPLETE_PAIRS) && n_surv) {
         KernelSpan sp(c, "k_complete_pairs(dedup)");
@@ -321,11 +317,10 @@ int qmcp_hip_solve_dedup_host(qmcp_hip_ctx* c, const uint32_t* starts, const uin
         if (qualities) HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, c->stream));
         if (tags) HIP_TRY(hipMemcpyAsync(c->dd_tags.p, tags, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_dedup_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                              (const uint32_t*)c->in_aux0.p, tags ? (const uint32_t*)c->dd_tags.p : nullptr,
-                              qualities ? (const uint32_t*)c->in_aux1.p : nullptr, n_reads, contig_lengths, n_contigs,
-                              max_coverage, flags, (uint64_t*)c->mask.p, dup_mask_out ? (uint64_t*)c->dd_dupm.p : nullptr,
-                              hist_out, hist_bins, stats, dstats));
+    TRY(solve_dedup_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(),
+        tags ? c->dd_tags.u32() : nullptr, qualities ? c->in_aux1.u32() : nullptr, n_reads, contig_lengths, n_contigs,
+        max_coverage, flags, c->mask.u64(), dup_mask_out ? c->dd_dupm.u64() : nullptr, hist_out, hist_bins, stats,
+        dstats));
     if (words) {
         HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         if (dup_mask_out)

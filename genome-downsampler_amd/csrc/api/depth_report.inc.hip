@@ -70,13 +70,13 @@ int depth_report_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     TRY(ensure(c, c->dr_hist, 2 * (size_t)n_bins * 8 + 16));
     TRY(ensure(c, c->dr_sums, (size_t)qmcp::depth_chunks((uint32_t)most) * 8 + 16));
     TRY(ensure(c, c->dr_cnt, 32));
-    uint32_t* d_len = (uint32_t*)c->dr_tab.p;
+    uint32_t* d_len = c->dr_tab.u32();
     uint32_t* d_boff = d_len + n_contigs;
     uint32_t* d_ci = d_boff + n_contigs;      // 3 x n_contigs
     uint32_t* d_ri = d_ci + 3 * (size_t)n_contigs;  // 3 x n_reg
-    uint64_t* d_acc64 = (uint64_t*)c->dr_acc.p;
+    uint64_t* d_acc64 = c->dr_acc.u64();
     uint32_t* d_acc32 = (uint32_t*)(d_acc64 + 5 * (size_t)n_rows);
-    uint64_t* d_cnt = (uint64_t*)c->dr_cnt.p;
+    uint64_t* d_cnt = c->dr_cnt.u64();
     uint32_t* d_err = (uint32_t*)(d_cnt + 2);
     EventPair ev(c);
     if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
@@ -129,18 +129,18 @@ int depth_report_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
         {
             KernelSpan sp(c, "k_depth_events");
             qmcp::launch_depth_events(st, d_starts, d_ends, d_ids, n, d_mask, d_len, d_boff, n_contigs, c0, c1,
-                                      (uint64_t*)c->dr_ev.p, d_cnt, d_err);
+                                      c->dr_ev.u64(), d_cnt, d_err);
         }
         {
             KernelSpan sp(c, "k_depth_chunk_sums + k_depth_spine");
-            qmcp::launch_depth_sums(st, (const uint64_t*)c->dr_ev.p, P, (uint64_t*)c->dr_sums.p);
+            qmcp::launch_depth_sums(st, c->dr_ev.u64(), P, c->dr_sums.u64());
         }
         {
             KernelSpan sp(c, "k_depth_consume");
-            qmcp::launch_depth_consume(st, (const uint64_t*)c->dr_ev.p, P, (const uint64_t*)c->dr_sums.p, M, d_ci,
+            qmcp::launch_depth_consume(st, c->dr_ev.u64(), P, c->dr_sums.u64(), M, d_ci,
                                        d_ci + bt.n_contigs, d_ci + 2 * (size_t)bt.n_contigs, n_ci, d_ri, d_ri + n_ri,
                                        d_ri + 2 * (size_t)n_ri, n_ri, dc.has_regions, n_rows, d_acc64, d_acc32, n_bins,
-                                       (uint64_t*)c->dr_hist.p);
+                                       c->dr_hist.u64());
         }
         HIP_TRY(hipGetLastError());
         if (dc.batches.size() > 1) HIP_TRY(hipStreamSynchronize(st));
@@ -151,7 +151,7 @@ int depth_report_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
         HIP_TRY(hipMemsetAsync(c->dr_ev.p, 0, 8, st));
         KernelSpan sp(c, "k_depth_events");
         qmcp::launch_depth_events(st, d_starts, d_ends, d_ids, n, d_mask, d_len, d_boff, n_contigs, 0, 0,
-                                  (uint64_t*)c->dr_ev.p, d_cnt, d_err);
+                                  c->dr_ev.u64(), d_cnt, d_err);
     }
     HIP_TRY(hipEventRecord(ev.b, st));
     HIP_TRY(hipGetLastError());
@@ -250,8 +250,8 @@ int qmcp_hip_depth_report_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
         if (keep_mask)
             HIP_TRY(hipMemcpyAsync(c->in_aux1.p, keep_mask, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     }
-    return depth_report_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                  (const uint32_t*)c->in_aux0.p, keep_mask ? (const uint64_t*)c->in_aux1.p : nullptr, n_reads,
+    return depth_report_on_device(c, c->in_starts.u32(), c->in_ends.u32(),
+                                  c->in_aux0.u32(), keep_mask ? c->in_aux1.u64() : nullptr, n_reads,
                                   contig_lengths, n_contigs, max_coverage, dc, n_bins, contig_rows, region_rows,
                                   n_region_rows_out, hist_in, hist_kept, stats);
 }

@@ -28,14 +28,14 @@ int depth_track_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
     TRY(ensure(c, c->dr_sums, (size_t)max_chunks * 8 + 16));
     TRY(ensure(c, c->dr_cnt, 32));
     TRY(ensure(c, c->dt_cnt, ((size_t)3 * max_chunks + 2) / 2 * 8 + 24));
-    uint32_t* d_len = (uint32_t*)c->dr_tab.p;
+    uint32_t* d_len = c->dr_tab.u32();
     uint32_t* d_boff = d_len + n_contigs;
     uint32_t* d_ci = d_boff + n_contigs;            // 3 x n_contigs
     uint32_t* d_ri = d_ci + 3 * (size_t)n_contigs;  // 3 x n_reg
-    uint64_t* d_cnt = (uint64_t*)c->dr_cnt.p;
+    uint64_t* d_cnt = c->dr_cnt.u64();
     uint32_t* d_err = (uint32_t*)(d_cnt + 2);
-    uint32_t* d_tc = (uint32_t*)c->dt_cnt.p;
-    uint64_t* d_tot = (uint64_t*)c->dt_cnt.p + ((size_t)3 * max_chunks + 2) / 2;  // (8-byte aligned, behind the counts)
+    uint32_t* d_tc = c->dt_cnt.u32();
+    uint64_t* d_tot = c->dt_cnt.u64() + ((size_t)3 * max_chunks + 2) / 2;  // (8-byte aligned, behind the counts)
     EventPair ev(c);
     if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
     HIP_TRY(hipMemcpyAsync(d_len, lengths, (size_t)n_contigs * 4, hipMemcpyHostToDevice, st));
@@ -84,11 +84,11 @@ int depth_track_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
         {
             KernelSpan sp(c, "k_depth_events");
             qmcp::launch_depth_events(st, d_starts, d_ends, d_ids, n, d_mask, d_len, d_boff, n_contigs, c0, c1,
-                                      (uint64_t*)c->dr_ev.p, d_cnt, d_err);
+                                      c->dr_ev.u64(), d_cnt, d_err);
         }
         {
             KernelSpan sp(c, "k_depth_chunk_sums + k_depth_spine");
-            qmcp::launch_depth_sums(st, (const uint64_t*)c->dr_ev.p, P, (uint64_t*)c->dr_sums.p);
+            qmcp::launch_depth_sums(st, c->dr_ev.u64(), P, c->dr_sums.u64());
         }
         // the scope's intervals: the merged regions when the call has regions (none in this batch: nothing is in scope)
         const uint32_t* s_lo = dc.has_regions ? d_ri : d_ci;
@@ -96,7 +96,7 @@ int depth_track_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
         const uint32_t n_s = dc.has_regions ? n_ri : n_ci;
         {
             KernelSpan sp(c, "k_track_count + k_track_spine");
-            qmcp::launch_track_count(st, (const uint64_t*)c->dr_ev.p, P, (const uint64_t*)c->dr_sums.p, M, flags, depth_cap,
+            qmcp::launch_track_count(st, c->dr_ev.u64(), P, c->dr_sums.u64(), M, flags, depth_cap,
                                      s_lo, s_hi, n_s, d_tc, d_tot);
         }
         HIP_TRY(hipGetLastError());
@@ -110,9 +110,9 @@ int depth_track_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
             TRY(ensure(c, c->dt_runs, (size_t)tot[0] * sizeof(qmcp_hip_track_run)));
             {
                 KernelSpan sp(c, "k_track_emit");
-                qmcp::launch_track_emit(st, (const uint64_t*)c->dr_ev.p, P, (const uint64_t*)c->dr_sums.p, M, flags,
+                qmcp::launch_track_emit(st, c->dr_ev.u64(), P, c->dr_sums.u64(), M, flags,
                                         depth_cap, s_lo, s_hi, n_s, d_ci, d_ci + bt.n_contigs,
-                                        d_ci + 2 * (size_t)bt.n_contigs, n_ci, d_tc, (qmcp_hip_track_run*)c->dt_runs.p);
+                                        d_ci + 2 * (size_t)bt.n_contigs, n_ci, d_tc, c->dt_runs.as<qmcp_hip_track_run>());
             }
             HIP_TRY(hipGetLastError());
             staged.resize((size_t)(total_runs + tot[0]));
@@ -130,7 +130,7 @@ int depth_track_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
         HIP_TRY(hipMemsetAsync(c->dr_ev.p, 0, 8, st));
         KernelSpan sp(c, "k_depth_events");
         qmcp::launch_depth_events(st, d_starts, d_ends, d_ids, n, d_mask, d_len, d_boff, n_contigs, 0, 0,
-                                  (uint64_t*)c->dr_ev.p, d_cnt, d_err);
+                                  c->dr_ev.u64(), d_cnt, d_err);
     }
     HIP_TRY(hipEventRecord(ev.b, st));
     HIP_TRY(hipGetLastError());
@@ -205,10 +205,9 @@ int qmcp_hip_depth_track_host(qmcp_hip_ctx* c, const uint32_t* starts, const uin
         if (keep_mask)
             HIP_TRY(hipMemcpyAsync(c->in_aux1.p, keep_mask, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     }
-    return depth_track_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                 (const uint32_t*)c->in_aux0.p, keep_mask ? (const uint64_t*)c->in_aux1.p : nullptr, n_reads,
-                                 contig_lengths, n_contigs, max_coverage, dc, flags, depth_cap, runs, run_capacity, n_runs_out,
-                                 stats);
+    return depth_track_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(),
+                                 keep_mask ? c->in_aux1.u64() : nullptr, n_reads, contig_lengths, n_contigs,
+                                 max_coverage, dc, flags, depth_cap, runs, run_capacity, n_runs_out, stats);
 }
 
 int qmcp_hip_depth_track_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_ends,

@@ -28,23 +28,20 @@ int coverage_common(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* end
         TRY(ensure(c, c->mask, words * 8));
         c->mask_reads = n64;
         HIP_TRY(hipMemcpyAsync(c->mask.p, keep_mask, words * 8, hipMemcpyHostToDevice, c->stream));
-        d_keep = (const uint64_t*)c->mask.p;
+        d_keep = c->mask.u64();
     }
     TRY(upload_tables(c, roff, pr));
     uint32_t hs[3];
-    TRY(run_prepare(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, pr, d_keep,
-                    true, true, false, 0, nullptr, hs));
+    TRY(run_prepare(c, c->in_starts.u32(), c->in_ends.u32(), pr, d_keep, true, true, false, 0, nullptr, hs));
     TRY(scan_counts(c, c->cstart, c->boff, ltot));
     TRY(ensure(c, c->ecnt, ((size_t)ltot + 1) * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(c->ecnt.p, 0, ((size_t)ltot + 1) * sizeof(uint32_t), c->stream));
-    qmcp::launch_general_keys(c->stream, false, (const uint32_t*)c->vals[1].p,
-                              (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, n, 0,
-                              hs[1], d_keep, nullptr, (uint32_t*)c->ecnt.p, ltot + 1);
+    qmcp::launch_general_keys(c->stream, false, c->vals[1].u32(), c->in_starts.u32(), c->in_ends.u32(), n, 0, hs[1],
+                              d_keep, nullptr, c->ecnt.u32(), ltot + 1);
     HIP_TRY(hipGetLastError());
     TRY(scan_counts(c, c->ecnt, c->eoff, ltot));
     TRY(ensure(c, c->cov, (size_t)ltot * sizeof(uint32_t)));
-    qmcp::launch_coverage(c->stream, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot,
-                          (uint32_t*)c->cov.p);
+    qmcp::launch_coverage(c->stream, c->boff.u32(), c->eoff.u32(), ltot, c->cov.u32());
     HIP_TRY(hipGetLastError());
     if (cov_out)
         HIP_TRY(hipMemcpyAsync(cov_out, c->cov.p, (size_t)ltot * sizeof(uint32_t), hipMemcpyDeviceToHost,
@@ -92,7 +89,7 @@ int upload_columns(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t* ends
         ends_on_device = differs.load() == 0;
         if (ends_on_device) {
             *columns_sent = 1;
-            qmcp::launch_fill_ends(c->stream, (const uint32_t*)c->in_starts.p, (uint32_t)n_reads, span0, (uint32_t*)c->in_ends.p);
+            qmcp::launch_fill_ends(c->stream, c->in_starts.u32(), (uint32_t)n_reads, span0, c->in_ends.u32());
         }
     } else if (hipMemcpyAsync(c->in_starts.p, starts, nb, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
         return fail(QMCP_EHIP, "H2D copy failed: %s", hipGetErrorString(hipGetLastError()));
@@ -155,54 +152,7 @@ void qmcp_hip_destroy(qmcp_hip_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    DevBuf* bufs[] = {&c->roff, &c->poff, &c->stats, &c->cstart, &c->boff, &c->ecnt, &c->eoff,
-                      &c->selend, &c->spine, &c->hist, &c->spine2, &c->hist2, &c->keys[0], &c->keys[1], &c->vals[0],
-                      &c->vals[1], &c->in_starts, &c->in_ends, &c->in_aux0, &c->in_aux1, &c->mask,
-                      &c->cov, &c->amp, &c->scalars, &c->next_head, &c->ranges, &c->rankamb, &c->pm_desc, &c->pm_work, &c->pm_grid, &c->segs, &c->specsnap, &c->specflags, &c->rings, &c->evpk, &c->evlast, &c->kidx, &c->f_starts, &c->f_ends, &c->f_map, &c->f_words, &c->f_mask, &c->nu_exc, &c->nu_nadj, &c->nu_ce, &c->nu_state, &c->nu_sus, &c->nu_ckpt, &c->nu_prev,
-                      &c->bc_key, &c->bc_rec[0], &c->bc_rec[1], &c->bc_hist, &c->bc_spine, &c->bc_offs, &c->bc_err, &c->bc_len,
-                      &c->bc_starts, &c->bc_ends, &c->bc_mask, &c->af_ids, &c->af_ids_c, &c->af_len, &c->af_tab,
-                      &c->af_err, &c->qc_words, &c->qc_tab, &c->qc_bare, &c->qc_keys[0], &c->qc_keys[1],
-                      &c->qc_vals[0], &c->qc_vals[1], &c->qc_hist, &c->qc_spine, &c->qc_kb, &c->qc_end, &c->qc_head,
-                      &c->tg_ps, &c->tg_pe, &c->tg_off, &c->tg_offw, &c->tg_q, &c->tg_tab,
-                      &c->dr_ev, &c->dr_tab, &c->dr_acc, &c->dr_hist, &c->dr_sums, &c->dr_cnt, &c->dt_cnt, &c->dt_runs,
-                      &c->ld_starts[0], &c->ld_starts[1], &c->ld_ends[0], &c->ld_ends[1], &c->ld_orig[0], &c->ld_orig[1],
-                      &c->ld_words, &c->ld_spine, &c->ld_offs[0], &c->ld_offs[1], &c->ld_levels, &c->ld_mask0,
-                      &c->st_strata, &c->st_rows,
-                      &c->dd_tab, &c->dd_stat, &c->dd_bare, &c->dd_keys[0], &c->dd_keys[1], &c->dd_vals[0], &c->dd_vals[1],
-                      &c->dd_hist, &c->dd_spine, &c->dd_flag, &c->dd_head, &c->dd_cid, &c->dd_surv, &c->dd_words,
-                      &c->dd_histo, &c->dd_cs, &c->dd_ce, &c->dd_ci, &c->dd_map, &c->dd_maskc, &c->dd_tags, &c->dd_dupm,
-                      &c->pf_need, &c->pf_tab, &c->pf_stat,
-                      &c->pr_in, &c->pr_rest, &c->pr_words, &c->pr_spine, &c->pr_offs[0], &c->pr_offs[1], &c->pr_poff,
-                      &c->pr_credit, &c->pr_cspine, &c->pr_starts, &c->pr_ends, &c->pr_orig, &c->pr_mask, &c->pr_need,
-                      &c->pr_stat, &c->tp_ids, &c->tp_flags, &c->tp_sizes, &c->tp_stat,
-                      &c->tq_tab, &c->tq_cap, &c->tq_flags, &c->tq_stat,
-                      &c->cl_poff, &c->cl_depth, &c->cl_spine, &c->cl_stat, &c->bg_acc, &c->bg_mask,
-                      &c->rp_starts[0], &c->rp_starts[1], &c->rp_ends[0], &c->rp_ends[1], &c->rp_orig[0], &c->rp_orig[1],
-                      &c->rp_words, &c->rp_spine, &c->rp_offs[0], &c->rp_offs[1], &c->rp_kept, &c->rp_taken, &c->rp_lmask,
-                      &c->rp_stat, &c->rp_labels, &c->rp_mask0};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (int i = 0; i < EV_COUNT; ++i)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-    for (auto& sp : c->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->h_tables) (void)hipHostFree(c->h_tables);
-    if (c->h_pm_grid) (void)hipHostFree(c->h_pm_grid);
-    if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_mask) (void)hipHostFree(c->h_mask);
-    for (hipEvent_t e : c->stage_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->stage_done) (void)hipEventDestroy(e);
-    for (hipStream_t st : c->stage_streams) (void)hipStreamDestroy(st);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_head) (void)hipEventDestroy(c->ev_head);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    if (c->h_head) (void)hipHostFree(c->h_head);
-    if (c->h_nu) (void)hipHostFree(c->h_nu);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // (every buffer, pinned block, event and stream is a member that frees itself: context.inc.hip)
 }
 
 int qmcp_hip_set_profiling(qmcp_hip_ctx* c, int enabled) {
@@ -264,43 +214,28 @@ int qmcp_hip_solve_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t*
     TRY(ensure(c, c->in_starts, nb));
     TRY(ensure(c, c->in_ends, nb));
     TRY(ensure(c, c->mask, words * sizeof(uint64_t)));
-    hipEvent_t t0, t1, t2, t3;
-    HIP_TRY(hipEventCreate(&t0)); HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventCreate(&t2)); HIP_TRY(hipEventCreate(&t3));
-    int rc = QMCP_OK;
+    EventPair up(c), down(c);  // the upload's two timing events, the read-back's two
+    if (!up.a || !up.b || !down.a || !down.b) return fail(QMCP_EHIP, "event creation failed");
     uint32_t sent_columns = 2;
-    do {
-        if (hipEventRecord(t0, c->stream) != hipSuccess) { rc = fail(QMCP_EHIP, "event record"); break; }
-        if (nb) {
-            rc = upload_columns(c, starts, ends, n_reads, &sent_columns);
-            if (rc != QMCP_OK) break;
-        }
-        (void)hipEventRecord(t1, c->stream);
-        c->mask_reads = 0;
-        rc = solve_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                             contig_read_offsets, contig_lengths, n_contigs, n_reads, max_coverage,
-                             (uint64_t*)c->mask.p, stats);
-        if (rc != QMCP_OK) break;
-        c->mask_reads = n_reads;
-        (void)hipEventRecord(t2, c->stream);
-        if (words) {
-            if (hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t),
-                               hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
-                rc = fail(QMCP_EHIP, "D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
-                break;
-            }
-        }
-        (void)hipEventRecord(t3, c->stream);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(QMCP_EHIP, "stream sync failed"); break; }
-        if (stats) {
-            stats->ms_h2d = elapsed(t0, t1);
-            stats->ms_d2h = elapsed(t2, t3);
-            stats->columns_sent = sent_columns;
-        }
-    } while (0);
-    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
-    (void)hipEventDestroy(t2); (void)hipEventDestroy(t3);
-    return rc;
+    if (hipEventRecord(up.a, c->stream) != hipSuccess) return fail(QMCP_EHIP, "event record");
+    if (nb) TRY(upload_columns(c, starts, ends, n_reads, &sent_columns));
+    (void)hipEventRecord(up.b, c->stream);
+    c->mask_reads = 0;
+    TRY(solve_on_device(c, c->in_starts.u32(), c->in_ends.u32(), contig_read_offsets, contig_lengths, n_contigs,
+                        n_reads, max_coverage, c->mask.u64(), stats));
+    c->mask_reads = n_reads;
+    (void)hipEventRecord(down.a, c->stream);
+    if (words && hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                c->stream) != hipSuccess)
+        return fail(QMCP_EHIP, "D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
+    (void)hipEventRecord(down.b, c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(QMCP_EHIP, "stream sync failed");
+    if (stats) {
+        stats->ms_h2d = elapsed(up.a, up.b);
+        stats->ms_d2h = elapsed(down.a, down.b);
+        stats->columns_sent = sent_columns;
+    }
+    return QMCP_OK;
 }
 
 int qmcp_hip_solve_host64(qmcp_hip_ctx* c, const uint64_t* start_inds, const uint64_t* end_inds,
@@ -332,24 +267,12 @@ int qmcp_hip_solve_host64(qmcp_hip_ctx* c, const uint64_t* start_inds, const uin
     if (hw != 0 && T > hw) T = hw;
     if (T > n_chunks) T = (unsigned)(n_chunks ? n_chunks : 1);
     const size_t stage_words = (size_t)T * 2 * 2 * kChunk;  // T threads x 2 slots x (starts + ends)
-    if (c->h_stage_words < stage_words) {
-        if (c->h_stage) HIP_TRY(hipHostFree(c->h_stage));
-        c->h_stage = nullptr;
-        c->h_stage_words = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->h_stage, stage_words * sizeof(uint32_t), hipHostMallocDefault));
-        c->h_stage_words = stage_words;
-    }
-    if (c->h_mask_words < words) {
-        if (c->h_mask) HIP_TRY(hipHostFree(c->h_mask));
-        c->h_mask = nullptr;
-        c->h_mask_words = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->h_mask, (words ? words : 1) * sizeof(uint64_t), hipHostMallocDefault));
-        c->h_mask_words = words ? words : 1;
-    }
+    TRY(ensure_pinned(c, c->h_stage, stage_words * sizeof(uint32_t)));
+    TRY(ensure_pinned(c, c->h_mask, words * sizeof(uint64_t)));
     while (c->stage_ev.size() < (size_t)T * 2) {
         hipEvent_t e = nullptr;
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->stage_ev.push_back(e);
+        c->stage_ev.emplace_back(e);
     }
     unsigned n_streams = 4;
     if (c->opt.copy_streams) n_streams = c->opt.copy_streams;
@@ -359,9 +282,9 @@ int qmcp_hip_solve_host64(qmcp_hip_ctx* c, const uint64_t* start_inds, const uin
         hipStream_t st = nullptr;
         hipEvent_t e = nullptr;
         HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        c->stage_streams.push_back(st);
+        c->stage_streams.emplace_back(st);
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->stage_done.push_back(e);
+        c->stage_done.emplace_back(e);
     }
     const clock::time_point t_copy = clock::now();
     // One span for every read (all of reads-gen's inputs): only the starts cross the link and the device
@@ -402,8 +325,8 @@ int qmcp_hip_solve_host64(qmcp_hip_ctx* c, const uint64_t* start_inds, const uin
                     ss[i] = (uint32_t)a;
                     ee[i] = (uint32_t)b;
                 }
-                ok = hipMemcpyAsync((uint32_t*)c->in_starts.p + lo, ss, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess &&
-                     hipMemcpyAsync((uint32_t*)c->in_ends.p + lo, ee, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess;
+                ok = hipMemcpyAsync(c->in_starts.u32() + lo, ss, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess &&
+                     hipMemcpyAsync(c->in_ends.u32() + lo, ee, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess;
             } else if (pass == kStartsChecked) {
                 for (size_t i = 0; i < cnt; ++i) {
                     const uint64_t a = s64[i], b = e64[i];
@@ -411,10 +334,10 @@ int qmcp_hip_solve_host64(qmcp_hip_ctx* c, const uint64_t* start_inds, const uin
                     differs |= (b - a) ^ span0;
                     ss[i] = (uint32_t)a;
                 }
-                ok = hipMemcpyAsync((uint32_t*)c->in_starts.p + lo, ss, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess;
+                ok = hipMemcpyAsync(c->in_starts.u32() + lo, ss, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess;
             } else {
                 for (size_t i = 0; i < cnt; ++i) ee[i] = (uint32_t)e64[i];  // (range-checked in the first pass)
-                ok = hipMemcpyAsync((uint32_t*)c->in_ends.p + lo, ee, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess;
+                ok = hipMemcpyAsync(c->in_ends.u32() + lo, ee, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, cs) == hipSuccess;
             }
             if (!ok || hipEventRecord(ev, cs) != hipSuccess) { hip_failed = 1; return; }
         }
@@ -445,13 +368,13 @@ int qmcp_hip_solve_host64(qmcp_hip_ctx* c, const uint64_t* start_inds, const uin
         HIP_TRY(hipEventRecord(c->stage_done[i], c->stage_streams[i]));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->stage_done[i], 0));
     }
-    if (send_starts_only) qmcp::launch_fill_ends(c->stream, (const uint32_t*)c->in_starts.p, (uint32_t)n, (uint32_t)span0,
-                                                 (uint32_t*)c->in_ends.p);
+    if (send_starts_only) qmcp::launch_fill_ends(c->stream, c->in_starts.u32(), (uint32_t)n, (uint32_t)span0,
+                                                 c->in_ends.u32());
     for (unsigned i = 0; i < n_streams; ++i) HIP_TRY(hipStreamSynchronize(c->stage_streams[i]));  // (for the breakdown)
     const float ms_copy = ms_since(t_copy);
     const clock::time_point t_solve = clock::now();
-    TRY(solve_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, contig_read_offsets,
-                        contig_lengths, n_contigs, n_reads, max_coverage, (uint64_t*)c->mask.p, stats));
+    TRY(solve_on_device(c, c->in_starts.u32(), c->in_ends.u32(), contig_read_offsets,
+                        contig_lengths, n_contigs, n_reads, max_coverage, c->mask.u64(), stats));
     const float ms_solve = ms_since(t_solve);
     c->mask_reads = n_reads;
     const clock::time_point t_d2h = clock::now();
@@ -484,22 +407,17 @@ int qmcp_hip_kept_indices_host(qmcp_hip_ctx* c, uint64_t n_reads, uint64_t* indi
         return fail(QMCP_EINVAL, "the context holds no keep mask of %llu reads (call a host solve first)",
                     (unsigned long long)n_reads);
     const uint32_t words = (uint32_t)((n_reads + 63) / 64);
-    TRY(ensure(c, c->f_words, ((size_t)words + 2) * sizeof(uint32_t)));
-    TRY(ensure(c, c->spine, (size_t)(qmcp::scan_spine_entries(words + 1) + 1) * sizeof(uint32_t) + 16));
-    qmcp::launch_word_popcounts(c->stream, (const uint64_t*)c->mask.p, words, (uint32_t*)c->f_words.p);
-    qmcp::launch_exclusive_scan(c->stream, (const uint32_t*)c->f_words.p, words, (uint32_t*)c->f_words.p,
-                                (uint32_t*)c->spine.p, true);
+    TRY(mask_ranks(c, c->stream, c->mask.u64(), words, c->f_words, c->spine));
     HIP_TRY(hipGetLastError());
     uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, (uint32_t*)c->f_words.p + words, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&total, c->f_words.u32() + words, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n_out = total;
     if (total == 0) return QMCP_OK;
     if (!indices_out || capacity < total) return fail(QMCP_EINVAL, "indices_out holds %llu entries, %u are kept",
                                                       (unsigned long long)capacity, total);
     TRY(ensure(c, c->kidx, (size_t)total * sizeof(uint64_t)));
-    qmcp::launch_mask_to_indices(c->stream, (const uint64_t*)c->mask.p, words, (const uint32_t*)c->f_words.p,
-                                 (unsigned long long*)c->kidx.p);
+    qmcp::launch_mask_to_indices(c->stream, c->mask.u64(), words, c->f_words.u32(), c->kidx.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(indices_out, c->kidx.p, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -532,8 +450,8 @@ int qmcp_hip_demand_host(qmcp_hip_ctx* c, const uint32_t* starts, const uint32_t
     const size_t nb = ((size_t)ref_genome_length + 1) * sizeof(int32_t);
     TRY(ensure(c, c->ecnt, nb));  // free after the coverage: b
     TRY(ensure(c, c->eoff, nb));  //                          d
-    qmcp::launch_b_and_demand(c->stream, (const uint32_t*)c->cov.p, ref_genome_length, max_coverage,
-                              (int32_t*)c->ecnt.p, (int32_t*)c->eoff.p);
+    qmcp::launch_b_and_demand(c->stream, c->cov.u32(), ref_genome_length, max_coverage,
+                              c->ecnt.as<int32_t>(), c->eoff.as<int32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(b_out, c->ecnt.p, nb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(d_out, c->eoff.p, nb, hipMemcpyDeviceToHost, c->stream));
@@ -563,7 +481,7 @@ int qmcp_hip_complete_pairs_host(qmcp_hip_ctx* c, uint64_t* keep_mask, uint64_t 
     TRY(ensure(c, c->mask, words * 8));
     c->mask_reads = n_reads;
     HIP_TRY(hipMemcpyAsync(c->mask.p, keep_mask, words * 8, hipMemcpyHostToDevice, c->stream));
-    qmcp::launch_complete_pairs(c->stream, (uint64_t*)c->mask.p, (uint32_t)words, n_reads);
+    qmcp::launch_complete_pairs(c->stream, c->mask.u64(), (uint32_t)words, n_reads);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(keep_mask, c->mask.p, words * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -591,15 +509,15 @@ int qmcp_hip_amplicon_filter_host(qmcp_hip_ctx* c, const uint32_t* starts, const
     if (seq_lengths) {
         TRY(ensure(c, c->in_aux0, nb));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, seq_lengths, nb, hipMemcpyHostToDevice, c->stream));
-        d_len = (const uint32_t*)c->in_aux0.p;
+        d_len = c->in_aux0.u32();
     }
     if (qualities) {
         TRY(ensure(c, c->in_aux1, nb));
         HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, c->stream));
-        d_q = (const uint32_t*)c->in_aux1.p;
+        d_q = c->in_aux1.u32();
     }
     TRY(ensure(c, c->amp, (size_t)2 * (n_amplicons + 1) * 4));
-    uint32_t* d_as = (uint32_t*)c->amp.p;
+    uint32_t* d_as = c->amp.u32();
     uint32_t* d_ae = d_as + n_amplicons + 1;
     if (n_amplicons) {
         HIP_TRY(hipMemcpyAsync(d_as, amp_starts, (size_t)n_amplicons * 4, hipMemcpyHostToDevice, c->stream));
@@ -607,9 +525,8 @@ int qmcp_hip_amplicon_filter_host(qmcp_hip_ctx* c, const uint32_t* starts, const
     }
     TRY(ensure(c, c->mask, words * 8));
     c->mask_reads = 0;  // (the buffer now holds pair bits)
-    qmcp::launch_amplicon_filter(c->stream, (const uint32_t*)c->in_starts.p,
-                                 (const uint32_t*)c->in_ends.p, d_len, d_q, n_pairs, d_as, d_ae,
-                                 n_amplicons, min_length, min_mapq, (uint64_t*)c->mask.p);
+    qmcp::launch_amplicon_filter(c->stream, c->in_starts.u32(), c->in_ends.u32(), d_len, d_q, n_pairs, d_as, d_ae,
+                                 n_amplicons, min_length, min_mapq, c->mask.u64());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(pair_keep_out, c->mask.p, words * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -645,7 +562,7 @@ int qmcp_hip_filter_solve_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
     TRY(ensure(c, c->f_mask, pwords * 8 + 16));
     TRY(ensure(c, c->mask, words * 8));
     TRY(ensure(c, c->cov, words * 8 + 16));  // compact-index keep mask
-    TRY(ensure(c, c->spine, (size_t)(qmcp::scan_spine_entries((uint32_t)pwords + 1) + 1) * 4 + 16));
+    TRY(ensure(c, c->spine, scan_spine_bytes((uint32_t)pwords + 1, 1)));
     uint32_t sent_columns = 2;
     TRY(upload_columns(c, starts, ends, n_reads, &sent_columns));
     const uint32_t* d_len = nullptr;
@@ -653,17 +570,17 @@ int qmcp_hip_filter_solve_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
     if (seq_lengths) {
         TRY(ensure(c, c->in_aux0, nb));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, seq_lengths, nb, hipMemcpyHostToDevice, st));
-        d_len = (const uint32_t*)c->in_aux0.p;
+        d_len = c->in_aux0.u32();
     }
     if (qualities) {
         TRY(ensure(c, c->in_aux1, nb));
         HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, st));
-        d_q = (const uint32_t*)c->in_aux1.p;
+        d_q = c->in_aux1.u32();
     }
     // 1. FILTER predicate per pair.  Without amplicons (AmpliconBehaviour::IGNORE) one interval
     //    covering every coordinate stands in for the amplicon set.
     TRY(ensure(c, c->amp, (size_t)2 * ((size_t)n_amplicons + 2) * 4));
-    uint32_t* d_as = (uint32_t*)c->amp.p;
+    uint32_t* d_as = c->amp.u32();
     uint32_t* d_ae = d_as + n_amplicons + 2;
     uint32_t n_amp_eff = n_amplicons;
     if (n_amplicons) {
@@ -676,27 +593,23 @@ int qmcp_hip_filter_solve_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
         HIP_TRY(hipStreamSynchronize(st));  // `everything` lives on this stack frame
         n_amp_eff = 1;
     }
-    qmcp::launch_amplicon_filter(st, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                 d_len, d_q, n_pairs, d_as, d_ae, n_amp_eff, min_length, min_mapq,
-                                 (uint64_t*)c->f_mask.p);
+    qmcp::launch_amplicon_filter(st, c->in_starts.u32(), c->in_ends.u32(), d_len, d_q, n_pairs, d_as, d_ae, n_amp_eff,
+                                 min_length, min_mapq, c->f_mask.u64());
     // 2. compaction: per-word popcounts -> exclusive scan -> scatter of surviving pairs
-    qmcp::launch_word_popcounts(st, (const uint64_t*)c->f_mask.p, (uint32_t)pwords, (uint32_t*)c->f_words.p);
-    qmcp::launch_exclusive_scan(st, (const uint32_t*)c->f_words.p, (uint32_t)pwords, (uint32_t*)c->f_words.p,
-                                (uint32_t*)c->spine.p, true);
+    queue_mask_ranks(st, c->f_mask.u64(), (uint32_t)pwords, c->f_words, c->spine);
     HIP_TRY(hipGetLastError());
     uint32_t n_surv_pairs = 0;
-    HIP_TRY(hipMemcpyAsync(&n_surv_pairs, (uint32_t*)c->f_words.p + pwords, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_surv_pairs, c->f_words.u32() + pwords, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (pairs_filtered_out) *pairs_filtered_out = n_pairs - n_surv_pairs;
-    qmcp::launch_compact_pairs(st, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                               (const uint64_t*)c->f_mask.p, (const uint32_t*)c->f_words.p, n_pairs,
-                               (uint32_t*)c->f_starts.p, (uint32_t*)c->f_ends.p, (uint32_t*)c->f_map.p);
+    qmcp::launch_compact_pairs(st, c->in_starts.u32(), c->in_ends.u32(), c->f_mask.u64(), c->f_words.u32(), n_pairs,
+                               c->f_starts.u32(), c->f_ends.u32(), c->f_map.u32());
     HIP_TRY(hipGetLastError());
     // 3. solve the survivors (device-resident), 4. complete mates, 5. back to original indices
     const uint64_t n_c = 2ull * n_surv_pairs;
     const uint64_t offs[2] = {0, n_c};
-    uint64_t* d_mask_c = (uint64_t*)c->cov.p;
-    TRY(solve_on_device(c, (const uint32_t*)c->f_starts.p, (const uint32_t*)c->f_ends.p, offs,
+    uint64_t* d_mask_c = c->cov.u64();
+    TRY(solve_on_device(c, c->f_starts.u32(), c->f_ends.u32(), offs,
                         &ref_genome_length, 1, n_c, max_coverage, d_mask_c, stats));
     const uint32_t words_c = (uint32_t)((n_c + 63) / 64);
     if (complete_pairs && words_c) {
@@ -705,8 +618,7 @@ int qmcp_hip_filter_solve_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
     }
     HIP_TRY(hipMemsetAsync(c->mask.p, 0, words * 8, st));
     if (n_c) {
-        qmcp::launch_expand_mask(st, d_mask_c, (const uint32_t*)c->f_map.p, (uint32_t)n_c,
-                                 (uint64_t*)c->mask.p);
+        qmcp::launch_expand_mask(st, d_mask_c, c->f_map.u32(), (uint32_t)n_c, c->mask.u64());
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * 8, hipMemcpyDeviceToHost, st));

@@ -38,16 +38,16 @@ int LadderSolver::after_batch(qmcp_hip_ctx* c, BatchView& v) {
         TRY(ensure(c, c->ld_offs[1], tab * sizeof(uint32_t)));
         const size_t words0 = ((size_t)nb + 63) / 64;
         TRY(ensure(c, c->ld_words, (words0 + 2) * sizeof(uint32_t)));
-        TRY(ensure(c, c->ld_spine, (size_t)(qmcp::scan_spine_entries((uint32_t)words0 + 1) + 1) * sizeof(uint32_t) + 16));
+        TRY(ensure(c, c->ld_spine, scan_spine_bytes((uint32_t)words0 + 1, 1)));
         v.tables32();
         HIP_TRY(hipMemcpyAsync(c->ld_offs[0].p, v.offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
     // the level whose mask is in bc_mask: its reads, their columns and their origins
     uint32_t n = nb;
-    const uint32_t* d_s = (const uint32_t*)c->bc_starts.p;
-    const uint32_t* d_e = (const uint32_t*)c->bc_ends.p;
+    const uint32_t* d_s = c->bc_starts.u32();
+    const uint32_t* d_e = c->bc_ends.u32();
     const void* d_o = v.records;
-    const uint64_t* d_m = (const uint64_t*)c->bc_mask.p;
+    const uint64_t* d_m = c->bc_mask.u64();
     bool compact_timed = false;
     for (uint32_t j = 0; j < n_levels; ++j) {
         const bool first = j == 0;
@@ -60,11 +60,9 @@ int LadderSolver::after_batch(qmcp_hip_ctx* c, BatchView& v) {
         if (!last) {
             const uint32_t words = (n + 63u) / 64u;
             KernelSpan sp(c, "ladder offsets(popcounts, scan, k_ladder_offsets)");
-            qmcp::launch_word_popcounts(st, d_m, words, (uint32_t*)c->ld_words.p);
-            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->ld_words.p, words, (uint32_t*)c->ld_words.p,
-                                        (uint32_t*)c->ld_spine.p, true);
-            qmcp::launch_ladder_offsets(st, (const uint32_t*)c->ld_offs[j & 1u].p, n_contigs, d_m,
-                                        (const uint32_t*)c->ld_words.p, (uint32_t*)c->ld_offs[(j & 1u) ^ 1u].p);
+            queue_mask_ranks(st, d_m, words, c->ld_words, c->ld_spine);
+            qmcp::launch_ladder_offsets(st, c->ld_offs[j & 1u].u32(), n_contigs, d_m,
+                                        c->ld_words.u32(), c->ld_offs[(j & 1u) ^ 1u].u32());
         }
         HIP_TRY(hipEventRecord(ev_a.b, st));
         HIP_TRY(hipGetLastError());
@@ -88,22 +86,20 @@ int LadderSolver::after_batch(qmcp_hip_ctx* c, BatchView& v) {
         HIP_TRY(hipEventRecord(ev_b.a, st));
         {
             KernelSpan sp(c, "k_ladder_compact");
-            qmcp::launch_ladder_compact(st, first, d_s, d_e, d_o, d_m, (const uint32_t*)c->ld_words.p, n,
-                                        (uint32_t*)c->ld_starts[set].p, (uint32_t*)c->ld_ends[set].p,
-                                        (uint32_t*)c->ld_orig[set].p);
+            qmcp::launch_ladder_compact(st, first, d_s, d_e, d_o, d_m, c->ld_words.u32(), n, c->ld_starts[set].u32(),
+                                        c->ld_ends[set].u32(), c->ld_orig[set].u32());
         }
         HIP_TRY(hipEventRecord(ev_b.b, st));
         HIP_TRY(hipGetLastError());
         compact_timed = true;
         n = n_next;
-        d_s = (const uint32_t*)c->ld_starts[set].p;
-        d_e = (const uint32_t*)c->ld_ends[set].p;
+        d_s = c->ld_starts[set].u32();
+        d_e = c->ld_ends[set].u32();
         d_o = c->ld_orig[set].p;
         cur.swap(next);
         qmcp_hip_stats bs;
         std::memset(&bs, 0, sizeof(bs));
-        TRY(solve_on_device(c, d_s, d_e, cur.data(), v.lengths, n_contigs, n, coverages[j + 1], (uint64_t*)c->bc_mask.p,
-                            &bs));
+        TRY(solve_on_device(c, d_s, d_e, cur.data(), v.lengths, n_contigs, n, coverages[j + 1], c->bc_mask.u64(), &bs));
         ls.n_kept[j + 1] += bs.n_kept;
         ls.ms_level[j + 1] += bs.ms_total;
     }
@@ -171,9 +167,8 @@ int qmcp_hip_solve_ladder_host(qmcp_hip_ctx* c, const uint32_t* starts, const ui
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_ladder_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                               (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, coverages, n_levels,
-                               (uint64_t*)c->mask.p, (uint8_t*)c->ld_levels.p, stats, lstats));
+    TRY(solve_ladder_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), n_reads, contig_lengths,
+        n_contigs, coverages, n_levels, c->mask.u64(), c->ld_levels.as<uint8_t>(), stats, lstats));
     if (n_reads) HIP_TRY(hipMemcpyAsync(levels_out, c->ld_levels.p, (size_t)n_reads, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;
@@ -192,7 +187,7 @@ int qmcp_hip_solve_ladder_device(qmcp_hip_ctx* c, const uint32_t* d_starts, cons
     TRY(ensure(c, c->ld_mask0, (size_t)((n_reads + 63) / 64) * sizeof(uint64_t)));
     TRY(order_after(c, hip_stream));
     return solve_ladder_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, coverages,
-                                  n_levels, (uint64_t*)c->ld_mask0.p, d_levels_out, stats, lstats);
+                                  n_levels, c->ld_mask0.u64(), d_levels_out, stats, lstats);
 }
 
 }  // extern "C"

@@ -119,13 +119,13 @@ int qmcp_hip_multi_solve_host(qmcp_hip_multi* m, const uint32_t* starts, const u
             for (size_t i = 0; i < mine.size(); ++i) {
                 const uint64_t lo = contig_read_offsets[mine[i]], cnt = loffs[i + 1] - loffs[i];
                 if (cnt == 0) continue;
-                HIP_TRY(hipMemcpyAsync((uint32_t*)c->in_starts.p + loffs[i], starts + lo, (size_t)cnt * sizeof(uint32_t),
+                HIP_TRY(hipMemcpyAsync(c->in_starts.u32() + loffs[i], starts + lo, (size_t)cnt * sizeof(uint32_t),
                                        hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipMemcpyAsync((uint32_t*)c->in_ends.p + loffs[i], ends + lo, (size_t)cnt * sizeof(uint32_t),
+                HIP_TRY(hipMemcpyAsync(c->in_ends.u32() + loffs[i], ends + lo, (size_t)cnt * sizeof(uint32_t),
                                        hipMemcpyHostToDevice, c->stream));
             }
-            TRY(solve_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, loffs.data(),
-                                llens.data(), (uint32_t)mine.size(), ln, max_coverage, (uint64_t*)c->mask.p,
+            TRY(solve_on_device(c, c->in_starts.u32(), c->in_ends.u32(), loffs.data(),
+                                llens.data(), (uint32_t)mine.size(), ln, max_coverage, c->mask.u64(),
                                 per_device_stats ? &per_device_stats[d] : nullptr));
             std::vector<uint64_t>& lm = m->local_mask[d];
             lm.resize(lwords);

@@ -33,7 +33,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     hipStream_t st = c->stream;
     const uint32_t cap = nu_cap_for(n);
     uint32_t n_exc = 0;
-    uint32_t* d_stats = (uint32_t*)c->stats.p;
+    uint32_t* d_stats = c->stats.u32();
     if (run.nu_filter == ell) {
         n_exc = c->h_head[5];  // (read back beside the statistics)
         if (c->h_head[6] != 0) { c->nu_ell = 0; local.near_uniform_giveup = QMCP_NU_GIVEUP_TOO_MANY; return QMCP_OK; }  // a pass held more exceptions than it can stage
@@ -57,7 +57,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         c->nu_ell = ell;
         if (run.pm) TRY(queue_pm_head(c, st, ell, true));
         else TRY(queue_rm_head(c, st, ell, true));
-        uint32_t* d_max_load = (uint32_t*)c->ranges.p + 65540;
+        uint32_t* d_max_load = c->ranges.u32() + 65540;
         HIP_TRY(hipMemcpyAsync(c->h_nu, d_max_load, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(c->h_nu + 1, d_stats + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -75,13 +75,13 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         TRY(ensure(c, c->evpk, qmcp::sweep_ev_pack_bytes(ltot, ell, n_contigs + 768)));
         TRY(ensure(c, c->evlast, qmcp::sweep_ev_last_bytes(ltot, ell, n_contigs + 768)));
     }
-    const uint32_t* boff = (const uint32_t*)c->boff.p;
-    const uint64_t* poff = (const uint64_t*)c->poff.p;
-    uint32_t* selend = (uint32_t*)c->selend.p;
-    uint32_t* exc = (uint32_t*)c->nu_exc.p;
-    int32_t* nadj = (int32_t*)c->nu_nadj.p;
-    uint32_t* state = (uint32_t*)c->nu_state.p;
-    unsigned long long* viol_key = (unsigned long long*)((char*)c->nu_state.p + 64);
+    const uint32_t* boff = c->boff.u32();
+    const uint64_t* poff = c->poff.u64();
+    uint32_t* selend = c->selend.u32();
+    uint32_t* exc = c->nu_exc.u32();
+    int32_t* nadj = c->nu_nadj.as<int32_t>();
+    uint32_t* state = c->nu_state.u32();
+    unsigned long long* viol_key = (unsigned long long*)(c->nu_state.as<char>() + 64);
     uint32_t* viol_idx = (uint32_t*)(viol_key + n_contigs);
     uint32_t* sweep_from[2] = {viol_idx + n_contigs, viol_idx + 2 * (size_t)n_contigs};  // this round's, the next round's
     if (!stretches) TRY(ensure(c, c->nu_ckpt, qmcp::sweep_ev_ckpt_bytes(ltot, ell, n_contigs + 768)));
@@ -90,7 +90,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
     {
         KernelSpan sp(c, "near-uniform setup (exception coverage, need, pre-selection)");
-        qmcp::launch_nu_setup(st, exc, cap, n_exc, d_stats + 6, boff, ltot, ell, M, (uint32_t*)c->nu_ce.p, (uint32_t*)c->spine.p,
+        qmcp::launch_nu_setup(st, exc, cap, n_exc, d_stats + 6, boff, ltot, ell, M, c->nu_ce.u32(), c->spine.u32(),
                               nadj, state);
     }
     const uint32_t* seg = nullptr;
@@ -99,12 +99,12 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     // stretches: the exact table once (the cut points do not move between rounds), the speculative ones per sweep
     if (windows != 0) {
         KernelSpan sp(c, "k_find_cuts", st);
-        seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, ell, M, windows, (uint32_t*)c->segs.p,
-                                          (const uint32_t*)c->nu_ce.p);
+        seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, ell, M, windows, c->segs.u32(),
+                                          c->nu_ce.u32());
         n_seg_max = n_contigs + windows;
     }
     // later rounds sweep only the exact stretches a selection of the round before touched (k_nu_select_apply marks them)
-    uint32_t* marks[2] = {(uint32_t*)((char*)c->nu_sus.p + qmcp::nu_suspect_bytes(nu_suspects_for(n))), nullptr};
+    uint32_t* marks[2] = {(uint32_t*)(c->nu_sus.as<char>() + qmcp::nu_suspect_bytes(nu_suspects_for(n))), nullptr};
     const uint32_t mw = nu_marks_words(n_contigs);
     marks[1] = marks[0] + mw;
     // ... and, where the sweeps speculate, only the first tier's stretches that read or write something a selection changed
@@ -115,7 +115,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     if (stretches) HIP_TRY(hipMemsetAsync(dirty[0], 0, 2 * qmcp::nu_cells_bytes(), st));
     // (the first tier's table: launch_sweep_segments_speculative(..., tier 1) builds it at this place on every sweep, from
     //  the same cut points -- the same table every round)
-    const uint32_t* seg_fine = speculate ? (const uint32_t*)c->segs.p + windows + (1 + 5 * ((size_t)n_contigs + windows)) : nullptr;
+    const uint32_t* seg_fine = speculate ? c->segs.u32() + windows + (1 + 5 * ((size_t)n_contigs + windows)) : nullptr;
     if (c->opt.near_uniform_debug == 2) seg_fine = nullptr;  // (lab: every round sweeps every stretch its exact marks cover)
     // Rounds are queued two at a time and the host looks at the state words after each pair: a round whose contigs are
     // all settled is eight launches that return at once (the chain sweeps nothing, the verification skips every
@@ -143,7 +143,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
                                                                   (table == seg_fine && rounds > 1) ? fine[0] : nullptr);
                         },
                         [&](const uint32_t* table, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
-                            qmcp::launch_spec_verify(st, table, n_seg_max, ell, selend, (const uint32_t*)c->cstart.p, mismatches,
+                            qmcp::launch_spec_verify(st, table, n_seg_max, ell, selend, c->cstart.u32(), mismatches,
                                                      redo_in, redo_out, (table == seg_fine && rounds > 1) ? fine[0] : nullptr);
                         },
                         rounds == 1 ? nullptr : marks[0]));
@@ -156,26 +156,26 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
             } else {
             {
                 KernelSpan sp(c, "k_sweep_pack", st);
-                qmcp::launch_sweep_ev_pack(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, (uint32_t*)c->evpk.p, nadj, sweep_from[0]);
+                qmcp::launch_sweep_ev_pack(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, c->evpk.u32(), nadj, sweep_from[0]);
             }
             {
                 KernelSpan sp(c, "k_sweep_uniform_ev", st);
-                qmcp::launch_sweep_ev_chain(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, (const uint32_t*)c->evpk.p,
-                                            (uint32_t*)c->cstart.p, (uint32_t*)c->evlast.p, d_iters, nadj, (uint32_t*)c->nu_ckpt.p,
+                qmcp::launch_sweep_ev_chain(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, c->evpk.u32(),
+                                            c->cstart.u32(), c->evlast.u32(), d_iters, nadj, c->nu_ckpt.u32(),
                                             sweep_from[0]);
             }
             {
                 KernelSpan sp(c, "k_sweep_expand", st);
-                qmcp::launch_sweep_ev_expand(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, (const uint32_t*)c->cstart.p,
-                                             (const uint32_t*)c->evlast.p, selend, sweep_from[0]);
+                qmcp::launch_sweep_ev_expand(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, c->cstart.u32(),
+                                             c->evlast.u32(), selend, sweep_from[0]);
             }
             }
             {
                 KernelSpan sp(c, "near-uniform round (verify, replay, select, apply)");
-                qmcp::launch_nu_round(st, exc, cap, n_exc, d_stats + 6, rounds == 1, boff, selend, nadj, (const uint32_t*)c->nu_ce.p, poff, n_contigs, ell, M,
-                                      (uint2*)c->nu_sus.p, nu_suspects_for(n), state, viol_key, viol_idx, sweep_from[0], sweep_from[1],
-                                      ltot, (uint32_t*)c->spine.p, stretches ? seg : nullptr, n_seg_max, marks[1],
-                                      stretches ? (uint32_t*)c->nu_prev.p : nullptr, dirty[0], dirty[1], seg_fine, fine[1]);
+                qmcp::launch_nu_round(st, exc, cap, n_exc, d_stats + 6, rounds == 1, boff, selend, nadj, c->nu_ce.u32(), poff, n_contigs, ell, M,
+                                      c->nu_sus.as<uint2>(), nu_suspects_for(n), state, viol_key, viol_idx, sweep_from[0], sweep_from[1],
+                                      ltot, c->spine.u32(), stretches ? seg : nullptr, n_seg_max, marks[1],
+                                      stretches ? c->nu_prev.u32() : nullptr, dirty[0], dirty[1], seg_fine, fine[1]);
                 std::swap(sweep_from[0], sweep_from[1]);
                 std::swap(marks[0], marks[1]);
                 std::swap(fine[0], fine[1]);
@@ -225,15 +225,14 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         queue_pm_rank(c, st, nullptr, nullptr, 0);
     } else {
         KernelSpan sp(c, "k_rank_mark");
-        qmcp::launch_rank_mark(st, (const uint16_t*)c->keys[0].p, (const uint32_t*)c->vals[0].p, (const uint32_t*)c->ranges.p,
-                               run.range_shift, ltot, boff, selend, (unsigned long long*)run.d_mask,
-                               (unsigned long long*)c->scalars.p, c->rankamb.p,
-                               qmcp::rank_scratch_by_records(run.range_shift, ltot, n));
+        qmcp::launch_rank_mark(st, c->keys[0].as<uint16_t>(), c->vals[0].u32(), c->ranges.u32(), run.range_shift, ltot,
+                               boff, selend, (unsigned long long*)run.d_mask, c->scalars.as<unsigned long long>(),
+                               c->rankamb.p, qmcp::rank_scratch_by_records(run.range_shift, ltot, n));
     }
     {
         KernelSpan sp(c, "k_nu_mark_selected");
         qmcp::launch_nu_mark_selected(st, exc, cap, n_exc, d_stats + 6, (unsigned long long*)run.d_mask,
-                                      (unsigned long long*)c->scalars.p);
+                                      c->scalars.as<unsigned long long>());
     }
     HIP_TRY(hipGetLastError());
     done = true;

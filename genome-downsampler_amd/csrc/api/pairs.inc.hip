@@ -50,9 +50,8 @@ struct PairNeed : StageNeed {
     explicit PairNeed(uint32_t t) : target(t) {}
     const char* name() const override { return "k_pair_need"; }
     void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
-        qmcp::launch_pair_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
-                               (const uint32_t*)c->pr_credit.p + qmcp::pair_credit_pad(), ltot, target, need,
-                               (unsigned long long*)c->pr_stat.p);
+        qmcp::launch_pair_need(st, c->boff.u32(), c->eoff.u32(), c->pr_credit.u32() + qmcp::pair_credit_pad(), ltot,
+                               target, need, c->pr_stat.as<unsigned long long>());
     }
 };
 
@@ -94,7 +93,7 @@ struct TargetNeeds : StageNeeds {
 int pair_complete_and_count(qmcp_hip_ctx* c, uint64_t* d_mask, uint64_t n64) {
     hipStream_t st = c->stream;
     const uint32_t words = (uint32_t)((n64 + 63) / 64);
-    unsigned long long* d_count = (unsigned long long*)c->pr_stat.p + 2;
+    unsigned long long* d_count = c->pr_stat.as<unsigned long long>() + 2;
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
     if (words) {
         KernelSpan sp(c, "k_complete_pairs(pairs) + k_pair_count_bits");
@@ -120,7 +119,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint6
     if (!ev_a.a || !ev_a.b || !ev_b.a || !ev_b.b) return fail(QMCP_EHIP, "event creation failed");
     TRY(ensure(c, c->pr_stat, 4 * sizeof(unsigned long long)));
     unsigned long long count = 0;
-    const unsigned long long* d_count = (const unsigned long long*)c->pr_stat.p + 2;
+    const unsigned long long* d_count = c->pr_stat.as<unsigned long long>() + 2;
     ps.n_selected[0] = first.n_kept;
     ps.ms_stage[0] = first.ms_total;
     // ev_a brackets what is queued between two host waits; `open` says its first event has been recorded
@@ -163,12 +162,12 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint6
             TRY(ensure(c, c->pr_in, (size_t)words * sizeof(uint64_t)));
             TRY(ensure(c, c->pr_rest, (size_t)words * sizeof(uint64_t)));
             TRY(ensure(c, c->pr_words, ((size_t)words + 2) * sizeof(uint32_t)));
-            TRY(ensure(c, c->pr_spine, (size_t)(qmcp::scan_spine_entries(words + 1) + 1) * sizeof(uint32_t) + 16));
+            TRY(ensure(c, c->pr_spine, scan_spine_bytes(words + 1, 1)));
             TRY(ensure(c, c->pr_offs[0], tab * sizeof(uint32_t)));
             TRY(ensure(c, c->pr_offs[1], tab * sizeof(uint32_t)));
             TRY(ensure(c, c->pr_poff, tab * sizeof(uint32_t)));
             TRY(ensure(c, c->pr_credit, ((size_t)ltot + pad + 4) * sizeof(uint32_t)));
-            TRY(ensure(c, c->pr_cspine, (size_t)(qmcp::scan_spine_entries(ltot + pad) + 1) * sizeof(uint32_t) + 16));
+            TRY(ensure(c, c->pr_cspine, scan_spine_bytes(ltot + pad, 1)));
             // 1 - 3: S and the candidates in grouped order, the candidates' offsets, the credit of S
             TRY(begin());
             HIP_TRY(hipMemcpyAsync(c->pr_offs[0].p, v.offs32.data(), tab * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -177,23 +176,20 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint6
             TRY(gather_batch(c, v, g.d_starts, g.d_ends));
             {
                 KernelSpan sp(c, "k_pair_gather_mask");
-                qmcp::launch_pair_gather_mask(st, v.records, nb, d_mask, (uint64_t*)c->pr_in.p, (uint64_t*)c->pr_rest.p);
+                qmcp::launch_pair_gather_mask(st, v.records, nb, d_mask, c->pr_in.u64(), c->pr_rest.u64());
             }
             {
                 KernelSpan sp(c, "pair candidates(popcounts, scan, k_ladder_offsets)");
-                qmcp::launch_word_popcounts(st, (const uint64_t*)c->pr_rest.p, words, (uint32_t*)c->pr_words.p);
-                qmcp::launch_exclusive_scan(st, (const uint32_t*)c->pr_words.p, words, (uint32_t*)c->pr_words.p,
-                                            (uint32_t*)c->pr_spine.p, true);
-                qmcp::launch_ladder_offsets(st, (const uint32_t*)c->pr_offs[0].p, bt.n_contigs, (const uint64_t*)c->pr_rest.p,
-                                            (const uint32_t*)c->pr_words.p, (uint32_t*)c->pr_offs[1].p);
+                queue_mask_ranks(st, c->pr_rest.u64(), words, c->pr_words, c->pr_spine);
+                qmcp::launch_ladder_offsets(st, c->pr_offs[0].u32(), bt.n_contigs, c->pr_rest.u64(),
+                                            c->pr_words.u32(), c->pr_offs[1].u32());
             }
             {
                 KernelSpan sp(c, "k_pair_credit_events + scan");
-                qmcp::launch_pair_credit_events(st, v.records, nb, (const uint64_t*)c->pr_in.p, (const uint32_t*)c->bc_starts.p,
-                                                (const uint32_t*)c->bc_ends.p, (const uint32_t*)c->pr_poff.p, bt.first_contig,
-                                                (uint32_t*)c->pr_credit.p);
-                qmcp::launch_exclusive_scan(st, (const uint32_t*)c->pr_credit.p, ltot + pad, (uint32_t*)c->pr_credit.p,
-                                            (uint32_t*)c->pr_cspine.p, false);
+                qmcp::launch_pair_credit_events(st, v.records, nb, c->pr_in.u64(), c->bc_starts.u32(), c->bc_ends.u32(),
+                                                c->pr_poff.u32(), bt.first_contig, c->pr_credit.u32());
+                qmcp::launch_exclusive_scan(st, c->pr_credit.u32(), ltot + pad, c->pr_credit.u32(),
+                                            c->pr_cspine.u32(), false);
             }
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(ranks.data(), c->pr_offs[1].p, tab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -210,9 +206,9 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint6
             HIP_TRY(hipEventRecord(ev_b.a, st));
             {
                 KernelSpan sp(c, "k_ladder_compact(pairs)");
-                qmcp::launch_ladder_compact(st, true, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.records,
-                                            (const uint64_t*)c->pr_rest.p, (const uint32_t*)c->pr_words.p, nb,
-                                            (uint32_t*)c->pr_starts.p, (uint32_t*)c->pr_ends.p, (uint32_t*)c->pr_orig.p);
+                qmcp::launch_ladder_compact(st, true, c->bc_starts.u32(), c->bc_ends.u32(), v.records,
+                                            c->pr_rest.u64(), c->pr_words.u32(), nb,
+                                            c->pr_starts.u32(), c->pr_ends.u32(), c->pr_orig.u32());
             }
             HIP_TRY(hipEventRecord(ev_b.b, st));
             HIP_TRY(hipGetLastError());
@@ -221,9 +217,8 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint6
             qmcp_hip_stats bs;
             std::memset(&bs, 0, sizeof(bs));
             bool swept = false;
-            TRY(capped_solve_batch(c, nd, max_cap, (const uint32_t*)c->pr_starts.p, (const uint32_t*)c->pr_ends.p,
-                                   cand_roff.data(), v.lengths, bt.n_contigs, n_c, (uint64_t*)c->pr_mask.p, &bs,
-                                   &swept));
+            TRY(capped_solve_batch(c, nd, max_cap, c->pr_starts.u32(), c->pr_ends.u32(), cand_roff.data(), v.lengths,
+                bt.n_contigs, n_c, c->pr_mask.u64(), &bs, &swept));
             ps.ms_pairs += elapsed(ev_b.a, ev_b.b) + nd.ms;
             ps.n_selected[j] += bs.n_kept;
             ps.ms_stage[j] += bs.ms_total;
@@ -234,7 +229,7 @@ int pair_later_stages(qmcp_hip_ctx* c, PairRun& pr, const GroupedReads& g, uint6
             if (bs.n_kept) {
                 TRY(begin());
                 KernelSpan sp(c, "k_expand_mask_reads(pairs)");
-                qmcp::launch_expand_mask_reads(st, (const uint64_t*)c->pr_mask.p, (const uint32_t*)c->pr_orig.p, n_c, d_mask);
+                qmcp::launch_expand_mask_reads(st, c->pr_mask.u64(), c->pr_orig.u32(), n_c, d_mask);
             }
             HIP_TRY(hipGetLastError());
         }
@@ -317,8 +312,8 @@ int qmcp_hip_solve_pairs_host(qmcp_hip_ctx* c, const uint32_t* starts, const uin
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_pairs_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, (const uint32_t*)c->in_aux0.p,
-                              n_reads, contig_lengths, n_contigs, targets, (uint64_t*)c->mask.p, stats, pstats));
+    TRY(solve_pairs_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(),
+                              n_reads, contig_lengths, n_contigs, targets, c->mask.u64(), stats, pstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

@@ -68,14 +68,12 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         if (st_out) *st_out = local;
         return QMCP_OK;
     }
-    if (!c->h_scalars) HIP_TRY(hipHostMalloc((void**)&c->h_scalars, 16 * sizeof(unsigned long long), hipHostMallocDefault));
+    TRY(ensure_pinned(c, c->h_scalars, 16 * sizeof(unsigned long long)));
     // the arena, sized before anything is queued
     const uint32_t n_tiles = qmcp::sort_tiles(n);
     c->sized = false;
     {
-        const uint32_t spine_a = qmcp::scan_spine_entries(256u * n_tiles);
-        const uint32_t spine_b = std::max(qmcp::scan_spine_entries(ltot + 1), qmcp::scan_spine_entries(n + 1)) + 1;
-        TRY(ensure(c, c->spine, (size_t)std::max(spine_a, spine_b) * sizeof(uint32_t) + 16));
+        TRY(ensure(c, c->spine, std::max(scan_spine_bytes(256u * n_tiles), scan_spine_bytes(std::max(ltot, n) + 1, 1))));
         TRY(ensure(c, c->hist, (size_t)256 * std::max(qmcp::seg_tile_bound(n), n_tiles) * sizeof(uint32_t)));
         TRY(ensure(c, c->keys[0], (size_t)n * sizeof(uint64_t)));
         TRY(ensure(c, c->keys[1], (size_t)n * sizeof(uint64_t)));
@@ -110,12 +108,12 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     const uint32_t pos_bits = bit_width(ltot - 1) == 0 ? 1u : bit_width(ltot - 1);
     const uint32_t span_bits = bit_width(max_span - min_span);
     const bool wide = pos_bits + span_bits > 32;
-    const uint32_t* d_gstart = (const uint32_t*)c->vals[1].p;
+    const uint32_t* d_gstart = c->vals[1].u32();
     HIP_TRY(hipMemsetAsync(c->ecnt.p, 0, ((size_t)ltot + 1) * sizeof(uint32_t), st));
     {
         KernelSpan sp(c, "k_general_keys");
         qmcp::launch_general_keys(st, wide, d_gstart, d_starts, d_ends, n, span_bits, max_span, nullptr,
-                                  wide ? c->keys[0].p : c->vals[0].p, (uint32_t*)c->ecnt.p, ltot + 1);
+                                  wide ? c->keys[0].p : c->vals[0].p, c->ecnt.u32(), ltot + 1);
     }
     HIP_TRY(hipGetLastError());
     TRY(scan_counts(c, c->ecnt, c->eoff, ltot));
@@ -127,38 +125,37 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     int kin = 0, vin = 0;
     const RadixNames radix_names = {"radix pass (hist, scan, scatter)"};
     if (!wide) {
-        TRY(radix_sort_records(c, st, (const uint32_t*)c->vals[0].p, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p,
+        TRY(radix_sort_records(c, st, c->vals[0].u32(), n, passes, c->hist.u32(), c->spine.u32(),
                                c->keys, radix_names, &kin));
     } else {
         WideBufs wb;
-        TRY(radix_sort_wide(c, st, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, c->keys, c->vals, radix_names, &wb));
+        TRY(radix_sort_wide(c, st, n, passes, c->hist.u32(), c->spine.u32(), c->keys, c->vals, radix_names, &wb));
         kin = wb.k;
         vin = wb.v;
     }
     HIP_TRY(hipMemsetAsync(c->boff.p, 0xFF, ((size_t)ltot + 1) * sizeof(uint32_t), st));
     {
         KernelSpan sp(c, "k_bucket_heads");
-        qmcp::launch_bucket_heads(st, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, n, span_bits, ltot,
-                                  (uint32_t*)c->boff.p);
+        qmcp::launch_bucket_heads(st, wide, c->keys[kin].p, c->vals[vin].u32(), n, span_bits, ltot, c->boff.u32());
     }
     {
         KernelSpan sp(c, "reverse_min_scan(3 kernels)");
-        qmcp::launch_reverse_min_scan(st, (uint32_t*)c->boff.p, ltot + 1, (uint32_t*)c->spine.p);
+        qmcp::launch_reverse_min_scan(st, c->boff.u32(), ltot + 1, c->spine.u32());
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
     // need[], cut points
-    const uint32_t* d_need = (const uint32_t*)nd.need_buf(c).p;
+    const uint32_t* d_need = nd.need_buf(c).u32();
     const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
     const uint32_t* seg = nullptr;
     uint32_t n_seg_max = 0;
-    uint32_t* d_iters = (uint32_t*)((char*)c->scalars.p + 16);
+    uint32_t* d_iters = (uint32_t*)(c->scalars.as<char>() + 16);
     EventPair ev_pf(c);
     if (!ev_pf.a || !ev_pf.b) return fail(QMCP_EHIP, "event creation failed");
     HIP_TRY(hipEventRecord(ev_pf.a, st));
     {
         KernelSpan sp(c, nd.name());
-        nd.launch(c, st, ltot, (uint32_t*)nd.need_buf(c).p);
+        nd.launch(c, st, ltot, nd.need_buf(c).u32());
     }
     bool idle = false;  // nothing is asked for anywhere: no sweep, the zeroed mask stands
     TRY(nd.no_demand(c, st, &idle));
@@ -166,7 +163,7 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         qmcp::plan_mixed_sweep(c->opt, n, max_span, ltot, n_contigs, nd.plan_cap(max_cap), in_regs, false).windows;
     if (windows != 0 && !idle) {
         KernelSpan sp(c, "k_profile_cuts");
-        seg = qmcp::launch_profile_segments(st, d_need, (const uint64_t*)c->poff.p, n_contigs, ltot, windows, (uint32_t*)c->segs.p);
+        seg = qmcp::launch_profile_segments(st, d_need, c->poff.u64(), n_contigs, ltot, windows, c->segs.u32());
         n_seg_max = n_contigs + windows;
         HIP_TRY(hipMemcpyAsync(d_iters + 2, seg, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     }
@@ -177,16 +174,16 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     if (in_regs && !idle) {
         {
             KernelSpan sp(c, "k_group_heads");
-            qmcp::launch_group_heads(st, wide, c->keys[kin].p, n, (uint32_t*)c->next_head.p);
+            qmcp::launch_group_heads(st, wide, c->keys[kin].p, n, c->next_head.u32());
         }
         {
             KernelSpan sp(c, "reverse_min_scan(3 kernels)");
-            qmcp::launch_reverse_min_scan(st, (uint32_t*)c->next_head.p, n + 1, (uint32_t*)c->spine.p);
+            qmcp::launch_reverse_min_scan(st, c->next_head.u32(), n + 1, c->spine.u32());
         }
         KernelSpan sp(c, "k_sweep_general_reg(capped)");
-        swept = qmcp::launch_sweep_general_reg_capped(st, wide, (const uint32_t*)c->boff.p, d_need, c->keys[kin].p,
-                                                      (const uint32_t*)c->next_head.p, (const uint64_t*)c->poff.p, n_contigs,
-                                                      span_bits, max_span, (uint32_t*)c->selend.p, seg, n_seg_max);
+        swept = qmcp::launch_sweep_general_reg_capped(st, wide, c->boff.u32(), d_need, c->keys[kin].p,
+                                                      c->next_head.u32(), c->poff.u64(), n_contigs,
+                                                      span_bits, max_span, c->selend.u32(), seg, n_seg_max);
     }
     if (!swept) {
         uint32_t ring = 64;
@@ -195,19 +192,18 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         if (max_span > qmcp::kMaxLdsRingSpan) {  // long reads: the two rings of a workgroup no longer fit LDS
             const size_t n_wg = seg ? n_seg_max : n_contigs;
             TRY(ensure(c, c->rings, n_wg * 2 * (size_t)ring * sizeof(uint32_t)));
-            g_rings = (uint32_t*)c->rings.p;
+            g_rings = c->rings.u32();
         }
         KernelSpan sp(c, "k_sweep_general(capped)");
-        qmcp::launch_sweep_general_capped(st, wide, (const uint32_t*)c->boff.p, d_need, c->keys[kin].p,
-                                          (const uint64_t*)c->poff.p, n_contigs, span_bits, max_span, (uint32_t*)c->selend.p,
-                                          ring, seg, n_seg_max, g_rings);
+        qmcp::launch_sweep_general_capped(st, wide, c->boff.u32(), d_need, c->keys[kin].p, c->poff.u64(), n_contigs,
+                                          span_bits, max_span, c->selend.u32(), ring, seg, n_seg_max, g_rings);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], st));
     if (!idle) {
         KernelSpan sp(c, "k_mark");
-        qmcp::launch_mark(st, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, ltot, (const uint32_t*)c->boff.p,
-                          (const uint32_t*)c->selend.p, d_mask, (unsigned long long*)c->scalars.p);
+        qmcp::launch_mark(st, wide, c->keys[kin].p, c->vals[vin].u32(), ltot, c->boff.u32(),
+                          c->selend.u32(), d_mask, c->scalars.as<unsigned long long>());
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_MARK], st));
@@ -240,7 +236,7 @@ struct ProfileNeed : CappedNeed {
     DevBuf& need_buf(qmcp_hip_ctx* c) override { return c->pf_need; }
     int reserve(qmcp_hip_ctx* c) override { return ensure(c, c->pf_tab, 3 * (size_t)n_reg * sizeof(uint32_t) + 16); }
     int upload(qmcp_hip_ctx* c, hipStream_t st) override {
-        uint32_t* d_rs = (uint32_t*)c->pf_tab.p;
+        uint32_t* d_rs = c->pf_tab.u32();
         if (n_reg) {
             HIP_TRY(hipMemcpyAsync(d_rs, pf.gs.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(d_rs + n_reg, pf.ge.data(), (size_t)n_reg * 4, hipMemcpyHostToDevice, st));
@@ -249,9 +245,9 @@ struct ProfileNeed : CappedNeed {
         return QMCP_OK;
     }
     void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
-        const uint32_t* d_rs = (const uint32_t*)c->pf_tab.p;
-        qmcp::launch_profile_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p, ltot, d_rs, d_rs + n_reg,
-                                  d_rs + 2 * (size_t)n_reg, n_reg, pf.default_cap, need, (unsigned long long*)c->pf_stat.p);
+        const uint32_t* d_rs = c->pf_tab.u32();
+        qmcp::launch_profile_need(st, c->boff.u32(), c->eoff.u32(), ltot, d_rs, d_rs + n_reg,
+                                  d_rs + 2 * (size_t)n_reg, n_reg, pf.default_cap, need, c->pf_stat.as<unsigned long long>());
     }
 };
 
@@ -267,8 +263,8 @@ struct ProfileSolver : BatchSolver {
         if (r0 == r1 && max_cap != 0) return PlainSolver(pf.default_cap).solve(c, v, bs);
         qmcp::batch_cap_table(tab, v.lengths - v.first_contig, v.first_contig, v.n_contigs, pf.gs, pf.ge, pf.gcap);
         ProfileNeed nd(pf, r1 - r0);
-        TRY(capped_solve_batch(c, nd, max_cap, (const uint32_t*)c->bc_starts.p, (const uint32_t*)c->bc_ends.p, v.roff.data(),
-                               v.lengths, v.n_contigs, v.nb, (uint64_t*)c->bc_mask.p, bs));
+        TRY(capped_solve_batch(c, nd, max_cap, c->bc_starts.u32(), c->bc_ends.u32(), v.roff.data(),
+                               v.lengths, v.n_contigs, v.nb, c->bc_mask.u64(), bs));
         pf.ms_profile += nd.ms;
         return QMCP_OK;
     }
@@ -353,9 +349,8 @@ int qmcp_hip_solve_profile_host(qmcp_hip_ctx* c, const uint32_t* starts, const u
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_profile_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, tab, default_cap,
-                                (uint64_t*)c->mask.p, stats, pstats));
+    TRY(solve_profile_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), n_reads, contig_lengths,
+        n_contigs, tab, default_cap, c->mask.u64(), stats, pstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

@@ -11,17 +11,6 @@
 // The pass is a function of (K, start, end, contig, quality) alone: no route of the solve is touched.
 namespace {
 
-// two pooled events, returned to the pool when the scope ends
-struct EventPair {
-    qmcp_hip_ctx* c;
-    hipEvent_t a, b;
-    explicit EventPair(qmcp_hip_ctx* ctx) : c(ctx), a(pool_event(ctx)), b(pool_event(ctx)) {}
-    ~EventPair() {
-        if (a) c->ev_pool.push_back(a);
-        if (b) c->ev_pool.push_back(b);
-    }
-};
-
 // the quality range of the placed reads (d_ids == NULL: every read), before the solve; ms: its device time
 struct QualityRange {
     uint32_t lo = 0xFFFFFFFFu, hi = 0u;
@@ -39,7 +28,7 @@ int quality_range(qmcp_hip_ctx* c, const uint32_t* d_q, const uint32_t* d_ids, u
     HIP_TRY(hipMemcpyAsync(c->qc_words.p, init, sizeof(init), hipMemcpyHostToDevice, st));
     {
         KernelSpan sp(c, "k_qc_range");
-        qmcp::launch_qc_range(st, d_q, d_ids, (uint32_t)n64, (uint32_t*)c->qc_words.p);
+        qmcp::launch_qc_range(st, d_q, d_ids, (uint32_t)n64, c->qc_words.u32());
     }
     HIP_TRY(hipGetLastError());
     uint32_t range[2] = {0xFFFFFFFFu, 0u};
@@ -105,13 +94,13 @@ int quality_pass(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         }
         TRY(ensure(c, c->qc_hist, (size_t)256 * n_tiles * sizeof(uint32_t)));
         const uint32_t spine_n = std::max(256u * n_tiles, n + 1);
-        TRY(ensure(c, c->qc_spine, (size_t)qmcp::scan_spine_entries(spine_n) * sizeof(uint32_t) + 16));
+        TRY(ensure(c, c->qc_spine, scan_spine_bytes(spine_n)));
         TRY(ensure(c, c->qc_kb, ((size_t)n + 1) * sizeof(uint32_t)));
         TRY(ensure(c, c->qc_end, (size_t)n * sizeof(uint32_t)));
         TRY(ensure(c, c->qc_head, (size_t)n * sizeof(uint32_t)));
         HIP_TRY(hipMemcpyAsync(c->qc_tab.p, h_tab.data(), 2 * tab * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync((uint64_t*)c->qc_words.p + 2, 0, 2 * sizeof(uint64_t), st));
-        const uint64_t* d_roff = (const uint64_t*)c->qc_tab.p;
+        HIP_TRY(hipMemsetAsync(c->qc_words.u64() + 2, 0, 2 * sizeof(uint64_t), st));
+        const uint64_t* d_roff = c->qc_tab.u64();
         const uint64_t* d_poff = d_roff + tab;
 
         // 2: keys
@@ -126,46 +115,46 @@ int quality_pass(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         const uint32_t* svals = nullptr;
         if (!wide) {
             int kin = 0;
-            TRY(radix_sort_records(c, st, (const uint32_t*)c->qc_bare.p, n, passes, (uint32_t*)c->qc_hist.p,
-                                   (uint32_t*)c->qc_spine.p, c->qc_keys,
+            TRY(radix_sort_records(c, st, c->qc_bare.u32(), n, passes, c->qc_hist.u32(),
+                                   c->qc_spine.u32(), c->qc_keys,
                                    {"k_radix_hist_rec(quality)", "scan_radix_hist(quality, 3 kernels)",
                                     "k_radix_scatter_rec(quality)"},
                                    &kin));
             sorted = c->qc_keys[kin].p;
         } else {
             WideBufs wb;
-            TRY(radix_sort_wide(c, st, n, passes, (uint32_t*)c->qc_hist.p, (uint32_t*)c->qc_spine.p, c->qc_keys, c->qc_vals,
+            TRY(radix_sort_wide(c, st, n, passes, c->qc_hist.u32(), c->qc_spine.u32(), c->qc_keys, c->qc_vals,
                                 {"k_radix_hist(quality, u64)", "scan_radix_hist(quality, 3 kernels)",
                                  "k_radix_scatter(quality, u64)"},
                                 &wb));
             sorted = c->qc_keys[wb.k].p;
-            svals = (const uint32_t*)c->qc_vals[wb.v].p;
+            svals = c->qc_vals[wb.v].u32();
         }
         // 4: segments and the choice
-        uint32_t* kb = (uint32_t*)c->qc_kb.p;
-        uint32_t* seg_end = (uint32_t*)c->qc_end.p;
-        uint32_t* seg_head = (uint32_t*)c->qc_head.p;
+        uint32_t* kb = c->qc_kb.u32();
+        uint32_t* seg_end = c->qc_end.u32();
+        uint32_t* seg_head = c->qc_head.u32();
         {
             KernelSpan sp(c, "k_qc_marks");
             qmcp::launch_qc_marks(st, wide, sorted, svals, n, q_bits, d_mask, kb, seg_end, seg_head);
         }
         {
             KernelSpan sp(c, "scan_kept(quality, 3 kernels)");
-            qmcp::launch_exclusive_scan(st, kb, n, kb, (uint32_t*)c->qc_spine.p, true);
+            qmcp::launch_exclusive_scan(st, kb, n, kb, c->qc_spine.u32(), true);
         }
         {
             KernelSpan sp(c, "k_rmin_*(quality segment bounds, 2 x 3 kernels)");
-            qmcp::launch_reverse_min_scan(st, seg_end, n, (uint32_t*)c->qc_spine.p);
-            qmcp::launch_reverse_min_scan(st, seg_head, n, (uint32_t*)c->qc_spine.p);
+            qmcp::launch_reverse_min_scan(st, seg_end, n, c->qc_spine.u32());
+            qmcp::launch_reverse_min_scan(st, seg_head, n, c->qc_spine.u32());
         }
         {
             KernelSpan sp(c, "k_qc_choose");
             qmcp::launch_qc_choose(st, wide, sorted, svals, n, kb, seg_end, seg_head, d_mask,
-                                   (unsigned long long*)c->qc_words.p + 2);
+                                   c->qc_words.as<unsigned long long>() + 2);
         }
         HIP_TRY(hipGetLastError());
         uint64_t counters[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(counters, (uint64_t*)c->qc_words.p + 2, sizeof(counters), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counters, c->qc_words.u64() + 2, sizeof(counters), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(e1, st));
         HIP_TRY(hipStreamSynchronize(st));
         qs.cells_contested = counters[0];
@@ -218,9 +207,8 @@ int qmcp_hip_solve_quality_host(qmcp_hip_ctx* c, const uint32_t* starts, const u
         TRY(upload_columns(c, starts, ends, n_reads, &sent_columns));
         HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_quality_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                (const uint32_t*)c->in_aux1.p, n_reads, contig_read_offsets, contig_lengths, n_contigs,
-                                max_coverage, (uint64_t*)c->mask.p, stats, qstats));
+    TRY(solve_quality_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux1.u32(), n_reads, contig_read_offsets,
+        contig_lengths, n_contigs, max_coverage, c->mask.u64(), stats, qstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;
@@ -266,15 +254,13 @@ int qmcp_hip_solve_quality_by_contig_host(qmcp_hip_ctx* c, const uint32_t* start
         HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, c->stream));
     }
     QualityRange qr;
-    TRY(quality_range(c, (const uint32_t*)c->in_aux1.p, (const uint32_t*)c->in_aux0.p, n_reads, qr));
+    TRY(quality_range(c, c->in_aux1.u32(), c->in_aux0.u32(), n_reads, qr));
     qmcp_hip_stats plain;
     std::memset(&plain, 0, sizeof(plain));
-    TRY(solve_by_contig_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                  (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, max_coverage,
-                                  (uint64_t*)c->mask.p, &plain));
-    TRY(quality_pass(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p, (const uint32_t*)c->in_aux1.p,
-                     (const uint32_t*)c->in_aux0.p, n_reads, nullptr, contig_lengths, n_contigs, qr, plain,
-                     (uint64_t*)c->mask.p, qstats));
+    TRY(solve_by_contig_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), n_reads, contig_lengths,
+        n_contigs, max_coverage, c->mask.u64(), &plain));
+    TRY(quality_pass(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux1.u32(), c->in_aux0.u32(), n_reads, nullptr,
+        contig_lengths, n_contigs, qr, plain, c->mask.u64(), qstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

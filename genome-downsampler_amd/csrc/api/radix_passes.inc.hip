@@ -60,7 +60,7 @@ int radix_sort_wide(qmcp_hip_ctx* c, hipStream_t st, uint32_t n, uint32_t passes
     const uint32_t n_tiles = qmcp::sort_tiles(n);
     for (uint32_t p = 0; p < passes; ++p) {
         const int kin = io->k, kout = kin ^ 1, vout = io->v < 0 ? 0 : (io->v ^ 1);
-        const uint32_t* vals_in = io->v < 0 ? nullptr : (const uint32_t*)vals[io->v].p;
+        const uint32_t* vals_in = io->v < 0 ? nullptr : vals[io->v].u32();
         {
             KernelSpan whole(c, nm.scan ? nullptr : nm.hist);
             {
@@ -73,7 +73,7 @@ int radix_sort_wide(qmcp_hip_ctx* c, hipStream_t st, uint32_t n, uint32_t passes
             }
             {
                 KernelSpan sp(c, nm.scatter);
-                qmcp::launch_radix_scatter(st, true, keys[kin].p, vals_in, n, 8 * p, hist, keys[kout].p, (uint32_t*)vals[vout].p);
+                qmcp::launch_radix_scatter(st, true, keys[kin].p, vals_in, n, 8 * p, hist, keys[kout].p, vals[vout].u32());
             }
         }
         HIP_TRY(hipGetLastError());

@@ -61,16 +61,16 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
     const size_t words_in = (size_t)((n64 + 63) / 64);
     const size_t words_b = (size_t)((most + 63) / 64);
     TRY(ensure(c, c->rp_stat, QMCP_REPLICATES_MAX * sizeof(unsigned long long)));
-    unsigned long long* d_mates = (unsigned long long*)c->rp_stat.p;  // per replicate: the reads that joined as mates
+    unsigned long long* d_mates = c->rp_stat.as<unsigned long long>();  // per replicate: the reads that joined as mates
     TRY(ensure(c, c->rp_words, (words_b + 2) * sizeof(uint32_t)));
-    TRY(ensure(c, c->rp_spine, (size_t)(qmcp::scan_spine_entries((uint32_t)words_b + 1) + 1) * sizeof(uint32_t) + 16));
+    TRY(ensure(c, c->rp_spine, scan_spine_bytes((uint32_t)words_b + 1, 1)));
     TRY(ensure(c, c->rp_offs[0], (size_t)tab_max * sizeof(uint32_t)));
     TRY(ensure(c, c->rp_offs[1], (size_t)tab_max * sizeof(uint32_t)));
     if (!by_mask) {
         TRY(ensure(c, c->rp_kept, words_b * sizeof(uint64_t)));
         TRY(ensure(c, c->rp_taken, words_in * sizeof(uint64_t)));
     }
-    uint64_t* d_taken = (uint64_t*)c->rp_taken.p;
+    uint64_t* d_taken = c->rp_taken.u64();
     // ev_a brackets what is queued between two host waits; ev_b a split, whose time is added at the next wait
     bool open = false, split_timed = false;
     auto begin = [&]() -> int {
@@ -117,11 +117,9 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
         TRY(begin());
         {
             KernelSpan sp(c, "replicate offsets(popcounts, scan, k_rep_offsets)");
-            qmcp::launch_word_popcounts(st, taken, words, (uint32_t*)c->rp_words.p);
-            qmcp::launch_exclusive_scan(st, (const uint32_t*)c->rp_words.p, words, (uint32_t*)c->rp_words.p,
-                                        (uint32_t*)c->rp_spine.p, true);
-            qmcp::launch_rep_offsets(st, (const uint32_t*)c->rp_offs[cur].p, n_contigs, taken, (const uint32_t*)c->rp_words.p,
-                                     (uint32_t*)c->rp_offs[cur ^ 1u].p);
+            queue_mask_ranks(st, taken, words, c->rp_words, c->rp_spine);
+            qmcp::launch_rep_offsets(st, c->rp_offs[cur].u32(), n_contigs, taken, c->rp_words.u32(),
+                                     c->rp_offs[cur ^ 1u].u32());
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(ranks.data(), c->rp_offs[cur ^ 1u].p, tab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -137,16 +135,16 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
             HIP_TRY(hipEventRecord(ev_b.a, st));
             {
                 KernelSpan sp(c, "k_rep_split");
-                qmcp::launch_rep_split(st, cd.first, cd.s, cd.e, cd.o, taken, (const uint32_t*)c->rp_words.p, cd.n, label,
-                                       rp.d_labels, (uint32_t*)c->rp_starts[set].p, (uint32_t*)c->rp_ends[set].p,
-                                       (uint32_t*)c->rp_orig[set].p);
+                qmcp::launch_rep_split(st, cd.first, cd.s, cd.e, cd.o, taken, c->rp_words.u32(), cd.n, label,
+                                       rp.d_labels, c->rp_starts[set].u32(), c->rp_ends[set].u32(),
+                                       c->rp_orig[set].u32());
             }
             HIP_TRY(hipEventRecord(ev_b.b, st));
             HIP_TRY(hipGetLastError());
             split_timed = true;
         }
-        cd.s = (const uint32_t*)c->rp_starts[set].p;
-        cd.e = (const uint32_t*)c->rp_ends[set].p;
+        cd.s = c->rp_starts[set].u32();
+        cd.e = c->rp_ends[set].u32();
         cd.o = c->rp_orig[set].p;
         cd.first = false;
         cd.n = n_next;
@@ -159,8 +157,8 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
     auto whole_batch = [&](size_t b, RepCands& cd) -> int {
         g.view(b, v);
         v.tables32();
-        cd.s = (const uint32_t*)c->bc_starts.p;
-        cd.e = (const uint32_t*)c->bc_ends.p;
+        cd.s = c->bc_starts.u32();
+        cd.e = c->bc_ends.u32();
         cd.o = v.records;
         cd.first = true;
         cd.n = v.nb;
@@ -177,7 +175,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
         qmcp_hip_stats bs;
         std::memset(&bs, 0, sizeof(bs));
         TRY(solve_on_device(c, cd.s, cd.e, cd.offs.data(), g.lengths + bt.first_contig, bt.n_contigs, cd.n, rp.coverages[j],
-                            (uint64_t*)c->bc_mask.p, &bs));
+                            c->bc_mask.u64(), &bs));
         add_batch_stats(rp.rep[j], bs, first_of_j, is_largest);
         rp.rep[j].n_contigs += bt.n_contigs;
         rp.rep[j].total_length += bt.positions;
@@ -193,7 +191,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
         TRY(whole_batch(live[0], cd));
         uint32_t unlabelled = 1;  // the replicate whose mask is in bc_mask and whose labels are not written yet
         for (uint32_t j = 1; j < K; ++j) {
-            TRY(advance(cd, (const uint64_t*)c->bc_mask.p, bt.n_contigs, j));
+            TRY(advance(cd, c->bc_mask.u64(), bt.n_contigs, j));
             unlabelled = 0;
             if (cd.n == 0) break;  // no read left: this replicate and every later one are empty
             TRY(solve(cd, bt, j, true, true));
@@ -202,7 +200,7 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
         if (unlabelled) {
             TRY(begin());
             KernelSpan sp(c, "k_ladder_levels(replicates)");
-            qmcp::launch_ladder_levels(st, cd.first, (const uint64_t*)c->bc_mask.p, cd.o, cd.n, unlabelled, rp.d_labels);
+            qmcp::launch_ladder_levels(st, cd.first, c->bc_mask.u64(), cd.o, cd.n, unlabelled, rp.d_labels);
         }
         HIP_TRY(hipGetLastError());
     } else if (!live.empty()) {
@@ -220,16 +218,15 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
                 if (cd.n == 0) continue;
                 {
                     KernelSpan sp(c, "k_rep_gather_taken");
-                    qmcp::launch_rep_gather_taken(st, cd.first, cd.o, cd.n, d_taken, (uint64_t*)c->rp_kept.p);
+                    qmcp::launch_rep_gather_taken(st, cd.first, cd.o, cd.n, d_taken, c->rp_kept.u64());
                 }
-                TRY(advance(cd, (const uint64_t*)c->rp_kept.p, bt.n_contigs, 0));
+                TRY(advance(cd, c->rp_kept.u64(), bt.n_contigs, 0));
                 if (cd.n == 0) continue;
                 TRY(solve(cd, bt, j, first_of_j, b == g.largest));
                 first_of_j = false;
                 TRY(begin());
                 KernelSpan sp(c, "k_rep_mark");
-                qmcp::launch_rep_mark(st, (const uint64_t*)c->bc_mask.p, (const uint32_t*)cd.o, cd.n, j + 1, rp.d_labels,
-                                      d_taken);
+                qmcp::launch_rep_mark(st, c->bc_mask.u64(), (const uint32_t*)cd.o, cd.n, j + 1, rp.d_labels, d_taken);
             }
             HIP_TRY(hipGetLastError());
             if (rs.n_offered[j] == 0) break;  // no read left anywhere
@@ -257,11 +254,11 @@ int replicates_later(qmcp_hip_ctx* c, ReplicatesRun& rp, const GroupedReads& g, 
         for (uint32_t j = 0; j < K; ++j) {
             {
                 KernelSpan sp(c, "k_rep_label_mask");
-                qmcp::launch_rep_label_mask(st, rp.d_labels, n64, j + 1, (uint64_t*)c->rp_lmask.p);
+                qmcp::launch_rep_label_mask(st, rp.d_labels, n64, j + 1, c->rp_lmask.u64());
             }
             HIP_TRY(hipGetLastError());
             qmcp_hip_depth_stats ds;
-            TRY(depth_report_on_device(c, g.d_starts, g.d_ends, g.d_ids, (const uint64_t*)c->rp_lmask.p, n64, g.lengths, g.n_contigs,
+            TRY(depth_report_on_device(c, g.d_starts, g.d_ends, g.d_ids, c->rp_lmask.u64(), n64, g.lengths, g.n_contigs,
                                        rp.coverages[j], dc, 0, rows.data(), nullptr, nullptr, nullptr, nullptr, &ds));
             for (const qmcp_hip_depth_row& row : rows) {
                 rs.short_positions[j] += row.deficit_positions;
@@ -346,9 +343,9 @@ int qmcp_hip_solve_replicates_host(qmcp_hip_ctx* c, const uint32_t* starts, cons
         HIP_TRY(hipMemcpyAsync(c->in_ends.p, ends, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_replicates_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                   (const uint32_t*)c->in_aux0.p, n_reads, contig_lengths, n_contigs, coverages, n_replicates,
-                                   flags, (uint64_t*)c->mask.p, (uint8_t*)c->rp_labels.p, stats, rep_stats, rstats));
+    TRY(solve_replicates_on_device(c, c->in_starts.u32(), c->in_ends.u32(),
+                                   c->in_aux0.u32(), n_reads, contig_lengths, n_contigs, coverages, n_replicates,
+                                   flags, c->mask.u64(), c->rp_labels.as<uint8_t>(), stats, rep_stats, rstats));
     if (n_reads) HIP_TRY(hipMemcpyAsync(labels_out, c->rp_labels.p, (size_t)n_reads, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;
@@ -368,7 +365,7 @@ int qmcp_hip_solve_replicates_device(qmcp_hip_ctx* c, const uint32_t* d_starts, 
     TRY(ensure(c, c->rp_mask0, (size_t)((n_reads + 63) / 64) * sizeof(uint64_t)));
     TRY(order_after(c, hip_stream));
     return solve_replicates_on_device(c, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, n_contigs, coverages,
-                                      n_replicates, flags, (uint64_t*)c->rp_mask0.p, d_labels_out, stats, rep_stats, rstats);
+                                      n_replicates, flags, c->rp_mask0.u64(), d_labels_out, stats, rep_stats, rstats);
 }
 
 }  // extern "C"

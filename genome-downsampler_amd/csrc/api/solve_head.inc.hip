@@ -36,7 +36,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
                  uint32_t M, uint64_t* d_mask) {
     if (c->pending) return fail(QMCP_EINVAL, "a solve is already pending on this context (call qmcp_hip_solve_end)");
     c->pend_spiky = false;
-    if (!c->h_scalars) HIP_TRY(hipHostMalloc((void**)&c->h_scalars, 16 * sizeof(unsigned long long), hipHostMallocDefault));
+    TRY(ensure_pinned(c, c->h_scalars, 16 * sizeof(unsigned long long)));
     SolveRun& run = c->run;
     run = SolveRun();
     run.d_starts = d_starts; run.d_ends = d_ends; run.roff = roff; run.lengths = lengths;
@@ -64,9 +64,8 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     qmcp::PmGridPlan grid;
     {
         const uint32_t tiles_seg = qmcp::seg_tile_bound(n);  // second partition level: tiles aligned to super-ranges
-        const uint32_t spine_a = qmcp::scan_spine_entries(256u * tiles_seg);
-        const uint32_t spine_b = qmcp::scan_spine_entries(ltot + 1) + 1;
-        TRY(ensure(c, c->spine, (size_t)(spine_a > spine_b ? spine_a : spine_b) * sizeof(uint32_t) + 16));
+        const size_t spine_bytes = std::max(scan_spine_bytes(256u * tiles_seg), scan_spine_bytes(ltot + 1, 1));
+        TRY(ensure(c, c->spine, spine_bytes));
         TRY(ensure(c, c->hist, (size_t)256 * tiles_seg * sizeof(uint32_t)));
         // (the pass-major form's two 16-bit record streams live in keys[0] and keys[1]: padded slices, ~6 B per read)
         // (which grid the form cuts its ranges on is decided here, before anything is queued: every size below follows it)
@@ -86,7 +85,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         }
         TRY(ensure(c, c->vals[0], (size_t)n * sizeof(uint32_t)));
         TRY(ensure(c, c->vals[1], (size_t)n * sizeof(uint32_t)));
-        TRY(ensure(c, c->spine2, (size_t)(spine_a > spine_b ? spine_a : spine_b) * sizeof(uint32_t) + 16));
+        TRY(ensure(c, c->spine2, spine_bytes));
         TRY(ensure(c, c->hist2, ((size_t)256 * qmcp::part_pass_pitch(n) + 4) * sizeof(uint32_t)));  // (+ the scan's total)
         TRY(ensure(c, c->cstart, ((size_t)ltot + 8) * sizeof(uint32_t)));  // also the event sweep's changed-block S
         TRY(ensure(c, c->boff, ((size_t)ltot + 1) * sizeof(uint32_t)));
@@ -109,7 +108,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
             TRY(ensure(c, c->ecnt, ((size_t)ltot + 1) * sizeof(uint32_t)));
             TRY(ensure(c, c->eoff, ((size_t)ltot + 1) * sizeof(uint32_t)));
             TRY(ensure(c, c->next_head, ((size_t)n + 2) * sizeof(uint32_t)));
-            TRY(ensure(c, c->spine, (size_t)(qmcp::scan_spine_entries(n + 1) + 1) * sizeof(uint32_t) + 16));
+            TRY(ensure(c, c->spine, scan_spine_bytes(n + 1, 1)));
         }
     }
     c->grew_mid_solve = 0;
@@ -124,7 +123,7 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     run.range_shift = qmcp::range_shift_for(ltot);
     run.may_rank = n >= rank_min_reads(c) && qmcp::range_path_supported(ltot);
     const uint32_t range_shift = run.range_shift;
-    uint32_t* d_range_start = (uint32_t*)c->ranges.p;
+    uint32_t* d_range_start = c->ranges.u32();
     uint32_t* d_max_load = d_range_start + 65540;
     uint32_t* d_seg_tables = d_range_start + 65544;  // super_start, tile_base, pass_base (257 each)
     run.two_level = qmcp::range_path_two_level(ltot);
@@ -167,13 +166,13 @@ int enqueue_head(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
         HIP_TRY(hipMemcpyAsync(hs, c->stats.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
         HIP_TRY(hipMemcpyAsync(hs + 3, d_max_load, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
         if (run.pm) HIP_TRY(hipMemcpyAsync(hs + 7, d_max_load + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));  // (the heaviest range's wave-slots: stats only)
-        if (run.nu_filter) HIP_TRY(hipMemcpyAsync(hs + 5, (uint32_t*)c->stats.p + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
+        if (run.nu_filter) HIP_TRY(hipMemcpyAsync(hs + 5, c->stats.u32() + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream2));
         // How spiky the starts are only decides WHICH exact sweep kernel runs, so the count of the previous
         // call of this shape is good enough (and saves waiting for k_range_offsets); a first call waits.
         if (c->spiky_known && c->spiky_n == n64 && c->spiky_ltot == pr.ltot) {
             hs[4] = c->spiky_empty;
         } else {
-            HIP_TRY(hipMemcpyAsync(hs + 4, (uint32_t*)c->stats.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s1));
+            HIP_TRY(hipMemcpyAsync(hs + 4, c->stats.u32() + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s1));
             run.wait_empty = true;
         }
         run.ranked_counted = true;
@@ -190,23 +189,23 @@ int queue_rm_head(qmcp_hip_ctx* c, hipStream_t s1, uint32_t filter, bool clear_m
     const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot, n_contigs = run.n_contigs;
     const uint32_t range_shift = run.range_shift;
     const bool two_level = run.two_level;
-    uint32_t* d_range_start = (uint32_t*)c->ranges.p;
+    uint32_t* d_range_start = c->ranges.u32();
     uint32_t* d_max_load = d_range_start + 65540;
     uint32_t* d_seg_tables = d_range_start + 65544;  // super_start, tile_base, pass_base (257 each)
     // (a re-run of the head -- after a span change, or with the filter switched on -- must not add to what the first
     //  run counted: empty positions, exceptions, list flag, overflow entries)
     static const uint32_t zeros[4] = {0u, 0u, 0u, 0u};
-    HIP_TRY(hipMemcpyAsync((uint32_t*)c->stats.p + 3, zeros, sizeof(zeros), hipMemcpyHostToDevice, s1));
-    uint32_t* exc = filter ? (uint32_t*)c->nu_exc.p : nullptr;
+    HIP_TRY(hipMemcpyAsync(c->stats.u32() + 3, zeros, sizeof(zeros), hipMemcpyHostToDevice, s1));
+    uint32_t* exc = filter ? c->nu_exc.u32() : nullptr;
     const uint32_t cap = nu_cap_for(n);
     uint32_t* exc_cnt = filter ? qmcp::nu_exc_counts(exc, cap) : nullptr;
     if (filter) HIP_TRY(hipMemsetAsync(exc_cnt, 0, ((size_t)cap / 128 + 4) * sizeof(uint32_t), s1));
     {
         KernelSpan sp(c, "k_prepare");
-        qmcp::launch_prepare(s1, run.d_starts, run.d_ends, n, (const uint64_t*)c->roff.p,
-                             (const uint64_t*)c->poff.p, n_contigs, nullptr, nullptr, nullptr,
-                             (uint32_t*)c->stats.p, two_level ? range_shift + 8 : range_shift,
-                             (uint32_t*)c->hist2.p, nullptr, nullptr,
+        qmcp::launch_prepare(s1, run.d_starts, run.d_ends, n, c->roff.u64(),
+                             c->poff.u64(), n_contigs, nullptr, nullptr, nullptr,
+                             c->stats.u32(), two_level ? range_shift + 8 : range_shift,
+                             c->hist2.u32(), nullptr, nullptr,
                              clear_mask ? (unsigned long long*)run.d_mask : nullptr,  // also clears the keep mask
                              filter, exc, cap, exc_cnt);
     }
@@ -214,37 +213,33 @@ int queue_rm_head(qmcp_hip_ctx* c, hipStream_t s1, uint32_t filter, bool clear_m
     HIP_TRY(hipEventRecord(c->ev[EV_PREP], s1));
     {
         KernelSpan sp(c, "scan_radix_hist(3 kernels)");
-        qmcp::launch_exclusive_scan(s1, (const uint32_t*)c->hist2.p, 256u * qmcp::part_pass_pitch(n),
-                                    (uint32_t*)c->hist2.p, (uint32_t*)c->spine2.p, true);
+        qmcp::launch_exclusive_scan(s1, c->hist2.u32(), 256u * qmcp::part_pass_pitch(n),
+                                    c->hist2.u32(), c->spine2.u32(), true);
     }
     if (!two_level) {
         KernelSpan sp(c, "k_range_partition");
-        qmcp::launch_range_partition(s1, nullptr, run.d_starts, (const uint64_t*)c->roff.p,
-                                     (const uint64_t*)c->poff.p, n_contigs, n, range_shift,
-                                     (const uint32_t*)c->hist2.p, (uint16_t*)c->keys[0].p,
-                                     (uint32_t*)c->vals[0].p, d_range_start, d_max_load, run.d_ends, filter);
+        qmcp::launch_range_partition(s1, nullptr, run.d_starts, c->roff.u64(), c->poff.u64(), n_contigs, n, range_shift,
+                                     c->hist2.u32(), c->keys[0].as<uint16_t>(), c->vals[0].u32(), d_range_start,
+                                     d_max_load, run.d_ends, filter);
     } else {
         // more than 256 ranges (genomes beyond 8.39 M positions): first into <= 256 super-ranges as
         // {global start, index} records, then every super-range into its final ranges
         {
             KernelSpan sp(c, "k_range_partition(level 1)");
-            qmcp::launch_partition_level1(s1, run.d_starts, (const uint64_t*)c->roff.p,
-                                          (const uint64_t*)c->poff.p, n_contigs, n, range_shift + 8,
-                                          (const uint32_t*)c->hist2.p, c->keys[1].p, d_seg_tables, d_max_load,
-                                          run.d_ends, filter);
+            qmcp::launch_partition_level1(s1, run.d_starts, c->roff.u64(), c->poff.u64(), n_contigs, n, range_shift + 8,
+                                          c->hist2.u32(), c->keys[1].p, d_seg_tables, d_max_load, run.d_ends, filter);
         }
         KernelSpan sp(c, "partition level 2 (tables, hist, scan, scatter)");
-        qmcp::launch_partition_level2(s1, c->keys[1].p, n, range_shift, d_seg_tables, (uint32_t*)c->hist.p,
-                                      (uint32_t*)c->spine.p, (uint16_t*)c->keys[0].p,
-                                      (uint32_t*)c->vals[0].p, d_range_start, d_max_load);
+        qmcp::launch_partition_level2(s1, c->keys[1].p, n, range_shift, d_seg_tables, c->hist.u32(), c->spine.u32(),
+                                      c->keys[0].as<uint16_t>(), c->vals[0].u32(), d_range_start, d_max_load);
     }
     HIP_TRY(hipEventRecord(c->ev_fork, s1));  // statistics and heaviest load are final here
     {
         // per-range LDS histogram scanned in place: bucket offsets without a genome-wide scan; it also
         // counts the positions that start no read (stats word 3: the host picks the sweep kernel by it)
         KernelSpan sp(c, "k_range_offsets");
-        qmcp::launch_range_offsets(s1, (const uint16_t*)c->keys[0].p, d_range_start, range_shift, ltot,
-                                   (uint32_t*)c->boff.p, (uint32_t*)c->stats.p + 3);
+        qmcp::launch_range_offsets(s1, c->keys[0].as<uint16_t>(), d_range_start, range_shift, ltot,
+                                   c->boff.u32(), c->stats.u32() + 3);
     }
     HIP_TRY(hipGetLastError());
     run.nu_filter = filter;
@@ -256,38 +251,38 @@ int queue_rm_head(qmcp_hip_ctx* c, hipStream_t s1, uint32_t filter, bool clear_m
 int queue_pm_head(qmcp_hip_ctx* c, hipStream_t st, uint32_t filter, bool rerun) {
     SolveRun& run = c->run;
     const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot, n_contigs = run.n_contigs;
-    const uint32_t* d_grid = (const uint32_t*)c->pm_grid.p;
-    uint32_t* d_stats = (uint32_t*)c->stats.p;
+    const uint32_t* d_grid = c->pm_grid.u32();
+    uint32_t* d_stats = c->stats.u32();
     // (a re-run must not add to what the first run counted -- empty positions, exceptions, list flag, overflow entries;
     //  the first run's words were cleared with the statistics' initial values)
     if (rerun) HIP_TRY(hipMemcpyAsync(d_stats + 3, c->h_stats_init + 1, 4 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    uint32_t* d_range_start = (uint32_t*)c->ranges.p;
+    uint32_t* d_range_start = c->ranges.u32();
     uint32_t* d_max_load = d_range_start + 65540;
     {
         KernelSpan sp(c, "k_pm_prepare_sort", st);
-        qmcp::launch_pm_prepare_sort(st, run.d_starts, run.d_ends, n, (const uint64_t*)c->roff.p, (const uint64_t*)c->poff.p,
-                                     n_contigs, run.range_shift, run.pm_ranges, d_grid, (uint16_t*)c->keys[0].p, (uint16_t*)c->keys[1].p,
-                                     (uint32_t*)c->hist2.p, (uint32_t*)c->hist.p, d_stats, (unsigned long long*)run.d_mask, filter,
-                                     filter ? (uint32_t*)c->nu_exc.p : nullptr, nu_cap_for(n),
-                                     filter ? qmcp::nu_exc_counts((uint32_t*)c->nu_exc.p, nu_cap_for(n)) : nullptr);
+        qmcp::launch_pm_prepare_sort(st, run.d_starts, run.d_ends, n, c->roff.u64(), c->poff.u64(),
+                                     n_contigs, run.range_shift, run.pm_ranges, d_grid, c->keys[0].as<uint16_t>(), c->keys[1].as<uint16_t>(),
+                                     c->hist2.u32(), c->hist.u32(), d_stats, (unsigned long long*)run.d_mask, filter,
+                                     filter ? c->nu_exc.u32() : nullptr, nu_cap_for(n),
+                                     filter ? qmcp::nu_exc_counts(c->nu_exc.u32(), nu_cap_for(n)) : nullptr);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_PREP], st));
     {
         KernelSpan sp(c, "k_pm_row_sums", st);
-        qmcp::launch_pm_row_sums(st, (const uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, (uint32_t*)c->pm_work.p);
+        qmcp::launch_pm_row_sums(st, c->hist2.u32(), c->hist.u32(), n, c->pm_work.u32());
     }
     {
         KernelSpan sp(c, "k_pm_tables", st);
-        qmcp::launch_pm_tables(st, (uint32_t*)c->hist2.p, (const uint32_t*)c->hist.p, n, run.pm_ranges,
-                               (uint32_t*)c->pm_desc.p, (const uint32_t*)c->pm_work.p, d_range_start, d_max_load,
-                               rerun ? nullptr : (uint32_t*)c->scalars.p);  // (the result scalars, 64 bytes: cleared here for the one-span tail)
+        qmcp::launch_pm_tables(st, c->hist2.u32(), c->hist.u32(), n, run.pm_ranges,
+                               c->pm_desc.u32(), c->pm_work.u32(), d_range_start, d_max_load,
+                               rerun ? nullptr : c->scalars.u32());  // (the result scalars, 64 bytes: cleared here for the one-span tail)
     }
     HIP_TRY(hipEventRecord(c->ev_fork, st));  // statistics and heaviest load are final here
     {
         KernelSpan sp(c, "k_pm_offsets", st);
-        qmcp::launch_pm_offsets(st, (const uint16_t*)c->keys[0].p, (const uint32_t*)c->pm_desc.p, (const uint32_t*)c->hist2.p, n,
-                                d_range_start, run.range_shift, run.pm_ranges, d_grid, ltot, (uint32_t*)c->boff.p, d_stats + 3);
+        qmcp::launch_pm_offsets(st, c->keys[0].as<uint16_t>(), c->pm_desc.u32(), c->hist2.u32(), n,
+                                d_range_start, run.range_shift, run.pm_ranges, d_grid, ltot, c->boff.u32(), d_stats + 3);
     }
     HIP_TRY(hipGetLastError());
     run.nu_filter = filter;
@@ -300,9 +295,8 @@ void queue_pm_rank(qmcp_hip_ctx* c, hipStream_t st, const uint32_t* ev_sev, cons
     const uint32_t n = (uint32_t)run.pr.n;
     const bool by_records = qmcp::pm_rank_scratch_by_records(run.range_shift, run.pm_ranges, n);
     KernelSpan sp(c, "k_pm_walk", st);
-    qmcp::launch_pm_walk(st, (const uint16_t*)c->keys[0].p, (const uint16_t*)c->keys[1].p, (const uint32_t*)c->pm_desc.p,
-                         (const uint32_t*)c->hist2.p, n, (const uint32_t*)c->ranges.p, run.range_shift, run.pm_ranges,
-                         (const uint32_t*)c->pm_grid.p, (const uint32_t*)c->boff.p, (const uint32_t*)c->selend.p, (unsigned long long*)run.d_mask,
-                         (unsigned long long*)c->scalars.p, c->rankamb.p, by_records, ev_sev, ev_lastns,
-                         (const uint64_t*)c->poff.p, run.n_contigs, ell);
+    qmcp::launch_pm_walk(st, c->keys[0].as<uint16_t>(), c->keys[1].as<uint16_t>(), c->pm_desc.u32(), c->hist2.u32(), n,
+                         c->ranges.u32(), run.range_shift, run.pm_ranges, c->pm_grid.u32(), c->boff.u32(),
+                         c->selend.u32(), (unsigned long long*)run.d_mask, c->scalars.as<unsigned long long>(),
+                         c->rankamb.p, by_records, ev_sev, ev_lastns, c->poff.u64(), run.n_contigs, ell);
 }

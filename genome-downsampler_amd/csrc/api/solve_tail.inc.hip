@@ -20,7 +20,7 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     }
     const uint32_t range_shift = run.range_shift;
     const bool may_rank = run.may_rank;
-    uint32_t* d_range_start = (uint32_t*)c->ranges.p;
+    uint32_t* d_range_start = c->ranges.u32();
     const uint32_t* hs = c->h_head;
     bool have_gstart = run.have_gstart;
     const bool ranked_counted = run.ranked_counted;
@@ -53,17 +53,16 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     const uint32_t pos_bits = bit_width(ltot - 1) == 0 ? 1u : bit_width(ltot - 1);
     uint32_t span_bits = 0;
     bool wide = false;
-    const uint32_t* d_gstart = (const uint32_t*)c->vals[1].p;
+    const uint32_t* d_gstart = c->vals[1].u32();
     const uint32_t* d_key32 = d_gstart;  // uniform span: the key is the start position itself
     auto need_gstart = [&]() {
         if (have_gstart) return;
         KernelSpan sp(c, "k_gstart");
-        qmcp::launch_gstart(c->stream, d_starts, n, (const uint64_t*)c->roff.p, (const uint64_t*)c->poff.p,
-                            n_contigs, (uint32_t*)c->vals[1].p);
+        qmcp::launch_gstart(c->stream, d_starts, n, c->roff.u64(), c->poff.u64(), n_contigs, c->vals[1].u32());
         have_gstart = true;
     };
     bool sweep_done = false, ranked = false;
-    uint32_t* d_iters = (uint32_t*)((char*)c->scalars.p + 16);
+    uint32_t* d_iters = (uint32_t*)(c->scalars.as<char>() + 16);
     bool near_done = false;
     uint32_t max_load_now = max_load;
     if (uniform && run.nu_filter != 0 && run.nu_filter != max_span) {
@@ -71,7 +70,7 @@ int enqueue_tail(qmcp_hip_ctx* c) {
         c->nu_ell = 0;
         if (run.pm) TRY(queue_pm_head(c, c->stream, 0, true));
         else TRY(queue_rm_head(c, c->stream, 0, true));
-        HIP_TRY(hipMemcpyAsync(c->h_nu, (uint32_t*)c->ranges.p + 65540, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_nu, c->ranges.u32() + 65540, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         max_load_now = c->h_nu[0];
     }
@@ -96,11 +95,11 @@ int enqueue_tail(qmcp_hip_ctx* c) {
         {
             KernelSpan sp(c, "k_general_keys");
             qmcp::launch_general_keys(c->stream, wide, d_gstart, d_starts, d_ends, n, span_bits,
-                                      max_span, nullptr, key_dst, (uint32_t*)c->ecnt.p, ltot + 1);
+                                      max_span, nullptr, key_dst, c->ecnt.u32(), ltot + 1);
         }
         HIP_TRY(hipGetLastError());
         TRY(scan_counts(c, c->ecnt, c->eoff, ltot));
-        d_key32 = (const uint32_t*)c->vals[0].p;
+        d_key32 = c->vals[0].u32();
     }
     if (!near_done) HIP_TRY(hipEventRecord(c->ev[EV_SCAN], c->stream));
     // Uniform span, large call: neither the sweep nor the keep mask needs a full sort.  One stable
@@ -125,15 +124,14 @@ int enqueue_tail(qmcp_hip_ctx* c) {
         HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], s1));
         sweep_done = true;
         if (ranked && run.pm) {
-            queue_pm_rank(c, s1, expand_left_out ? (const uint32_t*)c->cstart.p : nullptr, (const uint32_t*)c->evlast.p, max_span);
+            queue_pm_rank(c, s1, expand_left_out ? c->cstart.u32() : nullptr, c->evlast.u32(), max_span);
             HIP_TRY(hipGetLastError());
         } else if (ranked) {
             KernelSpan sp(c, "k_rank_mark");
-            qmcp::launch_rank_mark(s1, (const uint16_t*)c->keys[0].p, (const uint32_t*)c->vals[0].p,
-                                   d_range_start, range_shift, ltot,
-                                   (const uint32_t*)c->boff.p, (const uint32_t*)c->selend.p,
-                                   (unsigned long long*)d_mask, (unsigned long long*)c->scalars.p,
-                                   c->rankamb.p, qmcp::rank_scratch_by_records(range_shift, ltot, n));
+            qmcp::launch_rank_mark(s1, c->keys[0].as<uint16_t>(), c->vals[0].u32(), d_range_start, range_shift, ltot,
+                                   c->boff.u32(), c->selend.u32(), (unsigned long long*)d_mask,
+                                   c->scalars.as<unsigned long long>(), c->rankamb.p,
+                                   qmcp::rank_scratch_by_records(range_shift, ltot, n));
             HIP_TRY(hipGetLastError());
         }
     }
@@ -148,12 +146,12 @@ int enqueue_tail(qmcp_hip_ctx* c) {
         // keep mask already written by k_rank_mark
     } else if (!wide) {
         // records {key, read index}: keys[0] <-> keys[1]; the first pass reads bare keys
-        TRY(radix_sort_records(c, c->stream, d_key32, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, c->keys,
+        TRY(radix_sort_records(c, c->stream, d_key32, n, passes, c->hist.u32(), c->spine.u32(), c->keys,
                                {"k_radix_hist_rec", "scan_radix_hist(3 kernels)", "k_radix_scatter_rec"}, &kin));
     } else {
         // 64-bit composite keys (huge genome x wide span range): split key / payload arrays
         WideBufs wb;
-        TRY(radix_sort_wide(c, c->stream, n, passes, (uint32_t*)c->hist.p, (uint32_t*)c->spine.p, c->keys, c->vals,
+        TRY(radix_sort_wide(c, c->stream, n, passes, c->hist.u32(), c->spine.u32(), c->keys, c->vals,
                             {"k_radix_hist", "scan_radix_hist(3 kernels)", "k_radix_scatter"}, &wb));
         kin = wb.k;
         vin = wb.v;
@@ -163,12 +161,12 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     HIP_TRY(hipMemsetAsync(c->boff.p, 0xFF, ((size_t)ltot + 1) * sizeof(uint32_t), c->stream));
     {
         KernelSpan sp(c, "k_bucket_heads");
-        qmcp::launch_bucket_heads(c->stream, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, n,
-                                  span_bits, ltot, (uint32_t*)c->boff.p);
+        qmcp::launch_bucket_heads(c->stream, wide, c->keys[kin].p, c->vals[vin].u32(), n,
+                                  span_bits, ltot, c->boff.u32());
     }
     {
         KernelSpan sp(c, "reverse_min_scan(3 kernels)");
-        qmcp::launch_reverse_min_scan(c->stream, (uint32_t*)c->boff.p, ltot + 1, (uint32_t*)c->spine.p);
+        qmcp::launch_reverse_min_scan(c->stream, c->boff.u32(), ltot + 1, c->spine.u32());
     }
     }
     HIP_TRY(hipGetLastError());
@@ -193,9 +191,8 @@ int enqueue_tail(qmcp_hip_ctx* c) {
         const uint32_t windows = plan.windows;
         if (windows != 0) {
             KernelSpan sp(c, "k_find_cuts");
-            seg = qmcp::launch_sweep_segments(c->stream, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
-                                              (const uint64_t*)c->poff.p, n_contigs, ltot, max_span, M, windows,
-                                              (uint32_t*)c->segs.p);
+            seg = qmcp::launch_sweep_segments(c->stream, c->boff.u32(), c->eoff.u32(), c->poff.u64(), n_contigs, ltot,
+                                              max_span, M, windows, c->segs.u32());
             n_seg_max = n_contigs + windows;
             // stats.sweep_stretches: the table's count (the uniform kernels count themselves)
             HIP_TRY(hipMemcpyAsync(d_iters + 2, seg, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
@@ -206,18 +203,17 @@ int enqueue_tail(qmcp_hip_ctx* c) {
             while (ring < max_span + 64) ring <<= 1;  // 64 buckets enter per chunk
             // run lengths of equal (start, end) groups: heads + reverse min-scan -> next_head[]
             TRY(ensure(c, c->next_head, ((size_t)n + 2) * sizeof(uint32_t)));
-            TRY(ensure(c, c->spine, (size_t)(qmcp::scan_spine_entries(n + 1) + 1) * sizeof(uint32_t) + 16));
+            TRY(ensure(c, c->spine, scan_spine_bytes(n + 1, 1)));
             {
                 KernelSpan sp(c, "k_group_heads");
-                qmcp::launch_group_heads(c->stream, wide, c->keys[kin].p, n, (uint32_t*)c->next_head.p);
+                qmcp::launch_group_heads(c->stream, wide, c->keys[kin].p, n, c->next_head.u32());
             }
             {
                 KernelSpan sp(c, "reverse_min_scan(3 kernels)");
-                qmcp::launch_reverse_min_scan(c->stream, (uint32_t*)c->next_head.p, n + 1,
-                                              (uint32_t*)c->spine.p);
+                qmcp::launch_reverse_min_scan(c->stream, c->next_head.u32(), n + 1, c->spine.u32());
             }
             if (plan.sample_span_mode) {
-                uint32_t* d_share = (uint32_t*)c->stats.p + 6;
+                uint32_t* d_share = c->stats.u32() + 6;
                 qmcp::launch_span_mode_share(c->stream, d_starts, d_ends, n, d_share);
                 uint32_t share[3] = {0, 0, 0};
                 HIP_TRY(hipMemcpyAsync(share, d_share, sizeof(share), hipMemcpyDeviceToHost, c->stream));
@@ -234,33 +230,31 @@ int enqueue_tail(qmcp_hip_ctx* c) {
                     c, c->stream, n_contigs, ltot, windows, max_span, plan.round_to, plan.burn_blocks, plan.run_ins_apart, seg,
                     "k_sweep_general_reg",
                     [&](const uint32_t* table, uint32_t* out_odd, const uint32_t* redo_in) {
-                        return qmcp::launch_sweep_general_reg(c->stream, wide, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
-                                                              sorted, (const uint32_t*)c->next_head.p, (const uint64_t*)c->poff.p,
-                                                              n_contigs, span_bits, max_span, M, (uint32_t*)c->selend.p, table,
-                                                              n_seg_max, out_odd, redo_in, (uint32_t*)c->specsnap.p);
+                        return qmcp::launch_sweep_general_reg(c->stream, wide, c->boff.u32(), c->eoff.u32(),
+                                                              sorted, c->next_head.u32(), c->poff.u64(),
+                                                              n_contigs, span_bits, max_span, M, c->selend.u32(), table,
+                                                              n_seg_max, out_odd, redo_in, c->specsnap.u32());
                     },
                     [&](const uint32_t* table, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
-                        qmcp::launch_spec_verify_merge_mixed(c->stream, table, n_seg_max, max_span, (uint32_t*)c->selend.p,
-                                                             (const uint32_t*)c->cstart.p, (const uint32_t*)c->specsnap.p,
+                        qmcp::launch_spec_verify_merge_mixed(c->stream, table, n_seg_max, max_span, c->selend.u32(),
+                                                             c->cstart.u32(), c->specsnap.u32(),
                                                              mismatches, redo_in, redo_out);
                     }));
                 // stats.sweep_stretches: the first tier's table
-                HIP_TRY(hipMemcpyAsync(d_iters + 2, (uint32_t*)c->segs.p + windows + (1 + 5 * (size_t)n_seg_max), sizeof(uint32_t),
+                HIP_TRY(hipMemcpyAsync(d_iters + 2, c->segs.u32() + windows + (1 + 5 * (size_t)n_seg_max), sizeof(uint32_t),
                                        hipMemcpyDeviceToDevice, c->stream));
             }
             if (!speculate) {  // (else: swept above)
                 KernelSpan sp(c, in_regs ? "k_sweep_general_reg" : "k_sweep_general_cached");
                 if (!in_regs ||
-                    !qmcp::launch_sweep_general_reg(c->stream, wide, (const uint32_t*)c->boff.p,
-                                                    (const uint32_t*)c->eoff.p, c->keys[kin].p,
-                                                    (const uint32_t*)c->next_head.p, (const uint64_t*)c->poff.p,
-                                                    n_contigs, span_bits, max_span, M, (uint32_t*)c->selend.p, seg,
+                    !qmcp::launch_sweep_general_reg(c->stream, wide, c->boff.u32(),
+                                                    c->eoff.u32(), c->keys[kin].p,
+                                                    c->next_head.u32(), c->poff.u64(),
+                                                    n_contigs, span_bits, max_span, M, c->selend.u32(), seg,
                                                     n_seg_max))
-                    qmcp::launch_sweep_general_cached(c->stream, wide, (const uint32_t*)c->boff.p,
-                                                      (const uint32_t*)c->eoff.p, c->keys[kin].p,
-                                                      (const uint32_t*)c->next_head.p, (const uint64_t*)c->poff.p,
-                                                      n_contigs, span_bits, max_span, M,
-                                                      (uint32_t*)c->selend.p, ring, seg, n_seg_max);
+                    qmcp::launch_sweep_general_cached(c->stream, wide, c->boff.u32(), c->eoff.u32(), c->keys[kin].p,
+                                                      c->next_head.u32(), c->poff.u64(), n_contigs, span_bits, max_span,
+                                                      M, c->selend.u32(), ring, seg, n_seg_max);
             }
         } else {
             uint32_t* g_rings = nullptr;
@@ -268,13 +262,12 @@ int enqueue_tail(qmcp_hip_ctx* c) {
                 // long reads: the two rings of a workgroup no longer fit LDS
                 const size_t n_wg = seg ? n_seg_max : n_contigs;
                 TRY(ensure(c, c->rings, n_wg * 2 * (size_t)ring * sizeof(uint32_t)));
-                g_rings = (uint32_t*)c->rings.p;
+                g_rings = c->rings.u32();
             }
             KernelSpan sp(c, "k_sweep_general");
-            qmcp::launch_sweep_general(c->stream, wide, (const uint32_t*)c->boff.p,
-                                       (const uint32_t*)c->eoff.p, c->keys[kin].p,
-                                       (const uint64_t*)c->poff.p, n_contigs, span_bits, max_span, M,
-                                       (uint32_t*)c->selend.p, ring, seg, n_seg_max, g_rings);
+            qmcp::launch_sweep_general(c->stream, wide, c->boff.u32(), c->eoff.u32(), c->keys[kin].p, c->poff.u64(),
+                                       n_contigs, span_bits, max_span, M, c->selend.u32(), ring, seg, n_seg_max,
+                                       g_rings);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -283,9 +276,8 @@ int enqueue_tail(qmcp_hip_ctx* c) {
     // keep mask
     if (!ranked) {
         KernelSpan sp(c, "k_mark");
-        qmcp::launch_mark(c->stream, wide, c->keys[kin].p, (const uint32_t*)c->vals[vin].p, ltot,
-                          (const uint32_t*)c->boff.p, (const uint32_t*)c->selend.p, d_mask,
-                          (unsigned long long*)c->scalars.p);
+        qmcp::launch_mark(c->stream, wide, c->keys[kin].p, c->vals[vin].u32(), ltot, c->boff.u32(), c->selend.u32(),
+                          d_mask, c->scalars.as<unsigned long long>());
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_MARK], c->stream));
@@ -293,7 +285,7 @@ int enqueue_tail(qmcp_hip_ctx* c) {
                            c->stream));
     c->pend_spiky = ranked_counted;
     if (ranked_counted) {
-        HIP_TRY(hipMemcpyAsync(c->h_scalars + 7, (uint32_t*)c->stats.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_scalars + 7, c->stats.u32() + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         c->spiky_n = n64;
         c->spiky_ltot = pr.ltot;
     }
@@ -320,7 +312,7 @@ int collect_one(qmcp_hip_ctx* c, qmcp_hip_stats* st) {
             c->nu_need_rounds = 0;
             const SolveRun r = c->run;
             const size_t count = (size_t)r.n_contigs + 1;
-            std::vector<uint64_t> roff(c->h_tables, c->h_tables + count);
+            std::vector<uint64_t> roff(c->h_tables.p, c->h_tables.p + count);
             std::vector<uint32_t> lengths(r.n_contigs);
             for (uint32_t k = 0; k < r.n_contigs; ++k) lengths[k] = (uint32_t)(c->h_tables[count + k + 1] - c->h_tables[count + k]);
             TRY(solve_enqueue(c, r.d_starts, r.d_ends, roff.data(), lengths.data(), r.n_contigs, r.n64, r.M, r.d_mask));
@@ -415,27 +407,27 @@ int create_ctx(int device, qmcp_hip_ctx** out_ctx) {
     c->device = device;
     qmcp_hip_default_options(&c->opt);
     options_from_env(c->opt);
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    for (int i = 0; e == hipSuccess && i < EV_COUNT; ++i) e = hipEventCreate(&c->ev[i]);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming);
+    hipError_t e = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
+    for (int i = 0; e == hipSuccess && i < EV_COUNT; ++i) e = hipEventCreate(&c->ev[i].h);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_in.h, hipEventDisableTiming);
     if (e == hipSuccess) {
         int lo = 0, hi = 0;  // numerically lower == higher priority
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        e = hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, hi);
+        e = hipStreamCreateWithPriority(&c->stream2.h, hipStreamNonBlocking, hi);
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_head, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_head, 16 * sizeof(uint32_t), hipHostMallocDefault);
-    if (e == hipSuccess) {
-        c->h_stats_init = c->h_head + 8;
-        c->h_stats_init[0] = 0xFFFFFFFFu;
-        for (int i = 1; i < 8; ++i) c->h_stats_init[i] = 0u;
-    }
-    if (e != hipSuccess) {
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork.h, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_head.h, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done.h, hipEventDisableTiming);
+    // (a half-built context is deleted like a whole one: what was not created is null and is skipped)
+    int rc = e == hipSuccess ? ensure_pinned(c, c->h_head, 16 * sizeof(uint32_t))
+                             : fail(QMCP_EHIP, "context setup: %s", hipGetErrorString(e));
+    if (rc != QMCP_OK) {
         qmcp_hip_destroy(c);
-        return fail(QMCP_EHIP, "context setup: %s", hipGetErrorString(e));
+        return rc;
     }
+    c->h_stats_init = c->h_head + 8;
+    c->h_stats_init[0] = 0xFFFFFFFFu;
+    for (int i = 1; i < 8; ++i) c->h_stats_init[i] = 0u;
     *out_ctx = c;
     return QMCP_OK;
 }

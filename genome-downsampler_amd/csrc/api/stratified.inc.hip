@@ -49,8 +49,8 @@ int solve_stratified_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
          "k_bc_bounds(stratified)"},
         [&] {
             KernelSpan sp(c, "k_st_keys");
-            qmcp::launch_st_keys(st, d_starts, d_ends, d_ids, d_strata, n, (const uint32_t*)c->bc_len.p, n_contigs, n_strata,
-                                 (uint32_t*)c->bc_key.p, (uint32_t*)c->bc_err.p);
+            qmcp::launch_st_keys(st, d_starts, d_ends, d_ids, d_strata, n, c->bc_len.u32(), n_contigs, n_strata,
+                                 c->bc_key.u32(), c->bc_err.u32());
         },
         d_mask, offs, &sorted, &err));
     if (err & 1u) return fail(QMCP_EINVAL, "a contig id is neither < n_contigs (%u) nor QMCP_NO_CONTIG", n_contigs);
@@ -94,7 +94,7 @@ int solve_stratified_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
         HIP_TRY(hipMemsetAsync(c->st_rows.p, 0, (size_t)n_strata * sizeof(qmcp_hip_stratum_row), st));
         {
             KernelSpan sp(c, "k_st_tally");
-            qmcp::launch_st_tally(st, sorted, n_placed, n_contigs, d_starts, d_ends, d_mask, (uint64_t*)c->st_rows.p);
+            qmcp::launch_st_tally(st, sorted, n_placed, n_contigs, d_starts, d_ends, d_mask, c->st_rows.u64());
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(rows_out, c->st_rows.p, (size_t)n_strata * sizeof(qmcp_hip_stratum_row),
@@ -134,10 +134,9 @@ int qmcp_hip_solve_stratified_host(qmcp_hip_ctx* c, const uint32_t* starts, cons
     }
     // the rows land in a buffer of the call's own: a failure leaves rows_out as it was
     std::vector<qmcp_hip_stratum_row> rows(rows_out ? n_strata : 0);
-    TRY(solve_stratified_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                   (const uint32_t*)c->in_aux0.p, (const uint32_t*)c->st_strata.p, n_reads,
-                                   contig_lengths, n_contigs, max_coverages, n_strata, (uint64_t*)c->mask.p,
-                                   rows_out ? rows.data() : nullptr, stats));
+    TRY(solve_stratified_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), c->st_strata.u32(),
+        n_reads, contig_lengths, n_contigs, max_coverages, n_strata, c->mask.u64(), rows_out ? rows.data() : nullptr,
+        stats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (rows_out) std::memcpy(rows_out, rows.data(), rows.size() * sizeof(qmcp_hip_stratum_row));

@@ -48,12 +48,12 @@ int solve_targets_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     TRY(ensure(c, c->tg_off, words * 8 + 16));
     TRY(ensure(c, c->f_words, (words + 2) * 4));
     TRY(ensure(c, c->tg_offw, (words + 2) * 4));
-    TRY(ensure(c, c->spine, (size_t)(qmcp::scan_spine_entries((uint32_t)words + 1) + 1) * 4 + 16));
+    TRY(ensure(c, c->spine, scan_spine_bytes((uint32_t)words + 1, 1)));
     TRY(ensure(c, c->af_err, 16));
     // the table: lengths | offs | remap | rs | re | cum
     const size_t tab_words = 3 * (size_t)n_contigs + 1 + 3 * (size_t)n_reg;
     TRY(ensure(c, c->tg_tab, tab_words * 4));
-    uint32_t* d_len = (uint32_t*)c->tg_tab.p;
+    uint32_t* d_len = c->tg_tab.u32();
     uint32_t* d_offs = d_len + n_contigs;
     uint32_t* d_remap = d_offs + n_contigs + 1;
     uint32_t* d_rs = d_remap + n_contigs;
@@ -77,23 +77,18 @@ int solve_targets_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     {
         KernelSpan sp(c, "k_target_project");
         qmcp::launch_target_project(st, d_starts, d_ends, d_ids, n, d_len, n_contigs, d_offs, d_rs, d_re, d_cum, n_reg,
-                                    (uint32_t*)c->tg_ps.p, (uint32_t*)c->tg_pe.p, (uint64_t*)c->f_mask.p,
-                                    (uint64_t*)c->tg_off.p, (uint32_t*)c->af_err.p);
+                                    c->tg_ps.u32(), c->tg_pe.u32(), c->f_mask.u64(), c->tg_off.u64(), c->af_err.u32());
     }
     {
         KernelSpan sp(c, "count targets(2 x popcounts, scan)");
-        qmcp::launch_word_popcounts(st, (const uint64_t*)c->f_mask.p, (uint32_t)words, (uint32_t*)c->f_words.p);
-        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->f_words.p, (uint32_t)words, (uint32_t*)c->f_words.p,
-                                    (uint32_t*)c->spine.p, true);
-        qmcp::launch_word_popcounts(st, (const uint64_t*)c->tg_off.p, (uint32_t)words, (uint32_t*)c->tg_offw.p);
-        qmcp::launch_exclusive_scan(st, (const uint32_t*)c->tg_offw.p, (uint32_t)words, (uint32_t*)c->tg_offw.p,
-                                    (uint32_t*)c->spine.p, true);
+        queue_mask_ranks(st, c->f_mask.u64(), (uint32_t)words, c->f_words, c->spine);
+        queue_mask_ranks(st, c->tg_off.u64(), (uint32_t)words, c->tg_offw, c->spine);
     }
     HIP_TRY(hipEventRecord(ev_a.b, st));
     HIP_TRY(hipGetLastError());
     uint32_t err = 0, n_on = 0, n_off = 0;
-    HIP_TRY(hipMemcpyAsync(&n_on, (uint32_t*)c->f_words.p + words, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&n_off, (uint32_t*)c->tg_offw.p + words, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_on, c->f_words.u32() + words, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_off, c->tg_offw.u32() + words, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&err, c->af_err.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     collect_spans(c);
@@ -115,33 +110,32 @@ int solve_targets_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
         HIP_TRY(hipEventRecord(ev_b.a, st));
         {
             KernelSpan sp(c, "k_compact_reads");
-            qmcp::launch_compact_reads(st, (const uint32_t*)c->tg_ps.p, (const uint32_t*)c->tg_pe.p, d_ids, d_q, d_remap,
-                                       (const uint64_t*)c->f_mask.p, (const uint32_t*)c->f_words.p, n,
-                                       (uint32_t*)c->f_starts.p, (uint32_t*)c->f_ends.p, (uint32_t*)c->af_ids_c.p,
-                                       d_q ? (uint32_t*)c->tg_q.p : nullptr, (uint32_t*)c->f_map.p);
+            qmcp::launch_compact_reads(st, c->tg_ps.u32(), c->tg_pe.u32(), d_ids, d_q, d_remap, c->f_mask.u64(),
+                                       c->f_words.u32(), n, c->f_starts.u32(), c->f_ends.u32(), c->af_ids_c.u32(),
+                                       d_q ? c->tg_q.u32() : nullptr, c->f_map.u32());
         }
         HIP_TRY(hipEventRecord(ev_b.b, st));
         HIP_TRY(hipGetLastError());
         // 4. the projected problem
-        const uint32_t* cs = (const uint32_t*)c->f_starts.p;
-        const uint32_t* ce = (const uint32_t*)c->f_ends.p;
-        const uint32_t* cid = (const uint32_t*)c->af_ids_c.p;
-        uint64_t* d_mask_c = (uint64_t*)c->cov.p;
+        const uint32_t* cs = c->f_starts.u32();
+        const uint32_t* ce = c->f_ends.u32();
+        const uint32_t* cid = c->af_ids_c.u32();
+        uint64_t* d_mask_c = c->cov.u64();
         const uint32_t n_tc = (uint32_t)tlen.size();
         QualityRange qr;
-        if (d_q) TRY(quality_range(c, (const uint32_t*)c->tg_q.p, cid, n_on, qr));
+        if (d_q) TRY(quality_range(c, c->tg_q.u32(), cid, n_on, qr));
         qmcp_hip_stats plain;
         std::memset(&plain, 0, sizeof(plain));
         TRY(solve_by_contig_on_device(c, cs, ce, cid, n_on, tlen.data(), n_tc, M, d_mask_c, &plain));
         if (d_q)
-            TRY(quality_pass(c, cs, ce, (const uint32_t*)c->tg_q.p, cid, n_on, nullptr, tlen.data(), n_tc, qr, plain,
+            TRY(quality_pass(c, cs, ce, c->tg_q.u32(), cid, n_on, nullptr, tlen.data(), n_tc, qr, plain,
                              d_mask_c, nullptr));
         if (stats) *stats = plain;
         // 5. back to input order
         HIP_TRY(hipEventRecord(ev_c.a, st));
         {
             KernelSpan sp(c, "k_expand_mask_reads");
-            qmcp::launch_expand_mask_reads(st, d_mask_c, (const uint32_t*)c->f_map.p, n_on, d_mask);
+            qmcp::launch_expand_mask_reads(st, d_mask_c, c->f_map.u32(), n_on, d_mask);
         }
     } else {
         HIP_TRY(hipEventRecord(ev_b.a, st));
@@ -150,7 +144,7 @@ int solve_targets_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uin
     }
     if ((flags & QMCP_TARGETS_KEEP_OFF_TARGET) && n_off) {
         KernelSpan sp(c, "k_or_words(off-target reads)");
-        qmcp::launch_or_words(st, d_mask, (const uint64_t*)c->tg_off.p, (uint32_t)words);
+        qmcp::launch_or_words(st, d_mask, c->tg_off.u64(), (uint32_t)words);
     }
     HIP_TRY(hipEventRecord(ev_c.b, st));
     HIP_TRY(hipGetLastError());
@@ -208,9 +202,9 @@ int qmcp_hip_solve_targets_host(qmcp_hip_ctx* c, const uint32_t* starts, const u
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
         if (qualities) HIP_TRY(hipMemcpyAsync(c->in_aux1.p, qualities, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_targets_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                (const uint32_t*)c->in_aux0.p, qualities ? (const uint32_t*)c->in_aux1.p : nullptr, n_reads,
-                                contig_lengths, n_contigs, tab, max_coverage, flags, (uint64_t*)c->mask.p, stats, tstats));
+    TRY(solve_targets_on_device(c, c->in_starts.u32(), c->in_ends.u32(),
+                                c->in_aux0.u32(), qualities ? c->in_aux1.u32() : nullptr, n_reads,
+                                contig_lengths, n_contigs, tab, max_coverage, flags, c->mask.u64(), stats, tstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

@@ -22,13 +22,13 @@ struct TemplateCompletion : UnitCompletion {
     TemplateCompletion(const uint32_t* ids, uint32_t nt) : d_tids(ids), n_templates(nt) {}
     int complete_and_count(qmcp_hip_ctx* c, uint64_t* d_mask, uint64_t n64) override {
         hipStream_t st = c->stream;
-        unsigned long long* d_count = (unsigned long long*)c->pr_stat.p + 2;
+        unsigned long long* d_count = c->pr_stat.as<unsigned long long>() + 2;
         HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
         HIP_TRY(hipMemsetAsync(c->tp_flags.p, 0, tpl_flag_bytes(n_templates), st));
         if (n64) {
             KernelSpan sp(c, "k_tpl_mark + k_tpl_spread");
-            qmcp::launch_tpl_mark(st, d_mask, d_tids, (uint32_t)n64, n_templates, (uint32_t*)c->tp_flags.p);
-            qmcp::launch_tpl_spread(st, d_tids, (uint32_t)n64, n_templates, (const uint32_t*)c->tp_flags.p, d_mask, d_count);
+            qmcp::launch_tpl_mark(st, d_mask, d_tids, (uint32_t)n64, n_templates, c->tp_flags.u32());
+            qmcp::launch_tpl_spread(st, d_tids, (uint32_t)n64, n_templates, c->tp_flags.u32(), d_mask, d_count);
         }
         HIP_TRY(hipGetLastError());
         return QMCP_OK;
@@ -81,7 +81,7 @@ int solve_templates_staged(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     TRY(ensure(c, c->tp_stat, kTplStatWords * sizeof(unsigned long long)));
     TRY(ensure(c, c->tp_flags, tpl_flag_bytes(n_templates)));
     TRY(ensure(c, c->tp_sizes, (size_t)n_templates * sizeof(uint32_t)));
-    unsigned long long* d_tstat = (unsigned long long*)c->tp_stat.p;
+    unsigned long long* d_tstat = c->tp_stat.as<unsigned long long>();
     unsigned long long h_tstat[kTplStatWords] = {0};
     HIP_TRY(hipEventRecord(ev.a, st));
     if (words) HIP_TRY(hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), st));
@@ -89,7 +89,7 @@ int solve_templates_staged(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
     if (n) {
         HIP_TRY(hipMemsetAsync(c->tp_sizes.p, 0, (size_t)n_templates * sizeof(uint32_t), st));
         KernelSpan sp(c, "k_tpl_check + k_tpl_sizes + k_tpl_size_hist");
-        qmcp::launch_tpl_check_sizes(st, d_tids, n, n_templates, (uint32_t*)(d_tstat + kTplErr), (uint32_t*)c->tp_sizes.p,
+        qmcp::launch_tpl_check_sizes(st, d_tids, n, n_templates, (uint32_t*)(d_tstat + kTplErr), c->tp_sizes.u32(),
                                      d_tstat);
     }
     HIP_TRY(hipGetLastError());
@@ -118,7 +118,7 @@ int solve_templates_staged(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint
 
     // 3: the templates the last completion flagged
     HIP_TRY(hipEventRecord(ev.a, st));
-    qmcp::launch_pair_count_bits(st, (const uint64_t*)c->tp_flags.p, (uint32_t)(tpl_flag_bytes(n_templates) / sizeof(uint64_t)),
+    qmcp::launch_pair_count_bits(st, c->tp_flags.u64(), (uint32_t)(tpl_flag_bytes(n_templates) / sizeof(uint64_t)),
                                  d_tstat + kTplKept);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_tstat, d_tstat + kTplKept, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -171,9 +171,8 @@ int qmcp_hip_solve_templates_host(qmcp_hip_ctx* c, const uint32_t* starts, const
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->tp_ids.p, template_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_templates_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                  (const uint32_t*)c->in_aux0.p, (const uint32_t*)c->tp_ids.p, n_reads, n_templates,
-                                  contig_lengths, n_contigs, targets, (uint64_t*)c->mask.p, stats, tstats));
+    TRY(solve_templates_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), c->tp_ids.u32(), n_reads,
+        n_templates, contig_lengths, n_contigs, targets, c->mask.u64(), stats, tstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

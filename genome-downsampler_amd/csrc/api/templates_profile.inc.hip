@@ -23,7 +23,7 @@ struct TemplateProfileNeed : StageNeed {
     int upload(qmcp_hip_ctx* c, hipStream_t st) override {
         TRY(StageNeed::upload(c, st));
         const size_t n_reg = gs.size();
-        uint32_t* d_rs = (uint32_t*)c->tq_tab.p;
+        uint32_t* d_rs = c->tq_tab.u32();
         if (n_reg) {
             HIP_TRY(hipMemcpyAsync(d_rs, gs.data(), n_reg * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(d_rs + n_reg, ge.data(), n_reg * 4, hipMemcpyHostToDevice, st));
@@ -33,10 +33,10 @@ struct TemplateProfileNeed : StageNeed {
     }
     void launch(qmcp_hip_ctx* c, hipStream_t st, uint32_t ltot, uint32_t* need) override {
         const size_t n_reg = gs.size();
-        const uint32_t* d_rs = (const uint32_t*)c->tq_tab.p;
-        qmcp::launch_tpl_profile_need(st, (const uint32_t*)c->boff.p, (const uint32_t*)c->eoff.p,
-                                      (const uint32_t*)c->pr_credit.p + qmcp::pair_credit_pad(), ltot, d_rs, d_rs + n_reg,
-                                      d_rs + 2 * n_reg, (uint32_t)n_reg, default_cap, need, (unsigned long long*)c->pr_stat.p);
+        const uint32_t* d_rs = c->tq_tab.u32();
+        qmcp::launch_tpl_profile_need(st, c->boff.u32(), c->eoff.u32(),
+                                      c->pr_credit.u32() + qmcp::pair_credit_pad(), ltot, d_rs, d_rs + n_reg,
+                                      d_rs + 2 * n_reg, (uint32_t)n_reg, default_cap, need, c->pr_stat.as<unsigned long long>());
     }
 };
 
@@ -93,9 +93,9 @@ int count_on_cap(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     TRY(ensure(c, c->tq_cap, (n_offs + 4 * n_reg) * sizeof(uint32_t) + 16));
     TRY(ensure(c, c->tq_flags, flag_bytes));
     TRY(ensure(c, c->tq_stat, 2 * sizeof(unsigned long long)));
-    uint32_t* d_offs = (uint32_t*)c->tq_cap.p;
+    uint32_t* d_offs = c->tq_cap.u32();
     uint32_t* d_rs = d_offs + n_offs;
-    unsigned long long* d_stat = (unsigned long long*)c->tq_stat.p;
+    unsigned long long* d_stat = c->tq_stat.as<unsigned long long>();
     unsigned long long h_stat[2] = {0, 0};
     HIP_TRY(hipEventRecord(ev.a, st));
     HIP_TRY(hipMemsetAsync(d_stat, 0, sizeof(h_stat), st));
@@ -110,8 +110,8 @@ int count_on_cap(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint32_t* d_en
     if (n) {
         KernelSpan sp(c, "k_tpl_on_cap + k_pair_count_bits");
         qmcp::launch_tpl_on_cap(st, d_starts, d_ends, d_ids, d_tids, n, n_contigs, n_templates, d_offs, d_rs, d_rs + n_reg,
-                                d_rs + 2 * n_reg, d_rs + 3 * n_reg, default_cap != 0, (uint32_t*)c->tq_flags.p, d_stat);
-        qmcp::launch_pair_count_bits(st, (const uint64_t*)c->tq_flags.p, (uint32_t)(flag_bytes / sizeof(uint64_t)), d_stat + 1);
+                                d_rs + 2 * n_reg, d_rs + 3 * n_reg, default_cap != 0, c->tq_flags.u32(), d_stat);
+        qmcp::launch_pair_count_bits(st, c->tq_flags.u64(), (uint32_t)(flag_bytes / sizeof(uint64_t)), d_stat + 1);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_stat, d_stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
@@ -201,10 +201,9 @@ int qmcp_hip_solve_templates_profile_host(qmcp_hip_ctx* c, const uint32_t* start
         HIP_TRY(hipMemcpyAsync(c->in_aux0.p, contig_ids, nb, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(c->tp_ids.p, template_ids, nb, hipMemcpyHostToDevice, c->stream));
     }
-    TRY(solve_templates_profile_on_device(c, (const uint32_t*)c->in_starts.p, (const uint32_t*)c->in_ends.p,
-                                          (const uint32_t*)c->in_aux0.p, (const uint32_t*)c->tp_ids.p, n_reads, n_templates,
-                                          contig_lengths, n_contigs, max_coverage, targets, tab, default_cap,
-                                          (uint64_t*)c->mask.p, stats, tstats, qstats));
+    TRY(solve_templates_profile_on_device(c, c->in_starts.u32(), c->in_ends.u32(), c->in_aux0.u32(), c->tp_ids.u32(),
+        n_reads, n_templates, contig_lengths, n_contigs, max_coverage, targets, tab, default_cap, c->mask.u64(), stats,
+        tstats, qstats));
     if (words) HIP_TRY(hipMemcpyAsync(keep_mask_out, c->mask.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mask_reads = n_reads;

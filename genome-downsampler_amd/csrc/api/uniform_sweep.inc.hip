@@ -10,7 +10,7 @@ struct SpecWords {
     uint32_t* n_spec2;
 };
 SpecWords spec_words(qmcp_hip_ctx* c) {
-    uint32_t* w = (uint32_t*)((char*)c->scalars.p + 32);
+    uint32_t* w = (uint32_t*)(c->scalars.as<char>() + 32);
     return SpecWords{w, w + 1, w + 2, w + 3};
 }
 
@@ -26,10 +26,10 @@ int speculative_sweep(qmcp_hip_ctx* c, hipStream_t st, uint32_t n_contigs, uint3
                       const uint32_t* only_marked = nullptr /* per exact stretch: the parts of the genome to sweep at all
                                                                (the near-uniform route's later rounds); null: everything */) {
     const SpecWords w = spec_words(c);
-    const uint64_t* poff = (const uint64_t*)c->poff.p;
+    const uint64_t* poff = c->poff.u64();
     const uint32_t n_cand = n_contigs + windows;
     TRY(ensure(c, c->specflags, 2 * (size_t)n_cand * sizeof(uint32_t)));
-    uint32_t* redo1 = (uint32_t*)c->specflags.p;
+    uint32_t* redo1 = c->specflags.u32();
     uint32_t* redo2 = redo1 + n_cand;
     HIP_TRY(hipMemsetAsync(redo1, 0, 2 * (size_t)n_cand * sizeof(uint32_t), st));
     auto positions = [&](uint64_t blocks) { return (uint32_t)((blocks * unit + round_to - 1) / round_to * round_to); };
@@ -39,13 +39,13 @@ int speculative_sweep(qmcp_hip_ctx* c, hipStream_t st, uint32_t n_contigs, uint3
     const uint32_t *seg1, *seg2;
     {
         KernelSpan sp(c, "k_find_cuts", st);
-        seg1 = qmcp::launch_sweep_segments_speculative(st, poff, n_contigs, ltot, windows, burn1, (uint32_t*)c->segs.p,
+        seg1 = qmcp::launch_sweep_segments_speculative(st, poff, n_contigs, ltot, windows, burn1, c->segs.u32(),
                                                        w.n_spec1, run_ins_apart, 1);
-        seg2 = qmcp::launch_sweep_segments_speculative(st, poff, n_contigs, ltot, windows, burn2, (uint32_t*)c->segs.p,
+        seg2 = qmcp::launch_sweep_segments_speculative(st, poff, n_contigs, ltot, windows, burn2, c->segs.u32(),
                                                        w.n_spec2, run_ins_apart, 2);
     }
     // the second output: one span -- every stretch's run-in; a mix of spans -- the odd stretches' whole output
-    uint32_t* second_out = (uint32_t*)c->cstart.p;
+    uint32_t* second_out = c->cstart.u32();
     {
         KernelSpan sp(c, sweep_name, st);
         if (!sweep(seg1, second_out, only_marked)) return fail(QMCP_ERANGE, "speculative sweep: span not supported");
@@ -71,14 +71,14 @@ int launch_uniform_sweep(qmcp_hip_ctx* c, hipStream_t st, uint32_t n, uint32_t l
     const bool may_leave_expand = expand_left_out != nullptr && *expand_left_out;
     if (expand_left_out) *expand_left_out = false;
     const qmcp::UniformSweepPlan plan = qmcp::plan_uniform_sweep(c->opt, n, span, ltot, n_contigs, M, empty_positions);
-    const uint32_t* boff = (const uint32_t*)c->boff.p;
-    const uint64_t* poff = (const uint64_t*)c->poff.p;
-    uint32_t* selend = (uint32_t*)c->selend.p;
+    const uint32_t* boff = c->boff.u32();
+    const uint64_t* poff = c->poff.u64();
+    uint32_t* selend = c->selend.u32();
     const uint32_t* seg = nullptr;
     uint32_t n_seg_max = 0;
     if (plan.windows != 0) {
         KernelSpan sp(c, "k_find_cuts", st);
-        seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, span, M, plan.windows, (uint32_t*)c->segs.p);
+        seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, span, M, plan.windows, c->segs.u32());
         n_seg_max = n_contigs + plan.windows;
     }
     switch (plan.form) {
@@ -90,9 +90,9 @@ int launch_uniform_sweep(qmcp_hip_ctx* c, hipStream_t st, uint32_t n, uint32_t l
             TRY(ensure(c, c->evpk, qmcp::sweep_ev_pack_bytes(ltot, span, wg_max)));
             TRY(ensure(c, c->evlast, qmcp::sweep_ev_last_bytes(ltot, span, wg_max)));
         }
-        uint32_t* pk = (uint32_t*)c->evpk.p;
-        uint32_t* sev = (uint32_t*)c->cstart.p;
-        uint32_t* lastns = (uint32_t*)c->evlast.p;
+        uint32_t* pk = c->evpk.u32();
+        uint32_t* sev = c->cstart.u32();
+        uint32_t* lastns = c->evlast.u32();
         {
             KernelSpan sp(c, "k_sweep_pack", st);
             qmcp::launch_sweep_ev_pack(st, boff, poff, n_contigs, span, M, ltot, seg, n_seg_max, pk);
@@ -118,7 +118,7 @@ int launch_uniform_sweep(qmcp_hip_ctx* c, hipStream_t st, uint32_t n, uint32_t l
                                                       run_in_out, redo_in);
             },
             [&](const uint32_t* table, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
-                qmcp::launch_spec_verify(st, table, n_seg_max, span, selend, (const uint32_t*)c->cstart.p, mismatches,
+                qmcp::launch_spec_verify(st, table, n_seg_max, span, selend, c->cstart.u32(), mismatches,
                                          redo_in, redo_out);
             });
     case qmcp::UniformForm::General:

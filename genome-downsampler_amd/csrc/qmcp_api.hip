@@ -39,7 +39,9 @@
 
 // One translation unit, kept in parts under api/ (included below, in dependency order: a part uses only parts above it,
 // those a by-contig feature builds on are named in brackets):
-//   context             the solver context, its device arena, timing spans, problem checks, small stage helpers
+//   context             the solver context and the types that own its device arena, pinned blocks, events and streams
+//                       (deleting the context frees them all), ensure / ensure_pinned, typed buffer access, the event
+//                       pool and timing spans, problem checks, small stage helpers (the rank of a mask's bits)
 //   radix_passes        the stable LSD radix sort's passes (records form, wide u64 form): the one loop every sorting entry queues
 //   uniform_sweep       which one-length sweep a call takes and its launches (pipelines, event-driven form, stretches,
 //                       speculative tiers)
