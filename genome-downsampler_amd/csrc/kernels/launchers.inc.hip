@@ -17,11 +17,11 @@ void launch_prepare(hipStream_t st, const uint32_t* starts, const uint32_t* ends
                     const uint64_t* keep_mask, uint32_t* gstart, uint32_t* cstart,
                     uint32_t* stats, uint32_t part_shift, uint32_t* part_hist,
                     uint32_t* digit0_hist, uint32_t* global_digit_hist, unsigned long long* zero_mask,
-                    uint32_t ell_reg, uint32_t* exc, uint32_t exc_cap, uint32_t* exc_cnt) {
+                    uint32_t ell_reg, uint32_t* exc, uint32_t exc_cap, uint32_t* exc_cnt, uint32_t tiles_per_block) {
     const uint32_t n_tiles = sort_tiles(n);
     if (n_tiles == 0) return;
     if (exc == nullptr) ell_reg = 0;
-    uint32_t g = tiles_per_block_for(n_tiles);
+    uint32_t g = tiles_per_block != 0u ? (tiles_per_block > 8u ? 8u : tiles_per_block) : tiles_per_block_for(n_tiles);
     // the partition table has one entry per pass (a pair of tiles) and rows padded to part_pass_pitch(n):
     // a workgroup takes whole passes, and the workgroups cover the padding too (empty tiles: zero counts)
     if (part_hist) g = (g + 1u) & ~1u;

@@ -27,7 +27,9 @@ void launch_prepare(hipStream_t st, const uint32_t* starts, const uint32_t* ends
                     uint32_t* global_digit_hist /* [4][256] whole-call digit counts of gstart, or null */,
                     unsigned long long* zero_mask /* keep mask to clear (ceil(n/64) words), or null */,
                     uint32_t ell_reg = 0, uint32_t* exc = nullptr, uint32_t exc_cap = 0, uint32_t* exc_cnt = nullptr
-                    /* near-uniform route on the range-major form: see k_prepare */);
+                    /* near-uniform route on the range-major form: see k_prepare */,
+                    uint32_t tiles_per_block = 0 /* tiles a workgroup takes (at most 8; even with part_hist); 0: chosen by the
+                                                    tile count (the stage tests run the wider forms on a few tiles) */);
 uint32_t prepare_exc_slots(uint32_t n);  // slots of the exception list when k_prepare fills it (groups of 128 per wave and tile)
 void launch_general_keys(hipStream_t st, bool wide, const uint32_t* gstart, const uint32_t* starts,
                          const uint32_t* ends, uint32_t n, uint32_t span_bits, uint32_t max_span,

@@ -60,8 +60,9 @@ def quota_vectors(gs_regular, ltot, seed):
     return [np.asarray(v, np.int64).astype(np.uint32) for v in vectors]
 
 
-def write_case(case, directory):
-    """-> paths of case.json, case.bin"""
+def write_case(case, directory, more=None, write_quota=None):
+    """-> paths of case.json, case.bin.  more: further flat fields of case.json; write_quota(file, vector): how a driver
+    takes a quota vector (default: one u32 per global position)"""
     jpath, bpath = os.path.join(str(directory), "case.json"), os.path.join(str(directory), "case.bin")
     with open(bpath, "wb") as f:
         f.write(case["starts"].astype("<u4").tobytes())
@@ -69,11 +70,16 @@ def write_case(case, directory):
         f.write(case["lengths"].astype("<u8").tobytes())
         f.write(case["roff"].astype("<u8").tobytes())
         for q in case["quotas"]:
-            f.write(q.astype("<u4").tobytes())
+            if write_quota is None:
+                f.write(q.astype("<u4").tobytes())
+            else:
+                write_quota(f, q)
     with open(jpath, "w") as f:
-        json.dump({"n": int(case["starts"].size), "n_contigs": int(case["lengths"].size), "ltot": int(case["ltot"]),
-                   "wish": case["wish"], "ell_reg": case["ell_reg"], "stop_after": case["stop_after"],
-                   "n_quota": len(case["quotas"])}, f)
+        fields = {"n": int(case["starts"].size), "n_contigs": int(case["lengths"].size), "ltot": int(case["ltot"]),
+                  "wish": case["wish"], "ell_reg": case["ell_reg"], "stop_after": case["stop_after"],
+                  "n_quota": len(case["quotas"])}
+        fields.update(more or {})
+        json.dump(fields, f)
     return jpath, bpath
 
 
