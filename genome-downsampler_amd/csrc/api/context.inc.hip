@@ -75,6 +75,36 @@ struct Problem {
     std::vector<uint64_t> poff;
 };
 
+// A call's shape: what a context's memories of earlier calls are keyed by.  A memory that does not depend on a field
+// leaves it 0 on both sides; n == 0 is no call's shape (such a call is trivial), so Shape() matches nothing.
+struct Shape {
+    uint64_t n = 0, ltot = 0;
+    uint32_t M = 0, ell = 0;  // ell: the dominant span (near-uniform route)
+    bool operator==(const Shape& o) const { return n == o.n && ltot == o.ltot && M == o.M && ell == o.ell; }
+};
+// "A call of this shape did X last time": what a context remembers about earlier calls.
+struct Memories {
+    // {n, ltot}: positions that start no read, as counted by the last range-ranked solve (picks the sweep kernel of the next)
+    Shape spiky;
+    bool spiky_known = false;
+    uint32_t spiky_empty = 0;
+    // {n, ltot, M}: the mixed-span route's speculative boundaries disagreed nearly everywhere (data that forgets its state
+    // slowly: one dominant read length, deep): the next call of the shape does not speculate
+    Shape spec_hopeless;
+    // {n, ltot, M, ell}: the near-uniform route did not settle within its budget of rounds (or met a run the replay does
+    // not model): the next call goes straight to the mixed-span route instead of burning the budget again
+    Shape nu_failed;
+    // {n, ltot, M, ell}: ... and it settled within this many queued rounds: the next call queues them -- and the ranking
+    // behind them -- without waiting for the device in between (qmcp_hip_solve_device_begin returns at once; the state
+    // words are looked at when the solve is collected, and a call that turns out to need more is solved again the
+    // blocking way)
+    Shape nu_need;
+    uint32_t nu_need_rounds = 0;
+    // qmcp_hip_set_options: what was learnt under other options.  nu_need (and the context's nu_ell) stay, as they always
+    // have -- ADVICE.md round 4, finding 2; dropping them too changes what the next call queues.
+    void forget() { spiky_known = false; spec_hopeless = nu_failed = Shape(); }
+};
+
 // what the two halves of a solve's enqueue share (see enqueue_head)
 struct SolveRun {
     const uint32_t* d_starts = nullptr;
@@ -111,7 +141,7 @@ struct qmcp_hip_ctx {
     DevBuf keys[2], vals[2];
     DevBuf in_starts, in_ends, in_aux0, in_aux1, mask, cov, amp, next_head;
     DevBuf f_starts, f_ends, f_map, f_words, f_mask;  // filter -> solve pipeline
-    DevBuf ranges;     // range-ranked path: 257 range starts + heaviest load
+    DevBuf ranges;     // range-ranked path: range starts, heaviest load, level-2 tables (solve_words.h: Ranges)
     DevBuf rankamb;    // range-ranked path: per-range lists of quota-crossing groups, settled in the walk's tail
     // pass-major form (kernels/pass_major.inc.hip): one descriptor word per wave-slot; the table stage's working words
     DevBuf pm_desc, pm_work;
@@ -123,21 +153,12 @@ struct qmcp_hip_ctx {
     // near-uniform route (kernels/near_uniform.inc.hip): the dominant span of the last call that took it -- the next
     // call's head filters on it at once -- and the route's buffers
     uint32_t nu_ell = 0;
-    // a call of this shape did not settle within its budget of rounds (or met a run the replay does not model): the next
-    // one goes straight to the mixed-span route instead of burning the budget again
-    uint64_t nu_failed_n = 0, nu_failed_ltot = 0;
-    uint32_t nu_failed_ell = 0, nu_failed_M = 0;
-    // ... and a call of this shape settled within this many queued rounds: the next one queues them -- and the ranking
-    // behind them -- without waiting for the device in between (qmcp_hip_solve_device_begin returns at once; the state
-    // words are looked at when the solve is collected, and a call that turns out to need more is solved again the
-    // blocking way)
-    uint64_t nu_need_n = 0, nu_need_ltot = 0;
-    uint32_t nu_need_ell = 0, nu_need_M = 0, nu_need_rounds = 0;
+    Memories mem;                   // what earlier calls taught the context, by shape
     bool nu_deferred = false;       // the pending solve's rounds were queued unseen
     DevBuf nu_exc, nu_nadj, nu_ce, nu_state, nu_sus, nu_ckpt, nu_prev;
-    PinnedBuf<uint32_t> h_nu;  // pinned landing zone of the route's state words (8)
+    PinnedBuf<uint32_t> h_nu;  // pinned landing zone of the route's state words (solve_words.h: NearUniform)
     PinnedBuf<uint64_t> h_tables;  // pinned staging for the contig tables (2 x (n_contigs + 1))
-    PinnedBuf<unsigned long long> h_scalars;  // pinned landing zone of the solve's result scalars (4 words)
+    PinnedBuf<unsigned long long> h_scalars;  // pinned landing zone of the solve's result scalars (solve_words.h: HostScalars)
     // qmcp_hip_solve_host64: pinned staging, two slots per narrowing thread, and a pinned mask landing zone
     PinnedBuf<uint32_t> h_stage;
     PinnedBuf<uint64_t> h_mask;
@@ -148,16 +169,9 @@ struct qmcp_hip_ctx {
     bool pending = false;
     qmcp_hip_stats pend_stats;
     uint32_t pend_whole_contig_chains = 0;  // mixed spans without cut points: one chain per non-empty contig
-    // positions that start no read, as counted by the last range-ranked solve (picks the sweep kernel of the next)
-    bool spiky_known = false, pend_spiky = false;
-    uint64_t spiky_n = 0, spiky_ltot = 0;
-    uint32_t spiky_empty = 0;
-    // the mixed-span route's speculative boundaries disagreed nearly everywhere on the last call of this shape (data
-    // that forgets its state slowly: one dominant read length, deep): the next call of the shape does not speculate
-    uint64_t spec_hopeless_n = 0, spec_hopeless_ltot = 0;
-    uint32_t spec_hopeless_M = 0;
+    bool pend_spiky = false;                // ... and its head counted the positions that start no read (mem.spiky)
     uint32_t pend_M = 0;
-    DevBuf scalars;  // popcount + sweep iteration counters
+    DevBuf scalars;  // popcount + sweep iteration counters + speculation words (solve_words.h)
     DevBuf segs;     // cut-point windows and the sweep's stretch table
     DevBuf rings;    // mixed spans beyond 16 383: the plain event sweep's rings, in global memory
     DevBuf kidx;          // qmcp_hip_kept_indices_host: the expanded index list
@@ -228,8 +242,8 @@ struct qmcp_hip_ctx {
     uint32_t last_iters = 0, last_blocks = 0;
     // the two halves of a solve's enqueue (enqueue_head / enqueue_tail) and what they share
     SolveRun run;
-    PinnedBuf<uint32_t> h_head;       // pinned landing zone of the read-back that picks the route (8 words)
-    uint32_t* h_stats_init = nullptr; // in h_head, behind its 8 words: the statistics' initial values (8 words: ~0, then zeros)
+    PinnedBuf<uint32_t> h_head;       // pinned landing zone of the read-back that picks the route (solve_words.h: Head)
+    uint32_t* h_stats_init = nullptr; // in h_head, behind those words: the statistics' initial values (~0, then zeros)
     Event ev_head;                    // the solve's head (prepare, partition, bucket offsets) has been queued up to here
     Event ev_done;                    // everything of the solve has been queued up to here
     bool mixed_seen = false;          // a call took the mixed-span route: its arrays are sized up front from then on

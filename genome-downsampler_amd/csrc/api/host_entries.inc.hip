@@ -134,10 +134,7 @@ int qmcp_hip_set_options(qmcp_hip_ctx* c, const qmcp_hip_options* options) {
     qmcp_hip_default_options(&c->opt);
     std::memcpy(&c->opt, options, options->struct_size);   // (an older caller's shorter struct: the rest stays "the library chooses")
     c->opt.struct_size = (uint32_t)sizeof(qmcp_hip_options);
-    // (what a context remembered about earlier calls was learnt under other options)
-    c->spiky_known = false;
-    c->spec_hopeless_n = 0;
-    c->nu_failed_n = 0;
+    c->mem.forget();  // (what a context remembered about earlier calls was learnt under other options)
     return QMCP_OK;
 }
 

@@ -7,15 +7,18 @@
 // (stretches two run-ins long instead of the one-span route's four: the route sweeps several times, and a sweep is
 //  as long as its longest stretch -- two 10^7-position contigs at 1.5 x M: 0.43 -> 0.24 ms a sweep; one run-in long: 0.37)
 constexpr uint32_t kNuRunInsApart = 2;
-int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uint32_t max_load, uint32_t* d_iters, bool& done) {
+int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uint32_t max_load, bool& done) {
+    namespace w = qmcp::words;
     done = false;
     SolveRun& run = c->run;
+    uint32_t* const d_iters = w::sweep_iters(c->scalars.p);
     const Problem& pr = run.pr;
     qmcp_hip_stats& local = run.local;
     const uint32_t n = (uint32_t)pr.n, ltot = (uint32_t)pr.ltot, n_contigs = run.n_contigs, M = run.M;
     local.near_uniform_giveup = QMCP_NU_GIVEUP_NOT_TRIED;
     if (c->opt.near_uniform < 0) return QMCP_OK;
     const uint32_t ell = max_span;
+    const Shape shape{run.n64, pr.ltot, M, ell};
     uint32_t longest = 0;
     for (uint32_t k = 0; k < n_contigs; ++k) longest = run.lengths[k] > longest ? run.lengths[k] : longest;
     // which sweep the rounds run, and whether the route is tried at all (sweep_plan.h)
@@ -25,7 +28,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     if (dbg) fprintf(stderr, "[near] pm %d may_rank %d ell %u ev %d depth %.2f min_span %u filter %u\n", (int)run.pm,
                      (int)run.may_rank, ell, (int)qmcp::sweep_uniform_ev_supported(ell, M), plan.depth, min_span, run.nu_filter);
     if (!plan.tried) return QMCP_OK;
-    if (c->nu_failed_n == run.n64 && c->nu_failed_ltot == pr.ltot && c->nu_failed_ell == ell && c->nu_failed_M == M) {
+    if (c->mem.nu_failed == shape) {
         local.near_uniform_giveup = QMCP_NU_GIVEUP_REMEMBERED;
         c->nu_ell = 0;
         return QMCP_OK;
@@ -35,17 +38,18 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     uint32_t n_exc = 0;
     uint32_t* d_stats = c->stats.u32();
     if (run.nu_filter == ell) {
-        n_exc = c->h_head[5];  // (read back beside the statistics)
-        if (c->h_head[6] != 0) { c->nu_ell = 0; local.near_uniform_giveup = QMCP_NU_GIVEUP_TOO_MANY; return QMCP_OK; }  // a pass held more exceptions than it can stage
+        n_exc = c->h_head[w::kHeadExceptions];  // (read back beside the statistics)
+        if (c->h_head[w::kHeadListOverflowed] != 0) { c->nu_ell = 0; local.near_uniform_giveup = QMCP_NU_GIVEUP_TOO_MANY; return QMCP_OK; }  // a pass held more exceptions than it can stage
     } else {
         // how many reads have the longest span?  (one pass over the spans; the host waits for the count)
         TRY(ensure_near_uniform(c, n, ltot, n_contigs));
-        HIP_TRY(hipMemsetAsync(d_stats + 7, 0, sizeof(uint32_t), st));
-        qmcp::launch_nu_count_span(st, run.d_starts, run.d_ends, n, ell, d_stats + 7);
-        HIP_TRY(hipMemcpyAsync(c->h_nu, d_stats + 7, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        uint32_t* d_count = d_stats + w::kLongestSpanReads;
+        HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
+        qmcp::launch_nu_count_span(st, run.d_starts, run.d_ends, n, ell, d_count);
+        HIP_TRY(hipMemcpyAsync(c->h_nu + w::kNuScratch, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        n_exc = n - c->h_nu[0];
-        if (dbg) fprintf(stderr, "[near] reads of span %u: %u of %u, list holds %u\n", ell, c->h_nu[0], n, cap);
+        n_exc = n - c->h_nu[w::kNuScratch];
+        if (dbg) fprintf(stderr, "[near] reads of span %u: %u of %u, list holds %u\n", ell, c->h_nu[w::kNuScratch], n, cap);
         if (n_exc > n / 10u) {
             // (fewer than nine tenths of the reads have the LONGEST span: either many exceptions, or -- nearly all reads
             //  shorter than a few -- the dominant span is not the longest: reads lengthened by a deletion)
@@ -57,12 +61,11 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         c->nu_ell = ell;
         if (run.pm) TRY(queue_pm_head(c, st, ell, true));
         else TRY(queue_rm_head(c, st, ell, true));
-        uint32_t* d_max_load = c->ranges.u32() + 65540;
-        HIP_TRY(hipMemcpyAsync(c->h_nu, d_max_load, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(c->h_nu + 1, d_stats + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->h_nu + w::kNuScratch, w::max_load(c->ranges.u32()), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->h_nu + w::kNuSelectedLast, d_stats + w::kExceptions, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        max_load = c->h_nu[0];
-        if (c->h_nu[1] != n_exc || c->h_nu[2] != 0) { c->nu_ell = 0; local.near_uniform_giveup = QMCP_NU_GIVEUP_TOO_MANY; return QMCP_OK; }  // (a pass held more than it can stage)
+        max_load = c->h_nu[w::kNuScratch];
+        if (c->h_nu[w::kNuSelectedLast] != n_exc || c->h_nu[w::kNuFlags] != 0) { c->nu_ell = 0; local.near_uniform_giveup = QMCP_NU_GIVEUP_TOO_MANY; return QMCP_OK; }  // (a pass held more than it can stage)
     }
     local.near_uniform_exceptions = n_exc;
     if (n_exc == 0 || n_exc > n / 10u || (uint64_t)max_load * kRankBalance > (uint64_t)n) {
@@ -90,7 +93,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
     {
         KernelSpan sp(c, "near-uniform setup (exception coverage, need, pre-selection)");
-        qmcp::launch_nu_setup(st, exc, cap, n_exc, d_stats + 6, boff, ltot, ell, M, c->nu_ce.u32(), c->spine.u32(),
+        qmcp::launch_nu_setup(st, exc, cap, n_exc, d_stats + w::kOverflowEntries, boff, ltot, ell, M, c->nu_ce.u32(), c->spine.u32(),
                               nadj, state);
     }
     const uint32_t* seg = nullptr;
@@ -126,9 +129,8 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     const uint32_t budget = nu_round_budget(c, run.lengths, n_contigs);
     // A shape that settled within a few rounds last time: queue that many (a round whose contigs are all settled sweeps
     // and verifies nothing) and the ranking behind them WITHOUT waiting in between; collect_one looks at the state words.
-    const bool defer = !dbg && c->opt.near_uniform_rounds == 0 && c->nu_need_rounds != 0 && c->nu_need_rounds <= 8 &&
-                       c->nu_need_n == run.n64 && c->nu_need_ltot == pr.ltot && c->nu_need_ell == ell && c->nu_need_M == M &&
-                       run.nu_filter == ell;
+    const bool defer = !dbg && c->opt.near_uniform_rounds == 0 && c->mem.nu_need_rounds != 0 && c->mem.nu_need_rounds <= 8 &&
+                       c->mem.nu_need == shape && run.nu_filter == ell;
     while (rounds < budget && !settled) {
         const uint32_t batch = 2u;
         for (uint32_t r = 0; r < batch; ++r) {
@@ -172,7 +174,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
             }
             {
                 KernelSpan sp(c, "near-uniform round (verify, replay, select, apply)");
-                qmcp::launch_nu_round(st, exc, cap, n_exc, d_stats + 6, rounds == 1, boff, selend, nadj, c->nu_ce.u32(), poff, n_contigs, ell, M,
+                qmcp::launch_nu_round(st, exc, cap, n_exc, d_stats + w::kOverflowEntries, rounds == 1, boff, selend, nadj, c->nu_ce.u32(), poff, n_contigs, ell, M,
                                       c->nu_sus.as<uint2>(), nu_suspects_for(n), state, viol_key, viol_idx, sweep_from[0], sweep_from[1],
                                       ltot, c->spine.u32(), stretches ? seg : nullptr, n_seg_max, marks[1],
                                       stretches ? c->nu_prev.u32() : nullptr, dirty[0], dirty[1], seg_fine, fine[1]);
@@ -183,8 +185,8 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
             }
         }
         HIP_TRY(hipGetLastError());
-        if (defer && rounds < c->nu_need_rounds) continue;
-        HIP_TRY(hipMemcpyAsync(c->h_nu, state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (defer && rounds < c->mem.nu_need_rounds) continue;
+        HIP_TRY(hipMemcpyAsync(c->h_nu, state, w::kNuStateWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         if (defer) break;  // (looked at when the solve is collected)
         HIP_TRY(hipStreamSynchronize(st));
         if (dbg) {
@@ -192,46 +194,40 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
             (void)hipMemcpy(more, state + 8, sizeof(more), hipMemcpyDeviceToHost);
             fprintf(stderr, "[near] open question: s %u u1 %u S(u1-1) %u C(u1-1) %u b %u c0 %u\n", more[0], more[1], more[2], more[3], more[4], more[5]);
             fprintf(stderr, "[near] after %u rounds: last round selected %u, flags %u (read %u), selected in all %u, suspects %u, rounds that selected %u; next sweeps from block",
-                    rounds, c->h_nu[1], c->h_nu[2], c->h_nu[5], c->h_nu[3], c->h_nu[4], c->h_nu[6]);
+                    rounds, c->h_nu[w::kNuSelectedLast], c->h_nu[w::kNuFlags], c->h_nu[w::kNuFlagsRead], c->h_nu[w::kNuSelected],
+                    c->h_nu[w::kNuSuspects], c->h_nu[w::kNuRoundsThatSelected]);
             std::vector<uint32_t> from(n_contigs);
             (void)hipMemcpy(from.data(), sweep_from[0], (size_t)n_contigs * sizeof(uint32_t), hipMemcpyDeviceToHost);
             for (uint32_t k = 0; k < n_contigs && k < 16; ++k) fprintf(stderr, " %d", (int)from[k]);
             fprintf(stderr, "\n");
         }
-        if (c->h_nu[2] != 0) break;          // a run the replay does not model, or too many suspects
-        settled = c->h_nu[1] == 0;           // the last round wanted no exception: the sweep's counts are the greedy's
+        if (c->h_nu[w::kNuFlags] != 0) break;          // a run the replay does not model, or too many suspects
+        settled = c->h_nu[w::kNuSelectedLast] == 0;    // the last round wanted no exception: the sweep's counts are the greedy's
     }
     c->nu_deferred = defer;
     if (defer) {
         settled = true;  // (provisionally: collect_one checks, and solves the call again if it is not)
     } else if (settled) {
-        c->nu_need_n = run.n64; c->nu_need_ltot = pr.ltot; c->nu_need_ell = ell; c->nu_need_M = M;
-        c->nu_need_rounds = rounds;              // (queued: an even number)
-        rounds = c->h_nu[6] + 1;                 // (the rounds that did something, and the one that found nothing left)
+        c->mem.nu_need = shape;
+        c->mem.nu_need_rounds = rounds;                   // (queued: an even number)
+        rounds = c->h_nu[w::kNuRoundsThatSelected] + 1;   // (the rounds that did something, and the one that found nothing left)
     }
     local.near_uniform_rounds = rounds;
-    local.near_uniform_selected = defer ? 0u : c->h_nu[3];
+    local.near_uniform_selected = defer ? 0u : c->h_nu[w::kNuSelected];
     if (!settled) {
-        c->nu_need_rounds = 0;
+        c->mem.nu_need_rounds = 0;
         // (the head must not filter on this span again, and the next call of this shape must not burn the budget again)
-        local.near_uniform_giveup = c->h_nu[2] != 0 ? QMCP_NU_GIVEUP_UNMODELLED : QMCP_NU_GIVEUP_BUDGET;
+        local.near_uniform_giveup = c->h_nu[w::kNuFlags] != 0 ? QMCP_NU_GIVEUP_UNMODELLED : QMCP_NU_GIVEUP_BUDGET;
         c->nu_ell = 0;
-        c->nu_failed_n = run.n64; c->nu_failed_ltot = pr.ltot; c->nu_failed_ell = ell; c->nu_failed_M = M;
+        c->mem.nu_failed = shape;
         return QMCP_OK;
     }
     local.near_uniform_giveup = QMCP_NU_GIVEUP_NONE;
     HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], st));
-    if (run.pm) {
-        queue_pm_rank(c, st, nullptr, nullptr, 0);
-    } else {
-        KernelSpan sp(c, "k_rank_mark");
-        qmcp::launch_rank_mark(st, c->keys[0].as<uint16_t>(), c->vals[0].u32(), c->ranges.u32(), run.range_shift, ltot,
-                               boff, selend, (unsigned long long*)run.d_mask, c->scalars.as<unsigned long long>(),
-                               c->rankamb.p, qmcp::rank_scratch_by_records(run.range_shift, ltot, n));
-    }
+    queue_rank(c, st, nullptr, nullptr, 0);
     {
         KernelSpan sp(c, "k_nu_mark_selected");
-        qmcp::launch_nu_mark_selected(st, exc, cap, n_exc, d_stats + 6, (unsigned long long*)run.d_mask,
+        qmcp::launch_nu_mark_selected(st, exc, cap, n_exc, d_stats + w::kOverflowEntries, (unsigned long long*)run.d_mask,
                                       c->scalars.as<unsigned long long>());
     }
     HIP_TRY(hipGetLastError());

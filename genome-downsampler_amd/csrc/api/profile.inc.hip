@@ -68,7 +68,7 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         if (st_out) *st_out = local;
         return QMCP_OK;
     }
-    TRY(ensure_pinned(c, c->h_scalars, 16 * sizeof(unsigned long long)));
+    TRY(ensure_pinned(c, c->h_scalars, qmcp::words::kHostScalarsWords * sizeof(unsigned long long)));
     // the arena, sized before anything is queued
     const uint32_t n_tiles = qmcp::sort_tiles(n);
     c->sized = false;
@@ -84,8 +84,8 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         TRY(ensure(c, c->eoff, ((size_t)ltot + 1) * sizeof(uint32_t)));
         TRY(ensure(c, c->selend, ((size_t)ltot + 8) * sizeof(uint32_t)));
         TRY(ensure(c, c->next_head, ((size_t)n + 2) * sizeof(uint32_t)));
-        TRY(ensure(c, c->scalars, 64));
-        TRY(ensure(c, c->stats, 12 * sizeof(uint32_t)));
+        TRY(ensure(c, c->scalars, qmcp::words::kScalarsBytes));
+        TRY(ensure(c, c->stats, qmcp::words::kStatsWords * sizeof(uint32_t)));
         TRY(ensure(c, c->segs, qmcp::sweep_segment_words(n_contigs < 256 ? n_contigs : 0, qmcp::kMaxSweepWindows) * sizeof(uint32_t)));
         TRY(ensure(c, nd.need_buf(c), ((size_t)ltot + 8) * sizeof(uint32_t)));
         TRY(nd.reserve(c));
@@ -105,51 +105,21 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     local.max_span = max_span;
     if (max_span > qmcp::kMaxGeneralSpan)
         return fail(QMCP_ERANGE, "reads with span %u > %u are not supported by this build", max_span, qmcp::kMaxGeneralSpan);
-    const uint32_t pos_bits = bit_width(ltot - 1) == 0 ? 1u : bit_width(ltot - 1);
-    const uint32_t span_bits = bit_width(max_span - min_span);
-    const bool wide = pos_bits + span_bits > 32;
-    const uint32_t* d_gstart = c->vals[1].u32();
-    HIP_TRY(hipMemsetAsync(c->ecnt.p, 0, ((size_t)ltot + 1) * sizeof(uint32_t), st));
-    {
-        KernelSpan sp(c, "k_general_keys");
-        qmcp::launch_general_keys(st, wide, d_gstart, d_starts, d_ends, n, span_bits, max_span, nullptr,
-                                  wide ? c->keys[0].p : c->vals[0].p, c->ecnt.u32(), ltot + 1);
-    }
-    HIP_TRY(hipGetLastError());
-    TRY(scan_counts(c, c->ecnt, c->eoff, ltot));
+    // the plain solve's mixed route up to the bucket offsets (solve_stages.inc.hip), under this route's span names
+    SortedReads s = key_layout(ltot, min_span, max_span);
+    TRY(queue_mixed_keys(c, d_starts, d_ends, n, ltot, max_span, s));
     HIP_TRY(hipEventRecord(c->ev[EV_SCAN], st));
-    HIP_TRY(hipMemsetAsync(c->scalars.p, 0, 64, st));
-    // radix bucketing: stable LSD, 8-bit digits (as the plain solve's sort-based routes)
-    const uint32_t passes = (pos_bits + span_bits + 7) / 8;
-    local.sort_passes = passes;
-    int kin = 0, vin = 0;
+    HIP_TRY(hipMemsetAsync(c->scalars.p, 0, qmcp::words::kScalarsBytes, st));
+    local.sort_passes = s.passes;
     const RadixNames radix_names = {"radix pass (hist, scan, scatter)"};
-    if (!wide) {
-        TRY(radix_sort_records(c, st, c->vals[0].u32(), n, passes, c->hist.u32(), c->spine.u32(),
-                               c->keys, radix_names, &kin));
-    } else {
-        WideBufs wb;
-        TRY(radix_sort_wide(c, st, n, passes, c->hist.u32(), c->spine.u32(), c->keys, c->vals, radix_names, &wb));
-        kin = wb.k;
-        vin = wb.v;
-    }
-    HIP_TRY(hipMemsetAsync(c->boff.p, 0xFF, ((size_t)ltot + 1) * sizeof(uint32_t), st));
-    {
-        KernelSpan sp(c, "k_bucket_heads");
-        qmcp::launch_bucket_heads(st, wide, c->keys[kin].p, c->vals[vin].u32(), n, span_bits, ltot, c->boff.u32());
-    }
-    {
-        KernelSpan sp(c, "reverse_min_scan(3 kernels)");
-        qmcp::launch_reverse_min_scan(st, c->boff.u32(), ltot + 1, c->spine.u32());
-    }
-    HIP_TRY(hipGetLastError());
+    TRY(queue_sort(c, c->vals[0].u32(), n, s, radix_names, radix_names));
+    TRY(queue_bucket_offsets(c, n, ltot, s));
     HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
     // need[], cut points
     const uint32_t* d_need = nd.need_buf(c).u32();
     const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
     const uint32_t* seg = nullptr;
     uint32_t n_seg_max = 0;
-    uint32_t* d_iters = (uint32_t*)(c->scalars.as<char>() + 16);
     EventPair ev_pf(c);
     if (!ev_pf.a || !ev_pf.b) return fail(QMCP_EHIP, "event creation failed");
     HIP_TRY(hipEventRecord(ev_pf.a, st));
@@ -165,61 +135,37 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         KernelSpan sp(c, "k_profile_cuts");
         seg = qmcp::launch_profile_segments(st, d_need, c->poff.u64(), n_contigs, ltot, windows, c->segs.u32());
         n_seg_max = n_contigs + windows;
-        HIP_TRY(hipMemcpyAsync(d_iters + 2, seg, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(qmcp::words::sweep_iters(c->scalars.p) + qmcp::words::kStretches, seg, sizeof(uint32_t),
+                               hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(hipEventRecord(ev_pf.b, st));
     HIP_TRY(hipGetLastError());
     // the capped sweep
     bool swept = idle;
     if (in_regs && !idle) {
-        {
-            KernelSpan sp(c, "k_group_heads");
-            qmcp::launch_group_heads(st, wide, c->keys[kin].p, n, c->next_head.u32());
-        }
-        {
-            KernelSpan sp(c, "reverse_min_scan(3 kernels)");
-            qmcp::launch_reverse_min_scan(st, c->next_head.u32(), n + 1, c->spine.u32());
-        }
+        TRY(queue_run_lengths(c, n, s));
         KernelSpan sp(c, "k_sweep_general_reg(capped)");
-        swept = qmcp::launch_sweep_general_reg_capped(st, wide, c->boff.u32(), d_need, c->keys[kin].p,
+        swept = qmcp::launch_sweep_general_reg_capped(st, s.wide, c->boff.u32(), d_need, c->keys[s.k].p,
                                                       c->next_head.u32(), c->poff.u64(), n_contigs,
-                                                      span_bits, max_span, c->selend.u32(), seg, n_seg_max);
+                                                      s.span_bits, max_span, c->selend.u32(), seg, n_seg_max);
     }
     if (!swept) {
-        uint32_t ring = 64;
-        while (ring <= max_span) ring <<= 1;
-        uint32_t* g_rings = nullptr;
-        if (max_span > qmcp::kMaxLdsRingSpan) {  // long reads: the two rings of a workgroup no longer fit LDS
-            const size_t n_wg = seg ? n_seg_max : n_contigs;
-            TRY(ensure(c, c->rings, n_wg * 2 * (size_t)ring * sizeof(uint32_t)));
-            g_rings = c->rings.u32();
-        }
+        Rings rings;
+        TRY(sweep_rings(c, max_span, seg ? n_seg_max : n_contigs, rings));
         KernelSpan sp(c, "k_sweep_general(capped)");
-        qmcp::launch_sweep_general_capped(st, wide, c->boff.u32(), d_need, c->keys[kin].p, c->poff.u64(), n_contigs,
-                                          span_bits, max_span, c->selend.u32(), ring, seg, n_seg_max, g_rings);
+        qmcp::launch_sweep_general_capped(st, s.wide, c->boff.u32(), d_need, c->keys[s.k].p, c->poff.u64(), n_contigs,
+                                          s.span_bits, max_span, c->selend.u32(), rings.size, seg, n_seg_max, rings.global);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], st));
-    if (!idle) {
-        KernelSpan sp(c, "k_mark");
-        qmcp::launch_mark(st, wide, c->keys[kin].p, c->vals[vin].u32(), ltot, c->boff.u32(),
-                          c->selend.u32(), d_mask, c->scalars.as<unsigned long long>());
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[EV_MARK], st));
-    HIP_TRY(hipMemcpyAsync(c->h_scalars, c->scalars.p, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (!idle) queue_mark(c, ltot, s, d_mask);
+    TRY(queue_result_scalars(c));
     HIP_TRY(hipStreamSynchronize(st));
     collect_spans(c);
-    local.n_kept = c->h_scalars[0];
-    local.sweep_stretches = (uint32_t)(c->h_scalars[3] & 0xFFFFFFFFu);
-    if (seg == nullptr && !idle)  // one wave per non-empty contig
-        for (uint32_t k = 0; k < n_contigs; ++k) local.sweep_stretches += lengths[k] != 0 ? 1u : 0u;
-    local.ms_prepare = elapsed(c->ev[EV_BEGIN], c->ev[EV_PREP]);
-    local.ms_scan = elapsed(c->ev[EV_PREP], c->ev[EV_SCAN]);
-    local.ms_sort = elapsed(c->ev[EV_SCAN], c->ev[EV_SORT]);
-    local.ms_sweep = elapsed(c->ev[EV_SORT], c->ev[EV_SWEEP]);
-    local.ms_mark = elapsed(c->ev[EV_SWEEP], c->ev[EV_MARK]);
-    local.ms_total = elapsed(c->ev[EV_BEGIN], c->ev[EV_MARK]);
+    local.n_kept = c->h_scalars[qmcp::words::kHostKept];
+    local.sweep_stretches = qmcp::words::lo32(c->h_scalars[qmcp::words::kHostStretches]);
+    if (seg == nullptr && !idle) local.sweep_stretches += whole_contig_chains(lengths, n_contigs);
+    phase_times(c, local);
     local.arena_grown_mid_solve = c->grew_mid_solve;
     nd.ms += elapsed(ev_pf.a, ev_pf.b);
     if (swept_out) *swept_out = !idle;

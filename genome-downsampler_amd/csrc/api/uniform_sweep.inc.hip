@@ -2,18 +2,6 @@
 // The one-length sweep's launches: block-scan pipelines, event-driven form, stretches at cut points, speculative boundaries in
 // tiers.  Which of them a call takes is decided in sweep_plan.h (plan_uniform_sweep).
 
-// device words of a speculative sweep, behind the solve's other scalars
-struct SpecWords {
-    uint32_t* mismatches1;  // tier 1: boundaries that disagreed
-    uint32_t* n_spec1;      //         speculative boundaries
-    uint32_t* mismatches2;  // tier 2
-    uint32_t* n_spec2;
-};
-SpecWords spec_words(qmcp_hip_ctx* c) {
-    uint32_t* w = (uint32_t*)(c->scalars.as<char>() + 32);
-    return SpecWords{w, w + 1, w + 2, w + 3};
-}
-
 // The tiers of a speculative sweep.  `unit`: positions per block of run-in (the span; the largest span of a
 // mix), `round_to`: the run-in is made a multiple of this many positions.  sweep(table, second output or null,
 // marks to obey or null) launches the sweep kernel; check(table, mismatch counter, marks to obey or
@@ -25,7 +13,7 @@ int speculative_sweep(qmcp_hip_ctx* c, hipStream_t st, uint32_t n_contigs, uint3
                       const uint32_t* seg_exact, const char* sweep_name, Sweep sweep, Check check,
                       const uint32_t* only_marked = nullptr /* per exact stretch: the parts of the genome to sweep at all
                                                                (the near-uniform route's later rounds); null: everything */) {
-    const SpecWords w = spec_words(c);
+    const qmcp::words::SpecWords w = qmcp::words::spec_words(c->scalars.p);  // (behind the solve's other scalars)
     const uint64_t* poff = c->poff.u64();
     const uint32_t n_cand = n_contigs + windows;
     TRY(ensure(c, c->specflags, 2 * (size_t)n_cand * sizeof(uint32_t)));

@@ -36,6 +36,7 @@
 #include "cap_table.h"
 #include "pair_plan.h"
 #include "replicates_plan.h"
+#include "solve_words.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order: a part uses only parts above it,
 // those a by-contig feature builds on are named in brackets):
@@ -46,10 +47,13 @@
 //   uniform_sweep       which one-length sweep a call takes and its launches (pipelines, event-driven form, stretches,
 //                       speculative tiers)
 //   near_uniform_sizes  the near-uniform route's sizes, round budget and buffers
+//   solve_stages        the stages the sort-based routes share (plain solve and capped solve): keys, sort, bucket offsets,
+//                       run lengths, rings, mark, the result scalars, phase times
 //   solve_head          a solve's head: arena sizing, the range-ranked route's producers, bucket offsets; the pass-major
 //                       ranking
 //   near_uniform_route  the near-uniform route's half of a solve's tail
-//   solve_tail          a solve's tail, collection, context creation, enqueue / complete
+//   solve_tail          a solve's tail -- read the head's facts, pick the route, one function per route --, collection,
+//                       context creation, enqueue / complete
 //   host_entries        probes, column upload, the extern "C" entry points
 //   multi_device        several devices behind one call
 //   by_contig           reads in any order with a contig id each: the grouping as a value, a batch's view, the batch loop
@@ -89,6 +93,7 @@
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
 #include "api/near_uniform_sizes.inc.hip"
+#include "api/solve_stages.inc.hip"
 #include "api/solve_head.inc.hip"
 #include "api/near_uniform_route.inc.hip"
 #include "api/solve_tail.inc.hip"

@@ -34,13 +34,11 @@
 #include <vector>
 
 #include "qmcp_kernels.h"
+#include "solve_words.h"
 #include "stage_driver_common.h"
 
 namespace {
 using namespace stage_common;
-
-constexpr uint32_t kRangesWords = 65537 + 7 + 771 + 5;  // api/solve_head.inc.hip: range starts, heaviest load, level-2 tables
-constexpr uint32_t kMaxLoadAt = 65540, kSegTablesAt = 65544;
 
 struct Quota {
     uint32_t kind = 0, dflt = 0;
@@ -106,7 +104,7 @@ bool run(const Case& cs) {
         if (!alloc(hist, "hist", (size_t)256 * tiles_seg * 4, kCanary, nullptr, stage)) return false;
         if (!alloc(recs, "recs", (size_t)n * 8, kCanary, nullptr, stage)) return false;
     }
-    if (!alloc(ranges, "ranges", (size_t)kRangesWords * 4, kCanary, nullptr, stage)) return false;
+    if (!alloc(ranges, "ranges", (size_t)qmcp::words::kRangesWords * 4, kCanary, nullptr, stage)) return false;
     if (!alloc(stats, "stats", 12 * 4, kCanary, nullptr, stage)) return false;
     if (!alloc(boff, "boff", ((size_t)ltot + 1) * 4, kCanary, nullptr, stage)) return false;
     if (!alloc(selend, "selend", ((size_t)ltot + 8) * 4, kCanary, nullptr, stage)) return false;
@@ -117,8 +115,8 @@ bool run(const Case& cs) {
     uint32_t* const d_exc = filter ? exc.p<uint32_t>() : nullptr;
     uint32_t* const d_exc_cnt = filter ? qmcp::nu_exc_counts(d_exc, exc_cap) : nullptr;
     uint32_t* const d_range_start = ranges.p<uint32_t>();
-    uint32_t* const d_max_load = d_range_start + kMaxLoadAt;
-    uint32_t* const d_seg_tables = d_range_start + kSegTablesAt;
+    uint32_t* const d_max_load = qmcp::words::max_load(d_range_start);
+    uint32_t* const d_seg_tables = qmcp::words::seg_tables(d_range_start);
 
     hipStream_t st;
     CHK(hipStreamCreate(&st));
