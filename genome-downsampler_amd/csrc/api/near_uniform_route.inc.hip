@@ -74,9 +74,10 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         return QMCP_OK;
     }
     // scratch of the event-driven sweep (launch_uniform_sweep)
+    const uint32_t ev_wg_max = qmcp::sweep_ev_workgroups_max(n_contigs);
     if (!stretches) {
-        TRY(ensure(c, c->evpk, qmcp::sweep_ev_pack_bytes(ltot, ell, n_contigs + 768)));
-        TRY(ensure(c, c->evlast, qmcp::sweep_ev_last_bytes(ltot, ell, n_contigs + 768)));
+        TRY(ensure(c, c->evpk, qmcp::sweep_ev_pack_bytes(ltot, ell, ev_wg_max)));
+        TRY(ensure(c, c->evlast, qmcp::sweep_ev_last_bytes(ltot, ell, ev_wg_max)));
     }
     const uint32_t* boff = c->boff.u32();
     const uint64_t* poff = c->poff.u64();
@@ -87,7 +88,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     unsigned long long* viol_key = (unsigned long long*)(c->nu_state.as<char>() + 64);
     uint32_t* viol_idx = (uint32_t*)(viol_key + n_contigs);
     uint32_t* sweep_from[2] = {viol_idx + n_contigs, viol_idx + 2 * (size_t)n_contigs};  // this round's, the next round's
-    if (!stretches) TRY(ensure(c, c->nu_ckpt, qmcp::sweep_ev_ckpt_bytes(ltot, ell, n_contigs + 768)));
+    if (!stretches) TRY(ensure(c, c->nu_ckpt, qmcp::sweep_ev_ckpt_bytes(ltot, ell, ev_wg_max)));
     HIP_TRY(hipMemsetAsync(sweep_from[0], 0, (size_t)n_contigs * sizeof(uint32_t), st));
     HIP_TRY(hipEventRecord(c->ev[EV_SCAN], st));
     HIP_TRY(hipEventRecord(c->ev[EV_SORT], st));
@@ -96,15 +97,12 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
         qmcp::launch_nu_setup(st, exc, cap, n_exc, d_stats + w::kOverflowEntries, boff, ltot, ell, M, c->nu_ce.u32(), c->spine.u32(),
                               nadj, state);
     }
-    const uint32_t* seg = nullptr;
-    uint32_t n_seg_max = 0;
+    qmcp::SweepAxis ax{st, boff, poff, n_contigs, ltot};
     const uint32_t windows = plan.windows, burn_blocks = plan.burn_blocks;
     // stretches: the exact table once (the cut points do not move between rounds), the speculative ones per sweep
     if (windows != 0) {
         KernelSpan sp(c, "k_find_cuts", st);
-        seg = qmcp::launch_sweep_segments(st, boff, nullptr, poff, n_contigs, ltot, ell, M, windows, c->segs.u32(),
-                                          c->nu_ce.u32());
-        n_seg_max = n_contigs + windows;
+        ax = qmcp::launch_sweep_segments(ax, nullptr, ell, M, windows, c->segs.u32(), c->nu_ce.u32());
     }
     // later rounds sweep only the exact stretches a selection of the round before touched (k_nu_select_apply marks them)
     uint32_t* marks[2] = {(uint32_t*)(c->nu_sus.as<char>() + qmcp::nu_suspect_bytes(nu_suspects_for(n))), nullptr};
@@ -118,7 +116,7 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
     if (stretches) HIP_TRY(hipMemsetAsync(dirty[0], 0, 2 * qmcp::nu_cells_bytes(), st));
     // (the first tier's table: launch_sweep_segments_speculative(..., tier 1) builds it at this place on every sweep, from
     //  the same cut points -- the same table every round)
-    const uint32_t* seg_fine = speculate ? c->segs.u32() + windows + (1 + 5 * ((size_t)n_contigs + windows)) : nullptr;
+    const uint32_t* seg_fine = speculate ? c->segs.u32() + qmcp::sweep_segment_table_offset(n_contigs, windows, 1) : nullptr;
     if (c->opt.near_uniform_debug == 2) seg_fine = nullptr;  // (lab: every round sweeps every stretch its exact marks cover)
     // Rounds are queued two at a time and the host looks at the state words after each pair: a round whose contigs are
     // all settled is eight launches that return at once (the chain sweeps nothing, the verification skips every
@@ -137,46 +135,47 @@ int near_uniform_tail(qmcp_hip_ctx* c, uint32_t min_span, uint32_t max_span, uin
             ++rounds;
             if (stretches) {
                 if (speculate) {
+                    // (the first tier's stretches a selection of the round before left alone keep their output)
+                    auto own_marks = [&](const qmcp::SweepAxis& tier) {
+                        return (tier.seg == seg_fine && rounds > 1) ? fine[0] : nullptr;
+                    };
                     TRY(speculative_sweep(
-                        c, st, n_contigs, ltot, windows, ell, ell, burn_blocks, kNuRunInsApart, seg, "k_sweep_uniform_gen",
-                        [&](const uint32_t* table, uint32_t* run_in_out, const uint32_t* redo_in) {
-                            return qmcp::launch_sweep_uniform_gen(st, boff, poff, n_contigs, ell, M, ltot, selend, d_iters, table,
-                                                                  n_seg_max, run_in_out, redo_in, nadj,
-                                                                  (table == seg_fine && rounds > 1) ? fine[0] : nullptr);
+                        c, ax, ell, ell, burn_blocks, kNuRunInsApart, "k_sweep_uniform_gen",
+                        [&](const qmcp::SweepAxis& tier, uint32_t* run_in_out, const uint32_t* redo_in) {
+                            return qmcp::launch_sweep_uniform_gen(tier, ell, M, selend, d_iters, run_in_out, redo_in, nadj,
+                                                                  own_marks(tier));
                         },
-                        [&](const uint32_t* table, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
-                            qmcp::launch_spec_verify(st, table, n_seg_max, ell, selend, c->cstart.u32(), mismatches,
-                                                     redo_in, redo_out, (table == seg_fine && rounds > 1) ? fine[0] : nullptr);
+                        [&](const qmcp::SweepAxis& tier, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
+                            qmcp::launch_spec_verify(tier, ell, selend, c->cstart.u32(), mismatches, redo_in, redo_out,
+                                                     own_marks(tier));
                         },
                         rounds == 1 ? nullptr : marks[0]));
                 } else {
                     KernelSpan sp(c, "k_sweep_uniform_gen", st);
-                    if (!qmcp::launch_sweep_uniform_gen(st, boff, poff, n_contigs, ell, M, ltot, selend, d_iters, seg, n_seg_max,
-                                                        nullptr, (seg != nullptr && rounds > 1) ? marks[0] : nullptr, nadj))
+                    if (!qmcp::launch_sweep_uniform_gen(ax, ell, M, selend, d_iters, nullptr,
+                                                        (ax.seg != nullptr && rounds > 1) ? marks[0] : nullptr, nadj))
                         return fail(QMCP_ERANGE, "near-uniform route: span %u not supported", ell);
                 }
             } else {
             {
                 KernelSpan sp(c, "k_sweep_pack", st);
-                qmcp::launch_sweep_ev_pack(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, c->evpk.u32(), nadj, sweep_from[0]);
+                qmcp::launch_sweep_ev_pack(ax, ell, M, c->evpk.u32(), nadj, sweep_from[0]);
             }
             {
                 KernelSpan sp(c, "k_sweep_uniform_ev", st);
-                qmcp::launch_sweep_ev_chain(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, c->evpk.u32(),
-                                            c->cstart.u32(), c->evlast.u32(), d_iters, nadj, c->nu_ckpt.u32(),
-                                            sweep_from[0]);
+                qmcp::launch_sweep_ev_chain(ax, ell, M, c->evpk.u32(), c->cstart.u32(), c->evlast.u32(), d_iters, nadj,
+                                            c->nu_ckpt.u32(), sweep_from[0]);
             }
             {
                 KernelSpan sp(c, "k_sweep_expand", st);
-                qmcp::launch_sweep_ev_expand(st, boff, poff, n_contigs, ell, M, ltot, nullptr, 0, c->cstart.u32(),
-                                             c->evlast.u32(), selend, sweep_from[0]);
+                qmcp::launch_sweep_ev_expand(ax, ell, M, c->cstart.u32(), c->evlast.u32(), selend, sweep_from[0]);
             }
             }
             {
                 KernelSpan sp(c, "near-uniform round (verify, replay, select, apply)");
                 qmcp::launch_nu_round(st, exc, cap, n_exc, d_stats + w::kOverflowEntries, rounds == 1, boff, selend, nadj, c->nu_ce.u32(), poff, n_contigs, ell, M,
                                       c->nu_sus.as<uint2>(), nu_suspects_for(n), state, viol_key, viol_idx, sweep_from[0], sweep_from[1],
-                                      ltot, c->spine.u32(), stretches ? seg : nullptr, n_seg_max, marks[1],
+                                      ltot, c->spine.u32(), stretches ? ax.seg : nullptr, ax.n_seg_max, marks[1],
                                       stretches ? c->nu_prev.u32() : nullptr, dirty[0], dirty[1], seg_fine, fine[1]);
                 std::swap(sweep_from[0], sweep_from[1]);
                 std::swap(marks[0], marks[1]);

@@ -37,9 +37,9 @@ int ensure_near_uniform(qmcp_hip_ctx* c, uint32_t n, uint32_t ltot, uint32_t n_c
     if (c->nu_ell != 0) {
         // (the route's sweep scratch depends on the span: known from the last call that took the route, so a second call
         //  of the shape grows nothing after its first launch)
-        TRY(ensure(c, c->evpk, qmcp::sweep_ev_pack_bytes(ltot, c->nu_ell, n_contigs + 768)));
-        TRY(ensure(c, c->evlast, qmcp::sweep_ev_last_bytes(ltot, c->nu_ell, n_contigs + 768)));
-        TRY(ensure(c, c->nu_ckpt, qmcp::sweep_ev_ckpt_bytes(ltot, c->nu_ell, n_contigs + 768)));
+        TRY(ensure(c, c->evpk, qmcp::sweep_ev_pack_bytes(ltot, c->nu_ell, qmcp::sweep_ev_workgroups_max(n_contigs))));
+        TRY(ensure(c, c->evlast, qmcp::sweep_ev_last_bytes(ltot, c->nu_ell, qmcp::sweep_ev_workgroups_max(n_contigs))));
+        TRY(ensure(c, c->nu_ckpt, qmcp::sweep_ev_ckpt_bytes(ltot, c->nu_ell, qmcp::sweep_ev_workgroups_max(n_contigs))));
     }
     TRY(ensure(c, c->spine, scan_spine_bytes(ltot + 2, 1)));
     TRY(ensure_pinned(c, c->h_nu, 8 * sizeof(uint32_t)));

@@ -118,8 +118,7 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     // need[], cut points
     const uint32_t* d_need = nd.need_buf(c).u32();
     const bool in_regs = max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
-    const uint32_t* seg = nullptr;
-    uint32_t n_seg_max = 0;
+    qmcp::SweepAxis ax{st, c->boff.u32(), c->poff.u64(), n_contigs, ltot};
     EventPair ev_pf(c);
     if (!ev_pf.a || !ev_pf.b) return fail(QMCP_EHIP, "event creation failed");
     HIP_TRY(hipEventRecord(ev_pf.a, st));
@@ -133,28 +132,26 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
         qmcp::plan_mixed_sweep(c->opt, n, max_span, ltot, n_contigs, nd.plan_cap(max_cap), in_regs, false).windows;
     if (windows != 0 && !idle) {
         KernelSpan sp(c, "k_profile_cuts");
-        seg = qmcp::launch_profile_segments(st, d_need, c->poff.u64(), n_contigs, ltot, windows, c->segs.u32());
-        n_seg_max = n_contigs + windows;
-        HIP_TRY(hipMemcpyAsync(qmcp::words::sweep_iters(c->scalars.p) + qmcp::words::kStretches, seg, sizeof(uint32_t),
+        ax = qmcp::launch_profile_segments(ax, d_need, windows, c->segs.u32());
+        HIP_TRY(hipMemcpyAsync(qmcp::words::sweep_iters(c->scalars.p) + qmcp::words::kStretches, ax.seg, sizeof(uint32_t),
                                hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(hipEventRecord(ev_pf.b, st));
     HIP_TRY(hipGetLastError());
     // the capped sweep
     bool swept = idle;
+    const qmcp::SortedSpans reads{s.wide, c->keys[s.k].p, c->next_head.u32(), s.span_bits, max_span};
+    const qmcp::SweepDemand demand{d_need, true};
     if (in_regs && !idle) {
         TRY(queue_run_lengths(c, n, s));
         KernelSpan sp(c, "k_sweep_general_reg(capped)");
-        swept = qmcp::launch_sweep_general_reg_capped(st, s.wide, c->boff.u32(), d_need, c->keys[s.k].p,
-                                                      c->next_head.u32(), c->poff.u64(), n_contigs,
-                                                      s.span_bits, max_span, c->selend.u32(), seg, n_seg_max);
+        swept = qmcp::launch_sweep_general_reg(ax, reads, demand, 0, c->selend.u32());
     }
     if (!swept) {
         Rings rings;
-        TRY(sweep_rings(c, max_span, seg ? n_seg_max : n_contigs, rings));
+        TRY(sweep_rings(c, max_span, ax.workgroups(), rings));
         KernelSpan sp(c, "k_sweep_general(capped)");
-        qmcp::launch_sweep_general_capped(st, s.wide, c->boff.u32(), d_need, c->keys[s.k].p, c->poff.u64(), n_contigs,
-                                          s.span_bits, max_span, c->selend.u32(), rings.size, seg, n_seg_max, rings.global);
+        qmcp::launch_sweep_general(ax, reads, demand, 0, c->selend.u32(), rings.size, rings.global);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[EV_SWEEP], st));
@@ -164,7 +161,7 @@ int capped_solve_batch(qmcp_hip_ctx* c, CappedNeed& nd, uint32_t max_cap, const 
     collect_spans(c);
     local.n_kept = c->h_scalars[qmcp::words::kHostKept];
     local.sweep_stretches = qmcp::words::lo32(c->h_scalars[qmcp::words::kHostStretches]);
-    if (seg == nullptr && !idle) local.sweep_stretches += whole_contig_chains(lengths, n_contigs);
+    if (ax.seg == nullptr && !idle) local.sweep_stretches += whole_contig_chains(lengths, n_contigs);
     phase_times(c, local);
     local.arena_grown_mid_solve = c->grew_mid_solve;
     nd.ms += elapsed(ev_pf.a, ev_pf.b);

@@ -168,17 +168,12 @@ int near_uniform_route(qmcp_hip_ctx* c, const HeadFacts& h, bool& done) {
     return close_solve(c);
 }
 
-// a mixed sweep's stretch table (null: one wave per contig)
-struct Stretches {
-    const uint32_t* seg = nullptr;
-    uint32_t n_seg_max = 0, windows = 0;
-};
-
 // The mixed sweep for spans the LDS-cached walk takes: run lengths, then the register-resident walk (spans up to 448;
-// speculative boundaries where the plan asks for them) or the cached one.
-int mixed_sweep_cached(qmcp_hip_ctx* c, const HeadFacts& h, const SortedReads& s, qmcp::MixedSweepPlan plan, const Stretches& z) {
+// speculative boundaries where the plan asks for them) or the cached one.  ax: the axis, under the exact table if any.
+int mixed_sweep_cached(qmcp_hip_ctx* c, const HeadFacts& h, const SortedReads& s, qmcp::MixedSweepPlan plan,
+                       const qmcp::SweepAxis& ax) {
     SolveRun& run = c->run;
-    const uint32_t n = (uint32_t)run.pr.n, ltot = (uint32_t)run.pr.ltot, n_contigs = run.n_contigs, M = run.M;
+    const uint32_t n = (uint32_t)run.pr.n, n_contigs = run.n_contigs, M = run.M;
     const uint32_t max_span = h.max_span;
     TRY(queue_run_lengths(c, n, s));
     if (plan.sample_span_mode) {
@@ -191,36 +186,30 @@ int mixed_sweep_cached(qmcp_hip_ctx* c, const HeadFacts& h, const SortedReads& s
         for (uint32_t k = 0; k < n_contigs; ++k) longest = run.lengths[k] > longest ? run.lengths[k] : longest;
         plan = qmcp::refine_mixed_with_span_sample(c->opt, plan, share, longest);
     }
-    const void* sorted = c->keys[s.k].p;
+    const qmcp::SortedSpans reads{s.wide, c->keys[s.k].p, c->next_head.u32(), s.span_bits, max_span};
+    const qmcp::SweepDemand demand{c->eoff.u32(), false};
     if (!plan.speculate) {
         uint32_t ring = 64;
         while (ring < max_span + 64) ring <<= 1;  // 64 buckets enter per chunk
         KernelSpan sp(c, plan.in_regs ? "k_sweep_general_reg" : "k_sweep_general_cached");
-        if (!plan.in_regs ||
-            !qmcp::launch_sweep_general_reg(c->stream, s.wide, c->boff.u32(), c->eoff.u32(), sorted, c->next_head.u32(),
-                                            c->poff.u64(), n_contigs, s.span_bits, max_span, M, c->selend.u32(), z.seg, z.n_seg_max))
-            qmcp::launch_sweep_general_cached(c->stream, s.wide, c->boff.u32(), c->eoff.u32(), sorted, c->next_head.u32(),
-                                              c->poff.u64(), n_contigs, s.span_bits, max_span, M, c->selend.u32(), ring, z.seg,
-                                              z.n_seg_max);
+        if (!plan.in_regs || !qmcp::launch_sweep_general_reg(ax, reads, demand, M, c->selend.u32()))
+            qmcp::launch_sweep_general_cached(ax, reads, demand.per_position, M, c->selend.u32(), ring);
         return QMCP_OK;
     }
-    TRY(ensure(c, c->specsnap, qmcp::spec_snap_bytes(z.n_seg_max)));
+    TRY(ensure(c, c->specsnap, qmcp::spec_snap_bytes(ax.n_seg_max)));
     TRY(speculative_sweep(
-        c, c->stream, n_contigs, ltot, z.windows, max_span, plan.round_to, plan.burn_blocks, plan.run_ins_apart, z.seg,
-        "k_sweep_general_reg",
-        [&](const uint32_t* table, uint32_t* out_odd, const uint32_t* redo_in) {
-            return qmcp::launch_sweep_general_reg(c->stream, s.wide, c->boff.u32(), c->eoff.u32(), sorted, c->next_head.u32(),
-                                                  c->poff.u64(), n_contigs, s.span_bits, max_span, M, c->selend.u32(), table,
-                                                  z.n_seg_max, out_odd, redo_in, c->specsnap.u32());
+        c, ax, max_span, plan.round_to, plan.burn_blocks, plan.run_ins_apart, "k_sweep_general_reg",
+        [&](const qmcp::SweepAxis& tier, uint32_t* out_odd, const uint32_t* redo_in) {
+            return qmcp::launch_sweep_general_reg(tier, reads, demand, M, c->selend.u32(), out_odd, redo_in, c->specsnap.u32());
         },
-        [&](const uint32_t* table, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
-            qmcp::launch_spec_verify_merge_mixed(c->stream, table, z.n_seg_max, max_span, c->selend.u32(), c->cstart.u32(),
-                                                 c->specsnap.u32(), mismatches, redo_in, redo_out);
+        [&](const qmcp::SweepAxis& tier, uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
+            qmcp::launch_spec_verify_merge_mixed(tier, max_span, c->selend.u32(), c->cstart.u32(), c->specsnap.u32(),
+                                                 mismatches, redo_in, redo_out);
         }));
     // stats.sweep_stretches: the first tier's table
     HIP_TRY(hipMemcpyAsync(qmcp::words::sweep_iters(c->scalars.p) + qmcp::words::kStretches,
-                           c->segs.u32() + z.windows + (1 + 5 * (size_t)z.n_seg_max), sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                           c->stream));
+                           c->segs.u32() + qmcp::sweep_segment_table_offset(n_contigs, ax.n_seg_max - n_contigs, 1),
+                           sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     return QMCP_OK;
 }
 
@@ -233,24 +222,21 @@ int mixed_sweep(qmcp_hip_ctx* c, const HeadFacts& h, const SortedReads& s, bool&
     const bool in_regs = h.max_span + 64 <= 512 && !c->opt.mixed_sweep_in_lds;
     const qmcp::MixedSweepPlan plan = qmcp::plan_mixed_sweep(c->opt, n, h.max_span, ltot, n_contigs, M, in_regs,
                                                              c->mem.spec_hopeless == Shape{run.n64, run.pr.ltot, M});
-    Stretches z;
-    z.windows = plan.windows;
-    if (z.windows != 0) {
+    qmcp::SweepAxis ax{c->stream, c->boff.u32(), c->poff.u64(), n_contigs, ltot};
+    if (plan.windows != 0) {
         KernelSpan sp(c, "k_find_cuts");
-        z.seg = qmcp::launch_sweep_segments(c->stream, c->boff.u32(), c->eoff.u32(), c->poff.u64(), n_contigs, ltot, h.max_span,
-                                            M, z.windows, c->segs.u32());
-        z.n_seg_max = n_contigs + z.windows;
+        ax = qmcp::launch_sweep_segments(ax, c->eoff.u32(), h.max_span, M, plan.windows, c->segs.u32());
         // stats.sweep_stretches: the table's count (the uniform kernels count themselves)
-        HIP_TRY(hipMemcpyAsync(qmcp::words::sweep_iters(c->scalars.p) + qmcp::words::kStretches, z.seg, sizeof(uint32_t),
+        HIP_TRY(hipMemcpyAsync(qmcp::words::sweep_iters(c->scalars.p) + qmcp::words::kStretches, ax.seg, sizeof(uint32_t),
                                hipMemcpyDeviceToDevice, c->stream));
     }
-    whole_contigs = z.seg == nullptr;
-    if (h.max_span <= qmcp::kMaxCachedSpan) return mixed_sweep_cached(c, h, s, plan, z);
+    whole_contigs = ax.seg == nullptr;
+    if (h.max_span <= qmcp::kMaxCachedSpan) return mixed_sweep_cached(c, h, s, plan, ax);
     Rings rings;
-    TRY(sweep_rings(c, h.max_span, z.seg ? z.n_seg_max : n_contigs, rings));
+    TRY(sweep_rings(c, h.max_span, ax.workgroups(), rings));
     KernelSpan sp(c, "k_sweep_general");
-    qmcp::launch_sweep_general(c->stream, s.wide, c->boff.u32(), c->eoff.u32(), c->keys[s.k].p, c->poff.u64(), n_contigs,
-                               s.span_bits, h.max_span, M, c->selend.u32(), rings.size, z.seg, z.n_seg_max, rings.global);
+    qmcp::launch_sweep_general(ax, {s.wide, c->keys[s.k].p, nullptr, s.span_bits, h.max_span}, {c->eoff.u32(), false}, M,
+                               c->selend.u32(), rings.size, rings.global);
     return QMCP_OK;
 }
 

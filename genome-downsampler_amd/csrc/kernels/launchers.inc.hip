@@ -7,7 +7,37 @@ static inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t cap = 256 *
     return (uint32_t)g;
 }
 
-static inline uint32_t tiles_per_block_for(uint32_t n_tiles);
+uint32_t sort_tiles(uint32_t n) { return (n + kSortTile - 1) / kSortTile; }
+static inline uint32_t tiles_per_block_for(uint32_t n_tiles) {
+    // keep >= ~2048 workgroups in flight; up to 8 consecutive tiles per workgroup
+    uint32_t g = n_tiles / 2048;
+    return g < 1 ? 1 : (g > 8 ? 8 : g);
+}
+
+// A run-time integer to a compile-time one: f(std::integral_constant<int, V>{}) for the V among Vs that equals v;
+// false when none does (nothing is called).  The launchers pick their template instantiations with it.
+template <int... Vs, class F>
+static inline bool dispatch_int(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <class F>
+static inline void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// ... and the two layouts of sorted reads to the accessor the kernels take: f(SortedK64) or f(SortedRec); with the
+// values beside wide keys, f(KeysSplit64) or f(KeysRec)
+template <class F>
+static inline void dispatch_sorted(bool wide, const void* sorted, F&& f) {
+    if (wide) f(SortedK64{(const uint64_t*)sorted});
+    else f(SortedRec{(const Rec*)sorted});
+}
+template <class F>
+static inline void dispatch_keys(bool wide, const void* sorted, const uint32_t* svals, F&& f) {
+    if (wide) f(KeysSplit64{(const uint64_t*)sorted, svals});
+    else f(KeysRec{(const Rec*)sorted});
+}
+
 // row pitch, in partition passes (pairs of tiles), of the range partition's [digit][pass] count /
 // offset table
 uint32_t part_pass_pitch(uint32_t n) { return (((sort_tiles(n) + 1u) >> 1) + 3u) & ~3u; }
@@ -74,8 +104,6 @@ void launch_exclusive_scan(hipStream_t st, const uint32_t* in, uint32_t n, uint3
                        write_total ? 1 : 0);
 }
 
-uint32_t sort_tiles(uint32_t n) { return (n + kSortTile - 1) / kSortTile; }
-
 void launch_radix_hist(hipStream_t st, bool wide, const void* keys_in, uint32_t n, uint32_t shift,
                        uint32_t* hist) {
     const uint32_t n_tiles = sort_tiles(n);
@@ -103,314 +131,207 @@ void launch_radix_scatter(hipStream_t st, bool wide, const void* keys_in, const 
                            (uint32_t*)keys_out, vals_out);
 }
 
-size_t sweep_segment_words(uint32_t n_contigs, uint32_t n_windows) {
-    // the windows' cuts, then three tables (the exact one, and two with speculative boundaries): count,
-    // {start, end, contig end}, the owned-from position and the exact table's stretch per stretch
-    return (size_t)n_windows + 3 * (1 + 5 * ((size_t)n_contigs + n_windows));
-}
-// fills seg_words: [windows' cuts | count, stretches]; returns the table the sweep launchers take
-const uint32_t* launch_sweep_segments(hipStream_t st, const uint32_t* boff, const uint32_t* eoff,
-                                      const uint64_t* d_poff, uint32_t n_contigs, uint32_t ltot, uint32_t ell,
-                                      uint32_t M, uint32_t n_windows, uint32_t* seg_words, const uint32_t* other_cov) {
-    uint32_t* cut = seg_words;
-    uint32_t* seg = seg_words + n_windows;
-    const uint32_t win = (ltot + n_windows - 1) / n_windows;
-    hipLaunchKernelGGL(k_find_cuts, dim3(n_windows), dim3(256), 0, st, boff, eoff, d_poff, n_contigs, ltot, ell, M, win, cut, other_cov);
-    hipLaunchKernelGGL(k_build_segments, dim3(1), dim3(kSegThreads), 0, st, cut, n_windows, d_poff, n_contigs,
-                       ltot, win, 0u, 1u, seg, (uint32_t*)nullptr);
+// One table of seg_words ([windows' cuts | tier 0 | tier 1 | tier 2], sweep_plan.h) from the windows' cuts: the exact one
+// (tier 0, burn 0), or a tier with a boundary `burn` positions of run-in wide every `stride` windows without a cut
+static const uint32_t* launch_build_segments(const SweepAxis& ax, uint32_t n_windows, uint32_t* seg_words, uint32_t tier,
+                                             uint32_t burn, uint32_t stride, uint32_t* n_speculative) {
+    uint32_t* seg = seg_words + sweep_segment_table_offset(ax.n_contigs, n_windows, tier);
+    const uint32_t win = (ax.ltot + n_windows - 1) / n_windows;
+    hipLaunchKernelGGL(k_build_segments, dim3(1), dim3(kSegThreads), 0, ax.st, seg_words, n_windows, ax.poff, ax.n_contigs,
+                       ax.ltot, win, burn, stride, seg, n_speculative);
     return seg;
 }
-// the same windows' further tables (tier 1 or 2): speculative boundaries where a window has no cut (behind
-// the exact table in seg_words; launch_sweep_segments comes first); burn == 0 gives the exact table again
-const uint32_t* launch_sweep_segments_speculative(hipStream_t st, const uint64_t* d_poff, uint32_t n_contigs,
-                                                  uint32_t ltot, uint32_t n_windows, uint32_t burn,
+// the axis under the exact table its windows' cuts give
+static SweepAxis with_exact_segments(const SweepAxis& ax, uint32_t n_windows, uint32_t* seg_words) {
+    SweepAxis cut = ax.with_table(launch_build_segments(ax, n_windows, seg_words, 0, 0u, 1u, nullptr));
+    cut.n_seg_max = ax.n_contigs + n_windows;
+    return cut;
+}
+SweepAxis launch_sweep_segments(const SweepAxis& ax, const uint32_t* eoff, uint32_t ell, uint32_t M, uint32_t n_windows,
+                                uint32_t* seg_words, const uint32_t* other_cov) {
+    const uint32_t win = (ax.ltot + n_windows - 1) / n_windows;
+    hipLaunchKernelGGL(k_find_cuts, dim3(n_windows), dim3(256), 0, ax.st, ax.boff, eoff, ax.poff, ax.n_contigs, ax.ltot, ell,
+                       M, win, seg_words, other_cov);
+    return with_exact_segments(ax, n_windows, seg_words);
+}
+const uint32_t* launch_sweep_segments_speculative(const SweepAxis& ax, uint32_t n_windows, uint32_t burn,
                                                   uint32_t* seg_words, uint32_t* n_speculative, uint32_t run_ins_apart,
                                                   uint32_t tier) {
     // candidates this many run-ins apart at least (>= 2)
-    const uint32_t win0 = (ltot + n_windows - 1) / n_windows;
-    const uint32_t stride = (uint32_t)(((uint64_t)run_ins_apart * burn + win0 - 1) / win0);
-    const uint32_t* cut = seg_words;
-    uint32_t* seg = seg_words + n_windows + (size_t)tier * (1 + 5 * ((size_t)n_contigs + n_windows));
-    const uint32_t win = (ltot + n_windows - 1) / n_windows;
-    hipLaunchKernelGGL(k_build_segments, dim3(1), dim3(kSegThreads), 0, st, cut, n_windows, d_poff, n_contigs,
-                       ltot, win, burn, stride < 1 ? 1u : stride, seg, n_speculative);
-    return seg;
+    const uint32_t win = (ax.ltot + n_windows - 1) / n_windows;
+    const uint32_t stride = (uint32_t)(((uint64_t)run_ins_apart * burn + win - 1) / win);
+    return launch_build_segments(ax, n_windows, seg_words, tier, burn, stride < 1 ? 1u : stride, n_speculative);
 }
-size_t spec_snap_bytes(uint32_t n_cand) { return (size_t)n_cand * kSpecSnapWords * sizeof(uint32_t); }
-void launch_spec_verify_merge_mixed(hipStream_t st, const uint32_t* seg, uint32_t n_cand, uint32_t max_span,
-                                    uint32_t* out_even, const uint32_t* out_odd, const uint32_t* snap,
-                                    uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out) {
-    hipLaunchKernelGGL(k_spec_verify_mixed, dim3(n_cand), dim3(256), 0, st, seg, n_cand, max_span, out_even, out_odd, snap,
-                       kSpecSnapWords, mismatches, redo_in, redo_out);
-    hipLaunchKernelGGL(k_spec_merge_mixed, dim3(n_cand, 32), dim3(256), 0, st, seg, n_cand, max_span, out_even, out_odd,
-                       redo_in);
+void launch_spec_verify_merge_mixed(const SweepAxis& ax, uint32_t max_span, uint32_t* out_even, const uint32_t* out_odd,
+                                    const uint32_t* snap, uint32_t* mismatches, const uint32_t* redo_in,
+                                    uint32_t* redo_out) {
+    const uint32_t n_cand = ax.n_seg_max;
+    hipLaunchKernelGGL(k_spec_verify_mixed, dim3(n_cand), dim3(256), 0, ax.st, ax.seg, n_cand, max_span, out_even, out_odd,
+                       snap, kSpecSnapWords, mismatches, redo_in, redo_out);
+    hipLaunchKernelGGL(k_spec_merge_mixed, dim3(n_cand, 32), dim3(256), 0, ax.st, ax.seg, n_cand, max_span, out_even,
+                       out_odd, redo_in);
 }
-void launch_spec_verify(hipStream_t st, const uint32_t* seg, uint32_t n_cand, uint32_t ell,
-                        const uint32_t* owned, const uint32_t* run_in, uint32_t* mismatches,
-                        const uint32_t* redo_in, uint32_t* redo_out, const uint32_t* own_marks) {
-    hipLaunchKernelGGL(k_spec_verify, dim3(n_cand), dim3(256), 0, st, seg, n_cand, ell, owned, run_in, mismatches,
-                       redo_in, redo_out, own_marks);
+void launch_spec_verify(const SweepAxis& ax, uint32_t ell, const uint32_t* owned, const uint32_t* run_in,
+                        uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out, const uint32_t* own_marks) {
+    hipLaunchKernelGGL(k_spec_verify, dim3(ax.n_seg_max), dim3(256), 0, ax.st, ax.seg, ax.n_seg_max, ell, owned, run_in,
+                       mismatches, redo_in, redo_out, own_marks);
 }
 
-bool launch_sweep_uniform_mw(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
-                             uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
-                             uint32_t* selend, uint32_t* iter_stats, const uint32_t* seg, uint32_t n_seg_max) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t e = (ell + 63) / 64;
-#define QMCP_SWEEP_MW(EE)                                                                              \
-    {                                                                                                   \
-        const size_t lds = MwLayout<EE>::kBytes;                                                        \
-        (void)hipFuncSetAttribute((const void*)k_sweep_uniform_mw<EE>,                                  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-        hipLaunchKernelGGL(k_sweep_uniform_mw<EE>, dim3(n_wg), dim3(448), lds, st, boff, d_poff,       \
-                           ell, M, ltot, selend, iter_stats, seg);                                           \
-    }
-    switch (e) {
-        case 1: QMCP_SWEEP_MW(1); break;
-        case 2: QMCP_SWEEP_MW(2); break;
-        case 3: QMCP_SWEEP_MW(3); break;
-        case 4: QMCP_SWEEP_MW(4); break;
-        default: return false;  // wider spans: single-wave kernel
-    }
-#undef QMCP_SWEEP_MW
-    return true;
+// the E of the one-span kernels: 64-bit words a span's positions take
+static inline int span_words(uint32_t ell) { return (int)((ell + 63) / 64); }
+
+bool launch_sweep_uniform_mw(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* selend, uint32_t* iter_stats) {
+    return dispatch_int<1, 2, 3, 4>(span_words(ell), [&](auto e) {  // (wider spans: the single-wave kernel)
+        constexpr int E = decltype(e)::value;
+        const size_t lds = MwLayout<E>::kBytes;
+        (void)hipFuncSetAttribute((const void*)k_sweep_uniform_mw<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k_sweep_uniform_mw<E>, dim3(ax.workgroups()), dim3(448), lds, ax.st, ax.boff, ax.poff, ell, M,
+                           ax.ltot, selend, iter_stats, ax.seg);
+    });
 }
 
-bool launch_sweep_uniform_gen(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
-                              uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
-                              uint32_t* selend, uint32_t* iter_stats, const uint32_t* seg, uint32_t n_seg_max,
+bool launch_sweep_uniform_gen(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* selend, uint32_t* iter_stats,
                               uint32_t* selend_run_in, const uint32_t* redo_in, const int32_t* nadj,
                               const uint32_t* own_marks) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t e = (ell + 63) / 64;
-#define QMCP_SWEEP_GEN_K(EE, ADJ)                                                                      \
-    {                                                                                                   \
-        const size_t lds = MgLayout<EE>::kBytes;                                                        \
-        (void)hipFuncSetAttribute((const void*)k_sweep_uniform_gen<EE, ADJ>,                            \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-        hipLaunchKernelGGL((k_sweep_uniform_gen<EE, ADJ>), dim3(n_wg), dim3(448), lds, st, boff, d_poff, \
-                           ell, M, ltot, selend, iter_stats, seg, selend_run_in, redo_in, n_seg_max, nadj, own_marks);  \
-    }
-#define QMCP_SWEEP_GEN(EE)                                                                             \
-    {                                                                                                   \
-        if (nadj != nullptr) QMCP_SWEEP_GEN_K(EE, true) else QMCP_SWEEP_GEN_K(EE, false)               \
-    }
-    switch (e) {
-        case 1: QMCP_SWEEP_GEN(1); break;
-        case 2: QMCP_SWEEP_GEN(2); break;
-        case 3: QMCP_SWEEP_GEN(3); break;
-        case 4: QMCP_SWEEP_GEN(4); break;
-        default: return false;
-    }
-#undef QMCP_SWEEP_GEN
-#undef QMCP_SWEEP_GEN_K
-    return true;
+    return dispatch_int<1, 2, 3, 4>(span_words(ell), [&](auto e) {
+        dispatch_bool(nadj != nullptr, [&](auto adj) {
+            constexpr int E = decltype(e)::value;
+            auto* kernel = k_sweep_uniform_gen<E, decltype(adj)::value>;
+            const size_t lds = MgLayout<E>::kBytes;
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, dim3(ax.workgroups()), dim3(448), lds, ax.st, ax.boff, ax.poff, ell, M, ax.ltot,
+                               selend, iter_stats, ax.seg, selend_run_in, redo_in, ax.n_seg_max, nadj, own_marks);
+        });
+    });
 }
 
-uint32_t sweep_ev_pieces(uint32_t ltot, uint32_t ell, uint32_t n_wg) { return ltot / (4u * ell) + n_wg + 1; }
-size_t sweep_ev_pack_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) { return (size_t)sweep_ev_pieces(ltot, ell, n_wg) * 1024; }
-size_t sweep_ev_ckpt_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) {  // the chain's state at every 64th block
-    return ((size_t)sweep_ev_pieces(ltot, ell, n_wg) / 16 + 2 * (size_t)n_wg + 4) * 512 * sizeof(uint32_t);
-}
-size_t sweep_ev_last_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) {
-    return ((size_t)sweep_ev_pieces(ltot, ell, n_wg) * 4 + 64) * sizeof(uint32_t);
-}
 // the three launches of the event-driven form, separately (the host brackets each with events)
-#define QMCP_EV_DISPATCH(e, CALL)              \
-    switch (e) {                                \
-        case 1: { CALL(1) } break;              \
-        case 2: { CALL(2) } break;              \
-        case 3: { CALL(3) } break;              \
-        case 4: { CALL(4) } break;              \
-        default: return false;                  \
-    }
-bool launch_sweep_ev_pack(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,
-                          uint32_t ell, uint32_t M, uint32_t ltot, const uint32_t* seg, uint32_t n_seg_max,
-                          uint32_t* pk, const int32_t* nadj, const uint32_t* from) {
+bool launch_sweep_ev_pack(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* pk, const int32_t* nadj,
+                          const uint32_t* from) {
     if (!sweep_uniform_ev_supported(ell, M)) return false;
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t pieces = sweep_ev_pieces(ltot, ell, n_wg);
-#define QMCP_CALL(EE)                                                                                      \
-    hipLaunchKernelGGL(k_sweep_pack<EE>, dim3((pieces + 3) / 4), dim3(256), 0, st, boff, d_poff, n_wg, ell, \
-                       M, ltot, seg, pieces, pk, nadj, from);
-    QMCP_EV_DISPATCH((ell + 63) / 64, QMCP_CALL)
-#undef QMCP_CALL
-    return true;
+    const uint32_t n_wg = ax.workgroups(), pieces = sweep_ev_pieces(ax.ltot, ell, n_wg);
+    return dispatch_int<1, 2, 3, 4>(span_words(ell), [&](auto e) {
+        hipLaunchKernelGGL(k_sweep_pack<decltype(e)::value>, dim3((pieces + 3) / 4), dim3(256), 0, ax.st, ax.boff, ax.poff,
+                           n_wg, ell, M, ax.ltot, ax.seg, pieces, pk, nadj, from);
+    });
 }
-bool launch_sweep_ev_chain(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,
-                           uint32_t ell, uint32_t M, uint32_t ltot, const uint32_t* seg, uint32_t n_seg_max,
-                           const uint32_t* pk, uint32_t* sev, uint32_t* lastns, uint32_t* iter_stats,
-                           const int32_t* nadj, uint32_t* ckpt, const uint32_t* restart) {
+bool launch_sweep_ev_chain(const SweepAxis& ax, uint32_t ell, uint32_t M, const uint32_t* pk, uint32_t* sev,
+                           uint32_t* lastns, uint32_t* iter_stats, const int32_t* nadj, uint32_t* ckpt,
+                           const uint32_t* restart) {
     if (!sweep_uniform_ev_supported(ell, M)) return false;
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
     const size_t lds = (size_t)kEvSlots * 1024;
-#define QMCP_CALL(EE)                                                                                       \
-    (void)hipFuncSetAttribute((const void*)k_sweep_uniform_ev<EE>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                    \
-    hipLaunchKernelGGL(k_sweep_uniform_ev<EE>, dim3(n_wg), dim3(128), lds, st, boff, d_poff, n_contigs, ell,  \
-                       M, ltot, pk, sev, lastns, iter_stats, seg, nadj, ckpt, restart);
-    QMCP_EV_DISPATCH((ell + 63) / 64, QMCP_CALL)
-#undef QMCP_CALL
-    return true;
+    return dispatch_int<1, 2, 3, 4>(span_words(ell), [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        (void)hipFuncSetAttribute((const void*)k_sweep_uniform_ev<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k_sweep_uniform_ev<E>, dim3(ax.workgroups()), dim3(128), lds, ax.st, ax.boff, ax.poff,
+                           ax.n_contigs, ell, M, ax.ltot, pk, sev, lastns, iter_stats, ax.seg, nadj, ckpt, restart);
+    });
 }
-bool launch_sweep_ev_expand(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,
-                            uint32_t ell, uint32_t M, uint32_t ltot, const uint32_t* seg, uint32_t n_seg_max,
-                            const uint32_t* sev, const uint32_t* lastns, uint32_t* selend, const uint32_t* from) {
+bool launch_sweep_ev_expand(const SweepAxis& ax, uint32_t ell, uint32_t M, const uint32_t* sev, const uint32_t* lastns,
+                            uint32_t* selend, const uint32_t* from) {
     if (!sweep_uniform_ev_supported(ell, M)) return false;
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t pieces = sweep_ev_pieces(ltot, ell, n_wg);
-#define QMCP_CALL(EE)                                                                                    \
-    hipLaunchKernelGGL(k_sweep_expand<EE>, dim3(pieces), dim3(256), 0, st, boff, d_poff, n_wg, ell, ltot, \
-                       seg, pieces, sev, lastns, selend, from);
-    QMCP_EV_DISPATCH((ell + 63) / 64, QMCP_CALL)
-#undef QMCP_CALL
-    return true;
-}
-#undef QMCP_EV_DISPATCH
-
-bool launch_sweep_uniform(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
-                          uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
-                          uint32_t* selend, uint32_t* iter_stats, const uint32_t* seg, uint32_t n_seg_max) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t e = (ell + 63) / 64;
-#define QMCP_SWEEP(EE)                                                                          \
-    hipLaunchKernelGGL(k_sweep_uniform<EE>, dim3(n_wg), dim3(64), 0, st, boff, d_poff, ell, \
-                       M, ltot, selend, iter_stats, seg)
-    switch (e) {
-        case 1: QMCP_SWEEP(1); break;
-        case 2: QMCP_SWEEP(2); break;
-        case 3: QMCP_SWEEP(3); break;
-        case 4: QMCP_SWEEP(4); break;
-        case 5: QMCP_SWEEP(5); break;
-        case 6: QMCP_SWEEP(6); break;
-        case 7: QMCP_SWEEP(7); break;
-        case 8: QMCP_SWEEP(8); break;
-        default: return false;
-    }
-#undef QMCP_SWEEP
-    return true;
+    const uint32_t n_wg = ax.workgroups(), pieces = sweep_ev_pieces(ax.ltot, ell, n_wg);
+    return dispatch_int<1, 2, 3, 4>(span_words(ell), [&](auto e) {
+        hipLaunchKernelGGL(k_sweep_expand<decltype(e)::value>, dim3(pieces), dim3(256), 0, ax.st, ax.boff, ax.poff, n_wg, ell,
+                           ax.ltot, ax.seg, pieces, sev, lastns, selend, from);
+    });
 }
 
-void launch_sweep_general(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* eoff,
-                          const void* sorted, const uint64_t* d_poff, uint32_t n_contigs,
-                          uint32_t span_bits, uint32_t max_span, uint32_t M, uint32_t* selend,
-                          uint32_t ring_size, const uint32_t* seg, uint32_t n_seg_max, uint32_t* g_rings) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
+bool launch_sweep_uniform(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* selend, uint32_t* iter_stats) {
+    return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(span_words(ell), [&](auto e) {
+        hipLaunchKernelGGL(k_sweep_uniform<decltype(e)::value>, dim3(ax.workgroups()), dim3(64), 0, ax.st, ax.boff, ax.poff,
+                           ell, M, ax.ltot, selend, iter_stats, ax.seg);
+    });
+}
+
+void launch_sweep_general(const SweepAxis& ax, const SortedSpans& reads, SweepDemand demand, uint32_t M, uint32_t* selend,
+                          uint32_t ring_size, uint32_t* g_rings) {
     // rings in LDS while they fit (two of ring_size words); beyond that in g_rings (2 * ring_size words
     // per workgroup)
     const size_t lds = g_rings ? 0 : 2 * (size_t)ring_size * sizeof(uint32_t);
-#define QMCP_SWEEP_GENERAL(SORTED, ARG, GRING)                                                          \
-    {                                                                                                   \
-        (void)hipFuncSetAttribute((const void*)k_sweep_general<SORTED, GRING>,                          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-        hipLaunchKernelGGL((k_sweep_general<SORTED, GRING>), dim3(n_wg), dim3(64), lds, st, boff, eoff, \
-                           ARG, d_poff, span_bits, max_span, M, selend, ring_size, seg, g_rings);       \
-    }
-    if (wide) {
-        if (g_rings) QMCP_SWEEP_GENERAL(SortedK64, SortedK64{(const uint64_t*)sorted}, true)
-        else QMCP_SWEEP_GENERAL(SortedK64, SortedK64{(const uint64_t*)sorted}, false)
-    } else {
-        if (g_rings) QMCP_SWEEP_GENERAL(SortedRec, SortedRec{(const Rec*)sorted}, true)
-        else QMCP_SWEEP_GENERAL(SortedRec, SortedRec{(const Rec*)sorted}, false)
-    }
-#undef QMCP_SWEEP_GENERAL
+    if (demand.capped) M = 0;
+    auto launch = [&](auto keys, auto gring, auto capped) {
+        auto* kernel = k_sweep_general<decltype(keys), decltype(gring)::value, decltype(capped)::value>;
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(ax.workgroups()), dim3(64), lds, ax.st, ax.boff, demand.per_position, keys, ax.poff,
+                           reads.span_bits, reads.max_span, M, selend, ring_size, ax.seg, g_rings);
+    };
+    dispatch_sorted(reads.wide, reads.sorted, [&](auto keys) {
+        dispatch_bool(g_rings != nullptr, [&](auto gring) {
+            dispatch_bool(demand.capped, [&](auto capped) { launch(keys, gring, capped); });
+        });
+    });
 }
 
 void launch_group_heads(hipStream_t st, bool wide, const void* sorted, uint32_t n,
                         uint32_t* next_head) {
-    if (wide)
-        hipLaunchKernelGGL(k_group_heads<SortedK64>, dim3(grid_for((uint64_t)n + 1, 256)), dim3(256), 0, st,
-                           SortedK64{(const uint64_t*)sorted}, n, next_head);
-    else
-        hipLaunchKernelGGL(k_group_heads<SortedRec>, dim3(grid_for((uint64_t)n + 1, 256)), dim3(256), 0, st,
-                           SortedRec{(const Rec*)sorted}, n, next_head);
+    dispatch_sorted(wide, sorted, [&](auto keys) {
+        hipLaunchKernelGGL(k_group_heads<decltype(keys)>, dim3(grid_for((uint64_t)n + 1, 256)), dim3(256), 0, st, keys, n,
+                           next_head);
+    });
 }
 
-void launch_sweep_general_cached(hipStream_t st, bool wide, const uint32_t* boff,
-                                 const uint32_t* eoff, const void* sorted, const uint32_t* next_head,
-                                 const uint64_t* d_poff, uint32_t n_contigs, uint32_t span_bits,
-                                 uint32_t max_span, uint32_t M, uint32_t* selend, uint32_t ring,
-                                 const uint32_t* seg, uint32_t n_seg_max) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
+void launch_sweep_general_cached(const SweepAxis& ax, const SortedSpans& reads, const uint32_t* eoff, uint32_t M,
+                                 uint32_t* selend, uint32_t ring) {
     const size_t lds = (size_t)GenSlots::kWords * ring * sizeof(uint32_t);
-    if (wide) {
-        (void)hipFuncSetAttribute((const void*)k_sweep_general_cached<SortedK64>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_sweep_general_cached<SortedK64>, dim3(n_wg), dim3(64), lds, st, boff,
-                           eoff, SortedK64{(const uint64_t*)sorted}, next_head, d_poff, span_bits,
-                           max_span, M, selend, ring, seg);
-    } else {
-        (void)hipFuncSetAttribute((const void*)k_sweep_general_cached<SortedRec>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_sweep_general_cached<SortedRec>, dim3(n_wg), dim3(64), lds, st, boff,
-                           eoff, SortedRec{(const Rec*)sorted}, next_head, d_poff, span_bits, max_span,
-                           M, selend, ring, seg);
-    }
+    dispatch_sorted(reads.wide, reads.sorted, [&](auto keys) {
+        auto* kernel = k_sweep_general_cached<decltype(keys)>;
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(ax.workgroups()), dim3(64), lds, ax.st, ax.boff, eoff, keys, reads.next_head, ax.poff,
+                           reads.span_bits, reads.max_span, M, selend, ring, ax.seg);
+    });
 }
 
 // register-resident event sweep: buckets per lane B = ceil((max_span + 64) / 64), up to 8
-bool launch_sweep_general_reg(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* eoff,
-                              const void* sorted, const uint32_t* next_head, const uint64_t* d_poff,
-                              uint32_t n_contigs, uint32_t span_bits, uint32_t max_span, uint32_t M,
-                              uint32_t* selend, const uint32_t* seg, uint32_t n_seg_max,
-                              uint32_t* selend_odd, const uint32_t* redo_in, uint32_t* snap) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t b = (max_span + 64 + 63) / 64;
-#ifdef QMCP_GEN_STAMP
-#define QMCP_GEN_STAMP_ARG , (unsigned long long*)nullptr
-#else
-#define QMCP_GEN_STAMP_ARG
-#endif
-#define QMCP_GEN_REG_K(BB, KK)                                                                        \
-    if (wide)                                                                                          \
-        hipLaunchKernelGGL((k_sweep_general_reg<SortedK64, BB, KK>), dim3(n_wg), dim3(64 * (1 + KK)), 0, st, boff, \
-                           eoff, SortedK64{(const uint64_t*)sorted}, next_head, d_poff, span_bits,    \
-                           max_span, M, selend, seg, selend_odd, redo_in, n_seg_max, snap QMCP_GEN_STAMP_ARG); \
-    else                                                                                               \
-        hipLaunchKernelGGL((k_sweep_general_reg<SortedRec, BB, KK>), dim3(n_wg), dim3(64 * (1 + KK)), 0, st, boff, \
-                           eoff, SortedRec{(const Rec*)sorted}, next_head, d_poff, span_bits, max_span, \
-                           M, selend, seg, selend_odd, redo_in, n_seg_max, snap QMCP_GEN_STAMP_ARG);
+bool launch_sweep_general_reg(const SweepAxis& ax, const SortedSpans& reads, SweepDemand demand, uint32_t M,
+                              uint32_t* selend, uint32_t* selend_odd, const uint32_t* redo_in, uint32_t* snap) {
+    const uint32_t n_wg = ax.workgroups();
+    const uint32_t b = (reads.max_span + 64 + 63) / 64;
+    const int buckets = b <= 2 ? 2 : b == 5 ? 6 : b == 7 ? 8 : (int)b;  // instantiated for 2, 3, 4, 6 and 8
     // loader waves per walker: few workgroups (contigs) -> many loaders, so the walker never waits for an
     // entering chunk's three trips to memory; many workgroups (stretches) fill the chip by themselves
     // and extra waves only get in the walkers' way
-    int loaders = n_wg <= 64 ? 4 : 1;  // (769 stretches, cfg3-like mix: 1 loader 2.52 ms, 8 loaders 4.92 ms; one contig: 1.19 vs 1.09 ms)
-#define QMCP_GEN_REG(BB)                                                                              \
-    if (loaders >= 8) { QMCP_GEN_REG_K(BB, 8) }                                                        \
-    else if (loaders >= 4) { QMCP_GEN_REG_K(BB, 4) }                                                   \
-    else if (loaders >= 2) { QMCP_GEN_REG_K(BB, 2) }                                                   \
-    else { QMCP_GEN_REG_K(BB, 1) }
-    if (b <= 2) { QMCP_GEN_REG(2) }
-    else if (b == 3) { QMCP_GEN_REG(3) }
-    else if (b == 4) { QMCP_GEN_REG(4) }
-    else if (b <= 6) { QMCP_GEN_REG(6) }
-    else if (b <= 8) { QMCP_GEN_REG(8) }
-    else return false;
-#undef QMCP_GEN_REG
-#undef QMCP_GEN_REG_K
-#undef QMCP_GEN_STAMP_ARG
-    return true;
+    const int loaders = n_wg <= 64 ? 4 : 1;  // (769 stretches, cfg3-like mix: 1 loader 2.52 ms, 8 loaders 4.92 ms; one contig: 1.19 vs 1.09 ms)
+    if (demand.capped) M = 0;
+    auto launch = [&](auto keys, auto bb, auto kk, auto capped, auto... stamps) {
+        constexpr int B = decltype(bb)::value, K = decltype(kk)::value;
+        hipLaunchKernelGGL((k_sweep_general_reg<decltype(keys), B, K, decltype(capped)::value>), dim3(n_wg),
+                           dim3(64 * (1 + K)), 0, ax.st, ax.boff, demand.per_position, keys, reads.next_head, ax.poff,
+                           reads.span_bits, reads.max_span, M, selend, ax.seg, selend_odd, redo_in, ax.n_seg_max, snap,
+                           stamps...);
+    };
+    bool taken = false;
+    dispatch_sorted(reads.wide, reads.sorted, [&](auto keys) {
+        taken = dispatch_int<2, 3, 4, 6, 8>(buckets, [&](auto bb) {
+            dispatch_int<1, 4>(loaders, [&](auto kk) {
+                dispatch_bool(demand.capped, [&](auto capped) {
+#ifdef QMCP_GEN_STAMP
+                    launch(keys, bb, kk, capped, (unsigned long long*)nullptr);  // (lab builds: the kernel's stamps)
+#else
+                    launch(keys, bb, kk, capped);
+#endif
+                });
+            });
+        });
+    });
+    return taken;
 }
 
 void launch_mark(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals, uint32_t ltot,
                  const uint32_t* boff, const uint32_t* selend, uint64_t* mask,
                  unsigned long long* n_kept) {
-    if (wide)
-        hipLaunchKernelGGL(k_mark<KeysSplit64>, dim3(grid_for(ltot, 256)), dim3(256), 0, st,
-                           KeysSplit64{(const uint64_t*)sorted, svals}, ltot, boff, selend,
+    dispatch_keys(wide, sorted, svals, [&](auto keys) {
+        hipLaunchKernelGGL(k_mark<decltype(keys)>, dim3(grid_for(ltot, 256)), dim3(256), 0, st, keys, ltot, boff, selend,
                            (uint32_t*)mask, n_kept);
-    else
-        hipLaunchKernelGGL(k_mark<KeysRec>, dim3(grid_for(ltot, 256)), dim3(256), 0, st,
-                           KeysRec{(const Rec*)sorted}, ltot, boff, selend, (uint32_t*)mask, n_kept);
+    });
 }
 
 void launch_bucket_heads(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals,
                          uint32_t n, uint32_t span_bits, uint32_t ltot, uint32_t* boff) {
-    if (wide)
-        hipLaunchKernelGGL(k_bucket_heads<KeysSplit64>, dim3(grid_for(n, 256)), dim3(256), 0, st,
-                           KeysSplit64{(const uint64_t*)sorted, svals}, n, span_bits, ltot, boff);
-    else
-        hipLaunchKernelGGL(k_bucket_heads<KeysRec>, dim3(grid_for(n, 256)), dim3(256), 0, st,
-                           KeysRec{(const Rec*)sorted}, n, span_bits, ltot, boff);
+    dispatch_keys(wide, sorted, svals, [&](auto keys) {
+        hipLaunchKernelGGL(k_bucket_heads<decltype(keys)>, dim3(grid_for(n, 256)), dim3(256), 0, st, keys, n, span_bits, ltot,
+                           boff);
+    });
 }
 
 void launch_reverse_min_scan(hipStream_t st, uint32_t* data, uint32_t n, uint32_t* spine) {
@@ -419,12 +340,6 @@ void launch_reverse_min_scan(hipStream_t st, uint32_t* data, uint32_t n, uint32_
     hipLaunchKernelGGL(k_rmin_tile_mins, dim3(n_tiles), dim3(kScanThreads), 0, st, data, n, spine);
     hipLaunchKernelGGL(k_rmin_spine, dim3(1), dim3(kScanThreads), 0, st, spine, n_tiles);
     hipLaunchKernelGGL(k_rmin_tiles, dim3(n_tiles), dim3(kScanThreads), 0, st, data, n, spine);
-}
-
-static inline uint32_t tiles_per_block_for(uint32_t n_tiles) {
-    // keep >= ~2048 workgroups in flight; up to 8 consecutive tiles per workgroup
-    uint32_t g = n_tiles / 2048;
-    return g < 1 ? 1 : (g > 8 ? 8 : g);
 }
 
 void launch_radix_hist_rec(hipStream_t st, bool first, const uint32_t* keys, const void* recs,
@@ -538,33 +453,11 @@ void launch_partition_level2(hipStream_t st, const void* recs_in, uint32_t n, ui
     hipLaunchKernelGGL(k_seg_range_table, dim3(256), dim3(256), 0, st, hist, seg, n, range_start, max_load);
 }
 
-// global start position per read (what k_prepare writes when asked to): for the routes that need
-// the bare keys after a call that did not ask for them
-__global__ __launch_bounds__(256) void k_gstart(const uint32_t* __restrict__ starts, uint32_t n,
-                                               const uint64_t* __restrict__ contig_read_off,
-                                               const uint64_t* __restrict__ contig_pos_off,
-                                               uint32_t n_contigs, uint32_t* __restrict__ gstart) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t lo = 0, hi = n_contigs;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (contig_read_off[mid] <= i) lo = mid; else hi = mid;
-        }
-        gstart[i] = (uint32_t)contig_pos_off[lo] + starts[i];
-    }
-}
 void launch_gstart(hipStream_t st, const uint32_t* starts, uint32_t n, const uint64_t* d_roff,
                    const uint64_t* d_poff, uint32_t n_contigs, uint32_t* gstart) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_gstart, dim3(grid_for(n, 256)), dim3(256), 0, st, starts, n, d_roff, d_poff,
                        n_contigs, gstart);
-}
-// ends of reads that all have one span (the 64-bit host entry then sends the starts only)
-__global__ __launch_bounds__(256) void k_fill_ends(const uint32_t* __restrict__ starts, uint32_t n,
-                                                  uint32_t span_minus_1, uint32_t* __restrict__ ends) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) ends[i] = starts[i] + span_minus_1;
 }
 void launch_fill_ends(hipStream_t st, const uint32_t* starts, uint32_t n, uint32_t span_minus_1, uint32_t* ends) {
     if (n == 0) return;

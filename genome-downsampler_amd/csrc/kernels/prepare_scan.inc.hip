@@ -479,3 +479,26 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_tiles(const uint32_t* __r
     }
     if (write_total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = spine[gridDim.x];
 }
+
+// global start position per read (what k_prepare writes when asked to): for the routes that need
+// the bare keys after a call that did not ask for them
+__global__ __launch_bounds__(256) void k_gstart(const uint32_t* __restrict__ starts, uint32_t n,
+                                               const uint64_t* __restrict__ contig_read_off,
+                                               const uint64_t* __restrict__ contig_pos_off,
+                                               uint32_t n_contigs, uint32_t* __restrict__ gstart) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t lo = 0, hi = n_contigs;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (contig_read_off[mid] <= i) lo = mid; else hi = mid;
+        }
+        gstart[i] = (uint32_t)contig_pos_off[lo] + starts[i];
+    }
+}
+// ends of reads that all have one span (the 64-bit host entry then sends the starts only)
+__global__ __launch_bounds__(256) void k_fill_ends(const uint32_t* __restrict__ starts, uint32_t n,
+                                                  uint32_t span_minus_1, uint32_t* __restrict__ ends) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) ends[i] = starts[i] + span_minus_1;
+}

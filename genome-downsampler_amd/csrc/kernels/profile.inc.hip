@@ -5,7 +5,7 @@
 //   k_profile_cuts   k_find_cuts' window scan reading that bit instead of comparing with M; the same cut[] array, so
 //                    k_build_segments and the stretch tables are reused as they are
 // The capped forms of the mixed-span sweeps (kernels/sweep_mixed.inc.hip, kCapped) read need[] where the scalar
-// forms compute min(cov, M).
+// forms compute min(cov, M); launch_sweep_general and launch_sweep_general_reg launch both (SweepDemand).
 
 constexpr uint32_t kProfileLdsMax = 4096;  // regions staged in LDS (3 x 4 096 words = 48 KiB); above that they stay in L2
 constexpr uint32_t kNeedCutBit = 0x80000000u;
@@ -168,77 +168,9 @@ void launch_profile_need(hipStream_t st, const uint32_t* boff, const uint32_t* e
 }
 
 // launch_sweep_segments for a profile: fills seg_words ([windows' cuts | count, stretches]) from need's cut bits
-const uint32_t* launch_profile_segments(hipStream_t st, const uint32_t* need, const uint64_t* d_poff, uint32_t n_contigs,
-                                        uint32_t ltot, uint32_t n_windows, uint32_t* seg_words) {
-    uint32_t* cut = seg_words;
-    uint32_t* seg = seg_words + n_windows;
-    const uint32_t win = (ltot + n_windows - 1) / n_windows;
-    hipLaunchKernelGGL(k_profile_cuts, dim3(n_windows), dim3(256), 0, st, need, d_poff, n_contigs, ltot, win, cut);
-    hipLaunchKernelGGL(k_build_segments, dim3(1), dim3(kSegThreads), 0, st, cut, n_windows, d_poff, n_contigs, ltot, win, 0u,
-                       1u, seg, (uint32_t*)nullptr);
-    return seg;
-}
-
-// The capped forms of the two mixed-span sweeps a profile call takes (need[] in the place of eoff, M unused): the
-// register-resident walk for spans up to 448 (false beyond), the plain walk for everything longer, rings in LDS or in
-// g_rings as launch_sweep_general places them.
-bool launch_sweep_general_reg_capped(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* need,
-                                     const void* sorted, const uint32_t* next_head, const uint64_t* d_poff,
-                                     uint32_t n_contigs, uint32_t span_bits, uint32_t max_span, uint32_t* selend,
-                                     const uint32_t* seg, uint32_t n_seg_max) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const uint32_t b = (max_span + 64 + 63) / 64;
-    uint32_t* const none = nullptr;
-    const uint32_t* const no_redo = nullptr;
-#ifdef QMCP_GEN_STAMP
-#define QMCP_GEN_STAMP_ARG , (unsigned long long*)nullptr
-#else
-#define QMCP_GEN_STAMP_ARG
-#endif
-#define QMCP_CAP_REG_K(BB, KK)                                                                                            \
-    if (wide)                                                                                                             \
-        hipLaunchKernelGGL((k_sweep_general_reg<SortedK64, BB, KK, true>), dim3(n_wg), dim3(64 * (1 + KK)), 0, st, boff,  \
-                           need, SortedK64{(const uint64_t*)sorted}, next_head, d_poff, span_bits, max_span, 0u, selend,  \
-                           seg, none, no_redo, n_seg_max, none QMCP_GEN_STAMP_ARG);                                       \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((k_sweep_general_reg<SortedRec, BB, KK, true>), dim3(n_wg), dim3(64 * (1 + KK)), 0, st, boff,  \
-                           need, SortedRec{(const Rec*)sorted}, next_head, d_poff, span_bits, max_span, 0u, selend, seg,  \
-                           none, no_redo, n_seg_max, none QMCP_GEN_STAMP_ARG);
-    // loader waves per walker as launch_sweep_general_reg chooses them
-#define QMCP_CAP_REG(BB)                     \
-    if (n_wg <= 64) { QMCP_CAP_REG_K(BB, 4) } \
-    else { QMCP_CAP_REG_K(BB, 1) }
-    if (b <= 2) { QMCP_CAP_REG(2) }
-    else if (b == 3) { QMCP_CAP_REG(3) }
-    else if (b == 4) { QMCP_CAP_REG(4) }
-    else if (b <= 6) { QMCP_CAP_REG(6) }
-    else if (b <= 8) { QMCP_CAP_REG(8) }
-    else return false;
-#undef QMCP_CAP_REG
-#undef QMCP_CAP_REG_K
-#undef QMCP_GEN_STAMP_ARG
-    return true;
-}
-
-void launch_sweep_general_capped(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* need, const void* sorted,
-                                 const uint64_t* d_poff, uint32_t n_contigs, uint32_t span_bits, uint32_t max_span,
-                                 uint32_t* selend, uint32_t ring_size, const uint32_t* seg, uint32_t n_seg_max,
-                                 uint32_t* g_rings) {
-    const uint32_t n_wg = seg ? n_seg_max : n_contigs;
-    const size_t lds = g_rings ? 0 : 2 * (size_t)ring_size * sizeof(uint32_t);
-#define QMCP_SWEEP_CAPPED(SORTED, ARG, GRING)                                                                    \
-    {                                                                                                            \
-        (void)hipFuncSetAttribute((const void*)k_sweep_general<SORTED, GRING, true>,                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        hipLaunchKernelGGL((k_sweep_general<SORTED, GRING, true>), dim3(n_wg), dim3(64), lds, st, boff, need,    \
-                           ARG, d_poff, span_bits, max_span, 0u, selend, ring_size, seg, g_rings);               \
-    }
-    if (wide) {
-        if (g_rings) QMCP_SWEEP_CAPPED(SortedK64, SortedK64{(const uint64_t*)sorted}, true)
-        else QMCP_SWEEP_CAPPED(SortedK64, SortedK64{(const uint64_t*)sorted}, false)
-    } else {
-        if (g_rings) QMCP_SWEEP_CAPPED(SortedRec, SortedRec{(const Rec*)sorted}, true)
-        else QMCP_SWEEP_CAPPED(SortedRec, SortedRec{(const Rec*)sorted}, false)
-    }
-#undef QMCP_SWEEP_CAPPED
+SweepAxis launch_profile_segments(const SweepAxis& ax, const uint32_t* need, uint32_t n_windows, uint32_t* seg_words) {
+    const uint32_t win = (ax.ltot + n_windows - 1) / n_windows;
+    hipLaunchKernelGGL(k_profile_cuts, dim3(n_windows), dim3(256), 0, ax.st, need, ax.poff, ax.n_contigs, ax.ltot, win,
+                       seg_words);
+    return with_exact_segments(ax, n_windows, seg_words);
 }

@@ -353,8 +353,6 @@ __device__ __forceinline__ uint32_t reg_sweep_key(uint32_t gx, uint32_t gy, uint
     return gy != 0 ? (((gx - pbase) << 16) | (qrel << 7) | min(gy, 127u)) : 0u;
 }
 
-static constexpr uint32_t kSpecSnapWords = 512;  // >= the register sweep's window of live buckets
-
 // kCapped: as in k_sweep_general -- `eoff` is the profile's need[] array, read by the loader waves.
 template <typename Sorted, int B, int kRegLoaders, bool kCapped = false>
 __global__ __launch_bounds__(64 * (1 + kRegLoaders)) void k_sweep_general_reg(

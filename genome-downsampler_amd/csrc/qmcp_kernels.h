@@ -44,112 +44,114 @@ void launch_radix_hist(hipStream_t st, bool wide, const void* keys_in, uint32_t 
 void launch_radix_scatter(hipStream_t st, bool wide, const void* keys_in, const uint32_t* vals_in,
                           uint32_t n, uint32_t shift, const uint32_t* offs, void* keys_out,
                           uint32_t* vals_out);
-// Cut points (coverage <= M) split a contig's sweep exactly.  sweep_segment_windows (sweep_plan.h): how many
-// windows to look for cuts in (0: not worth it); launch_sweep_segments fills `seg_words`
-// (sweep_segment_words() uint32) and returns the stretch table the sweep launchers take as `seg`
-// together with n_seg_max = n_contigs + n_windows workgroups (null: one workgroup per contig).
 // row pitch, in partition passes (pairs of 4096-read tiles), of the range partition's [digit][pass]
 // table (k_prepare writes it, one plain scan over 256 * pitch entries turns it into offsets, the
 // partition reads it)
 uint32_t part_pass_pitch(uint32_t n);
-size_t sweep_segment_words(uint32_t n_contigs, uint32_t n_windows);
-// eoff: prefix counts of read ends for mixed spans (coverage = starts - ends); null for one span ell
-const uint32_t* launch_sweep_segments(hipStream_t st, const uint32_t* boff, const uint32_t* eoff,
-                                      const uint64_t* d_poff, uint32_t n_contigs, uint32_t ltot, uint32_t ell,
-                                      uint32_t M, uint32_t n_windows, uint32_t* seg_words,
-                                      const uint32_t* other_cov = nullptr /* reads outside boff covering position q - 1:
-                                          other_cov[q] (the near-uniform route's exceptions) */);
-// the same pipeline with every block in the general form (sparse data: the fast form rarely holds)
-// selend_run_in (or null): speculative tables -- a stretch's run-in is stored there, what it owns in selend;
-// redo_in (or null): a later tier -- only stretches whose exact stretch is marked there do anything
-bool launch_sweep_uniform_gen(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
-                              uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
-                              uint32_t* selend, uint32_t* iter_stats, const uint32_t* seg,
-                              uint32_t n_seg_max, uint32_t* selend_run_in = nullptr,
-                              const uint32_t* redo_in = nullptr,
-                              const int32_t* nadj = nullptr /* near-uniform route: need(p) += nadj[p], capped at the
-                                                               swept reads' coverage (ltot + 1 entries) */,
-                              const uint32_t* own_marks = nullptr /* per stretch of `seg`: 0 = leave its output alone */);
+
+// ------------------------------------------------------------------ the sweeps
+// Where a sweep runs: the stream, the bucket offsets of the reads it sweeps, the contigs on the global axis, and the
+// stretch table -- null: one workgroup per contig; else launch_sweep_segments' (or a speculative tier's), with a
+// workgroup for each of its n_seg_max = n_contigs + windows candidate stretches.  Built once per solve; every
+// launch_sweep_* and launch_spec_* takes it first, then what is its own.
+struct SweepAxis {
+    hipStream_t st;
+    const uint32_t* boff;
+    const uint64_t* poff;
+    uint32_t n_contigs, ltot;
+    const uint32_t* seg = nullptr;
+    uint32_t n_seg_max = 0;
+    uint32_t workgroups() const { return seg ? n_seg_max : n_contigs; }
+    // the same axis under another table of the same windows (the speculative tiers)
+    SweepAxis with_table(const uint32_t* table) const {
+        SweepAxis a = *this;
+        a.seg = table;
+        return a;
+    }
+};
+// The sorted reads a mixed-span sweep walks: Rec{key, val} records (wide == false) or u64 keys, the run lengths where
+// the walk reads them (launch_group_heads; null otherwise), and the key's span field.
+struct SortedSpans {
+    bool wide;
+    const void* sorted;
+    const uint32_t* next_head;
+    uint32_t span_bits, max_span;
+};
+// What a mixed-span sweep holds the coverage against, per position: eoff, the prefix counts of read ends (coverage =
+// starts - ends) under the scalar cap M; or, capped, a profile's need[] (M is not read).
+struct SweepDemand {
+    const uint32_t* per_position;
+    bool capped;
+};
+
+// Cut points (coverage <= M) split a contig's sweep exactly.  sweep_segment_windows (sweep_plan.h): how many
+// windows to look for cuts in (0: not worth it); launch_sweep_segments fills `seg_words` (sweep_segment_words()
+// uint32: [windows' cuts | count, stretches]) and returns the axis under that table.
+// eoff: prefix counts of read ends for mixed spans; null for one span ell
+SweepAxis launch_sweep_segments(const SweepAxis& ax, const uint32_t* eoff, uint32_t ell, uint32_t M, uint32_t n_windows,
+                                uint32_t* seg_words,
+                                const uint32_t* other_cov = nullptr /* reads outside boff covering position q - 1:
+                                    other_cov[q] (the near-uniform route's exceptions) */);
 // Speculative boundaries (kernels/sweep_segments.inc.hip): further tables of the same windows (tier 1, 2
 // behind the exact one in seg_words), with a boundary `burn` positions of run-in wide wherever a window has no
 // cut (call launch_sweep_segments first; *n_speculative receives how many; burn == 0: the exact table again),
-// and the check + merge of the two outputs behind a sweep (a disagreement marks its exact stretch in
+// and the check + merge of the two outputs behind a sweep of the axis' table (a disagreement marks its exact stretch in
 // redo_out; a later tier passes the previous tier's marks as redo_in).
-const uint32_t* launch_sweep_segments_speculative(hipStream_t st, const uint64_t* d_poff, uint32_t n_contigs,
-                                                  uint32_t ltot, uint32_t n_windows, uint32_t burn,
+const uint32_t* launch_sweep_segments_speculative(const SweepAxis& ax, uint32_t n_windows, uint32_t burn,
                                                   uint32_t* seg_words, uint32_t* n_speculative,
                                                   uint32_t run_ins_apart, uint32_t tier);
-void launch_spec_verify(hipStream_t st, const uint32_t* seg, uint32_t n_cand, uint32_t ell,
-                        const uint32_t* owned, const uint32_t* run_in, uint32_t* mismatches,
-                        const uint32_t* redo_in, uint32_t* redo_out,
-                        const uint32_t* own_marks = nullptr /* per stretch of `seg`: which were swept this time */);
-bool launch_sweep_uniform_mw(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
-                             uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
-                             uint32_t* selend, uint32_t* iter_stats, const uint32_t* seg,
-                             uint32_t n_seg_max);
-// event-driven form for deep data (kernels/sweep_uniform_events.inc.hip): pack, chain, expand.
-// pk / lastns are scratch of sweep_ev_pack_bytes / sweep_ev_last_bytes; sev has ltot + 8 words.
-size_t sweep_ev_pack_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg);
-size_t sweep_ev_last_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg);
-bool launch_sweep_ev_pack(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,
-                          uint32_t ell, uint32_t M, uint32_t ltot, const uint32_t* seg, uint32_t n_seg_max,
-                          uint32_t* pk, const int32_t* nadj = nullptr, const uint32_t* from = nullptr);
-bool launch_sweep_ev_chain(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,
-                           uint32_t ell, uint32_t M, uint32_t ltot, const uint32_t* seg, uint32_t n_seg_max,
-                           const uint32_t* pk, uint32_t* sev, uint32_t* lastns, uint32_t* iter_stats,
-                           const int32_t* nadj = nullptr, uint32_t* ckpt = nullptr /* sweep_ev_ckpt_bytes */,
+void launch_spec_verify(const SweepAxis& ax, uint32_t ell, const uint32_t* owned, const uint32_t* run_in,
+                        uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out,
+                        const uint32_t* own_marks = nullptr /* per stretch of the table: which were swept this time */);
+void launch_spec_verify_merge_mixed(const SweepAxis& ax, uint32_t max_span, uint32_t* out_even, const uint32_t* out_odd,
+                                    const uint32_t* snap, uint32_t* mismatches, const uint32_t* redo_in,
+                                    uint32_t* redo_out);
+// One span ell: the seven-wave pipelines (fast form with checked fallback; every block in the general form -- sparse
+// data: the fast form rarely holds) and the single-wave kernel.  false: the span is not one the form takes.
+bool launch_sweep_uniform_mw(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* selend, uint32_t* iter_stats);
+// selend_run_in (or null): speculative tables -- a stretch's run-in is stored there, what it owns in selend;
+// redo_in (or null): a later tier -- only stretches whose exact stretch is marked there do anything
+bool launch_sweep_uniform_gen(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* selend, uint32_t* iter_stats,
+                              uint32_t* selend_run_in = nullptr, const uint32_t* redo_in = nullptr,
+                              const int32_t* nadj = nullptr /* near-uniform route: need(p) += nadj[p], capped at the
+                                                               swept reads' coverage (ltot + 1 entries) */,
+                              const uint32_t* own_marks = nullptr /* per stretch of the table: 0 = leave its output alone */);
+bool launch_sweep_uniform(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* selend, uint32_t* iter_stats);
+// event-driven form for deep data (kernels/sweep_uniform_events.inc.hip): pack, chain, expand -- three launches, apart,
+// so that the host can bracket each.  pk / lastns are scratch of sweep_ev_pack_bytes / sweep_ev_last_bytes
+// (sweep_plan.h); sev has ltot + 8 words.
+bool launch_sweep_ev_pack(const SweepAxis& ax, uint32_t ell, uint32_t M, uint32_t* pk, const int32_t* nadj = nullptr,
+                          const uint32_t* from = nullptr);
+bool launch_sweep_ev_chain(const SweepAxis& ax, uint32_t ell, uint32_t M, const uint32_t* pk, uint32_t* sev,
+                           uint32_t* lastns, uint32_t* iter_stats, const int32_t* nadj = nullptr,
+                           uint32_t* ckpt = nullptr /* sweep_ev_ckpt_bytes */,
                            const uint32_t* restart = nullptr /* per stretch: first block to sweep (multiple of 64) */);
-size_t sweep_ev_ckpt_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg);
-bool launch_sweep_ev_expand(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff, uint32_t n_contigs,
-                            uint32_t ell, uint32_t M, uint32_t ltot, const uint32_t* seg, uint32_t n_seg_max,
-                            const uint32_t* sev, const uint32_t* lastns, uint32_t* selend, const uint32_t* from = nullptr);
-bool launch_sweep_uniform(hipStream_t st, const uint32_t* boff, const uint64_t* d_poff,
-                          uint32_t n_contigs, uint32_t ell, uint32_t M, uint32_t ltot,
-                          uint32_t* selend, uint32_t* iter_stats, const uint32_t* seg,
-                          uint32_t n_seg_max);
-void launch_sweep_general(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* eoff,
-                          const void* skeys, const uint64_t* d_poff, uint32_t n_contigs,
-                          uint32_t span_bits, uint32_t max_span, uint32_t M, uint32_t* selend,
-                          uint32_t ring_size, const uint32_t* seg, uint32_t n_seg_max,
-                          uint32_t* g_rings /* 2 * ring_size words per workgroup when the rings do not fit LDS, else null */);
+bool launch_sweep_ev_expand(const SweepAxis& ax, uint32_t ell, uint32_t M, const uint32_t* sev, const uint32_t* lastns,
+                            uint32_t* selend, const uint32_t* from = nullptr);
+// Mixed spans: the plain walk (any span; rings of ring_size words in LDS, or in g_rings -- 2 * ring_size words per
+// workgroup -- when they do not fit), the LDS-cached walk, and the register-resident one (buckets per lane
+// ceil((max_span + 64) / 64), up to 8: false beyond) with its speculative outputs.
+void launch_sweep_general(const SweepAxis& ax, const SortedSpans& reads, SweepDemand demand, uint32_t M, uint32_t* selend,
+                          uint32_t ring_size, uint32_t* g_rings);
 void launch_group_heads(hipStream_t st, bool wide, const void* sorted, uint32_t n,
                         uint32_t* next_head /* n + 1 entries; reverse-min-scan it afterwards */);
-void launch_sweep_general_cached(hipStream_t st, bool wide, const uint32_t* boff,
-                                 const uint32_t* eoff, const void* sorted, const uint32_t* next_head,
-                                 const uint64_t* d_poff, uint32_t n_contigs, uint32_t span_bits,
-                                 uint32_t max_span, uint32_t M, uint32_t* selend, uint32_t ring,
-                                 const uint32_t* seg, uint32_t n_seg_max);
-// `sorted` is a Rec{key,val} array (wide == false) or u64 keys with `svals` beside them
-bool launch_sweep_general_reg(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* eoff,
-                              const void* sorted, const uint32_t* next_head, const uint64_t* d_poff,
-                              uint32_t n_contigs, uint32_t span_bits, uint32_t max_span, uint32_t M,
-                              uint32_t* selend, const uint32_t* seg, uint32_t n_seg_max,
-                              uint32_t* selend_odd = nullptr, const uint32_t* redo_in = nullptr,
+void launch_sweep_general_cached(const SweepAxis& ax, const SortedSpans& reads, const uint32_t* eoff, uint32_t M,
+                                 uint32_t* selend, uint32_t ring);
+bool launch_sweep_general_reg(const SweepAxis& ax, const SortedSpans& reads, SweepDemand demand, uint32_t M,
+                              uint32_t* selend, uint32_t* selend_odd = nullptr, const uint32_t* redo_in = nullptr,
                               uint32_t* snap = nullptr /* speculative tables: spec_snap_bytes(n_seg_max) */);
-size_t spec_snap_bytes(uint32_t n_cand);
-void launch_spec_verify_merge_mixed(hipStream_t st, const uint32_t* seg, uint32_t n_cand, uint32_t max_span,
-                                    uint32_t* out_even, const uint32_t* out_odd, const uint32_t* snap,
-                                    uint32_t* mismatches, const uint32_t* redo_in, uint32_t* redo_out);
+// `sorted` is a Rec{key,val} array (wide == false) or u64 keys with `svals` beside them
 void launch_mark(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals, uint32_t ltot,
                  const uint32_t* boff, const uint32_t* selend, uint64_t* mask,
                  unsigned long long* n_kept);
 // Coverage profile (kernels/profile.inc.hip): need[p] = min(cov(p), cap(p)) with the top bit set where cov(p) <= cap(p),
 // from a batch's sorted, disjoint regions in global positions (rs / re / cap, n_regions of them; default_cap elsewhere);
 // pstat[0] += positions with cov > cap, pstat[1] += the sum of need.  launch_profile_segments is launch_sweep_segments
-// reading that bit; the two capped sweeps take need[] where the scalar ones take eoff and M.
+// reading that bit; the mixed-span sweeps take need[] as a capped SweepDemand.
 void launch_profile_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, uint32_t ltot, const uint32_t* rs,
                          const uint32_t* re, const uint32_t* cap, uint32_t n_regions, uint32_t default_cap, uint32_t* need,
                          unsigned long long* pstat);
-const uint32_t* launch_profile_segments(hipStream_t st, const uint32_t* need, const uint64_t* d_poff, uint32_t n_contigs,
-                                        uint32_t ltot, uint32_t n_windows, uint32_t* seg_words);
-bool launch_sweep_general_reg_capped(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* need,
-                                     const void* sorted, const uint32_t* next_head, const uint64_t* d_poff,
-                                     uint32_t n_contigs, uint32_t span_bits, uint32_t max_span, uint32_t* selend,
-                                     const uint32_t* seg, uint32_t n_seg_max);
-void launch_sweep_general_capped(hipStream_t st, bool wide, const uint32_t* boff, const uint32_t* need, const void* sorted,
-                                 const uint64_t* d_poff, uint32_t n_contigs, uint32_t span_bits, uint32_t max_span,
-                                 uint32_t* selend, uint32_t ring_size, const uint32_t* seg, uint32_t n_seg_max,
-                                 uint32_t* g_rings);
+SweepAxis launch_profile_segments(const SweepAxis& ax, const uint32_t* need, uint32_t n_windows, uint32_t* seg_words);
 void launch_bucket_heads(hipStream_t st, bool wide, const void* sorted, const uint32_t* svals,
                          uint32_t n, uint32_t span_bits, uint32_t ltot, uint32_t* boff);
 void launch_reverse_min_scan(hipStream_t st, uint32_t* data, uint32_t n, uint32_t* spine);

@@ -13,7 +13,8 @@
 //
 // One translation unit, kept in parts under kernels/ (included below, in dependency order):
 //   wave_primitives          DPP helpers, wave reductions and scans
-//   prepare_scan             k_prepare (validate, statistics, partition histogram), exclusive scan
+//   prepare_scan             k_prepare (validate, statistics, partition histogram), exclusive scan, the two columns a
+//                            route asks for late (k_gstart, k_fill_ends)
 //   radix_sort               LSD radix passes (sort-based routes)
 //   bucket_offsets           sort-based routes: bucket offsets from the sorted keys (heads + reverse min-scan)
 //   ranked_route             range partition (one or two levels), per-range offsets, ordered ranking
@@ -27,7 +28,9 @@
 //   sweep_mixed              mixed-span event sweeps (register-resident, LDS-cached, plain)
 //   mark_and_next_rows       keep-mask emission for the sort-based routes, coverage probes, FILTER,
 //                            pair compaction / completion
-//   launchers                host-side launch wrappers declared in qmcp_kernels.h
+//   launchers                host-side launch wrappers declared in qmcp_kernels.h (no kernels): the pick of a template
+//                            instantiation from run-time values (dispatch_int / _bool / _sorted / _keys), the sweeps
+//                            on a SweepAxis
 //   near_uniform             one dominant span + a few shorter reads: the one-span sweep over the regular reads, the
 //                            exceptions verified against it and selected one event at a time
 //   by_contig                reads in any order with a contig id each: sort keys, contig bounds, gather, mask scatter-back
@@ -47,7 +50,7 @@
 //   dedup                    duplicate families collapsed before the solve: ranges and validation, composite keys, head
 //                            flags, cell ids, survivor / duplicate bits, family statistics, compaction of the survivors
 //   profile                  a cap that varies along the genome: need(p) = min(cov(p), cap(p)) per position with its cut
-//                            flag, the cut-point scan over it, and the launchers of the capped mixed-span sweeps
+//                            flag, and the cut-point scan over it
 //   pairs                    pair-aware downsampling: the kept set's bits in a batch's grouped order and their complement,
 //                            the kept reads' depth as scanned events, need(p) = min(cov_rest(p), T - credit(p))
 //   templates                template-aware downsampling: id check and template sizes, and the completion of a kept set
@@ -63,6 +66,8 @@
 //                            the mates' completion, the packed mask of one label
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "qmcp_kernels.h"
 #include "target_table.h"  // project_read: shared with the host

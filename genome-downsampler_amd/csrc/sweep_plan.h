@@ -5,11 +5,13 @@
 // whether stretch boundaries are speculated on and with how long a run-in -- as one plan function per route; the call
 // sites (api/uniform_sweep.inc.hip, api/near_uniform_route.inc.hip, api/solve_tail.inc.hip) only execute the plan.
 // The routes keep rules of their own where they differ (what "sparse" means, the run-in, the shortest genome worth
-// stretches); those differences are named here, not aligned.  The multi-device cost model (api/multi_device.inc.hip,
+// stretches); those differences are named here, not aligned.  So do the layout of the stretch tables and the sizes of
+// the sweeps' scratch, which the launchers and the arena both read.  The multi-device cost model (api/multi_device.inc.hip,
 // mirrored by sharding.py) is here too, next to the predicate it prices.
 #ifndef QMCP_SWEEP_PLAN_H
 #define QMCP_SWEEP_PLAN_H
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #include "qmcp_hip.h"
@@ -83,6 +85,34 @@ inline bool sweep_uniform_ev_supported(uint32_t ell, uint32_t M) {
     if (!sweep_uniform_mw_supported(ell)) return false;
     return (uint64_t)M + 1 <= ev_pack_sat((ell + 63) / 64);
 }
+
+// ------------------------------------------------------------------ the sweeps' tables and scratch
+// A call's stretch tables (`seg_words`, k_build_segments writes them): the windows' cuts, then three tables -- tier 0, the
+// exact one, and tiers 1 and 2 with speculative boundaries --, each a count and per stretch {start, end, contig end}, the
+// owned-from position and the exact table's stretch it lies in.  Where a tier's table begins, and the words of all three:
+inline size_t sweep_segment_table_offset(uint32_t n_contigs, uint32_t n_windows, uint32_t tier) {
+    return (size_t)n_windows + (size_t)tier * (1 + 5 * ((size_t)n_contigs + n_windows));
+}
+inline size_t sweep_segment_words(uint32_t n_contigs, uint32_t n_windows) {
+    return sweep_segment_table_offset(n_contigs, n_windows, 3);
+}
+// The event-driven form's scratch (kernels/sweep_uniform_events.inc.hip) for n_wg workgroups: pieces of four blocks, 1 KiB
+// each packed; the chain's state at every 64th block; the last changed block per block.
+inline uint32_t sweep_ev_pieces(uint32_t ltot, uint32_t ell, uint32_t n_wg) { return ltot / (4u * ell) + n_wg + 1; }
+inline size_t sweep_ev_pack_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) {
+    return (size_t)sweep_ev_pieces(ltot, ell, n_wg) * 1024;
+}
+inline size_t sweep_ev_ckpt_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) {
+    return ((size_t)sweep_ev_pieces(ltot, ell, n_wg) / 16 + 2 * (size_t)n_wg + 4) * 512 * sizeof(uint32_t);
+}
+inline size_t sweep_ev_last_bytes(uint32_t ltot, uint32_t ell, uint32_t n_wg) {
+    return ((size_t)sweep_ev_pieces(ltot, ell, n_wg) * 4 + 64) * sizeof(uint32_t);
+}
+// the most workgroups an event-driven sweep gets: a stretch per contig and per cut-point window of the one-span routes
+inline uint32_t sweep_ev_workgroups_max(uint32_t n_contigs) { return n_contigs + kSweepWindowsOneSpan; }
+// the mixed-span walk's state at a speculative boundary (>= the register sweep's window of live buckets), per stretch
+constexpr uint32_t kSpecSnapWords = 512;
+inline size_t spec_snap_bytes(uint32_t n_cand) { return (size_t)n_cand * kSpecSnapWords * sizeof(uint32_t); }
 
 // ------------------------------------------------------------------ speculation
 inline uint32_t spec_burn_blocks(double depth) {

@@ -22,6 +22,7 @@ static void run_case(const char* name, double mean, uint32_t L, uint32_t ell, ui
     hipMemcpy(d_poff, poff.data(), (contigs + 1) * 8, hipMemcpyHostToDevice);
     hipMemset(d_it, 0, 128);
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b); float best = 1e9;
+    const SweepAxis ax{0, d_boff, d_poff, (uint32_t)contigs, (uint32_t)Lt};  // whole contigs on the default stream
     const int reps = 5;
     for (int it = 0; it < reps; ++it) {
         hipEventRecord(a);
@@ -49,7 +50,7 @@ static void run_case(const char* name, double mean, uint32_t L, uint32_t ell, ui
             // the table was just written by other CUs)
             hipMemsetAsync(d_flush, it, 768u << 20, 0);
             hipEventRecord(a);
-            launch_sweep_uniform_mw(0, d_boff, d_poff, contigs, ell, M, (uint32_t)Lt, d_sel, d_it, nullptr, 0);
+            launch_sweep_uniform_mw(ax, ell, M, d_sel, d_it);
             hipEventRecord(b); hipEventSynchronize(b); float msc; hipEventElapsedTime(&msc, a, b);
             if (msc < cold) cold = msc;
         }
@@ -57,7 +58,7 @@ static void run_case(const char* name, double mean, uint32_t L, uint32_t ell, ui
         hipMemset(d_it, 0, 128);
         for (int it = 0; it < reps; ++it) {
             hipEventRecord(a);
-            ok = launch_sweep_uniform_mw(0, d_boff, d_poff, contigs, ell, M, (uint32_t)Lt, d_sel, d_it, nullptr, 0);
+            ok = launch_sweep_uniform_mw(ax, ell, M, d_sel, d_it);
             hipEventRecord(b); hipEventSynchronize(b); float ms; hipEventElapsedTime(&ms, a, b); if (ms < best2) best2 = ms;
         }
         hipError_t e = hipDeviceSynchronize();
@@ -90,7 +91,7 @@ static void run_case(const char* name, double mean, uint32_t L, uint32_t ell, ui
         float best3 = 1e9;
         for (int it = 0; it < reps; ++it) {
             hipEventRecord(a);
-            launch_sweep_uniform_gen(0, d_boff, d_poff, contigs, ell, M, (uint32_t)Lt, d_sel, d_it, nullptr, 0);
+            launch_sweep_uniform_gen(ax, ell, M, d_sel, d_it);
             hipEventRecord(b); hipEventSynchronize(b); float ms; hipEventElapsedTime(&ms, a, b); if (ms < best3) best3 = ms;
         }
         hipError_t e = hipDeviceSynchronize();

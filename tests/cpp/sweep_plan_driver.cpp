@@ -6,6 +6,8 @@
 //   mixed   n= span= ltot= contigs= M= in_regs= hopeless=            plan_mixed_sweep, and where the plan samples the
 //           [s0= s1= s2= longest=]                                   spans and s0 is given, refine_mixed_with_span_sample
 //   share   reads= positions= contigs= span= M=                      share_sweeps_as_stretches
+//   sizes   contigs= windows= tier= ltot= ell= wg= cand=             the stretch tables' words and a tier's offset, the
+//                                                                    event-driven form's scratch, the boundary snapshots
 // Options on any line: sweep= cuts= spec= run_in= nu_min_depth= (qmcp_hip_options: sweep, cut_points, speculation,
 // speculation_run_in, near_uniform_min_depth).
 #include <cstdio>
@@ -73,6 +75,16 @@ int main() {
         } else if (route == "share") {
             std::printf("stretches=%d\n", (int)qmcp::share_sweeps_as_stretches(get("reads"), get("positions"),
                                                                               (size_t)get("contigs"), u32("span"), u32("M")));
+        } else if (route == "sizes") {
+            const uint32_t contigs = u32("contigs"), windows = u32("windows"), ltot = u32("ltot"), ell = u32("ell", 1.0),
+                           wg = u32("wg");
+            std::printf("words=%zu offset=%zu pieces=%u pack_bytes=%zu ckpt_bytes=%zu last_bytes=%zu ev_wg_max=%u "
+                        "snap_bytes=%zu\n",
+                        qmcp::sweep_segment_words(contigs, windows),
+                        qmcp::sweep_segment_table_offset(contigs, windows, u32("tier")), qmcp::sweep_ev_pieces(ltot, ell, wg),
+                        qmcp::sweep_ev_pack_bytes(ltot, ell, wg), qmcp::sweep_ev_ckpt_bytes(ltot, ell, wg),
+                        qmcp::sweep_ev_last_bytes(ltot, ell, wg), qmcp::sweep_ev_workgroups_max(contigs),
+                        qmcp::spec_snap_bytes(u32("cand")));
         } else {
             std::printf("error=unknown_route\n");
         }

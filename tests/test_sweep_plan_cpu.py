@@ -248,6 +248,33 @@ def test_mixed_gates_and_overrides(driver):
     assert mixed(driver, deep, 160, 8_000_000, 8, 100, cuts=1)["windows"] > 0
 
 
+# ------------------------------------------------------------------ the sweeps' tables and scratch
+def sizes(driver, **fields):
+    return run(driver, [line("sizes", **fields)])[0]
+
+
+def test_stretch_table_layout(driver):
+    """seg_words is the windows' cuts and then three tables of 1 + 5 (contigs + windows) words: 3 contigs and 128
+    windows give 128 + 3 x 656 words, tier t's table begins 128 + 656 t words in; a table of one contig without windows
+    is 6 words"""
+    assert sizes(driver, contigs=3, windows=128)["words"] == 2096
+    assert [sizes(driver, contigs=3, windows=128, tier=t)["offset"] for t in (0, 1, 2)] == [128, 784, 1440]
+    assert sizes(driver, contigs=1, windows=0, tier=1)["offset"] == 6
+    # the words are where a fourth table would begin; the arena's largest (255 contigs, 3 840 windows)
+    assert sizes(driver, contigs=3, windows=128, tier=3)["offset"] == 2096
+    assert sizes(driver, contigs=255, windows=3840)["words"] == 3840 + 3 * (1 + 5 * 4095)
+
+
+def test_event_sweep_scratch(driver):
+    """320 000 positions, reads of 150, 771 workgroups: 320 000 / 600 + 771 + 1 pieces of 1 KiB, a checkpoint of 512
+    words per 16 pieces and two per workgroup (+ 4), four words per piece (+ 64) of last changed blocks"""
+    s = sizes(driver, ltot=320000, ell=150, wg=771)
+    assert (s["pieces"], s["pack_bytes"], s["ckpt_bytes"], s["last_bytes"]) == (1305, 1336320, 3332096, 21136)
+    # the bound the scratch is sized with: a stretch per contig and per window of the one-span routes (768)
+    assert sizes(driver, contigs=3)["ev_wg_max"] == 771
+    assert sizes(driver, cand=4096)["snap_bytes"] == 4096 * 512 * 4
+
+
 # ------------------------------------------------------------------ the multi-device cost model
 def test_share_predicate_agrees_with_sharding_py(driver):
     """ADVICE round 4, finding 3: share_sweeps_as_stretches compiled from the header == sharding.py's mirror, on a seeded
