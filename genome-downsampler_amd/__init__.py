@@ -9,8 +9,11 @@ import, and without a GPU every solver call raises :class:`QmcpError`.
 """
 import contextlib
 import ctypes as C
+import fractions
 import heapq
 import math
+import numbers
+import operator
 import os
 
 import numpy as np
@@ -47,6 +50,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
     "qmcp_hip_solve_budget_host", "qmcp_hip_solve_budget_device",
     "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
+    "qmcp_hip_solve_proportional_host", "qmcp_hip_solve_proportional_device",
 )
 
 QMCP_OK = 0
@@ -59,6 +63,7 @@ PAIR_MAX_STAGES = 16  # QMCP_PAIR_MAX_STAGES
 CEILING_WHOLE_PAIRS = 1  # QMCP_CEILING_WHOLE_PAIRS
 BUDGET_WHOLE_PAIRS = 1  # QMCP_BUDGET_WHOLE_PAIRS
 BUDGET_CURVE_MAX = 8191  # QMCP_BUDGET_CURVE_MAX: the last coverage the curve of a budget solve reaches
+PROPORTION_DEN_MAX = 1 << 20  # QMCP_PROPORTION_DEN_MAX: the largest denominator of a proportional solve's fraction
 REPLICATES_MAX = 16  # QMCP_REPLICATES_MAX
 REPLICATES_WHOLE_PAIRS, REPLICATES_SHORTFALL = 1, 2  # QMCP_REPLICATES_*
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
@@ -143,6 +148,45 @@ class CeilingStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class ProportionalStats(C.Structure):
+    """qmcp_hip_proportional_stats: the bases a proportional solve saw and kept, what k_prop_need counted along the
+    positions (zeros when plain_route == 1: the call was the plain by-contig solve), and the fraction as given"""
+    _fields_ = [("reads_placed", C.c_uint64), ("bases_in", C.c_uint64), ("bases_kept", C.c_uint64),
+                ("demand", C.c_uint64), ("whole_positions", C.c_uint64), ("floor_positions", C.c_uint64),
+                ("capped_positions", C.c_uint64), ("max_depth", C.c_uint32), ("max_need", C.c_uint32),
+                ("num", C.c_uint32), ("den", C.c_uint32), ("floor", C.c_uint32), ("plain_route", C.c_uint32),
+                ("ms_need", C.c_float), ("ms_tally", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+def as_ratio(x):
+    """a proportion as (num, den) with 0 <= num <= den: a (num, den) pair or a fractions.Fraction is taken as is (a
+    denominator above PROPORTION_DEN_MAX is the library's to refuse: QMCP_ERANGE), any other number goes through
+    Fraction(x).limit_denominator(PROPORTION_DEN_MAX); values outside 0 .. 1 raise ValueError"""
+    if isinstance(x, (tuple, list)):
+        if len(x) != 2:
+            raise ValueError("a proportion given as a pair is (num, den)")
+        num, den = operator.index(x[0]), operator.index(x[1])
+    elif isinstance(x, fractions.Fraction):
+        num, den = x.numerator, x.denominator
+    else:
+        if not isinstance(x, numbers.Rational):
+            x = float(x)
+            if not math.isfinite(x):
+                raise ValueError(f"a proportion must lie in 0 .. 1, not {x!r}")
+        if not 0 <= x <= 1:  # (before the rounding, which would take 1.0000001 to 1)
+            raise ValueError(f"a proportion must lie in 0 .. 1, not {x!r}")
+        f = fractions.Fraction(x).limit_denominator(PROPORTION_DEN_MAX)
+        num, den = f.numerator, f.denominator
+    if den < 1:
+        raise ValueError("a proportion's denominator must be at least 1")
+    if not 0 <= num <= den:
+        raise ValueError(f"a proportion must lie in 0 .. 1, not {num} / {den}")
+    return int(num), int(den)
 
 
 class BudgetStats(C.Structure):
@@ -346,7 +390,9 @@ class DownsampleRequest(C.Structure):
                                            "n_template_stages", "n_replicates_further")]
         + [(name, C.c_int32) for name in ("amplicon_mode", "per_reference", "amplicons_by_reference", "keep_off_target",
                                           "dedup", "has_regions", "pair_aware", "template_aware", "split_spliced",
-                                          "include_secondary", "ceiling", "has_budget_reads", "has_replicates")])
+                                          "include_secondary", "ceiling", "has_budget_reads", "has_replicates")]
+        + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
+           ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
 
 SWEEP_AUTO, SWEEP_FAST, SWEEP_GENERAL, SWEEP_EVENTS = 0, 1, 2, 3
@@ -496,6 +542,13 @@ _hip.qmcp_hip_solve_budget_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c
 _hip.qmcp_hip_solve_budget_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(BudgetStats)]
+_hip.qmcp_hip_solve_proportional_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p,
+                                                  C.POINTER(Stats), C.POINTER(ProportionalStats)]
+_hip.qmcp_hip_solve_proportional_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                                    C.POINTER(ProportionalStats)]
 _hip.qmcp_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
 _hip.qmcp_hip_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
 if _host is not None:
@@ -653,6 +706,7 @@ class Solver:
         self.last_template_stats = None
         self.last_template_profile_stats = None
         self.last_ceiling_stats = None
+        self.last_proportional_stats = None
         self.last_budget_stats = None
         self.last_replicates_stats = None
         self.last_replicate_solve_stats = None
@@ -1059,6 +1113,42 @@ class Solver:
                                                   C.c_void_p(d_mask), C.c_void_p(stream), C.byref(st), C.byref(cs)))
         self.last_stats, self.last_ceiling_stats = st, cs
         return cs
+
+    def solve_proportional(self, starts, ends, contig_ids, contig_lengths, proportion, floor=0,
+                           max_coverage=2**31 - 1):
+        """keep a fraction of the depth everywhere (qmcp_hip_solve_proportional_host): with num / den =
+        as_ratio(proportion), the kept set covers every position p at least
+        min(cov(p), max_coverage, max(ceil(cov(p) * num / den), floor)) times with the fewest reads (the canonical
+        rule): the fraction of the depth rounded up, positions at or below `floor` whole, max_coverage a hard upper
+        end of the demand.  proportion 1 (or floor >= max_coverage) is solve_by_contig at max_coverage, proportion 0
+        is solve_by_contig at min(floor, max_coverage).  Host keep bitmask in INPUT order out; last_stats,
+        last_proportional_stats"""
+        num, den = as_ratio(proportion)
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ps = Stats(), ProportionalStats()
+        _check(_hip.qmcp_hip_solve_proportional_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                     lengths.size, num, den, int(floor), int(max_coverage), 0,
+                                                     _p64(mask), C.byref(st), C.byref(ps)))
+        self.last_stats, self.last_proportional_stats = st, ps
+        return mask[:mask_words(n)]
+
+    def solve_proportional_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, proportion, d_mask,
+                                  floor=0, max_coverage=2**31 - 1, stream=0):
+        """solve_proportional on device pointers (ints); the input-order mask is written to d_mask.  Returns the
+        proportional stats"""
+        num, den = as_ratio(proportion)
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        st, ps = Stats(), ProportionalStats()
+        _check(_hip.qmcp_hip_solve_proportional_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                       C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                       num, den, int(floor), int(max_coverage), 0, C.c_void_p(d_mask),
+                                                       C.c_void_p(stream), C.byref(st), C.byref(ps)))
+        self.last_stats, self.last_proportional_stats = st, ps
+        return ps
 
     @staticmethod
     def _budget_of(budget_reads, fraction, placed):
@@ -2128,6 +2218,9 @@ class _Mode:
         self.amplicon_files, self.quality_solver = amplicon_files, quality_solver
 
 
+_PROPORTIONAL = _Mode("proportional downsampling", ("replicates", "a budget", "ceiling", "pair_aware", "template_aware",
+                                                    "targets", "a depth report", "a depth track", "a coverage ladder",
+                                                    "stratify", "dedup", "a coverage profile"))
 _REPLICATES = _Mode("disjoint replicates", ("a budget", "ceiling", "pair_aware", "template_aware", "targets", "a depth report",
                                             "a depth track", "a coverage ladder", "stratify", "dedup", "a coverage profile"),
                     plural=True)
@@ -2184,7 +2277,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    template_aware=False, split_spliced=True, include_secondary=False, template_stages=None,
                    template_report=None, template_targets=None, template_target_padding=0, template_profile=None,
                    ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None,
-                   replicates=None, replicates_out=None, replicates_report=None):
+                   replicates=None, replicates_out=None, replicates_report=None, proportion=None, proportion_floor=0,
+                   proportional_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2280,9 +2374,18 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     mates, short_positions, short_bases, records_written -- and an n_full line.  Replicates are disjoint, not
     exchangeable: replicate 1 gets the first choices.  Needs per_reference=True; not together with targets, report,
     track, ladder, stratify, dedup, profile, pair_aware, template_aware, ceiling, a budget, amplicon files or
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes.
+    proportion=f (a float, a fractions.Fraction or a (num, den) pair: as_ratio; BamApiConfig::proportion) with
+    proportion_floor: every position keeps at least ceil(f * its depth), positions at or below proportion_floor are
+    kept whole, and max_coverage is a hard upper end of the demand (2**31 - 1: none) -- one
+    qmcp_hip_solve_proportional_host call.  find_pairs then completes mates as always: it only adds reads, so every
+    floor still holds.  proportional_report (a path) gets a stat<TAB>value TSV with the ProportionalStats and
+    records_written.  Needs per_reference=True; not together with replicates, a budget, ceiling, pair_aware,
+    template_aware, targets, report, track, ladder, stratify, dedup, profile, amplicon files or
     "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
-    given = {"a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
+    given = {"replicates": replicates is not None,
+             "a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
              "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
              "a depth report": bool(report), "a depth track": track is not None, "a coverage ladder": ladder is not None,
              "stratify": stratify is not None, "dedup": bool(dedup), "a coverage profile": profile is not None}
@@ -2328,9 +2431,23 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                   max_coverage=int(max_coverage), min_len=int(min_length), min_mapq=int(min_mapq),
                   per_reference=bool(per_reference))
     n_files = None  # a ladder and replicates write several files and return a list
-    if (replicates_out is not None or replicates_report is not None) and replicates is None:
+    if (proportion_floor or proportional_report is not None) and proportion is None:
+        raise ValueError("proportion_floor and proportional_report need proportion")
+    if proportion is not None:
+        num, den = as_ratio(proportion)
+        if den > PROPORTION_DEN_MAX:
+            raise ValueError(f"proportion: the denominator must not exceed {PROPORTION_DEN_MAX}")
+        if not 0 <= int(proportion_floor) < 1 << 32:
+            raise ValueError("proportion_floor must fit an unsigned 32-bit depth")
+        if not 0 <= int(max_coverage) < 1 << 31:
+            raise ValueError("proportional downsampling: max_coverage must lie in 0 .. 2^31 - 1")
+        need_per_reference(_PROPORTIONAL)
+        refuse(_PROPORTIONAL)
+        fields.update(has_proportion=1, proportion_num=num, proportion_den=den, proportion_floor=int(proportion_floor),
+                      proportional_report=proportional_report)
+    elif (replicates_out is not None or replicates_report is not None) and replicates is None:
         raise ValueError("replicates_out and replicates_report need replicates")
-    if replicates is not None:
+    elif replicates is not None:
         if isinstance(replicates, (int, np.integer)):
             if not 1 <= int(replicates) <= REPLICATES_MAX:
                 raise ValueError(f"replicates must lie in 1 .. {REPLICATES_MAX}")

@@ -1,6 +1,6 @@
 // by_contig.inc.hip -- part of qmcp_api.hip (one translation unit).
 // qmcp_hip_solve_by_contig_host / _device: reads of several contigs in any order, one contig id per read.  The pieces, which
-// every entry of the by-contig family (ladder, profile, ceiling, budget, pairs, templates, replicates; stratified with keys
+// every entry of the by-contig family (ladder, profile, ceiling, proportional, budget, pairs, templates, replicates; stratified with keys
 // and a plan of its own) puts together in a flow of its own:
 //   group_reads      a key kernel checks every read and writes its sort key; the stable record radix
 //                    (api/radix_passes.inc.hip) groups {key, read index} by key into the context's own record buffers (the

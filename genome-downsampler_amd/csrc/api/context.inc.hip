@@ -228,6 +228,9 @@ struct qmcp_hip_ctx {
     // ceiling solves (api/ceiling.inc.hip; need[] and the batch's regions are the profile's pf_need / pf_tab): a batch's
     // position offsets, the events of its dropped reads and their scan with its spine, and the call's counters
     DevBuf cl_poff, cl_depth, cl_spine, cl_stat;
+    // proportional solves (api/proportional.inc.hip; need[] is the profile's pf_need): the call's counters
+    // (qmcp_kernels.h: PropStat)
+    DevBuf pp_stat;
     // budget solves (api/budget.inc.hip), all its own: the accumulators, the curve and the depth histogram in one buffer
     // (BudgetWord words | curve | histogram), and the second input-order mask of the probes
     DevBuf bg_acc, bg_mask;

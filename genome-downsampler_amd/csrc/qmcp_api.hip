@@ -84,6 +84,9 @@
 //                       solver at the scaled caps, later stages build need[] from the scaled region table and the credit
 //   ceiling             (profile) kept depth never above the cap, the most reads kept: a batch solver with the dual need
 //                       max(0, cov(p) - cap(p)) selecting the DROPPED reads, a device-side check, and the complement
+//   proportional        (profile) a fraction of the depth everywhere: a batch solver with need(p) = min(cov(p), M,
+//                       max(ceil(cov(p) * num / den), floor)) built from the batch's own depth, the plain by-contig call at
+//                       both ends of the fraction's range, and a tally of the kept bases
 //   budget              (by_contig) the deepest coverage whose by-contig solve fits a number of reads: one grouping, the
 //                       curve S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
 //   replicates          (by_contig, depth_report) one read set split into disjoint downsamples: the batch loop at the
@@ -113,5 +116,6 @@
 #include "api/templates.inc.hip"
 #include "api/templates_profile.inc.hip"
 #include "api/ceiling.inc.hip"
+#include "api/proportional.inc.hip"
 #include "api/budget.inc.hip"
 #include "api/replicates.inc.hip"

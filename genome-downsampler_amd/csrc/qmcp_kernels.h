@@ -492,6 +492,28 @@ void launch_ceiling_check(hipStream_t st, const uint32_t* boff, const uint32_t* 
 void launch_ceiling_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, bool whole_pairs, uint64_t* mask,
                            unsigned long long* cst);
 
+// proportional downsampling (kernels/proportional.inc.hip; api/proportional.inc.hip drives them).  boff / eoff as
+// launch_profile_need takes them.  launch_prop_need: need[p] = min(cov(p), max_coverage, max(ceil(cov(p) * num / den),
+// floor_depth)) in exact integers (num <= den <= QMCP_PROPORTION_DEN_MAX), the cut bit where need(p) == cov(p).
+// launch_prop_tally, once per call: starts / ends / ids are the call's columns in input order, mask (ceil(n_reads / 64)
+// words) its final keep mask.  pst: kPropStatWords counters, zeroed by the caller.
+enum PropStat : uint32_t {
+    kPropDemand = 0,       // the sum of need
+    kPropWholePositions,   // positions with cov > 0 and need == cov
+    kPropFloorPositions,   // positions with q < min(floor, cov, max_coverage)
+    kPropCappedPositions,  // positions with max(q, floor) > max_coverage and cov > max_coverage
+    kPropMaxDepth,         // the largest depth (cleared per batch, with the next: the host keeps the call's maxima)
+    kPropMaxNeed,          // the largest need (it plans the batch's sweep)
+    kPropPlaced,           // placed reads
+    kPropBasesIn,          // the sum of their spans
+    kPropBasesKept,        // the sum of the kept reads' spans
+    kPropStatWords = 12
+};
+void launch_prop_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, uint32_t ltot, uint32_t num, uint32_t den,
+                      uint32_t floor_depth, uint32_t max_coverage, uint32_t* need, unsigned long long* pst);
+void launch_prop_tally(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids, uint64_t n_reads,
+                       const uint64_t* mask, unsigned long long* pst);
+
 // budget downsampling (kernels/budget.inc.hip; api/budget.inc.hip drives them).  launch_budget_tally: cov[0 .. ltot) is a
 // batch's per-position depth; hist (H bins, H <= kBudgetBinsMax) takes min(cov, H - 1), acc the largest depth and the sum of
 // the depths -- both live across the batches of a call, zeroed by the caller.  launch_budget_curve, once: curve[M] =

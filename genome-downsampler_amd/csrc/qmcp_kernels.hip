@@ -59,6 +59,8 @@
 //                            and the segments and templates that touch a positive cap
 //   ceiling                  ceiling downsampling: need(p) = max(0, cov(p) - cap(p)) for the dropped set, the check of the
 //                            kept depth against the caps, and the complement over the placed reads (mates joined first)
+//   proportional             proportional downsampling: need(p) = min(cov(p), M, max(ceil(cov(p) * num / den), floor)) in
+//                            exact integers with its cut flag, and the tally of the placed and the kept reads' bases
 //   budget                   budget downsampling: the depth histogram of a call, the curve S(M) = sum of min(cov, M) from
 //                            it, and a probe's pair completion with its popcount
 //   replicates               disjoint replicates: the dense split of a replicate's candidates into labels and the next
@@ -110,6 +112,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/templates.inc.hip"
 #include "kernels/templates_profile.inc.hip"
 #include "kernels/ceiling.inc.hip"
+#include "kernels/proportional.inc.hip"
 #include "kernels/budget.inc.hip"
 #include "kernels/replicates.inc.hip"
 

@@ -122,6 +122,16 @@ struct BamApiConfig {
     // goes together with nothing that budget downsampling refuses, nor with a budget or a coverage profile
     // (std::invalid_argument otherwise).  Not set: nothing changes.
     std::optional<std::vector<std::uint32_t>> replicates;
+    // Proportional downsampling: every position keeps at least ceil(cov * num / den) of its depth, positions at or below
+    // `floor` whole, max_coverage a hard upper end of the demand (QuasiMcpHipSolver::solve_proportional /
+    // qmcp_hip_solve_proportional_host).  find_pairs completes mates as always -- it only adds reads, so every floor
+    // still holds.  0 <= num <= den, 1 <= den <= QMCP_PROPORTION_DEN_MAX.  Needs per_reference and goes together with
+    // nothing that disjoint replicates refuse, nor with replicates or a coverage profile (std::invalid_argument
+    // otherwise).  Not set: nothing changes.
+    struct Proportion {
+        std::uint32_t num = 0, den = 1, floor = 0;
+    };
+    std::optional<Proportion> proportion;
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -174,6 +184,8 @@ class BamApi {
     std::uint64_t budget_for(std::uint64_t placed_reads) const;
     // BamApiConfig::replicates (not set: no replicate split)
     const std::optional<std::vector<std::uint32_t>>& replicates() const { return replicates_; }
+    // BamApiConfig::proportion (not set: no proportional solve)
+    const std::optional<BamApiConfig::Proportion>& proportion() const { return proportion_; }
     // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
     // get_template_segments call, which also fills get_filtered_out_reads
     bool template_aware() const { return template_aware_; }
@@ -219,6 +231,7 @@ class BamApi {
     std::optional<std::uint64_t> budget_reads_;
     std::optional<double> budget_fraction_;
     std::optional<std::vector<std::uint32_t>> replicates_;
+    std::optional<BamApiConfig::Proportion> proportion_;
     std::vector<std::uint32_t> pair_stages_;
     bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false;
     std::vector<std::uint32_t> template_stages_;

@@ -118,6 +118,12 @@ class QuasiMcpHipSolver : public Solver {
                                             const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
                                             const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps);
     const qmcp_hip_ceiling_stats& last_ceiling_stats() const { return clstats_; }
+    // Proportional downsampling for the reads of a BamApi built with BamApiConfig::proportion: one
+    // qmcp_hip_solve_proportional_host call with its num / den and floor, and required_cover as the hard upper end of the
+    // demand (2^31 - 1: none).  The caller completes pairs with find_pairs, as after solve_profile.
+    // std::invalid_argument for a BamApi without a proportion and for what the library refuses
+    std::unique_ptr<Solution> solve_proportional(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_proportional_stats& last_proportional_stats() const { return ppstats_; }
     // Budget downsampling for the reads of a BamApi built with BamApiConfig::budget_reads or budget_fraction: one
     // qmcp_hip_solve_budget_host call with QMCP_BUDGET_WHOLE_PAIRS, required_cover as the upper end of the search and
     // BamApi::budget_for(placed reads) as the budget.  The Solution holds whole pairs already -- the caller writes it
@@ -175,6 +181,7 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_ceiling_stats clstats_{};
+    qmcp_hip_proportional_stats ppstats_{};
     qmcp_hip_budget_stats bgstats_{};
     qmcp_hip_replicates_stats rpstats_{};
     std::vector<std::uint64_t> budget_curve_;

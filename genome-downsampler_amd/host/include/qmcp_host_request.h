@@ -86,6 +86,14 @@ typedef struct qmcp_host_downsample_request {
     int32_t ceiling;
     int32_t has_budget_reads;
     int32_t has_replicates;
+    /* proportional downsampling (proportion): has_proportion != 0 asks for it -- every position keeps
+     * ceil(cov * proportion_num / proportion_den) of its depth, positions at or below proportion_floor whole,
+     * max_coverage the hard upper end; proportional_report: stat<TAB>value lines */
+    const char* proportional_report;
+    uint32_t proportion_num;
+    uint32_t proportion_den;
+    uint32_t proportion_floor;
+    int32_t has_proportion;
 } qmcp_host_downsample_request;
 
 /* BamApi(in_path, the request's BamApiConfig) -> the solve the configuration selects -> the output file(s) -> the

@@ -204,6 +204,33 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
                 throw std::invalid_argument("disjoint replicates: every coverage must lie in 1 .. 2^31 - 1");
         replicates_ = config.replicates;
     }
+    if (config.proportion.has_value()) {
+        const BamApiConfig::Proportion& f = *config.proportion;
+        if (f.den == 0 || f.num > f.den) throw std::invalid_argument("proportion must lie in 0 .. 1");
+        if (f.den > (1u << 20)) throw std::invalid_argument("proportion: the denominator must not exceed 2^20");
+        if (!per_reference_)
+            throw std::invalid_argument("proportional downsampling needs per_reference: its fractions are solved one "
+                                        "reference at a time");
+        if (config.replicates.has_value()) throw std::invalid_argument("proportional downsampling does not take replicates");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value())
+            throw std::invalid_argument("proportional downsampling does not take a budget");
+        if (config.ceiling) throw std::invalid_argument("proportional downsampling does not take ceiling");
+        if (config.pair_aware) throw std::invalid_argument("proportional downsampling does not take pair_aware");
+        if (config.template_aware) throw std::invalid_argument("proportional downsampling does not take template_aware");
+        if (!config.targets_filepath.empty()) throw std::invalid_argument("proportional downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("proportional downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("proportional downsampling does not take a depth report");
+        if (!config.depth_track_filepath.empty())
+            throw std::invalid_argument("proportional downsampling does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("proportional downsampling does not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("proportional downsampling does not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("proportional downsampling does not take amplicon files");
+        proportion_ = config.proportion;
+    }
     if (config.template_aware) {
         if (!per_reference_)
             throw std::invalid_argument("template-aware downsampling needs per_reference: its stages are solved one "

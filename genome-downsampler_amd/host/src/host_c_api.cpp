@@ -176,13 +176,16 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
         cfg.replicates = std::vector<std::uint32_t>();
         if (q.replicates_further) cfg.replicates->assign(q.replicates_further, q.replicates_further + q.n_replicates_further);
     }
+    if (q.has_proportion)
+        cfg.proportion = bam_api::BamApiConfig::Proportion{q.proportion_num, q.proportion_den, q.proportion_floor};
     return cfg;
 }
 
 // Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
 // amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
-enum class Mode { REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+enum class Mode { PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
 Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (cfg.proportion || given(q.proportional_report)) return Mode::PROPORTIONAL;
     if (cfg.replicates) return Mode::REPLICATES;
     if (cfg.budget_reads || cfg.budget_fraction || given(q.budget_report)) return Mode::BUDGET;
     if (cfg.ceiling) return Mode::CEILING;
@@ -201,6 +204,7 @@ struct ModeWords {
 };
 ModeWords words_of(Mode mode) {
     switch (mode) {
+        case Mode::PROPORTIONAL: return {"proportional downsampling does not", "proportional downsampling"};
         case Mode::REPLICATES: return {"disjoint replicates do not", "disjoint replicates"};
         case Mode::BUDGET: return {"budget downsampling does not", "budget downsampling"};
         case Mode::CEILING: return {"ceiling downsampling does not", "ceiling downsampling"};
@@ -226,6 +230,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
     const std::string replicates_template = q.replicates_template ? q.replicates_template : "";
     if (mode == Mode::BUDGET && !cfg.budget_reads && !cfg.budget_fraction)
         refuse("budget downsampling needs budget_reads or budget_fraction");
+    if (mode == Mode::PROPORTIONAL && !cfg.proportion) refuse("proportional downsampling needs a proportion");
     if (mode == Mode::LADDER && cfg.coverage_ladder.empty()) refuse("a coverage ladder needs at least one level");
     if (mode == Mode::LADDER && ladder_template.find("{M}") == std::string::npos)
         refuse("the ladder's output template has no {M}");
@@ -242,7 +247,8 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
         if (!cfg.bed_filepath.empty() || !cfg.tsv_filepath.empty() || cfg.amplicons_by_reference)
             refuse("a coverage profile does not take amplicon files");
     }
-    if (q.has_regions && (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES))
+    if (q.has_regions &&
+        (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL))
         refuse(words.refuses + " go together with a coverage profile");
     if (mode != Mode::PLAIN && solver.uses_quality_of_reads()) refuse(words.refuses + " take a solver that grades by quality");
     if (mode != Mode::PLAIN && hip == nullptr) refuse("this solver has no " + words.noun);
@@ -307,6 +313,21 @@ bool write_ceiling_report(const char* path, const qmcp_hip_ceiling_stats& cs, st
                  (unsigned long long)cs.short_bases, (unsigned long long)cs.excess_positions);
     std::fprintf(f, "max_kept_depth\t%u\nregions_in\t%u\nregions_used\t%u\nrecords_written\t%u\n", cs.max_kept_depth,
                  cs.regions_in, cs.regions_used, (unsigned)written);
+    return std::fclose(f) == 0;
+}
+
+// stat<TAB>value: the qmcp_hip_proportional_stats and the records written
+bool write_proportional_report(const char* path, const qmcp_hip_proportional_stats& ps, std::int64_t written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "reads_placed\t%llu\nbases_in\t%llu\nbases_kept\t%llu\ndemand\t%llu\nwhole_positions\t%llu\n"
+                    "floor_positions\t%llu\ncapped_positions\t%llu\n",
+                 (unsigned long long)ps.reads_placed, (unsigned long long)ps.bases_in, (unsigned long long)ps.bases_kept,
+                 (unsigned long long)ps.demand, (unsigned long long)ps.whole_positions,
+                 (unsigned long long)ps.floor_positions, (unsigned long long)ps.capped_positions);
+    std::fprintf(f, "max_depth\t%u\nmax_need\t%u\nnum\t%u\nden\t%u\nfloor\t%u\nplain_route\t%u\nrecords_written\t%u\n",
+                 ps.max_depth, ps.max_need, ps.num, ps.den, ps.floor, ps.plain_route, (unsigned)written);
     return std::fclose(f) == 0;
 }
 
@@ -406,6 +427,7 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         case Mode::STRATIFIED: write_reads(*solver->solve(M, api), true, q.out_path); break;
         case Mode::DEDUP: write_reads(*hip->solve_dedup(M, api, kDedupBins), true, q.out_path); break;
         case Mode::PROFILE: write_reads(*hip->solve_profile(M, api, offsets, starts, ends, caps), true, q.out_path); break;
+        case Mode::PROPORTIONAL: write_reads(*hip->solve_proportional(M, api), true, q.out_path); break;
         case Mode::PAIRS: write_reads(*hip->solve_pairs(M, api), false, q.out_path); break;
         case Mode::CEILING: write_reads(*hip->solve_ceiling(M, api, offsets, starts, ends, caps), false, q.out_path); break;
         case Mode::BUDGET: write_reads(*hip->solve_budget(M, api), false, q.out_path); break;
@@ -449,6 +471,8 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
     if (mode == Mode::DEDUP && given(q.dedup_report)) reported = write_dedup_report(q.dedup_report, *hip);
     if (mode == Mode::CEILING && given(q.ceiling_report))
         reported = write_ceiling_report(q.ceiling_report, hip->last_ceiling_stats(), written[0]);
+    if (mode == Mode::PROPORTIONAL && given(q.proportional_report))
+        reported = write_proportional_report(q.proportional_report, hip->last_proportional_stats(), written[0]);
     if (mode == Mode::BUDGET && given(q.budget_report))
         reported = write_budget_report(q.budget_report, hip->last_budget_stats(), hip->last_budget_curve(), written[0]);
     if (mode == Mode::REPLICATES && given(q.replicates_report))

@@ -257,6 +257,38 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t require
     return expand_kept(n, t0);
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_proportional(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.proportion() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("proportional downsampling needs a BamApi built with BamApiConfig::proportion");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    const bam_api::BamApiConfig::Proportion& f = *bam_api.proportion();
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    int rc = qmcp_hip_solve_proportional_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                              reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(), f.num,
+                                              f.den, f.floor, required_cover, 0u, mask.data(), &stats_, &ppstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_proportional_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) {
+        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
+        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
+    }
+    return expand_kept(n, t0);
+}
+
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();

@@ -1216,6 +1216,65 @@ int qmcp_hip_solve_budget_device(qmcp_hip_ctx* ctx,
                                  uint32_t curve_capacity, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                  qmcp_hip_budget_stats* bstats);
 
+/* Proportional downsampling: keep a fraction of the depth everywhere.  Every other solving entry asks for a flat depth,
+ * min(cov(p), cap) with a cap from outside the data; this one takes its demand from the data's own depth, so the SHAPE of
+ * the coverage survives (copy-number calling, ChIP / ATAC / RNA signal, allele balance, "this run at a quarter of the
+ * sequencing") -- exactly at every position, where samtools view -s keeps the shape only in expectation.
+ * Input: reads in any order, contig_ids (QMCP_NO_CONTIG = unplaced), contig_lengths / n_contigs, limits and read
+ * validation exactly as in qmcp_hip_solve_by_contig_host.  num / den with 0 <= num <= den and 1 <= den <=
+ * QMCP_PROPORTION_DEN_MAX is the fraction; floor and max_coverage (< 2^31; 2^31 - 1: no limit) bound the demand.
+ * Answer: per contig, with cov the depth of its placed reads, all in exact integer arithmetic,
+ *   q(p)    = ceil(cov(p) * num / den)
+ *   need(p) = min(cov(p), max_coverage, max(q(p), floor))
+ * and the mask is the canonical selection (reads in input order; at the leftmost position with a deficit take the
+ * unselected covering reads with the furthest end, then the furthest start, then the lowest index: DESIGN.md sections 2
+ * and 4.12) under this need.  Every position keeps at least the fraction of its depth, rounded up; positions at or below
+ * floor are kept whole; max_coverage stays a hard upper end of the demand.  Unplaced reads are never kept.
+ * Guaranteed: kept(p) >= need(p) everywhere with the fewest reads; the result is deterministic.  NOT guaranteed: an upper
+ * bound on kept(p) -- a read kept for one position covers its neighbours too, as in every floor entry.
+ * Identities: (1) num == den or floor >= max_coverage gives the mask and the qmcp_hip_stats of qmcp_hip_solve_by_contig_*
+ * at max_coverage (the call IS that entry, every fast route of it included); (2) num == 0 gives that entry at
+ * min(floor, max_coverage), and nothing at 0; (3) otherwise the mask is that of qmcp_hip_solve_profile_* under the region
+ * table that spells need out with default_cap 0.
+ * Route of (3): the by-contig solve's grouping and batches; every batch with reads takes the sort-based mixed-span route
+ * of the profile entries with need built by k_prop_need.  Its cut bit marks need(p) == cov(p), the only positions behind
+ * which a stretch may start: deep data under a fraction is one serial chain per contig (limits).
+ * options.cut_points is honoured, nothing is speculated.
+ * Errors, all on the host before anything is copied or launched (the output mask is not written): null arrays, den == 0,
+ * num > den and unknown flag bits (flags must be 0) are QMCP_EINVAL; den > QMCP_PROPORTION_DEN_MAX and max_coverage >=
+ * 2^31 are QMCP_ERANGE.  A bad contig id or read is found on the device with the codes of the by-contig entry.
+ * stats (may be NULL): the batch-summed qmcp_hip_stats.  pstats (may be NULL): see the struct.  The device entry is
+ * ordered after hip_stream; both entries block (no _begin / _end form). */
+#define QMCP_PROPORTION_DEN_MAX (1u << 20)
+typedef struct qmcp_hip_proportional_stats {
+    uint64_t reads_placed;     /* placed reads                                                                       */
+    uint64_t bases_in;         /* the sum of their spans                                                             */
+    uint64_t bases_kept;       /* the sum of the kept reads' spans                                                   */
+    uint64_t demand;           /* the sum of need(p)                                                                 */
+    uint64_t whole_positions;  /* positions with cov > 0 and need == cov                                             */
+    uint64_t floor_positions;  /* positions with q < min(floor, cov, max_coverage): the floor (or the depth) decides  */
+    uint64_t capped_positions; /* positions with max(q, floor) > max_coverage and cov > max_coverage                 */
+    uint32_t max_depth;        /* the largest depth                                                                  */
+    uint32_t max_need;         /* the largest need                                                                   */
+    uint32_t num, den, floor;  /* as given                                                                           */
+    uint32_t plain_route;      /* 1: identity (1) or (2) applied; demand, the position counters and the two maxima
+                                  are then 0                                                                         */
+    float ms_need;             /* device time of k_prop_need (+ the cut-point scan), summed over the batches         */
+    float ms_tally;            /* device time of k_prop_tally                                                        */
+} qmcp_hip_proportional_stats;
+int qmcp_hip_solve_proportional_host(qmcp_hip_ctx* ctx,
+                                     const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                     uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                     uint32_t num, uint32_t den, uint32_t floor, uint32_t max_coverage, uint32_t flags,
+                                     uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                                     qmcp_hip_proportional_stats* pstats);
+int qmcp_hip_solve_proportional_device(qmcp_hip_ctx* ctx,
+                                       const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                       uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                       uint32_t num, uint32_t den, uint32_t floor, uint32_t max_coverage, uint32_t flags,
+                                       uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                       qmcp_hip_proportional_stats* pstats);
+
 #ifdef __cplusplus
 }
 #endif
