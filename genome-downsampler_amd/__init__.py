@@ -47,6 +47,8 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_pairs_host", "qmcp_hip_solve_pairs_device",
     "qmcp_hip_solve_templates_host", "qmcp_hip_solve_templates_device",
     "qmcp_hip_solve_templates_profile_host", "qmcp_hip_solve_templates_profile_device",
+    "qmcp_hip_clip_templates_host", "qmcp_hip_clip_templates_device",
+    "qmcp_hip_solve_fragments_host", "qmcp_hip_solve_fragments_device",
     "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
     "qmcp_hip_solve_budget_host", "qmcp_hip_solve_budget_device",
     "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
@@ -249,6 +251,18 @@ class TemplateProfileStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class FragmentStats(C.Structure):
+    """qmcp_hip_fragment_stats: what the overlap clip of a template's segments did: placed segments and their bases going
+    in, segments whose start moved, segments that became unplaced, the bases taken off (per-segment depth minus fragment
+    depth, summed), the templates with such a segment, the largest (template, contig) group and the device time"""
+    _fields_ = [("n_placed", C.c_uint64), ("n_clipped", C.c_uint64), ("n_emptied", C.c_uint64), ("bases_in", C.c_uint64),
+                ("bases_removed", C.c_uint64), ("n_templates_overlapping", C.c_uint64), ("max_group", C.c_uint32),
+                ("ms_clip", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class DepthRow(C.Structure):
     """qmcp_hip_depth_row: depth before (in) and after (kept) over the inclusive interval [start, end] of one contig"""
     _fields_ = [("contig", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("min_in", C.c_uint32),
@@ -382,15 +396,16 @@ class DownsampleRequest(C.Structure):
         + [(name, C.c_char_p) for name in ("ladder_template", "stratify", "strata_report", "dedup_report")]
         + [(name, C.POINTER(C.c_uint32)) for name in ("region_offsets", "region_starts", "region_ends", "region_caps")]
         + [("n_refs", C.c_uint64), ("pair_stages", C.POINTER(C.c_uint32)), ("template_stages", C.POINTER(C.c_uint32)),
-           ("ceiling_report", C.c_char_p), ("budget_report", C.c_char_p), ("budget_reads", C.c_uint64),
-           ("budget_fraction", C.c_double), ("replicates_further", C.POINTER(C.c_uint32)),
+           ("fragment_report", C.c_char_p), ("ceiling_report", C.c_char_p), ("budget_report", C.c_char_p),
+           ("budget_reads", C.c_uint64), ("budget_fraction", C.c_double), ("replicates_further", C.POINTER(C.c_uint32)),
            ("replicates_template", C.c_char_p), ("replicates_report", C.c_char_p)]
         + [(name, C.c_uint32) for name in ("max_coverage", "min_len", "min_mapq", "target_padding", "report_bins",
                                            "track_cap", "n_ladder_levels", "default_cap", "n_pair_stages",
                                            "n_template_stages", "n_replicates_further")]
         + [(name, C.c_int32) for name in ("amplicon_mode", "per_reference", "amplicons_by_reference", "keep_off_target",
                                           "dedup", "has_regions", "pair_aware", "template_aware", "split_spliced",
-                                          "include_secondary", "ceiling", "has_budget_reads", "has_replicates")]
+                                          "include_secondary", "fragment_depth", "ceiling", "has_budget_reads",
+                                          "has_replicates")]
         + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
            ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
@@ -522,6 +537,18 @@ _hip.qmcp_hip_solve_templates_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, 
 _hip.qmcp_hip_solve_templates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                  C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
                                                  C.c_void_p, C.POINTER(Stats), C.POINTER(TemplateStats)]
+_hip.qmcp_hip_clip_templates_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, _u32p,
+                                              C.c_uint32, _u32p, _u32p, C.POINTER(FragmentStats)]
+_hip.qmcp_hip_clip_templates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                C.c_uint32, _u32p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(FragmentStats)]
+_hip.qmcp_hip_solve_fragments_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, _u32p,
+                                               C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p, C.POINTER(Stats),
+                                               C.POINTER(TemplateStats), C.POINTER(FragmentStats)]
+_hip.qmcp_hip_solve_fragments_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                 C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(Stats), C.POINTER(TemplateStats),
+                                                 C.POINTER(FragmentStats)]
 _hip.qmcp_hip_solve_templates_profile_host.argtypes = [
     C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, _u32p, _u32p,
     C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u64p, C.POINTER(Stats), C.POINTER(TemplateStats),
@@ -705,6 +732,7 @@ class Solver:
         self.last_pair_stats = None
         self.last_template_stats = None
         self.last_template_profile_stats = None
+        self.last_fragment_stats = None
         self.last_ceiling_stats = None
         self.last_proportional_stats = None
         self.last_budget_stats = None
@@ -1276,16 +1304,89 @@ class Solver:
         self.last_stats, self.last_template_stats = st, ts
         return st, ts
 
+    def clip_templates(self, starts, ends, contig_ids, template_ids, n_templates, contig_lengths):
+        """the overlap clip of fragment depth (qmcp_hip_clip_templates_host): within every (template, contig) group, in
+        the order (start, input index), a segment that begins inside what the earlier members cover starts behind it, and
+        one that lies wholly inside becomes unplaced.  -> (clipped_starts, clipped_contig_ids, stats) in INPUT order;
+        ends do not change.  Depth per segment on the clipped columns (depth_report, depth_track, solve_templates_profile)
+        is fragment depth: a template counts once per position.  Also left in last_fragment_stats"""
+        starts, ends, ids, tids = _u32(starts), _u32(ends), _u32(contig_ids), _u32(template_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n and tids.size == n, \
+            "starts, ends, contig_ids and template_ids must have one entry per segment"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        out_s, out_c = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        fs = FragmentStats()
+        _check(_hip.qmcp_hip_clip_templates_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(tids), n,
+                                                 int(n_templates), _p32(lengths), lengths.size, _p32(out_s), _p32(out_c),
+                                                 C.byref(fs)))
+        self.last_fragment_stats = fs
+        return out_s[:n], out_c[:n], fs
+
+    def clip_templates_device(self, d_starts, d_ends, d_contig_ids, d_template_ids, n_reads, n_templates, contig_lengths,
+                              d_clipped_starts, d_clipped_contig_ids, stream=0):
+        """clip_templates on device pointers (ints); the two clipped columns are written to d_clipped_starts and
+        d_clipped_contig_ids, which must not overlap the inputs.  -> stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        fs = FragmentStats()
+        _check(_hip.qmcp_hip_clip_templates_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                   C.c_void_p(d_contig_ids), C.c_void_p(d_template_ids), int(n_reads),
+                                                   int(n_templates), _p32(lengths), lengths.size,
+                                                   C.c_void_p(d_clipped_starts), C.c_void_p(d_clipped_contig_ids),
+                                                   C.c_void_p(stream), C.byref(fs)))
+        self.last_fragment_stats = fs
+        return fs
+
+    def solve_fragments(self, starts, ends, contig_ids, template_ids, n_templates, contig_lengths, max_coverage,
+                        stages=None):
+        """template-aware downsampling on FRAGMENT depth (qmcp_hip_solve_fragments_host): solve_templates on
+        clip_templates' columns, so that a template counts once where its segments overlap (the two mates of a
+        short-insert pair).  -> (mask, stats, template_stats, fragment_stats): whole templates whose fragment depth is at
+        least min(fragment depth, max_coverage) everywhere.  Also left in last_stats / last_template_stats /
+        last_fragment_stats"""
+        starts, ends, ids, tids = _u32(starts), _u32(ends), _u32(contig_ids), _u32(template_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n and tids.size == n, \
+            "starts, ends, contig_ids and template_ids must have one entry per segment"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ts, fs = Stats(), TemplateStats(), FragmentStats()
+        _check(_hip.qmcp_hip_solve_fragments_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(tids), n,
+                                                  int(n_templates), _p32(lengths), lengths.size, int(max_coverage),
+                                                  _p32(tg), 0 if tg is None else tg.size, _p64(mask), C.byref(st),
+                                                  C.byref(ts), C.byref(fs)))
+        self.last_stats, self.last_template_stats, self.last_fragment_stats = st, ts, fs
+        return mask[:mask_words(n)], st, ts, fs
+
+    def solve_fragments_device(self, d_starts, d_ends, d_contig_ids, d_template_ids, n_reads, n_templates, contig_lengths,
+                               max_coverage, d_mask, stages=None, stream=0):
+        """solve_fragments on device pointers (ints); the input-order mask is written to d_mask, the caller's columns are
+        not modified.  -> (stats, template_stats, fragment_stats)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
+        st, ts, fs = Stats(), TemplateStats(), FragmentStats()
+        _check(_hip.qmcp_hip_solve_fragments_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                    C.c_void_p(d_contig_ids), C.c_void_p(d_template_ids), int(n_reads),
+                                                    int(n_templates), _p32(lengths), lengths.size, int(max_coverage),
+                                                    _p32(tg), 0 if tg is None else tg.size, C.c_void_p(d_mask),
+                                                    C.c_void_p(stream), C.byref(st), C.byref(ts), C.byref(fs)))
+        self.last_stats, self.last_template_stats, self.last_fragment_stats = st, ts, fs
+        return st, ts, fs
+
     def solve_templates_profile(self, starts, ends, contig_ids, template_ids, n_templates, contig_lengths, max_coverage,
                                 default_cap, region_offsets=None, region_starts=None, region_ends=None, region_caps=None,
-                                stages=None, flags=0):
+                                stages=None, flags=0, fragment_depth=False):
         """template-aware downsampling under a cap table (qmcp_hip_solve_templates_profile_host): solve_templates'
         segments and template ids, solve_profile's regions and default_cap.  Stage j of the schedule T_1 < ... < T_k =
         max_coverage (None: ceil(M / 2), then M) runs under ceil(cap(p) * T_j / M), credits the depth of the templates
         already kept and completes the templates again.  -> (mask, stats, template_stats, template_profile_stats): the
         host keep bitmask in INPUT order (whole templates that cover min(cov(p), cap(p)) everywhere), stage 1's Stats,
         the TemplateStats, the TemplateProfileStats.  Also left in last_stats / last_template_stats /
-        last_template_profile_stats"""
+        last_template_profile_stats.  fragment_depth=True: clip_templates runs first and the solve runs on its columns
+        (two calls), so the caps bound fragment depth; its stats are left in last_fragment_stats"""
+        if fragment_depth:
+            starts, contig_ids, _ = self.clip_templates(starts, ends, contig_ids, template_ids, n_templates, contig_lengths)
         starts, ends, ids, tids = _u32(starts), _u32(ends), _u32(contig_ids), _u32(template_ids)
         n = starts.size
         assert ends.size == n and ids.size == n and tids.size == n, \
@@ -1305,9 +1406,16 @@ class Solver:
     def solve_templates_profile_device(self, d_starts, d_ends, d_contig_ids, d_template_ids, n_reads, n_templates,
                                        contig_lengths, max_coverage, default_cap, d_mask, region_offsets=None,
                                        region_starts=None, region_ends=None, region_caps=None, stages=None, flags=0,
-                                       stream=0):
+                                       stream=0, fragment_depth=False, d_clipped_starts=0, d_clipped_contig_ids=0):
         """solve_templates_profile on device pointers (ints); the input-order mask is written to d_mask.  -> (stats,
-        template_stats, template_profile_stats)"""
+        template_stats, template_profile_stats).  fragment_depth=True: clip_templates_device runs first, into the two
+        device columns the caller provides (d_clipped_starts, d_clipped_contig_ids), and the solve runs on them"""
+        if fragment_depth:
+            if not d_clipped_starts or not d_clipped_contig_ids:
+                raise ValueError("fragment_depth=True needs d_clipped_starts and d_clipped_contig_ids")
+            self.clip_templates_device(d_starts, d_ends, d_contig_ids, d_template_ids, n_reads, n_templates,
+                                       contig_lengths, d_clipped_starts, d_clipped_contig_ids, stream=stream)
+            d_starts, d_contig_ids = d_clipped_starts, d_clipped_contig_ids
         lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
         offs, r0, r1, caps = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, region_caps)
         tg = None if stages is None else np.atleast_1d(np.ascontiguousarray(stages, dtype=np.uint32))
@@ -2278,7 +2386,7 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    template_report=None, template_targets=None, template_target_padding=0, template_profile=None,
                    ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None,
                    replicates=None, replicates_out=None, replicates_report=None, proportion=None, proportion_floor=0,
-                   proportional_report=None):
+                   proportional_report=None, fragment_depth=False, fragment_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2347,6 +2455,13 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     max_coverage is the scale of template_stages in both.  template_report then also lists segments_on_cap,
     templates_on_cap, regions_in, regions_used and positions_in_regions.  Not both at once, and not with anything
     template_aware refuses -- targets= and profile= included (ValueError).  None: nothing changes.
+    fragment_depth=True (BamApiConfig::fragment_depth, with template_aware=True): a template counts ONCE where its
+    segments overlap -- the two mates of a short-insert pair -- as in mosdepth, samtools depth -s and GATK: the solve is
+    one qmcp_hip_solve_fragments_host call, or with template_targets / template_profile qmcp_hip_clip_templates_host
+    followed by the cap-table entry on the clipped columns.  fragment_report (a path) gets a stat<TAB>value TSV with the
+    FragmentStats (segments_placed, segments_clipped, segments_emptied, bases_in, bases_removed, templates_overlapping,
+    max_group, ms_clip) and records_written.  Either without template_aware=True is a ValueError, and so is
+    fragment_report without fragment_depth=True.  False: nothing changes.
     ceiling=True (BamApiConfig::ceiling): max_coverage is a CEILING -- the written depth is at most max_coverage at every
     position and as many reads as possible are kept -- one qmcp_hip_solve_ceiling_host call with CEILING_WHOLE_PAIRS on
     the reads as the pair-aware flow pairs them.  With profile (a bedGraph file) the file's caps are ceilings and
@@ -2431,6 +2546,10 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                   max_coverage=int(max_coverage), min_len=int(min_length), min_mapq=int(min_mapq),
                   per_reference=bool(per_reference))
     n_files = None  # a ladder and replicates write several files and return a list
+    if (fragment_depth or fragment_report is not None) and not template_aware:
+        raise ValueError("fragment_depth and fragment_report need template_aware=True")
+    if fragment_report is not None and not fragment_depth:
+        raise ValueError("fragment_report needs fragment_depth=True")
     if (proportion_floor or proportional_report is not None) and proportion is None:
         raise ValueError("proportion_floor and proportional_report need proportion")
     if proportion is not None:
@@ -2498,7 +2617,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         need_per_reference(_TEMPLATES)
         refuse(_TEMPLATES)
         fields.update(template_aware=1, split_spliced=bool(split_spliced), include_secondary=bool(include_secondary),
-                      template_stages=stages_of(template_stages, "template_stages"))
+                      template_stages=stages_of(template_stages, "template_stages"),
+                      fragment_depth=bool(fragment_depth), fragment_report=fragment_report)
         if template_targets is not None or template_profile is not None:
             if int(template_target_padding) < 0:
                 raise ValueError("template_target_padding must not be negative")

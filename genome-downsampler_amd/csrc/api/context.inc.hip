@@ -225,6 +225,11 @@ struct qmcp_hip_ctx {
     // (starts | ends | caps), the call's table for the on-cap pass (offsets | starts | ends | caps | positive positions
     // before), the bitset of templates that touch a positive cap, and the two on-cap counters (segments, templates)
     DevBuf tq_tab, tq_cap, tq_flags, tq_stat;
+    // fragment depth (api/fragments.inc.hip; the id check, the template sizes and the bitset are the template entry's
+    // tp_*): the counters (qmcp_kernels.h: FragWord), the contig lengths, the sort's two key buffers and two index
+    // columns, its histogram, the spine of its scans and of the segmented scan, and the clipped starts and contig ids of
+    // the host entries and of the solve
+    DevBuf fr_stat, fr_len, fr_keys[2], fr_vals[2], fr_hist, fr_spine, fr_cs, fr_cc;
     // ceiling solves (api/ceiling.inc.hip; need[] and the batch's regions are the profile's pf_need / pf_tab): a batch's
     // position offsets, the events of its dropped reads and their scan with its spine, and the call's counters
     DevBuf cl_poff, cl_depth, cl_spine, cl_stat;

@@ -36,6 +36,7 @@
 #include "cap_table.h"
 #include "pair_plan.h"
 #include "replicates_plan.h"
+#include "fragment_plan.h"
 #include "solve_words.h"
 
 // One translation unit, kept in parts under api/ (included below, in dependency order: a part uses only parts above it,
@@ -82,6 +83,9 @@
 //                       id (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
 //   templates_profile   (templates, profile) the template stages under a cap per region: stage 1 is the profile's batch
 //                       solver at the scaled caps, later stages build need[] from the scaled region table and the credit
+//   fragments           (templates) fragment depth: the segments of a template clipped where they overlap (validation, the
+//                       sort by template, contig and start, a segmented running maximum, the columns written back), as an
+//                       entry of its own and in front of the template stages
 //   ceiling             (profile) kept depth never above the cap, the most reads kept: a batch solver with the dual need
 //                       max(0, cov(p) - cap(p)) selecting the DROPPED reads, a device-side check, and the complement
 //   proportional        (profile) a fraction of the depth everywhere: a batch solver with need(p) = min(cov(p), M,
@@ -115,6 +119,7 @@
 #include "api/pairs.inc.hip"
 #include "api/templates.inc.hip"
 #include "api/templates_profile.inc.hip"
+#include "api/fragments.inc.hip"
 #include "api/ceiling.inc.hip"
 #include "api/proportional.inc.hip"
 #include "api/budget.inc.hip"

@@ -448,6 +448,35 @@ void launch_tpl_mark(hipStream_t st, const uint64_t* mask, const uint32_t* ids, 
 void launch_tpl_spread(hipStream_t st, const uint32_t* ids, uint32_t n, uint32_t n_templates, const uint32_t* flags,
                        uint64_t* mask, unsigned long long* count);
 
+// fragment depth (kernels/fragments.inc.hip; api/fragments.inc.hip drives them).  fstat: the call's counters, zeroed by the
+// caller.  launch_frag_check, once per call over the rows in input order: kFragErr |= 1 for a contig id that is neither
+// < n_contigs nor QMCP_NO_CONTIG, |= 2 for a placed row with start > end or end >= its contig's length; kFragPlaced and
+// kFragBasesIn over the valid placed rows.  launch_frag_keys: a round's u64 keys (fragment_plan.h: FragmentRound), row j
+// being idx[j] (idx == NULL: j).  launch_frag_scan_apply: idx is the input index of every row in the order (template,
+// contig, start, input index); spine holds frag_spine_bytes(n) bytes; starts_out / cids_out (n words each, input order)
+// take every row's clipped start and contig id; tflags (a bitset of n_templates bits, zeroed by the caller) takes the
+// templates with a clipped or emptied segment.  frag_tile_rows(): the rows of one scan tile.
+enum FragWord : uint32_t {
+    kFragPlaced = 0,  // placed rows
+    kFragBasesIn,     // their bases
+    kFragClipped,     // rows whose start moved
+    kFragEmptied,     // rows that lie inside what their group's earlier members cover
+    kFragRemoved,     // the bases taken off both kinds
+    kFragMaxGroup,    // most placed rows of one template on one contig
+    kFragOverlapT,    // templates with a clipped or emptied row
+    kFragErr,
+    kFragWords
+};
+uint32_t frag_tile_rows();
+size_t frag_spine_bytes(uint32_t n);
+void launch_frag_check(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* cids, uint32_t n,
+                       const uint32_t* lengths, uint32_t n_contigs, unsigned long long* fstat);
+void launch_frag_keys(hipStream_t st, const uint32_t* starts, const uint32_t* cids, const uint32_t* tids, const uint32_t* idx,
+                      uint32_t n, uint32_t start_bytes, uint32_t contig_bytes, uint32_t template_bytes, void* keys);
+void launch_frag_scan_apply(hipStream_t st, const uint32_t* idx, const uint32_t* starts, const uint32_t* ends,
+                            const uint32_t* cids, const uint32_t* tids, uint32_t n, uint32_t n_templates, void* spine,
+                            uint32_t* starts_out, uint32_t* cids_out, uint32_t* tflags, unsigned long long* fstat);
+
 // template-aware downsampling under a cap table (kernels/templates_profile.inc.hip; api/templates_profile.inc.hip drives
 // them).  launch_tpl_profile_need is launch_pair_need with the target replaced by a region table as launch_profile_need
 // takes it (the batch's regions in its global positions, ascending and disjoint, caps already scaled to the stage):

@@ -57,6 +57,9 @@
 //                            through a bitset of template ids (mark, spread)
 //   templates_profile        the template stages under a cap table: need(p) from the regions' scaled caps and the credit,
 //                            and the segments and templates that touch a positive cap
+//   fragments                fragment depth: the segments of a template clipped where they overlap -- validation, sort keys
+//                            by (template, contig, start), a segmented running maximum of the ends (tiles, spine, apply)
+//                            and the clipped columns written back to input order
 //   ceiling                  ceiling downsampling: need(p) = max(0, cov(p) - cap(p)) for the dropped set, the check of the
 //                            kept depth against the caps, and the complement over the placed reads (mates joined first)
 //   proportional             proportional downsampling: need(p) = min(cov(p), M, max(ceil(cov(p) * num / den), floor)) in
@@ -111,6 +114,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/pairs.inc.hip"
 #include "kernels/templates.inc.hip"
 #include "kernels/templates_profile.inc.hip"
+#include "kernels/fragments.inc.hip"
 #include "kernels/ceiling.inc.hip"
 #include "kernels/proportional.inc.hip"
 #include "kernels/budget.inc.hip"

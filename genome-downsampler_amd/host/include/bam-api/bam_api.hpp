@@ -99,6 +99,11 @@ struct BamApiConfig {
     bool split_spliced = true;
     bool include_secondary = false;
     std::vector<std::uint32_t> template_stages;
+    // Fragment depth (with template_aware): a template counts once where its segments overlap -- the two mates of a
+    // short-insert pair -- as in mosdepth, samtools depth -s and GATK.  QuasiMcpHipSolver::solve_templates then calls
+    // qmcp_hip_solve_fragments_host, and solve_templates_profile calls qmcp_hip_clip_templates_host followed by the
+    // profile entry on the clipped columns.  Needs template_aware (std::invalid_argument otherwise).
+    bool fragment_depth = false;
     // Ceiling downsampling: max_coverage (and the caps of a coverage profile) bound the written depth from ABOVE, and as
     // many reads as possible are kept (QuasiMcpHipSolver::solve_ceiling / qmcp_hip_solve_ceiling_host with
     // QMCP_CEILING_WHOLE_PAIRS).  The output -- whole pairs -- is written from the final mask WITHOUT find_pairs, which
@@ -189,6 +194,7 @@ class BamApi {
     // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
     // get_template_segments call, which also fills get_filtered_out_reads
     bool template_aware() const { return template_aware_; }
+    bool fragment_depth() const { return fragment_depth_; }
     const std::vector<std::uint32_t>& template_stages() const { return template_stages_; }
     const TemplateSegments& get_template_segments();
     // the records with these ids (sorted in place), copied from the input; number of records written
@@ -233,7 +239,7 @@ class BamApi {
     std::optional<std::vector<std::uint32_t>> replicates_;
     std::optional<BamApiConfig::Proportion> proportion_;
     std::vector<std::uint32_t> pair_stages_;
-    bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false;
+    bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false, fragment_depth_ = false;
     std::vector<std::uint32_t> template_stages_;
     TemplateSegments template_segments_;
     bool are_segments_loaded_ = false;

@@ -156,6 +156,10 @@ class QuasiMcpHipSolver : public Solver {
                                                             const std::vector<std::uint32_t>& caps,
                                                             std::uint32_t default_cap);
     const qmcp_hip_template_profile_stats& last_template_profile_stats() const { return tqstats_; }
+    // With BamApiConfig::fragment_depth both count a template once where its segments overlap: solve_templates calls
+    // qmcp_hip_solve_fragments_host, solve_templates_profile calls qmcp_hip_clip_templates_host and runs the profile entry
+    // on the clipped columns.  What the clip did (zeros without fragment_depth):
+    const qmcp_hip_fragment_stats& last_fragment_stats() const { return frstats_; }
     const qmcp_hip_stats& last_stats() const { return stats_; }
     const qmcp_hip_target_stats& last_target_stats() const { return tstats_; }
     // host wall-clock of the last solve(): the library's parts, the mask -> Solution expansion, the whole call
@@ -187,6 +191,7 @@ class QuasiMcpHipSolver : public Solver {
     std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_template_stats tpstats_{};
     qmcp_hip_template_profile_stats tqstats_{};
+    qmcp_hip_fragment_stats frstats_{};
     std::vector<std::uint64_t> dedup_hist_;
     std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
     qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves

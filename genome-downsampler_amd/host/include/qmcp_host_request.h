@@ -50,6 +50,9 @@ typedef struct qmcp_host_downsample_request {
     /* the staged solves (pair_stages, template_stages); no stages: the default schedule */
     const uint32_t* pair_stages;
     const uint32_t* template_stages;
+    /* fragment depth (fragment_depth, with template_aware): stat<TAB>value lines of the qmcp_hip_fragment_stats and
+     * records_written, written by the host itself */
+    const char* fragment_report;
     const char* ceiling_report;
     /* budget downsampling (budget_reads, budget_fraction): has_budget_reads != 0 and / or budget_fraction >= 0 ask for
      * it; budget_report alone is refused */
@@ -83,6 +86,7 @@ typedef struct qmcp_host_downsample_request {
     int32_t template_aware;
     int32_t split_spliced;
     int32_t include_secondary;
+    int32_t fragment_depth;
     int32_t ceiling;
     int32_t has_budget_reads;
     int32_t has_replicates;

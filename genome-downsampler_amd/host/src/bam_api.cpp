@@ -253,6 +253,9 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
         split_spliced_ = config.split_spliced;
         include_secondary_ = config.include_secondary;
         template_stages_ = config.template_stages;
+        fragment_depth_ = config.fragment_depth;
+    } else if (config.fragment_depth) {
+        throw std::invalid_argument("fragment_depth needs template_aware");
     } else if (!config.template_stages.empty() || !config.split_spliced || config.include_secondary) {
         throw std::invalid_argument("template_stages, split_spliced and include_secondary need template_aware");
     }

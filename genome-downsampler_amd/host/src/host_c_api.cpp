@@ -168,6 +168,7 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
     cfg.template_aware = q.template_aware != 0;
     cfg.split_spliced = q.split_spliced != 0;
     cfg.include_secondary = q.include_secondary != 0;
+    cfg.fragment_depth = q.fragment_depth != 0;
     if (q.template_stages) cfg.template_stages.assign(q.template_stages, q.template_stages + q.n_template_stages);
     cfg.ceiling = q.ceiling != 0;
     if (q.has_budget_reads) cfg.budget_reads = q.budget_reads;
@@ -247,6 +248,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
         if (!cfg.bed_filepath.empty() || !cfg.tsv_filepath.empty() || cfg.amplicons_by_reference)
             refuse("a coverage profile does not take amplicon files");
     }
+    if (given(q.fragment_report) && !cfg.fragment_depth) refuse("a fragment report needs fragment_depth");
     if (q.has_regions &&
         (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL))
         refuse(words.refuses + " go together with a coverage profile");
@@ -313,6 +315,21 @@ bool write_ceiling_report(const char* path, const qmcp_hip_ceiling_stats& cs, st
                  (unsigned long long)cs.short_bases, (unsigned long long)cs.excess_positions);
     std::fprintf(f, "max_kept_depth\t%u\nregions_in\t%u\nregions_used\t%u\nrecords_written\t%u\n", cs.max_kept_depth,
                  cs.regions_in, cs.regions_used, (unsigned)written);
+    return std::fclose(f) == 0;
+}
+
+// stat<TAB>value: the qmcp_hip_fragment_stats and the records written
+bool write_fragment_report(const char* path, const qmcp_hip_fragment_stats& fs, std::int64_t written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "segments_placed\t%llu\nsegments_clipped\t%llu\nsegments_emptied\t%llu\nbases_in\t%llu\n"
+                    "bases_removed\t%llu\ntemplates_overlapping\t%llu\n",
+                 (unsigned long long)fs.n_placed, (unsigned long long)fs.n_clipped, (unsigned long long)fs.n_emptied,
+                 (unsigned long long)fs.bases_in, (unsigned long long)fs.bases_removed,
+                 (unsigned long long)fs.n_templates_overlapping);
+    std::fprintf(f, "max_group\t%u\nms_clip\t%.6g\nrecords_written\t%u\n", fs.max_group, (double)fs.ms_clip,
+                 (unsigned)written);
     return std::fclose(f) == 0;
 }
 
@@ -471,6 +488,8 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
     if (mode == Mode::DEDUP && given(q.dedup_report)) reported = write_dedup_report(q.dedup_report, *hip);
     if (mode == Mode::CEILING && given(q.ceiling_report))
         reported = write_ceiling_report(q.ceiling_report, hip->last_ceiling_stats(), written[0]);
+    if (mode == Mode::TEMPLATES && given(q.fragment_report))
+        reported = write_fragment_report(q.fragment_report, hip->last_fragment_stats(), written[0]);
     if (mode == Mode::PROPORTIONAL && given(q.proportional_report))
         reported = write_proportional_report(q.proportional_report, hip->last_proportional_stats(), written[0]);
     if (mode == Mode::BUDGET && given(q.budget_report))

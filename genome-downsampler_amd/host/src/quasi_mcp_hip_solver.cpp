@@ -471,13 +471,21 @@ std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates(std::uint32_t
     }
     const std::vector<std::uint32_t>& stages = bam_api.template_stages();
     std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    const int rc = qmcp_hip_solve_templates_host(ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(),
-                                                 seg.template_ids.data(), n, seg.n_templates, seg.contig_lengths.data(),
-                                                 (std::uint32_t)seg.contig_lengths.size(), required_cover,
-                                                 stages.empty() ? nullptr : stages.data(), (std::uint32_t)stages.size(),
-                                                 mask.data(), &stats_, &tpstats_);
+    frstats_ = qmcp_hip_fragment_stats{};
+    const bool fragments = bam_api.fragment_depth();
+    const int rc = fragments
+        ? qmcp_hip_solve_fragments_host(ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(),
+                                        seg.template_ids.data(), n, seg.n_templates, seg.contig_lengths.data(),
+                                        (std::uint32_t)seg.contig_lengths.size(), required_cover,
+                                        stages.empty() ? nullptr : stages.data(), (std::uint32_t)stages.size(), mask.data(),
+                                        &stats_, &tpstats_, &frstats_)
+        : qmcp_hip_solve_templates_host(ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(),
+                                        seg.template_ids.data(), n, seg.n_templates, seg.contig_lengths.data(),
+                                        (std::uint32_t)seg.contig_lengths.size(), required_cover,
+                                        stages.empty() ? nullptr : stages.data(), (std::uint32_t)stages.size(), mask.data(),
+                                        &stats_, &tpstats_);
     if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_templates_host", rc);
+    if (rc != QMCP_OK) die(fragments ? "qmcp_hip_solve_fragments_host" : "qmcp_hip_solve_templates_host", rc);
     breakdown_ = qmcp_hip_host_breakdown{};
     std::vector<bam_api::BAMReadId> records = records_of_kept_segments(seg, mask);
     ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -505,8 +513,23 @@ std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates_profile(std::
     }
     const std::vector<std::uint32_t>& stages = bam_api.template_stages();
     std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    // fragment depth: the clip first, the profile entry on its columns (two calls)
+    frstats_ = qmcp_hip_fragment_stats{};
+    std::vector<std::uint32_t> clipped_starts, clipped_ids;
+    if (bam_api.fragment_depth()) {
+        clipped_starts.resize(n);
+        clipped_ids.resize(n);
+        const int rc0 = qmcp_hip_clip_templates_host(ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(),
+                                                     seg.template_ids.data(), n, seg.n_templates, seg.contig_lengths.data(),
+                                                     (std::uint32_t)seg.contig_lengths.size(), clipped_starts.data(),
+                                                     clipped_ids.data(), &frstats_);
+        if (rc0 == QMCP_EINVAL || rc0 == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+        if (rc0 != QMCP_OK) die("qmcp_hip_clip_templates_host", rc0);
+    }
+    const std::uint32_t* starts = bam_api.fragment_depth() ? clipped_starts.data() : seg.starts.data();
+    const std::uint32_t* contig_ids = bam_api.fragment_depth() ? clipped_ids.data() : seg.contig_ids.data();
     const int rc = qmcp_hip_solve_templates_profile_host(
-        ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(), seg.template_ids.data(), n, seg.n_templates,
+        ctx_, starts, seg.ends.data(), contig_ids, seg.template_ids.data(), n, seg.n_templates,
         seg.contig_lengths.data(), (std::uint32_t)seg.contig_lengths.size(), offsets.data(), region_starts.data(),
         region_ends.data(), caps.data(), default_cap, 0u, required_cover, stages.empty() ? nullptr : stages.data(),
         (std::uint32_t)stages.size(), mask.data(), &stats_, &tpstats_, &tqstats_);

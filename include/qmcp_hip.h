@@ -989,7 +989,8 @@ int qmcp_hip_solve_pairs_device(qmcp_hip_ctx* ctx,
  * qmcp_hip_solve_pairs_* for the same stages, bit for bit; (2) ids that are all distinct with the one stage
  * {max_coverage} give the mask of qmcp_hip_solve_by_contig_* bit for bit; (3) one stage gives
  * qmcp_hip_solve_by_contig_* at max_coverage followed by template completion.
- * Not claimed: that S_k is minimum among whole-template solutions.
+ * Not claimed: that S_k is minimum among whole-template solutions.  (Depth counted once per template where its
+ * segments overlap: qmcp_hip_solve_fragments_* below.)
  * Errors: the stage-list and max_coverage errors of qmcp_hip_solve_pairs_host, then template_ids == NULL or
  * n_templates == 0 with n_reads > 0 (QMCP_EINVAL), all on the host before the context is looked at and before anything
  * is copied.  An id >= n_templates is found on the device: QMCP_EINVAL with a message; the mask has been cleared by
@@ -1052,8 +1053,8 @@ int qmcp_hip_solve_templates_device(qmcp_hip_ctx* ctx,
  * give the mask of qmcp_hip_solve_profile_* for the same table; (3) every cap equal to M, regions present, gives the mask
  * of qmcp_hip_solve_templates_* (another route, the same canonical rule); (4) one stage gives qmcp_hip_solve_profile_*
  * followed by template completion.
- * Not claimed: that S_k is minimum among whole-template solutions; that more stages are better; overlap-corrected depth
- * inside a template.
+ * Not claimed: that S_k is minimum among whole-template solutions; that more stages are better.  (Fragment depth under a
+ * cap table is two calls: qmcp_hip_clip_templates_* below, then this entry on its columns.)
  * Errors, all on the host before the context is looked at and before anything is copied or launched: those of
  * qmcp_hip_solve_templates_host (stage list, max_coverage == 0 or >= 2^31, template_ids == NULL, n_templates == 0), then
  * those of qmcp_hip_solve_profile_host (table shape QMCP_EINVAL, a cap or default_cap of 2^31 or more QMCP_ERANGE, unknown
@@ -1095,6 +1096,79 @@ int qmcp_hip_solve_templates_profile_device(qmcp_hip_ctx* ctx,
                                             const uint32_t* stages /* may be NULL */, uint32_t n_stages,
                                             uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                             qmcp_hip_template_stats* tstats, qmcp_hip_template_profile_stats* qstats);
+
+/* Fragment depth: a template counts ONCE where its segments overlap.  The template entries above count depth per
+ * segment, so where the two mates of a short-insert pair overlap one molecule is depth 2; here it is depth 1, as in
+ * mosdepth, samtools depth -s and GATK.
+ * Input: the segments of qmcp_hip_solve_templates_host: [start, end] inclusive on contig_id or QMCP_NO_CONTIG,
+ * template_ids[i] < n_templates, contig_lengths / n_contigs and limits as in qmcp_hip_solve_by_contig_host.
+ * Definition: clip(rows).  Take the placed segments of each (template id, contig) group in the order (start ascending,
+ * input index ascending); reach is the largest end among the group's earlier members, if there are any.  A member with
+ * start <= reach < end gets start' = reach + 1; a member with end <= reach becomes unplaced (its contig id becomes
+ * QMCP_NO_CONTIG, its start is unchanged); every other row is unchanged.  Ends never change.  The output is two columns
+ * in INPUT order: clipped starts and clipped contig ids.  After clip the placed segments of a template are pairwise
+ * disjoint and their union per contig is the union before, so depth per segment on the clipped columns is FRAGMENT
+ * DEPTH: the number of templates that cover a position.  clip is idempotent.  Gaps between mates are not filled.
+ * qmcp_hip_clip_templates_* returns the two columns, for depth_report, depth_track or qmcp_hip_solve_templates_profile_*
+ * (fragment depth there, in two calls).  qmcp_hip_solve_fragments_* is qmcp_hip_solve_templates_* on clip(rows), bit for
+ * bit: the mask and every per-stage statistic.  An emptied segment is, like an unplaced one, never a candidate and
+ * enters only through its template.  The result holds whole templates and its fragment depth is at least
+ * min(fragment depth of all rows, max_coverage) everywhere.
+ * Identities: (1) rows in which no two segments of one template overlap give qmcp_hip_solve_templates_*: the mask and
+ * every field of qmcp_hip_template_stats except the times; (2) ids that are all distinct with the one stage
+ * {max_coverage} give the mask of qmcp_hip_solve_by_contig_*.
+ * Not claimed: that the result is minimum among whole-template solutions; physical coverage (the gap between mates); a
+ * fused entry under a cap table; compositions with the other modes; a _begin / _end form.
+ * Errors: those of qmcp_hip_solve_templates_host in its order (the clip entries: template_ids == NULL or n_templates == 0
+ * with n_reads > 0), on the host before the context is looked at; then null buffers, the by-contig limits, and for the
+ * clip entries an output that overlaps an input column (QMCP_EINVAL).  Then, on the device and BEFORE anything is
+ * clipped: a template id >= n_templates (QMCP_EINVAL), a bad contig id (QMCP_EINVAL), a read with start > end or
+ * end >= its contig's length (QMCP_EREAD), with the by-contig messages -- a bad row inside an overlapping group is not
+ * hidden by being emptied.  After a device error the clip outputs are untouched; the solve's mask has been cleared, as
+ * in the templates entry, and the host entry does not write keep_mask_out.
+ * fstats (may be NULL).  A call in which no template has two segments is the identity: it costs the validation and a
+ * copy and launches no sort or scan kernel.  Otherwise: a stable LSD radix sort of the rows by the bytes in use of
+ * (template id, contig id, start), a segmented running maximum of the ends (no atomics, deterministic) and one pass that
+ * writes both columns.  Device memory: 24 bytes per row for the sort, 8 for the clipped columns of the solve entries.
+ * The solve entries never modify the caller's columns: the clipped copies live in the context.  The device entries take
+ * the columns in device memory, are ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and return after
+ * the work has completed. */
+typedef struct qmcp_hip_fragment_stats {
+    uint64_t n_placed;                 /* placed segments going in                                                     */
+    uint64_t n_clipped;                /* start moved, still placed                                                    */
+    uint64_t n_emptied;                /* inside what earlier members of the group cover: unplaced in the output       */
+    uint64_t bases_in;                 /* bases of the placed segments going in                                        */
+    uint64_t bases_removed;            /* bases clipped away = per-segment depth - fragment depth, summed              */
+    uint64_t n_templates_overlapping;  /* templates with a clipped or emptied segment                                  */
+    uint32_t max_group;                /* most placed segments of one template on one contig                           */
+    float ms_clip;                     /* device time of the clip: validation, sort, scan, write-back                  */
+} qmcp_hip_fragment_stats;
+int qmcp_hip_clip_templates_host(qmcp_hip_ctx* ctx,
+                                 const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                 const uint32_t* template_ids, uint64_t n_reads, uint32_t n_templates,
+                                 const uint32_t* contig_lengths, uint32_t n_contigs,
+                                 uint32_t* clipped_starts_out, uint32_t* clipped_contig_ids_out,
+                                 qmcp_hip_fragment_stats* fstats);
+int qmcp_hip_clip_templates_device(qmcp_hip_ctx* ctx,
+                                   const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                   const uint32_t* d_template_ids, uint64_t n_reads, uint32_t n_templates,
+                                   const uint32_t* contig_lengths, uint32_t n_contigs,
+                                   uint32_t* d_clipped_starts_out, uint32_t* d_clipped_contig_ids_out, void* hip_stream,
+                                   qmcp_hip_fragment_stats* fstats);
+int qmcp_hip_solve_fragments_host(qmcp_hip_ctx* ctx,
+                                  const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                  const uint32_t* template_ids, uint64_t n_reads, uint32_t n_templates,
+                                  const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                  const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                  uint64_t* keep_mask_out, qmcp_hip_stats* stats, qmcp_hip_template_stats* tstats,
+                                  qmcp_hip_fragment_stats* fstats);
+int qmcp_hip_solve_fragments_device(qmcp_hip_ctx* ctx,
+                                    const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                    const uint32_t* d_template_ids, uint64_t n_reads, uint32_t n_templates,
+                                    const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                    const uint32_t* stages /* may be NULL */, uint32_t n_stages,
+                                    uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
+                                    qmcp_hip_template_stats* tstats, qmcp_hip_fragment_stats* fstats);
 
 /* Ceiling downsampling: the kept depth never EXCEEDS the cap, and as many reads as possible are kept.  Every other entry
  * of this header is a floor (kept depth >= min(cov, cap), fewest reads) and may overshoot the cap; this one is for a hard
