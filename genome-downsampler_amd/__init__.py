@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_fragments_host", "qmcp_hip_solve_fragments_device",
     "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
     "qmcp_hip_solve_budget_host", "qmcp_hip_solve_budget_device",
+    "qmcp_hip_solve_mean_depth_host", "qmcp_hip_solve_mean_depth_device",
     "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
     "qmcp_hip_solve_proportional_host", "qmcp_hip_solve_proportional_device",
 )
@@ -65,6 +66,7 @@ PAIR_MAX_STAGES = 16  # QMCP_PAIR_MAX_STAGES
 CEILING_WHOLE_PAIRS = 1  # QMCP_CEILING_WHOLE_PAIRS
 BUDGET_WHOLE_PAIRS = 1  # QMCP_BUDGET_WHOLE_PAIRS
 BUDGET_CURVE_MAX = 8191  # QMCP_BUDGET_CURVE_MAX: the last coverage the curve of a budget solve reaches
+MEAN_DEPTH_WHOLE_PAIRS = 1  # QMCP_MEAN_DEPTH_WHOLE_PAIRS
 PROPORTION_DEN_MAX = 1 << 20  # QMCP_PROPORTION_DEN_MAX: the largest denominator of a proportional solve's fraction
 REPLICATES_MAX = 16  # QMCP_REPLICATES_MAX
 REPLICATES_WHOLE_PAIRS, REPLICATES_SHORTFALL = 1, 2  # QMCP_REPLICATES_*
@@ -202,6 +204,47 @@ class BudgetStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class MeanDepthStats(C.Structure):
+    """qmcp_hip_mean_depth_stats: the coverage a mean-depth solve ended on (coverage = M*), the bases it keeps inside the
+    regions there (kept_bases, in n_kept reads) and what one coverage more would keep (bases_above where a probe measured
+    it, else the bound S_R(M* + 1) = bound_above that ruled it out), the regions (positions, regions_in, regions_used),
+    the data's depth inside them (total_bases) and everywhere (max_depth, top) and the search's cost"""
+    _fields_ = [("budget", C.c_uint64), ("positions", C.c_uint64), ("reads_placed", C.c_uint64), ("n_kept", C.c_uint64),
+                ("kept_bases", C.c_uint64), ("bases_above", C.c_uint64), ("bound_above", C.c_uint64),
+                ("total_bases", C.c_uint64), ("coverage", C.c_uint32), ("max_depth", C.c_uint32), ("top", C.c_uint32),
+                ("probes", C.c_uint32), ("curve_entries", C.c_uint32), ("saturated", C.c_uint32),
+                ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_mean_depth", C.c_float),
+                ("ms_solves", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+def region_positions(contig_lengths, region_offsets, region_starts, region_ends):
+    """|R| as qmcp_hip_solve_mean_depth_* counts it: per contig the regions (inclusive bounds, any order, overlaps
+    allowed) clipped to the contig -- one that begins at or beyond its length is dropped -- and merged; every position
+    when region_offsets is None"""
+    lengths = np.atleast_1d(np.asarray(contig_lengths, dtype=np.int64))
+    if region_offsets is None:
+        return int(lengths.sum())
+    offs = np.asarray(region_offsets, dtype=np.int64)
+    if offs.size != lengths.size + 1:
+        raise ValueError("region_offsets needs n_contigs + 1 entries")
+    r0, r1 = (np.zeros(0, np.int64) if a is None else np.asarray(a, dtype=np.int64) for a in (region_starts, region_ends))
+    if min(r0.size, r1.size) < int(offs[-1]):
+        raise ValueError("region_starts / region_ends are shorter than region_offsets says")
+    total = 0
+    for c, length in enumerate(lengths.tolist()):
+        spans = sorted((int(s), min(int(e), length - 1)) for s, e in zip(r0[offs[c]:offs[c + 1]], r1[offs[c]:offs[c + 1]])
+                       if s < length)
+        reach = -1  # the last position counted so far
+        for s, e in spans:
+            if e > reach:
+                total += e - max(s, reach + 1) + 1
+                reach = e
+    return total
 
 
 class PairStats(C.Structure):
@@ -397,7 +440,9 @@ class DownsampleRequest(C.Structure):
         + [(name, C.POINTER(C.c_uint32)) for name in ("region_offsets", "region_starts", "region_ends", "region_caps")]
         + [("n_refs", C.c_uint64), ("pair_stages", C.POINTER(C.c_uint32)), ("template_stages", C.POINTER(C.c_uint32)),
            ("fragment_report", C.c_char_p), ("ceiling_report", C.c_char_p), ("budget_report", C.c_char_p),
-           ("budget_reads", C.c_uint64), ("budget_fraction", C.c_double), ("replicates_further", C.POINTER(C.c_uint32)),
+           ("budget_reads", C.c_uint64), ("budget_fraction", C.c_double), ("mean_depth_targets", C.c_char_p),
+           ("mean_depth_report", C.c_char_p), ("budget_bases", C.c_uint64), ("mean_depth", C.c_double),
+           ("replicates_further", C.POINTER(C.c_uint32)),
            ("replicates_template", C.c_char_p), ("replicates_report", C.c_char_p)]
         + [(name, C.c_uint32) for name in ("max_coverage", "min_len", "min_mapq", "target_padding", "report_bins",
                                            "track_cap", "n_ladder_levels", "default_cap", "n_pair_stages",
@@ -405,7 +450,7 @@ class DownsampleRequest(C.Structure):
         + [(name, C.c_int32) for name in ("amplicon_mode", "per_reference", "amplicons_by_reference", "keep_off_target",
                                           "dedup", "has_regions", "pair_aware", "template_aware", "split_spliced",
                                           "include_secondary", "fragment_depth", "ceiling", "has_budget_reads",
-                                          "has_replicates")]
+                                          "has_budget_bases", "has_mean_depth", "has_replicates")]
         + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
            ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
@@ -566,6 +611,13 @@ _hip.qmcp_hip_solve_ceiling_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_
 _hip.qmcp_hip_solve_budget_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
                                             C.c_uint64, C.c_uint32, _u64p, C.c_uint32, _u64p, C.POINTER(Stats),
                                             C.POINTER(BudgetStats)]
+_hip.qmcp_hip_solve_mean_depth_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
+                                                C.c_uint64, _u32p, _u32p, _u32p, C.c_uint32, _u64p, C.c_uint32, _u64p,
+                                                C.POINTER(Stats), C.POINTER(MeanDepthStats)]
+_hip.qmcp_hip_solve_mean_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                                  C.c_uint32, C.c_uint32, C.c_uint64, _u32p, _u32p, _u32p, C.c_uint32,
+                                                  _u64p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                                  C.POINTER(MeanDepthStats)]
 _hip.qmcp_hip_solve_budget_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(BudgetStats)]
@@ -736,6 +788,7 @@ class Solver:
         self.last_ceiling_stats = None
         self.last_proportional_stats = None
         self.last_budget_stats = None
+        self.last_mean_depth_stats = None
         self.last_replicates_stats = None
         self.last_replicate_solve_stats = None
 
@@ -1233,6 +1286,73 @@ class Solver:
         self.last_stats, self.last_budget_stats = st, bs
         out = (int(bs.coverage), bs)
         return out + (table[:bs.curve_entries],) if curve else out
+
+    @staticmethod
+    def _base_budget_of(mean_depth, budget_bases, positions):
+        """the base budget of a mean-depth solve: budget_bases, or floor(mean_depth * positions)"""
+        if (mean_depth is None) == (budget_bases is None):
+            raise ValueError("a mean-depth solve takes exactly one of mean_depth and budget_bases")
+        if budget_bases is not None:
+            if int(budget_bases) < 0 or int(budget_bases) >= 1 << 64:
+                raise ValueError("budget_bases must fit an unsigned 64-bit count")
+            return int(budget_bases)
+        mean = float(mean_depth)
+        if not (mean >= 0.0 and math.isfinite(mean)):
+            raise ValueError("mean_depth must be a finite depth of at least 0")
+        budget = int(math.floor(mean * int(positions)))
+        if budget >= 1 << 64:
+            raise ValueError("mean_depth * positions must fit an unsigned 64-bit count")
+        return budget
+
+    def _mean_depth_tables(self, lengths, mean_depth, budget_bases, region_offsets, region_starts, region_ends, curve):
+        offs, r0, r1, _ = self._region_tables(lengths.size, region_offsets, region_starts, region_ends, None)
+        positions = region_positions(lengths, offs, r0, r1) if mean_depth is not None else None
+        budget = self._base_budget_of(mean_depth, budget_bases, positions)
+        cap = BUDGET_CURVE_MAX + 1 if curve else 0
+        return offs, r0, r1, budget, cap, np.zeros(cap, dtype=np.uint64) if curve else None
+
+    def solve_mean_depth(self, starts, ends, contig_ids, contig_lengths, max_coverage, mean_depth=None, budget_bases=None,
+                         region_offsets=None, region_starts=None, region_ends=None, flags=0, curve=False):
+        """mean-depth downsampling (qmcp_hip_solve_mean_depth_host): solve_by_contig's reads, and the DEEPEST coverage M*
+        in 0 .. min(max_coverage, largest depth) whose solve keeps at most budget_bases bases inside the regions -- or
+        mean_depth, a mean over the regions' positions: floor(mean_depth * region_positions(...)).  Contig c owns regions
+        [region_offsets[c], region_offsets[c + 1]) of region_starts / region_ends (inclusive, any order, overlaps
+        allowed, clipped to the contig); region_offsets=None: every position.  flags: MEAN_DEPTH_WHOLE_PAIRS counts and
+        returns whole pairs (reads 2q, 2q + 1) among the placed reads.  -> (mask, M*, MeanDepthStats), the mask being
+        solve_by_contig's at M* bit for bit (all zero for M* == 0); curve=True appends S_R(M) = sum over the regions of
+        min(cov, M), M = 0 .. min(top, BUDGET_CURVE_MAX), as a uint64 array.  last_stats: the solve at M*"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, budget, cap, table = self._mean_depth_tables(lengths, mean_depth, budget_bases, region_offsets,
+                                                                   region_starts, region_ends, curve)
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        st, ms = Stats(), MeanDepthStats()
+        _check(_hip.qmcp_hip_solve_mean_depth_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                   lengths.size, int(max_coverage), budget, _p32(offs), _p32(r0), _p32(r1),
+                                                   int(flags), _p64(table), cap, _p64(mask), C.byref(st), C.byref(ms)))
+        self.last_stats, self.last_mean_depth_stats = st, ms
+        out = (mask[:mask_words(n)], int(ms.coverage), ms)
+        return out + (table[:ms.curve_entries],) if curve else out
+
+    def solve_mean_depth_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_mask,
+                                mean_depth=None, budget_bases=None, region_offsets=None, region_starts=None,
+                                region_ends=None, flags=0, curve=False, stream=0):
+        """solve_mean_depth on device pointers (ints); the region tables are host arrays, the input-order mask is
+        written to d_mask.  -> (M*, MeanDepthStats), with curve=True also the curve"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, r0, r1, budget, cap, table = self._mean_depth_tables(lengths, mean_depth, budget_bases, region_offsets,
+                                                                   region_starts, region_ends, curve)
+        st, ms = Stats(), MeanDepthStats()
+        _check(_hip.qmcp_hip_solve_mean_depth_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                     C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                     int(max_coverage), budget, _p32(offs), _p32(r0), _p32(r1), int(flags),
+                                                     _p64(table), cap, C.c_void_p(d_mask), C.c_void_p(stream),
+                                                     C.byref(st), C.byref(ms)))
+        self.last_stats, self.last_mean_depth_stats = st, ms
+        out = (int(ms.coverage), ms)
+        return out + (table[:ms.curve_entries],) if curve else out
 
     def solve_pairs(self, starts, ends, contig_ids, contig_lengths, max_coverage, stages=None):
         """pair-aware downsampling (qmcp_hip_solve_pairs_host): reads (2q, 2q + 1) are pair q, stages the rising targets
@@ -2326,6 +2446,9 @@ class _Mode:
         self.amplicon_files, self.quality_solver = amplicon_files, quality_solver
 
 
+_MEAN_DEPTH = _Mode("mean-depth downsampling", ("a proportion", "replicates", "a budget", "ceiling", "pair_aware",
+                                                "template_aware", "targets", "a depth report", "a depth track",
+                                                "a coverage ladder", "stratify", "dedup", "a coverage profile"))
 _PROPORTIONAL = _Mode("proportional downsampling", ("replicates", "a budget", "ceiling", "pair_aware", "template_aware",
                                                     "targets", "a depth report", "a depth track", "a coverage ladder",
                                                     "stratify", "dedup", "a coverage profile"))
@@ -2386,7 +2509,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    template_report=None, template_targets=None, template_target_padding=0, template_profile=None,
                    ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None,
                    replicates=None, replicates_out=None, replicates_report=None, proportion=None, proportion_floor=0,
-                   proportional_report=None, fragment_depth=False, fragment_report=None):
+                   proportional_report=None, fragment_depth=False, fragment_report=None, mean_depth=None,
+                   budget_bases=None, mean_depth_targets=None, mean_depth_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2497,9 +2621,20 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     floor still holds.  proportional_report (a path) gets a stat<TAB>value TSV with the ProportionalStats and
     records_written.  Needs per_reference=True; not together with replicates, a budget, ceiling, pair_aware,
     template_aware, targets, report, track, ladder, stratify, dedup, profile, amplicon files or
-    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
+    "quasi-mcp-hip-quality" (ValueError).  None: nothing changes.
+    mean_depth=d or budget_bases=N (BamApiConfig::mean_depth / budget_bases) with mean_depth_targets (a BED3+ file; None:
+    every position of every reference): the deepest downsample whose written records hold at most N bases inside the
+    regions -- or at most floor(d * the regions' positions), the regions clipped to their references and merged: "make
+    this file 30 x", "bring the exome to 100 x mean on target".  max_coverage is the upper end of the search; one
+    qmcp_hip_solve_mean_depth_host call with MEAN_DEPTH_WHOLE_PAIRS on the reads as the budget flow pairs them.  The
+    output is written from the final mask and no find_pairs follows (it would add bases).  mean_depth_report (a path)
+    gets a stat<TAB>value TSV with the MeanDepthStats, records_written and the two means mean_depth_in and
+    mean_depth_kept over the regions' positions, then one M<TAB>bases line per entry of the curve S_R(M).  Needs
+    per_reference=True; exactly one of mean_depth and budget_bases; not together with a proportion, replicates, a
+    budget, ceiling, pair_aware, template_aware, targets, report, track, ladder, stratify, dedup, profile, amplicon
+    files or "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
     _need_host()
-    given = {"replicates": replicates is not None,
+    given = {"a proportion": proportion is not None, "replicates": replicates is not None,
              "a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
              "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
              "a depth report": bool(report), "a depth track": track is not None, "a coverage ladder": ladder is not None,
@@ -2552,7 +2687,21 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         raise ValueError("fragment_report needs fragment_depth=True")
     if (proportion_floor or proportional_report is not None) and proportion is None:
         raise ValueError("proportion_floor and proportional_report need proportion")
-    if proportion is not None:
+    if (mean_depth_targets is not None or mean_depth_report is not None) and mean_depth is None and budget_bases is None:
+        raise ValueError("mean_depth_targets and mean_depth_report need mean_depth or budget_bases")
+    if mean_depth is not None or budget_bases is not None:
+        if mean_depth is not None and budget_bases is not None:
+            raise ValueError("mean-depth downsampling takes mean_depth or budget_bases, not both")
+        if budget_bases is not None and not 0 <= int(budget_bases) < 1 << 64:
+            raise ValueError("budget_bases must fit an unsigned 64-bit count")
+        if mean_depth is not None and not (float(mean_depth) >= 0.0 and math.isfinite(float(mean_depth))):
+            raise ValueError("mean_depth must be a finite depth of at least 0")
+        need_per_reference(_MEAN_DEPTH)
+        refuse(_MEAN_DEPTH)
+        fields.update(has_mean_depth=mean_depth is not None, mean_depth=float(mean_depth or 0.0),
+                      has_budget_bases=budget_bases is not None, budget_bases=int(budget_bases or 0),
+                      mean_depth_targets=mean_depth_targets, mean_depth_report=mean_depth_report)
+    elif proportion is not None:
         num, den = as_ratio(proportion)
         if den > PROPORTION_DEN_MAX:
             raise ValueError(f"proportion: the denominator must not exceed {PROPORTION_DEN_MAX}")

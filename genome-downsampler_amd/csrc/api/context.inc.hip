@@ -239,6 +239,10 @@ struct qmcp_hip_ctx {
     // budget solves (api/budget.inc.hip), all its own: the accumulators, the curve and the depth histogram in one buffer
     // (BudgetWord words | curve | histogram), and the second input-order mask of the probes
     DevBuf bg_acc, bg_mask;
+    // mean-depth solves (api/mean_depth.inc.hip; the accumulators and the second mask are the budget's bg_acc / bg_mask,
+    // with the MeanDepthWord words behind the histogram): the merged region table in contig coordinates (offs | rs | re |
+    // cum) followed by the batches' form of it (rpos | rcum), and the reads' weights
+    DevBuf md_tab, md_w;
     // disjoint replicates (api/replicates.inc.hip), all its own: the two sets of free reads' columns (starts, ends, input
     // indices) that ping-pong between replicates, the scanned word popcounts of the taken candidates and their spine, the
     // two offset tables, the candidates' taken bits, the input-order taken mask (whole pairs, several batches), the packed

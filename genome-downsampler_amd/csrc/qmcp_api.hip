@@ -93,6 +93,8 @@
 //                       both ends of the fraction's range, and a tally of the kept bases
 //   budget              (by_contig) the deepest coverage whose by-contig solve fits a number of reads: one grouping, the
 //                       curve S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
+//   mean_depth          (budget) the deepest coverage whose by-contig solve fits a number of bases inside a region set: the
+//                       budget's flow with the histogram restricted to the regions and a weighted count per probe
 //   replicates          (by_contig, depth_report) one read set split into disjoint downsamples: the batch loop at the
 //                       first coverage, every further replicate solved on the reads still free, replicate-major over the
 //                       one grouping's batches
@@ -123,4 +125,5 @@
 #include "api/ceiling.inc.hip"
 #include "api/proportional.inc.hip"
 #include "api/budget.inc.hip"
+#include "api/mean_depth.inc.hip"
 #include "api/replicates.inc.hip"

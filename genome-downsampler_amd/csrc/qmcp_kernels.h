@@ -561,6 +561,26 @@ void launch_budget_tally(hipStream_t st, const uint32_t* cov, uint32_t ltot, uin
 void launch_budget_curve(hipStream_t st, const unsigned long long* hist, uint32_t H, unsigned long long* curve);
 void launch_budget_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, uint64_t* mask, unsigned long long* acc);
 
+// mean-depth downsampling (kernels/mean_depth.inc.hip; api/mean_depth.inc.hip drives them, with launch_budget_curve and
+// launch_budget_finish above, and launch_budget_tally when there is no region table).  launch_md_tally: launch_budget_tally
+// with the histogram and the sum taken over the region positions of the batch only -- merged region k of the batch starts
+// at rpos[k] on the batch's concatenated axis and holds the ranks from rcum[k] on, n_pos positions in all -- while
+// acc[kBudgetMaxDepth] still takes the largest depth of ALL ltot positions.  launch_md_weights, once per call: w[i] = the
+// positions of read i inside its contig's merged regions (offs / rs / re / cum: target_table.h's table, contig
+// coordinates), or its span without a table; 0 for an unplaced read.  launch_md_count, per probe: acc[kMdBases] += the sum
+// of w over the set bits of the input-order mask, acc[kMdKept] += their number (both cleared by the caller).
+enum MeanDepthWord : uint32_t {
+    kMdBases = 0,  // a probe's kept bases inside the regions
+    kMdKept,       // a probe's kept reads
+    kMdWords = 2
+};
+void launch_md_tally(hipStream_t st, const uint32_t* cov, uint32_t ltot, const uint32_t* rpos, const uint32_t* rcum,
+                     uint32_t n_reg, uint32_t n_pos, uint32_t H, unsigned long long* acc, unsigned long long* hist);
+void launch_md_weights(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids, uint32_t n,
+                       uint32_t n_contigs, bool has_table, const uint32_t* offs, const uint32_t* rs, const uint32_t* re,
+                       const uint32_t* cum, uint32_t n_regions, uint32_t* w);
+void launch_md_count(hipStream_t st, const uint64_t* mask, const uint32_t* w, uint64_t n_reads, unsigned long long* acc);
+
 // disjoint replicates (kernels/replicates.inc.hip; api/replicates.inc.hip drives them).  A replicate's candidates are n
 // reads in three columns with an origin column (origin_in: the grouping's Rec{key, index} array when `first`, a plain
 // column of input indices otherwise); `taken` has one bit per candidate (the solve's mask, or the input-order taken mask

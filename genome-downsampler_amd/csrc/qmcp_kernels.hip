@@ -66,6 +66,8 @@
 //                            exact integers with its cut flag, and the tally of the placed and the kept reads' bases
 //   budget                   budget downsampling: the depth histogram of a call, the curve S(M) = sum of min(cov, M) from
 //                            it, and a probe's pair completion with its popcount
+//   mean_depth               mean-depth downsampling: the budget's histogram over the positions of a region set only, the
+//                            reads' weights inside it, and a probe's kept bases
 //   replicates               disjoint replicates: the dense split of a replicate's candidates into labels and the next
 //                            replicate's columns (LDS-staged), the next contig offsets, the taken mask and its gather,
 //                            the mates' completion, the packed mask of one label
@@ -118,6 +120,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/ceiling.inc.hip"
 #include "kernels/proportional.inc.hip"
 #include "kernels/budget.inc.hip"
+#include "kernels/mean_depth.inc.hip"
 #include "kernels/replicates.inc.hip"
 
 }  // namespace qmcp

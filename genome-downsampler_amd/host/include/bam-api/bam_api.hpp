@@ -119,6 +119,17 @@ struct BamApiConfig {
     // ceiling refuses, nor with ceiling or a coverage profile (std::invalid_argument otherwise).  Neither: nothing changes.
     std::optional<std::uint64_t> budget_reads;
     std::optional<double> budget_fraction;
+    // Mean-depth downsampling: the deepest coverage in 0 .. min(max_coverage, largest depth) whose solve, completed to
+    // whole pairs, writes at most budget_bases bases inside the regions of mean_depth_targets_filepath (a BED3+ file as
+    // targets_filepath, no padding; empty: every position of every reference) -- or at most floor(mean_depth * the
+    // regions' positions), the mean people quote as "30 x" or MEAN_TARGET_COVERAGE (QuasiMcpHipSolver::solve_mean_depth /
+    // qmcp_hip_solve_mean_depth_host with QMCP_MEAN_DEPTH_WHOLE_PAIRS).  The output is written from the final mask
+    // WITHOUT find_pairs, which would add bases.  Exactly one of the two; mean_depth finite and >= 0.  Needs
+    // per_reference and goes together with nothing that budget downsampling refuses, nor with a budget, replicates, a
+    // proportion or a coverage profile (std::invalid_argument otherwise).  Neither: nothing changes.
+    std::optional<double> mean_depth;
+    std::optional<std::uint64_t> budget_bases;
+    std::filesystem::path mean_depth_targets_filepath;
     // Disjoint replicates: the coverages of replicates 2 .. K (an empty list: one replicate); replicate 1 is solved at
     // the solve's max_coverage, replicate r + 1 on the reads the earlier ones left free
     // (QuasiMcpHipSolver::solve_replicates / qmcp_hip_solve_replicates_host with QMCP_REPLICATES_WHOLE_PAIRS |
@@ -187,6 +198,13 @@ class BamApi {
     // BamApiConfig::budget_reads / budget_fraction: whether one is set, and the budget for a number of placed reads
     bool budget() const { return budget_reads_.has_value() || budget_fraction_.has_value(); }
     std::uint64_t budget_for(std::uint64_t placed_reads) const;
+    // BamApiConfig::mean_depth / budget_bases: whether one is set, the regions of mean_depth_targets_filepath (none: every
+    // position), their positions after clipping to the references and merging, and the budget in bases
+    bool mean_depth() const { return mean_depth_.has_value() || budget_bases_.has_value(); }
+    bool has_mean_depth_regions() const { return has_mean_depth_regions_; }
+    const TargetRegions& mean_depth_regions() const { return mean_depth_regions_; }
+    std::uint64_t mean_depth_positions(const std::vector<std::uint32_t>& contig_lengths) const;
+    std::uint64_t base_budget_for(std::uint64_t positions) const;
     // BamApiConfig::replicates (not set: no replicate split)
     const std::optional<std::vector<std::uint32_t>>& replicates() const { return replicates_; }
     // BamApiConfig::proportion (not set: no proportional solve)
@@ -236,6 +254,10 @@ class BamApi {
     bool ceiling_ = false;
     std::optional<std::uint64_t> budget_reads_;
     std::optional<double> budget_fraction_;
+    std::optional<double> mean_depth_;
+    std::optional<std::uint64_t> budget_bases_;
+    TargetRegions mean_depth_regions_;
+    bool has_mean_depth_regions_ = false;
     std::optional<std::vector<std::uint32_t>> replicates_;
     std::optional<BamApiConfig::Proportion> proportion_;
     std::vector<std::uint32_t> pair_stages_;

@@ -130,6 +130,15 @@ class QuasiMcpHipSolver : public Solver {
     // without find_pairs.  std::invalid_argument for a BamApi without a budget and for what the library refuses
     std::unique_ptr<Solution> solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_budget_stats& last_budget_stats() const { return bgstats_; }
+    // Mean-depth downsampling for the reads of a BamApi built with BamApiConfig::mean_depth or budget_bases: one
+    // qmcp_hip_solve_mean_depth_host call with QMCP_MEAN_DEPTH_WHOLE_PAIRS, required_cover as the upper end of the search,
+    // the BamApi's mean-depth regions (none: every position) and BamApi::base_budget_for(their positions) as the budget.
+    // The Solution holds whole pairs already -- the caller writes it without find_pairs.  std::invalid_argument for a
+    // BamApi without a mean depth and for what the library refuses
+    std::unique_ptr<Solution> solve_mean_depth(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_mean_depth_stats& last_mean_depth_stats() const { return mdstats_; }
+    // S_R(M) = the bases inside the regions any answer at coverage M must hold, M = 0 .. curve_entries - 1
+    const std::vector<std::uint64_t>& last_mean_depth_curve() const { return mean_depth_curve_; }
     // Disjoint replicates for the reads of a BamApi built with BamApiConfig::replicates: one
     // qmcp_hip_solve_replicates_host call with QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL at required_cover,
     // then the BamApi's further coverages.  Returns one byte per read, the replicate that holds it (1-based, 0: none);
@@ -189,6 +198,8 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_budget_stats bgstats_{};
     qmcp_hip_replicates_stats rpstats_{};
     std::vector<std::uint64_t> budget_curve_;
+    qmcp_hip_mean_depth_stats mdstats_{};
+    std::vector<std::uint64_t> mean_depth_curve_;
     qmcp_hip_template_stats tpstats_{};
     qmcp_hip_template_profile_stats tqstats_{};
     qmcp_hip_fragment_stats frstats_{};

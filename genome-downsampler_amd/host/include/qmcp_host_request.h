@@ -59,6 +59,13 @@ typedef struct qmcp_host_downsample_request {
     const char* budget_report;
     uint64_t budget_reads;
     double budget_fraction;
+    /* mean-depth downsampling (mean_depth, budget_bases, mean_depth_targets_filepath): has_mean_depth != 0 and / or
+     * has_budget_bases != 0 ask for it; mean_depth_targets (a BED3+ file: the regions the bases are counted in) and
+     * mean_depth_report (stat<TAB>value lines, then the curve S_R) alone are refused */
+    const char* mean_depth_targets;
+    const char* mean_depth_report;
+    uint64_t budget_bases;
+    double mean_depth;
     /* disjoint replicates (replicates): has_replicates != 0 asks for them, replicate r + 2 at replicates_further[r],
      * written to replicates_template with its "{R}" replaced */
     const uint32_t* replicates_further;
@@ -89,6 +96,8 @@ typedef struct qmcp_host_downsample_request {
     int32_t fragment_depth;
     int32_t ceiling;
     int32_t has_budget_reads;
+    int32_t has_budget_bases;
+    int32_t has_mean_depth;
     int32_t has_replicates;
     /* proportional downsampling (proportion): has_proportion != 0 asks for it -- every position keeps
      * ceil(cov * proportion_num / proportion_den) of its depth, positions at or below proportion_floor whole,

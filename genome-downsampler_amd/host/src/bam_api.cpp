@@ -179,6 +179,50 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
         budget_reads_ = config.budget_reads;
         budget_fraction_ = config.budget_fraction;
     }
+    if (config.mean_depth.has_value() || config.budget_bases.has_value()) {
+        if (config.mean_depth.has_value() && config.budget_bases.has_value())
+            throw std::invalid_argument("mean-depth downsampling takes mean_depth or budget_bases, not both");
+        if (config.mean_depth.has_value() && !(*config.mean_depth >= 0.0 && std::isfinite(*config.mean_depth)))
+            throw std::invalid_argument("mean_depth must be a finite depth of at least 0");
+        if (!per_reference_)
+            throw std::invalid_argument("mean-depth downsampling needs per_reference: its probes are solved one reference "
+                                        "at a time");
+        if (config.proportion.has_value()) throw std::invalid_argument("mean-depth downsampling does not take a proportion");
+        if (config.replicates.has_value()) throw std::invalid_argument("mean-depth downsampling does not take replicates");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value())
+            throw std::invalid_argument("mean-depth downsampling does not take a budget");
+        if (config.ceiling) throw std::invalid_argument("mean-depth downsampling does not take ceiling");
+        if (config.pair_aware) throw std::invalid_argument("mean-depth downsampling does not take pair_aware");
+        if (config.template_aware) throw std::invalid_argument("mean-depth downsampling does not take template_aware");
+        if (!config.targets_filepath.empty()) throw std::invalid_argument("mean-depth downsampling does not take targets");
+        if (!config.coverage_ladder.empty())
+            throw std::invalid_argument("mean-depth downsampling does not take a coverage ladder");
+        if (!config.depth_report_filepath.empty())
+            throw std::invalid_argument("mean-depth downsampling does not take a depth report");
+        if (!config.depth_track_filepath.empty())
+            throw std::invalid_argument("mean-depth downsampling does not take a depth track");
+        if (config.stratify_by != Stratify::NONE)
+            throw std::invalid_argument("mean-depth downsampling does not take stratify_by");
+        if (config.dedup) throw std::invalid_argument("mean-depth downsampling does not take dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("mean-depth downsampling does not take amplicon files");
+        mean_depth_ = config.mean_depth;
+        budget_bases_ = config.budget_bases;
+        if (!config.mean_depth_targets_filepath.empty()) {
+            std::vector<std::string> names;
+            std::vector<std::uint32_t> lengths;
+            std::string err;
+            if (!read_bam_references(input_filepath_, names, lengths, &err)) {
+                std::fprintf(stderr, "[ERROR] %s\n", err.c_str());
+                std::exit(EXIT_FAILURE);  // (as read_bam_into on an unreadable input)
+            }
+            if (!target_regions_from_bed(config.mean_depth_targets_filepath, names, mean_depth_regions_, &err))
+                throw std::invalid_argument(err);
+            has_mean_depth_regions_ = true;
+        }
+    } else if (!config.mean_depth_targets_filepath.empty()) {
+        throw std::invalid_argument("mean_depth_targets need mean_depth or budget_bases");
+    }
     if (config.replicates.has_value()) {
         if (!per_reference_)
             throw std::invalid_argument("disjoint replicates need per_reference: every replicate is solved one reference "
@@ -457,6 +501,40 @@ std::uint64_t BamApi::budget_for(std::uint64_t placed_reads) const {
     if (!budget_fraction_.has_value()) throw std::invalid_argument("this BamApi was built without a budget");
     const double want = std::floor(*budget_fraction_ * static_cast<double>(placed_reads));
     return std::min(static_cast<std::uint64_t>(want), placed_reads);
+}
+
+// the regions clipped to their references (one that begins at or beyond the reference's length is dropped) and merged,
+// as qmcp_hip_solve_mean_depth_host counts them
+std::uint64_t BamApi::mean_depth_positions(const std::vector<std::uint32_t>& contig_lengths) const {
+    std::uint64_t total = 0;
+    if (!has_mean_depth_regions_) {
+        for (std::uint32_t l : contig_lengths) total += l;
+        return total;
+    }
+    const TargetRegions& t = mean_depth_regions_;
+    std::vector<std::pair<std::uint64_t, std::uint64_t>> spans;
+    for (std::size_t c = 0; c + 1 < t.offsets.size() && c < contig_lengths.size(); ++c) {
+        const std::uint64_t len = contig_lengths[c];
+        spans.clear();
+        for (std::uint32_t k = t.offsets[c]; k < t.offsets[c + 1]; ++k)
+            if (t.starts[k] < len) spans.emplace_back(t.starts[k], std::min<std::uint64_t>(t.ends[k], len - 1));
+        std::sort(spans.begin(), spans.end());
+        std::uint64_t next = 0;  // the first position not counted yet
+        for (const auto& s : spans)
+            if (s.second >= next) {
+                total += s.second - std::max(s.first, next) + 1;
+                next = s.second + 1;
+            }
+    }
+    return total;
+}
+
+std::uint64_t BamApi::base_budget_for(std::uint64_t positions) const {
+    if (budget_bases_.has_value()) return *budget_bases_;
+    if (!mean_depth_.has_value()) throw std::invalid_argument("this BamApi was built without a mean depth");
+    const double want = std::floor(*mean_depth_ * static_cast<double>(positions));
+    if (want >= 18446744073709551616.0) throw std::invalid_argument("mean_depth * positions exceeds 64 bits");
+    return static_cast<std::uint64_t>(want);
 }
 
 }  // namespace bam_api

@@ -173,6 +173,9 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
     cfg.ceiling = q.ceiling != 0;
     if (q.has_budget_reads) cfg.budget_reads = q.budget_reads;
     if (q.budget_fraction >= 0.0 || q.budget_fraction != q.budget_fraction) cfg.budget_fraction = q.budget_fraction;
+    if (q.has_mean_depth) cfg.mean_depth = q.mean_depth;
+    if (q.has_budget_bases) cfg.budget_bases = q.budget_bases;
+    if (given(q.mean_depth_targets)) cfg.mean_depth_targets_filepath = q.mean_depth_targets;
     if (q.has_replicates) {
         cfg.replicates = std::vector<std::uint32_t>();
         if (q.replicates_further) cfg.replicates->assign(q.replicates_further, q.replicates_further + q.n_replicates_further);
@@ -184,8 +187,10 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
 
 // Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
 // amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
-enum class Mode { PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+enum class Mode { MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
 Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (cfg.mean_depth || cfg.budget_bases || given(q.mean_depth_targets) || given(q.mean_depth_report))
+        return Mode::MEAN_DEPTH;
     if (cfg.proportion || given(q.proportional_report)) return Mode::PROPORTIONAL;
     if (cfg.replicates) return Mode::REPLICATES;
     if (cfg.budget_reads || cfg.budget_fraction || given(q.budget_report)) return Mode::BUDGET;
@@ -205,6 +210,7 @@ struct ModeWords {
 };
 ModeWords words_of(Mode mode) {
     switch (mode) {
+        case Mode::MEAN_DEPTH: return {"mean-depth downsampling does not", "mean-depth downsampling"};
         case Mode::PROPORTIONAL: return {"proportional downsampling does not", "proportional downsampling"};
         case Mode::REPLICATES: return {"disjoint replicates do not", "disjoint replicates"};
         case Mode::BUDGET: return {"budget downsampling does not", "budget downsampling"};
@@ -231,6 +237,8 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
     const std::string replicates_template = q.replicates_template ? q.replicates_template : "";
     if (mode == Mode::BUDGET && !cfg.budget_reads && !cfg.budget_fraction)
         refuse("budget downsampling needs budget_reads or budget_fraction");
+    if (mode == Mode::MEAN_DEPTH && !cfg.mean_depth && !cfg.budget_bases)
+        refuse("mean-depth downsampling needs mean_depth or budget_bases");
     if (mode == Mode::PROPORTIONAL && !cfg.proportion) refuse("proportional downsampling needs a proportion");
     if (mode == Mode::LADDER && cfg.coverage_ladder.empty()) refuse("a coverage ladder needs at least one level");
     if (mode == Mode::LADDER && ladder_template.find("{M}") == std::string::npos)
@@ -250,7 +258,8 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
     }
     if (given(q.fragment_report) && !cfg.fragment_depth) refuse("a fragment report needs fragment_depth");
     if (q.has_regions &&
-        (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL))
+        (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL ||
+         mode == Mode::MEAN_DEPTH))
         refuse(words.refuses + " go together with a coverage profile");
     if (mode != Mode::PLAIN && solver.uses_quality_of_reads()) refuse(words.refuses + " take a solver that grades by quality");
     if (mode != Mode::PLAIN && hip == nullptr) refuse("this solver has no " + words.noun);
@@ -367,6 +376,30 @@ bool write_budget_report(const char* path, const qmcp_hip_budget_stats& bs, cons
     return std::fclose(f) == 0;
 }
 
+// stat<TAB>value: the qmcp_hip_mean_depth_stats, the records written and the two means over the regions' positions, then
+// one M<TAB>bases line per entry of the curve S_R
+bool write_mean_depth_report(const char* path, const qmcp_hip_mean_depth_stats& ms, const std::vector<std::uint64_t>& curve,
+                             std::int64_t written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "budget\t%llu\npositions\t%llu\nreads_placed\t%llu\nn_kept\t%llu\nkept_bases\t%llu\n"
+                    "bases_above\t%llu\nbound_above\t%llu\ntotal_bases\t%llu\n",
+                 (unsigned long long)ms.budget, (unsigned long long)ms.positions, (unsigned long long)ms.reads_placed,
+                 (unsigned long long)ms.n_kept, (unsigned long long)ms.kept_bases, (unsigned long long)ms.bases_above,
+                 (unsigned long long)ms.bound_above, (unsigned long long)ms.total_bases);
+    std::fprintf(f, "coverage\t%u\nmax_depth\t%u\ntop\t%u\nprobes\t%u\ncurve_entries\t%u\nsaturated\t%u\n"
+                    "regions_in\t%u\nregions_used\t%u\nms_mean_depth\t%.6g\nms_solves\t%.6g\nrecords_written\t%u\n",
+                 ms.coverage, ms.max_depth, ms.top, ms.probes, ms.curve_entries, ms.saturated, ms.regions_in,
+                 ms.regions_used, (double)ms.ms_mean_depth, (double)ms.ms_solves, (unsigned)written);
+    const double positions = (double)ms.positions;
+    std::fprintf(f, "mean_depth_in\t%.6f\nmean_depth_kept\t%.6f\n", positions > 0 ? (double)ms.total_bases / positions : 0.0,
+                 positions > 0 ? (double)ms.kept_bases / positions : 0.0);
+    std::fprintf(f, "#M\tbases\n");
+    for (std::size_t m = 0; m < curve.size(); ++m) std::fprintf(f, "%zu\t%llu\n", m, (unsigned long long)curve[m]);
+    return std::fclose(f) == 0;
+}
+
 // one line per replicate -- coverage, offered, kept, mates, short_positions, short_bases, records_written -- and n_full
 bool write_replicates_report(const char* path, const qmcp_hip_replicates_stats& rs, std::uint32_t max_coverage,
                              const std::vector<std::uint32_t>& further, const std::vector<std::int64_t>& written) {
@@ -428,7 +461,7 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
 
     // solve, and write every kept set: `written` gets one record count per output file, out_path's first.  Pairs are
     // completed by find_pairs where the solve does not leave whole pairs itself -- and never where that would put
-    // depth or reads back (ceiling, budget) or copy a record into two files (replicates).
+    // depth, reads or bases back (ceiling, budget, mean depth) or copy a record into two files (replicates).
     std::vector<std::int64_t> written;
     std::vector<bam_api::ReadIndex> kept;  // the last kept set as written (the depth report and track describe it)
     const auto write_reads = [&](const qmcp::Solution& solution, bool complete_pairs, const std::string& path) {
@@ -448,6 +481,7 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         case Mode::PAIRS: write_reads(*hip->solve_pairs(M, api), false, q.out_path); break;
         case Mode::CEILING: write_reads(*hip->solve_ceiling(M, api, offsets, starts, ends, caps), false, q.out_path); break;
         case Mode::BUDGET: write_reads(*hip->solve_budget(M, api), false, q.out_path); break;
+        case Mode::MEAN_DEPTH: write_reads(*hip->solve_mean_depth(M, api), false, q.out_path); break;
         case Mode::LADDER: {
             const auto levels = hip->solve_ladder(M, api, api.coverage_ladder());
             for (std::size_t j = 0; j < levels.size(); ++j)
@@ -494,6 +528,9 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         reported = write_proportional_report(q.proportional_report, hip->last_proportional_stats(), written[0]);
     if (mode == Mode::BUDGET && given(q.budget_report))
         reported = write_budget_report(q.budget_report, hip->last_budget_stats(), hip->last_budget_curve(), written[0]);
+    if (mode == Mode::MEAN_DEPTH && given(q.mean_depth_report))
+        reported = write_mean_depth_report(q.mean_depth_report, hip->last_mean_depth_stats(), hip->last_mean_depth_curve(),
+                                           written[0]);
     if (mode == Mode::REPLICATES && given(q.replicates_report))
         reported = write_replicates_report(q.replicates_report, hip->last_replicates_stats(), M, *api.replicates(), written);
     if (!api.depth_report_filepath().empty() || !api.depth_track_filepath().empty()) {

@@ -449,6 +449,50 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_budget(std::uint32_t required
     return kept;
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_mean_depth(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.mean_depth() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("mean-depth downsampling needs a BamApi built with BamApiConfig::mean_depth or "
+                                    "budget_bases");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    const bam_api::TargetRegions* regions = bam_api.has_mean_depth_regions() ? &bam_api.mean_depth_regions() : nullptr;
+    if (regions && regions->offsets.size() != reads.contig_lengths.size() + 1)
+        throw std::invalid_argument("the mean-depth regions do not match the file's references");
+    const std::uint64_t budget = bam_api.base_budget_for(bam_api.mean_depth_positions(reads.contig_lengths));
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    mean_depth_curve_.assign(QMCP_BUDGET_CURVE_MAX + 1u, 0);
+    const int rc = qmcp_hip_solve_mean_depth_host(
+        ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(),
+        (std::uint32_t)reads.contig_lengths.size(), required_cover, budget, regions ? regions->offsets.data() : nullptr,
+        regions ? regions->starts.data() : nullptr, regions ? regions->ends.data() : nullptr, QMCP_MEAN_DEPTH_WHOLE_PAIRS,
+        mean_depth_curve_.data(), (std::uint32_t)mean_depth_curve_.size(), mask.data(), &stats_, &mdstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_mean_depth_host", rc);
+    mean_depth_curve_.resize(mdstats_.curve_entries);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    // the context holds the final mask
+    auto kept = std::make_unique<Solution>();
+    kept->resize(mdstats_.n_kept);
+    std::uint64_t n_out = 0;
+    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), mdstats_.n_kept, &n_out);
+    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
+    kept->resize(n_out);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return kept;
+}
+
 // a record is written iff one of its segments is kept; its segments are consecutive, in file order
 static std::vector<bam_api::BAMReadId> records_of_kept_segments(const bam_api::TemplateSegments& seg,
                                                                 const std::vector<std::uint64_t>& mask) {

@@ -1290,6 +1290,77 @@ int qmcp_hip_solve_budget_device(qmcp_hip_ctx* ctx,
                                  uint32_t curve_capacity, uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                  qmcp_hip_budget_stats* bstats);
 
+/* Mean-depth downsampling: the deepest coverage whose by-contig solve fits a number of BASES -- "make this 80 x genome
+ * 30 x", "bring the exome to 100 x mean on target".  The budget entries above answer in reads; a mean depth is a budget in
+ * bases, budget_bases = floor(mean * |R|), over a region set R: the whole genome, or the target regions whose mean Picard
+ * reports as MEAN_TARGET_COVERAGE.
+ * Input: reads, contig_ids, contig_lengths / n_contigs, limits and read validation exactly as in
+ * qmcp_hip_solve_by_contig_host; max_coverage (1 .. 2^31 - 1) is the upper end of the search.  region_offsets (n_contigs +
+ * 1 entries) / region_starts / region_ends in the form of qmcp_hip_solve_targets_host: inclusive bounds, any order,
+ * overlapping and nested regions allowed, clipped to the contig, a region that begins at or beyond the contig's length
+ * dropped, no padding.  R_c is the union of contig c's regions.  region_offsets == NULL: R_c is all of contig c.  A table
+ * that is present but empty is legal: R is empty.
+ * Definitions: keep_M, M >= 1, is the mask qmcp_hip_solve_by_contig_host returns at M; under QMCP_MEAN_DEPTH_WHOLE_PAIRS
+ * after the completion of QMCP_BUDGET_WHOLE_PAIRS (reads (2q, 2q + 1) are pair q, n_reads must be even, a placed read is
+ * also kept when its placed mate is, an unplaced mate is never kept).  keep_0 is empty.  bases(M) = the sum over the placed
+ * reads i in keep_M of |[start_i, end_i] n R_contig(i)|: the kept depth summed over the positions of R.  top =
+ * min(max_coverage, largest depth of the placed reads) -- the depth over ALL positions, not only those of R: the mask
+ * changes up to there.
+ * Answer: a coverage M* in 0 .. top (mstats->coverage) with
+ *   (1) bases(M*) <= budget_bases, and
+ *   (2) M* == top or bases(M* + 1) > budget_bases,
+ * and in keep_mask_out exactly keep_M*, bit for bit; M* == 0 is the all-zero mask.  The result is deterministic.
+ * Monotonicity of bases(M) has been observed on every input tried and is NOT proven, with or without regions or the flag:
+ * only (1) and (2) are promised.  Where bases is non-decreasing, M* is the one largest feasible coverage.
+ * Bound: S_R(M) = the sum over the positions p of R of min(cov(p), M) <= bases(M), because every valid answer at M keeps
+ * at least min(cov, M) at every position.  curve_out (may be NULL, then curve_capacity must be 0): curve_out[M] = S_R(M)
+ * for M = 0 .. min(top, QMCP_BUDGET_CURVE_MAX, curve_capacity - 1).  A HOST array in both entries.
+ * Errors, all decided from the arguments before the context is looked at: those of qmcp_hip_solve_budget_host -- null
+ * arrays, unknown flag bits, an odd n_reads under the flag, max_coverage == 0 or a curve_capacity without curve_out are
+ * QMCP_EINVAL; max_coverage >= 2^31, too many contigs or reads are QMCP_ERANGE --, then those of the targets entry for the
+ * region table -- offsets that do not start at 0 or decrease, a NULL column with a non-zero count, a region with start >
+ * end: QMCP_EINVAL.  A bad contig id or read is found on the device with the codes of the by-contig entry.  The output mask
+ * is written by a successful call only.
+ * stats (may be NULL): the batch-summed qmcp_hip_stats of the probe at M* (zeros for M* == 0).  mstats (may be NULL): see
+ * the struct.  The device entry is ordered after hip_stream; both entries block (no _begin / _end form). */
+#define QMCP_MEAN_DEPTH_WHOLE_PAIRS 1u
+typedef struct qmcp_hip_mean_depth_stats {
+    uint64_t budget;         /* budget_bases as given                                                                  */
+    uint64_t positions;      /* |R|: the positions of the merged, clipped regions; every position without a table       */
+    uint64_t reads_placed;   /* placed reads                                                                           */
+    uint64_t n_kept;         /* reads in keep_M*                                                                       */
+    uint64_t kept_bases;     /* bases(M*)                                                                              */
+    uint64_t bases_above;    /* bases(M* + 1) when a probe measured it, else 0                                         */
+    uint64_t bound_above;    /* else S_R(M* + 1), the bound that ruled M* + 1 out; both are 0 when M* == top            */
+    uint64_t total_bases;    /* the sum of the depth over the positions of R                                           */
+    uint32_t coverage;       /* M*                                                                                     */
+    uint32_t max_depth;      /* the largest depth of the placed reads, over all positions                              */
+    uint32_t top;            /* min(max_coverage, max_depth)                                                           */
+    uint32_t probes;         /* whole solves run                                                                       */
+    uint32_t curve_entries;  /* entries written to curve_out                                                           */
+    uint32_t saturated;      /* 1 when every placed read is kept                                                       */
+    uint32_t regions_in;     /* regions given (0 without a table)                                                      */
+    uint32_t regions_used;   /* regions after clipping and merging                                                     */
+    float ms_mean_depth;     /* device time of k_md_weights, the tallies, k_budget_curve, k_budget_finish, k_md_count   */
+    float ms_solves;         /* device time of the probes' solves                                                      */
+} qmcp_hip_mean_depth_stats;
+int qmcp_hip_solve_mean_depth_host(qmcp_hip_ctx* ctx,
+                                   const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                   uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                   uint32_t max_coverage, uint64_t budget_bases,
+                                   const uint32_t* region_offsets /* may be NULL */, const uint32_t* region_starts,
+                                   const uint32_t* region_ends, uint32_t flags, uint64_t* curve_out /* may be NULL */,
+                                   uint32_t curve_capacity, uint64_t* keep_mask_out, qmcp_hip_stats* stats,
+                                   qmcp_hip_mean_depth_stats* mstats);
+int qmcp_hip_solve_mean_depth_device(qmcp_hip_ctx* ctx,
+                                     const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                     uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                     uint32_t max_coverage, uint64_t budget_bases,
+                                     const uint32_t* region_offsets /* host; may be NULL */, const uint32_t* region_starts,
+                                     const uint32_t* region_ends, uint32_t flags, uint64_t* curve_out /* host; may be NULL */,
+                                     uint32_t curve_capacity, uint64_t* d_keep_mask_out, void* hip_stream,
+                                     qmcp_hip_stats* stats, qmcp_hip_mean_depth_stats* mstats);
+
 /* Proportional downsampling: keep a fraction of the depth everywhere.  Every other solving entry asks for a flat depth,
  * min(cov(p), cap) with a cap from outside the data; this one takes its demand from the data's own depth, so the SHAPE of
  * the coverage survives (copy-number calling, ChIP / ATAC / RNA signal, allele balance, "this run at a quarter of the
