@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_ceiling_host", "qmcp_hip_solve_ceiling_device",
     "qmcp_hip_solve_budget_host", "qmcp_hip_solve_budget_device",
     "qmcp_hip_solve_mean_depth_host", "qmcp_hip_solve_mean_depth_device",
+    "qmcp_hip_solve_thresholds_host", "qmcp_hip_solve_thresholds_device",
     "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
     "qmcp_hip_solve_proportional_host", "qmcp_hip_solve_proportional_device",
 )
@@ -67,6 +68,9 @@ CEILING_WHOLE_PAIRS = 1  # QMCP_CEILING_WHOLE_PAIRS
 BUDGET_WHOLE_PAIRS = 1  # QMCP_BUDGET_WHOLE_PAIRS
 BUDGET_CURVE_MAX = 8191  # QMCP_BUDGET_CURVE_MAX: the last coverage the curve of a budget solve reaches
 MEAN_DEPTH_WHOLE_PAIRS = 1  # QMCP_MEAN_DEPTH_WHOLE_PAIRS
+THRESHOLD_NEVER = 0xFFFF  # QMCP_THRESHOLD_NEVER: the threshold of a read that no coverage of the range keeps
+THRESHOLDS_COVERAGE_MAX = 65534  # QMCP_THRESHOLDS_COVERAGE_MAX
+THRESHOLDS_WHOLE_PAIRS = 1  # QMCP_THRESHOLDS_WHOLE_PAIRS
 PROPORTION_DEN_MAX = 1 << 20  # QMCP_PROPORTION_DEN_MAX: the largest denominator of a proportional solve's fraction
 REPLICATES_MAX = 16  # QMCP_REPLICATES_MAX
 REPLICATES_WHOLE_PAIRS, REPLICATES_SHORTFALL = 1, 2  # QMCP_REPLICATES_*
@@ -216,6 +220,20 @@ class MeanDepthStats(C.Structure):
                 ("total_bases", C.c_uint64), ("coverage", C.c_uint32), ("max_depth", C.c_uint32), ("top", C.c_uint32),
                 ("probes", C.c_uint32), ("curve_entries", C.c_uint32), ("saturated", C.c_uint32),
                 ("regions_in", C.c_uint32), ("regions_used", C.c_uint32), ("ms_mean_depth", C.c_float),
+                ("ms_solves", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class ThresholdsStats(C.Structure):
+    """qmcp_hip_thresholds_stats: the range of a thresholds solve (coverage_lo .. coverage_hi), the last coverage it had
+    to solve (top, after `solves` whole solves; saturated: every placed read has a threshold), the reads with a
+    threshold (n_kept), the (read, M) pairs in which a read with a threshold was not kept (nesting_violations: while it
+    is 0, thresholds <= M is solve_by_contig's mask at M bit for bit) and the cost"""
+    _fields_ = [("reads_placed", C.c_uint64), ("n_kept", C.c_uint64), ("nesting_violations", C.c_uint64),
+                ("coverage_lo", C.c_uint32), ("coverage_hi", C.c_uint32), ("top", C.c_uint32), ("solves", C.c_uint32),
+                ("saturated", C.c_uint32), ("count_entries", C.c_uint32), ("ms_thresholds", C.c_float),
                 ("ms_solves", C.c_float)]
 
     def as_dict(self):
@@ -442,15 +460,17 @@ class DownsampleRequest(C.Structure):
            ("fragment_report", C.c_char_p), ("ceiling_report", C.c_char_p), ("budget_report", C.c_char_p),
            ("budget_reads", C.c_uint64), ("budget_fraction", C.c_double), ("mean_depth_targets", C.c_char_p),
            ("mean_depth_report", C.c_char_p), ("budget_bases", C.c_uint64), ("mean_depth", C.c_double),
+           ("thresholds_tag", C.c_char_p), ("thresholds_report", C.c_char_p),
            ("replicates_further", C.POINTER(C.c_uint32)),
            ("replicates_template", C.c_char_p), ("replicates_report", C.c_char_p)]
         + [(name, C.c_uint32) for name in ("max_coverage", "min_len", "min_mapq", "target_padding", "report_bins",
                                            "track_cap", "n_ladder_levels", "default_cap", "n_pair_stages",
-                                           "n_template_stages", "n_replicates_further")]
+                                           "n_template_stages", "n_replicates_further", "thresholds_lo",
+                                           "thresholds_hi")]
         + [(name, C.c_int32) for name in ("amplicon_mode", "per_reference", "amplicons_by_reference", "keep_off_target",
                                           "dedup", "has_regions", "pair_aware", "template_aware", "split_spliced",
                                           "include_secondary", "fragment_depth", "ceiling", "has_budget_reads",
-                                          "has_budget_bases", "has_mean_depth", "has_replicates")]
+                                          "has_budget_bases", "has_mean_depth", "has_replicates", "has_thresholds")]
         + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
            ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
@@ -618,6 +638,13 @@ _hip.qmcp_hip_solve_mean_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_vo
                                                   C.c_uint32, C.c_uint32, C.c_uint64, _u32p, _u32p, _u32p, C.c_uint32,
                                                   _u64p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats),
                                                   C.POINTER(MeanDepthStats)]
+_u16p = C.POINTER(C.c_uint16)
+_hip.qmcp_hip_solve_thresholds_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, _u16p, _u64p, C.c_uint32, C.POINTER(Stats),
+                                                C.POINTER(ThresholdsStats)]
+_hip.qmcp_hip_solve_thresholds_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                                  C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u64p,
+                                                  C.c_uint32, C.c_void_p, C.POINTER(Stats), C.POINTER(ThresholdsStats)]
 _hip.qmcp_hip_solve_budget_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
                                               C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.POINTER(Stats), C.POINTER(BudgetStats)]
@@ -748,6 +775,15 @@ def ladder_mask(levels, j):
     return np.packbits(bits, bitorder="little").view(np.uint64).copy()
 
 
+def threshold_mask(thresholds, M):
+    """the packed keep mask (np.uint64 words, input order) of coverage M from the thresholds of Solver.solve_thresholds:
+    {i : thresholds[i] <= M}, for M inside the solved range"""
+    thresholds = np.ascontiguousarray(thresholds, dtype=np.uint16)
+    bits = np.zeros(mask_words(thresholds.size) * 64, dtype=np.uint8)
+    bits[:thresholds.size] = thresholds <= min(int(M), THRESHOLD_NEVER - 1)
+    return np.packbits(bits, bitorder="little").view(np.uint64).copy()
+
+
 def replicate_mask(labels, r):
     """the packed mask (np.uint64 words, input order) of replicate r (1-based) of a replicate split: R_r = {i : labels[i]
     == r}"""
@@ -789,6 +825,7 @@ class Solver:
         self.last_proportional_stats = None
         self.last_budget_stats = None
         self.last_mean_depth_stats = None
+        self.last_thresholds_stats = None
         self.last_replicates_stats = None
         self.last_replicate_solve_stats = None
 
@@ -1353,6 +1390,51 @@ class Solver:
         self.last_stats, self.last_mean_depth_stats = st, ms
         out = (int(ms.coverage), ms)
         return out + (table[:ms.curve_entries],) if curve else out
+
+    @staticmethod
+    def _thresholds_counts(coverage_lo, coverage_hi, counts):
+        cap = max(int(coverage_hi) - int(coverage_lo) + 1, 0) if counts else 0
+        if cap > THRESHOLDS_COVERAGE_MAX:  # (the call refuses such a range)
+            cap = THRESHOLDS_COVERAGE_MAX
+        return cap, np.zeros(max(cap, 1), dtype=np.uint64) if counts else None
+
+    def solve_thresholds(self, starts, ends, contig_ids, contig_lengths, coverage_hi, coverage_lo=1, flags=0, counts=False):
+        """coverage thresholds (qmcp_hip_solve_thresholds_host): solve_by_contig's reads, and per read the SMALLEST
+        coverage M in coverage_lo .. coverage_hi at which solve_by_contig keeps it -- THRESHOLD_NEVER for an unplaced read
+        and for one that no such M keeps.  One grouping, one whole solve per coverage from coverage_lo up, stopping once
+        every placed read has a threshold (ThresholdsStats.top).  While ThresholdsStats.nesting_violations is 0 -- it has
+        been on every input seen; not proven -- threshold_mask(thresholds, M) is solve_by_contig's mask at M bit for bit
+        for every M of the range.  flags: THRESHOLDS_WHOLE_PAIRS gives a placed read the smaller of its own and its
+        placed mate's threshold (reads 2q, 2q + 1).  -> (thresholds uint16, ThresholdsStats); counts=True appends the
+        reads with threshold <= M for M = coverage_lo .. coverage_hi as a uint64 array.  last_stats: the last solve"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        cap, table = self._thresholds_counts(coverage_lo, coverage_hi, counts)
+        thr = np.full(max(n, 1), THRESHOLD_NEVER, dtype=np.uint16)
+        st, ts = Stats(), ThresholdsStats()
+        _check(_hip.qmcp_hip_solve_thresholds_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), n, _p32(lengths),
+                                                   lengths.size, int(coverage_lo), int(coverage_hi), int(flags),
+                                                   thr.ctypes.data_as(_u16p), _p64(table), cap, C.byref(st), C.byref(ts)))
+        self.last_stats, self.last_thresholds_stats = st, ts
+        out = (thr[:n], ts)
+        return out + (table[:ts.count_entries],) if counts else out
+
+    def solve_thresholds_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, coverage_hi, d_thresholds,
+                                coverage_lo=1, flags=0, counts=False, stream=0):
+        """solve_thresholds on device pointers (ints); the uint16 thresholds are written to d_thresholds (n_reads
+        entries).  -> ThresholdsStats, with counts=True (ThresholdsStats, counts)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        cap, table = self._thresholds_counts(coverage_lo, coverage_hi, counts)
+        st, ts = Stats(), ThresholdsStats()
+        _check(_hip.qmcp_hip_solve_thresholds_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                     C.c_void_p(d_contig_ids), int(n_reads), _p32(lengths), lengths.size,
+                                                     int(coverage_lo), int(coverage_hi), int(flags),
+                                                     C.c_void_p(d_thresholds), _p64(table), cap, C.c_void_p(stream),
+                                                     C.byref(st), C.byref(ts)))
+        self.last_stats, self.last_thresholds_stats = st, ts
+        return (ts, table[:ts.count_entries]) if counts else ts
 
     def solve_pairs(self, starts, ends, contig_ids, contig_lengths, max_coverage, stages=None):
         """pair-aware downsampling (qmcp_hip_solve_pairs_host): reads (2q, 2q + 1) are pair q, stages the rising targets
@@ -2392,6 +2474,25 @@ def copy_records(in_path, out_path, ids):
     return int(n)
 
 
+def copy_records_tagged(in_path, out_path, ids, values, tag="XC"):
+    """copy_records with the aux field <tag>:S:<values[k]> appended to the record ids[k] -- five bytes, block_size grown by
+    five; <tag>:i:<value> in SAM text.  OSError, before anything is written, for a tag that is not [A-Za-z][A-Za-z0-9]
+    and for a record that carries the tag already"""
+    _need_host()
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    values = np.ascontiguousarray(values, dtype=np.uint16)
+    assert ids.size == values.size, "one value per record"
+    err = C.create_string_buffer(512)
+    _host.qmcp_host_copy_records_tagged.restype = C.c_int64
+    _host.qmcp_host_copy_records_tagged.argtypes = [C.c_char_p, C.c_char_p, _u64p, _u16p, C.c_uint64, C.c_char_p,
+                                                    C.c_char_p, C.c_size_t]
+    n = _host.qmcp_host_copy_records_tagged(str(in_path).encode(), str(out_path).encode(), _p64(ids),
+                                            values.ctypes.data_as(_u16p), ids.size, str(tag).encode(), err, 512)
+    if n < 0:
+        raise OSError(err.value.decode())
+    return int(n)
+
+
 def check_targets_config(in_path, targets, per_reference=True, target_padding=0):
     """BamApi(in_path, BamApiConfig{targets_filepath, target_padding, per_reference}) without a solve: the number of
     regions it parsed.  ValueError with BamApi's message when it refuses (targets without per_reference, a chrom that
@@ -2446,6 +2547,10 @@ class _Mode:
         self.amplicon_files, self.quality_solver = amplicon_files, quality_solver
 
 
+_THRESHOLDS = _Mode("coverage thresholds", ("a mean depth", "a proportion", "replicates", "a budget", "ceiling",
+                                            "pair_aware", "template_aware", "targets", "a depth report", "a depth track",
+                                            "a coverage ladder", "stratify", "dedup", "a coverage profile"),
+                    plural=True)
 _MEAN_DEPTH = _Mode("mean-depth downsampling", ("a proportion", "replicates", "a budget", "ceiling", "pair_aware",
                                                 "template_aware", "targets", "a depth report", "a depth track",
                                                 "a coverage ladder", "stratify", "dedup", "a coverage profile"))
@@ -2510,7 +2615,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    ceiling=False, ceiling_report=None, budget_reads=None, budget_fraction=None, budget_report=None,
                    replicates=None, replicates_out=None, replicates_report=None, proportion=None, proportion_floor=0,
                    proportional_report=None, fragment_depth=False, fragment_report=None, mean_depth=None,
-                   budget_bases=None, mean_depth_targets=None, mean_depth_report=None):
+                   budget_bases=None, mean_depth_targets=None, mean_depth_report=None, thresholds=None,
+                   thresholds_tag="XC", thresholds_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2632,9 +2738,21 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     mean_depth_kept over the regions' positions, then one M<TAB>bases line per entry of the curve S_R(M).  Needs
     per_reference=True; exactly one of mean_depth and budget_bases; not together with a proportion, replicates, a
     budget, ceiling, pair_aware, template_aware, targets, report, track, ladder, stratify, dedup, profile, amplicon
-    files or "quasi-mcp-hip-quality" (ValueError).  None: nothing changes"""
+    files or "quasi-mcp-hip-quality" (ValueError).  None: nothing changes.
+    thresholds=hi or (lo, hi) (BamApiConfig::thresholds_lo / thresholds_hi, lo = 1 when only hi is given) with
+    thresholds_tag (two characters, [A-Za-z][A-Za-z0-9]): tag the file once, cut any downsample later with a filter.  One
+    ingest and one qmcp_hip_solve_thresholds_host call with THRESHOLDS_WHOLE_PAIRS on the reads as the budget flow pairs
+    them; every record whose threshold is <= hi is written with the aux field <tag>:S:<threshold> -- the smallest
+    coverage of lo .. hi at which the by-contig solve, completed to whole pairs, keeps it -- and no find_pairs follows.
+    `samtools view -e '[XC]<=30'` of the output is then the downsample at 30 (while the report's nesting_violations is
+    0: it has been on every input seen, which is not proven).  max_coverage is not used.  An input record that carries
+    the tag already is refused before anything is written.  thresholds_report (a path) gets a stat<TAB>value TSV with
+    the ThresholdsStats and records_written, then one M<TAB>reads line per coverage of the range.  Needs
+    per_reference=True; not together with a mean depth, a proportion, replicates, a budget, ceiling, pair_aware,
+    template_aware, targets, report, track, ladder, stratify, dedup, profile, amplicon files or "quasi-mcp-hip-quality"
+    (ValueError).  None: nothing changes"""
     _need_host()
-    given = {"a proportion": proportion is not None, "replicates": replicates is not None,
+    given = {"a mean depth": mean_depth is not None or budget_bases is not None, "a proportion": proportion is not None, "replicates": replicates is not None,
              "a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
              "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
              "a depth report": bool(report), "a depth track": track is not None, "a coverage ladder": ladder is not None,
@@ -2689,7 +2807,21 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         raise ValueError("proportion_floor and proportional_report need proportion")
     if (mean_depth_targets is not None or mean_depth_report is not None) and mean_depth is None and budget_bases is None:
         raise ValueError("mean_depth_targets and mean_depth_report need mean_depth or budget_bases")
-    if mean_depth is not None or budget_bases is not None:
+    if thresholds is None and thresholds_report is not None:
+        raise ValueError("thresholds_report needs thresholds")
+    if thresholds is not None:
+        lo, hi = (1, thresholds) if np.isscalar(thresholds) else thresholds
+        lo, hi = int(lo), int(hi)
+        if not 1 <= lo <= hi <= THRESHOLDS_COVERAGE_MAX:
+            raise ValueError(f"thresholds need 1 <= lo <= hi <= {THRESHOLDS_COVERAGE_MAX}")
+        tag = str(thresholds_tag)
+        if not (len(tag) == 2 and tag.isascii() and tag[0].isalpha() and tag[1].isalnum()):
+            raise ValueError("thresholds_tag must be [A-Za-z][A-Za-z0-9]")
+        need_per_reference(_THRESHOLDS)
+        refuse(_THRESHOLDS)
+        fields.update(has_thresholds=1, thresholds_lo=lo, thresholds_hi=hi, thresholds_tag=str(thresholds_tag),
+                      thresholds_report=thresholds_report)
+    elif mean_depth is not None or budget_bases is not None:
         if mean_depth is not None and budget_bases is not None:
             raise ValueError("mean-depth downsampling takes mean_depth or budget_bases, not both")
         if budget_bases is not None and not 0 <= int(budget_bases) < 1 << 64:

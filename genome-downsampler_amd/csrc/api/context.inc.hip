@@ -243,6 +243,10 @@ struct qmcp_hip_ctx {
     // with the MeanDepthWord words behind the histogram): the merged region table in contig coordinates (offs | rs | re |
     // cum) followed by the batches' form of it (rpos | rcum), and the reads' weights
     DevBuf md_tab, md_w;
+    // coverage thresholds (api/thresholds.inc.hip), all its own: the input-order mask a coverage's solve scatters into,
+    // the reads that have a threshold, the accumulators with the histogram behind them (ThresholdsAccWord words | bins),
+    // and the host entry's thresholds
+    DevBuf th_mask, th_seen, th_acc, th_thr;
     // disjoint replicates (api/replicates.inc.hip), all its own: the two sets of free reads' columns (starts, ends, input
     // indices) that ping-pong between replicates, the scanned word popcounts of the taken candidates and their spine, the
     // two offset tables, the candidates' taken bits, the input-order taken mask (whole pairs, several batches), the packed

@@ -95,6 +95,8 @@
 //                       curve S(M) from a device-side depth histogram, and a few whole solves picked by budget_plan.h
 //   mean_depth          (budget) the deepest coverage whose by-contig solve fits a number of bases inside a region set: the
 //                       budget's flow with the histogram restricted to the regions and a weighted count per probe
+//   thresholds          (by_contig) every read's smallest keeping coverage in a range: one grouping, one whole solve per
+//                       coverage folded into the thresholds by thresholds_plan.h's word logic, the counts per coverage
 //   replicates          (by_contig, depth_report) one read set split into disjoint downsamples: the batch loop at the
 //                       first coverage, every further replicate solved on the reads still free, replicate-major over the
 //                       one grouping's batches
@@ -126,4 +128,5 @@
 #include "api/proportional.inc.hip"
 #include "api/budget.inc.hip"
 #include "api/mean_depth.inc.hip"
+#include "api/thresholds.inc.hip"
 #include "api/replicates.inc.hip"

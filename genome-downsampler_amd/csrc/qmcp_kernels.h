@@ -8,6 +8,7 @@
 #include "qmcp_hip.h"    // qmcp_hip_track_run
 #include "sweep_plan.h"  // the shape predicates and window counts the host decides with
 #include "dedup_plan.h"  // DedupPack, DedupSortForm: how a round's key is packed, which form the sort takes
+#include "thresholds_plan.h"  // thresholds_word: one mask word folded into the reads seen so far
 #include "pm_grid_plan.h"  // PmGridPlan: where the pass-major form cuts its ranges, and the tables that say so
 
 namespace qmcp {
@@ -580,6 +581,25 @@ void launch_md_weights(hipStream_t st, const uint32_t* starts, const uint32_t* e
                        uint32_t n_contigs, bool has_table, const uint32_t* offs, const uint32_t* rs, const uint32_t* re,
                        const uint32_t* cum, uint32_t n_regions, uint32_t* w);
 void launch_md_count(hipStream_t st, const uint64_t* mask, const uint32_t* w, uint64_t n_reads, unsigned long long* acc);
+
+// coverage thresholds (kernels/thresholds.inc.hip; api/thresholds.inc.hip drives them).  thr has one 16-bit threshold per
+// read and holds kThresholdNever everywhere before the first step.  launch_thresholds_step, per coverage M: the reads of
+// the input-order `mask` that `seen` lacks get thr = M and join seen; acc[kThSeen] += their number, acc[kThViolations] +=
+// the reads of seen that the mask lacks.  launch_thresholds_finish, once: under whole_pairs a placed read (ids) takes the
+// smaller of its own and its placed mate's threshold; hist[t - lo] += 1 for every read with final threshold t (n_bins
+// bins, zeroed by the caller; in LDS per workgroup up to kThresholdsBinsMax bins).  launch_thresholds_counts: hist's
+// running sum in place.
+static constexpr uint32_t kThresholdsBinsMax = 8192u;  // 32 KiB of LDS per workgroup
+enum ThresholdsAccWord : uint32_t {
+    kThSeen = 0,     // reads with a threshold so far
+    kThViolations,   // (read, M) pairs in which a read with a threshold is not kept
+    kThWords = 2
+};
+void launch_thresholds_step(hipStream_t st, const uint64_t* mask, uint64_t* seen, uint64_t n_reads, uint32_t M,
+                            uint16_t* thr, unsigned long long* acc);
+void launch_thresholds_finish(hipStream_t st, const uint32_t* ids, uint64_t n_reads, bool whole_pairs, uint32_t lo,
+                              uint32_t n_bins, uint16_t* thr, unsigned long long* hist);
+void launch_thresholds_counts(hipStream_t st, unsigned long long* counts, uint32_t n_bins);
 
 // disjoint replicates (kernels/replicates.inc.hip; api/replicates.inc.hip drives them).  A replicate's candidates are n
 // reads in three columns with an origin column (origin_in: the grouping's Rec{key, index} array when `first`, a plain

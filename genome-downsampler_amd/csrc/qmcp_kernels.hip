@@ -68,6 +68,8 @@
 //                            it, and a probe's pair completion with its popcount
 //   mean_depth               mean-depth downsampling: the budget's histogram over the positions of a region set only, the
 //                            reads' weights inside it, and a probe's kept bases
+//   thresholds               coverage thresholds: one coverage's mask folded into every read's smallest keeping
+//                            coverage, the mates' minimum, and the histogram and running sum of the final thresholds
 //   replicates               disjoint replicates: the dense split of a replicate's candidates into labels and the next
 //                            replicate's columns (LDS-staged), the next contig offsets, the taken mask and its gather,
 //                            the mates' completion, the packed mask of one label
@@ -121,6 +123,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/proportional.inc.hip"
 #include "kernels/budget.inc.hip"
 #include "kernels/mean_depth.inc.hip"
+#include "kernels/thresholds.inc.hip"
 #include "kernels/replicates.inc.hip"
 
 }  // namespace qmcp

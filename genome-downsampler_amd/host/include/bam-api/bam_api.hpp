@@ -148,6 +148,16 @@ struct BamApiConfig {
         std::uint32_t num = 0, den = 1, floor = 0;
     };
     std::optional<Proportion> proportion;
+    // Coverage thresholds: every pair's smallest coverage in thresholds_lo .. thresholds_hi at which the by-contig solve,
+    // completed to whole pairs, keeps it (QuasiMcpHipSolver::solve_thresholds / qmcp_hip_solve_thresholds_host with
+    // QMCP_THRESHOLDS_WHOLE_PAIRS).  The records with a threshold are written WITHOUT find_pairs, each with the aux field
+    // <thresholds_tag>:S:<threshold>, so that any downsample of the range is a filter on the tag.  thresholds_hi set asks
+    // for it; 1 <= thresholds_lo <= thresholds_hi <= QMCP_THRESHOLDS_COVERAGE_MAX, the tag [A-Za-z][A-Za-z0-9].  Needs
+    // per_reference and goes together with nothing that proportional downsampling refuses, nor with a proportion or a
+    // mean depth (std::invalid_argument otherwise).  Not set: nothing changes.
+    std::uint32_t thresholds_lo = 1;
+    std::optional<std::uint32_t> thresholds_hi;
+    std::string thresholds_tag = "XC";
 };
 
 // the parsed target BED of BamApiConfig::targets_filepath: reference c owns regions [offsets[c], offsets[c + 1]) of
@@ -209,6 +219,11 @@ class BamApi {
     const std::optional<std::vector<std::uint32_t>>& replicates() const { return replicates_; }
     // BamApiConfig::proportion (not set: no proportional solve)
     const std::optional<BamApiConfig::Proportion>& proportion() const { return proportion_; }
+    // BamApiConfig::thresholds_lo / thresholds_hi / thresholds_tag (thresholds_hi not set: no thresholds)
+    bool thresholds() const { return thresholds_hi_.has_value(); }
+    std::uint32_t thresholds_lo() const { return thresholds_lo_; }
+    std::uint32_t thresholds_hi() const { return thresholds_hi_.value_or(0); }
+    const std::string& thresholds_tag() const { return thresholds_tag_; }
     // BamApiConfig::template_aware and template_stages (empty: the default schedule); the segments are read on the first
     // get_template_segments call, which also fills get_filtered_out_reads
     bool template_aware() const { return template_aware_; }
@@ -220,6 +235,10 @@ class BamApi {
     // number of records written; the output is always BAM
     std::uint32_t write_paired_reads(const std::filesystem::path& output_filepath,
                                      std::vector<ReadIndex>& active_ids) const;
+    // the reads active_ids, each record with the aux field <tag>:S:<values[k]> appended (values: one per active id);
+    // std::invalid_argument, before anything is written, for a bad tag and for a record that carries the tag already
+    std::uint32_t write_tagged_reads(const std::filesystem::path& output_filepath, const std::vector<ReadIndex>& active_ids,
+                                     const std::vector<std::uint16_t>& values, const std::string& tag) const;
     std::uint32_t write_bam_api_filtered_out_reads(const std::filesystem::path& output_filepath);
 
     std::vector<ReadIndex> find_pairs(const std::vector<ReadIndex>& ids) const;
@@ -260,6 +279,9 @@ class BamApi {
     bool has_mean_depth_regions_ = false;
     std::optional<std::vector<std::uint32_t>> replicates_;
     std::optional<BamApiConfig::Proportion> proportion_;
+    std::uint32_t thresholds_lo_ = 1;
+    std::optional<std::uint32_t> thresholds_hi_;
+    std::string thresholds_tag_ = "XC";
     std::vector<std::uint32_t> pair_stages_;
     bool template_aware_ = false, split_spliced_ = true, include_secondary_ = false, fragment_depth_ = false;
     std::vector<std::uint32_t> template_stages_;

@@ -90,6 +90,14 @@ std::uint32_t write_bam(const std::filesystem::path& input, const std::filesyste
 
 // A record for the synthetic-BAM writer used by the tests (the reference's tests build reads in memory
 // and never write one): single reference, CIGAR given as (length, op) with op in "MIDNSHP=X".
+// write_bam with one aux field appended to every written record: <tag> S <uint16>, five bytes, block_size grown by five;
+// in SAM text <tag>:i:<value>.  tagged holds (record id, value) pairs (sorted here).  Refused BEFORE the output is
+// opened: a tag that is not [A-Za-z][A-Za-z0-9], and an input record among the written ones that carries the tag
+// already.  UINT32_MAX with *err set on a refusal or failure.
+std::uint32_t write_bam_tagged(const std::filesystem::path& input, const std::filesystem::path& output,
+                               std::vector<std::pair<BAMReadId, std::uint16_t>>& tagged, const std::string& tag,
+                               std::string* err);
+
 struct BamRecordSpec {
     std::string qname;
     std::uint16_t flag = 0;

@@ -130,6 +130,15 @@ class QuasiMcpHipSolver : public Solver {
     // without find_pairs.  std::invalid_argument for a BamApi without a budget and for what the library refuses
     std::unique_ptr<Solution> solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_budget_stats& last_budget_stats() const { return bgstats_; }
+    // Coverage thresholds for the reads of a BamApi built with BamApiConfig::thresholds_hi: one
+    // qmcp_hip_solve_thresholds_host call with QMCP_THRESHOLDS_WHOLE_PAIRS over thresholds_lo .. thresholds_hi.  The
+    // Solution holds the reads with a threshold (whole pairs already -- the caller writes them without find_pairs),
+    // last_thresholds() one threshold per read of the BamApi, last_threshold_counts() the reads at every coverage of
+    // the range.  std::invalid_argument for a BamApi without thresholds and for what the library refuses
+    std::unique_ptr<Solution> solve_thresholds(bam_api::BamApi& bam_api);
+    const qmcp_hip_thresholds_stats& last_thresholds_stats() const { return thstats_; }
+    const std::vector<std::uint16_t>& last_thresholds() const { return thresholds_; }
+    const std::vector<std::uint64_t>& last_threshold_counts() const { return threshold_counts_; }
     // Mean-depth downsampling for the reads of a BamApi built with BamApiConfig::mean_depth or budget_bases: one
     // qmcp_hip_solve_mean_depth_host call with QMCP_MEAN_DEPTH_WHOLE_PAIRS, required_cover as the upper end of the search,
     // the BamApi's mean-depth regions (none: every position) and BamApi::base_budget_for(their positions) as the budget.
@@ -196,6 +205,9 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_ceiling_stats clstats_{};
     qmcp_hip_proportional_stats ppstats_{};
     qmcp_hip_budget_stats bgstats_{};
+    qmcp_hip_thresholds_stats thstats_{};
+    std::vector<std::uint16_t> thresholds_;
+    std::vector<std::uint64_t> threshold_counts_;
     qmcp_hip_replicates_stats rpstats_{};
     std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_mean_depth_stats mdstats_{};

@@ -66,6 +66,13 @@ typedef struct qmcp_host_downsample_request {
     const char* mean_depth_report;
     uint64_t budget_bases;
     double mean_depth;
+    /* coverage thresholds (thresholds_lo, thresholds_hi, thresholds_tag): has_thresholds != 0 asks for them -- every
+     * written record gets the aux field <thresholds_tag>:S:<the smallest coverage in thresholds_lo .. thresholds_hi that
+     * keeps its pair>, and the records without one are not written; max_coverage is not used.  thresholds_tag NULL or
+     * "": "XC".  thresholds_report: stat<TAB>value lines, then one M<TAB>reads line per coverage.  thresholds_tag or
+     * thresholds_report alone are refused */
+    const char* thresholds_tag;
+    const char* thresholds_report;
     /* disjoint replicates (replicates): has_replicates != 0 asks for them, replicate r + 2 at replicates_further[r],
      * written to replicates_template with its "{R}" replaced */
     const uint32_t* replicates_further;
@@ -83,6 +90,8 @@ typedef struct qmcp_host_downsample_request {
     uint32_t n_pair_stages;
     uint32_t n_template_stages;
     uint32_t n_replicates_further;
+    uint32_t thresholds_lo;
+    uint32_t thresholds_hi;
     int32_t amplicon_mode; /* 0 IGNORE, 1 FILTER, 2 GRADE, -1: GRADE for a solver that grades by quality, else FILTER */
     int32_t per_reference;
     int32_t amplicons_by_reference;
@@ -99,6 +108,7 @@ typedef struct qmcp_host_downsample_request {
     int32_t has_budget_bases;
     int32_t has_mean_depth;
     int32_t has_replicates;
+    int32_t has_thresholds;
     /* proportional downsampling (proportion): has_proportion != 0 asks for it -- every position keeps
      * ceil(cov * proportion_num / proportion_den) of its depth, positions at or below proportion_floor whole,
      * max_coverage the hard upper end; proportional_report: stat<TAB>value lines */

@@ -275,6 +275,35 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
             throw std::invalid_argument("proportional downsampling does not take amplicon files");
         proportion_ = config.proportion;
     }
+    if (config.thresholds_hi.has_value()) {
+        const auto no = [](const char* what) { throw std::invalid_argument(std::string("coverage thresholds do not take ") + what); };
+        if (config.thresholds_lo == 0 || config.thresholds_lo > *config.thresholds_hi || *config.thresholds_hi > 65534u)
+            throw std::invalid_argument("coverage thresholds need 1 <= thresholds_lo <= thresholds_hi <= 65534");
+        const std::string& tag = config.thresholds_tag;
+        const auto alpha = [](char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); };
+        if (tag.size() != 2 || !alpha(tag[0]) || !(alpha(tag[1]) || (tag[1] >= '0' && tag[1] <= '9')))
+            throw std::invalid_argument("thresholds_tag must be [A-Za-z][A-Za-z0-9]");
+        if (!per_reference_)
+            throw std::invalid_argument("coverage thresholds need per_reference: every coverage is solved one reference at "
+                                        "a time");
+        if (config.proportion.has_value()) no("a proportion");
+        if (config.mean_depth.has_value() || config.budget_bases.has_value()) no("a mean depth");
+        if (config.replicates.has_value()) no("replicates");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value()) no("a budget");
+        if (config.ceiling) no("ceiling");
+        if (config.pair_aware) no("pair_aware");
+        if (config.template_aware) no("template_aware");
+        if (!config.targets_filepath.empty()) no("targets");
+        if (!config.coverage_ladder.empty()) no("a coverage ladder");
+        if (!config.depth_report_filepath.empty()) no("a depth report");
+        if (!config.depth_track_filepath.empty()) no("a depth track");
+        if (config.stratify_by != Stratify::NONE) no("stratify_by");
+        if (config.dedup) no("dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty()) no("amplicon files");
+        thresholds_lo_ = config.thresholds_lo;
+        thresholds_hi_ = config.thresholds_hi;
+        thresholds_tag_ = config.thresholds_tag;
+    }
     if (config.template_aware) {
         if (!per_reference_)
             throw std::invalid_argument("template-aware downsampling needs per_reference: its stages are solved one "
@@ -420,6 +449,21 @@ std::uint32_t BamApi::write_paired_reads(const std::filesystem::path& output_fil
     std::string err;
     const std::uint32_t n = write_bam(input_filepath_, output_filepath, bam_ids, &err);
     if (n == UINT32_MAX) { std::fprintf(stderr, "[ERROR] %s\n", err.c_str()); std::exit(EXIT_FAILURE); }
+    return n;
+}
+
+std::uint32_t BamApi::write_tagged_reads(const std::filesystem::path& output_filepath,
+                                         const std::vector<ReadIndex>& active_ids, const std::vector<std::uint16_t>& values,
+                                         const std::string& tag) const {
+    if (values.size() != active_ids.size()) throw std::invalid_argument("write_tagged_reads needs one value per read");
+    const PairedReads& reads = get_paired_reads();
+    std::vector<std::pair<BAMReadId, std::uint16_t>> tagged;
+    tagged.reserve(active_ids.size());
+    for (std::size_t k = 0; k < active_ids.size(); ++k)
+        tagged.emplace_back(reads.get_read_by_index(active_ids[k]).bam_id, values[k]);
+    std::string err;
+    const std::uint32_t n = write_bam_tagged(input_filepath_, output_filepath, tagged, tag, &err);
+    if (n == UINT32_MAX) throw std::invalid_argument(err);
     return n;
 }
 

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <thread>
 
@@ -780,8 +781,107 @@ bool read_bam_references(const std::filesystem::path& path, std::vector<std::str
     return true;
 }
 
+namespace {
+
+// whether the record carries an optional field named t0 t1 (any type); the walk of record_read_group.  *malformed: fields
+// that run past the record's end or have an unknown type
+bool record_has_tag(const std::vector<unsigned char>& rec, char t0, char t1, bool* malformed) {
+    const unsigned char* p = rec.data() + 4;
+    const std::size_t size = rec.size() - 4;
+    const std::size_t l_read_name = p[8], n_cigar = le16(p + 12), l_seq = le32(p + 16);
+    const std::size_t fixed_end = 32u + l_read_name + 4u * n_cigar + (l_seq + 1) / 2 + l_seq;
+    *malformed = true;
+    if (fixed_end > size) return false;
+    auto width = [](char t) -> std::size_t {
+        return t == 'A' || t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : t == 'i' || t == 'I' || t == 'f' ? 4 : 0;
+    };
+    const unsigned char* a = p + fixed_end;
+    const unsigned char* const end = p + size;
+    bool found = false;
+    while (a + 3 <= end) {
+        found = found || ((char)a[0] == t0 && (char)a[1] == t1);
+        const char type = (char)a[2];
+        a += 3;
+        if (type == 'Z' || type == 'H') {
+            while (a < end && *a != 0) ++a;
+            if (a >= end) return false;
+            ++a;
+        } else if (type == 'B') {
+            if (a + 5 > end) return false;
+            const std::size_t w = width((char)a[0]), count = le32(a + 1);
+            a += 5;
+            if (w == 0 || (char)a[-5] == 'A' || count > (std::size_t)(end - a) / w) return false;
+            a += count * w;
+        } else {
+            const std::size_t w = width(type);
+            if (w == 0 || a + w > end) return false;
+            a += w;
+        }
+    }
+    if (a != end) return false;
+    *malformed = false;
+    return found;
+}
+
+// what write_bam does to a record it is about to write, the k-th of the sorted ids (nothing when empty)
+using RecordEdit = std::function<void(std::vector<unsigned char>& rec, std::size_t k)>;
+std::uint32_t write_bam_edited(const std::filesystem::path& input, const std::filesystem::path& output,
+                               std::vector<BAMReadId>& bam_ids, const RecordEdit& edit, std::string* err);
+
+}  // namespace
+
 std::uint32_t write_bam(const std::filesystem::path& input, const std::filesystem::path& output,
                         std::vector<BAMReadId>& bam_ids, std::string* err) {
+    return write_bam_edited(input, output, bam_ids, RecordEdit(), err);
+}
+
+std::uint32_t write_bam_tagged(const std::filesystem::path& input, const std::filesystem::path& output,
+                               std::vector<std::pair<BAMReadId, std::uint16_t>>& tagged, const std::string& tag,
+                               std::string* err) {
+    const auto alpha = [](char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); };
+    if (tag.size() != 2 || !alpha(tag[0]) || !(alpha(tag[1]) || (tag[1] >= '0' && tag[1] <= '9'))) {
+        set_err(err, "the tag '" + tag + "' is not [A-Za-z][A-Za-z0-9]");
+        return UINT32_MAX;
+    }
+    std::sort(tagged.begin(), tagged.end());
+    std::vector<BAMReadId> bam_ids;
+    bam_ids.reserve(tagged.size());
+    for (const auto& t : tagged) bam_ids.push_back(t.first);
+    {  // a first pass over the records to be written: none may carry the tag (nothing is written before this is known)
+        BgzfReader in;
+        if (!in.open(input)) { set_err(err, "could not open " + input.string()); return UINT32_MAX; }
+        BamHeader h;
+        if (!read_header(in, h, err)) return UINT32_MAX;
+        std::vector<unsigned char> rec;
+        std::string rec_err;
+        auto next = bam_ids.begin();
+        for (BAMReadId id = 0; next != bam_ids.end() && read_record(in, rec, &rec_err); ++id) {
+            if (id != *next) continue;
+            while (next != bam_ids.end() && *next == id) ++next;
+            bool malformed = false;
+            if (record_has_tag(rec, tag[0], tag[1], &malformed)) {
+                set_err(err, "record " + std::to_string(id) + " already carries the tag " + tag);
+                return UINT32_MAX;
+            }
+            if (malformed) { set_err(err, "BAM record with optional fields past its end"); return UINT32_MAX; }
+        }
+        if (!rec_err.empty()) { set_err(err, rec_err); return UINT32_MAX; }
+    }
+    const RecordEdit append = [&](std::vector<unsigned char>& rec, std::size_t k) {
+        const std::uint16_t v = tagged[k].second;
+        const unsigned char field[5] = {(unsigned char)tag[0], (unsigned char)tag[1], 'S', (unsigned char)(v & 0xFF),
+                                        (unsigned char)(v >> 8)};
+        rec.insert(rec.end(), field, field + 5);
+        const std::uint32_t block_size = le32(rec.data()) + 5u;
+        for (int b = 0; b < 4; ++b) rec[b] = (unsigned char)((block_size >> (8 * b)) & 0xFF);
+    };
+    return write_bam_edited(input, output, bam_ids, append, err);
+}
+
+namespace {
+
+std::uint32_t write_bam_edited(const std::filesystem::path& input, const std::filesystem::path& output,
+                               std::vector<BAMReadId>& bam_ids, const RecordEdit& edit, std::string* err) {
     BgzfReader in;
     if (!in.open(input)) { set_err(err, "could not open " + input.string()); return UINT32_MAX; }
     BamHeader h;
@@ -808,6 +908,7 @@ std::uint32_t write_bam(const std::filesystem::path& input, const std::filesyste
     std::uint32_t written = 0;
     while (next != bam_ids.end() && read_record(in, rec, &rec_err)) {
         if (id == *next) {
+            if (edit) edit(rec, written);
             if (as_bam) {
                 if (!out.write(rec.data(), rec.size())) { set_err(err, "write failed"); return UINT32_MAX; }
             } else {
@@ -832,6 +933,8 @@ std::uint32_t write_bam(const std::filesystem::path& input, const std::filesyste
     }
     return written;
 }
+
+}  // namespace
 
 bool write_synthetic_bam(const std::filesystem::path& path, const std::string& ref_name,
                          std::uint32_t ref_length, const std::vector<BamRecordSpec>& records,

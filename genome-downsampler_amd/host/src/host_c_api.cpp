@@ -180,6 +180,11 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
         cfg.replicates = std::vector<std::uint32_t>();
         if (q.replicates_further) cfg.replicates->assign(q.replicates_further, q.replicates_further + q.n_replicates_further);
     }
+    if (q.has_thresholds) {
+        cfg.thresholds_lo = q.thresholds_lo;
+        cfg.thresholds_hi = q.thresholds_hi;
+    }
+    if (given(q.thresholds_tag)) cfg.thresholds_tag = q.thresholds_tag;
     if (q.has_proportion)
         cfg.proportion = bam_api::BamApiConfig::Proportion{q.proportion_num, q.proportion_den, q.proportion_floor};
     return cfg;
@@ -187,8 +192,9 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
 
 // Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
 // amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
-enum class Mode { MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+enum class Mode { THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
 Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (cfg.thresholds_hi || given(q.thresholds_tag) || given(q.thresholds_report)) return Mode::THRESHOLDS;
     if (cfg.mean_depth || cfg.budget_bases || given(q.mean_depth_targets) || given(q.mean_depth_report))
         return Mode::MEAN_DEPTH;
     if (cfg.proportion || given(q.proportional_report)) return Mode::PROPORTIONAL;
@@ -210,6 +216,7 @@ struct ModeWords {
 };
 ModeWords words_of(Mode mode) {
     switch (mode) {
+        case Mode::THRESHOLDS: return {"coverage thresholds do not", "coverage thresholds"};
         case Mode::MEAN_DEPTH: return {"mean-depth downsampling does not", "mean-depth downsampling"};
         case Mode::PROPORTIONAL: return {"proportional downsampling does not", "proportional downsampling"};
         case Mode::REPLICATES: return {"disjoint replicates do not", "disjoint replicates"};
@@ -239,6 +246,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
         refuse("budget downsampling needs budget_reads or budget_fraction");
     if (mode == Mode::MEAN_DEPTH && !cfg.mean_depth && !cfg.budget_bases)
         refuse("mean-depth downsampling needs mean_depth or budget_bases");
+    if (mode == Mode::THRESHOLDS && !cfg.thresholds_hi) refuse("thresholds_tag and thresholds_report need thresholds");
     if (mode == Mode::PROPORTIONAL && !cfg.proportion) refuse("proportional downsampling needs a proportion");
     if (mode == Mode::LADDER && cfg.coverage_ladder.empty()) refuse("a coverage ladder needs at least one level");
     if (mode == Mode::LADDER && ladder_template.find("{M}") == std::string::npos)
@@ -259,7 +267,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
     if (given(q.fragment_report) && !cfg.fragment_depth) refuse("a fragment report needs fragment_depth");
     if (q.has_regions &&
         (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL ||
-         mode == Mode::MEAN_DEPTH))
+         mode == Mode::MEAN_DEPTH || mode == Mode::THRESHOLDS))
         refuse(words.refuses + " go together with a coverage profile");
     if (mode != Mode::PLAIN && solver.uses_quality_of_reads()) refuse(words.refuses + " take a solver that grades by quality");
     if (mode != Mode::PLAIN && hip == nullptr) refuse("this solver has no " + words.noun);
@@ -354,6 +362,24 @@ bool write_proportional_report(const char* path, const qmcp_hip_proportional_sta
                  (unsigned long long)ps.floor_positions, (unsigned long long)ps.capped_positions);
     std::fprintf(f, "max_depth\t%u\nmax_need\t%u\nnum\t%u\nden\t%u\nfloor\t%u\nplain_route\t%u\nrecords_written\t%u\n",
                  ps.max_depth, ps.max_need, ps.num, ps.den, ps.floor, ps.plain_route, (unsigned)written);
+    return std::fclose(f) == 0;
+}
+
+// stat<TAB>value: the qmcp_hip_thresholds_stats and the records written, then one M<TAB>reads line per coverage of the range
+bool write_thresholds_report(const char* path, const qmcp_hip_thresholds_stats& ts, const std::vector<std::uint64_t>& counts,
+                             std::int64_t written) {
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "reads_placed\t%llu\nn_kept\t%llu\nnesting_violations\t%llu\n", (unsigned long long)ts.reads_placed,
+                 (unsigned long long)ts.n_kept, (unsigned long long)ts.nesting_violations);
+    std::fprintf(f, "coverage_lo\t%u\ncoverage_hi\t%u\ntop\t%u\nsolves\t%u\nsaturated\t%u\ncount_entries\t%u\n"
+                    "ms_thresholds\t%.6g\nms_solves\t%.6g\nrecords_written\t%u\n",
+                 ts.coverage_lo, ts.coverage_hi, ts.top, ts.solves, ts.saturated, ts.count_entries, (double)ts.ms_thresholds,
+                 (double)ts.ms_solves, (unsigned)written);
+    std::fprintf(f, "#M\treads\n");
+    for (std::size_t k = 0; k < counts.size(); ++k)
+        std::fprintf(f, "%zu\t%llu\n", (std::size_t)ts.coverage_lo + k, (unsigned long long)counts[k]);
     return std::fclose(f) == 0;
 }
 
@@ -482,6 +508,14 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         case Mode::CEILING: write_reads(*hip->solve_ceiling(M, api, offsets, starts, ends, caps), false, q.out_path); break;
         case Mode::BUDGET: write_reads(*hip->solve_budget(M, api), false, q.out_path); break;
         case Mode::MEAN_DEPTH: write_reads(*hip->solve_mean_depth(M, api), false, q.out_path); break;
+        case Mode::THRESHOLDS: {  // the reads with a threshold, each record with its tag; no find_pairs
+            kept = *hip->solve_thresholds(api);
+            std::vector<std::uint16_t> values;
+            values.reserve(kept.size());
+            for (bam_api::ReadIndex i : kept) values.push_back(hip->last_thresholds()[i]);
+            written.push_back(api.write_tagged_reads(q.out_path, kept, values, api.thresholds_tag()));
+            break;
+        }
         case Mode::LADDER: {
             const auto levels = hip->solve_ladder(M, api, api.coverage_ladder());
             for (std::size_t j = 0; j < levels.size(); ++j)
@@ -528,6 +562,9 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         reported = write_proportional_report(q.proportional_report, hip->last_proportional_stats(), written[0]);
     if (mode == Mode::BUDGET && given(q.budget_report))
         reported = write_budget_report(q.budget_report, hip->last_budget_stats(), hip->last_budget_curve(), written[0]);
+    if (mode == Mode::THRESHOLDS && given(q.thresholds_report))
+        reported = write_thresholds_report(q.thresholds_report, hip->last_thresholds_stats(), hip->last_threshold_counts(),
+                                           written[0]);
     if (mode == Mode::MEAN_DEPTH && given(q.mean_depth_report))
         reported = write_mean_depth_report(q.mean_depth_report, hip->last_mean_depth_stats(), hip->last_mean_depth_curve(),
                                            written[0]);
@@ -948,6 +985,29 @@ std::int64_t qmcp_host_copy_records(const char* in_path, const char* out_path, c
     try {
         std::vector<bam_api::BAMReadId> v(ids, ids + n);
         const std::uint32_t written = bam_api::write_bam(in_path, out_path, v, &msg);
+        if (written != UINT32_MAX) rc = (std::int64_t)written;
+    } catch (const std::exception& e) {
+        msg = e.what();
+    }
+    if (err && cap) {
+        std::strncpy(err, msg.c_str(), cap - 1);
+        err[cap - 1] = 0;
+    }
+    return rc;
+}
+
+// qmcp_host_copy_records with the aux field <tag>:S:<values[k]> appended to the record ids[k] (bam_api::write_bam_tagged):
+// -1 with the reason in err -- before anything is written -- for a tag that is not [A-Za-z][A-Za-z0-9] and for a record
+// that carries the tag already.
+std::int64_t qmcp_host_copy_records_tagged(const char* in_path, const char* out_path, const std::uint64_t* ids,
+                                           const std::uint16_t* values, std::uint64_t n, const char* tag, char* err,
+                                           std::size_t cap) {
+    std::string msg;
+    std::int64_t rc = -1;
+    try {
+        std::vector<std::pair<bam_api::BAMReadId, std::uint16_t>> tagged;
+        for (std::uint64_t k = 0; k < n; ++k) tagged.emplace_back(ids[k], values[k]);
+        const std::uint32_t written = bam_api::write_bam_tagged(in_path, out_path, tagged, tag ? tag : "", &msg);
         if (written != UINT32_MAX) rc = (std::int64_t)written;
     } catch (const std::exception& e) {
         msg = e.what();

@@ -407,6 +407,43 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_ceiling(std::uint32_t require
     return kept;
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_thresholds(bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    if (!bam_api.thresholds() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
+        throw std::invalid_argument("coverage thresholds need a BamApi built with BamApiConfig::thresholds_hi");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    const std::uint32_t lo = bam_api.thresholds_lo(), hi = bam_api.thresholds_hi();
+    thresholds_.assign(n, (std::uint16_t)QMCP_THRESHOLD_NEVER);
+    threshold_counts_.assign(hi >= lo ? (std::size_t)(hi - lo) + 1 : 0, 0);
+    const int rc = qmcp_hip_solve_thresholds_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
+                                                  reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                                  lo, hi, QMCP_THRESHOLDS_WHOLE_PAIRS, thresholds_.data(),
+                                                  threshold_counts_.data(), (std::uint32_t)threshold_counts_.size(), &stats_,
+                                                  &thstats_);
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    if (rc != QMCP_OK) die("qmcp_hip_solve_thresholds_host", rc);
+    threshold_counts_.resize(thstats_.count_entries);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    auto kept = std::make_unique<Solution>();
+    kept->reserve(thstats_.n_kept);
+    for (std::size_t i = 0; i < n; ++i)
+        if (thresholds_[i] != QMCP_THRESHOLD_NEVER) kept->push_back(i);
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return kept;
+}
+
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();

@@ -1361,6 +1361,63 @@ int qmcp_hip_solve_mean_depth_device(qmcp_hip_ctx* ctx,
                                      uint32_t curve_capacity, uint64_t* d_keep_mask_out, void* hip_stream,
                                      qmcp_hip_stats* stats, qmcp_hip_mean_depth_stats* mstats);
 
+/* Coverage thresholds: one call tags every read with the smallest coverage that keeps it -- a titration, a rarefaction
+ * curve, "tag the BAM once, cut any downsample later with a filter".  Every other entry answers "which reads at coverage
+ * M"; this one answers it for every M in coverage_lo .. coverage_hi at once, in one 16-bit integer per read.
+ * Input: reads, contig_ids, contig_lengths / n_contigs, limits and read validation exactly as in
+ * qmcp_hip_solve_by_contig_host; 1 <= coverage_lo <= coverage_hi <= QMCP_THRESHOLDS_COVERAGE_MAX.
+ * Definitions: keep_M is the mask qmcp_hip_solve_by_contig_host returns at M.
+ * Thresholds: thresholds_out[i] (n_reads entries) is the smallest M in coverage_lo .. coverage_hi with i in keep_M, and
+ * QMCP_THRESHOLD_NEVER for an unplaced read and for a read that no such M keeps.  Reads kept at coverage_lo get
+ * coverage_lo.  This definition needs nothing of the shape of the sets keep_M.
+ * Stop: M ascends from coverage_lo, one whole solve each, and solving stops after the first M at which every placed read
+ * has a threshold, or at coverage_hi: that M is tstats->top.  Later solves could not assign anything.
+ * Violations: tstats->nesting_violations counts the (read, M) pairs with coverage_lo <= M <= top in which a read that
+ * already has a threshold is not in keep_M.  WHILE IT IS 0, (thresholds_out[i] <= M) IS keep_M, BIT FOR BIT, FOR EVERY M
+ * IN coverage_lo .. coverage_hi.  That the kept sets are nested in M -- the count is 0 -- has been observed on every input
+ * tried (exhaustively on small contigs, and on random inputs at every coverage) and is NOT proven; a caller that relies
+ * on the equivalence checks the count.
+ * QMCP_THRESHOLDS_WHOLE_PAIRS: reads (2q, 2q + 1) are pair q and n_reads must be even.  A placed read takes the smaller
+ * of its own threshold and its PLACED mate's; an unplaced mate lends nothing and stays QMCP_THRESHOLD_NEVER.  Then
+ * (thresholds_out[i] <= M) is the mask of QMCP_BUDGET_WHOLE_PAIRS's completion of keep_M (while the count is 0).
+ * Counts: counts_out (may be NULL, then counts_capacity must be 0) [M - coverage_lo] = the reads with final threshold <= M,
+ * for M = coverage_lo .. min(coverage_hi, coverage_lo + counts_capacity - 1); tstats->count_entries entries are written.
+ * A HOST array in both entries.
+ * Errors, all decided from the arguments before the context is looked at: null arrays, unknown flag bits, an odd n_reads
+ * under the flag, coverage_lo == 0, coverage_lo > coverage_hi and a counts_capacity without counts_out are QMCP_EINVAL;
+ * coverage_hi > QMCP_THRESHOLDS_COVERAGE_MAX, n_contigs > 2^24 and n_reads > 2^31 are QMCP_ERANGE.  A bad contig id or
+ * read is found on the device with the codes of the by-contig entry, and thresholds_out is then left untouched.
+ * stats (may be NULL): the batch-summed qmcp_hip_stats of the last solve (at top).  tstats (may be NULL): see the struct.
+ * The device entry is ordered after hip_stream; both entries block (no _begin / _end form). */
+#define QMCP_THRESHOLD_NEVER 0xFFFFu
+#define QMCP_THRESHOLDS_COVERAGE_MAX 65534u
+#define QMCP_THRESHOLDS_WHOLE_PAIRS 1u
+typedef struct qmcp_hip_thresholds_stats {
+    uint64_t reads_placed;        /* placed reads                                                                       */
+    uint64_t n_kept;              /* reads with final threshold <= coverage_hi                                          */
+    uint64_t nesting_violations;  /* see above; 0 on every input seen so far                                            */
+    uint32_t coverage_lo;         /* as given                                                                           */
+    uint32_t coverage_hi;         /* as given                                                                           */
+    uint32_t top;                 /* the last coverage solved                                                           */
+    uint32_t solves;              /* whole solves run: top - coverage_lo + 1                                            */
+    uint32_t saturated;           /* 1 when every placed read has a threshold                                           */
+    uint32_t count_entries;       /* entries written to counts_out                                                      */
+    float ms_thresholds;          /* device time of k_thresholds_step, k_thresholds_finish, k_thresholds_counts         */
+    float ms_solves;              /* device time of the solves                                                          */
+} qmcp_hip_thresholds_stats;
+int qmcp_hip_solve_thresholds_host(qmcp_hip_ctx* ctx,
+                                   const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                   uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                   uint32_t coverage_lo, uint32_t coverage_hi, uint32_t flags, uint16_t* thresholds_out,
+                                   uint64_t* counts_out /* may be NULL */, uint32_t counts_capacity, qmcp_hip_stats* stats,
+                                   qmcp_hip_thresholds_stats* tstats);
+int qmcp_hip_solve_thresholds_device(qmcp_hip_ctx* ctx,
+                                     const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                     uint64_t n_reads, const uint32_t* contig_lengths, uint32_t n_contigs,
+                                     uint32_t coverage_lo, uint32_t coverage_hi, uint32_t flags, uint16_t* d_thresholds_out,
+                                     uint64_t* counts_out /* host; may be NULL */, uint32_t counts_capacity,
+                                     void* hip_stream, qmcp_hip_stats* stats, qmcp_hip_thresholds_stats* tstats);
+
 /* Proportional downsampling: keep a fraction of the depth everywhere.  Every other solving entry asks for a flat depth,
  * min(cov(p), cap) with a cap from outside the data; this one takes its demand from the data's own depth, so the SHAPE of
  * the coverage survives (copy-number calling, ChIP / ATAC / RNA signal, allele balance, "this run at a quarter of the
