@@ -12,7 +12,9 @@
 //                       read) at a slot that is a multiple of 64: pass P owns the slots [P stride, (P + 1) stride),
 //                       stride = 8192 + 64 n_ranges, the slices follow each other padded to whole groups of 64 slots.
 //                       Two tables laid out [range][pass]: the slice's record count rounded up to a multiple of 64, and
-//                       (first slot - P stride) / 64 | true count << 16.
+//                       (first slot - P stride) / 64 | true count << 16.  The stable rank inside a pass comes from per-lane
+//                       counts where the pass's digits span at most 32 ranges (pm_lane_rank.inc.hip; every pass of
+//                       cfg4), from part_rank_rounds' ballots otherwise: the same ranks, so the same buffers.
 //   k_pm_row_sums,      exclusive scan over the padded count table in two launches (partial sums of the rows' parts, then
 //   k_pm_tables         every part scanned from a base it derives itself): Tp[d][P] = the PADDED FLAT position of the slice --
 //                       range d's records in read-index order are its slices in pass order, each padded to whole
@@ -89,6 +91,36 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         }
         return lo;
     };
+    // A pass's contigs and the digits they span.  Which lane owns which read (below) follows from them, so they are
+    // worked out a pass ahead, behind the loads of the pass before; only the workgroup's first pass waits for them.
+    struct PassForm { uint32_t c_first, c_last, match_bits, d_lo, d_hi; };
+    auto form_of = [&](uint32_t base, uint32_t count) {
+        PassForm f;
+        f.c_first = n_contigs > 1 ? contig_of(base) : 0u;
+        f.c_last = n_contigs > 1 ? contig_of(base + count - 1) : 0u;
+        // the pass's digits lie in the ranges its contigs span on the grid's axis: from the first contig's first
+        // position to the last one's last
+        const uint32_t len_last = (uint32_t)(contig_pos_off[f.c_last + 1] - contig_pos_off[f.c_last]);
+        f.d_lo = (vbase[f.c_first] >> shift) & 255u;
+        f.d_hi = ((vbase[f.c_last] + (len_last ? len_last - 1u : 0u)) >> shift) & 255u;
+        f.match_bits = f.d_hi >= f.d_lo ? 32u - (uint32_t)__builtin_clz((f.d_hi - f.d_lo) | 1u) : 8u;
+        if (f.d_hi == f.d_lo) f.match_bits = 0;
+        // (uniform by construction; carried from pass to pass in scalar registers)
+        f.c_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.c_first);
+        f.c_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.c_last);
+        f.d_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.d_lo);
+        f.d_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.d_hi);
+        f.match_bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.match_bits);
+        return f;
+    };
+    // Ranking by per-lane counts (pm_lane_rank.inc.hip) serves the unfiltered producer -- the filter's exception lists
+    // are in read-index order per wave under the strided ownership -- and loads 16 bytes a lane.
+    const bool lane_form_ok = ell_reg == 0u && (((uintptr_t)starts | (uintptr_t)ends) & 15u) == 0u;
+    PassForm next_form = {0u, 0u, 0u, 0u, 0u};
+    {
+        const uint64_t base0 = (uint64_t)blockIdx.x * kPmPassesPerWg * kPmPass;
+        if (base0 < n) next_form = form_of((uint32_t)base0, min((uint32_t)kPmPass, n - (uint32_t)base0));
+    }
     for (int g = 0; g < kPmPassesPerWg; ++g) {
         const uint32_t P = blockIdx.x * kPmPassesPerWg + g;
         const uint64_t base64 = (uint64_t)P * kPmPass;
@@ -100,29 +132,40 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         const uint32_t base = (uint32_t)base64;
         const uint32_t count = min((uint32_t)kPmPass, n - base);
         const uint32_t wbase = base + w * (kSortItems * 64);
-        // all of the pass's loads first (32 in flight per thread)
+        const PassForm form = next_form;
+        const uint32_t c_first = form.c_first, c_last = form.c_last, match_bits = form.match_bits;
+        // (uniform) who owns which read of the wave's 1 024: lane l the sixteen consecutive reads from 16 l on, where the
+        // pass is ranked by per-lane counts; otherwise the reads l, l + 64, ...: the thread's k-th read is lane0 + k kstep
+        const bool blocked = lane_form_ok && match_bits <= kPmLaneFormBits;
+        const uint32_t lane0 = wbase + (blocked ? 16u * (uint32_t)lane : (uint32_t)lane);
+        const uint32_t kstep = blocked ? 1u : 64u;
+        // all of the pass's loads first (32 in flight per thread; eight of 16 bytes under the blocked ownership, where
+        // a lane's reads are 64 contiguous bytes of each array -- they read at the rate of the coalesced dwords)
         Rec rec[kSortItems];  // key: start, then global start; val: end
+        if (blocked && count == (uint32_t)kPmPass) {  // (uniform)
+            // (a vector type of the language, not uint4: that one is a struct, its load is split into four words
+            //  before the two branches meet, and the branches' word loads are then merged into one run of 32)
+            const PmQuad* const s4 = reinterpret_cast<const PmQuad*>(starts + lane0);
+            const PmQuad* const e4 = reinterpret_cast<const PmQuad*>(ends + lane0);
 #pragma unroll
-        for (int k = 0; k < kSortItems; ++k) {
-            const uint32_t i = min(wbase + k * 64 + lane, n - 1);  // clamped: every lane loads
-            rec[k].key = starts[i];
-            rec[k].val = ends[i];
+            for (int q = 0; q < kSortItems / 4; ++q) {
+                const PmQuad s = s4[q], e = e4[q];
+                rec[4 * q].key = s.x; rec[4 * q + 1].key = s.y; rec[4 * q + 2].key = s.z; rec[4 * q + 3].key = s.w;
+                rec[4 * q].val = e.x; rec[4 * q + 1].val = e.y; rec[4 * q + 2].val = e.z; rec[4 * q + 3].val = e.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kSortItems; ++k) {
+                const uint32_t i = min(lane0 + k * kstep, n - 1);  // clamped: every lane loads
+                rec[k].key = starts[i];
+                rec[k].val = ends[i];
+            }
         }
         for (int i = threadIdx.x; i < kPmWaves * 256; i += kPmThreads) s_cnt[i] = 0;
         // the pass's 128 words of the keep mask are cleared here (saves a memset launch)
         if (zero_mask && threadIdx.x < 128 && P * 128u + threadIdx.x < (n + 63u) / 64u) zero_mask[P * 128u + threadIdx.x] = 0ull;
-        const uint32_t c_first = n_contigs > 1 ? contig_of(base) : 0u;
-        const uint32_t c_last = n_contigs > 1 ? contig_of(base + count - 1) : 0u;
-        uint32_t match_bits;
-        {
-            // the pass's digits lie in the ranges its contigs span on the grid's axis: from the first contig's first
-            // position to the last one's last
-            const uint32_t len_last = (uint32_t)(contig_pos_off[c_last + 1] - contig_pos_off[c_last]);
-            const uint32_t d_lo = (vbase[c_first] >> shift) & 255u;
-            const uint32_t d_hi = ((vbase[c_last] + (len_last ? len_last - 1u : 0u)) >> shift) & 255u;
-            match_bits = d_hi >= d_lo ? 32u - (uint32_t)__builtin_clz((d_hi - d_lo) | 1u) : 8u;
-            if (d_hi == d_lo) match_bits = 0;
-        }
+        if (g + 1 < kPmPassesPerWg && base64 + kPmPass < n)
+            next_form = form_of(base + kPmPass, min((uint32_t)kPmPass, n - base - (uint32_t)kPmPass));
         uint32_t skip = 0;  // bit k: the thread's k-th read is an exception (near-uniform route)
         uint32_t filled = 0;  // (uniform) exceptions of the pass this wave has met
         // An exception is put aside the moment it is recognised (its end is then dead: kept until later, the sixteen
@@ -153,7 +196,7 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
             const uint32_t last = len ? len - 1u : 0u;
 #pragma unroll
             for (int k = 0; k < kSortItems; ++k) {
-                const uint32_t i = wbase + k * 64 + lane;
+                const uint32_t i = lane0 + k * kstep;
                 const uint32_t s = rec[k].key, e = rec[k].val;
                 bool isx = false;
                 if (i < n) {
@@ -169,7 +212,7 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         } else {
 #pragma unroll
             for (int k = 0; k < kSortItems; ++k) {
-                const uint32_t i = wbase + k * 64 + lane;
+                const uint32_t i = lane0 + k * kstep;
                 bool isx = false;
                 uint32_t gs = 0, ge = 0;
                 if (i < n) {
@@ -194,7 +237,12 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         {
             uint32_t* const s_cnt_w = s_cnt + w * 256;
             const uint32_t bound = base + count;
-            switch (match_bits) {  // uniform
+            if (blocked) {  // uniform
+                PmLdsWord* const s_w = (PmLdsWord*)(s_stage + w * (kSortItems * 64));
+                const uint32_t n_pairs = (form.d_hi - form.d_lo) / 2u + 1u;
+                if (count == (uint32_t)kPmPass) pm_rank_lane_counts<true>(rec, rank, lane0, bound, shift, form.d_lo, n_pairs, lane, s_w, s_cnt_w);
+                else pm_rank_lane_counts<false>(rec, rank, lane0, bound, shift, form.d_lo, n_pairs, lane, s_w, s_cnt_w);
+            } else switch (match_bits) {  // uniform
                 case 0: part_rank_rounds<0>(rec, rank, wbase, bound, shift, lane, s_cnt_w, skip); break;
                 case 1: part_rank_rounds<1>(rec, rank, wbase, bound, shift, lane, s_cnt_w, skip); break;
                 case 2: part_rank_rounds<2>(rec, rank, wbase, bound, shift, lane, s_cnt_w, skip); break;
@@ -240,10 +288,10 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < kSortItems; ++k) {
-            const uint32_t i = wbase + k * 64 + lane;
+            const uint32_t i = lane0 + k * kstep;
             if (i < n && !((skip >> k) & 1u)) {
                 const uint32_t d = (rec[k].key >> shift) & 255u;
-                const uint32_t local = (uint32_t)(w * (kSortItems * 64) + k * 64 + lane);  // < 8192
+                const uint32_t local = i - base;  // < 8192
                 s_stage[s_cnt[w * 256 + d] + rank[k]] = (rec[k].key & ((1u << shift) - 1u)) | (local << 16);
             }
         }

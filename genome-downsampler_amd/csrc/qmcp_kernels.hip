@@ -103,6 +103,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/sweep_mixed.inc.hip"
 #include "kernels/mark_and_next_rows.inc.hip"
 #include "kernels/launchers.inc.hip"
+#include "kernels/pm_lane_rank.inc.hip"
 #include "kernels/pass_major.inc.hip"
 #include "kernels/near_uniform.inc.hip"
 #include "kernels/by_contig.inc.hip"
