@@ -15,6 +15,14 @@
 //                       (first slot - P stride) / 64 | true count << 16.  The stable rank inside a pass comes from per-lane
 //                       counts where the pass's digits span at most 32 ranges (pm_lane_rank.inc.hip; every pass of
 //                       cfg4), from part_rank_rounds' ballots otherwise: the same ranks, so the same buffers.
+//                       Such a pass of the unfiltered producer (at most 32 slices, whichever form ranked it) is staged in
+//                       LDS in the padded layout it has in memory -- a record at its slice's padded base plus its rank --
+//                       and the stage's words [0, padded total) leave as ONE flat run to the slots from P stride on: two
+//                       16-byte LDS reads and one 16-byte store a stream per thread and step, a wave's store 1 KB, no
+//                       compare, no readlane, no loop over slices; the padding inside a group receives whatever the
+//                       stage held (the consumers mask by the record count), nothing beyond the padded total is written
+//                       (tests/pm_flat_writeout_model.py restates it on the host).  Other passes and the filtered
+//                       producer stage unpadded and go out slice by slice, two slices a wave at a time.
 //   k_pm_row_sums,      exclusive scan over the padded count table in two launches (partial sums of the rows' parts, then
 //   k_pm_tables         every part scanned from a base it derives itself): Tp[d][P] = the PADDED FLAT position of the slice --
 //                       range d's records in read-index order are its slices in pass order, each padded to whole
@@ -54,6 +62,14 @@ static constexpr int kPmPassesPerWg = 4;         // a workgroup's passes leave t
 static constexpr size_t kPmSortLds = ((size_t)kPmPass + kPmWaves * 256 + 2 * 256 + 16 + 2 * kPmPassesPerWg * 256 + kPmWaves * 3 * 128) * sizeof(uint32_t);
 static constexpr uint32_t kPmExcPerWave = 128;  // list slots per wave and pass: an eighth of the wave's 1 024 reads
 
+// The flat write-out (below): a pass of at most kPmFlatDigits slices is staged padded and leaves as one run.
+static constexpr uint32_t kPmFlatDigits = 32;
+static constexpr uint32_t kPmStageWords = 10240;
+static constexpr uint32_t kPmFlatSlots = 8;   // slots a thread copies per step: 16 bytes a stream (8-byte stores of 4 slots: 0.280 against 0.277 ms)
+static_assert(kPmStageWords >= (uint32_t)kPmPass + kPmFlatDigits * 63u, "a padded pass of 32 slices fits the stage");
+static_assert(kPmStageWords <= (uint32_t)kPmPass + kPmWaves * 3u * kPmExcPerWave, "the stage's tail aliases s_exc and nothing else");
+static_assert(kPmFlatDigits == 1u << kPmLaneFormBits, "a pass the lane counts rank is a pass the flat write-out takes");
+
 #ifndef QMCP_PM_MIN_WAVES
 #define QMCP_PM_MIN_WAVES 4  // waves per SIMD the register allocation aims at (6 -- three workgroups per CU -- spills: 0.42 against 0.29 ms)
 #endif
@@ -73,14 +89,18 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
     // is set if a wave met more than its slots hold (the list is then incomplete).  ell_reg == 0: every read is regular.
     uint32_t ell_reg, uint32_t* __restrict__ exc, uint32_t exc_cap, uint32_t* __restrict__ exc_cnt) {
     extern __shared__ uint32_t s_pm[];
-    uint32_t* s_stage = s_pm;                           // [8192] a pass's records, sorted: key | index in pass << 16
-    uint32_t* s_cnt = s_stage + kPmPass;                // [8][256] per-wave digit counts, then offsets
+    // A pass's records, sorted: key | index in pass << 16.  Back to back where the pass leaves slice by slice (8 192
+    // words); in the padded layout it has in memory -- every slice from a multiple of 64 -- where it leaves as one flat
+    // run (at most 32 slices: up to 63 words of padding each).  The words past 8 192 are the filtered producer's
+    // exception corner: the filter never takes the flat form, so the two never meet.
+    uint32_t* s_stage = s_pm;                           // [10240], the last 2 048 aliased by s_exc
+    uint32_t* s_exc = s_stage + kPmPass;                // [8][128][3] every wave's exceptions of the pass, until the pass is written out
+    uint32_t* s_cnt = s_exc + kPmWaves * 3 * kPmExcPerWave;  // [8][256] per-wave digit counts, then offsets
     uint32_t* s_gbase = s_cnt + kPmWaves * 256;         // [256] where a digit's records begin inside the sorted pass
     uint32_t* s_pbase = s_gbase + 256;                  // [256] ... and where its slice begins inside the pass's slots (padded)
     uint32_t* s_wave = s_pbase + 256;                   // [16]
     uint32_t* s_tabc = s_wave + 16;                     // [4][256] the workgroup's table entries
     uint32_t* s_tabl = s_tabc + kPmPassesPerWg * 256;   // [4][256]
-    uint32_t* s_exc = s_tabl + kPmPassesPerWg * 256;    // [8][128][3] every wave's exceptions of the pass, until the pass is written out
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t mn = 0xFFFFFFFFu, mx = 0, bad = 0;
     auto contig_of = [&](uint32_t i) {
@@ -139,6 +159,13 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         const bool blocked = lane_form_ok && match_bits <= kPmLaneFormBits;
         const uint32_t lane0 = wbase + (blocked ? 16u * (uint32_t)lane : (uint32_t)lane);
         const uint32_t kstep = blocked ? 1u : 64u;
+        // (uniform) the pass is staged padded and leaves as one flat run: at most 32 slices (match_bits <= 5 is
+        // d_lo <= d_hi <= d_lo + 31), whichever form ranks it; the filter keeps its corner of the stage
+#ifdef QMCP_PM_LAB_SLICE_WRITEOUT
+        const bool flat = false;  // (lab build only: the slice-by-slice write-out for every pass, to time against)
+#else
+        const bool flat = ell_reg == 0u && match_bits <= kPmLaneFormBits;
+#endif
         // all of the pass's loads first (32 in flight per thread; eight of 16 bytes under the blocked ownership, where
         // a lane's reads are 64 contiguous bytes of each array -- they read at the rate of the coalesced dwords)
         Rec rec[kSortItems];  // key: start, then global start; val: end
@@ -237,6 +264,16 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         {
             uint32_t* const s_cnt_w = s_cnt + w * 256;
             const uint32_t bound = base + count;
+#ifdef QMCP_PM_LAB_NO_RANK
+            // (lab build only: the producer without its ranking, to time against.  A record's rank is its lane's own
+            //  index, every digit of the interval is said to hold 32 records a wave: every index stays inside the
+            //  stage and the pass's slots, the buffers are not the model's and only the producer may run on them)
+            if (blocked) {
+#pragma unroll
+                for (int k = 0; k < kSortItems; ++k) rank[k] = (uint32_t)lane & 31u;
+                if (lane < 32 && form.d_lo + (uint32_t)lane < 256u) s_cnt_w[form.d_lo + (uint32_t)lane] = 32u;
+            } else
+#endif
             if (blocked) {  // uniform
                 PmLdsWord* const s_w = (PmLdsWord*)(s_stage + w * (kSortItems * 64));
                 const uint32_t n_pairs = (form.d_hi - form.d_lo) / 2u + 1u;
@@ -278,7 +315,7 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
             for (int x = 0; x < w; ++x) { wave_base += s_wave[x]; pwave_base += s_wave[8 + x]; }
             const uint32_t tile_off = s_gbase[d] + wave_base;
             const uint32_t ptile_off = s_pbase[d] + pwave_base;
-            uint32_t run = tile_off;
+            uint32_t run = flat ? ptile_off : tile_off;  // (the stage is padded where the pass leaves flat)
 #pragma unroll
             for (int x = 0; x < kPmWaves; ++x) { const uint32_t cx = s_cnt[x * 256 + d]; s_cnt[x * 256 + d] = run; run += cx; }
             s_gbase[d] = tile_off;
@@ -299,7 +336,28 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
         // out, slice by slice: wave w takes the digits w, w + 8, ..., two at a time -- one per half-wave --, four records
         // per lane and store (8 bytes of positions, 8 of indices: slices begin at multiples of 64 slots, so every store is
         // aligned and a half-wave's store is one 256-byte run)
-        {
+        if (flat) {  // uniform
+            // ... or flat: the stage already is the pass's slots [P stride, P stride + ptot), padding and all, so every
+            // thread copies runs of eight consecutive slots -- two aligned 16-byte LDS reads, the low halves to the
+            // positions, the high halves to the indices, 16 bytes a stream: a wave's store is one 1 KB run.  ptot, the
+            // pass's padded total, is a multiple of 64 and P stride one too: nothing at or beyond ptot is written.  The
+            // padding inside a group receives what the stage held (the consumers mask by the record count).
+            const uint32_t ptot = s_wave[8] + s_wave[9] + s_wave[10] + s_wave[11];  // (the digit threads' four waves)
+            const PmLdsQuad* const st4 = (const PmLdsQuad*)s_stage;
+            uint16_t* const kout = keys16 + (size_t)P * stride;
+            uint16_t* const iout = idx16 + (size_t)P * stride;
+            for (uint32_t s = kPmFlatSlots * threadIdx.x; s < ptot; s += kPmFlatSlots * kPmThreads) {
+                const PmQuad a = st4[s >> 2], b = st4[(s >> 2) + 1u];
+                const PmQuad kq = {(a.x & 0xFFFFu) | (a.y << 16), (a.z & 0xFFFFu) | (a.w << 16), (b.x & 0xFFFFu) | (b.y << 16), (b.z & 0xFFFFu) | (b.w << 16)};
+                const PmQuad iq = {(a.x >> 16) | (a.y & 0xFFFF0000u), (a.z >> 16) | (a.w & 0xFFFF0000u), (b.x >> 16) | (b.y & 0xFFFF0000u), (b.z >> 16) | (b.w & 0xFFFF0000u)};
+#ifndef QMCP_PM_LAB_NO_STORE  // (lab build only: the producer without its stores, to time against)
+                *reinterpret_cast<PmQuad*>(kout + s) = kq;
+                *reinterpret_cast<PmQuad*>(iout + s) = iq;
+#else
+                (void)kout; (void)iout; (void)kq; (void)iq;
+#endif
+            }
+        } else {
             const uint32_t my_d = (uint32_t)w + 8u * ((uint32_t)lane & 31u);
             const uint32_t my_tot = lane < 32 ? s_tabl[g * 256 + my_d] >> 16 : 0u;
             const uint32_t my_gb = s_gbase[my_d], my_pb = s_pbase[my_d];
@@ -326,8 +384,10 @@ __global__ __launch_bounds__(kPmThreads, QMCP_PM_MIN_WAVES) void k_pm_prepare_so
                         const uint32_t v1 = j + 1 < cnt ? s_stage[gb + j + 1] : 0u;
                         const uint32_t v2 = j + 2 < cnt ? s_stage[gb + j + 2] : 0u;
                         const uint32_t v3 = j + 3 < cnt ? s_stage[gb + j + 3] : 0u;
+#ifndef QMCP_PM_LAB_NO_STORE  // (lab build only: the producer without its stores, to time against)
                         *reinterpret_cast<uint2*>(keys16 + out0 + j) = make_uint2((v0 & 0xFFFFu) | (v1 << 16), (v2 & 0xFFFFu) | (v3 << 16));
                         *reinterpret_cast<uint2*>(idx16 + out0 + j) = make_uint2((v0 >> 16) | (v1 & 0xFFFF0000u), (v2 >> 16) | (v3 & 0xFFFF0000u));
+#endif
                     }
                 }
             }
