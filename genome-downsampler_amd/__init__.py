@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_thresholds_host", "qmcp_hip_solve_thresholds_device",
     "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
     "qmcp_hip_solve_proportional_host", "qmcp_hip_solve_proportional_device",
+    "qmcp_hip_solve_start_cap_host", "qmcp_hip_solve_start_cap_device",
 )
 
 QMCP_OK = 0
@@ -77,6 +78,8 @@ REPLICATES_WHOLE_PAIRS, REPLICATES_SHORTFALL = 1, 2  # QMCP_REPLICATES_*
 NO_STRATUM = 0xFFFFFFFF  # QMCP_NO_STRATUM: the stratum id of a read that belongs to no stratum (never kept)
 DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLETE_PAIRS
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
+START_CAP_SHORTFALL = 1  # QMCP_START_CAP_SHORTFALL
+START_CAP_REPORT_BINS = 64  # cell-size bins of downsample_bam(start_cap_report=)
 TRACK_IN, TRACK_KEPT, TRACK_SHORT_ONLY, TRACK_SKIP_ZERO = 1, 2, 4, 8  # QMCP_TRACK_*
 TRACK_FIRST_CAPACITY = 1 << 22  # records Solver.depth_track offers first (96 MiB); beyond it, one more call at the exact count
 STRATUM_TALLY_TILE = 1024  # qmcp::kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces
@@ -419,6 +422,23 @@ class DedupStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class StartCapStats(C.Structure):
+    """qmcp_hip_start_cap_stats: what the start cap before the solve found (cells: distinct (contig, start, group);
+    reads_survived: reads handed to the inner solve; cells_kept / largest_kept_cell: counted from the final mask;
+    short_positions / short_bases: only under START_CAP_SHORTFALL)"""
+    _fields_ = [("reads_placed", C.c_uint64), ("cells", C.c_uint64), ("cells_over_cap", C.c_uint64),
+                ("reads_capped", C.c_uint64), ("largest_cell", C.c_uint64), ("reads_survived", C.c_uint64),
+                ("cells_kept", C.c_uint64), ("largest_kept_cell", C.c_uint64), ("short_positions", C.c_uint64),
+                ("short_bases", C.c_uint64), ("key_bits", C.c_uint32), ("sort_passes", C.c_uint32), ("cap", C.c_uint32),
+                ("ms_cap", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+assert C.sizeof(StartCapStats) == 10 * 8 + 4 * 4
+
+
 class DepthReport:
     """what Solver.depth_report returns: contig_rows / region_rows (numpy structured arrays of DEPTH_ROW_DTYPE),
     hist_in / hist_kept (uint64, n_bins entries), stats (DepthStats); valid: no position in scope is short of
@@ -470,7 +490,9 @@ class DownsampleRequest(C.Structure):
         + [(name, C.c_int32) for name in ("amplicon_mode", "per_reference", "amplicons_by_reference", "keep_off_target",
                                           "dedup", "has_regions", "pair_aware", "template_aware", "split_spliced",
                                           "include_secondary", "fragment_depth", "ceiling", "has_budget_reads",
-                                          "has_budget_bases", "has_mean_depth", "has_replicates", "has_thresholds")]
+                                          "has_budget_bases", "has_mean_depth", "has_replicates", "has_thresholds",
+                                          "start_cap_by_strand")]
+        + [("start_cap", C.c_uint32), ("start_cap_report", C.c_char_p)]
         + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
            ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
@@ -585,6 +607,13 @@ _hip.qmcp_hip_solve_dedup_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_uint64, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                              C.c_void_p, _u64p, C.c_uint32, C.c_void_p, C.POINTER(Stats),
                                              C.POINTER(DedupStats)]
+_hip.qmcp_hip_solve_start_cap_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p,
+                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, _u64p,
+                                               C.c_uint32, C.POINTER(Stats), C.POINTER(StartCapStats)]
+_hip.qmcp_hip_solve_start_cap_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint64, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, _u64p, C.c_uint32, C.c_void_p, C.POINTER(Stats),
+                                                 C.POINTER(StartCapStats)]
 _hip.qmcp_hip_solve_profile_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p, _u32p,
                                              _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p, C.POINTER(Stats),
                                              C.POINTER(ProfileStats)]
@@ -817,6 +846,7 @@ class Solver:
         self.last_ladder_stats = None
         self.last_stratum_rows = None
         self.last_dedup_stats = None
+        self.last_start_cap_stats = None
         self.last_pair_stats = None
         self.last_template_stats = None
         self.last_template_profile_stats = None
@@ -1101,6 +1131,52 @@ class Solver:
                                                 int(hist_bins), C.c_void_p(stream), C.byref(st), C.byref(ds)))
         self.last_stats, self.last_dedup_stats = st, ds
         return ds.as_dict(), hist[:int(hist_bins)]
+
+    def solve_start_cap(self, starts, ends, contig_ids, contig_lengths, max_coverage, cap, groups=None, priorities=None,
+                        shortfall=False, hist_bins=0):
+        """at most `cap` reads of every (contig, start, group) cell reach solve_by_contig
+        (qmcp_hip_solve_start_cap_host): the survivors of a cell are its first `cap` reads by priority descending, span
+        descending, index ascending; the other placed reads are capped.  The mask is solve_by_contig's on the survivors,
+        in INPUT order.  groups / priorities: one uint32 per read or None (one group / all equal).  shortfall=True also
+        counts the positions (and bases) where the kept depth is below min(coverage of ALL placed reads, max_coverage).
+        -> (mask, capped, stats_dict, hist): capped marks the capped reads, hist[k - 1] counts the cells of size k (the
+        last of the hist_bins bins: sizes >= hist_bins).  last_stats is the inner solve's, last_start_cap_stats the
+        StartCapStats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        g = None if groups is None else _u32(groups)
+        q = None if priorities is None else _u32(priorities)
+        n = starts.size
+        assert ends.size == n and ids.size == n and (g is None or g.size == n) and (q is None or q.size == n), \
+            "one entry per read in every column"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        capped = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        hist = np.zeros(max(int(hist_bins), 1), dtype=np.uint64)
+        st, cs = Stats(), StartCapStats()
+        _check(_hip.qmcp_hip_solve_start_cap_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(g), _p32(q), n,
+                                                  _p32(lengths), lengths.size, int(max_coverage), int(cap),
+                                                  START_CAP_SHORTFALL if shortfall else 0, _p64(mask), _p64(capped),
+                                                  _p64(hist) if hist_bins else None, int(hist_bins), C.byref(st),
+                                                  C.byref(cs)))
+        self.last_stats, self.last_start_cap_stats = st, cs
+        return mask[:mask_words(n)], capped[:mask_words(n)], cs.as_dict(), hist[:int(hist_bins)]
+
+    def solve_start_cap_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, cap, d_mask,
+                               d_groups=0, d_priorities=0, shortfall=False, d_capped_mask=0, hist_bins=0, stream=0):
+        """the same on device pointers (ints; 0: no groups / no priorities / no capped mask), columns at any 4-byte
+        alignment; the masks are written to d_mask / d_capped_mask.  -> (stats_dict, hist)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        hist = np.zeros(max(int(hist_bins), 1), dtype=np.uint64)
+        st, cs = Stats(), StartCapStats()
+        _check(_hip.qmcp_hip_solve_start_cap_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends),
+                                                    C.c_void_p(d_contig_ids), C.c_void_p(d_groups or None),
+                                                    C.c_void_p(d_priorities or None), int(n_reads), _p32(lengths),
+                                                    lengths.size, int(max_coverage), int(cap),
+                                                    START_CAP_SHORTFALL if shortfall else 0, C.c_void_p(d_mask),
+                                                    C.c_void_p(d_capped_mask or None), _p64(hist) if hist_bins else None,
+                                                    int(hist_bins), C.c_void_p(stream), C.byref(st), C.byref(cs)))
+        self.last_stats, self.last_start_cap_stats = st, cs
+        return cs.as_dict(), hist[:int(hist_bins)]
 
     @staticmethod
     def _target_tables(n_contigs, target_offsets, target_starts, target_ends):
@@ -2576,6 +2652,9 @@ _DEDUP = _Mode("duplicate-aware downsampling", ("targets", "a depth report", "a 
                one_sentence=True)
 _STRATIFIED = _Mode("stratified downsampling", ("targets", "a depth report", "a coverage ladder"), one_sentence=True)
 _LADDER = _Mode("a coverage ladder", ("targets", "a depth report"), one_sentence=True, amplicon_files=True)
+_START_CAP = _Mode("a start cap", ("coverage thresholds", "a mean depth", "a proportion", "replicates", "a budget", "ceiling",
+                                   "pair_aware", "template_aware", "targets", "a depth report", "a depth track",
+                                   "a coverage ladder", "stratify", "dedup", "a coverage profile"))
 
 _REGION_FIELDS = ("region_offsets", "region_starts", "region_ends", "region_caps")
 _COUNT_FIELDS = {"ladder_levels": "n_ladder_levels", "pair_stages": "n_pair_stages", "template_stages": "n_template_stages",
@@ -2616,7 +2695,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    replicates=None, replicates_out=None, replicates_report=None, proportion=None, proportion_floor=0,
                    proportional_report=None, fragment_depth=False, fragment_report=None, mean_depth=None,
                    budget_bases=None, mean_depth_targets=None, mean_depth_report=None, thresholds=None,
-                   thresholds_tag="XC", thresholds_report=None):
+                   thresholds_tag="XC", thresholds_report=None, start_cap=None, start_cap_by_strand=False,
+                   start_cap_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2750,9 +2830,22 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     the ThresholdsStats and records_written, then one M<TAB>reads line per coverage of the range.  Needs
     per_reference=True; not together with a mean depth, a proportion, replicates, a budget, ceiling, pair_aware,
     template_aware, targets, report, track, ladder, stratify, dedup, profile, amplicon files or "quasi-mcp-hip-quality"
-    (ValueError).  None: nothing changes"""
+    (ValueError).  None: nothing changes.
+    start_cap=K (BamApiConfig::start_cap, with start_cap_by_strand): every alignment start -- (reference, start), with
+    start_cap_by_strand=True (reference, start, strand) -- offers the solve at most K reads: those of highest MAPQ, then
+    the longest, then the first in the file's pairing order.  One qmcp_hip_solve_start_cap_host call with
+    START_CAP_SHORTFALL on the reads that passed the ingest filters, then find_pairs and the write exactly as the plain
+    flow.  Mate completion only adds reads: every floor the solve reached still holds, but a written start may exceed K
+    through a mate -- the cap is on what the solve may choose from, as GATK's --max-reads-per-alignment-start is.
+    start_cap_report (a path) gets a stat<TAB>value TSV with the StartCapStats (cells_kept, short_positions, ...) and
+    records_written, then one size<TAB>cells line per cell-size bin (START_CAP_REPORT_BINS bins, the last holding the
+    larger sizes).  Needs per_reference=True; not together with any other mode -- thresholds, a mean depth, a
+    proportion, replicates, a budget, ceiling, pair_aware, template_aware, targets, report, track, ladder, stratify,
+    dedup, profile --, amplicon files or "quasi-mcp-hip-quality" (ValueError); start_cap_by_strand or start_cap_report
+    without start_cap is a ValueError too.  None: nothing changes"""
     _need_host()
-    given = {"a mean depth": mean_depth is not None or budget_bases is not None, "a proportion": proportion is not None, "replicates": replicates is not None,
+    given = {"coverage thresholds": thresholds is not None,
+             "a mean depth": mean_depth is not None or budget_bases is not None, "a proportion": proportion is not None, "replicates": replicates is not None,
              "a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
              "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
              "a depth report": bool(report), "a depth track": track is not None, "a coverage ladder": ladder is not None,
@@ -2809,7 +2902,16 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         raise ValueError("mean_depth_targets and mean_depth_report need mean_depth or budget_bases")
     if thresholds is None and thresholds_report is not None:
         raise ValueError("thresholds_report needs thresholds")
-    if thresholds is not None:
+    if start_cap is None and (start_cap_by_strand or start_cap_report is not None):
+        raise ValueError("start_cap_by_strand and start_cap_report need start_cap")
+    if start_cap is not None:
+        if not 1 <= int(start_cap) < 1 << 32:
+            raise ValueError("start_cap must lie in 1 .. 2^32 - 1")
+        need_per_reference(_START_CAP)
+        refuse(_START_CAP)
+        fields.update(start_cap=int(start_cap), start_cap_by_strand=bool(start_cap_by_strand),
+                      start_cap_report=start_cap_report)
+    elif thresholds is not None:
         lo, hi = (1, thresholds) if np.isscalar(thresholds) else thresholds
         lo, hi = int(lo), int(hi)
         if not 1 <= lo <= hi <= THRESHOLDS_COVERAGE_MAX:

@@ -209,6 +209,12 @@ struct qmcp_hip_ctx {
     // the host entry's tag column and duplicate mask
     DevBuf dd_tab, dd_stat, dd_bare, dd_keys[2], dd_vals[2], dd_hist, dd_spine, dd_flag, dd_head, dd_cid, dd_surv, dd_words,
         dd_histo, dd_cs, dd_ce, dd_ci, dd_map, dd_maskc, dd_tags, dd_dupm;
+    // start cap (api/start_cap.inc.hip), all its own, as the dd_* above: tables, range words and counters, the sort's
+    // buffers, the scanned head flags, the cells' first positions, the kept members per cell, the survivor mask and its
+    // scanned word popcounts, the size histogram, the survivors' columns, input indices and keep mask, and the host
+    // entry's group column and capped mask
+    DevBuf sc_tab, sc_stat, sc_bare, sc_keys[2], sc_vals[2], sc_hist, sc_spine, sc_flag, sc_head, sc_cnt, sc_surv, sc_words,
+        sc_histo, sc_cs, sc_ce, sc_ci, sc_map, sc_maskc, sc_groups, sc_capm;
     // coverage profile (api/profile.inc.hip): a batch's need[] (min(cov, cap) per position, top bit = cut position), its
     // regions in global positions (starts | ends | caps), and the call's two counters (capped positions, demand)
     DevBuf pf_need, pf_tab, pf_stat;

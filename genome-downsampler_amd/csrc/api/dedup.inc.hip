@@ -24,36 +24,44 @@ struct DedupSorted {
     uint32_t stride = 1;
 };
 
+// the buffers a sort works in: bare keys, two key buffers (records, or u64 keys), two index columns, histogram, spine
+struct DedupSortBufs {
+    const DevBuf& bare;
+    const DevBuf* keys;
+    const DevBuf* vals;
+    const DevBuf& hist;
+    const DevBuf& spine;
+};
+
 // the stable sort a plan describes, on n elements; build(round, key_bytes, idx, keys_out) queues the round's key kernel
 template <typename Build>
-int dedup_sort(qmcp_hip_ctx* c, uint32_t n, const qmcp::DedupSortPlan& plan, const char* what, Build build,
+int dedup_sort(qmcp_hip_ctx* c, const DedupSortBufs& b, uint32_t n, const qmcp::DedupSortPlan& plan, Build build,
                DedupSorted& out) {
     hipStream_t st = c->stream;
-    uint32_t* hist = c->dd_hist.u32();
-    uint32_t* spine = c->dd_spine.u32();
+    uint32_t* hist = b.hist.u32();
+    uint32_t* spine = b.spine.u32();
     out.form = plan.form;
-    (void)what;
     if (plan.form == qmcp::DEDUP_SORT_REC32) {
-        build(0u, 4u, (const uint32_t*)nullptr, c->dd_bare.p);
+        build(0u, 4u, (const uint32_t*)nullptr, b.bare.p);
         int kin = 0;
-        TRY(radix_sort_records(c, st, c->dd_bare.u32(), n, plan.rounds[0].passes, hist, spine, c->dd_keys,
+        TRY(radix_sort_records(c, st, b.bare.u32(), n, plan.rounds[0].passes, hist, spine, b.keys,
                                {"k_radix_hist_rec(dedup)", "scan_radix_hist(dedup, 3 kernels)", "k_radix_scatter_rec(dedup)"},
                                &kin));
-        out.keys = c->dd_keys[kin].p;
-        out.vals = c->dd_keys[kin].u32() + 1;
+        out.keys = b.keys[kin].p;
+        out.vals = b.keys[kin].u32() + 1;
         out.stride = 2;
         return QMCP_OK;
     }
     // one u64 sort per round; a later round's keys are built in the order the rounds before it left (the value column)
     WideBufs wb;
     for (uint32_t r = 0; r < plan.n_rounds; ++r) {
-        build(r, 8u, wb.v < 0 ? (const uint32_t*)nullptr : c->dd_vals[wb.v].u32(), c->dd_keys[wb.k].p);
-        TRY(radix_sort_wide(c, st, n, plan.rounds[r].passes, hist, spine, c->dd_keys, c->dd_vals,
+        build(r, 8u, wb.v < 0 ? (const uint32_t*)nullptr : b.vals[wb.v].u32(), b.keys[wb.k].p);
+        TRY(radix_sort_wide(c, st, n, plan.rounds[r].passes, hist, spine, b.keys, b.vals,
                             {"k_radix_hist(dedup, u64)", "scan_radix_hist(dedup, 3 kernels)", "k_radix_scatter(dedup, u64)"},
                             &wb));
     }
-    out.keys = c->dd_keys[wb.k].p;
-    out.vals = c->dd_vals[wb.v].u32();
+    out.keys = b.keys[wb.k].p;
+    out.vals = b.vals[wb.v].u32();
     out.stride = 1;
     return QMCP_OK;
 }
@@ -147,7 +155,8 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
     const qmcp::DedupSortPlan rplan = qmcp::plan_dedup_sort(rbits, 4);
     const uint32_t min_span = n_placed ? span_lo : 0u, tag_min = n_placed ? tag_lo : 0u, q_max = n_placed ? q_hi : 0u;
     DedupSorted sorted;
-    TRY(dedup_sort(c, n, rplan, "reads",
+    const DedupSortBufs bufs{c->dd_bare, c->dd_keys, c->dd_vals, c->dd_hist, c->dd_spine};
+    TRY(dedup_sort(c, bufs, n, rplan,
                    [&](uint32_t r, uint32_t key_bytes, const uint32_t* idx, void* keys) {
                        KernelSpan sp(c, "k_dd_read_keys");
                        qmcp::launch_dd_read_keys(st, key_bytes, d_starts, d_ends, d_ids, d_tags, pairs ? nullptr : d_q, idx,
@@ -177,7 +186,7 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
         if (!d_q) pbits[0] = 0;
         const qmcp::DedupSortPlan pplan = qmcp::plan_dedup_sort(pbits, 3);
         const uint32_t score_max = n_placed ? 2u * (q_hi - q_lo) : 0u;
-        TRY(dedup_sort(c, n_units, pplan, "pairs",
+        TRY(dedup_sort(c, bufs, n_units, pplan,
                        [&](uint32_t r, uint32_t key_bytes, const uint32_t* idx, void* keys) {
                            KernelSpan sp(c, "k_dd_pair_keys");
                            qmcp::launch_dd_pair_keys(st, key_bytes, cid, d_q, idx, n_units, n_placed, q_lo, score_max,
@@ -206,7 +215,7 @@ int solve_dedup_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const uint3
     }
     {
         KernelSpan sp(c, "k_dd_family_stats");
-        qmcp::launch_dd_family_stats(st, headpos, flag + n_act, n_act, hist_bins, c->dd_histo.u64(), d_counters);
+        qmcp::launch_dd_family_stats(st, headpos, flag + n_act, n_act, 1u, hist_bins, c->dd_histo.u64(), d_counters);
     }
     // 4. the survivors' count
     {

@@ -15,6 +15,7 @@
 //                     atomicOr, only set bits touched), and every family's first sorted position
 //   k_dd_family_stats over the families: size = next head - head; the size histogram in per-workgroup LDS bins (one
 //                     global atomic per non-empty bin and workgroup), families, duplicate units, the largest family
+//                     (the start cap runs it with its K: the units beyond K per family, the families above K)
 //   k_dd_compact      the stable compaction of the survivors' three columns and their input index
 // Every kernel is a grid-stride loop of 256 threads (four waves of 64) that moves bytes and nothing else.
 
@@ -216,29 +217,34 @@ __global__ __launch_bounds__(256) void k_dd_segments(const uint32_t* __restrict_
     }
 }
 
-// n_fam: the scan's total.  counters (u64, zeroed): families, duplicate units, largest family.  hist (u64, zeroed,
-// hist_bins <= kDedupHistMax words): hist[k - 1] = families of size k, the last bin the sizes >= hist_bins.
+// n_fam: the scan's total.  counters (u64, zeroed): families, the units beyond the first `keep` of their family (keep
+// == 1: the duplicate units), largest family, families larger than `keep`.  hist (u64, zeroed, hist_bins <= kDedupHistMax
+// words): hist[k - 1] = families of size k, the last bin the sizes >= hist_bins.
 __global__ __launch_bounds__(256) void k_dd_family_stats(const uint32_t* __restrict__ headpos,
-                                                         const uint32_t* __restrict__ n_fam, uint32_t hist_bins,
-                                                         unsigned long long* __restrict__ hist,
+                                                         const uint32_t* __restrict__ n_fam, uint32_t keep,
+                                                         uint32_t hist_bins, unsigned long long* __restrict__ hist,
                                                          unsigned long long* __restrict__ counters) {
     extern __shared__ uint32_t s_bins[];
-    __shared__ uint32_t s_f[4], s_d[4], s_l[4];
+    __shared__ uint32_t s_f[4], s_d[4], s_l[4], s_o[4];
     for (uint32_t b = threadIdx.x; b < hist_bins; b += blockDim.x) s_bins[b] = 0;
     __syncthreads();
     const uint32_t F = *n_fam;
-    uint32_t fam = 0, dups = 0, largest = 0;
+    uint32_t fam = 0, dups = 0, largest = 0, over = 0;
     for (uint32_t f = blockIdx.x * blockDim.x + threadIdx.x; f < F; f += gridDim.x * blockDim.x) {
         const uint32_t size = headpos[f + 1] - headpos[f];
         ++fam;
-        dups += size - 1u;
+        dups += size - min(size, keep);
+        over += size > keep ? 1u : 0u;
         largest = max(largest, size);
         if (hist_bins) atomicAdd(&s_bins[min(size, hist_bins) - 1u], 1u);
     }
     fam = wave_sum_u32(fam);
     dups = wave_sum_u32(dups);
     largest = wave_max_u32(largest);
-    if ((threadIdx.x & 63) == 0) { s_f[threadIdx.x >> 6] = fam; s_d[threadIdx.x >> 6] = dups; s_l[threadIdx.x >> 6] = largest; }
+    over = wave_sum_u32(over);
+    if ((threadIdx.x & 63) == 0) {
+        s_f[threadIdx.x >> 6] = fam; s_d[threadIdx.x >> 6] = dups; s_l[threadIdx.x >> 6] = largest; s_o[threadIdx.x >> 6] = over;
+    }
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < hist_bins; b += blockDim.x)
         if (s_bins[b]) atomicAdd(&hist[b], (unsigned long long)s_bins[b]);
@@ -246,6 +252,8 @@ __global__ __launch_bounds__(256) void k_dd_family_stats(const uint32_t* __restr
         fam = s_f[0] + s_f[1] + s_f[2] + s_f[3];
         dups = s_d[0] + s_d[1] + s_d[2] + s_d[3];
         largest = max(max(s_l[0], s_l[1]), max(s_l[2], s_l[3]));
+        over = s_o[0] + s_o[1] + s_o[2] + s_o[3];
+        if (over) atomicAdd(&counters[3], (unsigned long long)over);
         if (fam) atomicAdd(&counters[0], (unsigned long long)fam);
         if (dups) atomicAdd(&counters[1], (unsigned long long)dups);
         if (largest) atomicMax(&counters[2], (unsigned long long)largest);
@@ -344,11 +352,11 @@ void launch_dd_segments(hipStream_t st, bool pairs, const uint32_t* vals, uint32
                            headpos);
 }
 
-void launch_dd_family_stats(hipStream_t st, const uint32_t* headpos, const uint32_t* n_fam, uint32_t n_act,
+void launch_dd_family_stats(hipStream_t st, const uint32_t* headpos, const uint32_t* n_fam, uint32_t n_act, uint32_t keep,
                             uint32_t hist_bins, uint64_t* hist, uint64_t* counters) {
     if (n_act == 0) return;
     hipLaunchKernelGGL(k_dd_family_stats, dim3(grid_for(n_act, 256, 256)), dim3(256), (size_t)hist_bins * sizeof(uint32_t),
-                       st, headpos, n_fam, hist_bins, (unsigned long long*)hist, (unsigned long long*)counters);
+                       st, headpos, n_fam, keep, hist_bins, (unsigned long long*)hist, (unsigned long long*)counters);
 }
 
 void launch_dd_compact(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,

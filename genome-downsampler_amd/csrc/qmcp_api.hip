@@ -97,6 +97,9 @@
 //                       budget's flow with the histogram restricted to the regions and a weighted count per probe
 //   thresholds          (by_contig) every read's smallest keeping coverage in a range: one grouping, one whole solve per
 //                       coverage folded into the thresholds by thresholds_plan.h's word logic, the counts per coverage
+//   start_cap           (dedup, depth_report) every (contig, start, group) cell reduced to its best K reads before the
+//                       by-contig solve; capped mask, cell-size histogram, the cells the kept set uses, and the shortfall
+//                       against the demand of all placed reads through the depth report's pass
 //   replicates          (by_contig, depth_report) one read set split into disjoint downsamples: the batch loop at the
 //                       first coverage, every further replicate solved on the reads still free, replicate-major over the
 //                       one grouping's batches
@@ -130,3 +133,4 @@
 #include "api/mean_depth.inc.hip"
 #include "api/thresholds.inc.hip"
 #include "api/replicates.inc.hip"
+#include "api/start_cap.inc.hip"

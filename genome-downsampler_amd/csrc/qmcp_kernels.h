@@ -395,7 +395,8 @@ void launch_track_emit(hipStream_t st, const uint64_t* ev, uint32_t positions, c
 // head flags over the n_act active records of a sorted order (form: DedupSortForm; compared on the keys above low_bits, or
 // on the columns / cell ids after a sort field by field), the cell ids scattered to input order, survivor and duplicate
 // bits + every family's first position from the scanned flags E, the family statistics (counters: families, duplicate
-// units, largest; hist_bins <= dedup_hist_max()), and the stable compaction of the survivors
+// units, largest, families above `keep`; keep == 1 for dedup: the units beyond the first `keep` of a family are its
+// duplicates; hist_bins <= dedup_hist_max()), and the stable compaction of the survivors
 uint32_t dedup_hist_max();
 void launch_dd_range(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
                      const uint32_t* tags, const uint32_t* q, uint32_t n, const uint32_t* lengths, uint32_t n_contigs,
@@ -414,11 +415,30 @@ void launch_dd_cell_ids(hipStream_t st, const uint32_t* vals, uint32_t stride, c
                         uint32_t n, uint32_t idu, uint32_t* cid);
 void launch_dd_segments(hipStream_t st, bool pairs, const uint32_t* vals, uint32_t stride, const uint32_t* E,
                         uint32_t n_act, uint64_t* surv, uint64_t* dup, uint32_t* headpos);
-void launch_dd_family_stats(hipStream_t st, const uint32_t* headpos, const uint32_t* n_fam, uint32_t n_act,
+void launch_dd_family_stats(hipStream_t st, const uint32_t* headpos, const uint32_t* n_fam, uint32_t n_act, uint32_t keep,
                             uint32_t hist_bins, uint64_t* hist, uint64_t* counters);
 void launch_dd_compact(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
                        const uint64_t* surv, const uint32_t* word_base, uint32_t n, uint32_t* starts_c, uint32_t* ends_c,
                        uint32_t* ids_c, uint32_t* orig);
+
+// start cap (kernels/start_cap.inc.hip; api/start_cap.inc.hip drives them; the range pass, the family statistics and the
+// compaction are dedup's): a round's keys of the reads from {span_max - span, prio_max - prio, group - group_min, gstart},
+// head flags over the n_act placed records of a sorted order (on the keys above low_bits, or on contig, start and group
+// after a sort field by field), every cell's first position from the scanned flags E (headpos: cells + 1 entries),
+// survivor bits below rank `cap` and capped bits from there on (capped may be NULL), and the kept members per cell under
+// the final mask (cnt: one zeroed word per cell; counters, zeroed: cells with a kept member, the largest count)
+void launch_sc_keys(hipStream_t st, uint32_t key_bytes, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                    const uint32_t* groups, const uint32_t* prio, const uint32_t* idx, const uint64_t* poff, uint64_t ltot,
+                    uint32_t n, uint32_t span_max, uint32_t prio_max, uint32_t group_min, const DedupPack& pack,
+                    void* keys);
+void launch_sc_cell_flags(hipStream_t st, uint32_t form, const void* sorted, const uint32_t* svals, uint32_t low_bits,
+                          uint32_t n_act, const uint32_t* starts, const uint32_t* ids, const uint32_t* groups,
+                          uint32_t* flag);
+void launch_sc_heads(hipStream_t st, const uint32_t* E, uint32_t n_act, uint32_t* headpos);
+void launch_sc_rank(hipStream_t st, const uint32_t* vals, uint32_t stride, const uint32_t* E, const uint32_t* headpos,
+                    uint32_t n_act, uint32_t cap, uint64_t* surv, uint64_t* capped);
+void launch_sc_kept_cells(hipStream_t st, const uint32_t* vals, uint32_t stride, const uint32_t* E, uint32_t n_act,
+                          const uint64_t* mask, uint32_t* cnt, uint64_t* counters);
 
 // pair-aware downsampling (kernels/pairs.inc.hip; api/pairs.inc.hip drives them), one batch of the by-contig grouping and
 // one stage after the first: the input-order mask of the kept set S as bits in the batch's grouped order (in_bits) and

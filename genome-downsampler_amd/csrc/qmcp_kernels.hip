@@ -49,6 +49,8 @@
 //                            keys, and the per-stratum rows as a segmented reduction over the grouped records
 //   dedup                    duplicate families collapsed before the solve: ranges and validation, composite keys, head
 //                            flags, cell ids, survivor / duplicate bits, family statistics, compaction of the survivors
+//   start_cap                at most K reads per (contig, start, group) cell before the solve: composite keys, every
+//                            cell's first position, survivor / capped bits by rank in cell, the kept members per cell
 //   profile                  a cap that varies along the genome: need(p) = min(cov(p), cap(p)) per position with its cut
 //                            flag, and the cut-point scan over it
 //   pairs                    pair-aware downsampling: the kept set's bits in a batch's grouped order and their complement,
@@ -115,6 +117,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/depth_track.inc.hip"
 #include "kernels/stratified.inc.hip"
 #include "kernels/dedup.inc.hip"
+#include "kernels/start_cap.inc.hip"
 #include "kernels/profile.inc.hip"
 #include "kernels/pairs.inc.hip"
 #include "kernels/templates.inc.hip"

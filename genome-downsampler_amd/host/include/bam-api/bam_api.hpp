@@ -79,6 +79,15 @@ struct BamApiConfig {
     // the reads' strata column for it.  Needs per_reference; not together with targets, a depth report, a coverage
     // ladder, stratify_by or amplicon files (std::invalid_argument otherwise).  false: nothing changes.
     bool dedup = false;
+    // Start cap: every start site -- (reference, start), with start_cap_by_strand (reference, start, strand) -- offers the
+    // solve at most start_cap reads: those of highest MAPQ, then the longest, then the first in the file's pairing order
+    // (QuasiMcpHipSolver::solve_start_cap / qmcp_hip_solve_start_cap_host).  find_pairs then completes mates as always: it
+    // only adds reads, so every floor the solve reached still holds, but a written start may exceed the cap through a
+    // mate -- the cap is on what the solve may choose from.  With start_cap_by_strand the ingest keeps every record's
+    // reverse-strand bit as the reads' strata column, as it does for dedup.  Needs per_reference; not together with any
+    // other mode or with amplicon files (std::invalid_argument otherwise).  0: nothing changes.
+    std::uint32_t start_cap = 0;
+    bool start_cap_by_strand = false;
     // Pair-aware downsampling: the solve runs in stages that credit the coverage of the mates already kept
     // (QuasiMcpHipSolver::solve_pairs / qmcp_hip_solve_pairs_host), so the output -- whole pairs, written without a
     // further find_pairs -- stays near max_coverage instead of near twice that.  pair_stages: the stages' rising targets,
@@ -200,6 +209,9 @@ class BamApi {
     Stratify stratify_by() const { return stratify_by_; }
     // BamApiConfig::dedup (the reads' strata column then holds the reverse-strand bit)
     bool dedup() const { return dedup_; }
+    // BamApiConfig::start_cap (0: none) and start_cap_by_strand (the reads' strata column then holds the strand bit)
+    std::uint32_t start_cap() const { return start_cap_; }
+    bool start_cap_by_strand() const { return start_cap_by_strand_; }
     // BamApiConfig::pair_aware and pair_stages (empty: the default schedule)
     bool pair_aware() const { return pair_aware_; }
     const std::vector<std::uint32_t>& pair_stages() const { return pair_stages_; }
@@ -269,6 +281,8 @@ class BamApi {
     std::vector<std::uint32_t> coverage_ladder_;
     Stratify stratify_by_ = Stratify::NONE;
     bool dedup_ = false;
+    std::uint32_t start_cap_ = 0;
+    bool start_cap_by_strand_ = false;
     bool pair_aware_ = false;
     bool ceiling_ = false;
     std::optional<std::uint64_t> budget_reads_;

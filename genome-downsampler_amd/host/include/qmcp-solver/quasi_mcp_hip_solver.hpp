@@ -95,6 +95,14 @@ class QuasiMcpHipSolver : public Solver {
     std::unique_ptr<Solution> solve_dedup(std::uint32_t required_cover, bam_api::BamApi& bam_api, std::uint32_t hist_bins);
     const qmcp_hip_dedup_stats& last_dedup_stats() const { return dstats_; }
     const std::vector<std::uint64_t>& last_dedup_hist() const { return dedup_hist_; }
+    // Start cap for the reads of a BamApi built with BamApiConfig::start_cap: qmcp_hip_solve_start_cap_host with
+    // QMCP_START_CAP_SHORTFALL, group = the reads' strand bit under start_cap_by_strand (else one group), priority = MAPQ;
+    // hist_bins bins of cell sizes.  The Solution is the solve's own kept set: find_pairs completes it.
+    // std::invalid_argument for reads without contig ids (or without the strand column it asks for); std::terminate on a
+    // device failure, like solve()
+    std::unique_ptr<Solution> solve_start_cap(std::uint32_t required_cover, bam_api::BamApi& bam_api, std::uint32_t hist_bins);
+    const qmcp_hip_start_cap_stats& last_start_cap_stats() const { return scstats_; }
+    const std::vector<std::uint64_t>& last_start_cap_hist() const { return start_cap_hist_; }
     // Coverage profile for the reads of a per-reference BamApi: qmcp_hip_solve_profile_host with the regions in CSR form
     // per reference (offsets: one more entry than the file has references; inclusive bounds, disjoint per reference)
     // and required_cover as the default cap.  std::invalid_argument for reads without contig ids or a table of other
@@ -200,6 +208,8 @@ class QuasiMcpHipSolver : public Solver {
     std::vector<std::uint32_t> stratum_caps_;
     std::vector<qmcp_hip_stratum_row> stratum_rows_;
     qmcp_hip_dedup_stats dstats_{};
+    qmcp_hip_start_cap_stats scstats_{};
+    std::vector<std::uint64_t> start_cap_hist_;
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_ceiling_stats clstats_{};

@@ -109,6 +109,14 @@ typedef struct qmcp_host_downsample_request {
     int32_t has_mean_depth;
     int32_t has_replicates;
     int32_t has_thresholds;
+    /* start cap (start_cap, start_cap_by_strand): start_cap != 0 asks for it -- every (reference, start) site, with
+     * start_cap_by_strand every (reference, start, strand), offers the solve at most start_cap reads (highest MAPQ, then
+     * longest, then first); start_cap_report: stat<TAB>value lines, then one size<TAB>cells line per bin of the cell-size
+     * histogram.  start_cap_by_strand or start_cap_report alone are refused.  (The request ends with the proportion
+     * fields: these three stand in front of them.) */
+    int32_t start_cap_by_strand;
+    uint32_t start_cap;
+    const char* start_cap_report;
     /* proportional downsampling (proportion): has_proportion != 0 asks for it -- every position keeps
      * ceil(cov * proportion_num / proportion_den) of its depth, positions at or below proportion_floor whole,
      * max_coverage the hard upper end; proportional_report: stat<TAB>value lines */

@@ -70,6 +70,33 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     if (amplicons_by_reference_ && !per_reference_)
         throw std::invalid_argument("amplicons_by_reference needs per_reference: amplicons are matched to the "
                                     "references a per-reference ingest keeps");
+    if (config.start_cap) {
+        const auto no = [](const char* what) {
+            throw std::invalid_argument(std::string("a start cap does not go together with ") + what);
+        };
+        if (!per_reference_)
+            throw std::invalid_argument("a start cap needs per_reference: a start site includes its reference");
+        if (config.thresholds_hi.has_value()) no("coverage thresholds");
+        if (config.mean_depth.has_value() || config.budget_bases.has_value()) no("a mean depth");
+        if (config.proportion.has_value()) no("a proportion");
+        if (config.replicates.has_value()) no("replicates");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value()) no("a budget");
+        if (config.ceiling) no("ceiling");
+        if (config.pair_aware) no("pair_aware");
+        if (config.template_aware) no("template_aware");
+        if (!config.targets_filepath.empty()) no("targets");
+        if (!config.depth_report_filepath.empty()) no("a depth report");
+        if (!config.depth_track_filepath.empty()) no("a depth track");
+        if (!config.coverage_ladder.empty()) no("a coverage ladder");
+        if (config.stratify_by != Stratify::NONE) no("stratify_by");
+        if (config.dedup) no("dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("a start cap does not take amplicon files");
+        start_cap_ = config.start_cap;
+        start_cap_by_strand_ = config.start_cap_by_strand;
+    } else if (config.start_cap_by_strand) {
+        throw std::invalid_argument("start_cap_by_strand needs start_cap");
+    }
     if (!config.coverage_ladder.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a coverage ladder needs per_reference: its levels are solved one reference at "
@@ -406,7 +433,8 @@ void BamApi::read_bam_into(PairedReads& reads) {
     f.amplicon_behaviour = amplicon_behaviour_;
     f.amplicons = &amplicon_set_;
     f.per_reference = per_reference_;
-    f.stratify = dedup_ ? Stratify::STRAND : stratify_by_;  // (dedup: the strand bit is the duplicate cell's tag)
+    // (dedup: the strand bit is the duplicate cell's tag; a start cap by strand: it is the start site's group)
+    f.stratify = dedup_ || start_cap_by_strand_ ? Stratify::STRAND : stratify_by_;
     if (amplicons_by_reference_) f.reference_amplicons = &reference_amplicon_set_;
     std::string err;
     if (!read_bam(input_filepath_, f, reads, filtered_out_reads_, nullptr, &err)) {

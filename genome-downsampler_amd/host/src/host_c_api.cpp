@@ -163,6 +163,8 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
     if (q.ladder_levels) cfg.coverage_ladder.assign(q.ladder_levels, q.ladder_levels + q.n_ladder_levels);
     if (given(q.stratify)) cfg.stratify_by = stratify_from_name(q.stratify);
     cfg.dedup = q.dedup != 0;
+    cfg.start_cap = q.start_cap;
+    cfg.start_cap_by_strand = q.start_cap_by_strand != 0;
     cfg.pair_aware = q.pair_aware != 0;
     if (q.pair_stages) cfg.pair_stages.assign(q.pair_stages, q.pair_stages + q.n_pair_stages);
     cfg.template_aware = q.template_aware != 0;
@@ -192,8 +194,9 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
 
 // Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
 // amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
-enum class Mode { THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+enum class Mode { START_CAP, THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
 Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (cfg.start_cap || cfg.start_cap_by_strand || given(q.start_cap_report)) return Mode::START_CAP;
     if (cfg.thresholds_hi || given(q.thresholds_tag) || given(q.thresholds_report)) return Mode::THRESHOLDS;
     if (cfg.mean_depth || cfg.budget_bases || given(q.mean_depth_targets) || given(q.mean_depth_report))
         return Mode::MEAN_DEPTH;
@@ -216,6 +219,7 @@ struct ModeWords {
 };
 ModeWords words_of(Mode mode) {
     switch (mode) {
+        case Mode::START_CAP: return {"a start cap does not", "start cap"};
         case Mode::THRESHOLDS: return {"coverage thresholds do not", "coverage thresholds"};
         case Mode::MEAN_DEPTH: return {"mean-depth downsampling does not", "mean-depth downsampling"};
         case Mode::PROPORTIONAL: return {"proportional downsampling does not", "proportional downsampling"};
@@ -246,6 +250,8 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
         refuse("budget downsampling needs budget_reads or budget_fraction");
     if (mode == Mode::MEAN_DEPTH && !cfg.mean_depth && !cfg.budget_bases)
         refuse("mean-depth downsampling needs mean_depth or budget_bases");
+    if (mode == Mode::START_CAP && !cfg.start_cap) refuse("start_cap_by_strand and start_cap_report need start_cap");
+    if (mode == Mode::START_CAP && q.has_regions) refuse("a start cap does not go together with a coverage profile");
     if (mode == Mode::THRESHOLDS && !cfg.thresholds_hi) refuse("thresholds_tag and thresholds_report need thresholds");
     if (mode == Mode::PROPORTIONAL && !cfg.proportion) refuse("proportional downsampling needs a proportion");
     if (mode == Mode::LADDER && cfg.coverage_ladder.empty()) refuse("a coverage ladder needs at least one level");
@@ -316,6 +322,27 @@ bool write_dedup_report(const char* path, const qmcp::QuasiMcpHipSolver& hip) {
     std::fprintf(f, "#size\tfamilies\n");
     for (std::uint32_t b = 0; b < kDedupBins; ++b)
         std::fprintf(f, "%u\t%llu\n", b + 1, (unsigned long long)hip.last_dedup_hist()[b]);
+    return std::fclose(f) == 0;
+}
+
+// the statistics and the records written, then one size<TAB>cells line per bin of the cell-size histogram
+constexpr std::uint32_t kStartCapBins = 64;
+bool write_start_cap_report(const char* path, const qmcp::QuasiMcpHipSolver& hip, std::int64_t written) {
+    const qmcp_hip_start_cap_stats& cs = hip.last_start_cap_stats();
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#stat\tvalue\n");
+    std::fprintf(f, "cap\t%u\nreads_placed\t%llu\ncells\t%llu\ncells_over_cap\t%llu\nreads_capped\t%llu\n"
+                    "largest_cell\t%llu\nreads_survived\t%llu\ncells_kept\t%llu\nlargest_kept_cell\t%llu\n"
+                    "short_positions\t%llu\nshort_bases\t%llu\nrecords_written\t%lld\n",
+                 cs.cap, (unsigned long long)cs.reads_placed, (unsigned long long)cs.cells,
+                 (unsigned long long)cs.cells_over_cap, (unsigned long long)cs.reads_capped,
+                 (unsigned long long)cs.largest_cell, (unsigned long long)cs.reads_survived,
+                 (unsigned long long)cs.cells_kept, (unsigned long long)cs.largest_kept_cell,
+                 (unsigned long long)cs.short_positions, (unsigned long long)cs.short_bases, (long long)written);
+    std::fprintf(f, "#size\tcells\n");
+    for (std::uint32_t b = 0; b < kStartCapBins; ++b)
+        std::fprintf(f, "%u\t%llu\n", b + 1, (unsigned long long)hip.last_start_cap_hist()[b]);
     return std::fclose(f) == 0;
 }
 
@@ -502,6 +529,7 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         case Mode::PLAIN:
         case Mode::STRATIFIED: write_reads(*solver->solve(M, api), true, q.out_path); break;
         case Mode::DEDUP: write_reads(*hip->solve_dedup(M, api, kDedupBins), true, q.out_path); break;
+        case Mode::START_CAP: write_reads(*hip->solve_start_cap(M, api, kStartCapBins), true, q.out_path); break;
         case Mode::PROFILE: write_reads(*hip->solve_profile(M, api, offsets, starts, ends, caps), true, q.out_path); break;
         case Mode::PROPORTIONAL: write_reads(*hip->solve_proportional(M, api), true, q.out_path); break;
         case Mode::PAIRS: write_reads(*hip->solve_pairs(M, api), false, q.out_path); break;
@@ -554,6 +582,8 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
     if (mode == Mode::STRATIFIED && given(q.strata_report))
         reported = write_strata_report(q.strata_report, api.get_paired_reads_soa(), *hip);
     if (mode == Mode::DEDUP && given(q.dedup_report)) reported = write_dedup_report(q.dedup_report, *hip);
+    if (mode == Mode::START_CAP && given(q.start_cap_report))
+        reported = write_start_cap_report(q.start_cap_report, *hip, written[0]);
     if (mode == Mode::CEILING && given(q.ceiling_report))
         reported = write_ceiling_report(q.ceiling_report, hip->last_ceiling_stats(), written[0]);
     if (mode == Mode::TEMPLATES && given(q.fragment_report))

@@ -218,6 +218,45 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_dedup(std::uint32_t required_
     return kept;
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_start_cap(std::uint32_t required_cover, bam_api::BamApi& bam_api,
+                                                             std::uint32_t hist_bins) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    const bool by_strand = bam_api.start_cap_by_strand();
+    if (!bam_api.start_cap() || !reads.has_contig_ids() || reads.contig_ids.size() != n ||
+        (by_strand && reads.strata.size() != n))
+        throw std::invalid_argument("a start cap needs a BamApi built with BamApiConfig::start_cap");
+    if (reads.qualities.size() != n) throw std::invalid_argument("reads without one quality each");
+    if (ctx_ == nullptr) {
+        const int rc = qmcp_hip_create(device_, &ctx_);
+        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
+    }
+    std::vector<std::uint32_t> starts(n), ends(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
+        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
+        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
+        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
+    }
+    static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
+    start_cap_hist_.assign(hist_bins, 0);
+    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    int rc = qmcp_hip_solve_start_cap_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(),
+                                           by_strand ? reads.strata.data() : nullptr, reads.qualities.data(), n,
+                                           reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
+                                           required_cover, bam_api.start_cap(), QMCP_START_CAP_SHORTFALL, mask.data(),
+                                           nullptr, hist_bins ? start_cap_hist_.data() : nullptr, hist_bins, &stats_,
+                                           &scstats_);
+    if (rc != QMCP_OK) die("qmcp_hip_solve_start_cap_host", rc);
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) {
+        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
+        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
+    }
+    return expand_kept(n, t0);
+}
+
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t required_cover, bam_api::BamApi& bam_api,
                                                            const std::vector<std::uint32_t>& offsets,
                                                            const std::vector<std::uint32_t>& region_starts,

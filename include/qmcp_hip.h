@@ -1477,6 +1477,82 @@ int qmcp_hip_solve_proportional_device(qmcp_hip_ctx* ctx,
                                        uint64_t* d_keep_mask_out, void* hip_stream, qmcp_hip_stats* stats,
                                        qmcp_hip_proportional_stats* pstats);
 
+/* Start cap: at most K kept reads per alignment start.  The canonical selection fills a deficit from the reads with the
+ * furthest end, which on deep one-length data are the reads that start where the deficit opens: the kept reads pile up
+ * on a few start positions.  Here every start site may offer the solve at most K reads (GATK's
+ * --max-reads-per-alignment-start, MACS' --keep-dup k).  starts, ends, contig_ids, n_reads, contig_lengths / n_contigs,
+ * max_coverage, keep_mask_out, stats, limits (n_reads <= 2^31, n_contigs <= 2^24) and errors are those of
+ * qmcp_hip_solve_by_contig_host / _device.  In addition:
+ *   cap         K >= 1; 0 fails with QMCP_EINVAL.
+ *   groups      one uint32 per read, any value (strand, sample); NULL: one group.  Any range of values is fine.
+ *   priorities  one uint32 per read, higher is better (MAPQ); NULL: all equal.  A range (max - min over the placed
+ *               reads) above 65535 fails with QMCP_ERANGE before anything is written, as dedup's quality range does.
+ *   flags       QMCP_START_CAP_SHORTFALL asks for short_positions / short_bases; unknown bits fail with QMCP_EINVAL.
+ *   capped_mask_out  may be NULL; ceil(n_reads / 64) words, fully overwritten.
+ *   hist_out, hist_bins  may be NULL / 0; hist_bins uint64 words in host memory (both entries), at most 4096 bins
+ *               (QMCP_ERANGE beyond).
+ *   cstats      may be NULL.
+ * CELL: the cell of a placed read is (contig, start, group).  Unplaced reads belong to no cell and are never kept.
+ * ORDER inside a cell: priority descending, then span (end - start) descending, then input index ascending.  Longest
+ * first is deliberate: it is the read the canonical rule would prefer, and it makes the survivors independent of the
+ * input order up to index ties.
+ * SURVIVORS: the first min(K, size) reads of every cell in that order.  The other placed reads are CAPPED.
+ * RESULT: keep_mask_out is the mask qmcp_hip_solve_by_contig_host returns for the survivors in input order at
+ * max_coverage, bit for bit, mapped back to input positions; every other bit is clear.  Bit i of capped_mask_out is set
+ * iff read i is capped, so keep & capped == 0 always.  hist_out[k - 1] is the number of cells of size k for k <
+ * hist_bins, the last bin holds the sizes >= hist_bins.
+ * PROMISES: (1) at most K kept reads per cell.  (2) The kept depth is >= min(cov of the survivors, max_coverage)
+ * everywhere, with minimum cardinality for that demand.  (3) If no cell is larger than K the keep mask is
+ * qmcp_hip_solve_by_contig_host's bit for bit.  (4) With one span length in the call, groups == NULL and K == 1, the keep
+ * mask and the capped mask are qmcp_hip_solve_dedup_host's read mode (tags NULL, the priorities as qualities) keep mask
+ * and duplicate mask bit for bit.  (5) The same input gives the same masks, run to run.
+ * NOT PROMISED: kept depth >= min(cov, max_coverage) of ALL placed reads; that is what the shortfall reports.  With
+ * QMCP_START_CAP_SHORTFALL short_positions counts the positions where the kept depth is below min(cov of all placed
+ * reads, max_coverage) and short_bases sums the deficit there; they are counted on the device by the depth report's pass
+ * (its limit applies: n_reads < 2^31, QMCP_ERANGE otherwise).
+ * VALIDATION: every read is validated as the by-contig entries do -- the capped reads too -- before anything is written:
+ * a bad contig id gives QMCP_EINVAL, a bad read QMCP_EREAD, and no output buffer has been touched.
+ * HOW: one pass validates and takes the ranges of group, priority and span; the widths of the key gstart | group -
+ * group_min | prio_max - prio | span_max - span come from those ranges (a NULL column and one span cost nothing); dedup's
+ * stable LSD radix sorts {key, index} as 32-bit records, as split 64-bit keys, or -- beyond 64 bits -- field by field.
+ * A cell then is a run of the sorted order with its best read first; rank = position - the cell's first position, a
+ * survivor below K, capped from K on.  The survivors are compacted in input order, solved, and the mask expanded; one more
+ * pass over the sorted records counts the kept reads per cell from the final mask.
+ * stats (may be NULL) are the inner solve's: n_reads counts the survivors.
+ * The pass is blocking (no _begin / _end form).  The device entry takes the columns and both masks in device memory
+ * (contig_lengths, hist_out and the stats stay on the host), columns at any 4-byte alignment, and is ordered after
+ * `hip_stream` (or NULL) as qmcp_hip_solve_device is.  The host entry leaves the keep mask in the context. */
+#define QMCP_START_CAP_SHORTFALL 1u
+typedef struct qmcp_hip_start_cap_stats {
+    uint64_t reads_placed;       /* reads with a contig                                                               */
+    uint64_t cells;              /* distinct (contig, start, group) among them                                        */
+    uint64_t cells_over_cap;     /* cells with more than K reads                                                      */
+    uint64_t reads_capped;       /* reads_placed - reads_survived                                                     */
+    uint64_t largest_cell;       /* reads of the largest cell                                                         */
+    uint64_t reads_survived;     /* reads handed to the inner solve                                                   */
+    uint64_t cells_kept;         /* cells with at least one kept read: the diversity of the kept set                  */
+    uint64_t largest_kept_cell;  /* kept reads of the cell with the most (<= K), counted from the final mask          */
+    uint64_t short_positions;    /* QMCP_START_CAP_SHORTFALL: positions with kept < min(cov of all placed reads, M)    */
+    uint64_t short_bases;        /* QMCP_START_CAP_SHORTFALL: the deficit summed over them; both 0 without the flag   */
+    uint32_t key_bits;           /* width of the key the reads were sorted by                                         */
+    uint32_t sort_passes;        /* 8-bit LSD passes                                                                  */
+    uint32_t cap;                /* K as given                                                                        */
+    float ms_cap;                /* device time of everything except the inner solve                                  */
+} qmcp_hip_start_cap_stats;
+int qmcp_hip_solve_start_cap_host(qmcp_hip_ctx* ctx,
+                                  const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                  const uint32_t* groups, const uint32_t* priorities, uint64_t n_reads,
+                                  const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage, uint32_t cap,
+                                  uint32_t flags, uint64_t* keep_mask_out, uint64_t* capped_mask_out, uint64_t* hist_out,
+                                  uint32_t hist_bins, qmcp_hip_stats* stats, qmcp_hip_start_cap_stats* cstats);
+int qmcp_hip_solve_start_cap_device(qmcp_hip_ctx* ctx,
+                                    const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                    const uint32_t* d_groups, const uint32_t* d_priorities, uint64_t n_reads,
+                                    const uint32_t* contig_lengths, uint32_t n_contigs, uint32_t max_coverage,
+                                    uint32_t cap, uint32_t flags, uint64_t* d_keep_mask_out, uint64_t* d_capped_mask_out,
+                                    uint64_t* hist_out, uint32_t hist_bins, void* hip_stream, qmcp_hip_stats* stats,
+                                    qmcp_hip_start_cap_stats* cstats);
+
 #ifdef __cplusplus
 }
 #endif
