@@ -5,6 +5,7 @@
 #   make harness    -> tests/cpp/coverage_harness             (CoverageTester restatement)
 #   make pm_stage_driver -> tests/cpp/pm_stage_driver         (the pass-major kernels one stage at a time)
 #   make rm_stage_driver -> tests/cpp/rm_stage_driver         (the range-major kernels one stage at a time)
+#   make nu_stage_driver -> tests/cpp/nu_stage_driver         (the near-uniform route's kernels one stage at a time)
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
 CC       ?= gcc
@@ -18,8 +19,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
 CXXFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -I$(HOST)/include -DHIP_ENABLED
 CFLAGS   := -O3 -std=c11 -fPIC -Wall
 
-.PHONY: all lib oracle harness pm_stage_driver rm_stage_driver clean
-all: lib oracle harness pm_stage_driver rm_stage_driver
+.PHONY: all lib oracle harness pm_stage_driver rm_stage_driver nu_stage_driver clean
+all: lib oracle harness pm_stage_driver rm_stage_driver nu_stage_driver
 
 lib: $(LIBDIR)/libqmcp_hip.so $(LIBDIR)/libqmcp_host.so
 
@@ -58,5 +59,9 @@ rm_stage_driver: tests/cpp/rm_stage_driver
 tests/cpp/rm_stage_driver: tests/cpp/rm_stage_driver.hip tests/cpp/stage_driver_common.h $(CSRC)/qmcp_kernels.h $(CSRC)/solve_words.h $(LIBDIR)/libqmcp_hip.so
 	$(HIPCC) $(HIPFLAGS) $< -L$(LIBDIR) -lqmcp_hip -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -o $@
 
+nu_stage_driver: tests/cpp/nu_stage_driver
+tests/cpp/nu_stage_driver: tests/cpp/nu_stage_driver.hip tests/cpp/stage_driver_common.h $(CSRC)/qmcp_kernels.h $(CSRC)/solve_words.h $(CSRC)/sweep_plan.h $(LIBDIR)/libqmcp_hip.so
+	$(HIPCC) $(HIPFLAGS) $< -L$(LIBDIR) -lqmcp_hip -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -o $@
+
 clean:
-	rm -rf $(LIBDIR) oracle/libqmcp_oracle.so tests/cpp/coverage_harness tests/cpp/pm_stage_driver tests/cpp/rm_stage_driver
+	rm -rf $(LIBDIR) oracle/libqmcp_oracle.so tests/cpp/coverage_harness tests/cpp/pm_stage_driver tests/cpp/rm_stage_driver tests/cpp/nu_stage_driver

@@ -658,6 +658,7 @@ static NuExc nu_exc_view(uint32_t* exc, uint32_t cap, uint32_t n_dense, const ui
 }
 uint32_t* nu_exc_counts(uint32_t* exc, uint32_t cap) { return exc + 6 * (size_t)cap; }
 size_t nu_exc_bytes(uint32_t cap) { return ((size_t)cap * 7 + 2 * (cap / kNuGroup + 4) + 8) * sizeof(uint32_t); }
+uint32_t nu_overflow_slots() { return kNuOverflow; }
 void launch_nu_count_span(hipStream_t st, const uint32_t* starts, const uint32_t* ends, uint32_t n, uint32_t span, uint32_t* out) {
     hipLaunchKernelGGL(k_nu_count_span, dim3(grid_for(n, 256)), dim3(256), 0, st, starts, ends, n, span, out);
 }

@@ -250,6 +250,7 @@ void launch_pm_walk(hipStream_t st, const uint16_t* keys16, const uint16_t* idx1
 // near-uniform route (kernels/near_uniform.inc.hip): one dominant span, a few shorter reads as listed exceptions
 void launch_span_mode_share(hipStream_t st, const uint32_t* starts, const uint32_t* ends, uint32_t n, uint32_t* out /* 3 words: sampled, in the fullest bin, its span */);
 size_t nu_exc_bytes(uint32_t cap);
+uint32_t nu_overflow_slots();  // the overflow region: the list's last slots
 uint32_t* nu_exc_counts(uint32_t* exc, uint32_t cap);  // the groups' counts inside the list's buffer  // the exception list: start, end, index (k_pm_prepare_sort), selection time, event key, group counts
 void launch_nu_count_span(hipStream_t st, const uint32_t* starts, const uint32_t* ends, uint32_t n, uint32_t span, uint32_t* out);
 void launch_nu_setup(hipStream_t st, uint32_t* exc, uint32_t cap, uint32_t n_exc, const uint32_t* n_over /* the producer's stats[6] */,
