@@ -24,7 +24,7 @@ all: lib oracle harness pm_stage_driver rm_stage_driver nu_stage_driver
 
 lib: $(LIBDIR)/libqmcp_hip.so $(LIBDIR)/libqmcp_host.so
 
-$(LIBDIR)/qmcp_kernels.o: $(CSRC)/qmcp_kernels.hip $(CSRC)/qmcp_kernels.h $(CSRC)/sweep_plan.h $(CSRC)/target_table.h $(CSRC)/dedup_plan.h $(CSRC)/pm_grid_plan.h $(CSRC)/thresholds_plan.h include/qmcp_hip.h $(wildcard $(CSRC)/kernels/*.inc.hip)
+$(LIBDIR)/qmcp_kernels.o: $(CSRC)/qmcp_kernels.hip $(CSRC)/qmcp_kernels.h $(CSRC)/sweep_plan.h $(CSRC)/target_table.h $(CSRC)/dedup_plan.h $(CSRC)/pm_grid_plan.h $(CSRC)/pm_div.h $(CSRC)/thresholds_plan.h include/qmcp_hip.h $(wildcard $(CSRC)/kernels/*.inc.hip)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

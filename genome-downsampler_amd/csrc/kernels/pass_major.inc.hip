@@ -599,16 +599,62 @@ __device__ __forceinline__ uint32_t pm_grid_pos0(const uint32_t* __restrict__ gr
 __device__ __forceinline__ uint32_t pm_grid_live(const uint32_t* __restrict__ grid, uint32_t r) { return grid[kPmGridRows + r]; }
 __device__ __forceinline__ uint32_t pm_grid_contig(const uint32_t* __restrict__ grid, uint32_t r) { return grid[2u * kPmGridRows + r]; }
 
-#ifndef QMCP_PM_OFFSETS_U
-#define QMCP_PM_OFFSETS_U 8  // position requests a wave keeps in flight
+// Lab build only (-DQMCP_PM_STAMP, lab/build_variant.sh; read back by lab/pm_range_stamps.py): the two per-range
+// kernels stamp the shader clock at their phase borders, wave 0 of every workgroup, into a buffer of their own that no
+// kernel reads.  [kernel: 0 offsets, 1 walk][range][0..4 the clock at the borders, 5 set once the row is written,
+// 6..7 the 100 MHz clock at entry and end: what a tick is worth].  The product build contains no stamp.
+#ifdef QMCP_PM_STAMP
+__device__ unsigned long long g_pm_stamps[2][kPmGridRows][8];
+__device__ __forceinline__ unsigned long long pm_stamp() {
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    return t;
+}
+// ... once `dep` (a register a load writes) is there: the wait for that load comes before the stamp
+__device__ __forceinline__ unsigned long long pm_stamp_after(uint32_t dep) {
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(dep) : "memory");
+    return t;
+}
+__device__ __forceinline__ unsigned long long pm_stamp_real() {
+    unsigned long long t;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    return t;
+}
+#define QMCP_PM_STAMPS unsigned long long pm_t[5] = {0, 0, 0, 0, 0}; const unsigned long long pm_r0 = pm_stamp_real();
+#define QMCP_PM_STAMP_AT(i) pm_t[i] = pm_stamp();
+#define QMCP_PM_STAMP_AFTER(i, dep) pm_t[i] = pm_stamp_after(dep);
+#define QMCP_PM_STAMPS_OUT(kernel)                                                                         \
+    if (threadIdx.x == 0) {                                                                                \
+        unsigned long long* const row = g_pm_stamps[kernel][blockIdx.x];                                   \
+        for (int i = 0; i < 5; ++i) row[i] = pm_t[i];                                                      \
+        row[5] = 1ull; row[6] = pm_r0; row[7] = pm_stamp_real();                                           \
+    }
+#else
+#define QMCP_PM_STAMPS
+#define QMCP_PM_STAMP_AT(i)
+#define QMCP_PM_STAMP_AFTER(i, dep)
+#define QMCP_PM_STAMPS_OUT(kernel)
 #endif
-// k_range_offsets for the pass-major layout: the range's positions come as wave-slots, in any order.  A wave takes four
-// wave-slots at a time -- sixteen lanes each, four records (8 bytes) per lane: one 512-byte request -- and keeps kU
-// such requests in flight.  The descriptors of a round are asked for one round ahead, a word per quarter-wave in one
-// vector load, right behind the round's position requests: by the time the positions have been counted they are there.
-// (They were sixteen scalar loads by uniform index, each in another line of an array the previous kernel has just
-// written, waited for before the first position could be asked for: two dependent trips to memory per round, four
-// requests in flight.  cfg4, one solve alone, aligned grid: 0.086 -> 0.078 ms; the grid itself: 0.092 -> 0.086.)
+
+#ifndef QMCP_PM_OFFSETS_REC
+#define QMCP_PM_OFFSETS_REC 8  // records a lane loads at a time: 8 (16 bytes) or 4 (8 bytes)
+#endif
+#ifndef QMCP_PM_OFFSETS_U
+#define QMCP_PM_OFFSETS_U 4  // position requests a wave keeps in flight
+#endif
+// k_range_offsets for the pass-major layout: the range's positions come as wave-slots, in any order.  A wave takes
+// eight wave-slots at a time -- eight lanes each, eight records (16 bytes) per lane: one 1 024-byte request -- and keeps
+// kU such requests in flight.  The descriptors of a round are asked for one round ahead, a word per eighth of the wave
+// in one vector load, right behind the round's position requests: by the time the positions have been counted they
+// are there.  The first round's descriptors are asked for before the counters are cleared and its positions half way
+// through the clear (16 bytes a lane and store): the clear runs behind those two trips to memory.
+// (History, cfg4, one solve alone, aligned grid.  Sixteen scalar descriptor loads by uniform index, waited for before
+// the first position could be asked for: 0.086 ms.  A vector load a round ahead: 0.078.  16-byte position loads, four
+// requests of eight wave-slots instead of eight of four, and the clear behind the first requests: 0.075 -> 0.070
+// beside the parent on one box.  A second register set, round r + 1 asked for before round r is counted, bought
+// nothing -- the sixteen waves of the workgroup run through the loop without a barrier and overlap each other's
+// loads and atomics already -- and was removed: profiles/pm_range_trips.md.)
 // One workgroup per range of the grid (gridDim.x); the last one also writes the grand total, boff[ltot].
 __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict__ keys16, const uint32_t* __restrict__ desc,
                                                      const uint32_t* __restrict__ Tp, uint32_t pitch,
@@ -616,48 +662,74 @@ __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict_
                                                      const uint32_t* __restrict__ grid,
                                                      uint32_t shift, uint32_t stride, uint32_t ltot, uint32_t* __restrict__ boff,
                                                      uint32_t* __restrict__ empty_positions) {
-    extern __shared__ uint32_t s_cnt32[];  // [(1 << shift) padded] counters
+    extern __shared__ __align__(16) uint32_t s_cnt32[];  // [(1 << shift) padded] counters
 #define PADDED(i) ((i) + ((i) >> 5))
     __shared__ uint32_t s_wsum[16], s_esum[16];
     const uint32_t range = blockIdx.x, width = 1u << shift;
+    QMCP_PM_STAMPS
+    QMCP_PM_STAMP_AT(0)
     const uint32_t pos0 = pm_grid_pos0(grid, range), live = pm_grid_live(grid, range);
     const uint32_t lo_p = Tp[(size_t)range * pitch], hi_p = Tp[(size_t)(range + 1) * pitch];
     const uint32_t g0 = lo_p >> 6, n_ws = (hi_p - lo_p) >> 6;
     const uint32_t lo = range_start[range];
-    for (uint32_t i = threadIdx.x; i < width; i += blockDim.x) s_cnt32[PADDED(i)] = 0;
-    __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, nw = blockDim.x >> 6;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t sub = lane >> 4, l16 = lane & 15u;
     constexpr int kU = QMCP_PM_OFFSETS_U;
-    const uint32_t n_quads = (n_ws + 3u) >> 2;
-    // the lane's wave-slots of the kU quads from q0 on: their descriptors (beyond the range's last: that one's, never used)
+    constexpr uint32_t kRec = QMCP_PM_OFFSETS_REC;  // 64 / kRec lanes a wave-slot, kRec wave-slots (a GROUP) a request
+    static_assert(kRec == 4 || kRec == 8, "a lane loads 8 or 16 bytes");
+    const uint32_t sub = lane / (64u / kRec), l_in = lane % (64u / kRec);
+    const uint32_t n_groups = (n_ws + kRec - 1u) / kRec, step = (uint32_t)kU * nw;
+    // the lane's wave-slots of the kU groups from q0 on: their descriptors (beyond the range's last: that one's, never used)
     uint32_t dsc[kU];
     auto ask_descriptors = [&](uint32_t q0) {
 #pragma unroll
-        for (int u = 0; u < kU; ++u) dsc[u] = desc[g0 + min(4u * (q0 + (uint32_t)u * nw) + sub, n_ws - 1u)];
+        for (int u = 0; u < kU; ++u) dsc[u] = desc[g0 + min(kRec * (q0 + (uint32_t)u * nw) + sub, n_ws - 1u)];
+    };
+    uint32_t v[kU][kRec / 2], nv[kU];  // a round's positions (in flight) and its wave-slots' record counts
+    // round q0's positions through dsc[], then the next round's descriptors into dsc[], behind them
+    auto ask_round = [&](uint32_t q0) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const PmSlot at = pm_unpack<true>(dsc[u], kRec * (q0 + (uint32_t)u * nw) + sub < n_ws, stride);
+            nv[u] = at.nv;
+            const uint16_t* const src = keys16 + at.slot0 + kRec * l_in;   // (inside the slice's padded group: always readable)
+            if constexpr (kRec == 4) {
+                const uint2 x = *reinterpret_cast<const uint2*>(src);
+                v[u][0] = x.x; v[u][1] = x.y;
+            } else {
+                const uint4 x = *reinterpret_cast<const uint4*>(src);
+                v[u][0] = x.x; v[u][1] = x.y; v[u][2] = x.z; v[u][3] = x.w;
+            }
+        }
+        ask_descriptors(q0 + step);  // (the last round's too: clamped, a line already read)
     };
     if (n_ws != 0u) ask_descriptors(w);
-    for (uint32_t q0 = w; q0 < n_quads; q0 += kU * nw) {
-        uint2 v[kU];
-        uint32_t nv[kU];
+    // the clear: every word of the padded array (PADDED(width - 1) < width + width / 32, the array is one word longer)
+    const uint32_t n_words = width + (width >> 5), n_vec = n_words >> 2, half = (n_vec + 1u) >> 1;
+    uint4* const cnt4 = reinterpret_cast<uint4*>(s_cnt32);
+    for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) cnt4[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (w < n_groups) ask_round(w);  // (uniform)
+    for (uint32_t i = half + threadIdx.x; i < n_vec; i += blockDim.x) cnt4[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t i = 4u * n_vec + threadIdx.x; i < n_words; i += blockDim.x) s_cnt32[i] = 0u;
+    __syncthreads();
+    // v[] holds round q0, asked for; dsc[] round q0 + step's descriptors
+    for (uint32_t q0 = w; q0 < n_groups; q0 += step) {
+#ifdef QMCP_PM_STAMP
+        if (q0 == w) QMCP_PM_STAMP_AFTER(1, v[kU - 1][kRec / 2 - 1])
+#endif
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            const PmSlot at = pm_unpack<true>(dsc[u], 4u * (q0 + (uint32_t)u * nw) + sub < n_ws, stride);
-            nv[u] = at.nv;
-            v[u] = *reinterpret_cast<const uint2*>(keys16 + at.slot0 + 4u * l16);   // (inside the slice's padded group: always readable)
-        }
-        if (q0 + kU * nw < n_quads) ask_descriptors(q0 + kU * nw);  // (uniform) the next round's, behind this round's positions
+            const uint32_t e = kRec * l_in;
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const uint32_t e = 4u * l16;
-            if (e < nv[u]) atomicAdd(&s_cnt32[PADDED(v[u].x & 0xFFFFu)], 1u);
-            if (e + 1 < nv[u]) atomicAdd(&s_cnt32[PADDED(v[u].x >> 16)], 1u);
-            if (e + 2 < nv[u]) atomicAdd(&s_cnt32[PADDED(v[u].y & 0xFFFFu)], 1u);
-            if (e + 3 < nv[u]) atomicAdd(&s_cnt32[PADDED(v[u].y >> 16)], 1u);
+            for (uint32_t x = 0; x < kRec / 2; ++x) {
+                if (e + 2u * x < nv[u]) atomicAdd(&s_cnt32[PADDED(v[u][x] & 0xFFFFu)], 1u);
+                if (e + 2u * x + 1u < nv[u]) atomicAdd(&s_cnt32[PADDED(v[u][x] >> 16)], 1u);
+            }
         }
+        if (q0 + step < n_groups) ask_round(q0 + step);  // (uniform)
     }
     __syncthreads();
+    QMCP_PM_STAMP_AT(2)
     // counts -> bucket offsets, in place (k_range_offsets)
     const uint32_t per = width >= 1024u ? width >> 10 : 1u;  // positions per thread
     const uint32_t firstp = threadIdx.x * per;
@@ -690,70 +762,174 @@ __global__ __launch_bounds__(1024) void k_pm_offsets(const uint16_t* __restrict_
             run += cq;
         }
     __syncthreads();
+    QMCP_PM_STAMP_AT(3)
     for (uint32_t i = threadIdx.x; i < live; i += blockDim.x) boff[pos0 + i] = s_cnt32[PADDED(i)];
     // (the grand total: the ranges of the grid end where the genome does, so no range has a position ltot of its own)
     if (range == gridDim.x - 1u && threadIdx.x == 0) boff[ltot] = range_start[kPmGridRows];
+    QMCP_PM_STAMP_AT(4)
+    QMCP_PM_STAMPS_OUT(0)
 #undef PADDED
 }
 
 // Where the quotas come from when the event-driven sweep ran whole contigs (no stretch table): the kept count of
 // position p is sev[p - (k - lastns[k]) * ell], k its block -- what k_sweep_expand would write into selend[] for the
 // ranking to read back (30 us and 100 MB a solve; here the ranking reads the sweep's own output).
-struct EvQuota { const uint32_t* sev; const uint32_t* lastns; const uint64_t* poff; uint32_t n_contigs, ell; };
+// (div: ell's multiply-and-shift constants, computed by the launcher -- pm_div.h)
+struct EvQuota { const uint32_t* sev; const uint32_t* lastns; const uint64_t* poff; uint32_t n_contigs, ell; PmDiv div; };
+
+// The walk's quotas straight from the event-driven sweep's output: two dependent loads per position -- the block's
+// distance to the block that holds its value (lastns), then the value (sev) -- kQ positions of a thread in flight: at
+// kQ = 16 a range of 32 Ki positions takes two rounds (eight in flight and a divide per position: 16.5 us from the
+// kernel's entry to its first draw at cfg4; sixteen and the multiply: 8.1 - 9.7; all 32 in one round: no better --
+// profiles/pm_range_trips.md).  The block of a position, (p - base) / ell, is a multiply and a shift by the
+// launcher's constants (pm_div.h).  kOne: the range lies in contig c_range, whose base and
+// row of lastns[] are uniform; else every position's contig is looked up.
+template <int kQ, bool kOne>
+__device__ __forceinline__ void pm_event_quotas(const EvQuota& evq, uint32_t c_range, uint32_t pos0, uint32_t live, uint32_t tid,
+                                                uint32_t nthreads, int32_t* s_q) {
+    uint32_t base_u = 0, row_u = 0;
+    if (kOne) {
+        base_u = (uint32_t)evq.poff[c_range];
+        row_u = (pm_div(base_u, evq.div) >> 2) + c_range;  // base / (4 ell) + c
+    }
+    for (uint32_t i0 = tid; i0 < live; i0 += kQ * nthreads) {
+        uint32_t val[kQ];  // the distance in blocks, then the quota
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) {
+            const uint32_t p = pos0 + min(i0 + u * nthreads, live - 1);  // clamped: every load is issued
+            uint32_t base = base_u, row = row_u;
+            if (!kOne) {
+                uint32_t c_lo = 0, c_hi = evq.n_contigs;  // last contig with poff[c] <= p
+                while (c_hi - c_lo > 1) {
+                    const uint32_t mid = (c_lo + c_hi) >> 1;
+                    if ((uint32_t)evq.poff[mid] <= p) c_lo = mid; else c_hi = mid;
+                }
+                base = (uint32_t)evq.poff[c_lo];
+                row = (pm_div(base, evq.div) >> 2) + c_lo;
+            }
+            const uint32_t k = pm_div(p - base, evq.div);
+            val[u] = k - evq.lastns[(size_t)row * 4u + k];
+        }
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) val[u] = evq.sev[pos0 + min(i0 + u * nthreads, live - 1) - val[u] * evq.ell];
+#pragma unroll
+        for (int u = 0; u < kQ; ++u)
+            if (i0 + u * nthreads < live) s_q[i0 + u * nthreads] = (int32_t)val[u];
+    }
+}
 
 // Settling, in the walk's own tail: the listed (chunk, position) groups of the range.  The position's `skip` LAST records
 // of that chunk are the ones the quota did not reach, so a wave walks the chunk's sixteen wave-slots backwards, passes
 // over that many matches and keeps the rest.  The workgroup's sixteen waves deal the groups out (a few dozen per range
-// at cfg4: 20 000 in all), and a wave takes two at a time (all their loads asked for before either is looked at: a group
-// is four dependent trips to memory and little else).  -> records kept by this wave (uniform).  (This was a kernel of
-// its own, k_pm_settle -- a second launch that loaded Tp, the range's start and a per-range group count again.)
+// at cfg4: 20 000 in all).  A group is four dependent trips to memory -- list entry, descriptors, positions, read
+// indices -- and a walk of sixteen steps, so a wave overlaps them: the list entries of all its groups come in one load
+// (lane j: the wave's group j), and while group j is walked the positions of group j + 1 and the descriptors of group
+// j + 2 are on their way.  The read indices of a group's kept records are asked for step by step during its walk and
+// marked after the NEXT group's walk: no trip per step that holds a match, none per group.  -> records kept by this
+// wave (uniform).
+// (This was a kernel of its own, k_pm_settle -- a second launch that loaded Tp, the range's start and a per-range group
+// count again; then two groups at a time, nothing of the next two asked for: profiles/pm_range_trips.md.)
 __device__ __forceinline__ uint32_t pm_settle_groups(const uint16_t* __restrict__ keys16, const uint16_t* __restrict__ idx16,
                                                      const uint32_t* __restrict__ desc, uint32_t g0, uint32_t n_ws,
                                                      uint32_t stride, const uint2* amb, uint32_t namb, uint32_t w,
                                                      uint32_t lane, unsigned long long* __restrict__ mask) {
     const uint64_t gt_mask = lane == 63 ? 0ull : ~((2ull << lane) - 1ull);  // lanes above this one
     uint32_t kept = 0;
-    constexpr int kSteps = 16, kE = 2;
+    constexpr int kSteps = 16;
     constexpr uint32_t stride_k = 16;  // waves of the workgroup
-    for (uint32_t k0 = w; k0 < namb; k0 += kE * stride_k) {
-        uint32_t key[kE][kSteps], dscv[kE] /* lane t < 16: the descriptor of the chunk's wave-slot t */, p[kE], skip[kE], c_of[kE];
-#pragma unroll
-        for (int x = 0; x < kE; ++x) {
-            const uint32_t k = k0 + (uint32_t)x * stride_k;
-            const uint2 ent = k < namb ? amb[k] : make_uint2(0u, 0u);
-            c_of[x] = ent.x >> 15;
-            p[x] = k < namb ? ent.x & 0x7FFFu : 0xFFFFFFFFu;  // (no 16-bit position equals it)
-            skip[x] = ent.y;  // matches still to be passed over, from the chunk's end
-            const uint32_t ws = 16u * c_of[x] + (lane & 15u);
-            dscv[x] = ws < n_ws ? desc[g0 + ws] : 0u;
-        }
-#pragma unroll
-        for (int x = 0; x < kE; ++x) {
+    struct Group {
+        uint32_t key[kSteps];  // lane l: the position in slot l of the chunk's wave-slot t
+        uint32_t dscv;         // lane t < 16: the descriptor of the chunk's wave-slot t
+        uint32_t c, p, skip;   // (uniform) the chunk, the position, matches to be passed over from the chunk's end
+    };
+    struct Kept {              // of a walked group: what is still to be marked
+        uint32_t idx[kSteps];  // lane l: the read index inside its pass of the record in slot l of wave-slot t (asked for)
+        uint32_t marked;       // steps t whose record this lane keeps
+        uint32_t dscv;         // the group's descriptors (their passes)
+    };
+    const uint32_t mine = namb > w ? (namb - w + stride_k - 1u) / stride_k : 0u;  // (uniform) groups w, w + 16, ...
+    for (uint32_t j0 = 0; j0 < mine; j0 += 64u) {
+        const uint32_t nj = min(64u, mine - j0);
+        const uint32_t k_lane = w + stride_k * (j0 + lane);
+        const uint2 ent = k_lane < namb ? amb[k_lane] : make_uint2(0u, 0u);
+        uint32_t dsc_next;  // descriptors on their way
+        // (every request below is made without a condition, for the last group again where there is no further one:
+        //  under a condition the compiler loads into other registers and copies, and waits for the copy's sake)
+        auto ask_descriptors = [&](uint32_t j) {
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)ent.x, (int)min(j, nj - 1u)) >> 15;
+            const uint32_t ws = 16u * c + (lane & 15u);
+            dsc_next = desc[g0 + min(ws, n_ws - 1u)];  // (beyond the range's last: that one's, never used)
+        };
+        auto ask_positions = [&](Group& G, uint32_t j) {  // through dsc_next
+            const int jj = (int)min(j, nj - 1u);
+            const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)ent.x, jj);
+            G.c = e >> 15;
+            G.p = e & 0x7FFFu;
+            G.skip = (uint32_t)__builtin_amdgcn_readlane((int)ent.y, jj);
+            G.dscv = dsc_next;
 #pragma unroll
             for (int t = 0; t < kSteps; ++t) {
-                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)dscv[x], t);
-                key[x][t] = keys16[pm_unpack<false>(dsc, 16u * c_of[x] + (uint32_t)t < n_ws, stride).slot0 + lane];
+                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)G.dscv, t);
+                G.key[t] = keys16[pm_unpack<false>(dsc, 16u * G.c + (uint32_t)t < n_ws, stride).slot0 + lane];
             }
-        }
-#pragma unroll
-        for (int x = 0; x < kE; ++x) {
+        };
+        // the walk of one group: passes over `skip` matches from the chunk's end, asks for the read indices of the rest
+        auto walk = [&](const Group& G, Kept& K) {
+            uint32_t skip = G.skip;
+            K.marked = 0u;
+            K.dscv = G.dscv;
 #pragma unroll
             for (int t = kSteps - 1; t >= 0; --t) {
-                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)dscv[x], t);
-                const PmSlot at = pm_unpack<false>(dsc, 16u * c_of[x] + (uint32_t)t < n_ws, stride);
-                const bool member = lane < at.nv && key[x][t] == p[x];
+                const uint32_t dsc = (uint32_t)__builtin_amdgcn_readlane((int)G.dscv, t);
+                const PmSlot at = pm_unpack<false>(dsc, 16u * G.c + (uint32_t)t < n_ws, stride);
+                const bool member = lane < at.nv && G.key[t] == G.p;
                 const uint64_t m = __ballot(member);
+                K.idx[t] = 0u;
                 if (m == 0) continue;
                 const uint32_t above = (uint32_t)__popcll(m & gt_mask);  // matches after this one in the step
-                if (member && above >= skip[x]) {
-                    const uint32_t v = at.pass * (uint32_t)kPmPass + idx16[at.slot0 + lane];
-                    atomicOr(&mask[v >> 6], 1ull << (v & 63u));
+                if (member && above >= skip) {
+                    K.idx[t] = idx16[at.slot0 + lane];
+                    K.marked |= 1u << t;
                 }
                 const uint32_t in_step = (uint32_t)__popcll(m);
-                kept += in_step > skip[x] ? in_step - skip[x] : 0u;
-                skip[x] = skip[x] > in_step ? skip[x] - in_step : 0u;
+                kept += in_step > skip ? in_step - skip : 0u;
+                skip = skip > in_step ? skip - in_step : 0u;
             }
+        };
+        // ... and their marking, one group later: the read indices have had a walk's time to arrive
+        auto mark = [&](Kept& K) {
+            if (__ballot(K.marked != 0u) != 0) {
+#pragma unroll
+                for (int t = 0; t < kSteps; ++t)
+                    if ((K.marked >> t) & 1u) {
+                        const uint32_t v = ((uint32_t)__builtin_amdgcn_readlane((int)K.dscv, t) >> 15) * (uint32_t)kPmPass + K.idx[t];
+                        atomicOr(&mask[v >> 6], 1ull << (v & 63u));
+                    }
+            }
+            K.marked = 0u;
+        };
+        Group A, B;
+        Kept KA, KB;
+        KA.marked = KB.marked = 0u;
+        KA.dscv = KB.dscv = 0u;
+#pragma unroll
+        for (int t = 0; t < kSteps; ++t) KA.idx[t] = KB.idx[t] = 0u;
+        ask_descriptors(0u);
+        ask_positions(A, 0u);
+        ask_descriptors(1u);
+        for (uint32_t j = 0; j < nj; j += 2u) {
+            ask_positions(B, j + 1u);
+            ask_descriptors(j + 2u);
+            walk(A, KA);
+            mark(KB);  // group j - 1's
+            if (j + 1u >= nj) break;
+            ask_positions(A, j + 2u);
+            ask_descriptors(j + 3u);
+            walk(B, KB);
+            mark(KA);
         }
+        mark(KA);
+        mark(KB);
     }
     return kept;
 }
@@ -786,6 +962,8 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     const uint32_t tid = threadIdx.x, nthreads = blockDim.x;
     const uint32_t lane = tid & 63u;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    QMCP_PM_STAMPS
+    QMCP_PM_STAMP_AT(0)
     const uint32_t lo_p = Tp[(size_t)range * pitch];
     const uint32_t hi_p = Tp[(size_t)(range + 1) * pitch];  // (range 255: the scan's total)
     if (lo_p >= hi_p) return;  // uniform: a range without reads needs no quotas either
@@ -793,33 +971,17 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     const uint32_t n_chunks = (n_ws + 15u) >> 4;
     const uint32_t lo_true = range_start[range];
     uint2* const amb = amb_lists + (lists_by_records ? (size_t)lo_true : (size_t)range * width);
+    // the wave's descriptors of chunks 0..6, the plain way (compiler registers), asked for here: they are on their way
+    // while the quotas are fetched, not a trip of their own after them
+    uint32_t d0[kRankDepth - 1];
+#pragma unroll
+    for (int k = 0; k < kRankDepth - 1; ++k) d0[k] = desc[g0 + min(16u * (uint32_t)k + w, n_ws - 1u)];
     if (evq.sev != nullptr) {
-        // straight from the event-driven sweep's output (two dependent loads per position, eight positions in flight).
-        // On the aligned grid the range lies in one contig; a range of the global grid that straddles a border looks
-        // every position's contig up.
+        // straight from the event-driven sweep's output.  On the aligned grid the range lies in one contig; a range of
+        // the global grid that straddles a border looks every position's contig up.
         const uint32_t c_range = pm_grid_contig(grid, range);  // (uniform)
-        for (uint32_t i0 = tid; i0 < live; i0 += 8 * nthreads) {
-            uint32_t src[8], back[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const uint32_t p = pos0 + min(i0 + u * nthreads, live - 1);  // clamped: every load is issued
-                uint32_t c_lo = c_range, c_hi = c_range + 1u;
-                if (c_range == kPmNoContig) { c_lo = 0; c_hi = evq.n_contigs; }  // last contig with poff[c] <= p
-                while (c_hi - c_lo > 1) {
-                    const uint32_t mid = (c_lo + c_hi) >> 1;
-                    if ((uint32_t)evq.poff[mid] <= p) c_lo = mid; else c_hi = mid;
-                }
-                const uint32_t base = (uint32_t)evq.poff[c_lo];
-                const uint32_t k = (p - base) / evq.ell;
-                src[u] = p;
-                back[u] = k - evq.lastns[(size_t)(base / (4u * evq.ell) + c_lo) * 4u + k];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) src[u] = evq.sev[src[u] - back[u] * evq.ell];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (i0 + u * nthreads < live) s_q[i0 + u * nthreads] = (int32_t)src[u];
-        }
+        if (c_range != kPmNoContig) pm_event_quotas<16, true>(evq, c_range, pos0, live, tid, nthreads, s_q);
+        else pm_event_quotas<8, false>(evq, c_range, pos0, live, tid, nthreads, s_q);
     } else
     for (uint32_t i0 = tid; i0 < live; i0 += 8 * nthreads) {
         uint32_t a[8], b[8];
@@ -945,12 +1107,9 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     }
     Slot S[kRankDepth];
     {
-        // chunks 0..6: descriptors the plain way (nothing is in flight yet), their positions into the ring; descriptors
-        // of chunks 7..14 into the ring; then everything is waited for once -- the loop's counted wait assumes its own
-        // issue order (positions, descriptor, positions, ...), which these requests do not have
-        uint32_t d0[kRankDepth - 1];
-#pragma unroll
-        for (int k = 0; k < kRankDepth - 1; ++k) d0[k] = desc[desc_offset((uint32_t)k) / 4u];
+        // chunks 0..6: descriptors the plain way (d0[]: asked for ahead of the quotas), their positions into the ring;
+        // descriptors of chunks 7..14 into the ring; then everything is waited for once -- the loop's counted wait
+        // assumes its own issue order (positions, descriptor, positions, ...), which these requests do not have
 #pragma unroll
         for (int k = 0; k < kRankDepth - 1; ++k) S[k] = slot_of(d0[k], (uint32_t)k);
         S[kRankDepth - 1] = Slot{0u, 0u, 0u, false};
@@ -962,12 +1121,14 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
 #undef QMCP_PM_ASK_KEYS
 #undef QMCP_PM_ASK_DSC
     }
+    QMCP_PM_STAMP_AT(1)
     for (uint32_t c0 = 0; c0 < n_chunks; c0 += kRankDepth) {
         QMCP_PM_STEP(0, 7) QMCP_PM_STEP(1, 0) QMCP_PM_STEP(2, 1) QMCP_PM_STEP(3, 2)
         QMCP_PM_STEP(4, 3) QMCP_PM_STEP(5, 4) QMCP_PM_STEP(6, 5) QMCP_PM_STEP(7, 6)
     }
 #undef QMCP_PM_STEP
     asm volatile("s_waitcnt vmcnt(0)" : : : QMCP_PM_RING, "memory");  // (the loads asked for beyond the last chunk)
+    QMCP_PM_STAMP_AT(2)
     if (lane < cur - flushed) {
         const uint32_t v = ring[(flushed + lane) & 127u];
         atomicOr(&mask[v >> 6], 1ull << (v & 63u));
@@ -980,10 +1141,18 @@ __global__ __launch_bounds__(1024) void k_pm_walk(const uint16_t* __restrict__ k
     kept += pm_settle_groups(keys16, idx16, desc, g0, n_ws, stride, amb, s_namb, w, lane, mask);
     if (lane == 0 && kept) atomicAdd(&s_kept, kept);
     __syncthreads();
+    QMCP_PM_STAMP_AT(3)
+    QMCP_PM_STAMPS_OUT(1)
     if (tid == 0 && s_kept) atomicAdd(kept_total, (unsigned long long)s_kept);
 }
 
 // ---- launchers
+#ifdef QMCP_PM_STAMP
+// (lab build only) the stamps of the last k_pm_offsets and k_pm_walk launches -> out[2 * 256 * 8]
+extern "C" int qmcp_lab_pm_stamps(unsigned long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pm_stamps), sizeof(g_pm_stamps));
+}
+#endif
 uint32_t pm_pitch(uint32_t n) { return part_pass_pitch(n); }  // passes of the call, rounded up to a multiple of 4
 uint32_t pm_pass() { return (uint32_t)kPmPass; }
 uint32_t pm_stride(uint32_t n_ranges) { return pm_stride_of(n_ranges); }
@@ -1042,7 +1211,7 @@ void launch_pm_walk(hipStream_t st, const uint16_t* keys16, const uint16_t* idx1
                     const uint32_t* boff, const uint32_t* selend, unsigned long long* mask, unsigned long long* kept_total, void* scratch,
                     bool scratch_by_records, const uint32_t* ev_sev, const uint32_t* ev_lastns,
                     const uint64_t* d_poff, uint32_t n_contigs, uint32_t ell) {
-    const EvQuota evq{ev_sev, ev_lastns, d_poff, n_contigs, ell};
+    const EvQuota evq{ev_sev, ev_lastns, d_poff, n_contigs, ell, pm_div_make(ell)};
     const size_t lds = (((size_t)1 << shift) + 1) * sizeof(uint32_t);
     (void)hipFuncSetAttribute((const void*)k_pm_walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_pm_walk, dim3(n_ranges), dim3(1024), lds, st, keys16, idx16, desc, Tp, pm_pitch(n), range_start, d_grid, shift,

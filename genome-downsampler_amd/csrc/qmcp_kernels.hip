@@ -82,6 +82,7 @@
 
 #include "qmcp_kernels.h"
 #include "target_table.h"  // project_read: shared with the host
+#include "pm_div.h"        // the walk's division by the sweep's span: constants on the host, multiply on the device
 
 namespace qmcp {
 
