@@ -14,6 +14,8 @@
 //                    -- PlainSolver is the ordinary multi-contig solve at M -- fills the batch mask, which is ORed back
 //                    into input order; the batch's stats join the call's), then the solver's after_batch
 // The by-contig call itself is group_by_contig, run_batches with a PlainSolver, and the final wait.
+// The entries that solve one grouping at several coverages (budget, mean-depth, thresholds) put these together once more,
+// in api/cap_search.inc.hip: the probe solve, and for the first two the depth-curve stage and the search loop.
 namespace {
 
 // the batches' stats as one: counts and times summed, the route of the batch with the most reads

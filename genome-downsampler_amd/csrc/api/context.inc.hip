@@ -242,16 +242,16 @@ struct qmcp_hip_ctx {
     // proportional solves (api/proportional.inc.hip; need[] is the profile's pf_need): the call's counters
     // (qmcp_kernels.h: PropStat)
     DevBuf pp_stat;
-    // budget solves (api/budget.inc.hip), all its own: the accumulators, the curve and the depth histogram in one buffer
-    // (BudgetWord words | curve | histogram), and the second input-order mask of the probes
+    // budget and mean-depth solves (api/budget.inc.hip, api/mean_depth.inc.hip; laid out and searched by
+    // api/cap_search.inc.hip), their own: the accumulators, the curve and the depth histogram in one buffer (CapAcc:
+    // BudgetWord words | curve | histogram | mean-depth's MeanDepthWord words), and the second input-order mask of the probes
     DevBuf bg_acc, bg_mask;
-    // mean-depth solves (api/mean_depth.inc.hip; the accumulators and the second mask are the budget's bg_acc / bg_mask,
-    // with the MeanDepthWord words behind the histogram): the merged region table in contig coordinates (offs | rs | re |
-    // cum) followed by the batches' form of it (rpos | rcum), and the reads' weights
+    // mean-depth solves alone: the merged region table in contig coordinates (offs | rs | re | cum) followed by the
+    // batches' form of it (rpos | rcum), and the reads' weights
     DevBuf md_tab, md_w;
-    // coverage thresholds (api/thresholds.inc.hip), all its own: the input-order mask a coverage's solve scatters into,
-    // the reads that have a threshold, the accumulators with the histogram behind them (ThresholdsAccWord words | bins),
-    // and the host entry's thresholds
+    // coverage thresholds (api/thresholds.inc.hip), all its own: the input-order mask a coverage's solve (ProbeSolve,
+    // api/cap_search.inc.hip) scatters into, the reads that have a threshold, the accumulators with the histogram behind
+    // them (ThresholdsAccWord words | bins), and the host entry's thresholds
     DevBuf th_mask, th_seen, th_acc, th_thr;
     // disjoint replicates (api/replicates.inc.hip), all its own: the two sets of free reads' columns (starts, ends, input
     // indices) that ping-pong between replicates, the scanned word popcounts of the taken candidates and their spine, the

@@ -4,15 +4,14 @@
 // QMCP_MEAN_DEPTH_WHOLE_PAIRS), and that solve's mask.  The budget entry's flow (api/budget.inc.hip) with bases for reads:
 //   1. target_table.h merges the regions on the host (padding 0); group_by_contig, once per call
 //   2. k_md_weights, once: w[i] = |read i n R|
-//   3. per batch with reads, before the first probe: budget_batch_depth, then k_md_tally over the batch's part of R (its
-//      merged regions moved onto the batch's concatenated axis) -- k_budget_tally without a table
-//   4. k_budget_curve gives S_R(M) = sum over R of min(cov, M); it comes back with the largest depth and the sum in one copy
-//   5. budget_plan.h picks the probes with spans of 1: its bound is then S_R(M) itself, and the first probe the largest M
-//      with S_R(M) <= budget.  A probe is the budget's (run_batches with a PlainSolver into a cleared input-order mask,
-//      k_budget_finish under the flag), then k_md_count; the MeanDepthWord words come back in one copy.  Two masks swap
-//      roles as in the budget entry: nothing is solved twice
-// Buffers: bg_acc (BudgetWord words | curve | histogram | MeanDepthWord words), bg_mask, md_tab (offs | rs | re | cum in
-// contig coordinates, then rpos | rcum per batch), md_w.
+//   3. depth_curve (api/cap_search.inc.hip) with k_md_tally over the batch's part of R (its merged regions moved onto the
+//      batch's concatenated axis) -- k_budget_tally without a table: S_R(M) = sum over R of min(cov, M), the largest
+//      depth and the sum
+//   4. budget_plan.h starts with spans of 1: its bound is then S_R(M) itself, and the first probe the largest M with
+//      S_R(M) <= budget; search_cap (api/cap_search.inc.hip) runs its probes.  A probe counts the bases its mask keeps:
+//      k_budget_finish under the flag, then k_md_count; the MeanDepthWord words come back in one copy
+// Buffers: bg_acc (CapAcc: BudgetWord words | curve | histogram | MeanDepthWord words), bg_mask, md_tab (offs | rs | re |
+// cum in contig coordinates, then rpos | rcum per batch), md_w.
 namespace {
 
 // the regions as both entries check them: after the budget's checks, in the order of the targets entries
@@ -47,16 +46,9 @@ int solve_mean_depth_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     const size_t words = (size_t)((n64 + 63) / 64);
     const bool whole_pairs = (flags & QMCP_MEAN_DEPTH_WHOLE_PAIRS) != 0;
     hipStream_t st = c->stream;
-    const uint32_t H = std::min(max_coverage, (uint32_t)QMCP_BUDGET_CURVE_MAX) + 1u;
-    const size_t acc_words = (size_t)qmcp::kBudgetWords + 2 * (size_t)H + qmcp::kMdWords;
-    TRY(ensure(c, c->bg_mask, words * sizeof(uint64_t)));
-    TRY(ensure(c, c->bg_acc, acc_words * sizeof(unsigned long long)));
+    CapAcc a;
+    TRY(reserve_cap_acc(c, max_coverage, words, qmcp::kMdWords, a));
     TRY(ensure(c, c->md_w, (size_t)n64 * sizeof(uint32_t) + 16));
-    unsigned long long* d_acc = c->bg_acc.as<unsigned long long>();
-    unsigned long long* d_curve = d_acc + qmcp::kBudgetWords;
-    unsigned long long* d_hist = d_curve + H;
-    unsigned long long* d_md = d_hist + H;
-    HIP_TRY(hipMemsetAsync(d_acc, 0, acc_words * sizeof(unsigned long long), st));
 
     // 1: the grouping (the mask it clears is the call's own: a refused call leaves d_mask alone)
     GroupedReads g;
@@ -98,130 +90,54 @@ int solve_mean_depth_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
         }
     }
 
-    std::vector<std::unique_ptr<EventPair>> evs;  // one for k_md_weights, one per tally, one for k_budget_curve
-    auto bracket = [&]() -> EventPair* {
-        evs.emplace_back(new EventPair(c));
-        return evs.back()->a && evs.back()->b ? evs.back().get() : nullptr;
-    };
     // 2: the weights
-    {
-        EventPair* ev = bracket();
-        if (!ev) return fail(QMCP_EHIP, "event creation failed");
-        HIP_TRY(hipEventRecord(ev->a, st));
-        {
-            KernelSpan sp(c, "k_md_weights");
-            qmcp::launch_md_weights(st, d_starts, d_ends, d_ids, (uint32_t)n64, n_contigs, tab != nullptr, d_offs, d_rs, d_re,
-                                    d_cum, n_reg, c->md_w.u32());
-        }
-        HIP_TRY(hipEventRecord(ev->b, st));
-        HIP_TRY(hipGetLastError());
-    }
-    // 3-4: the depth histogram inside R over every batch, the curve
-    uint32_t span_max = 0;
-    BatchView v;
-    for (size_t b : g.live) {  // (no read: no depth)
-        g.view(b, v);
-        TRY(gather_batch(c, v, d_starts, d_ends));
-        uint32_t ltot = 0;
-        TRY(budget_batch_depth(c, c->bc_starts.u32(), c->bc_ends.u32(), v.roff.data(), v.lengths, v.n_contigs, v.nb, &ltot,
-                               &span_max));
-        EventPair* ev = bracket();
-        if (!ev) return fail(QMCP_EHIP, "event creation failed");
-        HIP_TRY(hipEventRecord(ev->a, st));
-        if (tab) {
-            const uint32_t r0 = tab->offs[v.first_contig], r1 = tab->offs[v.first_contig + v.n_contigs];
-            KernelSpan sp(c, "k_md_tally");
-            qmcp::launch_md_tally(st, c->cov.u32(), ltot, d_rpos + r0, d_rcum + r0, r1 - r0, batch_pos[b], H, d_acc, d_hist);
-        } else {
-            KernelSpan sp(c, "k_budget_tally");
-            qmcp::launch_budget_tally(st, c->cov.u32(), ltot, H, d_acc, d_hist);
-        }
-        HIP_TRY(hipEventRecord(ev->b, st));
-        HIP_TRY(hipGetLastError());
-    }
-    {
-        EventPair* ev = bracket();
-        if (!ev) return fail(QMCP_EHIP, "event creation failed");
-        HIP_TRY(hipEventRecord(ev->a, st));
-        {
-            KernelSpan sp(c, "k_budget_curve");
-            qmcp::launch_budget_curve(st, d_hist, H, d_curve);
-        }
-        HIP_TRY(hipEventRecord(ev->b, st));
-        HIP_TRY(hipGetLastError());
-    }
-    std::vector<unsigned long long> back((size_t)qmcp::kBudgetWords + H);
-    HIP_TRY(hipMemcpyAsync(back.data(), d_acc, back.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (auto& ev : evs) ms.ms_mean_depth += elapsed(ev->a, ev->b);
-    evs.clear();
-    const uint64_t* curve = (const uint64_t*)(back.data() + qmcp::kBudgetWords);
+    ProbeSolve probe{g};
+    TimedLaunches timed{c};
+    TRY(timed.run([&] {
+        KernelSpan sp(c, "k_md_weights");
+        qmcp::launch_md_weights(st, d_starts, d_ends, d_ids, (uint32_t)n64, n_contigs, tab != nullptr, d_offs, d_rs, d_re,
+                                d_cum, n_reg, c->md_w.u32());
+    }));
+    // 3: the depth histogram inside R over every batch, the curve
+    auto tally = [&](size_t b, const BatchView& v, uint32_t ltot) {
+        if (!tab) return tally_every_position(c, a, ltot);
+        const uint32_t r0 = tab->offs[v.first_contig], r1 = tab->offs[v.first_contig + v.n_contigs];
+        KernelSpan sp(c, "k_md_tally");
+        qmcp::launch_md_tally(st, c->cov.u32(), ltot, d_rpos + r0, d_rcum + r0, r1 - r0, batch_pos[b], a.H, a.acc, a.hist);
+    };
+    DepthCurve d;
+    TRY(depth_curve(c, probe, a, max_coverage, timed, tally, d));
+    ms.ms_mean_depth = d.ms;
     ms.reads_placed = placed;
-    ms.max_depth = (uint32_t)back[qmcp::kBudgetMaxDepth];
-    ms.total_bases = back[qmcp::kBudgetTotalBases];
-    ms.top = std::min(max_coverage, ms.max_depth);
-    if (curve_out && curve_capacity) {
-        ms.curve_entries = std::min(std::min(ms.top, (uint32_t)QMCP_BUDGET_CURVE_MAX), curve_capacity - 1u) + 1u;
-        for (uint32_t m = 0; m < ms.curve_entries; ++m) curve_out[m] = curve[m];
-    }
+    ms.max_depth = d.max_depth;
+    ms.total_bases = d.total_bases;
+    ms.top = d.top;
+    ms.curve_entries = d.copy_out(curve_out, curve_capacity);
 
-    // 5: the probes.  Spans of 1: the planner's bound is the curve itself, its mean span 1
+    // 4: the probes.  Spans of 1: the planner's bound is the curve itself, its mean span 1
     qmcp::BudgetPlan plan;
-    plan.start(curve, H, ms.top, 1, placed, placed, budget);
-    uint64_t* masks[2] = {d_mask, c->bg_mask.u64()};
-    int best = -1, scratch = 0;
-    uint64_t kept_lo = 0;
-    qmcp_hip_stats best_stats;
-    std::memset(&best_stats, 0, sizeof(best_stats));
-    EventPair fin(c);
-    if (!fin.a || !fin.b) return fail(QMCP_EHIP, "event creation failed");
-    while (!plan.done()) {
-        const uint32_t M = plan.next();
-        uint64_t* pm = masks[scratch];
-        if (words) HIP_TRY(hipMemsetAsync(pm, 0, words * sizeof(uint64_t), st));  // (k_bc_scatter_mask ORs)
-        PlainSolver plain(M);
-        qmcp_hip_stats sum;
-        if (g.live.size() > 1) {
-            TRY(run_batches(c, g, plain, pm, sum));
-        } else {  // v is the one batch with reads, if any, and bc_starts / bc_ends hold its columns since step 3
-            start_sum(g, sum);
-            if (!g.live.empty()) TRY(solve_scatter_batch(c, v, plain, pm, sum, true, true));
-        }
+    plan.start(d.curve, a.H, d.top, 1, placed, placed, budget);
+    uint64_t kept_lo = 0;  // the reads of the best feasible probe
+    auto kept_bases = [&](uint64_t* pm, const qmcp_hip_stats&, uint64_t* count) -> int {
         unsigned long long got[qmcp::kMdWords] = {0, 0};
-        HIP_TRY(hipMemsetAsync(d_md, 0, sizeof(got), st));
-        HIP_TRY(hipEventRecord(fin.a, st));
-        if (whole_pairs) {
-            HIP_TRY(hipMemsetAsync(d_acc + qmcp::kBudgetKept, 0, sizeof(unsigned long long), st));
-            KernelSpan sp(c, "k_budget_finish");
-            qmcp::launch_budget_finish(st, d_ids, n64, pm, d_acc);
-        }
-        {
+        HIP_TRY(hipMemsetAsync(a.extra, 0, sizeof(got), st));
+        if (whole_pairs) HIP_TRY(hipMemsetAsync(a.acc + qmcp::kBudgetKept, 0, sizeof(unsigned long long), st));
+        TRY(timed.run([&] {
+            if (whole_pairs) {
+                KernelSpan sp(c, "k_budget_finish");
+                qmcp::launch_budget_finish(st, d_ids, n64, pm, a.acc);
+            }
             KernelSpan sp(c, "k_md_count");
-            qmcp::launch_md_count(st, pm, c->md_w.u32(), n64, d_md);
-        }
-        HIP_TRY(hipEventRecord(fin.b, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(got, d_md, sizeof(got), hipMemcpyDeviceToHost, st));
+            qmcp::launch_md_count(st, pm, c->md_w.u32(), n64, a.extra);
+        }));
+        HIP_TRY(hipMemcpyAsync(got, a.extra, sizeof(got), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        ms.ms_mean_depth += elapsed(fin.a, fin.b);
-        ms.ms_solves += sum.ms_total;
-        const uint64_t bases = got[qmcp::kMdBases];
-        plan.report(M, bases);
-        if (bases <= budget) {  // the best feasible probe so far: the other mask takes the next one
-            best = scratch;
-            scratch ^= 1;
-            best_stats = sum;
-            kept_lo = got[qmcp::kMdKept];
-        }
-    }
-    if (words) {
-        if (best < 0)
-            HIP_TRY(hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), st));
-        else if (masks[best] != d_mask)
-            HIP_TRY(hipMemcpyAsync(d_mask, masks[best], words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    collect_spans(c);
+        ms.ms_mean_depth += timed.total();
+        *count = got[qmcp::kMdBases];
+        if (*count <= budget) kept_lo = got[qmcp::kMdKept];
+        return QMCP_OK;
+    };
+    TRY(search_cap(c, plan, d_mask, c->bg_mask.u64(), words, probe, kept_bases, stats, &ms.ms_solves));
     ms.coverage = plan.lo;
     ms.n_kept = kept_lo;
     ms.kept_bases = plan.count_lo;
@@ -231,7 +147,6 @@ int solve_mean_depth_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
         ms.bound_above = plan.bound_hi;
     }
     ms.saturated = ms.n_kept == placed ? 1u : 0u;
-    if (stats) *stats = best_stats;
     if (mstats) *mstats = ms;
     return QMCP_OK;
 }

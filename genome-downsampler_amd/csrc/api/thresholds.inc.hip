@@ -3,9 +3,9 @@
 // solve keeps it (QMCP_THRESHOLD_NEVER where none does), and the reads kept at every coverage of the range.
 //   1. group_by_contig (api/by_contig.inc.hip): once per call; a call of one batch with reads gathers its columns once
 //   2. the thresholds filled with QMCP_THRESHOLD_NEVER, `seen` and the accumulators cleared
-//   3. M = coverage_lo, coverage_lo + 1, ...: a whole solve at M into the cleared probe mask (solve_scatter_batch on the
-//      gathered batch, or run_batches with a PlainSolver), k_thresholds_step, and the two accumulator words read back;
-//      the loop ends after the first M at which every placed read has a threshold, or at coverage_hi
+//   3. M = coverage_lo, coverage_lo + 1, ...: a whole solve at M into the cleared probe mask (ProbeSolve,
+//      api/cap_search.inc.hip), k_thresholds_step, and the two accumulator words read back; the loop ends after the
+//      first M at which every placed read has a threshold, or at coverage_hi
 //   4. k_thresholds_finish (the mates' minimum under the flag, the histogram), k_thresholds_counts, one copy of the counts
 // Buffers, all its own: th_mask (the probe mask; the grouping clears it, so a refused call leaves the caller's array
 // alone), th_seen, th_acc (ThresholdsAccWord words | histogram), th_thr (the host entry's thresholds).
@@ -55,11 +55,8 @@ int solve_thresholds_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     TRY(group_by_contig(c, d_starts, d_ends, d_ids, n64, lengths, n_contigs, c->th_mask.u64(), g));
     const uint64_t placed = g.offs[n_contigs];
     ts.reads_placed = placed;
-    BatchView v;
-    if (g.live.size() == 1) {  // its columns stay in bc_starts / bc_ends for every solve
-        g.view(g.live.front(), v);
-        TRY(gather_batch(c, v, d_starts, d_ends));
-    }
+    ProbeSolve probe{g};
+    if (g.live.size() == 1) TRY(probe.gather(c, g.live.front()));  // its columns stay in bc_starts / bc_ends for every solve
 
     // 2: nothing seen, every threshold NEVER (0xFFFF: both bytes 0xFF)
     if (words) HIP_TRY(hipMemsetAsync(c->th_seen.p, 0, words * sizeof(uint64_t), st));
@@ -70,8 +67,7 @@ int solve_thresholds_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)qmcp::kThWords * sizeof(unsigned long long), st));
 
     // 3: the solves
-    EventPair ev(c);
-    if (!ev.a || !ev.b) return fail(QMCP_EHIP, "event creation failed");
+    TimedLaunches timed{c};
     unsigned long long back[qmcp::kThWords] = {0, 0};
     qmcp_hip_stats last;
     std::memset(&last, 0, sizeof(last));
@@ -79,24 +75,15 @@ int solve_thresholds_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     for (;; ++M) {
         uint64_t* pm = c->th_mask.u64();
         if (words && M != lo) HIP_TRY(hipMemsetAsync(pm, 0, words * sizeof(uint64_t), st));  // (k_bc_scatter_mask ORs)
-        PlainSolver plain(M);
         qmcp_hip_stats sum;
-        if (g.live.size() > 1) {
-            TRY(run_batches(c, g, plain, pm, sum));
-        } else {
-            start_sum(g, sum);
-            if (!g.live.empty()) TRY(solve_scatter_batch(c, v, plain, pm, sum, true, true));
-        }
-        HIP_TRY(hipEventRecord(ev.a, st));
-        {
+        TRY(probe.solve(c, M, pm, sum));
+        TRY(timed.run([&] {
             KernelSpan sp(c, "k_thresholds_step");
             qmcp::launch_thresholds_step(st, pm, c->th_seen.u64(), n64, M, d_thr, d_acc);
-        }
-        HIP_TRY(hipEventRecord(ev.b, st));
-        HIP_TRY(hipGetLastError());
+        }));
         HIP_TRY(hipMemcpyAsync(back, d_acc, sizeof(back), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        ts.ms_thresholds += elapsed(ev.a, ev.b);
+        ts.ms_thresholds += timed.total();
         ts.ms_solves += sum.ms_total;
         ts.solves += 1;
         last = sum;
@@ -110,20 +97,17 @@ int solve_thresholds_on_device(qmcp_hip_ctx* c, const uint32_t* d_starts, const 
     const uint32_t n_bins = ts.top - lo + 1u;
     std::vector<unsigned long long> counts(n_bins, 0ull);
     HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)n_bins * sizeof(unsigned long long), st));
-    HIP_TRY(hipEventRecord(ev.a, st));
-    {
-        KernelSpan sp(c, "k_thresholds_finish");
-        qmcp::launch_thresholds_finish(st, d_ids, n64, whole_pairs, lo, n_bins, d_thr, d_hist);
-    }
-    {
+    TRY(timed.run([&] {
+        {
+            KernelSpan sp(c, "k_thresholds_finish");
+            qmcp::launch_thresholds_finish(st, d_ids, n64, whole_pairs, lo, n_bins, d_thr, d_hist);
+        }
         KernelSpan sp(c, "k_thresholds_counts");
         qmcp::launch_thresholds_counts(st, d_hist, n_bins);
-    }
-    HIP_TRY(hipEventRecord(ev.b, st));
-    HIP_TRY(hipGetLastError());
+    }));
     HIP_TRY(hipMemcpyAsync(counts.data(), d_hist, (size_t)n_bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    ts.ms_thresholds += elapsed(ev.a, ev.b);
+    ts.ms_thresholds += timed.total();
     collect_spans(c);
     ts.n_kept = counts[n_bins - 1];
     if (counts_out && counts_capacity) {  // (no threshold lies above top: the counts stay there)

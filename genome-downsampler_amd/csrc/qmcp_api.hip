@@ -129,6 +129,7 @@
 #include "api/fragments.inc.hip"
 #include "api/ceiling.inc.hip"
 #include "api/proportional.inc.hip"
+#include "api/cap_search.inc.hip"
 #include "api/budget.inc.hip"
 #include "api/mean_depth.inc.hip"
 #include "api/thresholds.inc.hip"

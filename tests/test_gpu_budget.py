@@ -175,11 +175,19 @@ def test_edges(pkg, oracle, solver):
     assert bm.Model(oracle, s, e, ids, lengths, 25).count(25) < model.placed      # (so saturated == 0 was exercised)
 
 
+def launches(solver, name):
+    return solver.kernel_times().get(name, (0, 0.0))[0]
+
+
 def test_several_batches(pkg, oracle, solver, mixed):
     """two empty contigs as long as one solver call allows between case 1's contigs cut the call into several batches,
     three of them with reads: every probe then runs over all of them, and the depth histogram adds up across them.  The
-    model sees the two at length 1: a contig without reads decides nothing"""
+    model sees the two at length 1: a contig without reads decides nothing.  Then one such contig in front of the only
+    contig with reads: two batches, the second the one with reads -- its columns are gathered once, for the depth, and
+    every probe reuses them; with several batches with reads (two of seed 3's, three of seed 4's) the depth and every probe
+    gather each of them"""
     huge = (1 << 31) - 3
+    cases = []
     for seed, flags in ((3, 0), (4, pkg.BUDGET_WHOLE_PAIRS)):
         s, e, ids, lengths, _ = mixed[seed]
         n = s.size & ~1
@@ -188,15 +196,36 @@ def test_several_batches(pkg, oracle, solver, mixed):
         assert len(set(ids[on].tolist())) >= 3                                    # reads on either side of both
         ids[on] = np.array([0, 2, 3, 5], np.uint32)[ids[on]]
         wide = np.array([lengths[0], huge, lengths[1], lengths[2], huge, lengths[3]], np.uint32)
+        live = sum(bool(np.isin(ids, group).any()) for group in ([0], [2, 3], [5]))   # seed 3: two, seed 4: three
+        assert live == (3 if seed == 4 else 2)
+        cases.append((s, e, ids, wide, [1, 4], live, flags))
+    rng = np.random.default_rng(91)
+    L, n = 3000, 400
+    span = rng.integers(1, 120, n)
+    s = (rng.random(n) * (L - span + 1)).astype(np.uint32)
+    e = (s + span - 1).astype(np.uint32)
+    ids = np.where(rng.random(n) < 0.04, NO_CONTIG, 1).astype(np.uint32)
+    assert 0 < np.count_nonzero(ids == NO_CONTIG) < n // 4
+    for flags in (0, pkg.BUDGET_WHOLE_PAIRS):
+        cases.append((s, e, ids, np.array([huge, L], np.uint32), [0], 1, flags))
+    for s, e, ids, wide, long_ones, live, flags in cases:
         small = wide.copy()
-        small[[1, 4]] = 1
+        small[long_ones] = 1
         model = bm.Model(oracle, s, e, ids, small, 64, whole_pairs=bool(flags))
         for budget in (model.placed // 5, model.placed // 2, model.placed):
-            got, M, bs, curve = solver.solve_budget(s, e, ids, wide, 64, budget_reads=budget, flags=flags, curve=True)
+            solver.set_profiling(True)
+            try:
+                got, M, bs, curve = solver.solve_budget(s, e, ids, wide, 64, budget_reads=budget, flags=flags, curve=True)
+                gathers, scatters = launches(solver, "k_bc_gather"), launches(solver, "k_bc_scatter_mask")
+            finally:
+                solver.set_profiling(False)
             assert M in model.answers(budget) and (flags or model.answers(budget) == [M])
             check_answer(model, budget, got, M, bs, curve)
-            st = solver.last_stats
-            assert st.n_contigs == 6 and st.total_length == int(wide.astype(np.int64).sum()) and st.n_kept <= bs.n_kept
+            st = solver.last_stats                                                # the probe's at M*: zeros for M* == 0
+            assert (st.n_contigs, st.total_length) == ((wide.size, int(wide.astype(np.int64).sum())) if M else (0, 0))
+            assert st.n_kept <= bs.n_kept
+            assert gathers == (1 if live == 1 else live * (1 + bs.probes)), (live, bs.probes, gathers)
+            assert scatters == live * bs.probes, (live, bs.probes, scatters)
 
 
 # ------------------------------------------------------------------------------------------ 6: the device entry

@@ -25,6 +25,10 @@ def popcount(mask):
     return int(np.unpackbits(np.ascontiguousarray(mask).view(np.uint8)).sum())
 
 
+def launches(solver, name):
+    return solver.kernel_times().get(name, (0, 0.0))[0]
+
+
 def merged_regions(model):
     """the maximal runs of region positions, contig by contig (regions that touch or overlap are one)"""
     runs, at = 0, 0
@@ -224,8 +228,12 @@ def test_several_batches(pkg, oracle, solver, mixed):
     three of them with reads, and the regions lie on contigs of different batches: the region histogram adds up across
     them.  Contig 2 has a region that ends on its last position and contig 3, in the same batch, one that starts at 0:
     two regions on the batch's axis.  The model sees the two long contigs at length 1: a contig without reads decides
-    nothing, and their one region is position 0"""
+    nothing, and their one region is position 0.  Then one such contig, with that region, in front of the only contig
+    with reads: two batches, the second the one with reads -- its regions start behind the first's in the table, and its
+    columns are gathered once, for the depth, and reused by every probe; with several batches with reads (two of seed
+    3's, three of seed 4's) the depth and every probe gather each of them"""
     huge = (1 << 31) - 3
+    cases = []
     for seed, flags in ((3, 0), (4, pkg.MEAN_DEPTH_WHOLE_PAIRS)):
         s, e, ids, lengths, _, _ = mixed(seed, False, pairs=True)
         ids = ids.copy()
@@ -233,24 +241,54 @@ def test_several_batches(pkg, oracle, solver, mixed):
         assert len(set(ids[on].tolist())) >= 3                                    # reads on either side of both
         ids[on] = np.array([0, 2, 3, 5], np.uint32)[ids[on]]
         wide = np.array([lengths[0], huge, lengths[1], lengths[2], huge, lengths[3]], np.uint32)
-        small = wide.copy()
-        small[[1, 4]] = 1
         w = wide.astype(np.int64)
         regions = (np.array([0, 2, 3, 5, 6, 7, 9], np.uint32),
                    np.array([w[0] - 60, 5, 0, w[2] - 100, 20, 0, 0, 3, w[5] // 2], np.uint32),
                    np.array([w[0] - 1, 40, 0, w[2] - 1, 30, w[3] // 2, 0, 9, w[5] + 7], np.uint32))
+        live = sum(bool(np.isin(ids, group).any()) for group in ([0], [2, 3], [5]))   # seed 3: two, seed 4: three
+        assert live == (3 if seed == 4 else 2)
+        cases.append((s, e, ids, wide, [1, 4], regions, live, flags))
+    rng = np.random.default_rng(91)
+    L, n = 3000, 400
+    span = rng.integers(1, 120, n)
+    s = (rng.random(n) * (L - span + 1)).astype(np.uint32)
+    e = (s + span - 1).astype(np.uint32)
+    ids = np.where(rng.random(n) < 0.04, NO_CONTIG, 1).astype(np.uint32)
+    assert 0 < np.count_nonzero(ids == NO_CONTIG) < n // 4
+    regions = (np.array([0, 1, 4], np.uint32), np.array([0, 700, 40, L - 90], np.uint32),
+               np.array([0, 1500, 300, L + 7], np.uint32))
+    for flags in (0, pkg.MEAN_DEPTH_WHOLE_PAIRS):
+        cases.append((s, e, ids, np.array([huge, L], np.uint32), [0], regions, 1, flags))
+
+    def profiled(reads, live, **kw):
+        solver.set_profiling(True)
+        try:
+            out = solver.solve_mean_depth(*reads, 64, **kw)
+            gathers, scatters = launches(solver, "k_bc_gather"), launches(solver, "k_bc_scatter_mask")
+        finally:
+            solver.set_profiling(False)
+        probes = out[2].probes
+        assert gathers == (1 if live == 1 else live * (1 + probes)), (live, probes, gathers)
+        assert scatters == live * probes, (live, probes, scatters)
+        return out
+
+    for s, e, ids, wide, long_ones, regions, live, flags in cases:
+        small = wide.copy()
+        small[long_ones] = 1
+        w = wide.astype(np.int64)
         model = mm.Model(oracle, s, e, ids, small, 64, regions=regions, whole_pairs=bool(flags))
-        assert model.inside[small[:3].sum() - 1] and model.inside[small[:3].sum()]  # adjacent on the axis, two contigs
+        if wide.size == 6:
+            assert model.inside[small[:3].sum() - 1] and model.inside[small[:3].sum()]  # adjacent on the axis, two contigs
         total = model.total_bases
         for budget in (total // 5, total // 2, total):
-            got, M, ms, curve = solver.solve_mean_depth(s, e, ids, wide, 64, budget_bases=budget, flags=flags, curve=True,
-                                                        **table_args(regions))
+            got, M, ms, curve = profiled((s, e, ids, wide), live, budget_bases=budget, flags=flags, curve=True,
+                                         **table_args(regions))
             assert M in model.answers(budget) and (flags or model.answers(budget) == [M])
             check_answer(model, budget, got, M, ms, curve, regions)
-            st = solver.last_stats
-            assert st.n_contigs == 6 and st.total_length == int(w.sum()) and st.n_kept <= ms.n_kept
+            st = solver.last_stats                                                # the probe's at M*: zeros for M* == 0
+            assert (st.n_contigs, st.total_length) == ((wide.size, int(w.sum())) if M else (0, 0)) and st.n_kept <= ms.n_kept
         # without a table every position counts: the long contigs' too
-        got, M, ms = solver.solve_mean_depth(s, e, ids, wide, 64, mean_depth=1e-6, flags=flags)
+        got, M, ms = profiled((s, e, ids, wide), live, mean_depth=1e-6, flags=flags)
         assert ms.positions == int(w.sum()) and ms.budget == int(np.floor(1e-6 * int(w.sum())))
         assert M in mm.Model(oracle, s, e, ids, small, 64, whole_pairs=bool(flags)).answers(int(ms.budget))
 

@@ -123,7 +123,9 @@ def test_one_read_length_under_every_forced_route(solver, one_length, route):
 def test_several_batches(pkg, oracle, solver):
     """two empty contigs as long as one solver call allows between the others cut the call into several batches, three
     of them with reads: every coverage then runs over all of them.  The model sees the two at length 1: a contig without
-    reads decides nothing.  Depth at most 12"""
+    reads decides nothing.  Then one such contig in front of the only contig with reads: two batches, the second the
+    one with reads -- its columns are gathered once and every coverage's solve reuses them; with several batches with
+    reads every coverage gathers each of them.  Depth at most 12"""
     huge = (1 << 31) - 3
     rng = np.random.default_rng(77)
     lengths = np.array([3000, 1800, 2400, 900], np.int64)
@@ -135,15 +137,31 @@ def test_several_batches(pkg, oracle, solver):
     on = ids != NO_CONTIG
     ids[on] = np.array([0, 2, 3, 5], np.uint32)[ids[on]]
     wide = np.array([lengths[0], huge, lengths[1], lengths[2], huge, lengths[3]], np.uint32)
-    small = wide.copy()
-    small[[1, 4]] = 1
-    assert bm.depth(s, e, ids, small).max() <= 12
-    for flags in (0, pkg.THRESHOLDS_WHOLE_PAIRS):
-        want = tm.Thresholds(oracle, s, e, ids, small, 1, 12, whole_pairs=bool(flags))
-        thr, ts, counts = solver.solve_thresholds(s, e, ids, wide, 12, flags=flags, counts=True)
-        check(want, thr, ts, counts)
-        st = solver.last_stats
-        assert st.n_contigs == 6 and st.total_length == int(wide.astype(np.int64).sum())
+    cases = [(s, e, ids, wide, [1, 4], 3)]
+    L, n = 3000, 400
+    span = rng.integers(1, 60, n)
+    s = (rng.random(n) * (L - span + 1)).astype(np.uint32)
+    e = (s + span - 1).astype(np.uint32)
+    ids = np.where(rng.random(n) < 0.04, NO_CONTIG, 1).astype(np.uint32)
+    assert 0 < np.count_nonzero(ids == NO_CONTIG) < n // 4
+    cases.append((s, e, ids, np.array([huge, L], np.uint32), [0], 1))
+    for s, e, ids, wide, long_ones, live in cases:
+        small = wide.copy()
+        small[long_ones] = 1
+        assert bm.depth(s, e, ids, small).max() <= 12
+        for flags in (0, pkg.THRESHOLDS_WHOLE_PAIRS):
+            want = tm.Thresholds(oracle, s, e, ids, small, 1, 12, whole_pairs=bool(flags))
+            solver.set_profiling(True)
+            try:
+                thr, ts, counts = solver.solve_thresholds(s, e, ids, wide, 12, flags=flags, counts=True)
+                kt = solver.kernel_times()
+            finally:
+                solver.set_profiling(False)
+            check(want, thr, ts, counts)
+            st = solver.last_stats
+            assert st.n_contigs == wide.size and st.total_length == int(wide.astype(np.int64).sum())
+            assert kt["k_bc_gather"][0] == (1 if live == 1 else live * ts.solves), (live, ts.solves, kt["k_bc_gather"])
+            assert kt["k_bc_scatter_mask"][0] == live * ts.solves, (live, ts.solves, kt["k_bc_scatter_mask"])
 
 
 def test_edges(pkg, oracle, solver):
