@@ -21,6 +21,9 @@ class QuasiMcpHipQualitySolver : public QuasiMcpHipSolver {
 
     const qmcp_hip_quality_stats& last_quality_stats() const { return qstats_; }
 
+   protected:
+    const char* name() const override { return "quasi-mcp-hip-quality"; }
+
    private:
     qmcp_hip_quality_stats qstats_{};
 };

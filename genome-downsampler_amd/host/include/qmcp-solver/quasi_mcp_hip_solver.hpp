@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "qmcp-solver/adapter_columns.hpp"
 #include "qmcp-solver/solver.hpp"
 #include "qmcp_hip.h"
 
@@ -138,6 +139,8 @@ class QuasiMcpHipSolver : public Solver {
     // without find_pairs.  std::invalid_argument for a BamApi without a budget and for what the library refuses
     std::unique_ptr<Solution> solve_budget(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_budget_stats& last_budget_stats() const { return bgstats_; }
+    // S(M) = the bases any answer at coverage M must hold, M = 0 .. last_budget_stats().curve_entries - 1
+    const std::vector<std::uint64_t>& last_budget_curve() const { return budget_curve_; }
     // Coverage thresholds for the reads of a BamApi built with BamApiConfig::thresholds_hi: one
     // qmcp_hip_solve_thresholds_host call with QMCP_THRESHOLDS_WHOLE_PAIRS over thresholds_lo .. thresholds_hi.  The
     // Solution holds the reads with a threshold (whole pairs already -- the caller writes them without find_pairs),
@@ -163,8 +166,6 @@ class QuasiMcpHipSolver : public Solver {
     // BamApi without replicates and for what the library refuses
     std::vector<std::uint8_t> solve_replicates(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_replicates_stats& last_replicates_stats() const { return rpstats_; }
-    // S(M) = the bases any answer at coverage M must hold, M = 0 .. last_budget_stats().curve_entries - 1
-    const std::vector<std::uint64_t>& last_budget_curve() const { return budget_curve_; }
     // Template-aware downsampling for a BamApi built with BamApiConfig::template_aware: qmcp_hip_solve_templates_host on
     // its segments under its template_stages (empty: the default schedule).  Returns the ids of the records whose
     // template is kept (ascending) -- the caller writes them with BamApi::write_records, without find_pairs.
@@ -193,7 +194,8 @@ class QuasiMcpHipSolver : public Solver {
     float last_expand_ms() const { return ms_expand_; }
     float last_solve_call_ms() const { return ms_solve_call_; }
 
-   protected:  // (QuasiMcpHipQualitySolver shares the context and the expansion)
+   protected:  // (QuasiMcpHipQualitySolver shares the helpers and the state)
+    // what solve() hands over to, by what the reads carry
     std::unique_ptr<Solution> solve_by_contig(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
                                               std::chrono::steady_clock::time_point t0);
     // the BamApi holds target regions (BamApiConfig::targets_filepath): qmcp_hip_solve_targets_host, with the reads'
@@ -201,13 +203,56 @@ class QuasiMcpHipSolver : public Solver {
     std::unique_ptr<Solution> solve_targets(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
                                             const bam_api::TargetRegions& targets, bool with_qualities,
                                             std::chrono::steady_clock::time_point t0);
-    qmcp_hip_target_stats tstats_{};
-    qmcp_hip_ladder_stats lstats_{};
     std::unique_ptr<Solution> solve_stratified(std::uint32_t required_cover, const bam_api::SOAPairedReads& reads,
                                                bam_api::Stratify by, std::chrono::steady_clock::time_point t0);
+
+    // The steps every entry shares.  The reference's GPU solver has no error channel: a device failure ends in
+    // std::terminate(), and so does die(), under the solver's name
+    virtual const char* name() const { return "quasi-mcp-hip"; }
+    [[noreturn]] void die(const char* what, int rc) const;
+    // the two return-code policies: any failure ends the process; or QMCP_EINVAL / QMCP_ERANGE -- what the library
+    // refuses in the arguments -- throw std::invalid_argument with its message and anything else ends the process
+    void ok_or_die(const char* what, int rc) const;
+    void ok_or_throw(const char* what, int rc) const;
+    qmcp_hip_ctx* context();  // created on first use, reused across solves; die() on failure
+    // the reads' 64-bit coordinates as the uint32 columns of the C ABI (narrow_columns, by the contig ids when the
+    // reads have them) and the number of placed reads; die("narrowing a coordinate") on a coordinate above UINT32_MAX
+    struct Columns {
+        std::vector<std::uint32_t> starts, ends;
+        std::uint64_t placed = 0;
+    };
+    Columns narrowed(const bam_api::SOAPairedReads& reads) const;
+    static bool one_contig_id_each(const bam_api::SOAPairedReads& reads);
+    // std::invalid_argument(message) unless the BamApi is `configured` for the entry and holds per-reference reads with
+    // one contig id each
+    static void need_per_reference(bool configured, const bam_api::SOAPairedReads& reads, const char* message);
+    // a region table in CSR form against n_refs references: std::invalid_argument for a table of other references and
+    // for arrays shorter than the offsets say
+    static void check_regions(const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
+                              const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps,
+                              std::size_t n_refs);
+    // the context's keep mask of n reads as the ascending Solution, sized by `upper` kept reads at most; stamps
+    // ms_expand_ and, from t0, ms_solve_call_
+    std::unique_ptr<Solution> expand(std::uint64_t n, std::uint64_t upper, std::chrono::steady_clock::time_point t0);
+    // ... with the upper bound of a solve that left stats_.n_kept: twice that under complete_pairs_
+    std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
+    // the end of an entry that solved into `mask`: no breakdown, mates completed if asked, expand_kept
+    std::unique_ptr<Solution> finish(std::vector<std::uint64_t>& mask, std::uint64_t n,
+                                     std::chrono::steady_clock::time_point t0);
+
+    qmcp_hip_ctx* ctx_ = nullptr;
+    int device_ = 0;
+    std::vector<int> devices_{0};
+    bool complete_pairs_ = false;
+    qmcp_hip_stats stats_{};
+    qmcp_hip_host_breakdown breakdown_{};
+    float ms_expand_ = 0.f, ms_solve_call_ = 0.f;
+    // what the last call of each entry left, in the order of the entries above
+    qmcp_hip_ladder_stats lstats_{};
     std::vector<std::uint32_t> stratum_caps_;
     std::vector<qmcp_hip_stratum_row> stratum_rows_;
     qmcp_hip_dedup_stats dstats_{};
+    std::vector<std::uint64_t> dedup_hist_;
     qmcp_hip_start_cap_stats scstats_{};
     std::vector<std::uint64_t> start_cap_hist_;
     qmcp_hip_profile_stats pstats_{};
@@ -215,25 +260,17 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_ceiling_stats clstats_{};
     qmcp_hip_proportional_stats ppstats_{};
     qmcp_hip_budget_stats bgstats_{};
+    std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_thresholds_stats thstats_{};
     std::vector<std::uint16_t> thresholds_;
     std::vector<std::uint64_t> threshold_counts_;
-    qmcp_hip_replicates_stats rpstats_{};
-    std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_mean_depth_stats mdstats_{};
     std::vector<std::uint64_t> mean_depth_curve_;
+    qmcp_hip_replicates_stats rpstats_{};
     qmcp_hip_template_stats tpstats_{};
     qmcp_hip_template_profile_stats tqstats_{};
     qmcp_hip_fragment_stats frstats_{};
-    std::vector<std::uint64_t> dedup_hist_;
-    std::unique_ptr<Solution> expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0);
-    qmcp_hip_ctx* ctx_ = nullptr;  // created on first solve, reused across solves
-    int device_ = 0;
-    std::vector<int> devices_{0};
-    bool complete_pairs_ = false;
-    qmcp_hip_stats stats_{};
-    qmcp_hip_host_breakdown breakdown_{};
-    float ms_expand_ = 0.f, ms_solve_call_ = 0.f;
+    qmcp_hip_target_stats tstats_{};
 };
 
 }  // namespace qmcp

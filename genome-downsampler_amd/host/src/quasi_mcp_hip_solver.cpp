@@ -10,24 +10,112 @@
 #include <vector>
 
 namespace qmcp {
-namespace {
 
-// The reference's GPU solver has no error channel: any device failure ends in
-// std::terminate() (libs/qmcp-solver/include/qmcp-solver/cuda_helpers.cuh:13-22).
-// The C ABI returns codes; the adapter restores the reference behaviour.
-[[noreturn]] void die(const char* what, int rc) {
-    std::fprintf(stderr, "[ERROR] quasi-mcp-hip: %s failed (%d): %s\n", what, rc,
-                 qmcp_hip_last_error());
-    std::terminate();
-}
-
-}  // namespace
+static_assert(sizeof(bam_api::Index) == sizeof(std::uint64_t), "Index is size_t on an LP64 host (read.hpp:11)");
+static_assert(sizeof(bam_api::ReadIndex) == sizeof(std::uint64_t), "ReadIndex is size_t on an LP64 host");
+static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
 
 QuasiMcpHipSolver::~QuasiMcpHipSolver() {
     if (ctx_ != nullptr) qmcp_hip_destroy(ctx_);
 }
 
 void QuasiMcpHipSolver::set_device(int device) { device_ = device; }
+
+// ------------------------------------------------------------------------------------------ the shared steps
+
+// The reference's GPU solver has no error channel: any device failure ends in
+// std::terminate() (libs/qmcp-solver/include/qmcp-solver/cuda_helpers.cuh:13-22).
+// The C ABI returns codes; the adapter restores the reference behaviour.
+void QuasiMcpHipSolver::die(const char* what, int rc) const {
+    std::fprintf(stderr, "[ERROR] %s: %s failed (%d): %s\n", name(), what, rc, qmcp_hip_last_error());
+    std::terminate();
+}
+
+void QuasiMcpHipSolver::ok_or_die(const char* what, int rc) const {
+    if (rc != QMCP_OK) die(what, rc);
+}
+
+void QuasiMcpHipSolver::ok_or_throw(const char* what, int rc) const {
+    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
+    ok_or_die(what, rc);
+}
+
+qmcp_hip_ctx* QuasiMcpHipSolver::context() {
+    if (ctx_ == nullptr) ok_or_die("qmcp_hip_create", qmcp_hip_create(device_, &ctx_));
+    return ctx_;
+}
+
+QuasiMcpHipSolver::Columns QuasiMcpHipSolver::narrowed(const bam_api::SOAPairedReads& reads) const {
+    const std::size_t n = reads.start_inds.size();
+    Columns c;
+    c.starts.resize(n);
+    c.ends.resize(n);
+    const Narrowed r = narrow_columns(reads.start_inds.data(), reads.end_inds.data(),
+                                      reads.has_contig_ids() ? reads.contig_ids.data() : nullptr, n, c.starts.data(),
+                                      c.ends.data());
+    if (r.bad != n) die("narrowing a coordinate", QMCP_ERANGE);
+    c.placed = r.placed;
+    return c;
+}
+
+bool QuasiMcpHipSolver::one_contig_id_each(const bam_api::SOAPairedReads& reads) {
+    return reads.has_contig_ids() && reads.contig_ids.size() == reads.start_inds.size();
+}
+
+void QuasiMcpHipSolver::need_per_reference(bool configured, const bam_api::SOAPairedReads& reads, const char* message) {
+    if (!configured || !one_contig_id_each(reads)) throw std::invalid_argument(message);
+}
+
+void QuasiMcpHipSolver::check_regions(const std::vector<std::uint32_t>& offsets, const std::vector<std::uint32_t>& starts,
+                                      const std::vector<std::uint32_t>& ends, const std::vector<std::uint32_t>& caps,
+                                      std::size_t n_refs) {
+    if (offsets.size() != n_refs + 1) throw std::invalid_argument("cap regions of other references");
+    if (starts.size() < offsets.back() || ends.size() < offsets.back() || caps.size() < offsets.back())
+        throw std::invalid_argument("cap region arrays are shorter than their offsets say");
+}
+
+// ascending ReadIndex, as obtain_sequence produces (quasi_mcp_cpu_max_flow_solver.cpp:93-97): expanded from
+// the keep mask on the device (popcounts, scan, scatter) and copied out -- 5 % of the reads at cfg4's depth
+std::unique_ptr<Solution> QuasiMcpHipSolver::expand(std::uint64_t n, std::uint64_t upper,
+                                                    std::chrono::steady_clock::time_point t0) {
+    const auto t1 = std::chrono::steady_clock::now();
+    auto kept = std::make_unique<Solution>();
+    kept->resize(upper);
+    std::uint64_t n_out = 0;
+    ok_or_die("qmcp_hip_kept_indices_host",
+              qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out));
+    kept->resize(n_out);
+    const auto t2 = std::chrono::steady_clock::now();
+    ms_expand_ = std::chrono::duration<float, std::milli>(t2 - t1).count();
+    ms_solve_call_ = std::chrono::duration<float, std::milli>(t2 - t0).count();
+    return kept;
+}
+
+std::unique_ptr<Solution> QuasiMcpHipSolver::expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0) {
+    return expand(n, complete_pairs_ ? std::min<std::uint64_t>(n, 2 * stats_.n_kept) : stats_.n_kept, t0);
+}
+
+std::unique_ptr<Solution> QuasiMcpHipSolver::finish(std::vector<std::uint64_t>& mask, std::uint64_t n,
+                                                    std::chrono::steady_clock::time_point t0) {
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_)  // (leaves the completed mask in the context)
+        ok_or_die("qmcp_hip_complete_pairs_host", qmcp_hip_complete_pairs_host(ctx_, mask.data(), n));
+    return expand_kept(n, t0);
+}
+
+namespace {
+
+std::vector<std::uint64_t> empty_mask(std::size_t n) { return std::vector<std::uint64_t>((n + 63) / 64, 0); }
+
+std::uint32_t n_contigs(const bam_api::SOAPairedReads& reads) { return (std::uint32_t)reads.contig_lengths.size(); }
+
+float ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ solve() and its routes
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
                                                    bam_api::BamApi& bam_api) {
@@ -39,12 +127,7 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
     const std::size_t n = reads.start_inds.size();
     constexpr std::size_t kMax = std::numeric_limits<std::uint32_t>::max();
     if (reads.ref_genome_length > kMax && !reads.has_contig_ids()) die("narrowing ref_genome_length", QMCP_ERANGE);
-    static_assert(sizeof(bam_api::Index) == sizeof(std::uint64_t), "Index is size_t on an LP64 host (read.hpp:11)");
-
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
+    context();
 
     if (reads.has_strata()) return solve_stratified(required_cover, reads, bam_api.stratify_by(), t0);
     if (bam_api.has_targets()) return solve_targets(required_cover, reads, bam_api.get_targets(), false, t0);
@@ -57,16 +140,13 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve(std::uint32_t required_cover,
     // complete_pairs needs the mask on the host side of the ABI; otherwise it stays on the device and only
     // the Solution comes back
     std::vector<std::uint64_t> mask;
-    if (complete_pairs_) mask.assign((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_host64(ctx_, reinterpret_cast<const std::uint64_t*>(reads.start_inds.data()),
-                                   reinterpret_cast<const std::uint64_t*>(reads.end_inds.data()), n, offsets,
-                                   &length, 1, required_cover, complete_pairs_ ? mask.data() : nullptr, &stats_,
-                                   &breakdown_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_host64", rc);
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
+    if (complete_pairs_) mask = empty_mask(n);
+    ok_or_die("qmcp_hip_solve_host64",
+              qmcp_hip_solve_host64(ctx_, reinterpret_cast<const std::uint64_t*>(reads.start_inds.data()),
+                                    reinterpret_cast<const std::uint64_t*>(reads.end_inds.data()), n, offsets, &length, 1,
+                                    required_cover, complete_pairs_ ? mask.data() : nullptr, &stats_, &breakdown_));
+    // (the library's breakdown stands: not finish())
+    if (complete_pairs_) ok_or_die("qmcp_hip_complete_pairs_host", qmcp_hip_complete_pairs_host(ctx_, mask.data(), n));
     return expand_kept(n, t0);
 }
 
@@ -77,25 +157,14 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_by_contig(std::uint32_t requi
                                                              const bam_api::SOAPairedReads& reads,
                                                              std::chrono::steady_clock::time_point t0) {
     const std::size_t n = reads.start_inds.size();
-    if (reads.contig_ids.size() != n) die("per-reference reads without one contig id each", QMCP_EINVAL);
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_by_contig_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                           reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                           required_cover, mask.data(), &stats_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_by_contig_host", rc);
-    breakdown_ = qmcp_hip_host_breakdown{};
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
-    return expand_kept(n, t0);
+    if (!one_contig_id_each(reads)) die("per-reference reads without one contig id each", QMCP_EINVAL);
+    const Columns c = narrowed(reads);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_die("qmcp_hip_solve_by_contig_host",
+              qmcp_hip_solve_by_contig_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                            reads.contig_lengths.data(), n_contigs(reads), required_cover, mask.data(),
+                                            &stats_));
+    return finish(mask, n, t0);
 }
 
 // STRAND: the two strands share M, the forward strand taking the odd one; every other stratification brings every
@@ -116,29 +185,18 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_stratified(std::uint32_t requ
                                                               const bam_api::SOAPairedReads& reads, bam_api::Stratify by,
                                                               std::chrono::steady_clock::time_point t0) {
     const std::size_t n = reads.start_inds.size();
-    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("strata without one contig id per read", QMCP_EINVAL);
+    if (!one_contig_id_each(reads)) die("strata without one contig id per read", QMCP_EINVAL);
     if (reads.strata.size() != n) die("stratified reads without one stratum each", QMCP_EINVAL);
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    const Columns c = narrowed(reads);
     stratum_caps_ = stratum_caps(required_cover, by, reads.stratum_names.size());
     stratum_rows_.assign(stratum_caps_.size(), qmcp_hip_stratum_row{});
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_stratified_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), reads.strata.data(),
-                                            n, reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                            stratum_caps_.data(), (std::uint32_t)stratum_caps_.size(), mask.data(),
-                                            stratum_rows_.data(), &stats_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_stratified_host", rc);
-    breakdown_ = qmcp_hip_host_breakdown{};
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
-    return expand_kept(n, t0);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_die("qmcp_hip_solve_stratified_host",
+              qmcp_hip_solve_stratified_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(),
+                                             reads.strata.data(), n, reads.contig_lengths.data(), n_contigs(reads),
+                                             stratum_caps_.data(), (std::uint32_t)stratum_caps_.size(), mask.data(),
+                                             stratum_rows_.data(), &stats_));
+    return finish(mask, n, t0);
 }
 
 // Per-reference reads with target regions (BamApiConfig::targets_filepath): coverage capped inside the regions only,
@@ -148,74 +206,44 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_targets(std::uint32_t require
                                                            const bam_api::TargetRegions& targets, bool with_qualities,
                                                            std::chrono::steady_clock::time_point t0) {
     const std::size_t n = reads.start_inds.size();
-    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("target regions without one contig id per read", QMCP_EINVAL);
+    if (!one_contig_id_each(reads)) die("target regions without one contig id per read", QMCP_EINVAL);
     if (with_qualities && reads.qualities.size() != n) die("reads without one quality each", QMCP_EINVAL);
     if (targets.offsets.size() != reads.contig_lengths.size() + 1) die("target regions of other references", QMCP_EINVAL);
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_targets_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(),
-                                         with_qualities ? reads.qualities.data() : nullptr, n,
-                                         reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                         targets.offsets.data(), targets.starts.data(), targets.ends.data(),
-                                         targets.padding, required_cover,
-                                         targets.keep_off_target ? QMCP_TARGETS_KEEP_OFF_TARGET : 0u, mask.data(),
-                                         &stats_, &tstats_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_targets_host", rc);
+    const Columns c = narrowed(reads);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_die("qmcp_hip_solve_targets_host",
+              qmcp_hip_solve_targets_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(),
+                                          with_qualities ? reads.qualities.data() : nullptr, n,
+                                          reads.contig_lengths.data(), n_contigs(reads), targets.offsets.data(),
+                                          targets.starts.data(), targets.ends.data(), targets.padding, required_cover,
+                                          targets.keep_off_target ? QMCP_TARGETS_KEEP_OFF_TARGET : 0u, mask.data(),
+                                          &stats_, &tstats_));
     if (targets.keep_off_target) stats_.n_kept += tstats_.reads_off_target;  // (expand_kept sizes the Solution by it)
-    breakdown_ = qmcp_hip_host_breakdown{};
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
-    return expand_kept(n, t0);
+    return finish(mask, n, t0);
 }
+
+// ------------------------------------------------------------------------------------------ the entries by mode
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_dedup(std::uint32_t required_cover, bam_api::BamApi& bam_api,
                                                          std::uint32_t hist_bins) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.dedup() || !reads.has_contig_ids() || reads.contig_ids.size() != n || reads.strata.size() != n)
-        throw std::invalid_argument("duplicate-aware downsampling needs a BamApi built with BamApiConfig::dedup");
+    need_per_reference(bam_api.dedup() && reads.strata.size() == n, reads,
+                       "duplicate-aware downsampling needs a BamApi built with BamApiConfig::dedup");
     if (reads.qualities.size() != n) throw std::invalid_argument("reads without one quality each");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
+    context();
+    const Columns c = narrowed(reads);
     dedup_hist_.assign(hist_bins, 0);
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    const int rc = qmcp_hip_solve_dedup_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), reads.strata.data(),
-                                             reads.qualities.data(), n, reads.contig_lengths.data(),
-                                             (std::uint32_t)reads.contig_lengths.size(), required_cover,
-                                             QMCP_DEDUP_PAIRS | QMCP_DEDUP_COMPLETE_PAIRS, mask.data(), nullptr,
-                                             hist_bins ? dedup_hist_.data() : nullptr, hist_bins, &stats_, &dstats_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_dedup_host", rc);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_die("qmcp_hip_solve_dedup_host",
+              qmcp_hip_solve_dedup_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), reads.strata.data(),
+                                        reads.qualities.data(), n, reads.contig_lengths.data(), n_contigs(reads),
+                                        required_cover, QMCP_DEDUP_PAIRS | QMCP_DEDUP_COMPLETE_PAIRS, mask.data(), nullptr,
+                                        hist_bins ? dedup_hist_.data() : nullptr, hist_bins, &stats_, &dstats_));
     breakdown_ = qmcp_hip_host_breakdown{};
     // the context holds the completed mask: at most two reads per read the solve kept
-    auto kept = std::make_unique<Solution>();
-    const std::uint64_t upper = std::min<std::uint64_t>(n, 2 * stats_.n_kept);
-    kept->resize(upper);
-    std::uint64_t n_out = 0;
-    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
-    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
-    kept->resize(n_out);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return kept;
+    return expand(n, std::min<std::uint64_t>(n, 2 * stats_.n_kept), t0);
 }
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_start_cap(std::uint32_t required_cover, bam_api::BamApi& bam_api,
@@ -224,37 +252,20 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_start_cap(std::uint32_t requi
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
     const bool by_strand = bam_api.start_cap_by_strand();
-    if (!bam_api.start_cap() || !reads.has_contig_ids() || reads.contig_ids.size() != n ||
-        (by_strand && reads.strata.size() != n))
-        throw std::invalid_argument("a start cap needs a BamApi built with BamApiConfig::start_cap");
+    need_per_reference(bam_api.start_cap() && (!by_strand || reads.strata.size() == n), reads,
+                       "a start cap needs a BamApi built with BamApiConfig::start_cap");
     if (reads.qualities.size() != n) throw std::invalid_argument("reads without one quality each");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    static_assert(sizeof(bam_api::ReadQuality) == sizeof(std::uint32_t), "ReadQuality is uint32 (read.hpp)");
+    context();
+    const Columns c = narrowed(reads);
     start_cap_hist_.assign(hist_bins, 0);
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_start_cap_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(),
-                                           by_strand ? reads.strata.data() : nullptr, reads.qualities.data(), n,
-                                           reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                           required_cover, bam_api.start_cap(), QMCP_START_CAP_SHORTFALL, mask.data(),
-                                           nullptr, hist_bins ? start_cap_hist_.data() : nullptr, hist_bins, &stats_,
-                                           &scstats_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_start_cap_host", rc);
-    breakdown_ = qmcp_hip_host_breakdown{};
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
-    return expand_kept(n, t0);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_die("qmcp_hip_solve_start_cap_host",
+              qmcp_hip_solve_start_cap_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(),
+                                            by_strand ? reads.strata.data() : nullptr, reads.qualities.data(), n,
+                                            reads.contig_lengths.data(), n_contigs(reads), required_cover,
+                                            bam_api.start_cap(), QMCP_START_CAP_SHORTFALL, mask.data(), nullptr,
+                                            hist_bins ? start_cap_hist_.data() : nullptr, hist_bins, &stats_, &scstats_));
+    return finish(mask, n, t0);
 }
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t required_cover, bam_api::BamApi& bam_api,
@@ -265,136 +276,75 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t require
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("a coverage profile needs per_reference reads (one contig id per read)");
-    if (offsets.size() != reads.contig_lengths.size() + 1) throw std::invalid_argument("cap regions of other references");
-    if (region_starts.size() < offsets.back() || region_ends.size() < offsets.back() || caps.size() < offsets.back())
-        throw std::invalid_argument("cap region arrays are shorter than their offsets say");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_profile_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                         reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                         offsets.data(), region_starts.data(), region_ends.data(), caps.data(),
-                                         required_cover, 0u, mask.data(), &stats_, &pstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_profile_host", rc);
-    breakdown_ = qmcp_hip_host_breakdown{};
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
-    return expand_kept(n, t0);
+    need_per_reference(true, reads, "a coverage profile needs per_reference reads (one contig id per read)");
+    check_regions(offsets, region_starts, region_ends, caps, reads.contig_lengths.size());
+    context();
+    const Columns c = narrowed(reads);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_throw("qmcp_hip_solve_profile_host",
+                qmcp_hip_solve_profile_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                            reads.contig_lengths.data(), n_contigs(reads), offsets.data(),
+                                            region_starts.data(), region_ends.data(), caps.data(), required_cover, 0u,
+                                            mask.data(), &stats_, &pstats_));
+    return finish(mask, n, t0);
 }
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_proportional(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.proportion() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("proportional downsampling needs a BamApi built with BamApiConfig::proportion");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    need_per_reference(bam_api.proportion().has_value(), reads,
+                       "proportional downsampling needs a BamApi built with BamApiConfig::proportion");
+    context();
+    const Columns c = narrowed(reads);
     const bam_api::BamApiConfig::Proportion& f = *bam_api.proportion();
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    int rc = qmcp_hip_solve_proportional_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                              reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(), f.num,
-                                              f.den, f.floor, required_cover, 0u, mask.data(), &stats_, &ppstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_proportional_host", rc);
-    breakdown_ = qmcp_hip_host_breakdown{};
-    if (complete_pairs_) {
-        rc = qmcp_hip_complete_pairs_host(ctx_, mask.data(), n);   // (leaves the completed mask in the context)
-        if (rc != QMCP_OK) die("qmcp_hip_complete_pairs_host", rc);
-    }
-    return expand_kept(n, t0);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_throw("qmcp_hip_solve_proportional_host",
+                qmcp_hip_solve_proportional_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                                 reads.contig_lengths.data(), n_contigs(reads), f.num, f.den, f.floor,
+                                                 required_cover, 0u, mask.data(), &stats_, &ppstats_));
+    return finish(mask, n, t0);
 }
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.pair_aware() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("pair-aware downsampling needs a BamApi built with BamApiConfig::pair_aware");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    need_per_reference(bam_api.pair_aware(), reads,
+                       "pair-aware downsampling needs a BamApi built with BamApiConfig::pair_aware");
+    context();
+    const Columns c = narrowed(reads);
     const std::vector<std::uint32_t>& stages = bam_api.pair_stages();
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    const int rc = qmcp_hip_solve_pairs_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                             reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                             required_cover, stages.empty() ? nullptr : stages.data(),
-                                             (std::uint32_t)stages.size(), mask.data(), &stats_, &prstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_pairs_host", rc);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_throw("qmcp_hip_solve_pairs_host",
+                qmcp_hip_solve_pairs_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                          reads.contig_lengths.data(), n_contigs(reads), required_cover,
+                                          stages.empty() ? nullptr : stages.data(), (std::uint32_t)stages.size(),
+                                          mask.data(), &stats_, &prstats_));
     breakdown_ = qmcp_hip_host_breakdown{};
     // the context holds the last stage's completed mask
-    auto kept = std::make_unique<Solution>();
-    const std::uint64_t upper = prstats_.n_kept[prstats_.n_stages - 1];
-    kept->resize(upper);
-    std::uint64_t n_out = 0;
-    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
-    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
-    kept->resize(n_out);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return kept;
+    return expand(n, prstats_.n_kept[prstats_.n_stages - 1], t0);
 }
 
 std::vector<std::uint8_t> QuasiMcpHipSolver::solve_replicates(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.replicates().has_value() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("disjoint replicates need a BamApi built with BamApiConfig::replicates");
+    need_per_reference(bam_api.replicates().has_value(), reads,
+                       "disjoint replicates need a BamApi built with BamApiConfig::replicates");
     std::vector<std::uint32_t> coverages{required_cover};
     coverages.insert(coverages.end(), bam_api.replicates()->begin(), bam_api.replicates()->end());
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    context();
+    const Columns c = narrowed(reads);
     std::vector<std::uint8_t> labels(n, 0);
-    const int rc = qmcp_hip_solve_replicates_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                                  reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                                  coverages.data(), (std::uint32_t)coverages.size(),
-                                                  QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL, labels.data(),
-                                                  &stats_, nullptr, &rpstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_replicates_host", rc);
+    ok_or_throw("qmcp_hip_solve_replicates_host",
+                qmcp_hip_solve_replicates_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                               reads.contig_lengths.data(), n_contigs(reads), coverages.data(),
+                                               (std::uint32_t)coverages.size(),
+                                               QMCP_REPLICATES_WHOLE_PAIRS | QMCP_REPLICATES_SHORTFALL, labels.data(),
+                                               &stats_, nullptr, &rpstats_));
     breakdown_ = qmcp_hip_host_breakdown{};
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_solve_call_ = ms_since(t0);
     return labels;
 }
 
@@ -406,80 +356,46 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_ceiling(std::uint32_t require
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.ceiling() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("ceiling downsampling needs a BamApi built with BamApiConfig::ceiling");
+    need_per_reference(bam_api.ceiling(), reads, "ceiling downsampling needs a BamApi built with BamApiConfig::ceiling");
     const bool with_regions = !offsets.empty();
-    if (with_regions) {
-        if (offsets.size() != reads.contig_lengths.size() + 1) throw std::invalid_argument("cap regions of other references");
-        if (region_starts.size() < offsets.back() || region_ends.size() < offsets.back() || caps.size() < offsets.back())
-            throw std::invalid_argument("cap region arrays are shorter than their offsets say");
-    }
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    const int rc = qmcp_hip_solve_ceiling_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                               reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                               with_regions ? offsets.data() : nullptr, region_starts.data(),
-                                               region_ends.data(), caps.data(), required_cover, QMCP_CEILING_WHOLE_PAIRS,
-                                               mask.data(), &stats_, &clstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_ceiling_host", rc);
+    if (with_regions) check_regions(offsets, region_starts, region_ends, caps, reads.contig_lengths.size());
+    context();
+    const Columns c = narrowed(reads);
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_throw("qmcp_hip_solve_ceiling_host",
+                qmcp_hip_solve_ceiling_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                            reads.contig_lengths.data(), n_contigs(reads),
+                                            with_regions ? offsets.data() : nullptr, region_starts.data(),
+                                            region_ends.data(), caps.data(), required_cover, QMCP_CEILING_WHOLE_PAIRS,
+                                            mask.data(), &stats_, &clstats_));
     breakdown_ = qmcp_hip_host_breakdown{};
     // the context holds the final mask
-    auto kept = std::make_unique<Solution>();
-    const std::uint64_t upper = clstats_.reads_placed - clstats_.reads_dropped;
-    kept->resize(upper);
-    std::uint64_t n_out = 0;
-    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
-    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
-    kept->resize(n_out);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return kept;
+    return expand(n, clstats_.reads_placed - clstats_.reads_dropped, t0);
 }
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_thresholds(bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.thresholds() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("coverage thresholds need a BamApi built with BamApiConfig::thresholds_hi");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    need_per_reference(bam_api.thresholds(), reads,
+                       "coverage thresholds need a BamApi built with BamApiConfig::thresholds_hi");
+    context();
+    const Columns c = narrowed(reads);
     const std::uint32_t lo = bam_api.thresholds_lo(), hi = bam_api.thresholds_hi();
     thresholds_.assign(n, (std::uint16_t)QMCP_THRESHOLD_NEVER);
     threshold_counts_.assign(hi >= lo ? (std::size_t)(hi - lo) + 1 : 0, 0);
-    const int rc = qmcp_hip_solve_thresholds_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                                  reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                                  lo, hi, QMCP_THRESHOLDS_WHOLE_PAIRS, thresholds_.data(),
-                                                  threshold_counts_.data(), (std::uint32_t)threshold_counts_.size(), &stats_,
-                                                  &thstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_thresholds_host", rc);
+    ok_or_throw("qmcp_hip_solve_thresholds_host",
+                qmcp_hip_solve_thresholds_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                               reads.contig_lengths.data(), n_contigs(reads), lo, hi,
+                                               QMCP_THRESHOLDS_WHOLE_PAIRS, thresholds_.data(), threshold_counts_.data(),
+                                               (std::uint32_t)threshold_counts_.size(), &stats_, &thstats_));
     threshold_counts_.resize(thstats_.count_entries);
     breakdown_ = qmcp_hip_host_breakdown{};
     auto kept = std::make_unique<Solution>();
     kept->reserve(thstats_.n_kept);
     for (std::size_t i = 0; i < n; ++i)
         if (thresholds_[i] != QMCP_THRESHOLD_NEVER) kept->push_back(i);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_solve_call_ = ms_since(t0);
     return kept;
 }
 
@@ -487,86 +403,48 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_budget(std::uint32_t required
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.budget() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("budget downsampling needs a BamApi built with BamApiConfig::budget_reads or "
-                                    "budget_fraction");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    std::uint64_t placed = 0;
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-        ++placed;
-    }
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    need_per_reference(bam_api.budget(), reads,
+                       "budget downsampling needs a BamApi built with BamApiConfig::budget_reads or budget_fraction");
+    context();
+    const Columns c = narrowed(reads);
+    std::vector<std::uint64_t> mask = empty_mask(n);
     budget_curve_.assign(QMCP_BUDGET_CURVE_MAX + 1u, 0);
-    const int rc = qmcp_hip_solve_budget_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                              reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                              required_cover, bam_api.budget_for(placed), QMCP_BUDGET_WHOLE_PAIRS,
-                                              budget_curve_.data(), (std::uint32_t)budget_curve_.size(), mask.data(),
-                                              &stats_, &bgstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_budget_host", rc);
+    ok_or_throw("qmcp_hip_solve_budget_host",
+                qmcp_hip_solve_budget_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                           reads.contig_lengths.data(), n_contigs(reads), required_cover,
+                                           bam_api.budget_for(c.placed), QMCP_BUDGET_WHOLE_PAIRS, budget_curve_.data(),
+                                           (std::uint32_t)budget_curve_.size(), mask.data(), &stats_, &bgstats_));
     budget_curve_.resize(bgstats_.curve_entries);
     breakdown_ = qmcp_hip_host_breakdown{};
     // the context holds the final mask
-    auto kept = std::make_unique<Solution>();
-    kept->resize(bgstats_.n_kept);
-    std::uint64_t n_out = 0;
-    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), bgstats_.n_kept, &n_out);
-    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
-    kept->resize(n_out);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return kept;
+    return expand(n, bgstats_.n_kept, t0);
 }
 
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_mean_depth(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = reads.start_inds.size();
-    if (!bam_api.mean_depth() || !reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("mean-depth downsampling needs a BamApi built with BamApiConfig::mean_depth or "
-                                    "budget_bases");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    need_per_reference(bam_api.mean_depth(), reads,
+                       "mean-depth downsampling needs a BamApi built with BamApiConfig::mean_depth or budget_bases");
+    context();
+    const Columns c = narrowed(reads);
     const bam_api::TargetRegions* regions = bam_api.has_mean_depth_regions() ? &bam_api.mean_depth_regions() : nullptr;
     if (regions && regions->offsets.size() != reads.contig_lengths.size() + 1)
         throw std::invalid_argument("the mean-depth regions do not match the file's references");
     const std::uint64_t budget = bam_api.base_budget_for(bam_api.mean_depth_positions(reads.contig_lengths));
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    std::vector<std::uint64_t> mask = empty_mask(n);
     mean_depth_curve_.assign(QMCP_BUDGET_CURVE_MAX + 1u, 0);
-    const int rc = qmcp_hip_solve_mean_depth_host(
-        ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(),
-        (std::uint32_t)reads.contig_lengths.size(), required_cover, budget, regions ? regions->offsets.data() : nullptr,
-        regions ? regions->starts.data() : nullptr, regions ? regions->ends.data() : nullptr, QMCP_MEAN_DEPTH_WHOLE_PAIRS,
-        mean_depth_curve_.data(), (std::uint32_t)mean_depth_curve_.size(), mask.data(), &stats_, &mdstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_mean_depth_host", rc);
+    ok_or_throw("qmcp_hip_solve_mean_depth_host",
+                qmcp_hip_solve_mean_depth_host(
+                    ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(),
+                    n_contigs(reads), required_cover, budget, regions ? regions->offsets.data() : nullptr,
+                    regions ? regions->starts.data() : nullptr, regions ? regions->ends.data() : nullptr,
+                    QMCP_MEAN_DEPTH_WHOLE_PAIRS, mean_depth_curve_.data(), (std::uint32_t)mean_depth_curve_.size(),
+                    mask.data(), &stats_, &mdstats_));
     mean_depth_curve_.resize(mdstats_.curve_entries);
     breakdown_ = qmcp_hip_host_breakdown{};
     // the context holds the final mask
-    auto kept = std::make_unique<Solution>();
-    kept->resize(mdstats_.n_kept);
-    std::uint64_t n_out = 0;
-    const int rc2 = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), mdstats_.n_kept, &n_out);
-    if (rc2 != QMCP_OK) die("qmcp_hip_kept_indices_host", rc2);
-    kept->resize(n_out);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return kept;
+    return expand(n, mdstats_.n_kept, t0);
 }
 
 // a record is written iff one of its segments is kept; its segments are consecutive, in file order
@@ -585,12 +463,9 @@ std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates(std::uint32_t
     const bam_api::TemplateSegments& seg = bam_api.get_template_segments();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = seg.starts.size();
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
+    context();
     const std::vector<std::uint32_t>& stages = bam_api.template_stages();
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    std::vector<std::uint64_t> mask = empty_mask(n);
     frstats_ = qmcp_hip_fragment_stats{};
     const bool fragments = bam_api.fragment_depth();
     const int rc = fragments
@@ -604,11 +479,10 @@ std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates(std::uint32_t
                                         (std::uint32_t)seg.contig_lengths.size(), required_cover,
                                         stages.empty() ? nullptr : stages.data(), (std::uint32_t)stages.size(), mask.data(),
                                         &stats_, &tpstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die(fragments ? "qmcp_hip_solve_fragments_host" : "qmcp_hip_solve_templates_host", rc);
+    ok_or_throw(fragments ? "qmcp_hip_solve_fragments_host" : "qmcp_hip_solve_templates_host", rc);
     breakdown_ = qmcp_hip_host_breakdown{};
     std::vector<bam_api::BAMReadId> records = records_of_kept_segments(seg, mask);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_solve_call_ = ms_since(t0);
     return records;
 }
 
@@ -624,40 +498,34 @@ std::vector<bam_api::BAMReadId> QuasiMcpHipSolver::solve_templates_profile(std::
     const bam_api::TemplateSegments& seg = bam_api.get_template_segments();
     const auto t0 = std::chrono::steady_clock::now();
     const std::size_t n = seg.starts.size();
-    if (offsets.size() != seg.contig_lengths.size() + 1) throw std::invalid_argument("cap regions of other references");
-    if (region_starts.size() < offsets.back() || region_ends.size() < offsets.back() || caps.size() < offsets.back())
-        throw std::invalid_argument("cap region arrays are shorter than their offsets say");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
+    check_regions(offsets, region_starts, region_ends, caps, seg.contig_lengths.size());
+    context();
     const std::vector<std::uint32_t>& stages = bam_api.template_stages();
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
+    std::vector<std::uint64_t> mask = empty_mask(n);
     // fragment depth: the clip first, the profile entry on its columns (two calls)
     frstats_ = qmcp_hip_fragment_stats{};
     std::vector<std::uint32_t> clipped_starts, clipped_ids;
     if (bam_api.fragment_depth()) {
         clipped_starts.resize(n);
         clipped_ids.resize(n);
-        const int rc0 = qmcp_hip_clip_templates_host(ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(),
-                                                     seg.template_ids.data(), n, seg.n_templates, seg.contig_lengths.data(),
-                                                     (std::uint32_t)seg.contig_lengths.size(), clipped_starts.data(),
-                                                     clipped_ids.data(), &frstats_);
-        if (rc0 == QMCP_EINVAL || rc0 == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-        if (rc0 != QMCP_OK) die("qmcp_hip_clip_templates_host", rc0);
+        ok_or_throw("qmcp_hip_clip_templates_host",
+                    qmcp_hip_clip_templates_host(ctx_, seg.starts.data(), seg.ends.data(), seg.contig_ids.data(),
+                                                 seg.template_ids.data(), n, seg.n_templates, seg.contig_lengths.data(),
+                                                 (std::uint32_t)seg.contig_lengths.size(), clipped_starts.data(),
+                                                 clipped_ids.data(), &frstats_));
     }
     const std::uint32_t* starts = bam_api.fragment_depth() ? clipped_starts.data() : seg.starts.data();
     const std::uint32_t* contig_ids = bam_api.fragment_depth() ? clipped_ids.data() : seg.contig_ids.data();
-    const int rc = qmcp_hip_solve_templates_profile_host(
-        ctx_, starts, seg.ends.data(), contig_ids, seg.template_ids.data(), n, seg.n_templates,
-        seg.contig_lengths.data(), (std::uint32_t)seg.contig_lengths.size(), offsets.data(), region_starts.data(),
-        region_ends.data(), caps.data(), default_cap, 0u, required_cover, stages.empty() ? nullptr : stages.data(),
-        (std::uint32_t)stages.size(), mask.data(), &stats_, &tpstats_, &tqstats_);
-    if (rc == QMCP_EINVAL || rc == QMCP_ERANGE) throw std::invalid_argument(qmcp_hip_last_error());
-    if (rc != QMCP_OK) die("qmcp_hip_solve_templates_profile_host", rc);
+    ok_or_throw("qmcp_hip_solve_templates_profile_host",
+                qmcp_hip_solve_templates_profile_host(
+                    ctx_, starts, seg.ends.data(), contig_ids, seg.template_ids.data(), n, seg.n_templates,
+                    seg.contig_lengths.data(), (std::uint32_t)seg.contig_lengths.size(), offsets.data(),
+                    region_starts.data(), region_ends.data(), caps.data(), default_cap, 0u, required_cover,
+                    stages.empty() ? nullptr : stages.data(), (std::uint32_t)stages.size(), mask.data(), &stats_,
+                    &tpstats_, &tqstats_));
     breakdown_ = qmcp_hip_host_breakdown{};
     std::vector<bam_api::BAMReadId> records = records_of_kept_segments(seg, mask);
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_solve_call_ = ms_since(t0);
     return records;
 }
 
@@ -676,25 +544,14 @@ std::vector<std::unique_ptr<Solution>> QuasiMcpHipSolver::solve_ladder(std::uint
     if (coverages.back() == 0) throw std::invalid_argument("a coverage ladder ends at a coverage >= 1");
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const std::size_t n = reads.start_inds.size();
-    if (!reads.has_contig_ids() || reads.contig_ids.size() != n)
-        throw std::invalid_argument("a coverage ladder needs per_reference reads (one contig id each)");
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
+    need_per_reference(true, reads, "a coverage ladder needs per_reference reads (one contig id each)");
+    context();
+    const Columns c = narrowed(reads);
     std::vector<std::uint8_t> bytes(n, 0);
-    const int rc = qmcp_hip_solve_ladder_host(ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n,
-                                              reads.contig_lengths.data(), (std::uint32_t)reads.contig_lengths.size(),
-                                              coverages.data(), (std::uint32_t)coverages.size(), bytes.data(), &stats_,
-                                              &lstats_);
-    if (rc != QMCP_OK) die("qmcp_hip_solve_ladder_host", rc);
+    ok_or_die("qmcp_hip_solve_ladder_host",
+              qmcp_hip_solve_ladder_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n,
+                                         reads.contig_lengths.data(), n_contigs(reads), coverages.data(),
+                                         (std::uint32_t)coverages.size(), bytes.data(), &stats_, &lstats_));
     breakdown_ = qmcp_hip_host_breakdown{};
     std::vector<std::unique_ptr<Solution>> out;
     for (std::size_t j = 0; j < coverages.size(); ++j) {
@@ -707,41 +564,31 @@ std::vector<std::unique_ptr<Solution>> QuasiMcpHipSolver::solve_ladder(std::uint
     return out;
 }
 
+// ------------------------------------------------------------------------------------------ depth before and after
+
 void QuasiMcpHipSolver::depth_report(std::uint32_t required_cover, bam_api::BamApi& bam_api,
                                      const std::vector<bam_api::ReadIndex>& kept, std::uint32_t n_bins, DepthReport& out) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const std::size_t n = reads.start_inds.size();
-    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("a depth report without one contig id per read", QMCP_EINVAL);
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    for (const bam_api::ReadIndex i : kept)
-        if (i < n) mask[i >> 6] |= 1ull << (i & 63);
-    const std::uint32_t n_contigs = (std::uint32_t)reads.contig_lengths.size();
+    if (!one_contig_id_each(reads)) die("a depth report without one contig id per read", QMCP_EINVAL);
+    context();
+    const Columns c = narrowed(reads);
+    const std::vector<std::uint64_t> mask = keep_mask_of(kept, n);
     const bool regions = bam_api.has_targets();
     const bam_api::TargetRegions& t = bam_api.get_targets();
     out = DepthReport();
-    out.contig_rows.resize(n_contigs);
+    out.contig_rows.resize(n_contigs(reads));
     out.region_rows.resize(regions ? t.starts.size() : 0);
     out.hist_in.assign(n_bins, 0);
     out.hist_kept.assign(n_bins, 0);
     std::uint64_t n_rows = 0;
-    const int rc = qmcp_hip_depth_report_host(
-        ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(), n_contigs, mask.data(),
-        required_cover, regions ? t.offsets.data() : nullptr, regions ? t.starts.data() : nullptr,
-        regions ? t.ends.data() : nullptr, regions ? t.padding : 0u, n_bins, out.contig_rows.data(), out.region_rows.data(),
-        out.region_rows.size(), &n_rows, n_bins ? out.hist_in.data() : nullptr, n_bins ? out.hist_kept.data() : nullptr,
-        &out.stats);
-    if (rc != QMCP_OK) die("qmcp_hip_depth_report_host", rc);
+    ok_or_die("qmcp_hip_depth_report_host",
+              qmcp_hip_depth_report_host(
+                  ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(),
+                  n_contigs(reads), mask.data(), required_cover, regions ? t.offsets.data() : nullptr,
+                  regions ? t.starts.data() : nullptr, regions ? t.ends.data() : nullptr, regions ? t.padding : 0u, n_bins,
+                  out.contig_rows.data(), out.region_rows.data(), out.region_rows.size(), &n_rows,
+                  n_bins ? out.hist_in.data() : nullptr, n_bins ? out.hist_kept.data() : nullptr, &out.stats));
     out.region_rows.resize(n_rows);
 }
 
@@ -750,33 +597,21 @@ void QuasiMcpHipSolver::depth_track(std::uint32_t required_cover, bam_api::BamAp
                                     std::uint32_t depth_cap, DepthTrack& out) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const std::size_t n = reads.start_inds.size();
-    if (!reads.has_contig_ids() || reads.contig_ids.size() != n) die("a depth track without one contig id per read", QMCP_EINVAL);
-    if (ctx_ == nullptr) {
-        const int rc = qmcp_hip_create(device_, &ctx_);
-        if (rc != QMCP_OK) die("qmcp_hip_create", rc);
-    }
-    std::vector<std::uint32_t> starts(n), ends(n);
-    for (std::size_t i = 0; i < n; ++i) {
-        if (reads.contig_ids[i] == QMCP_NO_CONTIG) continue;  // (zero-initialised)
-        if (reads.start_inds[i] > UINT32_MAX || reads.end_inds[i] > UINT32_MAX) die("narrowing a coordinate", QMCP_ERANGE);
-        starts[i] = static_cast<std::uint32_t>(reads.start_inds[i]);
-        ends[i] = static_cast<std::uint32_t>(reads.end_inds[i]);
-    }
-    std::vector<std::uint64_t> mask((n + 63) / 64, 0);
-    for (const bam_api::ReadIndex i : kept)
-        if (i < n) mask[i >> 6] |= 1ull << (i & 63);
-    const std::uint32_t n_contigs = (std::uint32_t)reads.contig_lengths.size();
+    if (!one_contig_id_each(reads)) die("a depth track without one contig id per read", QMCP_EINVAL);
+    context();
+    const Columns c = narrowed(reads);
+    const std::vector<std::uint64_t> mask = keep_mask_of(kept, n);
     const bool regions = bam_api.has_targets();
     const bam_api::TargetRegions& t = bam_api.get_targets();
     out = DepthTrack();
     std::uint64_t n_runs = 0;
     for (int pass = 0; pass < 2; ++pass) {  // the count, then the records at that size
-        const int rc = qmcp_hip_depth_track_host(
-            ctx_, starts.data(), ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(), n_contigs,
-            mask.data(), required_cover, regions ? t.offsets.data() : nullptr, regions ? t.starts.data() : nullptr,
-            regions ? t.ends.data() : nullptr, regions ? t.padding : 0u, flags, depth_cap,
-            pass ? out.runs.data() : nullptr, out.runs.size(), &n_runs, &out.stats);
-        if (rc != QMCP_OK) die("qmcp_hip_depth_track_host", rc);
+        ok_or_die("qmcp_hip_depth_track_host",
+                  qmcp_hip_depth_track_host(
+                      ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), n, reads.contig_lengths.data(),
+                      n_contigs(reads), mask.data(), required_cover, regions ? t.offsets.data() : nullptr,
+                      regions ? t.starts.data() : nullptr, regions ? t.ends.data() : nullptr, regions ? t.padding : 0u,
+                      flags, depth_cap, pass ? out.runs.data() : nullptr, out.runs.size(), &n_runs, &out.stats));
         if (pass == 0) {
             if (n_runs == 0) break;
             out.runs.resize(n_runs);
@@ -831,27 +666,6 @@ bool write_depth_report_tsv(const std::filesystem::path& path, const DepthReport
         std::fprintf(f, "#hist\t%zu\t%llu\t%llu\n", b, (unsigned long long)report.hist_in[b],
                      (unsigned long long)report.hist_kept[b]);
     return std::fclose(f) == 0;
-}
-
-// the context's keep mask as the ascending Solution
-std::unique_ptr<Solution> QuasiMcpHipSolver::expand_kept(std::uint64_t n, std::chrono::steady_clock::time_point t0) {
-    int rc = QMCP_OK;
-    const auto t1 = std::chrono::steady_clock::now();
-
-    // ascending ReadIndex, as obtain_sequence produces (quasi_mcp_cpu_max_flow_solver.cpp:93-97): expanded from
-    // the keep mask on the device (popcounts, scan, scatter) and copied out -- 5 % of the reads at cfg4's depth
-    auto kept = std::make_unique<Solution>();
-    static_assert(sizeof(bam_api::ReadIndex) == sizeof(std::uint64_t), "ReadIndex is size_t on an LP64 host");
-    const std::uint64_t upper = complete_pairs_ ? std::min<std::uint64_t>(n, 2 * stats_.n_kept) : stats_.n_kept;
-    kept->resize(upper);
-    std::uint64_t n_out = 0;
-    rc = qmcp_hip_kept_indices_host(ctx_, n, reinterpret_cast<std::uint64_t*>(kept->data()), upper, &n_out);
-    if (rc != QMCP_OK) die("qmcp_hip_kept_indices_host", rc);
-    kept->resize(n_out);
-    const auto t2 = std::chrono::steady_clock::now();
-    ms_expand_ = std::chrono::duration<float, std::milli>(t2 - t1).count();
-    ms_solve_call_ = std::chrono::duration<float, std::milli>(t2 - t0).count();
-    return kept;
 }
 
 }  // namespace qmcp

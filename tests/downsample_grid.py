@@ -1,8 +1,10 @@
 """The characterisation grid of downsample_bam: every subset of at most two of SWITCHES on top of per_reference=True,
-on one tiny two-reference BAM, through the public downsample_bam alone.  `outcome` runs one case and returns what it did
--- the exception's type and message, or the returned counts with a hash of the DECODED records of every BAM written
-(tests/bam_py.py reads them back; the compressed bytes depend on the zlib at hand) and the text of every report.
-Run as a script on a GPU it records the whole grid:
+then each of LATER_SWITCHES alone and with each of LATER_PARTNERS (an explicit list: squaring the grid again would not
+pay), on one tiny two-reference BAM, through the public downsample_bam alone.  `outcome` runs one case and returns what
+it did -- the exception's type and message, or the returned counts with a hash of the DECODED records of every BAM
+written (tests/bam_py.py reads them back; the compressed bytes depend on the zlib at hand) and the text of every report.
+Run as a script on a GPU it records the cases the file does not hold yet (all of them into a new file) and leaves the
+recorded ones as they are:
 
     python tests/downsample_grid.py tests/golden/downsample_grid.json
 
@@ -10,7 +12,7 @@ tests/test_downsample_grid_cpu.py and tests/test_gpu_downsample_grid.py replay t
 
 The input comes from the writer in tests/bam_py.py: genome-downsampler_amd's write_synthetic_bam writes one reference
 only, and the grid needs two so that per-reference grouping and mates on the other reference do something.  The lines
-ms_budget / ms_solves of the budget report are timings and are left out of the recorded text."""
+of a report that begin with ms_ are timings and are left out of the recorded text."""
 import hashlib
 import itertools
 import json
@@ -30,6 +32,11 @@ SWITCHES = ("single_reference", "bed", "targets", "report", "track", "ladder", "
             "pair_aware", "template_aware", "template_targets", "ceiling", "budget_reads", "budget_fraction",
             "replicates", "quality")
 CASES = [combo for k in range(3) for combo in itertools.combinations(SWITCHES, k)]
+# the modes that came after the grid: alone, and with the three switches every one of them refuses
+LATER_SWITCHES = ("proportion", "mean_depth", "budget_bases", "thresholds", "start_cap", "fragment_depth")
+LATER_PARTNERS = ("report", "track", "quality")
+CASES += [(name,) for name in LATER_SWITCHES]
+CASES += [(name, partner) for partner in LATER_PARTNERS for name in LATER_SWITCHES]
 
 
 def key_of(combo):
@@ -75,6 +82,13 @@ def arguments(combo, inputs, out_dir):
         "budget_fraction": dict(budget_fraction=0.5),
         "replicates": dict(replicates=3, replicates_out=out("replicate_{R}.bam"), replicates_report=out("replicates.tsv")),
         "quality": {},
+        "proportion": dict(proportion=(1, 4), proportion_floor=1, proportional_report=out("proportional.tsv")),
+        "mean_depth": dict(mean_depth=2.5, mean_depth_report=out("mean_depth.tsv")),
+        "budget_bases": dict(budget_bases=20000, mean_depth_report=out("budget_bases.tsv")),
+        "thresholds": dict(thresholds=(1, 4), thresholds_report=out("thresholds.tsv")),
+        "start_cap": dict(start_cap=1, start_cap_by_strand=True, start_cap_report=out("start_cap.tsv")),
+        "fragment_depth": dict(template_aware=True, fragment_depth=True, fragment_report=out("fragments.tsv"),
+                               template_report=out("templates.tsv")),
     }
     kwargs = dict(per_reference=True, filtered_path=out("filtered.bam"), min_mapq=MIN_MAPQ)
     for name in combo:
@@ -116,10 +130,12 @@ def main(argv):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     pkg = importlib.import_module("genome-downsampler_amd")
-    record = {}
+    record = json.load(open(argv[1])) if os.path.exists(argv[1]) else {}
     with tempfile.TemporaryDirectory() as tmp:
         inputs = make_inputs(tmp)
         for i, combo in enumerate(CASES):
+            if key_of(combo) in record:
+                continue
             out_dir = os.path.join(tmp, f"case{i}")
             os.mkdir(out_dir)
             record[key_of(combo)] = outcome(pkg, combo, inputs, out_dir)

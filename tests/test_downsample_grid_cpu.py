@@ -22,7 +22,7 @@ def inputs(tmp_path_factory):
 
 
 def test_the_record_covers_the_grid():
-    assert sorted(RECORD) == sorted(grid.key_of(combo) for combo in grid.CASES) and len(grid.CASES) == 154
+    assert sorted(RECORD) == sorted(grid.key_of(combo) for combo in grid.CASES) and len(grid.CASES) == 178
     assert 100 < len(REFUSED) < len(grid.CASES)
 
 
