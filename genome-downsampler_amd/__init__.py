@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_replicates_host", "qmcp_hip_solve_replicates_device",
     "qmcp_hip_solve_proportional_host", "qmcp_hip_solve_proportional_device",
     "qmcp_hip_solve_start_cap_host", "qmcp_hip_solve_start_cap_device",
+    "qmcp_hip_solve_amplicons_host", "qmcp_hip_solve_amplicons_device",
 )
 
 QMCP_OK = 0
@@ -80,6 +81,9 @@ DEDUP_PAIRS, DEDUP_COMPLETE_PAIRS = 1, 2  # QMCP_DEDUP_PAIRS, QMCP_DEDUP_COMPLET
 DEDUP_REPORT_BINS = 64  # family-size bins of downsample_bam(dedup_report=)
 START_CAP_SHORTFALL = 1  # QMCP_START_CAP_SHORTFALL
 START_CAP_REPORT_BINS = 64  # cell-size bins of downsample_bam(start_cap_report=)
+AMPLICONS_SINGLE_END, AMPLICONS_PER_AMPLICON, AMPLICONS_COMPLETE_PAIRS = 1, 2, 4  # QMCP_AMPLICONS_*
+NO_AMPLICON = 0xFFFFFFFF  # QMCP_NO_AMPLICON: the label of a unit that no amplicon contains
+AMPLICON_LDS_MAX = 2560  # qmcp::kAcLdsMax: the largest amplicon table the assign kernel stages in LDS
 TRACK_IN, TRACK_KEPT, TRACK_SHORT_ONLY, TRACK_SKIP_ZERO = 1, 2, 4, 8  # QMCP_TRACK_*
 TRACK_FIRST_CAPACITY = 1 << 22  # records Solver.depth_track offers first (96 MiB); beyond it, one more call at the exact count
 STRATUM_TALLY_TILE = 1024  # qmcp::kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces
@@ -439,6 +443,22 @@ class StartCapStats(C.Structure):
 assert C.sizeof(StartCapStats) == 10 * 8 + 4 * 4
 
 
+class AmpliconsStats(C.Structure):
+    """qmcp_hip_amplicons_stats: what the assign step of an amplicon-aware solve did (units: pairs, or reads when
+    single-end; units == units_assigned + units_filtered + units_no_amplicon; the reads_* and bases_clipped count the
+    reads of assigned units only)"""
+    _fields_ = [("units", C.c_uint64), ("units_assigned", C.c_uint64), ("units_filtered", C.c_uint64),
+                ("units_no_amplicon", C.c_uint64), ("units_in_several", C.c_uint64), ("reads_shortened", C.c_uint64),
+                ("reads_clipped_away", C.c_uint64), ("bases_clipped", C.c_uint64), ("amplicons", C.c_uint64),
+                ("amplicons_unused", C.c_uint64), ("ms_assign", C.c_float), ("ms_report", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+assert C.sizeof(AmpliconsStats) == 10 * 8 + 2 * 4
+
+
 class DepthReport:
     """what Solver.depth_report returns: contig_rows / region_rows (numpy structured arrays of DEPTH_ROW_DTYPE),
     hist_in / hist_kept (uint64, n_bins entries), stats (DepthStats); valid: no position in scope is short of
@@ -493,6 +513,7 @@ class DownsampleRequest(C.Structure):
                                           "has_budget_bases", "has_mean_depth", "has_replicates", "has_thresholds",
                                           "start_cap_by_strand")]
         + [("start_cap", C.c_uint32), ("start_cap_report", C.c_char_p)]
+        + [("primer_clip", C.c_int32), ("per_amplicon", C.c_int32), ("amplicon_report", C.c_char_p)]
         + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
            ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
@@ -614,6 +635,14 @@ _hip.qmcp_hip_solve_start_cap_device.argtypes = [C.c_void_p, C.c_void_p, C.c_voi
                                                  C.c_uint64, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                  C.c_void_p, C.c_void_p, _u64p, C.c_uint32, C.c_void_p, C.POINTER(Stats),
                                                  C.POINTER(StartCapStats)]
+_amplicons_tail = [_u32p, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+_hip.qmcp_hip_solve_amplicons_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, C.c_uint64] + \
+                                              _amplicons_tail + [_u64p, _u32p, C.c_void_p, C.POINTER(Stats),
+                                                                 C.POINTER(AmpliconsStats)]
+_hip.qmcp_hip_solve_amplicons_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint64] + _amplicons_tail + \
+                                                [C.c_void_p, _u32p, C.c_void_p, C.c_void_p, C.POINTER(Stats),
+                                                 C.POINTER(AmpliconsStats)]
 _hip.qmcp_hip_solve_profile_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, _u32p, _u32p,
                                              _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p, C.POINTER(Stats),
                                              C.POINTER(ProfileStats)]
@@ -847,6 +876,7 @@ class Solver:
         self.last_stratum_rows = None
         self.last_dedup_stats = None
         self.last_start_cap_stats = None
+        self.last_amplicons_stats = None
         self.last_pair_stats = None
         self.last_template_stats = None
         self.last_template_profile_stats = None
@@ -1177,6 +1207,80 @@ class Solver:
                                                     int(hist_bins), C.c_void_p(stream), C.byref(st), C.byref(cs)))
         self.last_stats, self.last_start_cap_stats = st, cs
         return cs.as_dict(), hist[:int(hist_bins)]
+
+    @staticmethod
+    def _amplicons_flags(single_end, per_amplicon, complete_pairs):
+        return ((AMPLICONS_SINGLE_END if single_end else 0) | (AMPLICONS_PER_AMPLICON if per_amplicon else 0)
+                | (AMPLICONS_COMPLETE_PAIRS if complete_pairs else 0))
+
+    @staticmethod
+    def _amplicons_tables(n_contigs, amp_offsets, amp_starts, amp_ends, insert_starts, insert_ends):
+        offs = None if amp_offsets is None else _u32(amp_offsets)
+        if offs is not None:
+            assert offs.size == n_contigs + 1, "amp_offsets needs n_contigs + 1 entries"
+        n_amp = 0 if offs is None else int(offs[-1])
+        cols = [None if a is None else _u32(a) for a in (amp_starts, amp_ends, insert_starts, insert_ends)]
+        for a in cols:
+            assert a is None or a.size == n_amp, "one entry per amplicon in every table column"
+        return offs, n_amp, cols
+
+    def solve_amplicons(self, starts, ends, contig_ids, contig_lengths, max_coverage, amp_offsets, amp_starts, amp_ends,
+                        insert_starts=None, insert_ends=None, seq_lengths=None, qualities=None, min_length=0, min_mapq=0,
+                        single_end=False, per_amplicon=False, complete_pairs=False, labels=True, rows=True):
+        """amplicon-aware downsampling (qmcp_hip_solve_amplicons_host): every unit -- the pair 2q, 2q + 1, or one read
+        with single_end -- that passes the length / MAPQ filters is assigned to the amplicon of its contig that contains
+        all of it (several: the greatest start, then the smallest end, then the smallest index), its reads are clipped
+        to that amplicon's insert [insert_starts[k], insert_ends[k]] (None: the amplicon itself), and the clipped reads
+        are solved: pooled per contig, or with per_amplicon one coverage problem per amplicon on its insert.  The
+        amplicons of contig c are [amp_offsets[c], amp_offsets[c + 1]) of the table columns.
+        -> (mask over the input reads, labels or None (uint32 per unit, NO_AMPLICON: none), rows or None (one
+        DEPTH_ROW_DTYPE record per amplicon over its insert: depth of the clipped reads before, of the final mask
+        after), stats_dict).  last_stats is the inner solve's, last_amplicons_stats the AmpliconsStats"""
+        starts, ends, ids = _u32(starts), _u32(ends), _u32(contig_ids)
+        n = starts.size
+        assert ends.size == n and ids.size == n, "starts, ends and contig_ids must have one entry per read"
+        sl = None if seq_lengths is None else _u32(seq_lengths)
+        q = None if qualities is None else _u32(qualities)
+        assert (sl is None or sl.size == n) and (q is None or q.size == n), "one entry per read in every column"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, n_amp, (a0, a1, i0, i1) = self._amplicons_tables(lengths.size, amp_offsets, amp_starts, amp_ends,
+                                                               insert_starts, insert_ends)
+        n_units = n if single_end else n // 2
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        lab = np.full(max(n_units, 1), NO_AMPLICON, dtype=np.uint32) if labels else None
+        rws = np.zeros(max(n_amp, 1), dtype=DEPTH_ROW_DTYPE) if rows else None
+        st, ast = Stats(), AmpliconsStats()
+        _check(_hip.qmcp_hip_solve_amplicons_host(
+            self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(sl), _p32(q), n, _p32(lengths), lengths.size, _p32(offs),
+            _p32(a0), _p32(a1), _p32(i0), _p32(i1), int(min_length), int(min_mapq), int(max_coverage),
+            self._amplicons_flags(single_end, per_amplicon, complete_pairs), _p64(mask), _p32(lab),
+            C.c_void_p(rws.ctypes.data) if rows else None, C.byref(st), C.byref(ast)))
+        self.last_stats, self.last_amplicons_stats = st, ast
+        return (mask[:mask_words(n)], lab[:n_units] if labels else None, rws[:n_amp] if rows else None, ast.as_dict())
+
+    def solve_amplicons_device(self, d_starts, d_ends, d_contig_ids, n_reads, contig_lengths, max_coverage, d_mask,
+                               amp_offsets, amp_starts, amp_ends, insert_starts=None, insert_ends=None, d_seq_lengths=0,
+                               d_qualities=0, min_length=0, min_mapq=0, single_end=False, per_amplicon=False,
+                               complete_pairs=False, labels=True, rows=True, stream=0):
+        """the same on device pointers (ints; 0: no lengths / no qualities); the mask is written to d_mask, the tables,
+        labels and rows stay on the host.  With pairs the columns must be 8-byte aligned (QMCP_EINVAL otherwise).
+        -> (labels or None, rows or None, stats_dict)"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        offs, n_amp, (a0, a1, i0, i1) = self._amplicons_tables(lengths.size, amp_offsets, amp_starts, amp_ends,
+                                                               insert_starts, insert_ends)
+        n = int(n_reads)
+        n_units = n if single_end else n // 2
+        lab = np.full(max(n_units, 1), NO_AMPLICON, dtype=np.uint32) if labels else None
+        rws = np.zeros(max(n_amp, 1), dtype=DEPTH_ROW_DTYPE) if rows else None
+        st, ast = Stats(), AmpliconsStats()
+        _check(_hip.qmcp_hip_solve_amplicons_device(
+            self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends), C.c_void_p(d_contig_ids), C.c_void_p(d_seq_lengths or None),
+            C.c_void_p(d_qualities or None), n, _p32(lengths), lengths.size, _p32(offs), _p32(a0), _p32(a1), _p32(i0),
+            _p32(i1), int(min_length), int(min_mapq), int(max_coverage),
+            self._amplicons_flags(single_end, per_amplicon, complete_pairs), C.c_void_p(d_mask), _p32(lab),
+            C.c_void_p(rws.ctypes.data) if rows else None, C.c_void_p(stream), C.byref(st), C.byref(ast)))
+        self.last_stats, self.last_amplicons_stats = st, ast
+        return lab[:n_units] if labels else None, rws[:n_amp] if rows else None, ast.as_dict()
 
     @staticmethod
     def _target_tables(n_contigs, target_offsets, target_starts, target_ends):
@@ -2071,6 +2175,49 @@ def amplicons_by_reference(bed_path, tsv_path, reference_names):
     return offs, a0[:n].copy(), a1[:n].copy()
 
 
+def amplicon_inserts_by_reference(bed_path, tsv_path, reference_names):
+    """the inserts and left primer names of amplicons_by_reference's amplicons, in the same order -> (insert_starts,
+    insert_ends, left_names).  From BED primers [ls, le) and [rs, re) the amplicon is [ls, re] (the reference's
+    inclusive quirk) and the insert [le, rs - 1], inclusive: what Solver.solve_amplicons takes as insert_starts /
+    insert_ends.  ValueError for what amplicons_by_reference refuses and for a primer pair that leaves no insert (its
+    primers touch or overlap), naming the pair"""
+    _need_host()
+    names = [str(n) for n in reference_names]
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    cap = 1 << 20
+    i0 = np.empty(cap, dtype=np.uint32)
+    i1 = np.empty(cap, dtype=np.uint32)
+    buf = C.create_string_buffer(1 << 24)
+    err = C.create_string_buffer(1024)
+    fn = _host.qmcp_host_amplicon_inserts_by_reference
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint64, _u32p, _u32p, C.c_uint64, C.c_char_p,
+                   C.c_size_t, C.c_char_p, C.c_size_t]
+    fn.restype = C.c_int64
+    n = fn(str(bed_path).encode(), str(tsv_path).encode() if tsv_path else None, arr, len(names), _p32(i0), _p32(i1), cap,
+           buf, len(buf), err, 1024)
+    if n == -4:
+        raise ValueError(err.value.decode())
+    if n < 0:
+        raise OSError(f"cannot build amplicon inserts by reference from {bed_path} / {tsv_path} ({n})")
+    return i0[:n].copy(), i1[:n].copy(), buf.value.decode().split("\n")[:n]
+
+
+def write_amplicon_report(path, chroms, amp_starts, amp_ends, left_names, units, reads_kept, rows):
+    """the TSV of downsample_bam(amplicon_report=): one line per amplicon -- chrom, amplicon start / end, insert start /
+    end (rows' start / end: the insert the solve used), left primer, units assigned, reads kept, minimum and mean depth
+    over the insert before and after, positions short of min(before, max_coverage).  chroms, amp_starts, amp_ends,
+    left_names, units and reads_kept hold one entry per amplicon; rows are Solver.solve_amplicons' (DEPTH_ROW_DTYPE
+    records, or tuples in that field order)"""
+    with open(path, "w") as f:
+        f.write("#chrom\tamplicon_start\tamplicon_end\tinsert_start\tinsert_end\tleft_primer\tunits\treads_kept\t"
+                "min_depth_in\tmean_depth_in\tmin_depth_kept\tmean_depth_kept\tdeficit_positions\n")
+        for k, row in enumerate(rows):
+            r = dict(zip(DEPTH_ROW_DTYPE.names, (int(x) for x in tuple(row))))
+            f.write(f"{chroms[k]}\t{int(amp_starts[k])}\t{int(amp_ends[k])}\t{r['start']}\t{r['end']}\t{left_names[k]}\t"
+                    f"{int(units[k])}\t{int(reads_kept[k])}\t{r['min_in']}\t{r['sum_in'] / r['positions']:.6f}\t"
+                    f"{r['min_kept']}\t{r['sum_kept'] / r['positions']:.6f}\t{r['deficit_positions']}\n")
+
+
 def targets_from_bed(bed_path, reference_names):
     """target regions from a BED file (BED3+, further columns ignored) matched to references by name -> (offsets, starts,
     ends) as Solver.solve_targets takes them: reference c owns regions [offsets[c], offsets[c + 1]), in file order.  BED
@@ -2655,6 +2802,7 @@ _LADDER = _Mode("a coverage ladder", ("targets", "a depth report"), one_sentence
 _START_CAP = _Mode("a start cap", ("coverage thresholds", "a mean depth", "a proportion", "replicates", "a budget", "ceiling",
                                    "pair_aware", "template_aware", "targets", "a depth report", "a depth track",
                                    "a coverage ladder", "stratify", "dedup", "a coverage profile"))
+_AMPLICONS = _Mode("amplicon-aware downsampling", ("a start cap",) + _START_CAP.refuses, amplicon_files=True)
 
 _REGION_FIELDS = ("region_offsets", "region_starts", "region_ends", "region_caps")
 _COUNT_FIELDS = {"ladder_levels": "n_ladder_levels", "pair_stages": "n_pair_stages", "template_stages": "n_template_stages",
@@ -2696,7 +2844,7 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    proportional_report=None, fragment_depth=False, fragment_report=None, mean_depth=None,
                    budget_bases=None, mean_depth_targets=None, mean_depth_report=None, thresholds=None,
                    thresholds_tag="XC", thresholds_report=None, start_cap=None, start_cap_by_strand=False,
-                   start_cap_report=None):
+                   start_cap_report=None, primer_clip=False, per_amplicon=False, amplicon_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -2842,9 +2990,22 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     larger sizes).  Needs per_reference=True; not together with any other mode -- thresholds, a mean depth, a
     proportion, replicates, a budget, ceiling, pair_aware, template_aware, targets, report, track, ladder, stratify,
     dedup, profile --, amplicon files or "quasi-mcp-hip-quality" (ValueError); start_cap_by_strand or start_cap_report
-    without start_cap is a ValueError too.  None: nothing changes"""
+    without start_cap is a ValueError too.  None: nothing changes.
+    primer_clip / per_amplicon / amplicon_report (BamApiConfig::primer_clip, per_amplicon, amplicon_report_filepath):
+    amplicon-aware downsampling in one qmcp_hip_solve_amplicons_host call on the pairs that passed the ingest (its
+    FILTER included).  primer_clip=True counts depth on the reads clipped to their amplicon's insert -- from BED primers
+    [ls, le) and [rs, re) the amplicon stays [ls, re], the insert is [le, rs - 1]; a pair that leaves no insert is a
+    ValueError naming it -- so "M x" of output is M x after primer trimming.  per_amplicon=True solves every amplicon as
+    a coverage problem of its own (ARTIC's --normalise): it keeps more reads, and where inserts overlap the kept depth
+    reaches up to about twice M and more.  Clipping decides what COUNTS as depth, not what is written: the output holds
+    the original, unclipped records of the kept reads, completed by find_pairs as always.  amplicon_report (a path) gets
+    one line per amplicon (write_amplicon_report's TSV); alone it runs the entry with clipping off and pooled, which
+    selects what the plain flow selects.  They need bed, per_reference=True, amplicons_by_reference=True and
+    "quasi-mcp-hip"; not together with any other mode -- a start cap, thresholds, a mean depth, a proportion,
+    replicates, a budget, ceiling, pair_aware, template_aware, targets, report, track, ladder, stratify, dedup, profile
+    (ValueError).  False / None: nothing changes"""
     _need_host()
-    given = {"coverage thresholds": thresholds is not None,
+    given = {"a start cap": start_cap is not None, "coverage thresholds": thresholds is not None,
              "a mean depth": mean_depth is not None or budget_bases is not None, "a proportion": proportion is not None, "replicates": replicates is not None,
              "a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
              "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
@@ -2904,7 +3065,15 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         raise ValueError("thresholds_report needs thresholds")
     if start_cap is None and (start_cap_by_strand or start_cap_report is not None):
         raise ValueError("start_cap_by_strand and start_cap_report need start_cap")
-    if start_cap is not None:
+    if primer_clip or per_amplicon or amplicon_report is not None:
+        if not (bed and per_reference and amplicons_by_reference):
+            raise ValueError("primer_clip, per_amplicon and amplicon_report need bed, per_reference=True and "
+                             "amplicons_by_reference=True")
+        refuse(_AMPLICONS)
+        fields.update(bed=bed, tsv=tsv or None, amplicon_mode=None if amplicon_mode is None else int(amplicon_mode),
+                      amplicons_by_reference=True, primer_clip=bool(primer_clip), per_amplicon=bool(per_amplicon),
+                      amplicon_report=amplicon_report)
+    elif start_cap is not None:
         if not 1 <= int(start_cap) < 1 << 32:
             raise ValueError("start_cap must lie in 1 .. 2^32 - 1")
         need_per_reference(_START_CAP)

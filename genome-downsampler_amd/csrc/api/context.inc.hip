@@ -215,6 +215,11 @@ struct qmcp_hip_ctx {
     // entry's group column and capped mask
     DevBuf sc_tab, sc_stat, sc_bare, sc_keys[2], sc_vals[2], sc_hist, sc_spine, sc_flag, sc_head, sc_cnt, sc_surv, sc_words,
         sc_histo, sc_cs, sc_ce, sc_ci, sc_map, sc_maskc, sc_groups, sc_capm;
+    // amplicon assignment and clipping (api/amplicon_clip.inc.hip), all its own: the tables (offsets, the sorted table,
+    // contig lengths), the units' labels, the unit mask with its scanned word popcounts and their spine, the solve
+    // columns and the rebased columns (3 + 3), the compacted columns, the survivors' input units, the compact keep mask,
+    // the amplicons in use, the blocks' counters with their totals behind them, and the validation word
+    DevBuf ac_tab, ac_label, ac_keep, ac_words, ac_spine, ac_col[6], ac_comp[3], ac_map, ac_maskc, ac_used, ac_part, ac_err;
     // coverage profile (api/profile.inc.hip): a batch's need[] (min(cov, cap) per position, top bit = cut position), its
     // regions in global positions (starts | ends | caps), and the call's two counters (capped positions, demand)
     DevBuf pf_need, pf_tab, pf_stat;

@@ -32,6 +32,7 @@
 #include "stratified_plan.h"
 #include "dedup_plan.h"
 #include "amplicon_table.h"
+#include "amplicon_assign.h"
 #include "target_table.h"
 #include "cap_table.h"
 #include "pair_plan.h"
@@ -103,6 +104,9 @@
 //   replicates          (by_contig, depth_report) one read set split into disjoint downsamples: the batch loop at the
 //                       first coverage, every further replicate solved on the reads still free, replicate-major over the
 //                       one grouping's batches
+//   amplicon_clip       (amplicon_by_contig, dedup, depth_report) every unit assigned to one amplicon of its contig and
+//                       clipped to its insert: the assign pass, compaction, the by-contig solve pooled or per amplicon,
+//                       mates, the mask expanded back, and one depth row per amplicon through the depth report's pass
 #include "api/context.inc.hip"
 #include "api/radix_passes.inc.hip"
 #include "api/uniform_sweep.inc.hip"
@@ -135,3 +139,4 @@
 #include "api/thresholds.inc.hip"
 #include "api/replicates.inc.hip"
 #include "api/start_cap.inc.hip"
+#include "api/amplicon_clip.inc.hip"

@@ -441,6 +441,32 @@ void launch_sc_rank(hipStream_t st, const uint32_t* vals, uint32_t stride, const
 void launch_sc_kept_cells(hipStream_t st, const uint32_t* vals, uint32_t stride, const uint32_t* E, uint32_t n_act,
                           const uint64_t* mask, uint32_t* cnt, uint64_t* counters);
 
+// amplicon assignment and primer clipping (kernels/amplicon_clip.inc.hip; api/amplicon_clip.inc.hip drives it): the
+// units (pairs of reads, or single reads) validated, filtered, assigned to an amplicon of their contig (tab:
+// amplicon_assign.h's AssignTable::words on the device; at most kAcLdsMax amplicons are staged in LDS, more are read
+// from global memory) and clipped to its insert.  label: one word per unit; unit_keep: one bit per unit; cs / ce / ci:
+// the solve columns, one word per read; rs / re / ri (all NULL or all given): the columns rebased to the insert with the
+// amplicon as id; used: n_amp zeroed words; partials: ac_partial_rows() x kAcCounts words; totals: kAcCounts words, the
+// counters below; err as launch_bc_keys.  With pairs every column is read and written as uint2: 8-byte aligned.
+enum AcCount : uint32_t {
+    kAcAssigned = 0,    // units with an amplicon
+    kAcFiltered = 1,    // units dropped by the length / MAPQ filters
+    kAcNoAmplicon = 2,  // units that passed the filters and lie in no amplicon
+    kAcSeveral = 3,     // assigned units that more than one amplicon contains
+    kAcShortened = 4,   // reads that lost bases and kept some
+    kAcAway = 5,        // reads wholly outside the insert
+    kAcBases = 6,       // bases clipped off the reads of assigned units
+    kAcUnused = 7,      // amplicons no unit was assigned to (k_ac_totals counts them)
+    kAcCounts = 8
+};
+uint32_t ac_partial_rows();
+void launch_amplicon_clip(hipStream_t st, bool pairs, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
+                          const uint32_t* seq_lengths, const uint32_t* qualities, uint64_t n_units,
+                          const uint32_t* lengths, uint32_t n_contigs, const uint32_t* amp_offs, const uint32_t* tab,
+                          uint32_t n_amp, uint32_t min_length, uint32_t min_mapq, bool per_amplicon, uint32_t* label,
+                          uint64_t* unit_keep, uint32_t* cs, uint32_t* ce, uint32_t* ci, uint32_t* rs, uint32_t* re,
+                          uint32_t* ri, uint32_t* used, uint64_t* partials, uint64_t* totals, uint32_t* err);
+
 // pair-aware downsampling (kernels/pairs.inc.hip; api/pairs.inc.hip drives them), one batch of the by-contig grouping and
 // one stage after the first: the input-order mask of the kept set S as bits in the batch's grouped order (in_bits) and
 // its complement inside the batch (rest_bits: the stage's candidates), ceil(n / 64) words each; the events of the batch's

@@ -51,6 +51,8 @@
 //                            flags, cell ids, survivor / duplicate bits, family statistics, compaction of the survivors
 //   start_cap                at most K reads per (contig, start, group) cell before the solve: composite keys, every
 //                            cell's first position, survivor / capped bits by rank in cell, the kept members per cell
+//   amplicon_clip            amplicon-aware downsampling: one streaming pass that validates, filters, assigns every unit
+//                            to one amplicon of its contig and clips its reads to the insert; the counters' totals
 //   profile                  a cap that varies along the genome: need(p) = min(cov(p), cap(p)) per position with its cut
 //                            flag, and the cut-point scan over it
 //   pairs                    pair-aware downsampling: the kept set's bits in a batch's grouped order and their complement,
@@ -119,6 +121,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/stratified.inc.hip"
 #include "kernels/dedup.inc.hip"
 #include "kernels/start_cap.inc.hip"
+#include "kernels/amplicon_clip.inc.hip"
 #include "kernels/profile.inc.hip"
 #include "kernels/pairs.inc.hip"
 #include "kernels/templates.inc.hip"

@@ -75,6 +75,14 @@ bool read_primer_bed_by_chrom(const std::filesystem::path& path, ChromPrimerMap&
 struct ReferenceAmpliconSet {
     std::vector<std::uint32_t> offsets{0};
     std::vector<Index> starts, ends;
+    // What the primer-clipped entries (qmcp_hip_solve_amplicons_host) need besides: the insert of every amplicon --
+    // from BED primers [ls, le) and [rs, re) the amplicon stays [ls, re] (the reference's inclusive quirk) and the
+    // insert is [le, rs - 1], inclusive -- and the name of its left primer.  A pair whose primers touch or overlap has
+    // no insert (insert_start > insert_end there): empty_insert names the first such pair, and whoever asks for the
+    // inserts must refuse the set; the FILTER and GRADE never look at them.
+    std::vector<Index> insert_starts, insert_ends;
+    std::vector<std::string> left_names;
+    std::string empty_insert;
     std::size_t n_references() const { return offsets.size() - 1; }
     // r1 on reference c1, r2 on c2: both on one reference, inside one of its amplicons
     bool member_includes_both(std::uint32_t c1, const Read& r1, std::uint32_t c2, const Read& r2) const {

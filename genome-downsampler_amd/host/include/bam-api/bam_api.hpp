@@ -88,6 +88,17 @@ struct BamApiConfig {
     // other mode or with amplicon files (std::invalid_argument otherwise).  0: nothing changes.
     std::uint32_t start_cap = 0;
     bool start_cap_by_strand = false;
+    // Amplicon-aware downsampling (QuasiMcpHipSolver::solve_amplicons / qmcp_hip_solve_amplicons_host): primer_clip counts
+    // depth on the reads clipped to their amplicon's insert (the amplicon without its primers, from the BED), per_amplicon
+    // solves every amplicon as a coverage problem of its own ("every amplicon to M x"), amplicon_report_filepath gets one
+    // line per amplicon; the report alone runs the entry with clipping off and pooled.  Clipping decides what counts as
+    // depth, NOT what is written: the output holds the original, unclipped records of the kept reads, completed by
+    // find_pairs as always.  All three need per_reference, amplicons_by_reference and a BED; together with any other
+    // mode (targets, ladder, stratify_by, dedup, start cap, ...) the constructor throws std::invalid_argument, and so it
+    // does under primer_clip for a primer pair that leaves no insert, naming the pair.
+    bool primer_clip = false;
+    bool per_amplicon = false;
+    std::filesystem::path amplicon_report_filepath;
     // Pair-aware downsampling: the solve runs in stages that credit the coverage of the mates already kept
     // (QuasiMcpHipSolver::solve_pairs / qmcp_hip_solve_pairs_host), so the output -- whole pairs, written without a
     // further find_pairs -- stays near max_coverage instead of near twice that.  pair_stages: the stages' rising targets,
@@ -212,6 +223,11 @@ class BamApi {
     // BamApiConfig::start_cap (0: none) and start_cap_by_strand (the reads' strata column then holds the strand bit)
     std::uint32_t start_cap() const { return start_cap_; }
     bool start_cap_by_strand() const { return start_cap_by_strand_; }
+    // BamApiConfig::primer_clip, per_amplicon and amplicon_report_filepath; the amplicons matched to the references
+    bool primer_clip() const { return primer_clip_; }
+    bool per_amplicon() const { return per_amplicon_; }
+    const std::filesystem::path& amplicon_report_filepath() const { return amplicon_report_filepath_; }
+    const ReferenceAmpliconSet& reference_amplicons() const { return reference_amplicon_set_; }
     // BamApiConfig::pair_aware and pair_stages (empty: the default schedule)
     bool pair_aware() const { return pair_aware_; }
     const std::vector<std::uint32_t>& pair_stages() const { return pair_stages_; }
@@ -283,6 +299,8 @@ class BamApi {
     bool dedup_ = false;
     std::uint32_t start_cap_ = 0;
     bool start_cap_by_strand_ = false;
+    bool primer_clip_ = false, per_amplicon_ = false;
+    std::filesystem::path amplicon_report_filepath_;
     bool pair_aware_ = false;
     bool ceiling_ = false;
     std::optional<std::uint64_t> budget_reads_;

@@ -104,6 +104,15 @@ class QuasiMcpHipSolver : public Solver {
     std::unique_ptr<Solution> solve_start_cap(std::uint32_t required_cover, bam_api::BamApi& bam_api, std::uint32_t hist_bins);
     const qmcp_hip_start_cap_stats& last_start_cap_stats() const { return scstats_; }
     const std::vector<std::uint64_t>& last_start_cap_hist() const { return start_cap_hist_; }
+    // Amplicon-aware downsampling for the reads of a BamApi built with BamApiConfig::primer_clip, per_amplicon or
+    // amplicon_report_filepath: qmcp_hip_solve_amplicons_host on the pairs with QMCP_AMPLICONS_COMPLETE_PAIRS, the table
+    // and (under primer_clip) the inserts of the BamApi's reference amplicons, per amplicon or pooled.  The Solution holds
+    // whole pairs; last_amplicon_labels() has one label per pair, last_amplicon_rows() one row per amplicon over the
+    // insert the solve used.  Throws std::invalid_argument for a BamApi configured otherwise.
+    std::unique_ptr<Solution> solve_amplicons(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const qmcp_hip_amplicons_stats& last_amplicons_stats() const { return astats_; }
+    const std::vector<std::uint32_t>& last_amplicon_labels() const { return amplicon_labels_; }
+    const std::vector<qmcp_hip_depth_row>& last_amplicon_rows() const { return amplicon_rows_; }
     // Coverage profile for the reads of a per-reference BamApi: qmcp_hip_solve_profile_host with the regions in CSR form
     // per reference (offsets: one more entry than the file has references; inclusive bounds, disjoint per reference)
     // and required_cover as the default cap.  std::invalid_argument for reads without contig ids or a table of other
@@ -255,6 +264,9 @@ class QuasiMcpHipSolver : public Solver {
     std::vector<std::uint64_t> dedup_hist_;
     qmcp_hip_start_cap_stats scstats_{};
     std::vector<std::uint64_t> start_cap_hist_;
+    qmcp_hip_amplicons_stats astats_{};
+    std::vector<std::uint32_t> amplicon_labels_;
+    std::vector<qmcp_hip_depth_row> amplicon_rows_;
     qmcp_hip_profile_stats pstats_{};
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_ceiling_stats clstats_{};

@@ -117,6 +117,15 @@ typedef struct qmcp_host_downsample_request {
     int32_t start_cap_by_strand;
     uint32_t start_cap;
     const char* start_cap_report;
+    /* amplicon-aware downsampling (primer_clip, per_amplicon, amplicon_report): primer_clip != 0 counts depth on the
+     * reads clipped to their amplicon's insert, per_amplicon != 0 solves every amplicon as a coverage problem of its
+     * own; amplicon_report: one line per amplicon (chrom, amplicon, insert, left primer, units, reads kept, minimum
+     * and mean insert depth before and after, deficit positions); the report alone runs with clipping off, pooled.
+     * They need bed, per_reference and amplicons_by_reference and go with no other mode.  (These three stand in front
+     * of the proportion fields too.) */
+    int32_t primer_clip;
+    int32_t per_amplicon;
+    const char* amplicon_report;
     /* proportional downsampling (proportion): has_proportion != 0 asks for it -- every position keeps
      * ceil(cov * proportion_num / proportion_den) of its depth, positions at or below proportion_floor whole,
      * max_coverage the hard upper end; proportional_report: stat<TAB>value lines */

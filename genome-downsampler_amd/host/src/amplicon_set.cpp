@@ -124,7 +124,18 @@ bool build_reference_amplicon_set(ChromPrimerMap primers, const std::vector<std:
     for (const std::string& chrom : chroms)
         if (ref_of.find(chrom) == ref_of.end())
             return fail("BED chrom \"" + chrom + "\" names no reference of the BAM file (names must match exactly)");
-    std::vector<std::vector<Amplicon>> per(ref_names.size());
+    // an amplicon with what the primer-clipped entries need besides its bounds: the insert [left.end, right.start - 1]
+    // (the BED end is exclusive) and the left primer's name
+    struct Paired {
+        Amplicon amplicon;
+        Index insert_start, insert_end;  // insert_start > insert_end: the primers touch or overlap
+        std::string left_name, right_name;
+    };
+    std::vector<std::vector<Paired>> per(ref_names.size());
+    auto paired = [](const ChromPrimer& left, const ChromPrimer& right, const std::string& ln, const std::string& rn) {
+        const bool empty = right.start == 0 || left.end > right.start - 1;
+        return Paired{Amplicon(left.start, right.end), empty ? 1 : left.end, empty ? 0 : right.start - 1, ln, rn};
+    };
     if (pairs != nullptr) {
         for (const auto& names : *pairs) {
             const auto il = primers.find(names.first), ir = primers.find(names.second);
@@ -138,29 +149,37 @@ bool build_reference_amplicon_set(ChromPrimerMap primers, const std::vector<std:
             if (left.chrom != right.chrom)
                 return fail("TSV pair " + names.first + " / " + names.second + " crosses references: " + names.first +
                             " on " + left.chrom + ", " + names.second + " on " + right.chrom);
-            if (left.start > right.start) std::swap(left, right);
-            per[ref_of[left.chrom]].emplace_back(left.start, right.end);
+            const bool swapped = left.start > right.start;
+            if (swapped) std::swap(left, right);
+            per[ref_of[left.chrom]].push_back(paired(left, right, swapped ? names.second : names.first,
+                                                     swapped ? names.first : names.second));
         }
     } else {
         // name order within each chrom: the primers map is in name order already
-        std::map<std::string, std::vector<const ChromPrimer*>> by_chrom;
-        for (const auto& kv : primers) by_chrom[kv.second.chrom].push_back(&kv.second);
+        std::map<std::string, std::vector<const ChromPrimerMap::value_type*>> by_chrom;
+        for (const auto& kv : primers) by_chrom[kv.second.chrom].push_back(&kv);
         for (const auto& kv : by_chrom) {
-            const std::vector<const ChromPrimer*>& v = kv.second;
-            std::vector<Amplicon>& dst = per[ref_of[kv.first]];
+            const auto& v = kv.second;
+            std::vector<Paired>& dst = per[ref_of[kv.first]];
             for (std::size_t i = 0; i + 1 < v.size(); i += 2) {
-                const ChromPrimer* left = v[i];
-                const ChromPrimer* right = v[i + 1];
-                if (left->start > right->start) std::swap(left, right);
-                dst.emplace_back(left->start, right->end);
+                const auto* left = v[i];
+                const auto* right = v[i + 1];
+                if (left->second.start > right->second.start) std::swap(left, right);
+                dst.push_back(paired(left->second, right->second, left->first, right->first));
             }
         }
     }
     out = ReferenceAmpliconSet();
     for (const auto& v : per) {
-        for (const Amplicon& a : v) {
-            out.starts.push_back(a.start);
-            out.ends.push_back(a.end);
+        for (const Paired& a : v) {
+            out.starts.push_back(a.amplicon.start);
+            out.ends.push_back(a.amplicon.end);
+            out.insert_starts.push_back(a.insert_start);
+            out.insert_ends.push_back(a.insert_end);
+            out.left_names.push_back(a.left_name);
+            if (a.insert_start > a.insert_end && out.empty_insert.empty())
+                out.empty_insert = "primer pair " + a.left_name + " / " + a.right_name +
+                                   " leaves no insert: the primers touch or overlap";
         }
         out.offsets.push_back((std::uint32_t)out.starts.size());
     }

@@ -97,6 +97,32 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     } else if (config.start_cap_by_strand) {
         throw std::invalid_argument("start_cap_by_strand needs start_cap");
     }
+    if (config.primer_clip || config.per_amplicon || !config.amplicon_report_filepath.empty()) {
+        const auto no = [](const char* what) {
+            throw std::invalid_argument(std::string("amplicon-aware downsampling does not go together with ") + what);
+        };
+        if (!per_reference_ || !amplicons_by_reference_ || config.bed_filepath.empty())
+            throw std::invalid_argument("primer_clip, per_amplicon and amplicon_report need bed, per_reference and "
+                                        "amplicons_by_reference: a read is clipped by an amplicon of its own reference");
+        if (config.start_cap) no("a start cap");
+        if (config.thresholds_hi.has_value()) no("coverage thresholds");
+        if (config.mean_depth.has_value() || config.budget_bases.has_value()) no("a mean depth");
+        if (config.proportion.has_value()) no("a proportion");
+        if (config.replicates.has_value()) no("replicates");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value()) no("a budget");
+        if (config.ceiling) no("ceiling");
+        if (config.pair_aware) no("pair_aware");
+        if (config.template_aware) no("template_aware");
+        if (!config.targets_filepath.empty()) no("targets");
+        if (!config.depth_report_filepath.empty()) no("a depth report");
+        if (!config.depth_track_filepath.empty()) no("a depth track");
+        if (!config.coverage_ladder.empty()) no("a coverage ladder");
+        if (config.stratify_by != Stratify::NONE) no("stratify_by");
+        if (config.dedup) no("dedup");
+        primer_clip_ = config.primer_clip;
+        per_amplicon_ = config.per_amplicon;
+        amplicon_report_filepath_ = config.amplicon_report_filepath;
+    }
     if (!config.coverage_ladder.empty()) {
         if (!per_reference_)
             throw std::invalid_argument("a coverage ladder needs per_reference: its levels are solved one reference at "
@@ -413,6 +439,8 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
             if (!reference_amplicon_set_from_files(config.bed_filepath, config.tsv_filepath, names,
                                                    reference_amplicon_set_, &err))
                 throw std::invalid_argument(err);
+            if (primer_clip_ && !reference_amplicon_set_.empty_insert.empty())
+                throw std::invalid_argument(reference_amplicon_set_.empty_insert);
             amplicon_behaviour_ = config.amplicon_behaviour;
         }
         return;

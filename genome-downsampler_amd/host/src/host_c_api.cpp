@@ -165,6 +165,9 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
     cfg.dedup = q.dedup != 0;
     cfg.start_cap = q.start_cap;
     cfg.start_cap_by_strand = q.start_cap_by_strand != 0;
+    cfg.primer_clip = q.primer_clip != 0;
+    cfg.per_amplicon = q.per_amplicon != 0;
+    if (given(q.amplicon_report)) cfg.amplicon_report_filepath = q.amplicon_report;
     cfg.pair_aware = q.pair_aware != 0;
     if (q.pair_stages) cfg.pair_stages.assign(q.pair_stages, q.pair_stages + q.n_pair_stages);
     cfg.template_aware = q.template_aware != 0;
@@ -194,8 +197,9 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
 
 // Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
 // amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
-enum class Mode { START_CAP, THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+enum class Mode { AMPLICONS, START_CAP, THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
 Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (cfg.primer_clip || cfg.per_amplicon || !cfg.amplicon_report_filepath.empty()) return Mode::AMPLICONS;
     if (cfg.start_cap || cfg.start_cap_by_strand || given(q.start_cap_report)) return Mode::START_CAP;
     if (cfg.thresholds_hi || given(q.thresholds_tag) || given(q.thresholds_report)) return Mode::THRESHOLDS;
     if (cfg.mean_depth || cfg.budget_bases || given(q.mean_depth_targets) || given(q.mean_depth_report))
@@ -219,6 +223,7 @@ struct ModeWords {
 };
 ModeWords words_of(Mode mode) {
     switch (mode) {
+        case Mode::AMPLICONS: return {"amplicon-aware downsampling does not", "amplicon-aware downsampling"};
         case Mode::START_CAP: return {"a start cap does not", "start cap"};
         case Mode::THRESHOLDS: return {"coverage thresholds do not", "coverage thresholds"};
         case Mode::MEAN_DEPTH: return {"mean-depth downsampling does not", "mean-depth downsampling"};
@@ -273,7 +278,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
     if (given(q.fragment_report) && !cfg.fragment_depth) refuse("a fragment report needs fragment_depth");
     if (q.has_regions &&
         (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL ||
-         mode == Mode::MEAN_DEPTH || mode == Mode::THRESHOLDS))
+         mode == Mode::MEAN_DEPTH || mode == Mode::THRESHOLDS || mode == Mode::AMPLICONS))
         refuse(words.refuses + " go together with a coverage profile");
     if (mode != Mode::PLAIN && solver.uses_quality_of_reads()) refuse(words.refuses + " take a solver that grades by quality");
     if (mode != Mode::PLAIN && hip == nullptr) refuse("this solver has no " + words.noun);
@@ -343,6 +348,36 @@ bool write_start_cap_report(const char* path, const qmcp::QuasiMcpHipSolver& hip
     std::fprintf(f, "#size\tcells\n");
     for (std::uint32_t b = 0; b < kStartCapBins; ++b)
         std::fprintf(f, "%u\t%llu\n", b + 1, (unsigned long long)hip.last_start_cap_hist()[b]);
+    return std::fclose(f) == 0;
+}
+
+// One line per amplicon, in the order of the references and within a reference of the BED / TSV: chrom, amplicon start
+// and end, the insert the solve used (the amplicon itself without primer_clip), left primer, units assigned, reads kept
+// (of the written set), minimum and mean depth over the insert before and after, positions short of min(before, M)
+bool write_amplicon_report(const std::filesystem::path& path, const bam_api::ReferenceAmpliconSet& set,
+                           const std::vector<std::string>& names, const qmcp::QuasiMcpHipSolver& hip,
+                           const std::vector<bam_api::ReadIndex>& kept) {
+    const std::vector<std::uint32_t>& labels = hip.last_amplicon_labels();
+    const std::vector<qmcp_hip_depth_row>& rows = hip.last_amplicon_rows();
+    std::vector<std::uint64_t> units(rows.size(), 0), reads_kept(rows.size(), 0);
+    for (std::uint32_t l : labels)
+        if (l != QMCP_NO_AMPLICON) units[l]++;
+    for (bam_api::ReadIndex i : kept)
+        if (labels[i / 2] != QMCP_NO_AMPLICON) reads_kept[labels[i / 2]]++;
+    std::FILE* f = std::fopen(path.c_str(), "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#chrom\tamplicon_start\tamplicon_end\tinsert_start\tinsert_end\tleft_primer\tunits\treads_kept\t"
+                    "min_depth_in\tmean_depth_in\tmin_depth_kept\tmean_depth_kept\tdeficit_positions\n");
+    for (std::size_t c = 0; c < set.n_references(); ++c)
+        for (std::uint32_t k = set.offsets[c]; k < set.offsets[c + 1]; ++k) {
+            const qmcp_hip_depth_row& r = rows[k];
+            const double positions = (double)r.positions;
+            std::fprintf(f, "%s\t%llu\t%llu\t%u\t%u\t%s\t%llu\t%llu\t%u\t%.6f\t%u\t%.6f\t%llu\n", names[c].c_str(),
+                         (unsigned long long)set.starts[k], (unsigned long long)set.ends[k], r.start, r.end,
+                         set.left_names[k].c_str(), (unsigned long long)units[k], (unsigned long long)reads_kept[k],
+                         r.min_in, (double)r.sum_in / positions, r.min_kept, (double)r.sum_kept / positions,
+                         (unsigned long long)r.deficit_positions);
+        }
     return std::fclose(f) == 0;
 }
 
@@ -530,6 +565,7 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         case Mode::STRATIFIED: write_reads(*solver->solve(M, api), true, q.out_path); break;
         case Mode::DEDUP: write_reads(*hip->solve_dedup(M, api, kDedupBins), true, q.out_path); break;
         case Mode::START_CAP: write_reads(*hip->solve_start_cap(M, api, kStartCapBins), true, q.out_path); break;
+        case Mode::AMPLICONS: write_reads(*hip->solve_amplicons(M, api), true, q.out_path); break;
         case Mode::PROFILE: write_reads(*hip->solve_profile(M, api, offsets, starts, ends, caps), true, q.out_path); break;
         case Mode::PROPORTIONAL: write_reads(*hip->solve_proportional(M, api), true, q.out_path); break;
         case Mode::PAIRS: write_reads(*hip->solve_pairs(M, api), false, q.out_path); break;
@@ -584,6 +620,13 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
     if (mode == Mode::DEDUP && given(q.dedup_report)) reported = write_dedup_report(q.dedup_report, *hip);
     if (mode == Mode::START_CAP && given(q.start_cap_report))
         reported = write_start_cap_report(q.start_cap_report, *hip, written[0]);
+    if (mode == Mode::AMPLICONS && given(q.amplicon_report)) {
+        std::vector<std::string> names;
+        std::vector<std::uint32_t> lengths;
+        std::string why;
+        reported = bam_api::read_bam_references(q.in_path, names, lengths, &why) &&
+                   write_amplicon_report(q.amplicon_report, api.reference_amplicons(), names, *hip, kept);
+    }
     if (mode == Mode::CEILING && given(q.ceiling_report))
         reported = write_ceiling_report(q.ceiling_report, hip->last_ceiling_stats(), written[0]);
     if (mode == Mode::TEMPLATES && given(q.fragment_report))
@@ -952,6 +995,42 @@ std::int64_t qmcp_host_amplicons_by_reference(const char* bed_path, const char* 
             starts_out[i] = static_cast<std::uint32_t>(set.starts[i]);
             ends_out[i] = static_cast<std::uint32_t>(set.ends[i]);
         }
+        return static_cast<std::int64_t>(set.starts.size());
+    } catch (const std::bad_alloc&) {
+        return -3;
+    }
+}
+
+// The same set's inserts and left primer names, parallel to qmcp_host_amplicons_by_reference's starts / ends:
+// insert_starts_out / insert_ends_out (cap entries, inclusive: from BED primers [ls, le) and [rs, re) the insert is
+// [le, rs - 1]) and the names '\n'-separated in names_out (capacity names_cap).  Returns the number of amplicons, -2 if
+// a capacity is too small, -4 with the message in err -- also for a primer pair that leaves no insert, naming it.
+std::int64_t qmcp_host_amplicon_inserts_by_reference(const char* bed_path, const char* tsv_path,
+                                                     const char* const* ref_names, std::uint64_t n_refs,
+                                                     std::uint32_t* insert_starts_out, std::uint32_t* insert_ends_out,
+                                                     std::uint64_t cap, char* names_out, std::size_t names_cap, char* err,
+                                                     std::size_t err_cap) {
+    try {
+        std::vector<std::string> names;
+        for (std::uint64_t r = 0; r < n_refs; ++r) names.emplace_back(ref_names[r]);
+        bam_api::ReferenceAmpliconSet set;
+        std::string msg;
+        if (!bam_api::reference_amplicon_set_from_files(bed_path, tsv_path ? tsv_path : "", names, set, &msg)) {
+            copy_err(msg, err, err_cap);
+            return -4;
+        }
+        if (!set.empty_insert.empty()) {
+            copy_err(set.empty_insert, err, err_cap);
+            return -4;
+        }
+        std::string all;
+        for (const std::string& n : set.left_names) { all += n; all += '\n'; }
+        if (set.starts.size() > cap || all.size() + 1 > names_cap) return -2;
+        for (std::size_t i = 0; i < set.starts.size(); ++i) {
+            insert_starts_out[i] = static_cast<std::uint32_t>(set.insert_starts[i]);
+            insert_ends_out[i] = static_cast<std::uint32_t>(set.insert_ends[i]);
+        }
+        std::memcpy(names_out, all.c_str(), all.size() + 1);
         return static_cast<std::int64_t>(set.starts.size());
     } catch (const std::bad_alloc&) {
         return -3;

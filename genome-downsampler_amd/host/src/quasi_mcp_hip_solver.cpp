@@ -268,6 +268,51 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_start_cap(std::uint32_t requi
     return finish(mask, n, t0);
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_amplicons(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    const bam_api::ReferenceAmpliconSet& set = bam_api.reference_amplicons();
+    need_per_reference(bam_api.primer_clip() || bam_api.per_amplicon() || !bam_api.amplicon_report_filepath().empty(), reads,
+                       "amplicon-aware downsampling needs a BamApi built with BamApiConfig::primer_clip, per_amplicon or "
+                       "amplicon_report_filepath");
+    if (set.n_references() != reads.contig_lengths.size()) throw std::invalid_argument("amplicons of other references");
+    if (reads.qualities.size() != n || reads.seq_lengths.size() != n)
+        throw std::invalid_argument("reads without one quality and one length each");
+    context();
+    const Columns c = narrowed(reads);
+    const auto narrow = [](const std::vector<bam_api::Index>& v) {
+        std::vector<std::uint32_t> out(v.size());
+        for (std::size_t k = 0; k < v.size(); ++k) {
+            if (v[k] > std::numeric_limits<std::uint32_t>::max()) throw std::invalid_argument("an amplicon beyond 2^32");
+            out[k] = (std::uint32_t)v[k];
+        }
+        return out;
+    };
+    const std::vector<std::uint32_t> a0 = narrow(set.starts), a1 = narrow(set.ends);
+    std::vector<std::uint32_t> i0, i1;
+    if (bam_api.primer_clip()) {
+        i0 = narrow(set.insert_starts);
+        i1 = narrow(set.insert_ends);
+    }
+    amplicon_labels_.assign(n / 2, QMCP_NO_AMPLICON);
+    amplicon_rows_.assign(a0.size(), qmcp_hip_depth_row{});
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    // (the ingest applied the length / MAPQ filters and the FILTER already: the entry sees the pairs that passed)
+    ok_or_throw("qmcp_hip_solve_amplicons_host",
+                qmcp_hip_solve_amplicons_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), nullptr, nullptr,
+                                              n, reads.contig_lengths.data(), n_contigs(reads), set.offsets.data(),
+                                              a0.data(), a1.data(), bam_api.primer_clip() ? i0.data() : nullptr,
+                                              bam_api.primer_clip() ? i1.data() : nullptr, 0, 0, required_cover,
+                                              QMCP_AMPLICONS_COMPLETE_PAIRS |
+                                                  (bam_api.per_amplicon() ? QMCP_AMPLICONS_PER_AMPLICON : 0u),
+                                              mask.data(), amplicon_labels_.data(), amplicon_rows_.data(), &stats_,
+                                              &astats_));
+    breakdown_ = qmcp_hip_host_breakdown{};
+    // the context holds the completed mask: at most two reads per read the solve kept
+    return expand(n, std::min<std::uint64_t>(n, 2 * stats_.n_kept), t0);
+}
+
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_profile(std::uint32_t required_cover, bam_api::BamApi& bam_api,
                                                            const std::vector<std::uint32_t>& offsets,
                                                            const std::vector<std::uint32_t>& region_starts,

@@ -1553,6 +1553,109 @@ int qmcp_hip_solve_start_cap_device(qmcp_hip_ctx* ctx,
                                     uint64_t* hist_out, uint32_t hist_bins, void* hip_stream, qmcp_hip_stats* stats,
                                     qmcp_hip_start_cap_stats* cstats);
 
+/* Amplicon-aware downsampling: primer-clipped depth, optionally one coverage problem per amplicon.  On a tiled amplicon
+ * panel the primer bases are synthetic and every pipeline masks them before calling variants, so depth that counts them
+ * overstates what is left after trimming.  Here every unit of reads is assigned to ONE amplicon of its contig, its reads
+ * are clipped to that amplicon's insert (the amplicon without its primers), and the clipped reads are solved.  starts,
+ * ends, contig_ids, seq_lengths, qualities, n_reads, contig_lengths / n_contigs, amp_offsets / amp_starts / amp_ends,
+ * min_length, min_mapq, max_coverage, keep_mask_out, stats, limits (n_reads <= 2^31, n_contigs <= 2^24) and errors are
+ * those of qmcp_hip_filter_solve_by_contig_host.  In addition:
+ *   amp_offsets        must be given (QMCP_EINVAL when NULL): this entry is about amplicons; filtering without them
+ *                      stays with qmcp_hip_filter_solve_by_contig_host.
+ *   amp_insert_starts, amp_insert_ends  one word per amplicon, inclusive, parallel to amp_starts / amp_ends; both NULL:
+ *                      the insert is the amplicon and nothing is clipped.  amp_start <= insert_start <= insert_end <=
+ *                      amp_end must hold for every amplicon: otherwise QMCP_EINVAL names the first one that breaks it,
+ *                      before anything is copied.
+ *   flags              QMCP_AMPLICONS_SINGLE_END, QMCP_AMPLICONS_PER_AMPLICON, QMCP_AMPLICONS_COMPLETE_PAIRS; unknown
+ *                      bits fail with QMCP_EINVAL.
+ *   amplicon_of_out    may be NULL; one uint32 per unit in host memory (both entries).
+ *   amplicon_rows      may be NULL; one qmcp_hip_depth_row per amplicon in host memory (both entries).
+ *   astats             may be NULL.
+ * UNIT: the pair of reads 2q, 2q + 1 (n_reads even, QMCP_EINVAL otherwise); with QMCP_AMPLICONS_SINGLE_END one read, and
+ * n_reads may be odd.
+ * FILTERING: a unit passes min_length / min_mapq exactly as in the FILTER (every read of it, when the column is given).
+ * ASSIGNMENT: a unit that passed the filters is assigned to an amplicon of its contig that contains all of its reads:
+ * every read placed, all on one contig, amp_start <= the smallest start and amp_end >= the largest end (the OUTER bounds,
+ * inclusive: Amplicon::includes, as in the FILTER).  If several amplicons contain it: the greatest start, then the
+ * smallest end, then the smallest index in the caller's table; the unit also counts in units_in_several.  A unit that no
+ * amplicon contains has none (QMCP_NO_AMPLICON) and is dropped.
+ * CLIPPING: every read of an assigned unit is intersected with its amplicon's insert.  A read wholly inside a primer is
+ * unplaced for the solve: it is never selected itself and comes back only through mate completion.
+ * SOLVE, pooled (default): qmcp_hip_solve_by_contig_host on the clipped reads of the assigned units, in genome
+ * coordinates, in input order -- step 3 of qmcp_hip_filter_solve_by_contig_host on the clipped columns.
+ * SOLVE, QMCP_AMPLICONS_PER_AMPLICON: every amplicon is a coverage problem of its own: its assigned reads, rebased to the
+ * insert (start - insert_start), solved in input order on a contig of the insert's length -- the by-contig solve with
+ * the amplicon's index as contig id; the mask is the union.  At most 2^24 amplicons then, and whenever amplicon_rows is
+ * given (QMCP_ERANGE beyond).  It keeps more reads than the pooled solve, and where inserts overlap the kept depth can
+ * reach the sum of the overlapping amplicons' caps.
+ * MATES: QMCP_AMPLICONS_COMPLETE_PAIRS completes the mates of the kept reads as the FILTER flow's complete_pairs does;
+ * together with QMCP_AMPLICONS_SINGLE_END it is QMCP_EINVAL.
+ * OUTPUTS: keep_mask_out in input order.  amplicon_of_out[u]: the amplicon's index in the caller's table, or
+ * QMCP_NO_AMPLICON.  amplicon_rows[k], in the caller's table order, covers the insert of amplicon k: contig = k, start /
+ * end = the insert in genome coordinates; the `in` fields are the depth of the clipped reads assigned to k, the `kept`
+ * fields that of those in the FINAL mask (after completion), the deficits are against min(in, max_coverage).  The rows
+ * come from the depth report's device pass over the rebased columns (its limit applies: n_reads < 2^31); nothing per
+ * position crosses the link.
+ * PROMISES: (1) with both insert arrays NULL, pooled, the keep mask is qmcp_hip_filter_solve_by_contig_host's bit for bit
+ * for the same arguments, with and without completion.  (2) With disjoint amplicons (an uncovered base between any two),
+ * inserts NULL and every unit inside one amplicon, both modes give the same mask.  (3) Single-end, inserts NULL, one
+ * amplicon spanning each whole contig: the mask is qmcp_hip_solve_by_contig_host's.  (4) The same input gives the same
+ * outputs, run to run.
+ * VALIDATION: every read is validated as the FILTER does -- those of dropped units too -- before any output is written:
+ * a bad contig id gives QMCP_EINVAL, a bad read QMCP_EREAD, and no output buffer has been touched.  The same holds for
+ * everything the call refuses from its arguments.  It does NOT hold for a failure after validation (an allocation or a
+ * HIP error in the solve or in the rows' pass): the device entry's mask may then have been written; labels, rows and
+ * stats are still untouched.
+ * HOW: the host sorts each contig's amplicons by (start ascending, end descending, index descending) and keeps the
+ * running maximum of the ends.  One streaming kernel validates, filters, finds the last amplicon starting at or before
+ * the unit's smallest start by binary search and walks backwards to the first container -- one or two steps on a tiled
+ * panel, linear in the contig's amplicons on a deeply nested table --, clips, and writes the label, one keep bit per unit
+ * and the clipped columns.  Up to 2 560 amplicons are staged in LDS (60 KiB, two workgroups a CU); larger tables are read
+ * from global memory.  The surviving units are compacted in input order, solved, and the mask expanded back.
+ * stats (may be NULL) are the inner solve's: n_reads counts the reads of the assigned units.
+ * The pass is blocking (no _begin / _end form); a context with a pending qmcp_hip_solve_device_begin is refused.  The
+ * device entry takes the five columns and the mask in device memory (tables, labels, rows and stats stay on the host)
+ * and is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is.  With pairs its kernel reads a pair as one
+ * 8-byte word: columns that are not 8-byte aligned are REFUSED with QMCP_EINVAL (single-end takes any 4-byte alignment).
+ * The host entry leaves the keep mask in the context. */
+#define QMCP_AMPLICONS_SINGLE_END 1u
+#define QMCP_AMPLICONS_PER_AMPLICON 2u
+#define QMCP_AMPLICONS_COMPLETE_PAIRS 4u
+#define QMCP_NO_AMPLICON 0xFFFFFFFFu
+typedef struct qmcp_hip_amplicons_stats {
+    uint64_t units;               /* pairs, or reads with QMCP_AMPLICONS_SINGLE_END                                    */
+    uint64_t units_assigned;      /* units with an amplicon: what the solve sees                                       */
+    uint64_t units_filtered;      /* units dropped by min_length / min_mapq                                            */
+    uint64_t units_no_amplicon;   /* units that passed the filters and lie in no amplicon                              */
+    uint64_t units_in_several;    /* assigned units that more than one amplicon contains                               */
+    uint64_t reads_shortened;     /* reads of assigned units that lost bases and kept some                             */
+    uint64_t reads_clipped_away;  /* reads of assigned units wholly outside the insert                                 */
+    uint64_t bases_clipped;       /* bases taken off the reads of assigned units                                       */
+    uint64_t amplicons;           /* amplicons in the caller's table                                                   */
+    uint64_t amplicons_unused;    /* amplicons no unit was assigned to                                                 */
+    float ms_assign;              /* device time of the assign step (k_amplicon_clip and its totals)                   */
+    float ms_report;              /* device time of the rows' pass; 0 without amplicon_rows                            */
+} qmcp_hip_amplicons_stats;
+int qmcp_hip_solve_amplicons_host(qmcp_hip_ctx* ctx,
+                                  const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                                  const uint32_t* seq_lengths, const uint32_t* qualities, uint64_t n_reads,
+                                  const uint32_t* contig_lengths, uint32_t n_contigs, const uint32_t* amp_offsets,
+                                  const uint32_t* amp_starts, const uint32_t* amp_ends,
+                                  const uint32_t* amp_insert_starts, const uint32_t* amp_insert_ends,
+                                  uint32_t min_length, uint32_t min_mapq, uint32_t max_coverage, uint32_t flags,
+                                  uint64_t* keep_mask_out, uint32_t* amplicon_of_out, qmcp_hip_depth_row* amplicon_rows,
+                                  qmcp_hip_stats* stats, qmcp_hip_amplicons_stats* astats);
+int qmcp_hip_solve_amplicons_device(qmcp_hip_ctx* ctx,
+                                    const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                    const uint32_t* d_seq_lengths, const uint32_t* d_qualities, uint64_t n_reads,
+                                    const uint32_t* contig_lengths, uint32_t n_contigs, const uint32_t* amp_offsets,
+                                    const uint32_t* amp_starts, const uint32_t* amp_ends,
+                                    const uint32_t* amp_insert_starts, const uint32_t* amp_insert_ends,
+                                    uint32_t min_length, uint32_t min_mapq, uint32_t max_coverage, uint32_t flags,
+                                    uint64_t* d_keep_mask_out, uint32_t* amplicon_of_out,
+                                    qmcp_hip_depth_row* amplicon_rows, void* hip_stream, qmcp_hip_stats* stats,
+                                    qmcp_hip_amplicons_stats* astats);
+
 #ifdef __cplusplus
 }
 #endif
