@@ -28,7 +28,7 @@ $(LIBDIR)/qmcp_kernels.o: $(CSRC)/qmcp_kernels.hip $(CSRC)/qmcp_kernels.h $(CSRC
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/qmcp_api.o: $(CSRC)/qmcp_api.hip $(wildcard $(CSRC)/api/*.inc.hip) $(CSRC)/qmcp_kernels.h $(CSRC)/sweep_plan.h $(CSRC)/by_contig_plan.h $(CSRC)/ladder_plan.h $(CSRC)/stratified_plan.h $(CSRC)/dedup_plan.h $(CSRC)/amplicon_table.h $(CSRC)/amplicon_assign.h $(CSRC)/target_table.h $(CSRC)/cap_table.h $(CSRC)/pair_plan.h $(CSRC)/replicates_plan.h $(CSRC)/fragment_plan.h $(CSRC)/budget_plan.h $(CSRC)/thresholds_plan.h $(CSRC)/pm_grid_plan.h $(CSRC)/solve_words.h include/qmcp_hip.h
+$(LIBDIR)/qmcp_api.o: $(CSRC)/qmcp_api.hip $(wildcard $(CSRC)/api/*.inc.hip) $(CSRC)/qmcp_kernels.h $(CSRC)/sweep_plan.h $(CSRC)/by_contig_plan.h $(CSRC)/ladder_plan.h $(CSRC)/stratified_plan.h $(CSRC)/tiers_plan.h $(CSRC)/dedup_plan.h $(CSRC)/amplicon_table.h $(CSRC)/amplicon_assign.h $(CSRC)/target_table.h $(CSRC)/cap_table.h $(CSRC)/pair_plan.h $(CSRC)/replicates_plan.h $(CSRC)/fragment_plan.h $(CSRC)/budget_plan.h $(CSRC)/thresholds_plan.h $(CSRC)/pm_grid_plan.h $(CSRC)/solve_words.h include/qmcp_hip.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "qmcp_hip_solve_proportional_host", "qmcp_hip_solve_proportional_device",
     "qmcp_hip_solve_start_cap_host", "qmcp_hip_solve_start_cap_device",
     "qmcp_hip_solve_amplicons_host", "qmcp_hip_solve_amplicons_device",
+    "qmcp_hip_solve_tiers_host", "qmcp_hip_solve_tiers_device",
 )
 
 QMCP_OK = 0
@@ -86,6 +87,8 @@ NO_AMPLICON = 0xFFFFFFFF  # QMCP_NO_AMPLICON: the label of a unit that no amplic
 AMPLICON_LDS_MAX = 2560  # qmcp::kAcLdsMax: the largest amplicon table the assign kernel stages in LDS
 TRACK_IN, TRACK_KEPT, TRACK_SHORT_ONLY, TRACK_SKIP_ZERO = 1, 2, 4, 8  # QMCP_TRACK_*
 TRACK_FIRST_CAPACITY = 1 << 22  # records Solver.depth_track offers first (96 MiB); beyond it, one more call at the exact count
+NO_TIER = 0xFFFFFFFF  # QMCP_NO_TIER: the tier of a read that belongs to no tier (never kept)
+TIERS_MAX = 16  # QMCP_TIERS_MAX
 STRATUM_TALLY_TILE = 1024  # qmcp::kStratumTallyTile: the grouped records one workgroup of k_st_tally reduces
 
 
@@ -415,6 +418,31 @@ class StratumRow(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TierRow(C.Structure):
+    """qmcp_hip_tier_row: a tier's placed reads, how many of them are kept, the bases of both; for a tier after the first
+    the sum of need_t, the positions with need_t > 0 and those where its coverage exceeds max(0, M - credit_t); the solver
+    calls that queued a sweep and their device time"""
+    _fields_ = [("n_reads", C.c_uint64), ("n_kept", C.c_uint64), ("bases_in", C.c_uint64), ("bases_kept", C.c_uint64),
+                ("demand", C.c_uint64), ("asked_positions", C.c_uint64), ("capped_positions", C.c_uint64),
+                ("sweeps", C.c_uint32), ("ms_stage", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TiersStats(C.Structure):
+    """qmcp_hip_tiers_stats: the tiers of the call, those that kept a read, the reads with NO_TIER, and the call's device
+    time outside its solver calls"""
+    _fields_ = [("n_tiers", C.c_uint32), ("tiers_used", C.c_uint32), ("reads_untiered", C.c_uint64),
+                ("ms_tiers", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+assert C.sizeof(TierRow) == 64 and C.sizeof(TiersStats) == 24
+
+
 class DedupStats(C.Structure):
     """qmcp_hip_dedup_stats: what the duplicate pass before the solve found (units: placed reads, or pairs with a placed
     mate; families: distinct cells / signatures; reads_survived: reads handed to the inner solve)"""
@@ -514,6 +542,7 @@ class DownsampleRequest(C.Structure):
                                           "start_cap_by_strand")]
         + [("start_cap", C.c_uint32), ("start_cap_report", C.c_char_p)]
         + [("primer_clip", C.c_int32), ("per_amplicon", C.c_int32), ("amplicon_report", C.c_char_p)]
+        + [("mapq_tiers", C.POINTER(C.c_uint32)), ("n_mapq_tiers", C.c_uint32), ("tiers_report", C.c_char_p)]
         + [("proportional_report", C.c_char_p), ("proportion_num", C.c_uint32), ("proportion_den", C.c_uint32),
            ("proportion_floor", C.c_uint32), ("has_proportion", C.c_int32)])
 
@@ -618,6 +647,11 @@ _hip.qmcp_hip_solve_ladder_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p
                                               C.POINTER(LadderStats)]
 _hip.qmcp_hip_solve_stratified_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32,
                                                 _u32p, C.c_uint32, _u64p, C.POINTER(StratumRow), C.POINTER(Stats)]
+_hip.qmcp_hip_solve_tiers_host.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, _u64p, C.POINTER(TierRow), C.POINTER(Stats), C.POINTER(TiersStats)]
+_hip.qmcp_hip_solve_tiers_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _u32p,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(TierRow), C.c_void_p,
+                                             C.POINTER(Stats), C.POINTER(TiersStats)]
 _hip.qmcp_hip_solve_stratified_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                   _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_void_p,
                                                   C.POINTER(StratumRow), C.c_void_p, C.POINTER(Stats)]
@@ -874,6 +908,8 @@ class Solver:
         self.last_target_stats = None
         self.last_ladder_stats = None
         self.last_stratum_rows = None
+        self.last_tier_rows = None
+        self.last_tiers_stats = None
         self.last_dedup_stats = None
         self.last_start_cap_stats = None
         self.last_amplicons_stats = None
@@ -1112,6 +1148,42 @@ class Solver:
                                                      _p32(lengths), lengths.size, _p32(caps), caps.size,
                                                      C.c_void_p(d_mask), rows, C.c_void_p(stream), C.byref(st)))
         self.last_stats, self.last_stratum_rows = st, list(rows)[:caps.size]
+        return st
+
+    def solve_tiers(self, starts, ends, contig_ids, tiers, contig_lengths, max_coverage, n_tiers):
+        """the best tier first, worse tiers only where the better ones leave the depth short of min(coverage,
+        max_coverage) (qmcp_hip_solve_tiers_host): tiers[i] < n_tiers names read i's tier, 0 the best, NO_TIER a read
+        that is never kept.  Tier 0 is solve_by_contig of its reads alone; tier t is the canonical selection of its reads
+        alone under need_t = min(its coverage, max(0, max_coverage - the depth of the earlier tiers' kept reads)).  The
+        kept depth is >= min(coverage of all tiered reads, max_coverage) everywhere.  -> host keep bitmask in INPUT
+        order; last_stats (tier 0's solves), last_tier_rows (a list of TierRow, one per tier), last_tiers_stats"""
+        starts, ends, ids, tiers = _u32(starts), _u32(ends), _u32(contig_ids), _u32(tiers)
+        n = starts.size
+        assert ends.size == n and ids.size == n and tiers.size == n, \
+            "starts, ends, contig_ids and tiers must have one entry per read"
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        mask = np.zeros(max(mask_words(n), 1), dtype=np.uint64)
+        rows = (TierRow * max(int(n_tiers), 1))()
+        st, ts = Stats(), TiersStats()
+        column = tiers if n else np.zeros(1, np.uint32)   # (tiers == NULL is refused, also without reads)
+        _check(_hip.qmcp_hip_solve_tiers_host(self._ctx, _p32(starts), _p32(ends), _p32(ids), _p32(column), n, _p32(lengths),
+                                              lengths.size, int(max_coverage), int(n_tiers), _p64(mask), rows, C.byref(st),
+                                              C.byref(ts)))
+        self.last_stats, self.last_tier_rows, self.last_tiers_stats = st, list(rows)[:int(n_tiers)], ts
+        return mask[:mask_words(n)]
+
+    def solve_tiers_device(self, d_starts, d_ends, d_contig_ids, d_tiers, n_reads, contig_lengths, max_coverage, n_tiers,
+                           d_mask, stream=0):
+        """the same on device pointers (ints); the input-order mask is written to d_mask, the rows come back to the host
+        (last_tier_rows, last_tiers_stats).  Returns the stats"""
+        lengths = np.atleast_1d(np.ascontiguousarray(contig_lengths, dtype=np.uint32))
+        rows = (TierRow * max(int(n_tiers), 1))()
+        st, ts = Stats(), TiersStats()
+        _check(_hip.qmcp_hip_solve_tiers_device(self._ctx, C.c_void_p(d_starts), C.c_void_p(d_ends), C.c_void_p(d_contig_ids),
+                                                C.c_void_p(d_tiers), int(n_reads), _p32(lengths), lengths.size,
+                                                int(max_coverage), int(n_tiers), C.c_void_p(d_mask), rows,
+                                                C.c_void_p(stream), C.byref(st), C.byref(ts)))
+        self.last_stats, self.last_tier_rows, self.last_tiers_stats = st, list(rows)[:int(n_tiers)], ts
         return st
 
     def solve_dedup(self, starts, ends, contig_ids, contig_lengths, max_coverage, tags=None, qualities=None, pairs=False,
@@ -2379,6 +2451,40 @@ DEPTH_REPORT_COLUMNS = ("kind", "reference", "start", "end", "positions", "mean_
                         "min_kept", "max_kept", "capped_positions", "deficit_positions", "deficit_sum")
 
 
+def tiers_from_mapq(mapq, thresholds):
+    """MAPQ bands as tiers for Solver.solve_tiers: thresholds must fall strictly (e.g. [30, 10, 0]); mapq >=
+    thresholds[0] is tier 0, thresholds[0] > mapq >= thresholds[1] tier 1, and so on; a value below the last threshold
+    is NO_TIER.  -> uint32 array, one tier per read; the number of tiers is len(thresholds)"""
+    th = [int(x) for x in np.atleast_1d(thresholds).tolist()]
+    if not th or any(x < 0 for x in th):
+        raise ValueError("thresholds must be a non-empty list of non-negative MAPQ values")
+    if any(a <= b for a, b in zip(th, th[1:])):
+        raise ValueError(f"thresholds must fall strictly, not {th}")
+    if len(th) > TIERS_MAX:
+        raise ValueError(f"at most {TIERS_MAX} tiers, not {len(th)}")
+    q = np.asarray(mapq).astype(np.int64)
+    rising = np.array(th[::-1], dtype=np.int64)
+    at_least = np.searchsorted(rising, q, side="right")         # the thresholds a value reaches
+    return np.where(at_least == 0, NO_TIER, len(th) - at_least).astype(np.uint32)
+
+
+def write_tiers_report(path, rows, bands, total_length, records_written=None, mates_added=None):
+    """the TSV of a tiered solve: a '#'-prefixed header line, then one line per tier -- its band (`bands`: one label per
+    tier, e.g. "mapq>=30"), reads, kept, mean depth before and after (bases / total_length, six decimals), demand and
+    asked positions --, then records_written and mates_added as name<TAB>value lines when given.  rows: a list of
+    TierRow"""
+    total = float(total_length) if total_length else 1.0
+    with open(path, "w") as out:
+        out.write("#tier\tband\treads\tkept\tmean_depth_in\tmean_depth_kept\tdemand\tasked_positions\n")
+        for t, (row, band) in enumerate(zip(rows, bands)):
+            out.write(f"{t}\t{band}\t{row.n_reads}\t{row.n_kept}\t{row.bases_in / total:.6f}\t"
+                      f"{row.bases_kept / total:.6f}\t{row.demand}\t{row.asked_positions}\n")
+        if records_written is not None:
+            out.write(f"records_written\t{int(records_written)}\n")
+        if mates_added is not None:
+            out.write(f"mates_added\t{int(mates_added)}\n")
+
+
 def write_depth_report(path, report, reference_names):
     """a DepthReport as TSV: a '#'-prefixed header line (DEPTH_REPORT_COLUMNS), then one line per contig row and one per
     region row -- start 0-based, end exclusive (BED style), the means with six decimals.  Histograms, when the report
@@ -2803,10 +2909,11 @@ _START_CAP = _Mode("a start cap", ("coverage thresholds", "a mean depth", "a pro
                                    "pair_aware", "template_aware", "targets", "a depth report", "a depth track",
                                    "a coverage ladder", "stratify", "dedup", "a coverage profile"))
 _AMPLICONS = _Mode("amplicon-aware downsampling", ("a start cap",) + _START_CAP.refuses, amplicon_files=True)
+_TIERS = _Mode("tiered downsampling", ("amplicon-aware downsampling",) + _AMPLICONS.refuses)
 
 _REGION_FIELDS = ("region_offsets", "region_starts", "region_ends", "region_caps")
 _COUNT_FIELDS = {"ladder_levels": "n_ladder_levels", "pair_stages": "n_pair_stages", "template_stages": "n_template_stages",
-                 "replicates_further": "n_replicates_further"}
+                 "replicates_further": "n_replicates_further", "mapq_tiers": "n_mapq_tiers"}
 
 
 def _downsample_request(**fields):
@@ -2844,7 +2951,8 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
                    proportional_report=None, fragment_depth=False, fragment_report=None, mean_depth=None,
                    budget_bases=None, mean_depth_targets=None, mean_depth_report=None, thresholds=None,
                    thresholds_tag="XC", thresholds_report=None, start_cap=None, start_cap_by_strand=False,
-                   start_cap_report=None, primer_clip=False, per_amplicon=False, amplicon_report=None):
+                   start_cap_report=None, primer_clip=False, per_amplicon=False, amplicon_report=None, mapq_tiers=None,
+                   tiers_report=None):
     """BamApi(in) -> solve -> find_pairs -> write_paired_reads(out): App::execute's file-to-file flow.
     per_reference=True: one coverage problem per reference of the file (BamApiConfig::per_reference).
     bed / tsv (amplicon_mode: 0 IGNORE, 1 FILTER, 2 GRADE; None: the solver decides, as App::execute does -- GRADE for
@@ -3003,9 +3111,21 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
     selects what the plain flow selects.  They need bed, per_reference=True, amplicons_by_reference=True and
     "quasi-mcp-hip"; not together with any other mode -- a start cap, thresholds, a mean depth, a proportion,
     replicates, a budget, ceiling, pair_aware, template_aware, targets, report, track, ladder, stratify, dedup, profile
-    (ValueError).  False / None: nothing changes"""
+    (ValueError).  False / None: nothing changes
+    mapq_tiers / tiers_report (BamApiConfig::mapq_tiers): tiered downsampling by MAPQ band in one
+    qmcp_hip_solve_tiers_host call on the reads that passed the ingest filters -- strictly falling thresholds, e.g.
+    [30, 10, 0]: the reads of MAPQ >= 30 are solved first, those of 10 .. 29 only fill what they leave short of
+    min(coverage, max_coverage), those below 10 only what both leave short; then find_pairs and the write, as in the plain
+    flow (completion only adds reads, so the floor holds).  The last threshold must equal min_mapq, so that every read
+    the ingest lets through has a tier; at most TIERS_MAX thresholds.  tiers_report (a path) gets one line per tier --
+    band, reads, kept, mean depth before and after, demand, asked positions --, then records_written and mates_added
+    (the records completion added); without mapq_tiers it is a ValueError.  Needs per_reference=True and
+    "quasi-mcp-hip"; not together with any other mode -- amplicon-aware downsampling, a start cap, thresholds, a mean
+    depth, a proportion, replicates, a budget, ceiling, pair_aware, template_aware, targets, report, track, ladder,
+    stratify, dedup, profile --, nor with amplicon files (ValueError).  None: nothing changes"""
     _need_host()
-    given = {"a start cap": start_cap is not None, "coverage thresholds": thresholds is not None,
+    given = {"amplicon-aware downsampling": bool(primer_clip or per_amplicon or amplicon_report is not None),
+             "a start cap": start_cap is not None, "coverage thresholds": thresholds is not None,
              "a mean depth": mean_depth is not None or budget_bases is not None, "a proportion": proportion is not None, "replicates": replicates is not None,
              "a budget": budget_reads is not None or budget_fraction is not None, "ceiling": bool(ceiling),
              "pair_aware": bool(pair_aware), "template_aware": bool(template_aware), "targets": bool(targets),
@@ -3065,7 +3185,18 @@ def downsample_bam(solver_name, in_path, out_path, max_coverage, filtered_path=N
         raise ValueError("thresholds_report needs thresholds")
     if start_cap is None and (start_cap_by_strand or start_cap_report is not None):
         raise ValueError("start_cap_by_strand and start_cap_report need start_cap")
-    if primer_clip or per_amplicon or amplicon_report is not None:
+    if tiers_report is not None and mapq_tiers is None:
+        raise ValueError("tiers_report needs mapq_tiers")
+    if mapq_tiers is not None:
+        bands = [int(x) for x in mapq_tiers]
+        tiers_from_mapq([], bands)  # (ValueError: empty, negative, not strictly falling, more than TIERS_MAX)
+        if bands[-1] != int(min_mapq):
+            raise ValueError(f"the last threshold of mapq_tiers ({bands[-1]}) must equal min_mapq ({int(min_mapq)}): every "
+                             "read the ingest lets through needs a tier")
+        need_per_reference(_TIERS)
+        refuse(_TIERS)
+        fields.update(mapq_tiers=bands, tiers_report=tiers_report)
+    elif primer_clip or per_amplicon or amplicon_report is not None:
         if not (bed and per_reference and amplicons_by_reference):
             raise ValueError("primer_clip, per_amplicon and amplicon_report need bed, per_reference=True and "
                              "amplicons_by_reference=True")

@@ -229,6 +229,10 @@ struct qmcp_hip_ctx {
     // candidates' columns, input indices and keep mask, need[], and the counters (capped positions, demand, |S|)
     DevBuf pr_in, pr_rest, pr_words, pr_spine, pr_offs[2], pr_poff, pr_credit, pr_cspine, pr_starts, pr_ends, pr_orig,
         pr_mask, pr_need, pr_stat;
+    // tiered solves (api/tiers.inc.hip), all its own: the host entry's tier column, the per-tier rows, the counters
+    // (capped positions, demand, asked positions, reads without a tier), the kept list, the scanned word popcounts of a
+    // batch's mask and their spine, a batch's position offsets, the credit events and their scan with its spine, need[]
+    DevBuf tr_tiers, tr_rows, tr_stat, tr_list, tr_words, tr_spine, tr_poff, tr_credit, tr_cspine, tr_need;
     // template-aware solves (api/templates.inc.hip): the host entry's id column, the bitset of template ids a completion
     // goes through, the segments per template, and the counters (size histogram, templates in use, largest, kept, error)
     DevBuf tp_ids, tp_flags, tp_sizes, tp_stat;

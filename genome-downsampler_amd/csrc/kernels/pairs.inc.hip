@@ -56,16 +56,18 @@ __global__ __launch_bounds__(256) void k_pair_credit_events(const Rec* __restric
 }
 
 // k_profile_need's shape: four positions per thread, 16-byte loads of boff, eoff and credit, one 16-byte store; the
-// last positions of the axis go one by one.  pstat: [0] positions with cov_rest > cap, [1] the sum of need.
+// last positions of the axis go one by one.  pstat: [0] positions with cov_rest > cap, [1] the sum of need; ASKED (the
+// tiered entry): [2] the positions with need > 0 as well -- without it the kernel is what it was.
+template <bool ASKED>
 __global__ __launch_bounds__(256) void k_pair_need(const uint32_t* __restrict__ boff, const uint32_t* __restrict__ eoff,
                                                    const uint32_t* __restrict__ credit, uint32_t ltot, uint32_t target,
                                                    uint32_t* __restrict__ need, unsigned long long* __restrict__ pstat) {
-    __shared__ unsigned long long s_acc[2];
-    if (threadIdx.x < 2) s_acc[threadIdx.x] = 0;
+    __shared__ unsigned long long s_acc[3];
+    if (threadIdx.x < 3) s_acc[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t n_groups = (ltot + 3u) / 4u;
     const uint32_t stride = gridDim.x * blockDim.x;
-    uint32_t capped = 0;
+    uint32_t capped = 0, asked = 0;
     unsigned long long demand = 0;
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n_groups; g += stride) {
         const uint32_t p0 = 4u * g;
@@ -92,6 +94,7 @@ __global__ __launch_bounds__(256) void k_pair_need(const uint32_t* __restrict__ 
             out[r] = nd | (cov[r] <= cap ? kNeedCutBit : 0u);
             if (p0 + (uint32_t)r < ltot) {
                 capped += cov[r] > cap ? 1u : 0u;
+                if (ASKED) asked += nd != 0u ? 1u : 0u;
                 demand += nd;
             }
         }
@@ -104,16 +107,19 @@ __global__ __launch_bounds__(256) void k_pair_need(const uint32_t* __restrict__ 
         }
     }
     capped = wave_sum_u32(capped);
+    if (ASKED) asked = wave_sum_u32(asked);
     const uint32_t d_lo = wave_sum_u32((uint32_t)(demand & 0xFFFFu)), d_mid = wave_sum_u32((uint32_t)((demand >> 16) & 0xFFFFu));
     const uint32_t d_hi = wave_sum_u32((uint32_t)(demand >> 32));  // (a thread's sum stays far below 2^48: 64 lanes of 16 bits fit)
     if ((threadIdx.x & 63u) == 0) {
         atomicAdd(&s_acc[0], (unsigned long long)capped);
         atomicAdd(&s_acc[1], (unsigned long long)d_lo + ((unsigned long long)d_mid << 16) + ((unsigned long long)d_hi << 32));
+        if (ASKED) atomicAdd(&s_acc[2], (unsigned long long)asked);
     }
     __syncthreads();
     if (threadIdx.x == 0 && (s_acc[0] | s_acc[1]) != 0) {
         if (s_acc[0]) atomicAdd(&pstat[0], s_acc[0]);
         if (s_acc[1]) atomicAdd(&pstat[1], s_acc[1]);
+        if (ASKED && s_acc[2]) atomicAdd(&pstat[2], s_acc[2]);  // (need > 0 somewhere: the demand is not 0 either)
     }
 }
 
@@ -150,10 +156,13 @@ void launch_pair_credit_events(hipStream_t st, const void* sorted, uint32_t n, c
 }
 
 void launch_pair_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, const uint32_t* credit, uint32_t ltot,
-                      uint32_t target, uint32_t* need, unsigned long long* pstat) {
+                      uint32_t target, uint32_t* need, unsigned long long* pstat, bool count_asked) {
     if (ltot == 0) return;
-    hipLaunchKernelGGL(k_pair_need, dim3(grid_for(((uint64_t)ltot + 3) / 4, 256)), dim3(256), 0, st, boff, eoff, credit, ltot,
-                       target, need, pstat);
+    const dim3 grid(grid_for(((uint64_t)ltot + 3) / 4, 256)), block(256);
+    if (count_asked)
+        hipLaunchKernelGGL(k_pair_need<true>, grid, block, 0, st, boff, eoff, credit, ltot, target, need, pstat);
+    else
+        hipLaunchKernelGGL(k_pair_need<false>, grid, block, 0, st, boff, eoff, credit, ltot, target, need, pstat);
 }
 
 void launch_pair_count_bits(hipStream_t st, const uint64_t* mask, uint32_t n_words, unsigned long long* count) {

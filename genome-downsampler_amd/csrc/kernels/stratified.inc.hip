@@ -8,13 +8,17 @@
 // One pass over the four columns; a thread's loads are all issued before anything depends on them.  A read without a
 // contig or without a stratum gets the key n_strata * n_contigs, which sorts behind every (stratum, contig) and is never
 // solved; it is still validated.  err (one word, zeroed by the host): bits 0 and 1 as k_bc_keys sets them, bit 2 a
-// stratum id that is neither < n_strata nor QMCP_NO_STRATUM.
+// stratum id that is neither < n_strata nor QMCP_NO_STRATUM.  COUNT_NONE (the tiered entry, whose tier column is a
+// strata column): *none_count (zeroed by the host) += the reads whose id is QMCP_NO_STRATUM, reduced per wave -- one
+// atomic per wave that saw any; without it the kernel is what it was.
+template <bool COUNT_NONE>
 __global__ __launch_bounds__(256) void k_st_keys(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ ends,
                                                  const uint32_t* __restrict__ ids, const uint32_t* __restrict__ strata,
                                                  uint32_t n, const uint32_t* __restrict__ lengths, uint32_t n_contigs,
                                                  uint32_t n_strata, uint32_t* __restrict__ keys,
-                                                 uint32_t* __restrict__ err) {
-    uint32_t bad = 0;
+                                                 uint32_t* __restrict__ err,
+                                                 unsigned long long* __restrict__ none_count) {
+    uint32_t bad = 0, none = 0;
     const uint32_t unplaced = n_strata * n_contigs;  // <= 2^24 (checked by the host)
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t id = ids[i], sid = strata[i], s = starts[i], e = ends[i];
@@ -26,9 +30,14 @@ __global__ __launch_bounds__(256) void k_st_keys(const uint32_t* __restrict__ st
             bad |= 1u;
         }
         if (sid >= n_strata && sid != QMCP_NO_STRATUM) bad |= 4u;
+        if (COUNT_NONE && sid == QMCP_NO_STRATUM) ++none;
         keys[i] = key;
     }
     if (bad) atomicOr(err, bad);
+    if (COUNT_NONE) {
+        none = wave_sum_u32(none);  // (a thread sees at most 2^31 / 2^19 reads: the wave's sum fits)
+        if ((threadIdx.x & 63u) == 0 && none) atomicAdd(none_count, (unsigned long long)none);
+    }
 }
 
 // One step of a wave64 segmented inclusive scan over lanes whose segment ids `seg` do not decrease with the lane: a lane
@@ -156,10 +165,14 @@ __global__ __launch_bounds__(256) void k_st_tally(const Rec* __restrict__ sorted
 
 void launch_st_keys(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
                     const uint32_t* strata, uint32_t n, const uint32_t* lengths, uint32_t n_contigs, uint32_t n_strata,
-                    uint32_t* keys, uint32_t* err) {
+                    uint32_t* keys, uint32_t* err, unsigned long long* none_count) {
     if (n == 0) return;
-    hipLaunchKernelGGL(k_st_keys, dim3(grid_for(n, 256)), dim3(256), 0, st, starts, ends, ids, strata, n, lengths,
-                       n_contigs, n_strata, keys, err);
+    if (none_count)
+        hipLaunchKernelGGL(k_st_keys<true>, dim3(grid_for(n, 256)), dim3(256), 0, st, starts, ends, ids, strata, n, lengths,
+                           n_contigs, n_strata, keys, err, none_count);
+    else
+        hipLaunchKernelGGL(k_st_keys<false>, dim3(grid_for(n, 256)), dim3(256), 0, st, starts, ends, ids, strata, n, lengths,
+                           n_contigs, n_strata, keys, err, none_count);
 }
 void launch_st_tally(hipStream_t st, const void* sorted, uint32_t n_placed, uint32_t n_contigs, const uint32_t* starts,
                      const uint32_t* ends, const uint64_t* mask, uint64_t* rows) {

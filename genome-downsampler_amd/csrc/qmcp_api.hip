@@ -30,6 +30,7 @@
 #include "ladder_plan.h"
 #include "budget_plan.h"
 #include "stratified_plan.h"
+#include "tiers_plan.h"
 #include "dedup_plan.h"
 #include "amplicon_table.h"
 #include "amplicon_assign.h"
@@ -80,6 +81,9 @@
 //   pairs               (by_contig, profile) pair-aware downsampling: the batch loop at a first target, then stages over
 //                       all batches that credit the depth of the pairs already kept and top up among the other reads on
 //                       the capped route
+//   tiers               (by_contig, profile) tiered downsampling: reads grouped once by (tier, contig), tier 0 solved plainly
+//                       at M, every later tier on the capped route under need = min(its coverage, M - the depth of the
+//                       earlier tiers' kept reads), which a list of the kept reads carries from batch to batch
 //   templates           (pairs) the pair-aware stages with the unit generalised: every segment that carries one template
 //                       id (single-end reads, pairs, split reads, spliced blocks), completed through a bitset of ids
 //   templates_profile   (templates, profile) the template stages under a cap per region: stage 1 is the profile's batch
@@ -128,6 +132,7 @@
 #include "api/dedup.inc.hip"
 #include "api/profile.inc.hip"
 #include "api/pairs.inc.hip"
+#include "api/tiers.inc.hip"
 #include "api/templates.inc.hip"
 #include "api/templates_profile.inc.hip"
 #include "api/fragments.inc.hip"

@@ -311,7 +311,7 @@ void launch_ladder_levels(hipStream_t st, bool first, const uint64_t* mask, cons
 static constexpr uint32_t kStratumTallyTile = 1024;
 void launch_st_keys(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const uint32_t* ids,
                     const uint32_t* strata, uint32_t n, const uint32_t* lengths, uint32_t n_contigs, uint32_t n_strata,
-                    uint32_t* keys, uint32_t* err);
+                    uint32_t* keys, uint32_t* err, unsigned long long* none_count = nullptr);
 void launch_st_tally(hipStream_t st, const void* sorted, uint32_t n_placed, uint32_t n_contigs, const uint32_t* starts,
                      const uint32_t* ends, const uint64_t* mask, uint64_t* rows);
 
@@ -481,8 +481,23 @@ void launch_pair_credit_events(hipStream_t st, const void* sorted, uint32_t n, c
                                const uint32_t* starts, const uint32_t* ends, const uint32_t* pos_off, uint32_t first_contig,
                                uint32_t* ev);
 void launch_pair_need(hipStream_t st, const uint32_t* boff, const uint32_t* eoff, const uint32_t* credit, uint32_t ltot,
-                      uint32_t target, uint32_t* need, unsigned long long* pstat);
+                      uint32_t target, uint32_t* need, unsigned long long* pstat, bool count_asked = false);
 void launch_pair_count_bits(hipStream_t st, const uint64_t* mask, uint32_t n_words, unsigned long long* count);
+
+// tiered downsampling (kernels/tiers.inc.hip; api/tiers.inc.hip drives them).  Its keys are launch_st_keys with a
+// none_count (zeroed by the caller: += the reads whose stratum -- tier -- is QMCP_NO_STRATUM), its need is
+// launch_pair_need with count_asked (pstat[2] += the positions with need > 0).  launch_tier_keep_list appends the reads
+// that `mask` keeps of one solved batch (its gathered columns, its grouped Rec records, word_base: the mask's scanned
+// word popcounts; key_base = tier * n_contigs) to the kept list at `out`, 16-byte entries {contig, start, end, 0}, in
+// grouped order, at most `room` of them.  launch_tier_credit_events adds the events of the list's n_list entries that
+// lie on the contigs [first_contig, first_contig + n_contigs) to launch_pair_credit_events' axis (same layout, same
+// scan).
+constexpr size_t kTierKeptBytes = 16;
+void launch_tier_keep_list(hipStream_t st, const uint32_t* starts, const uint32_t* ends, const void* sorted,
+                           const uint64_t* mask, const uint32_t* word_base, uint32_t n, uint32_t key_base, void* out,
+                           uint32_t room);
+void launch_tier_credit_events(hipStream_t st, const void* list, uint32_t n_list, uint32_t first_contig, uint32_t n_contigs,
+                               const uint32_t* pos_off, uint32_t* ev);
 
 // template-aware downsampling (kernels/templates.inc.hip; api/templates.inc.hip drives them): ids holds one template id
 // per segment, n <= 2^31.  Once per call: err |= 1 for an id >= n_templates, sizes[id] (n_templates zeroed words) counts

@@ -57,6 +57,9 @@
 //                            flag, and the cut-point scan over it
 //   pairs                    pair-aware downsampling: the kept set's bits in a batch's grouped order and their complement,
 //                            the kept reads' depth as scanned events, need(p) = min(cov_rest(p), T - credit(p))
+//   tiers                    tiered downsampling: tier-major sort keys, the kept reads of a solved batch appended to a
+//                            list of {contig, start, end}, the list's depth on a later batch's axis as scanned events,
+//                            need(p) = min(cov_tier(p), M - credit(p)) with its three counters
 //   templates                template-aware downsampling: id check and template sizes, and the completion of a kept set
 //                            through a bitset of template ids (mark, spread)
 //   templates_profile        the template stages under a cap table: need(p) from the regions' scaled caps and the credit,
@@ -124,6 +127,7 @@ static constexpr uint32_t kInf = 0x40000000u;
 #include "kernels/amplicon_clip.inc.hip"
 #include "kernels/profile.inc.hip"
 #include "kernels/pairs.inc.hip"
+#include "kernels/tiers.inc.hip"
 #include "kernels/templates.inc.hip"
 #include "kernels/templates_profile.inc.hip"
 #include "kernels/fragments.inc.hip"

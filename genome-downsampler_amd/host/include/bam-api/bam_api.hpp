@@ -88,6 +88,14 @@ struct BamApiConfig {
     // other mode or with amplicon files (std::invalid_argument otherwise).  0: nothing changes.
     std::uint32_t start_cap = 0;
     bool start_cap_by_strand = false;
+    // Tiered downsampling by MAPQ band (QuasiMcpHipSolver::solve_tiers / qmcp_hip_solve_tiers_host): strictly falling
+    // thresholds, e.g. {30, 10, 0} -- a read of MAPQ >= mapq_tiers[0] is of tier 0, one below it and >= mapq_tiers[1] of
+    // tier 1, and so on.  The best tier is solved first, a lower tier only fills what the better ones leave short of
+    // min(coverage, max_coverage).  The last threshold must equal min_mapq, so that every read the ingest lets through has
+    // a tier; at most QMCP_TIERS_MAX thresholds.  find_pairs completes mates as always: it only adds reads, so the floor
+    // still holds.  Needs per_reference; not together with any other mode or with amplicon files (std::invalid_argument
+    // otherwise).  Empty: nothing changes.
+    std::vector<std::uint32_t> mapq_tiers;
     // Amplicon-aware downsampling (QuasiMcpHipSolver::solve_amplicons / qmcp_hip_solve_amplicons_host): primer_clip counts
     // depth on the reads clipped to their amplicon's insert (the amplicon without its primers, from the BED), per_amplicon
     // solves every amplicon as a coverage problem of its own ("every amplicon to M x"), amplicon_report_filepath gets one
@@ -222,6 +230,8 @@ class BamApi {
     bool dedup() const { return dedup_; }
     // BamApiConfig::start_cap (0: none) and start_cap_by_strand (the reads' strata column then holds the strand bit)
     std::uint32_t start_cap() const { return start_cap_; }
+    // BamApiConfig::mapq_tiers (empty: no tiered solve)
+    const std::vector<std::uint32_t>& mapq_tiers() const { return mapq_tiers_; }
     bool start_cap_by_strand() const { return start_cap_by_strand_; }
     // BamApiConfig::primer_clip, per_amplicon and amplicon_report_filepath; the amplicons matched to the references
     bool primer_clip() const { return primer_clip_; }
@@ -298,6 +308,7 @@ class BamApi {
     Stratify stratify_by_ = Stratify::NONE;
     bool dedup_ = false;
     std::uint32_t start_cap_ = 0;
+    std::vector<std::uint32_t> mapq_tiers_;
     bool start_cap_by_strand_ = false;
     bool primer_clip_ = false, per_amplicon_ = false;
     std::filesystem::path amplicon_report_filepath_;

@@ -142,6 +142,13 @@ class QuasiMcpHipSolver : public Solver {
     // std::invalid_argument for a BamApi without a proportion and for what the library refuses
     std::unique_ptr<Solution> solve_proportional(std::uint32_t required_cover, bam_api::BamApi& bam_api);
     const qmcp_hip_proportional_stats& last_proportional_stats() const { return ppstats_; }
+    // Tiered downsampling for the reads of a BamApi built with BamApiConfig::mapq_tiers: every read's tier from its MAPQ
+    // (the band it falls in; below the last threshold: QMCP_NO_TIER), then one qmcp_hip_solve_tiers_host call at
+    // required_cover.  The caller completes pairs with find_pairs.  last_tier_rows has one row per threshold.
+    // std::invalid_argument for a BamApi without mapq_tiers and for what the library refuses
+    std::unique_ptr<Solution> solve_tiers(std::uint32_t required_cover, bam_api::BamApi& bam_api);
+    const std::vector<qmcp_hip_tier_row>& last_tier_rows() const { return tier_rows_; }
+    const qmcp_hip_tiers_stats& last_tiers_stats() const { return trstats_; }
     // Budget downsampling for the reads of a BamApi built with BamApiConfig::budget_reads or budget_fraction: one
     // qmcp_hip_solve_budget_host call with QMCP_BUDGET_WHOLE_PAIRS, required_cover as the upper end of the search and
     // BamApi::budget_for(placed reads) as the budget.  The Solution holds whole pairs already -- the caller writes it
@@ -271,6 +278,8 @@ class QuasiMcpHipSolver : public Solver {
     qmcp_hip_pair_stats prstats_{};
     qmcp_hip_ceiling_stats clstats_{};
     qmcp_hip_proportional_stats ppstats_{};
+    std::vector<qmcp_hip_tier_row> tier_rows_;
+    qmcp_hip_tiers_stats trstats_{};
     qmcp_hip_budget_stats bgstats_{};
     std::vector<std::uint64_t> budget_curve_;
     qmcp_hip_thresholds_stats thstats_{};

@@ -126,6 +126,14 @@ typedef struct qmcp_host_downsample_request {
     int32_t primer_clip;
     int32_t per_amplicon;
     const char* amplicon_report;
+    /* tiered downsampling by MAPQ band (mapq_tiers): n_mapq_tiers strictly falling thresholds ask for it -- the best
+     * band is solved first, a lower band only fills what the better ones leave short of min(coverage, max_coverage);
+     * the last threshold must equal min_mapq.  tiers_report: one line per tier (band, reads, kept, mean depth before
+     * and after, demand, asked positions), then records_written and mates_added; alone it is refused.  It needs
+     * per_reference and goes with no other mode.  (These three stand in front of the proportion fields too.) */
+    const uint32_t* mapq_tiers;
+    uint32_t n_mapq_tiers;
+    const char* tiers_report;
     /* proportional downsampling (proportion): has_proportion != 0 asks for it -- every position keeps
      * ceil(cov * proportion_num / proportion_den) of its depth, positions at or below proportion_floor whole,
      * max_coverage the hard upper end; proportional_report: stat<TAB>value lines */

@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "bam-api/bam_io.hpp"
+#include "qmcp_hip.h"  // QMCP_TIERS_MAX
 
 namespace bam_api {
 
@@ -70,6 +71,41 @@ BamApi::BamApi(const std::filesystem::path& input_filepath, const BamApiConfig& 
     if (amplicons_by_reference_ && !per_reference_)
         throw std::invalid_argument("amplicons_by_reference needs per_reference: amplicons are matched to the "
                                     "references a per-reference ingest keeps");
+    if (!config.mapq_tiers.empty()) {
+        const auto no = [](const char* what) {
+            throw std::invalid_argument(std::string("tiered downsampling does not go together with ") + what);
+        };
+        if (!per_reference_)
+            throw std::invalid_argument("tiered downsampling needs per_reference: a tier is solved one reference at a time");
+        if (config.mapq_tiers.size() > QMCP_TIERS_MAX)
+            throw std::invalid_argument("mapq_tiers: at most " + std::to_string(QMCP_TIERS_MAX) + " thresholds");
+        for (std::size_t k = 1; k < config.mapq_tiers.size(); ++k)
+            if (config.mapq_tiers[k] >= config.mapq_tiers[k - 1])
+                throw std::invalid_argument("mapq_tiers must fall strictly");
+        if (config.mapq_tiers.back() != config.min_mapq)
+            throw std::invalid_argument("the last threshold of mapq_tiers must equal min_mapq: every read the ingest lets "
+                                        "through needs a tier");
+        if (config.primer_clip || config.per_amplicon || !config.amplicon_report_filepath.empty())
+            no("amplicon-aware downsampling");
+        if (config.start_cap) no("a start cap");
+        if (config.thresholds_hi.has_value()) no("coverage thresholds");
+        if (config.mean_depth.has_value() || config.budget_bases.has_value()) no("a mean depth");
+        if (config.proportion.has_value()) no("a proportion");
+        if (config.replicates.has_value()) no("replicates");
+        if (config.budget_reads.has_value() || config.budget_fraction.has_value()) no("a budget");
+        if (config.ceiling) no("ceiling");
+        if (config.pair_aware) no("pair_aware");
+        if (config.template_aware) no("template_aware");
+        if (!config.targets_filepath.empty()) no("targets");
+        if (!config.depth_report_filepath.empty()) no("a depth report");
+        if (!config.depth_track_filepath.empty()) no("a depth track");
+        if (!config.coverage_ladder.empty()) no("a coverage ladder");
+        if (config.stratify_by != Stratify::NONE) no("stratify_by");
+        if (config.dedup) no("dedup");
+        if (config.amplicons_by_reference || !config.bed_filepath.empty() || !config.tsv_filepath.empty())
+            throw std::invalid_argument("tiered downsampling does not take amplicon files");
+        mapq_tiers_ = config.mapq_tiers;
+    }
     if (config.start_cap) {
         const auto no = [](const char* what) {
             throw std::invalid_argument(std::string("a start cap does not go together with ") + what);

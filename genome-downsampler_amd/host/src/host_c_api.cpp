@@ -168,6 +168,7 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
     cfg.primer_clip = q.primer_clip != 0;
     cfg.per_amplicon = q.per_amplicon != 0;
     if (given(q.amplicon_report)) cfg.amplicon_report_filepath = q.amplicon_report;
+    if (q.mapq_tiers) cfg.mapq_tiers.assign(q.mapq_tiers, q.mapq_tiers + q.n_mapq_tiers);
     cfg.pair_aware = q.pair_aware != 0;
     if (q.pair_stages) cfg.pair_stages.assign(q.pair_stages, q.pair_stages + q.n_pair_stages);
     cfg.template_aware = q.template_aware != 0;
@@ -197,8 +198,9 @@ bam_api::BamApiConfig config_of(const qmcp_host_downsample_request& q, qmcp::Sol
 
 // Which solve a request asks for: the first of these that it switches on.  PLAIN is Solver::solve -- with targets,
 // amplicons, a depth report or a depth track, which any solver takes; every other mode is a method of the hip solver.
-enum class Mode { AMPLICONS, START_CAP, THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
+enum class Mode { TIERS, AMPLICONS, START_CAP, THRESHOLDS, MEAN_DEPTH, PROPORTIONAL, REPLICATES, BUDGET, CEILING, TEMPLATES, PAIRS, PROFILE, DEDUP, STRATIFIED, LADDER, PLAIN };
 Mode mode_of(const qmcp_host_downsample_request& q, const bam_api::BamApiConfig& cfg) {
+    if (!cfg.mapq_tiers.empty() || given(q.tiers_report)) return Mode::TIERS;
     if (cfg.primer_clip || cfg.per_amplicon || !cfg.amplicon_report_filepath.empty()) return Mode::AMPLICONS;
     if (cfg.start_cap || cfg.start_cap_by_strand || given(q.start_cap_report)) return Mode::START_CAP;
     if (cfg.thresholds_hi || given(q.thresholds_tag) || given(q.thresholds_report)) return Mode::THRESHOLDS;
@@ -223,6 +225,7 @@ struct ModeWords {
 };
 ModeWords words_of(Mode mode) {
     switch (mode) {
+        case Mode::TIERS: return {"tiered downsampling does not", "tiered downsampling"};
         case Mode::AMPLICONS: return {"amplicon-aware downsampling does not", "amplicon-aware downsampling"};
         case Mode::START_CAP: return {"a start cap does not", "start cap"};
         case Mode::THRESHOLDS: return {"coverage thresholds do not", "coverage thresholds"};
@@ -255,6 +258,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
         refuse("budget downsampling needs budget_reads or budget_fraction");
     if (mode == Mode::MEAN_DEPTH && !cfg.mean_depth && !cfg.budget_bases)
         refuse("mean-depth downsampling needs mean_depth or budget_bases");
+    if (mode == Mode::TIERS && cfg.mapq_tiers.empty()) refuse("tiers_report needs mapq_tiers");
     if (mode == Mode::START_CAP && !cfg.start_cap) refuse("start_cap_by_strand and start_cap_report need start_cap");
     if (mode == Mode::START_CAP && q.has_regions) refuse("a start cap does not go together with a coverage profile");
     if (mode == Mode::THRESHOLDS && !cfg.thresholds_hi) refuse("thresholds_tag and thresholds_report need thresholds");
@@ -278,7 +282,7 @@ void refuse_before_ingest(const qmcp_host_downsample_request& q, const bam_api::
     if (given(q.fragment_report) && !cfg.fragment_depth) refuse("a fragment report needs fragment_depth");
     if (q.has_regions &&
         (mode == Mode::PAIRS || mode == Mode::BUDGET || mode == Mode::REPLICATES || mode == Mode::PROPORTIONAL ||
-         mode == Mode::MEAN_DEPTH || mode == Mode::THRESHOLDS || mode == Mode::AMPLICONS))
+         mode == Mode::MEAN_DEPTH || mode == Mode::THRESHOLDS || mode == Mode::AMPLICONS || mode == Mode::TIERS))
         refuse(words.refuses + " go together with a coverage profile");
     if (mode != Mode::PLAIN && solver.uses_quality_of_reads()) refuse(words.refuses + " take a solver that grades by quality");
     if (mode != Mode::PLAIN && hip == nullptr) refuse("this solver has no " + words.noun);
@@ -311,6 +315,26 @@ bool write_strata_report(const char* path, const bam_api::SOAPairedReads& r, con
                      positions > 0 ? (double)row.bases_in / positions : 0.0,
                      positions > 0 ? (double)row.bases_kept / positions : 0.0);
     }
+    return std::fclose(f) == 0;
+}
+
+// one line per tier: its MAPQ band, reads, kept, mean depth before and after (bases / the sum of the reference lengths) of
+// the solve's own kept set, demand and asked positions; then the records written and how many of them find_pairs added
+bool write_tiers_report(const char* path, const bam_api::SOAPairedReads& r, const std::vector<std::uint32_t>& bands,
+                        const qmcp::QuasiMcpHipSolver& hip, std::int64_t written, std::uint64_t mates_added) {
+    double positions = 0;
+    for (std::uint32_t l : r.contig_lengths) positions += l;
+    if (positions <= 0) positions = 1;
+    std::FILE* f = std::fopen(path, "w");
+    if (f == nullptr) return false;
+    std::fprintf(f, "#tier\tband\treads\tkept\tmean_depth_in\tmean_depth_kept\tdemand\tasked_positions\n");
+    for (std::size_t t = 0; t < bands.size(); ++t) {
+        const qmcp_hip_tier_row& row = hip.last_tier_rows()[t];
+        std::fprintf(f, "%zu\tmapq>=%u\t%llu\t%llu\t%.6f\t%.6f\t%llu\t%llu\n", t, bands[t], (unsigned long long)row.n_reads,
+                     (unsigned long long)row.n_kept, (double)row.bases_in / positions, (double)row.bases_kept / positions,
+                     (unsigned long long)row.demand, (unsigned long long)row.asked_positions);
+    }
+    std::fprintf(f, "records_written\t%lld\nmates_added\t%llu\n", (long long)written, (unsigned long long)mates_added);
     return std::fclose(f) == 0;
 }
 
@@ -560,7 +584,14 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
         std::string path = path_template;
         return path.replace(path.find(token), 3, std::to_string(value));
     };
+    std::uint64_t mates_added = 0;  // tiered downsampling: the reads find_pairs put next to the solve's own
     switch (mode) {
+        case Mode::TIERS: {
+            const std::unique_ptr<qmcp::Solution> solution = hip->solve_tiers(M, api);
+            write_reads(*solution, true, q.out_path);
+            mates_added = kept.size() - solution->size();
+            break;
+        }
         case Mode::PLAIN:
         case Mode::STRATIFIED: write_reads(*solver->solve(M, api), true, q.out_path); break;
         case Mode::DEDUP: write_reads(*hip->solve_dedup(M, api, kDedupBins), true, q.out_path); break;
@@ -617,6 +648,8 @@ std::int64_t downsample(const qmcp_host_downsample_request& q, std::int64_t* wri
     bool reported = true;
     if (mode == Mode::STRATIFIED && given(q.strata_report))
         reported = write_strata_report(q.strata_report, api.get_paired_reads_soa(), *hip);
+    if (mode == Mode::TIERS && given(q.tiers_report))
+        reported = write_tiers_report(q.tiers_report, api.get_paired_reads_soa(), api.mapq_tiers(), *hip, written[0], mates_added);
     if (mode == Mode::DEDUP && given(q.dedup_report)) reported = write_dedup_report(q.dedup_report, *hip);
     if (mode == Mode::START_CAP && given(q.start_cap_report))
         reported = write_start_cap_report(q.start_cap_report, *hip, written[0]);

@@ -351,6 +351,35 @@ std::unique_ptr<Solution> QuasiMcpHipSolver::solve_proportional(std::uint32_t re
     return finish(mask, n, t0);
 }
 
+std::unique_ptr<Solution> QuasiMcpHipSolver::solve_tiers(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
+    const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::size_t n = reads.start_inds.size();
+    const std::vector<std::uint32_t>& bands = bam_api.mapq_tiers();
+    need_per_reference(!bands.empty(), reads, "tiered downsampling needs a BamApi built with BamApiConfig::mapq_tiers");
+    context();
+    const Columns c = narrowed(reads);
+    std::vector<std::uint32_t> tiers(std::max<std::size_t>(n, 1), QMCP_NO_TIER);  // (never NULL, also without reads)
+    for (std::size_t i = 0; i < n; ++i)
+        for (std::size_t t = 0; t < bands.size(); ++t)
+            if (reads.qualities[i] >= bands[t]) {
+                tiers[i] = (std::uint32_t)t;
+                break;
+            }
+    tier_rows_.assign(bands.size(), qmcp_hip_tier_row{});
+    std::vector<std::uint64_t> mask = empty_mask(n);
+    ok_or_throw("qmcp_hip_solve_tiers_host",
+                qmcp_hip_solve_tiers_host(ctx_, c.starts.data(), c.ends.data(), reads.contig_ids.data(), tiers.data(), n,
+                                          reads.contig_lengths.data(), n_contigs(reads), required_cover,
+                                          (std::uint32_t)bands.size(), mask.data(), tier_rows_.data(), &stats_, &trstats_));
+    // (stats_ are tier 0's solver calls: the mask holds the kept reads of every tier)
+    std::uint64_t kept = 0;
+    for (const qmcp_hip_tier_row& row : tier_rows_) kept += row.n_kept;
+    breakdown_ = qmcp_hip_host_breakdown{};
+    if (complete_pairs_) ok_or_die("qmcp_hip_complete_pairs_host", qmcp_hip_complete_pairs_host(ctx_, mask.data(), n));
+    return expand(n, complete_pairs_ ? std::min<std::uint64_t>(n, 2 * kept) : kept, t0);
+}
+
 std::unique_ptr<Solution> QuasiMcpHipSolver::solve_pairs(std::uint32_t required_cover, bam_api::BamApi& bam_api) {
     const bam_api::SOAPairedReads& reads = bam_api.get_paired_reads_soa();
     const auto t0 = std::chrono::steady_clock::now();

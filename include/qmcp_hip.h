@@ -846,6 +846,93 @@ int qmcp_hip_solve_stratified_device(qmcp_hip_ctx* ctx,
                                      uint64_t* d_keep_mask_out, qmcp_hip_stratum_row* rows_out, void* hip_stream,
                                      qmcp_hip_stats* stats);
 
+/* Tiered downsampling: the best reads first, worse reads only where the better ones cannot bring the depth to
+ * min(coverage, M).  The tier is any small integer per read (a MAPQ band, primary before supplementary, non-duplicates
+ * before duplicates, run A before run B, properly paired before orphans), 0 the best.  Reads, contig_ids, contig_lengths
+ * / n_contigs, the per-read rules and the limits are those of qmcp_hip_solve_by_contig_host.  tiers[i] < n_tiers names
+ * read i's tier, QMCP_NO_TIER marks a read that is never kept; it is still validated against its contig, like a
+ * QMCP_NO_STRATUM read.  1 <= n_tiers <= QMCP_TIERS_MAX, n_tiers * n_contigs <= 2^24.
+ * Definition: S_(-1) is empty.  For t = 0 .. n_tiers - 1:
+ *   R_t        the placed reads of tier t, alone, in input order
+ *   credit_t   credit_t(p) = the depth of S_(t-1) at p
+ *   need_t     need_t(p) = min(cov_(R_t)(p), max(0, M - credit_t(p)))
+ *   K_t        the canonical selection of qmcp_hip_solve_profile_host over R_t under need_t -- per contig: the leftmost
+ *              deficit first, then the furthest end, the furthest start, the lowest index
+ *   S_t        S_(t-1) | K_t
+ * The result is S_(n_tiers - 1), a mask in input order.  No tier is kept whole: every tier, the first included, is
+ * downsampled.  There is no pair completion inside the entry.
+ * Guarantees:
+ *   1. the kept depth is >= min(cov_all(p), M) at every position p.  (By induction depth(S_t) >= min(cov_(tiers <= t),
+ *      M): where credit < M, credit + min(cov_t, M - credit) = min(credit + cov_t, M).)
+ *   2. tier 0 restricted to itself is qmcp_hip_solve_by_contig_* of R_0 at M bit for bit, taken on that call's own
+ *      routes (every fast route stays in use): n_tiers == 1 with every placed read in tier 0 gives the by-contig mask
+ *      and stats.n_kept bit for bit.
+ *   3. a read of tier t is kept only through need_t: where S_(t-1) already reaches M on the whole support of tier t,
+ *      the tier keeps nothing and no sweep is queued for it.
+ *   4. the first tier that has reads on a contig is solved there with zero credit: its selection on that contig equals
+ *      the by-contig solve of those reads.
+ * Not claimed: minimum cardinality of the whole result, or the optimum of the reference's min-cost objective.
+ * How: the reads are grouped once, on the device, by the key tier * n_contigs + contig; every tier with reads is cut
+ * into solver calls of its own (never across a tier; one (tier, contig) must fit one call: 2^30 reads, 2^31 - 2
+ * positions, QMCP_ERANGE naming the pair otherwise).  Tier 0's calls are the plain solve at M.  After a call of any
+ * tier its kept reads are compacted into a kept list of (contig, start, end) entries, while a later tier has reads; a
+ * call of tier t >= 1 turns the list's entries on its contigs into credit (events on a zeroed axis, scanned), builds
+ * need_t on the device and takes the sort-based mixed-span route of the profile entries under it, exact cut points
+ * only (options.cut_points is honoured, nothing is speculated).  Known cost: a later tier with real demand on deep data
+ * is one serial chain per contig, as for the ceiling and proportional entries.
+ * rows_out (host memory in both entries, n_tiers rows, may be NULL; written on success only), one row per tier:
+ * the stratified row's four counts; demand (the sum of need_t), asked_positions (need_t > 0) and capped_positions
+ * (cov_(R_t) > max(0, M - credit_t)), all three 0 for tier 0, whose plain solves build no need; sweeps (tier 0: its
+ * solver calls; later tiers: the calls that queued a sweep -- a call whose demand is 0 queues none); ms_stage (the
+ * device time of the tier's solver calls).  max_coverage == 0 keeps nothing: no solver call is made, and every field
+ * behind the four counts is 0.
+ * tstats (may be NULL): n_tiers, tiers_used (tiers that kept a read), reads_untiered (reads with QMCP_NO_TIER, placed
+ * or not), ms_tiers (the call's device time outside the solver calls: grouping, gathers, kept lists, credit, rows).
+ * stats (may be NULL) are tier 0's solver calls, as stats are stage 1's in the pair entry: summed, the route of the
+ * largest; n_contigs and total_length are the call's.
+ * Errors: NULL buffers, tiers == NULL (also without reads) and n_tiers == 0 fail with QMCP_EINVAL, n_tiers >
+ * QMCP_TIERS_MAX, n_tiers * n_contigs > 2^24 and max_coverage >= 2^31 with QMCP_ERANGE, all on the host before anything is copied or launched.
+ * A tier id that is neither < n_tiers nor QMCP_NO_TIER (QMCP_EINVAL), a bad contig id (QMCP_EINVAL) and a bad read
+ * (QMCP_EREAD) are found on the device; by then the device mask (d_keep_mask_out, or the context's own for the host
+ * entry) has been cleared -- ceil(n_reads / 64) words and nothing beyond them -- and the host entry does not write
+ * keep_mask_out.  The device entry takes the four columns and the mask in device memory (contig_lengths and rows_out
+ * stay on the host), is ordered after `hip_stream` (or NULL) as qmcp_hip_solve_device is, and returns after the work
+ * has completed.  The host entry leaves the mask in the context, for qmcp_hip_kept_indices_host. */
+#define QMCP_NO_TIER 0xFFFFFFFFu
+#define QMCP_TIERS_MAX 16
+typedef struct qmcp_hip_tier_row {   /* 64 bytes */
+    uint64_t n_reads;           /* placed reads of the tier                                                            */
+    uint64_t n_kept;            /* ... of which the mask keeps                                                         */
+    uint64_t bases_in;          /* sum of (end - start + 1) over n_reads                                               */
+    uint64_t bases_kept;        /* ... over the kept ones                                                              */
+    uint64_t demand;            /* sum of need_t over the positions (0 for tier 0)                                     */
+    uint64_t asked_positions;   /* positions with need_t > 0 (0 for tier 0)                                            */
+    uint64_t capped_positions;  /* positions where the tier's coverage exceeds max(0, M - credit_t) (0 for tier 0)    */
+    uint32_t sweeps;            /* tier 0: solver calls; later tiers: solver calls that queued a sweep                 */
+    float ms_stage;             /* device time of the tier's solver calls                                              */
+} qmcp_hip_tier_row;
+typedef struct qmcp_hip_tiers_stats {   /* 24 bytes */
+    uint32_t n_tiers;
+    uint32_t tiers_used;       /* tiers that kept at least one read                                                    */
+    uint64_t reads_untiered;   /* reads whose tier is QMCP_NO_TIER                                                     */
+    float ms_tiers;            /* the call's device time outside the solver calls                                      */
+    uint32_t reserved;         /* 0                                                                                    */
+} qmcp_hip_tiers_stats;
+int qmcp_hip_solve_tiers_host(qmcp_hip_ctx* ctx,
+                              const uint32_t* starts, const uint32_t* ends, const uint32_t* contig_ids,
+                              const uint32_t* tiers, uint64_t n_reads,
+                              const uint32_t* contig_lengths, uint32_t n_contigs,
+                              uint32_t max_coverage, uint32_t n_tiers,
+                              uint64_t* keep_mask_out, qmcp_hip_tier_row* rows_out, qmcp_hip_stats* stats,
+                              qmcp_hip_tiers_stats* tstats);
+int qmcp_hip_solve_tiers_device(qmcp_hip_ctx* ctx,
+                                const uint32_t* d_starts, const uint32_t* d_ends, const uint32_t* d_contig_ids,
+                                const uint32_t* d_tiers, uint64_t n_reads,
+                                const uint32_t* contig_lengths, uint32_t n_contigs,
+                                uint32_t max_coverage, uint32_t n_tiers,
+                                uint64_t* d_keep_mask_out, qmcp_hip_tier_row* rows_out, void* hip_stream,
+                                qmcp_hip_stats* stats, qmcp_hip_tiers_stats* tstats);
+
 /* Duplicate-aware downsampling: duplicate families are collapsed to one representative each BEFORE the solve, so that a
  * PCR or optical duplicate does not count towards min(coverage, M) like an independent read.  starts, ends, contig_ids,
  * n_reads, contig_lengths / n_contigs, max_coverage, keep_mask_out, stats, limits and errors are those of
